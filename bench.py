@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- glyphs/sec of one full training step (forward + MSE + backward + AdamW) of the hot path.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c1|r0|c5] [--dtype bf16|f32]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c1|r0|c5] [--dtype bf16|f32] [--full]
+         [--dump-outputs DIR]
          (run directly with N > 1 it starts its own N rank processes before touching a GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W          (one rank per GPU, RCCL)
@@ -20,6 +21,14 @@ host time; reported as "preheat_ms"): the part needs ~20 ms of sustained work to
 Inputs are synthetic and resident in HBM before the timed region: the 95 printable ASCII codes (x font ids) repeated over
 the batch, with the FreeType rasterisations of FiraCode-Retina / Montserrat-Regular as uint8 targets (tests/golden/
 glyph_bitmaps.npz); R0: strings from the seeded text generator, hashed sheets.  A step = the loop body of reference model.py:292-310.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, pre-heats, warms up, times the K steps and prints the line (glyphs/s and ms_per_step).  --full adds
+what takes runs or work of its own: the from-cold run (cold_ms_per_step), the roofline of the dominant kernel and the
+per-kernel table of profiled warm-up steps (--table prints it), the f32 parity mode, the R0 record beside C3, the CPU
+baseline and the bitmap differences against the oracle (--no-extras / --no-cpu-baseline drop parts of it).
+--dump-outputs DIR writes what the last timed step handed its caller: loss.npy (that step's loss, float32 [1]) and
+param.<state_dict name>.npy (the updated f32 master weights; models above DUMP_MAX_VALUES parameters write a fixed, seeded
+sample of every tensor).  Inputs and initial weights are generated from fixed seeds: the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -190,8 +199,27 @@ def spawn_ranks(n, argv):
     return subprocess.run(cmd, env=env).returncode
 
 
-def measure(name, dtype, B, K, W, rank, world, dist, with_roofline=True, want_sample=False):
-    """W warm-up steps, then exactly K timed steps between fences.  Returns (engine, elapsed_s, dominant, table, loss)."""
+DUMP_MAX_VALUES = 8 << 20      # --dump-outputs: parameters written in full up to this many (32 MB of float32), else sampled
+
+
+def dump_outputs(out_dir, eng, last_loss):
+    """The last timed step's outputs as out_dir/<name>.npy: its loss and the updated f32 master weights (state_dict order and
+    names).  Above DUMP_MAX_VALUES parameters every tensor contributes the same share of its elements, at indices drawn from
+    a generator seeded with the tensor's position in the layout: the same sample on every run and every build."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), last_loss.detach().float().cpu().numpy().reshape(1))
+    frac = min(1.0, DUMP_MAX_VALUES / max(eng.n_flat, 1))
+    for i, (nm, _, _, k) in enumerate(eng.layout):
+        p = eng.params[nm].detach()
+        if frac < 1.0:
+            idx = np.sort(np.random.default_rng(i).integers(0, k, max(1, int(k * frac))))
+            p = p.reshape(-1)[torch.from_numpy(idx).to(p.device)]
+        np.save(os.path.join(out_dir, f"param.{nm}.npy"), p.float().cpu().numpy())
+
+
+def measure(name, dtype, B, K, W, rank, world, dist, with_roofline=True, want_sample=False, dump_dir=None):
+    """W warm-up steps, then exactly K timed steps between fences.  Returns (engine, elapsed_s, dominant, table, loss).
+    dump_dir: write the last timed step's outputs there (rank 0; dump_outputs)."""
     from ai_font_renderer_amd.engine import Engine
     from ai_font_renderer_amd.parallel import DataParallelStepper
     cfg = WORKLOADS[name]["cfg"]
@@ -243,7 +271,12 @@ def measure(name, dtype, B, K, W, rank, world, dist, with_roofline=True, want_sa
         run(max(W, 1))
     fence()
     t0 = time.perf_counter()
-    run(K)
+    if dump_dir is None:
+        run(K)
+    else:
+        run(K - 1)
+        before = eng.loss_accum.clone()           # one 4-byte copy on the stream: the loss accumulator before the last step
+        run(1)
     fence()
     elapsed = time.perf_counter() - t0
     if with_roofline:
@@ -253,6 +286,12 @@ def measure(name, dtype, B, K, W, rank, world, dist, with_roofline=True, want_sa
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if dump_dir is not None:
+        last = eng.loss_accum - before            # this rank's share of the last step's loss (each share is / mean_elems)
+        if dist is not None:
+            dist.all_reduce(last)
+        if rank == 0:
+            dump_outputs(dump_dir, eng, last)
     loss = eng.read_loss() / max(K + W, 1)
     if eng.error_flags():
         raise SystemExit("device error flag set (embedding index out of range / cooperative split-K timeout)")
@@ -270,6 +309,58 @@ def measure(name, dtype, B, K, W, rank, world, dist, with_roofline=True, want_sa
     return eng, elapsed, dom, table, loss
 
 
+def roofline(name, cfg, dtype, B, ms_step, dom, table, batch_override):
+    """--full: the dominant kernel of the timed steps against its roof, the whole step against the MFMA peak and the
+    products of the widest Linear (per-shape rows of the profiled warm-up table)."""
+    # The dominant kernel against the roof SURVEY.md 8(d) names for it: the MFMA peak of its operand type for the dense
+    # products (C3, R0 in f32), HBM for the streaming kernels and for R0's bf16 weight-gradient GEMM with the fused
+    # optimizer (26 B of p/m/v traffic per output element; 8(d): "bf16 mode: HBM until B >~ 2700/GPU").
+    secs = dom["avg_ms"] * 1e-3
+    kern = dom["kernel"]
+    f32_kernel = kern.startswith(("sheet_", "gemm_f32")) or "<f32>" in kern
+    peak_fl = PEAK["f32"] if f32_kernel else PEAK[dtype]           # f32 VALU peak == f32 MFMA peak (157.3 TF)
+    fl = dom["algo_flops"] / secs / 1e12
+    by = dom["algo_bytes"] / secs / 1e9
+    # which roof binds the dominant kernel: the one it is closer to (R0's bf16 weight-gradient GEMM with the fused optimizer
+    # moves 26 B of p/m/v per output element and sits at 0.55 of HBM against 0.14 of MFMA; C3's products the other way)
+    hbm_bound = dom["algo_flops"] <= 0 or by / HBM_PEAK_GBS > fl / peak_fl
+    if hbm_bound:
+        roof = {"bound": "hbm", "kernel": kern, "achieved": by, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": by / HBM_PEAK_GBS}
+    else:
+        # every dense product of the path runs on the matrix cores (the f32 forms at the f32 VALU's rate, 157.3 TF)
+        roof = {"bound": "mfma", "kernel": kern, "achieved": fl, "peak": peak_fl, "unit": "TFLOP/s", "frac": fl / peak_fl}
+    tr, src = pmc_traffic(name, kern) if (dtype == DEFAULT_DTYPE[name] and not batch_override) else (None, None)
+    roof.update({"traffic": tr, "traffic_unit": f"bytes/launch (PMC FETCH_SIZE x2 + WRITE_SIZE, {src})" if tr is not None else src,
+                 "avg_launch_ms": dom["avg_ms"], "launches": dom["launches"], "algo_flops_per_launch": dom["algo_flops"],
+                 "algo_bytes_per_launch": dom["algo_bytes"], "mfma_frac": fl / peak_fl if dom["algo_flops"] > 0 else None,
+                 "hbm_frac": by / HBM_PEAK_GBS})
+    # whole step against the MFMA peak, and the three products of the widest Linear (per-shape rows of the warm-up table)
+    sf = step_flops(cfg, B)
+    roof["step"] = {"algo_flops": sf, "achieved_tflops": sf / (ms_step * 1e-3) / 1e12, "peak": PEAK[dtype],
+                    "frac": sf / (ms_step * 1e-3) / 1e12 / PEAK[dtype]}
+    wn, wk = widest_linear(cfg)
+    Bm = B * cfg.tokens if isinstance(cfg, PixelConfig) else B          # rows of a Linear's products (every pixel token is a row)
+    # (operand orientation, MxNxK) of the three products: forward x.W^T, input gradient dy.W, weight gradient dy^T.x
+    shapes = {"fwd": ("<0,0", f"[{Bm}x{wn}x{wk}]"), "dX": ("<0,1", f"[{Bm}x{wk}x{wn}]"), "dW": ("<1,1", f"[{wn}x{wk}x{Bm}]")}
+    wl = {}
+    for r in table:
+        for role, (ori, sh) in shapes.items():
+            plain = r["kernel"].startswith("gemm") and ori in r["kernel"] and r["kernel"].endswith(sh)
+            body = r["kernel"].startswith("gemm_bf16_group256" + sh + ori)          # a plain product on the 256x256 body: name[shape]<a,b>
+            if (plain or body) and role not in wl and r["avg_ms"] > 0:
+                tf = r["algo_flops"] / (r["avg_ms"] * 1e-3) / 1e12
+                wl[role] = {"kernel": r["kernel"], "avg_us": r["avg_ms"] * 1e3, "tflops": tf, "frac": tf / (PEAK["f32"] if "f32" in r["kernel"] else PEAK[dtype])}
+    # a layer's weight and input gradients leave as ONE grouped launch when both qualify (afr_gemm_pair_plan)
+    for r in table:
+        if r["kernel"].startswith("gemm_bf16_group") and shapes["dX"][1][1:-1] in r["kernel"] and shapes["dW"][1][1:-1] in r["kernel"] \
+                and "dW+dX" not in wl and r["avg_ms"] > 0:
+            tf = r["algo_flops"] / (r["avg_ms"] * 1e-3) / 1e12
+            wl["dW+dX"] = {"kernel": r["kernel"], "avg_us": r["avg_ms"] * 1e3, "tflops": tf, "frac": tf / PEAK[dtype],
+                           "note": "weight gradient (split-K slabs) and input gradient of the layer in one grouped launch"}
+    roof["widest_linear"] = {"layer": f"{wk}->{wn}", "source": "hipEvent brackets, warm-up steps (every launch timed)", **wl}
+    return roof
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -282,7 +373,15 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the parity-mode (f32) and R0 side records")
     ap.add_argument("--table", action="store_true", help="also print the per-kernel time table to stderr")
     ap.add_argument("--preheat-ms", type=float, default=30.0, help="inference forwards issued for this long before the warm-up steps (0: none)")
+    ap.add_argument("--full", action="store_true", help="also the side measurements: from-cold run, roofline and per-kernel table, "
+                    "f32 parity mode, R0 record, CPU baseline, bitmap differences against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's loss and updated weights as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.table and not args.full:
+        ap.error("--table prints the per-kernel table of the profiled warm-up steps, which only --full runs")
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))                # nothing above this line touches a GPU
@@ -313,66 +412,21 @@ def main():
 
     # from cold first (no pre-heat forwards; the process has done next to no GPU work so far), then the steady-state run
     cold_ms = None
-    if args.preheat_ms > 0 and not args.no_extras:
+    if args.full and args.preheat_ms > 0 and not args.no_extras:
         PREHEAT_MS = 0.0
         e0, el0, _, _, _ = measure(name, dtype, B, K, W, rank, world, dist, with_roofline=False)
         cold_ms = el0 / K * 1e3
         del e0
         torch.cuda.empty_cache()
         PREHEAT_MS = args.preheat_ms
-    want_diff = world == 1 and not args.no_cpu_baseline
-    eng, elapsed, dom, table, loss = measure(name, dtype, B, K, W, rank, world, dist, want_sample=want_diff)
+    want_diff = args.full and world == 1 and not args.no_cpu_baseline
+    eng, elapsed, dom, table, loss = measure(name, dtype, B, K, W, rank, world, dist, with_roofline=args.full, want_sample=want_diff,
+                                             dump_dir=args.dump_outputs)
     samples = {dtype: getattr(eng, "sample", None)}
 
     if rank == 0:
         value = world * B * K / elapsed
         ms_step = elapsed / K * 1e3
-        # The dominant kernel against the roof SURVEY.md 8(d) names for it: the MFMA peak of its operand type for the dense
-        # products (C3, R0 in f32), HBM for the streaming kernels and for R0's bf16 weight-gradient GEMM with the fused
-        # optimizer (26 B of p/m/v traffic per output element; 8(d): "bf16 mode: HBM until B >~ 2700/GPU").
-        secs = dom["avg_ms"] * 1e-3
-        kern = dom["kernel"]
-        f32_kernel = kern.startswith(("sheet_", "gemm_f32")) or "<f32>" in kern
-        peak_fl = PEAK["f32"] if f32_kernel else PEAK[dtype]           # f32 VALU peak == f32 MFMA peak (157.3 TF)
-        fl = dom["algo_flops"] / secs / 1e12
-        by = dom["algo_bytes"] / secs / 1e9
-        # which roof binds the dominant kernel: the one it is closer to (R0's bf16 weight-gradient GEMM with the fused optimizer
-        # moves 26 B of p/m/v per output element and sits at 0.55 of HBM against 0.14 of MFMA; C3's products the other way)
-        hbm_bound = dom["algo_flops"] <= 0 or by / HBM_PEAK_GBS > fl / peak_fl
-        if hbm_bound:
-            roof = {"bound": "hbm", "kernel": kern, "achieved": by, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": by / HBM_PEAK_GBS}
-        else:
-            # every dense product of the path runs on the matrix cores (the f32 forms at the f32 VALU's rate, 157.3 TF)
-            roof = {"bound": "mfma", "kernel": kern, "achieved": fl, "peak": peak_fl, "unit": "TFLOP/s", "frac": fl / peak_fl}
-        tr, src = pmc_traffic(name, kern) if (dtype == DEFAULT_DTYPE[name] and not args.batch) else (None, None)
-        roof.update({"traffic": tr, "traffic_unit": f"bytes/launch (PMC FETCH_SIZE x2 + WRITE_SIZE, {src})" if tr is not None else src,
-                     "avg_launch_ms": dom["avg_ms"], "launches": dom["launches"], "algo_flops_per_launch": dom["algo_flops"],
-                     "algo_bytes_per_launch": dom["algo_bytes"], "mfma_frac": fl / peak_fl if dom["algo_flops"] > 0 else None,
-                     "hbm_frac": by / HBM_PEAK_GBS})
-        # whole step against the MFMA peak, and the three products of the widest Linear (per-shape rows of the warm-up table)
-        sf = step_flops(cfg, B)
-        roof["step"] = {"algo_flops": sf, "achieved_tflops": sf / (ms_step * 1e-3) / 1e12, "peak": PEAK[dtype],
-                        "frac": sf / (ms_step * 1e-3) / 1e12 / PEAK[dtype]}
-        wn, wk = widest_linear(cfg)
-        Bm = B * cfg.tokens if isinstance(cfg, PixelConfig) else B          # rows of a Linear's products (every pixel token is a row)
-        # (operand orientation, MxNxK) of the three products: forward x.W^T, input gradient dy.W, weight gradient dy^T.x
-        shapes = {"fwd": ("<0,0", f"[{Bm}x{wn}x{wk}]"), "dX": ("<0,1", f"[{Bm}x{wk}x{wn}]"), "dW": ("<1,1", f"[{wn}x{wk}x{Bm}]")}
-        wl = {}
-        for r in table:
-            for role, (ori, sh) in shapes.items():
-                plain = r["kernel"].startswith("gemm") and ori in r["kernel"] and r["kernel"].endswith(sh)
-                body = r["kernel"].startswith("gemm_bf16_group256" + sh + ori)          # a plain product on the 256x256 body: name[shape]<a,b>
-                if (plain or body) and role not in wl and r["avg_ms"] > 0:
-                    tf = r["algo_flops"] / (r["avg_ms"] * 1e-3) / 1e12
-                    wl[role] = {"kernel": r["kernel"], "avg_us": r["avg_ms"] * 1e3, "tflops": tf, "frac": tf / (PEAK["f32"] if "f32" in r["kernel"] else PEAK[dtype])}
-        # a layer's weight and input gradients leave as ONE grouped launch when both qualify (afr_gemm_pair_plan)
-        for r in table:
-            if r["kernel"].startswith("gemm_bf16_group") and shapes["dX"][1][1:-1] in r["kernel"] and shapes["dW"][1][1:-1] in r["kernel"] \
-                    and "dW+dX" not in wl and r["avg_ms"] > 0:
-                tf = r["algo_flops"] / (r["avg_ms"] * 1e-3) / 1e12
-                wl["dW+dX"] = {"kernel": r["kernel"], "avg_us": r["avg_ms"] * 1e3, "tflops": tf, "frac": tf / PEAK[dtype],
-                               "note": "weight gradient (split-K slabs) and input gradient of the layer in one grouped launch"}
-        roof["widest_linear"] = {"layer": f"{wk}->{wn}", "source": "hipEvent brackets, warm-up steps (every launch timed)", **wl}
         out = {
             "metric": "glyphs/sec training (batch fwd+bwd+step)", "value": value, "unit": "glyphs/s", "n_gpus": world,
             "steps": K, "warmup": W, "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak",
@@ -380,14 +434,15 @@ def main():
             "config": {"workload": DESCR[name], "per_gpu_batch": B, "global_batch": world * B,
                        "parallelism": f"dp{world}" if world > 1 else "single", "params": int(sum(n for _, _, _, n in eng.layout)),
                        "mean_loss": loss},
-            "roofline": roof,
         }
+        if args.full:
+            out["roofline"] = roofline(name, cfg, dtype, B, ms_step, dom, table, args.batch)
         if args.table:
             for r in table:
                 print(f"{r['kernel']:44s} n={r['launches']:4d} avg={r['avg_ms'] * 1e3:9.1f} us total={r['total_ms']:9.3f} ms", file=sys.stderr)
     del eng
     torch.cuda.empty_cache()
-    if world == 1 and rank == 0:
+    if world == 1 and rank == 0 and args.full:
         if not args.no_extras and not args.batch:
             # parity mode of the SAME config (exact-f32 MFMA everywhere: the mode that meets the 1e-4 bitmap bar)
             if dtype != "f32":

@@ -12,12 +12,12 @@ mkdir -p $O
 export TMPDIR=/tmp
 B="--steps 100 --warmup 10 --no-extras --no-cpu-baseline --preheat-ms 0"     # no pre-heat forwards in the kernel statistics
 for w in c1 c2 c3 r0; do
-  python3 bench.py --workload $w --steps 200 --warmup 20 --table --no-extras > $O/bench_$w.log 2>&1
+  python3 bench.py --workload $w --steps 200 --warmup 20 --full --table --no-extras > $O/bench_$w.log 2>&1
   echo "bench $w done"
 done
-python3 bench.py --steps 200 --warmup 20 > $O/bench_default.log 2>&1
+python3 bench.py --steps 200 --warmup 20 --full > $O/bench_default.log 2>&1
 echo "bench default done"
-python3 bench.py --workload c5 --table > $O/bench_c5.log 2>&1          # one micro-batch of BASELINE configs[4]
+python3 bench.py --workload c5 --full --table > $O/bench_c5.log 2>&1          # one micro-batch of BASELINE configs[4]
 echo "bench c5 done"
 python3 tools/c5_step_bench.py 32 bf16 > $O/c5_step.log 2>&1
 echo "c5 step table done"
