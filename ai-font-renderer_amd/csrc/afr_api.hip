@@ -72,6 +72,7 @@ struct afr_plan {
     std::vector<GemmParams> pend;
     std::vector<std::string> pend_tag;
     double pend_flops = 0.0, pend_bytes = 0.0;
+    unsigned* pend_arrived = nullptr;   // the cooperative member's Layer::coop_arrived, advanced once the launch is enqueued
     // workspace offsets (bytes)
     size_t o_shadow = 0, o_err = 0, o_loss = 0, o_u = 0, o_z = 0, o_dz = 0, o_slab_e = 0, o_save = 0;
     std::vector<size_t> o_act;     // glyph: activations h0..h_nh
@@ -90,7 +91,6 @@ struct afr_plan {
     // glyph, bf16 training steps: hidden activations written by a GEMM epilogue also leave their ReLU mask as bits
     // (o_mbits[i] for the output of layer i, 0 = none); the next layer's input-gradient product reads those instead of the activation
     std::vector<size_t> o_mbits; bool mbits_on = false;
-    size_t o_fix = 0, o_fixcnt = 0; bool have_fix = false;   // in-launch split-K: slice parking area + per-tile arrival counters
     // bf16 glyph nets: TWO weight shadows.  A fused optimizer step writes every tensor's new bf16 copy into the one that is
     // not being read (a layer's weight-gradient workgroups update the weights while the same launch's input-gradient
     // workgroups still read them), and the roles swap when the step is complete.
@@ -109,7 +109,7 @@ struct afr_plan {
            o_dctx = 0, o_headp = 0;
     // glyph layer table
     struct Layer { int N, K; int64_t w_off, b_off; int sk = 1; size_t o_slab_w = 0, o_slab_b = 0;
-                   size_t o_cnt = 0; int n_cnt = 0; unsigned coop_epoch = 0; };   // cooperative split-K: per-tile arrival counters, launches so far
+                   size_t o_cnt = 0; int n_cnt = 0; unsigned coop_arrived = 0; };   // cooperative split-K: per-tile arrival counters, arrivals enqueued so far
     std::vector<Layer> layers;
     std::vector<Layer> pxl;          // the 5 Linears of every block as weight-gradient descriptors: q, kv, out-proj, fc1, fc2
     int64_t emb_off = 0, font_off = 0;
@@ -153,9 +153,6 @@ static int64_t off_of(const afr_plan* p, const char* name) {
 }
 
 static_assert(AFR_RT_MAXSEG >= 2 * AFR_MAX_HIDDEN + 2 * AFR_L1F_MAX_SPLIT + 4, "a backward pass of the deepest glyph net must fit one grouped reduce");
-#ifndef AFR_SPLITK_TARGET
-#define AFR_SPLITK_TARGET 512
-#endif
 static int choose_splitk(int M, int N, int K) {
     // a small weight gradient reduced over very many rows (the pixel transformer's: 131072 token rows into 2048 x 512): as many
     // K-slices as make the 256x256 tiles fill the chip exactly once -- the launcher then takes the 256x256 body for it
@@ -163,7 +160,7 @@ static int choose_splitk(int M, int N, int K) {
     const int t256 = ((M + 255) / 256) * ((N + 255) / 256);
     if (K >= 32768 && t256 >= 8 && t256 <= 64 && 256 % t256 == 0 && K / (256 / t256) >= 1024) return 256 / t256;
     const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
-    int s = (AFR_SPLITK_TARGET + tiles - 1) / tiles;
+    int s = (512 + tiles - 1) / tiles;                 // about 512 blocks of 128x128 tiles
     const int maxs = K / 256 > 0 ? K / 256 : 1;
     if (s > maxs) s = maxs;
     if (s < 1) s = 1;
@@ -223,12 +220,6 @@ extern "C" int afr_plan_create(const afr_config* c, afr_plan** out) {
         p->layers.push_back(ly);
         p->o_slab_e = carve((size_t)afr_sheet_blocks((int)B) * (size_t)p->s_wout * sizeof(float));
         p->o_save = carve(B * (size_t)L * AFR_SHEET_SAVE_PER_POS * sizeof(float));
-        if (c->dtype == AFR_BF16 && (c->reserved & 8)) {   // opt-in: fc_output's input-gradient product as in-launch split-K
-            int hd, sk;
-            if (afr_gemm_fix_plan((int)B, Pix, (int)Kz, &hd, &sk) || afr_gemm_fix_plan((int)B, (int)Kz, Pix, &hd, &sk)) {
-                p->o_fix = carve(AFR_FIX_WS_BYTES); p->o_fixcnt = carve(AFR_FIX_MAX_SLICES * sizeof(unsigned)); p->have_fix = true;
-            }
-        }
     } else if (c->kind == AFR_KIND_GLYPH) {
         if (c->n_hidden < 0 || c->n_hidden > AFR_MAX_HIDDEN) { delete p; return fail(AFR_EINVAL, "n_hidden out of range"); }
         if (E % 8) { delete p; return fail(AFR_EUNSUPPORTED, "embed_dim must be a multiple of 8"); }
@@ -303,7 +294,7 @@ extern "C" int afr_plan_create(const afr_config* c, afr_plan** out) {
             const size_t ncombo = (size_t)c->vocab * (c->n_fonts > 0 ? c->n_fonts : 1);
             if (c->dtype == AFR_BF16 && p->l1f && c->n_hidden >= 2 && ncombo <= 1024 && !(c->reserved & (64 | 16))) {
                 p->combo_ok = true;
-                p->h1c_ld = c->hidden[0] + (getenv("AFR_H1C_PAD") ? atoi(getenv("AFR_H1C_PAD")) : 0);      // kernel A/B measurements
+                p->h1c_ld = c->hidden[0];
                 p->o_h1c = carve(ncombo * p->h1c_ld * 2); p->o_h0c = carve(ncombo * E * 2); p->o_cidx = carve(B * sizeof(int));
             }
         }
@@ -438,13 +429,9 @@ extern "C" int afr_bind(afr_plan* p, float* params, float* grads, float* m, floa
     p->have_du = false;
     p->wT_valid = false;
     p->shadow_cur = 0; p->step_on = false; p->adam_done.clear();
-    for (auto& l : p->layers) {                          // cooperative split-K: arrival counters and launch count start at zero
-        l.coop_epoch = 0;
+    for (auto& l : p->layers) {                          // cooperative split-K: arrival counters and their host count start at zero
+        l.coop_arrived = 0;
         if (l.n_cnt) { DevGuard dg(dev); HIPCHK(hipMemset(p->ws + l.o_cnt, 0, (size_t)l.n_cnt * sizeof(unsigned))); }
-    }
-    if (p->have_fix) {                                   // arrival counters start at zero; the kernels re-arm them
-        DevGuard dg(dev);
-        HIPCHK(hipMemset(p->ws + p->o_fixcnt, 0, AFR_FIX_MAX_SLICES * sizeof(unsigned)));
     }
     return AFR_OK;
 }
@@ -629,16 +616,6 @@ static int run_gemm(afr_plan* p, hipStream_t s, int flags, const void* A, const 
     const double out_bytes = fa ? (double)M * N * (24.0 + (fa->shadow ? 2.0 : 0.0)) : (splitk > 1 ? 4.0 : ob) * (double)M * N;
     char tag[96];
     const double fl_ = 2.0 * M * (double)N * K, by_ = eb * ((double)M * K + (double)N * K) + out_bytes;
-    int hd = 0, fsk = 1;
-    if (p->have_fix && p->cfg.dtype == AFR_BF16 && splitk == 1 && !fl && !fa && !colsum && (p->cfg.reserved & 8) &&
-        afr_gemm_fix_plan(M, N, K, &hd, &fsk)) {
-        g.head_tiles = hd; g.splitk = fsk;
-        g.fix_ws = (float*)(p->ws + p->o_fix); g.fix_cnt = (unsigned*)(p->ws + p->o_fixcnt);
-        snprintf(tag, sizeof tag, "gemm_bf16_group256[%dx%dx%d]", M, N, K);
-        ProfScope ps(p, s, tag, fl_, by_);
-        HIPCHK(afr_launch_gemm_fix(g, s));
-        return AFR_OK;
-    }
     {
         const char* kn = afr_gemm_kernel_name(p->cfg.dtype, g);
         if (strcmp(kn, "gemm_bf16_group256") == 0)     // a plain product on the 256x256 body: the operand orientation follows the shape
@@ -657,6 +634,12 @@ static int run_gemm(afr_plan* p, hipStream_t s, int flags, const void* A, const 
     HIPCHK(afr_launch_gemm(p->cfg.dtype, g, s));
     return AFR_OK;
 }
+// forget what run_gemm collected (after its launch, or when a call fails before it)
+static void drop_pending(afr_plan* p) {
+    p->defer = false;
+    p->pend.clear(); p->pend_tag.clear(); p->pend_flops = p->pend_bytes = 0.0;
+    p->pend_arrived = nullptr;
+}
 // launch what run_gemm collected while p->defer was set: one grouped launch (or the plain one when only one qualified)
 static int flush_gemms(afr_plan* p, hipStream_t s) {
     p->defer = false;
@@ -672,7 +655,9 @@ static int flush_gemms(afr_plan* p, hipStream_t s) {
         ProfScope ps(p, s, tag.c_str(), p->pend_flops, p->pend_bytes);
         e = afr_launch_gemm_group(p->cfg.dtype, p->pend.data(), (int)p->pend.size(), p->pend_tile256, s);
     }
-    p->pend.clear(); p->pend_tag.clear(); p->pend_flops = p->pend_bytes = 0.0;
+    // the launch carries the cooperative member's arrivals: the host count follows only once it is enqueued
+    if (e == hipSuccess && p->pend_arrived) *p->pend_arrived = p->pend[0].coop_target;
+    drop_pending(p);
     if (e != hipSuccess) return fail(AFR_EHIP, "grouped GEMM launch: %s", hipGetErrorString(e));
     return AFR_OK;
 }
@@ -695,12 +680,14 @@ static int run_dw(afr_plan* p, hipStream_t s, afr_plan::Layer& l, const void* dy
         // cooperative split-K: the slices meet inside the launch; the product leaves as the finished gradient, or -- during a
         // fused optimizer step -- as the AdamW update of this weight (its new bf16 copy goes to the write shadow, which the
         // launch's input-gradient workgroups do not read)
-        CoopArgs ca{sw, (unsigned*)(p->ws + l.o_cnt), ++l.coop_epoch * (unsigned)sk};
+        // (each launch adds sk arrivals to every tile's counter; the slices of this one wait for the total after it)
+        CoopArgs ca{sw, (unsigned*)(p->ws + l.o_cnt), l.coop_arrived + (unsigned)sk};
         FusedAdam fa{p->P + l.w_off, p->M + l.w_off, p->V + l.w_off, shadow_wr(p) ? shadow_wr(p) + l.w_off : nullptr,
                      p->st_decay, p->st_b1, p->st_b2, p->st_eps, p->st_step, p->st_rsqrt_bc2};
         int rc = run_gemm(p, s, fl, dy, a, p->G + l.w_off, nullptr, nullptr, N, K, Bn, N, a_rows ? a_ld : K, K, 0, sk, 0, sb, N, nullptr,
                           p->step_on ? &fa : nullptr, &ca, rm);
         if (rc) return rc;
+        p->pend_arrived = &l.coop_arrived;                // run_gemm deferred it (a cooperative product is never launched alone)
         if (p->step_on) p->adam_done.push_back(l.w_off);
         afr_rtable_add(rt, p->G + l.b_off, sb, sk, N, N);
         return AFR_OK;
@@ -1172,14 +1159,14 @@ static int backward_stage_impl(afr_plan* p, int stage, int64_t* g_off, int64_t* 
     }
     p->pend_tile256 = tile256;
     p->defer = sk_group > 0;
-    if ((rc = run_dw(p, s, l, dy, a, B, rt, sk_group, coop, cidx, p->h1c_ld))) { p->defer = false; p->pend.clear(); p->pend_tag.clear(); p->pend_flops = p->pend_bytes = 0.0; return rc; }
+    if ((rc = run_dw(p, s, l, dy, a, B, rt, sk_group, coop, cidx, p->h1c_ld))) { drop_pending(p); return rc; }
     void* dx = p->ws + p->o_d[stage & 1];
     const int fl = AFR_GEMM_B_KSTRIDED | ob | (i > 0 ? AFR_GEMM_RELU_MASK : 0);
     RowMaps rmx{nullptr, nullptr, cidx};
     const bool use_bits = p->mbits_on && i >= 2 && p->o_mbits[i - 1] && (fl & AFR_GEMM_OUT_BF16);
     if (use_bits) { rmx.mask_in = (const unsigned char*)(p->ws + p->o_mbits[i - 1]); rmx.ldmask = l.K / 8; }
     if ((rc = run_gemm(p, s, fl, dy, weight_ptr(p, l.w_off), dx, nullptr, i > 0 ? a : nullptr, B, l.K, l.N, l.N, l.K, l.K,
-                       gath ? p->h1c_ld : l.K, 1, 0, nullptr, 0, nullptr, nullptr, nullptr, (gath || use_bits) ? &rmx : nullptr))) { p->defer = false; p->pend.clear(); p->pend_tag.clear(); p->pend_flops = p->pend_bytes = 0.0; return rc; }
+                       gath ? p->h1c_ld : l.K, 1, 0, nullptr, 0, nullptr, nullptr, nullptr, (gath || use_bits) ? &rmx : nullptr))) { drop_pending(p); return rc; }
     if ((rc = flush_gemms(p, s))) return rc;
     const int64_t end = l.b_off + (l.N + 63) / 64 * 64;
     if (i > 0) {

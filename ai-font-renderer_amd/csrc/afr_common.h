@@ -156,10 +156,9 @@ hipError_t afr_launch_f32_to_fp8(const float* src, unsigned char* dst, long long
 bool afr_gemm_groupable(int dtype, const GemmParams& p);
 hipError_t afr_launch_gemm_group(int dtype, const GemmParams* ps, int n, int tile256, hipStream_t s);
 void afr_gemm_pair_plan(int B, int n_out, int k_in, int* tile256, int* splitk);
-// in-launch split-K plan for one bf16 product on 256x256 tiles: true when it beats the ring kernels by the launch model;
-// workspace need is (tiles - head_tiles) * splitk * AFR_FIX_SLICE_BYTES, never more than AFR_FIX_WS_BYTES
-constexpr size_t AFR_FIX_SLICE_BYTES = 256 * 256 * 4, AFR_FIX_MAX_SLICES = 256, AFR_FIX_WS_BYTES = AFR_FIX_SLICE_BYTES * AFR_FIX_MAX_SLICES;
-bool afr_gemm_fix_plan(int M, int N, int K, int* head_tiles, int* splitk);
+// in-launch split-K for one bf16 product on 256x256 tiles (GemmParams::fix_ws): the workspace needs
+// (tiles - head_tiles) * splitk * AFR_FIX_SLICE_BYTES
+constexpr size_t AFR_FIX_SLICE_BYTES = 256 * 256 * 4;
 hipError_t afr_launch_gemm_fix(const GemmParams& p, hipStream_t s);
 const char* afr_gemm_kernel_name(int dtype, const GemmParams& p);
 bool afr_gemm_wide_ok(int M, int N, int K);      // a bf16 product of this shape (no split, no fused optimizer) runs on the 256x128 ring kernel

@@ -682,10 +682,8 @@ template <int WM> struct RingGeom {
 };
 // One output tile (and k-split) of one product: block `bid` of the `nblk` blocks that product was given.  A plain launch
 // passes its own blockIdx / gridDim; a grouped launch (gemm_bf16_group) a sub-range of its grid.
-// ABL (kernel-development builds only, -DAFR_GEMM_LAB): ablation bits for the ring loop -- 1: no DMA inside the loop,
-// 2: no fragment reads inside the loop, 4: no MFMAs.  Results are wrong by construction; only the time is read.
 // GA: the k-contiguous A operand's rows are gathered through p.a_rowmap (ALAY == 0, WM == 4 only)
-template <int ALAY, int BLAY, int WM, int ABL = 0, int GA = 0>
+template <int ALAY, int BLAY, int WM, int GA = 0>
 __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p, const int bid, const int nblk, char* smem) {
     static_assert(!GA || (ALAY == 0 && WM == 4), "row gather: k-contiguous A on the 256x128 ring kernel");
     constexpr int BM = 64 * WM, NW = 2 * WM, ASUB = WM / 2;
@@ -827,7 +825,6 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p, const int bi
     };
     // operands swapped on purpose: D'[n][m] so that a lane owns 4 consecutive n of one row m
     auto mma = [&](const bf16x8 (&fa)[4], const bf16x8 (&fb)[4]) {
-#ifndef AFR_ABLATE_NOMFMA
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -835,10 +832,6 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p, const int bi
             for (int j = 0; j < 4; ++j)
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
         __builtin_amdgcn_s_setprio(0);
-#else
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { asm volatile("" ::"v"(fa[i])); asm volatile("" ::"v"(fb[i])); }
-#endif
     };
     // k-step-1 MFMAs of tile t with the refill of the freed slot (tile t+3) and the fragment reads of tile t+1 (k-step 0)
     // issued BETWEEN the rows of MFMAs instead of ahead of them: the memory instructions go out while the matrix pipe works.
@@ -860,18 +853,14 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p, const int bi
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            if constexpr (!(ABL & 4)) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
-            } else {
-                asm volatile("" ::"v"(fa[i]), "v"(fb[i]));
-            }
-            if (do_stage && !(ABL & 1)) {
+            for (int j = 0; j < 4; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
+            if (do_stage) {
 #pragma unroll
                 for (int q = i * NP / 4; q < (i + 1) * NP / 4; ++q) stage_piece(tn, slot, q);
             }
-            if (do_read && !(ABL & 2)) {
+            if (do_read) {
                 ra[i] = read_frag<ALAY>(Sn + (wm >> 1) * SUB, (wm & 1) * 64 + 16 * i, ks, lane);
                 rb[i] = read_frag<BLAY>(Sn + ASUB * SUB, wn * 64 + 16 * i, ks, lane);
             }
@@ -922,30 +911,13 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p, const int bi
         for (int t = 0; t < nt; ++t) {
             const char* S = smem + slot * STAGE_BYTES;
             if (ALAY == 1 && do_cs) colsum_tile(S);
-            if ((ABL & 8) && wave >= 4) {
-                // waves 4..7 (the SIMD partners of 0..3) re-fill the ring in the FIRST half of an iteration, waves 0..3 in
-                // the second: at any time only one of a SIMD's two waves is issuing DMA (an LDS-DMA piece holds its wave for
-                // ~100 cycles), the other has bare MFMAs + LDS reads for the matrix pipe.  Slot (t+2)%3 held tile t-1, which
-                // every wave finished reading before the barrier of iteration t-1.
-                int ps = slot + 2; if (ps >= 3) ps -= 3;
-                mma_mem(a0, b0, t >= 1 && t + 2 < nt, t + 2, ps, true, S, 1, a1, b1);
-            } else {
-                mma_mem(a0, b0, false, 0, 0, true, S, 1, a1, b1);                     // A inside B
-            }
+            mma_mem(a0, b0, false, 0, 0, true, S, 1, a1, b1);                     // A inside B
             if (t + 1 < nt) {
-                if ((ABL & 8) && wave >= 4) {
-                    // outstanding here: tile t+1 (6 pieces, issued one iteration ago) and tile t+2 (just issued)
-                    if (t >= 1 && t + 2 < nt) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
-                    else if (t == 0 && nt > 2) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");   // prologue's tiles 1, 2
-                    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                } else {
-                    if (t + 2 < nt) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");   // C
-                    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                }
+                if (t + 2 < nt) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");   // C
+                else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
                 int ns = slot + 1; if (ns == 3) ns = 0;
-                if ((ABL & 8) && wave >= 4) mma_mem(a1, b1, false, 0, 0, true, smem + ns * STAGE_BYTES, 0, a0, b0);
-                else mma_mem(a1, b1, t + 3 < nt, t + 3, slot, true, smem + ns * STAGE_BYTES, 0, a0, b0);   // D, E inside F
+                mma_mem(a1, b1, t + 3 < nt, t + 3, slot, true, smem + ns * STAGE_BYTES, 0, a0, b0);   // D, E inside F
                 slot = ns;
             } else {
                 mma(a1, b1);
@@ -962,9 +934,7 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p, const int bi
         int slot = 0;
         for (int t = 0; t < nt; ++t) {
             // tile t+1 streams into the other slot, which every wave finished reading before the last barrier
-#ifndef AFR_ABLATE_NOLOAD
             if (t + 1 < nt) stage(t + 1, slot ^ 1);
-#endif
             const char* S = smem + slot * STAGE_BYTES;
             bf16x8 fa[4], fb[4];
 #pragma unroll
@@ -1050,7 +1020,7 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p, const int bi
 //     per K-tile, in phase 3 ahead of its first barrier: the four newest sub-tiles (tile t+2) stay in flight, tile t+1 has
 //     landed; its first read is two barriers later (the trailing group's wait sits one barrier after the leading one's).
 // GB: the k-strided B operand's rows (its k index: batch rows of a weight-gradient product) are gathered through p.b_rowmap
-template <int ALAY, int BLAY, int ABL = 0, int GB = 0>
+template <int ALAY, int BLAY, int GB = 0>
 __device__ __forceinline__ void gemm_bf16_256_body(const GemmParams& p, const int bid, const int nblk, char* smem) {
     static_assert(!GB || BLAY == 1, "row gather: k-strided B on the 256x256 kernel");
     constexpr int BM = 256, BNN = 256;
@@ -1136,12 +1106,7 @@ __device__ __forceinline__ void gemm_bf16_256_body(const GemmParams& p, const in
         bm_base = (const __attribute__((address_space(4))) int*)(((unsigned long long)hi << 32) | lo);
     }
     auto bmap_load = [&](int t) -> i32x8 {
-#ifdef AFR_FAKE_BMAP      // kernel-development build: arithmetic rows instead of the scalar load (wrong results, timing only)
-        const int k = kbeg + t * BK + wave * 8;
-        return (i32x8){k & 255, (k + 1) & 255, (k + 2) & 255, (k + 3) & 255, (k + 4) & 255, (k + 5) & 255, (k + 6) & 255, (k + 7) & 255};
-#else
         return *reinterpret_cast<const __attribute__((address_space(4))) i32x8*>(bm_base + t * BK);
-#endif
     };
     auto bmap_apply = [&](const i32x8 mv) {
         const int kr = lane >> 4;
@@ -1161,12 +1126,6 @@ __device__ __forceinline__ void gemm_bf16_256_body(const GemmParams& p, const in
     const unsigned subA = ALAY == 0 ? 128u * p.lda * 2 : 256u, subB = BLAY == 0 ? 128u * p.ldb * 2 : 256u;
     const unsigned tileA = ALAY == 0 ? 128u : 64u * p.lda * 2, tileB = BLAY == 0 ? 128u : 64u * p.ldb * 2;
     auto dma_pair = [&](i32x4 rsrc, unsigned lds_a, unsigned voff, unsigned soff_a, unsigned soff_b) {
-        if constexpr (ABL & 4) {
-            i32x4 d0, d1;
-            asm volatile("s_nop 3\n\tbuffer_load_dwordx4 %0, %2, %5, %3 offen\n\tbuffer_load_dwordx4 %1, %2, %5, %4 offen"
-                         : "=&v"(d0), "=&v"(d1) : "v"(voff), "s"(soff_a), "s"(soff_b), "s"(rsrc) : "memory");
-            return;
-        }
         unsigned keep;
         asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 3\n\tbuffer_load_dwordx4 %1, %5, %3 offen lds\n\t"
                      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %5, %4 offen lds\n\ts_mov_b32 m0, %0"
@@ -1232,13 +1191,13 @@ __device__ __forceinline__ void gemm_bf16_256_body(const GemmParams& p, const in
 #pragma unroll
         for (int ph = 0; ph < 4; ++ph) {
             // ---- this phase's LDS reads
-            if (ph == 0 && !((ABL & 2) && t > 0)) {
+            if (ph == 0) {
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) fb[ks][j] = read_frag<BLAY>(Bs, bx + 16 * j, ks, lane);
             }
-            if ((ph == 0 || ph == 2) && !((ABL & 2) && t > 0)) {
+            if (ph == 0 || ph == 2) {
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -1250,7 +1209,7 @@ __device__ __forceinline__ void gemm_bf16_256_body(const GemmParams& p, const in
                 if (ph == 1) bmap_apply(mvn);
             }
             // ---- this phase's DMA: sub-tile ph of tile t+2
-            if (t + 2 < nt && !(ABL & 1)) stage_sub(t + 2, sa2, ph);
+            if (t + 2 < nt) stage_sub(t + 2, sa2, ph);
             if (ph == 3) {
                 if (t + 2 < nt) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");       // tile t+2 (8 pieces per wave) stays in flight
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1429,10 +1388,10 @@ __device__ __forceinline__ void gemm_bf16_256_body(const GemmParams& p, const in
 #endif
 }
 
-template <int ALAY, int BLAY, int WM, int ABL = 0, int GA = 0>
+template <int ALAY, int BLAY, int WM, int GA = 0>
 __global__ __launch_bounds__(128 * WM, 2) void gemm_bf16(GemmParams p) {
     __shared__ __attribute__((aligned(16))) char smem[RingGeom<WM>::LDS_BYTES];
-    gemm_bf16_body<ALAY, BLAY, WM, ABL, GA>(p, blockIdx.x, gridDim.x, smem);
+    gemm_bf16_body<ALAY, BLAY, WM, GA>(p, blockIdx.x, gridDim.x, smem);
 }
 
 // Several independent products in ONE launch (a layer's weight gradient and input gradient both consume the same dy):
@@ -1463,19 +1422,12 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_group256(GemmGroup g) {
     const GemmParams& p = g.p[i];
     const int bid = b - g.blk0[i], nblk = g.blk0[i + 1] - g.blk0[i];
     const int lay = ((p.flags & AFR_GEMM_A_KSTRIDED) ? 2 : 0) | ((p.flags & AFR_GEMM_B_KSTRIDED) ? 1 : 0);
-    if (lay == 3 && p.b_rowmap) gemm_bf16_256_body<1, 1, 0, 1>(p, bid, nblk, smem);
+    if (lay == 3 && p.b_rowmap) gemm_bf16_256_body<1, 1, 1>(p, bid, nblk, smem);
     else if (lay == 3) gemm_bf16_256_body<1, 1>(p, bid, nblk, smem);
     else if (lay == 1) gemm_bf16_256_body<0, 1>(p, bid, nblk, smem);
     else if (lay == 0) gemm_bf16_256_body<0, 0>(p, bid, nblk, smem);
     else gemm_bf16_256_body<1, 0>(p, bid, nblk, smem);
 }
-#ifdef AFR_GEMM_LAB
-template <int ABL>
-__global__ __launch_bounds__(512, 2) void gemm_bf16_lab256(GemmGroup g) {
-    __shared__ __attribute__((aligned(16))) char smem[10 * SUB];
-    gemm_bf16_256_body<0, 0, ABL>(g.p[0], blockIdx.x, gridDim.x, smem);
-}
-#endif
 
 // ------------------------------------------------------------ folded first layer of the glyph nets: backward in ONE kernel
 // (throughput mode).  Inputs: d1 = d(loss)/d(pre-activation of fc1) [B][N1] (the layer above already applied the ReLU mask),
@@ -1508,12 +1460,6 @@ __global__ __launch_bounds__(512) void glyph_l1_bwd_fused_kernel(L1BwdArgs a) {
     int* ids = reinterpret_cast<int*>(sm + (NS + 1) * SUB);  // [64] codes, [64] vocab + font id (or -1)
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)sm;
     float* slab = a.slabs + (size_t)blockIdx.x * a.slab_stride;
-#ifdef AFR_L1F_DEBUG
-    unsigned long long ts_[8]; int nts_ = 0;
-#define L1STAMP() do { __syncthreads(); ts_[nts_++] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define L1STAMP() do { } while (0)
-#endif
     // this wave's W1^T operands of the dh0 product (16 bytes per lane and k-step, <= 32 k-steps): independent of the staging
     // below, so they are requested first and arrive under it
     constexpr int L1_MAXKS = 32;
@@ -1526,7 +1472,6 @@ __global__ __launch_bounds__(512) void glyph_l1_bwd_fused_kernel(L1BwdArgs a) {
         for (int j = 0; j < L1_MAXKS; ++j)
             if (j < nks) wv[j] = *reinterpret_cast<const bf16x8*>(wrow + j * 32);
     }
-    L1STAMP();
     {
         const i32x4 rD = make_rsrc(a.d1), rH = make_rsrc(a.h0);
         const int pieces = (NS + 1) * 16;
@@ -1549,7 +1494,6 @@ __global__ __launch_bounds__(512) void glyph_l1_bwd_fused_kernel(L1BwdArgs a) {
         }
         __syncthreads();
     }
-    L1STAMP();
     // ---- dh0 tile of this wave: glyph rows (wave>>1)*16.., embedding columns (wave&1)*16..; reduction over all N1
     f32x4 dh0 = {0.f, 0.f, 0.f, 0.f};
     {
@@ -1564,7 +1508,6 @@ __global__ __launch_bounds__(512) void glyph_l1_bwd_fused_kernel(L1BwdArgs a) {
             }
         }
     }
-    L1STAMP();
     // ---- dW1 / db1: output tiles [16 n][48 e'] (e' = 32: the ones column), reduction over the block's 64 glyphs
     {
         bf16x8 hf[3][2];
@@ -1588,7 +1531,6 @@ __global__ __launch_bounds__(512) void glyph_l1_bwd_fused_kernel(L1BwdArgs a) {
             if (q == 0) slab[a.o_b + n] = acc[2][0];
         }
     }
-    L1STAMP();
     __syncthreads();                                         // every read of the d1 / h0 images is done: the area is reused
     // ---- embedding_dense_backward as one more product (as glyph1_step_kernel): dh0^T [E][64] and the one-hot image [VT][64]
     bf16_t* dh0T = reinterpret_cast<bf16_t*>(sm);
@@ -1617,10 +1559,6 @@ __global__ __launch_bounds__(512) void glyph_l1_bwd_fused_kernel(L1BwdArgs a) {
         const int v = vt * 16 + r;
         if (v < rows_tot) *reinterpret_cast<f32x4*>(slab + a.o_tab + (size_t)v * L1_E + et * 16 + 4 * q) = acc;
     }
-    L1STAMP();
-#ifdef AFR_L1F_DEBUG
-    if (blockIdx.x == 5 && tid == 0) { printf("l1f phases (us):"); for (int i = 1; i < nts_; ++i) printf(" %.2f", (double)(ts_[i] - ts_[i - 1]) * 0.01); printf("\n"); }
-#endif
 }
 }  // namespace bf16k
 
@@ -1781,10 +1719,6 @@ hipError_t afr_launch_gemm_fp8(const GemmParams& p, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------- launch
-#ifdef AFR_GEMM_LAB
-static int g_gemm_variant = getenv("AFR_GEMM_VARIANT") ? atoi(getenv("AFR_GEMM_VARIANT")) : 0;
-extern "C" void afr_dbg_set_gemm_variant(int v) { g_gemm_variant = v; }
-#endif
 #ifdef AFR_GEMM_TIMING
 static int g_dbg_slot = 0;
 extern "C" int afr_dbg_gemm_stamps(void* devbuf) {
@@ -1810,8 +1744,7 @@ static bool bf16_use_wide(const GemmParams& p) {
 // chip, so that the ragged last round is small change.  Measured on the pixel transformer's products (131072 rows): 8-20 %
 // faster than the 256x128 ring (K = 512: 466 -> 390 us forward, 104 -> 87 us input gradient; K = 2048: 322 -> 266 us).
 static bool bf16_use_body256(const GemmParams& p) {
-    static const int off = getenv("AFR_GEMM_NO_BODY256") ? atoi(getenv("AFR_GEMM_NO_BODY256")) : 0;      // kernel A/B measurements
-    if (off || p.mse_target || p.ad_p || p.a_rowmap || p.b_rowmap || p.coop_ws || p.fix_ws) return false;
+    if (p.mse_target || p.ad_p || p.a_rowmap || p.b_rowmap || p.coop_ws || p.fix_ws) return false;
     const long long t = (long long)((p.M + 255) / 256) * ((p.N + 255) / 256);
     // weight gradients (both operands k-strided, split-K slabs): when the slices of the 256x256 tiles make whole rounds of the chip
     const bool kk = (p.flags & AFR_GEMM_A_KSTRIDED) && (p.flags & AFR_GEMM_B_KSTRIDED);
@@ -1847,53 +1780,36 @@ void afr_gemm_pair_plan(int B, int n_out, int k_in, int* tile256, int* splitk) {
     int sk = n_out > 0 ? (B + n_out - 1) / n_out : 1;                 // dW K-tiles per block == dX K-tiles per block
     if (sk < 1) sk = 1;
     const long long total = dx256 + dw256 * sk;
-    const char* force = getenv("AFR_GEMM_PAIR_TILE");                  // 128 | 256: kernel A/B measurements
-    bool use256 = total >= 192 && total <= 272 && B / sk >= 256;
-    if (force) use256 = atoi(force) == 256;
-    if (use256) { *tile256 = 1; *splitk = sk; return; }
+    if (total >= 192 && total <= 272 && B / sk >= 256) { *tile256 = 1; *splitk = sk; return; }
     *tile256 = 0;
     sk = n_out > 0 ? (B + 2 * n_out - 1) / (2 * n_out) : 1;
     if (sk < 1) sk = 1;
     if (B / sk < 256) sk = 0;                                         // 0: no grouped launch
     *splitk = sk;
 }
-// In-launch split-K on 256x256 tiles (GemmParams::fix_ws): worth it when the tile count leaves the last round of the chip
-// mostly empty -- the tail tiles are then cut along K so that the round's work is spread over every CU -- and the product
-// is deep enough that the 256x256 kernel's fewer staged bytes per FLOP outweigh the parked slices.  Launch model in
-// microseconds per K-tile (measured, operands in L2/MALL): 1.5 per block-round of the 256x256 kernel, 0.92 of the 256x128
-// ring, 0.95 of the 128x128 kernel at two blocks per CU; 12 us for parking and summing the slices.
-bool afr_gemm_fix_plan(int M, int N, int K, int* head_tiles, int* splitk) {
-    static const int force = getenv("AFR_GEMM_FIX") ? atoi(getenv("AFR_GEMM_FIX")) : -1;     // 0 | 1: kernel A/B measurements
-    if (force == 0 || M < 256 || N < 256 || K < 2048) return false;
-    const int kt = (K + 63) / 64;
-    const int tiles = ((M + 255) / 256) * ((N + 255) / 256);
-    const int rounds = tiles / 256, rem = tiles % 256;
-    int sk = 1;
-    if (rem) {
-        sk = 256 / rem;
-        if (sk > 8) sk = 8;
-        while (sk > 1 && kt / sk < 8) --sk;
-    }
-    if (getenv("AFR_GEMM_FIX_SK") && rem) sk = atoi(getenv("AFR_GEMM_FIX_SK"));            // kernel A/B measurements
-    if ((size_t)rem * sk > AFR_FIX_MAX_SLICES) return false;
-    const double c256 = (rounds * (double)kt + (rem ? (kt + sk - 1) / sk : 0)) * 1.5 + (sk > 1 ? 12.0 : 0.0);
-    const long long tw = (long long)((M + 255) / 256) * ((N + 127) / 128), tn = (long long)((M + 127) / 128) * ((N + 127) / 128);
-    const double cw = (double)((tw + 255) / 256) * kt * 0.92, cn = (double)((tn + 511) / 512) * kt * 0.95;
-    const double cr = cw < cn ? cw : cn;
-    if (force != 1 && !(c256 < 0.9 * cr)) return false;
-    *head_tiles = tiles - rem;
-    *splitk = sk;
-    return true;
-}
-hipError_t afr_launch_gemm_fix(const GemmParams& p, hipStream_t s) {
-    const int tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-    const int head = p.head_tiles < tiles ? p.head_tiles : tiles;
+// Products ps[0..n) in ONE launch of a grouped kernel: 256x256 tiles (gemm_bf16_group256) or 256x128 (gemm_bf16_group).
+// Product i takes a block per tile and K-slice; with in-launch split-K (fix_ws) its first head_tiles tiles are whole and
+// only the rest are sliced.  pad8: each product's range starts on a multiple of 8, so that blocks b, b+8, ... keep sharing
+// an XCD (the grouped launches); without it a lone product takes exactly its blocks.
+static hipError_t launch_grouped(const GemmParams* ps, int n, bool tile256, bool pad8, hipStream_t s) {
     bf16k::GemmGroup g;
-    g.n = 1; g.p[0] = p; g.blk0[0] = 0;
-    g.blk0[1] = head + (tiles - head) * p.splitk;
-    hipLaunchKernelGGL(bf16k::gemm_bf16_group256, dim3(g.blk0[1]), dim3(512), 0, s, g);
+    g.n = n;
+    int total = 0;
+    for (int i = 0; i < n; ++i) {
+        const GemmParams& p = ps[i];
+        const int tiles = ((p.M + 255) / 256) * ((p.N + (tile256 ? 255 : 127)) / (tile256 ? 256 : 128));
+        const int head = p.fix_ws ? (p.head_tiles < tiles ? p.head_tiles : tiles) : 0;
+        const int nb = head + (tiles - head) * p.splitk;
+        g.p[i] = p;
+        g.blk0[i] = total;
+        total += pad8 ? (nb + 7) & ~7 : nb;
+    }
+    g.blk0[n] = total;
+    if (tile256) hipLaunchKernelGGL(bf16k::gemm_bf16_group256, dim3(total), dim3(512), 0, s, g);
+    else hipLaunchKernelGGL(bf16k::gemm_bf16_group, dim3(total), dim3(512), 0, s, g);
     return hipGetLastError();
 }
+hipError_t afr_launch_gemm_fix(const GemmParams& p, hipStream_t s) { return launch_grouped(&p, 1, true, false, s); }
 hipError_t afr_launch_gemm_group(int dtype, const GemmParams* ps, int n, int tile256, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     bool ok = n <= 4, coop = false;
@@ -1917,22 +1833,12 @@ hipError_t afr_launch_gemm_group(int dtype, const GemmParams* ps, int n, int til
         for (int i = 0; i < n; ++i) { hipError_t e = afr_launch_gemm(dtype, ps[i], s); if (e != hipSuccess) return e; }
         return hipSuccess;
     }
-    bf16k::GemmGroup g;
-    g.n = n;
-    int total = 0;
-    for (int i = 0; i < n; ++i) {
-        g.p[i] = ps[i];
-        g.blk0[i] = total;
-        int nb = ((ps[i].M + 255) / 256) * ((ps[i].N + (tile256 ? 255 : 127)) / (tile256 ? 256 : 128)) * ps[i].splitk;
-        total += (nb + 7) & ~7;        // each product's range starts on a multiple of 8: blocks b, b+8, ... keep sharing an XCD
-    }
-    g.blk0[n] = total;
 #ifdef AFR_GEMM_TIMING
-    { const int slot = g_dbg_slot++ & 63; for (int i = 0; i < n; ++i) g.p[i].dbg_slot = slot; }
+    GemmParams q[4];
+    { const int slot = g_dbg_slot++ & 63; for (int i = 0; i < n; ++i) { q[i] = ps[i]; q[i].dbg_slot = slot; } }
+    ps = q;
 #endif
-    if (tile256) hipLaunchKernelGGL(bf16k::gemm_bf16_group256, dim3(total), dim3(512), 0, s, g);
-    else hipLaunchKernelGGL(bf16k::gemm_bf16_group, dim3(total), dim3(512), 0, s, g);
-    return hipGetLastError();
+    return launch_grouped(ps, n, tile256, true, s);
 }
 hipError_t afr_launch_gemm(int dtype, const GemmParams& p_in, hipStream_t s) {
 #ifdef AFR_GEMM_TIMING
@@ -1949,57 +1855,14 @@ hipError_t afr_launch_gemm(int dtype, const GemmParams& p_in, hipStream_t s) {
             (p.aux_rowmap && !(p.flags & AFR_GEMM_OUT_BF16))) return hipErrorInvalidValue;
     }
     if (dtype == AFR_BF16) {
-        if (bf16_use_body256(p)) {
-            bf16k::GemmGroup g;
-            g.n = 1; g.p[0] = p; g.blk0[0] = 0;
-            g.blk0[1] = ((p.M + 255) / 256) * ((p.N + 255) / 256) * p.splitk;
-            hipLaunchKernelGGL(bf16k::gemm_bf16_group256, dim3(g.blk0[1]), dim3(512), 0, s, g);
-            return hipGetLastError();
-        }
+        if (bf16_use_body256(p)) return launch_grouped(&p, 1, true, false, s);
         const bool wide = bf16_use_wide(p);
         const int bm = wide ? 256 : 128;
         const int tiles = ((p.M + bm - 1) / bm) * ((p.N + 127) / 128);
         dim3 grid(tiles * p.splitk, 1, 1);
 #define LB(AL, BL) do { if (wide) hipLaunchKernelGGL((bf16k::gemm_bf16<AL, BL, 4>), grid, dim3(512), 0, s, p); \
                         else hipLaunchKernelGGL((bf16k::gemm_bf16<AL, BL, 2>), grid, dim3(256), 0, s, p); } while (0)
-#ifdef AFR_GEMM_LAB
-        if (g_gemm_variant == 260 && !a && !b) {
-            bf16k::GemmGroup g;
-            g.n = 1; g.p[0] = p; g.blk0[0] = 0;
-            g.blk0[1] = ((((p.M + 255) / 256) * ((p.N + 255) / 256) * p.splitk) + 7) & ~7;
-            hipLaunchKernelGGL((bf16k::gemm_bf16_lab256<6>), dim3(g.blk0[1]), dim3(512), 0, s, g);
-            return hipGetLastError();
-        }
-        if (g_gemm_variant >= 257 && g_gemm_variant <= 259 && !a && !b) {
-            bf16k::GemmGroup g;
-            g.n = 1; g.p[0] = p; g.blk0[0] = 0;
-            g.blk0[1] = ((((p.M + 255) / 256) * ((p.N + 255) / 256) * p.splitk) + 7) & ~7;
-            if (g_gemm_variant == 257) hipLaunchKernelGGL((bf16k::gemm_bf16_lab256<1>), dim3(g.blk0[1]), dim3(512), 0, s, g);
-            else if (g_gemm_variant == 258) hipLaunchKernelGGL((bf16k::gemm_bf16_lab256<2>), dim3(g.blk0[1]), dim3(512), 0, s, g);
-            else hipLaunchKernelGGL((bf16k::gemm_bf16_lab256<3>), dim3(g.blk0[1]), dim3(512), 0, s, g);
-            return hipGetLastError();
-        }
-        if (g_gemm_variant == 256 || g_gemm_variant == 128) {       // one product through the grouped kernels
-            bf16k::GemmGroup g;
-            g.n = 1; g.p[0] = p; g.blk0[0] = 0;
-            const int t256 = g_gemm_variant == 256;
-            const int nb = ((p.M + 255) / 256) * ((p.N + (t256 ? 255 : 127)) / (t256 ? 256 : 128)) * p.splitk;
-            g.blk0[1] = (nb + 7) & ~7;
-            if (t256) hipLaunchKernelGGL(bf16k::gemm_bf16_group256, dim3(g.blk0[1]), dim3(512), 0, s, g);
-            else hipLaunchKernelGGL(bf16k::gemm_bf16_group, dim3(g.blk0[1]), dim3(512), 0, s, g);
-            return hipGetLastError();
-        }
-        if (wide && !a && !b && g_gemm_variant >= 100 && g_gemm_variant < 116) {
-            switch (g_gemm_variant - 100) {
-#define LABL(x) case x: hipLaunchKernelGGL((bf16k::gemm_bf16<0, 0, 4, x>), grid, dim3(512), 0, s, p); break;
-                LABL(1) LABL(2) LABL(3) LABL(8)
-#undef LABL
-                default: hipLaunchKernelGGL((bf16k::gemm_bf16<0, 0, 4, 0>), grid, dim3(512), 0, s, p);
-            }
-            return hipGetLastError();
-        }
-#endif
-        if (p.a_rowmap) hipLaunchKernelGGL((bf16k::gemm_bf16<0, 0, 4, 0, 1>), grid, dim3(512), 0, s, p);
+        if (p.a_rowmap) hipLaunchKernelGGL((bf16k::gemm_bf16<0, 0, 4, 1>), grid, dim3(512), 0, s, p);
         else if (!a && !b) LB(0, 0);
         else if (!a && b) LB(0, 1);
         else if (a && !b) LB(1, 0);
@@ -2020,7 +1883,7 @@ hipError_t afr_launch_gemm(int dtype, const GemmParams& p_in, hipStream_t s) {
 
 // ---- folded first layer, fused backward (bf16)
 bool afr_glyph_l1_bwd_fused_eligible(int dtype, int E, int N1, int vocab, int n_fonts) {
-    return dtype == AFR_BF16 && E == bf16k::L1_E && N1 % 128 == 0 && N1 >= 256 && N1 <= 1024 && vocab + n_fonts <= 144 && !getenv("AFR_NO_L1_FUSED");
+    return dtype == AFR_BF16 && E == bf16k::L1_E && N1 % 128 == 0 && N1 >= 256 && N1 <= 1024 && vocab + n_fonts <= 144;
 }
 // column ranges per row block: enough blocks to cover the chip, ranges of whole 128-column sub-tiles
 int afr_glyph_l1_bwd_fused_split(int B, int N1) {

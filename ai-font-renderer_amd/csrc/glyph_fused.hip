@@ -180,9 +180,6 @@ __global__ __launch_bounds__(MM<T>::NTH) void glyph1_step_kernel(Glyph1Args a) {
     T* h1T = h1 + R * ldN;
     T* du = h1T + N1 * ldR;
     T* duT = du + R * ldP;
-#ifdef AFR_G1_DEBUG
-    const unsigned long long t_entry = __builtin_amdgcn_s_memrealtime();
-#endif
     const int cs = a.cs, rb = (int)blockIdx.x / cs, pc = (int)blockIdx.x - rb * cs;
     const int npt = P / 16 / cs, pt0 = pc * npt;       // this block's output-column tiles [pt0, pt0 + npt)
     const int b0 = rb * R;
@@ -205,13 +202,6 @@ __global__ __launch_bounds__(MM<T>::NTH) void glyph1_step_kernel(Glyph1Args a) {
                 }
         }
     }
-#ifdef AFR_G1_DEBUG
-    unsigned long long tstamp[12]; int nst = 0;
-#define G1STAMP() do { __syncthreads(); tstamp[nst++] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define G1STAMP() do { } while (0)
-#endif
-    G1STAMP();
     // (plain stores: streaming ones made this kernel 2 us shorter and the reduce, which then reads the slabs from HBM, 3 us longer)
     float* slab = a.slabs + (size_t)blockIdx.x * a.slab_stride;
 
@@ -268,7 +258,6 @@ __global__ __launch_bounds__(MM<T>::NTH) void glyph1_step_kernel(Glyph1Args a) {
         }, PF ? &ftA : nullptr);
     __syncthreads();
 
-    G1STAMP();   // 1: gather + P1
     // ---- u = h1 . W2^T + b2 ; clamp, MSE, du (rows past the batch contribute nothing)
     float lsum = 0.f;
     const float g2 = 2.f * a.inv_n;
@@ -294,7 +283,6 @@ __global__ __launch_bounds__(MM<T>::NTH) void glyph1_step_kernel(Glyph1Args a) {
             }
         }, PF ? &ftB : nullptr);
     __syncthreads();
-    G1STAMP();   // 2: P2 + loss
     // dh1's first W2^T tile is requested now and arrives under the dW2 phase (which reads LDS only)
     const T* W2T = reinterpret_cast<const T*>(a.W2T);
     const int kb0 = pt0 * 16 / KB, nkbp = npt * 16 / KB;          // this block's k-blocks of the reduction over P (npt * 16 is a multiple of KB)
@@ -328,7 +316,6 @@ __global__ __launch_bounds__(MM<T>::NTH) void glyph1_step_kernel(Glyph1Args a) {
         slab[a.o_b2 + pp] = s;
     }
     __syncthreads();                     // every wave is done reading h1T (dW2) before dpre1 overwrites it below
-    G1STAMP();   // 3: dW2 + db2
 
     // ---- dh1 = du . W2 (over this block's columns: a partial sum when cs > 1) ; dpre1 = dh1 * [h1 > 0], written over h1 / h1T
     // (each element is read and rewritten by its owner only)
@@ -347,7 +334,6 @@ __global__ __launch_bounds__(MM<T>::NTH) void glyph1_step_kernel(Glyph1Args a) {
             }
         }, PF ? &ftA : nullptr);
     __syncthreads();
-    G1STAMP();   // 4: dh1
 
     // ---- dW1[n][e] = sum_b dpre1[b][n] h0[b][e]  (+ db1)
     for (int t = wave; t < (N1 / 16) * (E / 16); t += NW) {
@@ -363,7 +349,6 @@ __global__ __launch_bounds__(MM<T>::NTH) void glyph1_step_kernel(Glyph1Args a) {
         slab[a.o_b1 + n] = s;
     }
 
-    G1STAMP();   // 5: dW1 + db1
     // ---- dh0 = dpre1 . W1, kept transposed ([E][R], operand type) in the du area; then embedding_dense_backward as one more
     // product, dTab[v][e] = sum_b onehot[b][v] dh0[b][e] (A = dh0T rows e, B = onehotT rows v; the one-hot image is built in
     // LDS: row v has a 1 at every batch row that used table row v).  Fixed summation order: bitwise reproducible.  (A serial
@@ -387,7 +372,6 @@ __global__ __launch_bounds__(MM<T>::NTH) void glyph1_step_kernel(Glyph1Args a) {
             }
         });
     __syncthreads();
-    G1STAMP();   // 6: dh0
     if (tid < nb) {
         ohT[ids[tid] * ldR + tid] = cvt<T>(1.f);
         if (a.n_fonts > 0) ohT[(a.vocab + fids[tid]) * ldR + tid] = cvt<T>(1.f);
@@ -403,14 +387,6 @@ __global__ __launch_bounds__(MM<T>::NTH) void glyph1_step_kernel(Glyph1Args a) {
         else if (v < rows_tot) *reinterpret_cast<f32x4*>(slab + a.o_font + (size_t)(v - a.vocab) * E + et * 16 + 4 * q) = acc;
     }
 
-    G1STAMP();   // 7: scatter + table store
-#ifdef AFR_G1_DEBUG
-    if (blockIdx.x == 0 && tid == 0) {
-        printf("entry->first stamp %.2f us; phases (us):", (double)(tstamp[0] - t_entry) * 0.01);
-        for (int i = 1; i < nst; ++i) printf(" %.2f", (double)(tstamp[i] - tstamp[i - 1]) * 0.01);
-        printf("\n");
-    }
-#endif
     // ---- loss: block partial -> ticketed finish (fixed order)
     float* red = reinterpret_cast<float*>(h0);
     __syncthreads();
@@ -421,10 +397,6 @@ __global__ __launch_bounds__(MM<T>::NTH) void glyph1_step_kernel(Glyph1Args a) {
 #pragma unroll
     for (int w = 0; w < NW; ++w) bsum += red[w];
     loss_block_finish(bsum, a.loss_partial, a.counter, a.loss_accum, a.inv_n, red + 16);
-#ifdef AFR_G1_DEBUG
-    if (blockIdx.x == 0 && tid == 0) printf("last stamp -> exit %.2f us; entry -> exit %.2f us\n", (double)(__builtin_amdgcn_s_memrealtime() - tstamp[nst - 1]) * 0.01,
-                                            (double)(__builtin_amdgcn_s_memrealtime() - t_entry) * 0.01);
-#endif
 }
 
 // W [N][K] f32 -> WT [K][N] bf16 (the transposed operand copies of the bf16 fused step)
@@ -437,21 +409,19 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(const float* __rest
 
 int afr_glyph1_rows(int dtype) { return dtype == AFR_BF16 ? MM<bf16_t>::R : MM<float>::R; }
 // Blocks per row block: as many (4, 2, 1) as keep the launch within one round of the chip, with whole k-blocks of the
-// dh1 reduction per block (P / cs a multiple of 32 bf16 / 16 f32 elements).  AFR_G1_CS overrides (kernel A/B measurements).
+// dh1 reduction per block (P / cs a multiple of 32 bf16 / 16 f32 elements).
 int afr_glyph1_colsplit(int dtype, int B, int P) {
-    static const int force = getenv("AFR_G1_CS") ? atoi(getenv("AFR_G1_CS")) : 0;
     const int R = afr_glyph1_rows(dtype), kb = dtype == AFR_BF16 ? MM<bf16_t>::KB : MM<float>::KB, nrb = (B + R - 1) / R;
-    int cs = force > 0 ? force : 4;
-    while (cs > 1 && ((P / cs) % kb != 0 || (P / 16) % cs != 0 || (force <= 0 && nrb * cs > 256))) cs >>= 1;
+    int cs = 4;
+    while (cs > 1 && ((P / cs) % kb != 0 || (P / 16) % cs != 0 || nrb * cs > 256)) cs >>= 1;
     return cs;
 }
 int afr_glyph1_max_blocks(int dtype, int max_batch, int P) {
     const int R = afr_glyph1_rows(dtype), nrb = (max_batch + R - 1) / R;
     int m = nrb * afr_glyph1_colsplit(dtype, max_batch, P);
-    // a smaller batch may split further: at most 4 blocks per row block, and (unless forced) never more than 256 blocks then
+    // a smaller batch may split further: at most 4 blocks per row block, and never more than 256 blocks then
     const int alt = nrb * 4 < 256 ? nrb * 4 : 256;
     if (alt > m) m = alt;
-    if (getenv("AFR_G1_CS")) m = nrb * 4;
     return m;
 }
 bool afr_glyph1_eligible(int E, int N1, int P, int vocab, int n_fonts) {

@@ -24,10 +24,7 @@ namespace {
 constexpr int E = 32, H = 4, D = 8, F = 64, QKV = 96;
 constexpr int SE = 33, SQ = 100, SD = 36;       // LDS row strides: SE odd (conflict-free column walks); SQ, SD multiples of 4
                                                 // so that a head's 8 q/k/v/dO values are two aligned 16-byte LDS reads
-#ifndef AFR_SHEET_NT
-#define AFR_SHEET_NT 1024
-#endif
-constexpr int NT = AFR_SHEET_NT;                // threads per workgroup: many waves hide the LDS/FMA latencies of the serial phases
+constexpr int NT = 1024;                        // threads per workgroup: many waves hide the LDS/FMA latencies of the serial phases
 constexpr int NG = NT / 32;                     // 32-lane column groups (accumulator ownership)
 static_assert(NT == 1024, "the weight-gradient tile ownership below assumes 16 waves per workgroup");
 constexpr int W_FLOATS = QKV * SE + QKV + E * SE + E + E + E + F * SE + F;   // weights block
@@ -290,12 +287,6 @@ __device__ __forceinline__ float dqkv_at(const float* dq, const float* big, int 
     return j < E ? dq[l * SE + j] : big[l * SQ + j];
 }
 
-// Phase timing for kernel development: build with -DAFR_SHEET_TIMING and block 0 prints per-phase totals (10 ns ticks).
-#ifdef AFR_SHEET_TIMING
-#define TMARK(k) do { __syncthreads(); if (threadIdx.x == 0) { const long long t_ = wall_clock64(); tacc[k] += t_ - tlast; tlast = t_; } } while (0)
-#else
-#define TMARK(k) do { } while (0)
-#endif
 // partial column sums of an [L][ncols] LDS array: thread t < ncols*P owns column t%ncols and rows t/ncols, +P, ... ; the
 // P partials per column land in red[part*ncols + c] and are added by the column's owner after the next barrier
 template <class F>
@@ -356,9 +347,6 @@ __global__ __launch_bounds__(NT) void sheet_bwd_kernel(SheetDims dm, SheetParams
     // 14 MB host-side memset launch in front of every backward.)  The first accumulation is many barriers away.
     for (int i = tid0; i < so.total / 4; i += NT) reinterpret_cast<float4*>(Sblk)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     const bool saved = dr.save != nullptr;
-#ifdef AFR_SHEET_TIMING
-    long long tacc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = wall_clock64();
-#endif
 
     for (int b = blockIdx.x; b < B; b += gridDim.x) {
         // Every per-thread LDS address below depends only on the thread id and L, i.e. is invariant across this loop; left
@@ -367,7 +355,6 @@ __global__ __launch_bounds__(NT) void sheet_bwd_kernel(SheetDims dm, SheetParams
         int tid = tid0;
         asm volatile("" : "+v"(tid));
         const int c32 = tid & 31, g8 = tid >> 5, wave = tid >> 6, lane = tid & 63;     // g8: column group 0..NG-1
-        TMARK(11);
         // ---- codes, then the embedded string; o and the softmax statistics come from the training forward
         ph_tokens(tok, x, ldx, b, L, dm.vocab, nullptr, tid);
         if (saved) {
@@ -398,25 +385,21 @@ __global__ __launch_bounds__(NT) void sheet_bwd_kernel(SheetDims dm, SheetParams
             ph_attention(o, big, dr, b, L, tid, smax, sinv, dr.training ? mb : nullptr);
             __syncthreads();
         }
-        TMARK(0);
         ph_outproj_res(xh, e, o, w, L, tid);
         __syncthreads();
         ph_layernorm(xh, nbuf, rstd, w, L, eps, tid);        // qkv dead: n overwrites the front of `big`
         __syncthreads();
-        TMARK(1);
         // ---- df = dz * dropout-mask * [pre>0]
         const T* dzr = dz + (size_t)b * Kz;
         for (int i = tid; i < L * F; i += NT) df[i] = (float)dzr[i] * fc_mask(dr, b, L, i);
         __syncthreads();
         lds_mma(nbuf, SE, 1, w.W1, SE, 1, L, F, E, tid, [&](int m, int j, float v) { if (!(v + w.b1[j] > 0.f)) df[m * F + j] = 0.f; });
         __syncthreads();
-        TMARK(2);
         // ---- dW1 += df^T n (persistent MFMA tiles, waves 0-7) ; db1 partials (waves 12-15) ; dn = df . W1
         if (wave < 8) lds_mma_tile(accA, df, 1, F, nbuf, 1, SE, 16 * (wave >> 1), 16 * (wave & 1), L, lane);
         col_partials(redA, tid - 768, F, 4, L, [&](int l, int c) { return df[l * F + c]; });
         lds_mma(df, F, 1, w.W1, 1, SE, L, E, F, tid, [&](int m, int c, float v) { dn[m * SE + c] = v; });
         __syncthreads();
-        TMARK(3);
         // ---- LayerNorm backward: dgamma, dbeta partials (4 row groups x 64 columns), then dr in place (8 lanes per row)
         if (tid < F) a_b1 += col_total(redA, tid, F, 4);
         col_partials(redB, tid, 2 * E, 4, L, [&](int l, int c) {
@@ -439,17 +422,14 @@ __global__ __launch_bounds__(NT) void sheet_bwd_kernel(SheetDims dm, SheetParams
             }
         }
         __syncthreads();
-        TMARK(4);
         // ---- out-proj backward: dWo += dr^T o (waves 8-11) ; dbo partials (waves 0-1) ; dO = dr . Wo  (over xhat, which is dead)
         if (wave >= 8 && wave < 12) lds_mma_tile(accA, dn, 1, SE, o, 1, SE, 16 * ((wave - 8) >> 1), 16 * (wave & 1), L, lane);
         col_partials(redA, tid, E, 4, L, [&](int l, int c) { return dn[l * SE + c]; });
         lds_mma(dn, SE, 1, w.Wo, 1, SE, L, E, E, tid, [&](int m, int c, float v) { xh[m * SD + c] = v; });
         __syncthreads();                                     // n, df dead; o dead after the dWo loop above
-        TMARK(5);
         if (tid < E) a_bo += col_total(redA, tid, E, 4);
         ph_inproj(big, e, w, L, tid);                        // recompute qkv
         __syncthreads();
-        TMARK(6);
         // ---- attention backward, by ROW: delta = sum_j dA.A, dq      (dq -> `o` buffer)
         //      two adjacent lanes per (head, query row): keys split even/odd, combined with xor-1 shuffles
         for (int rr = tid; rr < 2 * H * L; rr += NT) {
@@ -497,7 +477,6 @@ __global__ __launch_bounds__(NT) void sheet_bwd_kernel(SheetDims dm, SheetParams
             }
         }
         __syncthreads();
-        TMARK(7);
         // ---- attention backward, by COLUMN: dk_j, dv_j; two lanes per (head, key), queries split even/odd.  The pair
         //      reads k_j, v_j into registers first and only then (after the shuffles) lane 0 overwrites them in place.
         for (int rr = tid; rr < 2 * H * L; rr += NT) {
@@ -531,7 +510,6 @@ __global__ __launch_bounds__(NT) void sheet_bwd_kernel(SheetDims dm, SheetParams
             }
         }
         __syncthreads();
-        TMARK(8);
         // ---- in-proj backward: dWin += dqkv^T e ; dbin partials (waves 8-11) ; de = dr + dqkv . Win   (de in place over dr)
         //      dqkv lives in two places: dq in `o` (columns 0..31), dk|dv in `big` (columns 32..95).
         //      The slab words this string's embedding gradient will be added to are fetched now and used after the barrier.
@@ -553,7 +531,6 @@ __global__ __launch_bounds__(NT) void sheet_bwd_kernel(SheetDims dm, SheetParams
         lds_mma(o, SE, 1, w.Win, 1, SE, L, E, E, tid, [&](int m, int c, float v) { dn[m * SE + c] += v; });
         lds_mma(big + E, SQ, 1, w.Win + E * SE, 1, SE, L, E, 2 * E, tid, [&](int m, int c, float v) { dn[m * SE + c] += v; });
         __syncthreads();
-        TMARK(9);
         // ---- dP += de ; dEmb[code] += sum over the code's occurrences of de * embed-dropout-mask.  The (first occurrence,
         //      channel) item owns the sum, walks the chain in position order and adds it to the block's slab in HBM/L2.
         if (tid < QKV) a_bin += col_total(redB, tid, QKV, 2);
@@ -578,10 +555,6 @@ __global__ __launch_bounds__(NT) void sheet_bwd_kernel(SheetDims dm, SheetParams
         }
         __syncthreads();
     }
-    TMARK(10);
-#ifdef AFR_SHEET_TIMING
-    if (blockIdx.x == 0 && tid0 == 0) { printf("sheet_bwd phases (x10ns):"); for (int k = 0; k < 12; ++k) printf(" %lld", tacc[k]); printf("\n"); }
-#endif
     // ---- one partial slab per block, laid out like the flat parameter buffer (pads were zeroed by the host memset)
     const int tid = tid0, c32 = tid & 31, g8 = tid >> 5, wave = tid >> 6, lane = tid & 63;
     float* S = Sblk;

@@ -64,8 +64,7 @@ typedef struct afr_config {
                             bit 1: one launch per product in backward (no grouped dW+dX launches): A/B measurements
                             bit 2: small one-hidden-layer glyph nets through the generic per-layer kernels instead of
                             the fused whole-step kernel of afr_train_step (A/B measurements, parity cross-checks)
-                            bit 3: OPT IN to in-launch split-K (afr_op_gemm_fix) for the sheet model's fc_output products
-                            that have no fused loss / optimizer tail (today: the input gradient)
+                            bit 3: unused
                             bit 4: the glyph nets' folded first layer backward through the weight-gradient GEMM + post-pass
                             instead of the fused kernel (A/B measurements, parity cross-checks)
                             bit 5: weight gradients of grouped 256x256 launches as split-K partial slabs summed by the grouped
@@ -202,7 +201,7 @@ int afr_op_gemm(int dtype, int flags, const void* A, const void* B, void* C, con
  * gradient: 100 tiles cut 2 ways).  Measured on R0's input gradient (1024 x 6400 x 19200): 220 us against the 128x128
  * kernel's 276 us with the weight operand warm in the infinity cache, but 343 us against 281 us inside a training step,
  * where the 246 MB weight shadow streams from HBM and one 160-KiB workgroup per CU hides that latency worse than two
- * 64-KiB ones -- so afr_train_step uses it only when config.reserved bit 3 asks for it.  workspace: afr_op_gemm_fix_workspace_bytes() bytes, 16-byte
+ * 64-KiB ones -- so afr_train_step does not use it.  workspace: afr_op_gemm_fix_workspace_bytes() bytes, 16-byte
  * aligned, whose trailing counter words (one per tail tile) are ZERO before the first call; the kernel leaves them zero. */
 size_t afr_op_gemm_fix_workspace_bytes(int M, int N, int head_tiles, int splitk);
 int afr_op_gemm_fix(int flags, const void* A, const void* B, void* C, const float* bias, const void* aux,

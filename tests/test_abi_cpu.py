@@ -96,3 +96,18 @@ def test_grouped_reduce_refuses_more_segments_than_it_can_hold():
     ln = (C.c_int64 * n)(*[64] * n)
     assert lib.afr_op_reduce_group(n, ptrs, ptrs, ns, st, ln, None) == -1      # AFR_EINVAL
     assert b"at most 32" in lib.afr_last_error()
+
+
+def test_library_sources_read_no_environment_and_keep_one_build_switch():
+    """Kernel selection depends on the shapes and config.reserved only: the library reads no environment variables, and
+    the one build-time switch left is the GEMM timeline instrumentation (-DAFR_GEMM_TIMING, tools/gemm_timeline.py)."""
+    csrc = os.path.join(ROOT, "ai-font-renderer_amd", "csrc")
+    sources = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h", ".hpp", ".cpp", ".cc", ".c")))
+    assert "gemm.hip" in sources and "afr_api.hip" in sources
+    symbols = set()
+    for f in sources:
+        src = open(os.path.join(csrc, f)).read()
+        assert not re.search(r"\bgetenv\s*\(", src), f"{f} calls getenv"
+        for cond in re.findall(r"^\s*#\s*(?:if|ifdef|ifndef|elif|elifdef|elifndef)\b(.*)$", src, flags=re.M):
+            symbols |= set(re.findall(r"[A-Za-z_]\w*", cond)) - {"defined"}
+    assert symbols == {"AFR_GEMM_TIMING"}, symbols

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-K-tile slope and fixed cost of afr_op_gemm at a given M x N: times K = 256 .. 4096, hot (back to back) and cold
 (a 256 MiB buffer rewritten and A re-written between launches, single launches bracketed by events).
-usage: python tools/gemm_ksweep.py M N [lay] [variant]"""
+usage: python tools/gemm_ksweep.py M N [lay]"""
 import ctypes as C
 import os
 import sys
@@ -14,12 +14,9 @@ from ai_font_renderer_amd import _lib  # noqa: E402
 
 M, N = int(sys.argv[1]), int(sys.argv[2])
 lay = sys.argv[3] if len(sys.argv) > 3 else "-"
-variant = int(sys.argv[4]) if len(sys.argv) > 4 else None
 lib = C.CDLL(_lib.LIB_PATH)
 lib.afr_op_gemm.restype = C.c_int
 lib.afr_op_gemm.argtypes = _lib.SIGNATURES["afr_op_gemm"][1]
-if variant is not None:
-    lib.afr_dbg_set_gemm_variant(variant)
 ak, bk = "a" in lay, "b" in lay
 st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 p = lambda t: C.c_void_p(t.data_ptr())
