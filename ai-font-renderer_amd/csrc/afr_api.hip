@@ -57,7 +57,8 @@ struct Tensor {
 struct ProfRec { int tag; hipEvent_t a, b; double flops, bytes; };
 
 struct afr_plan {
-    afr_config cfg;
+    afr_config cfg;                // cfg.dtype is the ACTIVATION dtype (AFR_F32 or AFR_BF16) every non-GEMM kernel runs in
+    int gemm_dtype = AFR_F32;      // the dtype run_gemm launches its products in: cfg.dtype, or AFR_BF16X3 over f32 activations
     std::vector<Tensor> params;
     int64_t total = 0;
     int act_bytes = 4;
@@ -170,13 +171,20 @@ static int choose_splitk(int M, int N, int K) {
 
 extern "C" int afr_plan_create(const afr_config* c, afr_plan** out) {
     if (!c || !out) return fail(AFR_EINVAL, "null argument");
-    if (c->dtype != AFR_F32 && c->dtype != AFR_BF16) return fail(AFR_EINVAL, "dtype must be AFR_F32 or AFR_BF16");
+    if (c->dtype != AFR_F32 && c->dtype != AFR_BF16 && c->dtype != AFR_BF16X3)
+        return fail(AFR_EINVAL, "dtype must be AFR_F32, AFR_BF16 or AFR_BF16X3");
+    // AFR_BF16X3 is the f32 plan (activations, layout, workspace, every non-GEMM kernel) whose products run bf16x3
+    afr_config cf = *c;
+    const int gemm_dtype = cf.dtype;
+    if (cf.dtype == AFR_BF16X3) cf.dtype = AFR_F32;
+    c = &cf;
     if (c->max_batch <= 0) return fail(AFR_EINVAL, "max_batch must be positive");
     if (c->vocab <= 0 || c->embed_dim <= 0 || c->out_h <= 0 || c->out_w <= 0) return fail(AFR_EINVAL, "bad shape");
     const int Pix = c->out_h * c->out_w;
     if (Pix % 8) return fail(AFR_EUNSUPPORTED, "out_h*out_w must be a multiple of 8 (got %d)", Pix);
     afr_plan* p = new afr_plan();
     p->cfg = *c;
+    p->gemm_dtype = gemm_dtype;
     p->act_bytes = c->dtype == AFR_BF16 ? 2 : 4;
     const int E = c->embed_dim;
     const size_t B = (size_t)c->max_batch;
@@ -588,7 +596,8 @@ static int run_gemm(afr_plan* p, hipStream_t s, int flags, const void* A, const 
                     const void* aux, int M, int N, int K, int lda, int ldb, int ldc, int ldaux, int splitk,
                     long long slab_stride, float* colsum = nullptr, long long colsum_stride = 0, const FusedLoss* fl = nullptr,
                     const FusedAdam* fa = nullptr, const CoopArgs* coop = nullptr, const RowMaps* rm = nullptr) {
-    if (p->cfg.dtype == AFR_BF16) {
+    const int gdt = p->gemm_dtype;
+    if (gdt == AFR_BF16) {
         const bool ak = flags & AFR_GEMM_A_KSTRIDED, bk = flags & AFR_GEMM_B_KSTRIDED;
         const long long ea = (long long)(ak ? K : M) * lda * 2, ebb = (long long)(bk ? K : N) * ldb * 2;
         if (ea >= (1ll << 31) || ebb >= (1ll << 31)) return fail(AFR_EUNSUPPORTED, "bf16 GEMM operand of 2 GiB or more (%lld / %lld bytes)", ea, ebb);
@@ -609,7 +618,7 @@ static int run_gemm(afr_plan* p, hipStream_t s, int flags, const void* A, const 
     g.A = A; g.B = B; g.C = C; g.bias = bias; g.aux = aux;
     g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldaux = ldaux;
     g.flags = flags; g.splitk = splitk; g.slab_stride = slab_stride;
-    const double eb = p->cfg.dtype == AFR_BF16 ? 2.0 : 4.0;
+    const double eb = gdt == AFR_BF16 ? 2.0 : 4.0;
     const double ob = (flags & AFR_GEMM_OUT_BF16) ? 2.0 : 4.0;
     // algorithmic bytes: operands once + the product once (split-K partial slabs are an implementation choice, not
     // algorithmic output); with the fused optimizer the output is p,m,v read + p,m,v(,shadow) written
@@ -617,21 +626,21 @@ static int run_gemm(afr_plan* p, hipStream_t s, int flags, const void* A, const 
     char tag[96];
     const double fl_ = 2.0 * M * (double)N * K, by_ = eb * ((double)M * K + (double)N * K) + out_bytes;
     {
-        const char* kn = afr_gemm_kernel_name(p->cfg.dtype, g);
+        const char* kn = afr_gemm_kernel_name(gdt, g);
         if (strcmp(kn, "gemm_bf16_group256") == 0)     // a plain product on the 256x256 body: the operand orientation follows the shape
             snprintf(tag, sizeof tag, "%s[%dx%dx%d]<%d,%d>", kn, M, N, K, (flags & AFR_GEMM_A_KSTRIDED) ? 1 : 0, (flags & AFR_GEMM_B_KSTRIDED) ? 1 : 0);
         else snprintf(tag, sizeof tag, "%s[%dx%dx%d]", kn, M, N, K);
     }
-    if (coop && !(p->defer && p->pend_tile256 && p->pend.empty() && afr_gemm_groupable(p->cfg.dtype, g)))
+    if (coop && !(p->defer && p->pend_tile256 && p->pend.empty() && afr_gemm_groupable(gdt, g)))
         return fail(AFR_ESTATE, "cooperative split-K product outside a 256x256 grouped launch");
-    if (rm && rm->b && !(p->defer && p->pend_tile256 && afr_gemm_groupable(p->cfg.dtype, g)))
+    if (rm && rm->b && !(p->defer && p->pend_tile256 && afr_gemm_groupable(gdt, g)))
         return fail(AFR_ESTATE, "gathered k-strided operand outside a 256x256 grouped launch");
-    if (p->defer && afr_gemm_groupable(p->cfg.dtype, g) && p->pend.size() < 4) {
+    if (p->defer && afr_gemm_groupable(gdt, g) && p->pend.size() < 4) {
         p->pend.push_back(g); p->pend_tag.push_back(tag); p->pend_flops += fl_; p->pend_bytes += by_;
         return AFR_OK;
     }
     ProfScope ps(p, s, tag, fl_, by_);
-    HIPCHK(afr_launch_gemm(p->cfg.dtype, g, s));
+    HIPCHK(afr_launch_gemm(gdt, g, s));
     return AFR_OK;
 }
 // forget what run_gemm collected (after its launch, or when a call fails before it)
@@ -653,7 +662,7 @@ static int flush_gemms(afr_plan* p, hipStream_t s) {
     hipError_t e;
     {
         ProfScope ps(p, s, tag.c_str(), p->pend_flops, p->pend_bytes);
-        e = afr_launch_gemm_group(p->cfg.dtype, p->pend.data(), (int)p->pend.size(), p->pend_tile256, s);
+        e = afr_launch_gemm_group(p->gemm_dtype, p->pend.data(), (int)p->pend.size(), p->pend_tile256, s);
     }
     // the launch carries the cooperative member's arrivals: the host count follows only once it is enqueued
     if (e == hipSuccess && p->pend_arrived) *p->pend_arrived = p->pend[0].coop_target;
@@ -1513,6 +1522,8 @@ extern "C" int afr_op_gemm(int dtype, int flags, const void* A, const void* B, v
                            int M, int N, int K, int lda, int ldb, int ldc, int ldaux, int splitk, void* stream) {
     if (!A || !B || !C) return fail(AFR_EINVAL, "null operand");
     if (M <= 0 || N <= 0 || K <= 0 || splitk < 1) return fail(AFR_EINVAL, "bad GEMM extents");
+    if (dtype != AFR_F32 && dtype != AFR_BF16 && dtype != AFR_BF16X3) return fail(AFR_EINVAL, "dtype must be AFR_F32, AFR_BF16 or AFR_BF16X3");
+    if (dtype == AFR_BF16X3 && (flags & AFR_GEMM_OUT_BF16)) return fail(AFR_EINVAL, "AFR_BF16X3 products have an f32 output (no AFR_GEMM_OUT_BF16)");
     const int v = dtype == AFR_BF16 ? 8 : 4;
     const bool ak = flags & AFR_GEMM_A_KSTRIDED, bk = flags & AFR_GEMM_B_KSTRIDED;
     if ((ak ? M : K) % v || (bk ? N : K) % v || lda % v || ldb % v || N % v || ldc % v)

@@ -8,9 +8,10 @@
 //   input grad dx = dy . W      A = dy [M][N]  k-contiguous,  B = W  [n][k'] : reduction index is the ROW -> B k-strided
 //   weight grad dW = dy^T . x   A = dy [m][n]  k-strided,     B = x  [m][k'] k-strided (reduction over the batch)
 //
-// Two operand types:
-//   f32   v_mfma_f32_32x32x2_f32  : exact f32 (one rounding per product, k-ordered fma chain) -- the parity mode
-//   bf16  v_mfma_f32_16x16x32_bf16: bf16 operands, f32 accumulation -- the throughput mode
+// Three operand types:
+//   f32    v_mfma_f32_32x32x2_f32  : exact f32 (one rounding per product, k-ordered fma chain) -- the parity mode
+//   bf16x3 v_mfma_f32_32x32x16_bf16: f32 operands split into bf16 hi + lo, three MFMAs per product -- the fast parity mode
+//   bf16   v_mfma_f32_16x16x32_bf16: bf16 operands, f32 accumulation -- the throughput mode
 // Tile 128x128 per 256-thread workgroup (4 waves as 2x2, 64x64 per wave), double-buffered LDS, one barrier per
 // K-tile.  bf16: tiles go global -> LDS by LDS-DMA (buffer_load ... lds: no VGPR staging, no ds_write -- ds_write
 // bandwidth was the measured limiter of the register-staged version), tile t+1 in flight during the MFMAs on t.
@@ -110,6 +111,72 @@ __device__ __forceinline__ void store_tile(float* S, int tid, const float4 (&r)[
     }
 }
 
+// The epilogue of the 128x128 tile shared by gemm_f32 and gemm_bf16x3 (both keep f32x16 acc[2][2] of 32x32 MFMA results,
+// whose accumulator layout is the same for v_mfma_f32_32x32x2_f32 and v_mfma_f32_32x32x16_bf16).
+// Bias-gradient column sums: part q of column x (q < nparts, x < 128) sits at smem[q * 128 + x]; summed in part order.
+__device__ __forceinline__ void colsum_store(const GemmParams& p, float* smem, const int tid, const int m0, const int z, const int nparts) {
+    __syncthreads();
+    if (tid < 128 && m0 + tid < p.M) {
+        float s = smem[tid];
+        for (int q = 1; q < nparts; ++q) s += smem[q * 128 + tid];
+        p.colsum[(size_t)z * p.colsum_stride + m0 + tid] = s;
+    }
+}
+// bias, ReLU, ReLU mask, split-K slabs, bf16 output, fused clamp/MSE/du, fused AdamW; smem: >= 16 + 256 floats of scratch
+__device__ __forceinline__ void tile_epilogue(const GemmParams& p, const f32x16 (&acc)[2][2], const int m0, const int n0, const int z,
+                                              const int tid, float* smem) {
+    const int lane = tid & 63, wid = tid >> 6;
+    const int wm = wid >> 1, wn = wid & 1;
+    // epilogue: D[row = (r&3) + 8*(r>>2) + 4*(lane>>5)][col = lane&31]; rows are m, columns n
+    const int flags = p.flags;
+    const bool out_bf16 = flags & AFR_GEMM_OUT_BF16;
+    const bool mse = p.mse_target != nullptr;
+    float* Cf = reinterpret_cast<float*>(p.C) + (size_t)z * p.slab_stride;
+    bf16_t* Cb = reinterpret_cast<bf16_t*>(p.C);
+    const float* aux = reinterpret_cast<const float*>(p.aux);
+    float lsum = 0.f;
+    const float g2 = 2.f * p.mse_inv_n;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int n = n0 + wn * 64 + j * 32 + (lane & 31);
+            if (n >= p.N) continue;
+            const float bias = (flags & AFR_GEMM_BIAS) ? p.bias[n] : 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                if (m >= p.M) continue;
+                float v = acc[i][j][r] + bias;
+                if (flags & AFR_GEMM_RELU) v = fmaxf(v, 0.f);
+                if (flags & AFR_GEMM_RELU_MASK) v = (aux[(size_t)m * p.ldaux + n] > 0.f) ? v : 0.f;
+                if (mse) {
+                    if (out_bf16) v = (float)(bf16_t)v;
+                    const size_t ti = (size_t)m * p.N + n;
+                    const float t = p.mse_target_dtype == AFR_TARGET_U8 ? (float)reinterpret_cast<const uint8_t*>(p.mse_target)[ti] / 255.0f
+                                                                        : reinterpret_cast<const float*>(p.mse_target)[ti];
+                    const float diff = fminf(fmaxf(v, 0.f), 1.f) - t;
+                    lsum += diff * diff;
+                    v = (v >= 0.f && v <= 1.f) ? g2 * diff : 0.f;
+                }
+                if (p.ad_p) {                          // fused AdamW on weight element (m, n); v is its gradient
+                    const size_t wi = (size_t)m * p.ldc + n;
+                    float pp = p.ad_p[wi], mm = p.ad_m[wi], vv = p.ad_v[wi];
+                    adamw_elem(pp, mm, vv, v, p.ad_decay, p.ad_b1, p.ad_b2, p.ad_eps, p.ad_step, p.ad_rsqrt_bc2);
+                    p.ad_p[wi] = pp; p.ad_m[wi] = mm; p.ad_v[wi] = vv;
+                } else if (out_bf16) Cb[(size_t)m * p.ldc + n] = f32_to_bf16(v);
+                else Cf[(size_t)m * p.ldc + n] = v;
+            }
+        }
+    if (mse) {
+        __syncthreads();
+        lsum = wave_sum(lsum);
+        if (lane == 0) smem[wid] = lsum;
+        __syncthreads();
+        loss_block_finish((smem[0] + smem[1]) + (smem[2] + smem[3]), p.mse_partial, p.mse_counter, p.mse_loss_accum, p.mse_inv_n, smem + 16);
+    }
+}
+
 template <int ALAY, int BLAY>
 __global__ __launch_bounds__(256) void gemm_f32(GemmParams p) {
     constexpr int LDA = Lds<ALAY>::LD, LDB = Lds<BLAY>::LD;
@@ -182,59 +249,175 @@ __global__ __launch_bounds__(256) void gemm_f32(GemmParams p) {
 
     if (ALAY == 1 && do_cs) {
         smem[tid] = cs;
-        __syncthreads();
-        if (tid < 128 && m0 + tid < p.M) p.colsum[(size_t)z * p.colsum_stride + m0 + tid] = smem[tid] + smem[tid + 128];
+        colsum_store(p, smem, tid, m0, z, 2);
     }
-    // epilogue: D[row = (r&3) + 8*(r>>2) + 4*(lane>>5)][col = lane&31]; rows are m, columns n
-    const int flags = p.flags;
-    const bool out_bf16 = flags & AFR_GEMM_OUT_BF16;
-    const bool mse = p.mse_target != nullptr;
-    float* Cf = reinterpret_cast<float*>(p.C) + (size_t)z * p.slab_stride;
-    bf16_t* Cb = reinterpret_cast<bf16_t*>(p.C);
-    const float* aux = reinterpret_cast<const float*>(p.aux);
-    float lsum = 0.f;
-    const float g2 = 2.f * p.mse_inv_n;
+    tile_epilogue(p, acc, m0, n0, z, tid, smem);
+}
+}  // namespace f32k
+
+// ---------------------------------------------------------------------------------------- bf16x3
+// f32 operands split at staging as x = hi + lo, hi = bf16(x), lo = bf16(x - hi) (x - hi is exact in f32), and the product
+// taken as lo.hi + hi.lo + hi.hi by three v_mfma_f32_32x32x16_bf16 into one f32 accumulator (lo.lo, <= 2^-16 |ab|, is
+// dropped).  Same 128x128 tile, 4 waves of 64x64, acc[2][2] and epilogue as gemm_f32.  BK = 32, two LDS stages of 32 KiB
+// (2 workgroups per CU); register staging, since the split sits between the global load and the LDS write: tile t+1 is
+// written AFTER the barrier that ends tile t-1's MFMAs and tile t+3's loads are issued right behind that write (two
+// register sets, so that a load has two K-tiles of MFMAs to land).
+// LDS image of one operand plane: [128 x][32 k] bf16, 64-byte rows; row x sits at x ^ ((x >> 2) & 3) and its 16-byte chunk
+// c at c ^ ((x >> 2) & 3), so that the MFMA reads (16 lanes = 16 rows, one chunk) and the staging writes of either
+// orientation (4 rows x 64 B per 32 lanes) are bank-conflict free.
+namespace x3k {
+constexpr int BM = 128, BN = 128, BK = 32;
+constexpr int PLANE = 128 * BK * 2;          // 8 KiB: hi or lo of one operand tile
+constexpr int STAGE = 4 * PLANE;             // A hi, A lo, B hi, B lo
+
+__device__ __forceinline__ int xoff(int x, int c) {
+    const int s = (x >> 2) & 3;
+    return 64 * (x ^ s) + 16 * (c ^ s);
+}
+__device__ __forceinline__ void split4(float a, float b, float c, float d, bf16x4& hi, bf16x4& lo) {
+    hi[0] = (bf16_t)a; hi[1] = (bf16_t)b; hi[2] = (bf16_t)c; hi[3] = (bf16_t)d;
+    lo[0] = (bf16_t)(a - (float)hi[0]); lo[1] = (bf16_t)(b - (float)hi[1]);
+    lo[2] = (bf16_t)(c - (float)hi[2]); lo[3] = (bf16_t)(d - (float)hi[3]);
+}
+// global -> registers, 4 float4 per thread, branch-free (an element outside the operand loads from a clamped address and
+// is replaced by 0).  LAY 0 ([x][k] in memory): float4 i = row idx >> 3, k 4 (idx & 7) with idx = tid + 256 i.  LAY 1 ([k][x]):
+// thread (kq = tid & 7, xc = tid >> 3) takes k rows 4 kq + i of columns 4 xc .. 4 xc + 3 (a wave reads 8 rows x 128 contiguous
+// bytes per load), so that it holds 4 consecutive k of each of its columns.  X and kend are multiples of 4 where contiguous.
+template <int LAY>
+__device__ __forceinline__ void load_tile(const float* __restrict__ G, int ld, int X, int x0, int k0, int kend, int tid, float4 (&r)[4]) {
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        int gx, gk;
+        if (LAY == 0) { const int idx = tid + 256 * i; gx = x0 + (idx >> 3); gk = k0 + 4 * (idx & 7); }
+        else { gx = x0 + 4 * (tid >> 3); gk = k0 + 4 * (tid & 7) + i; }
+        const bool ok = gx < X && gk < kend;
+        const int cx = min(gx, LAY == 0 ? X - 1 : X - 4), ck = min(gk, LAY == 0 ? kend - 4 : kend - 1);
+        const float4 v = LAY == 0 ? *reinterpret_cast<const float4*>(G + (size_t)cx * ld + ck)
+                                  : *reinterpret_cast<const float4*>(G + (size_t)ck * ld + cx);
+        r[i] = ok ? v : zero;
+    }
+}
+// registers -> the hi and lo planes (8 bytes = 4 k of one row per ds_write_b64)
+template <int LAY>
+__device__ __forceinline__ void store_tile(char* Shi, char* Slo, int tid, const float4 (&r)[4]) {
+    bf16x4 hi, lo;
+    if (LAY == 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int idx = tid + 256 * i, row = idx >> 3, kc = idx & 7;
+            const int o = xoff(row, kc >> 1) + 8 * (kc & 1);
+            split4(r[i].x, r[i].y, r[i].z, r[i].w, hi, lo);
+            *reinterpret_cast<bf16x4*>(Shi + o) = hi;
+            *reinterpret_cast<bf16x4*>(Slo + o) = lo;
+        }
+    } else {
+        const int kq = tid & 7, xb = 4 * (tid >> 3);
+#define X3_COL(e, comp) do { const int o = xoff(xb + e, kq >> 1) + 8 * (kq & 1); \
+                             split4(r[0].comp, r[1].comp, r[2].comp, r[3].comp, hi, lo); \
+                             *reinterpret_cast<bf16x4*>(Shi + o) = hi; *reinterpret_cast<bf16x4*>(Slo + o) = lo; } while (0)
+        X3_COL(0, x); X3_COL(1, y); X3_COL(2, z); X3_COL(3, w);
+#undef X3_COL
+    }
+}
+// fragment of the 32x32x16 MFMA: lane holds X(x = xb + (lane & 31), k = 16 ks + 8 (lane >> 5) + j), j = 0..7
+__device__ __forceinline__ bf16x8 frag(const char* S, int xb, int ks, int lane) {
+    return *reinterpret_cast<const bf16x8*>(S + xoff(xb + (lane & 31), 2 * ks + (lane >> 5)));
+}
+
+template <int ALAY, int BLAY>
+__global__ __launch_bounds__(256, 2) void gemm_bf16x3(GemmParams p) {
+    __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wm = wid >> 1, wn = wid & 1;
+    int tm, tn, z;
+    tile_of_block(p, BM, BN, blockIdx.x, gridDim.x, tm, tn, z);
+    const int m0 = tm * BM, n0 = tn * BN;
+    const int klen = ((p.K + p.splitk - 1) / p.splitk + BK - 1) / BK * BK;
+    const int kbeg = z * klen;
+    const int kend = min(p.K, kbeg + klen);
+    const float* A = reinterpret_cast<const float*>(p.A);
+    const float* B = reinterpret_cast<const float*>(p.B);
+
+    f32x16 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int n = n0 + wn * 64 + j * 32 + (lane & 31);
-            if (n >= p.N) continue;
-            const float bias = (flags & AFR_GEMM_BIAS) ? p.bias[n] : 0.f;
+        for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (m >= p.M) continue;
-                float v = acc[i][j][r] + bias;
-                if (flags & AFR_GEMM_RELU) v = fmaxf(v, 0.f);
-                if (flags & AFR_GEMM_RELU_MASK) v = (aux[(size_t)m * p.ldaux + n] > 0.f) ? v : 0.f;
-                if (mse) {
-                    if (out_bf16) v = (float)(bf16_t)v;
-                    const size_t ti = (size_t)m * p.N + n;
-                    const float t = p.mse_target_dtype == AFR_TARGET_U8 ? (float)reinterpret_cast<const uint8_t*>(p.mse_target)[ti] / 255.0f
-                                                                        : reinterpret_cast<const float*>(p.mse_target)[ti];
-                    const float diff = fminf(fmaxf(v, 0.f), 1.f) - t;
-                    lsum += diff * diff;
-                    v = (v >= 0.f && v <= 1.f) ? g2 * diff : 0.f;
-                }
-                if (p.ad_p) {                          // fused AdamW on weight element (m, n); v is its gradient
-                    const size_t wi = (size_t)m * p.ldc + n;
-                    float pp = p.ad_p[wi], mm = p.ad_m[wi], vv = p.ad_v[wi];
-                    adamw_elem(pp, mm, vv, v, p.ad_decay, p.ad_b1, p.ad_b2, p.ad_eps, p.ad_step, p.ad_rsqrt_bc2);
-                    p.ad_p[wi] = pp; p.ad_m[wi] = mm; p.ad_v[wi] = vv;
-                } else if (out_bf16) Cb[(size_t)m * p.ldc + n] = f32_to_bf16(v);
-                else Cf[(size_t)m * p.ldc + n] = v;
-            }
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    // fused bias gradient: column sums of the A tiles, from the f32 values before the split (A k-strided: the thread's
+    // 4 columns over its 4 k rows per tile; part kq of the column sums)
+    const bool do_cs = (ALAY == 1) && p.colsum != nullptr && tn == 0;
+    float cs[4] = {0.f, 0.f, 0.f, 0.f};
+    const int nt = (kend > kbeg) ? (kend - kbeg + BK - 1) / BK : 0;
+    auto colsum_add = [&](const float4 (&ra)[4]) {
+        if (ALAY == 1 && do_cs) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { cs[0] += ra[i].x; cs[1] += ra[i].y; cs[2] += ra[i].z; cs[3] += ra[i].w; }
         }
-    if (mse) {
-        __syncthreads();
-        lsum = wave_sum(lsum);
-        if (lane == 0) smem[wid] = lsum;
-        __syncthreads();
-        loss_block_finish((smem[0] + smem[1]) + (smem[2] + smem[3]), p.mse_partial, p.mse_counter, p.mse_loss_accum, p.mse_inv_n, smem + 16);
+    };
+    auto load = [&](int t, float4 (&ra)[4], float4 (&rb)[4]) {
+        load_tile<ALAY>(A, p.lda, p.M, m0, kbeg + t * BK, kend, tid, ra);
+        load_tile<BLAY>(B, p.ldb, p.N, n0, kbeg + t * BK, kend, tid, rb);
+    };
+    auto store = [&](char* S, const float4 (&ra)[4], const float4 (&rb)[4]) {
+        colsum_add(ra);
+        store_tile<ALAY>(S, S + PLANE, tid, ra);
+        store_tile<BLAY>(S + 2 * PLANE, S + 3 * PLANE, tid, rb);
+    };
+    // two register sets: set (t & 1) holds tile t+1 while the MFMAs run on tile t, so a load has two K-tiles of MFMAs to land
+    float4 ra0[4], rb0[4], ra1[4], rb1[4];
+    if (nt > 0) {
+        load(0, ra0, rb0);
+        store(smem, ra0, rb0);
+        if (nt > 1) load(1, ra0, rb0);
+        if (nt > 2) load(2, ra1, rb1);
     }
+    __syncthreads();
+    auto ktile = [&](int t, float4 (&ra)[4], float4 (&rb)[4]) {
+        if (t + 1 < nt) {        // tile t+1: registers -> the stage tile t-1 used (its reads ended at the last barrier)
+            store(smem + ((t + 1) & 1) * STAGE, ra, rb);
+            if (t + 3 < nt) load(t + 3, ra, rb);
+        }
+        const char* S = smem + (t & 1) * STAGE;
+#pragma unroll
+        for (int ks = 0; ks < BK / 16; ++ks) {
+            bf16x8 ah[2], al[2], bh[2], bl[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                ah[i] = frag(S, wm * 64 + 32 * i, ks, lane);
+                al[i] = frag(S + PLANE, wm * 64 + 32 * i, ks, lane);
+                bh[i] = frag(S + 2 * PLANE, wn * 64 + 32 * i, ks, lane);
+                bl[i] = frag(S + 3 * PLANE, wn * 64 + 32 * i, ks, lane);
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+                }
+        }
+        __syncthreads();
+    };
+    for (int t = 0; t < nt; t += 2) {
+        ktile(t, ra0, rb0);
+        if (t + 1 < nt) ktile(t + 1, ra1, rb1);
+    }
+
+    float* sf = reinterpret_cast<float*>(smem);
+    if (ALAY == 1 && do_cs) {
+        const int kq = tid & 7, xb = 4 * (tid >> 3);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sf[kq * 128 + xb + e] = cs[e];
+        f32k::colsum_store(p, sf, tid, m0, z, 8);
+    }
+    f32k::tile_epilogue(p, acc, m0, n0, z, tid, sf);
 }
-}  // namespace f32k
+}  // namespace x3k
 
 // ------------------------------------------------------------------------------------------ bf16
 namespace bf16k {
@@ -1763,6 +1946,8 @@ const char* afr_gemm_kernel_name(int dtype, const GemmParams& p) {
     static const char* f32n[2][2] = {{"gemm_f32<0,0>", "gemm_f32<0,1>"}, {"gemm_f32<1,0>", "gemm_f32<1,1>"}};
     static const char* bfn[2][2][2] = {{{"gemm_bf16<0,0,2>", "gemm_bf16<0,0,4>"}, {"gemm_bf16<0,1,2>", "gemm_bf16<0,1,4>"}},
                                        {{"gemm_bf16<1,0,2>", "gemm_bf16<1,0,4>"}, {"gemm_bf16<1,1,2>", "gemm_bf16<1,1,4>"}}};
+    static const char* x3n[2][2] = {{"gemm_bf16x3<0,0>", "gemm_bf16x3<0,1>"}, {"gemm_bf16x3<1,0>", "gemm_bf16x3<1,1>"}};
+    if (dtype == AFR_BF16X3) return x3n[a][b];
     if (dtype != AFR_BF16) return f32n[a][b];
     if (bf16_use_body256(p)) return "gemm_bf16_group256";
     return bfn[a][b][bf16_use_wide(p) ? 1 : 0];
@@ -1868,6 +2053,15 @@ hipError_t afr_launch_gemm(int dtype, const GemmParams& p_in, hipStream_t s) {
         else if (a && !b) LB(1, 0);
         else LB(1, 1);
 #undef LB
+    } else if (dtype == AFR_BF16X3) {
+        const int tiles = ((p.M + x3k::BM - 1) / x3k::BM) * ((p.N + x3k::BN - 1) / x3k::BN);
+        dim3 grid(tiles * p.splitk, 1, 1), block(256, 1, 1);
+#define LX(AL, BL) hipLaunchKernelGGL((x3k::gemm_bf16x3<AL, BL>), grid, block, 0, s, p)
+        if (!a && !b) LX(0, 0);
+        else if (!a && b) LX(0, 1);
+        else if (a && !b) LX(1, 0);
+        else LX(1, 1);
+#undef LX
     } else {
         const int tiles = ((p.M + 127) / 128) * ((p.N + 127) / 128);
         dim3 grid(tiles * p.splitk, 1, 1), block(256, 1, 1);

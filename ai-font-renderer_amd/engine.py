@@ -12,7 +12,8 @@ import torch
 from . import _lib
 from .config import GlyphConfig, PixelConfig, SheetConfig
 
-_DT = {"f32": _lib.AFR_F32, "fp32": _lib.AFR_F32, "float32": _lib.AFR_F32, "bf16": _lib.AFR_BF16, "bfloat16": _lib.AFR_BF16}
+_DT = {"f32": _lib.AFR_F32, "fp32": _lib.AFR_F32, "float32": _lib.AFR_F32, "bf16": _lib.AFR_BF16, "bfloat16": _lib.AFR_BF16,
+       "bf16x3": _lib.AFR_BF16X3}
 
 
 def _ptr(t):

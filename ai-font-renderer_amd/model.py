@@ -14,7 +14,8 @@ What is deliberately different from the reference, and why:
     shuffle order reproduce random_split / DataLoader(shuffle=True, generator=g) draw for draw (_EpochOrder);
   * loss.item() per step (model.py:311) becomes one device->host read per epoch (the loss accumulates on device);
   * dropout uses a counter-hash stream instead of torch's bernoulli_ stream (same rates, same placement);
-  * AFR_DTYPE=bf16 selects the throughput mode (bf16 MFMA operands); the default f32 mode is the parity mode.
+  * AFR_DTYPE=bf16 selects the throughput mode (bf16 MFMA operands); the default f32 mode is the parity mode, and
+    AFR_DTYPE=bf16x3 the fast parity mode (f32 except that every Linear product runs as three split-bf16 MFMAs).
 """
 import datetime
 import os

@@ -32,7 +32,13 @@ enum { AFR_KIND_SHEET = 0,   /* AttentionFontRenderer, model.py:129-204         
                                 (<= 512, = 64 * heads), fc_dim = ff width, n_hidden = blocks, out_h * out_w = pixel tokens.
                                 Every entry point serves it; one backward stage per block, last block first.                */
 enum { AFR_F32 = 0,          /* exact-f32 MFMA everywhere: parity mode (<=1e-4 vs reference)     */
-       AFR_BF16 = 1 };       /* bf16 MFMA operands, f32 accumulate, f32 master weights           */
+       AFR_BF16 = 1,         /* bf16 MFMA operands, f32 accumulate, f32 master weights           */
+       AFR_BF16X3 = 2 };     /* AFR_F32 except that every Linear product (afr_op_gemm and the plan's GEMMs) runs as
+                                three bf16 MFMAs on operands split x = hi + lo at staging, f32 accumulate: per product
+                                term <= 3*2^-16 relative error, with a 2.5 PF / 3 = 833 TF matrix ceiling against the f32
+                                MFMA's 157 TF (DESIGN.md 4 has the measured steps).  f32 activations, memory layout, parameter table
+                                and workspace of the AFR_F32 plan; the non-GEMM kernels (sheet front end, fused
+                                small glyph net, pixel token kernels) run their exact-f32 path. */
 enum { AFR_TARGET_U8 = 0,    /* 8-bit pixels as stored in the BMPs; k/255.0f on device           */
        AFR_TARGET_F32 = 1 }; /* float32 targets as helpers.load_string_dataset returns them      */
 
@@ -40,7 +46,7 @@ enum { AFR_TARGET_U8 = 0,    /* 8-bit pixels as stored in the BMPs; k/255.0f on 
 
 typedef struct afr_config {
     int32_t kind;        /* AFR_KIND_*                                                            */
-    int32_t dtype;       /* AFR_F32 | AFR_BF16                                                    */
+    int32_t dtype;       /* AFR_F32 | AFR_BF16 | AFR_BF16X3                                       */
     int32_t max_batch;   /* largest B any call will pass                                          */
     int32_t vocab;       /* embedding rows (128, model.py:136)                                    */
     int32_t embed_dim;   /* EMBEDDING_DIM (32, model.py:79)                                       */
@@ -187,7 +193,8 @@ enum { AFR_GEMM_BIAS = 1, AFR_GEMM_RELU = 2, AFR_GEMM_RELU_MASK = 4, AFR_GEMM_OU
        AFR_GEMM_A_KSTRIDED = 16, AFR_GEMM_B_KSTRIDED = 32 };
 /* C[m][n] = sum_k A(m,k) * B(n,k) (+bias[n]) (relu) (* (aux[m][n] > 0)).
  * A(m,k) = A[m*lda+k], or A[k*lda+m] with AFR_GEMM_A_KSTRIDED; B likewise.  dtype selects f32 or
- * bf16 operands (aux has the operand dtype); C is f32 unless AFR_GEMM_OUT_BF16.  splitk>1 writes
+ * bf16 operands (aux has the operand dtype), or AFR_BF16X3: f32 operands and aux, split-bf16 products, f32 C only
+ * (AFR_GEMM_OUT_BF16 is AFR_EINVAL).  C is f32 unless AFR_GEMM_OUT_BF16.  splitk>1 writes
  * splitk partial f32 slabs of M*ldc elements each, to be summed by the caller (afr_op_reduce). */
 int afr_op_gemm(int dtype, int flags, const void* A, const void* B, void* C, const float* bias,
                 const void* aux, int M, int N, int K, int lda, int ldb, int ldc, int ldaux,
