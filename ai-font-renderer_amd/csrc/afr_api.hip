@@ -123,6 +123,11 @@ struct afr_plan {
     uint64_t last_step = 0;
     bool have_du = false;
     int next_stage = 0;
+    // the bound data set (afr_bind_dataset; caller-owned device buffers) and the workspace staging of the afr_*_rows calls: the
+    // narrowed row indices the loss kernels' row maps read, and the batch's codes / font ids for the id consumers
+    const int64_t* ds_x = nullptr; const int64_t* ds_font = nullptr; const void* ds_target = nullptr;
+    int ds_tdtype = 0, ds_L = 0; int64_t ds_rows = 0;
+    size_t o_ridx = 0, o_sx = 0, o_sfont = 0;
     // profiling
     int prof_mode = 0;      // 0 off, 1 every launch, 2 only prof_only, 3 every 4th launch of prof_only
     unsigned prof_seen = 0; // launches of prof_only met in mode 3
@@ -393,6 +398,10 @@ extern "C" int afr_plan_create(const afr_config* c, afr_plan** out) {
         for (const auto& l : p->layers)
             if ((long long)l.N * l.K * 2 >= (1ll << 31)) { delete p; return fail(AFR_EUNSUPPORTED, "a %d x %d weight is 2 GiB or more in bf16", l.N, l.K); }
     }
+    // staging of the afr_*_rows calls: row indices int [max_batch], codes int64 [max_batch][max_length or 1], font ids int64 [max_batch]
+    p->o_ridx = carve(B * sizeof(int));
+    p->o_sx = carve(B * (size_t)(c->kind == AFR_KIND_SHEET ? c->max_length : 1) * sizeof(int64_t));
+    p->o_sfont = carve(B * sizeof(int64_t));
     p->ws_need = off;
     *out = p;
     return AFR_OK;
@@ -573,7 +582,8 @@ extern "C" int afr_profile_dump(afr_plan* p, char* buf, int cap) {
 }
 
 // ------------------------------------------------------------------------------------ helpers
-struct FusedLoss { const void* target; int tdtype; int64_t mean_elems; float* loss_accum; };
+struct FusedLoss { const void* target; int tdtype; int64_t mean_elems; float* loss_accum;
+                   const int* rowmap = nullptr; };       // targets of batch row b = row rowmap[b] of `target` (afr_*_rows); NULL = row b
 struct FusedAdam { float *p, *m, *v; bf16_t* shadow; float decay, b1, b2, eps, step_size, rsqrt_bc2; };
 struct CoopArgs { float* ws; unsigned* cnt; unsigned target; };
 struct RowMaps { const int* a; const int* b; const int* aux;        // GemmParams::a_rowmap / b_rowmap / aux_rowmap
@@ -612,7 +622,7 @@ static int run_gemm(afr_plan* p, hipStream_t s, int flags, const void* A, const 
     if (coop) { g.coop_ws = coop->ws; g.coop_cnt = coop->cnt; g.coop_target = coop->target; g.err = (uint32_t*)(p->ws + p->o_err); }
     if (fl) {
         float* scratch = (float*)(p->ws + p->o_loss);
-        g.mse_target = fl->target; g.mse_target_dtype = fl->tdtype; g.mse_inv_n = (float)(1.0 / (double)fl->mean_elems);
+        g.mse_target = fl->target; g.mse_rowmap = fl->rowmap; g.mse_target_dtype = fl->tdtype; g.mse_inv_n = (float)(1.0 / (double)fl->mean_elems);
         g.mse_partial = scratch + 1040; g.mse_counter = reinterpret_cast<unsigned*>(scratch + 1032); g.mse_loss_accum = fl->loss_accum;
     }
     g.A = A; g.B = B; g.C = C; g.bias = bias; g.aux = aux;
@@ -853,7 +863,7 @@ static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int 
         p->have_du = false;
         if (fl) {        // the loss on the f32 pre-clamp output (model.py:156,268-270): du in place over u
             ProfScope ps(p, s, "mse_grad", 0.0, (double)rows * 9.0);
-            HIPCHK(afr_launch_mse_grad(AFR_F32, u, fl->target, fl->tdtype, u, B, Pix, fl->mean_elems, fl->loss_accum, (float*)(p->ws + p->o_loss), s));
+            HIPCHK(afr_launch_mse_grad(AFR_F32, u, fl->target, fl->tdtype, u, B, Pix, fl->mean_elems, fl->loss_accum, (float*)(p->ws + p->o_loss), s, fl->rowmap));
             p->have_du = true;
         }
         return AFR_OK;
@@ -919,8 +929,8 @@ extern "C" int afr_forward(afr_plan* p, const int64_t* x, const int64_t* font, i
 }
 
 // --------------------------------------------------------------------------------- loss + grad
-extern "C" int afr_loss_grad(afr_plan* p, const void* target, int tdtype, int B, int64_t mean_elems, float* loss_accum,
-                             void* stream) {
+static int loss_grad_impl(afr_plan* p, const void* target, int tdtype, const int* rowmap, int B, int64_t mean_elems, float* loss_accum,
+                          void* stream) {
     if (!p || !p->P) return fail(AFR_ESTATE, "plan has no bound parameters");
     DevGuard dg(p->device);
     if (!target || !loss_accum) return fail(AFR_EINVAL, "target and loss_accum are required");
@@ -933,9 +943,13 @@ extern "C" int afr_loss_grad(afr_plan* p, const void* target, int tdtype, int B,
     const double tb = tdtype == AFR_TARGET_U8 ? 1.0 : 4.0;
     ProfScope ps(p, s, "mse_grad", 0.0, (double)B * Pix * (2.0 * p->act_bytes + tb));
     HIPCHK(afr_launch_mse_grad(p->cfg.kind == AFR_KIND_PIXEL ? AFR_F32 : p->cfg.dtype, u, target, tdtype, u, B, Pix, mean_elems, loss_accum,
-                               (float*)(p->ws + p->o_loss), s));      // (the pixel transformer's pre-clamp output is f32 in both modes)
+                               (float*)(p->ws + p->o_loss), s, rowmap));      // (the pixel transformer's pre-clamp output is f32 in both modes)
     p->have_du = true;
     return AFR_OK;
+}
+extern "C" int afr_loss_grad(afr_plan* p, const void* target, int tdtype, int B, int64_t mean_elems, float* loss_accum,
+                             void* stream) {
+    return loss_grad_impl(p, target, tdtype, nullptr, B, mean_elems, loss_accum, stream);
 }
 
 extern "C" int afr_set_output_grad(afr_plan* p, const float* dy, int B, void* stream) {
@@ -1338,7 +1352,7 @@ static int sheet_fused_step(afr_plan* p, hipStream_t s, float lr, float b1, floa
 
 // One fused launch for the whole forward + loss + backward of a small one-hidden-layer glyph net (glyph_fused.hip); the
 // per-block partial gradients it leaves are registered in `rt` for the grouped reduce (with or without AdamW).
-static int glyph1_fused(afr_plan* p, const int64_t* x, const int64_t* font, const void* target, int tdtype, int B,
+static int glyph1_fused(afr_plan* p, const int64_t* x, const int64_t* font, const void* target, int tdtype, const int* rowmap, int B,
                         int64_t mean_elems, float* loss_accum, hipStream_t s, RTable& rt) {
     const afr_config& c = p->cfg;
     if (!x) return fail(AFR_EINVAL, "x is null");
@@ -1355,7 +1369,7 @@ static int glyph1_fused(afr_plan* p, const int64_t* x, const int64_t* font, cons
         p->wT_valid = true;
     }
     Glyph1Args a;
-    a.x = x; a.font = font; a.target = target; a.tdtype = tdtype;
+    a.x = x; a.font = font; a.target = target; a.tdtype = tdtype; a.rowmap = rowmap;
     a.B = B; a.E = E; a.N1 = N1; a.P = Pix; a.vocab = c.vocab; a.n_fonts = c.n_fonts;
     a.emb = p->P + p->emb_off; a.femb = c.n_fonts > 0 ? p->P + p->font_off : nullptr;
     a.b1 = p->P + l1.b_off; a.b2 = p->P + l2.b_off;
@@ -1401,18 +1415,22 @@ static int glyph1_fused(afr_plan* p, const int64_t* x, const int64_t* font, cons
     return AFR_OK;
 }
 
-extern "C" int afr_forward_loss(afr_plan* p, const int64_t* x, const int64_t* font, const void* target, int tdtype, int B, int L,
-                                int64_t mean_elems, float* loss_accum, uint64_t step, void* stream) {
+static int forward_loss_impl(afr_plan* p, const int64_t* x, const int64_t* font, const void* target, int tdtype, const int* rowmap, int B, int L,
+                             int64_t mean_elems, float* loss_accum, uint64_t step, void* stream) {
     if (!target || !loss_accum) return fail(AFR_EINVAL, "target and loss_accum are required");
     if (tdtype != AFR_TARGET_U8 && tdtype != AFR_TARGET_F32) return fail(AFR_EINVAL, "bad target dtype");
     if (mean_elems <= 0) return fail(AFR_EINVAL, "mean_elems must be positive");
-    FusedLoss fl{target, tdtype, mean_elems, loss_accum};
+    FusedLoss fl{target, tdtype, mean_elems, loss_accum, rowmap};
     return forward_impl(p, x, font, B, L, nullptr, 1, step, stream, &fl);
 }
+extern "C" int afr_forward_loss(afr_plan* p, const int64_t* x, const int64_t* font, const void* target, int tdtype, int B, int L,
+                                int64_t mean_elems, float* loss_accum, uint64_t step, void* stream) {
+    return forward_loss_impl(p, x, font, target, tdtype, nullptr, B, L, mean_elems, loss_accum, step, stream);
+}
 
-extern "C" int afr_train_step(afr_plan* p, const int64_t* x, const int64_t* font, const void* target, int tdtype, int B,
-                              int L, int64_t mean_elems, float* loss_accum, uint64_t step, int do_step, float lr, float b1,
-                              float b2, float eps, float wd, int64_t t, void* stream) {
+static int train_step_impl(afr_plan* p, const int64_t* x, const int64_t* font, const void* target, int tdtype, const int* rowmap, int B,
+                           int L, int64_t mean_elems, float* loss_accum, uint64_t step, int do_step, float lr, float b1,
+                           float b2, float eps, float wd, int64_t t, void* stream) {
     int rc;
     if (!target || !loss_accum) return fail(AFR_EINVAL, "target and loss_accum are required");
     if (tdtype != AFR_TARGET_U8 && tdtype != AFR_TARGET_F32) return fail(AFR_EINVAL, "bad target dtype");
@@ -1423,7 +1441,7 @@ extern "C" int afr_train_step(afr_plan* p, const int64_t* x, const int64_t* font
         // small glyph net: forward + loss + backward in ONE launch, then the grouped reduce (with AdamW when stepping here)
         if (!p->G) return fail(AFR_ESTATE, "plan has no bound gradient buffer");
         RTable rt;
-        if ((rc = glyph1_fused(p, x, font, target, tdtype, B, mean_elems, loss_accum, (hipStream_t)stream, rt))) return rc;
+        if ((rc = glyph1_fused(p, x, font, target, tdtype, rowmap, B, mean_elems, loss_accum, (hipStream_t)stream, rt))) return rc;
         if (do_step && p->M && p->V && !(p->cfg.reserved & 1)) {
             if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
             rc = reduce_and_step(p, (hipStream_t)stream, rt, lr, b1, b2, eps, wd, t);
@@ -1435,7 +1453,7 @@ extern "C" int afr_train_step(afr_plan* p, const int64_t* x, const int64_t* font
         return AFR_OK;
     }
     // the loss and its gradient are computed in the epilogue of the last forward GEMM: u never touches HBM
-    FusedLoss fl{target, tdtype, mean_elems, loss_accum};
+    FusedLoss fl{target, tdtype, mean_elems, loss_accum, rowmap};
     if ((rc = forward_impl(p, x, font, B, L, nullptr, 1, step, stream, &fl))) return rc;
     if (do_step && fused_step_eligible(p, B) && !(p->cfg.reserved & 1)) {
         if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
@@ -1462,6 +1480,69 @@ extern "C" int afr_train_step(afr_plan* p, const int64_t* x, const int64_t* font
     if ((rc = afr_backward(p, stream))) return rc;
     if (do_step && (rc = afr_adamw_step(p, lr, b1, b2, eps, wd, t, 1.f, stream))) return rc;
     return AFR_OK;
+}
+extern "C" int afr_train_step(afr_plan* p, const int64_t* x, const int64_t* font, const void* target, int tdtype, int B,
+                              int L, int64_t mean_elems, float* loss_accum, uint64_t step, int do_step, float lr, float b1,
+                              float b2, float eps, float wd, int64_t t, void* stream) {
+    return train_step_impl(p, x, font, target, tdtype, nullptr, B, L, mean_elems, loss_accum, step, do_step, lr, b1, b2, eps, wd, t, stream);
+}
+
+// ------------------------------------------------------------------- resident data set, by row index
+// The afr_*_rows entry points are the dense ones with (x, font, target) taken from the bound data set at rows[b]: the targets
+// through the loss kernels' row maps (read in place), codes and font ids through the workspace staging that
+// dataset_rows_kernel fills -- which is what last_x / last_font then name, so the backward entry points need nothing new.
+extern "C" int afr_bind_dataset(afr_plan* p, const int64_t* x, const int64_t* font, const void* target, int tdtype, int64_t n_rows, int L) {
+    if (!p) return fail(AFR_EINVAL, "null plan");
+    if (!x && !font && !target) {
+        p->ds_x = p->ds_font = nullptr; p->ds_target = nullptr; p->ds_rows = 0; p->ds_L = 0;
+        return AFR_OK;
+    }
+    if (n_rows >= (1ll << 31)) return fail(AFR_EUNSUPPORTED, "a data set of %lld rows: row indices are narrowed to 32 bits (fewer than 2^31 rows)", (long long)n_rows);
+    if (!x || !target || n_rows <= 0) return fail(AFR_EINVAL, "a data set needs codes, targets and at least one row");
+    if (p->cfg.n_fonts > 0 && !font) return fail(AFR_EINVAL, "font ids are required when n_fonts > 0");
+    if (L <= 0 || (p->cfg.kind != AFR_KIND_SHEET && L != 1)) return fail(AFR_EINVAL, "bad row length L = %d (sheet: positive; glyph / pixel: 1)", L);
+    if (tdtype != AFR_TARGET_U8 && tdtype != AFR_TARGET_F32) return fail(AFR_EINVAL, "bad target dtype");
+    p->ds_x = x; p->ds_font = p->cfg.n_fonts > 0 ? font : nullptr; p->ds_target = target; p->ds_tdtype = tdtype; p->ds_rows = n_rows; p->ds_L = L;
+    return AFR_OK;
+}
+// the checks every afr_*_rows call starts with, then (stage_ids) the prepare kernel; *Lc = the staged row length
+static int rows_begin(afr_plan* p, const int64_t* rows, int B, bool stage_ids, void* stream, int* Lc) {
+    if (!p || !p->ds_target) return fail(AFR_ESTATE, "no data set bound (afr_bind_dataset)");
+    if (!rows) return fail(AFR_EINVAL, "rows is null");
+    if (B <= 0 || B > p->cfg.max_batch) return fail(AFR_EINVAL, "batch %d outside 1..max_batch=%d", B, p->cfg.max_batch);
+    if (!p->P || !p->ws) return fail(AFR_ESTATE, "plan has no bound parameters");
+    DevGuard dg(p->device);
+    hipStream_t s = (hipStream_t)stream;
+    *Lc = p->cfg.kind == AFR_KIND_SHEET ? (p->ds_L < p->cfg.max_length ? p->ds_L : p->cfg.max_length) : 1;
+    ProfScope ps(p, s, "dataset_rows", 0.0, (double)B * (stage_ids ? 16.0 * *Lc + 28.0 : 12.0));
+    HIPCHK(afr_launch_dataset_rows(rows, B, p->ds_rows, p->ds_x, p->ds_font, p->ds_L, *Lc, (int*)(p->ws + p->o_ridx),
+                                   stage_ids ? (int64_t*)(p->ws + p->o_sx) : nullptr, (int64_t*)(p->ws + p->o_sfont), (uint32_t*)(p->ws + p->o_err), s));
+    return AFR_OK;
+}
+static inline const int64_t* staged_font(const afr_plan* p) { return p->ds_font ? (const int64_t*)(p->ws + p->o_sfont) : nullptr; }
+extern "C" int afr_forward_rows(afr_plan* p, const int64_t* rows, int B, float* y, int training, uint64_t step, void* stream) {
+    int Lc, rc;
+    if ((rc = rows_begin(p, rows, B, true, stream, &Lc))) return rc;
+    return forward_impl(p, (const int64_t*)(p->ws + p->o_sx), staged_font(p), B, Lc, y, training, step, stream, nullptr);
+}
+extern "C" int afr_loss_grad_rows(afr_plan* p, const int64_t* rows, int B, int64_t mean_elems, float* loss_accum, void* stream) {
+    int Lc, rc;      // (the row indices alone: the staged codes of the forward stay as they are for the backward)
+    if ((rc = rows_begin(p, rows, B, false, stream, &Lc))) return rc;
+    return loss_grad_impl(p, p->ds_target, p->ds_tdtype, (const int*)(p->ws + p->o_ridx), B, mean_elems, loss_accum, stream);
+}
+extern "C" int afr_forward_loss_rows(afr_plan* p, const int64_t* rows, int B, int64_t mean_elems, float* loss_accum, uint64_t step,
+                                     void* stream) {
+    int Lc, rc;
+    if ((rc = rows_begin(p, rows, B, true, stream, &Lc))) return rc;
+    return forward_loss_impl(p, (const int64_t*)(p->ws + p->o_sx), staged_font(p), p->ds_target, p->ds_tdtype, (const int*)(p->ws + p->o_ridx),
+                             B, Lc, mean_elems, loss_accum, step, stream);
+}
+extern "C" int afr_train_step_rows(afr_plan* p, const int64_t* rows, int B, int64_t mean_elems, float* loss_accum, uint64_t step,
+                                   int do_step, float lr, float b1, float b2, float eps, float wd, int64_t t, void* stream) {
+    int Lc, rc;
+    if ((rc = rows_begin(p, rows, B, true, stream, &Lc))) return rc;
+    return train_step_impl(p, (const int64_t*)(p->ws + p->o_sx), staged_font(p), p->ds_target, p->ds_tdtype, (const int*)(p->ws + p->o_ridx),
+                           B, Lc, mean_elems, loss_accum, step, do_step, lr, b1, b2, eps, wd, t, stream);
 }
 
 extern "C" int afr_error_flags(afr_plan* p, void* stream, uint32_t* out) {

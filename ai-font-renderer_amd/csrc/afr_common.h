@@ -104,6 +104,8 @@ struct GemmParams {
     // optional fused loss (last forward layer of a training step): instead of u = A.B^T + bias the epilogue writes
     // du = 2 (clamp(u,0,1) - t) / mean_elems * [0<=u<=1] and accumulates the MSE (reference model.py:156,268-270)
     const void* mse_target = nullptr;   // [M][N] uint8 or float32
+    const int* mse_rowmap = nullptr;    // optional: the targets of output row m are row mse_rowmap[m] of mse_target (a resident data set
+                                        // read in place, 64-bit addressing); NULL = row m
     int mse_target_dtype = 0;           // AFR_TARGET_*
     float mse_inv_n = 0.f;              // 1 / mean_elems
     float* mse_partial = nullptr;       // per-block partial sums (>= grid floats)
@@ -139,7 +141,7 @@ struct GemmParams {
     int dbg_slot = 0;     // kernel-development builds: which 1024-block region of the stamp buffer this launch writes
 #endif
 };
-constexpr uint32_t AFR_ERR_INDEX = 1u, AFR_ERR_COOP_TIMEOUT = 2u;    // bits of the plan's device error word
+constexpr uint32_t AFR_ERR_INDEX = 1u, AFR_ERR_COOP_TIMEOUT = 2u, AFR_ERR_ROW = 4u;    // bits of the plan's device error word
 // torch.optim.AdamW element update (reference model.py:273,310); shared by adamw_kernel and the fused GEMM epilogue
 __device__ __forceinline__ void adamw_elem(float& p, float& m, float& v, float g, float decay, float b1, float b2,
                                            float eps, float step_size, float rsqrt_bc2) {
@@ -194,7 +196,11 @@ int afr_mse_blocks(long long rows, long long cols);
 // scratch: >= 1028 floats; scratch[1024] (as unsigned) is the arrival counter, zero before the first call
 hipError_t afr_launch_mse_grad(int act_dtype, const void* u, const void* target, int target_dtype, void* du,
                                long long rows, long long cols, long long mean_elems, float* loss_accum,
-                               float* scratch, hipStream_t s);
+                               float* scratch, hipStream_t s, const int* rowmap = nullptr /* target row of u row r; NULL = r */);
+// Batch rows of a resident data set (afr_*_rows): validates and clamps rows[b] (AFR_ERR_ROW), writes ridx[b] = the narrowed index
+// the loss kernels' row maps read and, when sx is not NULL, stages x[rows[b]][0 .. Lc) into sx [B][Lc] and font[rows[b]] into sfont.
+hipError_t afr_launch_dataset_rows(const int64_t* rows, int B, long long n_rows, const int64_t* x, const int64_t* font, int L, int Lc,
+                                   int* ridx, int64_t* sx, int64_t* sfont, uint32_t* err_flag, hipStream_t s);
 hipError_t afr_launch_f32_to_bf16(const float* src, bf16_t* dst, long long n, hipStream_t s);
 hipError_t afr_launch_clamp_bwd(int act_dtype, void* u_inout, const float* dy, long long n, hipStream_t s);
 hipError_t afr_launch_clamp_out(int act_dtype, const void* u, float* y, long long n, hipStream_t s);
@@ -258,6 +264,7 @@ hipError_t afr_launch_sheet_bwd(int act_dtype, const SheetDims& d, const SheetPa
 // fused step of the small one-hidden-layer glyph nets (glyph_fused.hip)
 struct Glyph1Args {
     const int64_t* x; const int64_t* font; const void* target; int tdtype;
+    const int* rowmap = nullptr;             // optional: the targets of glyph b are row rowmap[b] of target (NULL = row b)
     int B, E, N1, P, vocab, n_fonts;
     const float *emb, *femb, *b1, *b2;       // f32 masters
     const void *W1, *W2;                     // [N1][E], [P][N1] in the operand type (f32 masters / bf16 shadow)

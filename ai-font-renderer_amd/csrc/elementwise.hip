@@ -279,14 +279,21 @@ hipError_t afr_launch_clamp_bwd(int act_dtype, void* u, const float* dy, long lo
 // (reference model.py:156,268-270 and the first step of loss.backward(), model.py:309).
 // 8 pixels per lane per iteration: u as 2 x 16 B (f32) or 16 B (bf16), target as 8 B (u8) or 2 x 16 B (f32).
 // du may alias u.  Per-lane sums -> wave shuffle -> LDS -> one partial per block -> fixed-order finisher.
-template <typename T, typename TT>
+// ROWS: the targets of row r of u are row rowmap[r] of tgt (a resident data set read in place; cols8 = groups of 8 pixels per
+// row): the same walk over u, the target group addressed as (row, column group) with 64-bit arithmetic.
+template <typename T, typename TT, bool ROWS>
 __global__ __launch_bounds__(256) void mse_grad_kernel(const T* __restrict__ u, const TT* __restrict__ tgt,
                                                        T* __restrict__ du, long long n8, float inv_n,
                                                        float* __restrict__ partial, unsigned* __restrict__ counter,
-                                                       float* __restrict__ loss_accum) {
+                                                       float* __restrict__ loss_accum, const int* __restrict__ rowmap, int cols8) {
     float lsum = 0.f;
     const float g2 = 2.f * inv_n;
     for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
+        size_t ti = (size_t)i;                   // the target's group of 8 pixels
+        if (ROWS) {
+            const long long r = i / cols8;
+            ti = (size_t)rowmap[r] * (size_t)cols8 + (size_t)(i - r * cols8);
+        }
         float uu[8], tt[8];
         if (sizeof(T) == 4) {
             const float4 a = reinterpret_cast<const float4*>(u)[2 * i], b = reinterpret_cast<const float4*>(u)[2 * i + 1];
@@ -297,14 +304,14 @@ __global__ __launch_bounds__(256) void mse_grad_kernel(const T* __restrict__ u, 
             for (int k = 0; k < 8; ++k) uu[k] = (float)a[k];
         }
         if (sizeof(TT) == 1) {
-            const uint2 a = reinterpret_cast<const uint2*>(tgt)[i];
+            const uint2 a = reinterpret_cast<const uint2*>(tgt)[ti];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 tt[k] = (float)((a.x >> (8 * k)) & 0xFF) / 255.0f;       // helpers.py:121: uint8 / 255.0 in float32
                 tt[4 + k] = (float)((a.y >> (8 * k)) & 0xFF) / 255.0f;
             }
         } else {
-            const float4 a = reinterpret_cast<const float4*>(tgt)[2 * i], b = reinterpret_cast<const float4*>(tgt)[2 * i + 1];
+            const float4 a = reinterpret_cast<const float4*>(tgt)[2 * ti], b = reinterpret_cast<const float4*>(tgt)[2 * ti + 1];
             tt[0] = a.x; tt[1] = a.y; tt[2] = a.z; tt[3] = a.w; tt[4] = b.x; tt[5] = b.y; tt[6] = b.z; tt[7] = b.w;
         }
         float dd[8];
@@ -335,21 +342,58 @@ __global__ __launch_bounds__(256) void mse_grad_kernel(const T* __restrict__ u, 
 int afr_mse_blocks(long long rows, long long cols) { return grid_for(rows * cols / 8, 256, 1024); }
 hipError_t afr_launch_mse_grad(int act_dtype, const void* u, const void* target, int target_dtype, void* du,
                                long long rows, long long cols, long long mean_elems, float* loss_accum,
-                               float* scratch, hipStream_t s) {
+                               float* scratch, hipStream_t s, const int* rowmap) {
     const long long n = rows * cols;
     if (n <= 0) return hipSuccess;
-    if (n & 7) return hipErrorInvalidValue;
+    if ((n & 7) || (rowmap && (cols & 7))) return hipErrorInvalidValue;
     const int blocks = afr_mse_blocks(rows, cols);
     const float inv_n = (float)(1.0 / (double)mean_elems);
     dim3 g(blocks), b(256);
     unsigned* counter = reinterpret_cast<unsigned*>(scratch + 1024);
-#define MSE(T, TT) hipLaunchKernelGGL((mse_grad_kernel<T, TT>), g, b, 0, s, (const T*)u, (const TT*)target, (T*)du, n / 8, inv_n, scratch, counter, loss_accum)
+#define MSE(T, TT)                                                                                                                      \
+    do {                                                                                                                                \
+        if (rowmap) hipLaunchKernelGGL((mse_grad_kernel<T, TT, true>), g, b, 0, s, (const T*)u, (const TT*)target, (T*)du, n / 8, inv_n, \
+                                       scratch, counter, loss_accum, rowmap, (int)(cols / 8));                                          \
+        else hipLaunchKernelGGL((mse_grad_kernel<T, TT, false>), g, b, 0, s, (const T*)u, (const TT*)target, (T*)du, n / 8, inv_n,      \
+                                scratch, counter, loss_accum, (const int*)nullptr, 0);                                                  \
+    } while (0)
     if (act_dtype == AFR_BF16) {
         if (target_dtype == AFR_TARGET_U8) MSE(bf16_t, uint8_t); else MSE(bf16_t, float);
     } else {
         if (target_dtype == AFR_TARGET_U8) MSE(float, uint8_t); else MSE(float, float);
     }
 #undef MSE
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------- batch rows of a resident data set
+// The prepare step of the afr_*_rows entry points: batch row b is data-set row rows[b].  An index outside [0, n_rows) sets
+// AFR_ERR_ROW and is clamped BEFORE anything is addressed with it (as glyph_embed_kernel does for code indices).  ridx[b] is
+// the narrowed index the loss kernels' row maps read; the codes x[row][0 .. Lc) and the font id are copied into the staging
+// area the id consumers (sheet_fwd / glyph_embed / pixel_ctx ... and their backward kernels) are handed (sx NULL: ridx only).
+__global__ __launch_bounds__(256) void dataset_rows_kernel(const int64_t* __restrict__ rows, int B, long long n_rows,
+                                                           const int64_t* __restrict__ x, const int64_t* __restrict__ font, int L, int Lc,
+                                                           int* __restrict__ ridx, int64_t* __restrict__ sx, int64_t* __restrict__ sfont,
+                                                           uint32_t* err_flag) {
+    const int per = sx ? Lc : 1;
+    const long long total = (long long)B * per;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int b = (int)(i / per), l = (int)(i - (long long)b * per);
+        long long r = rows[b];
+        if (r < 0 || r >= n_rows) { if (l == 0) atomicOr(err_flag, AFR_ERR_ROW); r = min(max(r, 0ll), n_rows - 1); }
+        if (l == 0) {
+            ridx[b] = (int)r;
+            if (sx && sfont && font) sfont[b] = font[r];
+        }
+        if (sx) sx[(size_t)b * Lc + l] = x[(size_t)r * L + l];
+    }
+}
+hipError_t afr_launch_dataset_rows(const int64_t* rows, int B, long long n_rows, const int64_t* x, const int64_t* font, int L, int Lc,
+                                   int* ridx, int64_t* sx, int64_t* sfont, uint32_t* err_flag, hipStream_t s) {
+    if (B <= 0) return hipSuccess;
+    if (n_rows <= 0 || n_rows > 0x7fffffffll || (sx && (Lc <= 0 || Lc > L))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dataset_rows_kernel, dim3(grid_for((long long)B * (sx ? Lc : 1), 256)), dim3(256), 0, s, rows, B, n_rows, x, font, L, Lc,
+                       ridx, sx, sfont, err_flag);
     return hipGetLastError();
 }
 

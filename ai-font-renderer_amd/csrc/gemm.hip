@@ -123,6 +123,9 @@ __device__ __forceinline__ void colsum_store(const GemmParams& p, float* smem, c
     }
 }
 // bias, ReLU, ReLU mask, split-K slabs, bf16 output, fused clamp/MSE/du, fused AdamW; smem: >= 16 + 256 floats of scratch
+// TROWS: the fused loss' targets are rows p.mse_rowmap[m] of a resident data set (its own instantiation: the dense kernels carry
+// no row-map code)
+template <bool TROWS = false>
 __device__ __forceinline__ void tile_epilogue(const GemmParams& p, const f32x16 (&acc)[2][2], const int m0, const int n0, const int z,
                                               const int tid, float* smem) {
     const int lane = tid & 63, wid = tid >> 6;
@@ -152,7 +155,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& p, const f32x16 
                 if (flags & AFR_GEMM_RELU_MASK) v = (aux[(size_t)m * p.ldaux + n] > 0.f) ? v : 0.f;
                 if (mse) {
                     if (out_bf16) v = (float)(bf16_t)v;
-                    const size_t ti = (size_t)m * p.N + n;
+                    const size_t ti = (size_t)(TROWS ? p.mse_rowmap[m] : m) * p.N + n;
                     const float t = p.mse_target_dtype == AFR_TARGET_U8 ? (float)reinterpret_cast<const uint8_t*>(p.mse_target)[ti] / 255.0f
                                                                         : reinterpret_cast<const float*>(p.mse_target)[ti];
                     const float diff = fminf(fmaxf(v, 0.f), 1.f) - t;
@@ -177,7 +180,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& p, const f32x16 
     }
 }
 
-template <int ALAY, int BLAY>
+template <int ALAY, int BLAY, bool TROWS = false>
 __global__ __launch_bounds__(256) void gemm_f32(GemmParams p) {
     constexpr int LDA = Lds<ALAY>::LD, LDB = Lds<BLAY>::LD;
     constexpr int TILE = BK * LDA + BK * LDB;
@@ -251,7 +254,7 @@ __global__ __launch_bounds__(256) void gemm_f32(GemmParams p) {
         smem[tid] = cs;
         colsum_store(p, smem, tid, m0, z, 2);
     }
-    tile_epilogue(p, acc, m0, n0, z, tid, smem);
+    tile_epilogue<TROWS>(p, acc, m0, n0, z, tid, smem);
 }
 }  // namespace f32k
 
@@ -325,7 +328,7 @@ __device__ __forceinline__ bf16x8 frag(const char* S, int xb, int ks, int lane) 
     return *reinterpret_cast<const bf16x8*>(S + xoff(xb + (lane & 31), 2 * ks + (lane >> 5)));
 }
 
-template <int ALAY, int BLAY>
+template <int ALAY, int BLAY, bool TROWS = false>
 __global__ __launch_bounds__(256, 2) void gemm_bf16x3(GemmParams p) {
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -415,7 +418,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3(GemmParams p) {
         for (int e = 0; e < 4; ++e) sf[kq * 128 + xb + e] = cs[e];
         f32k::colsum_store(p, sf, tid, m0, z, 8);
     }
-    f32k::tile_epilogue(p, acc, m0, n0, z, tid, sf);
+    f32k::tile_epilogue<TROWS>(p, acc, m0, n0, z, tid, sf);
 }
 }  // namespace x3k
 
@@ -554,7 +557,9 @@ __device__ __forceinline__ void epilogue_bias(const GemmParams& p, const int nb0
 }
 // (acc_at(i, j): the wave's accumulator fragment of rows 16 i .., columns 16 j .. -- an accessor, so that the 256x256 body can hand
 // over either half of its 128 x 64 tile without copying 64 registers)
-template <int ALAY, int BLAY, int WM, bool SCALE = false, bool EARLYB_ = true, class ACC>      // SCALE: the accumulators are multiplied by p.out_scale first (fp8 per-tensor scales)
+// (TROWS: the fused loss' targets are rows p.mse_rowmap[m] of a resident data set, read in place -- its own instantiation of the
+// forward-layout ring kernels, so that the dense kernels carry no row-map code)
+template <int ALAY, int BLAY, int WM, bool SCALE = false, bool EARLYB_ = true, bool TROWS = false, class ACC>      // SCALE: the accumulators are multiplied by p.out_scale first (fp8 per-tensor scales)
 __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC& acc_at, const int mb, const int nb0, const int z,
                                                  float* Wt, const int lane, float& lsum, const float* lut255 = nullptr,
                                                  const float (*pre_bias)[8] = nullptr) {
@@ -588,11 +593,26 @@ __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC&
     // (forward layout on the ring kernels only: the 256x256 body takes no fused loss)
     uint2 tu8[8];
     const bool early_t = EARLYB && pre_bias == nullptr && mse && p.mse_target_dtype == AFR_TARGET_U8;
-    if (early_t) {
+    if (early_t && !TROWS) {
 #pragma unroll
         for (int ps = 0; ps < 8; ++ps) {
             const int m = mb + ps * 8 + (lane >> 3);
             if (m < p.M && ncol) tu8[ps] = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(p.mse_target) + (size_t)m * p.N + n);
+        }
+    }
+    // (row-mapped: one int per row pass, shared by the 8 lanes of the row, all 8 asked for before the first target; 64-bit
+    // addressing: a data set's target buffer may pass 2 GiB)
+    if (early_t && TROWS) {
+        int tm[8];
+#pragma unroll
+        for (int ps = 0; ps < 8; ++ps) {
+            const int m = mb + ps * 8 + (lane >> 3);
+            tm[ps] = m < p.M ? p.mse_rowmap[m] : 0;
+        }
+#pragma unroll
+        for (int ps = 0; ps < 8; ++ps) {
+            const int m = mb + ps * 8 + (lane >> 3);
+            if (m < p.M && ncol) tu8[ps] = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(p.mse_target) + (size_t)tm[ps] * p.N + n);
         }
     }
 #pragma unroll
@@ -647,7 +667,7 @@ __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC&
                     if (p.mask_in) auxv[ps][0] = __builtin_bit_cast(bf16_t, (unsigned short)p.mask_in[(size_t)m * p.ldmask + (n >> 3)]);   // the 8 bits travel in element 0
                     else auxv[ps] = *reinterpret_cast<const bf16x8*>(aux + (size_t)am[ps] * p.ldaux + n);
                 }
-                if (mse && !early_t) tu8[ps] = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(p.mse_target) + (size_t)m * p.N + n);
+                if (mse && !early_t) tu8[ps] = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(p.mse_target) + (size_t)(TROWS ? p.mse_rowmap[m] : m) * p.N + n);
             }
         }
     }
@@ -750,7 +770,6 @@ __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC&
         }
         if (mse) {
             float t[8];
-            const size_t ti = (size_t)m * p.N + n;
             if (p.mse_target_dtype == AFR_TARGET_U8) {
                 const uint2 w = tu8[ps];
                 if (lut255) {                          // k / 255.0f looked up (the block computed the 256 quotients once): same values
@@ -761,6 +780,7 @@ __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC&
                     for (int r = 0; r < 4; ++r) { t[r] = (float)((w.x >> (8 * r)) & 0xFF) / 255.0f; t[4 + r] = (float)((w.y >> (8 * r)) & 0xFF) / 255.0f; }
                 }
             } else {
+                const size_t ti = (size_t)(TROWS ? p.mse_rowmap[m] : m) * p.N + n;
                 const float4 w0 = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.mse_target) + ti);
                 const float4 w1 = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.mse_target) + ti + 4);
                 t[0] = w0.x; t[1] = w0.y; t[2] = w0.z; t[3] = w0.w; t[4] = w1.x; t[5] = w1.y; t[6] = w1.z; t[7] = w1.w;
@@ -790,10 +810,10 @@ __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC&
     }
 }
 
-template <int ALAY, int BLAY, int WM, bool SCALE = false, bool EARLYB_ = true>
+template <int ALAY, int BLAY, int WM, bool SCALE = false, bool EARLYB_ = true, bool TROWS = false>
 __device__ __forceinline__ void wave_epilogue(const GemmParams& p, const f32x4 (&acc)[4][4], const int mb, const int nb0, const int z,
                                               float* Wt, const int lane, float& lsum, const float* lut255 = nullptr) {
-    wave_epilogue_at<ALAY, BLAY, WM, SCALE, EARLYB_>(p, [&](int i, int j) { return acc[i][j]; }, mb, nb0, z, Wt, lane, lsum, lut255);
+    wave_epilogue_at<ALAY, BLAY, WM, SCALE, EARLYB_, TROWS>(p, [&](int i, int j) { return acc[i][j]; }, mb, nb0, z, Wt, lane, lsum, lut255);
 }
 
 // Finish of one wave's 16 x 64 f32 strip of a weight gradient (cooperative split-K, gemm_bf16_256_body): v[j] holds rows
@@ -866,9 +886,11 @@ template <int WM> struct RingGeom {
 // One output tile (and k-split) of one product: block `bid` of the `nblk` blocks that product was given.  A plain launch
 // passes its own blockIdx / gridDim; a grouped launch (gemm_bf16_group) a sub-range of its grid.
 // GA: the k-contiguous A operand's rows are gathered through p.a_rowmap (ALAY == 0, WM == 4 only)
-template <int ALAY, int BLAY, int WM, int GA = 0>
+// TROWS: the fused loss reads its targets through p.mse_rowmap (forward layout only)
+template <int ALAY, int BLAY, int WM, int GA = 0, bool TROWS = false>
 __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p, const int bid, const int nblk, char* smem) {
     static_assert(!GA || (ALAY == 0 && WM == 4), "row gather: k-contiguous A on the 256x128 ring kernel");
+    static_assert(!TROWS || (ALAY == 0 && BLAY == 0 && !GA), "row-mapped loss targets: the forward layout");
     constexpr int BM = 64 * WM, NW = 2 * WM, ASUB = WM / 2;
     constexpr int STAGES = RingGeom<WM>::STAGES;
     constexpr int STAGE_BYTES = RingGeom<WM>::STAGE_BYTES;
@@ -1158,7 +1180,7 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p, const int bi
         __syncthreads();
         lut255 = l;
     }
-    wave_epilogue<ALAY, BLAY, WM>(p, acc, m0 + wm * 64, n0 + wn * 64, z, reinterpret_cast<float*>(smem) + wave * 4096, lane, lsum, lut255);
+    wave_epilogue<ALAY, BLAY, WM, false, true, TROWS>(p, acc, m0 + wm * 64, n0 + wn * 64, z, reinterpret_cast<float*>(smem) + wave * 4096, lane, lsum, lut255);
     if (mse) {
         float* red = reinterpret_cast<float*>(smem);
         __syncthreads();                       // every wave is done with its staging tile
@@ -1571,10 +1593,10 @@ __device__ __forceinline__ void gemm_bf16_256_body(const GemmParams& p, const in
 #endif
 }
 
-template <int ALAY, int BLAY, int WM, int GA = 0>
+template <int ALAY, int BLAY, int WM, int GA = 0, bool TROWS = false>
 __global__ __launch_bounds__(128 * WM, 2) void gemm_bf16(GemmParams p) {
     __shared__ __attribute__((aligned(16))) char smem[RingGeom<WM>::LDS_BYTES];
-    gemm_bf16_body<ALAY, BLAY, WM, GA>(p, blockIdx.x, gridDim.x, smem);
+    gemm_bf16_body<ALAY, BLAY, WM, GA, TROWS>(p, blockIdx.x, gridDim.x, smem);
 }
 
 // Several independent products in ONE launch (a layer's weight gradient and input gradient both consume the same dy):
@@ -2034,6 +2056,8 @@ hipError_t afr_launch_gemm(int dtype, const GemmParams& p_in, hipStream_t s) {
 #endif
     const int a = (p.flags & AFR_GEMM_A_KSTRIDED) ? 1 : 0, b = (p.flags & AFR_GEMM_B_KSTRIDED) ? 1 : 0;
     if (p.M <= 0 || p.N <= 0) return hipSuccess;
+    // row-mapped loss targets: the forward layout of the ring / tile kernels, its own instantiations
+    if (p.mse_rowmap && (!p.mse_target || a || b || p.a_rowmap || p.splitk != 1 || (dtype == AFR_BF16 && bf16_use_body256(p)))) return hipErrorInvalidValue;
     if (p.a_rowmap || p.b_rowmap || p.aux_rowmap) {
         // row gathers: A k-contiguous on the 256x128 ring kernel; aux with a bf16 output (B: grouped 256x256 launches only)
         if (dtype != AFR_BF16 || p.b_rowmap || (p.a_rowmap && (a || b || !bf16_use_wide(p))) ||
@@ -2048,6 +2072,10 @@ hipError_t afr_launch_gemm(int dtype, const GemmParams& p_in, hipStream_t s) {
 #define LB(AL, BL) do { if (wide) hipLaunchKernelGGL((bf16k::gemm_bf16<AL, BL, 4>), grid, dim3(512), 0, s, p); \
                         else hipLaunchKernelGGL((bf16k::gemm_bf16<AL, BL, 2>), grid, dim3(256), 0, s, p); } while (0)
         if (p.a_rowmap) hipLaunchKernelGGL((bf16k::gemm_bf16<0, 0, 4, 1>), grid, dim3(512), 0, s, p);
+        else if (p.mse_rowmap) {
+            if (wide) hipLaunchKernelGGL((bf16k::gemm_bf16<0, 0, 4, 0, true>), grid, dim3(512), 0, s, p);
+            else hipLaunchKernelGGL((bf16k::gemm_bf16<0, 0, 2, 0, true>), grid, dim3(256), 0, s, p);
+        }
         else if (!a && !b) LB(0, 0);
         else if (!a && b) LB(0, 1);
         else if (a && !b) LB(1, 0);
@@ -2057,7 +2085,8 @@ hipError_t afr_launch_gemm(int dtype, const GemmParams& p_in, hipStream_t s) {
         const int tiles = ((p.M + x3k::BM - 1) / x3k::BM) * ((p.N + x3k::BN - 1) / x3k::BN);
         dim3 grid(tiles * p.splitk, 1, 1), block(256, 1, 1);
 #define LX(AL, BL) hipLaunchKernelGGL((x3k::gemm_bf16x3<AL, BL>), grid, block, 0, s, p)
-        if (!a && !b) LX(0, 0);
+        if (p.mse_rowmap) hipLaunchKernelGGL((x3k::gemm_bf16x3<0, 0, true>), grid, block, 0, s, p);
+        else if (!a && !b) LX(0, 0);
         else if (!a && b) LX(0, 1);
         else if (a && !b) LX(1, 0);
         else LX(1, 1);
@@ -2066,7 +2095,8 @@ hipError_t afr_launch_gemm(int dtype, const GemmParams& p_in, hipStream_t s) {
         const int tiles = ((p.M + 127) / 128) * ((p.N + 127) / 128);
         dim3 grid(tiles * p.splitk, 1, 1), block(256, 1, 1);
 #define LF(AL, BL) hipLaunchKernelGGL((f32k::gemm_f32<AL, BL>), grid, block, 0, s, p)
-        if (!a && !b) LF(0, 0);
+        if (p.mse_rowmap) hipLaunchKernelGGL((f32k::gemm_f32<0, 0, true>), grid, block, 0, s, p);
+        else if (!a && !b) LF(0, 0);
         else if (!a && b) LF(0, 1);
         else if (a && !b) LF(1, 0);
         else LF(1, 1);

@@ -159,7 +159,9 @@ __device__ __forceinline__ void rows_times_global_u(const T* A, int lda, int nti
 }  // namespace
 
 
-template <typename T, bool TU8>
+// TROWS: the targets of glyph b are row a.rowmap[b] of a resident data set, read in place (its own instantiation: the dense
+// kernels carry no row-map code)
+template <typename T, bool TU8, bool TROWS>
 __global__ __launch_bounds__(MM<T>::NTH) void glyph1_step_kernel(Glyph1Args a) {
     using M_ = MM<T>;
     constexpr int KB = M_::KB, R = M_::R, MT = R / 16, NT = M_::NTH, NW = NT / 64;
@@ -188,6 +190,13 @@ __global__ __launch_bounds__(MM<T>::NTH) void glyph1_step_kernel(Glyph1Args a) {
     // they arrive under the gather and fc1 (asked for when a tile's MFMAs start, each tile waited ~1.5 us for them)
     constexpr int TPW = 16 / NW;
     float tv[TPW][MT][4];
+    int trow[TROWS ? MT : 1][4];          // row-mapped: the data-set row of each of the lane's glyphs, asked for once
+    if constexpr (TROWS) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) trow[m][i] = a.rowmap[b0 + min(m * 16 + 4 * q + i, nb - 1)];
+    }
 #pragma unroll
     for (int it = 0; it < TPW; ++it) {
         const int pcol = (pt0 + wave + it * NW) * 16 + r;
@@ -196,7 +205,9 @@ __global__ __launch_bounds__(MM<T>::NTH) void glyph1_step_kernel(Glyph1Args a) {
             for (int m = 0; m < MT; ++m)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const size_t ti = (size_t)(b0 + min(m * 16 + 4 * q + i, nb - 1)) * P + pcol;
+                    size_t ti;
+                    if constexpr (TROWS) ti = (size_t)trow[m][i] * P + pcol;
+                    else ti = (size_t)(b0 + min(m * 16 + 4 * q + i, nb - 1)) * P + pcol;
                     if constexpr (TU8) tv[it][m][i] = __builtin_bit_cast(float, (unsigned)reinterpret_cast<const uint8_t*>(a.target)[ti]);
                     else tv[it][m][i] = reinterpret_cast<const float*>(a.target)[ti];
                 }
@@ -440,33 +451,33 @@ hipError_t afr_launch_transpose_bf16(const float* W, bf16_t* WT, int N, int K, h
     hipLaunchKernelGGL(transpose_bf16_kernel, dim3((unsigned)((n + 255) / 256 > 512 ? 512 : (n + 255) / 256)), dim3(256), 0, s, W, WT, N, K);
     return hipGetLastError();
 }
+// one instantiation: its dynamic-LDS limit is raised once per device (devices 0..7 remembered), then the launch
+template <typename T, bool TU8, bool TROWS>
+static hipError_t launch_glyph1(const Glyph1Args& a, int nblk, size_t lds, int dev, hipStream_t s) {
+    static size_t done[8];
+    if (lds > 48 * 1024 && (dev < 0 || dev >= 8 || done[dev] < lds)) {
+        hipError_t e = hipFuncSetAttribute((const void*)glyph1_step_kernel<T, TU8, TROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        if (dev >= 0 && dev < 8) done[dev] = lds;
+    }
+    hipLaunchKernelGGL((glyph1_step_kernel<T, TU8, TROWS>), dim3(nblk), dim3(MM<T>::NTH), lds, s, a);
+    return hipSuccess;
+}
 hipError_t afr_launch_glyph1_step(int dtype, const Glyph1Args& a, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;
     const int R = afr_glyph1_rows(dtype);
     const size_t lds = afr_glyph1_lds_bytes(dtype, a.E, a.N1, a.P, a.vocab + a.n_fonts);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    static size_t set16[16], set32[16];
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
-    const bool u8 = a.tdtype == AFR_TARGET_U8;
-    const void* kern = dtype == AFR_BF16 ? (u8 ? (const void*)glyph1_step_kernel<bf16_t, true> : (const void*)glyph1_step_kernel<bf16_t, false>)
-                                         : (u8 ? (const void*)glyph1_step_kernel<float, true> : (const void*)glyph1_step_kernel<float, false>);
-    size_t* done = (dtype == AFR_BF16 ? set16 : set32) + (u8 ? 0 : 8);          // devices 0..7 per (dtype, target type)
-    if (lds > 48 * 1024 && (dev < 0 || dev >= 8 || done[dev] < lds)) {
-        e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 8) done[dev] = lds;
-    }
     if (a.cs < 1 || (a.P / 16) % a.cs) return hipErrorInvalidValue;
     const int nblk = (a.B + R - 1) / R * a.cs;
-    const int NTL = dtype == AFR_BF16 ? MM<bf16_t>::NTH : MM<float>::NTH;
-    if (dtype == AFR_BF16) {
-        if (u8) hipLaunchKernelGGL((glyph1_step_kernel<bf16_t, true>), dim3(nblk), dim3(NTL), lds, s, a);
-        else hipLaunchKernelGGL((glyph1_step_kernel<bf16_t, false>), dim3(nblk), dim3(NTL), lds, s, a);
-    } else {
-        if (u8) hipLaunchKernelGGL((glyph1_step_kernel<float, true>), dim3(nblk), dim3(NTL), lds, s, a);
-        else hipLaunchKernelGGL((glyph1_step_kernel<float, false>), dim3(nblk), dim3(NTL), lds, s, a);
-    }
+    const bool u8 = a.tdtype == AFR_TARGET_U8, rows = a.rowmap != nullptr;
+#define G1(T, U8, RW) launch_glyph1<T, U8, RW>(a, nblk, lds, dev, s)
+    if (dtype == AFR_BF16) e = u8 ? (rows ? G1(bf16_t, true, true) : G1(bf16_t, true, false)) : (rows ? G1(bf16_t, false, true) : G1(bf16_t, false, false));
+    else e = u8 ? (rows ? G1(float, true, true) : G1(float, true, false)) : (rows ? G1(float, false, true) : G1(float, false, false));
+#undef G1
+    if (e != hipSuccess) return e;
     return hipGetLastError();
 }

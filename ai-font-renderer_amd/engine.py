@@ -76,6 +76,7 @@ class Engine:
         self.seed, self.rank, self.flags = int(seed), int(rank), int(flags)
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         self._plan = None
+        self._ds = None       # the bound data set: (x, font, target, target dtype code, rows, L), see bind_dataset
         self._make_plan(self.max_batch)
         n = self.lib.afr_param_elems(self._plan)
         self.n_flat = int(n)
@@ -119,6 +120,37 @@ class Engine:
             self.workspace = torch.zeros(self.ws_bytes, dtype=torch.uint8, device=self.device)
         _lib.check(self.lib.afr_bind(self._plan, _ptr(self.flat_params), _ptr(self.flat_grads), _ptr(self.exp_avg),
                                      _ptr(self.exp_avg_sq), _ptr(self.workspace), self.ws_bytes))
+        self._bind_ds()
+
+    def _bind_ds(self):
+        if self._ds is not None:
+            x, font, t, td, n, L = self._ds
+            _lib.check(self.lib.afr_bind_dataset(self._plan, _ptr(x), _ptr(font), _ptr(t), td, n, L))
+
+    def bind_dataset(self, x, target, font=None):
+        """Make a data set resident and bind it: codes int64 [N, L] (sheet) or [N] (glyph / pixel, with font ids [N] when the
+        model has fonts), targets uint8 or float32 [N, pixels] / [N, H, W].  forward_rows / loss_grad_rows / forward_loss_rows /
+        train_step_rows then take a vector of row indices; the kernels read the targets where they lie.  The engine holds
+        references to the tensors, and binds them again when ensure_batch re-creates the plan."""
+        x, font = self._prep_x(x, font)
+        t, td = self._target(target)
+        if isinstance(self.cfg, SheetConfig):
+            if x.dim() != 2:
+                raise ValueError("sheet model takes int64 [N, L] codes")
+            L = x.shape[1]
+        else:
+            x, L = x.reshape(-1), 1
+        n = x.shape[0]
+        t = t.view(t.shape[0], -1)
+        if t.shape != (n, self.pixels) or (font is not None and font.reshape(-1).shape[0] != n):
+            raise ValueError(f"data set of {n} rows: targets {tuple(t.shape)} (expected {(n, self.pixels)}) / font ids do not match")
+        self._ds = (x, None if font is None else font.reshape(-1), t, td, n, L)
+        self._bind_ds()
+
+    def _rows(self, rows):
+        if self._ds is None:
+            raise _lib.AfrError("no data set bound: call bind_dataset before stepping by rows")
+        return rows.to(self.device, dtype=torch.int64, non_blocking=True).contiguous().reshape(-1)
 
     def ensure_batch(self, B):
         """Grow the plan's workspace for a larger batch; parameters, gradients and moments stay where they are."""
@@ -187,6 +219,60 @@ class Engine:
         h, w = (self.cfg.sheet_h, self.cfg.sheet_w) if isinstance(self.cfg, SheetConfig) else (self.cfg.out_h, self.cfg.out_w)     # glyph / pixel
         return y.view(B, h, w)
 
+    def forward_rows(self, rows, training=False, step=0, want_output=True):
+        """forward() on the rows `rows` (int64 indices, duplicates allowed) of the bound data set."""
+        rows = self._rows(rows)
+        if self.micro_batch and rows.shape[0] > self.micro_batch:
+            outs = [self.forward_rows(rows[lo:lo + self.micro_batch], training, step, want_output) for lo in range(0, rows.shape[0], self.micro_batch)]
+            return torch.cat(outs) if want_output else None
+        B = rows.shape[0]
+        self.ensure_batch(B)
+        y = torch.empty(B, self.pixels, dtype=torch.float32, device=self.device) if want_output else None
+        self._call(self.lib.afr_forward_rows, self._plan, _ptr(rows), B, _ptr(y), int(bool(training)), int(step))
+        self._keep = (rows, None)
+        if y is None:
+            return None
+        h, w = (self.cfg.sheet_h, self.cfg.sheet_w) if isinstance(self.cfg, SheetConfig) else (self.cfg.out_h, self.cfg.out_w)
+        return y.view(B, h, w)
+
+    def loss_grad_rows(self, rows, mean_elems=None):
+        """loss_grad() against the targets of data-set rows `rows` (the rows of the forward before it)."""
+        rows = self._rows(rows)
+        B = rows.shape[0]
+        me = int(mean_elems) if mean_elems is not None else B * self.pixels
+        self._call(self.lib.afr_loss_grad_rows, self._plan, _ptr(rows), B, me, _ptr(self.loss_accum))
+        self._keep_t = rows
+
+    def forward_loss_rows(self, rows, step=None, mean_elems=None):
+        """forward_loss() on rows of the bound data set."""
+        rows = self._rows(rows)
+        B = rows.shape[0]
+        if self.micro_batch and B > self.micro_batch:
+            raise ValueError(f"forward_loss / backward work on one micro-batch (<= {self.micro_batch} samples); a batch of {B} "
+                             "accumulates through train_step_rows")
+        self.ensure_batch(B)
+        me = int(mean_elems) if mean_elems is not None else B * self.pixels
+        st = int(step if step is not None else self.t + 1)
+        self._call(self.lib.afr_forward_loss_rows, self._plan, _ptr(rows), B, me, _ptr(self.loss_accum), st)
+        self._keep = self._keep_t = (rows, None)
+
+    def train_step_rows(self, rows, step=None, lr=1e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=5e-4, mean_elems=None, do_step=True):
+        """train_step() on rows of the bound data set: one C call, no gather in front of it."""
+        rows = self._rows(rows)
+        B = rows.shape[0]
+        if self.micro_batch and B > self.micro_batch:
+            def micro(lo, hi, st, me):
+                self.train_step_rows(rows[lo:hi], step=st, mean_elems=me, do_step=False)
+            return self._train_step_accumulated(B, micro, step, lr, betas, eps, weight_decay, mean_elems, do_step)
+        self.ensure_batch(B)
+        me = int(mean_elems) if mean_elems is not None else B * self.pixels
+        if do_step:
+            self.t += 1
+        st = int(step if step is not None else self.t)
+        self._call(self.lib.afr_train_step_rows, self._plan, _ptr(rows), B, me, _ptr(self.loss_accum), st,
+                   int(bool(do_step)), lr, betas[0], betas[1], eps, weight_decay, max(self.t, 1))
+        self._keep = self._keep_t = (rows, None)
+
     def _target(self, target):
         if target.dtype == torch.uint8:
             return target.to(self.device, non_blocking=True).contiguous(), _lib.AFR_TARGET_U8
@@ -253,7 +339,11 @@ class Engine:
         """zero_grad -> forward -> loss -> backward -> AdamW, one C call (model.py:292-310)."""
         x, font = self._prep_x(x, font)
         if self.micro_batch and x.shape[0] > self.micro_batch:
-            return self._train_step_accumulated(x, target, font, step, lr, betas, eps, weight_decay, mean_elems, do_step)
+            t, _ = self._target(target)
+
+            def micro(lo, hi, st, me):
+                self.train_step(x[lo:hi], t[lo:hi], font=None if font is None else font[lo:hi], step=st, mean_elems=me, do_step=False)
+            return self._train_step_accumulated(x.shape[0], micro, step, lr, betas, eps, weight_decay, mean_elems, do_step)
         self.ensure_batch(x.shape[0])
         t, td = self._target(target)
         if isinstance(self.cfg, SheetConfig):
@@ -270,20 +360,18 @@ class Engine:
         self._keep = (x, font)
         self._keep_t = t
 
-    def _train_step_accumulated(self, x, target, font, step, lr, betas, eps, weight_decay, mean_elems, do_step):
+    def _train_step_accumulated(self, B, micro, step, lr, betas, eps, weight_decay, mean_elems, do_step):
         """Gradient accumulation: the batch in micro-steps of self.micro_batch samples (forward + loss + backward each, the loss
-        and its gradient scaled for the WHOLE batch through mean_elems), gradients summed in micro-step order, one AdamW step."""
-        B = x.shape[0]
+        and its gradient scaled for the WHOLE batch through mean_elems), gradients summed in micro-step order, one AdamW step.
+        micro(lo, hi, step, mean_elems) runs batch rows [lo, hi) without an optimizer step (dense tensors or data-set rows)."""
         me = int(mean_elems) if mean_elems is not None else B * self.pixels
-        t, _ = self._target(target)
         if self._grad_acc is None:
             self._grad_acc = torch.empty_like(self.flat_grads)
         st = int(step if step is not None else self.t + (1 if do_step else 0))
         for i, lo in enumerate(range(0, B, self.micro_batch)):
             hi = min(B, lo + self.micro_batch)
             # (models with dropout: micro-step i draws its masks from stream st * 65536 + i)
-            self.train_step(x[lo:hi], t[lo:hi], font=None if font is None else font[lo:hi], step=st * 65536 + i if step is None else st,
-                            mean_elems=me, do_step=False)
+            micro(lo, hi, st * 65536 + i if step is None else st, me)
             # acc (+)= this micro-step's gradient, by the library's own slab-sum kernel (fixed order: micro-step by micro-step)
             self._call(self.lib.afr_op_reduce, _ptr(self._grad_acc), _ptr(self.flat_grads), 1, self.n_flat, self.n_flat, 1.0, int(i > 0))
         self._call(self.lib.afr_op_reduce, _ptr(self.flat_grads), _ptr(self._grad_acc), 1, self.n_flat, self.n_flat, 1.0, 0)

@@ -263,10 +263,47 @@ def _dist():
     return None, 1, 0
 
 
+def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True):
+    """One epoch of the reference loop (model.py:288-333): the training pass over order.train_epoch(), then the validation
+    pass; returns the two means of per-batch mean losses.  by_rows: the engine has the data set bound (Engine.bind_dataset)
+    and every step is driven by this rank's slice of the epoch's index vector -- the kernels read the rows where they lie.
+    by_rows=False gathers each batch with index_select and hands the step dense tensors (the form tools/epoch_bench.py
+    measures the other against)."""
+    from .parallel import shard_rows
+    eng = model.engine
+    pixels = targets[0].numel()
+    model.train()
+    idx = order.train_epoch().to(inputs.device)
+    nb = _num_batches(order.train_size, batch_size)
+    for b in range(nb):
+        rows = idx[b * batch_size:(b + 1) * batch_size]
+        mine = rows[shard_rows(rows.numel(), rank, world)]
+        hyper = dict(step=model._next_step(), lr=lr, betas=ADAM_BETAS, weight_decay=WEIGHT_DECAY)
+        if by_rows:
+            stepper.step_rows(mine, rows.numel() * pixels, **hyper)
+        else:
+            stepper.step(inputs.index_select(0, mine), targets.index_select(0, mine), None, rows.numel() * pixels, **hyper)
+    avg_train_loss = stepper.global_loss() / nb                 # mean of per-batch means (model.py:311,333)
+
+    model.eval()
+    vidx = order.val_epoch().to(inputs.device)
+    nvb = _num_batches(order.val_size, batch_size)
+    for b in range(nvb):
+        rows = vidx[b * batch_size:(b + 1) * batch_size]
+        mine = rows[shard_rows(rows.numel(), rank, world)]
+        if by_rows:
+            eng.forward_rows(mine, training=False, want_output=False)
+            eng.loss_grad_rows(mine, mean_elems=rows.numel() * pixels)
+        else:
+            eng.forward(inputs.index_select(0, mine), training=False, want_output=False)
+            eng.loss_grad(targets.index_select(0, mine), mean_elems=rows.numel() * pixels)
+    return avg_train_loss, stepper.global_loss() / max(nvb, 1)
+
+
 def train_attention_model(model, dataset, batch_size):
     """Reference model.py:209-384: config.txt, 80/20 split, AdamW + ReduceLROnPlateau + early stopping, progress
     prints and test-string dumps every 5 epochs, training_results.txt.  Returns the model."""
-    from .parallel import DataParallelStepper, shard_rows
+    from .parallel import DataParallelStepper
     dist, world, rank = _dist()
     eng = model.engine
     os.makedirs(OUTPUT_DIR, exist_ok=True)
@@ -289,7 +326,7 @@ def train_attention_model(model, dataset, batch_size):
     inputs = inputs.to(device)
     t8 = helpers.targets_as_uint8(targets)
     targets = (t8 if t8 is not None else targets.to(torch.float32)).to(device)
-    pixels = SHEET_HEIGHT * SHEET_WIDTH
+    eng.bind_dataset(inputs, targets)       # a batch is a vector of row indices from here on: nothing is gathered per step
 
     # ReduceLROnPlateau is host logic on one float; torch's own class drives it through a one-parameter stand-in
     lr_holder = torch.optim.SGD([nn.Parameter(torch.zeros(1))], lr=LEARNING_RATE)
@@ -301,26 +338,8 @@ def train_attention_model(model, dataset, batch_size):
     best_model_state = None
     epoch = -1
     for epoch in range(NUM_EPOCHS):
-        model.train()
         lr = lr_holder.param_groups[0]["lr"]
-        idx = order.train_epoch().to(device)
-        nb = _num_batches(order.train_size, batch_size)
-        for b in range(nb):
-            rows = idx[b * batch_size:(b + 1) * batch_size]
-            mine = rows[shard_rows(rows.numel(), rank, world)]
-            stepper.step(inputs.index_select(0, mine), targets.index_select(0, mine), None, rows.numel() * pixels,
-                         step=model._next_step(), lr=lr, betas=ADAM_BETAS, weight_decay=WEIGHT_DECAY)
-        avg_train_loss = stepper.global_loss() / nb                 # mean of per-batch means (model.py:311,333)
-
-        model.eval()
-        vidx = order.val_epoch().to(device)
-        nvb = _num_batches(order.val_size, batch_size)
-        for b in range(nvb):
-            rows = vidx[b * batch_size:(b + 1) * batch_size]
-            mine = rows[shard_rows(rows.numel(), rank, world)]
-            eng.forward(inputs.index_select(0, mine), training=False, want_output=False)
-            eng.loss_grad(targets.index_select(0, mine), mean_elems=rows.numel() * pixels)
-        avg_val_loss = stepper.global_loss() / max(nvb, 1)
+        avg_train_loss, avg_val_loss = _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True)
 
         scheduler.step(avg_val_loss)
         is_best = avg_val_loss < best_val_loss

@@ -12,7 +12,7 @@ as an opt-in (AFR_DP_SCHEDULE=shard) until a multi-GPU node has run it.  Every s
 each rank draws its own dropout stream (rank is part of the counter-hash key).
 
 `engine` is anything with train_step(x, target, font=, mean_elems=, do_step=), flat_grads, adamw_step(**hyper)
-and loss_accum: the HIP Engine in production; tests drive the same logic on CPU (gloo) with a stand-in.
+and loss_accum (step_rows: train_step_rows(rows, mean_elems=, do_step=) on a data set bound to the engine): the HIP Engine in production; tests drive the same logic on CPU (gloo) with a stand-in.
 """
 import os
 
@@ -97,20 +97,36 @@ class DataParallelStepper:
     def step(self, x, target, font=None, mean_elems=None, **hyper):
         """One optimiser step on this rank's shard.  mean_elems = global_rows * pixels."""
         eng = self.engine
+        self._step(x.shape[0], mean_elems, hyper,
+                   lambda do_step, **kw: eng.train_step(x, target, font=font, mean_elems=mean_elems, do_step=do_step, **kw),
+                   lambda **kw: eng.forward_loss(x, target, font=font, mean_elems=mean_elems, **kw))
+
+    def step_rows(self, rows, mean_elems=None, **hyper):
+        """step() on rows of the data set bound to the engine (Engine.bind_dataset): `rows` is this rank's shard of the batch's
+        index vector.  The same schedules; nothing is gathered in front of the step."""
+        eng = self.engine
+        self._step(rows.shape[0], mean_elems, hyper,
+                   lambda do_step, **kw: eng.train_step_rows(rows, mean_elems=mean_elems, do_step=do_step, **kw),
+                   lambda **kw: eng.forward_loss_rows(rows, mean_elems=mean_elems, **kw))
+
+    def _step(self, n_rows, mean_elems, hyper, train_step, forward_loss):
+        """The schedules of one step.  train_step(do_step, **hyper) and forward_loss(step=) are the engine calls on this
+        rank's shard, by dense tensors (step) or by data-set rows (step_rows)."""
+        eng = self.engine
         if (self.world == 1 and not (_schedule() == "shard-force" and self.dist is not None)) or self.dist is None:
-            eng.train_step(x, target, font=font, mean_elems=mean_elems, do_step=True, **hyper)
+            train_step(True, **hyper)
             return
         opt = {k: v for k, v in hyper.items() if k in ("lr", "betas", "eps", "weight_decay")}
         stages = getattr(eng, "backward_stages", 0)
         mb = getattr(eng, "micro_batch", None)
-        accumulating = bool(mb) and x.shape[0] > mb          # gradient accumulation: the sum exists only after the last micro-step
+        accumulating = bool(mb) and n_rows > mb          # gradient accumulation: the sum exists only after the last micro-step
         if stages and eng.flat_grads.numel() * 4 >= OVERLAP_MIN_BYTES and not self.sharded() and not accumulating:
             # Backward runs last layer first.  Two collectives per step: the last layer's gradient range (half of the
             # bytes in the glyph nets, 99.98 % in the sheet model) is all-reduced ASYNCHRONOUSLY as soon as stage 0 has
             # produced it and overlaps the rest of the backward pass; everything else is one contiguous range
             # [0, start of that range) reduced when the last stage is done.  (One collective per stage overlapped more
             # bytes but paid ~20 us of cross-stream event hand-offs per collective: measured with a world of one.)
-            eng.forward_loss(x, target, font=font, step=hyper.get("step"), mean_elems=mean_elems)
+            forward_loss(step=hyper.get("step"))
             first = eng.backward_stage(0)
             work = self.dist.all_reduce(first, async_op=True)
             for s in range(1, stages):
@@ -121,7 +137,7 @@ class DataParallelStepper:
             work.wait()
         elif self.sharded():
             # sharded optimizer: backward -> reduce-scatter -> AdamW on this rank's slice -> all-gather of the parameters
-            eng.train_step(x, target, font=font, mean_elems=mean_elems, do_step=False, **hyper)
+            train_step(False, **hyper)
             ws = self.dist.get_world_size()               # == self.world except under shard-force (a world of one)
             rk = self.rank if ws == self.world else self.dist.get_rank()
             n = eng.flat_grads.numel() // ws
@@ -132,7 +148,7 @@ class DataParallelStepper:
                 eng.sync_params()               # bf16 mode: the shadow of the slices other ranks updated
             return
         else:
-            eng.train_step(x, target, font=font, mean_elems=mean_elems, do_step=False, **hyper)
+            train_step(False, **hyper)
             if GRAD_BF16 and getattr(eng, "dtype", "f32") == "bf16":
                 g16 = eng.flat_grads.to(torch.bfloat16)
                 self.dist.all_reduce(g16)

@@ -157,9 +157,33 @@ int afr_train_step(afr_plan* plan, const int64_t* x, const int64_t* font, const 
                    uint64_t step, int do_step, float lr, float beta1, float beta2, float eps,
                    float weight_decay, int64_t t, void* stream);
 
+/* ---- HBM-resident data set, addressed by row index (the whole data set lives on the device) ----
+ * afr_bind_dataset attaches caller-owned device buffers: x int64 [n_rows][L] codes (glyph / pixel models: L = 1), font
+ * int64 [n_rows] or NULL (required when n_fonts > 0), target [n_rows][out_h*out_w] uint8 or float32.  All three NULL
+ * unbinds.  Host-only: nothing is launched or copied, the buffers are not read before an afr_*_rows call.  n_rows < 2^31
+ * (AFR_EUNSUPPORTED beyond); the target buffer may be larger than 2 GiB (it is addressed with 64-bit arithmetic).
+ * The four afr_*_rows calls are the entry points of the same name with a row vector in place of the dense batch: `rows`
+ * is a device vector of B int64 indices into the data set, duplicates allowed; batch row b means data-set row rows[b].
+ * Dropout is keyed by the in-batch row b, mean_elems / loss_accum / step / the optimizer arguments mean what they mean
+ * there, and afr_backward / afr_backward_stage / afr_adamw_step follow as usual.  The targets are read where they lie
+ * (the loss kernels take the row as an index); codes and font ids of the batch are staged in the workspace by one small
+ * kernel, after which (in stream order) `rows` is not read again.  An index outside [0, n_rows) sets bit 2 of the error
+ * word and is clamped before anything is addressed with it.  Errors, in this order: no data set bound -> AFR_ESTATE;
+ * rows NULL or B outside 1..max_batch -> AFR_EINVAL. */
+int afr_bind_dataset(afr_plan* plan, const int64_t* x, const int64_t* font, const void* target, int target_dtype,
+                     int64_t n_rows, int L);
+int afr_forward_rows(afr_plan* plan, const int64_t* rows, int B, float* y, int training, uint64_t step, void* stream);
+/* after afr_forward_rows on the same rows */
+int afr_loss_grad_rows(afr_plan* plan, const int64_t* rows, int B, int64_t mean_elems, float* loss_accum, void* stream);
+int afr_forward_loss_rows(afr_plan* plan, const int64_t* rows, int B, int64_t mean_elems, float* loss_accum, uint64_t step,
+                          void* stream);
+int afr_train_step_rows(afr_plan* plan, const int64_t* rows, int B, int64_t mean_elems, float* loss_accum, uint64_t step,
+                        int do_step, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t t, void* stream);
+
 /* Set / read the device-side error word (bit 0: an embedding index outside [0,vocab), the
  * condition on which the reference raises IndexError; model.py:136,167; bit 1: a cooperative split-K
- * workgroup gave up waiting for its partners -- the step's results are invalid).  Reading synchronises and clears. */
+ * workgroup gave up waiting for its partners -- the step's results are invalid; bit 2: a row index of an afr_*_rows call
+ * outside the bound data set, clamped into it).  Reading synchronises and clears. */
 int afr_error_flags(afr_plan* plan, void* stream, uint32_t* flags_out);
 
 /* Name and average duration (ms, hipEvent-timed on the launch stream) of the plan's dominant
