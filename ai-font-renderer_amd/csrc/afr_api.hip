@@ -55,6 +55,7 @@ struct Tensor {
 };
 
 struct ProfRec { int tag; hipEvent_t a, b; double flops, bytes; };
+struct AdamArgs { float lr, b1, b2, eps, wd; int64_t t; };      // the optimizer arguments of afr_train_step
 
 struct afr_plan {
     afr_config cfg;                // cfg.dtype is the ACTIVATION dtype (AFR_F32 or AFR_BF16) every non-GEMM kernel runs in
@@ -98,7 +99,7 @@ struct afr_plan {
     size_t o_shadow2 = 0; int shadow_cur = 0;
     // hyper-parameters of the optimizer step in progress (afr_train_step): set while backward runs, so that weight-gradient
     // products with a cooperative split-K tail apply AdamW themselves; adam_done lists the tensors they have updated
-    bool step_on = false; float st_decay = 1.f, st_b1 = 0.f, st_b2 = 0.f, st_eps = 0.f, st_step = 0.f, st_rsqrt_bc2 = 1.f;
+    bool step_on = false; AdamArgs st{};
     std::vector<int64_t> adam_done;
     // pixel-token transformer (AFR_KIND_PIXEL): per-block parameter offsets and the forward's workspace
     struct PixBlock { int64_t ln1g, ln1b, win, bin, wo, bo, ln2g, ln2b, w1, b1, w2, b2; };
@@ -271,7 +272,7 @@ extern "C" int afr_plan_create(const afr_config* c, afr_plan** out) {
             if ((size_t)c->hidden[i] > maxw) maxw = (size_t)c->hidden[i];
         }
         p->o_mbits.assign(c->n_hidden + 1, 0);
-        if (c->dtype == AFR_BF16 && !(c->reserved & 128))
+        if (c->dtype == AFR_BF16 && !(c->reserved & AFR_CFG_RELU_MASK_FROM_ACT))
             for (int i = 1; i < c->n_hidden; ++i)          // layer 0's output comes from the table / gather kernels, not a GEMM
                 if (c->hidden[i] % 8 == 0) p->o_mbits[i] = carve(B * (size_t)(c->hidden[i] / 8));
         p->o_u = carve(B * Pix * ab);
@@ -305,7 +306,7 @@ extern "C" int afr_plan_create(const afr_config* c, afr_plan** out) {
         p->o_slab_e = carve(eb * (size_t)(c->vocab + c->n_fonts) * E * sizeof(float));
         {
             const size_t ncombo = (size_t)c->vocab * (c->n_fonts > 0 ? c->n_fonts : 1);
-            if (c->dtype == AFR_BF16 && p->l1f && c->n_hidden >= 2 && ncombo <= 1024 && !(c->reserved & (64 | 16))) {
+            if (c->dtype == AFR_BF16 && p->l1f && c->n_hidden >= 2 && ncombo <= 1024 && !(c->reserved & (AFR_CFG_NO_COMBO_TABLE | AFR_CFG_L1_BWD_UNFUSED))) {
                 p->combo_ok = true;
                 p->h1c_ld = c->hidden[0];
                 p->o_h1c = carve(ncombo * p->h1c_ld * 2); p->o_h0c = carve(ncombo * E * 2); p->o_cidx = carve(B * sizeof(int));
@@ -584,10 +585,13 @@ extern "C" int afr_profile_dump(afr_plan* p, char* buf, int cap) {
 // ------------------------------------------------------------------------------------ helpers
 struct FusedLoss { const void* target; int tdtype; int64_t mean_elems; float* loss_accum;
                    const int* rowmap = nullptr; };       // targets of batch row b = row rowmap[b] of `target` (afr_*_rows); NULL = row b
-struct FusedAdam { float *p, *m, *v; bf16_t* shadow; float decay, b1, b2, eps, step_size, rsqrt_bc2; };
-struct CoopArgs { float* ws; unsigned* cnt; unsigned target; };
-struct RowMaps { const int* a; const int* b; const int* aux;        // GemmParams::a_rowmap / b_rowmap / aux_rowmap
-                 unsigned char* mask_out = nullptr; const unsigned char* mask_in = nullptr; int ldmask = 0; };   // ... mask_out / mask_in
+// the six AdamW scalars of a fused update (GemmParams::ad_* / RTable::ad_*), as afr_launch_adamw derives them from its arguments
+template <class T> static void set_adam(T& o, const AdamArgs& h) {
+    const float bc1 = (float)(1.0 - std::pow((double)h.b1, (double)h.t));
+    const float bc2 = (float)(1.0 - std::pow((double)h.b2, (double)h.t));
+    o.ad_decay = 1.f - h.lr * h.wd; o.ad_b1 = h.b1; o.ad_b2 = h.b2; o.ad_eps = h.eps; o.ad_step = h.lr / bc1;
+    o.ad_rsqrt_bc2 = (float)(1.0 / std::sqrt((double)bc2));
+}
 // the bf16 weight shadow the GEMMs read / the one a fused optimizer step writes (the same buffer unless the plan has two)
 static inline bf16_t* shadow_rd(const afr_plan* p) {
     if (p->cfg.dtype != AFR_BF16) return nullptr;
@@ -602,48 +606,70 @@ static inline const void* weight_ptr(const afr_plan* p, int64_t off) {
     if (p->cfg.dtype == AFR_BF16) return shadow_rd(p) + off;
     return p->P + off;
 }
-static int run_gemm(afr_plan* p, hipStream_t s, int flags, const void* A, const void* B, void* C, const float* bias,
-                    const void* aux, int M, int N, int K, int lda, int ldb, int ldc, int ldaux, int splitk,
-                    long long slab_stride, float* colsum = nullptr, long long colsum_stride = 0, const FusedLoss* fl = nullptr,
-                    const FusedAdam* fa = nullptr, const CoopArgs* coop = nullptr, const RowMaps* rm = nullptr) {
-    const int gdt = p->gemm_dtype;
-    if (gdt == AFR_BF16) {
-        const bool ak = flags & AFR_GEMM_A_KSTRIDED, bk = flags & AFR_GEMM_B_KSTRIDED;
-        const long long ea = (long long)(ak ? K : M) * lda * 2, ebb = (long long)(bk ? K : N) * ldb * 2;
-        if (ea >= (1ll << 31) || ebb >= (1ll << 31)) return fail(AFR_EUNSUPPORTED, "bf16 GEMM operand of 2 GiB or more (%lld / %lld bytes)", ea, ebb);
-    }
+// The three products of a Linear y[B][N] = x[B][K] . W[N][K]^T + b (gemm.hip) as launch descriptions: M/N/K, the operand
+// orientations and dense row-major leading dimensions follow from (B, N, K); `ep` adds epilogue flags.  Whatever else a launch
+// carries (row maps, bit masks, fused AdamW, cooperative split-K) the caller sets on the result, by field name.
+static inline int out_flag(const afr_plan* p) { return p->cfg.dtype == AFR_BF16 ? AFR_GEMM_OUT_BF16 : 0; }
+static GemmParams lin_desc(int flags, const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc) {
     GemmParams g;
-    if (fa) {
-        g.ad_p = fa->p; g.ad_m = fa->m; g.ad_v = fa->v; g.ad_shadow = fa->shadow;
-        g.ad_decay = fa->decay; g.ad_b1 = fa->b1; g.ad_b2 = fa->b2; g.ad_eps = fa->eps; g.ad_step = fa->step_size; g.ad_rsqrt_bc2 = fa->rsqrt_bc2;
-    }
-    g.colsum = colsum; g.colsum_stride = colsum_stride;
-    if (rm) { g.a_rowmap = rm->a; g.b_rowmap = rm->b; g.aux_rowmap = rm->aux; g.mask_out = rm->mask_out; g.mask_in = rm->mask_in; g.ldmask = rm->ldmask; }
-    if (coop) { g.coop_ws = coop->ws; g.coop_cnt = coop->cnt; g.coop_target = coop->target; g.err = (uint32_t*)(p->ws + p->o_err); }
-    if (fl) {
-        float* scratch = (float*)(p->ws + p->o_loss);
-        g.mse_target = fl->target; g.mse_rowmap = fl->rowmap; g.mse_target_dtype = fl->tdtype; g.mse_inv_n = (float)(1.0 / (double)fl->mean_elems);
-        g.mse_partial = scratch + 1040; g.mse_counter = reinterpret_cast<unsigned*>(scratch + 1032); g.mse_loss_accum = fl->loss_accum;
-    }
-    g.A = A; g.B = B; g.C = C; g.bias = bias; g.aux = aux;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldaux = ldaux;
-    g.flags = flags; g.splitk = splitk; g.slab_stride = slab_stride;
+    g.A = A; g.B = B; g.C = C; g.bias = nullptr; g.aux = nullptr; g.M = M; g.N = N; g.K = K;
+    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldaux = 0; g.flags = flags; g.splitk = 1; g.slab_stride = 0;
+    return g;
+}
+// forward: y = x . W^T + b, in the plan's activation dtype
+static GemmParams lin_fwd(const afr_plan* p, const afr_plan::Layer& l, const void* x, void* y, int B, int ep = 0) {
+    GemmParams g = lin_desc(AFR_GEMM_BIAS | out_flag(p) | ep, x, weight_ptr(p, l.w_off), y, B, l.N, l.K, l.K, l.K, l.N);
+    g.bias = p->P + l.b_off;
+    return g;
+}
+// input gradient: dx = dy . W; aux [B][K] (the layer's input, NULL = none) masks it with ReLU's gate
+static GemmParams lin_dx(const void* dy, const void* W, void* dx, const void* aux, int B, int N, int K, int ep) {
+    GemmParams g = lin_desc(AFR_GEMM_B_KSTRIDED | (aux ? AFR_GEMM_RELU_MASK : 0) | ep, dy, W, dx, B, K, N, N, K, K);
+    g.aux = aux; g.ldaux = aux ? K : 0;
+    return g;
+}
+static GemmParams lin_dx(const afr_plan* p, const afr_plan::Layer& l, const void* dy, void* dx, const void* aux, int B) {
+    return lin_dx(dy, weight_ptr(p, l.w_off), dx, aux, B, l.N, l.K, out_flag(p));
+}
+// weight gradient: dW = dy^T . x with db as the fused column sum; sk > 1: one partial of each per K-slice
+static GemmParams lin_dw(const void* dy, const void* x, float* dW, float* db, int B, int N, int K, int sk = 1, long long slab_stride = 0) {
+    GemmParams g = lin_desc(AFR_GEMM_A_KSTRIDED | AFR_GEMM_B_KSTRIDED, dy, x, dW, N, K, B, N, K, K);
+    g.splitk = sk; g.slab_stride = slab_stride; g.colsum = db; g.colsum_stride = sk > 1 ? N : 0;
+    return g;
+}
+// the loss fused into the epilogue of the last forward product
+static void fuse_loss(const afr_plan* p, GemmParams& g, const FusedLoss& fl) {
+    float* scratch = (float*)(p->ws + p->o_loss);
+    g.mse_target = fl.target; g.mse_rowmap = fl.rowmap; g.mse_target_dtype = fl.tdtype; g.mse_inv_n = (float)(1.0 / (double)fl.mean_elems);
+    g.mse_partial = scratch + 1040; g.mse_counter = reinterpret_cast<unsigned*>(scratch + 1032); g.mse_loss_accum = fl.loss_accum;
+}
+// the bf16 LDS-DMA path addresses an operand with 32-bit byte offsets: 2 GiB per operand
+static int check_operand_bytes(const GemmParams& g) {
+    const long long ea = (long long)((g.flags & AFR_GEMM_A_KSTRIDED) ? g.K : g.M) * g.lda * 2;
+    const long long eb = (long long)((g.flags & AFR_GEMM_B_KSTRIDED) ? g.K : g.N) * g.ldb * 2;
+    if (ea < (1ll << 31) && eb < (1ll << 31)) return AFR_OK;
+    return fail(AFR_EUNSUPPORTED, "a bf16 GEMM operand must be smaller than 2 GiB (A %lld bytes, B %lld bytes)", ea, eb);
+}
+static int run_gemm(afr_plan* p, hipStream_t s, const GemmParams& g) {
+    const int gdt = p->gemm_dtype, M = g.M, N = g.N, K = g.K;
+    int rc;
+    if (gdt == AFR_BF16 && (rc = check_operand_bytes(g))) return rc;
     const double eb = gdt == AFR_BF16 ? 2.0 : 4.0;
-    const double ob = (flags & AFR_GEMM_OUT_BF16) ? 2.0 : 4.0;
+    const double ob = (g.flags & AFR_GEMM_OUT_BF16) ? 2.0 : 4.0;
     // algorithmic bytes: operands once + the product once (split-K partial slabs are an implementation choice, not
     // algorithmic output); with the fused optimizer the output is p,m,v read + p,m,v(,shadow) written
-    const double out_bytes = fa ? (double)M * N * (24.0 + (fa->shadow ? 2.0 : 0.0)) : (splitk > 1 ? 4.0 : ob) * (double)M * N;
+    const double out_bytes = g.ad_p ? (double)M * N * (24.0 + (g.ad_shadow ? 2.0 : 0.0)) : (g.splitk > 1 ? 4.0 : ob) * (double)M * N;
     char tag[96];
     const double fl_ = 2.0 * M * (double)N * K, by_ = eb * ((double)M * K + (double)N * K) + out_bytes;
     {
         const char* kn = afr_gemm_kernel_name(gdt, g);
         if (strcmp(kn, "gemm_bf16_group256") == 0)     // a plain product on the 256x256 body: the operand orientation follows the shape
-            snprintf(tag, sizeof tag, "%s[%dx%dx%d]<%d,%d>", kn, M, N, K, (flags & AFR_GEMM_A_KSTRIDED) ? 1 : 0, (flags & AFR_GEMM_B_KSTRIDED) ? 1 : 0);
+            snprintf(tag, sizeof tag, "%s[%dx%dx%d]<%d,%d>", kn, M, N, K, (g.flags & AFR_GEMM_A_KSTRIDED) ? 1 : 0, (g.flags & AFR_GEMM_B_KSTRIDED) ? 1 : 0);
         else snprintf(tag, sizeof tag, "%s[%dx%dx%d]", kn, M, N, K);
     }
-    if (coop && !(p->defer && p->pend_tile256 && p->pend.empty() && afr_gemm_groupable(gdt, g)))
+    if (g.coop_ws && !(p->defer && p->pend_tile256 && p->pend.empty() && afr_gemm_groupable(gdt, g)))
         return fail(AFR_ESTATE, "cooperative split-K product outside a 256x256 grouped launch");
-    if (rm && rm->b && !(p->defer && p->pend_tile256 && afr_gemm_groupable(gdt, g)))
+    if (g.b_rowmap && !(p->defer && p->pend_tile256 && afr_gemm_groupable(gdt, g)))
         return fail(AFR_ESTATE, "gathered k-strided operand outside a 256x256 grouped launch");
     if (p->defer && afr_gemm_groupable(gdt, g) && p->pend.size() < 4) {
         p->pend.push_back(g); p->pend_tag.push_back(tag); p->pend_flops += fl_; p->pend_bytes += by_;
@@ -685,14 +711,11 @@ static int flush_gemms(afr_plan* p, hipStream_t s) {
 // by the grouped reduce; large ones (fc_output of the sheet model) write the gradient buffer directly.
 static int run_dw(afr_plan* p, hipStream_t s, afr_plan::Layer& l, const void* dy, const void* a, int Bn, RTable& rt, int sk_want = 0,
                   bool coop = false, const int* a_rows = nullptr, int a_ld = 0) {
-    const RowMaps rmv{nullptr, a_rows, nullptr};
-    const RowMaps* rm = a_rows ? &rmv : nullptr;          // the layer's input rows are gathered from a table (k-strided B operand)
-    if (rm && !coop) return fail(AFR_ESTATE, "gathered weight-gradient operand needs the cooperative 256x256 launch");
-    const int fl = AFR_GEMM_A_KSTRIDED | AFR_GEMM_B_KSTRIDED;
+    if (a_rows && !coop) return fail(AFR_ESTATE, "gathered weight-gradient operand needs the cooperative 256x256 launch");
     const int N = l.N, K = l.K;
     int sk = sk_want > 0 ? sk_want : choose_splitk(N, K, Bn);
     if (sk > l.sk) sk = l.sk;
-    if (sk == 1) return run_gemm(p, s, fl, dy, a, p->G + l.w_off, nullptr, nullptr, N, K, Bn, N, K, K, 0, 1, 0, p->G + l.b_off, 0);
+    if (sk == 1) return run_gemm(p, s, lin_dw(dy, a, p->G + l.w_off, p->G + l.b_off, Bn, N, K));
     float* sw = (float*)(p->ws + l.o_slab_w);
     float* sb = (float*)(p->ws + l.o_slab_b);
     if (coop) {
@@ -700,18 +723,22 @@ static int run_dw(afr_plan* p, hipStream_t s, afr_plan::Layer& l, const void* dy
         // fused optimizer step -- as the AdamW update of this weight (its new bf16 copy goes to the write shadow, which the
         // launch's input-gradient workgroups do not read)
         // (each launch adds sk arrivals to every tile's counter; the slices of this one wait for the total after it)
-        CoopArgs ca{sw, (unsigned*)(p->ws + l.o_cnt), l.coop_arrived + (unsigned)sk};
-        FusedAdam fa{p->P + l.w_off, p->M + l.w_off, p->V + l.w_off, shadow_wr(p) ? shadow_wr(p) + l.w_off : nullptr,
-                     p->st_decay, p->st_b1, p->st_b2, p->st_eps, p->st_step, p->st_rsqrt_bc2};
-        int rc = run_gemm(p, s, fl, dy, a, p->G + l.w_off, nullptr, nullptr, N, K, Bn, N, a_rows ? a_ld : K, K, 0, sk, 0, sb, N, nullptr,
-                          p->step_on ? &fa : nullptr, &ca, rm);
+        GemmParams g = lin_dw(dy, a, p->G + l.w_off, sb, Bn, N, K, sk);
+        g.coop_ws = sw; g.coop_cnt = (unsigned*)(p->ws + l.o_cnt); g.coop_target = l.coop_arrived + (unsigned)sk;
+        g.err = (uint32_t*)(p->ws + p->o_err);
+        if (a_rows) { g.b_rowmap = a_rows; g.ldb = a_ld; }      // the layer's input rows are gathered from a table whose rows are a_ld apart
+        if (p->step_on) {
+            g.ad_p = p->P + l.w_off; g.ad_m = p->M + l.w_off; g.ad_v = p->V + l.w_off; g.ad_shadow = shadow_wr(p) ? shadow_wr(p) + l.w_off : nullptr;
+            set_adam(g, p->st);
+        }
+        int rc = run_gemm(p, s, g);
         if (rc) return rc;
         p->pend_arrived = &l.coop_arrived;                // run_gemm deferred it (a cooperative product is never launched alone)
         if (p->step_on) p->adam_done.push_back(l.w_off);
         afr_rtable_add(rt, p->G + l.b_off, sb, sk, N, N);
         return AFR_OK;
     }
-    int rc = run_gemm(p, s, fl, dy, a, sw, nullptr, nullptr, N, K, Bn, N, K, K, 0, sk, (long long)N * K, sb, N);
+    int rc = run_gemm(p, s, lin_dw(dy, a, sw, sb, Bn, N, K, sk, (long long)N * K));
     if (rc) return rc;
     afr_rtable_add(rt, p->G + l.w_off, sw, sk, (long long)N * K, (long long)N * K);
     afr_rtable_add(rt, p->G + l.b_off, sb, sk, N, N);
@@ -758,20 +785,44 @@ static SheetParams sheet_params(const afr_plan* p) {
     return sp;
 }
 
+// The sheet backward's stage 1 after its dz product: the fused front-end reverse into per-block slabs, registered in rt
+static int sheet_front_bwd(afr_plan* p, hipStream_t s, RTable& rt, double flops_per_string) {
+    const afr_config& c = p->cfg;
+    const int B = p->last_B;
+    SheetDims d{p->last_L, c.max_length, c.embed_dim, c.heads, c.fc_dim, c.vocab};
+    float* slabs = (float*)(p->ws + p->o_slab_e);
+    // a slab is laid out like the flat buffer's first s_wout floats: the 10 small tensors (pos .. fc1.bias)
+    SheetSlabOff so{(int)p->s_pos, (int)p->s_emb, (int)p->s_win, (int)p->s_bin, (int)p->s_wo, (int)p->s_bo, (int)p->s_g,
+                    (int)p->s_b, (int)p->s_w1, (int)p->s_b1, (int)p->s_wout};
+    {
+        ProfScope ps(p, s, "sheet_bwd", flops_per_string * B, 0.0);
+        HIPCHK(afr_launch_sheet_bwd(c.dtype, d, sheet_params(p), make_drop(p, p->last_training, p->last_step), p->last_x,
+                                    p->last_ldx, B, p->ws + p->o_dz, c.ln_eps, slabs, so, s));
+    }
+    afr_rtable_add(rt, p->G, slabs, afr_sheet_blocks(B), (long long)so.total, (long long)so.total);
+    return AFR_OK;
+}
+
 // How a glyph layer's gradient pair (dW + dX) leaves at batch B: as ONE grouped launch (sk_group > 0) on 256x256 tiles
 // (tile256) with the weight gradient's slices meeting inside the launch (coop), or as separate launches (all zero).
 struct PairPlan { int sk_group = 0, tile256 = 0; bool coop = false; };
-static PairPlan pair_plan_for(const afr_plan* p, const afr_plan::Layer& l, int B) {
+// what the shape alone allows (afr_op_gemm_pair runs exactly the cooperative ones)
+static PairPlan pair_plan_shape(int B, int N, int K) {
     PairPlan pp;
-    const afr_config& c = p->cfg;
-    if (c.dtype != AFR_BF16 || (c.reserved & 2)) return pp;
-    const long long dx_tiles = (long long)((B + 255) / 256) * ((l.K + 127) / 128);
-    if (dx_tiles >= 232 && l.N >= 256) afr_gemm_pair_plan(B, l.N, l.K, &pp.tile256, &pp.sk_group);
-    if (pp.sk_group > l.sk) { pp.sk_group = 0; pp.tile256 = 0; }          // the plan's slab space bounds the split
+    if (B <= 0 || N < 256 || K <= 0 || (long long)((B + 255) / 256) * ((K + 127) / 128) < 232) return pp;   // (tiles of the input gradient)
+    afr_gemm_pair_plan(B, N, K, &pp.tile256, &pp.sk_group);
     // with 256x256 tiles the weight gradient's split-K slices are summed inside the launch (cooperative split-K): no slabs
-    // for the grouped reduce to re-read; config.reserved bit 5 keeps the slab path (A/B measurements, parity cross-checks)
-    pp.coop = pp.tile256 && (pp.sk_group == 2 || pp.sk_group == 4 || pp.sk_group == 8) && !(c.reserved & 32) &&
-              (long long)((l.N + 255) / 256) * ((l.K + 255) / 256) * pp.sk_group <= 256;
+    // for the grouped reduce to re-read
+    pp.coop = pp.tile256 && (pp.sk_group == 2 || pp.sk_group == 4 || pp.sk_group == 8) &&
+              (long long)((N + 255) / 256) * ((K + 255) / 256) * pp.sk_group <= 256;
+    return pp;
+}
+static PairPlan pair_plan_for(const afr_plan* p, const afr_plan::Layer& l, int B) {
+    const afr_config& c = p->cfg;
+    if (c.dtype != AFR_BF16 || (c.reserved & AFR_CFG_NO_GROUPED_GEMM)) return PairPlan();
+    PairPlan pp = pair_plan_shape(B, l.N, l.K);
+    if (pp.sk_group > l.sk) return PairPlan();                 // the plan's slab space bounds the split
+    if (c.reserved & AFR_CFG_SLAB_SPLITK) pp.coop = false;     // keeps the slab path (A/B measurements, parity cross-checks)
     return pp;
 }
 // A training forward at batch B runs the first layer as a combination table when every consumer of h1 / h0 can gather: the
@@ -793,7 +844,6 @@ static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int 
     hipStream_t s = (hipStream_t)stream;
     const afr_config& c = p->cfg;
     const int Pix = c.out_h * c.out_w;
-    const int ob = c.dtype == AFR_BF16 ? AFR_GEMM_OUT_BF16 : 0;
     uint32_t* err = (uint32_t*)(p->ws + p->o_err);
     void* u = p->ws + p->o_u;
     if (c.kind == AFR_KIND_SHEET) {
@@ -805,9 +855,9 @@ static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int 
             ProfScope ps(p, s, "sheet_fwd", 2.5e6 * B, 0.0);        // ~2.5 MFLOP of f32 VALU work per string
             HIPCHK(afr_launch_sheet_fwd(c.dtype, d, sheet_params(p), make_drop(p, training, step), x, L, B, z, c.ln_eps, err, s));
         }
-        const int Kz = c.max_length * c.fc_dim;
-        int rc = run_gemm(p, s, AFR_GEMM_BIAS | ob, z, weight_ptr(p, p->s_wout), u, p->P + p->s_bout, nullptr, B, Pix, Kz,
-                          Kz, Kz, Pix, 0, 1, 0, nullptr, 0, fl);
+        GemmParams g = lin_fwd(p, p->layers[0], z, u, B);        // fc_output
+        if (fl) fuse_loss(p, g, *fl);
+        int rc = run_gemm(p, s, g);
         if (rc) return rc;
         p->last_L = Lc;
         p->last_ldx = L;
@@ -827,6 +877,7 @@ static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int 
         for (int l = 0; l < c.n_hidden; ++l) {
             const afr_plan::PixBlock& b = p->pix[l];
             const afr_plan::PixSave& sv = p->pxs[l];
+            const afr_plan::Layer* L5 = &p->pxl[(size_t)l * 5];           // the block's Linears: q, kv, out-proj, fc1, fc2
             float *hin = (float*)(p->ws + sv.hin), *h1 = (float*)(p->ws + sv.h1);
             void *n1 = p->ws + sv.n1, *q = p->ws + sv.q, *o = p->ws + sv.o, *n2 = p->ws + sv.n2, *kv = p->ws + sv.kv, *f = p->ws + sv.f;
             {
@@ -835,23 +886,22 @@ static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int 
                                                l == 0 ? nullptr : a, p->P + b.ln1g, p->P + b.ln1b, n1, rows, T, d, c.ln_eps, s));
             }
             // packed in-projection (model.py:144): rows [0, d) of in_proj_weight make q from the pixel tokens, rows [d, 3d) k | v from the context
-            if ((rc = run_gemm(p, s, AFR_GEMM_BIAS | ob, n1, weight_ptr(p, b.win), q, p->P + b.bin, nullptr, (int)rows, d, d, d, d, d, 0, 1, 0))) return rc;
-            if ((rc = run_gemm(p, s, AFR_GEMM_BIAS | ob, ctx, weight_ptr(p, b.win + (int64_t)d * d), kv, p->P + b.bin + d, nullptr, B * C, 2 * d, d, d, d, 2 * d, 0, 1, 0))) return rc;
+            if ((rc = run_gemm(p, s, lin_fwd(p, L5[0], n1, q, (int)rows)))) return rc;
+            if ((rc = run_gemm(p, s, lin_fwd(p, L5[1], ctx, kv, B * C)))) return rc;
             {
                 ProfScope ps(p, s, "pixel_attn", 0.0, (double)rows * d * 2.0 * p->act_bytes);
                 HIPCHK(afr_launch_pixel_attn(c.dtype, q, kv, o, rows, T, d, c.heads, C, s));
             }
-            if ((rc = run_gemm(p, s, AFR_GEMM_BIAS | ob, o, weight_ptr(p, b.wo), a, p->P + b.bo, nullptr, (int)rows, d, d, d, d, d, 0, 1, 0))) return rc;
+            if ((rc = run_gemm(p, s, lin_fwd(p, L5[2], o, a, (int)rows)))) return rc;
             {
                 ProfScope ps(p, s, "pixel_add_ln", 0.0, (double)rows * d * (8.0 + 2.0 * p->act_bytes));
                 HIPCHK(afr_launch_pixel_add_ln(c.dtype, hin, h1, nullptr, a, p->P + b.ln2g, p->P + b.ln2b, n2, rows, T, d, c.ln_eps, s));
             }
             // (bf16 mode: the epilogue also leaves the ReLU gate of the stored values as bits for the backward's input-gradient product)
-            RowMaps rmf{nullptr, nullptr, nullptr};
-            if (sv.fbits) { rmf.mask_out = (unsigned char*)(p->ws + sv.fbits); rmf.ldmask = ff / 8; }
-            if ((rc = run_gemm(p, s, AFR_GEMM_BIAS | AFR_GEMM_RELU | ob, n2, weight_ptr(p, b.w1), f, p->P + b.b1, nullptr, (int)rows, ff, d, d, d, ff, 0, 1, 0,
-                               nullptr, 0, nullptr, nullptr, nullptr, sv.fbits ? &rmf : nullptr))) return rc;
-            if ((rc = run_gemm(p, s, AFR_GEMM_BIAS | ob, f, weight_ptr(p, b.w2), a, p->P + b.b2, nullptr, (int)rows, d, ff, ff, ff, d, 0, 1, 0))) return rc;
+            GemmParams g1 = lin_fwd(p, L5[3], n2, f, (int)rows, AFR_GEMM_RELU);
+            if (sv.fbits) { g1.mask_out = (unsigned char*)(p->ws + sv.fbits); g1.ldmask = ff / 8; }
+            if ((rc = run_gemm(p, s, g1))) return rc;
+            if ((rc = run_gemm(p, s, lin_fwd(p, L5[4], f, a, (int)rows)))) return rc;
         }
         {
             ProfScope ps(p, s, "pixel_head", 0.0, (double)rows * d * (8.0 + p->act_bytes));
@@ -874,9 +924,8 @@ static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int 
         const float* femb = c.n_fonts > 0 ? p->P + p->font_off : nullptr;
         int first = 0;
         const bool combo = fl != nullptr && p->k0 && combo_for(p, B);
-        const RowMaps rma{(const int*)(p->ws + p->o_cidx), nullptr, nullptr};
         if (combo) {
-            // training step: the first layer as a combination table; the second layer gathers its input rows from it
+            // training step: the first layer as a combination table
             const auto& l = p->layers[0];
             ProfScope ps(p, s, "glyph_l1_combo", 0.0, (double)c.vocab * (c.n_fonts > 0 ? c.n_fonts : 1) * l.N * 2.0);
             HIPCHK(afr_launch_glyph_combo(p->P + p->emb_off, femb, p->P + l.w_off, p->P + l.b_off, x, font, B, c.embed_dim, l.N, c.vocab,
@@ -902,11 +951,12 @@ static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int 
             const auto& l = p->layers[i];
             const bool last = (i == nl - 1);
             void* outp = last ? u : (void*)(p->ws + p->o_act[i + 1]);
-            RowMaps rmi{(combo && i == 1) ? rma.a : nullptr, nullptr, nullptr};
-            if (bits && !last && p->o_mbits[i]) { rmi.mask_out = (unsigned char*)(p->ws + p->o_mbits[i]); rmi.ldmask = l.N / 8; }
-            int rc = run_gemm(p, s, AFR_GEMM_BIAS | (last ? 0 : AFR_GEMM_RELU) | ob, h, weight_ptr(p, l.w_off), outp,
-                              p->P + l.b_off, nullptr, B, l.N, l.K, (combo && i == 1) ? p->h1c_ld : l.K, l.K, l.N, 0, 1, 0, nullptr, 0,
-                              last ? fl : nullptr, nullptr, nullptr, (rmi.a || rmi.mask_out) ? &rmi : nullptr);
+            GemmParams g = lin_fwd(p, l, h, outp, B, last ? 0 : AFR_GEMM_RELU);
+            // after the combination table the second layer gathers its input rows from it (rows h1c_ld apart)
+            if (combo && i == 1) { g.a_rowmap = (const int*)(p->ws + p->o_cidx); g.lda = p->h1c_ld; }
+            if (bits && !last && p->o_mbits[i]) { g.mask_out = (unsigned char*)(p->ws + p->o_mbits[i]); g.ldmask = l.N / 8; }
+            if (last && fl) fuse_loss(p, g, *fl);
+            int rc = run_gemm(p, s, g);
             if (rc) return rc;
             h = outp;
         }
@@ -929,14 +979,18 @@ extern "C" int afr_forward(afr_plan* p, const int64_t* x, const int64_t* font, i
 }
 
 // --------------------------------------------------------------------------------- loss + grad
+static int check_loss_args(const void* target, int tdtype, int64_t mean_elems, const float* loss_accum) {
+    if (!target || !loss_accum) return fail(AFR_EINVAL, "target and loss_accum are required");
+    if (tdtype != AFR_TARGET_U8 && tdtype != AFR_TARGET_F32) return fail(AFR_EINVAL, "bad target dtype");
+    if (mean_elems <= 0) return fail(AFR_EINVAL, "mean_elems must be positive");
+    return AFR_OK;
+}
 static int loss_grad_impl(afr_plan* p, const void* target, int tdtype, const int* rowmap, int B, int64_t mean_elems, float* loss_accum,
                           void* stream) {
     if (!p || !p->P) return fail(AFR_ESTATE, "plan has no bound parameters");
     DevGuard dg(p->device);
-    if (!target || !loss_accum) return fail(AFR_EINVAL, "target and loss_accum are required");
+    if (int rc = check_loss_args(target, tdtype, mean_elems, loss_accum)) return rc;
     if (B != p->last_B) return fail(AFR_ESTATE, "loss_grad batch %d does not match the last forward (%d)", B, p->last_B);
-    if (tdtype != AFR_TARGET_U8 && tdtype != AFR_TARGET_F32) return fail(AFR_EINVAL, "bad target dtype");
-    if (mean_elems <= 0) return fail(AFR_EINVAL, "mean_elems must be positive");
     hipStream_t s = (hipStream_t)stream;
     const int Pix = p->cfg.out_h * p->cfg.out_w;
     void* u = p->ws + p->o_u;
@@ -979,10 +1033,8 @@ extern "C" int afr_set_output_grad(afr_plan* p, const float* dy, int B, void* st
 static int pixel_backward(afr_plan* p, hipStream_t s, int stage, int64_t* g_off, int64_t* g_len) {
     const afr_config& c = p->cfg;
     RTable rt;
-    rt.nseg = 0; rt.nblocks = 0; rt.adam = 0;
     const int B = p->last_B, d = c.embed_dim, ff = c.fc_dim, T = c.out_h * c.out_w, C = c.n_fonts > 0 ? 2 : 1;
     const long long rows = (long long)B * T;
-    const int ob = c.dtype == AFR_BF16 ? AFR_GEMM_OUT_BF16 : 0;
     const int nbp = afr_pixel_bwd_blocks(rows);
     float* du = (float*)(p->ws + p->o_u);
     float* dh = (float*)(p->ws + p->o_dh);
@@ -1006,12 +1058,11 @@ static int pixel_backward(afr_plan* p, hipStream_t s, int stage, int64_t* g_off,
         afr_plan::Layer* L5 = &p->pxl[(size_t)l * 5];                 // q, kv, out-proj, fc1, fc2
         // ---- MLP:  h_out = h1 + fc2(relu(fc1(LN2(h1))))
         if ((rc = run_dw(p, s, L5[4], dhT, p->ws + sv.f, (int)rows, rt))) return rc;
-        RowMaps rmf{nullptr, nullptr, nullptr};
-        if (sv.fbits) { rmf.mask_in = (const unsigned char*)(p->ws + sv.fbits); rmf.ldmask = ff / 8; }
-        if ((rc = run_gemm(p, s, AFR_GEMM_B_KSTRIDED | AFR_GEMM_RELU_MASK | ob, dhT, weight_ptr(p, b.w2), dfb, nullptr, p->ws + sv.f, (int)rows, ff, d, d, ff, ff, ff, 1, 0,
-                           nullptr, 0, nullptr, nullptr, nullptr, sv.fbits ? &rmf : nullptr))) return rc;
+        GemmParams g2 = lin_dx(p, L5[4], dhT, dfb, p->ws + sv.f, (int)rows);
+        if (sv.fbits) { g2.mask_in = (const unsigned char*)(p->ws + sv.fbits); g2.ldmask = ff / 8; }
+        if ((rc = run_gemm(p, s, g2))) return rc;
         if ((rc = run_dw(p, s, L5[3], dfb, p->ws + sv.n2, (int)rows, rt))) return rc;
-        if ((rc = run_gemm(p, s, AFR_GEMM_B_KSTRIDED | ob, dfb, weight_ptr(p, b.w1), dn, nullptr, nullptr, (int)rows, d, ff, ff, d, d, 0, 1, 0))) return rc;
+        if ((rc = run_gemm(p, s, lin_dx(p, L5[3], dfb, dn, nullptr, (int)rows)))) return rc;
         {
             float* lp = (float*)(p->ws + sv.ln2p);
             ProfScope ps(p, s, "pixel_ln_bwd", 0.0, (double)rows * d * (12.0 + 2.0 * p->act_bytes));
@@ -1021,7 +1072,7 @@ static int pixel_backward(afr_plan* p, hipStream_t s, int stage, int64_t* g_off,
         }
         // ---- attention:  h1 = hin + out_proj(softmax(q k^T) v)
         if ((rc = run_dw(p, s, L5[2], dhT, p->ws + sv.o, (int)rows, rt))) return rc;
-        if ((rc = run_gemm(p, s, AFR_GEMM_B_KSTRIDED | ob, dhT, weight_ptr(p, b.wo), dn, nullptr, nullptr, (int)rows, d, d, d, d, d, 0, 1, 0))) return rc;
+        if ((rc = run_gemm(p, s, lin_dx(p, L5[2], dhT, dn, nullptr, (int)rows)))) return rc;
         const int chunk = afr_pixel_attn_chunk(T), chunks = (T + chunk - 1) / chunk;
         float *dkvp = (float*)(p->ws + p->o_dkvp), *dkv = (float*)(p->ws + p->o_dkv);
         {
@@ -1037,9 +1088,9 @@ static int pixel_backward(afr_plan* p, hipStream_t s, int stage, int64_t* g_off,
         void* dkvT = p->ws + p->o_dkvt;
         HIPCHK(afr_launch_pixel_cast(c.dtype, dkvT, chunks > 1 ? dkv : dkvp, B, C * 2 * d, 4 * d, s));
         if ((rc = run_dw(p, s, L5[0], dq, p->ws + sv.n1, (int)rows, rt))) return rc;
-        if ((rc = run_gemm(p, s, AFR_GEMM_B_KSTRIDED | ob, dq, weight_ptr(p, b.win), dn, nullptr, nullptr, (int)rows, d, d, d, d, d, 0, 1, 0))) return rc;
+        if ((rc = run_gemm(p, s, lin_dx(p, L5[0], dq, dn, nullptr, (int)rows)))) return rc;
         if ((rc = run_dw(p, s, L5[1], dkvT, ctx, B * C, rt))) return rc;
-        if ((rc = run_gemm(p, s, AFR_GEMM_B_KSTRIDED | ob, dkvT, weight_ptr(p, b.win + (int64_t)d * d), p->ws + p->o_dctxt, nullptr, nullptr, B * C, d, 2 * d, 2 * d, d, d, 0, 1, 0))) return rc;
+        if ((rc = run_gemm(p, s, lin_dx(p, L5[1], dkvT, p->ws + p->o_dctxt, nullptr, B * C)))) return rc;
         HIPCHK(afr_launch_pixel_accum(c.dtype, (float*)(p->ws + p->o_dctx), p->ws + p->o_dctxt, (long long)B * C * d, l == c.n_hidden - 1, s));
         {
             float* lp = (float*)(p->ws + sv.ln1p);
@@ -1066,41 +1117,25 @@ static int pixel_backward(afr_plan* p, hipStream_t s, int stage, int64_t* g_off,
 
 static int backward_stage_impl(afr_plan* p, int stage, int64_t* g_off, int64_t* g_len, hipStream_t s, RTable* shared_rt) {
     const afr_config& c = p->cfg;
-    const int B = p->last_B, Pix = c.out_h * c.out_w;
-    const int ob = c.dtype == AFR_BF16 ? AFR_GEMM_OUT_BF16 : 0;
+    const int B = p->last_B;
     void* du = p->ws + p->o_u;
     int rc;
     // slab reductions: flushed per stage (so the stage's gradient range is final), or deferred to ONE grouped launch
     // at the end of a monolithic afr_backward (shared_rt)
     RTable local_rt;
-    local_rt.nseg = 0; local_rt.nblocks = 0; local_rt.adam = 0;
     RTable& rt = shared_rt ? *shared_rt : local_rt;
     auto flush = [&]() -> int { return shared_rt ? AFR_OK : run_reduce_group(p, s, rt); };
     if (c.kind == AFR_KIND_PIXEL) return pixel_backward(p, s, stage, g_off, g_len);     // (its slab reductions are flushed per stage inside)
     if (c.kind == AFR_KIND_SHEET) {
-        const int Kz = c.max_length * c.fc_dim;
-        void* z = p->ws + p->o_z;
-        void* dz = p->ws + p->o_dz;
         if (stage == 0) {
-            if ((rc = run_dw(p, s, p->layers[0], du, z, B, rt))) return rc;
+            if ((rc = run_dw(p, s, p->layers[0], du, p->ws + p->o_z, B, rt))) return rc;
             if ((rc = flush())) return rc;
             if (g_off) *g_off = p->s_wout;
             if (g_len) *g_len = p->total - p->s_wout;
             return AFR_OK;
         }
-        if ((rc = run_gemm(p, s, AFR_GEMM_B_KSTRIDED | ob, du, weight_ptr(p, p->s_wout), dz, nullptr, nullptr, B, Kz, Pix, Pix,
-                           Kz, Kz, 0, 1, 0))) return rc;
-        SheetDims d{p->last_L, c.max_length, c.embed_dim, c.heads, c.fc_dim, c.vocab};
-        float* slabs = (float*)(p->ws + p->o_slab_e);
-        // a slab is laid out like the flat buffer's first s_wout floats: the 10 small tensors (pos .. fc1.bias)
-        SheetSlabOff so{(int)p->s_pos, (int)p->s_emb, (int)p->s_win, (int)p->s_bin, (int)p->s_wo, (int)p->s_bo, (int)p->s_g,
-                        (int)p->s_b, (int)p->s_w1, (int)p->s_b1, (int)p->s_wout};
-        {
-            ProfScope ps(p, s, "sheet_bwd", 7.0e6 * B, 0.0);       // partial recompute + reverse: ~7 MFLOP of f32 work per string
-            HIPCHK(afr_launch_sheet_bwd(c.dtype, d, sheet_params(p), make_drop(p, p->last_training, p->last_step), p->last_x,
-                                        p->last_ldx, B, dz, c.ln_eps, slabs, so, s));
-        }
-        afr_rtable_add(rt, p->G, slabs, afr_sheet_blocks(B), (long long)so.total, (long long)so.total);
+        if ((rc = run_gemm(p, s, lin_dx(p, p->layers[0], du, p->ws + p->o_dz, nullptr, B)))) return rc;
+        if ((rc = sheet_front_bwd(p, s, rt, 7.0e6))) return rc;       // partial recompute + reverse: ~7 MFLOP of f32 work per string
         if ((rc = flush())) return rc;
         if (g_off) *g_off = 0;
         if (g_len) *g_len = p->s_wout;
@@ -1117,7 +1152,7 @@ static int backward_stage_impl(afr_plan* p, int stage, int64_t* g_off, int64_t* 
         // and the per-table-row segment sums; a small kernel turns those into dEmb / dFont.  No input-gradient GEMM,
         // no scatter-add.
         const int K0 = p->k0, E = c.embed_dim;
-        if (p->l1f && !(c.reserved & 16)) {
+        if (p->l1f && !(c.reserved & AFR_CFG_L1_BWD_UNFUSED)) {
             // throughput mode: one kernel per 64 glyphs (gemm.hip: glyph_l1_bwd_fused_kernel) -> [dW1 | db1 | dTab] slabs
             float* sl = (float*)(p->ws + p->o_l1f);
             const int CS = afr_glyph_l1_bwd_fused_split(B, l.N), nb = afr_glyph_l1_bwd_fused_blocks(B, l.N), nc = l.N / CS;
@@ -1145,10 +1180,7 @@ static int backward_stage_impl(afr_plan* p, int stage, int64_t* g_off, int64_t* 
         float* sw = (float*)(p->ws + l.o_slab_w);
         float* sb = (float*)(p->ws + l.o_slab_b);
         const long long stride = (long long)l.N * K0;
-        const int gfl = AFR_GEMM_A_KSTRIDED | AFR_GEMM_B_KSTRIDED;
-        if (sk == 1) rc = run_gemm(p, s, gfl, dy, a, sw, nullptr, nullptr, l.N, K0, B, l.N, K0, K0, 0, 1, 0, p->G + l.b_off, 0);
-        else rc = run_gemm(p, s, gfl, dy, a, sw, nullptr, nullptr, l.N, K0, B, l.N, K0, K0, 0, sk, stride, sb, l.N);
-        if (rc) return rc;
+        if ((rc = run_gemm(p, s, lin_dw(dy, a, sw, sk == 1 ? p->G + l.b_off : sb, B, l.N, K0, sk, sk == 1 ? 0 : stride)))) return rc;
         if (sk > 1) afr_rtable_add(rt, p->G + l.b_off, sb, sk, l.N, l.N);
         float* dw1 = (float*)(p->ws + p->o_dw1);
         float* part = (float*)(p->ws + p->o_slab_e);
@@ -1184,12 +1216,10 @@ static int backward_stage_impl(afr_plan* p, int stage, int64_t* g_off, int64_t* 
     p->defer = sk_group > 0;
     if ((rc = run_dw(p, s, l, dy, a, B, rt, sk_group, coop, cidx, p->h1c_ld))) { drop_pending(p); return rc; }
     void* dx = p->ws + p->o_d[stage & 1];
-    const int fl = AFR_GEMM_B_KSTRIDED | ob | (i > 0 ? AFR_GEMM_RELU_MASK : 0);
-    RowMaps rmx{nullptr, nullptr, cidx};
-    const bool use_bits = p->mbits_on && i >= 2 && p->o_mbits[i - 1] && (fl & AFR_GEMM_OUT_BF16);
-    if (use_bits) { rmx.mask_in = (const unsigned char*)(p->ws + p->o_mbits[i - 1]); rmx.ldmask = l.K / 8; }
-    if ((rc = run_gemm(p, s, fl, dy, weight_ptr(p, l.w_off), dx, nullptr, i > 0 ? a : nullptr, B, l.K, l.N, l.N, l.K, l.K,
-                       gath ? p->h1c_ld : l.K, 1, 0, nullptr, 0, nullptr, nullptr, nullptr, (gath || use_bits) ? &rmx : nullptr))) { drop_pending(p); return rc; }
+    GemmParams g = lin_dx(p, l, dy, dx, i > 0 ? a : nullptr, B);
+    if (gath) { g.aux_rowmap = cidx; g.ldaux = p->h1c_ld; }      // the ReLU gate is read from the gathered H1c rows
+    if (p->mbits_on && i >= 2 && p->o_mbits[i - 1]) { g.mask_in = (const unsigned char*)(p->ws + p->o_mbits[i - 1]); g.ldmask = l.K / 8; }
+    if ((rc = run_gemm(p, s, g))) { drop_pending(p); return rc; }
     if ((rc = flush_gemms(p, s))) return rc;
     const int64_t end = l.b_off + (l.N + 63) / 64 * 64;
     if (i > 0) {
@@ -1241,7 +1271,6 @@ extern "C" int afr_backward(afr_plan* p, void* stream) {
     if (!p->have_du) return fail(AFR_ESTATE, "afr_backward needs afr_forward + afr_loss_grad first");
     const int n = afr_backward_stages(p);
     RTable rt;
-    rt.nseg = 0; rt.nblocks = 0; rt.adam = 0;
     for (int st = 0; st < n; ++st) {
         int rc = backward_stage_impl(p, st, nullptr, nullptr, (hipStream_t)stream, &rt);
         if (rc) return rc;
@@ -1272,13 +1301,11 @@ extern "C" int afr_adamw_step(afr_plan* p, float lr, float b1, float b2, float e
 // Single-GPU optimiser step fused into the grouped slab reduction: every tensor whose gradient was produced as partial
 // slabs (split-K dW, bias partials, embedding partials, the sheet model's small tensors) is updated in the kernel that
 // sums its slabs -- the summed gradient is never stored; tensors whose gradient a GEMM wrote directly get the plain kernel.
-static int reduce_and_step(afr_plan* p, hipStream_t s, RTable& rt, float lr, float b1, float b2, float eps, float wd, int64_t t,
-                           int64_t skip_off = -1) {
-    const float bc1 = (float)(1.0 - std::pow((double)b1, (double)t));
-    const float bc2 = (float)(1.0 - std::pow((double)b2, (double)t));
+static int reduce_and_step(afr_plan* p, hipStream_t s, RTable& rt, const AdamArgs& h, int64_t skip_off = -1) {
+    const float bc1 = (float)(1.0 - std::pow((double)h.b1, (double)h.t));
+    const float bc2 = (float)(1.0 - std::pow((double)h.b2, (double)h.t));
     bf16_t* shadow = shadow_wr(p);        // every tensor's new bf16 copy goes to the write shadow; the roles swap below
-    rt.adam = 1; rt.ad_decay = 1.f - lr * wd; rt.ad_b1 = b1; rt.ad_b2 = b2; rt.ad_eps = eps; rt.ad_step = lr / bc1;
-    rt.ad_rsqrt_bc2 = (float)(1.0 / std::sqrt((double)bc2));
+    rt.adam = 1; set_adam(rt, h);
     rt.gbase = p->G; rt.P = p->P; rt.M = p->M; rt.V = p->V; rt.shadow = shadow;
     p->wT_valid = false;
     int rc = run_reduce_group(p, s, rt);
@@ -1298,8 +1325,8 @@ static int reduce_and_step(afr_plan* p, hipStream_t s, RTable& rt, float lr, flo
         if (cov >= tn.numel) continue;
         const int64_t n = (tn.numel + 63) / 64 * 64;
         ProfScope ps(p, s, "adamw", 0.0, (double)n * 28.0);
-        HIPCHK(afr_launch_adamw(p->P + tn.off, p->G + tn.off, p->M + tn.off, p->V + tn.off, shadow ? shadow + tn.off : nullptr, n, lr, b1,
-                                b2, eps, wd, bc1, bc2, 1.f, s));
+        HIPCHK(afr_launch_adamw(p->P + tn.off, p->G + tn.off, p->M + tn.off, p->V + tn.off, shadow ? shadow + tn.off : nullptr, n, h.lr, h.b1,
+                                h.b2, h.eps, h.wd, bc1, bc2, 1.f, s));
     }
     if (p->o_shadow2) p->shadow_cur ^= 1;   // every tensor has been rewritten: the write shadow is the current one now
     p->adam_done.clear();
@@ -1313,38 +1340,22 @@ static int reduce_and_step(afr_plan* p, hipStream_t s, RTable& rt, float lr, flo
 static bool fused_step_eligible(const afr_plan* p, int B) {
     return p->cfg.kind == AFR_KIND_SHEET && p->M && p->V && choose_splitk(p->layers[0].N, p->layers[0].K, B) == 1;
 }
-static int sheet_fused_step(afr_plan* p, hipStream_t s, float lr, float b1, float b2, float eps, float wd, int64_t t) {
-    const afr_config& c = p->cfg;
-    const int B = p->last_B, Pix = c.out_h * c.out_w, Kz = c.max_length * c.fc_dim;
-    const int ob = c.dtype == AFR_BF16 ? AFR_GEMM_OUT_BF16 : 0;
+static int sheet_fused_step(afr_plan* p, hipStream_t s, const AdamArgs& h) {
+    const afr_plan::Layer& l = p->layers[0];      // fc_output
+    const int B = p->last_B;
     void* du = p->ws + p->o_u;
-    void* z = p->ws + p->o_z;
-    void* dz = p->ws + p->o_dz;
     bf16_t* shadow = shadow_rd(p);        // the sheet model keeps ONE shadow: its input-gradient product runs before the update
-    const float bc1 = (float)(1.0 - std::pow((double)b1, (double)t));
-    const float bc2 = (float)(1.0 - std::pow((double)b2, (double)t));
     int rc;
-    if ((rc = run_gemm(p, s, AFR_GEMM_B_KSTRIDED | ob, du, weight_ptr(p, p->s_wout), dz, nullptr, nullptr, B, Kz, Pix, Pix,
-                       Kz, Kz, 0, 1, 0))) return rc;
-    FusedAdam fa{p->P + p->s_wout, p->M + p->s_wout, p->V + p->s_wout, shadow ? shadow + p->s_wout : nullptr,
-                 1.f - lr * wd, b1, b2, eps, lr / bc1, (float)(1.0 / std::sqrt((double)bc2))};
-    if ((rc = run_gemm(p, s, AFR_GEMM_A_KSTRIDED | AFR_GEMM_B_KSTRIDED, du, z, p->G + p->s_wout, nullptr, nullptr, Pix, Kz, B, Pix, Kz,
-                       Kz, 0, 1, 0, p->G + p->s_bout, 0, nullptr, &fa))) return rc;
-    SheetDims d{p->last_L, c.max_length, c.embed_dim, c.heads, c.fc_dim, c.vocab};
-    float* slabs = (float*)(p->ws + p->o_slab_e);
-    SheetSlabOff so{(int)p->s_pos, (int)p->s_emb, (int)p->s_win, (int)p->s_bin, (int)p->s_wo, (int)p->s_bo, (int)p->s_g,
-                    (int)p->s_b, (int)p->s_w1, (int)p->s_b1, (int)p->s_wout};
-    {
-        ProfScope ps(p, s, "sheet_bwd", 9.0e6 * B, 0.0);
-        HIPCHK(afr_launch_sheet_bwd(c.dtype, d, sheet_params(p), make_drop(p, p->last_training, p->last_step), p->last_x,
-                                    p->last_ldx, B, dz, c.ln_eps, slabs, so, s));
-    }
+    if ((rc = run_gemm(p, s, lin_dx(p, l, du, p->ws + p->o_dz, nullptr, B)))) return rc;
+    GemmParams g = lin_dw(du, p->ws + p->o_z, p->G + l.w_off, p->G + l.b_off, B, l.N, l.K);
+    g.ad_p = p->P + l.w_off; g.ad_m = p->M + l.w_off; g.ad_v = p->V + l.w_off; g.ad_shadow = shadow ? shadow + l.w_off : nullptr;
+    set_adam(g, h);
+    if ((rc = run_gemm(p, s, g))) return rc;
     RTable rt;
-    rt.nseg = 0; rt.nblocks = 0; rt.adam = 0;
-    afr_rtable_add(rt, p->G, slabs, afr_sheet_blocks(B), (long long)so.total, (long long)so.total);
+    if ((rc = sheet_front_bwd(p, s, rt, 9.0e6))) return rc;
     // the ten small tensors are updated inside the slab reduction; fc_output.bias by the plain kernel; fc_output.weight
     // was updated in the dW GEMM above (skipped here)
-    if ((rc = reduce_and_step(p, s, rt, lr, b1, b2, eps, wd, t, p->s_wout))) return rc;
+    if ((rc = reduce_and_step(p, s, rt, h, l.w_off))) return rc;
     p->have_du = false;
     p->next_stage = 0;
     return AFR_OK;
@@ -1417,9 +1428,7 @@ static int glyph1_fused(afr_plan* p, const int64_t* x, const int64_t* font, cons
 
 static int forward_loss_impl(afr_plan* p, const int64_t* x, const int64_t* font, const void* target, int tdtype, const int* rowmap, int B, int L,
                              int64_t mean_elems, float* loss_accum, uint64_t step, void* stream) {
-    if (!target || !loss_accum) return fail(AFR_EINVAL, "target and loss_accum are required");
-    if (tdtype != AFR_TARGET_U8 && tdtype != AFR_TARGET_F32) return fail(AFR_EINVAL, "bad target dtype");
-    if (mean_elems <= 0) return fail(AFR_EINVAL, "mean_elems must be positive");
+    if (int rc = check_loss_args(target, tdtype, mean_elems, loss_accum)) return rc;
     FusedLoss fl{target, tdtype, mean_elems, loss_accum, rowmap};
     return forward_impl(p, x, font, B, L, nullptr, 1, step, stream, &fl);
 }
@@ -1432,19 +1441,19 @@ static int train_step_impl(afr_plan* p, const int64_t* x, const int64_t* font, c
                            int L, int64_t mean_elems, float* loss_accum, uint64_t step, int do_step, float lr, float b1,
                            float b2, float eps, float wd, int64_t t, void* stream) {
     int rc;
-    if (!target || !loss_accum) return fail(AFR_EINVAL, "target and loss_accum are required");
-    if (tdtype != AFR_TARGET_U8 && tdtype != AFR_TARGET_F32) return fail(AFR_EINVAL, "bad target dtype");
-    if (mean_elems <= 0) return fail(AFR_EINVAL, "mean_elems must be positive");
+    if ((rc = check_loss_args(target, tdtype, mean_elems, loss_accum))) return rc;
     if (!p || !p->P) return fail(AFR_ESTATE, "plan has no bound parameters");
     DevGuard dg(p->device);
-    if (p->fused1 && !(p->cfg.reserved & 4)) {
+    const AdamArgs h{lr, b1, b2, eps, wd, t};
+    const bool fuse_opt = do_step && !(p->cfg.reserved & AFR_CFG_UNFUSED_OPTIMIZER);
+    if (p->fused1 && !(p->cfg.reserved & AFR_CFG_NO_FUSED_GLYPH1)) {
         // small glyph net: forward + loss + backward in ONE launch, then the grouped reduce (with AdamW when stepping here)
         if (!p->G) return fail(AFR_ESTATE, "plan has no bound gradient buffer");
         RTable rt;
         if ((rc = glyph1_fused(p, x, font, target, tdtype, rowmap, B, mean_elems, loss_accum, (hipStream_t)stream, rt))) return rc;
-        if (do_step && p->M && p->V && !(p->cfg.reserved & 1)) {
+        if (fuse_opt && p->M && p->V) {
             if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
-            rc = reduce_and_step(p, (hipStream_t)stream, rt, lr, b1, b2, eps, wd, t);
+            rc = reduce_and_step(p, (hipStream_t)stream, rt, h);
             p->wT_valid = rc == AFR_OK;                 // the reduce's AdamW wrote W1T / W2T beside the shadow
             return rc;
         }
@@ -1455,27 +1464,22 @@ static int train_step_impl(afr_plan* p, const int64_t* x, const int64_t* font, c
     // the loss and its gradient are computed in the epilogue of the last forward GEMM: u never touches HBM
     FusedLoss fl{target, tdtype, mean_elems, loss_accum, rowmap};
     if ((rc = forward_impl(p, x, font, B, L, nullptr, 1, step, stream, &fl))) return rc;
-    if (do_step && fused_step_eligible(p, B) && !(p->cfg.reserved & 1)) {
+    if (fuse_opt && fused_step_eligible(p, B)) {
         if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
-        return sheet_fused_step(p, (hipStream_t)stream, lr, b1, b2, eps, wd, t);
+        return sheet_fused_step(p, (hipStream_t)stream, h);
     }
-    if (do_step && p->M && p->V && !(p->cfg.reserved & 1) && p->cfg.kind != AFR_KIND_PIXEL) {
+    if (fuse_opt && p->M && p->V && p->cfg.kind != AFR_KIND_PIXEL) {
         if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
         const int n = afr_backward_stages(p);
         RTable rt;
-        rt.nseg = 0; rt.nblocks = 0; rt.adam = 0;
-        {   // weight-gradient products with a cooperative split-K tail apply this step's AdamW themselves
-            const float bc1 = (float)(1.0 - std::pow((double)b1, (double)t)), bc2 = (float)(1.0 - std::pow((double)b2, (double)t));
-            p->step_on = true; p->adam_done.clear();
-            p->st_decay = 1.f - lr * wd; p->st_b1 = b1; p->st_b2 = b2; p->st_eps = eps; p->st_step = lr / bc1;
-            p->st_rsqrt_bc2 = (float)(1.0 / std::sqrt((double)bc2));
-        }
+        // weight-gradient products with a cooperative split-K tail apply this step's AdamW themselves
+        p->step_on = true; p->adam_done.clear(); p->st = h;
         for (int st = 0; st < n; ++st)
             if ((rc = backward_stage_impl(p, st, nullptr, nullptr, (hipStream_t)stream, &rt))) { p->step_on = false; return rc; }
         p->step_on = false;
         p->next_stage = 0;
         p->have_du = false;
-        return reduce_and_step(p, (hipStream_t)stream, rt, lr, b1, b2, eps, wd, t);
+        return reduce_and_step(p, (hipStream_t)stream, rt, h);
     }
     if ((rc = afr_backward(p, stream))) return rc;
     if (do_step && (rc = afr_adamw_step(p, lr, b1, b2, eps, wd, t, 1.f, stream))) return rc;
@@ -1611,16 +1615,13 @@ extern "C" int afr_op_gemm(int dtype, int flags, const void* A, const void* B, v
         return fail(AFR_EUNSUPPORTED, "contiguous extents and leading dimensions must be multiples of %d", v);
     if (splitk > 1 && (flags & (AFR_GEMM_BIAS | AFR_GEMM_RELU | AFR_GEMM_RELU_MASK | AFR_GEMM_OUT_BF16)))
         return fail(AFR_EINVAL, "split-K output is plain f32 partial slabs");
-    if (dtype == AFR_BF16) {      // the LDS-DMA path addresses an operand with 32-bit byte offsets: 2 GiB per operand
-        const long long ea = (long long)(ak ? K : M) * lda * 2, ebb = (long long)(bk ? K : N) * ldb * 2;
-        if (ea >= (1ll << 31) || ebb >= (1ll << 31))
-            return fail(AFR_EUNSUPPORTED, "a bf16 GEMM operand must be smaller than 2 GiB (A %lld bytes, B %lld bytes)", ea, ebb);
-    }
-    DevGuard dg(device_of(C));
     GemmParams g;
     g.A = A; g.B = B; g.C = C; g.bias = bias; g.aux = aux; g.M = M; g.N = N; g.K = K;
     g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldaux = ldaux; g.flags = flags; g.splitk = splitk;
     g.slab_stride = (long long)M * ldc;
+    int rc;
+    if (dtype == AFR_BF16 && (rc = check_operand_bytes(g))) return rc;
+    DevGuard dg(device_of(C));
     HIPCHK(afr_launch_gemm(dtype, g, (hipStream_t)stream));
     return AFR_OK;
 }
@@ -1637,34 +1638,25 @@ extern "C" int afr_op_gemm_fix(int flags, const void* A, const void* B, void* C,
     const bool ak = flags & AFR_GEMM_A_KSTRIDED, bk = flags & AFR_GEMM_B_KSTRIDED;
     if ((ak ? M : K) % 8 || (bk ? N : K) % 8 || lda % 8 || ldb % 8 || N % 8 || ldc % 8)
         return fail(AFR_EUNSUPPORTED, "contiguous extents and leading dimensions must be multiples of 8");
-    const long long ea = (long long)(ak ? K : M) * lda * 2, ebb = (long long)(bk ? K : N) * ldb * 2;
-    if (ea >= (1ll << 31) || ebb >= (1ll << 31))
-        return fail(AFR_EUNSUPPORTED, "a bf16 GEMM operand must be smaller than 2 GiB (A %lld bytes, B %lld bytes)", ea, ebb);
+    GemmParams g;
+    g.A = A; g.B = B; g.C = C; g.bias = bias; g.aux = aux; g.M = M; g.N = N; g.K = K;
+    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldaux = ldaux; g.flags = flags; g.splitk = splitk;
+    if (int rc = check_operand_bytes(g)) return rc;
     const size_t need = afr_op_gemm_fix_workspace_bytes(M, N, head_tiles, splitk);
     if (workspace_bytes < need || ((uintptr_t)workspace & 15)) return fail(AFR_EINVAL, "workspace too small or misaligned: %zu < %zu", workspace_bytes, need);
     const long long tiles = (long long)((M + 255) / 256) * ((N + 255) / 256);
     const long long tail = tiles - (head_tiles < tiles ? head_tiles : tiles);
     DevGuard dg(device_of(C));
-    GemmParams g;
-    g.A = A; g.B = B; g.C = C; g.bias = bias; g.aux = aux; g.M = M; g.N = N; g.K = K;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldaux = ldaux; g.flags = flags; g.splitk = splitk;
     g.head_tiles = head_tiles;
     g.fix_ws = (float*)workspace;
     g.fix_cnt = (unsigned*)((char*)workspace + (size_t)(tail * splitk) * AFR_FIX_SLICE_BYTES);
     HIPCHK(afr_launch_gemm_fix(g, (hipStream_t)stream));
     return AFR_OK;
 }
-static bool pair_plan(int B, int N, int K, int* sk) {
-    int tile256 = 0;
-    *sk = 0;
-    if (B <= 0 || N < 256 || K <= 0) return false;
-    if ((long long)((B + 255) / 256) * ((K + 127) / 128) < 232) return false;          // as backward_stage_impl decides
-    afr_gemm_pair_plan(B, N, K, &tile256, sk);
-    return tile256 && (*sk == 2 || *sk == 4 || *sk == 8) && (long long)((N + 255) / 256) * ((K + 255) / 256) * *sk <= 256;
-}
 extern "C" int afr_op_gemm_pair_plan(int B, int N, int K, int* splitk, size_t* workspace_bytes) {
-    int sk;
-    if (!pair_plan(B, N, K, &sk)) return fail(AFR_EUNSUPPORTED, "%d x %d x %d does not run as a cooperative 256x256 pair", B, N, K);
+    const PairPlan pp = pair_plan_shape(B, N, K);
+    const int sk = pp.sk_group;
+    if (!pp.coop) return fail(AFR_EUNSUPPORTED, "%d x %d x %d does not run as a cooperative 256x256 pair", B, N, K);
     const size_t tiles = (size_t)((N + 255) / 256) * ((K + 255) / 256);
     if (splitk) *splitk = sk;
     if (workspace_bytes) *workspace_bytes = tiles * sk * AFR_FIX_SLICE_BYTES + align_up(tiles * sizeof(unsigned), 256);
@@ -1678,21 +1670,14 @@ extern "C" int afr_op_gemm_pair(const void* dy, const void* x, const void* W, co
     if (rc) return rc;
     if (N % 8 || K % 8) return fail(AFR_EUNSUPPORTED, "N and K must be multiples of 8");
     if (workspace_bytes < need || ((uintptr_t)workspace & 255)) return fail(AFR_EINVAL, "workspace too small or misaligned: %zu < %zu", workspace_bytes, need);
-    if ((long long)B * N * 2 >= (1ll << 31) || (long long)B * K * 2 >= (1ll << 31) || (long long)N * K * 2 >= (1ll << 31))
-        return fail(AFR_EUNSUPPORTED, "a bf16 GEMM operand must be smaller than 2 GiB");
+    GemmParams g[2] = {lin_dw(dy, x, dW, db_part, B, N, K, sk), lin_dx(dy, W, dX, aux, B, N, K, AFR_GEMM_OUT_BF16)};
+    if ((rc = check_operand_bytes(g[0])) || (rc = check_operand_bytes(g[1]))) return rc;
     DevGuard dg(device_of(dW));
     hipStream_t s = (hipStream_t)stream;
     const size_t tiles = (size_t)((N + 255) / 256) * ((K + 255) / 256);
     unsigned* cnt = (unsigned*)((char*)workspace + tiles * sk * AFR_FIX_SLICE_BYTES);
     HIPCHK(hipMemsetAsync(cnt, 0, align_up(tiles * sizeof(unsigned), 256), s));
-    GemmParams g[2];
-    g[0].A = dy; g[0].B = x; g[0].C = dW; g[0].M = N; g[0].N = K; g[0].K = B; g[0].lda = N; g[0].ldb = K; g[0].ldc = K; g[0].ldaux = 0;
-    g[0].bias = nullptr; g[0].aux = nullptr; g[0].flags = AFR_GEMM_A_KSTRIDED | AFR_GEMM_B_KSTRIDED; g[0].splitk = sk; g[0].slab_stride = 0;
-    g[0].colsum = db_part; g[0].colsum_stride = N;
-    g[0].coop_ws = (float*)workspace; g[0].coop_cnt = cnt; g[0].coop_target = (unsigned)sk; g[0].err = nullptr;
-    g[1].A = dy; g[1].B = W; g[1].C = dX; g[1].M = B; g[1].N = K; g[1].K = N; g[1].lda = N; g[1].ldb = K; g[1].ldc = K; g[1].ldaux = K;
-    g[1].bias = nullptr; g[1].aux = aux; g[1].flags = AFR_GEMM_B_KSTRIDED | AFR_GEMM_OUT_BF16 | (aux ? AFR_GEMM_RELU_MASK : 0);
-    g[1].splitk = 1; g[1].slab_stride = 0;
+    g[0].coop_ws = (float*)workspace; g[0].coop_cnt = cnt; g[0].coop_target = (unsigned)sk;
     HIPCHK(afr_launch_gemm_group(AFR_BF16, g, 2, 1, s));
     return AFR_OK;
 }

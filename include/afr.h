@@ -81,6 +81,9 @@ typedef struct afr_config {
                             bit 7: ReLU masks of the input-gradient products read from the stored activations instead of the
                             bit masks the forward epilogues leave (bits 6, 7: A/B measurements; bitwise equal results)      */
 } afr_config;
+/* the bits of afr_config.reserved, as described above */
+enum { AFR_CFG_UNFUSED_OPTIMIZER = 1, AFR_CFG_NO_GROUPED_GEMM = 2, AFR_CFG_NO_FUSED_GLYPH1 = 4, AFR_CFG_L1_BWD_UNFUSED = 16,
+       AFR_CFG_SLAB_SPLITK = 32, AFR_CFG_NO_COMBO_TABLE = 64, AFR_CFG_RELU_MASK_FROM_ACT = 128 };
 
 typedef struct afr_plan afr_plan;
 
