@@ -13,9 +13,19 @@ LIB_PATH = os.environ.get("AFR_LIB_PATH") or os.path.join(HERE, "csrc", "libafr.
 AFR_KIND_SHEET, AFR_KIND_GLYPH, AFR_KIND_PIXEL = 0, 1, 2
 AFR_F32, AFR_BF16, AFR_BF16X3 = 0, 1, 2
 AFR_TARGET_U8, AFR_TARGET_F32 = 0, 1
+AFR_LOSS_MSE, AFR_LOSS_BCE = 0, 1
+LOSS_KINDS = {"mse": AFR_LOSS_MSE, "bce": AFR_LOSS_BCE}
+
 AFR_MAX_HIDDEN = 8
 BUF_U, BUF_Z, BUF_DZ, BUF_W1T, BUF_W2T, BUF_ACT = 0, 1, 2, 4, 5, 16
 GEMM_BIAS, GEMM_RELU, GEMM_RELU_MASK, GEMM_OUT_BF16, GEMM_A_KSTRIDED, GEMM_B_KSTRIDED = 1, 2, 4, 8, 16, 32
+
+
+def loss_kind(loss):
+    """"mse" | "bce" -> AFR_LOSS_*; anything else is a ValueError."""
+    if not isinstance(loss, str) or loss not in LOSS_KINDS:
+        raise ValueError(f"loss must be 'mse' or 'bce', got {loss!r}")
+    return LOSS_KINDS[loss]
 
 
 class AfrConfig(C.Structure):
@@ -26,6 +36,7 @@ class AfrConfig(C.Structure):
         ("p_embed", C.c_float), ("p_attn", C.c_float), ("p_fc", C.c_float), ("ln_eps", C.c_float),
         ("n_hidden", C.c_int32), ("hidden", C.c_int32 * AFR_MAX_HIDDEN), ("n_fonts", C.c_int32),
         ("seed", C.c_uint64), ("rank", C.c_int32), ("reserved", C.c_int32),
+        ("loss", C.c_int32),
     ]
 
 
@@ -72,6 +83,7 @@ SIGNATURES = {
     "afr_op_reduce_group": (_i32, [_i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "afr_op_adamw": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _f32, _vp]),
     "afr_op_mse_grad": (_i32, [_i32, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "afr_op_bce_grad": (_i32, [_i32, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "afr_op_f32_to_bf16": (_i32, [_vp, _vp, _i64, _vp]),
     "afr_op_f32_to_fp8": (_i32, [_vp, _vp, _i64, _f32, _vp]),
     "afr_op_gemm_fp8": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),

@@ -2,6 +2,7 @@
 // launch sequences of forward / loss / backward / AdamW for both model families.
 #include "afr_common.h"
 #include "../../include/afr.h"
+static_assert(AFR_LOSS_MSE == LOSS_MSE && AFR_LOSS_BCE == LOSS_BCE, "afr.h and afr_common.h name the same loss kinds");
 
 #include <cmath>
 #include <cstdarg>
@@ -179,6 +180,8 @@ extern "C" int afr_plan_create(const afr_config* c, afr_plan** out) {
     if (!c || !out) return fail(AFR_EINVAL, "null argument");
     if (c->dtype != AFR_F32 && c->dtype != AFR_BF16 && c->dtype != AFR_BF16X3)
         return fail(AFR_EINVAL, "dtype must be AFR_F32, AFR_BF16 or AFR_BF16X3");
+    if (c->loss != AFR_LOSS_MSE && c->loss != AFR_LOSS_BCE)
+        return fail(AFR_EINVAL, "afr_config.loss must be AFR_LOSS_MSE (0) or AFR_LOSS_BCE (1), got %d", c->loss);
     // AFR_BF16X3 is the f32 plan (activations, layout, workspace, every non-GEMM kernel) whose products run bf16x3
     afr_config cf = *c;
     const int gemm_dtype = cf.dtype;
@@ -584,7 +587,8 @@ extern "C" int afr_profile_dump(afr_plan* p, char* buf, int cap) {
 
 // ------------------------------------------------------------------------------------ helpers
 struct FusedLoss { const void* target; int tdtype; int64_t mean_elems; float* loss_accum;
-                   const int* rowmap = nullptr; };       // targets of batch row b = row rowmap[b] of `target` (afr_*_rows); NULL = row b
+                   const int* rowmap = nullptr;          // targets of batch row b = row rowmap[b] of `target` (afr_*_rows); NULL = row b
+                   int kind = AFR_LOSS_MSE; };           // AFR_LOSS_*: the plan's loss kind
 // the six AdamW scalars of a fused update (GemmParams::ad_* / RTable::ad_*), as afr_launch_adamw derives them from its arguments
 template <class T> static void set_adam(T& o, const AdamArgs& h) {
     const float bc1 = (float)(1.0 - std::pow((double)h.b1, (double)h.t));
@@ -642,6 +646,7 @@ static void fuse_loss(const afr_plan* p, GemmParams& g, const FusedLoss& fl) {
     float* scratch = (float*)(p->ws + p->o_loss);
     g.mse_target = fl.target; g.mse_rowmap = fl.rowmap; g.mse_target_dtype = fl.tdtype; g.mse_inv_n = (float)(1.0 / (double)fl.mean_elems);
     g.mse_partial = scratch + 1040; g.mse_counter = reinterpret_cast<unsigned*>(scratch + 1032); g.mse_loss_accum = fl.loss_accum;
+    g.loss_kind = fl.kind;
 }
 // the bf16 LDS-DMA path addresses an operand with 32-bit byte offsets: 2 GiB per operand
 static int check_operand_bytes(const GemmParams& g) {
@@ -906,14 +911,15 @@ static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int 
         {
             ProfScope ps(p, s, "pixel_head", 0.0, (double)rows * d * (8.0 + p->act_bytes));
             HIPCHK(afr_launch_pixel_head(c.dtype, (const float*)(p->ws + p->pxs.back().h1), (float*)(p->ws + p->o_hf), a, p->P + p->px_lnfg, p->P + p->px_lnfb,
-                                         p->P + p->px_wout, p->P + p->px_bout, (float*)u, y, rows, d, c.ln_eps, s));
+                                         p->P + p->px_wout, p->P + p->px_bout, (float*)u, y, rows, d, c.ln_eps, s, c.loss));
         }
         p->last_x = x; p->last_font = font; p->last_B = B; p->last_L = 1; p->last_training = training; p->last_step = step;
         p->next_stage = 0; p->combo_on = false; p->mbits_on = false;
         p->have_du = false;
         if (fl) {        // the loss on the f32 pre-clamp output (model.py:156,268-270): du in place over u
-            ProfScope ps(p, s, "mse_grad", 0.0, (double)rows * 9.0);
-            HIPCHK(afr_launch_mse_grad(AFR_F32, u, fl->target, fl->tdtype, u, B, Pix, fl->mean_elems, fl->loss_accum, (float*)(p->ws + p->o_loss), s, fl->rowmap));
+            ProfScope ps(p, s, fl->kind == AFR_LOSS_BCE ? "bce_grad" : "mse_grad", 0.0, (double)rows * 9.0);
+            HIPCHK(afr_launch_mse_grad(AFR_F32, u, fl->target, fl->tdtype, u, B, Pix, fl->mean_elems, fl->loss_accum, (float*)(p->ws + p->o_loss), s, fl->rowmap,
+                                       fl->kind));
             p->have_du = true;
         }
         return AFR_OK;
@@ -963,8 +969,8 @@ static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int 
         p->last_L = 1;
     }
     if (y) {
-        ProfScope ps(p, s, "clamp_out", 0.0, 0.0);
-        HIPCHK(afr_launch_clamp_out(c.dtype, u, y, (long long)B * Pix, s));
+        ProfScope ps(p, s, c.loss == AFR_LOSS_BCE ? "sigmoid_out" : "clamp_out", 0.0, 0.0);
+        HIPCHK(afr_launch_clamp_out(c.dtype, u, y, (long long)B * Pix, s, c.loss));
     }
     p->last_x = x; p->last_font = font; p->last_B = B; p->last_training = training; p->last_step = step;
     p->next_stage = 0;
@@ -995,9 +1001,9 @@ static int loss_grad_impl(afr_plan* p, const void* target, int tdtype, const int
     const int Pix = p->cfg.out_h * p->cfg.out_w;
     void* u = p->ws + p->o_u;
     const double tb = tdtype == AFR_TARGET_U8 ? 1.0 : 4.0;
-    ProfScope ps(p, s, "mse_grad", 0.0, (double)B * Pix * (2.0 * p->act_bytes + tb));
+    ProfScope ps(p, s, p->cfg.loss == AFR_LOSS_BCE ? "bce_grad" : "mse_grad", 0.0, (double)B * Pix * (2.0 * p->act_bytes + tb));
     HIPCHK(afr_launch_mse_grad(p->cfg.kind == AFR_KIND_PIXEL ? AFR_F32 : p->cfg.dtype, u, target, tdtype, u, B, Pix, mean_elems, loss_accum,
-                               (float*)(p->ws + p->o_loss), s, rowmap));      // (the pixel transformer's pre-clamp output is f32 in both modes)
+                               (float*)(p->ws + p->o_loss), s, rowmap, p->cfg.loss));      // (the pixel transformer's pre-clamp output is f32 in both modes)
     p->have_du = true;
     return AFR_OK;
 }
@@ -1011,7 +1017,8 @@ extern "C" int afr_set_output_grad(afr_plan* p, const float* dy, int B, void* st
     DevGuard dg(p->device);
     if (!dy) return fail(AFR_EINVAL, "dy is null");
     if (B != p->last_B) return fail(AFR_ESTATE, "batch %d does not match the last forward (%d)", B, p->last_B);
-    HIPCHK(afr_launch_clamp_bwd(p->cfg.kind == AFR_KIND_PIXEL ? AFR_F32 : p->cfg.dtype, p->ws + p->o_u, dy, (long long)B * p->cfg.out_h * p->cfg.out_w, (hipStream_t)stream));
+    HIPCHK(afr_launch_clamp_bwd(p->cfg.kind == AFR_KIND_PIXEL ? AFR_F32 : p->cfg.dtype, p->ws + p->o_u, dy, (long long)B * p->cfg.out_h * p->cfg.out_w, (hipStream_t)stream,
+                                p->cfg.loss));
     p->have_du = true;
     return AFR_OK;
 }
@@ -1380,7 +1387,7 @@ static int glyph1_fused(afr_plan* p, const int64_t* x, const int64_t* font, cons
         p->wT_valid = true;
     }
     Glyph1Args a;
-    a.x = x; a.font = font; a.target = target; a.tdtype = tdtype; a.rowmap = rowmap;
+    a.x = x; a.font = font; a.target = target; a.tdtype = tdtype; a.rowmap = rowmap; a.loss_kind = c.loss;
     a.B = B; a.E = E; a.N1 = N1; a.P = Pix; a.vocab = c.vocab; a.n_fonts = c.n_fonts;
     a.emb = p->P + p->emb_off; a.femb = c.n_fonts > 0 ? p->P + p->font_off : nullptr;
     a.b1 = p->P + l1.b_off; a.b2 = p->P + l2.b_off;
@@ -1429,7 +1436,7 @@ static int glyph1_fused(afr_plan* p, const int64_t* x, const int64_t* font, cons
 static int forward_loss_impl(afr_plan* p, const int64_t* x, const int64_t* font, const void* target, int tdtype, const int* rowmap, int B, int L,
                              int64_t mean_elems, float* loss_accum, uint64_t step, void* stream) {
     if (int rc = check_loss_args(target, tdtype, mean_elems, loss_accum)) return rc;
-    FusedLoss fl{target, tdtype, mean_elems, loss_accum, rowmap};
+    FusedLoss fl{target, tdtype, mean_elems, loss_accum, rowmap, p->cfg.loss};
     return forward_impl(p, x, font, B, L, nullptr, 1, step, stream, &fl);
 }
 extern "C" int afr_forward_loss(afr_plan* p, const int64_t* x, const int64_t* font, const void* target, int tdtype, int B, int L,
@@ -1462,7 +1469,7 @@ static int train_step_impl(afr_plan* p, const int64_t* x, const int64_t* font, c
         return AFR_OK;
     }
     // the loss and its gradient are computed in the epilogue of the last forward GEMM: u never touches HBM
-    FusedLoss fl{target, tdtype, mean_elems, loss_accum, rowmap};
+    FusedLoss fl{target, tdtype, mean_elems, loss_accum, rowmap, p->cfg.loss};
     if ((rc = forward_impl(p, x, font, B, L, nullptr, 1, step, stream, &fl))) return rc;
     if (fuse_opt && fused_step_eligible(p, B)) {
         if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
@@ -1578,6 +1585,9 @@ extern "C" int afr_debug_copy(afr_plan* p, int which, void* dst, size_t cap, siz
         const int i = which - AFR_BUF_ACT;
         off = p->o_act[i];
         bytes = B * (size_t)(i == 0 ? (p->k0 ? p->k0 : c.embed_dim) : c.hidden[i - 1]) * ab;
+    } else if (which >= AFR_BUF_ACT && c.kind == AFR_KIND_PIXEL && which - AFR_BUF_ACT < (int)p->pxs.size()) {
+        off = p->pxs[which - AFR_BUF_ACT].f;           // block i's ReLU output f [B * tokens][fc_dim]: its sign is the MLP's gate
+        bytes = B * (size_t)c.out_h * c.out_w * c.fc_dim * ab;
     } else return fail(AFR_EINVAL, "no such buffer %d for this model kind", which);
     if (bytes > cap) return fail(AFR_EINVAL, "destination too small: %zu < %zu", cap, bytes);
     HIPCHK(hipMemcpyAsync(dst, p->ws + off, bytes, hipMemcpyDefault, (hipStream_t)stream));
@@ -1717,6 +1727,14 @@ extern "C" int afr_op_mse_grad(int act_dtype, const void* u, const void* target,
     DevGuard dg(device_of(du));
     HIPCHK(afr_launch_mse_grad(act_dtype, u, target, tdtype, du, rows, cols, mean_elems, loss_accum, scratch,
                                (hipStream_t)stream));
+    return AFR_OK;
+}
+extern "C" int afr_op_bce_grad(int act_dtype, const void* u, const void* target, int tdtype, void* du, int64_t rows,
+                               int64_t cols, int64_t mean_elems, float* loss_accum, float* scratch, void* stream) {
+    if (!u || !target || !du || !loss_accum || !scratch) return fail(AFR_EINVAL, "null argument");
+    DevGuard dg(device_of(du));
+    HIPCHK(afr_launch_mse_grad(act_dtype, u, target, tdtype, du, rows, cols, mean_elems, loss_accum, scratch,
+                               (hipStream_t)stream, nullptr, AFR_LOSS_BCE));
     return AFR_OK;
 }
 extern "C" int afr_op_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream) {

@@ -85,6 +85,27 @@ __device__ __forceinline__ void loss_block_finish(float block_sum, float* partia
     }
 }
 
+// Loss kinds of a plan (afr_config.loss; the values of AFR_LOSS_* in afr.h).  The kind is a template parameter of every kernel
+// that computes a loss or an output head: the LOSS_MSE instantiations hold no BCE code.
+constexpr int LOSS_MSE = 0, LOSS_BCE = 1;
+// The sigmoid head of a BCE plan, stable form: e = exp(-|u|) <= 1, so nothing overflows at either end.
+__device__ __forceinline__ float sigmoid_of(float u, float e) {
+    const float r = __builtin_amdgcn_rcpf(1.f + e);
+    return u >= 0.f ? r : e * r;
+}
+__device__ __forceinline__ float sigmoid_f(float u) { return sigmoid_of(u, __expf(-fabsf(u))); }
+// Binary cross-entropy on the logit u of ONE pixel with soft target t (F.binary_cross_entropy_with_logits): returns the loss
+// term max(u,0) - t u + log1p(exp(-|u|)) and leaves du = (sigmoid(u) - t) * inv_n.  Every BCE site -- the loss kernel, the two
+// GEMM epilogues, the fused small-net step -- calls this, so that fused and unfused paths give du bit for bit (sub then mul:
+// nothing for the compiler to contract).  One v_exp_f32, one v_rcp_f32, one v_log_f32.  log1p is taken as log(1 + e): below
+// e = 6e-8 the term is dropped, an absolute error per pixel smaller than one rounding of t u there; it saves the epilogues
+// the registers and branches of a true log1p.
+__device__ __forceinline__ float bce_logits_elem(float u, float t, float inv_n, float& du) {
+    const float e = __expf(-fabsf(u));
+    du = (sigmoid_of(u, e) - t) * inv_n;
+    return fmaf(-t, u, fmaxf(u, 0.f)) + __logf(1.f + e);
+}
+
 __device__ __forceinline__ float bf16_to_f32(bf16_t x) { return (float)x; }
 __device__ __forceinline__ bf16_t f32_to_bf16(float x) { return (bf16_t)x; }
 
@@ -111,6 +132,7 @@ struct GemmParams {
     float* mse_partial = nullptr;       // per-block partial sums (>= grid floats)
     unsigned* mse_counter = nullptr;    // arrival counter, zero on entry, re-armed by the last block
     float* mse_loss_accum = nullptr;    // device scalar: += sum(partials) / mean_elems
+    int loss_kind = 0;                  // LOSS_MSE, or LOSS_BCE: du = (sigmoid(u) - t) / mean_elems and the BCE-with-logits sum instead
     // optional fused optimizer (dW GEMMs only, single GPU): C is the weight's gradient tile; instead of storing it
     // the epilogue applies AdamW to the matching tile of p/m/v (same [M][ldc] layout) and refreshes the bf16 shadow
     float* ad_p = nullptr; float* ad_m = nullptr; float* ad_v = nullptr; bf16_t* ad_shadow = nullptr;
@@ -196,14 +218,16 @@ int afr_mse_blocks(long long rows, long long cols);
 // scratch: >= 1028 floats; scratch[1024] (as unsigned) is the arrival counter, zero before the first call
 hipError_t afr_launch_mse_grad(int act_dtype, const void* u, const void* target, int target_dtype, void* du,
                                long long rows, long long cols, long long mean_elems, float* loss_accum,
-                               float* scratch, hipStream_t s, const int* rowmap = nullptr /* target row of u row r; NULL = r */);
+                               float* scratch, hipStream_t s, const int* rowmap = nullptr /* target row of u row r; NULL = r */,
+                               int loss_kind = LOSS_MSE);
 // Batch rows of a resident data set (afr_*_rows): validates and clamps rows[b] (AFR_ERR_ROW), writes ridx[b] = the narrowed index
 // the loss kernels' row maps read and, when sx is not NULL, stages x[rows[b]][0 .. Lc) into sx [B][Lc] and font[rows[b]] into sfont.
 hipError_t afr_launch_dataset_rows(const int64_t* rows, int B, long long n_rows, const int64_t* x, const int64_t* font, int L, int Lc,
                                    int* ridx, int64_t* sx, int64_t* sfont, uint32_t* err_flag, hipStream_t s);
 hipError_t afr_launch_f32_to_bf16(const float* src, bf16_t* dst, long long n, hipStream_t s);
-hipError_t afr_launch_clamp_bwd(int act_dtype, void* u_inout, const float* dy, long long n, hipStream_t s);
-hipError_t afr_launch_clamp_out(int act_dtype, const void* u, float* y, long long n, hipStream_t s);
+// the output head and its backward for a caller-side loss: clamp(u, 0, 1), or sigmoid(u) on a LOSS_BCE plan
+hipError_t afr_launch_clamp_bwd(int act_dtype, void* u_inout, const float* dy, long long n, hipStream_t s, int loss_kind = LOSS_MSE);
+hipError_t afr_launch_clamp_out(int act_dtype, const void* u, float* y, long long n, hipStream_t s, int loss_kind = LOSS_MSE);
 // glyph embedding gather / deterministic scatter-add
 hipError_t afr_launch_glyph_embed(int act_dtype, const float* emb, const float* font_emb, const int64_t* x,
                                   const int64_t* font, int B, int E, int vocab, int n_fonts, void* out,
@@ -265,6 +289,7 @@ hipError_t afr_launch_sheet_bwd(int act_dtype, const SheetDims& d, const SheetPa
 struct Glyph1Args {
     const int64_t* x; const int64_t* font; const void* target; int tdtype;
     const int* rowmap = nullptr;             // optional: the targets of glyph b are row rowmap[b] of target (NULL = row b)
+    int loss_kind = 0;                       // LOSS_MSE | LOSS_BCE
     int B, E, N1, P, vocab, n_fonts;
     const float *emb, *femb, *b1, *b2;       // f32 masters
     const void *W1, *W2;                     // [N1][E], [P][N1] in the operand type (f32 masters / bf16 shadow)
@@ -289,7 +314,7 @@ hipError_t afr_launch_pixel_add_ln(int act_dtype, const float* hin, float* h, co
                                    long long rows, int Tk, int d, float eps, hipStream_t s);
 hipError_t afr_launch_pixel_attn(int act_dtype, const void* q, const void* kv, void* o, long long rows, int Tk, int d, int heads, int C, hipStream_t s);
 hipError_t afr_launch_pixel_head(int act_dtype, const float* hin, float* h, const void* add, const float* g, const float* b, const float* w_out, const float* b_out,
-                                 float* u, float* y, long long rows, int d, float eps, hipStream_t s);
+                                 float* u, float* y, long long rows, int d, float eps, hipStream_t s, int loss_kind = LOSS_MSE);
 int afr_pixel_bwd_blocks(long long rows);           // blocks (= partial slabs) of the head / LayerNorm backward kernels
 int afr_pixel_attn_chunk(int Tk);                   // tokens per attention-backward block
 hipError_t afr_launch_pixel_head_bwd(int act_dtype, const float* du, const float* hf, const float* g, const float* b, const float* w_out, float* dh,

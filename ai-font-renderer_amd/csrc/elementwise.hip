@@ -244,32 +244,45 @@ hipError_t afr_launch_f32_to_fp8(const float* src, unsigned char* dst, long long
 }
 
 // -------------------------------------------------------------------- clamp output (eval path)
-// y = clamp(u, 0, 1) as float32: the model's output activation (reference model.py:156,202)
-template <typename T>
+// y = clamp(u, 0, 1) as float32: the model's output activation (reference model.py:156,202); LOSS_BCE: y = sigmoid(u)
+template <typename T, int LOSS = LOSS_MSE>
 __global__ __launch_bounds__(256) void clamp_out_kernel(const T* __restrict__ u, float* __restrict__ y, long long n) {
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
-        y[i] = fminf(fmaxf((float)u[i], 0.f), 1.f);
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        if constexpr (LOSS == LOSS_BCE) y[i] = sigmoid_f((float)u[i]);
+        else y[i] = fminf(fmaxf((float)u[i], 0.f), 1.f);
+    }
 }
-hipError_t afr_launch_clamp_out(int act_dtype, const void* u, float* y, long long n, hipStream_t s) {
+hipError_t afr_launch_clamp_out(int act_dtype, const void* u, float* y, long long n, hipStream_t s, int loss_kind) {
     if (n <= 0) return hipSuccess;
-    if (act_dtype == AFR_BF16)
-        hipLaunchKernelGGL(clamp_out_kernel<bf16_t>, dim3(grid_for(n, 256)), dim3(256), 0, s, (const bf16_t*)u, y, n);
+    const dim3 g(grid_for(n, 256)), b(256);
+    if (loss_kind == LOSS_BCE) {
+        if (act_dtype == AFR_BF16) hipLaunchKernelGGL((clamp_out_kernel<bf16_t, LOSS_BCE>), g, b, 0, s, (const bf16_t*)u, y, n);
+        else hipLaunchKernelGGL((clamp_out_kernel<float, LOSS_BCE>), g, b, 0, s, (const float*)u, y, n);
+    } else if (act_dtype == AFR_BF16)
+        hipLaunchKernelGGL(clamp_out_kernel<bf16_t>, g, b, 0, s, (const bf16_t*)u, y, n);
     else
-        hipLaunchKernelGGL(clamp_out_kernel<float>, dim3(grid_for(n, 256)), dim3(256), 0, s, (const float*)u, y, n);
+        hipLaunchKernelGGL(clamp_out_kernel<float>, g, b, 0, s, (const float*)u, y, n);
     return hipGetLastError();
 }
 
 // du = dy * [0 <= u <= 1], in place over u: torch.clamp's backward (reference model.py:156) for a caller-side loss
-template <typename T>
+// LOSS_BCE (sigmoid head): du = dy * y * (1 - y) with y = sigmoid(u) recomputed from the stored u
+template <typename T, int LOSS = LOSS_MSE>
 __global__ __launch_bounds__(256) void clamp_bwd_kernel(T* __restrict__ u, const float* __restrict__ dy, long long n) {
     for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const float uv = (float)u[i];
-        u[i] = (T)((uv >= 0.f && uv <= 1.f) ? dy[i] : 0.f);
+        if constexpr (LOSS == LOSS_BCE) {
+            const float y = sigmoid_f(uv);
+            u[i] = (T)(dy[i] * y * (1.f - y));
+        } else u[i] = (T)((uv >= 0.f && uv <= 1.f) ? dy[i] : 0.f);
     }
 }
-hipError_t afr_launch_clamp_bwd(int act_dtype, void* u, const float* dy, long long n, hipStream_t s) {
+hipError_t afr_launch_clamp_bwd(int act_dtype, void* u, const float* dy, long long n, hipStream_t s, int loss_kind) {
     if (n <= 0) return hipSuccess;
-    if (act_dtype == AFR_BF16) hipLaunchKernelGGL(clamp_bwd_kernel<bf16_t>, dim3(grid_for(n, 256)), dim3(256), 0, s, (bf16_t*)u, dy, n);
+    if (loss_kind == LOSS_BCE) {
+        if (act_dtype == AFR_BF16) hipLaunchKernelGGL((clamp_bwd_kernel<bf16_t, LOSS_BCE>), dim3(grid_for(n, 256)), dim3(256), 0, s, (bf16_t*)u, dy, n);
+        else hipLaunchKernelGGL((clamp_bwd_kernel<float, LOSS_BCE>), dim3(grid_for(n, 256)), dim3(256), 0, s, (float*)u, dy, n);
+    } else if (act_dtype == AFR_BF16) hipLaunchKernelGGL(clamp_bwd_kernel<bf16_t>, dim3(grid_for(n, 256)), dim3(256), 0, s, (bf16_t*)u, dy, n);
     else hipLaunchKernelGGL(clamp_bwd_kernel<float>, dim3(grid_for(n, 256)), dim3(256), 0, s, (float*)u, dy, n);
     return hipGetLastError();
 }
@@ -281,7 +294,9 @@ hipError_t afr_launch_clamp_bwd(int act_dtype, void* u, const float* dy, long lo
 // du may alias u.  Per-lane sums -> wave shuffle -> LDS -> one partial per block -> fixed-order finisher.
 // ROWS: the targets of row r of u are row rowmap[r] of tgt (a resident data set read in place; cols8 = groups of 8 pixels per
 // row): the same walk over u, the target group addressed as (row, column group) with 64-bit arithmetic.
-template <typename T, typename TT, bool ROWS>
+// LOSS_BCE: the same walk, loads, stores and block finish with loss = sum(max(u,0) - t u + log1p(exp(-|u|))) / mean_elems and
+// du = (sigmoid(u) - t) / mean_elems (bce_logits_elem): F.binary_cross_entropy_with_logits on the sigmoid head's logits.
+template <typename T, typename TT, bool ROWS, int LOSS = LOSS_MSE>
 __global__ __launch_bounds__(256) void mse_grad_kernel(const T* __restrict__ u, const TT* __restrict__ tgt,
                                                        T* __restrict__ du, long long n8, float inv_n,
                                                        float* __restrict__ partial, unsigned* __restrict__ counter,
@@ -317,10 +332,13 @@ __global__ __launch_bounds__(256) void mse_grad_kernel(const T* __restrict__ u, 
         float dd[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const float y = fminf(fmaxf(uu[k], 0.f), 1.f);
-            const float diff = y - tt[k];
-            lsum += diff * diff;
-            dd[k] = (uu[k] >= 0.f && uu[k] <= 1.f) ? g2 * diff : 0.f;
+            if constexpr (LOSS == LOSS_BCE) lsum += bce_logits_elem(uu[k], tt[k], inv_n, dd[k]);
+            else {
+                const float y = fminf(fmaxf(uu[k], 0.f), 1.f);
+                const float diff = y - tt[k];
+                lsum += diff * diff;
+                dd[k] = (uu[k] >= 0.f && uu[k] <= 1.f) ? g2 * diff : 0.f;
+            }
         }
         if (sizeof(T) == 4) {
             reinterpret_cast<float4*>(du)[2 * i] = make_float4(dd[0], dd[1], dd[2], dd[3]);
@@ -342,7 +360,7 @@ __global__ __launch_bounds__(256) void mse_grad_kernel(const T* __restrict__ u, 
 int afr_mse_blocks(long long rows, long long cols) { return grid_for(rows * cols / 8, 256, 1024); }
 hipError_t afr_launch_mse_grad(int act_dtype, const void* u, const void* target, int target_dtype, void* du,
                                long long rows, long long cols, long long mean_elems, float* loss_accum,
-                               float* scratch, hipStream_t s, const int* rowmap) {
+                               float* scratch, hipStream_t s, const int* rowmap, int loss_kind) {
     const long long n = rows * cols;
     if (n <= 0) return hipSuccess;
     if ((n & 7) || (rowmap && (cols & 7))) return hipErrorInvalidValue;
@@ -350,19 +368,21 @@ hipError_t afr_launch_mse_grad(int act_dtype, const void* u, const void* target,
     const float inv_n = (float)(1.0 / (double)mean_elems);
     dim3 g(blocks), b(256);
     unsigned* counter = reinterpret_cast<unsigned*>(scratch + 1024);
-#define MSE(T, TT)                                                                                                                      \
-    do {                                                                                                                                \
-        if (rowmap) hipLaunchKernelGGL((mse_grad_kernel<T, TT, true>), g, b, 0, s, (const T*)u, (const TT*)target, (T*)du, n / 8, inv_n, \
-                                       scratch, counter, loss_accum, rowmap, (int)(cols / 8));                                          \
-        else hipLaunchKernelGGL((mse_grad_kernel<T, TT, false>), g, b, 0, s, (const T*)u, (const TT*)target, (T*)du, n / 8, inv_n,      \
-                                scratch, counter, loss_accum, (const int*)nullptr, 0);                                                  \
+#define MSE_K(T, TT, K)                                                                                                                    \
+    do {                                                                                                                                   \
+        if (rowmap) hipLaunchKernelGGL((mse_grad_kernel<T, TT, true, K>), g, b, 0, s, (const T*)u, (const TT*)target, (T*)du, n / 8, inv_n, \
+                                       scratch, counter, loss_accum, rowmap, (int)(cols / 8));                                             \
+        else hipLaunchKernelGGL((mse_grad_kernel<T, TT, false, K>), g, b, 0, s, (const T*)u, (const TT*)target, (T*)du, n / 8, inv_n,      \
+                                scratch, counter, loss_accum, (const int*)nullptr, 0);                                                     \
     } while (0)
+#define MSE(T, TT) do { if (loss_kind == LOSS_BCE) MSE_K(T, TT, LOSS_BCE); else MSE_K(T, TT, LOSS_MSE); } while (0)
     if (act_dtype == AFR_BF16) {
         if (target_dtype == AFR_TARGET_U8) MSE(bf16_t, uint8_t); else MSE(bf16_t, float);
     } else {
         if (target_dtype == AFR_TARGET_U8) MSE(float, uint8_t); else MSE(float, float);
     }
 #undef MSE
+#undef MSE_K
     return hipGetLastError();
 }
 

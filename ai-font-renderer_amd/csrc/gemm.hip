@@ -124,8 +124,9 @@ __device__ __forceinline__ void colsum_store(const GemmParams& p, float* smem, c
 }
 // bias, ReLU, ReLU mask, split-K slabs, bf16 output, fused clamp/MSE/du, fused AdamW; smem: >= 16 + 256 floats of scratch
 // TROWS: the fused loss' targets are rows p.mse_rowmap[m] of a resident data set (its own instantiation: the dense kernels carry
-// no row-map code)
-template <bool TROWS = false>
+// no row-map code).  LOSS: the fused loss' kind, likewise an instantiation of its own (LOSS_BCE: sigmoid head + BCE on the logits,
+// bce_logits_elem; the LOSS_MSE kernels carry none of it)
+template <bool TROWS = false, int LOSS = LOSS_MSE>
 __device__ __forceinline__ void tile_epilogue(const GemmParams& p, const f32x16 (&acc)[2][2], const int m0, const int n0, const int z,
                                               const int tid, float* smem) {
     const int lane = tid & 63, wid = tid >> 6;
@@ -158,9 +159,14 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& p, const f32x16 
                     const size_t ti = (size_t)(TROWS ? p.mse_rowmap[m] : m) * p.N + n;
                     const float t = p.mse_target_dtype == AFR_TARGET_U8 ? (float)reinterpret_cast<const uint8_t*>(p.mse_target)[ti] / 255.0f
                                                                         : reinterpret_cast<const float*>(p.mse_target)[ti];
-                    const float diff = fminf(fmaxf(v, 0.f), 1.f) - t;
-                    lsum += diff * diff;
-                    v = (v >= 0.f && v <= 1.f) ? g2 * diff : 0.f;
+                    if constexpr (LOSS == LOSS_BCE) {
+                        const float uu = v;
+                        lsum += bce_logits_elem(uu, t, p.mse_inv_n, v);
+                    } else {
+                        const float diff = fminf(fmaxf(v, 0.f), 1.f) - t;
+                        lsum += diff * diff;
+                        v = (v >= 0.f && v <= 1.f) ? g2 * diff : 0.f;
+                    }
                 }
                 if (p.ad_p) {                          // fused AdamW on weight element (m, n); v is its gradient
                     const size_t wi = (size_t)m * p.ldc + n;
@@ -180,7 +186,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& p, const f32x16 
     }
 }
 
-template <int ALAY, int BLAY, bool TROWS = false>
+template <int ALAY, int BLAY, bool TROWS = false, int LOSS = LOSS_MSE>
 __global__ __launch_bounds__(256) void gemm_f32(GemmParams p) {
     constexpr int LDA = Lds<ALAY>::LD, LDB = Lds<BLAY>::LD;
     constexpr int TILE = BK * LDA + BK * LDB;
@@ -254,7 +260,7 @@ __global__ __launch_bounds__(256) void gemm_f32(GemmParams p) {
         smem[tid] = cs;
         colsum_store(p, smem, tid, m0, z, 2);
     }
-    tile_epilogue<TROWS>(p, acc, m0, n0, z, tid, smem);
+    tile_epilogue<TROWS, LOSS>(p, acc, m0, n0, z, tid, smem);
 }
 }  // namespace f32k
 
@@ -328,7 +334,7 @@ __device__ __forceinline__ bf16x8 frag(const char* S, int xb, int ks, int lane) 
     return *reinterpret_cast<const bf16x8*>(S + xoff(xb + (lane & 31), 2 * ks + (lane >> 5)));
 }
 
-template <int ALAY, int BLAY, bool TROWS = false>
+template <int ALAY, int BLAY, bool TROWS = false, int LOSS = LOSS_MSE>
 __global__ __launch_bounds__(256, 2) void gemm_bf16x3(GemmParams p) {
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -418,7 +424,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3(GemmParams p) {
         for (int e = 0; e < 4; ++e) sf[kq * 128 + xb + e] = cs[e];
         f32k::colsum_store(p, sf, tid, m0, z, 8);
     }
-    f32k::tile_epilogue<TROWS>(p, acc, m0, n0, z, tid, sf);
+    f32k::tile_epilogue<TROWS, LOSS>(p, acc, m0, n0, z, tid, sf);
 }
 }  // namespace x3k
 
@@ -559,7 +565,8 @@ __device__ __forceinline__ void epilogue_bias(const GemmParams& p, const int nb0
 // over either half of its 128 x 64 tile without copying 64 registers)
 // (TROWS: the fused loss' targets are rows p.mse_rowmap[m] of a resident data set, read in place -- its own instantiation of the
 // forward-layout ring kernels, so that the dense kernels carry no row-map code)
-template <int ALAY, int BLAY, int WM, bool SCALE = false, bool EARLYB_ = true, bool TROWS = false, class ACC>      // SCALE: the accumulators are multiplied by p.out_scale first (fp8 per-tensor scales)
+// (LOSS: the fused loss' kind, an instantiation of its own as well: the LOSS_MSE kernels carry no BCE code)
+template <int ALAY, int BLAY, int WM, bool SCALE = false, bool EARLYB_ = true, bool TROWS = false, int LOSS = LOSS_MSE, class ACC>      // SCALE: the accumulators are multiplied by p.out_scale first (fp8 per-tensor scales)
 __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC& acc_at, const int mb, const int nb0, const int z,
                                                  float* Wt, const int lane, float& lsum, const float* lut255 = nullptr,
                                                  const float (*pre_bias)[8] = nullptr) {
@@ -788,9 +795,12 @@ __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC&
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
                 const float u = out_bf16 ? (float)(bf16_t)v[r] : v[r];     // the value the unfused path would store
-                const float diff = fminf(fmaxf(u, 0.f), 1.f) - t[r];
-                lsum += diff * diff;
-                v[r] = (u >= 0.f && u <= 1.f) ? g2 * diff : 0.f;
+                if constexpr (LOSS == LOSS_BCE) lsum += bce_logits_elem(u, t[r], p.mse_inv_n, v[r]);
+                else {
+                    const float diff = fminf(fmaxf(u, 0.f), 1.f) - t[r];
+                    lsum += diff * diff;
+                    v[r] = (u >= 0.f && u <= 1.f) ? g2 * diff : 0.f;
+                }
             }
         }
         {
@@ -810,10 +820,10 @@ __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC&
     }
 }
 
-template <int ALAY, int BLAY, int WM, bool SCALE = false, bool EARLYB_ = true, bool TROWS = false>
+template <int ALAY, int BLAY, int WM, bool SCALE = false, bool EARLYB_ = true, bool TROWS = false, int LOSS = LOSS_MSE>
 __device__ __forceinline__ void wave_epilogue(const GemmParams& p, const f32x4 (&acc)[4][4], const int mb, const int nb0, const int z,
                                               float* Wt, const int lane, float& lsum, const float* lut255 = nullptr) {
-    wave_epilogue_at<ALAY, BLAY, WM, SCALE, EARLYB_, TROWS>(p, [&](int i, int j) { return acc[i][j]; }, mb, nb0, z, Wt, lane, lsum, lut255);
+    wave_epilogue_at<ALAY, BLAY, WM, SCALE, EARLYB_, TROWS, LOSS>(p, [&](int i, int j) { return acc[i][j]; }, mb, nb0, z, Wt, lane, lsum, lut255);
 }
 
 // Finish of one wave's 16 x 64 f32 strip of a weight gradient (cooperative split-K, gemm_bf16_256_body): v[j] holds rows
@@ -887,10 +897,11 @@ template <int WM> struct RingGeom {
 // passes its own blockIdx / gridDim; a grouped launch (gemm_bf16_group) a sub-range of its grid.
 // GA: the k-contiguous A operand's rows are gathered through p.a_rowmap (ALAY == 0, WM == 4 only)
 // TROWS: the fused loss reads its targets through p.mse_rowmap (forward layout only)
-template <int ALAY, int BLAY, int WM, int GA = 0, bool TROWS = false>
+template <int ALAY, int BLAY, int WM, int GA = 0, bool TROWS = false, int LOSS = LOSS_MSE>
 __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p, const int bid, const int nblk, char* smem) {
     static_assert(!GA || (ALAY == 0 && WM == 4), "row gather: k-contiguous A on the 256x128 ring kernel");
     static_assert(!TROWS || (ALAY == 0 && BLAY == 0 && !GA), "row-mapped loss targets: the forward layout");
+    static_assert(LOSS == LOSS_MSE || (ALAY == 0 && BLAY == 0 && !GA), "a fused BCE loss: the forward layout");
     constexpr int BM = 64 * WM, NW = 2 * WM, ASUB = WM / 2;
     constexpr int STAGES = RingGeom<WM>::STAGES;
     constexpr int STAGE_BYTES = RingGeom<WM>::STAGE_BYTES;
@@ -1180,7 +1191,7 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p, const int bi
         __syncthreads();
         lut255 = l;
     }
-    wave_epilogue<ALAY, BLAY, WM, false, true, TROWS>(p, acc, m0 + wm * 64, n0 + wn * 64, z, reinterpret_cast<float*>(smem) + wave * 4096, lane, lsum, lut255);
+    wave_epilogue<ALAY, BLAY, WM, false, true, TROWS, LOSS>(p, acc, m0 + wm * 64, n0 + wn * 64, z, reinterpret_cast<float*>(smem) + wave * 4096, lane, lsum, lut255);
     if (mse) {
         float* red = reinterpret_cast<float*>(smem);
         __syncthreads();                       // every wave is done with its staging tile
@@ -1593,10 +1604,10 @@ __device__ __forceinline__ void gemm_bf16_256_body(const GemmParams& p, const in
 #endif
 }
 
-template <int ALAY, int BLAY, int WM, int GA = 0, bool TROWS = false>
+template <int ALAY, int BLAY, int WM, int GA = 0, bool TROWS = false, int LOSS = LOSS_MSE>
 __global__ __launch_bounds__(128 * WM, 2) void gemm_bf16(GemmParams p) {
     __shared__ __attribute__((aligned(16))) char smem[RingGeom<WM>::LDS_BYTES];
-    gemm_bf16_body<ALAY, BLAY, WM, GA, TROWS>(p, blockIdx.x, gridDim.x, smem);
+    gemm_bf16_body<ALAY, BLAY, WM, GA, TROWS, LOSS>(p, blockIdx.x, gridDim.x, smem);
 }
 
 // Several independent products in ONE launch (a layer's weight gradient and input gradient both consume the same dy):
@@ -2056,6 +2067,10 @@ hipError_t afr_launch_gemm(int dtype, const GemmParams& p_in, hipStream_t s) {
 #endif
     const int a = (p.flags & AFR_GEMM_A_KSTRIDED) ? 1 : 0, b = (p.flags & AFR_GEMM_B_KSTRIDED) ? 1 : 0;
     if (p.M <= 0 || p.N <= 0) return hipSuccess;
+    if (p.loss_kind != LOSS_MSE && p.loss_kind != LOSS_BCE) return hipErrorInvalidValue;
+    // a fused BCE loss: the forward layout of the ring / tile kernels, one instantiation per (row map, kernel)
+    const bool bce = p.loss_kind == LOSS_BCE && p.mse_target;
+    if (bce && (a || b || p.a_rowmap || p.splitk != 1)) return hipErrorInvalidValue;      // (a gathered A has its own kernel, without this loss)
     // row-mapped loss targets: the forward layout of the ring / tile kernels, its own instantiations
     if (p.mse_rowmap && (!p.mse_target || a || b || p.a_rowmap || p.splitk != 1 || (dtype == AFR_BF16 && bf16_use_body256(p)))) return hipErrorInvalidValue;
     if (p.a_rowmap || p.b_rowmap || p.aux_rowmap) {
@@ -2072,6 +2087,13 @@ hipError_t afr_launch_gemm(int dtype, const GemmParams& p_in, hipStream_t s) {
 #define LB(AL, BL) do { if (wide) hipLaunchKernelGGL((bf16k::gemm_bf16<AL, BL, 4>), grid, dim3(512), 0, s, p); \
                         else hipLaunchKernelGGL((bf16k::gemm_bf16<AL, BL, 2>), grid, dim3(256), 0, s, p); } while (0)
         if (p.a_rowmap) hipLaunchKernelGGL((bf16k::gemm_bf16<0, 0, 4, 1>), grid, dim3(512), 0, s, p);
+        else if (bce) {
+            if (p.mse_rowmap) {
+                if (wide) hipLaunchKernelGGL((bf16k::gemm_bf16<0, 0, 4, 0, true, LOSS_BCE>), grid, dim3(512), 0, s, p);
+                else hipLaunchKernelGGL((bf16k::gemm_bf16<0, 0, 2, 0, true, LOSS_BCE>), grid, dim3(256), 0, s, p);
+            } else if (wide) hipLaunchKernelGGL((bf16k::gemm_bf16<0, 0, 4, 0, false, LOSS_BCE>), grid, dim3(512), 0, s, p);
+            else hipLaunchKernelGGL((bf16k::gemm_bf16<0, 0, 2, 0, false, LOSS_BCE>), grid, dim3(256), 0, s, p);
+        }
         else if (p.mse_rowmap) {
             if (wide) hipLaunchKernelGGL((bf16k::gemm_bf16<0, 0, 4, 0, true>), grid, dim3(512), 0, s, p);
             else hipLaunchKernelGGL((bf16k::gemm_bf16<0, 0, 2, 0, true>), grid, dim3(256), 0, s, p);
@@ -2085,7 +2107,9 @@ hipError_t afr_launch_gemm(int dtype, const GemmParams& p_in, hipStream_t s) {
         const int tiles = ((p.M + x3k::BM - 1) / x3k::BM) * ((p.N + x3k::BN - 1) / x3k::BN);
         dim3 grid(tiles * p.splitk, 1, 1), block(256, 1, 1);
 #define LX(AL, BL) hipLaunchKernelGGL((x3k::gemm_bf16x3<AL, BL>), grid, block, 0, s, p)
-        if (p.mse_rowmap) hipLaunchKernelGGL((x3k::gemm_bf16x3<0, 0, true>), grid, block, 0, s, p);
+        if (bce && p.mse_rowmap) hipLaunchKernelGGL((x3k::gemm_bf16x3<0, 0, true, LOSS_BCE>), grid, block, 0, s, p);
+        else if (bce) hipLaunchKernelGGL((x3k::gemm_bf16x3<0, 0, false, LOSS_BCE>), grid, block, 0, s, p);
+        else if (p.mse_rowmap) hipLaunchKernelGGL((x3k::gemm_bf16x3<0, 0, true>), grid, block, 0, s, p);
         else if (!a && !b) LX(0, 0);
         else if (!a && b) LX(0, 1);
         else if (a && !b) LX(1, 0);
@@ -2095,7 +2119,9 @@ hipError_t afr_launch_gemm(int dtype, const GemmParams& p_in, hipStream_t s) {
         const int tiles = ((p.M + 127) / 128) * ((p.N + 127) / 128);
         dim3 grid(tiles * p.splitk, 1, 1), block(256, 1, 1);
 #define LF(AL, BL) hipLaunchKernelGGL((f32k::gemm_f32<AL, BL>), grid, block, 0, s, p)
-        if (p.mse_rowmap) hipLaunchKernelGGL((f32k::gemm_f32<0, 0, true>), grid, block, 0, s, p);
+        if (bce && p.mse_rowmap) hipLaunchKernelGGL((f32k::gemm_f32<0, 0, true, LOSS_BCE>), grid, block, 0, s, p);
+        else if (bce) hipLaunchKernelGGL((f32k::gemm_f32<0, 0, false, LOSS_BCE>), grid, block, 0, s, p);
+        else if (p.mse_rowmap) hipLaunchKernelGGL((f32k::gemm_f32<0, 0, true>), grid, block, 0, s, p);
         else if (!a && !b) LF(0, 0);
         else if (!a && b) LF(0, 1);
         else if (a && !b) LF(1, 0);

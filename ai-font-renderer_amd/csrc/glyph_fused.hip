@@ -160,8 +160,9 @@ __device__ __forceinline__ void rows_times_global_u(const T* A, int lda, int nti
 
 
 // TROWS: the targets of glyph b are row a.rowmap[b] of a resident data set, read in place (its own instantiation: the dense
-// kernels carry no row-map code)
-template <typename T, bool TU8, bool TROWS>
+// kernels carry no row-map code).  LOSS: the plan's loss kind -- clamp + MSE, or (LOSS_BCE) sigmoid head + BCE on the logits
+// through bce_logits_elem; everything else of the step is the same
+template <typename T, bool TU8, bool TROWS, int LOSS = LOSS_MSE>
 __global__ __launch_bounds__(MM<T>::NTH) void glyph1_step_kernel(Glyph1Args a) {
     using M_ = MM<T>;
     constexpr int KB = M_::KB, R = M_::R, MT = R / 16, NT = M_::NTH, NW = NT / 64;
@@ -285,10 +286,17 @@ __global__ __launch_bounds__(MM<T>::NTH) void glyph1_step_kernel(Glyph1Args a) {
                     float u = acc[m][i] + bias;
                     if constexpr (sizeof(T) == 2) u = (float)(bf16_t)u;          // the value the unfused path stores
                     const float t = TU8 ? lut[__builtin_bit_cast(unsigned, tv[it][m][i])] : tv[it][m][i];
-                    const float diff = fminf(fmaxf(u, 0.f), 1.f) - t;
                     const bool live = row < nb;
-                    lsum += live ? diff * diff : 0.f;
-                    v[i] = (live && u >= 0.f && u <= 1.f) ? g2 * diff : 0.f;
+                    if constexpr (LOSS == LOSS_BCE) {
+                        float d;
+                        const float l = bce_logits_elem(u, t, a.inv_n, d);
+                        lsum += live ? l : 0.f;
+                        v[i] = live ? d : 0.f;
+                    } else {
+                        const float diff = fminf(fmaxf(u, 0.f), 1.f) - t;
+                        lsum += live ? diff * diff : 0.f;
+                        v[i] = (live && u >= 0.f && u <= 1.f) ? g2 * diff : 0.f;
+                    }
                 }
                 put_both(du, ldP, duT, ldR, m * 16, (pt0 + nt) * 16, v);
             }
@@ -452,15 +460,15 @@ hipError_t afr_launch_transpose_bf16(const float* W, bf16_t* WT, int N, int K, h
     return hipGetLastError();
 }
 // one instantiation: its dynamic-LDS limit is raised once per device (devices 0..7 remembered), then the launch
-template <typename T, bool TU8, bool TROWS>
+template <typename T, bool TU8, bool TROWS, int LOSS>
 static hipError_t launch_glyph1(const Glyph1Args& a, int nblk, size_t lds, int dev, hipStream_t s) {
     static size_t done[8];
     if (lds > 48 * 1024 && (dev < 0 || dev >= 8 || done[dev] < lds)) {
-        hipError_t e = hipFuncSetAttribute((const void*)glyph1_step_kernel<T, TU8, TROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void*)glyph1_step_kernel<T, TU8, TROWS, LOSS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
         if (dev >= 0 && dev < 8) done[dev] = lds;
     }
-    hipLaunchKernelGGL((glyph1_step_kernel<T, TU8, TROWS>), dim3(nblk), dim3(MM<T>::NTH), lds, s, a);
+    hipLaunchKernelGGL((glyph1_step_kernel<T, TU8, TROWS, LOSS>), dim3(nblk), dim3(MM<T>::NTH), lds, s, a);
     return hipSuccess;
 }
 hipError_t afr_launch_glyph1_step(int dtype, const Glyph1Args& a, hipStream_t s) {
@@ -474,7 +482,7 @@ hipError_t afr_launch_glyph1_step(int dtype, const Glyph1Args& a, hipStream_t s)
     if (a.cs < 1 || (a.P / 16) % a.cs) return hipErrorInvalidValue;
     const int nblk = (a.B + R - 1) / R * a.cs;
     const bool u8 = a.tdtype == AFR_TARGET_U8, rows = a.rowmap != nullptr;
-#define G1(T, U8, RW) launch_glyph1<T, U8, RW>(a, nblk, lds, dev, s)
+#define G1(T, U8, RW) (a.loss_kind == LOSS_BCE ? launch_glyph1<T, U8, RW, LOSS_BCE>(a, nblk, lds, dev, s) : launch_glyph1<T, U8, RW, LOSS_MSE>(a, nblk, lds, dev, s))
     if (dtype == AFR_BF16) e = u8 ? (rows ? G1(bf16_t, true, true) : G1(bf16_t, true, false)) : (rows ? G1(bf16_t, false, true) : G1(bf16_t, false, false));
     else e = u8 ? (rows ? G1(float, true, true) : G1(float, true, false)) : (rows ? G1(float, false, true) : G1(float, false, false));
 #undef G1

@@ -155,8 +155,8 @@ __global__ __launch_bounds__(256) void pixel_attn_kernel(const T* __restrict__ q
         }
     }
 }
-// h += add;  u = LayerNorm_f(h) . w_out + b_out;  y = clamp(u, 0, 1)      (model.py:152-156 idiom)
-template <typename T>
+// h += add;  u = LayerNorm_f(h) . w_out + b_out;  y = clamp(u, 0, 1)      (model.py:152-156 idiom); LOSS_BCE: y = sigmoid(u)
+template <typename T, int LOSS = LOSS_MSE>
 __global__ __launch_bounds__(256) void pixel_head_kernel(const float* __restrict__ hin, float* __restrict__ h, const T* __restrict__ add, const float* __restrict__ g,
                                                          const float* __restrict__ b, const float* __restrict__ w_out, const float* __restrict__ b_out,
                                                          float* __restrict__ u, float* __restrict__ y, long long rows, int d, float eps) {
@@ -189,7 +189,8 @@ __global__ __launch_bounds__(256) void pixel_head_kernel(const float* __restrict
         a = wave_sum(a) + bo;
         if (lane == 0) {
             if (u) u[r] = a;
-            if (y) y[r] = fminf(fmaxf(a, 0.f), 1.f);
+            if constexpr (LOSS == LOSS_BCE) { if (y) y[r] = sigmoid_f(a); }
+            else if (y) y[r] = fminf(fmaxf(a, 0.f), 1.f);
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) { v[j] = vn[j]; av[j] = avn[j]; }
@@ -224,9 +225,12 @@ hipError_t afr_launch_pixel_attn(int act_dtype, const void* q, const void* kv, v
     return hipGetLastError();
 }
 hipError_t afr_launch_pixel_head(int act_dtype, const float* hin, float* h, const void* add, const float* g, const float* b, const float* w_out, const float* b_out,
-                                 float* u, float* y, long long rows, int d, float eps, hipStream_t s) {
+                                 float* u, float* y, long long rows, int d, float eps, hipStream_t s, int loss_kind) {
     if (d > 512 || (d & 7)) return hipErrorInvalidValue;
-    if (act_dtype == AFR_BF16) hipLaunchKernelGGL(pixel_head_kernel<bf16_t>, dim3(pix_grid(rows)), dim3(256), 0, s, hin, h, (const bf16_t*)add, g, b, w_out, b_out, u, y, rows, d, eps);
+    if (loss_kind == LOSS_BCE) {
+        if (act_dtype == AFR_BF16) hipLaunchKernelGGL((pixel_head_kernel<bf16_t, LOSS_BCE>), dim3(pix_grid(rows)), dim3(256), 0, s, hin, h, (const bf16_t*)add, g, b, w_out, b_out, u, y, rows, d, eps);
+        else hipLaunchKernelGGL((pixel_head_kernel<float, LOSS_BCE>), dim3(pix_grid(rows)), dim3(256), 0, s, hin, h, (const float*)add, g, b, w_out, b_out, u, y, rows, d, eps);
+    } else if (act_dtype == AFR_BF16) hipLaunchKernelGGL(pixel_head_kernel<bf16_t>, dim3(pix_grid(rows)), dim3(256), 0, s, hin, h, (const bf16_t*)add, g, b, w_out, b_out, u, y, rows, d, eps);
     else hipLaunchKernelGGL(pixel_head_kernel<float>, dim3(pix_grid(rows)), dim3(256), 0, s, hin, h, (const float*)add, g, b, w_out, b_out, u, y, rows, d, eps);
     return hipGetLastError();
 }

@@ -26,8 +26,10 @@ def _stream(device=None):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
-def make_afr_config(cfg, dtype, max_batch, seed=42, rank=0, flags=0):
+def make_afr_config(cfg, dtype, max_batch, seed=42, rank=0, flags=0, loss="mse"):
+    """loss: "mse" (clamp head + MSE, the reference's) or "bce" (sigmoid head + binary cross-entropy on the logits)."""
     c = _lib.AfrConfig()
+    c.loss = _lib.loss_kind(loss)
     c.reserved = int(flags)          # include/afr.h: bit 0 un-fused optimizer, bit 1 no grouped GEMM launches, bit 2 no fused small-net step
     c.dtype = _DT[dtype]
     c.max_batch = int(max_batch)
@@ -61,12 +63,15 @@ class Engine:
     """One plan + its device buffers.  `params[name]` are views into the flat float32 buffer in
     state_dict order, so checkpoints interchange with the reference (helpers.py:76-105)."""
 
-    def __init__(self, cfg, dtype="f32", max_batch=1024, device=None, seed=42, rank=0, with_optimizer=True, flags=0, micro_batch=None):
+    def __init__(self, cfg, dtype="f32", max_batch=1024, device=None, seed=42, rank=0, with_optimizer=True, flags=0, micro_batch=None,
+                 loss="mse"):
         """micro_batch: train_step / forward_loss + backward of a batch larger than this many samples run as micro-steps of at
         most that many, their gradients summed (gradient accumulation: the saved activations of BASELINE configs[4]'s 2048
         glyphs per GPU would be 800 GB; 32 at a time they are 12.6 GB).  The plan is then sized for micro_batch, not max_batch."""
         if not torch.cuda.is_available():
             raise RuntimeError("ai_font_renderer_amd.Engine needs an MI355X: the hot path has no CPU fallback")
+        _lib.loss_kind(loss)          # ValueError for anything but "mse" | "bce"
+        self.loss = loss
         self.lib = _lib.lib()
         self.micro_batch = int(micro_batch) if micro_batch else None
         if self.micro_batch:
@@ -110,7 +115,7 @@ class Engine:
         if self._plan:
             self.lib.afr_plan_destroy(self._plan)
         self.max_batch = int(max_batch)
-        self._c = make_afr_config(self.cfg, self.dtype, self.max_batch, self.seed, self.rank, self.flags)
+        self._c = make_afr_config(self.cfg, self.dtype, self.max_batch, self.seed, self.rank, self.flags, self.loss)
         self._plan = C.c_void_p()
         _lib.check(self.lib.afr_plan_create(C.byref(self._c), C.byref(self._plan)))
 
@@ -286,7 +291,8 @@ class Engine:
         self._keep_t = t
 
     def set_output_grad(self, dy):
-        """dy = d(loss)/d(clamped output) from a caller-side loss (autograd); float32 [B, pixels]."""
+        """dy = d(loss)/d(output) from a caller-side loss (autograd); float32 [B, pixels].  The output is the clamped one, or the
+        sigmoid of a loss="bce" engine."""
         dy = dy.to(self.device, dtype=torch.float32).contiguous()
         self._call(self.lib.afr_set_output_grad, self._plan, _ptr(dy), dy.shape[0])
         self._keep_t = dy
@@ -391,11 +397,14 @@ class Engine:
         return out.value
 
     def debug_read(self, which, index=0):
-        """Copy an internal activation buffer of the last call (u/du, z, dz, glyph activation i) as float32."""
+        """Copy an internal activation buffer of the last call (u/du, z, dz, glyph activation i, pixel block i's ReLU output)
+        as float32."""
         code = {"u": _lib.BUF_U, "z": _lib.BUF_Z, "dz": _lib.BUF_DZ, "act": _lib.BUF_ACT + int(index), "w1t": _lib.BUF_W1T, "w2t": _lib.BUF_W2T}[which]
         dt = torch.bfloat16 if (self.dtype in ("bf16", "bfloat16") or which in ("w1t", "w2t")) else torch.float32
         es = 2 if dt == torch.bfloat16 else 4
-        cap = max(self.max_batch * max(self.pixels, getattr(self.cfg, "flat_dim", 0), *(getattr(self.cfg, "hidden", (0,))), self.cfg.embed_dim) * es, 1 << 20)
+        widest = max(self.pixels, getattr(self.cfg, "flat_dim", 0), *(getattr(self.cfg, "hidden", (0,))), getattr(self.cfg, "embed_dim", 0),
+                     getattr(self.cfg, "tokens", 0) * getattr(self.cfg, "ff_dim", 0))     # (pixel model: a block's ReLU output)
+        cap = max(self.max_batch * widest * es, 1 << 20)
         buf = torch.empty(cap, dtype=torch.uint8, device=self.device)
         n = C.c_size_t()
         self._call(self.lib.afr_debug_copy, self._plan, code, _ptr(buf), cap, C.byref(n))

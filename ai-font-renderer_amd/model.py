@@ -15,7 +15,10 @@ What is deliberately different from the reference, and why:
   * loss.item() per step (model.py:311) becomes one device->host read per epoch (the loss accumulates on device);
   * dropout uses a counter-hash stream instead of torch's bernoulli_ stream (same rates, same placement);
   * AFR_DTYPE=bf16 selects the throughput mode (bf16 MFMA operands); the default f32 mode is the parity mode, and
-    AFR_DTYPE=bf16x3 the fast parity mode (f32 except that every Linear product runs as three split-bf16 MFMAs).
+    AFR_DTYPE=bf16x3 the fast parity mode (f32 except that every Linear product runs as three split-bf16 MFMAs);
+  * AFR_LOSS=bce selects a sigmoid output head trained with binary cross-entropy on the logits (the loss the reference's
+    clamp head replaced, model.py:155) through the same fused step; the default, mse, is the reference's clamp + MSE.  A
+    checkpoint does not record the head: the caller says which one it wants, as with the dtype.
 """
 import datetime
 import os
@@ -50,6 +53,7 @@ MIN_LEARNING_RATE = 1e-6
 SEED = 42
 ADAM_BETAS = (0.9, 0.99)                      # model.py:273
 COMPUTE_DTYPE = os.environ.get("AFR_DTYPE", "f32")
+COMPUTE_LOSS = os.environ.get("AFR_LOSS", "mse")     # "mse" | "bce"
 
 random.seed(SEED)
 np.random.seed(SEED)
@@ -151,9 +155,11 @@ class _EngineForward(torch.autograd.Function):
 class AttentionFontRenderer(nn.Module):
     """Reference model.py:129-204.  forward(x: int64 [B,L]) -> float32 [B, SHEET_HEIGHT, SHEET_WIDTH] in [0,1];
     L > max_length is truncated, L < max_length zero-pads the flattened features; an index >= 128 raises
-    IndexError (checked when `strict_indices`, default, at the cost of a device sync in eval mode only)."""
+    IndexError (checked when `strict_indices`, default, at the cost of a device sync in eval mode only).
+    loss: "mse" (clamp head, the reference's) or "bce" (sigmoid head: forward returns sigmoid(u), the fused steps train with
+    binary cross-entropy on u); None takes AFR_LOSS from the environment.  state_dict() is the same for both."""
 
-    def __init__(self, max_length=MAX_CHARS_PER_SHEET, dtype=None, max_batch=1024, seed=SEED, rank=None, init=True):
+    def __init__(self, max_length=MAX_CHARS_PER_SHEET, dtype=None, max_batch=1024, seed=SEED, rank=None, init=True, loss=None):
         super().__init__()
         from .engine import Engine
         self.max_length = max_length
@@ -162,7 +168,9 @@ class AttentionFontRenderer(nn.Module):
                                   sheet_h=SHEET_HEIGHT, sheet_w=SHEET_WIDTH, p_embed=DROPOUT_RATE, p_attn=DROPOUT_RATE,
                                   p_fc=DROPOUT_RATE + 0.05)
         rank = int(os.environ.get("RANK", "0")) if rank is None else rank
-        self.engine = Engine(self.config, dtype=dtype or COMPUTE_DTYPE, max_batch=max_batch, device=device, seed=seed, rank=rank)
+        self.engine = Engine(self.config, dtype=dtype or COMPUTE_DTYPE, max_batch=max_batch, device=device, seed=seed, rank=rank,
+                             loss=loss or COMPUTE_LOSS)
+        self.loss = self.engine.loss
         P = {k: nn.Parameter(v) for k, v in self.engine.params.items()}
         self.positional_encoding = P["positional_encoding"]
         self.embedding = _Bag(weight=P["embedding.weight"])
@@ -317,6 +325,8 @@ def train_attention_model(model, dataset, batch_size):
                          ("max_chars_per_sheet", MAX_CHARS_PER_SHEET), ("num_samples", NUM_SAMPLES), ("data_size", len(dataset)),
                          ("random_seed", SEED), ("sheet_height", SHEET_HEIGHT), ("sheet_width", SHEET_WIDTH)):
                 f.write(f"{k} = {v}\n")
+            if eng.loss != "mse":               # only a non-default loss is recorded: a default run's artefacts stay as they were
+                f.write(f"loss = {eng.loss}\n")
 
     order = _EpochOrder(len(dataset))
     print(f"Dataset split: {order.train_size} training samples, {order.val_size} validation samples")

@@ -42,6 +42,11 @@ enum { AFR_F32 = 0,          /* exact-f32 MFMA everywhere: parity mode (<=1e-4 v
 enum { AFR_TARGET_U8 = 0,    /* 8-bit pixels as stored in the BMPs; k/255.0f on device           */
        AFR_TARGET_F32 = 1 }; /* float32 targets as helpers.load_string_dataset returns them      */
 
+enum { AFR_LOSS_MSE = 0,     /* clamp(u,0,1) head + F.mse_loss (model.py:156,268-270): the default            */
+       AFR_LOSS_BCE = 1 };   /* sigmoid head + F.binary_cross_entropy_with_logits on u, soft targets k/255:
+                                  y = sigmoid(u);  loss = sum(max(u,0) - t u + log1p(exp(-|u|))) / mean_elems;
+                                  du = (sigmoid(u) - t) / mean_elems                                          */
+
 #define AFR_MAX_HIDDEN 8
 
 typedef struct afr_config {
@@ -80,6 +85,9 @@ typedef struct afr_config {
                             instead of the (character, font) combination table gathered inside the consuming products
                             bit 7: ReLU masks of the input-gradient products read from the stored activations instead of the
                             bit masks the forward epilogues leave (bits 6, 7: A/B measurements; bitwise equal results)      */
+    int32_t loss;        /* AFR_LOSS_*: the output head and loss of every entry point below (0 = clamp + MSE); any other
+                            value is AFR_EINVAL.  Appended after `reserved` (the struct grew by 8 bytes with it): a zero-initialised
+                            config means what it meant, a caller compiled against the older header must be rebuilt          */
 } afr_config;
 /* the bits of afr_config.reserved, as described above */
 enum { AFR_CFG_UNFUSED_OPTIMIZER = 1, AFR_CFG_NO_GROUPED_GEMM = 2, AFR_CFG_NO_FUSED_GLYPH1 = 4, AFR_CFG_L1_BWD_UNFUSED = 16,
@@ -116,7 +124,7 @@ int afr_sync_params(afr_plan* plan, void* stream);
 
 /* forward(x): model.py:158-204.  x int64 [B, L] (sheet; L>max_length truncated, L<max_length
  * zero-padded features) or int64 [B] glyph codes with optional font ids.  y: float32 [B, out_h*out_w]
- * clamped to [0,1], or NULL when only the saved pre-activation is wanted (training).
+ * clamped to [0,1] (AFR_LOSS_BCE plan: sigmoid(u)), or NULL when only the saved pre-activation is wanted (training).
  * training!=0 enables the three dropouts with the counter-hash stream (seed, rank, step). */
 int afr_forward(afr_plan* plan, const int64_t* x, const int64_t* font, int B, int L, float* y,
                 int training, uint64_t step, void* stream);
@@ -124,12 +132,15 @@ int afr_forward(afr_plan* plan, const int64_t* x, const int64_t* font, int B, in
 /* compute_loss + the first backward step: F.mse_loss(clamp(u,0,1), target) (model.py:268-270) and
  * d(loss)/du with the inclusive clamp mask.  Uses the pre-activation the last afr_forward left in
  * the workspace.  mean_elems = B_global*out_h*out_w (the mean's denominator; lets data-parallel
- * shards weight a short last batch exactly).  *loss_accum (device float) += this shard's share. */
+ * shards weight a short last batch exactly).  *loss_accum (device float) += this shard's share.
+ * AFR_LOSS_BCE plan: binary cross-entropy with logits on u and du = (sigmoid(u) - t) / mean_elems instead; this call, afr_forward_loss,
+ * afr_train_step and the afr_*_rows calls all follow the plan's loss kind. */
 int afr_loss_grad(afr_plan* plan, const void* target, int target_dtype, int B, int64_t mean_elems,
                   float* loss_accum, void* stream);
 
 /* Entry for a caller-owned loss (torch.autograd): dy = d(loss)/d(y) for the clamped output y [B, pixels], float32.
- * Applies the clamp's gradient mask (0 <= u <= 1, inclusive) and leaves du where afr_backward expects it. */
+ * Applies the clamp's gradient mask (0 <= u <= 1, inclusive) and leaves du where afr_backward expects it.
+ * AFR_LOSS_BCE plan: y is the sigmoid output, du = dy * y * (1 - y) with y recomputed from the saved u. */
 int afr_set_output_grad(afr_plan* plan, const float* dy, int B, void* stream);
 
 /* loss.backward(): model.py:309.  Overwrites the flat gradient buffer (zero_grad, model.py:292,
@@ -143,7 +154,8 @@ int afr_backward_stages(const afr_plan* plan);
 int afr_backward_stage(afr_plan* plan, int stage, int64_t* grad_offset, int64_t* grad_elems, void* stream);
 
 /* Training forward with the loss and d(loss)/du computed in the epilogue of the last layer (u never reaches HBM):
- * afr_forward(training) + afr_loss_grad in one pass; follow with afr_backward / afr_backward_stage. */
+ * afr_forward(training) + afr_loss_grad in one pass; follow with afr_backward / afr_backward_stage.  The loss is the plan's
+ * (afr_config.loss); fused and unfused paths leave the same du bit for bit. */
 int afr_forward_loss(afr_plan* plan, const int64_t* x, const int64_t* font, const void* target, int target_dtype,
                      int B, int L, int64_t mean_elems, float* loss_accum, uint64_t step, void* stream);
 
@@ -154,7 +166,8 @@ int afr_adamw_step(afr_plan* plan, float lr, float beta1, float beta2, float eps
 
 /* One whole iteration of the loop body model.py:292-310 on this rank's shard:
  * forward(training) -> loss+grad -> backward [-> AdamW when do_step!=0].  With do_step!=0 the loss is fused into
- * the last forward GEMM and, for the sheet model, the AdamW update of fc_output.weight into its dW GEMM. */
+ * the last forward GEMM and, for the sheet model, the AdamW update of fc_output.weight into its dW GEMM.
+ * The loss is the plan's (afr_config.loss). */
 int afr_train_step(afr_plan* plan, const int64_t* x, const int64_t* font, const void* target,
                    int target_dtype, int B, int L, int64_t mean_elems, float* loss_accum,
                    uint64_t step, int do_step, float lr, float beta1, float beta2, float eps,
@@ -168,7 +181,7 @@ int afr_train_step(afr_plan* plan, const int64_t* x, const int64_t* font, const 
  * The four afr_*_rows calls are the entry points of the same name with a row vector in place of the dense batch: `rows`
  * is a device vector of B int64 indices into the data set, duplicates allowed; batch row b means data-set row rows[b].
  * Dropout is keyed by the in-batch row b, mean_elems / loss_accum / step / the optimizer arguments mean what they mean
- * there, and afr_backward / afr_backward_stage / afr_adamw_step follow as usual.  The targets are read where they lie
+ * there, the loss kind is the plan's, and afr_backward / afr_backward_stage / afr_adamw_step follow as usual.  The targets are read where they lie
  * (the loss kernels take the row as an index); codes and font ids of the batch are staged in the workspace by one small
  * kernel, after which (in stream order) `rows` is not read again.  An index outside [0, n_rows) sets bit 2 of the error
  * word and is clamped before anything is addressed with it.  Errors, in this order: no data set bound -> AFR_ESTATE;
@@ -207,7 +220,8 @@ enum { AFR_BUF_U = 0,      /* pre-clamp output u [B, pixels]; after afr_loss_gra
        AFR_BUF_DZ = 2,     /* sheet: gradient w.r.t. z                                                            */
        AFR_BUF_W1T = 4,    /* small glyph nets, bf16: the transposed operand copy W1^T [E][N1] the fused step reads */
        AFR_BUF_W2T = 5,    /*                         and W2^T [N1][pixels] (always bf16)                          */
-       AFR_BUF_ACT = 16 }; /* glyph: AFR_BUF_ACT + i = activation i (0 = embedding sum, i = output of hidden i)   */
+       AFR_BUF_ACT = 16 }; /* glyph: AFR_BUF_ACT + i = activation i (0 = embedding sum, i = output of hidden i);
+                              pixel: AFR_BUF_ACT + i = block i's MLP ReLU output [B * tokens, fc_dim] (its ReLU gates) */
 int afr_debug_copy(afr_plan* plan, int which, void* dst, size_t dst_bytes, size_t* bytes_out, void* stream);
 /* Inspection of the sheet model's in-kernel embedding gather (model.py:136,167): runs the front end of an eval forward on
  * x [B, L] and leaves the rows it gathered, Emb[x[b][l]] for l < min(L, max_length), in e0 (device, float32
@@ -264,6 +278,11 @@ int afr_op_adamw(float* p, const float* g, float* m, float* v, void* shadow_bf16
                  void* stream);
 /* scratch: >= 1040 floats, zero before the first call (holds per-block partials and the arrival counter) */
 int afr_op_mse_grad(int act_dtype, const void* u, const void* target, int target_dtype, void* du,
+                    int64_t rows, int64_t cols, int64_t mean_elems, float* loss_accum, float* scratch,
+                    void* stream);
+/* The AFR_LOSS_BCE form of the same launch: loss += sum(max(u,0) - t u + log1p(exp(-|u|))) / mean_elems over the logits u,
+ * du = (sigmoid(u) - t) / mean_elems (F.binary_cross_entropy_with_logits and its gradient).  Same scratch, same fixed summation order. */
+int afr_op_bce_grad(int act_dtype, const void* u, const void* target, int target_dtype, void* du,
                     int64_t rows, int64_t cols, int64_t mean_elems, float* loss_accum, float* scratch,
                     void* stream);
 int afr_op_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);
