@@ -56,6 +56,10 @@ struct Tensor {
 };
 
 struct ProfRec { int tag; hipEvent_t a, b; double flops, bytes; };
+// The loss scratch of a plan (o_loss) or of an afr_op_*_grad caller, in floats: the loss kernel's own launch keeps its <= 1024
+// partials at the front and its arrival counter behind them; a loss fused into another kernel (GEMM epilogue, small-net step)
+// has a counter of its own and its partials, one per block of that launch, behind it.
+constexpr int LOSS_WS_COUNTER = 1024, LOSS_WS_FUSED_COUNTER = 1032, LOSS_WS_FUSED_PARTIAL = 1040;
 struct AdamArgs { float lr, b1, b2, eps, wd; int64_t t; };      // the optimizer arguments of afr_train_step
 
 struct afr_plan {
@@ -227,7 +231,7 @@ extern "C" int afr_plan_create(const afr_config* c, afr_plan** out) {
         const size_t Kz = (size_t)L * F;
         if (c->dtype == AFR_BF16) p->o_shadow = carve((size_t)p->total * 2);
         p->o_err = carve(256);
-        p->o_loss = carve(((size_t)((B + 127) / 128) * ((Pix + 127) / 128) + 1040) * sizeof(float));
+        p->o_loss = carve(((size_t)((B + 127) / 128) * ((Pix + 127) / 128) + LOSS_WS_FUSED_PARTIAL) * sizeof(float));
         p->o_z = carve(B * Kz * ab);
         p->o_u = carve(B * Pix * ab);
         p->o_dz = carve(B * Kz * ab);
@@ -265,7 +269,7 @@ extern "C" int afr_plan_create(const afr_config* c, afr_plan** out) {
         p->font_off = c->n_fonts > 0 ? off_of(p, "font_embedding.weight") : -1;
         if (c->dtype == AFR_BF16) { p->o_shadow = carve((size_t)p->total * 2); p->o_shadow2 = carve((size_t)p->total * 2); }
         p->o_err = carve(256);
-        p->o_loss = carve(((size_t)((B + 127) / 128) * ((Pix + 127) / 128) + 1040) * sizeof(float));
+        p->o_loss = carve(((size_t)((B + 127) / 128) * ((Pix + 127) / 128) + LOSS_WS_FUSED_PARTIAL) * sizeof(float));
         size_t maxw = (size_t)E, maxn = 0;
         p->k0 = c->n_hidden > 0 ? afr_glyph_k0(E, c->vocab, c->n_fonts) : 0;
         if (p->k0 > 512 || E > 128) p->k0 = 0;     // beyond what the folded-layer kernels stage per block: plain embedding + GEMM path
@@ -320,7 +324,7 @@ extern "C" int afr_plan_create(const afr_config* c, afr_plan** out) {
             p->fused1 = true;
             const size_t nblk = (size_t)afr_glyph1_max_blocks(c->dtype, (int)B, Pix);      // row blocks x column split
             p->o_slab1 = carve(nblk * (size_t)p->total * sizeof(float));
-            p->o_loss = carve((1040 + nblk + 64) * sizeof(float));           // room for one loss partial per block
+            p->o_loss = carve((LOSS_WS_FUSED_PARTIAL + nblk + 64) * sizeof(float));           // room for one loss partial per block
             if (c->dtype == AFR_BF16) {
                 if (!p->l1f) p->o_w1t = carve((size_t)c->hidden[0] * E * 2);
                 p->o_w2t = carve((size_t)Pix * c->hidden[0] * 2);
@@ -356,7 +360,7 @@ extern "C" int afr_plan_create(const afr_config* c, afr_plan** out) {
             { delete p; return fail(AFR_EUNSUPPORTED, "max_batch %d x %d tokens: an activation operand would reach 2 GiB in bf16", c->max_batch, T); }
         if (c->dtype == AFR_BF16) p->o_shadow = carve((size_t)p->total * 2);
         p->o_err = carve(256);
-        p->o_loss = carve((1040 + 1040) * sizeof(float));
+        p->o_loss = carve((LOSS_WS_FUSED_PARTIAL + 1040) * sizeof(float));
         p->o_ctx = carve(B * C * d * ab);
         const size_t nbp = (size_t)afr_pixel_bwd_blocks((long long)rows);
         for (int l = 0; l < c->n_hidden; ++l) {
@@ -586,15 +590,25 @@ extern "C" int afr_profile_dump(afr_plan* p, char* buf, int cap) {
 }
 
 // ------------------------------------------------------------------------------------ helpers
-struct FusedLoss { const void* target; int tdtype; int64_t mean_elems; float* loss_accum;
-                   const int* rowmap = nullptr;          // targets of batch row b = row rowmap[b] of `target` (afr_*_rows); NULL = row b
-                   int kind = AFR_LOSS_MSE; };           // AFR_LOSS_*: the plan's loss kind
-// the six AdamW scalars of a fused update (GemmParams::ad_* / RTable::ad_*), as afr_launch_adamw derives them from its arguments
-template <class T> static void set_adam(T& o, const AdamArgs& h) {
+static LossArgs loss_slots(LossArgs l, float* scratch, bool fused) {
+    l.partial = scratch + (fused ? LOSS_WS_FUSED_PARTIAL : 0);
+    l.counter = reinterpret_cast<unsigned*>(scratch + (fused ? LOSS_WS_FUSED_COUNTER : LOSS_WS_COUNTER));
+    return l;
+}
+// what every loss site is handed (rowmap: targets of batch row b = row rowmap[b] of `target`, afr_*_rows; NULL = row b)
+static LossArgs loss_args(float* scratch, bool fused, int kind, const void* target, int tdtype, const int* rowmap, int64_t mean_elems, float* loss_accum) {
+    LossArgs l;
+    l.target = target; l.rowmap = rowmap; l.tdtype = tdtype; l.inv_n = (float)(1.0 / (double)mean_elems); l.loss_accum = loss_accum; l.kind = kind;
+    return loss_slots(l, scratch, fused);
+}
+static LossArgs loss_args(const afr_plan* p, bool fused, const void* target, int tdtype, const int* rowmap, int64_t mean_elems, float* loss_accum) {
+    return loss_args((float*)(p->ws + p->o_loss), fused, p->cfg.loss, target, tdtype, rowmap, mean_elems, loss_accum);
+}
+// the scalars of an AdamW step (torch.optim.AdamW, bias corrections in double as torch takes them)
+static AdamHyper adam_hyper(const AdamArgs& h) {
     const float bc1 = (float)(1.0 - std::pow((double)h.b1, (double)h.t));
     const float bc2 = (float)(1.0 - std::pow((double)h.b2, (double)h.t));
-    o.ad_decay = 1.f - h.lr * h.wd; o.ad_b1 = h.b1; o.ad_b2 = h.b2; o.ad_eps = h.eps; o.ad_step = h.lr / bc1;
-    o.ad_rsqrt_bc2 = (float)(1.0 / std::sqrt((double)bc2));
+    return AdamHyper{1.f - h.lr * h.wd, h.b1, h.b2, h.eps, h.lr / bc1, (float)(1.0 / std::sqrt((double)bc2))};
 }
 // the bf16 weight shadow the GEMMs read / the one a fused optimizer step writes (the same buffer unless the plan has two)
 static inline bf16_t* shadow_rd(const afr_plan* p) {
@@ -640,13 +654,6 @@ static GemmParams lin_dw(const void* dy, const void* x, float* dW, float* db, in
     GemmParams g = lin_desc(AFR_GEMM_A_KSTRIDED | AFR_GEMM_B_KSTRIDED, dy, x, dW, N, K, B, N, K, K);
     g.splitk = sk; g.slab_stride = slab_stride; g.colsum = db; g.colsum_stride = sk > 1 ? N : 0;
     return g;
-}
-// the loss fused into the epilogue of the last forward product
-static void fuse_loss(const afr_plan* p, GemmParams& g, const FusedLoss& fl) {
-    float* scratch = (float*)(p->ws + p->o_loss);
-    g.mse_target = fl.target; g.mse_rowmap = fl.rowmap; g.mse_target_dtype = fl.tdtype; g.mse_inv_n = (float)(1.0 / (double)fl.mean_elems);
-    g.mse_partial = scratch + 1040; g.mse_counter = reinterpret_cast<unsigned*>(scratch + 1032); g.mse_loss_accum = fl.loss_accum;
-    g.loss_kind = fl.kind;
 }
 // the bf16 LDS-DMA path addresses an operand with 32-bit byte offsets: 2 GiB per operand
 static int check_operand_bytes(const GemmParams& g) {
@@ -734,7 +741,7 @@ static int run_dw(afr_plan* p, hipStream_t s, afr_plan::Layer& l, const void* dy
         if (a_rows) { g.b_rowmap = a_rows; g.ldb = a_ld; }      // the layer's input rows are gathered from a table whose rows are a_ld apart
         if (p->step_on) {
             g.ad_p = p->P + l.w_off; g.ad_m = p->M + l.w_off; g.ad_v = p->V + l.w_off; g.ad_shadow = shadow_wr(p) ? shadow_wr(p) + l.w_off : nullptr;
-            set_adam(g, p->st);
+            g.ad = adam_hyper(p->st);
         }
         int rc = run_gemm(p, s, g);
         if (rc) return rc;
@@ -841,7 +848,7 @@ static bool combo_for(const afr_plan* p, int B) {
 
 // ------------------------------------------------------------------------------------- forward
 static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int B, int L, float* y, int training,
-                        uint64_t step, void* stream, const FusedLoss* fl) {
+                        uint64_t step, void* stream, const LossArgs* fl /* the plan's, fused slots */) {
     if (!p || !p->P) return fail(AFR_ESTATE, "plan has no bound parameters");
     DevGuard dg(p->device);
     if (!x) return fail(AFR_EINVAL, "x is null");
@@ -861,7 +868,7 @@ static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int 
             HIPCHK(afr_launch_sheet_fwd(c.dtype, d, sheet_params(p), make_drop(p, training, step), x, L, B, z, c.ln_eps, err, s));
         }
         GemmParams g = lin_fwd(p, p->layers[0], z, u, B);        // fc_output
-        if (fl) fuse_loss(p, g, *fl);
+        if (fl) g.loss = *fl;
         int rc = run_gemm(p, s, g);
         if (rc) return rc;
         p->last_L = Lc;
@@ -918,8 +925,7 @@ static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int 
         p->have_du = false;
         if (fl) {        // the loss on the f32 pre-clamp output (model.py:156,268-270): du in place over u
             ProfScope ps(p, s, fl->kind == AFR_LOSS_BCE ? "bce_grad" : "mse_grad", 0.0, (double)rows * 9.0);
-            HIPCHK(afr_launch_mse_grad(AFR_F32, u, fl->target, fl->tdtype, u, B, Pix, fl->mean_elems, fl->loss_accum, (float*)(p->ws + p->o_loss), s, fl->rowmap,
-                                       fl->kind));
+            HIPCHK(afr_launch_mse_grad(AFR_F32, u, u, B, Pix, loss_slots(*fl, (float*)(p->ws + p->o_loss), false), s));
             p->have_du = true;
         }
         return AFR_OK;
@@ -961,7 +967,7 @@ static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int 
             // after the combination table the second layer gathers its input rows from it (rows h1c_ld apart)
             if (combo && i == 1) { g.a_rowmap = (const int*)(p->ws + p->o_cidx); g.lda = p->h1c_ld; }
             if (bits && !last && p->o_mbits[i]) { g.mask_out = (unsigned char*)(p->ws + p->o_mbits[i]); g.ldmask = l.N / 8; }
-            if (last && fl) fuse_loss(p, g, *fl);
+            if (last && fl) g.loss = *fl;
             int rc = run_gemm(p, s, g);
             if (rc) return rc;
             h = outp;
@@ -1002,8 +1008,8 @@ static int loss_grad_impl(afr_plan* p, const void* target, int tdtype, const int
     void* u = p->ws + p->o_u;
     const double tb = tdtype == AFR_TARGET_U8 ? 1.0 : 4.0;
     ProfScope ps(p, s, p->cfg.loss == AFR_LOSS_BCE ? "bce_grad" : "mse_grad", 0.0, (double)B * Pix * (2.0 * p->act_bytes + tb));
-    HIPCHK(afr_launch_mse_grad(p->cfg.kind == AFR_KIND_PIXEL ? AFR_F32 : p->cfg.dtype, u, target, tdtype, u, B, Pix, mean_elems, loss_accum,
-                               (float*)(p->ws + p->o_loss), s, rowmap, p->cfg.loss));      // (the pixel transformer's pre-clamp output is f32 in both modes)
+    HIPCHK(afr_launch_mse_grad(p->cfg.kind == AFR_KIND_PIXEL ? AFR_F32 : p->cfg.dtype, u, u, B, Pix,      // (the pixel transformer's pre-clamp output is f32 in both modes)
+                               loss_args(p, false, target, tdtype, rowmap, mean_elems, loss_accum), s));
     p->have_du = true;
     return AFR_OK;
 }
@@ -1296,11 +1302,9 @@ extern "C" int afr_adamw_step(afr_plan* p, float lr, float b1, float b2, float e
     DevGuard dg(p->device);
     if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
     hipStream_t s = (hipStream_t)stream;
-    const float bc1 = (float)(1.0 - std::pow((double)b1, (double)t));
-    const float bc2 = (float)(1.0 - std::pow((double)b2, (double)t));
     bf16_t* shadow = shadow_rd(p);        // nothing reads the weights concurrently: updated in place
     ProfScope ps(p, s, "adamw", 0.0, (double)p->total * (shadow ? 30.0 : 28.0));
-    HIPCHK(afr_launch_adamw(p->P, p->G, p->M, p->V, shadow, p->total, lr, b1, b2, eps, wd, bc1, bc2, gscale, s));
+    HIPCHK(afr_launch_adamw(p->P, p->G, p->M, p->V, shadow, p->total, lr, wd, adam_hyper(AdamArgs{lr, b1, b2, eps, wd, t}), gscale, s));
     p->wT_valid = false;
     return AFR_OK;
 }
@@ -1309,10 +1313,8 @@ extern "C" int afr_adamw_step(afr_plan* p, float lr, float b1, float b2, float e
 // slabs (split-K dW, bias partials, embedding partials, the sheet model's small tensors) is updated in the kernel that
 // sums its slabs -- the summed gradient is never stored; tensors whose gradient a GEMM wrote directly get the plain kernel.
 static int reduce_and_step(afr_plan* p, hipStream_t s, RTable& rt, const AdamArgs& h, int64_t skip_off = -1) {
-    const float bc1 = (float)(1.0 - std::pow((double)h.b1, (double)h.t));
-    const float bc2 = (float)(1.0 - std::pow((double)h.b2, (double)h.t));
     bf16_t* shadow = shadow_wr(p);        // every tensor's new bf16 copy goes to the write shadow; the roles swap below
-    rt.adam = 1; set_adam(rt, h);
+    rt.adam = 1; rt.ad = adam_hyper(h);
     rt.gbase = p->G; rt.P = p->P; rt.M = p->M; rt.V = p->V; rt.shadow = shadow;
     p->wT_valid = false;
     int rc = run_reduce_group(p, s, rt);
@@ -1332,8 +1334,8 @@ static int reduce_and_step(afr_plan* p, hipStream_t s, RTable& rt, const AdamArg
         if (cov >= tn.numel) continue;
         const int64_t n = (tn.numel + 63) / 64 * 64;
         ProfScope ps(p, s, "adamw", 0.0, (double)n * 28.0);
-        HIPCHK(afr_launch_adamw(p->P + tn.off, p->G + tn.off, p->M + tn.off, p->V + tn.off, shadow ? shadow + tn.off : nullptr, n, h.lr, h.b1,
-                                h.b2, h.eps, h.wd, bc1, bc2, 1.f, s));
+        HIPCHK(afr_launch_adamw(p->P + tn.off, p->G + tn.off, p->M + tn.off, p->V + tn.off, shadow ? shadow + tn.off : nullptr, n, h.lr, h.wd,
+                                rt.ad, 1.f, s));
     }
     if (p->o_shadow2) p->shadow_cur ^= 1;   // every tensor has been rewritten: the write shadow is the current one now
     p->adam_done.clear();
@@ -1356,7 +1358,7 @@ static int sheet_fused_step(afr_plan* p, hipStream_t s, const AdamArgs& h) {
     if ((rc = run_gemm(p, s, lin_dx(p, l, du, p->ws + p->o_dz, nullptr, B)))) return rc;
     GemmParams g = lin_dw(du, p->ws + p->o_z, p->G + l.w_off, p->G + l.b_off, B, l.N, l.K);
     g.ad_p = p->P + l.w_off; g.ad_m = p->M + l.w_off; g.ad_v = p->V + l.w_off; g.ad_shadow = shadow ? shadow + l.w_off : nullptr;
-    set_adam(g, h);
+    g.ad = adam_hyper(h);
     if ((rc = run_gemm(p, s, g))) return rc;
     RTable rt;
     if ((rc = sheet_front_bwd(p, s, rt, 9.0e6))) return rc;
@@ -1387,7 +1389,7 @@ static int glyph1_fused(afr_plan* p, const int64_t* x, const int64_t* font, cons
         p->wT_valid = true;
     }
     Glyph1Args a;
-    a.x = x; a.font = font; a.target = target; a.tdtype = tdtype; a.rowmap = rowmap; a.loss_kind = c.loss;
+    a.x = x; a.font = font; a.loss = loss_args(p, true, target, tdtype, rowmap, mean_elems, loss_accum);
     a.B = B; a.E = E; a.N1 = N1; a.P = Pix; a.vocab = c.vocab; a.n_fonts = c.n_fonts;
     a.emb = p->P + p->emb_off; a.femb = c.n_fonts > 0 ? p->P + p->font_off : nullptr;
     a.b1 = p->P + l1.b_off; a.b2 = p->P + l2.b_off;
@@ -1396,9 +1398,7 @@ static int glyph1_fused(afr_plan* p, const int64_t* x, const int64_t* font, cons
     a.W2T = b16 ? (const void*)(p->ws + p->o_w2t) : (const void*)(p->P + l2.w_off);
     a.slabs = (float*)(p->ws + p->o_slab1); a.slab_stride = p->total;
     a.o_emb = p->emb_off; a.o_font = c.n_fonts > 0 ? p->font_off : 0; a.o_w1 = l1.w_off; a.o_b1 = l1.b_off; a.o_w2 = l2.w_off; a.o_b2 = l2.b_off;
-    float* scratch = (float*)(p->ws + p->o_loss);
-    a.inv_n = (float)(1.0 / (double)mean_elems); a.loss_partial = scratch + 1040; a.counter = reinterpret_cast<unsigned*>(scratch + 1032);
-    a.loss_accum = loss_accum; a.err = (uint32_t*)(p->ws + p->o_err);
+    a.err = (uint32_t*)(p->ws + p->o_err);
     const int R = afr_glyph1_rows(c.dtype), nrb = (B + R - 1) / R, cs = afr_glyph1_colsplit(c.dtype, B, Pix), nblk = nrb * cs;
     a.cs = cs;
     {
@@ -1436,7 +1436,7 @@ static int glyph1_fused(afr_plan* p, const int64_t* x, const int64_t* font, cons
 static int forward_loss_impl(afr_plan* p, const int64_t* x, const int64_t* font, const void* target, int tdtype, const int* rowmap, int B, int L,
                              int64_t mean_elems, float* loss_accum, uint64_t step, void* stream) {
     if (int rc = check_loss_args(target, tdtype, mean_elems, loss_accum)) return rc;
-    FusedLoss fl{target, tdtype, mean_elems, loss_accum, rowmap, p->cfg.loss};
+    const LossArgs fl = loss_args(p, true, target, tdtype, rowmap, mean_elems, loss_accum);
     return forward_impl(p, x, font, B, L, nullptr, 1, step, stream, &fl);
 }
 extern "C" int afr_forward_loss(afr_plan* p, const int64_t* x, const int64_t* font, const void* target, int tdtype, int B, int L,
@@ -1469,7 +1469,7 @@ static int train_step_impl(afr_plan* p, const int64_t* x, const int64_t* font, c
         return AFR_OK;
     }
     // the loss and its gradient are computed in the epilogue of the last forward GEMM: u never touches HBM
-    FusedLoss fl{target, tdtype, mean_elems, loss_accum, rowmap, p->cfg.loss};
+    const LossArgs fl = loss_args(p, true, target, tdtype, rowmap, mean_elems, loss_accum);
     if ((rc = forward_impl(p, x, font, B, L, nullptr, 1, step, stream, &fl))) return rc;
     if (fuse_opt && fused_step_eligible(p, B)) {
         if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
@@ -1716,25 +1716,21 @@ extern "C" int afr_op_adamw(float* p, const float* g, float* m, float* v, void* 
                             float b2, float eps, float wd, int64_t t, float gscale, void* stream) {
     if (!p || !g || !m || !v || t < 1) return fail(AFR_EINVAL, "bad AdamW arguments");
     DevGuard dg(device_of(p));
-    const float bc1 = (float)(1.0 - std::pow((double)b1, (double)t));
-    const float bc2 = (float)(1.0 - std::pow((double)b2, (double)t));
-    HIPCHK(afr_launch_adamw(p, g, m, v, (bf16_t*)shadow, n, lr, b1, b2, eps, wd, bc1, bc2, gscale, (hipStream_t)stream));
+    HIPCHK(afr_launch_adamw(p, g, m, v, (bf16_t*)shadow, n, lr, wd, adam_hyper(AdamArgs{lr, b1, b2, eps, wd, t}), gscale, (hipStream_t)stream));
     return AFR_OK;
 }
 extern "C" int afr_op_mse_grad(int act_dtype, const void* u, const void* target, int tdtype, void* du, int64_t rows,
                                int64_t cols, int64_t mean_elems, float* loss_accum, float* scratch, void* stream) {
     if (!u || !target || !du || !loss_accum || !scratch) return fail(AFR_EINVAL, "null argument");
     DevGuard dg(device_of(du));
-    HIPCHK(afr_launch_mse_grad(act_dtype, u, target, tdtype, du, rows, cols, mean_elems, loss_accum, scratch,
-                               (hipStream_t)stream));
+    HIPCHK(afr_launch_mse_grad(act_dtype, u, du, rows, cols, loss_args(scratch, false, AFR_LOSS_MSE, target, tdtype, nullptr, mean_elems, loss_accum), (hipStream_t)stream));
     return AFR_OK;
 }
 extern "C" int afr_op_bce_grad(int act_dtype, const void* u, const void* target, int tdtype, void* du, int64_t rows,
                                int64_t cols, int64_t mean_elems, float* loss_accum, float* scratch, void* stream) {
     if (!u || !target || !du || !loss_accum || !scratch) return fail(AFR_EINVAL, "null argument");
     DevGuard dg(device_of(du));
-    HIPCHK(afr_launch_mse_grad(act_dtype, u, target, tdtype, du, rows, cols, mean_elems, loss_accum, scratch,
-                               (hipStream_t)stream, nullptr, AFR_LOSS_BCE));
+    HIPCHK(afr_launch_mse_grad(act_dtype, u, du, rows, cols, loss_args(scratch, false, AFR_LOSS_BCE, target, tdtype, nullptr, mean_elems, loss_accum), (hipStream_t)stream));
     return AFR_OK;
 }
 extern "C" int afr_op_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream) {

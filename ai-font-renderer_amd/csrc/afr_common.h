@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <type_traits>
 
 typedef __bf16 bf16_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -105,6 +106,84 @@ __device__ __forceinline__ float bce_logits_elem(float u, float t, float inv_n, 
     du = (sigmoid_of(u, e) - t) * inv_n;
     return fmaf(-t, u, fmaxf(u, 0.f)) + __logf(1.f + e);
 }
+// The loss head of ONE pixel: returns the loss term of u against target t and leaves du.  LOSS_MSE: (clamp(u,0,1) - t)^2 and
+// du = 2 (clamp(u,0,1) - t) / mean_elems * [0<=u<=1] (reference model.py:156,268-270); g2 = 2 * inv_n is the caller's, hoisted out
+// of its pixel loop (taken here it costs an instruction per pixel).  LOSS_BCE: bce_logits_elem.  Every loss site calls this.
+template <int LOSS>
+__device__ __forceinline__ float loss_elem(float u, float t, float inv_n, float g2, float& du) {
+    if constexpr (LOSS == LOSS_BCE) return bce_logits_elem(u, t, inv_n, du);
+    else {
+        const float diff = fminf(fmaxf(u, 0.f), 1.f) - t;
+        du = (u >= 0.f && u <= 1.f) ? g2 * diff : 0.f;
+        return diff * diff;
+    }
+}
+// 8 packed uint8 targets as floats, pixel / 255.0f (helpers.py:121): divided, or (LUT) looked up in the block's table of the 256
+// quotients -- the same values.  (A kernel that has the table only sometimes branches at the call: one branch for the eight.)
+template <bool LUT>
+__device__ __forceinline__ void targets_u8x8(uint2 w, const float* lut255, float (&t)[8]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const unsigned a = (w.x >> (8 * r)) & 0xFF, b = (w.y >> (8 * r)) & 0xFF;
+        t[r] = LUT ? lut255[a] : (float)a / 255.0f;
+        t[4 + r] = LUT ? lut255[b] : (float)b / 255.0f;
+    }
+}
+// What a loss site needs besides its logits.  One host function builds it (afr_api.hip loss_args).
+struct LossArgs {
+    const void* target = nullptr;   // [rows][cols] uint8 or float32; NULL in a GemmParams = no fused loss
+    const int* rowmap = nullptr;    // optional: the targets of output row m are row rowmap[m] of target (a resident data set read in
+                                    // place, 64-bit addressing); NULL = row m
+    int tdtype = 0;                 // AFR_TARGET_*
+    float inv_n = 0.f;              // 1 / mean_elems
+    float* partial = nullptr;       // per-block partial sums (>= grid floats)
+    unsigned* counter = nullptr;    // arrival counter, zero on entry, re-armed by the last block
+    float* loss_accum = nullptr;    // device scalar: += sum(partials) / mean_elems
+    int kind = LOSS_MSE;            // LOSS_MSE: clamp head + MSE; LOSS_BCE: sigmoid head + BCE with logits
+};
+// the target row of output row m (TROWS: an instantiation of its own, so that the dense kernels carry no row-map code)
+template <bool TROWS> __device__ __forceinline__ int loss_target_row(const LossArgs& l, int m) { return TROWS ? l.rowmap[m] : m; }
+
+// torch.optim.AdamW (reference model.py:273,310) with the step's scalars folded on the host (afr_api.hip adam_hyper):
+//   p *= decay;  m += (g-m)*(1-b1);  v = b2*v + (1-b2)*g*g;  p -= step * m / (sqrt(v) * rsqrt_bc2 + eps)
+struct AdamHyper { float decay = 1.f, b1 = 0.f, b2 = 0.f, eps = 0.f, step = 0.f /* lr / bc1 */, rsqrt_bc2 = 1.f; };
+// The fused multiply-adds are spelled out: left to the compiler's contraction, one site (adamw_kernel, with its gradient scale
+// ahead of the update) rounded b2 * v instead of (1 - b2) g g, and the data-parallel step no longer equalled the fused one bit
+// for bit.  These are the forms every site of the parent compiled to.
+__device__ __forceinline__ void adamw_elem(float& p, float& m, float& v, float g, const AdamHyper& h) {
+    m = __builtin_fmaf(g - m, 1.f - h.b1, m);
+    v = __builtin_fmaf(v, h.b2, (1.f - h.b2) * g * g);
+    const float denom = __builtin_fmaf(sqrtf(v), h.rsqrt_bc2, h.eps);
+    p = __builtin_fmaf(p, h.decay, -h.step * (m / denom));
+}
+// The same update as the f32 / bf16x3 tile epilogue has always computed it, one element at a time: the plain expressions, which
+// the compiler does not fuse there.  Kept apart so that this path's weights stay what they were, bit for bit; it agrees with
+// adamw_elem to the last bit only (tests/test_gpu_edges.py test_fused_optimizer_step_equals_unfused_step).
+__device__ __forceinline__ void adamw_elem_plain(float& p, float& m, float& v, float g, const AdamHyper& h) {
+    p *= h.decay;
+    m = m + (g - m) * (1.f - h.b1);
+    v = v * h.b2 + (1.f - h.b2) * g * g;
+    const float denom = sqrtf(v) * h.rsqrt_bc2 + h.eps;
+    p -= h.step * (m / denom);
+}
+// The update of four consecutive elements with gradient g; returns the new weights as the bf16 shadow's value.  A site loads
+// and stores p/m/v(/shadow) its own way (streaming buffer loads, an LDS prefetch, nt stores, plain ones).
+// (p/m/v as native vectors, updated element by element: repacked through float4 the 4-wave weight-gradient kernel allocated 247
+// VGPRs for 206)
+__device__ __forceinline__ bf16x4 adamw_quad(f32x4& p, f32x4& m, f32x4& v, f32x4 g, const AdamHyper& h) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { float a = p[r], b = m[r], c = v[r]; adamw_elem(a, b, c, g[r], h); p[r] = a; m[r] = b; v[r] = c; }
+    return (bf16x4){(bf16_t)p[0], (bf16_t)p[1], (bf16_t)p[2], (bf16_t)p[3]};
+}
+
+// Runtime value -> template argument: f is a generic lambda and receives the value as a tag, `[&](auto rows) { k<rows()> ... }` or
+// `[&](auto t) { using T = typename decltype(t)::type; ... }`.  Nest them; instantiate only what exists.
+template <class T> struct TypeTag { using type = T; };
+template <class F> static inline auto with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <class F> static inline auto with_loss(int kind, F&& f) {
+    return kind == LOSS_BCE ? f(std::integral_constant<int, LOSS_BCE>{}) : f(std::integral_constant<int, LOSS_MSE>{});
+}
+template <class F> static inline auto with_act(bool is_bf16, F&& f) { return is_bf16 ? f(TypeTag<bf16_t>{}) : f(TypeTag<float>{}); }
 
 __device__ __forceinline__ float bf16_to_f32(bf16_t x) { return (float)x; }
 __device__ __forceinline__ bf16_t f32_to_bf16(float x) { return (bf16_t)x; }
@@ -122,21 +201,13 @@ struct GemmParams {
     // optional fused bias gradient (A must be k-strided): colsum[z*colsum_stride + m] = sum_k A(m,k) over split z
     float* colsum = nullptr;
     long long colsum_stride = 0;
-    // optional fused loss (last forward layer of a training step): instead of u = A.B^T + bias the epilogue writes
-    // du = 2 (clamp(u,0,1) - t) / mean_elems * [0<=u<=1] and accumulates the MSE (reference model.py:156,268-270)
-    const void* mse_target = nullptr;   // [M][N] uint8 or float32
-    const int* mse_rowmap = nullptr;    // optional: the targets of output row m are row mse_rowmap[m] of mse_target (a resident data set
-                                        // read in place, 64-bit addressing); NULL = row m
-    int mse_target_dtype = 0;           // AFR_TARGET_*
-    float mse_inv_n = 0.f;              // 1 / mean_elems
-    float* mse_partial = nullptr;       // per-block partial sums (>= grid floats)
-    unsigned* mse_counter = nullptr;    // arrival counter, zero on entry, re-armed by the last block
-    float* mse_loss_accum = nullptr;    // device scalar: += sum(partials) / mean_elems
-    int loss_kind = 0;                  // LOSS_MSE, or LOSS_BCE: du = (sigmoid(u) - t) / mean_elems and the BCE-with-logits sum instead
+    // optional fused loss (last forward layer of a training step; loss.target set): instead of u = A.B^T + bias the epilogue
+    // writes du and accumulates the loss (loss_elem)
+    LossArgs loss;
     // optional fused optimizer (dW GEMMs only, single GPU): C is the weight's gradient tile; instead of storing it
     // the epilogue applies AdamW to the matching tile of p/m/v (same [M][ldc] layout) and refreshes the bf16 shadow
     float* ad_p = nullptr; float* ad_m = nullptr; float* ad_v = nullptr; bf16_t* ad_shadow = nullptr;
-    float ad_decay = 1.f, ad_b1 = 0.f, ad_b2 = 0.f, ad_eps = 0.f, ad_step = 0.f, ad_rsqrt_bc2 = 1.f;
+    AdamHyper ad;
     // optional in-launch split-K (bf16, 256x256 tiles; gemm.hip gemm_bf16_256_body): the first head_tiles tiles of the
     // walk are computed whole, each remaining tile as `splitk` K-slices parked in fix_ws (256 KiB per slice) and summed in
     // slice order by the slice block that arrives last (fix_cnt: one zeroed counter per tail tile, re-armed by the kernel).
@@ -164,15 +235,6 @@ struct GemmParams {
 #endif
 };
 constexpr uint32_t AFR_ERR_INDEX = 1u, AFR_ERR_COOP_TIMEOUT = 2u, AFR_ERR_ROW = 4u;    // bits of the plan's device error word
-// torch.optim.AdamW element update (reference model.py:273,310); shared by adamw_kernel and the fused GEMM epilogue
-__device__ __forceinline__ void adamw_elem(float& p, float& m, float& v, float g, float decay, float b1, float b2,
-                                           float eps, float step_size, float rsqrt_bc2) {
-    p *= decay;
-    m = m + (g - m) * (1.f - b1);
-    v = v * b2 + (1.f - b2) * g * g;
-    const float denom = sqrtf(v) * rsqrt_bc2 + eps;
-    p -= step_size * (m / denom);
-}
 hipError_t afr_launch_gemm(int dtype, const GemmParams& p, hipStream_t s);
 hipError_t afr_launch_gemm_fp8(const GemmParams& p, hipStream_t s);          // e4m3 x e4m3, both k-contiguous (gemm.hip fp8k)
 hipError_t afr_launch_f32_to_fp8(const float* src, unsigned char* dst, long long n, float inv_scale, hipStream_t s);
@@ -203,23 +265,20 @@ struct RTable {
     int nseg = 0; int nblocks = 0; int overflow = 0;
     // optional fused optimizer: the summed gradient is not stored; AdamW is applied to p/m/v at the same flat offset
     // (offset of seg.dst from `gbase`)
-    int adam = 0; float ad_decay, ad_b1, ad_b2, ad_eps, ad_step, ad_rsqrt_bc2;
+    int adam = 0; AdamHyper ad;
     const float* gbase; float* P; float* M; float* V; bf16_t* shadow;
     RSeg seg[AFR_RT_MAXSEG];
 };
 void afr_rtable_add(RTable& t, float* dst, const float* src, int nslabs, long long stride, long long n);
 hipError_t afr_launch_reduce_group(const RTable& t, hipStream_t s);
-hipError_t afr_launch_adamw(float* p, const float* g, float* m, float* v, bf16_t* shadow, long long n, float lr,
-                            float beta1, float beta2, float eps, float wd, float bc1, float bc2, float grad_scale,
-                            hipStream_t s);
+// (lr and wd besides h: the kernel folds its decay = 1 - lr * wd on the device, as it always has; h.decay is not read)
+hipError_t afr_launch_adamw(float* p, const float* g, float* m, float* v, bf16_t* shadow, long long n, float lr, float wd,
+                            const AdamHyper& h, float grad_scale, hipStream_t s);
 // loss: u (act dtype) [rows][cols] -> du in place or to `du`; per-block partial sums to scratch, then
 // a 1-block finisher adds sum(scratch) to *loss_accum (deterministic order).
 int afr_mse_blocks(long long rows, long long cols);
-// scratch: >= 1028 floats; scratch[1024] (as unsigned) is the arrival counter, zero before the first call
-hipError_t afr_launch_mse_grad(int act_dtype, const void* u, const void* target, int target_dtype, void* du,
-                               long long rows, long long cols, long long mean_elems, float* loss_accum,
-                               float* scratch, hipStream_t s, const int* rowmap = nullptr /* target row of u row r; NULL = r */,
-                               int loss_kind = LOSS_MSE);
+// l.partial: >= afr_mse_blocks floats
+hipError_t afr_launch_mse_grad(int act_dtype, const void* u, void* du, long long rows, long long cols, const LossArgs& l, hipStream_t s);
 // Batch rows of a resident data set (afr_*_rows): validates and clamps rows[b] (AFR_ERR_ROW), writes ridx[b] = the narrowed index
 // the loss kernels' row maps read and, when sx is not NULL, stages x[rows[b]][0 .. Lc) into sx [B][Lc] and font[rows[b]] into sfont.
 hipError_t afr_launch_dataset_rows(const int64_t* rows, int B, long long n_rows, const int64_t* x, const int64_t* font, int L, int Lc,
@@ -287,16 +346,15 @@ hipError_t afr_launch_sheet_bwd(int act_dtype, const SheetDims& d, const SheetPa
 
 // fused step of the small one-hidden-layer glyph nets (glyph_fused.hip)
 struct Glyph1Args {
-    const int64_t* x; const int64_t* font; const void* target; int tdtype;
-    const int* rowmap = nullptr;             // optional: the targets of glyph b are row rowmap[b] of target (NULL = row b)
-    int loss_kind = 0;                       // LOSS_MSE | LOSS_BCE
+    const int64_t* x; const int64_t* font;
+    LossArgs loss;                           // targets [B][P] (rowmap: of glyph b = row rowmap[b]), the loss scratch and kind
     int B, E, N1, P, vocab, n_fonts;
     const float *emb, *femb, *b1, *b2;       // f32 masters
     const void *W1, *W2;                     // [N1][E], [P][N1] in the operand type (f32 masters / bf16 shadow)
     const void *W1T, *W2T;                   // bf16 mode: [E][N1], [N1][P]; f32 mode: the f32 masters again (gathered)
     float* slabs; long long slab_stride;     // slab b: this block's partial gradients, flat-buffer layout
     long long o_emb, o_font, o_w1, o_b1, o_w2, o_b2;
-    float inv_n; float* loss_partial; unsigned* counter; float* loss_accum; uint32_t* err;
+    uint32_t* err;
     int cs = 1;                              // column split: cs blocks share a row block, each owning P / cs output columns
 };
 int afr_glyph1_rows(int dtype);

@@ -70,26 +70,18 @@ __device__ __forceinline__ float4 slab_sum(const float* src, long long stride, i
     }
     return a;
 }
-__device__ __forceinline__ void reduce_finish(const RTable& t, const RSeg& sg, long long i, float4 a, float4 pp, float4 mm, float4 vv) {
+__device__ __forceinline__ void reduce_finish(const RTable& t, const RSeg& sg, long long i, float4 a, f32x4 pp, f32x4 mm, f32x4 vv) {
     if (t.adam) {
         const long long off = (sg.dst - t.gbase) + 4 * i;
-        adamw_elem(pp.x, mm.x, vv.x, a.x, t.ad_decay, t.ad_b1, t.ad_b2, t.ad_eps, t.ad_step, t.ad_rsqrt_bc2);
-        adamw_elem(pp.y, mm.y, vv.y, a.y, t.ad_decay, t.ad_b1, t.ad_b2, t.ad_eps, t.ad_step, t.ad_rsqrt_bc2);
-        adamw_elem(pp.z, mm.z, vv.z, a.z, t.ad_decay, t.ad_b1, t.ad_b2, t.ad_eps, t.ad_step, t.ad_rsqrt_bc2);
-        adamw_elem(pp.w, mm.w, vv.w, a.w, t.ad_decay, t.ad_b1, t.ad_b2, t.ad_eps, t.ad_step, t.ad_rsqrt_bc2);
-        *reinterpret_cast<float4*>(t.P + off) = pp;
-        *reinterpret_cast<float4*>(t.M + off) = mm;
-        *reinterpret_cast<float4*>(t.V + off) = vv;
-        if (t.shadow) {
-            bf16x4 o = {(bf16_t)pp.x, (bf16_t)pp.y, (bf16_t)pp.z, (bf16_t)pp.w};
-            *reinterpret_cast<bf16x4*>(t.shadow + off) = o;
-        }
+        const bf16x4 o = adamw_quad(pp, mm, vv, (f32x4){a.x, a.y, a.z, a.w}, t.ad);
+        *reinterpret_cast<f32x4*>(t.P + off) = pp;
+        *reinterpret_cast<f32x4*>(t.M + off) = mm;
+        *reinterpret_cast<f32x4*>(t.V + off) = vv;
+        if (t.shadow) *reinterpret_cast<bf16x4*>(t.shadow + off) = o;
         if (sg.shT) {                      // 4 consecutive k of one row n (tK is a multiple of 4)
             const int n = (int)((4 * i) / sg.tK), k = (int)(4 * i - (long long)n * sg.tK);
-            sg.shT[(size_t)k * sg.tN + n] = (bf16_t)pp.x;
-            sg.shT[(size_t)(k + 1) * sg.tN + n] = (bf16_t)pp.y;
-            sg.shT[(size_t)(k + 2) * sg.tN + n] = (bf16_t)pp.z;
-            sg.shT[(size_t)(k + 3) * sg.tN + n] = (bf16_t)pp.w;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sg.shT[(size_t)(k + r) * sg.tN + n] = (bf16_t)pp[r];
         }
     } else {
         reinterpret_cast<float4*>(sg.dst)[i] = a;
@@ -99,7 +91,7 @@ __global__ __launch_bounds__(256) void reduce_group_kernel(RTable t) {
     int si = 0;
     for (int k = 1; k < t.nseg; ++k) if ((int)blockIdx.x >= t.seg[k].blk0) si = k;
     const RSeg sg = t.seg[si];
-    float4 pp = make_float4(0.f, 0.f, 0.f, 0.f), mm = pp, vv = pp;
+    f32x4 pp = {0.f, 0.f, 0.f, 0.f}, mm = pp, vv = pp;
     if (sg.deep) {
         // many slabs, few columns (the per-block partials of the sheet backward): a block owns 64 float4 columns and
         // each of its 4 waves sums a quarter of the slabs; the quarters meet in LDS and are added in wave order.
@@ -113,7 +105,7 @@ __global__ __launch_bounds__(256) void reduce_group_kernel(RTable t) {
             if (live) {
                 if (grp == 0 && t.adam) {
                     const long long off = (sg.dst - t.gbase) + 4 * i;
-                    pp = *reinterpret_cast<float4*>(t.P + off); mm = *reinterpret_cast<float4*>(t.M + off); vv = *reinterpret_cast<float4*>(t.V + off);
+                    pp = *reinterpret_cast<f32x4*>(t.P + off); mm = *reinterpret_cast<f32x4*>(t.M + off); vv = *reinterpret_cast<f32x4*>(t.V + off);
                 }
                 const int s0 = grp * per, s1 = min(sg.nslabs, s0 + per);
                 a = slab_sum(sg.src + 4 * i, sg.stride, s0, s1);
@@ -132,7 +124,7 @@ __global__ __launch_bounds__(256) void reduce_group_kernel(RTable t) {
     for (long long i = (long long)(blockIdx.x - sg.blk0) * 256 + threadIdx.x; i < sg.n4; i += (long long)sg.nblk * 256) {
         if (t.adam) {   // issued ahead of the slab loads so that everything this element needs is in flight at once
             const long long off = (sg.dst - t.gbase) + 4 * i;
-            pp = *reinterpret_cast<float4*>(t.P + off); mm = *reinterpret_cast<float4*>(t.M + off); vv = *reinterpret_cast<float4*>(t.V + off);
+            pp = *reinterpret_cast<f32x4*>(t.P + off); mm = *reinterpret_cast<f32x4*>(t.M + off); vv = *reinterpret_cast<f32x4*>(t.V + off);
         }
         const float4 a = slab_sum(sg.src + 4 * i, sg.stride, 0, sg.nslabs);
         reduce_finish(t, sg, i, a, pp, mm, vv);
@@ -168,34 +160,26 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
                                                     bf16_t* __restrict__ shadow, long long n4, float lr, float b1,
                                                     float b2, float eps, float wd, float step_size, float rsqrt_bc2,
                                                     float gscale) {
-    const float decay = 1.f - lr * wd;
+    const AdamHyper h{1.f - lr * wd, b1, b2, eps, step_size, rsqrt_bc2};
     for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-        float4 pp = reinterpret_cast<float4*>(p)[i];
-        float4 gg = reinterpret_cast<const float4*>(g)[i];
-        float4 mm = reinterpret_cast<float4*>(m)[i];
-        float4 vv = reinterpret_cast<float4*>(v)[i];
-        float pa[4] = {pp.x, pp.y, pp.z, pp.w}, ga[4] = {gg.x, gg.y, gg.z, gg.w};
-        float ma[4] = {mm.x, mm.y, mm.z, mm.w}, va[4] = {vv.x, vv.y, vv.z, vv.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) adamw_elem(pa[k], ma[k], va[k], ga[k] * gscale, decay, b1, b2, eps, step_size, rsqrt_bc2);
-        reinterpret_cast<float4*>(p)[i] = make_float4(pa[0], pa[1], pa[2], pa[3]);
-        reinterpret_cast<float4*>(m)[i] = make_float4(ma[0], ma[1], ma[2], ma[3]);
-        reinterpret_cast<float4*>(v)[i] = make_float4(va[0], va[1], va[2], va[3]);
-        if (shadow) {
-            bf16x4 o = {(bf16_t)pa[0], (bf16_t)pa[1], (bf16_t)pa[2], (bf16_t)pa[3]};
-            reinterpret_cast<bf16x4*>(shadow)[i] = o;
-        }
+        const float4 p4 = reinterpret_cast<float4*>(p)[i];
+        const float4 gg = reinterpret_cast<const float4*>(g)[i];
+        const float4 m4 = reinterpret_cast<float4*>(m)[i];
+        const float4 v4 = reinterpret_cast<float4*>(v)[i];
+        f32x4 pp = {p4.x, p4.y, p4.z, p4.w}, mm = {m4.x, m4.y, m4.z, m4.w}, vv = {v4.x, v4.y, v4.z, v4.w};
+        const bf16x4 o = adamw_quad(pp, mm, vv, (f32x4){gg.x * gscale, gg.y * gscale, gg.z * gscale, gg.w * gscale}, h);
+        reinterpret_cast<float4*>(p)[i] = make_float4(pp[0], pp[1], pp[2], pp[3]);
+        reinterpret_cast<float4*>(m)[i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
+        reinterpret_cast<float4*>(v)[i] = make_float4(vv[0], vv[1], vv[2], vv[3]);
+        if (shadow) reinterpret_cast<bf16x4*>(shadow)[i] = o;
     }
 }
-hipError_t afr_launch_adamw(float* p, const float* g, float* m, float* v, bf16_t* shadow, long long n, float lr,
-                            float beta1, float beta2, float eps, float wd, float bc1, float bc2, float grad_scale,
-                            hipStream_t s) {
+hipError_t afr_launch_adamw(float* p, const float* g, float* m, float* v, bf16_t* shadow, long long n, float lr, float wd,
+                            const AdamHyper& h, float grad_scale, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     if (n & 3) return hipErrorInvalidValue;   // flat buffers are padded to multiples of 64
-    const float step_size = lr / bc1;
-    const float rsqrt_bc2 = (float)(1.0 / sqrt((double)bc2));
     hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n / 4, 256, 4096)), dim3(256), 0, s, p, g, m, v, shadow, n / 4, lr,
-                       beta1, beta2, eps, wd, step_size, rsqrt_bc2, grad_scale);
+                       h.b1, h.b2, h.eps, wd, h.step, h.rsqrt_bc2, grad_scale);
     return hipGetLastError();
 }
 
@@ -254,14 +238,10 @@ __global__ __launch_bounds__(256) void clamp_out_kernel(const T* __restrict__ u,
 }
 hipError_t afr_launch_clamp_out(int act_dtype, const void* u, float* y, long long n, hipStream_t s, int loss_kind) {
     if (n <= 0) return hipSuccess;
-    const dim3 g(grid_for(n, 256)), b(256);
-    if (loss_kind == LOSS_BCE) {
-        if (act_dtype == AFR_BF16) hipLaunchKernelGGL((clamp_out_kernel<bf16_t, LOSS_BCE>), g, b, 0, s, (const bf16_t*)u, y, n);
-        else hipLaunchKernelGGL((clamp_out_kernel<float, LOSS_BCE>), g, b, 0, s, (const float*)u, y, n);
-    } else if (act_dtype == AFR_BF16)
-        hipLaunchKernelGGL(clamp_out_kernel<bf16_t>, g, b, 0, s, (const bf16_t*)u, y, n);
-    else
-        hipLaunchKernelGGL(clamp_out_kernel<float>, g, b, 0, s, (const float*)u, y, n);
+    with_act(act_dtype == AFR_BF16, [&](auto t) { with_loss(loss_kind, [&](auto loss) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((clamp_out_kernel<T, loss()>), dim3(grid_for(n, 256)), dim3(256), 0, s, (const T*)u, y, n);
+    }); });
     return hipGetLastError();
 }
 
@@ -279,11 +259,10 @@ __global__ __launch_bounds__(256) void clamp_bwd_kernel(T* __restrict__ u, const
 }
 hipError_t afr_launch_clamp_bwd(int act_dtype, void* u, const float* dy, long long n, hipStream_t s, int loss_kind) {
     if (n <= 0) return hipSuccess;
-    if (loss_kind == LOSS_BCE) {
-        if (act_dtype == AFR_BF16) hipLaunchKernelGGL((clamp_bwd_kernel<bf16_t, LOSS_BCE>), dim3(grid_for(n, 256)), dim3(256), 0, s, (bf16_t*)u, dy, n);
-        else hipLaunchKernelGGL((clamp_bwd_kernel<float, LOSS_BCE>), dim3(grid_for(n, 256)), dim3(256), 0, s, (float*)u, dy, n);
-    } else if (act_dtype == AFR_BF16) hipLaunchKernelGGL(clamp_bwd_kernel<bf16_t>, dim3(grid_for(n, 256)), dim3(256), 0, s, (bf16_t*)u, dy, n);
-    else hipLaunchKernelGGL(clamp_bwd_kernel<float>, dim3(grid_for(n, 256)), dim3(256), 0, s, (float*)u, dy, n);
+    with_act(act_dtype == AFR_BF16, [&](auto t) { with_loss(loss_kind, [&](auto loss) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((clamp_bwd_kernel<T, loss()>), dim3(grid_for(n, 256)), dim3(256), 0, s, (T*)u, dy, n);
+    }); });
     return hipGetLastError();
 }
 
@@ -319,27 +298,14 @@ __global__ __launch_bounds__(256) void mse_grad_kernel(const T* __restrict__ u, 
             for (int k = 0; k < 8; ++k) uu[k] = (float)a[k];
         }
         if (sizeof(TT) == 1) {
-            const uint2 a = reinterpret_cast<const uint2*>(tgt)[ti];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                tt[k] = (float)((a.x >> (8 * k)) & 0xFF) / 255.0f;       // helpers.py:121: uint8 / 255.0 in float32
-                tt[4 + k] = (float)((a.y >> (8 * k)) & 0xFF) / 255.0f;
-            }
+            targets_u8x8<false>(reinterpret_cast<const uint2*>(tgt)[ti], nullptr, tt);
         } else {
             const float4 a = reinterpret_cast<const float4*>(tgt)[2 * ti], b = reinterpret_cast<const float4*>(tgt)[2 * ti + 1];
             tt[0] = a.x; tt[1] = a.y; tt[2] = a.z; tt[3] = a.w; tt[4] = b.x; tt[5] = b.y; tt[6] = b.z; tt[7] = b.w;
         }
         float dd[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            if constexpr (LOSS == LOSS_BCE) lsum += bce_logits_elem(uu[k], tt[k], inv_n, dd[k]);
-            else {
-                const float y = fminf(fmaxf(uu[k], 0.f), 1.f);
-                const float diff = y - tt[k];
-                lsum += diff * diff;
-                dd[k] = (uu[k] >= 0.f && uu[k] <= 1.f) ? g2 * diff : 0.f;
-            }
-        }
+        for (int k = 0; k < 8; ++k) lsum += loss_elem<LOSS>(uu[k], tt[k], inv_n, g2, dd[k]);
         if (sizeof(T) == 4) {
             reinterpret_cast<float4*>(du)[2 * i] = make_float4(dd[0], dd[1], dd[2], dd[3]);
             reinterpret_cast<float4*>(du)[2 * i + 1] = make_float4(dd[4], dd[5], dd[6], dd[7]);
@@ -358,31 +324,19 @@ __global__ __launch_bounds__(256) void mse_grad_kernel(const T* __restrict__ u, 
     loss_block_finish((wsum[0] + wsum[1]) + (wsum[2] + wsum[3]), partial, counter, loss_accum, inv_n, sh);
 }
 int afr_mse_blocks(long long rows, long long cols) { return grid_for(rows * cols / 8, 256, 1024); }
-hipError_t afr_launch_mse_grad(int act_dtype, const void* u, const void* target, int target_dtype, void* du,
-                               long long rows, long long cols, long long mean_elems, float* loss_accum,
-                               float* scratch, hipStream_t s, const int* rowmap, int loss_kind) {
+hipError_t afr_launch_mse_grad(int act_dtype, const void* u, void* du, long long rows, long long cols, const LossArgs& l, hipStream_t s) {
     const long long n = rows * cols;
     if (n <= 0) return hipSuccess;
-    if ((n & 7) || (rowmap && (cols & 7))) return hipErrorInvalidValue;
-    const int blocks = afr_mse_blocks(rows, cols);
-    const float inv_n = (float)(1.0 / (double)mean_elems);
-    dim3 g(blocks), b(256);
-    unsigned* counter = reinterpret_cast<unsigned*>(scratch + 1024);
-#define MSE_K(T, TT, K)                                                                                                                    \
-    do {                                                                                                                                   \
-        if (rowmap) hipLaunchKernelGGL((mse_grad_kernel<T, TT, true, K>), g, b, 0, s, (const T*)u, (const TT*)target, (T*)du, n / 8, inv_n, \
-                                       scratch, counter, loss_accum, rowmap, (int)(cols / 8));                                             \
-        else hipLaunchKernelGGL((mse_grad_kernel<T, TT, false, K>), g, b, 0, s, (const T*)u, (const TT*)target, (T*)du, n / 8, inv_n,      \
-                                scratch, counter, loss_accum, (const int*)nullptr, 0);                                                     \
-    } while (0)
-#define MSE(T, TT) do { if (loss_kind == LOSS_BCE) MSE_K(T, TT, LOSS_BCE); else MSE_K(T, TT, LOSS_MSE); } while (0)
-    if (act_dtype == AFR_BF16) {
-        if (target_dtype == AFR_TARGET_U8) MSE(bf16_t, uint8_t); else MSE(bf16_t, float);
-    } else {
-        if (target_dtype == AFR_TARGET_U8) MSE(float, uint8_t); else MSE(float, float);
-    }
-#undef MSE
-#undef MSE_K
+    if ((n & 7) || (l.rowmap && (cols & 7))) return hipErrorInvalidValue;
+    const dim3 g(afr_mse_blocks(rows, cols)), b(256);
+    with_act(act_dtype == AFR_BF16, [&](auto ta) { with_bool(l.tdtype == AFR_TARGET_U8, [&](auto u8) { with_bool(l.rowmap != nullptr, [&](auto tr) {
+        with_loss(l.kind, [&](auto loss) {
+            using T = typename decltype(ta)::type;
+            using TT = std::conditional_t<u8(), uint8_t, float>;
+            hipLaunchKernelGGL((mse_grad_kernel<T, TT, tr(), loss()>), g, b, 0, s, (const T*)u, (const TT*)l.target, (T*)du, n / 8, l.inv_n, l.partial,
+                               l.counter, l.loss_accum, l.rowmap, tr() ? (int)(cols / 8) : 0);
+        });
+    }); }); });
     return hipGetLastError();
 }
 

@@ -64,6 +64,13 @@ __device__ __forceinline__ void tile_of_block(const GemmParams& p, int BM, int B
     z = v / tiles;
     tile_coords(p, BM, BN, v - z * tiles, nb >> 3, nb & 7, tm, tn);
 }
+// K range [kbeg, kend) of K-slice z of `splitk`: equal slices of whole BK-tiles, the last one clipped to K
+template <int BK>
+__device__ __forceinline__ void k_range(int K, int splitk, int z, int& kbeg, int& kend) {
+    const int klen = ((K + splitk - 1) / splitk + BK - 1) / BK * BK;
+    kbeg = z * klen;
+    kend = min(K, kbeg + klen);
+}
 
 // ------------------------------------------------------------------------------------------- f32
 namespace f32k {
@@ -123,7 +130,7 @@ __device__ __forceinline__ void colsum_store(const GemmParams& p, float* smem, c
     }
 }
 // bias, ReLU, ReLU mask, split-K slabs, bf16 output, fused clamp/MSE/du, fused AdamW; smem: >= 16 + 256 floats of scratch
-// TROWS: the fused loss' targets are rows p.mse_rowmap[m] of a resident data set (its own instantiation: the dense kernels carry
+// TROWS: the fused loss' targets are rows p.loss.rowmap[m] of a resident data set (its own instantiation: the dense kernels carry
 // no row-map code).  LOSS: the fused loss' kind, likewise an instantiation of its own (LOSS_BCE: sigmoid head + BCE on the logits,
 // bce_logits_elem; the LOSS_MSE kernels carry none of it)
 template <bool TROWS = false, int LOSS = LOSS_MSE>
@@ -134,12 +141,12 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& p, const f32x16 
     // epilogue: D[row = (r&3) + 8*(r>>2) + 4*(lane>>5)][col = lane&31]; rows are m, columns n
     const int flags = p.flags;
     const bool out_bf16 = flags & AFR_GEMM_OUT_BF16;
-    const bool mse = p.mse_target != nullptr;
+    const bool mse = p.loss.target != nullptr;
     float* Cf = reinterpret_cast<float*>(p.C) + (size_t)z * p.slab_stride;
     bf16_t* Cb = reinterpret_cast<bf16_t*>(p.C);
     const float* aux = reinterpret_cast<const float*>(p.aux);
     float lsum = 0.f;
-    const float g2 = 2.f * p.mse_inv_n;
+    const float g2 = 2.f * p.loss.inv_n;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -156,22 +163,16 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& p, const f32x16 
                 if (flags & AFR_GEMM_RELU_MASK) v = (aux[(size_t)m * p.ldaux + n] > 0.f) ? v : 0.f;
                 if (mse) {
                     if (out_bf16) v = (float)(bf16_t)v;
-                    const size_t ti = (size_t)(TROWS ? p.mse_rowmap[m] : m) * p.N + n;
-                    const float t = p.mse_target_dtype == AFR_TARGET_U8 ? (float)reinterpret_cast<const uint8_t*>(p.mse_target)[ti] / 255.0f
-                                                                        : reinterpret_cast<const float*>(p.mse_target)[ti];
-                    if constexpr (LOSS == LOSS_BCE) {
-                        const float uu = v;
-                        lsum += bce_logits_elem(uu, t, p.mse_inv_n, v);
-                    } else {
-                        const float diff = fminf(fmaxf(v, 0.f), 1.f) - t;
-                        lsum += diff * diff;
-                        v = (v >= 0.f && v <= 1.f) ? g2 * diff : 0.f;
-                    }
+                    const size_t ti = (size_t)loss_target_row<TROWS>(p.loss, m) * p.N + n;
+                    const float t = p.loss.tdtype == AFR_TARGET_U8 ? (float)reinterpret_cast<const uint8_t*>(p.loss.target)[ti] / 255.0f
+                                                                   : reinterpret_cast<const float*>(p.loss.target)[ti];
+                    const float uu = v;
+                    lsum += loss_elem<LOSS>(uu, t, p.loss.inv_n, g2, v);
                 }
                 if (p.ad_p) {                          // fused AdamW on weight element (m, n); v is its gradient
                     const size_t wi = (size_t)m * p.ldc + n;
                     float pp = p.ad_p[wi], mm = p.ad_m[wi], vv = p.ad_v[wi];
-                    adamw_elem(pp, mm, vv, v, p.ad_decay, p.ad_b1, p.ad_b2, p.ad_eps, p.ad_step, p.ad_rsqrt_bc2);
+                    adamw_elem_plain(pp, mm, vv, v, p.ad);
                     p.ad_p[wi] = pp; p.ad_m[wi] = mm; p.ad_v[wi] = vv;
                 } else if (out_bf16) Cb[(size_t)m * p.ldc + n] = f32_to_bf16(v);
                 else Cf[(size_t)m * p.ldc + n] = v;
@@ -182,7 +183,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& p, const f32x16 
         lsum = wave_sum(lsum);
         if (lane == 0) smem[wid] = lsum;
         __syncthreads();
-        loss_block_finish((smem[0] + smem[1]) + (smem[2] + smem[3]), p.mse_partial, p.mse_counter, p.mse_loss_accum, p.mse_inv_n, smem + 16);
+        loss_block_finish((smem[0] + smem[1]) + (smem[2] + smem[3]), p.loss.partial, p.loss.counter, p.loss.loss_accum, p.loss.inv_n, smem + 16);
     }
 }
 
@@ -196,9 +197,8 @@ __global__ __launch_bounds__(256) void gemm_f32(GemmParams p) {
     int tm, tn, z;
     tile_of_block(p, BM, BN, blockIdx.x, gridDim.x, tm, tn, z);
     const int m0 = tm * BM, n0 = tn * BN;
-    const int klen = ((p.K + p.splitk - 1) / p.splitk + BK - 1) / BK * BK;
-    const int kbeg = z * klen;
-    const int kend = min(p.K, kbeg + klen);
+    int kbeg, kend;
+    k_range<BK>(p.K, p.splitk, z, kbeg, kend);
     const float* A = reinterpret_cast<const float*>(p.A);
     const float* B = reinterpret_cast<const float*>(p.B);
 
@@ -342,9 +342,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3(GemmParams p) {
     int tm, tn, z;
     tile_of_block(p, BM, BN, blockIdx.x, gridDim.x, tm, tn, z);
     const int m0 = tm * BM, n0 = tn * BN;
-    const int klen = ((p.K + p.splitk - 1) / p.splitk + BK - 1) / BK * BK;
-    const int kbeg = z * klen;
-    const int kend = min(p.K, kbeg + klen);
+    int kbeg, kend;
+    k_range<BK>(p.K, p.splitk, z, kbeg, kend);
     const float* A = reinterpret_cast<const float*>(p.A);
     const float* B = reinterpret_cast<const float*>(p.B);
 
@@ -459,23 +458,6 @@ __device__ __forceinline__ i32x4 make_rsrc(const void* base) {
     i32x4 r = {(int)(unsigned)a, (int)((unsigned)(a >> 32) & 0xFFFFu), 0x7FFFFFFF, 0x00020000};
     return r;
 }
-// byte offset of lane `lane`'s 16 source bytes of piece `inst` of a sub-tile (out of range -> past the descriptor: zeros)
-template <int LAY>
-__device__ __forceinline__ unsigned piece_voff(int ld, int X, int x0, int k0, int kend, int inst, int lane) {
-    int gx, gk;
-    if (LAY == 0) {
-        const int r = inst * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ (r & 7);
-        gx = x0 + r; gk = k0 + 8 * c;
-    } else {
-        const int kr = inst * 4 + (lane >> 4);
-        const int c = (lane & 15) ^ (fswz(kr) << 1);
-        gk = k0 + kr; gx = x0 + 8 * c;
-    }
-    unsigned off = (LAY == 0) ? (unsigned)(((size_t)gx * ld + gk) * 2) : (unsigned)(((size_t)gk * ld + gx) * 2);
-    if (gx >= X || gk >= kend) off = 0x80000000u;
-    return off;
-}
 // rowmap (optional): the operand's memory row (x for LAY 0, k for LAY 1) is row rowmap[row] of the table behind rsrc
 template <int LAY>
 __device__ __forceinline__ void stage_inst(i32x4 rsrc, unsigned lds_sub, int ld, int X, int x0, int k0,
@@ -563,7 +545,7 @@ __device__ __forceinline__ void epilogue_bias(const GemmParams& p, const int nb0
 }
 // (acc_at(i, j): the wave's accumulator fragment of rows 16 i .., columns 16 j .. -- an accessor, so that the 256x256 body can hand
 // over either half of its 128 x 64 tile without copying 64 registers)
-// (TROWS: the fused loss' targets are rows p.mse_rowmap[m] of a resident data set, read in place -- its own instantiation of the
+// (TROWS: the fused loss' targets are rows p.loss.rowmap[m] of a resident data set, read in place -- its own instantiation of the
 // forward-layout ring kernels, so that the dense kernels carry no row-map code)
 // (LOSS: the fused loss' kind, an instantiation of its own as well: the LOSS_MSE kernels carry no BCE code)
 template <int ALAY, int BLAY, int WM, bool SCALE = false, bool EARLYB_ = true, bool TROWS = false, int LOSS = LOSS_MSE, class ACC>      // SCALE: the accumulators are multiplied by p.out_scale first (fp8 per-tensor scales)
@@ -579,7 +561,7 @@ __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC&
     constexpr bool EARLYB = EARLYB_ && ALAY == 0 && BLAY == 0;
     const int flags = p.flags;
     const bool out_bf16 = flags & AFR_GEMM_OUT_BF16;
-    const bool mse = p.mse_target != nullptr;
+    const bool mse = p.loss.target != nullptr;
     const int c8 = lane & 7;
     const int n = nb0 + 8 * c8;
     const bool ncol = n < p.N;
@@ -599,12 +581,12 @@ __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC&
     // the fused loss' uint8 targets of the wave's 8 row passes (8 bytes per lane and pass) are requested before the park as well
     // (forward layout on the ring kernels only: the 256x256 body takes no fused loss)
     uint2 tu8[8];
-    const bool early_t = EARLYB && pre_bias == nullptr && mse && p.mse_target_dtype == AFR_TARGET_U8;
+    const bool early_t = EARLYB && pre_bias == nullptr && mse && p.loss.tdtype == AFR_TARGET_U8;
     if (early_t && !TROWS) {
 #pragma unroll
         for (int ps = 0; ps < 8; ++ps) {
             const int m = mb + ps * 8 + (lane >> 3);
-            if (m < p.M && ncol) tu8[ps] = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(p.mse_target) + (size_t)m * p.N + n);
+            if (m < p.M && ncol) tu8[ps] = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(p.loss.target) + (size_t)m * p.N + n);
         }
     }
     // (row-mapped: one int per row pass, shared by the 8 lanes of the row, all 8 asked for before the first target; 64-bit
@@ -614,12 +596,12 @@ __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC&
 #pragma unroll
         for (int ps = 0; ps < 8; ++ps) {
             const int m = mb + ps * 8 + (lane >> 3);
-            tm[ps] = m < p.M ? p.mse_rowmap[m] : 0;
+            tm[ps] = m < p.M ? p.loss.rowmap[m] : 0;
         }
 #pragma unroll
         for (int ps = 0; ps < 8; ++ps) {
             const int m = mb + ps * 8 + (lane >> 3);
-            if (m < p.M && ncol) tu8[ps] = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(p.mse_target) + (size_t)tm[ps] * p.N + n);
+            if (m < p.M && ncol) tu8[ps] = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(p.loss.target) + (size_t)tm[ps] * p.N + n);
         }
     }
 #pragma unroll
@@ -646,7 +628,7 @@ __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC&
     float* Cf = reinterpret_cast<float*>(p.C) + (size_t)z * p.slab_stride;
     bf16_t* Cb = reinterpret_cast<bf16_t*>(p.C);
     const bf16_t* aux = reinterpret_cast<const bf16_t*>(p.aux);
-    const float g2 = 2.f * p.mse_inv_n;
+    const float g2 = 2.f * p.loss.inv_n;
     const bool relu_mask = flags & AFR_GEMM_RELU_MASK;
     // the tails' global operands (aux for the ReLU mask, targets for the fused loss) are fetched for all 8 row passes
     // up front: one memory latency instead of eight serial ones
@@ -659,7 +641,7 @@ __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC&
     uint2 mrow = {0u, 0u};
     if (wide_bits && mb + lane < p.M && nb0 < p.N)
         mrow = *reinterpret_cast<const uint2*>(p.mask_in + (size_t)(mb + lane) * p.ldmask + (nb0 >> 3));
-    if ((relu_mask && !wide_bits) || (mse && !early_t && p.mse_target_dtype == AFR_TARGET_U8)) {
+    if ((relu_mask && !wide_bits) || (mse && !early_t && p.loss.tdtype == AFR_TARGET_U8)) {
         int am[8];                                   // aux rows (gathered through aux_rowmap when the mask operand is a table)
 #pragma unroll
         for (int ps = 0; ps < 8; ++ps) {
@@ -674,7 +656,7 @@ __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC&
                     if (p.mask_in) auxv[ps][0] = __builtin_bit_cast(bf16_t, (unsigned short)p.mask_in[(size_t)m * p.ldmask + (n >> 3)]);   // the 8 bits travel in element 0
                     else auxv[ps] = *reinterpret_cast<const bf16x8*>(aux + (size_t)am[ps] * p.ldaux + n);
                 }
-                if (mse && !early_t) tu8[ps] = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(p.mse_target) + (size_t)(TROWS ? p.mse_rowmap[m] : m) * p.N + n);
+                if (mse && !early_t) tu8[ps] = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(p.loss.target) + (size_t)loss_target_row<TROWS>(p.loss, m) * p.N + n);
             }
         }
     }
@@ -733,17 +715,12 @@ __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC&
             }
             if (adam) {
                 const int bf = ps % ADF;
-                float pp[4] = {qp[bf].x, qp[bf].y, qp[bf].z, qp[bf].w}, mm[4] = {qm[bf].x, qm[bf].y, qm[bf].z, qm[bf].w};
-                float vv[4] = {qv[bf].x, qv[bf].y, qv[bf].z, qv[bf].w};
-#pragma unroll
-                for (int r = 0; r < 4; ++r) adamw_elem(pp[r], mm[r], vv[r], g[r], p.ad_decay, p.ad_b1, p.ad_b2, p.ad_eps, p.ad_step, p.ad_rsqrt_bc2);
-                ADST(p.ad_p + wi, make_float4(pp[0], pp[1], pp[2], pp[3]));
-                ADST(p.ad_m + wi, make_float4(mm[0], mm[1], mm[2], mm[3]));
-                ADST(p.ad_v + wi, make_float4(vv[0], vv[1], vv[2], vv[3]));
-                if (p.ad_shadow) {
-                    bf16x4 o = {(bf16_t)pp[0], (bf16_t)pp[1], (bf16_t)pp[2], (bf16_t)pp[3]};
-                    __builtin_nontemporal_store(o, reinterpret_cast<bf16x4*>(p.ad_shadow + wi));
-                }
+                f32x4 np = {qp[bf].x, qp[bf].y, qp[bf].z, qp[bf].w}, nm = {qm[bf].x, qm[bf].y, qm[bf].z, qm[bf].w}, nv = {qv[bf].x, qv[bf].y, qv[bf].z, qv[bf].w};
+                const bf16x4 o = adamw_quad(np, nm, nv, g, p.ad);
+                __builtin_nontemporal_store(np, reinterpret_cast<f32x4*>(p.ad_p + wi));
+                __builtin_nontemporal_store(nm, reinterpret_cast<f32x4*>(p.ad_m + wi));
+                __builtin_nontemporal_store(nv, reinterpret_cast<f32x4*>(p.ad_v + wi));
+                if (p.ad_shadow) __builtin_nontemporal_store(o, reinterpret_cast<bf16x4*>(p.ad_shadow + wi));
             } else {
                 nt_st4(Cf + wi, make_float4(g[0], g[1], g[2], g[3]));
             }
@@ -777,30 +754,19 @@ __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC&
         }
         if (mse) {
             float t[8];
-            if (p.mse_target_dtype == AFR_TARGET_U8) {
-                const uint2 w = tu8[ps];
-                if (lut255) {                          // k / 255.0f looked up (the block computed the 256 quotients once): same values
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { t[r] = lut255[(w.x >> (8 * r)) & 0xFF]; t[4 + r] = lut255[(w.y >> (8 * r)) & 0xFF]; }
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { t[r] = (float)((w.x >> (8 * r)) & 0xFF) / 255.0f; t[4 + r] = (float)((w.y >> (8 * r)) & 0xFF) / 255.0f; }
-                }
+            if (p.loss.tdtype == AFR_TARGET_U8) {
+                if (lut255) targets_u8x8<true>(tu8[ps], lut255, t);
+                else targets_u8x8<false>(tu8[ps], nullptr, t);
             } else {
-                const size_t ti = (size_t)(TROWS ? p.mse_rowmap[m] : m) * p.N + n;
-                const float4 w0 = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.mse_target) + ti);
-                const float4 w1 = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.mse_target) + ti + 4);
+                const size_t ti = (size_t)loss_target_row<TROWS>(p.loss, m) * p.N + n;
+                const float4 w0 = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.loss.target) + ti);
+                const float4 w1 = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.loss.target) + ti + 4);
                 t[0] = w0.x; t[1] = w0.y; t[2] = w0.z; t[3] = w0.w; t[4] = w1.x; t[5] = w1.y; t[6] = w1.z; t[7] = w1.w;
             }
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
                 const float u = out_bf16 ? (float)(bf16_t)v[r] : v[r];     // the value the unfused path would store
-                if constexpr (LOSS == LOSS_BCE) lsum += bce_logits_elem(u, t[r], p.mse_inv_n, v[r]);
-                else {
-                    const float diff = fminf(fmaxf(u, 0.f), 1.f) - t[r];
-                    lsum += diff * diff;
-                    v[r] = (u >= 0.f && u <= 1.f) ? g2 * diff : 0.f;
-                }
+                lsum += loss_elem<LOSS>(u, t[r], p.loss.inv_n, g2, v[r]);
             }
         }
         {
@@ -874,16 +840,12 @@ __device__ __forceinline__ void strip_finish(const GemmParams& p, const f32x4 (&
             float4 qp, qm, qv;
             if (pre) { qp = pmv[(3 * ps + 0) * 64]; qm = pmv[(3 * ps + 1) * 64]; qv = pmv[(3 * ps + 2) * 64]; }
             else { qp = ADLD(p.ad_p + wi); qm = ADLD(p.ad_m + wi); qv = ADLD(p.ad_v + wi); }
-            float pp[4] = {qp.x, qp.y, qp.z, qp.w}, mm[4] = {qm.x, qm.y, qm.z, qm.w}, vv[4] = {qv.x, qv.y, qv.z, qv.w};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) adamw_elem(pp[r], mm[r], vv[r], g[r], p.ad_decay, p.ad_b1, p.ad_b2, p.ad_eps, p.ad_step, p.ad_rsqrt_bc2);
-            ADST(p.ad_p + wi, make_float4(pp[0], pp[1], pp[2], pp[3]));
-            ADST(p.ad_m + wi, make_float4(mm[0], mm[1], mm[2], mm[3]));
-            ADST(p.ad_v + wi, make_float4(vv[0], vv[1], vv[2], vv[3]));
-            if (p.ad_shadow) {
-                bf16x4 o = {(bf16_t)pp[0], (bf16_t)pp[1], (bf16_t)pp[2], (bf16_t)pp[3]};
-                __builtin_nontemporal_store(o, reinterpret_cast<bf16x4*>(p.ad_shadow + wi));
-            }
+            f32x4 np = {qp.x, qp.y, qp.z, qp.w}, nm = {qm.x, qm.y, qm.z, qm.w}, nv = {qv.x, qv.y, qv.z, qv.w};
+            const bf16x4 o = adamw_quad(np, nm, nv, g, p.ad);
+            __builtin_nontemporal_store(np, reinterpret_cast<f32x4*>(p.ad_p + wi));
+            __builtin_nontemporal_store(nm, reinterpret_cast<f32x4*>(p.ad_m + wi));
+            __builtin_nontemporal_store(nv, reinterpret_cast<f32x4*>(p.ad_v + wi));
+            if (p.ad_shadow) __builtin_nontemporal_store(o, reinterpret_cast<bf16x4*>(p.ad_shadow + wi));
         } else {
             nt_st4(Cf + wi, make_float4(g[0], g[1], g[2], g[3]));
         }
@@ -896,7 +858,7 @@ template <int WM> struct RingGeom {
 // One output tile (and k-split) of one product: block `bid` of the `nblk` blocks that product was given.  A plain launch
 // passes its own blockIdx / gridDim; a grouped launch (gemm_bf16_group) a sub-range of its grid.
 // GA: the k-contiguous A operand's rows are gathered through p.a_rowmap (ALAY == 0, WM == 4 only)
-// TROWS: the fused loss reads its targets through p.mse_rowmap (forward layout only)
+// TROWS: the fused loss reads its targets through p.loss.rowmap (forward layout only)
 template <int ALAY, int BLAY, int WM, int GA = 0, bool TROWS = false, int LOSS = LOSS_MSE>
 __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p, const int bid, const int nblk, char* smem) {
     static_assert(!GA || (ALAY == 0 && WM == 4), "row gather: k-contiguous A on the 256x128 ring kernel");
@@ -923,9 +885,8 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p, const int bi
     tile_of_block(p, BM, BN, bid, nblk, tm, tn, z);
     if (z >= p.splitk) return;                       // padding block of a grouped launch (ranges are rounded up to 8)
     const int m0 = tm * BM, n0 = tn * BN;
-    const int klen = ((p.K + p.splitk - 1) / p.splitk + BK - 1) / BK * BK;
-    const int kbeg = z * klen;
-    const int kend = min(p.K, kbeg + klen);
+    int kbeg, kend;
+    k_range<BK>(p.K, p.splitk, z, kbeg, kend);
     const bf16_t* A = reinterpret_cast<const bf16_t*>(p.A);
     const bf16_t* B = reinterpret_cast<const bf16_t*>(p.B);
 
@@ -1180,12 +1141,12 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p, const int bi
         }
         __syncthreads();                       // the staging below reuses this LDS
     }
-    const bool mse = p.mse_target != nullptr;
+    const bool mse = p.loss.target != nullptr;
     float lsum = 0.f;
     // uint8 targets of the fused loss are pixel / 255.0f (helpers.py:121): 256 true divisions per block instead of one per
     // output element (the 8-wave kernel's LDS has room behind the waves' staging tiles)
     const float* lut255 = nullptr;
-    if (WM == 4 && mse && p.mse_target_dtype == AFR_TARGET_U8) {
+    if (WM == 4 && mse && p.loss.tdtype == AFR_TARGET_U8) {
         float* l = reinterpret_cast<float*>(smem) + NW * 4096;
         if (tid < 256) l[tid] = (float)tid / 255.0f;
         __syncthreads();
@@ -1201,7 +1162,7 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p, const int bi
         float bs = 0.f;
 #pragma unroll
         for (int w = 0; w < NW; ++w) bs += red[w];
-        loss_block_finish(bs, p.mse_partial, p.mse_counter, p.mse_loss_accum, p.mse_inv_n, red + 16);
+        loss_block_finish(bs, p.loss.partial, p.loss.counter, p.loss.loss_accum, p.loss.inv_n, red + 16);
     }
 #ifdef AFR_GEMM_TIMING
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1279,9 +1240,8 @@ __device__ __forceinline__ void gemm_bf16_256_body(const GemmParams& p, const in
     }
 #endif
     const int m0 = tm * BM, n0 = tn * BNN;
-    const int klen = ((p.K + ksplit - 1) / ksplit + BK - 1) / BK * BK;
-    const int kbeg = z * klen;
-    const int kend = min(p.K, kbeg + klen);
+    int kbeg, kend;
+    k_range<BK>(p.K, ksplit, z, kbeg, kend);
     const int nt = (kend > kbeg) ? (kend - kbeg + BK - 1) / BK : 0;
     const i32x4 rA = make_rsrc(p.A), rB = make_rsrc(p.B);
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
@@ -1617,32 +1577,32 @@ __global__ __launch_bounds__(128 * WM, 2) void gemm_bf16(GemmParams p) {
 // other CUs are still in their epilogues.  Products with a fused loss epilogue cannot be grouped (its arrival counter
 // counts the blocks of ONE launch).
 struct GemmGroup { int n; int blk0[5]; GemmParams p[4]; };
-__global__ __launch_bounds__(512, 2) void gemm_bf16_group(GemmGroup g) {
-    __shared__ __attribute__((aligned(16))) char smem[RingGeom<4>::LDS_BYTES];
+// block -> (its product, its place among that product's blocks, the operand layouts as compile-time tags)
+template <class F>
+__device__ __forceinline__ void group_member(const GemmGroup& g, F&& body) {
     const int b = blockIdx.x;
     int i = 0;
     while (i + 1 < g.n && b >= g.blk0[i + 1]) ++i;
     const GemmParams& p = g.p[i];
     const int bid = b - g.blk0[i], nblk = g.blk0[i + 1] - g.blk0[i];
     const int lay = ((p.flags & AFR_GEMM_A_KSTRIDED) ? 2 : 0) | ((p.flags & AFR_GEMM_B_KSTRIDED) ? 1 : 0);
-    if (lay == 3) gemm_bf16_body<1, 1, 4>(p, bid, nblk, smem);
-    else if (lay == 1) gemm_bf16_body<0, 1, 4>(p, bid, nblk, smem);
-    else if (lay == 0) gemm_bf16_body<0, 0, 4>(p, bid, nblk, smem);
-    else gemm_bf16_body<1, 0, 4>(p, bid, nblk, smem);
+    if (lay == 3) body(p, bid, nblk, std::true_type{}, std::true_type{});
+    else if (lay == 1) body(p, bid, nblk, std::false_type{}, std::true_type{});
+    else if (lay == 0) body(p, bid, nblk, std::false_type{}, std::false_type{});
+    else body(p, bid, nblk, std::true_type{}, std::false_type{});
+}
+__global__ __launch_bounds__(512, 2) void gemm_bf16_group(GemmGroup g) {
+    __shared__ __attribute__((aligned(16))) char smem[RingGeom<4>::LDS_BYTES];
+    group_member(g, [&](const GemmParams& p, int bid, int nblk, auto a, auto b) { gemm_bf16_body<a(), b(), 4>(p, bid, nblk, smem); });
 }
 __global__ __launch_bounds__(512, 2) void gemm_bf16_group256(GemmGroup g) {
     __shared__ __attribute__((aligned(16))) char smem[10 * SUB];   // all 160 KiB: A ring 3 x 32 KiB + B ring 2 x 32 KiB
-    const int b = blockIdx.x;
-    int i = 0;
-    while (i + 1 < g.n && b >= g.blk0[i + 1]) ++i;
-    const GemmParams& p = g.p[i];
-    const int bid = b - g.blk0[i], nblk = g.blk0[i + 1] - g.blk0[i];
-    const int lay = ((p.flags & AFR_GEMM_A_KSTRIDED) ? 2 : 0) | ((p.flags & AFR_GEMM_B_KSTRIDED) ? 1 : 0);
-    if (lay == 3 && p.b_rowmap) gemm_bf16_256_body<1, 1, 1>(p, bid, nblk, smem);
-    else if (lay == 3) gemm_bf16_256_body<1, 1>(p, bid, nblk, smem);
-    else if (lay == 1) gemm_bf16_256_body<0, 1>(p, bid, nblk, smem);
-    else if (lay == 0) gemm_bf16_256_body<0, 0>(p, bid, nblk, smem);
-    else gemm_bf16_256_body<1, 0>(p, bid, nblk, smem);
+    group_member(g, [&](const GemmParams& p, int bid, int nblk, auto a, auto b) {
+        if constexpr (a() && b()) {                                // gathered B rows: weight gradients only
+            if (p.b_rowmap) { gemm_bf16_256_body<1, 1, 1>(p, bid, nblk, smem); return; }
+        }
+        gemm_bf16_256_body<a(), b()>(p, bid, nblk, smem);
+    });
 }
 
 // ------------------------------------------------------------ folded first layer of the glyph nets: backward in ONE kernel
@@ -1928,7 +1888,7 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8(GemmParams p) {
 hipError_t afr_launch_gemm_fp8(const GemmParams& p, hipStream_t s) {
     if (p.M <= 0 || p.N <= 0) return hipSuccess;
     if ((p.flags & (AFR_GEMM_A_KSTRIDED | AFR_GEMM_B_KSTRIDED)) || p.splitk != 1 || (p.K & 15) || (p.lda & 15) || (p.ldb & 15) ||
-        p.mse_target || p.ad_p || p.colsum || (p.flags & AFR_GEMM_RELU_MASK)) return hipErrorInvalidValue;
+        p.loss.target || p.ad_p || p.colsum || (p.flags & AFR_GEMM_RELU_MASK)) return hipErrorInvalidValue;
     const int tiles = ((p.M + 255) / 256) * ((p.N + 127) / 128);
     hipLaunchKernelGGL(fp8k::gemm_fp8, dim3(tiles), dim3(512), 0, s, p);
     return hipGetLastError();
@@ -1960,7 +1920,7 @@ static bool bf16_use_wide(const GemmParams& p) {
 // chip, so that the ragged last round is small change.  Measured on the pixel transformer's products (131072 rows): 8-20 %
 // faster than the 256x128 ring (K = 512: 466 -> 390 us forward, 104 -> 87 us input gradient; K = 2048: 322 -> 266 us).
 static bool bf16_use_body256(const GemmParams& p) {
-    if (p.mse_target || p.ad_p || p.a_rowmap || p.b_rowmap || p.coop_ws || p.fix_ws) return false;
+    if (p.loss.target || p.ad_p || p.a_rowmap || p.b_rowmap || p.coop_ws || p.fix_ws) return false;
     const long long t = (long long)((p.M + 255) / 256) * ((p.N + 255) / 256);
     // weight gradients (both operands k-strided, split-K slabs): when the slices of the 256x256 tiles make whole rounds of the chip
     const bool kk = (p.flags & AFR_GEMM_A_KSTRIDED) && (p.flags & AFR_GEMM_B_KSTRIDED);
@@ -1987,7 +1947,7 @@ const char* afr_gemm_kernel_name(int dtype, const GemmParams& p) {
 }
 // true when the product would run on the 256x128 ring kernel by itself (what a grouped launch is built from)
 bool afr_gemm_groupable(int dtype, const GemmParams& p) {
-    return dtype == AFR_BF16 && p.M > 0 && p.N > 0 && !p.mse_target && (!p.ad_p || p.coop_ws) && p.K / p.splitk >= 256;
+    return dtype == AFR_BF16 && p.M > 0 && p.N > 0 && !p.loss.target && (!p.ad_p || p.coop_ws) && p.K / p.splitk >= 256;
 }
 // How a layer's gradient pair (dX: B x K_in over N_out; dW: N_out x K_in over the batch) is launched: with 256x256 tiles
 // when those fill most of the chip in ONE round (dW split so that its blocks run as many K-tiles as dX's), else with
@@ -2067,67 +2027,35 @@ hipError_t afr_launch_gemm(int dtype, const GemmParams& p_in, hipStream_t s) {
 #endif
     const int a = (p.flags & AFR_GEMM_A_KSTRIDED) ? 1 : 0, b = (p.flags & AFR_GEMM_B_KSTRIDED) ? 1 : 0;
     if (p.M <= 0 || p.N <= 0) return hipSuccess;
-    if (p.loss_kind != LOSS_MSE && p.loss_kind != LOSS_BCE) return hipErrorInvalidValue;
+    if (p.loss.kind != LOSS_MSE && p.loss.kind != LOSS_BCE) return hipErrorInvalidValue;
     // a fused BCE loss: the forward layout of the ring / tile kernels, one instantiation per (row map, kernel)
-    const bool bce = p.loss_kind == LOSS_BCE && p.mse_target;
+    const bool bce = p.loss.kind == LOSS_BCE && p.loss.target, trows = p.loss.rowmap != nullptr;
     if (bce && (a || b || p.a_rowmap || p.splitk != 1)) return hipErrorInvalidValue;      // (a gathered A has its own kernel, without this loss)
     // row-mapped loss targets: the forward layout of the ring / tile kernels, its own instantiations
-    if (p.mse_rowmap && (!p.mse_target || a || b || p.a_rowmap || p.splitk != 1 || (dtype == AFR_BF16 && bf16_use_body256(p)))) return hipErrorInvalidValue;
+    if (trows && (!p.loss.target || a || b || p.a_rowmap || p.splitk != 1 || (dtype == AFR_BF16 && bf16_use_body256(p)))) return hipErrorInvalidValue;
     if (p.a_rowmap || p.b_rowmap || p.aux_rowmap) {
         // row gathers: A k-contiguous on the 256x128 ring kernel; aux with a bf16 output (B: grouped 256x256 launches only)
         if (dtype != AFR_BF16 || p.b_rowmap || (p.a_rowmap && (a || b || !bf16_use_wide(p))) ||
             (p.aux_rowmap && !(p.flags & AFR_GEMM_OUT_BF16))) return hipErrorInvalidValue;
     }
-    if (dtype == AFR_BF16) {
-        if (bf16_use_body256(p)) return launch_grouped(&p, 1, true, false, s);
-        const bool wide = bf16_use_wide(p);
-        const int bm = wide ? 256 : 128;
-        const int tiles = ((p.M + bm - 1) / bm) * ((p.N + 127) / 128);
-        dim3 grid(tiles * p.splitk, 1, 1);
-#define LB(AL, BL) do { if (wide) hipLaunchKernelGGL((bf16k::gemm_bf16<AL, BL, 4>), grid, dim3(512), 0, s, p); \
-                        else hipLaunchKernelGGL((bf16k::gemm_bf16<AL, BL, 2>), grid, dim3(256), 0, s, p); } while (0)
-        if (p.a_rowmap) hipLaunchKernelGGL((bf16k::gemm_bf16<0, 0, 4, 1>), grid, dim3(512), 0, s, p);
-        else if (bce) {
-            if (p.mse_rowmap) {
-                if (wide) hipLaunchKernelGGL((bf16k::gemm_bf16<0, 0, 4, 0, true, LOSS_BCE>), grid, dim3(512), 0, s, p);
-                else hipLaunchKernelGGL((bf16k::gemm_bf16<0, 0, 2, 0, true, LOSS_BCE>), grid, dim3(256), 0, s, p);
-            } else if (wide) hipLaunchKernelGGL((bf16k::gemm_bf16<0, 0, 4, 0, false, LOSS_BCE>), grid, dim3(512), 0, s, p);
-            else hipLaunchKernelGGL((bf16k::gemm_bf16<0, 0, 2, 0, false, LOSS_BCE>), grid, dim3(256), 0, s, p);
-        }
-        else if (p.mse_rowmap) {
-            if (wide) hipLaunchKernelGGL((bf16k::gemm_bf16<0, 0, 4, 0, true>), grid, dim3(512), 0, s, p);
-            else hipLaunchKernelGGL((bf16k::gemm_bf16<0, 0, 2, 0, true>), grid, dim3(256), 0, s, p);
-        }
-        else if (!a && !b) LB(0, 0);
-        else if (!a && b) LB(0, 1);
-        else if (a && !b) LB(1, 0);
-        else LB(1, 1);
-#undef LB
-    } else if (dtype == AFR_BF16X3) {
-        const int tiles = ((p.M + x3k::BM - 1) / x3k::BM) * ((p.N + x3k::BN - 1) / x3k::BN);
-        dim3 grid(tiles * p.splitk, 1, 1), block(256, 1, 1);
-#define LX(AL, BL) hipLaunchKernelGGL((x3k::gemm_bf16x3<AL, BL>), grid, block, 0, s, p)
-        if (bce && p.mse_rowmap) hipLaunchKernelGGL((x3k::gemm_bf16x3<0, 0, true, LOSS_BCE>), grid, block, 0, s, p);
-        else if (bce) hipLaunchKernelGGL((x3k::gemm_bf16x3<0, 0, false, LOSS_BCE>), grid, block, 0, s, p);
-        else if (p.mse_rowmap) hipLaunchKernelGGL((x3k::gemm_bf16x3<0, 0, true>), grid, block, 0, s, p);
-        else if (!a && !b) LX(0, 0);
-        else if (!a && b) LX(0, 1);
-        else if (a && !b) LX(1, 0);
-        else LX(1, 1);
-#undef LX
-    } else {
-        const int tiles = ((p.M + 127) / 128) * ((p.N + 127) / 128);
-        dim3 grid(tiles * p.splitk, 1, 1), block(256, 1, 1);
-#define LF(AL, BL) hipLaunchKernelGGL((f32k::gemm_f32<AL, BL>), grid, block, 0, s, p)
-        if (bce && p.mse_rowmap) hipLaunchKernelGGL((f32k::gemm_f32<0, 0, true, LOSS_BCE>), grid, block, 0, s, p);
-        else if (bce) hipLaunchKernelGGL((f32k::gemm_f32<0, 0, false, LOSS_BCE>), grid, block, 0, s, p);
-        else if (p.mse_rowmap) hipLaunchKernelGGL((f32k::gemm_f32<0, 0, true>), grid, block, 0, s, p);
-        else if (!a && !b) LF(0, 0);
-        else if (!a && b) LF(0, 1);
-        else if (a && !b) LF(1, 0);
-        else LF(1, 1);
-#undef LF
-    }
+    if (dtype == AFR_BF16 && bf16_use_body256(p)) return launch_grouped(&p, 1, true, false, s);
+    const bool wide = dtype == AFR_BF16 && bf16_use_wide(p);
+    const int tiles = ((p.M + (wide ? 255 : 127)) / (wide ? 256 : 128)) * ((p.N + 127) / 128);      // (f32k and x3k: 128 x 128 as well)
+    auto launch = [&](auto kernel, int threads) { hipLaunchKernelGGL(kernel, dim3(tiles * p.splitk), dim3(threads), 0, s, p); };
+    // The kernels that exist: the four operand layouts, and for the forward layout (row-mapped targets) x (loss kind) -- never
+    // their cross product (static_asserts in gemm_bf16_body).  al, bl, tr, loss arrive as tags.
+    auto variant = [&](auto al, auto bl, auto tr, auto loss) {
+        if (dtype == AFR_BF16) {
+            if (wide) launch(bf16k::gemm_bf16<al(), bl(), 4, 0, tr(), loss()>, 512);
+            else launch(bf16k::gemm_bf16<al(), bl(), 2, 0, tr(), loss()>, 256);
+        } else if (dtype == AFR_BF16X3) launch(x3k::gemm_bf16x3<al(), bl(), tr(), loss()>, 256);
+        else launch(f32k::gemm_f32<al(), bl(), tr(), loss()>, 256);
+    };
+    if (p.a_rowmap) launch(bf16k::gemm_bf16<0, 0, 4, 1>, 512);
+    else if (bce || trows)
+        with_bool(trows, [&](auto tr) { with_loss(bce ? LOSS_BCE : LOSS_MSE, [&](auto loss) { variant(std::false_type{}, std::false_type{}, tr, loss); }); });
+    else
+        with_bool(a, [&](auto al) { with_bool(b, [&](auto bl) { variant(al, bl, std::false_type{}, std::integral_constant<int, LOSS_MSE>{}); }); });
     return hipGetLastError();
 }
 

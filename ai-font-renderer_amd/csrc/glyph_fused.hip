@@ -196,7 +196,7 @@ __global__ __launch_bounds__(MM<T>::NTH) void glyph1_step_kernel(Glyph1Args a) {
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) trow[m][i] = a.rowmap[b0 + min(m * 16 + 4 * q + i, nb - 1)];
+            for (int i = 0; i < 4; ++i) trow[m][i] = a.loss.rowmap[b0 + min(m * 16 + 4 * q + i, nb - 1)];
     }
 #pragma unroll
     for (int it = 0; it < TPW; ++it) {
@@ -209,8 +209,8 @@ __global__ __launch_bounds__(MM<T>::NTH) void glyph1_step_kernel(Glyph1Args a) {
                     size_t ti;
                     if constexpr (TROWS) ti = (size_t)trow[m][i] * P + pcol;
                     else ti = (size_t)(b0 + min(m * 16 + 4 * q + i, nb - 1)) * P + pcol;
-                    if constexpr (TU8) tv[it][m][i] = __builtin_bit_cast(float, (unsigned)reinterpret_cast<const uint8_t*>(a.target)[ti]);
-                    else tv[it][m][i] = reinterpret_cast<const float*>(a.target)[ti];
+                    if constexpr (TU8) tv[it][m][i] = __builtin_bit_cast(float, (unsigned)reinterpret_cast<const uint8_t*>(a.loss.target)[ti]);
+                    else tv[it][m][i] = reinterpret_cast<const float*>(a.loss.target)[ti];
                 }
         }
     }
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(MM<T>::NTH) void glyph1_step_kernel(Glyph1Args a) {
 
     // ---- u = h1 . W2^T + b2 ; clamp, MSE, du (rows past the batch contribute nothing)
     float lsum = 0.f;
-    const float g2 = 2.f * a.inv_n;
+    const float g2 = 2.f * a.loss.inv_n;
     rows_times_global_u<T, MT, NW, TPW>(h1, ldN, npt, N1 / KB, wave, r, q, loadW2o,
         [&](int nt, int) { bias_v = a.b2[(pt0 + nt) * 16 + r]; },
         [&](int nt, int it, const f32x4 (&acc)[MT]) {
@@ -287,16 +287,10 @@ __global__ __launch_bounds__(MM<T>::NTH) void glyph1_step_kernel(Glyph1Args a) {
                     if constexpr (sizeof(T) == 2) u = (float)(bf16_t)u;          // the value the unfused path stores
                     const float t = TU8 ? lut[__builtin_bit_cast(unsigned, tv[it][m][i])] : tv[it][m][i];
                     const bool live = row < nb;
-                    if constexpr (LOSS == LOSS_BCE) {
-                        float d;
-                        const float l = bce_logits_elem(u, t, a.inv_n, d);
-                        lsum += live ? l : 0.f;
-                        v[i] = live ? d : 0.f;
-                    } else {
-                        const float diff = fminf(fmaxf(u, 0.f), 1.f) - t;
-                        lsum += live ? diff * diff : 0.f;
-                        v[i] = (live && u >= 0.f && u <= 1.f) ? g2 * diff : 0.f;
-                    }
+                    float d;
+                    const float l = loss_elem<LOSS>(u, t, a.loss.inv_n, g2, d);
+                    lsum += live ? l : 0.f;
+                    v[i] = live ? d : 0.f;
                 }
                 put_both(du, ldP, duT, ldR, m * 16, (pt0 + nt) * 16, v);
             }
@@ -415,7 +409,7 @@ __global__ __launch_bounds__(MM<T>::NTH) void glyph1_step_kernel(Glyph1Args a) {
     float bsum = 0.f;
 #pragma unroll
     for (int w = 0; w < NW; ++w) bsum += red[w];
-    loss_block_finish(bsum, a.loss_partial, a.counter, a.loss_accum, a.inv_n, red + 16);
+    loss_block_finish(bsum, a.loss.partial, a.loss.counter, a.loss.loss_accum, a.loss.inv_n, red + 16);
 }
 
 // W [N][K] f32 -> WT [K][N] bf16 (the transposed operand copies of the bf16 fused step)
@@ -481,11 +475,9 @@ hipError_t afr_launch_glyph1_step(int dtype, const Glyph1Args& a, hipStream_t s)
     if (e != hipSuccess) return e;
     if (a.cs < 1 || (a.P / 16) % a.cs) return hipErrorInvalidValue;
     const int nblk = (a.B + R - 1) / R * a.cs;
-    const bool u8 = a.tdtype == AFR_TARGET_U8, rows = a.rowmap != nullptr;
-#define G1(T, U8, RW) (a.loss_kind == LOSS_BCE ? launch_glyph1<T, U8, RW, LOSS_BCE>(a, nblk, lds, dev, s) : launch_glyph1<T, U8, RW, LOSS_MSE>(a, nblk, lds, dev, s))
-    if (dtype == AFR_BF16) e = u8 ? (rows ? G1(bf16_t, true, true) : G1(bf16_t, true, false)) : (rows ? G1(bf16_t, false, true) : G1(bf16_t, false, false));
-    else e = u8 ? (rows ? G1(float, true, true) : G1(float, true, false)) : (rows ? G1(float, false, true) : G1(float, false, false));
-#undef G1
+    e = with_act(dtype == AFR_BF16, [&](auto t) { return with_bool(a.loss.tdtype == AFR_TARGET_U8, [&](auto u8) { return with_bool(a.loss.rowmap != nullptr, [&](auto tr) {
+        return with_loss(a.loss.kind, [&](auto loss) { return launch_glyph1<typename decltype(t)::type, u8(), tr(), loss()>(a, nblk, lds, dev, s); });
+    }); }); });
     if (e != hipSuccess) return e;
     return hipGetLastError();
 }

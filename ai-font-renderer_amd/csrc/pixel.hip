@@ -198,40 +198,40 @@ __global__ __launch_bounds__(256) void pixel_head_kernel(const float* __restrict
 }
 
 static inline int pix_grid(long long rows) { long long g = (rows + 3) / 4; return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g)); }
-#define PIX_DISPATCH(KERNEL, GRID, ...)                                                                        \
-    do {                                                                                                       \
-        if (act_dtype == AFR_BF16) hipLaunchKernelGGL((KERNEL<bf16_t>), dim3(GRID), dim3(256), 0, s, __VA_ARGS__); \
-        else hipLaunchKernelGGL((KERNEL<float>), dim3(GRID), dim3(256), 0, s, __VA_ARGS__);                    \
-    } while (0)
 hipError_t afr_launch_pixel_ctx(int act_dtype, const float* emb, const float* femb, const int64_t* x, const int64_t* font, int B, int d,
                                 int vocab, int n_fonts, void* ctx, uint32_t* err, hipStream_t s) {
     const long long n = (long long)B * (n_fonts > 0 ? 2 : 1) * d;
     const int grid = (int)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256);
-    if (act_dtype == AFR_BF16) hipLaunchKernelGGL(pixel_ctx_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, emb, femb, x, font, B, d, vocab, n_fonts, (bf16_t*)ctx, err);
-    else hipLaunchKernelGGL(pixel_ctx_kernel<float>, dim3(grid), dim3(256), 0, s, emb, femb, x, font, B, d, vocab, n_fonts, (float*)ctx, err);
+    with_act(act_dtype == AFR_BF16, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(pixel_ctx_kernel<T>, dim3(grid), dim3(256), 0, s, emb, femb, x, font, B, d, vocab, n_fonts, (T*)ctx, err);
+    });
     return hipGetLastError();
 }
 hipError_t afr_launch_pixel_add_ln(int act_dtype, const float* hin, float* h, const float* pos, const void* add, const float* g, const float* b, void* n,
                                    long long rows, int Tk, int d, float eps, hipStream_t s) {
     if (d > 512 || (d & 7)) return hipErrorInvalidValue;
-    if (act_dtype == AFR_BF16) hipLaunchKernelGGL(pixel_add_ln_kernel<bf16_t>, dim3(pix_grid(rows)), dim3(256), 0, s, hin, h, pos, (const bf16_t*)add, g, b, (bf16_t*)n, rows, Tk, d, eps);
-    else hipLaunchKernelGGL(pixel_add_ln_kernel<float>, dim3(pix_grid(rows)), dim3(256), 0, s, hin, h, pos, (const float*)add, g, b, (float*)n, rows, Tk, d, eps);
+    with_act(act_dtype == AFR_BF16, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(pixel_add_ln_kernel<T>, dim3(pix_grid(rows)), dim3(256), 0, s, hin, h, pos, (const T*)add, g, b, (T*)n, rows, Tk, d, eps);
+    });
     return hipGetLastError();
 }
 hipError_t afr_launch_pixel_attn(int act_dtype, const void* q, const void* kv, void* o, long long rows, int Tk, int d, int heads, int C, hipStream_t s) {
     if (d > 512 || d != heads * 64 || C < 1 || C > 2) return hipErrorInvalidValue;       // 8 lanes x 8 channels per head
-    if (act_dtype == AFR_BF16) hipLaunchKernelGGL(pixel_attn_kernel<bf16_t>, dim3(pix_grid(rows)), dim3(256), 0, s, (const bf16_t*)q, (const bf16_t*)kv, (bf16_t*)o, rows, Tk, d, C);
-    else hipLaunchKernelGGL(pixel_attn_kernel<float>, dim3(pix_grid(rows)), dim3(256), 0, s, (const float*)q, (const float*)kv, (float*)o, rows, Tk, d, C);
+    with_act(act_dtype == AFR_BF16, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(pixel_attn_kernel<T>, dim3(pix_grid(rows)), dim3(256), 0, s, (const T*)q, (const T*)kv, (T*)o, rows, Tk, d, C);
+    });
     return hipGetLastError();
 }
 hipError_t afr_launch_pixel_head(int act_dtype, const float* hin, float* h, const void* add, const float* g, const float* b, const float* w_out, const float* b_out,
                                  float* u, float* y, long long rows, int d, float eps, hipStream_t s, int loss_kind) {
     if (d > 512 || (d & 7)) return hipErrorInvalidValue;
-    if (loss_kind == LOSS_BCE) {
-        if (act_dtype == AFR_BF16) hipLaunchKernelGGL((pixel_head_kernel<bf16_t, LOSS_BCE>), dim3(pix_grid(rows)), dim3(256), 0, s, hin, h, (const bf16_t*)add, g, b, w_out, b_out, u, y, rows, d, eps);
-        else hipLaunchKernelGGL((pixel_head_kernel<float, LOSS_BCE>), dim3(pix_grid(rows)), dim3(256), 0, s, hin, h, (const float*)add, g, b, w_out, b_out, u, y, rows, d, eps);
-    } else if (act_dtype == AFR_BF16) hipLaunchKernelGGL(pixel_head_kernel<bf16_t>, dim3(pix_grid(rows)), dim3(256), 0, s, hin, h, (const bf16_t*)add, g, b, w_out, b_out, u, y, rows, d, eps);
-    else hipLaunchKernelGGL(pixel_head_kernel<float>, dim3(pix_grid(rows)), dim3(256), 0, s, hin, h, (const float*)add, g, b, w_out, b_out, u, y, rows, d, eps);
+    with_act(act_dtype == AFR_BF16, [&](auto t) { with_loss(loss_kind, [&](auto loss) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((pixel_head_kernel<T, loss()>), dim3(pix_grid(rows)), dim3(256), 0, s, hin, h, (const T*)add, g, b, w_out, b_out, u, y, rows, d, eps);
+    }); });
     return hipGetLastError();
 }
 
@@ -492,8 +492,10 @@ int afr_pixel_attn_chunk(int Tk) { return Tk <= 256 ? Tk : 256; }
 hipError_t afr_launch_pixel_attn_bwd(int act_dtype, const void* dO, const void* q, const void* kv, void* dq, float* dkv_part, int B, int Tk, int d, int C,
                                      hipStream_t s) {
     const int chunk = afr_pixel_attn_chunk(Tk), chunks = (Tk + chunk - 1) / chunk;
-    if (act_dtype == AFR_BF16) hipLaunchKernelGGL(pixel_attn_bwd_kernel<bf16_t>, dim3(B * chunks), dim3(PIX_BWD_THREADS), 0, s, (const bf16_t*)dO, (const bf16_t*)q, (const bf16_t*)kv, (bf16_t*)dq, dkv_part, Tk, chunk, d, C);
-    else hipLaunchKernelGGL(pixel_attn_bwd_kernel<float>, dim3(B * chunks), dim3(PIX_BWD_THREADS), 0, s, (const float*)dO, (const float*)q, (const float*)kv, (float*)dq, dkv_part, Tk, chunk, d, C);
+    with_act(act_dtype == AFR_BF16, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(pixel_attn_bwd_kernel<T>, dim3(B * chunks), dim3(PIX_BWD_THREADS), 0, s, (const T*)dO, (const T*)q, (const T*)kv, (T*)dq, dkv_part, Tk, chunk, d, C);
+    });
     return hipGetLastError();
 }
 hipError_t afr_launch_pixel_ctx_bwd(const float* dctx, const int64_t* x, const int64_t* font, int B, int d, int vocab, int n_fonts, float* demb, float* dfont,
@@ -503,14 +505,18 @@ hipError_t afr_launch_pixel_ctx_bwd(const float* dctx, const int64_t* x, const i
 }
 hipError_t afr_launch_pixel_accum(int act_dtype, float* acc, const void* src, long long n, int first, hipStream_t s) {
     const int grid = (int)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256);
-    if (act_dtype == AFR_BF16) hipLaunchKernelGGL(pixel_accum_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, acc, (const bf16_t*)src, n, first);
-    else hipLaunchKernelGGL(pixel_accum_kernel<float>, dim3(grid), dim3(256), 0, s, acc, (const float*)src, n, first);
+    with_act(act_dtype == AFR_BF16, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(pixel_accum_kernel<T>, dim3(grid), dim3(256), 0, s, acc, (const T*)src, n, first);
+    });
     return hipGetLastError();
 }
 hipError_t afr_launch_pixel_cast(int act_dtype, void* dst, const float* src, long long rows, int w, int ld_src, hipStream_t s) {
     const long long n = rows * w;
     const int grid = (int)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256);
-    if (act_dtype == AFR_BF16) hipLaunchKernelGGL(pixel_cast_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (bf16_t*)dst, src, rows, w, ld_src);
-    else hipLaunchKernelGGL(pixel_cast_kernel<float>, dim3(grid), dim3(256), 0, s, (float*)dst, src, rows, w, ld_src);
+    with_act(act_dtype == AFR_BF16, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(pixel_cast_kernel<T>, dim3(grid), dim3(256), 0, s, (T*)dst, src, rows, w, ld_src);
+    });
     return hipGetLastError();
 }
