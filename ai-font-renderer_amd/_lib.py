@@ -62,6 +62,8 @@ SIGNATURES = {
     "afr_backward_stage": (_i32, [_vp, _i32, C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "afr_forward_loss": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _u64, _vp]),
     "afr_adamw_step": (_i32, [_vp, _f32, _f32, _f32, _f32, _f32, _i64, _f32, _vp]),
+    "afr_set_grad_clip": (_i32, [_vp, _f32, _vp]),
+    "afr_grad_sumsq": (_i32, [_vp, _i64, _i64, _vp, _vp]),
     "afr_train_step": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _u64, _i32, _f32, _f32, _f32, _f32, _f32, _i64, _vp]),
     "afr_bind_dataset": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _i32]),
     "afr_forward_rows": (_i32, [_vp, _vp, _i32, _vp, _i32, _u64, _vp]),
@@ -82,6 +84,7 @@ SIGNATURES = {
     "afr_op_reduce": (_i32, [_vp, _vp, _i32, _i64, _i64, _f32, _i32, _vp]),
     "afr_op_reduce_group": (_i32, [_i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "afr_op_adamw": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _f32, _vp]),
+    "afr_op_adamw_clip": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _f32, _vp, _f32, _vp]),
     "afr_op_mse_grad": (_i32, [_i32, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "afr_op_bce_grad": (_i32, [_i32, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "afr_op_f32_to_bf16": (_i32, [_vp, _vp, _i64, _vp]),

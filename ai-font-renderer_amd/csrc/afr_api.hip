@@ -61,6 +61,9 @@ struct ProfRec { int tag; hipEvent_t a, b; double flops, bytes; };
 // has a counter of its own and its partials, one per block of that launch, behind it.
 constexpr int LOSS_WS_COUNTER = 1024, LOSS_WS_FUSED_COUNTER = 1032, LOSS_WS_FUSED_PARTIAL = 1040;
 struct AdamArgs { float lr, b1, b2, eps, wd; int64_t t; };      // the optimizer arguments of afr_train_step
+// The clip scratch of a plan (o_clip), in floats: grad_sumsq_kernel's scratch, the word its sum goes to, the segment table
+constexpr int CLIP_WS_SUMSQ = AFR_SUMSQ_SCRATCH_FLOATS, CLIP_WS_TABLE = AFR_SUMSQ_SCRATCH_FLOATS + 8;
+static_assert(CLIP_WS_TABLE * sizeof(float) % alignof(SumsqSeg) == 0, "the segment table is aligned");
 
 struct afr_plan {
     afr_config cfg;                // cfg.dtype is the ACTIVATION dtype (AFR_F32 or AFR_BF16) every non-GEMM kernel runs in
@@ -134,6 +137,11 @@ struct afr_plan {
     const int64_t* ds_x = nullptr; const int64_t* ds_font = nullptr; const void* ds_target = nullptr;
     int ds_tdtype = 0, ds_L = 0; int64_t ds_rows = 0;
     size_t o_ridx = 0, o_sx = 0, o_sfont = 0;
+    // clipping by global gradient norm (afr_set_grad_clip): 0 = off; o_clip = [block partials + arrival counter | sumsq word |
+    // the (offset, numel) table of the parameter tensors], uploaded / zeroed by afr_bind
+    float clip_norm = 0.f; float* clip_stats = nullptr;
+    std::vector<SumsqSeg> clip_segs;        // host copy of that table
+    size_t o_clip = 0;
     // profiling
     int prof_mode = 0;      // 0 off, 1 every launch, 2 only prof_only, 3 every 4th launch of prof_only
     unsigned prof_seen = 0; // launches of prof_only met in mode 3
@@ -410,6 +418,8 @@ extern "C" int afr_plan_create(const afr_config* c, afr_plan** out) {
     p->o_ridx = carve(B * sizeof(int));
     p->o_sx = carve(B * (size_t)(c->kind == AFR_KIND_SHEET ? c->max_length : 1) * sizeof(int64_t));
     p->o_sfont = carve(B * sizeof(int64_t));
+    for (const Tensor& t : p->params) p->clip_segs.push_back(SumsqSeg{(long long)t.off, (long long)t.numel});
+    p->o_clip = carve(CLIP_WS_TABLE * sizeof(float) + p->clip_segs.size() * sizeof(SumsqSeg));
     p->ws_need = off;
     *out = p;
     return AFR_OK;
@@ -457,6 +467,12 @@ extern "C" int afr_bind(afr_plan* p, float* params, float* grads, float* m, floa
     for (auto& l : p->layers) {                          // cooperative split-K: arrival counters and their host count start at zero
         l.coop_arrived = 0;
         if (l.n_cnt) { DevGuard dg(dev); HIPCHK(hipMemset(p->ws + l.o_cnt, 0, (size_t)l.n_cnt * sizeof(unsigned))); }
+    }
+    {   // the norm kernel's scratch starts at zero (it leaves it so) and its table of tensor elements is the parameter table
+        DevGuard dg(dev);
+        HIPCHK(hipMemset(p->ws + p->o_clip, 0, CLIP_WS_TABLE * sizeof(float)));
+        HIPCHK(hipMemcpy(p->ws + p->o_clip + CLIP_WS_TABLE * sizeof(float), p->clip_segs.data(), p->clip_segs.size() * sizeof(SumsqSeg),
+                         hipMemcpyHostToDevice));
     }
     return AFR_OK;
 }
@@ -1296,6 +1312,31 @@ extern "C" int afr_backward(afr_plan* p, void* stream) {
 }
 
 // --------------------------------------------------------------------------------------- AdamW
+// the sum of squared gradients over the tensor elements inside [lo, hi) of the flat buffer -> *out (device)
+static int grad_sumsq_impl(afr_plan* p, int64_t lo, int64_t hi, float* out, float* stats, float gscale, uint32_t* err, hipStream_t s) {
+    float* cw = (float*)(p->ws + p->o_clip);
+    ProfScope ps(p, s, "grad_sumsq", 2.0 * (double)(hi - lo), 4.0 * (double)(hi - lo));
+    HIPCHK(afr_launch_grad_sumsq(p->G, (const SumsqSeg*)(cw + CLIP_WS_TABLE), p->clip_segs.data(), (int)p->clip_segs.size(), lo, hi, cw, out,
+                                 stats, gscale, p->clip_norm, err, s));
+    return AFR_OK;
+}
+extern "C" int afr_set_grad_clip(afr_plan* p, float max_norm, float* stats) {
+    if (!p) return fail(AFR_EINVAL, "null plan");
+    if (!(max_norm >= 0.f) || std::isinf(max_norm)) return fail(AFR_EINVAL, "max_norm must be finite and >= 0 (0 = no clipping), got %g", (double)max_norm);
+    p->clip_norm = max_norm;
+    p->clip_stats = max_norm > 0.f ? stats : nullptr;
+    return AFR_OK;
+}
+extern "C" int afr_grad_sumsq(afr_plan* p, int64_t offset, int64_t n, float* out, void* stream) {
+    if (!p) return fail(AFR_EINVAL, "null plan");
+    if ((offset | n) & 3) return fail(AFR_EINVAL, "offset %lld and n %lld must be multiples of 4", (long long)offset, (long long)n);
+    if (offset < 0 || n < 0 || offset > p->total || n > p->total - offset)
+        return fail(AFR_EINVAL, "range [%lld, +%lld) lies outside the gradient buffer of %lld elements", (long long)offset, (long long)n, (long long)p->total);
+    if (!out) return fail(AFR_EINVAL, "out is null");
+    if (!p->G || !p->ws) return fail(AFR_ESTATE, "plan has no bound gradient buffer");
+    DevGuard dg(p->device);
+    return grad_sumsq_impl(p, offset, offset + n, out, nullptr, 1.f, nullptr, (hipStream_t)stream);
+}
 extern "C" int afr_adamw_step(afr_plan* p, float lr, float b1, float b2, float eps, float wd, int64_t t, float gscale,
                               void* stream) {
     if (!p || !p->P || !p->G || !p->M || !p->V) return fail(AFR_ESTATE, "AdamW needs params, grads and both moments bound");
@@ -1303,8 +1344,16 @@ extern "C" int afr_adamw_step(afr_plan* p, float lr, float b1, float b2, float e
     if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
     hipStream_t s = (hipStream_t)stream;
     bf16_t* shadow = shadow_rd(p);        // nothing reads the weights concurrently: updated in place
-    ProfScope ps(p, s, "adamw", 0.0, (double)p->total * (shadow ? 30.0 : 28.0));
-    HIPCHK(afr_launch_adamw(p->P, p->G, p->M, p->V, shadow, p->total, lr, wd, adam_hyper(AdamArgs{lr, b1, b2, eps, wd, t}), gscale, s));
+    const float* sumsq = nullptr;
+    if (p->clip_norm > 0.f) {             // clipping plan: the global norm first, then the update reads it
+        float* cw = (float*)(p->ws + p->o_clip);
+        int rc = grad_sumsq_impl(p, 0, p->total, cw + CLIP_WS_SUMSQ, p->clip_stats, gscale, (uint32_t*)(p->ws + p->o_err), s);
+        if (rc) return rc;
+        sumsq = cw + CLIP_WS_SUMSQ;
+    }
+    ProfScope ps(p, s, sumsq ? "adamw_clip" : "adamw", 0.0, (double)p->total * (shadow ? 30.0 : 28.0));
+    HIPCHK(afr_launch_adamw(p->P, p->G, p->M, p->V, shadow, p->total, lr, wd, adam_hyper(AdamArgs{lr, b1, b2, eps, wd, t}), gscale, s, sumsq,
+                            p->clip_norm));
     p->wT_valid = false;
     return AFR_OK;
 }
@@ -1452,7 +1501,8 @@ static int train_step_impl(afr_plan* p, const int64_t* x, const int64_t* font, c
     if (!p || !p->P) return fail(AFR_ESTATE, "plan has no bound parameters");
     DevGuard dg(p->device);
     const AdamArgs h{lr, b1, b2, eps, wd, t};
-    const bool fuse_opt = do_step && !(p->cfg.reserved & AFR_CFG_UNFUSED_OPTIMIZER);
+    // (a clipping plan needs the global norm before any update: every gradient is materialised, then afr_adamw_step)
+    const bool fuse_opt = do_step && !(p->cfg.reserved & AFR_CFG_UNFUSED_OPTIMIZER) && !(p->clip_norm > 0.f);
     if (p->fused1 && !(p->cfg.reserved & AFR_CFG_NO_FUSED_GLYPH1)) {
         // small glyph net: forward + loss + backward in ONE launch, then the grouped reduce (with AdamW when stepping here)
         if (!p->G) return fail(AFR_ESTATE, "plan has no bound gradient buffer");
@@ -1717,6 +1767,16 @@ extern "C" int afr_op_adamw(float* p, const float* g, float* m, float* v, void* 
     if (!p || !g || !m || !v || t < 1) return fail(AFR_EINVAL, "bad AdamW arguments");
     DevGuard dg(device_of(p));
     HIPCHK(afr_launch_adamw(p, g, m, v, (bf16_t*)shadow, n, lr, wd, adam_hyper(AdamArgs{lr, b1, b2, eps, wd, t}), gscale, (hipStream_t)stream));
+    return AFR_OK;
+}
+extern "C" int afr_op_adamw_clip(float* p, const float* g, float* m, float* v, void* shadow, int64_t n, float lr, float b1, float b2,
+                                 float eps, float wd, int64_t t, float gscale, const float* sumsq, float max_norm, void* stream) {
+    if (!p || !g || !m || !v || !sumsq) return fail(AFR_EINVAL, "null argument");
+    if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
+    if (!(max_norm > 0.f) || std::isinf(max_norm)) return fail(AFR_EINVAL, "max_norm must be finite and > 0, got %g", (double)max_norm);
+    DevGuard dg(device_of(p));
+    HIPCHK(afr_launch_adamw(p, g, m, v, (bf16_t*)shadow, n, lr, wd, adam_hyper(AdamArgs{lr, b1, b2, eps, wd, t}), gscale, (hipStream_t)stream, sumsq,
+                            max_norm));
     return AFR_OK;
 }
 extern "C" int afr_op_mse_grad(int act_dtype, const void* u, const void* target, int tdtype, void* du, int64_t rows,

@@ -234,7 +234,7 @@ struct GemmParams {
     int dbg_slot = 0;     // kernel-development builds: which 1024-block region of the stamp buffer this launch writes
 #endif
 };
-constexpr uint32_t AFR_ERR_INDEX = 1u, AFR_ERR_COOP_TIMEOUT = 2u, AFR_ERR_ROW = 4u;    // bits of the plan's device error word
+constexpr uint32_t AFR_ERR_INDEX = 1u, AFR_ERR_COOP_TIMEOUT = 2u, AFR_ERR_ROW = 4u, AFR_ERR_GRAD_NONFINITE = 8u;    // bits of the plan's device error word
 hipError_t afr_launch_gemm(int dtype, const GemmParams& p, hipStream_t s);
 hipError_t afr_launch_gemm_fp8(const GemmParams& p, hipStream_t s);          // e4m3 x e4m3, both k-contiguous (gemm.hip fp8k)
 hipError_t afr_launch_f32_to_fp8(const float* src, unsigned char* dst, long long n, float inv_scale, hipStream_t s);
@@ -272,8 +272,21 @@ struct RTable {
 void afr_rtable_add(RTable& t, float* dst, const float* src, int nslabs, long long stride, long long n);
 hipError_t afr_launch_reduce_group(const RTable& t, hipStream_t s);
 // (lr and wd besides h: the kernel folds its decay = 1 - lr * wd on the device, as it always has; h.decay is not read)
+// sumsq (device word, optional): clip by global gradient norm -- every lane derives coef = clip_coef(*sumsq, |grad_scale|, max_norm)
+// and the gradient enters the update as g * fl32(grad_scale * coef); a non-finite *sumsq leaves p/m/v/shadow untouched.
+// sumsq NULL: the unclipped kernel, bit for bit what it has always computed.
 hipError_t afr_launch_adamw(float* p, const float* g, float* m, float* v, bf16_t* shadow, long long n, float lr, float wd,
-                            const AdamHyper& h, float grad_scale, hipStream_t s);
+                            const AdamHyper& h, float grad_scale, hipStream_t s, const float* sumsq = nullptr, float max_norm = 0.f);
+// Global gradient norm (elementwise.hip grad_sumsq_kernel): *out = sum of g[i]^2 over the tensor elements -- the (offset, numel)
+// segments of the table `segs` (at most 256), flat-buffer padding excluded -- that lie inside [lo, hi) of g; lo, hi multiples of 4.
+// scratch: AFR_SUMSQ_SCRATCH_FLOATS floats, zero before the first launch and left zero (block partials + arrival counter, the loss
+// scratch's convention).  stats (optional): stats[0] = |grad_scale| * sqrt(sum), stats[1] = clip_coef.  err (optional): a
+// non-finite sum sets AFR_ERR_GRAD_NONFINITE.  Fixed summation order: bitwise reproducible.
+struct SumsqSeg { long long off, numel; };
+constexpr int AFR_SUMSQ_MAX_BLOCKS = 1024, AFR_SUMSQ_COUNTER = 1024, AFR_SUMSQ_SCRATCH_FLOATS = 1032;
+hipError_t afr_launch_grad_sumsq(const float* g, const SumsqSeg* segs /* device */, const SumsqSeg* segs_host /* the same table */, int nseg,
+                                 long long lo, long long hi, float* scratch, float* out, float* stats, float grad_scale, float max_norm,
+                                 uint32_t* err, hipStream_t s);
 // loss: u (act dtype) [rows][cols] -> du in place or to `du`; per-block partial sums to scratch, then
 // a 1-block finisher adds sum(scratch) to *loss_accum (deterministic order).
 int afr_mse_blocks(long long rows, long long cols);

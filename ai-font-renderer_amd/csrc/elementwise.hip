@@ -155,19 +155,41 @@ hipError_t afr_launch_reduce_group(const RTable& t, hipStream_t s) {
 // torch.optim.AdamW single-tensor update (reference model.py:273,310), one pass over p,g,m,v:
 //   p *= 1 - lr*wd;  m += (g-m)*(1-b1);  v = b2*v + (1-b2)*g*g;  p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
 // Also refreshes the bf16 shadow copy the bf16 GEMMs read.  28 (+2) bytes per element of HBM traffic.
+// CLIP (clipping by global gradient norm, afr_set_grad_clip): every lane loads the one word *sumsq and derives the coefficient
+// itself (clip_coef: the same few instructions everywhere, so every slice and every rank agrees); the gradient enters the update
+// as g * fl32(gscale * coef) -- one rounded factor, then one rounded product that is NOT contracted into adamw_quad's FMAs
+// (mul_rn).  A non-finite *sumsq skips the step: nothing is written.  The CLIP = false instantiation is the kernel as it was.
+__device__ __forceinline__ float clip_coef(float sumsq, float gscale_abs, float max_norm, float& total_norm) {
+    total_norm = gscale_abs * sqrtf(sumsq);
+    return fminf(1.f, max_norm / (total_norm + 1e-6f));      // torch.nn.utils.clip_grad_norm_, in f32
+}
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ bool finite_f(float x) { return fabsf(x) <= 3.402823466e38f; }
+template <bool CLIP>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v,
                                                     bf16_t* __restrict__ shadow, long long n4, float lr, float b1,
                                                     float b2, float eps, float wd, float step_size, float rsqrt_bc2,
-                                                    float gscale) {
+                                                    float gscale, const float* __restrict__ sumsq, float max_norm) {
     const AdamHyper h{1.f - lr * wd, b1, b2, eps, step_size, rsqrt_bc2};
+    if constexpr (CLIP) {
+        const float ss = *sumsq;
+        if (!finite_f(ss)) return;
+        float tn;
+        gscale = mul_rn(gscale, clip_coef(ss, fabsf(gscale), max_norm, tn));
+    }
     for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
         const float4 p4 = reinterpret_cast<float4*>(p)[i];
         const float4 gg = reinterpret_cast<const float4*>(g)[i];
         const float4 m4 = reinterpret_cast<float4*>(m)[i];
         const float4 v4 = reinterpret_cast<float4*>(v)[i];
         f32x4 pp = {p4.x, p4.y, p4.z, p4.w}, mm = {m4.x, m4.y, m4.z, m4.w}, vv = {v4.x, v4.y, v4.z, v4.w};
-        const bf16x4 o = adamw_quad(pp, mm, vv, (f32x4){gg.x * gscale, gg.y * gscale, gg.z * gscale, gg.w * gscale}, h);
+        const f32x4 ge = CLIP ? (f32x4){mul_rn(gg.x, gscale), mul_rn(gg.y, gscale), mul_rn(gg.z, gscale), mul_rn(gg.w, gscale)}
+                              : (f32x4){gg.x * gscale, gg.y * gscale, gg.z * gscale, gg.w * gscale};
+        const bf16x4 o = adamw_quad(pp, mm, vv, ge, h);
         reinterpret_cast<float4*>(p)[i] = make_float4(pp[0], pp[1], pp[2], pp[3]);
         reinterpret_cast<float4*>(m)[i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
         reinterpret_cast<float4*>(v)[i] = make_float4(vv[0], vv[1], vv[2], vv[3]);
@@ -175,11 +197,127 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     }
 }
 hipError_t afr_launch_adamw(float* p, const float* g, float* m, float* v, bf16_t* shadow, long long n, float lr, float wd,
-                            const AdamHyper& h, float grad_scale, hipStream_t s) {
+                            const AdamHyper& h, float grad_scale, hipStream_t s, const float* sumsq, float max_norm) {
     if (n <= 0) return hipSuccess;
     if (n & 3) return hipErrorInvalidValue;   // flat buffers are padded to multiples of 64
-    hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n / 4, 256, 4096)), dim3(256), 0, s, p, g, m, v, shadow, n / 4, lr,
-                       h.b1, h.b2, h.eps, wd, h.step, h.rsqrt_bc2, grad_scale);
+    with_bool(sumsq != nullptr, [&](auto clip) {
+        hipLaunchKernelGGL(adamw_kernel<clip()>, dim3(grid_for(n / 4, 256, 4096)), dim3(256), 0, s, p, g, m, v, shadow, n / 4, lr,
+                           h.b1, h.b2, h.eps, wd, h.step, h.rsqrt_bc2, grad_scale, sumsq, max_norm);
+    });
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------ global gradient norm
+// *out = sum of g[i]^2 over the ELEMENTS of the parameter tensors inside [lo, hi) of the flat gradient buffer, from a device table
+// of (offset, numel) segments, each clipped to the range (segments start on multiples of 64 elements and lo, hi are multiples of
+// 4, so a clipped segment starts 16-byte aligned).  The 64-element padding between tensors is never read: the fused glyph step,
+// the slab reduces and the gradient accumulation leave arbitrary values there.
+// A block belongs to ONE segment (as in the grouped reduce: a walk of every segment by every block paid one memory latency per
+// tensor, 21 us for C3's 8.5 MB): segment k gets ceil(n4_k / (256 q)) blocks, at least one, of q float4 per lane; the launcher
+// picks the smallest power of two q that fits the grid cap and the blocks find their segment by the same count.  16-byte loads,
+// four in flight per lane; scalar loads for the <= 3 elements of a tail (the pixel head's bias has ONE element).
+// Fixed order: four FMA accumulators per lane (one per float4 component), (a0 + a1) + (a2 + a3), wave shuffle, the four waves
+// through LDS, one partial per block; the last block to arrive adds the partials in block order -- loss_block_finish's hand-off
+// (write-through partial store, drained, agent-scope ticket; the reader loads with agent-scope atomics; cdna_hip_programming.md
+// Guideline 16 R1) -- and writes the sum, the statistics and, for a non-finite sum, the error bit.  No float atomics.
+constexpr int SUMSQ_MAX_SEGS = 256;
+static inline long long sumsq_seg_blocks(long long numel, int qshift) {          // host twin of the kernel's count
+    if (numel <= 0) return 0;
+    const long long nb = ((numel >> 2) + (256ll << qshift) - 1) >> (8 + qshift);
+    return nb ? nb : 1;
+}
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, const SumsqSeg* __restrict__ segs, int nseg,
+                                                         long long lo, long long hi, int qshift, float* __restrict__ partial,
+                                                         unsigned* __restrict__ counter, float* __restrict__ out,
+                                                         float* __restrict__ stats, float gscale_abs, float max_norm, uint32_t* err) {
+    __shared__ long long sb[SUMSQ_MAX_SEGS], sn[SUMSQ_MAX_SEGS];      // the clipped segments: first element, elements
+    __shared__ float sh[256];
+    __shared__ unsigned ticket;
+    if ((int)threadIdx.x < nseg) {
+        const SumsqSeg sg = segs[threadIdx.x];
+        const long long b = max(sg.off, lo), e = min(sg.off + sg.numel, hi);
+        sb[threadIdx.x] = b; sn[threadIdx.x] = e > b ? e - b : 0;
+    }
+    __syncthreads();
+    const long long per = 256ll << qshift;                            // float4 per block
+    long long j = blockIdx.x, n = 0;
+    const float* src = g;
+    for (int k = 0; k < nseg; ++k) {
+        const long long nk = sn[k];
+        if (nk == 0) continue;
+        long long nb = ((nk >> 2) + per - 1) >> (8 + qshift);
+        if (nb == 0) nb = 1;
+        if (j < nb) { src = g + sb[k]; n = nk; break; }
+        j -= nb;
+    }
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    if (n > 0) {                                                      // (a block past the last segment has n = 0: it adds nothing)
+        const long long n4 = n >> 2, i0 = j * per + threadIdx.x, iend = min(n4, (j + 1) * per);
+        long long i = i0;
+        if ((j + 1) * per <= n4 && qshift >= 2) {                     // a whole block: unconditional loads, four in flight
+            for (; i < iend; i += 4 * 256) {
+                float4 v[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) v[u] = reinterpret_cast<const float4*>(src)[i + u * 256];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    a0 = __builtin_fmaf(v[u].x, v[u].x, a0); a1 = __builtin_fmaf(v[u].y, v[u].y, a1);
+                    a2 = __builtin_fmaf(v[u].z, v[u].z, a2); a3 = __builtin_fmaf(v[u].w, v[u].w, a3);
+                }
+            }
+        }
+        for (; i < iend; i += 256) {
+            const float4 v = reinterpret_cast<const float4*>(src)[i];
+            a0 = __builtin_fmaf(v.x, v.x, a0); a1 = __builtin_fmaf(v.y, v.y, a1);
+            a2 = __builtin_fmaf(v.z, v.z, a2); a3 = __builtin_fmaf(v.w, v.w, a3);
+        }
+        const long long t = (n4 << 2) + threadIdx.x;                 // tail: lanes 0..2 of the segment's first block
+        if (j == 0 && t < n) { const float x = src[t]; a0 = __builtin_fmaf(x, x, a0); }
+    }
+    const float lsum = wave_sum((a0 + a1) + (a2 + a3));
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = lsum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __hip_atomic_store(partial + blockIdx.x, (sh[0] + sh[1]) + (sh[2] + sh[3]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (ticket != gridDim.x - 1) return;
+    float a = 0.f;
+    for (int i = threadIdx.x; i < (int)gridDim.x; i += 256)
+        a += __hip_atomic_load(partial + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    sh[threadIdx.x] = a;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float ss = sh[0];
+        out[0] = ss;
+        float tn;
+        const float coef = clip_coef(ss, gscale_abs, max_norm, tn);
+        if (stats) { stats[0] = tn; stats[1] = coef; }
+        if (err && !finite_f(ss)) atomicOr(err, AFR_ERR_GRAD_NONFINITE);
+        __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-arm for the next call
+    }
+}
+hipError_t afr_launch_grad_sumsq(const float* g, const SumsqSeg* segs, const SumsqSeg* segs_host, int nseg, long long lo, long long hi,
+                                 float* scratch, float* out, float* stats, float grad_scale, float max_norm, uint32_t* err, hipStream_t s) {
+    if (lo < 0 || hi < lo || ((lo | hi) & 3) || nseg < 0 || nseg > SUMSQ_MAX_SEGS) return hipErrorInvalidValue;
+    int qshift = 0;
+    long long blocks = 0;
+    for (;; ++qshift) {              // the smallest power of two of float4 per lane whose block count fits the cap
+        blocks = 0;
+        for (int k = 0; k < nseg; ++k) {
+            const long long b = std::max(segs_host[k].off, lo), e = std::min(segs_host[k].off + segs_host[k].numel, hi);
+            blocks += sumsq_seg_blocks(e - b, qshift);
+        }
+        if (blocks <= AFR_SUMSQ_MAX_BLOCKS) break;
+    }
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(blocks ? (unsigned)blocks : 1u), dim3(256), 0, s, g, segs, nseg, lo, hi, qshift, scratch,
+                       reinterpret_cast<unsigned*>(scratch + AFR_SUMSQ_COUNTER), out, stats, fabsf(grad_scale), max_norm, err);
     return hipGetLastError();
 }
 

@@ -64,8 +64,9 @@ class Engine:
     state_dict order, so checkpoints interchange with the reference (helpers.py:76-105)."""
 
     def __init__(self, cfg, dtype="f32", max_batch=1024, device=None, seed=42, rank=0, with_optimizer=True, flags=0, micro_batch=None,
-                 loss="mse"):
-        """micro_batch: train_step / forward_loss + backward of a batch larger than this many samples run as micro-steps of at
+                 loss="mse", max_grad_norm=None):
+        """max_grad_norm: clip the gradients by their global L2 norm inside every optimizer step (set_grad_clip); None or 0 = off.
+        micro_batch: train_step / forward_loss + backward of a batch larger than this many samples run as micro-steps of at
         most that many, their gradients summed (gradient accumulation: the saved activations of BASELINE configs[4]'s 2048
         glyphs per GPU would be 800 GB; 32 at a time they are 12.6 GB).  The plan is then sized for micro_batch, not max_batch."""
         if not torch.cuda.is_available():
@@ -81,6 +82,8 @@ class Engine:
         self.seed, self.rank, self.flags = int(seed), int(rank), int(flags)
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         self._plan = None
+        self.max_grad_norm = self._check_clip(max_grad_norm)
+        self._clip_stats = None     # device float[2] the library writes (total_norm, coef) into on a clipping plan
         self._ds = None       # the bound data set: (x, font, target, target dtype code, rows, L), see bind_dataset
         self._make_plan(self.max_batch)
         n = self.lib.afr_param_elems(self._plan)
@@ -126,6 +129,51 @@ class Engine:
         _lib.check(self.lib.afr_bind(self._plan, _ptr(self.flat_params), _ptr(self.flat_grads), _ptr(self.exp_avg),
                                      _ptr(self.exp_avg_sq), _ptr(self.workspace), self.ws_bytes))
         self._bind_ds()
+        self._apply_clip()
+
+    @staticmethod
+    def _check_clip(v):
+        v = 0.0 if v is None else float(v)
+        if not (np.isfinite(v) and v >= 0.0):
+            raise ValueError(f"max_grad_norm must be a finite number >= 0 (0 or None: off), got {v!r}")
+        return v or None
+
+    def _apply_clip(self):
+        """Hand the plan its clip setting (host-only call; ensure_batch's new plan gets it again)."""
+        if self.max_grad_norm and self._clip_stats is None:
+            with torch.cuda.device(self.device):
+                self._clip_stats = torch.zeros(2, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.afr_set_grad_clip(self._plan, float(self.max_grad_norm or 0.0), _ptr(self._clip_stats if self.max_grad_norm else None)))
+
+    def set_grad_clip(self, max_grad_norm):
+        """Clip by global gradient norm from the next optimizer step on: g_eff = g * min(1, max_norm / (|grad_scale| * ||g|| + 1e-6)),
+        the norm over every parameter tensor's elements (torch.nn.utils.clip_grad_norm_'s formula).  The coefficient lives inside
+        the update: flat_grads is NOT rescaled (the one difference from torch).  A step whose gradients are not finite is skipped
+        and sets bit 3 of error_flags().  None or 0 switches clipping off."""
+        self.max_grad_norm = self._check_clip(max_grad_norm)
+        self._apply_clip()
+
+    def grad_sumsq(self, offset=0, n=None):
+        """Sum of squares of the gradient buffer over the tensor elements (padding excluded) inside [offset, offset + n) of the flat
+        layout, as a 1-element device tensor; works with clipping on or off.  offset and n are multiples of 4."""
+        n = self.n_flat - int(offset) if n is None else int(n)
+        with torch.cuda.device(self.device):
+            out = torch.empty(1, dtype=torch.float32, device=self.device)
+        self._call(self.lib.afr_grad_sumsq, self._plan, int(offset), n, _ptr(out))
+        return out
+
+    def _read_clip_stats(self):
+        if self._clip_stats is None or not self.max_grad_norm:
+            raise _lib.AfrError("no clip statistics: clipping is off (Engine(max_grad_norm=...) / set_grad_clip)")
+        return self._clip_stats.cpu()        # one synchronising copy
+
+    def grad_norm(self):
+        """|grad_scale| * global L2 norm of the gradients the last clipped optimizer step saw (before clipping)."""
+        return float(self._read_clip_stats()[0])
+
+    def clip_coef(self):
+        """The coefficient min(1, max_norm / (norm + 1e-6)) the last clipped optimizer step applied."""
+        return float(self._read_clip_stats()[1])
 
     def _bind_ds(self):
         if self._ds is not None:
@@ -332,11 +380,19 @@ class Engine:
         self.t += 1
         self._call(self.lib.afr_adamw_step, self._plan, lr, betas[0], betas[1], eps, weight_decay, self.t, grad_scale)
 
-    def adamw_range(self, offset, n, lr=1e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=5e-4, grad_scale=1.0):
+    def adamw_range(self, offset, n, lr=1e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=5e-4, grad_scale=1.0, sumsq=None):
         """One AdamW step on the flat-buffer slice [offset, offset + n) only (sharded optimizer under data parallelism:
-        parallel.py).  Advances the step counter; the bf16 shadow is NOT refreshed (the caller syncs after its all-gather)."""
+        parallel.py).  Advances the step counter; the bf16 shadow is NOT refreshed (the caller syncs after its all-gather).
+        sumsq: a 1-element device tensor holding the GLOBAL sum of squared gradients (grad_sumsq of every rank's range,
+        all-reduced): the slice is then updated with the clip coefficient of self.max_grad_norm, as adamw_step would."""
         self.t += 1
         o, e = int(offset), int(offset) + int(n)
+        if sumsq is not None:
+            self._call(self.lib.afr_op_adamw_clip, _ptr(self.flat_params[o:e]), _ptr(self.flat_grads[o:e]), _ptr(self.exp_avg[o:e]),
+                       _ptr(self.exp_avg_sq[o:e]), C.c_void_p(0), int(n), lr, betas[0], betas[1], eps, weight_decay, self.t, grad_scale,
+                       _ptr(sumsq), float(self.max_grad_norm or 0.0))
+            self._keep_ss = sumsq
+            return
         self._call(self.lib.afr_op_adamw, _ptr(self.flat_params[o:e]), _ptr(self.flat_grads[o:e]), _ptr(self.exp_avg[o:e]),
                    _ptr(self.exp_avg_sq[o:e]), C.c_void_p(0), int(n), lr, betas[0], betas[1], eps, weight_decay, self.t, grad_scale)
 

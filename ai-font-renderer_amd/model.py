@@ -18,7 +18,9 @@ What is deliberately different from the reference, and why:
     AFR_DTYPE=bf16x3 the fast parity mode (f32 except that every Linear product runs as three split-bf16 MFMAs);
   * AFR_LOSS=bce selects a sigmoid output head trained with binary cross-entropy on the logits (the loss the reference's
     clamp head replaced, model.py:155) through the same fused step; the default, mse, is the reference's clamp + MSE.  A
-    checkpoint does not record the head: the caller says which one it wants, as with the dtype.
+    checkpoint does not record the head: the caller says which one it wants, as with the dtype;
+  * AFR_CLIP_NORM=<max_norm> clips the gradients by their global L2 norm inside the optimizer step
+    (torch.nn.utils.clip_grad_norm_'s formula; Engine.set_grad_clip).  Unset or 0: no clipping, the reference's loop.
 """
 import datetime
 import os
@@ -54,6 +56,7 @@ SEED = 42
 ADAM_BETAS = (0.9, 0.99)                      # model.py:273
 COMPUTE_DTYPE = os.environ.get("AFR_DTYPE", "f32")
 COMPUTE_LOSS = os.environ.get("AFR_LOSS", "mse")     # "mse" | "bce"
+CLIP_NORM = float(os.environ.get("AFR_CLIP_NORM", "0") or 0) or None     # global gradient-norm clip; None = off
 
 random.seed(SEED)
 np.random.seed(SEED)
@@ -157,9 +160,12 @@ class AttentionFontRenderer(nn.Module):
     L > max_length is truncated, L < max_length zero-pads the flattened features; an index >= 128 raises
     IndexError (checked when `strict_indices`, default, at the cost of a device sync in eval mode only).
     loss: "mse" (clamp head, the reference's) or "bce" (sigmoid head: forward returns sigmoid(u), the fused steps train with
-    binary cross-entropy on u); None takes AFR_LOSS from the environment.  state_dict() is the same for both."""
+    binary cross-entropy on u); None takes AFR_LOSS from the environment.  state_dict() is the same for both.
+    max_grad_norm: clip the gradients by their global L2 norm inside the engine's optimizer step (Engine.set_grad_clip); None
+    takes AFR_CLIP_NORM from the environment (unset: off).  A torch optimizer on the autograd path clips with torch's own call."""
 
-    def __init__(self, max_length=MAX_CHARS_PER_SHEET, dtype=None, max_batch=1024, seed=SEED, rank=None, init=True, loss=None):
+    def __init__(self, max_length=MAX_CHARS_PER_SHEET, dtype=None, max_batch=1024, seed=SEED, rank=None, init=True, loss=None,
+                 max_grad_norm=None):
         super().__init__()
         from .engine import Engine
         self.max_length = max_length
@@ -169,8 +175,9 @@ class AttentionFontRenderer(nn.Module):
                                   p_fc=DROPOUT_RATE + 0.05)
         rank = int(os.environ.get("RANK", "0")) if rank is None else rank
         self.engine = Engine(self.config, dtype=dtype or COMPUTE_DTYPE, max_batch=max_batch, device=device, seed=seed, rank=rank,
-                             loss=loss or COMPUTE_LOSS)
+                             loss=loss or COMPUTE_LOSS, max_grad_norm=CLIP_NORM if max_grad_norm is None else max_grad_norm)
         self.loss = self.engine.loss
+        self.max_grad_norm = self.engine.max_grad_norm
         P = {k: nn.Parameter(v) for k, v in self.engine.params.items()}
         self.positional_encoding = P["positional_encoding"]
         self.embedding = _Bag(weight=P["embedding.weight"])
@@ -327,6 +334,8 @@ def train_attention_model(model, dataset, batch_size):
                 f.write(f"{k} = {v}\n")
             if eng.loss != "mse":               # only a non-default loss is recorded: a default run's artefacts stay as they were
                 f.write(f"loss = {eng.loss}\n")
+            if eng.max_grad_norm:               # likewise only when set
+                f.write(f"max_grad_norm = {eng.max_grad_norm:g}\n")
 
     order = _EpochOrder(len(dataset))
     print(f"Dataset split: {order.train_size} training samples, {order.val_size} validation samples")

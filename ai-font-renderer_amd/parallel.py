@@ -142,7 +142,14 @@ class DataParallelStepper:
             rk = self.rank if ws == self.world else self.dist.get_rank()
             n = eng.flat_grads.numel() // ws
             _reduce_scatter_inplace(self.dist, eng.flat_grads, rk, ws)
-            eng.adamw_range(rk * n, n, **opt)
+            if getattr(eng, "max_grad_norm", None):
+                # clipping by the GLOBAL norm: every rank sums the squares of its own range, the all-reduced sum gives every
+                # rank the same coefficient (the choice depends on the engine's setting alone: rank-invariant)
+                ss = eng.grad_sumsq(rk * n, n)
+                self.dist.all_reduce(ss)
+                eng.adamw_range(rk * n, n, sumsq=ss, **opt)
+            else:
+                eng.adamw_range(rk * n, n, **opt)
             _all_gather_inplace(self.dist, eng.flat_params, rk, ws)
             if hasattr(eng, "sync_params"):
                 eng.sync_params()               # bf16 mode: the shadow of the slices other ranks updated

@@ -164,6 +164,29 @@ int afr_forward_loss(afr_plan* plan, const int64_t* x, const int64_t* font, cons
 int afr_adamw_step(afr_plan* plan, float lr, float beta1, float beta2, float eps, float weight_decay,
                    int64_t t, float grad_scale, void* stream);
 
+/* Clipping by the GLOBAL gradient norm inside the optimizer step (torch.nn.utils.clip_grad_norm_; the reference's loop has
+ * none).  Off by default; with max_norm > 0 every optimizer step of the plan (afr_adamw_step, afr_train_step* with do_step)
+ * computes, on the device,
+ *     sumsq      = sum of g[i]^2 over the ELEMENTS of the parameter tensors (afr_param_info offsets / numel; the 64-element
+ *                  padding between tensors in the flat buffer is not part of the sum)
+ *     total_norm = |grad_scale| * sqrt(sumsq)
+ *     coef       = min(1, max_norm / (total_norm + 1e-6))                     (f32)
+ *     AdamW(p, m, v, g * fl32(grad_scale * coef))
+ * The gradient buffer is NOT rescaled in place -- the coefficient lives only inside the update: the one difference from
+ * torch.  A sumsq that is not finite (an inf or NaN gradient) SKIPS the step -- params, both moments and the bf16 shadow stay
+ * bit-identical -- and sets bit 3 of the error word.  The sum has a fixed order (per lane, wave, block partial, partials in block
+ * order): bitwise reproducible.  On a clipping plan afr_train_step* with do_step materialise every gradient (the path
+ * AFR_CFG_UNFUSED_OPTIMIZER takes) and end in afr_adamw_step.
+ * max_norm: 0 = off; negative or non-finite -> AFR_EINVAL.  stats: caller-owned device float[2] or NULL; every clipped step
+ * leaves stats[0] = total_norm, stats[1] = coef.  Host-only: nothing is launched; the setting lives in the plan (a new plan
+ * starts with clipping off). */
+int afr_set_grad_clip(afr_plan* plan, float max_norm, float* stats);
+/* *out (device float) = the sum of squares of the bound gradient buffer over the tensor elements that lie inside
+ * [offset, offset + n) of the flat layout -- the logging entry (a gradient norm without copying the buffer back and masking its
+ * padding), and the per-rank share of the norm under a sharded optimizer.  offset and n must be multiples of 4 and the range
+ * must lie inside the buffer (AFR_EINVAL otherwise).  Works whether clipping is on or off. */
+int afr_grad_sumsq(afr_plan* plan, int64_t offset, int64_t n, float* out, void* stream);
+
 /* One whole iteration of the loop body model.py:292-310 on this rank's shard:
  * forward(training) -> loss+grad -> backward [-> AdamW when do_step!=0].  With do_step!=0 the loss is fused into
  * the last forward GEMM and, for the sheet model, the AdamW update of fc_output.weight into its dW GEMM.
@@ -199,7 +222,8 @@ int afr_train_step_rows(afr_plan* plan, const int64_t* rows, int B, int64_t mean
 /* Set / read the device-side error word (bit 0: an embedding index outside [0,vocab), the
  * condition on which the reference raises IndexError; model.py:136,167; bit 1: a cooperative split-K
  * workgroup gave up waiting for its partners -- the step's results are invalid; bit 2: a row index of an afr_*_rows call
- * outside the bound data set, clamped into it).  Reading synchronises and clears. */
+ * outside the bound data set, clamped into it; bit 3: a clipping plan (afr_set_grad_clip) met gradients whose sum of squares
+ * is not finite and skipped that optimizer step).  Reading synchronises and clears. */
 int afr_error_flags(afr_plan* plan, void* stream, uint32_t* flags_out);
 
 /* Name and average duration (ms, hipEvent-timed on the launch stream) of the plan's dominant
@@ -276,6 +300,13 @@ int afr_op_reduce_group(int nseg, float* const* dst, const float* const* slabs, 
 int afr_op_adamw(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr,
                  float beta1, float beta2, float eps, float weight_decay, int64_t t, float grad_scale,
                  void* stream);
+/* afr_op_adamw with clipping by a caller-supplied global norm: sumsq_dev is a device float holding the sum of squared gradients
+ * of the WHOLE model (under a sharded optimizer: the all-reduced sum of every rank's afr_grad_sumsq over its range); the slice
+ * is updated with coef = min(1, max_norm / (|grad_scale| * sqrt(*sumsq_dev) + 1e-6)) as afr_adamw_step does on a clipping plan.
+ * A non-finite *sumsq_dev leaves p, m, v untouched (no plan, hence no error word: the caller holds the sum).  max_norm > 0. */
+int afr_op_adamw_clip(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr,
+                      float beta1, float beta2, float eps, float weight_decay, int64_t t, float grad_scale,
+                      const float* sumsq_dev, float max_norm, void* stream);
 /* scratch: >= 1040 floats, zero before the first call (holds per-block partials and the arrival counter) */
 int afr_op_mse_grad(int act_dtype, const void* u, const void* target, int target_dtype, void* du,
                     int64_t rows, int64_t cols, int64_t mean_elems, float* loss_accum, float* scratch,
