@@ -15,6 +15,8 @@ AFR_F32, AFR_BF16, AFR_BF16X3 = 0, 1, 2
 AFR_TARGET_U8, AFR_TARGET_F32 = 0, 1
 AFR_LOSS_MSE, AFR_LOSS_BCE = 0, 1
 LOSS_KINDS = {"mse": AFR_LOSS_MSE, "bce": AFR_LOSS_BCE}
+AFR_OPT_ADAMW, AFR_OPT_LION = 0, 1
+OPT_KINDS = {"adamw": AFR_OPT_ADAMW, "lion": AFR_OPT_LION}
 
 AFR_MAX_HIDDEN = 8
 BUF_U, BUF_Z, BUF_DZ, BUF_W1T, BUF_W2T, BUF_ACT = 0, 1, 2, 4, 5, 16
@@ -26,6 +28,13 @@ def loss_kind(loss):
     if not isinstance(loss, str) or loss not in LOSS_KINDS:
         raise ValueError(f"loss must be 'mse' or 'bce', got {loss!r}")
     return LOSS_KINDS[loss]
+
+
+def opt_kind(optimizer):
+    """"adamw" | "lion" -> AFR_OPT_*; anything else is a ValueError."""
+    if not isinstance(optimizer, str) or optimizer not in OPT_KINDS:
+        raise ValueError(f"optimizer must be 'adamw' or 'lion', got {optimizer!r}")
+    return OPT_KINDS[optimizer]
 
 
 class AfrConfig(C.Structure):
@@ -63,6 +72,7 @@ SIGNATURES = {
     "afr_forward_loss": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _u64, _vp]),
     "afr_adamw_step": (_i32, [_vp, _f32, _f32, _f32, _f32, _f32, _i64, _f32, _vp]),
     "afr_set_grad_clip": (_i32, [_vp, _f32, _vp]),
+    "afr_set_optimizer": (_i32, [_vp, _i32]),
     "afr_grad_sumsq": (_i32, [_vp, _i64, _i64, _vp, _vp]),
     "afr_train_step": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _u64, _i32, _f32, _f32, _f32, _f32, _f32, _i64, _vp]),
     "afr_bind_dataset": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _i32]),
@@ -85,6 +95,7 @@ SIGNATURES = {
     "afr_op_reduce_group": (_i32, [_i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "afr_op_adamw": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _f32, _vp]),
     "afr_op_adamw_clip": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _f32, _vp, _f32, _vp]),
+    "afr_op_lion": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _vp, _f32, _vp]),
     "afr_op_mse_grad": (_i32, [_i32, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "afr_op_bce_grad": (_i32, [_i32, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "afr_op_f32_to_bf16": (_i32, [_vp, _vp, _i64, _vp]),

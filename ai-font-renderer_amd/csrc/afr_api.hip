@@ -140,6 +140,7 @@ struct afr_plan {
     // clipping by global gradient norm (afr_set_grad_clip): 0 = off; o_clip = [block partials + arrival counter | sumsq word |
     // the (offset, numel) table of the parameter tensors], uploaded / zeroed by afr_bind
     float clip_norm = 0.f; float* clip_stats = nullptr;
+    int opt_kind = OPT_ADAMW;               // afr_set_optimizer: the update every optimizer step of the plan applies
     std::vector<SumsqSeg> clip_segs;        // host copy of that table
     size_t o_clip = 0;
     // profiling
@@ -620,8 +621,15 @@ static LossArgs loss_args(float* scratch, bool fused, int kind, const void* targ
 static LossArgs loss_args(const afr_plan* p, bool fused, const void* target, int tdtype, const int* rowmap, int64_t mean_elems, float* loss_accum) {
     return loss_args((float*)(p->ws + p->o_loss), fused, p->cfg.loss, target, tdtype, rowmap, mean_elems, loss_accum);
 }
-// the scalars of an AdamW step (torch.optim.AdamW, bias corrections in double as torch takes them)
-static AdamHyper adam_hyper(const AdamArgs& h) {
+// the scalars of an AdamW step (torch.optim.AdamW, bias corrections in double as torch takes them); OPT_LION: decay, b1, b2 and
+// step = lr -- no bias correction, eps and t are not read.  Lion's decay is the rounded product subtracted from one, never a fused
+// multiply-add: the elementwise kernel folds the same two roundings on the device.
+static AdamHyper adam_hyper(const AdamArgs& h, int kind = OPT_ADAMW) {
+    if (kind == OPT_LION) {
+#pragma clang fp contract(off)
+        const float lw = h.lr * h.wd;
+        return AdamHyper{1.f - lw, h.b1, h.b2, 0.f, h.lr, 1.f};
+    }
     const float bc1 = (float)(1.0 - std::pow((double)h.b1, (double)h.t));
     const float bc2 = (float)(1.0 - std::pow((double)h.b2, (double)h.t));
     return AdamHyper{1.f - h.lr * h.wd, h.b1, h.b2, h.eps, h.lr / bc1, (float)(1.0 / std::sqrt((double)bc2))};
@@ -635,6 +643,14 @@ static inline bf16_t* shadow_wr(const afr_plan* p) {
     if (p->cfg.dtype != AFR_BF16) return nullptr;
     if (!p->o_shadow2) return (bf16_t*)(p->ws + p->o_shadow);
     return (bf16_t*)(p->ws + (p->shadow_cur ? p->o_shadow : p->o_shadow2));
+}
+// the moments the plan's optimizer kind needs are bound (Lion keeps exp_avg only)
+static inline bool moments_bound(const afr_plan* p) { return p->M && (p->V || p->opt_kind == OPT_LION); }
+// the fused optimizer step of a weight-gradient product: AdamW / Lion on the tensor at flat offset `off`
+static void set_fused_opt(const afr_plan* p, GemmParams& g, int64_t off, bf16_t* shadow, const AdamArgs& h) {
+    g.ad_p = p->P + off; g.ad_m = p->M + off; g.ad_v = p->opt_kind == OPT_LION ? nullptr : p->V + off;
+    g.ad_shadow = shadow ? shadow + off : nullptr;
+    g.ad = adam_hyper(h, p->opt_kind); g.ad_kind = p->opt_kind;
 }
 static inline const void* weight_ptr(const afr_plan* p, int64_t off) {
     if (p->cfg.dtype == AFR_BF16) return shadow_rd(p) + off;
@@ -686,7 +702,8 @@ static int run_gemm(afr_plan* p, hipStream_t s, const GemmParams& g) {
     const double ob = (g.flags & AFR_GEMM_OUT_BF16) ? 2.0 : 4.0;
     // algorithmic bytes: operands once + the product once (split-K partial slabs are an implementation choice, not
     // algorithmic output); with the fused optimizer the output is p,m,v read + p,m,v(,shadow) written
-    const double out_bytes = g.ad_p ? (double)M * N * (24.0 + (g.ad_shadow ? 2.0 : 0.0)) : (g.splitk > 1 ? 4.0 : ob) * (double)M * N;
+    // (Lion: p and m only)
+    const double out_bytes = g.ad_p ? (double)M * N * ((g.ad_kind == OPT_LION ? 16.0 : 24.0) + (g.ad_shadow ? 2.0 : 0.0)) : (g.splitk > 1 ? 4.0 : ob) * (double)M * N;
     char tag[96];
     const double fl_ = 2.0 * M * (double)N * K, by_ = eb * ((double)M * K + (double)N * K) + out_bytes;
     {
@@ -755,10 +772,7 @@ static int run_dw(afr_plan* p, hipStream_t s, afr_plan::Layer& l, const void* dy
         g.coop_ws = sw; g.coop_cnt = (unsigned*)(p->ws + l.o_cnt); g.coop_target = l.coop_arrived + (unsigned)sk;
         g.err = (uint32_t*)(p->ws + p->o_err);
         if (a_rows) { g.b_rowmap = a_rows; g.ldb = a_ld; }      // the layer's input rows are gathered from a table whose rows are a_ld apart
-        if (p->step_on) {
-            g.ad_p = p->P + l.w_off; g.ad_m = p->M + l.w_off; g.ad_v = p->V + l.w_off; g.ad_shadow = shadow_wr(p) ? shadow_wr(p) + l.w_off : nullptr;
-            g.ad = adam_hyper(p->st);
-        }
+        if (p->step_on) set_fused_opt(p, g, l.w_off, shadow_wr(p), p->st);
         int rc = run_gemm(p, s, g);
         if (rc) return rc;
         p->pend_arrived = &l.coop_arrived;                // run_gemm deferred it (a cooperative product is never launched alone)
@@ -1337,9 +1351,16 @@ extern "C" int afr_grad_sumsq(afr_plan* p, int64_t offset, int64_t n, float* out
     DevGuard dg(p->device);
     return grad_sumsq_impl(p, offset, offset + n, out, nullptr, 1.f, nullptr, (hipStream_t)stream);
 }
+extern "C" int afr_set_optimizer(afr_plan* p, int kind) {
+    if (!p) return fail(AFR_EINVAL, "null plan");
+    if (kind != AFR_OPT_ADAMW && kind != AFR_OPT_LION) return fail(AFR_EINVAL, "optimizer kind must be AFR_OPT_ADAMW (0) or AFR_OPT_LION (1), got %d", kind);
+    p->opt_kind = kind;
+    return AFR_OK;
+}
 extern "C" int afr_adamw_step(afr_plan* p, float lr, float b1, float b2, float eps, float wd, int64_t t, float gscale,
                               void* stream) {
-    if (!p || !p->P || !p->G || !p->M || !p->V) return fail(AFR_ESTATE, "AdamW needs params, grads and both moments bound");
+    if (!p || !p->P || !p->G || !moments_bound(p))
+        return fail(AFR_ESTATE, p && p->opt_kind == OPT_LION ? "Lion needs params, grads and exp_avg bound" : "AdamW needs params, grads and both moments bound");
     DevGuard dg(p->device);
     if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
     hipStream_t s = (hipStream_t)stream;
@@ -1351,9 +1372,10 @@ extern "C" int afr_adamw_step(afr_plan* p, float lr, float b1, float b2, float e
         if (rc) return rc;
         sumsq = cw + CLIP_WS_SUMSQ;
     }
-    ProfScope ps(p, s, sumsq ? "adamw_clip" : "adamw", 0.0, (double)p->total * (shadow ? 30.0 : 28.0));
-    HIPCHK(afr_launch_adamw(p->P, p->G, p->M, p->V, shadow, p->total, lr, wd, adam_hyper(AdamArgs{lr, b1, b2, eps, wd, t}), gscale, s, sumsq,
-                            p->clip_norm));
+    const bool lion = p->opt_kind == OPT_LION;
+    ProfScope ps(p, s, lion ? (sumsq ? "lion_clip" : "lion") : (sumsq ? "adamw_clip" : "adamw"), 0.0, (double)p->total * ((lion ? 20.0 : 28.0) + (shadow ? 2.0 : 0.0)));
+    HIPCHK(afr_launch_adamw(p->P, p->G, p->M, lion ? nullptr : p->V, shadow, p->total, lr, wd, adam_hyper(AdamArgs{lr, b1, b2, eps, wd, t}, p->opt_kind),
+                            gscale, s, sumsq, p->clip_norm, p->opt_kind));
     p->wT_valid = false;
     return AFR_OK;
 }
@@ -1363,8 +1385,9 @@ extern "C" int afr_adamw_step(afr_plan* p, float lr, float b1, float b2, float e
 // sums its slabs -- the summed gradient is never stored; tensors whose gradient a GEMM wrote directly get the plain kernel.
 static int reduce_and_step(afr_plan* p, hipStream_t s, RTable& rt, const AdamArgs& h, int64_t skip_off = -1) {
     bf16_t* shadow = shadow_wr(p);        // every tensor's new bf16 copy goes to the write shadow; the roles swap below
-    rt.adam = 1; rt.ad = adam_hyper(h);
-    rt.gbase = p->G; rt.P = p->P; rt.M = p->M; rt.V = p->V; rt.shadow = shadow;
+    const bool lion = p->opt_kind == OPT_LION;
+    rt.adam = 1; rt.ad = adam_hyper(h, p->opt_kind); rt.kind = p->opt_kind;
+    rt.gbase = p->G; rt.P = p->P; rt.M = p->M; rt.V = lion ? nullptr : p->V; rt.shadow = shadow;
     p->wT_valid = false;
     int rc = run_reduce_group(p, s, rt);
     if (rc) return rc;
@@ -1382,9 +1405,9 @@ static int reduce_and_step(afr_plan* p, hipStream_t s, RTable& rt, const AdamArg
         }
         if (cov >= tn.numel) continue;
         const int64_t n = (tn.numel + 63) / 64 * 64;
-        ProfScope ps(p, s, "adamw", 0.0, (double)n * 28.0);
-        HIPCHK(afr_launch_adamw(p->P + tn.off, p->G + tn.off, p->M + tn.off, p->V + tn.off, shadow ? shadow + tn.off : nullptr, n, h.lr, h.wd,
-                                rt.ad, 1.f, s));
+        ProfScope ps(p, s, lion ? "lion" : "adamw", 0.0, (double)n * (lion ? 20.0 : 28.0));
+        HIPCHK(afr_launch_adamw(p->P + tn.off, p->G + tn.off, p->M + tn.off, lion ? nullptr : p->V + tn.off, shadow ? shadow + tn.off : nullptr, n, h.lr, h.wd,
+                                rt.ad, 1.f, s, nullptr, 0.f, p->opt_kind));
     }
     if (p->o_shadow2) p->shadow_cur ^= 1;   // every tensor has been rewritten: the write shadow is the current one now
     p->adam_done.clear();
@@ -1396,7 +1419,7 @@ static int reduce_and_step(afr_plan* p, hipStream_t s, RTable& rt, const AdamArg
 // or re-read from HBM (-8 bytes/parameter/step) and the update traffic overlaps other tiles' MFMA work.  dz = du.W
 // runs FIRST because it must see the pre-update weights.  The small tensors take the ordinary AdamW kernel.
 static bool fused_step_eligible(const afr_plan* p, int B) {
-    return p->cfg.kind == AFR_KIND_SHEET && p->M && p->V && choose_splitk(p->layers[0].N, p->layers[0].K, B) == 1;
+    return p->cfg.kind == AFR_KIND_SHEET && moments_bound(p) && choose_splitk(p->layers[0].N, p->layers[0].K, B) == 1;
 }
 static int sheet_fused_step(afr_plan* p, hipStream_t s, const AdamArgs& h) {
     const afr_plan::Layer& l = p->layers[0];      // fc_output
@@ -1406,8 +1429,7 @@ static int sheet_fused_step(afr_plan* p, hipStream_t s, const AdamArgs& h) {
     int rc;
     if ((rc = run_gemm(p, s, lin_dx(p, l, du, p->ws + p->o_dz, nullptr, B)))) return rc;
     GemmParams g = lin_dw(du, p->ws + p->o_z, p->G + l.w_off, p->G + l.b_off, B, l.N, l.K);
-    g.ad_p = p->P + l.w_off; g.ad_m = p->M + l.w_off; g.ad_v = p->V + l.w_off; g.ad_shadow = shadow ? shadow + l.w_off : nullptr;
-    g.ad = adam_hyper(h);
+    set_fused_opt(p, g, l.w_off, shadow, h);
     if ((rc = run_gemm(p, s, g))) return rc;
     RTable rt;
     if ((rc = sheet_front_bwd(p, s, rt, 9.0e6))) return rc;
@@ -1508,7 +1530,7 @@ static int train_step_impl(afr_plan* p, const int64_t* x, const int64_t* font, c
         if (!p->G) return fail(AFR_ESTATE, "plan has no bound gradient buffer");
         RTable rt;
         if ((rc = glyph1_fused(p, x, font, target, tdtype, rowmap, B, mean_elems, loss_accum, (hipStream_t)stream, rt))) return rc;
-        if (fuse_opt && p->M && p->V) {
+        if (fuse_opt && moments_bound(p)) {
             if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
             rc = reduce_and_step(p, (hipStream_t)stream, rt, h);
             p->wT_valid = rc == AFR_OK;                 // the reduce's AdamW wrote W1T / W2T beside the shadow
@@ -1525,7 +1547,7 @@ static int train_step_impl(afr_plan* p, const int64_t* x, const int64_t* font, c
         if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
         return sheet_fused_step(p, (hipStream_t)stream, h);
     }
-    if (fuse_opt && p->M && p->V && p->cfg.kind != AFR_KIND_PIXEL) {
+    if (fuse_opt && moments_bound(p) && p->cfg.kind != AFR_KIND_PIXEL) {
         if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
         const int n = afr_backward_stages(p);
         RTable rt;
@@ -1777,6 +1799,15 @@ extern "C" int afr_op_adamw_clip(float* p, const float* g, float* m, float* v, v
     DevGuard dg(device_of(p));
     HIPCHK(afr_launch_adamw(p, g, m, v, (bf16_t*)shadow, n, lr, wd, adam_hyper(AdamArgs{lr, b1, b2, eps, wd, t}), gscale, (hipStream_t)stream, sumsq,
                             max_norm));
+    return AFR_OK;
+}
+extern "C" int afr_op_lion(float* p, const float* g, float* m, void* shadow, int64_t n, float lr, float b1, float b2, float wd,
+                           float gscale, const float* sumsq, float max_norm, void* stream) {
+    if (!p || !g || !m) return fail(AFR_EINVAL, "null argument");
+    if (sumsq && (!(max_norm > 0.f) || std::isinf(max_norm))) return fail(AFR_EINVAL, "max_norm must be finite and > 0, got %g", (double)max_norm);
+    DevGuard dg(device_of(p));
+    HIPCHK(afr_launch_adamw(p, g, m, nullptr, (bf16_t*)shadow, n, lr, wd, adam_hyper(AdamArgs{lr, b1, b2, 0.f, wd, 1}, OPT_LION), gscale,
+                            (hipStream_t)stream, sumsq, max_norm, OPT_LION));
     return AFR_OK;
 }
 extern "C" int afr_op_mse_grad(int act_dtype, const void* u, const void* target, int tdtype, void* du, int64_t rows,

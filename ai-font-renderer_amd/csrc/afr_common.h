@@ -176,12 +176,40 @@ __device__ __forceinline__ bf16x4 adamw_quad(f32x4& p, f32x4& m, f32x4& v, f32x4
     return (bf16x4){(bf16_t)p[0], (bf16_t)p[1], (bf16_t)p[2], (bf16_t)p[3]};
 }
 
+// Optimizer kinds of a plan (afr_set_optimizer; the values of AFR_OPT_* in afr.h).  Like the loss kind, a template parameter of
+// every kernel that updates parameters: the OPT_ADAMW instantiations hold no Lion code and are the kernels they were.
+constexpr int OPT_ADAMW = 0, OPT_LION = 1;
+// Lion (Chen et al. 2023, "Symbolic Discovery of Optimization Algorithms"): one moment, the update is the sign of an interpolation.
+//   c = b1*m + (1-b1)*g;  p = p*decay - lr*sign(c)  (sign(0) = 0);  m = b2*m + (1-b2)*g        decay = 1 - lr*wd
+// Takes the AdamHyper of the step: decay, b1, b2 and step = lr (no bias correction: eps and rsqrt_bc2 are not read).  FMAs spelled
+// out as in adamw_elem, and this is the ONLY statement of the update: given the same p, m, g every site agrees bit for bit.
+__device__ __forceinline__ void lion_elem(float& p, float& m, float g, const AdamHyper& h) {
+    const float c = __builtin_fmaf(g - m, 1.f - h.b1, m);
+    const float s = (float)((c > 0.f) - (c < 0.f));
+    p = __builtin_fmaf(p, h.decay, -h.step * s);
+    m = __builtin_fmaf(g - m, 1.f - h.b2, m);
+}
+__device__ __forceinline__ bf16x4 lion_quad(f32x4& p, f32x4& m, f32x4 g, const AdamHyper& h) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { float a = p[r], b = m[r]; lion_elem(a, b, g[r], h); p[r] = a; m[r] = b; }
+    return (bf16x4){(bf16_t)p[0], (bf16_t)p[1], (bf16_t)p[2], (bf16_t)p[3]};
+}
+// The update of four elements by the kernel's optimizer kind (OPT_LION: v is neither read nor written)
+template <int OPT>
+__device__ __forceinline__ bf16x4 opt_quad(f32x4& p, f32x4& m, f32x4& v, f32x4 g, const AdamHyper& h) {
+    if constexpr (OPT == OPT_LION) return lion_quad(p, m, g, h);
+    else return adamw_quad(p, m, v, g, h);
+}
+
 // Runtime value -> template argument: f is a generic lambda and receives the value as a tag, `[&](auto rows) { k<rows()> ... }` or
 // `[&](auto t) { using T = typename decltype(t)::type; ... }`.  Nest them; instantiate only what exists.
 template <class T> struct TypeTag { using type = T; };
 template <class F> static inline auto with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 template <class F> static inline auto with_loss(int kind, F&& f) {
     return kind == LOSS_BCE ? f(std::integral_constant<int, LOSS_BCE>{}) : f(std::integral_constant<int, LOSS_MSE>{});
+}
+template <class F> static inline auto with_opt(int kind, F&& f) {
+    return kind == OPT_LION ? f(std::integral_constant<int, OPT_LION>{}) : f(std::integral_constant<int, OPT_ADAMW>{});
 }
 template <class F> static inline auto with_act(bool is_bf16, F&& f) { return is_bf16 ? f(TypeTag<bf16_t>{}) : f(TypeTag<float>{}); }
 
@@ -212,7 +240,10 @@ struct GemmParams {
     // walk are computed whole, each remaining tile as `splitk` K-slices parked in fix_ws (256 KiB per slice) and summed in
     // slice order by the slice block that arrives last (fix_cnt: one zeroed counter per tail tile, re-armed by the kernel).
     // The output then takes the full epilogue (bias / ReLU / mask / bf16), unlike plain split-K's f32 partial slabs.
-    int head_tiles = 0; float* fix_ws = nullptr; unsigned* fix_cnt = nullptr;
+    int head_tiles = 0;
+    int ad_kind = OPT_ADAMW;   // the fused optimizer's kind (OPT_*), read by the launchers only: it selects the instantiation.  (Declared
+                               // here it takes the padding ahead of fix_ws: no kernel argument of the AdamW kernels moves.)
+    float* fix_ws = nullptr; unsigned* fix_cnt = nullptr;
     // optional COOPERATIVE split-K (bf16, 256x256 tiles, grouped launches; gemm.hip gemm_bf16_256_body): the `splitk` (2, 4 or
     // 8) slice workgroups of a tile park their accumulators in coop_ws (256 KiB per slice, write-through), arrive on the
     // tile's counter and WAIT for each other (every workgroup of the launch is resident: one per CU); then slice z adds rows
@@ -268,6 +299,8 @@ struct RTable {
     int adam = 0; AdamHyper ad;
     const float* gbase; float* P; float* M; float* V; bf16_t* shadow;
     RSeg seg[AFR_RT_MAXSEG];
+    int kind = OPT_ADAMW;      // the fused optimizer's kind (OPT_*; V is not touched on OPT_LION), read by the launcher only -- last, so
+                               // that no kernel argument of the AdamW instantiation moves
 };
 void afr_rtable_add(RTable& t, float* dst, const float* src, int nslabs, long long stride, long long n);
 hipError_t afr_launch_reduce_group(const RTable& t, hipStream_t s);
@@ -275,8 +308,11 @@ hipError_t afr_launch_reduce_group(const RTable& t, hipStream_t s);
 // sumsq (device word, optional): clip by global gradient norm -- every lane derives coef = clip_coef(*sumsq, |grad_scale|, max_norm)
 // and the gradient enters the update as g * fl32(grad_scale * coef); a non-finite *sumsq leaves p/m/v/shadow untouched.
 // sumsq NULL: the unclipped kernel, bit for bit what it has always computed.
+// kind OPT_LION: the Lion update by the same kernel (v is not touched and may be NULL); the kernel folds decay = fl(1 - fl(lr * wd)),
+// uncontracted, which is what adam_hyper hands the other sites as h.decay.
 hipError_t afr_launch_adamw(float* p, const float* g, float* m, float* v, bf16_t* shadow, long long n, float lr, float wd,
-                            const AdamHyper& h, float grad_scale, hipStream_t s, const float* sumsq = nullptr, float max_norm = 0.f);
+                            const AdamHyper& h, float grad_scale, hipStream_t s, const float* sumsq = nullptr, float max_norm = 0.f,
+                            int kind = OPT_ADAMW);
 // Global gradient norm (elementwise.hip grad_sumsq_kernel): *out = sum of g[i]^2 over the tensor elements -- the (offset, numel)
 // segments of the table `segs` (at most 256), flat-buffer padding excluded -- that lie inside [lo, hi) of g; lo, hi multiples of 4.
 // scratch: AFR_SUMSQ_SCRATCH_FLOATS floats, zero before the first launch and left zero (block partials + arrival counter, the loss

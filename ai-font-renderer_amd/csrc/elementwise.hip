@@ -70,13 +70,14 @@ __device__ __forceinline__ float4 slab_sum(const float* src, long long stride, i
     }
     return a;
 }
+template <int OPT>
 __device__ __forceinline__ void reduce_finish(const RTable& t, const RSeg& sg, long long i, float4 a, f32x4 pp, f32x4 mm, f32x4 vv) {
     if (t.adam) {
         const long long off = (sg.dst - t.gbase) + 4 * i;
-        const bf16x4 o = adamw_quad(pp, mm, vv, (f32x4){a.x, a.y, a.z, a.w}, t.ad);
+        const bf16x4 o = opt_quad<OPT>(pp, mm, vv, (f32x4){a.x, a.y, a.z, a.w}, t.ad);
         *reinterpret_cast<f32x4*>(t.P + off) = pp;
         *reinterpret_cast<f32x4*>(t.M + off) = mm;
-        *reinterpret_cast<f32x4*>(t.V + off) = vv;
+        if constexpr (OPT == OPT_ADAMW) *reinterpret_cast<f32x4*>(t.V + off) = vv;
         if (t.shadow) *reinterpret_cast<bf16x4*>(t.shadow + off) = o;
         if (sg.shT) {                      // 4 consecutive k of one row n (tK is a multiple of 4)
             const int n = (int)((4 * i) / sg.tK), k = (int)(4 * i - (long long)n * sg.tK);
@@ -87,6 +88,8 @@ __device__ __forceinline__ void reduce_finish(const RTable& t, const RSeg& sg, l
         reinterpret_cast<float4*>(sg.dst)[i] = a;
     }
 }
+// OPT: the optimizer kind of a fused step (t.adam); the OPT_LION instantiation neither loads nor stores V
+template <int OPT = OPT_ADAMW>
 __global__ __launch_bounds__(256) void reduce_group_kernel(RTable t) {
     int si = 0;
     for (int k = 1; k < t.nseg; ++k) if ((int)blockIdx.x >= t.seg[k].blk0) si = k;
@@ -105,7 +108,8 @@ __global__ __launch_bounds__(256) void reduce_group_kernel(RTable t) {
             if (live) {
                 if (grp == 0 && t.adam) {
                     const long long off = (sg.dst - t.gbase) + 4 * i;
-                    pp = *reinterpret_cast<f32x4*>(t.P + off); mm = *reinterpret_cast<f32x4*>(t.M + off); vv = *reinterpret_cast<f32x4*>(t.V + off);
+                    pp = *reinterpret_cast<f32x4*>(t.P + off); mm = *reinterpret_cast<f32x4*>(t.M + off);
+                    if constexpr (OPT == OPT_ADAMW) vv = *reinterpret_cast<f32x4*>(t.V + off);
                 }
                 const int s0 = grp * per, s1 = min(sg.nslabs, s0 + per);
                 a = slab_sum(sg.src + 4 * i, sg.stride, s0, s1);
@@ -115,7 +119,7 @@ __global__ __launch_bounds__(256) void reduce_group_kernel(RTable t) {
             if (grp == 0 && live) {
 #pragma unroll
                 for (int g = 0; g < 3; ++g) { const float4 v = part[g][col]; a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
-                reduce_finish(t, sg, i, a, pp, mm, vv);
+                reduce_finish<OPT>(t, sg, i, a, pp, mm, vv);
             }
             __syncthreads();
         }
@@ -124,10 +128,11 @@ __global__ __launch_bounds__(256) void reduce_group_kernel(RTable t) {
     for (long long i = (long long)(blockIdx.x - sg.blk0) * 256 + threadIdx.x; i < sg.n4; i += (long long)sg.nblk * 256) {
         if (t.adam) {   // issued ahead of the slab loads so that everything this element needs is in flight at once
             const long long off = (sg.dst - t.gbase) + 4 * i;
-            pp = *reinterpret_cast<f32x4*>(t.P + off); mm = *reinterpret_cast<f32x4*>(t.M + off); vv = *reinterpret_cast<f32x4*>(t.V + off);
+            pp = *reinterpret_cast<f32x4*>(t.P + off); mm = *reinterpret_cast<f32x4*>(t.M + off);
+            if constexpr (OPT == OPT_ADAMW) vv = *reinterpret_cast<f32x4*>(t.V + off);
         }
         const float4 a = slab_sum(sg.src + 4 * i, sg.stride, 0, sg.nslabs);
-        reduce_finish(t, sg, i, a, pp, mm, vv);
+        reduce_finish<OPT>(t, sg, i, a, pp, mm, vv);
     }
 }
 void afr_rtable_add(RTable& t, float* dst, const float* src, int nslabs, long long stride, long long n) {
@@ -147,7 +152,7 @@ void afr_rtable_add(RTable& t, float* dst, const float* src, int nslabs, long lo
 hipError_t afr_launch_reduce_group(const RTable& t, hipStream_t s) {
     if (t.overflow) return hipErrorInvalidValue;
     if (t.nseg == 0) return hipSuccess;
-    hipLaunchKernelGGL(reduce_group_kernel, dim3(t.nblocks), dim3(256), 0, s, t);
+    with_opt(t.adam ? t.kind : OPT_ADAMW, [&](auto opt) { hipLaunchKernelGGL(reduce_group_kernel<opt()>, dim3(t.nblocks), dim3(256), 0, s, t); });
     return hipGetLastError();
 }
 
@@ -159,6 +164,9 @@ hipError_t afr_launch_reduce_group(const RTable& t, hipStream_t s) {
 // itself (clip_coef: the same few instructions everywhere, so every slice and every rank agrees); the gradient enters the update
 // as g * fl32(gscale * coef) -- one rounded factor, then one rounded product that is NOT contracted into adamw_quad's FMAs
 // (mul_rn).  A non-finite *sumsq skips the step: nothing is written.  The CLIP = false instantiation is the kernel as it was.
+// OPT_LION (afr_set_optimizer): the same walk with lion_quad on p, g, m -- v is neither loaded nor stored, 20 (+2) bytes per element;
+// step_size carries lr.  Its scalars are folded without contraction, clipped or not: decay = fl(1 - fl(lr * wd)) as the host hands it
+// to the fused sites, and the gradient enters as fl(g * gscale), so that every Lion site sees the same decay and the same g.
 __device__ __forceinline__ float clip_coef(float sumsq, float gscale_abs, float max_norm, float& total_norm) {
     total_norm = gscale_abs * sqrtf(sumsq);
     return fminf(1.f, max_norm / (total_norm + 1e-6f));      // torch.nn.utils.clip_grad_norm_, in f32
@@ -168,13 +176,13 @@ __device__ __forceinline__ float mul_rn(float a, float b) {
     return a * b;
 }
 __device__ __forceinline__ bool finite_f(float x) { return fabsf(x) <= 3.402823466e38f; }
-template <bool CLIP>
+template <bool CLIP, int OPT = OPT_ADAMW>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v,
                                                     bf16_t* __restrict__ shadow, long long n4, float lr, float b1,
                                                     float b2, float eps, float wd, float step_size, float rsqrt_bc2,
                                                     float gscale, const float* __restrict__ sumsq, float max_norm) {
-    const AdamHyper h{1.f - lr * wd, b1, b2, eps, step_size, rsqrt_bc2};
+    const AdamHyper h{OPT == OPT_LION ? 1.f - mul_rn(lr, wd) : 1.f - lr * wd, b1, b2, eps, step_size, rsqrt_bc2};
     if constexpr (CLIP) {
         const float ss = *sumsq;
         if (!finite_f(ss)) return;
@@ -185,25 +193,26 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
         const float4 p4 = reinterpret_cast<float4*>(p)[i];
         const float4 gg = reinterpret_cast<const float4*>(g)[i];
         const float4 m4 = reinterpret_cast<float4*>(m)[i];
-        const float4 v4 = reinterpret_cast<float4*>(v)[i];
+        float4 v4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (OPT == OPT_ADAMW) v4 = reinterpret_cast<float4*>(v)[i];
         f32x4 pp = {p4.x, p4.y, p4.z, p4.w}, mm = {m4.x, m4.y, m4.z, m4.w}, vv = {v4.x, v4.y, v4.z, v4.w};
-        const f32x4 ge = CLIP ? (f32x4){mul_rn(gg.x, gscale), mul_rn(gg.y, gscale), mul_rn(gg.z, gscale), mul_rn(gg.w, gscale)}
-                              : (f32x4){gg.x * gscale, gg.y * gscale, gg.z * gscale, gg.w * gscale};
-        const bf16x4 o = adamw_quad(pp, mm, vv, ge, h);
+        const f32x4 ge = (CLIP || OPT == OPT_LION) ? (f32x4){mul_rn(gg.x, gscale), mul_rn(gg.y, gscale), mul_rn(gg.z, gscale), mul_rn(gg.w, gscale)}
+                                                   : (f32x4){gg.x * gscale, gg.y * gscale, gg.z * gscale, gg.w * gscale};
+        const bf16x4 o = opt_quad<OPT>(pp, mm, vv, ge, h);
         reinterpret_cast<float4*>(p)[i] = make_float4(pp[0], pp[1], pp[2], pp[3]);
         reinterpret_cast<float4*>(m)[i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
-        reinterpret_cast<float4*>(v)[i] = make_float4(vv[0], vv[1], vv[2], vv[3]);
+        if constexpr (OPT == OPT_ADAMW) reinterpret_cast<float4*>(v)[i] = make_float4(vv[0], vv[1], vv[2], vv[3]);
         if (shadow) reinterpret_cast<bf16x4*>(shadow)[i] = o;
     }
 }
 hipError_t afr_launch_adamw(float* p, const float* g, float* m, float* v, bf16_t* shadow, long long n, float lr, float wd,
-                            const AdamHyper& h, float grad_scale, hipStream_t s, const float* sumsq, float max_norm) {
+                            const AdamHyper& h, float grad_scale, hipStream_t s, const float* sumsq, float max_norm, int kind) {
     if (n <= 0) return hipSuccess;
     if (n & 3) return hipErrorInvalidValue;   // flat buffers are padded to multiples of 64
-    with_bool(sumsq != nullptr, [&](auto clip) {
-        hipLaunchKernelGGL(adamw_kernel<clip()>, dim3(grid_for(n / 4, 256, 4096)), dim3(256), 0, s, p, g, m, v, shadow, n / 4, lr,
+    with_bool(sumsq != nullptr, [&](auto clip) { with_opt(kind, [&](auto opt) {
+        hipLaunchKernelGGL((adamw_kernel<clip(), opt()>), dim3(grid_for(n / 4, 256, 4096)), dim3(256), 0, s, p, g, m, v, shadow, n / 4, lr,
                            h.b1, h.b2, h.eps, wd, h.step, h.rsqrt_bc2, grad_scale, sumsq, max_norm);
-    });
+    }); });
     return hipGetLastError();
 }
 

@@ -132,8 +132,9 @@ __device__ __forceinline__ void colsum_store(const GemmParams& p, float* smem, c
 // bias, ReLU, ReLU mask, split-K slabs, bf16 output, fused clamp/MSE/du, fused AdamW; smem: >= 16 + 256 floats of scratch
 // TROWS: the fused loss' targets are rows p.loss.rowmap[m] of a resident data set (its own instantiation: the dense kernels carry
 // no row-map code).  LOSS: the fused loss' kind, likewise an instantiation of its own (LOSS_BCE: sigmoid head + BCE on the logits,
-// bce_logits_elem; the LOSS_MSE kernels carry none of it)
-template <bool TROWS = false, int LOSS = LOSS_MSE>
+// bce_logits_elem; the LOSS_MSE kernels carry none of it).  OPT: the fused optimizer's kind, likewise (OPT_LION: lion_elem on p and m,
+// v untouched; the weight-gradient layout only)
+template <bool TROWS = false, int LOSS = LOSS_MSE, int OPT = OPT_ADAMW>
 __device__ __forceinline__ void tile_epilogue(const GemmParams& p, const f32x16 (&acc)[2][2], const int m0, const int n0, const int z,
                                               const int tid, float* smem) {
     const int lane = tid & 63, wid = tid >> 6;
@@ -171,9 +172,15 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& p, const f32x16 
                 }
                 if (p.ad_p) {                          // fused AdamW on weight element (m, n); v is its gradient
                     const size_t wi = (size_t)m * p.ldc + n;
-                    float pp = p.ad_p[wi], mm = p.ad_m[wi], vv = p.ad_v[wi];
-                    adamw_elem_plain(pp, mm, vv, v, p.ad);
-                    p.ad_p[wi] = pp; p.ad_m[wi] = mm; p.ad_v[wi] = vv;
+                    if constexpr (OPT == OPT_LION) {
+                        float pp = p.ad_p[wi], mm = p.ad_m[wi];
+                        lion_elem(pp, mm, v, p.ad);
+                        p.ad_p[wi] = pp; p.ad_m[wi] = mm;
+                    } else {
+                        float pp = p.ad_p[wi], mm = p.ad_m[wi], vv = p.ad_v[wi];
+                        adamw_elem_plain(pp, mm, vv, v, p.ad);
+                        p.ad_p[wi] = pp; p.ad_m[wi] = mm; p.ad_v[wi] = vv;
+                    }
                 } else if (out_bf16) Cb[(size_t)m * p.ldc + n] = f32_to_bf16(v);
                 else Cf[(size_t)m * p.ldc + n] = v;
             }
@@ -187,7 +194,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& p, const f32x16 
     }
 }
 
-template <int ALAY, int BLAY, bool TROWS = false, int LOSS = LOSS_MSE>
+template <int ALAY, int BLAY, bool TROWS = false, int LOSS = LOSS_MSE, int OPT = OPT_ADAMW>
 __global__ __launch_bounds__(256) void gemm_f32(GemmParams p) {
     constexpr int LDA = Lds<ALAY>::LD, LDB = Lds<BLAY>::LD;
     constexpr int TILE = BK * LDA + BK * LDB;
@@ -260,7 +267,7 @@ __global__ __launch_bounds__(256) void gemm_f32(GemmParams p) {
         smem[tid] = cs;
         colsum_store(p, smem, tid, m0, z, 2);
     }
-    tile_epilogue<TROWS, LOSS>(p, acc, m0, n0, z, tid, smem);
+    tile_epilogue<TROWS, LOSS, OPT>(p, acc, m0, n0, z, tid, smem);
 }
 }  // namespace f32k
 
@@ -334,7 +341,7 @@ __device__ __forceinline__ bf16x8 frag(const char* S, int xb, int ks, int lane) 
     return *reinterpret_cast<const bf16x8*>(S + xoff(xb + (lane & 31), 2 * ks + (lane >> 5)));
 }
 
-template <int ALAY, int BLAY, bool TROWS = false, int LOSS = LOSS_MSE>
+template <int ALAY, int BLAY, bool TROWS = false, int LOSS = LOSS_MSE, int OPT = OPT_ADAMW>
 __global__ __launch_bounds__(256, 2) void gemm_bf16x3(GemmParams p) {
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -423,7 +430,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3(GemmParams p) {
         for (int e = 0; e < 4; ++e) sf[kq * 128 + xb + e] = cs[e];
         f32k::colsum_store(p, sf, tid, m0, z, 8);
     }
-    f32k::tile_epilogue<TROWS, LOSS>(p, acc, m0, n0, z, tid, sf);
+    f32k::tile_epilogue<TROWS, LOSS, OPT>(p, acc, m0, n0, z, tid, sf);
 }
 }  // namespace x3k
 
@@ -548,7 +555,9 @@ __device__ __forceinline__ void epilogue_bias(const GemmParams& p, const int nb0
 // (TROWS: the fused loss' targets are rows p.loss.rowmap[m] of a resident data set, read in place -- its own instantiation of the
 // forward-layout ring kernels, so that the dense kernels carry no row-map code)
 // (LOSS: the fused loss' kind, an instantiation of its own as well: the LOSS_MSE kernels carry no BCE code)
-template <int ALAY, int BLAY, int WM, bool SCALE = false, bool EARLYB_ = true, bool TROWS = false, int LOSS = LOSS_MSE, class ACC>      // SCALE: the accumulators are multiplied by p.out_scale first (fp8 per-tensor scales)
+// (OPT: the fused optimizer's kind, weight-gradient layout only: the OPT_LION instantiation prefetches and stores p, m and the shadow,
+// never v, and the OPT_ADAMW ones carry no Lion code)
+template <int ALAY, int BLAY, int WM, bool SCALE = false, bool EARLYB_ = true, bool TROWS = false, int LOSS = LOSS_MSE, int OPT = OPT_ADAMW, class ACC>      // SCALE: the accumulators are multiplied by p.out_scale first (fp8 per-tensor scales)
 __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC& acc_at, const int mb, const int nb0, const int z,
                                                  float* Wt, const int lane, float& lsum, const float* lut255 = nullptr,
                                                  const float (*pre_bias)[8] = nullptr) {
@@ -670,11 +679,14 @@ __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC&
         // in LDS.  (Issuing some before the K loop was slower: vmcnt is in-order, so the ring's counted waits then also wait
         // for these HBM loads.)
         constexpr bool ADAM = (ALAY == 1 && BLAY == 1);
-        constexpr int ADF = !ADAM ? 1 : (WM == 2) ? 14 : 4;    // 14: the deepest that allocates without scratch
+        static_assert(OPT == OPT_ADAMW || ADAM, "a fused Lion step: the weight-gradient layout");
+        constexpr bool LION = OPT == OPT_LION;
+        // 14: the deepest that allocates without scratch (AdamW: 3 x 16 B per pass); Lion's 2 x 16 B per pass fit all 16 passes
+        constexpr int ADF = !ADAM ? 1 : (WM == 2) ? (LION ? 16 : 14) : 4;
         const int c4 = lane & 15;
         const int nf = nb0 + 4 * c4;
         const bool okc = nf < p.N;
-        float4 qp[ADF], qm[ADF], qv[ADF];
+        float4 qp[ADF], qm[ADF], qv[LION ? 1 : ADF];
         // The optimizer state is read as STREAMING data (buffer loads with the nt bit): 3 GB of p/m/v pass through the L2s during
         // R0's weight-gradient product, and without the hint they displace the operand slabs the 64 concurrent tiles of an XCD
         // share (PMC: 2.37 GB fetched per launch against 1.47 GB of state + 52 MB of operands).  Measured on R0: 655 -> 602 us.
@@ -683,14 +695,14 @@ __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC&
         const bool adam_ld = ADAM && p.ad_p != nullptr;
         const __amdgpu_buffer_rsrc_t rp_ = __builtin_amdgcn_make_buffer_rsrc((void*)(adam_ld ? p.ad_p + tile0 : nullptr), 0, 0x7FFFFFFF, 0x00020000);
         const __amdgpu_buffer_rsrc_t rm_ = __builtin_amdgcn_make_buffer_rsrc((void*)(adam_ld ? p.ad_m + tile0 : nullptr), 0, 0x7FFFFFFF, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rv_ = __builtin_amdgcn_make_buffer_rsrc((void*)(adam_ld ? p.ad_v + tile0 : nullptr), 0, 0x7FFFFFFF, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rv_ = __builtin_amdgcn_make_buffer_rsrc((void*)(adam_ld && !LION ? p.ad_v + tile0 : nullptr), 0, 0x7FFFFFFF, 0x00020000);
         auto load_f = [&](int ps, int buf) {
             const int m = mb + ps * 4 + (lane >> 4);
             if (m < p.M && okc) {
                 const unsigned vo = (unsigned)(((ps * 4 + (lane >> 4)) * p.ldc + 4 * c4) * 4);
                 qp[buf] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rp_, vo, 0, 2));
                 qm[buf] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rm_, vo, 0, 2));
-                qv[buf] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rv_, vo, 0, 2));
+                if constexpr (!LION) qv[buf] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rv_, vo, 0, 2));
             }
         };
         const bool adam = ADAM && p.ad_p != nullptr;
@@ -715,11 +727,12 @@ __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC&
             }
             if (adam) {
                 const int bf = ps % ADF;
-                f32x4 np = {qp[bf].x, qp[bf].y, qp[bf].z, qp[bf].w}, nm = {qm[bf].x, qm[bf].y, qm[bf].z, qm[bf].w}, nv = {qv[bf].x, qv[bf].y, qv[bf].z, qv[bf].w};
-                const bf16x4 o = adamw_quad(np, nm, nv, g, p.ad);
+                f32x4 np = {qp[bf].x, qp[bf].y, qp[bf].z, qp[bf].w}, nm = {qm[bf].x, qm[bf].y, qm[bf].z, qm[bf].w}, nv = {0.f, 0.f, 0.f, 0.f};
+                if constexpr (!LION) nv = (f32x4){qv[bf].x, qv[bf].y, qv[bf].z, qv[bf].w};
+                const bf16x4 o = opt_quad<OPT>(np, nm, nv, g, p.ad);
                 __builtin_nontemporal_store(np, reinterpret_cast<f32x4*>(p.ad_p + wi));
                 __builtin_nontemporal_store(nm, reinterpret_cast<f32x4*>(p.ad_m + wi));
-                __builtin_nontemporal_store(nv, reinterpret_cast<f32x4*>(p.ad_v + wi));
+                if constexpr (!LION) __builtin_nontemporal_store(nv, reinterpret_cast<f32x4*>(p.ad_v + wi));
                 if (p.ad_shadow) __builtin_nontemporal_store(o, reinterpret_cast<bf16x4*>(p.ad_shadow + wi));
             } else {
                 nt_st4(Cf + wi, make_float4(g[0], g[1], g[2], g[3]));
@@ -786,10 +799,10 @@ __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC&
     }
 }
 
-template <int ALAY, int BLAY, int WM, bool SCALE = false, bool EARLYB_ = true, bool TROWS = false, int LOSS = LOSS_MSE>
+template <int ALAY, int BLAY, int WM, bool SCALE = false, bool EARLYB_ = true, bool TROWS = false, int LOSS = LOSS_MSE, int OPT = OPT_ADAMW>
 __device__ __forceinline__ void wave_epilogue(const GemmParams& p, const f32x4 (&acc)[4][4], const int mb, const int nb0, const int z,
                                               float* Wt, const int lane, float& lsum, const float* lut255 = nullptr) {
-    wave_epilogue_at<ALAY, BLAY, WM, SCALE, EARLYB_, TROWS, LOSS>(p, [&](int i, int j) { return acc[i][j]; }, mb, nb0, z, Wt, lane, lsum, lut255);
+    wave_epilogue_at<ALAY, BLAY, WM, SCALE, EARLYB_, TROWS, LOSS, OPT>(p, [&](int i, int j) { return acc[i][j]; }, mb, nb0, z, Wt, lane, lsum, lut255);
 }
 
 // Finish of one wave's 16 x 64 f32 strip of a weight gradient (cooperative split-K, gemm_bf16_256_body): v[j] holds rows
@@ -815,7 +828,8 @@ __device__ __forceinline__ void strip_prefetch(const GemmParams& p, const int mb
         dma16(rv, lds + (3 * ps + 2) * 1024, off);
     }
 }
-// pre: the strip's p/m/v were prefetched into Wt (strip_prefetch); else they are loaded here
+// pre: the strip's p/m/v were prefetched into Wt (strip_prefetch); else they are loaded here.  OPT_LION: v is neither read nor written
+template <int OPT = OPT_ADAMW>
 __device__ __forceinline__ void strip_finish(const GemmParams& p, const f32x4 (&v)[4], const int mb, const int nb0, float* Wt, const int lane,
                                              const bool pre) {
     const int ml = lane & 15;
@@ -837,14 +851,14 @@ __device__ __forceinline__ void strip_finish(const GemmParams& p, const f32x4 (&
         if (m >= p.M || !okc) continue;
         const size_t wi = (size_t)m * p.ldc + nf;
         if (adam) {
-            float4 qp, qm, qv;
-            if (pre) { qp = pmv[(3 * ps + 0) * 64]; qm = pmv[(3 * ps + 1) * 64]; qv = pmv[(3 * ps + 2) * 64]; }
-            else { qp = ADLD(p.ad_p + wi); qm = ADLD(p.ad_m + wi); qv = ADLD(p.ad_v + wi); }
+            float4 qp, qm, qv = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (pre) { qp = pmv[(3 * ps + 0) * 64]; qm = pmv[(3 * ps + 1) * 64]; if constexpr (OPT == OPT_ADAMW) qv = pmv[(3 * ps + 2) * 64]; }
+            else { qp = ADLD(p.ad_p + wi); qm = ADLD(p.ad_m + wi); if constexpr (OPT == OPT_ADAMW) qv = ADLD(p.ad_v + wi); }
             f32x4 np = {qp.x, qp.y, qp.z, qp.w}, nm = {qm.x, qm.y, qm.z, qm.w}, nv = {qv.x, qv.y, qv.z, qv.w};
-            const bf16x4 o = adamw_quad(np, nm, nv, g, p.ad);
+            const bf16x4 o = opt_quad<OPT>(np, nm, nv, g, p.ad);
             __builtin_nontemporal_store(np, reinterpret_cast<f32x4*>(p.ad_p + wi));
             __builtin_nontemporal_store(nm, reinterpret_cast<f32x4*>(p.ad_m + wi));
-            __builtin_nontemporal_store(nv, reinterpret_cast<f32x4*>(p.ad_v + wi));
+            if constexpr (OPT == OPT_ADAMW) __builtin_nontemporal_store(nv, reinterpret_cast<f32x4*>(p.ad_v + wi));
             if (p.ad_shadow) __builtin_nontemporal_store(o, reinterpret_cast<bf16x4*>(p.ad_shadow + wi));
         } else {
             nt_st4(Cf + wi, make_float4(g[0], g[1], g[2], g[3]));
@@ -859,7 +873,8 @@ template <int WM> struct RingGeom {
 // passes its own blockIdx / gridDim; a grouped launch (gemm_bf16_group) a sub-range of its grid.
 // GA: the k-contiguous A operand's rows are gathered through p.a_rowmap (ALAY == 0, WM == 4 only)
 // TROWS: the fused loss reads its targets through p.loss.rowmap (forward layout only)
-template <int ALAY, int BLAY, int WM, int GA = 0, bool TROWS = false, int LOSS = LOSS_MSE>
+// OPT: the kind of a fused optimizer step (p.ad_p; weight-gradient layout)
+template <int ALAY, int BLAY, int WM, int GA = 0, bool TROWS = false, int LOSS = LOSS_MSE, int OPT = OPT_ADAMW>
 __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p, const int bid, const int nblk, char* smem) {
     static_assert(!GA || (ALAY == 0 && WM == 4), "row gather: k-contiguous A on the 256x128 ring kernel");
     static_assert(!TROWS || (ALAY == 0 && BLAY == 0 && !GA), "row-mapped loss targets: the forward layout");
@@ -1152,7 +1167,7 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p, const int bi
         __syncthreads();
         lut255 = l;
     }
-    wave_epilogue<ALAY, BLAY, WM, false, true, TROWS, LOSS>(p, acc, m0 + wm * 64, n0 + wn * 64, z, reinterpret_cast<float*>(smem) + wave * 4096, lane, lsum, lut255);
+    wave_epilogue<ALAY, BLAY, WM, false, true, TROWS, LOSS, OPT>(p, acc, m0 + wm * 64, n0 + wn * 64, z, reinterpret_cast<float*>(smem) + wave * 4096, lane, lsum, lut255);
     if (mse) {
         float* red = reinterpret_cast<float*>(smem);
         __syncthreads();                       // every wave is done with its staging tile
@@ -1197,7 +1212,7 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p, const int bi
 //     per K-tile, in phase 3 ahead of its first barrier: the four newest sub-tiles (tile t+2) stay in flight, tile t+1 has
 //     landed; its first read is two barriers later (the trailing group's wait sits one barrier after the leading one's).
 // GB: the k-strided B operand's rows (its k index: batch rows of a weight-gradient product) are gathered through p.b_rowmap
-template <int ALAY, int BLAY, int GB = 0>
+template <int ALAY, int BLAY, int GB = 0, int OPT = OPT_ADAMW>
 __device__ __forceinline__ void gemm_bf16_256_body(const GemmParams& p, const int bid, const int nblk, char* smem) {
     static_assert(!GB || BLAY == 1, "row gather: k-strided B on the 256x256 kernel");
     constexpr int BM = 256, BNN = 256;
@@ -1500,7 +1515,7 @@ __device__ __forceinline__ void gemm_bf16_256_body(const GemmParams& p, const in
 #pragma unroll
                     for (int zq = 0; zq < 4; ++zq) v[j] += q[zq][j];
             }
-            strip_finish(p, v, m0 + wr * 128 + 16 * i, n0 + wc * 64, Wt, lane, false);
+            strip_finish<OPT>(p, v, m0 + wr * 128 + 16 * i, n0 + wc * 64, Wt, lane, false);
         }
 #ifdef AFR_GEMM_TIMING
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1550,7 +1565,7 @@ __device__ __forceinline__ void gemm_bf16_256_body(const GemmParams& p, const in
     if (ALAY == 0 && BLAY == 0) epilogue_bias(p, n0 + wc * 64, lane, bia);       // one request for both halves, ahead of the first park
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        wave_epilogue_at<ALAY, BLAY, 4, false, true>(p, [&](int i, int j) {
+        wave_epilogue_at<ALAY, BLAY, 4, false, true, false, LOSS_MSE, (ALAY == 1 && BLAY == 1) ? OPT : OPT_ADAMW>(p, [&](int i, int j) {
             f32x4 v;
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = h ? acc[4 + i][j][r] : acc[i][j][r];
@@ -1564,10 +1579,10 @@ __device__ __forceinline__ void gemm_bf16_256_body(const GemmParams& p, const in
 #endif
 }
 
-template <int ALAY, int BLAY, int WM, int GA = 0, bool TROWS = false, int LOSS = LOSS_MSE>
+template <int ALAY, int BLAY, int WM, int GA = 0, bool TROWS = false, int LOSS = LOSS_MSE, int OPT = OPT_ADAMW>
 __global__ __launch_bounds__(128 * WM, 2) void gemm_bf16(GemmParams p) {
     __shared__ __attribute__((aligned(16))) char smem[RingGeom<WM>::LDS_BYTES];
-    gemm_bf16_body<ALAY, BLAY, WM, GA, TROWS, LOSS>(p, blockIdx.x, gridDim.x, smem);
+    gemm_bf16_body<ALAY, BLAY, WM, GA, TROWS, LOSS, OPT>(p, blockIdx.x, gridDim.x, smem);
 }
 
 // Several independent products in ONE launch (a layer's weight gradient and input gradient both consume the same dy):
@@ -1602,6 +1617,18 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_group256(GemmGroup g) {
             if (p.b_rowmap) { gemm_bf16_256_body<1, 1, 1>(p, bid, nblk, smem); return; }
         }
         gemm_bf16_256_body<a(), b()>(p, bid, nblk, smem);
+    });
+}
+// The same launch on a Lion plan: the cooperative weight-gradient member's split-K tail applies lion_quad (strip_finish<OPT_LION>);
+// the other members carry no optimizer.  (A kernel of its own, not a template argument of the one above: that one keeps its symbol
+// and its code.)
+__global__ __launch_bounds__(512, 2) void gemm_bf16_group256_lion(GemmGroup g) {
+    __shared__ __attribute__((aligned(16))) char smem[10 * SUB];
+    group_member(g, [&](const GemmParams& p, int bid, int nblk, auto a, auto b) {
+        if constexpr (a() && b()) {
+            if (p.b_rowmap) gemm_bf16_256_body<1, 1, 1, OPT_LION>(p, bid, nblk, smem);
+            else gemm_bf16_256_body<1, 1, 0, OPT_LION>(p, bid, nblk, smem);
+        } else gemm_bf16_256_body<a(), b()>(p, bid, nblk, smem);
     });
 }
 
@@ -1983,7 +2010,11 @@ static hipError_t launch_grouped(const GemmParams* ps, int n, bool tile256, bool
         total += pad8 ? (nb + 7) & ~7 : nb;
     }
     g.blk0[n] = total;
-    if (tile256) hipLaunchKernelGGL(bf16k::gemm_bf16_group256, dim3(total), dim3(512), 0, s, g);
+    bool lion = false;           // (only a cooperative weight-gradient member carries a fused optimizer step into a grouped launch)
+    for (int i = 0; i < n; ++i) lion = lion || (ps[i].ad_p && ps[i].ad_kind == OPT_LION);
+    if (lion && !tile256) return hipErrorInvalidValue;
+    if (lion) hipLaunchKernelGGL(bf16k::gemm_bf16_group256_lion, dim3(total), dim3(512), 0, s, g);
+    else if (tile256) hipLaunchKernelGGL(bf16k::gemm_bf16_group256, dim3(total), dim3(512), 0, s, g);
     else hipLaunchKernelGGL(bf16k::gemm_bf16_group, dim3(total), dim3(512), 0, s, g);
     return hipGetLastError();
 }
@@ -2051,7 +2082,15 @@ hipError_t afr_launch_gemm(int dtype, const GemmParams& p_in, hipStream_t s) {
         } else if (dtype == AFR_BF16X3) launch(x3k::gemm_bf16x3<al(), bl(), tr(), loss()>, 256);
         else launch(f32k::gemm_f32<al(), bl(), tr(), loss()>, 256);
     };
-    if (p.a_rowmap) launch(bf16k::gemm_bf16<0, 0, 4, 1>, 512);
+    if (p.ad_p && p.ad_kind == OPT_LION) {
+        // a fused Lion step: the weight-gradient layout, no fused loss; bf16 on the 128x128 ring kernel (bf16_use_wide)
+        if (!a || !b || p.loss.target || p.a_rowmap || wide) return hipErrorInvalidValue;
+        constexpr int MSE = LOSS_MSE;
+        if (dtype == AFR_BF16) launch(bf16k::gemm_bf16<1, 1, 2, 0, false, MSE, OPT_LION>, 256);
+        else if (dtype == AFR_BF16X3) launch(x3k::gemm_bf16x3<1, 1, false, MSE, OPT_LION>, 256);
+        else launch(f32k::gemm_f32<1, 1, false, MSE, OPT_LION>, 256);
+    } else if (p.ad_p && p.ad_kind != OPT_ADAMW) return hipErrorInvalidValue;
+    else if (p.a_rowmap) launch(bf16k::gemm_bf16<0, 0, 4, 1>, 512);
     else if (bce || trows)
         with_bool(trows, [&](auto tr) { with_loss(bce ? LOSS_BCE : LOSS_MSE, [&](auto loss) { variant(std::false_type{}, std::false_type{}, tr, loss); }); });
     else

@@ -64,8 +64,10 @@ class Engine:
     state_dict order, so checkpoints interchange with the reference (helpers.py:76-105)."""
 
     def __init__(self, cfg, dtype="f32", max_batch=1024, device=None, seed=42, rank=0, with_optimizer=True, flags=0, micro_batch=None,
-                 loss="mse", max_grad_norm=None):
-        """max_grad_norm: clip the gradients by their global L2 norm inside every optimizer step (set_grad_clip); None or 0 = off.
+                 loss="mse", max_grad_norm=None, optimizer="adamw"):
+        """optimizer: "adamw" (torch.optim.AdamW, the reference's) or "lion" (one moment, sign update: include/afr.h afr_set_optimizer);
+        every optimizer step of the engine follows it, and a Lion engine allocates no exp_avg_sq.
+        max_grad_norm: clip the gradients by their global L2 norm inside every optimizer step (set_grad_clip); None or 0 = off.
         micro_batch: train_step / forward_loss + backward of a batch larger than this many samples run as micro-steps of at
         most that many, their gradients summed (gradient accumulation: the saved activations of BASELINE configs[4]'s 2048
         glyphs per GPU would be 800 GB; 32 at a time they are 12.6 GB).  The plan is then sized for micro_batch, not max_batch."""
@@ -73,6 +75,8 @@ class Engine:
             raise RuntimeError("ai_font_renderer_amd.Engine needs an MI355X: the hot path has no CPU fallback")
         _lib.loss_kind(loss)          # ValueError for anything but "mse" | "bce"
         self.loss = loss
+        _lib.opt_kind(optimizer)      # ValueError for anything but "adamw" | "lion"
+        self.optimizer = optimizer
         self.lib = _lib.lib()
         self.micro_batch = int(micro_batch) if micro_batch else None
         if self.micro_batch:
@@ -92,7 +96,7 @@ class Engine:
             self.flat_params = torch.zeros(n, dtype=torch.float32, device=self.device)
             self.flat_grads = torch.zeros(n, dtype=torch.float32, device=self.device)
             self.exp_avg = torch.zeros(n, dtype=torch.float32, device=self.device) if with_optimizer else None
-            self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=self.device) if with_optimizer else None
+            self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=self.device) if with_optimizer and optimizer == "adamw" else None
             self.loss_accum = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._bind()
         self.layout = []
@@ -130,6 +134,7 @@ class Engine:
                                      _ptr(self.exp_avg_sq), _ptr(self.workspace), self.ws_bytes))
         self._bind_ds()
         self._apply_clip()
+        _lib.check(self.lib.afr_set_optimizer(self._plan, _lib.opt_kind(self.optimizer)))      # host-only; ensure_batch's new plan gets it again
 
     @staticmethod
     def _check_clip(v):
@@ -239,8 +244,9 @@ class Engine:
         return {nm: self.params[nm].detach().clone() for nm, _, _, _ in self.layout}
 
     def reset_optimizer(self):
-        self.exp_avg.zero_()
-        self.exp_avg_sq.zero_()
+        for moment in (self.exp_avg, self.exp_avg_sq):
+            if moment is not None:
+                moment.zero_()
         self.t = 0
 
     # ---------------------------------------------------------------- the hot path
@@ -377,16 +383,22 @@ class Engine:
         self._keep, self._keep_t = (x, font), t
 
     def adamw_step(self, lr=1e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=5e-4, grad_scale=1.0):
+        """One optimizer step of the engine's kind (the name is the AdamW engine's; a Lion engine ignores eps)."""
         self.t += 1
         self._call(self.lib.afr_adamw_step, self._plan, lr, betas[0], betas[1], eps, weight_decay, self.t, grad_scale)
 
     def adamw_range(self, offset, n, lr=1e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=5e-4, grad_scale=1.0, sumsq=None):
-        """One AdamW step on the flat-buffer slice [offset, offset + n) only (sharded optimizer under data parallelism:
+        """One optimizer step (AdamW, or Lion on a Lion engine) on the flat-buffer slice [offset, offset + n) only (sharded optimizer under data parallelism:
         parallel.py).  Advances the step counter; the bf16 shadow is NOT refreshed (the caller syncs after its all-gather).
         sumsq: a 1-element device tensor holding the GLOBAL sum of squared gradients (grad_sumsq of every rank's range,
         all-reduced): the slice is then updated with the clip coefficient of self.max_grad_norm, as adamw_step would."""
         self.t += 1
         o, e = int(offset), int(offset) + int(n)
+        if self.optimizer == "lion":      # the same slice step by afr_op_lion, clipped when sumsq is given
+            self._call(self.lib.afr_op_lion, _ptr(self.flat_params[o:e]), _ptr(self.flat_grads[o:e]), _ptr(self.exp_avg[o:e]), C.c_void_p(0), int(n),
+                       lr, betas[0], betas[1], weight_decay, grad_scale, _ptr(sumsq), float(self.max_grad_norm or 0.0))
+            self._keep_ss = sumsq
+            return
         if sumsq is not None:
             self._call(self.lib.afr_op_adamw_clip, _ptr(self.flat_params[o:e]), _ptr(self.flat_grads[o:e]), _ptr(self.exp_avg[o:e]),
                        _ptr(self.exp_avg_sq[o:e]), C.c_void_p(0), int(n), lr, betas[0], betas[1], eps, weight_decay, self.t, grad_scale,

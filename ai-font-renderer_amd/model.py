@@ -20,7 +20,10 @@ What is deliberately different from the reference, and why:
     clamp head replaced, model.py:155) through the same fused step; the default, mse, is the reference's clamp + MSE.  A
     checkpoint does not record the head: the caller says which one it wants, as with the dtype;
   * AFR_CLIP_NORM=<max_norm> clips the gradients by their global L2 norm inside the optimizer step
-    (torch.nn.utils.clip_grad_norm_'s formula; Engine.set_grad_clip).  Unset or 0: no clipping, the reference's loop.
+    (torch.nn.utils.clip_grad_norm_'s formula; Engine.set_grad_clip).  Unset or 0: no clipping, the reference's loop;
+  * AFR_OPTIMIZER=lion trains with Lion (one moment, sign update; include/afr.h afr_set_optimizer) instead of AdamW.  The loop then
+    steps with LEARNING_RATE / 10 and WEIGHT_DECAY * 10 -- the Lion paper's rule of thumb, which keeps lr * weight_decay what it
+    was; the plateau scheduler still works on the LEARNING_RATE scale.  Unset or adamw: the reference's optimizer.
 """
 import datetime
 import os
@@ -56,6 +59,7 @@ SEED = 42
 ADAM_BETAS = (0.9, 0.99)                      # model.py:273
 COMPUTE_DTYPE = os.environ.get("AFR_DTYPE", "f32")
 COMPUTE_LOSS = os.environ.get("AFR_LOSS", "mse")     # "mse" | "bce"
+COMPUTE_OPTIMIZER = os.environ.get("AFR_OPTIMIZER", "adamw")     # "adamw" | "lion"
 CLIP_NORM = float(os.environ.get("AFR_CLIP_NORM", "0") or 0) or None     # global gradient-norm clip; None = off
 
 random.seed(SEED)
@@ -162,10 +166,12 @@ class AttentionFontRenderer(nn.Module):
     loss: "mse" (clamp head, the reference's) or "bce" (sigmoid head: forward returns sigmoid(u), the fused steps train with
     binary cross-entropy on u); None takes AFR_LOSS from the environment.  state_dict() is the same for both.
     max_grad_norm: clip the gradients by their global L2 norm inside the engine's optimizer step (Engine.set_grad_clip); None
-    takes AFR_CLIP_NORM from the environment (unset: off).  A torch optimizer on the autograd path clips with torch's own call."""
+    takes AFR_CLIP_NORM from the environment (unset: off).  A torch optimizer on the autograd path clips with torch's own call.
+    optimizer: "adamw" (the reference's) or "lion"; None takes AFR_OPTIMIZER from the environment.  train_attention_model steps a Lion
+    model with LEARNING_RATE / 10 and WEIGHT_DECAY * 10 (the Lion paper's rule of thumb: lr * weight_decay stays what it was)."""
 
     def __init__(self, max_length=MAX_CHARS_PER_SHEET, dtype=None, max_batch=1024, seed=SEED, rank=None, init=True, loss=None,
-                 max_grad_norm=None):
+                 max_grad_norm=None, optimizer=None):
         super().__init__()
         from .engine import Engine
         self.max_length = max_length
@@ -175,8 +181,10 @@ class AttentionFontRenderer(nn.Module):
                                   p_fc=DROPOUT_RATE + 0.05)
         rank = int(os.environ.get("RANK", "0")) if rank is None else rank
         self.engine = Engine(self.config, dtype=dtype or COMPUTE_DTYPE, max_batch=max_batch, device=device, seed=seed, rank=rank,
-                             loss=loss or COMPUTE_LOSS, max_grad_norm=CLIP_NORM if max_grad_norm is None else max_grad_norm)
+                             loss=loss or COMPUTE_LOSS, max_grad_norm=CLIP_NORM if max_grad_norm is None else max_grad_norm,
+                             optimizer=optimizer or COMPUTE_OPTIMIZER)
         self.loss = self.engine.loss
+        self.optimizer = self.engine.optimizer
         self.max_grad_norm = self.engine.max_grad_norm
         P = {k: nn.Parameter(v) for k, v in self.engine.params.items()}
         self.positional_encoding = P["positional_encoding"]
@@ -278,6 +286,14 @@ def _dist():
     return None, 1, 0
 
 
+def _step_hyper(eng, lr):
+    """(lr, weight_decay) of one optimizer step at the schedule's learning rate: AdamW takes them as they are, Lion a tenth of the
+    learning rate and ten times the decay (Chen et al. 2023, section 5: its sign update has a larger norm than AdamW's)."""
+    if eng.optimizer == "lion":
+        return lr / 10, WEIGHT_DECAY * 10
+    return lr, WEIGHT_DECAY
+
+
 def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True):
     """One epoch of the reference loop (model.py:288-333): the training pass over order.train_epoch(), then the validation
     pass; returns the two means of per-batch mean losses.  by_rows: the engine has the data set bound (Engine.bind_dataset)
@@ -293,7 +309,8 @@ def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, wor
     for b in range(nb):
         rows = idx[b * batch_size:(b + 1) * batch_size]
         mine = rows[shard_rows(rows.numel(), rank, world)]
-        hyper = dict(step=model._next_step(), lr=lr, betas=ADAM_BETAS, weight_decay=WEIGHT_DECAY)
+        step_lr, step_wd = _step_hyper(eng, lr)
+        hyper = dict(step=model._next_step(), lr=step_lr, betas=ADAM_BETAS, weight_decay=step_wd)
         if by_rows:
             stepper.step_rows(mine, rows.numel() * pixels, **hyper)
         else:
@@ -334,6 +351,8 @@ def train_attention_model(model, dataset, batch_size):
                 f.write(f"{k} = {v}\n")
             if eng.loss != "mse":               # only a non-default loss is recorded: a default run's artefacts stay as they were
                 f.write(f"loss = {eng.loss}\n")
+            if eng.optimizer != "adamw":        # likewise
+                f.write(f"optimizer = {eng.optimizer}\n")
             if eng.max_grad_norm:               # likewise only when set
                 f.write(f"max_grad_norm = {eng.max_grad_norm:g}\n")
 

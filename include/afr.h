@@ -114,7 +114,8 @@ int afr_param_info(const afr_plan* plan, int index, char* name, int name_cap, in
 size_t afr_workspace_bytes(const afr_plan* plan);
 
 /* Attach caller-owned device buffers.  params/grads/exp_avg/exp_avg_sq: afr_param_elems() floats
- * each (grads, moments may be NULL for inference-only use); workspace: afr_workspace_bytes(). */
+ * each (grads, moments may be NULL for inference-only use; exp_avg_sq also on a Lion plan, afr_set_optimizer); workspace:
+ * afr_workspace_bytes(). */
 int afr_bind(afr_plan* plan, float* params, float* grads, float* exp_avg, float* exp_avg_sq,
              void* workspace, size_t workspace_bytes);
 
@@ -163,6 +164,21 @@ int afr_forward_loss(afr_plan* plan, const int64_t* x, const int64_t* font, cons
  * multiplies every gradient first (1/world after a sum all-reduce; 1 otherwise). */
 int afr_adamw_step(afr_plan* plan, float lr, float beta1, float beta2, float eps, float weight_decay,
                    int64_t t, float grad_scale, void* stream);
+
+/* The optimizer kind of a plan.  AFR_OPT_ADAMW (the default of a new plan) is the update above.  AFR_OPT_LION is Lion (Chen et al.
+ * 2023, "Symbolic Discovery of Optimization Algorithms"), which keeps ONE moment:
+ *     c = fma(g - m, 1 - beta1, m)                      b1*m + (1-b1)*g
+ *     s = (c > 0) - (c < 0)                             0 for c == 0
+ *     p = fma(p, decay, -lr * s)                        decay = 1 - lr * weight_decay
+ *     m = fma(g - m, 1 - beta2, m)
+ * in plain f32, stated once in the library: every path of a step (fused or not, clipped or not, dense or by rows) applies these
+ * operations bit for bit.  g enters multiplied by grad_scale (on a clipping plan by fl32(grad_scale * coef), as for AdamW).  Every
+ * optimizer step of the plan follows the kind -- afr_adamw_step (which keeps its name), afr_train_step* with do_step -- the way the
+ * loss entry points follow afr_config.loss.  eps and t are accepted and ignored by a Lion step (no bias correction; t < 1 stays an
+ * error).  exp_avg_sq is neither read nor written: on a Lion plan afr_bind may be given exp_avg_sq = NULL.  The kind may change
+ * between steps; an AdamW step on a plan without exp_avg_sq is AFR_ESTATE.  Host-only; any other kind -> AFR_EINVAL. */
+enum { AFR_OPT_ADAMW = 0, AFR_OPT_LION = 1 };
+int afr_set_optimizer(afr_plan* plan, int kind);
 
 /* Clipping by the GLOBAL gradient norm inside the optimizer step (torch.nn.utils.clip_grad_norm_; the reference's loop has
  * none).  Off by default; with max_norm > 0 every optimizer step of the plan (afr_adamw_step, afr_train_step* with do_step)
@@ -307,6 +323,10 @@ int afr_op_adamw(float* p, const float* g, float* m, float* v, void* shadow_bf16
 int afr_op_adamw_clip(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr,
                       float beta1, float beta2, float eps, float weight_decay, int64_t t, float grad_scale,
                       const float* sumsq_dev, float max_norm, void* stream);
+/* The Lion update (afr_set_optimizer) on a slice: the sharded optimizer's and the unit tests' entry.  sumsq_dev NULL: no clipping
+ * (max_norm is not read); else the clip semantics of afr_op_adamw_clip, a non-finite *sumsq_dev leaving p, m and the shadow untouched. */
+int afr_op_lion(float* p, const float* g, float* m, void* shadow_bf16, int64_t n, float lr, float beta1, float beta2,
+                float weight_decay, float grad_scale, const float* sumsq_dev /* NULL = no clip */, float max_norm, void* stream);
 /* scratch: >= 1040 floats, zero before the first call (holds per-block partials and the arrival counter) */
 int afr_op_mse_grad(int act_dtype, const void* u, const void* target, int target_dtype, void* du,
                     int64_t rows, int64_t cols, int64_t mean_elems, float* loss_accum, float* scratch,
