@@ -18,6 +18,8 @@ LOSS_KINDS = {"mse": AFR_LOSS_MSE, "bce": AFR_LOSS_BCE}
 AFR_OPT_ADAMW, AFR_OPT_LION = 0, 1
 OPT_KINDS = {"adamw": AFR_OPT_ADAMW, "lion": AFR_OPT_LION}
 
+AFR_OK, AFR_EINVAL, AFR_ESTATE, AFR_EHIP, AFR_EUNSUPPORTED = 0, -1, -2, -3, -4
+
 AFR_MAX_HIDDEN = 8
 BUF_U, BUF_Z, BUF_DZ, BUF_W1T, BUF_W2T, BUF_ACT = 0, 1, 2, 4, 5, 16
 GEMM_BIAS, GEMM_RELU, GEMM_RELU_MASK, GEMM_OUT_BF16, GEMM_A_KSTRIDED, GEMM_B_KSTRIDED = 1, 2, 4, 8, 16, 32
@@ -74,6 +76,10 @@ SIGNATURES = {
     "afr_set_grad_clip": (_i32, [_vp, _f32, _vp]),
     "afr_set_optimizer": (_i32, [_vp, _i32]),
     "afr_grad_sumsq": (_i32, [_vp, _i64, _i64, _vp, _vp]),
+    "afr_set_ema": (_i32, [_vp, _vp, _f32, _i32]),
+    "afr_ema_update": (_i32, [_vp, _vp, _vp]),
+    "afr_op_ema": (_i32, [_vp, _vp, _i64, _f32, _vp, _vp]),
+    "afr_use_ema": (_i32, [_vp, _i32, _vp]),
     "afr_train_step": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _u64, _i32, _f32, _f32, _f32, _f32, _f32, _i64, _vp]),
     "afr_bind_dataset": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _i32]),
     "afr_forward_rows": (_i32, [_vp, _vp, _i32, _vp, _i32, _u64, _vp]),
@@ -105,7 +111,11 @@ SIGNATURES = {
 
 
 class AfrError(RuntimeError):
-    pass
+    """code: the AFR_E* value of a failed library call (None when the Python side raised it without one)."""
+
+    def __init__(self, msg, code=None):
+        super().__init__(msg)
+        self.code = code
 
 
 def load(path=LIB_PATH):
@@ -137,4 +147,4 @@ def lib():
 
 def check(rc):
     if rc != 0:
-        raise AfrError(f"libafr error {rc}: {lib().afr_last_error().decode()}")
+        raise AfrError(f"libafr error {rc}: {lib().afr_last_error().decode()}", rc)

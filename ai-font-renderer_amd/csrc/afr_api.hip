@@ -10,6 +10,7 @@ static_assert(AFR_LOSS_MSE == LOSS_MSE && AFR_LOSS_BCE == LOSS_BCE, "afr.h and a
 #include <cstring>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 // --------------------------------------------------------------------------------- error plumbing
@@ -143,6 +144,10 @@ struct afr_plan {
     int opt_kind = OPT_ADAMW;               // afr_set_optimizer: the update every optimizer step of the plan applies
     std::vector<SumsqSeg> clip_segs;        // host copy of that table
     size_t o_clip = 0;
+    // weight EMA (afr_set_ema): E = the caller's buffer in the parameter layout (NULL = off), updated by every ema_every-th optimizer
+    // step of the plan (ema_count of them since afr_set_ema).  ema_on (afr_use_ema): P and E have changed places, the forward
+    // entry points read the EMA weights and every call that trains or steps is refused.
+    float* E = nullptr; float ema_decay = 0.f; int ema_every = 1; int64_t ema_count = 0; bool ema_on = false;
     // profiling
     int prof_mode = 0;      // 0 off, 1 every launch, 2 only prof_only, 3 every 4th launch of prof_only
     unsigned prof_seen = 0; // launches of prof_only met in mode 3
@@ -451,6 +456,7 @@ extern "C" size_t afr_workspace_bytes(const afr_plan* p) { return p ? p->ws_need
 
 extern "C" int afr_bind(afr_plan* p, float* params, float* grads, float* m, float* v, void* ws, size_t ws_bytes) {
     if (!p || !params || !ws) return fail(AFR_EINVAL, "params and workspace are required");
+    if (p->ema_on) return fail(AFR_ESTATE, "afr_bind while the plan reads its EMA weights: afr_use_ema(plan, 0) first");
     if (ws_bytes < p->ws_need) return fail(AFR_EINVAL, "workspace too small: %zu < %zu", ws_bytes, p->ws_need);
     if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ws) & 255)
         return fail(AFR_EINVAL, "buffers must be 256-byte aligned");
@@ -803,6 +809,61 @@ extern "C" int afr_sync_params(afr_plan* p, void* stream) {
     return AFR_OK;
 }
 
+// ------------------------------------------------------------------------------------ weight EMA
+// while the plan reads its EMA weights (afr_use_ema) nothing may train or step: the gradients, the moments and the step count
+// belong to the weights that are parked in p->E meanwhile
+static int ema_guard(const afr_plan* p, const char* what) {
+    if (p && p->ema_on) return fail(AFR_ESTATE, "%s while the plan reads its EMA weights: afr_use_ema(plan, 0) first", what);
+    return AFR_OK;
+}
+static bool ema_decay_ok(float decay) { return decay > 0.f && decay < 1.f; }      // (false for NaN)
+extern "C" int afr_set_ema(afr_plan* p, float* ema, float decay, int every) {
+    if (!p) return fail(AFR_EINVAL, "null plan");
+    if (int rc = ema_guard(p, "afr_set_ema")) return rc;
+    if (!ema) { p->E = nullptr; p->ema_count = 0; return AFR_OK; }
+    if (!ema_decay_ok(decay)) return fail(AFR_EINVAL, "the EMA decay must be finite and inside (0, 1), got %g", (double)decay);
+    if (every < 1) return fail(AFR_EINVAL, "the EMA interval must be >= 1 optimizer steps, got %d", every);
+    if ((uintptr_t)ema & 255) return fail(AFR_EINVAL, "buffers must be 256-byte aligned");
+    const int d = device_of(ema);
+    if (d >= 0 && p->device >= 0 && d != p->device) return fail(AFR_EINVAL, "the EMA buffer lives on device %d, the plan's buffers on %d", d, p->device);
+    p->E = ema; p->ema_decay = decay; p->ema_every = every; p->ema_count = 0;
+    return AFR_OK;
+}
+// one optimizer step has happened: the EMA follows when the interval says so (the plan's own steps and afr_ema_update end here)
+static int ema_step(afr_plan* p, const float* sumsq, hipStream_t s) {
+    if (!p->E) return AFR_OK;
+    if (++p->ema_count % p->ema_every) return AFR_OK;
+    ProfScope ps(p, s, "ema", 2.0 * (double)p->total, 12.0 * (double)p->total);
+    HIPCHK(afr_launch_ema(p->E, p->P, p->total, p->ema_decay, sumsq, s));
+    return AFR_OK;
+}
+extern "C" int afr_ema_update(afr_plan* p, const float* sumsq_dev, void* stream) {
+    if (!p) return fail(AFR_EINVAL, "null plan");
+    if (!p->E) return fail(AFR_ESTATE, "no EMA set (afr_set_ema)");
+    if (int rc = ema_guard(p, "afr_ema_update")) return rc;
+    if (!p->P) return fail(AFR_ESTATE, "plan has no bound parameters");
+    DevGuard dg(p->device);
+    return ema_step(p, sumsq_dev, (hipStream_t)stream);
+}
+extern "C" int afr_use_ema(afr_plan* p, int on, void* stream) {
+    if (!p) return fail(AFR_EINVAL, "null plan");
+    if ((on != 0) == p->ema_on) return AFR_OK;
+    if (!p->E) return fail(AFR_ESTATE, "no EMA set (afr_set_ema)");
+    if (!p->P || !p->ws) return fail(AFR_ESTATE, "plan has no bound parameters");
+    std::swap(p->P, p->E);
+    p->ema_on = on != 0;
+    p->have_du = false; p->next_stage = 0;      // a saved forward belongs to the weights it ran with
+    return afr_sync_params(p, stream);          // the bf16 shadow and the transposed copies follow p->P
+}
+extern "C" int afr_op_ema(float* e, const float* p, int64_t n, float decay, const float* sumsq_dev, void* stream) {
+    if (!e || !p) return fail(AFR_EINVAL, "null argument");
+    if (n < 0 || (n & 3)) return fail(AFR_EINVAL, "n = %lld must be a non-negative multiple of 4", (long long)n);
+    if (!ema_decay_ok(decay)) return fail(AFR_EINVAL, "the EMA decay must be finite and inside (0, 1), got %g", (double)decay);
+    DevGuard dg(device_of(e));
+    HIPCHK(afr_launch_ema(e, p, n, decay, sumsq_dev, (hipStream_t)stream));
+    return AFR_OK;
+}
+
 static SheetDrop make_drop(const afr_plan* p, int training, uint64_t step) {
     SheetDrop d;
     const afr_config& c = p->cfg;
@@ -880,6 +941,7 @@ static bool combo_for(const afr_plan* p, int B) {
 static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int B, int L, float* y, int training,
                         uint64_t step, void* stream, const LossArgs* fl /* the plan's, fused slots */) {
     if (!p || !p->P) return fail(AFR_ESTATE, "plan has no bound parameters");
+    if (training || fl) if (int rc = ema_guard(p, "a training forward")) return rc;
     DevGuard dg(p->device);
     if (!x) return fail(AFR_EINVAL, "x is null");
     if (B <= 0 || B > p->cfg.max_batch) return fail(AFR_EINVAL, "batch %d outside 1..max_batch=%d", B, p->cfg.max_batch);
@@ -1296,6 +1358,7 @@ extern "C" int afr_backward_stages(const afr_plan* p) {
 
 extern "C" int afr_backward_stage(afr_plan* p, int stage, int64_t* grad_offset, int64_t* grad_elems, void* stream) {
     if (!p || !p->P || !p->G) return fail(AFR_ESTATE, "plan has no bound parameter/gradient buffers");
+    if (int rc = ema_guard(p, "afr_backward_stage")) return rc;
     DevGuard dg(p->device);
     const int n = afr_backward_stages(p);
     if (stage < 0 || stage >= n) return fail(AFR_EINVAL, "stage %d outside 0..%d", stage, n - 1);
@@ -1310,6 +1373,7 @@ extern "C" int afr_backward_stage(afr_plan* p, int stage, int64_t* grad_offset, 
 
 extern "C" int afr_backward(afr_plan* p, void* stream) {
     if (!p || !p->P || !p->G) return fail(AFR_ESTATE, "plan has no bound parameter/gradient buffers");
+    if (int rc = ema_guard(p, "afr_backward")) return rc;
     DevGuard dg(p->device);
     if (!p->have_du) return fail(AFR_ESTATE, "afr_backward needs afr_forward + afr_loss_grad first");
     const int n = afr_backward_stages(p);
@@ -1354,6 +1418,7 @@ extern "C" int afr_grad_sumsq(afr_plan* p, int64_t offset, int64_t n, float* out
 extern "C" int afr_set_optimizer(afr_plan* p, int kind) {
     if (!p) return fail(AFR_EINVAL, "null plan");
     if (kind != AFR_OPT_ADAMW && kind != AFR_OPT_LION) return fail(AFR_EINVAL, "optimizer kind must be AFR_OPT_ADAMW (0) or AFR_OPT_LION (1), got %d", kind);
+    if (int rc = ema_guard(p, "afr_set_optimizer")) return rc;
     p->opt_kind = kind;
     return AFR_OK;
 }
@@ -1361,6 +1426,7 @@ extern "C" int afr_adamw_step(afr_plan* p, float lr, float b1, float b2, float e
                               void* stream) {
     if (!p || !p->P || !p->G || !moments_bound(p))
         return fail(AFR_ESTATE, p && p->opt_kind == OPT_LION ? "Lion needs params, grads and exp_avg bound" : "AdamW needs params, grads and both moments bound");
+    if (int rc = ema_guard(p, "an optimizer step")) return rc;
     DevGuard dg(p->device);
     if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
     hipStream_t s = (hipStream_t)stream;
@@ -1373,11 +1439,13 @@ extern "C" int afr_adamw_step(afr_plan* p, float lr, float b1, float b2, float e
         sumsq = cw + CLIP_WS_SUMSQ;
     }
     const bool lion = p->opt_kind == OPT_LION;
-    ProfScope ps(p, s, lion ? (sumsq ? "lion_clip" : "lion") : (sumsq ? "adamw_clip" : "adamw"), 0.0, (double)p->total * ((lion ? 20.0 : 28.0) + (shadow ? 2.0 : 0.0)));
-    HIPCHK(afr_launch_adamw(p->P, p->G, p->M, lion ? nullptr : p->V, shadow, p->total, lr, wd, adam_hyper(AdamArgs{lr, b1, b2, eps, wd, t}, p->opt_kind),
-                            gscale, s, sumsq, p->clip_norm, p->opt_kind));
+    {
+        ProfScope ps(p, s, lion ? (sumsq ? "lion_clip" : "lion") : (sumsq ? "adamw_clip" : "adamw"), 0.0, (double)p->total * ((lion ? 20.0 : 28.0) + (shadow ? 2.0 : 0.0)));
+        HIPCHK(afr_launch_adamw(p->P, p->G, p->M, lion ? nullptr : p->V, shadow, p->total, lr, wd, adam_hyper(AdamArgs{lr, b1, b2, eps, wd, t}, p->opt_kind),
+                                gscale, s, sumsq, p->clip_norm, p->opt_kind));
+    }
     p->wT_valid = false;
-    return AFR_OK;
+    return ema_step(p, sumsq, s);       // (a skipped step leaves the EMA alone too: the kernel reads the same sum)
 }
 
 // Single-GPU optimiser step fused into the grouped slab reduction: every tensor whose gradient was produced as partial
@@ -1411,7 +1479,7 @@ static int reduce_and_step(afr_plan* p, hipStream_t s, RTable& rt, const AdamArg
     }
     if (p->o_shadow2) p->shadow_cur ^= 1;   // every tensor has been rewritten: the write shadow is the current one now
     p->adam_done.clear();
-    return AFR_OK;
+    return ema_step(p, nullptr, s);         // the step's last parameter write is behind us (never a clipping plan here)
 }
 
 // Single-GPU sheet step with the optimizer fused into the weight-gradient GEMM: fc_output.weight (99.98 % of the
@@ -1521,6 +1589,7 @@ static int train_step_impl(afr_plan* p, const int64_t* x, const int64_t* font, c
     int rc;
     if ((rc = check_loss_args(target, tdtype, mean_elems, loss_accum))) return rc;
     if (!p || !p->P) return fail(AFR_ESTATE, "plan has no bound parameters");
+    if ((rc = ema_guard(p, "afr_train_step"))) return rc;
     DevGuard dg(p->device);
     const AdamArgs h{lr, b1, b2, eps, wd, t};
     // (a clipping plan needs the global norm before any update: every gradient is materialised, then afr_adamw_step)
@@ -1605,6 +1674,7 @@ static int rows_begin(afr_plan* p, const int64_t* rows, int B, bool stage_ids, v
 static inline const int64_t* staged_font(const afr_plan* p) { return p->ds_font ? (const int64_t*)(p->ws + p->o_sfont) : nullptr; }
 extern "C" int afr_forward_rows(afr_plan* p, const int64_t* rows, int B, float* y, int training, uint64_t step, void* stream) {
     int Lc, rc;
+    if (training && (rc = ema_guard(p, "a training forward"))) return rc;
     if ((rc = rows_begin(p, rows, B, true, stream, &Lc))) return rc;
     return forward_impl(p, (const int64_t*)(p->ws + p->o_sx), staged_font(p), B, Lc, y, training, step, stream, nullptr);
 }
@@ -1616,6 +1686,7 @@ extern "C" int afr_loss_grad_rows(afr_plan* p, const int64_t* rows, int B, int64
 extern "C" int afr_forward_loss_rows(afr_plan* p, const int64_t* rows, int B, int64_t mean_elems, float* loss_accum, uint64_t step,
                                      void* stream) {
     int Lc, rc;
+    if ((rc = ema_guard(p, "afr_forward_loss_rows"))) return rc;
     if ((rc = rows_begin(p, rows, B, true, stream, &Lc))) return rc;
     return forward_loss_impl(p, (const int64_t*)(p->ws + p->o_sx), staged_font(p), p->ds_target, p->ds_tdtype, (const int*)(p->ws + p->o_ridx),
                              B, Lc, mean_elems, loss_accum, step, stream);
@@ -1623,6 +1694,7 @@ extern "C" int afr_forward_loss_rows(afr_plan* p, const int64_t* rows, int B, in
 extern "C" int afr_train_step_rows(afr_plan* p, const int64_t* rows, int B, int64_t mean_elems, float* loss_accum, uint64_t step,
                                    int do_step, float lr, float b1, float b2, float eps, float wd, int64_t t, void* stream) {
     int Lc, rc;
+    if ((rc = ema_guard(p, "afr_train_step_rows"))) return rc;
     if ((rc = rows_begin(p, rows, B, true, stream, &Lc))) return rc;
     return train_step_impl(p, (const int64_t*)(p->ws + p->o_sx), staged_font(p), p->ds_target, p->ds_tdtype, (const int*)(p->ws + p->o_ridx),
                            B, Lc, mean_elems, loss_accum, step, do_step, lr, b1, b2, eps, wd, t, stream);

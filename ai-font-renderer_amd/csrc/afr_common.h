@@ -313,6 +313,9 @@ hipError_t afr_launch_reduce_group(const RTable& t, hipStream_t s);
 hipError_t afr_launch_adamw(float* p, const float* g, float* m, float* v, bf16_t* shadow, long long n, float lr, float wd,
                             const AdamHyper& h, float grad_scale, hipStream_t s, const float* sumsq = nullptr, float max_norm = 0.f,
                             int kind = OPT_ADAMW);
+// Weight EMA (elementwise.hip ema_kernel): e = fma(p - e, fl(1 - decay), e) over n elements (a multiple of 4); sumsq as above: NULL,
+// or the device word whose non-finite value leaves e untouched.
+hipError_t afr_launch_ema(float* e, const float* p, long long n, float decay, const float* sumsq, hipStream_t s);
 // Global gradient norm (elementwise.hip grad_sumsq_kernel): *out = sum of g[i]^2 over the tensor elements -- the (offset, numel)
 // segments of the table `segs` (at most 256), flat-buffer padding excluded -- that lie inside [lo, hi) of g; lo, hi multiples of 4.
 // scratch: AFR_SUMSQ_SCRATCH_FLOATS floats, zero before the first launch and left zero (block partials + arrival counter, the loss

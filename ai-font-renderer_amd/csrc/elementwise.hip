@@ -216,6 +216,32 @@ hipError_t afr_launch_adamw(float* p, const float* g, float* m, float* v, bf16_t
     return hipGetLastError();
 }
 
+// ----------------------------------------------------------------------------------- weight EMA
+// e[i] = fma(p[i] - e[i], alpha, e[i]), alpha = fl(1 - decay) from the host (afr_set_ema / afr_op_ema): the exponential moving
+// average of the weights, one pass over the whole flat buffer AFTER the optimizer step (the padding of e follows the padding of p).
+// 12 bytes per element: e is streamed -- loaded and stored non-temporally, nothing reads it again before the next update -- while p
+// was just written by the optimizer and is what the next forward reads.  p[i] == e[i] gives e[i] back bit for bit (0 * alpha + e).
+// sumsq (NULL = none): the clipping plan's sum of squared gradients; a non-finite one means the optimizer step was skipped, and the
+// EMA then stays as it is too.  Every lane loads the one word, as in adamw_kernel<true>.
+__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ e, const float* __restrict__ p, long long n4, float alpha,
+                                                  const float* __restrict__ sumsq) {
+    if (sumsq && !finite_f(*sumsq)) return;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        const f32x4 ee = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(e) + i);
+        const f32x4 pp = reinterpret_cast<const f32x4*>(p)[i];
+        f32x4 o;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = __builtin_fmaf(pp[r] - ee[r], alpha, ee[r]);
+        __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(e) + i);
+    }
+}
+hipError_t afr_launch_ema(float* e, const float* p, long long n, float decay, const float* sumsq, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (n & 3) return hipErrorInvalidValue;   // flat buffers are padded to multiples of 64
+    hipLaunchKernelGGL(ema_kernel, dim3(grid_for(n / 4, 256, 4096)), dim3(256), 0, s, e, p, n / 4, 1.0f - decay, sumsq);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------ global gradient norm
 // *out = sum of g[i]^2 over the ELEMENTS of the parameter tensors inside [lo, hi) of the flat gradient buffer, from a device table
 // of (offset, numel) segments, each clipped to the range (segments start on multiples of 64 elements and lo, hi are multiples of

@@ -4,6 +4,7 @@ loop body (model.py:292-310) as forward -> loss_grad -> backward -> [all-reduce]
 
 Needs a GPU and the built extension; raises otherwise (no CPU path).
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -64,8 +65,10 @@ class Engine:
     state_dict order, so checkpoints interchange with the reference (helpers.py:76-105)."""
 
     def __init__(self, cfg, dtype="f32", max_batch=1024, device=None, seed=42, rank=0, with_optimizer=True, flags=0, micro_batch=None,
-                 loss="mse", max_grad_norm=None, optimizer="adamw"):
-        """optimizer: "adamw" (torch.optim.AdamW, the reference's) or "lion" (one moment, sign update: include/afr.h afr_set_optimizer);
+                 loss="mse", max_grad_norm=None, optimizer="adamw", ema_decay=None, ema_every=1):
+        """ema_decay: keep an exponential moving average of the weights (set_ema); None = off.  ema_every: update it every that many
+        optimizer steps.
+        optimizer: "adamw" (torch.optim.AdamW, the reference's) or "lion" (one moment, sign update: include/afr.h afr_set_optimizer);
         every optimizer step of the engine follows it, and a Lion engine allocates no exp_avg_sq.
         max_grad_norm: clip the gradients by their global L2 norm inside every optimizer step (set_grad_clip); None or 0 = off.
         micro_batch: train_step / forward_loss + backward of a batch larger than this many samples run as micro-steps of at
@@ -89,6 +92,9 @@ class Engine:
         self.max_grad_norm = self._check_clip(max_grad_norm)
         self._clip_stats = None     # device float[2] the library writes (total_norm, coef) into on a clipping plan
         self._ds = None       # the bound data set: (x, font, target, target dtype code, rows, L), see bind_dataset
+        # the weight EMA (set_ema): flat_ema in the parameter layout, ema_params its views; _ema_on inside ema_weights()
+        self.ema_decay, self.ema_every = self._check_ema(ema_decay, ema_every)
+        self.flat_ema, self.ema_params, self._ema_on = None, {}, False
         self._make_plan(self.max_batch)
         n = self.lib.afr_param_elems(self._plan)
         self.n_flat = int(n)
@@ -111,6 +117,8 @@ class Engine:
         self.pixels = cfg.pixels
         self.t = 0            # AdamW step counter (model.py:310)
         self._keep = None     # keeps the last inputs alive until backward has consumed them
+        if self.ema_decay is not None:
+            self.set_ema(self.ema_decay, self.ema_every)
 
     def _call(self, fn, *args):
         """One libafr call that enqueues work: on THIS engine's device and on the caller's current stream of that device
@@ -135,6 +143,82 @@ class Engine:
         self._bind_ds()
         self._apply_clip()
         _lib.check(self.lib.afr_set_optimizer(self._plan, _lib.opt_kind(self.optimizer)))      # host-only; ensure_batch's new plan gets it again
+        self._apply_ema()
+        if self._ema_on:          # a re-plan inside ema_weights(): the new plan reads the EMA too
+            self._call(self.lib.afr_use_ema, self._plan, 1)
+
+    # ---------------------------------------------------------------- weight EMA
+    @staticmethod
+    def _check_ema(decay, every):
+        if decay is None:
+            return None, 1
+        decay = float(decay)
+        if not (0.0 < decay < 1.0):
+            raise ValueError(f"ema_decay must lie inside (0, 1) (None: off), got {decay!r}")
+        if isinstance(every, bool) or int(every) != every or int(every) < 1:
+            raise ValueError(f"ema_every must be an integer >= 1, got {every!r}")
+        return decay, int(every)
+
+    def _apply_ema(self):
+        """Hand the plan its EMA setting (host-only call; ensure_batch's new plan gets it again, its count of steps starting anew)."""
+        on = self.flat_ema is not None
+        _lib.check(self.lib.afr_set_ema(self._plan, _ptr(self.flat_ema), float(self.ema_decay) if on else 0.0, int(self.ema_every) if on else 1))
+
+    def _not_in_ema(self, what):
+        """Inside ema_weights() nothing trains or steps (the library refuses with AFR_ESTATE; checked here before the step counter moves)."""
+        if self._ema_on:
+            raise _lib.AfrError(f"libafr error {_lib.AFR_ESTATE}: {what} while the engine reads its EMA weights (inside ema_weights())", _lib.AFR_ESTATE)
+
+    def set_ema(self, decay, every=1):
+        """Keep an exponential moving average of the weights from now on: after every `every`-th optimizer step of the engine
+        (train_step*, adamw_step, the data-parallel schedules) e += (p - e) * (1 - decay), one pass over the flat buffer on the
+        device (include/afr.h afr_set_ema).  flat_ema / ema_params / ema_state_dict() expose it, ema_weights() evaluates from it.
+        The EMA starts as a copy of the parameters, and the count of steps at 0.  decay None switches it off."""
+        self._not_in_ema("set_ema")
+        self.ema_decay, self.ema_every = self._check_ema(decay, every)
+        if self.ema_decay is None:
+            self.flat_ema, self.ema_params = None, {}
+            self._apply_ema()
+            return
+        if self.flat_ema is None:
+            with torch.cuda.device(self.device):
+                self.flat_ema = torch.zeros(self.n_flat, dtype=torch.float32, device=self.device)
+            self.ema_params = {nm: self.flat_ema[o:o + k].view(shp) for nm, shp, o, k in self.layout}
+        self._apply_ema()
+        self.reset_ema()
+
+    def reset_ema(self):
+        """EMA := the current parameters (load_params does it; reset_optimizer does not)."""
+        self._not_in_ema("reset_ema")
+        if self.flat_ema is None:
+            raise _lib.AfrError("no EMA set (Engine(ema_decay=...) / set_ema)")
+        self.flat_ema.copy_(self.flat_params)
+
+    def ema_state_dict(self):
+        if self.flat_ema is None:
+            raise _lib.AfrError("no EMA set (Engine(ema_decay=...) / set_ema)")
+        return {nm: self.ema_params[nm].detach().clone() for nm, _, _, _ in self.layout}
+
+    def ema_update(self, sumsq=None):
+        """Count one optimizer step that the engine did not perform itself (adamw_range on slices: parallel.py) and update the EMA
+        when the interval says so.  sumsq: the 1-element device tensor the clipped slice update read; a non-finite value (a skipped
+        step) leaves the EMA untouched."""
+        self._not_in_ema("ema_update")
+        self._call(self.lib.afr_ema_update, self._plan, _ptr(sumsq))
+        self._keep_ss = sumsq
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block forward / forward_rows (+ loss_grad*) and debug_read see the EMA weights (afr_use_ema: the bf16 shadow is
+        re-derived on entry and on exit, one pass each); train_step*, forward_loss*, backward*, adamw_step and ema_update raise."""
+        self._not_in_ema("ema_weights")
+        self._call(self.lib.afr_use_ema, self._plan, 1)
+        self._ema_on = True
+        try:
+            yield self
+        finally:
+            self._ema_on = False
+            self._call(self.lib.afr_use_ema, self._plan, 0)
 
     @staticmethod
     def _check_clip(v):
@@ -228,7 +312,8 @@ class Engine:
 
     # ---------------------------------------------------------------- parameters
     def load_params(self, tensors):
-        """tensors: dict name -> numpy array / torch tensor (any device), state_dict keys."""
+        """tensors: dict name -> numpy array / torch tensor (any device), state_dict keys.  An EMA restarts from them."""
+        self._not_in_ema("load_params")
         for nm, shp, _, _ in self.layout:
             src = tensors[nm]
             src = torch.from_numpy(np.ascontiguousarray(src)) if isinstance(src, np.ndarray) else src.detach()
@@ -236,6 +321,8 @@ class Engine:
                 raise ValueError(f"{nm}: shape {tuple(src.shape)} != {tuple(shp)}")
             self.params[nm].copy_(src.to(torch.float32))
         self.sync_params()
+        if self.flat_ema is not None:
+            self.reset_ema()
 
     def sync_params(self):
         self._call(self.lib.afr_sync_params, self._plan)
@@ -317,6 +404,7 @@ class Engine:
 
     def train_step_rows(self, rows, step=None, lr=1e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=5e-4, mean_elems=None, do_step=True):
         """train_step() on rows of the bound data set: one C call, no gather in front of it."""
+        self._not_in_ema("train_step_rows")
         rows = self._rows(rows)
         B = rows.shape[0]
         if self.micro_batch and B > self.micro_batch:
@@ -384,6 +472,7 @@ class Engine:
 
     def adamw_step(self, lr=1e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=5e-4, grad_scale=1.0):
         """One optimizer step of the engine's kind (the name is the AdamW engine's; a Lion engine ignores eps)."""
+        self._not_in_ema("adamw_step")
         self.t += 1
         self._call(self.lib.afr_adamw_step, self._plan, lr, betas[0], betas[1], eps, weight_decay, self.t, grad_scale)
 
@@ -391,7 +480,9 @@ class Engine:
         """One optimizer step (AdamW, or Lion on a Lion engine) on the flat-buffer slice [offset, offset + n) only (sharded optimizer under data parallelism:
         parallel.py).  Advances the step counter; the bf16 shadow is NOT refreshed (the caller syncs after its all-gather).
         sumsq: a 1-element device tensor holding the GLOBAL sum of squared gradients (grad_sumsq of every rank's range,
-        all-reduced): the slice is then updated with the clip coefficient of self.max_grad_norm, as adamw_step would."""
+        all-reduced): the slice is then updated with the clip coefficient of self.max_grad_norm, as adamw_step would.
+        The EMA is not touched: the caller counts the step with ema_update once every slice is in place."""
+        self._not_in_ema("adamw_range")
         self.t += 1
         o, e = int(offset), int(offset) + int(n)
         if self.optimizer == "lion":      # the same slice step by afr_op_lion, clipped when sumsq is given
@@ -411,6 +502,7 @@ class Engine:
     def train_step(self, x, target, font=None, step=None, lr=1e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=5e-4,
                    mean_elems=None, do_step=True):
         """zero_grad -> forward -> loss -> backward -> AdamW, one C call (model.py:292-310)."""
+        self._not_in_ema("train_step")
         x, font = self._prep_x(x, font)
         if self.micro_batch and x.shape[0] > self.micro_batch:
             t, _ = self._target(target)

@@ -23,8 +23,13 @@ What is deliberately different from the reference, and why:
     (torch.nn.utils.clip_grad_norm_'s formula; Engine.set_grad_clip).  Unset or 0: no clipping, the reference's loop;
   * AFR_OPTIMIZER=lion trains with Lion (one moment, sign update; include/afr.h afr_set_optimizer) instead of AdamW.  The loop then
     steps with LEARNING_RATE / 10 and WEIGHT_DECAY * 10 -- the Lion paper's rule of thumb, which keeps lr * weight_decay what it
-    was; the plateau scheduler still works on the LEARNING_RATE scale.  Unset or adamw: the reference's optimizer.
+    was; the plateau scheduler still works on the LEARNING_RATE scale.  Unset or adamw: the reference's optimizer;
+  * AFR_EMA=<decay> or AFR_EMA=<decay>:<every> (0.999, 0.999:8) keeps an exponential moving average of the weights, updated on the
+    device after every <every>-th optimizer step (Engine.set_ema).  The validation loss that picks the best epoch and drives the
+    plateau scheduler, the 5-epoch test-string dumps and the saved model are then taken from the average.  Unset: the reference's
+    loop, nothing changes.
 """
+import contextlib
 import datetime
 import os
 import random
@@ -61,6 +66,24 @@ COMPUTE_DTYPE = os.environ.get("AFR_DTYPE", "f32")
 COMPUTE_LOSS = os.environ.get("AFR_LOSS", "mse")     # "mse" | "bce"
 COMPUTE_OPTIMIZER = os.environ.get("AFR_OPTIMIZER", "adamw")     # "adamw" | "lion"
 CLIP_NORM = float(os.environ.get("AFR_CLIP_NORM", "0") or 0) or None     # global gradient-norm clip; None = off
+
+
+def _ema_from_env():
+    """AFR_EMA = "<decay>" | "<decay>:<every>" -> (decay, every); unset or empty -> (None, 1).  Read when a model is constructed; a
+    value that does not parse, or lies outside what Engine.set_ema takes, is a ValueError."""
+    spec = os.environ.get("AFR_EMA", "").strip()
+    if not spec:
+        return None, 1
+    decay, _, every = spec.partition(":")
+    try:
+        return float(decay), int(every) if every else 1
+    except ValueError:
+        raise ValueError(f"AFR_EMA must be <decay> or <decay>:<every>, e.g. 0.999 or 0.999:8, got {spec!r}") from None
+
+
+def _eval_weights(eng):
+    """The weights evaluation is taken from: the engine's EMA when it keeps one, the weights themselves otherwise."""
+    return eng.ema_weights() if eng.ema_decay is not None else contextlib.nullcontext()
 
 random.seed(SEED)
 np.random.seed(SEED)
@@ -168,10 +191,12 @@ class AttentionFontRenderer(nn.Module):
     max_grad_norm: clip the gradients by their global L2 norm inside the engine's optimizer step (Engine.set_grad_clip); None
     takes AFR_CLIP_NORM from the environment (unset: off).  A torch optimizer on the autograd path clips with torch's own call.
     optimizer: "adamw" (the reference's) or "lion"; None takes AFR_OPTIMIZER from the environment.  train_attention_model steps a Lion
-    model with LEARNING_RATE / 10 and WEIGHT_DECAY * 10 (the Lion paper's rule of thumb: lr * weight_decay stays what it was)."""
+    model with LEARNING_RATE / 10 and WEIGHT_DECAY * 10 (the Lion paper's rule of thumb: lr * weight_decay stays what it was).
+    ema_decay, ema_every: keep an exponential moving average of the weights (Engine.set_ema); ema_decay None takes AFR_EMA from the
+    environment (unset: off).  train_attention_model then validates, renders and saves from the average."""
 
     def __init__(self, max_length=MAX_CHARS_PER_SHEET, dtype=None, max_batch=1024, seed=SEED, rank=None, init=True, loss=None,
-                 max_grad_norm=None, optimizer=None):
+                 max_grad_norm=None, optimizer=None, ema_decay=None, ema_every=1):
         super().__init__()
         from .engine import Engine
         self.max_length = max_length
@@ -180,9 +205,11 @@ class AttentionFontRenderer(nn.Module):
                                   sheet_h=SHEET_HEIGHT, sheet_w=SHEET_WIDTH, p_embed=DROPOUT_RATE, p_attn=DROPOUT_RATE,
                                   p_fc=DROPOUT_RATE + 0.05)
         rank = int(os.environ.get("RANK", "0")) if rank is None else rank
+        if ema_decay is None:
+            ema_decay, ema_every = _ema_from_env()
         self.engine = Engine(self.config, dtype=dtype or COMPUTE_DTYPE, max_batch=max_batch, device=device, seed=seed, rank=rank,
                              loss=loss or COMPUTE_LOSS, max_grad_norm=CLIP_NORM if max_grad_norm is None else max_grad_norm,
-                             optimizer=optimizer or COMPUTE_OPTIMIZER)
+                             optimizer=optimizer or COMPUTE_OPTIMIZER, ema_decay=ema_decay, ema_every=ema_every)
         self.loss = self.engine.loss
         self.optimizer = self.engine.optimizer
         self.max_grad_norm = self.engine.max_grad_norm
@@ -243,6 +270,8 @@ class AttentionFontRenderer(nn.Module):
     def load_state_dict(self, state_dict, strict=True, assign=False):
         out = super().load_state_dict(state_dict, strict=strict, assign=False)
         self.engine.sync_params()                                  # refresh bf16 shadows
+        if self.engine.flat_ema is not None:
+            self.engine.reset_ema()                                # the average restarts from the loaded weights
         return out
 
 
@@ -296,7 +325,7 @@ def _step_hyper(eng, lr):
 
 def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True):
     """One epoch of the reference loop (model.py:288-333): the training pass over order.train_epoch(), then the validation
-    pass; returns the two means of per-batch mean losses.  by_rows: the engine has the data set bound (Engine.bind_dataset)
+    pass; returns the two means of per-batch mean losses.  An engine that keeps a weight EMA validates from it.  by_rows: the engine has the data set bound (Engine.bind_dataset)
     and every step is driven by this rank's slice of the epoch's index vector -- the kernels read the rows where they lie.
     by_rows=False gathers each batch with index_select and hands the step dense tensors (the form tools/epoch_bench.py
     measures the other against)."""
@@ -320,15 +349,16 @@ def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, wor
     model.eval()
     vidx = order.val_epoch().to(inputs.device)
     nvb = _num_batches(order.val_size, batch_size)
-    for b in range(nvb):
-        rows = vidx[b * batch_size:(b + 1) * batch_size]
-        mine = rows[shard_rows(rows.numel(), rank, world)]
-        if by_rows:
-            eng.forward_rows(mine, training=False, want_output=False)
-            eng.loss_grad_rows(mine, mean_elems=rows.numel() * pixels)
-        else:
-            eng.forward(inputs.index_select(0, mine), training=False, want_output=False)
-            eng.loss_grad(targets.index_select(0, mine), mean_elems=rows.numel() * pixels)
+    with _eval_weights(eng):
+        for b in range(nvb):
+            rows = vidx[b * batch_size:(b + 1) * batch_size]
+            mine = rows[shard_rows(rows.numel(), rank, world)]
+            if by_rows:
+                eng.forward_rows(mine, training=False, want_output=False)
+                eng.loss_grad_rows(mine, mean_elems=rows.numel() * pixels)
+            else:
+                eng.forward(inputs.index_select(0, mine), training=False, want_output=False)
+                eng.loss_grad(targets.index_select(0, mine), mean_elems=rows.numel() * pixels)
     return avg_train_loss, stepper.global_loss() / max(nvb, 1)
 
 
@@ -355,6 +385,8 @@ def train_attention_model(model, dataset, batch_size):
                 f.write(f"optimizer = {eng.optimizer}\n")
             if eng.max_grad_norm:               # likewise only when set
                 f.write(f"max_grad_norm = {eng.max_grad_norm:g}\n")
+            if eng.ema_decay is not None:       # likewise
+                f.write(f"ema_decay = {eng.ema_decay:g}\nema_every = {eng.ema_every}\n")
 
     order = _EpochOrder(len(dataset))
     print(f"Dataset split: {order.train_size} training samples, {order.val_size} validation samples")
@@ -374,6 +406,12 @@ def train_attention_model(model, dataset, batch_size):
     best_val_loss = float("inf")
     patience_counter = 0
     best_model_state = None
+
+    # what the model holds when training ends: the (aliased, see below) best state, or -- with a weight EMA -- the average, which the
+    # final render and font_renderer.pth are then taken from (the checkpoint layout is the same)
+    def final_state():
+        return eng.ema_state_dict() if eng.ema_decay is not None else best_model_state
+
     epoch = -1
     for epoch in range(NUM_EPOCHS):
         lr = lr_holder.param_groups[0]["lr"]
@@ -397,18 +435,19 @@ def train_attention_model(model, dataset, batch_size):
                 if is_best:
                     status += " (New Best)"
                 print(status)
-                render_strings(model, test_strings, output_dir=f"{OUTPUT_DIR}/epoch_{epoch}", sheet_height=SHEET_HEIGHT,
-                               sheet_width=SHEET_WIDTH, device=device)
+                with _eval_weights(eng):
+                    render_strings(model, test_strings, output_dir=f"{OUTPUT_DIR}/epoch_{epoch}", sheet_height=SHEET_HEIGHT,
+                                   sheet_width=SHEET_WIDTH, device=device)
             elif is_best:
                 print(f"Epoch {epoch}, New best validation loss: {avg_val_loss:.6f}")
         if patience_counter >= EARLY_STOPPING_PATIENCE:
             if rank == 0:
                 print(f"Early stopping at epoch {epoch}, Best Val Loss: {best_val_loss:.6f}")
-            model.load_state_dict(best_model_state)
+            model.load_state_dict(final_state())
             break
 
     if best_model_state is not None and patience_counter < EARLY_STOPPING_PATIENCE:
-        model.load_state_dict(best_model_state)
+        model.load_state_dict(final_state())
         if rank == 0:
             print(f"Training completed, Best Val Loss: {best_val_loss:.6f}")
 

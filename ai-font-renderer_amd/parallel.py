@@ -12,7 +12,7 @@ as an opt-in (AFR_DP_SCHEDULE=shard) until a multi-GPU node has run it.  Every s
 each rank draws its own dropout stream (rank is part of the counter-hash key).
 
 `engine` is anything with train_step(x, target, font=, mean_elems=, do_step=), flat_grads, adamw_step(**hyper)
-and loss_accum (step_rows: train_step_rows(rows, mean_elems=, do_step=) on a data set bound to the engine): the HIP Engine in production; tests drive the same logic on CPU (gloo) with a stand-in.
+(which also moves the engine's weight EMA, if it keeps one; the sharded schedule calls ema_update(sumsq=) itself) and loss_accum (step_rows: train_step_rows(rows, mean_elems=, do_step=) on a data set bound to the engine): the HIP Engine in production; tests drive the same logic on CPU (gloo) with a stand-in.
 """
 import os
 
@@ -142,6 +142,7 @@ class DataParallelStepper:
             rk = self.rank if ws == self.world else self.dist.get_rank()
             n = eng.flat_grads.numel() // ws
             _reduce_scatter_inplace(self.dist, eng.flat_grads, rk, ws)
+            ss = None
             if getattr(eng, "max_grad_norm", None):
                 # clipping by the GLOBAL norm: every rank sums the squares of its own range, the all-reduced sum gives every
                 # rank the same coefficient (the choice depends on the engine's setting alone: rank-invariant)
@@ -151,6 +152,10 @@ class DataParallelStepper:
             else:
                 eng.adamw_range(rk * n, n, **opt)
             _all_gather_inplace(self.dist, eng.flat_params, rk, ws)
+            if getattr(eng, "ema_decay", None):
+                # the slices were stepped outside the plan: count the step once the whole parameter buffer is in place.  The EMA is
+                # replicated (every rank averages all of it), and the engine's setting alone decides: rank-invariant
+                eng.ema_update(sumsq=ss)
             if hasattr(eng, "sync_params"):
                 eng.sync_params()               # bf16 mode: the shadow of the slices other ranks updated
             return

@@ -203,6 +203,37 @@ int afr_set_grad_clip(afr_plan* plan, float max_norm, float* stats);
  * must lie inside the buffer (AFR_EINVAL otherwise).  Works whether clipping is on or off. */
 int afr_grad_sumsq(afr_plan* plan, int64_t offset, int64_t n, float* out, void* stream);
 
+/* ---- exponential moving average (EMA) of the weights ----
+ * afr_set_ema hands the plan a caller-owned buffer `ema` of afr_param_elems() floats in the parameter layout (256-byte aligned, on
+ * the plan's device; the caller initialises it, usually with the parameters -- it is not read before the first update).  From then
+ * on every optimizer step the plan performs -- afr_adamw_step, afr_train_step* with do_step, fused or not, clipped or not -- counts
+ * one step after its last parameter write, and every `every`-th of them (count % every == 0) ends in ONE more launch over the whole
+ * flat buffer, padding included:
+ *     alpha = 1.0f - decay                     (f32, on the host)
+ *     e[i]  = fmaf(p[i] - e[i], alpha, e[i])   (p: the parameters after the optimizer step)
+ * With every = k the average takes every k-th iterate with the same decay (choose decay^k for the same horizon); the pass costs
+ * 12 bytes per parameter when it runs.  On a clipping plan (afr_set_grad_clip) a skipped step leaves the EMA bit-identical, like the
+ * parameters and the moments; it still ADVANCES the count -- the host cannot know that the step was skipped.
+ * ema == NULL switches the EMA off (decay and every are ignored).  Otherwise decay must be finite and inside (0, 1) and every >= 1
+ * (AFR_EINVAL; checked before the pointer is looked at).  The call resets the count to 0.  Host-only: nothing is launched.  The
+ * setting lives in the plan and survives afr_bind; a new plan starts without an EMA. */
+int afr_set_ema(afr_plan* plan, float* ema, float decay, int every);
+/* Count one optimizer step that happened OUTSIDE the plan (the sharded data-parallel schedule steps slices with afr_op_adamw /
+ * afr_op_lion): the same hook the plan's own steps end in.  sumsq_dev: NULL, or the device word holding the global sum of squared
+ * gradients the clipped slice update read -- a non-finite value leaves the EMA untouched.  AFR_ESTATE when no EMA is set. */
+int afr_ema_update(afr_plan* plan, const float* sumsq_dev, void* stream);
+/* The update on a slice (unit tests; callers that keep an EMA of their own): n a multiple of 4, decay inside (0, 1). */
+int afr_op_ema(float* e, const float* p, int64_t n, float decay, const float* sumsq_dev /* NULL = none */, void* stream);
+/* Evaluate from the EMA.  on != 0: the plan's parameter and EMA pointers change places and everything a forward reads besides the
+ * f32 parameters is re-derived as afr_sync_params does (the bf16 shadow in one pass; the transposed operand copies of the small
+ * glyph nets on their next use) -- no second shadow is kept.  While on, afr_forward (training == 0), afr_forward_rows, the
+ * afr_loss_grad* that follow them, afr_debug_copy and afr_debug_sheet_gather see the EMA weights, and every call that trains or
+ * steps returns AFR_ESTATE: afr_forward with training != 0, afr_forward_loss*, afr_train_step*, afr_backward*, afr_adamw_step,
+ * afr_ema_update, afr_set_optimizer (also afr_set_ema and afr_bind).  on == 0 swaps back and re-derives again; a forward saved
+ * before either switch cannot be followed by afr_backward.  Switching to the current state launches nothing; switching on without
+ * an EMA is AFR_ESTATE. */
+int afr_use_ema(afr_plan* plan, int on, void* stream);
+
 /* One whole iteration of the loop body model.py:292-310 on this rank's shard:
  * forward(training) -> loss+grad -> backward [-> AdamW when do_step!=0].  With do_step!=0 the loss is fused into
  * the last forward GEMM and, for the sheet model, the AdamW update of fc_output.weight into its dW GEMM.
