@@ -107,6 +107,16 @@ SIGNATURES = {
     "afr_op_f32_to_bf16": (_i32, [_vp, _vp, _i64, _vp]),
     "afr_op_f32_to_fp8": (_i32, [_vp, _vp, _i64, _f32, _vp]),
     "afr_op_gemm_fp8": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "afr_pixel_bwd_blocks": (_i32, [C.c_longlong]),
+    "afr_pixel_attn_chunk": (_i32, [_i32]),
+    "afr_op_pixel_ctx": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "afr_op_pixel_ctx_bwd": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "afr_op_pixel_add_ln": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp]),
+    "afr_op_pixel_attn": (_i32, [_i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "afr_op_pixel_attn_bwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "afr_op_pixel_head": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp]),
+    "afr_op_pixel_head_bwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp]),
+    "afr_op_pixel_ln_bwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp]),
 }
 
 

@@ -1922,3 +1922,90 @@ extern "C" int afr_op_gemm_fp8(int flags, const void* A, const void* B, void* C,
     HIPCHK(afr_launch_gemm_fp8(g, (hipStream_t)stream));
     return AFR_OK;
 }
+
+// ---- the pixel transformer's token kernels one launch each (include/afr.h): argument checks, then the launcher the plan calls
+static int pixel_op_shape(const char* what, int act_dtype, long long rows, int d) {
+    if (act_dtype != AFR_F32 && act_dtype != AFR_BF16) return fail(AFR_EINVAL, "%s: act_dtype must be AFR_F32 or AFR_BF16, got %d", what, act_dtype);
+    if (rows < 1) return fail(AFR_EINVAL, "%s: rows = %lld must be >= 1", what, rows);
+    if (d < 64 || d > 512 || d % 64) return fail(AFR_EUNSUPPORTED, "%s: d = %d must be 64 * heads <= 512", what, d);
+    return AFR_OK;
+}
+static int pixel_op_attn_shape(const char* what, int tokens, int d, int heads, int C) {
+    if (tokens < 1) return fail(AFR_EINVAL, "%s: tokens = %d must be >= 1", what, tokens);
+    if (d != 64 * heads) return fail(AFR_EUNSUPPORTED, "%s: d = %d must be 64 * heads (heads = %d)", what, d, heads);
+    if (C < 1 || C > 2) return fail(AFR_EINVAL, "%s: C = %d context tokens, must be 1 or 2", what, C);
+    return AFR_OK;
+}
+extern "C" int afr_op_pixel_ctx(int act_dtype, const float* emb, const float* femb, const int64_t* x, const int64_t* font, int B, int d, int vocab,
+                                int n_fonts, void* ctx, uint32_t* err, void* stream) {
+    if (int rc = pixel_op_shape("afr_op_pixel_ctx", act_dtype, B, d)) return rc;
+    if (!emb || !x || !ctx || !err || (n_fonts > 0 && (!femb || !font))) return fail(AFR_EINVAL, "afr_op_pixel_ctx: null argument");
+    if (vocab < 1 || n_fonts < 0) return fail(AFR_EINVAL, "afr_op_pixel_ctx: vocab = %d, n_fonts = %d", vocab, n_fonts);
+    DevGuard dg(device_of(ctx));
+    HIPCHK(afr_launch_pixel_ctx(act_dtype, emb, femb, x, font, B, d, vocab, n_fonts, ctx, err, (hipStream_t)stream));
+    return AFR_OK;
+}
+extern "C" int afr_op_pixel_ctx_bwd(const float* dctx, const int64_t* x, const int64_t* font, int B, int d, int vocab, int n_fonts, float* demb,
+                                    float* dfont, void* stream) {
+    if (int rc = pixel_op_shape("afr_op_pixel_ctx_bwd", AFR_F32, B, d)) return rc;
+    if (!dctx || !x || !demb || (n_fonts > 0 && (!font || !dfont))) return fail(AFR_EINVAL, "afr_op_pixel_ctx_bwd: null argument");
+    if (vocab < 1 || n_fonts < 0) return fail(AFR_EINVAL, "afr_op_pixel_ctx_bwd: vocab = %d, n_fonts = %d", vocab, n_fonts);
+    DevGuard dg(device_of(demb));
+    HIPCHK(afr_launch_pixel_ctx_bwd(dctx, x, font, B, d, vocab, n_fonts, demb, dfont, (hipStream_t)stream));
+    return AFR_OK;
+}
+extern "C" int afr_op_pixel_add_ln(int act_dtype, const float* hin, float* h, const float* pos, const void* add, const float* g, const float* b,
+                                   void* n, int64_t rows, int tokens, int d, float eps, void* stream) {
+    if (int rc = pixel_op_shape("afr_op_pixel_add_ln", act_dtype, rows, d)) return rc;
+    if (!h || (hin == nullptr) == (pos == nullptr)) return fail(AFR_EINVAL, "afr_op_pixel_add_ln: h and exactly one of hin / pos are required");
+    if (n && (!g || !b)) return fail(AFR_EINVAL, "afr_op_pixel_add_ln: n without g, b");
+    if (tokens < 1) return fail(AFR_EINVAL, "afr_op_pixel_add_ln: tokens = %d must be >= 1", tokens);
+    DevGuard dg(device_of(h));
+    HIPCHK(afr_launch_pixel_add_ln(act_dtype, hin, h, pos, add, g, b, n, rows, tokens, d, eps, (hipStream_t)stream));
+    return AFR_OK;
+}
+extern "C" int afr_op_pixel_attn(int act_dtype, const void* q, const void* kv, void* o, int64_t rows, int tokens, int d, int heads, int C,
+                                 void* stream) {
+    if (int rc = pixel_op_shape("afr_op_pixel_attn", act_dtype, rows, d)) return rc;
+    if (int rc = pixel_op_attn_shape("afr_op_pixel_attn", tokens, d, heads, C)) return rc;
+    if (!q || !kv || !o) return fail(AFR_EINVAL, "afr_op_pixel_attn: null argument");
+    DevGuard dg(device_of(o));
+    HIPCHK(afr_launch_pixel_attn(act_dtype, q, kv, o, rows, tokens, d, heads, C, (hipStream_t)stream));
+    return AFR_OK;
+}
+extern "C" int afr_op_pixel_attn_bwd(int act_dtype, const void* dO, const void* q, const void* kv, void* dq, float* dkv_part, int B, int tokens,
+                                     int d, int heads, int C, void* stream) {
+    if (int rc = pixel_op_shape("afr_op_pixel_attn_bwd", act_dtype, B, d)) return rc;
+    if (int rc = pixel_op_attn_shape("afr_op_pixel_attn_bwd", tokens, d, heads, C)) return rc;
+    if (!dO || !q || !kv || !dq || !dkv_part) return fail(AFR_EINVAL, "afr_op_pixel_attn_bwd: null argument");
+    const int chunk = afr_pixel_attn_chunk(tokens);
+    if ((long long)B * ((tokens + chunk - 1) / chunk) >= (1ll << 31)) return fail(AFR_EUNSUPPORTED, "afr_op_pixel_attn_bwd: B * chunks must stay below 2^31");
+    DevGuard dg(device_of(dq));
+    HIPCHK(afr_launch_pixel_attn_bwd(act_dtype, dO, q, kv, dq, dkv_part, B, tokens, d, C, (hipStream_t)stream));
+    return AFR_OK;
+}
+extern "C" int afr_op_pixel_head(int act_dtype, int loss_kind, const float* hin, float* h, const void* add, const float* g, const float* b,
+                                 const float* w_out, const float* b_out, float* u, float* y, int64_t rows, int d, float eps, void* stream) {
+    if (int rc = pixel_op_shape("afr_op_pixel_head", act_dtype, rows, d)) return rc;
+    if (loss_kind != AFR_LOSS_MSE && loss_kind != AFR_LOSS_BCE) return fail(AFR_EINVAL, "afr_op_pixel_head: loss kind must be AFR_LOSS_MSE (0) or AFR_LOSS_BCE (1), got %d", loss_kind);
+    if (!hin || !h || !add || !g || !b || !w_out || !b_out) return fail(AFR_EINVAL, "afr_op_pixel_head: null argument");
+    DevGuard dg(device_of(h));
+    HIPCHK(afr_launch_pixel_head(act_dtype, hin, h, add, g, b, w_out, b_out, u, y, rows, d, eps, (hipStream_t)stream, loss_kind));
+    return AFR_OK;
+}
+extern "C" int afr_op_pixel_head_bwd(int act_dtype, const float* du, const float* hf, const float* g, const float* b, const float* w_out, float* dh,
+                                     void* dhT, float* part, int64_t rows, int d, float eps, void* stream) {
+    if (int rc = pixel_op_shape("afr_op_pixel_head_bwd", act_dtype, rows, d)) return rc;
+    if (!du || !hf || !g || !b || !w_out || !dh || !part) return fail(AFR_EINVAL, "afr_op_pixel_head_bwd: null argument");
+    DevGuard dg(device_of(dh));
+    HIPCHK(afr_launch_pixel_head_bwd(act_dtype, du, hf, g, b, w_out, dh, dhT, part, rows, d, eps, (hipStream_t)stream));
+    return AFR_OK;
+}
+extern "C" int afr_op_pixel_ln_bwd(int act_dtype, const void* dy, const float* hin, const float* g, float* dh, void* dhT, float* part, int64_t rows,
+                                   int d, float eps, void* stream) {
+    if (int rc = pixel_op_shape("afr_op_pixel_ln_bwd", act_dtype, rows, d)) return rc;
+    if (!dy || !hin || !g || !dh || !part) return fail(AFR_EINVAL, "afr_op_pixel_ln_bwd: null argument");
+    DevGuard dg(device_of(dh));
+    HIPCHK(afr_launch_pixel_ln_bwd(act_dtype, dy, hin, g, dh, dhT, part, rows, d, eps, (hipStream_t)stream));
+    return AFR_OK;
+}

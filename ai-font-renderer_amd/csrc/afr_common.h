@@ -425,8 +425,9 @@ hipError_t afr_launch_pixel_add_ln(int act_dtype, const float* hin, float* h, co
 hipError_t afr_launch_pixel_attn(int act_dtype, const void* q, const void* kv, void* o, long long rows, int Tk, int d, int heads, int C, hipStream_t s);
 hipError_t afr_launch_pixel_head(int act_dtype, const float* hin, float* h, const void* add, const float* g, const float* b, const float* w_out, const float* b_out,
                                  float* u, float* y, long long rows, int d, float eps, hipStream_t s, int loss_kind = LOSS_MSE);
-int afr_pixel_bwd_blocks(long long rows);           // blocks (= partial slabs) of the head / LayerNorm backward kernels
-int afr_pixel_attn_chunk(int Tk);                   // tokens per attention-backward block
+// (these two are also exported, include/afr.h: a caller of the afr_op_pixel_* entries sizes its partial slabs with them)
+extern "C" int afr_pixel_bwd_blocks(long long rows);    // blocks (= partial slabs) of the head / LayerNorm backward kernels
+extern "C" int afr_pixel_attn_chunk(int Tk);            // tokens per attention-backward block
 hipError_t afr_launch_pixel_head_bwd(int act_dtype, const float* du, const float* hf, const float* g, const float* b, const float* w_out, float* dh,
                                      void* dhT, float* part /*[blocks][4][d]: dgamma, dbeta, dw_out, db_out*/, long long rows, int d, float eps, hipStream_t s);
 hipError_t afr_launch_pixel_ln_bwd(int act_dtype, const void* dy, const float* hin, const float* g, float* dh, void* dhT, float* part /*[blocks][2][d]*/,

@@ -369,6 +369,49 @@ int afr_op_bce_grad(int act_dtype, const void* u, const void* target, int target
                     void* stream);
 int afr_op_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);
 
+/* ---- the token-wise kernels of the per-pixel-token transformer (AFR_KIND_PIXEL), one launch each, exactly as the plan issues
+ * them.  One wave per token row: rows >= 1, d = 64 * heads <= 512 (the widths a plan can reach; AFR_EUNSUPPORTED otherwise),
+ * C = context tokens per glyph, 1 or 2; act_dtype AFR_F32 or AFR_BF16 is the type T of the GEMM operands (ctx, add, n, q, kv, o,
+ * dO, dq, dy, dhT); the residual stream h / dh, the parameters and every partial slab are float32.  Pointers not marked
+ * "or NULL" are required (AFR_EINVAL).  Rows are dense: row r starts at element r * d.
+ *   pixel_ctx      ctx T [B][C][d]: ctx[b][0] = emb[x[b]], ctx[b][1] = femb[font[b]] (C = 2 iff n_fonts > 0; font, femb NULL
+ *                  otherwise).  An index outside its table sets bit 0 of *err (device word) and is clamped.
+ *   pixel_ctx_bwd  demb [vocab][d] (and dfont [n_fonts][d]): row v = sum of dctx[b][0] (dctx[b][1]) over the glyphs b with
+ *                  x[b] == v (font[b] == v), in b order; a row no glyph uses is written 0.  dctx f32 [B][C][d].
+ *   pixel_add_ln   h = (pos ? pos[r % tokens] : hin[r]) + (add ? add[r] : 0);  n = LayerNorm(h) * g + b.  Exactly one of pos / hin
+ *                  is given; add and n may be NULL (n == NULL: g, b are not read).  hin == h is allowed.
+ *   pixel_attn     o[r] = softmax_c(q[r]_head . k[b][c]_head / 8) . v[b][c]_head per head of 64 channels, b = r / tokens;
+ *                  kv T [B][C][2 d] = [k | v].
+ *   pixel_attn_bwd dq T [B * tokens][d]; dkv_part f32 [chunks][B][4 d] = [dk_0 | dv_0 | dk_1 | dv_1] summed over the
+ *                  chunk's tokens (C == 1: the second half is written 0), chunks = ceil(tokens / afr_pixel_attn_chunk(tokens)):
+ *                  the sum of the chunk slabs (afr_op_reduce) is dk | dv of every context token.
+ *   pixel_head     h = hin + add;  u[r] = LayerNorm(h[r]) * g + b  .  w_out + b_out[0];  y = clamp(u, 0, 1), or sigmoid(u) with
+ *                  AFR_LOSS_BCE.  u and y may each be NULL.
+ *   pixel_head_bwd dh[r] = LayerNorm-backward(du[r] * w_out; x = hf[r]);  dhT (T copy of dh; AFR_BF16 only, or NULL; ignored in
+ *                  AFR_F32);  part f32 [afr_pixel_bwd_blocks(rows)][4][d]: per-block sums of dgamma, dbeta, dw_out and (element
+ *                  [3][0]) db_out, the rest of [3] zero.
+ *   pixel_ln_bwd   dh[r] += LayerNorm-backward(dy[r]; x = hin[r]) in place;  dhT as above;  part f32 [blocks][2][d]: dgamma, dbeta.
+ * Every block of the two slab kernels writes its whole slab (zeros where it had no row): no slab needs clearing. */
+int afr_pixel_bwd_blocks(long long rows);     /* host-only: partial slabs of pixel_head_bwd / pixel_ln_bwd for a row count */
+int afr_pixel_attn_chunk(int tokens);         /* host-only: tokens per attention-backward chunk */
+int afr_op_pixel_ctx(int act_dtype, const float* emb, const float* femb, const int64_t* x, const int64_t* font, int B, int d,
+                     int vocab, int n_fonts, void* ctx, uint32_t* err, void* stream);
+int afr_op_pixel_ctx_bwd(const float* dctx, const int64_t* x, const int64_t* font, int B, int d, int vocab, int n_fonts,
+                         float* demb, float* dfont, void* stream);
+int afr_op_pixel_add_ln(int act_dtype, const float* hin, float* h, const float* pos, const void* add /* or NULL */, const float* g,
+                        const float* b, void* n /* or NULL */, int64_t rows, int tokens, int d, float eps, void* stream);
+int afr_op_pixel_attn(int act_dtype, const void* q, const void* kv, void* o, int64_t rows, int tokens, int d, int heads, int C,
+                      void* stream);
+int afr_op_pixel_attn_bwd(int act_dtype, const void* dO, const void* q, const void* kv, void* dq, float* dkv_part, int B, int tokens,
+                          int d, int heads, int C, void* stream);
+int afr_op_pixel_head(int act_dtype, int loss_kind, const float* hin, float* h, const void* add, const float* g, const float* b,
+                      const float* w_out, const float* b_out, float* u /* or NULL */, float* y /* or NULL */, int64_t rows, int d,
+                      float eps, void* stream);
+int afr_op_pixel_head_bwd(int act_dtype, const float* du, const float* hf, const float* g, const float* b, const float* w_out,
+                          float* dh, void* dhT /* or NULL */, float* part, int64_t rows, int d, float eps, void* stream);
+int afr_op_pixel_ln_bwd(int act_dtype, const void* dy, const float* hin, const float* g, float* dh, void* dhT /* or NULL */,
+                        float* part, int64_t rows, int d, float eps, void* stream);
+
 /* ---- fp8 building blocks of BASELINE configs[4] ("fp8 MFMA weights on CDNA4"; no counterpart in the reference) ----
  * Operands are OCP e4m3fn bytes (gfx950's native fp8: exponent bias 7, largest finite 448, no infinities) with ONE float
  * scale per tensor: value = scale * e4m3.  afr_op_f32_to_fp8: dst[i] = e4m3(src[i] / scale), round to nearest even,

@@ -229,6 +229,36 @@ def test_full_width_block_with_32768_token_rows_takes_the_256x256_body_for_its_l
     assert eng.error_flags() == 0
 
 
+def test_second_trip_of_the_forward_token_kernels_through_the_plan():
+    """8 glyphs of 64 x 72 = 4608 pixel tokens are 36864 token rows: 36864 / (8192 * 4) = 1.125, so the plan itself drives
+    pixel_add_ln, pixel_attn and pixel_head (8192 blocks of 4 waves at most) into a second trip -- the benchmarked c5 step runs four.
+    The narrowest model that does so (d_model 64, one head, one block), f32, against the oracle: bitmaps, loss, and every gradient
+    against the model evaluated in fp64, at the bounds of test_c5_mini_backward_and_adamw_trajectory_match_the_torch_nn_twin."""
+    from ai_font_renderer_amd.config import PixelConfig
+    from ai_font_renderer_amd.engine import Engine
+    cfg = PixelConfig(out_h=64, out_w=72, d_model=64, heads=1, layers=1, ff_dim=8, n_fonts=2)
+    B = 8
+    assert B * cfg.tokens == 36864
+    x = torch.from_numpy((40 + (np.arange(B) * 7) % 80).astype(np.int64))
+    font = torch.from_numpy((np.arange(B) % 2).astype(np.int64))
+    tgt = torch.from_numpy(synth.hash_u8(936, (B, cfg.out_h, cfg.out_w)))
+    eng = Engine(cfg, dtype="f32", max_batch=B)
+    eng.load_params(synth.make_params(cfg))
+    y = eng.forward(x, font).cpu()
+    yref, _ = oracle.pixel_forward(tparams(cfg), x, font, cfg)
+    assert float((y - yref).abs().max()) < 2e-5
+    eng.train_step(x, tgt, font=font, do_step=False)
+    P64 = {k: v.double() for k, v in tparams(cfg).items()}
+    _, c64 = oracle.pixel_forward(P64, x, font, cfg)
+    loss64, du64 = oracle.mse_loss_grad(c64["u"], tgt.double() / 255.0)
+    G64 = oracle.pixel_backward(P64, c64, du64, cfg)
+    assert abs(eng.read_loss() - float(loss64)) < 1e-6
+    for n, _ in cfg.param_shapes():
+        ref = G64[n].numpy()
+        assert maxabs(eng.grads[n].cpu().numpy(), ref) <= 1e-5 * float(np.abs(ref).max()), n
+    assert eng.error_flags() == 0
+
+
 def test_pixel_plan_limits_and_caller_side_loss():
     """Shapes the plan refuses say so (never a silent wrong answer); the narrowest supported model (d_model 64, one head, one
     block, 8 pixel tokens, one context token) runs; a caller-side loss enters through set_output_grad exactly like the fused MSE."""
