@@ -51,6 +51,11 @@ class AfrConfig(C.Structure):
     ]
 
 
+class AfrOptRange(C.Structure):
+    """One merged range of the optimizer groups (include/afr.h afr_opt_range): flat elements up to `end` take these multipliers."""
+    _fields_ = [("end", C.c_int64), ("lr_mult", C.c_float), ("wd_mult", C.c_float)]
+
+
 _vp, _i32, _i64, _f32, _u64, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64, C.c_size_t
 
 # name -> (restype, argtypes): every function include/afr.h declares
@@ -75,6 +80,8 @@ SIGNATURES = {
     "afr_adamw_step": (_i32, [_vp, _f32, _f32, _f32, _f32, _f32, _i64, _f32, _vp]),
     "afr_set_grad_clip": (_i32, [_vp, _f32, _vp]),
     "afr_set_optimizer": (_i32, [_vp, _i32]),
+    "afr_set_param_groups": (_i32, [_vp, C.POINTER(_f32), C.POINTER(_f32), _i32]),
+    "afr_param_group_ranges": (_i32, [_vp, C.POINTER(AfrOptRange), _i32]),
     "afr_grad_sumsq": (_i32, [_vp, _i64, _i64, _vp, _vp]),
     "afr_set_ema": (_i32, [_vp, _vp, _f32, _i32]),
     "afr_ema_update": (_i32, [_vp, _vp, _vp]),
@@ -102,6 +109,8 @@ SIGNATURES = {
     "afr_op_adamw": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _f32, _vp]),
     "afr_op_adamw_clip": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _f32, _vp, _f32, _vp]),
     "afr_op_lion": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _vp, _f32, _vp]),
+    "afr_op_opt_groups": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, C.POINTER(AfrOptRange), _i32, _f32, _f32, _f32, _f32, _f32, _i64, _f32,
+                                 _vp, _f32, _vp]),
     "afr_op_mse_grad": (_i32, [_i32, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "afr_op_bce_grad": (_i32, [_i32, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "afr_op_f32_to_bf16": (_i32, [_vp, _vp, _i64, _vp]),

@@ -150,6 +150,13 @@ def flat_layout(cfg):
     return table, off
 
 
+def no_decay_names(cfg):
+    """The default rule of the optimizer groups (Engine.set_param_groups): the tensors that are usually kept out of weight decay --
+    every 1-D tensor (biases, LayerNorm gains and biases), the positional table and the embedding tables -- in state_dict order."""
+    tables = ("positional_encoding", "embedding.weight", "font_embedding.weight")
+    return [name for name, shape in cfg.param_shapes() if len(shape) == 1 or name in tables]
+
+
 # Named workloads (SURVEY.md 8d).  batch is per GPU.
 WORKLOADS = {
     "r0": dict(cfg=SheetConfig(), batch=1024),

@@ -142,6 +142,9 @@ struct afr_plan {
     // the (offset, numel) table of the parameter tensors], uploaded / zeroed by afr_bind
     float clip_norm = 0.f; float* clip_stats = nullptr;
     int opt_kind = OPT_ADAMW;               // afr_set_optimizer: the update every optimizer step of the plan applies
+    // optimizer groups (afr_set_param_groups): adjacent tensors with equal multipliers merged into ranges of the flat buffer, in
+    // offset order, the last one ending at `total`; empty = off (one lr, one weight decay for every tensor)
+    std::vector<afr_opt_range> groups;
     std::vector<SumsqSeg> clip_segs;        // host copy of that table
     size_t o_clip = 0;
     // weight EMA (afr_set_ema): E = the caller's buffer in the parameter layout (NULL = off), updated by every ema_every-th optimizer
@@ -640,6 +643,49 @@ static AdamHyper adam_hyper(const AdamArgs& h, int kind = OPT_ADAMW) {
     const float bc2 = (float)(1.0 - std::pow((double)h.b2, (double)h.t));
     return AdamHyper{1.f - h.lr * h.wd, h.b1, h.b2, h.eps, h.lr / bc1, (float)(1.0 / std::sqrt((double)bc2))};
 }
+// ---- optimizer groups: the ONE place a tensor's (lr_i, wd_i) are formed; every site that steps takes them from here
+static inline float mul_f32(float a, float b) {      // one rounded product, never contracted into what follows
+#pragma clang fp contract(off)
+    return a * b;
+}
+static inline AdamArgs group_args(const AdamArgs& h, const afr_opt_range& r) {
+    AdamArgs a = h;
+    a.lr = mul_f32(h.lr, r.lr_mult); a.wd = mul_f32(h.wd, r.wd_mult);
+    return a;
+}
+static const afr_opt_range* range_at(const afr_plan* p, int64_t off) {      // the range that holds flat element `off` (groups on)
+    for (const afr_opt_range& r : p->groups) if (off < r.end) return &r;
+    return &p->groups.back();
+}
+// the optimizer arguments of the tensor at flat offset `off`: the step's own when the plan has no groups
+static inline AdamArgs args_at(const afr_plan* p, const AdamArgs& h, int64_t off) {
+    return p->groups.empty() ? h : group_args(h, *range_at(p, off));
+}
+static bool mult_ok(float v) { return v >= 0.f && !std::isinf(v); }      // (false for NaN)
+// The kernel's table for the slice [first, first + n) from ranges in flat coordinates: the ranges that end at or before `first`
+// and those that begin at or after the slice's end are left out; lr_i, wd_i and step_i are folded here, by adam_hyper.
+static int build_range_tab(const afr_opt_range* r, int nr, int64_t first, int64_t n, const AdamArgs& h, int kind, OptRangeTab& tab) {
+    if (!r || nr < 1) return fail(AFR_EINVAL, "optimizer groups: no ranges");
+    if (first < 0 || n < 0 || ((first | n) & 3)) return fail(AFR_EINVAL, "optimizer groups: first = %lld and n = %lld must be non-negative multiples of 4", (long long)first, (long long)n);
+    int64_t prev = 0;
+    for (int k = 0; k < nr; ++k) {
+        if (r[k].end <= prev || (r[k].end & 3)) return fail(AFR_EINVAL, "optimizer groups: range ends must be multiples of 4 and strictly increasing (range %d ends at %lld)", k, (long long)r[k].end);
+        if (!mult_ok(r[k].lr_mult) || !mult_ok(r[k].wd_mult)) return fail(AFR_EINVAL, "optimizer groups: the multipliers of range %d must be finite and >= 0", k);
+        prev = r[k].end;
+    }
+    if (prev < first + n) return fail(AFR_EINVAL, "optimizer groups: the last range ends at %lld, before the slice's end %lld", (long long)prev, (long long)(first + n));
+    tab.n = 0;
+    for (int k = 0; k < nr; ++k) {
+        if (r[k].end <= first) continue;
+        if (tab.n >= AFR_OPT_MAX_RANGES) return fail(AFR_EUNSUPPORTED, "optimizer groups: a slice may cross at most %d ranges", AFR_OPT_MAX_RANGES);
+        if (r[k].end / 4 > 0xffffffffll) return fail(AFR_EUNSUPPORTED, "optimizer groups: a flat buffer of 2^34 elements or more");
+        const AdamArgs a = group_args(h, r[k]);
+        tab.end4[tab.n] = (unsigned)(r[k].end / 4); tab.lr[tab.n] = a.lr; tab.wd[tab.n] = a.wd; tab.step[tab.n] = adam_hyper(a, kind).step;
+        tab.n++;
+        if (r[k].end >= first + n) break;
+    }
+    return AFR_OK;
+}
 // the bf16 weight shadow the GEMMs read / the one a fused optimizer step writes (the same buffer unless the plan has two)
 static inline bf16_t* shadow_rd(const afr_plan* p) {
     if (p->cfg.dtype != AFR_BF16) return nullptr;
@@ -656,7 +702,7 @@ static inline bool moments_bound(const afr_plan* p) { return p->M && (p->V || p-
 static void set_fused_opt(const afr_plan* p, GemmParams& g, int64_t off, bf16_t* shadow, const AdamArgs& h) {
     g.ad_p = p->P + off; g.ad_m = p->M + off; g.ad_v = p->opt_kind == OPT_LION ? nullptr : p->V + off;
     g.ad_shadow = shadow ? shadow + off : nullptr;
-    g.ad = adam_hyper(h, p->opt_kind); g.ad_kind = p->opt_kind;
+    g.ad = adam_hyper(args_at(p, h, off), p->opt_kind); g.ad_kind = p->opt_kind;
 }
 static inline const void* weight_ptr(const afr_plan* p, int64_t off) {
     if (p->cfg.dtype == AFR_BF16) return shadow_rd(p) + off;
@@ -792,11 +838,11 @@ static int run_dw(afr_plan* p, hipStream_t s, afr_plan::Layer& l, const void* dy
     afr_rtable_add(rt, p->G + l.b_off, sb, sk, N, N);
     return AFR_OK;
 }
-static int run_reduce_group(afr_plan* p, hipStream_t s, const RTable& rt) {
+static int run_reduce_group(afr_plan* p, hipStream_t s, const RTable& rt, const AdamHyper* seg_ad = nullptr) {
     double bytes = 0;
     for (int i = 0; i < rt.nseg; ++i) bytes += 16.0 * rt.seg[i].n4 * (rt.seg[i].nslabs + 1);
     ProfScope ps(p, s, "reduce_group", 0.0, bytes);
-    HIPCHK(afr_launch_reduce_group(rt, s));
+    HIPCHK(afr_launch_reduce_group(rt, s, seg_ad));
     return AFR_OK;
 }
 
@@ -1422,6 +1468,37 @@ extern "C" int afr_set_optimizer(afr_plan* p, int kind) {
     p->opt_kind = kind;
     return AFR_OK;
 }
+extern "C" int afr_set_param_groups(afr_plan* p, const float* lr_mult, const float* wd_mult, int n) {
+    if (!p) return fail(AFR_EINVAL, "null plan");
+    if (int rc = ema_guard(p, "afr_set_param_groups")) return rc;
+    if (n != (int)p->params.size()) return fail(AFR_EINVAL, "afr_set_param_groups: n = %d, the plan has %d parameter tensors", n, (int)p->params.size());
+    for (int i = 0; i < n; ++i)
+        if ((lr_mult && !mult_ok(lr_mult[i])) || (wd_mult && !mult_ok(wd_mult[i])))
+            return fail(AFR_EINVAL, "afr_set_param_groups: the multipliers of tensor %d (%s) must be finite and >= 0", i, p->params[i].name.c_str());
+    p->groups.clear();
+    if (!lr_mult && !wd_mult) return AFR_OK;
+    for (int i = 0; i < n; ++i) {
+        const float lm = lr_mult ? lr_mult[i] : 1.f, wm = wd_mult ? wd_mult[i] : 1.f;
+        const int64_t end = i + 1 < n ? p->params[i + 1].off : p->total;      // the padding behind a tensor belongs to its range
+        if (!p->groups.empty() && p->groups.back().lr_mult == lm && p->groups.back().wd_mult == wm) p->groups.back().end = end;
+        else p->groups.push_back(afr_opt_range{end, lm, wm});
+    }
+    return AFR_OK;
+}
+extern "C" int afr_param_group_ranges(const afr_plan* p, afr_opt_range* out, int cap) {
+    if (!p) return 0;
+    const int n = (int)p->groups.size();
+    for (int k = 0; out && k < n && k < cap; ++k) out[k] = p->groups[k];
+    return n;
+}
+// the grouped flat update of [first, first + n) of caller-owned buffers: the plan's own step and afr_op_opt_groups end here
+static int opt_groups_launch(int kind, float* P, const float* G, float* M, float* V, bf16_t* shadow, int64_t n, int64_t first, const afr_opt_range* r,
+                             int nr, const AdamArgs& h, float gscale, const float* sumsq, float max_norm, hipStream_t s) {
+    OptRangeTab tab;
+    if (int rc = build_range_tab(r, nr, first, n, h, kind, tab)) return rc;
+    HIPCHK(afr_launch_opt_groups(P, G, M, kind == OPT_LION ? nullptr : V, shadow, n, first, tab, adam_hyper(h, kind), gscale, s, sumsq, max_norm, kind));
+    return AFR_OK;
+}
 extern "C" int afr_adamw_step(afr_plan* p, float lr, float b1, float b2, float eps, float wd, int64_t t, float gscale,
                               void* stream) {
     if (!p || !p->P || !p->G || !moments_bound(p))
@@ -1439,7 +1516,12 @@ extern "C" int afr_adamw_step(afr_plan* p, float lr, float b1, float b2, float e
         sumsq = cw + CLIP_WS_SUMSQ;
     }
     const bool lion = p->opt_kind == OPT_LION;
-    {
+    if (!p->groups.empty()) {             // optimizer groups: the whole buffer in ONE launch of the range-aware kernel
+        ProfScope ps(p, s, lion ? (sumsq ? "lion_groups_clip" : "lion_groups") : (sumsq ? "adamw_groups_clip" : "adamw_groups"), 0.0,
+                     (double)p->total * ((lion ? 20.0 : 28.0) + (shadow ? 2.0 : 0.0)));
+        if (int rc = opt_groups_launch(p->opt_kind, p->P, p->G, p->M, p->V, shadow, p->total, 0, p->groups.data(), (int)p->groups.size(),
+                                       AdamArgs{lr, b1, b2, eps, wd, t}, gscale, sumsq, p->clip_norm, s)) return rc;
+    } else {
         ProfScope ps(p, s, lion ? (sumsq ? "lion_clip" : "lion") : (sumsq ? "adamw_clip" : "adamw"), 0.0, (double)p->total * ((lion ? 20.0 : 28.0) + (shadow ? 2.0 : 0.0)));
         HIPCHK(afr_launch_adamw(p->P, p->G, p->M, lion ? nullptr : p->V, shadow, p->total, lr, wd, adam_hyper(AdamArgs{lr, b1, b2, eps, wd, t}, p->opt_kind),
                                 gscale, s, sumsq, p->clip_norm, p->opt_kind));
@@ -1451,13 +1533,44 @@ extern "C" int afr_adamw_step(afr_plan* p, float lr, float b1, float b2, float e
 // Single-GPU optimiser step fused into the grouped slab reduction: every tensor whose gradient was produced as partial
 // slabs (split-K dW, bias partials, embedding partials, the sheet model's small tensors) is updated in the kernel that
 // sums its slabs -- the summed gradient is never stored; tensors whose gradient a GEMM wrote directly get the plain kernel.
+// Optimizer groups: a segment of the grouped reduce is updated with ONE hyper, so a segment that crosses a boundary between two
+// ranges (the sheet model's ten small tensors arrive as one) is cut there; the pieces sum the same slabs in the same order.  A
+// segment that also keeps a transposed copy cannot be cut (it never spans two tensors): refused, never given one side's scalars.
+static int split_segments_at_groups(const afr_plan* p, RTable& rt) {
+    RTable nt = rt;
+    nt.nseg = 0; nt.nblocks = 0; nt.overflow = 0;
+    for (int i = 0; i < rt.nseg; ++i) {
+        const RSeg& sg = rt.seg[i];
+        const int64_t so = sg.dst - p->G, se = so + sg.n4 * 4;
+        for (int64_t cur = so; cur < se;) {
+            const int64_t re = range_at(p, cur)->end, pe = re < se ? re : se;
+            const bool whole = cur == so && pe == se;
+            if (!whole && sg.shT) return fail(AFR_ESTATE, "optimizer groups: a reduce segment with a transposed copy crosses a range boundary at %lld", (long long)re);
+            afr_rtable_add(nt, sg.dst + (cur - so), sg.src + (cur - so), sg.nslabs, sg.stride, pe - cur);
+            if (whole && !nt.overflow) { RSeg& ns = nt.seg[nt.nseg - 1]; ns.shT = sg.shT; ns.tN = sg.tN; ns.tK = sg.tK; }
+            cur = pe;
+        }
+    }
+    if (nt.overflow) return fail(AFR_EUNSUPPORTED, "optimizer groups: the step's reduce segments, cut at the range boundaries, exceed %d", AFR_RT_MAXSEG);
+    rt = nt;
+    return AFR_OK;
+}
 static int reduce_and_step(afr_plan* p, hipStream_t s, RTable& rt, const AdamArgs& h, int64_t skip_off = -1) {
     bf16_t* shadow = shadow_wr(p);        // every tensor's new bf16 copy goes to the write shadow; the roles swap below
     const bool lion = p->opt_kind == OPT_LION;
+    const bool grouped = !p->groups.empty();
     rt.adam = 1; rt.ad = adam_hyper(h, p->opt_kind); rt.kind = p->opt_kind;
     rt.gbase = p->G; rt.P = p->P; rt.M = p->M; rt.V = lion ? nullptr : p->V; rt.shadow = shadow;
     p->wT_valid = false;
-    int rc = run_reduce_group(p, s, rt);
+    AdamHyper seg_ad[AFR_RT_MAXSEG];
+    int rc;
+    if (grouped) {                        // every segment takes the hyper of the range its flat offset lies in
+        if (rt.overflow) return fail(AFR_EUNSUPPORTED, "optimizer groups: the step's reduce has more than %d segments", AFR_RT_MAXSEG);
+        if ((rc = split_segments_at_groups(p, rt))) return rc;
+        for (int i = 0; i < rt.nseg; ++i) seg_ad[i] = adam_hyper(args_at(p, h, rt.seg[i].dst - p->G), p->opt_kind);
+    }
+    // (an empty table launches nothing either way: the launcher returns before it looks at the hypers)
+    rc = run_reduce_group(p, s, rt, grouped ? seg_ad : nullptr);
     if (rc) return rc;
     for (const Tensor& tn : p->params) {
         if (tn.off == skip_off) continue;
@@ -1474,8 +1587,9 @@ static int reduce_and_step(afr_plan* p, hipStream_t s, RTable& rt, const AdamArg
         if (cov >= tn.numel) continue;
         const int64_t n = (tn.numel + 63) / 64 * 64;
         ProfScope ps(p, s, lion ? "lion" : "adamw", 0.0, (double)n * (lion ? 20.0 : 28.0));
-        HIPCHK(afr_launch_adamw(p->P + tn.off, p->G + tn.off, p->M + tn.off, lion ? nullptr : p->V + tn.off, shadow ? shadow + tn.off : nullptr, n, h.lr, h.wd,
-                                rt.ad, 1.f, s, nullptr, 0.f, p->opt_kind));
+        const AdamArgs ht = args_at(p, h, tn.off);
+        HIPCHK(afr_launch_adamw(p->P + tn.off, p->G + tn.off, p->M + tn.off, lion ? nullptr : p->V + tn.off, shadow ? shadow + tn.off : nullptr, n, ht.lr, ht.wd,
+                                grouped ? adam_hyper(ht, p->opt_kind) : rt.ad, 1.f, s, nullptr, 0.f, p->opt_kind));
     }
     if (p->o_shadow2) p->shadow_cur ^= 1;   // every tensor has been rewritten: the write shadow is the current one now
     p->adam_done.clear();
@@ -1881,6 +1995,17 @@ extern "C" int afr_op_lion(float* p, const float* g, float* m, void* shadow, int
     HIPCHK(afr_launch_adamw(p, g, m, nullptr, (bf16_t*)shadow, n, lr, wd, adam_hyper(AdamArgs{lr, b1, b2, 0.f, wd, 1}, OPT_LION), gscale,
                             (hipStream_t)stream, sumsq, max_norm, OPT_LION));
     return AFR_OK;
+}
+extern "C" int afr_op_opt_groups(int kind, float* p, const float* g, float* m, float* v, void* shadow, int64_t n, int64_t first,
+                                 const afr_opt_range* ranges, int n_ranges, float lr, float b1, float b2, float eps, float wd, int64_t t, float gscale,
+                                 const float* sumsq, float max_norm, void* stream) {
+    if (kind != AFR_OPT_ADAMW && kind != AFR_OPT_LION) return fail(AFR_EINVAL, "optimizer kind must be AFR_OPT_ADAMW (0) or AFR_OPT_LION (1), got %d", kind);
+    if (!p || !g || !m || (kind == AFR_OPT_ADAMW && !v)) return fail(AFR_EINVAL, "null argument");
+    if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
+    if (sumsq && (!(max_norm > 0.f) || std::isinf(max_norm))) return fail(AFR_EINVAL, "max_norm must be finite and > 0, got %g", (double)max_norm);
+    DevGuard dg(device_of(p));
+    return opt_groups_launch(kind, p, g, m, v, (bf16_t*)shadow, n, first, ranges, n_ranges, AdamArgs{lr, b1, b2, eps, wd, kind == AFR_OPT_LION ? 1 : t}, gscale,
+                             sumsq, max_norm, (hipStream_t)stream);
 }
 extern "C" int afr_op_mse_grad(int act_dtype, const void* u, const void* target, int tdtype, void* du, int64_t rows,
                                int64_t cols, int64_t mean_elems, float* loss_accum, float* scratch, void* stream) {

@@ -71,10 +71,10 @@ __device__ __forceinline__ float4 slab_sum(const float* src, long long stride, i
     return a;
 }
 template <int OPT>
-__device__ __forceinline__ void reduce_finish(const RTable& t, const RSeg& sg, long long i, float4 a, f32x4 pp, f32x4 mm, f32x4 vv) {
+__device__ __forceinline__ void reduce_finish(const RTable& t, const AdamHyper& ad, const RSeg& sg, long long i, float4 a, f32x4 pp, f32x4 mm, f32x4 vv) {
     if (t.adam) {
         const long long off = (sg.dst - t.gbase) + 4 * i;
-        const bf16x4 o = opt_quad<OPT>(pp, mm, vv, (f32x4){a.x, a.y, a.z, a.w}, t.ad);
+        const bf16x4 o = opt_quad<OPT>(pp, mm, vv, (f32x4){a.x, a.y, a.z, a.w}, ad);
         *reinterpret_cast<f32x4*>(t.P + off) = pp;
         *reinterpret_cast<f32x4*>(t.M + off) = mm;
         if constexpr (OPT == OPT_ADAMW) *reinterpret_cast<f32x4*>(t.V + off) = vv;
@@ -89,11 +89,19 @@ __device__ __forceinline__ void reduce_finish(const RTable& t, const RSeg& sg, l
     }
 }
 // OPT: the optimizer kind of a fused step (t.adam); the OPT_LION instantiation neither loads nor stores V
-template <int OPT = OPT_ADAMW>
-__global__ __launch_bounds__(256) void reduce_group_kernel(RTable t) {
+// GROUPS (optimizer groups, afr_set_param_groups): the argument is an RTableG and the block's segment is updated with ITS hyper
+// (seg_ad[si], looked up by the host from the segment's flat offset) instead of the table's one; with GROUPS false the body is as it was.
+__device__ __forceinline__ const RTable& rtable_of(const RTable& t) { return t; }
+__device__ __forceinline__ const RTable& rtable_of(const RTableG& t) { return t.t; }
+__device__ __forceinline__ const AdamHyper& hyper_of(const RTable& t, int) { return t.ad; }
+__device__ __forceinline__ const AdamHyper& hyper_of(const RTableG& t, int si) { return t.seg_ad[si]; }
+template <int OPT = OPT_ADAMW, bool GROUPS = false>
+__global__ __launch_bounds__(256) void reduce_group_kernel(std::conditional_t<GROUPS, RTableG, RTable> tt) {
+    const RTable& t = rtable_of(tt);
     int si = 0;
     for (int k = 1; k < t.nseg; ++k) if ((int)blockIdx.x >= t.seg[k].blk0) si = k;
     const RSeg sg = t.seg[si];
+    const AdamHyper& ad = hyper_of(tt, si);
     f32x4 pp = {0.f, 0.f, 0.f, 0.f}, mm = pp, vv = pp;
     if (sg.deep) {
         // many slabs, few columns (the per-block partials of the sheet backward): a block owns 64 float4 columns and
@@ -119,7 +127,7 @@ __global__ __launch_bounds__(256) void reduce_group_kernel(RTable t) {
             if (grp == 0 && live) {
 #pragma unroll
                 for (int g = 0; g < 3; ++g) { const float4 v = part[g][col]; a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
-                reduce_finish<OPT>(t, sg, i, a, pp, mm, vv);
+                reduce_finish<OPT>(t, ad, sg, i, a, pp, mm, vv);
             }
             __syncthreads();
         }
@@ -132,7 +140,7 @@ __global__ __launch_bounds__(256) void reduce_group_kernel(RTable t) {
             if constexpr (OPT == OPT_ADAMW) vv = *reinterpret_cast<f32x4*>(t.V + off);
         }
         const float4 a = slab_sum(sg.src + 4 * i, sg.stride, 0, sg.nslabs);
-        reduce_finish<OPT>(t, sg, i, a, pp, mm, vv);
+        reduce_finish<OPT>(t, ad, sg, i, a, pp, mm, vv);
     }
 }
 void afr_rtable_add(RTable& t, float* dst, const float* src, int nslabs, long long stride, long long n) {
@@ -149,9 +157,16 @@ void afr_rtable_add(RTable& t, float* dst, const float* src, int nslabs, long lo
     t.nblocks += (int)nb;
     t.nseg++;
 }
-hipError_t afr_launch_reduce_group(const RTable& t, hipStream_t s) {
-    if (t.overflow) return hipErrorInvalidValue;
+hipError_t afr_launch_reduce_group(const RTable& t, hipStream_t s, const AdamHyper* seg_ad) {
+    if (t.overflow || (seg_ad && !t.adam)) return hipErrorInvalidValue;
     if (t.nseg == 0) return hipSuccess;
+    if (seg_ad) {
+        RTableG tg;
+        tg.t = t;
+        for (int k = 0; k < t.nseg; ++k) tg.seg_ad[k] = seg_ad[k];
+        with_opt(t.kind, [&](auto opt) { hipLaunchKernelGGL((reduce_group_kernel<opt(), true>), dim3(t.nblocks), dim3(256), 0, s, tg); });
+        return hipGetLastError();
+    }
     with_opt(t.adam ? t.kind : OPT_ADAMW, [&](auto opt) { hipLaunchKernelGGL(reduce_group_kernel<opt()>, dim3(t.nblocks), dim3(256), 0, s, t); });
     return hipGetLastError();
 }
@@ -212,6 +227,78 @@ hipError_t afr_launch_adamw(float* p, const float* g, float* m, float* v, bf16_t
     with_bool(sumsq != nullptr, [&](auto clip) { with_opt(kind, [&](auto opt) {
         hipLaunchKernelGGL((adamw_kernel<clip(), opt()>), dim3(grid_for(n / 4, 256, 4096)), dim3(256), 0, s, p, g, m, v, shadow, n / 4, lr,
                            h.b1, h.b2, h.eps, wd, h.step, h.rsqrt_bc2, grad_scale, sumsq, max_norm);
+    }); });
+    return hipGetLastError();
+}
+
+// ----------------------------------------------------------------------------- optimizer groups
+// adamw_kernel's walk over a slice whose tensors carry their own (lr, wd): afr_set_param_groups / afr_op_opt_groups.  ONE launch for the
+// whole slice, the grid adamw_kernel would take.  The range table arrives by value; the block's first tab.n lanes fold each range's
+// decay exactly as adamw_kernel folds it from its scalars (so a range is updated bit for bit as adamw_kernel<CLIP, OPT> would update it
+// with that range's lr, wd) and park (end, decay, step) in LDS, ends relative to the slice.  A lane keeps a cursor into the table that
+// only moves forward as its grid-stride index grows: at most tab.n LDS reads over the lane's whole life on top of two per quad, and no
+// extra global traffic -- the 16-byte accesses and the 28 (+2) / 20 (+2) bytes per element are adamw_kernel's.  Lanes of one wave may sit
+// in different ranges (tensor offsets are multiples of 64 elements, a wave covers 256).  No pow, no division: step is the host's.
+template <bool CLIP, int OPT>
+__global__ __launch_bounds__(256) void opt_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, bf16_t* __restrict__ shadow, long long n4, unsigned first4,
+                                                         float b1, float b2, float eps, float rsqrt_bc2, float gscale,
+                                                         const float* __restrict__ sumsq, float max_norm, OptRangeTab tab) {
+    __shared__ unsigned s_end[AFR_OPT_MAX_RANGES];
+    __shared__ float s_decay[AFR_OPT_MAX_RANGES], s_step[AFR_OPT_MAX_RANGES];
+    if constexpr (CLIP) {
+        const float ss = *sumsq;
+        if (!finite_f(ss)) return;
+        float tn;
+        gscale = mul_rn(gscale, clip_coef(ss, fabsf(gscale), max_norm, tn));
+    }
+    // the first trip's loads are issued AHEAD of the table staging, so that the block's start-up (table loads, LDS, barrier) hides
+    // behind them instead of standing in front of its first byte in flight
+    const long long stride = (long long)gridDim.x * 256;
+    long long i = blockIdx.x * 256ll + threadIdx.x;
+    float4 p4 = make_float4(0.f, 0.f, 0.f, 0.f), gg = p4, m4 = p4, v4 = p4;
+    auto load = [&]() {
+        p4 = reinterpret_cast<float4*>(p)[i];
+        gg = reinterpret_cast<const float4*>(g)[i];
+        m4 = reinterpret_cast<float4*>(m)[i];
+        if constexpr (OPT == OPT_ADAMW) v4 = reinterpret_cast<float4*>(v)[i];
+    };
+    if (i < n4) load();
+    if ((int)threadIdx.x < tab.n) {
+        const int k = threadIdx.x;
+        const float lr = tab.lr[k], wd = tab.wd[k];
+        const unsigned e = tab.end4[k];
+        s_end[k] = e > first4 ? e - first4 : 0u;
+        s_decay[k] = OPT == OPT_LION ? 1.f - mul_rn(lr, wd) : 1.f - lr * wd;
+        s_step[k] = tab.step[k];
+    }
+    __syncthreads();
+    const int last = tab.n - 1;
+    int cur = 0;
+    while (i < n4) {
+        while (cur < last && (unsigned long long)i >= s_end[cur]) ++cur;      // (the last range reaches the end of the slice)
+        const AdamHyper h{s_decay[cur], b1, b2, eps, s_step[cur], rsqrt_bc2};
+        f32x4 pp = {p4.x, p4.y, p4.z, p4.w}, mm = {m4.x, m4.y, m4.z, m4.w}, vv = {v4.x, v4.y, v4.z, v4.w};
+        const f32x4 ge = (CLIP || OPT == OPT_LION) ? (f32x4){mul_rn(gg.x, gscale), mul_rn(gg.y, gscale), mul_rn(gg.z, gscale), mul_rn(gg.w, gscale)}
+                                                   : (f32x4){gg.x * gscale, gg.y * gscale, gg.z * gscale, gg.w * gscale};
+        const bf16x4 o = opt_quad<OPT>(pp, mm, vv, ge, h);
+        reinterpret_cast<float4*>(p)[i] = make_float4(pp[0], pp[1], pp[2], pp[3]);
+        reinterpret_cast<float4*>(m)[i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
+        if constexpr (OPT == OPT_ADAMW) reinterpret_cast<float4*>(v)[i] = make_float4(vv[0], vv[1], vv[2], vv[3]);
+        if (shadow) reinterpret_cast<bf16x4*>(shadow)[i] = o;
+        i += stride;
+        if (i < n4) load();
+    }
+}
+hipError_t afr_launch_opt_groups(float* p, const float* g, float* m, float* v, bf16_t* shadow, long long n, long long first, const OptRangeTab& tab,
+                                 const AdamHyper& h, float grad_scale, hipStream_t s, const float* sumsq, float max_norm, int kind) {
+    if (n <= 0) return hipSuccess;
+    // the table must cover the slice: a cursor that ran past it would hand the tail the last range's scalars silently
+    if ((n & 3) || (first & 3) || first < 0 || tab.n < 1 || tab.n > AFR_OPT_MAX_RANGES || (first + n) / 4 > (long long)tab.end4[tab.n - 1])
+        return hipErrorInvalidValue;
+    with_bool(sumsq != nullptr, [&](auto clip) { with_opt(kind, [&](auto opt) {
+        hipLaunchKernelGGL((opt_groups_kernel<clip(), opt()>), dim3(grid_for(n / 4, 256, 4096)), dim3(256), 0, s, p, g, m, v, shadow, n / 4,
+                           (unsigned)(first / 4), h.b1, h.b2, h.eps, h.rsqrt_bc2, grad_scale, sumsq, max_norm, tab);
     }); });
     return hipGetLastError();
 }

@@ -65,8 +65,10 @@ class Engine:
     state_dict order, so checkpoints interchange with the reference (helpers.py:76-105)."""
 
     def __init__(self, cfg, dtype="f32", max_batch=1024, device=None, seed=42, rank=0, with_optimizer=True, flags=0, micro_batch=None,
-                 loss="mse", max_grad_norm=None, optimizer="adamw", ema_decay=None, ema_every=1):
-        """ema_decay: keep an exponential moving average of the weights (set_ema); None = off.  ema_every: update it every that many
+                 loss="mse", max_grad_norm=None, optimizer="adamw", ema_decay=None, ema_every=1, lr_mult=None, wd_mult=None):
+        """lr_mult, wd_mult: optimizer groups (set_param_groups): dicts of tensor name -> multiplier of the step's lr / weight decay;
+        None = the reference's single group.
+        ema_decay: keep an exponential moving average of the weights (set_ema); None = off.  ema_every: update it every that many
         optimizer steps.
         optimizer: "adamw" (torch.optim.AdamW, the reference's) or "lion" (one moment, sign update: include/afr.h afr_set_optimizer);
         every optimizer step of the engine follows it, and a Lion engine allocates no exp_avg_sq.
@@ -95,6 +97,8 @@ class Engine:
         # the weight EMA (set_ema): flat_ema in the parameter layout, ema_params its views; _ema_on inside ema_weights()
         self.ema_decay, self.ema_every = self._check_ema(ema_decay, ema_every)
         self.flat_ema, self.ema_params, self._ema_on = None, {}, False
+        self.lr_mult, self.wd_mult, self._ranges = None, None, None      # optimizer groups (set_param_groups); _ranges: the plan's merged table
+        self.layout = None          # read from the plan below, once it is bound
         self._make_plan(self.max_batch)
         n = self.lib.afr_param_elems(self._plan)
         self.n_flat = int(n)
@@ -119,6 +123,8 @@ class Engine:
         self._keep = None     # keeps the last inputs alive until backward has consumed them
         if self.ema_decay is not None:
             self.set_ema(self.ema_decay, self.ema_every)
+        if lr_mult is not None or wd_mult is not None:
+            self.set_param_groups(lr_mult, wd_mult)
 
     def _call(self, fn, *args):
         """One libafr call that enqueues work: on THIS engine's device and on the caller's current stream of that device
@@ -144,8 +150,51 @@ class Engine:
         self._apply_clip()
         _lib.check(self.lib.afr_set_optimizer(self._plan, _lib.opt_kind(self.optimizer)))      # host-only; ensure_batch's new plan gets it again
         self._apply_ema()
+        self._apply_groups()
         if self._ema_on:          # a re-plan inside ema_weights(): the new plan reads the EMA too
             self._call(self.lib.afr_use_ema, self._plan, 1)
+
+    # ---------------------------------------------------------------- optimizer groups
+    def _mult_array(self, mult):
+        """dict name -> multiplier as the float array afr_set_param_groups takes, in layout order (missing names: 1.0); None stays None."""
+        if mult is None:
+            return None
+        names = [nm for nm, _, _, _ in self.layout]
+        for nm in mult:
+            if nm not in names:
+                raise KeyError(f"{nm!r} is no parameter tensor of this model")
+        return (C.c_float * len(names))(*[float(mult.get(nm, 1.0)) for nm in names])
+
+    def _apply_groups(self):
+        """Hand the plan its groups (host-only call; ensure_batch's new plan gets them again) and read the merged table back."""
+        if self.layout is None:               # the constructor's first bind: the layout is not read yet, and there are no groups
+            return
+        lm, wm = self._mult_array(self.lr_mult), self._mult_array(self.wd_mult)
+        _lib.check(self.lib.afr_set_param_groups(self._plan, lm, wm, len(self.layout)))
+        n = int(self.lib.afr_param_group_ranges(self._plan, None, 0))
+        self._ranges = (_lib.AfrOptRange * n)() if n else None
+        if n:
+            self.lib.afr_param_group_ranges(self._plan, self._ranges, n)
+
+    def set_param_groups(self, lr_mult=None, wd_mult=None):
+        """Optimizer groups from the next optimizer step on: tensor `name` is stepped with fl32(lr * lr_mult[name]) and
+        fl32(weight_decay * wd_mult[name]) (include/afr.h afr_set_param_groups) through every path of a step -- fused or not, clipped or
+        not, by rows, accumulated, and the slices of adamw_range.  Each argument is a dict of tensor name -> float; names that are
+        missing take 1.0, an unknown name is a KeyError, a negative or non-finite value an AfrError.  Both None: groups off, the
+        reference's single group.  state_dict() and the saved file know nothing of it."""
+        self._not_in_ema("set_param_groups")
+        old = self.lr_mult, self.wd_mult
+        self.lr_mult = None if lr_mult is None else dict(lr_mult)
+        self.wd_mult = None if wd_mult is None else dict(wd_mult)
+        try:
+            self._apply_groups()
+        except Exception:
+            self.lr_mult, self.wd_mult = old
+            raise
+
+    def param_group_ranges(self):
+        """The plan's merged table: [(end offset, lr_mult, wd_mult)], [] when groups are off."""
+        return [(int(r.end), float(r.lr_mult), float(r.wd_mult)) for r in (self._ranges or [])]
 
     # ---------------------------------------------------------------- weight EMA
     @staticmethod
@@ -485,6 +534,13 @@ class Engine:
         self._not_in_ema("adamw_range")
         self.t += 1
         o, e = int(offset), int(offset) + int(n)
+        if self._ranges is not None:      # optimizer groups: the slice in one launch of the range-aware kernel, with the plan's table
+            lion = self.optimizer == "lion"
+            self._call(self.lib.afr_op_opt_groups, _lib.opt_kind(self.optimizer), _ptr(self.flat_params[o:e]), _ptr(self.flat_grads[o:e]),
+                       _ptr(self.exp_avg[o:e]), C.c_void_p(0) if lion else _ptr(self.exp_avg_sq[o:e]), C.c_void_p(0), int(n), o, self._ranges,
+                       len(self._ranges), lr, betas[0], betas[1], eps, weight_decay, self.t, grad_scale, _ptr(sumsq), float(self.max_grad_norm or 0.0))
+            self._keep_ss = sumsq
+            return
         if self.optimizer == "lion":      # the same slice step by afr_op_lion, clipped when sumsq is given
             self._call(self.lib.afr_op_lion, _ptr(self.flat_params[o:e]), _ptr(self.flat_grads[o:e]), _ptr(self.exp_avg[o:e]), C.c_void_p(0), int(n),
                        lr, betas[0], betas[1], weight_decay, grad_scale, _ptr(sumsq), float(self.max_grad_norm or 0.0))

@@ -27,7 +27,9 @@ What is deliberately different from the reference, and why:
   * AFR_EMA=<decay> or AFR_EMA=<decay>:<every> (0.999, 0.999:8) keeps an exponential moving average of the weights, updated on the
     device after every <every>-th optimizer step (Engine.set_ema).  The validation loss that picks the best epoch and drives the
     plateau scheduler, the 5-epoch test-string dumps and the saved model are then taken from the average.  Unset: the reference's
-    loop, nothing changes.
+    loop, nothing changes;
+  * AFR_NO_DECAY=1 takes the tensors of config.no_decay_names -- every bias and LayerNorm tensor, the positional table and the
+    embedding -- out of weight decay (optimizer groups, Engine.set_param_groups).  Unset: one group, the reference's optimizer.
 """
 import contextlib
 import datetime
@@ -40,7 +42,7 @@ import torch
 import torch.nn as nn
 
 from . import helpers
-from .config import SheetConfig
+from .config import SheetConfig, no_decay_names
 from .helpers import MODEL_FILENAME, load_model, load_string_dataset, render_strings, save_model  # noqa: F401
 
 # ---------------------------------------------------------------- constants (reference model.py:64-87)
@@ -193,10 +195,12 @@ class AttentionFontRenderer(nn.Module):
     optimizer: "adamw" (the reference's) or "lion"; None takes AFR_OPTIMIZER from the environment.  train_attention_model steps a Lion
     model with LEARNING_RATE / 10 and WEIGHT_DECAY * 10 (the Lion paper's rule of thumb: lr * weight_decay stays what it was).
     ema_decay, ema_every: keep an exponential moving average of the weights (Engine.set_ema); ema_decay None takes AFR_EMA from the
-    environment (unset: off).  train_attention_model then validates, renders and saves from the average."""
+    environment (unset: off).  train_attention_model then validates, renders and saves from the average.
+    no_decay: True steps the tensors of config.no_decay_names with weight decay 0 (Engine.set_param_groups); None takes AFR_NO_DECAY=1
+    from the environment (unset: off, the reference's single group)."""
 
     def __init__(self, max_length=MAX_CHARS_PER_SHEET, dtype=None, max_batch=1024, seed=SEED, rank=None, init=True, loss=None,
-                 max_grad_norm=None, optimizer=None, ema_decay=None, ema_every=1):
+                 max_grad_norm=None, optimizer=None, ema_decay=None, ema_every=1, no_decay=None):
         super().__init__()
         from .engine import Engine
         self.max_length = max_length
@@ -210,6 +214,9 @@ class AttentionFontRenderer(nn.Module):
         self.engine = Engine(self.config, dtype=dtype or COMPUTE_DTYPE, max_batch=max_batch, device=device, seed=seed, rank=rank,
                              loss=loss or COMPUTE_LOSS, max_grad_norm=CLIP_NORM if max_grad_norm is None else max_grad_norm,
                              optimizer=optimizer or COMPUTE_OPTIMIZER, ema_decay=ema_decay, ema_every=ema_every)
+        self.no_decay = os.environ.get("AFR_NO_DECAY") == "1" if no_decay is None else bool(no_decay)
+        if self.no_decay:
+            self.engine.set_param_groups(wd_mult={name: 0.0 for name in no_decay_names(self.config)})
         self.loss = self.engine.loss
         self.optimizer = self.engine.optimizer
         self.max_grad_norm = self.engine.max_grad_norm

@@ -180,6 +180,23 @@ int afr_adamw_step(afr_plan* plan, float lr, float beta1, float beta2, float eps
 enum { AFR_OPT_ADAMW = 0, AFR_OPT_LION = 1 };
 int afr_set_optimizer(afr_plan* plan, int kind);
 
+/* ---- optimizer groups: a learning-rate and a weight-decay multiplier per parameter tensor (torch.optim's param groups) ----
+ * For the tensor with index i of afr_param_info and multipliers lr_mult[i], wd_mult[i] every optimizer step of the plan uses
+ *     lr_i = fl32(lr * lr_mult[i])      wd_i = fl32(weight_decay * wd_mult[i])      (on the host, f32, not contracted)
+ * and updates that tensor by the plan's optimizer kind exactly as every site of a step updates it when handed lr_i and wd_i as its
+ * lr and weight_decay: the same folding of the scalars, the same roundings -- a multiplier of exactly 1.0f reproduces the bits of a
+ * plan without groups.  The 64-element padding behind a tensor belongs to that tensor's range.  beta1, beta2, eps, t, grad_scale,
+ * the clip coefficient and the EMA stay global, and the global gradient norm does not see the multipliers.
+ * n must equal afr_param_count().  Either pointer may be NULL (all ones for that multiplier); both NULL switch groups off.  Every
+ * value must be finite and >= 0 (AFR_EINVAL, checked before anything is stored).  Adjacent tensors with equal multipliers are merged
+ * into ranges {end offset, lr_mult, wd_mult} of the flat buffer, which afr_param_group_ranges returns (its result: the number of
+ * ranges, 0 = groups off; at most cap of them are written, out may be NULL).  A flat update crosses at most 128 ranges in one launch
+ * (AFR_EUNSUPPORTED beyond, never a silent drop).  Host-only: nothing is launched or allocated.  The setting lives in the plan and
+ * survives afr_bind; a new plan has no groups.  AFR_ESTATE while afr_use_ema is on. */
+typedef struct afr_opt_range { int64_t end; float lr_mult, wd_mult; } afr_opt_range;
+int afr_set_param_groups(afr_plan* plan, const float* lr_mult, const float* wd_mult, int n);
+int afr_param_group_ranges(const afr_plan* plan, afr_opt_range* out, int cap);
+
 /* Clipping by the GLOBAL gradient norm inside the optimizer step (torch.nn.utils.clip_grad_norm_; the reference's loop has
  * none).  Off by default; with max_norm > 0 every optimizer step of the plan (afr_adamw_step, afr_train_step* with do_step)
  * computes, on the device,
@@ -358,6 +375,15 @@ int afr_op_adamw_clip(float* p, const float* g, float* m, float* v, void* shadow
  * (max_norm is not read); else the clip semantics of afr_op_adamw_clip, a non-finite *sumsq_dev leaving p, m and the shadow untouched. */
 int afr_op_lion(float* p, const float* g, float* m, void* shadow_bf16, int64_t n, float lr, float beta1, float beta2,
                 float weight_decay, float grad_scale, const float* sumsq_dev /* NULL = no clip */, float max_norm, void* stream);
+/* The grouped update (afr_set_param_groups) on a slice, in ONE launch: the sharded optimizer's and the unit tests' entry.  p, g, m, v
+ * and shadow_bf16 point at the slice's first element, which is element `first` of the flat buffer the ranges describe; n and first
+ * are multiples of 4.  ranges: a HOST array of n_ranges entries in flat coordinates -- ends multiples of 4 and strictly increasing,
+ * the last one >= first + n; range k covers [ranges[k-1].end, ranges[k].end) and is updated with fl32(lr * lr_mult), fl32(weight_decay
+ * * wd_mult).  kind AFR_OPT_ADAMW: afr_op_adamw's update (afr_op_adamw_clip's with sumsq_dev); AFR_OPT_LION: afr_op_lion's (v, eps and
+ * t are not read).  sumsq_dev NULL: no clipping.  Bit for bit what those entries give when launched range by range. */
+int afr_op_opt_groups(int kind, float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, int64_t first,
+                      const afr_opt_range* ranges, int n_ranges, float lr, float beta1, float beta2, float eps, float weight_decay,
+                      int64_t t, float grad_scale, const float* sumsq_dev /* NULL = no clip */, float max_norm, void* stream);
 /* scratch: >= 1040 floats, zero before the first call (holds per-block partials and the arrival counter) */
 int afr_op_mse_grad(int act_dtype, const void* u, const void* target, int target_dtype, void* du,
                     int64_t rows, int64_t cols, int64_t mean_elems, float* loss_accum, float* scratch,
