@@ -56,6 +56,22 @@ class AfrOptRange(C.Structure):
     _fields_ = [("end", C.c_int64), ("lr_mult", C.c_float), ("wd_mult", C.c_float)]
 
 
+class AfrSheetParams(C.Structure):
+    """The ten small tensors of the sheet front end (include/afr.h afr_sheet_params), device pointers."""
+    _fields_ = [(n, C.c_void_p) for n in ("pos", "emb", "w_in", "b_in", "w_o", "b_o", "ln_g", "ln_b", "w1", "b1")]
+
+
+class AfrSheetDropout(C.Structure):
+    """One training pass's dropout description (include/afr.h afr_sheet_dropout)."""
+    _fields_ = [("seed", C.c_uint64), ("step", C.c_uint64), ("rank", C.c_int32), ("p_embed", C.c_float), ("p_attn", C.c_float),
+                ("p_fc", C.c_float)]
+
+
+class AfrSheetSlabLayout(C.Structure):
+    """Offsets in floats of the ten tensors inside one partial-gradient slab, and the slab's length (afr_sheet_slab_layout)."""
+    _fields_ = [(n, C.c_int32) for n in ("pos", "emb", "w_in", "b_in", "w_o", "b_o", "ln_g", "ln_b", "w1", "b1", "total")]
+
+
 _vp, _i32, _i64, _f32, _u64, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64, C.c_size_t
 
 # name -> (restype, argtypes): every function include/afr.h declares
@@ -126,6 +142,11 @@ SIGNATURES = {
     "afr_op_pixel_head": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp]),
     "afr_op_pixel_head_bwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp]),
     "afr_op_pixel_ln_bwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp]),
+    "afr_sheet_blocks": (_i32, [_i32]),
+    "afr_sheet_save_floats": (_sz, [_i32, _i32]),
+    "afr_op_sheet_fwd": (_i32, [_i32, C.POINTER(AfrSheetParams), _vp, _i32, _i32, _i32, _i32, _i32, _f32, C.POINTER(AfrSheetDropout), _vp, _vp, _vp, _vp]),
+    "afr_op_sheet_bwd": (_i32, [_i32, C.POINTER(AfrSheetParams), _vp, _i32, _i32, _i32, _i32, _i32, _f32, C.POINTER(AfrSheetDropout), _vp, _vp, _vp,
+                                C.POINTER(AfrSheetSlabLayout), _vp]),
 }
 
 

@@ -910,21 +910,26 @@ extern "C" int afr_op_ema(float* e, const float* p, int64_t n, float decay, cons
     return AFR_OK;
 }
 
-static SheetDrop make_drop(const afr_plan* p, int training, uint64_t step) {
+// the dropout description of one pass from the config fields that define it (the plan's, or an afr_op_sheet_* caller's)
+static SheetDrop sheet_drop(uint64_t seed, uint64_t step, int rank, float p_embed, float p_attn, float p_fc, int training, float* save) {
     SheetDrop d;
-    const afr_config& c = p->cfg;
     d.training = training;
-    d.key_e = afr_dropout_key(c.seed, step, AFR_STREAM_EMBED, (uint64_t)c.rank);
-    d.key_a = afr_dropout_key(c.seed, step, AFR_STREAM_ATTN, (uint64_t)c.rank);
-    d.key_f = afr_dropout_key(c.seed, step, AFR_STREAM_FC, (uint64_t)c.rank);
-    d.thr_e = afr_keep_threshold(1.f - c.p_embed);
-    d.thr_a = afr_keep_threshold(1.f - c.p_attn);
-    d.thr_f = afr_keep_threshold(1.f - c.p_fc);
-    d.sc_e = 1.f / (1.f - c.p_embed);
-    d.sc_a = 1.f / (1.f - c.p_attn);
-    d.sc_f = 1.f / (1.f - c.p_fc);
-    d.save = training ? (float*)(p->ws + p->o_save) : nullptr;     // only a training forward leaves o + softmax stats behind
+    d.key_e = afr_dropout_key(seed, step, AFR_STREAM_EMBED, (uint64_t)rank);
+    d.key_a = afr_dropout_key(seed, step, AFR_STREAM_ATTN, (uint64_t)rank);
+    d.key_f = afr_dropout_key(seed, step, AFR_STREAM_FC, (uint64_t)rank);
+    d.thr_e = afr_keep_threshold(1.f - p_embed);
+    d.thr_a = afr_keep_threshold(1.f - p_attn);
+    d.thr_f = afr_keep_threshold(1.f - p_fc);
+    d.sc_e = 1.f / (1.f - p_embed);
+    d.sc_a = 1.f / (1.f - p_attn);
+    d.sc_f = 1.f / (1.f - p_fc);
+    d.save = save;
     return d;
+}
+static SheetDrop make_drop(const afr_plan* p, int training, uint64_t step) {
+    const afr_config& c = p->cfg;
+    // only a training forward leaves o + softmax stats behind
+    return sheet_drop(c.seed, step, c.rank, c.p_embed, c.p_attn, c.p_fc, training, training ? (float*)(p->ws + p->o_save) : nullptr);
 }
 static SheetParams sheet_params(const afr_plan* p) {
     SheetParams sp;
@@ -2132,5 +2137,72 @@ extern "C" int afr_op_pixel_ln_bwd(int act_dtype, const void* dy, const float* h
     if (!dy || !hin || !g || !dh || !part) return fail(AFR_EINVAL, "afr_op_pixel_ln_bwd: null argument");
     DevGuard dg(device_of(dh));
     HIPCHK(afr_launch_pixel_ln_bwd(act_dtype, dy, hin, g, dh, dhT, part, rows, d, eps, (hipStream_t)stream));
+    return AFR_OK;
+}
+
+// ---- the sheet front end's two kernels one launch each (include/afr.h): argument checks, then the launcher the plan calls
+static int sheet_op_args(const char* what, int act_dtype, const afr_sheet_params* P, const int64_t* x, int ldx, int B, int L, int max_length,
+                         int vocab, const afr_sheet_dropout* drop) {
+    if (act_dtype != AFR_F32 && act_dtype != AFR_BF16) return fail(AFR_EINVAL, "%s: act_dtype must be AFR_F32 or AFR_BF16, got %d", what, act_dtype);
+    if (B < 1) return fail(AFR_EINVAL, "%s: B = %d must be >= 1", what, B);
+    if (L < 1) return fail(AFR_EINVAL, "%s: L = %d must be >= 1", what, L);
+    if (max_length < 1 || vocab < 1) return fail(AFR_EINVAL, "%s: max_length = %d, vocab = %d must be >= 1", what, max_length, vocab);
+    if (L > max_length) return fail(AFR_EINVAL, "%s: L = %d exceeds max_length = %d", what, L, max_length);
+    if (L > 120) return fail(AFR_EUNSUPPORTED, "%s: L = %d exceeds 120 (a string's state must fit one compute unit's LDS)", what, L);
+    if (ldx < L) return fail(AFR_EINVAL, "%s: ldx = %d is below L = %d", what, ldx, L);
+    if ((long long)max_length * 32 >= (1ll << 31) || (long long)vocab * 32 >= (1ll << 31)) return fail(AFR_EUNSUPPORTED, "%s: a table must stay below 2^31 floats", what);
+    if (!P || !x) return fail(AFR_EINVAL, "%s: null argument", what);
+    if (!P->pos || !P->emb || !P->w_in || !P->b_in || !P->w_o || !P->b_o || !P->ln_g || !P->ln_b || !P->w1 || !P->b1)
+        return fail(AFR_EINVAL, "%s: null parameter pointer", what);
+    if (drop) {
+        const float ps[3] = {drop->p_embed, drop->p_attn, drop->p_fc};
+        for (float pr : ps)
+            if (!(pr >= 0.f && pr < 1.f)) return fail(AFR_EINVAL, "%s: dropout rate %g outside [0, 1)", what, (double)pr);
+    }
+    return AFR_OK;
+}
+static SheetParams sheet_op_params(const afr_sheet_params* P) {
+    SheetParams sp;
+    sp.pos = P->pos; sp.emb = P->emb; sp.w_in = P->w_in; sp.b_in = P->b_in; sp.w_o = P->w_o; sp.b_o = P->b_o;
+    sp.ln_g = P->ln_g; sp.ln_b = P->ln_b; sp.w1 = P->w1; sp.b1 = P->b1;
+    return sp;
+}
+static SheetDrop sheet_op_drop(const afr_sheet_dropout* drop, float* save) {
+    if (!drop) return sheet_drop(0, 0, 0, 0.f, 0.f, 0.f, 0, save);
+    return sheet_drop(drop->seed, drop->step, drop->rank, drop->p_embed, drop->p_attn, drop->p_fc, 1, save);
+}
+extern "C" size_t afr_sheet_save_floats(int B, int L) {
+    return B > 0 && L > 0 ? (size_t)B * (size_t)L * AFR_SHEET_SAVE_PER_POS : 0;
+}
+extern "C" int afr_op_sheet_fwd(int act_dtype, const afr_sheet_params* params, const int64_t* x, int ldx, int B, int L, int max_length, int vocab,
+                                float ln_eps, const afr_sheet_dropout* drop, void* z, float* save, uint32_t* err, void* stream) {
+    if (int rc = sheet_op_args("afr_op_sheet_fwd", act_dtype, params, x, ldx, B, L, max_length, vocab, drop)) return rc;
+    if (!z) return fail(AFR_EINVAL, "afr_op_sheet_fwd: null argument");
+    DevGuard dg(device_of(z));
+    SheetDims d{L, max_length, 32, 4, 64, vocab};
+    HIPCHK(afr_launch_sheet_fwd(act_dtype, d, sheet_op_params(params), sheet_op_drop(drop, save), x, ldx, B, z, ln_eps, err, (hipStream_t)stream));
+    return AFR_OK;
+}
+extern "C" int afr_op_sheet_bwd(int act_dtype, const afr_sheet_params* params, const int64_t* x, int ldx, int B, int L, int max_length, int vocab,
+                                float ln_eps, const afr_sheet_dropout* drop, const void* dz, const float* save, float* slabs,
+                                const afr_sheet_slab_layout* lay, void* stream) {
+    const char* what = "afr_op_sheet_bwd";
+    if (int rc = sheet_op_args(what, act_dtype, params, x, ldx, B, L, max_length, vocab, drop)) return rc;
+    if (!dz || !slabs || !lay) return fail(AFR_EINVAL, "%s: null argument", what);
+    if (lay->total < 4 || (lay->total & 3)) return fail(AFR_EINVAL, "%s: total = %d must be a positive multiple of 4 (a block zeroes its slab 16 bytes at a time)", what, lay->total);
+    if ((uintptr_t)slabs & 15) return fail(AFR_EINVAL, "%s: slabs must be 16-byte aligned", what);
+    // the ten tensor ranges lie inside a slab and do not overlap
+    const long long off[10] = {lay->pos, lay->emb, lay->w_in, lay->b_in, lay->w_o, lay->b_o, lay->ln_g, lay->ln_b, lay->w1, lay->b1};
+    const long long len[10] = {(long long)max_length * 32, (long long)vocab * 32, 96 * 32, 96, 32 * 32, 32, 32, 32, 64 * 32, 64};
+    for (int i = 0; i < 10; ++i) {
+        if (off[i] < 0 || off[i] + len[i] > lay->total) return fail(AFR_EINVAL, "%s: tensor %d (offset %lld, %lld floats) lies outside total = %d", what, i, off[i], len[i], lay->total);
+        for (int j = 0; j < i; ++j)
+            if (off[i] < off[j] + len[j] && off[j] < off[i] + len[i]) return fail(AFR_EINVAL, "%s: tensors %d and %d overlap", what, j, i);
+    }
+    DevGuard dg(device_of(slabs));
+    SheetDims d{L, max_length, 32, 4, 64, vocab};
+    SheetSlabOff so{lay->pos, lay->emb, lay->w_in, lay->b_in, lay->w_o, lay->b_o, lay->ln_g, lay->ln_b, lay->w1, lay->b1, lay->total};
+    HIPCHK(afr_launch_sheet_bwd(act_dtype, d, sheet_op_params(params), sheet_op_drop(drop, const_cast<float*>(save)), x, ldx, B, dz, ln_eps, slabs, so,
+                                (hipStream_t)stream));
     return AFR_OK;
 }

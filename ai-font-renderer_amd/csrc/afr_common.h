@@ -401,7 +401,7 @@ struct SheetDrop {
 };
 // offsets (in floats) of the 10 small tensors inside one partial-gradient slab == their flat-buffer offsets
 struct SheetSlabOff { int pos, emb, win, bin, wo, bo, g, b, w1, b1, total; };
-int afr_sheet_blocks(int B);
+extern "C" int afr_sheet_blocks(int B);   // (also exported, include/afr.h: a caller of the afr_op_sheet_* entries sizes its slabs with it)
 size_t afr_sheet_fwd_lds_bytes(const SheetDims& d);
 size_t afr_sheet_bwd_lds_bytes(const SheetDims& d);
 hipError_t afr_launch_sheet_fwd(int act_dtype, const SheetDims& d, const SheetParams& P, const SheetDrop& dr,

@@ -162,9 +162,14 @@ def make_params(cfg, seed=SEED):
 def sheet_dropout_masks(cfg, B, L, seed, step, rank=0):
     """The three keep masks (uint8 0/1) exactly as the HIP kernels derive them."""
     E, H, F = cfg.embed_dim, cfg.heads, cfg.fc_dim
-    me = dropout_keep_mask(dropout_key(seed, step, STREAM_EMBED, rank), B * L * E, 1.0 - cfg.p_embed)
-    ma = dropout_keep_mask(dropout_key(seed, step, STREAM_ATTN, rank), B * H * L * L, 1.0 - cfg.p_attn)
-    mf = dropout_keep_mask(dropout_key(seed, step, STREAM_FC, rank), B * L * F, 1.0 - cfg.p_fc)
+
+    def keep(p):
+        # the keep probability as the kernels form it, in float32 from the float32 rate (afr_api.hip sheet_drop): for p = 0.2 that is
+        # 13421773 / 2^24, one threshold step above the double 0.8 -- the element whose hash is 13421772 is KEPT
+        return float(np.float32(1.0) - np.float32(p))
+    me = dropout_keep_mask(dropout_key(seed, step, STREAM_EMBED, rank), B * L * E, keep(cfg.p_embed))
+    ma = dropout_keep_mask(dropout_key(seed, step, STREAM_ATTN, rank), B * H * L * L, keep(cfg.p_attn))
+    mf = dropout_keep_mask(dropout_key(seed, step, STREAM_FC, rank), B * L * F, keep(cfg.p_fc))
     return dict(embed=me.reshape(B, L, E).astype(np.uint8), attn=ma.reshape(B, H, L, L).astype(np.uint8),
                 fc=mf.reshape(B, L, F).astype(np.uint8))
 

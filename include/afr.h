@@ -438,6 +438,42 @@ int afr_op_pixel_head_bwd(int act_dtype, const float* du, const float* hf, const
 int afr_op_pixel_ln_bwd(int act_dtype, const void* dy, const float* hin, const float* g, float* dh, void* dhT /* or NULL */,
                         float* part, int64_t rows, int d, float eps, void* stream);
 
+/* ---- the sheet model's front end (AFR_KIND_SHEET), its two fused kernels one launch each, exactly as the plan issues them.
+ * One 1024-thread block owns a string at a time and loops over the batch (afr_sheet_blocks(B) blocks).  The widths are the
+ * reference's: embed_dim 32, 4 heads of 8, fc1 width 64.  act_dtype AFR_F32 or AFR_BF16 is the type T of z and dz (anything else
+ * is AFR_EINVAL); parameters, the save area and the slabs are float32.  Pointers not marked "or NULL" are required.
+ *   params     the ten small tensors in state_dict order: positional_encoding [max_length][32], embedding.weight [vocab][32],
+ *              in_proj_weight [96][32], in_proj_bias [96], out_proj.weight [32][32], out_proj.bias [32], layer_norm.weight [32],
+ *              layer_norm.bias [32], fc1.weight [64][32], fc1.bias [64].
+ *   x, ldx     int64 codes [B][ldx]; the first L of every row are read (ldx >= L).  A code outside 0 .. vocab-1 sets bit 0 of
+ *              *err (device word, or NULL) and is clamped into the table.
+ *   drop       NULL: eval (no dropout).  Otherwise a training pass: the three keep masks come from the counter hash of
+ *              (seed, step, rank), exactly as a plan with these afr_config fields derives them; every rate is in [0, 1).
+ *   z          T [B][max_length*64]: fc1 + ReLU + dropout of the first L positions, then exact zeros.
+ *   save       or NULL.  float32 [B][L*56] (afr_sheet_save_floats(B, L) floats; 56 = 32 + 4 + 4 + 16 per position): per string the attention
+ *              output o [L][32], the softmax row maxima [4][L], 1/row-sum [4][L] and, in training only, the attention-dropout
+ *              keep bits as uint32 [4][L][4]: row (h, i), key j is bit (j>>1)&31 of word (j&1)*2 + (j>>6).  The forward writes
+ *              it; the backward reads it, or with save == NULL recomputes the attention from the same dropout stream.
+ *   dz         T [B][max_length*64]: the gradient with respect to z (the part beyond L*64 is not read).
+ *   slabs      float32 [afr_sheet_blocks(B)][layout->total], 16-byte aligned: every block writes its whole slab -- its partial
+ *              gradient of each tensor at the tensor's offset, zeros everywhere else (rows of the positional gradient at or beyond
+ *              L, embedding rows of codes it did not meet, the space between tensors) -- so no slab needs clearing and the sum of
+ *              the slabs (afr_op_reduce) is the gradient.  layout: the ten offsets in floats (tensor order as in params) and
+ *              total, a multiple of 4; the ranges lie inside total and do not overlap.
+ * Refused with a message: B < 1, L < 1, L > max_length, ldx < L, vocab < 1, a rate outside [0, 1) (AFR_EINVAL); L > 120
+ * (AFR_EUNSUPPORTED: a string's state must fit one compute unit's LDS). */
+typedef struct afr_sheet_params { const float *pos, *emb, *w_in, *b_in, *w_o, *b_o, *ln_g, *ln_b, *w1, *b1; } afr_sheet_params;
+typedef struct afr_sheet_dropout { uint64_t seed, step; int32_t rank; float p_embed, p_attn, p_fc; } afr_sheet_dropout;
+typedef struct afr_sheet_slab_layout { int32_t pos, emb, w_in, b_in, w_o, b_o, ln_g, ln_b, w1, b1, total; } afr_sheet_slab_layout;
+int afr_sheet_blocks(int B);                  /* host-only: blocks (= partial slabs) of both kernels for a batch of B strings */
+size_t afr_sheet_save_floats(int B, int L);   /* host-only: floats of the save area */
+int afr_op_sheet_fwd(int act_dtype, const afr_sheet_params* params, const int64_t* x, int ldx, int B, int L, int max_length, int vocab,
+                     float ln_eps, const afr_sheet_dropout* drop /* or NULL */, void* z, float* save /* or NULL */,
+                     uint32_t* err /* or NULL */, void* stream);
+int afr_op_sheet_bwd(int act_dtype, const afr_sheet_params* params, const int64_t* x, int ldx, int B, int L, int max_length, int vocab,
+                     float ln_eps, const afr_sheet_dropout* drop /* or NULL */, const void* dz, const float* save /* or NULL */,
+                     float* slabs, const afr_sheet_slab_layout* layout, void* stream);
+
 /* ---- fp8 building blocks of BASELINE configs[4] ("fp8 MFMA weights on CDNA4"; no counterpart in the reference) ----
  * Operands are OCP e4m3fn bytes (gfx950's native fp8: exponent bias 7, largest finite 448, no infinities) with ONE float
  * scale per tensor: value = scale * e4m3.  afr_op_f32_to_fp8: dst[i] = e4m3(src[i] / scale), round to nearest even,

@@ -64,6 +64,48 @@ def test_bad_configs_are_rejected_with_a_message():
     assert lib.afr_plan_create(C.byref(c), C.byref(plan)) < 0
     with pytest.raises(_lib.AfrError):
         _lib.check(lib.afr_plan_create(C.byref(c), C.byref(plan)))
+    # the sheet front end's one-launch entries refuse what their kernels cannot take, before anything is launched
+    EI, EU = _lib.AFR_EINVAL, _lib.AFR_EUNSUPPORTED
+    fk = C.c_void_p(0x1000)
+    prm = _lib.AfrSheetParams(*[0x1000] * 10)
+    lay = _lib.AfrSheetSlabLayout(0, 3840, 7936, 11008, 11136, 12160, 12224, 12288, 12352, 14400, 14464)   # max_length 120, vocab 128
+
+    def fwd(dt=0, ldx=24, B=4, L=24, ML=120, vocab=128, drop=None, z=fk, p=prm):
+        return lib.afr_op_sheet_fwd(dt, C.byref(p) if p is not None else None, fk, ldx, B, L, ML, vocab, 1e-5, drop, z, None, None, None)
+
+    def bwd(dt=0, ldx=24, B=4, L=24, ML=120, vocab=128, drop=None, dz=fk, slabs=fk, la=lay):
+        return lib.afr_op_sheet_bwd(dt, C.byref(prm), fk, ldx, B, L, ML, vocab, 1e-5, drop, dz, None, slabs, C.byref(la) if la is not None else None, None)
+
+    assert lib.afr_sheet_blocks(1) == 1 and lib.afr_sheet_blocks(256) == 256 and lib.afr_sheet_blocks(600) == 256
+    assert lib.afr_sheet_save_floats(3, 17) == 3 * 17 * 56
+    for call in (fwd, bwd):
+        assert call(dt=2) == EI and b"act_dtype" in lib.afr_last_error()                 # AFR_BF16X3 is a plan mode, not an activation type
+        assert call(L=0) == EI and b"L = 0" in lib.afr_last_error()
+        assert call(L=121, ML=200, ldx=121) == EU and b"120" in lib.afr_last_error()
+        assert call(L=30, ML=24, ldx=30) == EI and b"max_length" in lib.afr_last_error()
+        assert call(ldx=23) == EI and b"ldx" in lib.afr_last_error()
+        assert call(B=0) == EI and b"B = 0" in lib.afr_last_error()
+        assert call(vocab=0) == EI
+        for rates in ((1.0, 0.0, 0.0), (0.0, -0.1, 0.0), (0.0, 0.0, float("nan"))):
+            d = _lib.AfrSheetDropout(42, 1, 0, *rates)
+            assert call(drop=C.byref(d)) == EI and b"outside [0, 1)" in lib.afr_last_error()
+    assert fwd(z=None) == EI and fwd(p=None) == EI
+    assert fwd(p=_lib.AfrSheetParams(*([0x1000] * 9 + [None]))) == EI and b"parameter" in lib.afr_last_error()
+    assert bwd(dz=None) == EI and bwd(slabs=None) == EI and bwd(la=None) == EI
+    assert bwd(slabs=C.c_void_p(0x1008)) == EI and b"16-byte" in lib.afr_last_error()
+    bad = _lib.AfrSheetSlabLayout.from_buffer_copy(lay)
+    bad.total = 14466
+    assert bwd(la=bad) == EI and b"multiple of 4" in lib.afr_last_error()
+    bad = _lib.AfrSheetSlabLayout.from_buffer_copy(lay)
+    bad.total = 14460                                                                  # fc1.bias ends at 14464
+    assert bwd(la=bad) == EI and b"outside" in lib.afr_last_error()
+    bad = _lib.AfrSheetSlabLayout.from_buffer_copy(lay)
+    bad.emb = 3836                                                                     # the embedding rows start inside pos
+    assert bwd(la=bad) == EI and b"overlap" in lib.afr_last_error()
+    bad = _lib.AfrSheetSlabLayout.from_buffer_copy(lay)
+    bad.b1 = -64
+    assert bwd(la=bad) == EI
+    assert bwd(vocab=129) == EI and b"overlap" in lib.afr_last_error()                 # the layout was made for 128 rows
 
 
 def test_operands_of_2gib_or_more_are_rejected_not_silently_zero_filled():

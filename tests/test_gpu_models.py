@@ -160,16 +160,17 @@ def test_r0_train_step_grads_match_reference():
 
 
 # ----------------------------------------------------------------------------- sheet model vs oracle (seeded)
-@pytest.mark.parametrize("dtype,tol", [("f32", 1e-4), ("bf16", 3e-2)])
-def test_sheet_train_step_vs_oracle_ragged_batch_dropout(dtype, tol):
-    """B=37 strings of a 24-char model (neither a tile multiple), dropout on, uint8 targets."""
+@pytest.mark.parametrize("dtype,tol,B", [pytest.param("f32", 1e-4, 37, id="f32-0.0001"), pytest.param("bf16", 3e-2, 37, id="bf16-0.03"),
+                                         pytest.param("f32", 1e-4, 600, id="f32-0.0001-B600"), pytest.param("bf16", 3e-2, 600, id="bf16-0.03-B600")])
+def test_sheet_train_step_vs_oracle_ragged_batch_dropout(dtype, tol, B):
+    """B=37 strings of a 24-char model (neither a tile multiple), dropout on, uint8 targets; B=600: the front end's persistent blocks
+    make a second and a third trip (2.34 strings per block), the only whole-model oracle comparison past one trip."""
     from .util import SheetConfig
     cfg = SheetConfig(max_length=24, sheet_h=16, sheet_w=40)
-    B = 37
     strings = synth.dataset_strings(B)
     x = synth.encode_strings(strings, 24)
     tu8 = synth.synth_sheet_targets(B, 16, 40, tensor_id=930)
-    eng = _engine(cfg, dtype=dtype, max_batch=64, seed=5)
+    eng = _engine(cfg, dtype=dtype, max_batch=max(64, B), seed=5)
     eng.train_step(torch.from_numpy(x), torch.from_numpy(tu8), step=11, do_step=False)
     loss = eng.read_loss()
     P = tparams(cfg)
