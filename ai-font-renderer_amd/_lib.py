@@ -109,6 +109,8 @@ SIGNATURES = {
     "afr_loss_grad_rows": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp]),
     "afr_forward_loss_rows": (_i32, [_vp, _vp, _i32, _i64, _vp, _u64, _vp]),
     "afr_train_step_rows": (_i32, [_vp, _vp, _i32, _i64, _vp, _u64, _i32, _f32, _f32, _f32, _f32, _f32, _i64, _vp]),
+    "afr_eval": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "afr_eval_rows": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "afr_error_flags": (_i32, [_vp, _vp, C.POINTER(C.c_uint32)]),
     "afr_profile_dominant": (_i32, [_vp, _i32]),
     "afr_profile_read": (_i32, [_vp, C.c_char_p, _i32, C.POINTER(C.c_double), C.POINTER(_i64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -129,6 +131,7 @@ SIGNATURES = {
                                  _vp, _f32, _vp]),
     "afr_op_mse_grad": (_i32, [_i32, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "afr_op_bce_grad": (_i32, [_i32, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "afr_op_eval": (_i32, [_i32, _i32, _vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "afr_op_f32_to_bf16": (_i32, [_vp, _vp, _i64, _vp]),
     "afr_op_f32_to_fp8": (_i32, [_vp, _vp, _i64, _f32, _vp]),
     "afr_op_gemm_fp8": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),

@@ -132,6 +132,7 @@ struct afr_plan {
     int last_B = 0, last_L = 0, last_ldx = 0, last_training = 0;
     uint64_t last_step = 0;
     bool have_du = false;
+    bool have_u = false;          // the u buffer holds the pre-activation of the last forward (afr_eval*): not yet overwritten by du
     int next_stage = 0;
     // the bound data set (afr_bind_dataset; caller-owned device buffers) and the workspace staging of the afr_*_rows calls: the
     // narrowed row indices the loss kernels' row maps read, and the batch's codes / font ids for the id consumers
@@ -471,7 +472,7 @@ extern "C" int afr_bind(afr_plan* p, float* params, float* grads, float* m, floa
     p->device = dev;
     p->P = params; p->G = grads; p->M = m; p->V = v;
     p->ws = (char*)ws; p->ws_bytes = ws_bytes;
-    p->have_du = false;
+    p->have_du = false; p->have_u = false;
     p->wT_valid = false;
     p->shadow_cur = 0; p->step_on = false; p->adam_done.clear();
     for (auto& l : p->layers) {                          // cooperative split-K: arrival counters and their host count start at zero
@@ -898,7 +899,7 @@ extern "C" int afr_use_ema(afr_plan* p, int on, void* stream) {
     if (!p->P || !p->ws) return fail(AFR_ESTATE, "plan has no bound parameters");
     std::swap(p->P, p->E);
     p->ema_on = on != 0;
-    p->have_du = false; p->next_stage = 0;      // a saved forward belongs to the weights it ran with
+    p->have_du = false; p->have_u = false; p->next_stage = 0;      // a saved forward belongs to the weights it ran with
     return afr_sync_params(p, stream);          // the bf16 shadow and the transposed copies follow p->P
 }
 extern "C" int afr_op_ema(float* e, const float* p, int64_t n, float decay, const float* sumsq_dev, void* stream) {
@@ -1065,7 +1066,7 @@ static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int 
         }
         p->last_x = x; p->last_font = font; p->last_B = B; p->last_L = 1; p->last_training = training; p->last_step = step;
         p->next_stage = 0; p->combo_on = false; p->mbits_on = false;
-        p->have_du = false;
+        p->have_du = false; p->have_u = fl == nullptr;
         if (fl) {        // the loss on the f32 pre-clamp output (model.py:156,268-270): du in place over u
             ProfScope ps(p, s, fl->kind == AFR_LOSS_BCE ? "bce_grad" : "mse_grad", 0.0, (double)rows * 9.0);
             HIPCHK(afr_launch_mse_grad(AFR_F32, u, u, B, Pix, loss_slots(*fl, (float*)(p->ws + p->o_loss), false), s));
@@ -1126,6 +1127,7 @@ static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int 
     p->combo_on = c.kind == AFR_KIND_GLYPH && fl != nullptr && p->k0 && combo_for(p, B);
     p->mbits_on = c.kind == AFR_KIND_GLYPH && fl != nullptr && c.dtype == AFR_BF16;
     p->have_du = fl != nullptr;      // with the loss fused into the last layer's epilogue the buffer already holds du
+    p->have_u = fl == nullptr;
     return AFR_OK;
 }
 extern "C" int afr_forward(afr_plan* p, const int64_t* x, const int64_t* font, int B, int L, float* y, int training,
@@ -1153,12 +1155,41 @@ static int loss_grad_impl(afr_plan* p, const void* target, int tdtype, const int
     ProfScope ps(p, s, p->cfg.loss == AFR_LOSS_BCE ? "bce_grad" : "mse_grad", 0.0, (double)B * Pix * (2.0 * p->act_bytes + tb));
     HIPCHK(afr_launch_mse_grad(p->cfg.kind == AFR_KIND_PIXEL ? AFR_F32 : p->cfg.dtype, u, u, B, Pix,      // (the pixel transformer's pre-clamp output is f32 in both modes)
                                loss_args(p, false, target, tdtype, rowmap, mean_elems, loss_accum), s));
-    p->have_du = true;
+    p->have_du = true; p->have_u = false;
     return AFR_OK;
 }
 extern "C" int afr_loss_grad(afr_plan* p, const void* target, int tdtype, int B, int64_t mean_elems, float* loss_accum,
                              void* stream) {
     return loss_grad_impl(p, target, tdtype, nullptr, B, mean_elems, loss_accum, stream);
+}
+
+// ---------------------------------------------------------------------------------- evaluation
+// afr_eval / afr_eval_rows: ONE launch of eval_rows_kernel over the u the last forward saved; u is only read.
+static int eval_impl(afr_plan* p, const void* target, int tdtype, const int* rowmap, int B, float* loss_rows, uint32_t* stats, uint8_t* q,
+                     void* stream) {
+    if (!p || !p->P || !p->ws) return fail(AFR_ESTATE, "plan has no bound parameters");
+    if (!loss_rows && !stats && !q) return fail(AFR_EINVAL, "afr_eval: loss_rows, stats and q are all NULL");
+    if (!target && (loss_rows || stats)) return fail(AFR_EINVAL, "afr_eval: loss_rows and stats need a target");
+    if (target && tdtype != AFR_TARGET_U8 && tdtype != AFR_TARGET_F32) return fail(AFR_EINVAL, "bad target dtype");
+    if (B <= 0 || B > p->cfg.max_batch) return fail(AFR_EINVAL, "batch %d outside 1..max_batch=%d", B, p->cfg.max_batch);
+    if (((uintptr_t)stats & 15) || ((uintptr_t)q & 7) || ((uintptr_t)loss_rows & 3) || ((uintptr_t)target & (tdtype == AFR_TARGET_U8 ? 7 : 15)))
+        return fail(AFR_EINVAL, "afr_eval: stats must be 16-byte aligned, q 8-byte, uint8 targets 8-byte, float32 targets 16-byte");
+    if (p->last_B <= 0) return fail(AFR_ESTATE, "afr_eval needs afr_forward first");
+    if (B != p->last_B) return fail(AFR_ESTATE, "afr_eval batch %d does not match the last forward (%d)", B, p->last_B);
+    if (!p->have_u) return fail(AFR_ESTATE, "afr_eval: the output buffer no longer holds u (a loss has written du over it); run afr_forward again");
+    DevGuard dg(p->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int Pix = p->cfg.out_h * p->cfg.out_w;
+    const int ad = p->cfg.kind == AFR_KIND_PIXEL ? AFR_F32 : p->cfg.dtype;       // (the pixel transformer's pre-clamp output is f32 in both modes)
+    const bool need_t = loss_rows || stats;
+    const double bytes = (double)B * Pix * ((ad == AFR_BF16 ? 2.0 : 4.0) + (need_t ? (tdtype == AFR_TARGET_U8 ? 1.0 : 4.0) : 0.0) + (q ? 1.0 : 0.0)) +
+                         (double)B * ((loss_rows ? 4.0 : 0.0) + (stats ? 16.0 : 0.0) + (need_t && rowmap ? 4.0 : 0.0));
+    ProfScope ps(p, s, "eval_rows", 0.0, bytes);
+    HIPCHK(afr_launch_eval_rows(ad, p->cfg.loss, p->ws + p->o_u, target, tdtype, target ? rowmap : nullptr, B, Pix, loss_rows, stats, q, s));
+    return AFR_OK;
+}
+extern "C" int afr_eval(afr_plan* p, const void* target, int tdtype, int B, float* loss_rows, uint32_t* stats, uint8_t* q, void* stream) {
+    return eval_impl(p, target, tdtype, nullptr, B, loss_rows, stats, q, stream);
 }
 
 extern "C" int afr_set_output_grad(afr_plan* p, const float* dy, int B, void* stream) {
@@ -1168,7 +1199,7 @@ extern "C" int afr_set_output_grad(afr_plan* p, const float* dy, int B, void* st
     if (B != p->last_B) return fail(AFR_ESTATE, "batch %d does not match the last forward (%d)", B, p->last_B);
     HIPCHK(afr_launch_clamp_bwd(p->cfg.kind == AFR_KIND_PIXEL ? AFR_F32 : p->cfg.dtype, p->ws + p->o_u, dy, (long long)B * p->cfg.out_h * p->cfg.out_w, (hipStream_t)stream,
                                 p->cfg.loss));
-    p->have_du = true;
+    p->have_du = true; p->have_u = false;
     return AFR_OK;
 }
 
@@ -1687,7 +1718,7 @@ static int glyph1_fused(afr_plan* p, const int64_t* x, const int64_t* font, cons
         }
     }
     p->last_x = x; p->last_font = font; p->last_B = B; p->last_L = 1; p->last_training = 1;
-    p->have_du = false; p->next_stage = 0;
+    p->have_du = false; p->have_u = false; p->next_stage = 0;
     return AFR_OK;
 }
 
@@ -1801,6 +1832,12 @@ extern "C" int afr_loss_grad_rows(afr_plan* p, const int64_t* rows, int B, int64
     int Lc, rc;      // (the row indices alone: the staged codes of the forward stay as they are for the backward)
     if ((rc = rows_begin(p, rows, B, false, stream, &Lc))) return rc;
     return loss_grad_impl(p, p->ds_target, p->ds_tdtype, (const int*)(p->ws + p->o_ridx), B, mean_elems, loss_accum, stream);
+}
+extern "C" int afr_eval_rows(afr_plan* p, const int64_t* rows, int B, float* loss_rows, uint32_t* stats, uint8_t* q, void* stream) {
+    int Lc, rc;      // (the row indices alone, as afr_loss_grad_rows: the kernel reads the targets where they lie)
+    if (!loss_rows && !stats && !q) return fail(AFR_EINVAL, "afr_eval_rows: loss_rows, stats and q are all NULL");
+    if ((rc = rows_begin(p, rows, B, false, stream, &Lc))) return rc;
+    return eval_impl(p, p->ds_target, p->ds_tdtype, (const int*)(p->ws + p->o_ridx), B, loss_rows, stats, q, stream);
 }
 extern "C" int afr_forward_loss_rows(afr_plan* p, const int64_t* rows, int B, int64_t mean_elems, float* loss_accum, uint64_t step,
                                      void* stream) {
@@ -2024,6 +2061,23 @@ extern "C" int afr_op_bce_grad(int act_dtype, const void* u, const void* target,
     if (!u || !target || !du || !loss_accum || !scratch) return fail(AFR_EINVAL, "null argument");
     DevGuard dg(device_of(du));
     HIPCHK(afr_launch_mse_grad(act_dtype, u, du, rows, cols, loss_args(scratch, false, AFR_LOSS_BCE, target, tdtype, nullptr, mean_elems, loss_accum), (hipStream_t)stream));
+    return AFR_OK;
+}
+extern "C" int afr_op_eval(int act_dtype, int loss_kind, const void* u, const void* target, int tdtype, const int32_t* rowmap, int64_t rows,
+                           int64_t cols, float* loss_rows, uint32_t* stats, uint8_t* q, void* stream) {
+    if (!u) return fail(AFR_EINVAL, "afr_op_eval: u is null");
+    if (act_dtype != AFR_F32 && act_dtype != AFR_BF16) return fail(AFR_EINVAL, "afr_op_eval: act_dtype must be AFR_F32 or AFR_BF16");
+    if (loss_kind != AFR_LOSS_MSE && loss_kind != AFR_LOSS_BCE) return fail(AFR_EINVAL, "afr_op_eval: loss_kind must be AFR_LOSS_MSE (0) or AFR_LOSS_BCE (1), got %d", loss_kind);
+    if (!loss_rows && !stats && !q) return fail(AFR_EINVAL, "afr_op_eval: loss_rows, stats and q are all NULL");
+    if (!target && (loss_rows || stats)) return fail(AFR_EINVAL, "afr_op_eval: loss_rows and stats need a target");
+    if (target && tdtype != AFR_TARGET_U8 && tdtype != AFR_TARGET_F32) return fail(AFR_EINVAL, "bad target dtype");
+    if (rows <= 0 || cols <= 0) return fail(AFR_EINVAL, "afr_op_eval: rows and cols must be positive");
+    if (cols % 8) return fail(AFR_EUNSUPPORTED, "afr_op_eval: cols must be a multiple of 8 (got %lld)", (long long)cols);
+    if (((uintptr_t)u & 15) || ((uintptr_t)stats & 15) || ((uintptr_t)q & 7) || ((uintptr_t)loss_rows & 3) || ((uintptr_t)rowmap & 3) ||
+        ((uintptr_t)target & (tdtype == AFR_TARGET_U8 ? 7 : 15)))
+        return fail(AFR_EINVAL, "afr_op_eval: u, stats and float32 targets must be 16-byte aligned, q and uint8 targets 8-byte");
+    DevGuard dg(device_of(u));
+    HIPCHK(afr_launch_eval_rows(act_dtype, loss_kind, u, target, tdtype, target ? rowmap : nullptr, rows, cols, loss_rows, stats, q, (hipStream_t)stream));
     return AFR_OK;
 }
 extern "C" int afr_op_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream) {

@@ -346,6 +346,12 @@ hipError_t afr_launch_grad_sumsq(const float* g, const SumsqSeg* segs /* device 
 int afr_mse_blocks(long long rows, long long cols);
 // l.partial: >= afr_mse_blocks floats
 hipError_t afr_launch_mse_grad(int act_dtype, const void* u, void* du, long long rows, long long cols, const LossArgs& l, hipStream_t s);
+// evaluation of saved pre-activations (elementwise.hip eval_rows_kernel): per-row loss, 8-bit error counts against the targets, u8 levels.
+// target NULL: q only.  cols % 8 == 0; a row belongs to one wave or one workgroup, the grid is capped and loops over the rows.
+constexpr int AFR_EVAL_MAX_BLOCKS = 2048;
+int afr_eval_blocks(long long rows, long long cols);
+hipError_t afr_launch_eval_rows(int act_dtype, int loss_kind, const void* u, const void* target, int tdtype, const int* rowmap, long long rows,
+                                long long cols, float* loss_rows, uint32_t* stats, uint8_t* q, hipStream_t s);
 // Batch rows of a resident data set (afr_*_rows): validates and clamps rows[b] (AFR_ERR_ROW), writes ridx[b] = the narrowed index
 // the loss kernels' row maps read and, when sx is not NULL, stages x[rows[b]][0 .. Lc) into sx [B][Lc] and font[rows[b]] into sfont.
 hipError_t afr_launch_dataset_rows(const int64_t* rows, int B, long long n_rows, const int64_t* x, const int64_t* font, int L, int Lc,

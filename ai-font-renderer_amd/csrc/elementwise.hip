@@ -600,6 +600,150 @@ hipError_t afr_launch_mse_grad(int act_dtype, const void* u, void* du, long long
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------ evaluation rows
+// One read-only pass over the saved pre-activation u [rows][cols] (afr_eval / afr_op_eval): per batch row b
+//   q[b][i]      = (uint8)(y * 255.0f), truncating (helpers.binary_array_to_image), y = the plan's head of u (clamp_out_kernel's
+//                  inlines: clamp(u,0,1), or sigmoid_f(u) for LOSS_BCE); a NaN u gives level 0
+//   loss_rows[b] = (sum_i term(u, t)) / cols, term = what loss_elem<LOSS> returns (called with inv_n = g2 = 0, du dropped), t as the
+//                  loss kernels form it (k / 255.0f, or the float target); a NaN u makes its row's loss NaN
+//   stats[b][4]  = #(d >= 1), #(d >= 2), max d, #((q >= 128) != (t8 >= 128)) with d = |q - t8|, t8 = k or rintf(t * 255.f) in 0..255
+// mse_grad_kernel's loads (8 pixels per lane per group: u as 2 x 16 B or 16 B, targets as 8 B or 2 x 16 B, the ROWS target row
+// addressed with 64-bit arithmetic) and 8-byte stores of q.  Absent outputs: HAS_T false carries no target code, HAS_Q false no
+// store; loss_rows / stats alone are tested once per row.
+// A row is owned by ONE wave (BLOCK false: cols <= EVAL_WAVE_COLS, row = 4 * block + wave) or ONE 256-lane workgroup (BLOCK true);
+// rows beyond the grid are taken in a loop.  Nothing passes between workgroups: no tickets, no atomics.
+// SUMMATION ORDER of loss_rows[b] (f32, every addition rounded on its own, no contraction), L = 64 lanes (wave) or 256 (block):
+//   1. lane l starts at 0.f and adds the terms of its groups g = l, l + L, l + 2L, ... (< cols / 8) in ascending g, the 8 pixels of a
+//      group in ascending pixel order: a chain of 8 * ceil((cols/8 - l) / L) additions;
+//   2. wave_sum: 6 butterfly steps, v += shfl_xor(v, o) for o = 32, 16, 8, 4, 2, 1 (lanes without a group hold 0.f);
+//   3. BLOCK only: ((w0 + w1) + w2) + w3, the four waves in wave order;
+//   4. one division by (float)cols.
+// Longest chain of additions: D(cols) = 8 * ceil(cols / (8 L)) + 6 (+ 3 for BLOCK).  A row's results depend on the row's data alone.
+constexpr int EVAL_WAVE_COLS = 2048;      // up to here a wave owns a row (<= 4 groups per lane); beyond, a workgroup does
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+template <typename T, typename TT, bool ROWS, int LOSS, bool BLOCK, bool HAS_T, bool HAS_Q>
+__global__ __launch_bounds__(256) void eval_rows_kernel(const T* __restrict__ u, const TT* __restrict__ tgt, const int* __restrict__ rowmap,
+                                                        long long rows, int cols8, float* __restrict__ loss_rows,
+                                                        uint32_t* __restrict__ stats, uint8_t* __restrict__ q) {
+    constexpr int L = BLOCK ? 256 : 64;
+    const int lane = BLOCK ? (int)threadIdx.x : (int)(threadIdx.x & 63), wave = threadIdx.x >> 6;
+    __shared__ float wf[4];
+    __shared__ unsigned wu[4][4];
+    const float fcols = (float)(8 * cols8);
+    const long long rstep = BLOCK ? (long long)gridDim.x : 4ll * gridDim.x;
+    for (long long b = BLOCK ? (long long)blockIdx.x : 4ll * blockIdx.x + wave; b < rows; b += rstep) {
+        const size_t ub = (size_t)b * (size_t)cols8;                   // the row's first group of 8 pixels
+        size_t tb = ub;
+        if constexpr (HAS_T && ROWS) tb = (size_t)rowmap[b] * (size_t)cols8;
+        float lsum = 0.f;
+        unsigned c1 = 0, c2 = 0, mx = 0, c3 = 0;
+#pragma unroll 2
+        for (int g = lane; g < cols8; g += L) {
+            const size_t i = ub + g;
+            float uu[8];
+            if (sizeof(T) == 4) {
+                const float4 a = reinterpret_cast<const float4*>(u)[2 * i], c = reinterpret_cast<const float4*>(u)[2 * i + 1];
+                uu[0] = a.x; uu[1] = a.y; uu[2] = a.z; uu[3] = a.w; uu[4] = c.x; uu[5] = c.y; uu[6] = c.z; uu[7] = c.w;
+            } else {
+                const bf16x8 a = reinterpret_cast<const bf16x8*>(u)[i];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) uu[k] = (float)a[k];
+            }
+            float tt[8];
+            int t8[8];
+            if constexpr (HAS_T) {
+                const size_t ti = tb + g;
+                if (sizeof(TT) == 1) {
+                    const uint2 w = reinterpret_cast<const uint2*>(tgt)[ti];
+                    targets_u8x8<false>(w, nullptr, tt);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { t8[r] = (int)((w.x >> (8 * r)) & 0xFF); t8[4 + r] = (int)((w.y >> (8 * r)) & 0xFF); }
+                } else {
+                    const float4 a = reinterpret_cast<const float4*>(tgt)[2 * ti], c = reinterpret_cast<const float4*>(tgt)[2 * ti + 1];
+                    tt[0] = a.x; tt[1] = a.y; tt[2] = a.z; tt[3] = a.w; tt[4] = c.x; tt[5] = c.y; tt[6] = c.z; tt[7] = c.w;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) t8[k] = (int)fminf(fmaxf(rintf(tt[k] * 255.f), 0.f), 255.f);
+                }
+            }
+            unsigned qq[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                float v;
+                if constexpr (LOSS == LOSS_BCE) v = fmaxf(sigmoid_f(uu[k]) * 255.0f, 0.f);      // (fmaxf: a NaN becomes level 0)
+                else v = fminf(fmaxf(uu[k], 0.f), 1.f) * 255.0f;                               // (the clamp already drops a NaN)
+                qq[k] = (unsigned)v;
+                if constexpr (HAS_T) {
+                    float du;
+                    float term = loss_elem<LOSS>(uu[k], tt[k], 0.f, 0.f, du);
+                    if constexpr (LOSS == LOSS_MSE) term = uu[k] == uu[k] ? term : uu[k];       // the clamp hides a NaN: the row's loss must not
+                    lsum = add_rn(lsum, term);
+                    const int df = (int)qq[k] - t8[k];
+                    const unsigned d = (unsigned)(df < 0 ? -df : df);
+                    c1 += d >= 1u; c2 += d >= 2u; mx = max(mx, d);
+                    c3 += (qq[k] >= 128u) != (t8[k] >= 128);
+                }
+            }
+            if constexpr (HAS_Q) {
+                uint2 o;
+                o.x = qq[0] | (qq[1] << 8) | (qq[2] << 16) | (qq[3] << 24);
+                o.y = qq[4] | (qq[5] << 8) | (qq[6] << 16) | (qq[7] << 24);
+                reinterpret_cast<uint2*>(q)[i] = o;
+            }
+        }
+        if constexpr (HAS_T) {
+            lsum = wave_sum(lsum);
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                c1 += __shfl_xor(c1, o, 64); c2 += __shfl_xor(c2, o, 64); c3 += __shfl_xor(c3, o, 64);
+                mx = max(mx, (unsigned)__shfl_xor(mx, o, 64));
+            }
+            if constexpr (BLOCK) {
+                if ((threadIdx.x & 63) == 0) { wf[wave] = lsum; wu[wave][0] = c1; wu[wave][1] = c2; wu[wave][2] = mx; wu[wave][3] = c3; }
+                __syncthreads();
+                if (threadIdx.x == 0) {
+                    lsum = add_rn(add_rn(add_rn(wf[0], wf[1]), wf[2]), wf[3]);
+                    c1 = wu[0][0] + wu[1][0] + wu[2][0] + wu[3][0];
+                    c2 = wu[0][1] + wu[1][1] + wu[2][1] + wu[3][1];
+                    mx = max(max(wu[0][2], wu[1][2]), max(wu[2][2], wu[3][2]));
+                    c3 = wu[0][3] + wu[1][3] + wu[2][3] + wu[3][3];
+                }
+            }
+            if (lane == 0) {
+                if (loss_rows) loss_rows[b] = lsum / fcols;
+                if (stats) *reinterpret_cast<uint4*>(stats + 4 * b) = make_uint4(c1, c2, mx, c3);
+            }
+            if constexpr (BLOCK) __syncthreads();          // (wf / wu are free again before the block's next row)
+        }
+    }
+}
+int afr_eval_blocks(long long rows, long long cols) {
+    return cols <= EVAL_WAVE_COLS ? grid_for(rows, 4, AFR_EVAL_MAX_BLOCKS) : grid_for(rows, 1, AFR_EVAL_MAX_BLOCKS);
+}
+hipError_t afr_launch_eval_rows(int act_dtype, int loss_kind, const void* u, const void* target, int tdtype, const int* rowmap, long long rows,
+                                long long cols, float* loss_rows, uint32_t* stats, uint8_t* q, hipStream_t s) {
+    if (rows <= 0 || cols <= 0) return hipSuccess;
+    if ((cols & 7) || cols / 8 > 0x7fffffffll || (!target && (loss_rows || stats || rowmap)) || (!loss_rows && !stats && !q)) return hipErrorInvalidValue;
+    if (!loss_rows && !stats) target = nullptr;           // nothing needs the target: the launch that carries no target code
+    const dim3 g(afr_eval_blocks(rows, cols)), b(256);
+    const int cols8 = (int)(cols / 8);
+    auto launch = [&](auto ta, auto tt, auto tr, auto loss, auto blk, auto ht, auto hq) {
+        using T = typename decltype(ta)::type;
+        using TT = typename decltype(tt)::type;
+        hipLaunchKernelGGL((eval_rows_kernel<T, TT, tr(), loss(), blk(), ht(), hq()>), g, b, 0, s, (const T*)u, (const TT*)target, rowmap, rows, cols8,
+                           loss_rows, stats, q);
+    };
+    with_act(act_dtype == AFR_BF16, [&](auto ta) { with_loss(loss_kind, [&](auto loss) { with_bool(cols > EVAL_WAVE_COLS, [&](auto blk) {
+        if (!target) { launch(ta, TypeTag<uint8_t>{}, std::false_type{}, loss, blk, std::false_type{}, std::true_type{}); return; }
+        with_bool(tdtype == AFR_TARGET_U8, [&](auto u8) { with_bool(rowmap != nullptr, [&](auto tr) { with_bool(q != nullptr, [&](auto hq) {
+            launch(ta, TypeTag<std::conditional_t<u8(), uint8_t, float>>{}, tr, loss, blk, std::true_type{}, hq);
+        }); }); });
+    }); }); });
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------- batch rows of a resident data set
 // The prepare step of the afr_*_rows entry points: batch row b is data-set row rows[b].  An index outside [0, n_rows) sets
 // AFR_ERR_ROW and is clamped BEFORE anything is addressed with it (as glyph_embed_kernel does for code indices).  ridx[b] is

@@ -60,6 +60,22 @@ def make_afr_config(cfg, dtype, max_batch, seed=42, rank=0, flags=0, loss="mse")
     return c
 
 
+class EvalResult:
+    """What Engine.evaluate* returns, device tensors: loss_rows float32 [B] (per-sample mean loss), stats int64 [B, 4] (pixels off by
+    >= 1 level, by >= 2 levels, the largest level difference, wrong-ink pixels: include/afr.h afr_eval) -- both None without a target --
+    and u8 uint8 [B, H, W], the levels a BMP dump would hold, or None when not asked for."""
+    __slots__ = ("loss_rows", "stats", "u8")
+
+    def __init__(self, loss_rows, stats, u8):
+        self.loss_rows, self.stats, self.u8 = loss_rows, stats, u8
+
+    @staticmethod
+    def cat(parts):
+        def j(ts):
+            return None if ts[0] is None else torch.cat(ts)
+        return EvalResult(j([r.loss_rows for r in parts]), j([r.stats for r in parts]), j([r.u8 for r in parts]))
+
+
 class Engine:
     """One plan + its device buffers.  `params[name]` are views into the flat float32 buffer in
     state_dict order, so checkpoints interchange with the reference (helpers.py:76-105)."""
@@ -121,6 +137,7 @@ class Engine:
         self.pixels = cfg.pixels
         self.t = 0            # AdamW step counter (model.py:310)
         self._keep = None     # keeps the last inputs alive until backward has consumed them
+        self._last_B = 0      # batch rows of the last forward / forward_rows (evaluate_last)
         if self.ema_decay is not None:
             self.set_ema(self.ema_decay, self.ema_every)
         if lr_mult is not None or wd_mult is not None:
@@ -409,6 +426,7 @@ class Engine:
         y = torch.empty(B, self.pixels, dtype=torch.float32, device=self.device) if want_output else None
         self._call(self.lib.afr_forward, self._plan, _ptr(x), _ptr(font), B, L, _ptr(y), int(bool(training)), int(step))
         self._keep = (x, font)
+        self._last_B = B
         if y is None:
             return None
         h, w = (self.cfg.sheet_h, self.cfg.sheet_w) if isinstance(self.cfg, SheetConfig) else (self.cfg.out_h, self.cfg.out_w)     # glyph / pixel
@@ -425,10 +443,70 @@ class Engine:
         y = torch.empty(B, self.pixels, dtype=torch.float32, device=self.device) if want_output else None
         self._call(self.lib.afr_forward_rows, self._plan, _ptr(rows), B, _ptr(y), int(bool(training)), int(step))
         self._keep = (rows, None)
+        self._last_B = B
         if y is None:
             return None
         h, w = (self.cfg.sheet_h, self.cfg.sheet_w) if isinstance(self.cfg, SheetConfig) else (self.cfg.out_h, self.cfg.out_w)
         return y.view(B, h, w)
+
+    # ---------------------------------------------------------------- evaluation on the device
+    def _hw(self):
+        return (self.cfg.sheet_h, self.cfg.sheet_w) if isinstance(self.cfg, SheetConfig) else (self.cfg.out_h, self.cfg.out_w)
+
+    def evaluate_last(self, target=None, rows=None, want_u8=False):
+        """The evaluation kernel alone (afr_eval / afr_eval_rows: one launch, nothing allocated by the library) on the pre-activation
+        the last forward / forward_rows left in the workspace; the buffer is only read, so loss_grad* / set_output_grad / backward may
+        follow as if nothing had happened.  target: uint8 or float32 [B, pixels] / [B, H, W]; or rows: the data-set rows of the
+        forward_rows before it; neither: the bitmaps alone (want_u8 is then implied).  Returns an EvalResult."""
+        if target is not None and rows is not None:
+            raise ValueError("evaluate_last takes a target or rows, not both")
+        with torch.cuda.device(self.device):
+            if rows is not None:
+                rows = self._rows(rows)
+                B = rows.shape[0]
+            elif target is not None:
+                t, td = self._target(target)
+                B = t.shape[0]
+            else:
+                B, want_u8 = self._last_B, True
+            need_t = rows is not None or target is not None
+            loss_rows = torch.empty(B, dtype=torch.float32, device=self.device) if need_t else None
+            stats = torch.empty(B, 4, dtype=torch.int32, device=self.device) if need_t else None      # the library's uint32 words (<= pixels)
+            q = torch.empty(B, self.pixels, dtype=torch.uint8, device=self.device) if want_u8 else None
+        if rows is not None:
+            self._call(self.lib.afr_eval_rows, self._plan, _ptr(rows), B, _ptr(loss_rows), _ptr(stats), _ptr(q))
+            self._keep_e = rows
+        else:
+            self._call(self.lib.afr_eval, self._plan, _ptr(t) if need_t else C.c_void_p(0), td if need_t else 0, B, _ptr(loss_rows), _ptr(stats), _ptr(q))
+            self._keep_e = t if need_t else None
+        return EvalResult(loss_rows, None if stats is None else stats.to(torch.int64), None if q is None else q.view(B, *self._hw()))
+
+    def evaluate(self, x, target=None, font=None, want_u8=False):
+        """An eval forward (no float32 output is materialised) followed by the evaluation kernel: per-sample loss and the 8-bit error
+        counts against `target`, and with want_u8 (or without a target) the uint8 bitmaps.  A batch larger than micro_batch is split
+        as forward() splits it."""
+        x, font = self._prep_x(x, font)
+        n = x.shape[0]
+        if self.micro_batch and n > self.micro_batch:
+            return EvalResult.cat([self.evaluate(x[lo:lo + self.micro_batch], None if target is None else target[lo:lo + self.micro_batch],
+                                                 None if font is None else font[lo:lo + self.micro_batch], want_u8)
+                                   for lo in range(0, n, self.micro_batch)])
+        if target is not None and target.shape[0] != n:
+            raise ValueError(f"{target.shape[0]} targets for a batch of {n}")
+        self.forward(x, font=font, training=False, want_output=False)
+        return self.evaluate_last(target=target, want_u8=want_u8)
+
+    def evaluate_rows(self, rows, want_u8=False):
+        """evaluate() on rows of the bound data set (duplicates allowed), against their targets where they lie."""
+        rows = self._rows(rows)
+        if self.micro_batch and rows.shape[0] > self.micro_batch:
+            return EvalResult.cat([self.evaluate_rows(rows[lo:lo + self.micro_batch], want_u8) for lo in range(0, rows.shape[0], self.micro_batch)])
+        self.forward_rows(rows, training=False, want_output=False)
+        return self.evaluate_last(rows=rows, want_u8=want_u8)
+
+    def render_u8(self, x, font=None):
+        """uint8 [B, H, W]: the levels binary_array_to_image would write for forward(x), quantised on the device."""
+        return self.evaluate(x, font=font, want_u8=True).u8
 
     def loss_grad_rows(self, rows, mean_elems=None):
         """loss_grad() against the targets of data-set rows `rows` (the rows of the forward before it)."""

@@ -28,6 +28,15 @@ def binary_array_to_image(binary_array, output_path=None):
     return image
 
 
+def u8_array_to_image(levels, output_path=None):
+    """[H,W] uint8 levels (Engine.render_u8, already quantised on the device) -> 8-bit PIL image, optionally saved as BMP."""
+    image = Image.fromarray(np.ascontiguousarray(levels, dtype=np.uint8))
+    if output_path:
+        os.makedirs(os.path.dirname(output_path) or ".", exist_ok=True)
+        image.save(output_path, "BMP")
+    return image
+
+
 def encode_for_model(strings, max_length, warn=True):
     """ord() codes, cut to max_length (with the reference's warning, helpers.py:52-54), zero padded (:57-59)."""
     rows = np.zeros((len(strings), max_length), dtype=np.int64)

@@ -29,7 +29,11 @@ What is deliberately different from the reference, and why:
     plateau scheduler, the 5-epoch test-string dumps and the saved model are then taken from the average.  Unset: the reference's
     loop, nothing changes;
   * AFR_NO_DECAY=1 takes the tensors of config.no_decay_names -- every bias and LayerNorm tensor, the positional table and the
-    embedding -- out of weight decay (optimizer groups, Engine.set_param_groups).  Unset: one group, the reference's optimizer.
+    embedding -- out of weight decay (optimizer groups, Engine.set_param_groups).  Unset: one group, the reference's optimizer;
+  * AFR_VAL_REPORT=<k> (k >= 1) adds a validation report, counted on the device (Engine.evaluate_last): on the epochs that print a
+    status line, one more line with the rates of pixels whose 8-bit level is off by >= 1 and by >= 2 and of wrong-ink pixels, the
+    largest level difference and the k validation sheets with the largest loss, whose predicted bitmaps are written as
+    epoch_<e>/val_worst_<j>.bmp.  Unset: nothing changes.
 """
 import contextlib
 import datetime
@@ -81,6 +85,57 @@ def _ema_from_env():
         return float(decay), int(every) if every else 1
     except ValueError:
         raise ValueError(f"AFR_EMA must be <decay> or <decay>:<every>, e.g. 0.999 or 0.999:8, got {spec!r}") from None
+
+
+def _val_report_from_env():
+    """AFR_VAL_REPORT = "<k>", k >= 1: the validation report with the k worst sheets; unset or empty -> None (off).  Anything else is
+    a ValueError."""
+    spec = os.environ.get("AFR_VAL_REPORT", "").strip()
+    if not spec:
+        return None
+    try:
+        k = int(spec)
+    except ValueError:
+        k = 0
+    if k < 1:
+        raise ValueError(f"AFR_VAL_REPORT must be an integer >= 1 (the number of worst validation sheets to list), got {spec!r}")
+    return k
+
+
+VAL_REPORT = _val_report_from_env()     # read at import, like the settings above: a bad value stops the run before it starts
+
+
+class _ValReport:
+    """What AFR_VAL_REPORT keeps on the device during one validation pass: the column sums of the evaluation kernel's counts, their
+    maximum, and the k largest per-sample losses with their data-set indices (merged batch by batch with torch.topk)."""
+
+    def __init__(self, k, dev, bitmaps=False):
+        self.k, self.bitmaps = int(k), bool(bitmaps)
+        self.sums = torch.zeros(4, dtype=torch.int64, device=dev)         # pixels off by >= 1, by >= 2, wrong ink; sheets
+        self.max = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.loss = torch.empty(0, dtype=torch.float32, device=dev)
+        self.idx = torch.empty(0, dtype=torch.int64, device=dev)
+        self.u8 = None                                                    # [k, H, W] of the worst sheets (bitmaps, rank 0)
+
+    def add(self, res, idx):
+        st = res.stats
+        self.sums[:3] += st[:, [0, 1, 3]].sum(0)
+        self.sums[3] += st.shape[0]
+        self.max = torch.maximum(self.max, st[:, 2].max().reshape(1))
+        loss, ids = torch.cat([self.loss, res.loss_rows]), torch.cat([self.idx, idx.to(self.idx.device).reshape(-1)])
+        top = torch.topk(loss, min(self.k, loss.numel()))
+        self.loss, self.idx = top.values, ids[top.indices]
+
+    def all_reduce(self, dist):
+        """Every rank issues both collectives (the setting is rank-invariant); the worst list stays this rank's."""
+        dist.all_reduce(self.sums, op=dist.ReduceOp.SUM)
+        dist.all_reduce(self.max, op=dist.ReduceOp.MAX)
+
+    def line(self, pixels, world=1):
+        s, n = self.sums.tolist(), max(1, int(self.sums[3]) * pixels)
+        worst = ", ".join(f"{i}({v:.6f})" for i, v in zip(self.idx.tolist(), self.loss.tolist()))
+        return (f"Val report: off by >= 1 level {s[0] / n:.6f}, off by >= 2 levels {s[1] / n:.6f}, wrong ink {s[2] / n:.6f}, "
+                f"max level diff {int(self.max)}, worst {len(self.idx)}{' of rank 0 shard' if world > 1 else ''}: {worst}")
 
 
 def _eval_weights(eng):
@@ -252,6 +307,17 @@ class AttentionFontRenderer(nn.Module):
         self._steps += 1
         return self._steps
 
+    def render_u8(self, codes):
+        """uint8 [B, SHEET_HEIGHT, SHEET_WIDTH] on the device: binary_array_to_image's levels of the eval-mode forward(codes), quantised
+        by the library (Engine.render_u8) instead of on the host.  The same shape, shadow-refresh and index checks as forward."""
+        if codes.dim() != 2:
+            raise ValueError(f"expected [batch, seq_len] codes, got shape {tuple(codes.shape)}")
+        self._refresh_shadow_if_params_changed()
+        q = self.engine.render_u8(codes)
+        if self.strict_indices and self.engine.error_flags():
+            raise IndexError("index out of range in self")          # what nn.Embedding raises in the reference
+        return q
+
     def forward(self, x):
         if x.dim() != 2:
             raise ValueError(f"expected [batch, seq_len] codes, got shape {tuple(x.shape)}")
@@ -330,12 +396,13 @@ def _step_hyper(eng, lr):
     return lr, WEIGHT_DECAY
 
 
-def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True):
+def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True, report=None):
     """One epoch of the reference loop (model.py:288-333): the training pass over order.train_epoch(), then the validation
     pass; returns the two means of per-batch mean losses.  An engine that keeps a weight EMA validates from it.  by_rows: the engine has the data set bound (Engine.bind_dataset)
     and every step is driven by this rank's slice of the epoch's index vector -- the kernels read the rows where they lie.
     by_rows=False gathers each batch with index_select and hands the step dense tensors (the form tools/epoch_bench.py
-    measures the other against)."""
+    measures the other against).  report: a _ValReport (AFR_VAL_REPORT) that every validation batch is evaluated into between its
+    forward and its loss; None: the pass as it always was."""
     from .parallel import shard_rows
     eng = model.engine
     pixels = targets[0].numel()
@@ -362,10 +429,21 @@ def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, wor
             mine = rows[shard_rows(rows.numel(), rank, world)]
             if by_rows:
                 eng.forward_rows(mine, training=False, want_output=False)
+                if report is not None:
+                    report.add(eng.evaluate_last(rows=mine), mine)
                 eng.loss_grad_rows(mine, mean_elems=rows.numel() * pixels)
             else:
                 eng.forward(inputs.index_select(0, mine), training=False, want_output=False)
-                eng.loss_grad(targets.index_select(0, mine), mean_elems=rows.numel() * pixels)
+                tb = targets.index_select(0, mine)
+                if report is not None:
+                    report.add(eng.evaluate_last(target=tb), mine)
+                eng.loss_grad(tb, mean_elems=rows.numel() * pixels)
+        if report is not None:
+            if world > 1:
+                report.all_reduce(_dist()[0])
+            if report.bitmaps and rank == 0 and report.idx.numel():      # the worst sheets once more, for their bitmaps (no collective)
+                report.u8 = (eng.evaluate_rows(report.idx, want_u8=True) if by_rows else
+                             eng.evaluate(inputs.index_select(0, report.idx), want_u8=True)).u8
     return avg_train_loss, stepper.global_loss() / max(nvb, 1)
 
 
@@ -394,6 +472,8 @@ def train_attention_model(model, dataset, batch_size):
                 f.write(f"max_grad_norm = {eng.max_grad_norm:g}\n")
             if eng.ema_decay is not None:       # likewise
                 f.write(f"ema_decay = {eng.ema_decay:g}\nema_every = {eng.ema_every}\n")
+            if VAL_REPORT:                      # likewise
+                f.write(f"val_report = {VAL_REPORT}\n")
 
     order = _EpochOrder(len(dataset))
     print(f"Dataset split: {order.train_size} training samples, {order.val_size} validation samples")
@@ -422,7 +502,8 @@ def train_attention_model(model, dataset, batch_size):
     epoch = -1
     for epoch in range(NUM_EPOCHS):
         lr = lr_holder.param_groups[0]["lr"]
-        avg_train_loss, avg_val_loss = _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True)
+        report = _ValReport(VAL_REPORT, device, bitmaps=epoch % 5 == 0) if VAL_REPORT else None
+        avg_train_loss, avg_val_loss = _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True, report=report)
 
         scheduler.step(avg_val_loss)
         is_best = avg_val_loss < best_val_loss
@@ -442,6 +523,10 @@ def train_attention_model(model, dataset, batch_size):
                 if is_best:
                     status += " (New Best)"
                 print(status)
+                if report is not None:
+                    print(report.line(targets[0].numel(), world))
+                    for j in range(0 if report.u8 is None else report.u8.shape[0]):
+                        helpers.u8_array_to_image(report.u8[j].cpu().numpy(), f"{OUTPUT_DIR}/epoch_{epoch}/val_worst_{j}.bmp")
                 with _eval_weights(eng):
                     render_strings(model, test_strings, output_dir=f"{OUTPUT_DIR}/epoch_{epoch}", sheet_height=SHEET_HEIGHT,
                                    sheet_width=SHEET_WIDTH, device=device)

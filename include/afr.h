@@ -283,6 +283,33 @@ int afr_forward_loss_rows(afr_plan* plan, const int64_t* rows, int B, int64_t me
 int afr_train_step_rows(afr_plan* plan, const int64_t* rows, int B, int64_t mean_elems, float* loss_accum, uint64_t step,
                         int do_step, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t t, void* stream);
 
+/* ---- evaluation on the device: per-sample loss, 8-bit error counts, u8 bitmaps (DESIGN.md 4 "Evaluation") ----
+ * afr_eval follows an afr_forward (training 0 or 1) and reads the pre-activation u [B][pixels] that forward saved; afr_eval_rows
+ * follows afr_forward_rows on the same rows of the bound data set.  The contract is afr_loss_grad's / afr_loss_grad_rows': B must
+ * equal the last forward's.  u is left bit-identical, so afr_loss_grad*, afr_set_output_grad and afr_backward may follow as if
+ * nothing had happened.  The call launches ONE kernel and allocates nothing.  Each output is a caller-owned device buffer or NULL.
+ * For batch row b and pixel i, with y = the plan's output head of u (clamp(u, 0, 1); sigmoid(u) on an AFR_LOSS_BCE plan) and
+ * t = the target as the loss sees it (k / 255.0f for uint8 pixels k, the float otherwise):
+ *   q[b][i]      uint8 [B][pixels]: (uint8)(y * 255.0f), truncating -- the level helpers.binary_array_to_image writes to a BMP.
+ *                A NaN u gives level 0.  Needs no target.
+ *   loss_rows[b] float [B]: (sum_i term(u, t)) / pixels; term = (y - t)^2 (MSE) or max(u,0) - t u + log1p(exp(-|u|)) (BCE), the
+ *                values afr_loss_grad sums.  A row that holds a NaN is NaN; no other row is affected.
+ *   stats[b][4]  uint32 [B][4], with t8 = k, or rintf(t * 255.f) limited to 0..255 for float targets, and d = |q - t8| over row b:
+ *                [0] = #(d >= 1), [1] = #(d >= 2), [2] = max d, [3] = #((q >= 128) != (t8 >= 128)), the wrong-ink pixels.
+ * A row is summed by one wave (pixels <= 2048) or one 256-lane workgroup, in float32 and in a fixed order: each of the L = 64 (256)
+ * lanes adds the terms of its groups of 8 pixels g = lane, lane + L, ... in ascending order, pixel by pixel; then six butterfly
+ * steps across the wave (offsets 32, 16, 8, 4, 2, 1); then, for a workgroup, ((w0 + w1) + w2) + w3 over its four waves; then one
+ * division by pixels.  A row's three results therefore depend on that row's data only -- not on B, the row's position or the
+ * grid -- and are bitwise reproducible.  No atomics, no communication between workgroups.
+ * Errors: all three outputs NULL, target NULL while loss_rows or stats is given, a bad target dtype, B outside 1..max_batch,
+ * stats not 16-byte / q or uint8 targets not 8-byte / float32 targets not 16-byte aligned -> AFR_EINVAL; B != the last
+ * forward's, or the u buffer already holds du (after afr_loss_grad*, afr_set_output_grad, afr_forward_loss*, afr_train_step*) ->
+ * AFR_ESTATE; afr_eval_rows without a bound data set -> AFR_ESTATE.  Both are allowed while afr_use_ema is on: they see whatever
+ * the forward saw. */
+int afr_eval(afr_plan* plan, const void* target /* or NULL */, int target_dtype, int B,
+             float* loss_rows /* or NULL */, uint32_t* stats /* or NULL */, uint8_t* q /* or NULL */, void* stream);
+int afr_eval_rows(afr_plan* plan, const int64_t* rows, int B, float* loss_rows, uint32_t* stats, uint8_t* q, void* stream);
+
 /* Set / read the device-side error word (bit 0: an embedding index outside [0,vocab), the
  * condition on which the reference raises IndexError; model.py:136,167; bit 1: a cooperative split-K
  * workgroup gave up waiting for its partners -- the step's results are invalid; bit 2: a row index of an afr_*_rows call
@@ -393,6 +420,12 @@ int afr_op_mse_grad(int act_dtype, const void* u, const void* target, int target
 int afr_op_bce_grad(int act_dtype, const void* u, const void* target, int target_dtype, void* du,
                     int64_t rows, int64_t cols, int64_t mean_elems, float* loss_accum, float* scratch,
                     void* stream);
+/* afr_eval's kernel on caller-owned buffers: u [rows][cols] float32 (AFR_F32) or bf16 (AFR_BF16), loss_kind AFR_LOSS_*, cols a
+ * multiple of 8 (AFR_EUNSUPPORTED otherwise).  rowmap (or NULL): int32 [rows], the targets of row r are row rowmap[r] of target
+ * (64-bit addressing); it is not read without a target.  Outputs, formulas, summation order and argument errors as afr_eval. */
+int afr_op_eval(int act_dtype, int loss_kind, const void* u, const void* target /* or NULL */, int target_dtype,
+                const int32_t* rowmap /* or NULL */, int64_t rows, int64_t cols,
+                float* loss_rows, uint32_t* stats, uint8_t* q, void* stream);
 int afr_op_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);
 
 /* ---- the token-wise kernels of the per-pixel-token transformer (AFR_KIND_PIXEL), one launch each, exactly as the plan issues

@@ -1,0 +1,397 @@
+"""GPU: evaluation on the device -- afr_op_eval / afr_eval / afr_eval_rows, Engine.evaluate*, render_u8 and AFR_VAL_REPORT.
+
+Yardsticks: tests/eval_ref.py (fp64 restatement; its float32 restatement gives the summation depth D(cols) of the bound), numpy's
+own float32 quantisation for the MSE levels, torch's CPU float32 binary_cross_entropy_with_logits for the BCE loss (as
+tests/test_gpu_bce.py does for afr_op_bce_grad), the engine's own forward for the plan-level levels, and committed fixtures."""
+import ctypes as C
+import functools
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from . import eval_ref as R
+from . import lion_ref
+from .util import ROOT, load, oracle, synth
+
+pytestmark = pytest.mark.gpu
+
+COLS = (8, 64, 504, 512, 520, 2040, 2048, 2056, 4096, 19200)      # 2048 is the wave / workgroup threshold: 2040, 2048, 2056 straddle it
+SHAPES = [(r, c) for c in COLS for r in (1, 3, 300)] + [(2500, 64), (8 * 1024 + 8, 8)]      # the last two: a second trip of the row loop
+#   (2500 rows as the issue words it; the grid cap of 2048 blocks x 4 waves is 8192 rows in wave form, so 8200 rows of 8 pixels pass it)
+DELTA = 1e-4              # BCE levels: either neighbour where fp64 255 sigmoid(u) is this close to an integer
+SAT = 17.0                # from here 1 + exp(-u) rounds to 1 in float32: levels 254 and 255 both allowed (planted values only)
+
+
+def _planted(loss):
+    # (k = 2 is left out of the planted levels on purpose: 255 sigmoid(2 / 255.0f) = 127.99985, inside DELTA of 128, and planted in
+    # two rows it alone would spend the near-integer cap of the small shapes)
+    p = [0.0, -0.0, 1.0] + [float(np.float32(k) / np.float32(255.0)) for k in (1, 3, 127, 128, 254)] + [-3.0, 7.0]
+    return np.array(p + ([30.0, -30.0, 104.0, -104.0] if loss == "bce" else []), dtype=np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def _inputs(rows, cols, loss, act):
+    """u (the float32 values the kernel reads: rounded to bf16 first for act == "bf16"), uint8 targets [2 rows][cols], the row map
+    (a reversed range with duplicates into the 2 x rows target rows)."""
+    g = np.random.default_rng(1000 * cols + rows + (7 if loss == "bce" else 0))
+    lo, hi = (-8.0, 8.0) if loss == "bce" else (-0.5, 1.5)
+    u = g.uniform(lo, hi, (rows, cols)).astype(np.float32)
+    p = _planted(loss)
+    n = min(cols, len(p))
+    u[0, :n] = p[:n]
+    u[-1, cols - n:] = p[len(p) - n:]
+    if act == "bf16":
+        u = torch.from_numpy(u).to(torch.bfloat16).float().numpy()
+    k = g.integers(0, 256, (2 * rows, cols), dtype=np.uint8)
+    rowmap = ((2 * rows - 1 - np.arange(rows)) // 2 * 2).astype(np.int32)
+    return u, k, rowmap
+
+
+def _guarded(nbytes, fill=0xFF):
+    buf = torch.full((nbytes + 512,), fill, dtype=torch.uint8, device="cuda")
+    return buf, buf[256:256 + nbytes]
+
+
+def _guards_ok(buf):
+    return bool((buf[:256] == 0xFF).all()) and bool((buf[-256:] == 0xFF).all())
+
+
+def op_eval(u_dev, loss, tgt=None, rowmap=None, want=(True, True, True)):
+    """One afr_op_eval launch into guarded, pre-filled buffers (0xFF bytes: a NaN in loss_rows, 0xFFFFFFFF in stats).  Returns
+    (loss_rows f32 [R] | None, stats int64 [R, 4] | None, q uint8 [R, C] | None) on the device."""
+    from ai_font_renderer_amd import _lib
+    from .gpu_util import ptr, stream
+    rows, cols = u_dev.shape
+    ad = _lib.AFR_BF16 if u_dev.dtype == torch.bfloat16 else _lib.AFR_F32
+    td = _lib.AFR_TARGET_U8 if tgt is None or tgt.dtype == torch.uint8 else _lib.AFR_TARGET_F32
+    bufs = [_guarded(n) if w else (None, None) for n, w in zip((4 * rows, 16 * rows, rows * cols), want)]
+    _lib.check(_lib.lib().afr_op_eval(ad, _lib.loss_kind(loss), ptr(u_dev), ptr(tgt), td, ptr(rowmap), rows, cols,
+                                      ptr(bufs[0][1]), ptr(bufs[1][1]), ptr(bufs[2][1]), stream()))
+    torch.cuda.synchronize()
+    for b, _ in bufs:
+        assert b is None or _guards_ok(b)
+    lr = bufs[0][1].view(torch.float32) if want[0] else None
+    st = bufs[1][1].view(torch.int32).view(rows, 4) if want[1] else None
+    if st is not None:
+        assert bool((st >= 0).all()) and bool((st <= max(cols, 255)).all())          # came back whole: no 0xFFFFFFFF word left
+        st = st.to(torch.int64)
+    return lr, st, bufs[2][1].view(rows, cols) if want[2] else None
+
+
+def _check_q(q, u, loss):
+    """The levels against the yardstick; returns nothing, asserts."""
+    if loss == "mse":
+        assert np.array_equal(q, (np.clip(u, 0, 1) * 255).astype(np.uint8))           # numpy's own float32 dump, exactly
+        return
+    v = 255.0 * R.head64(u, "bce")
+    want = np.floor(v).astype(np.int64)
+    near = (np.abs(v - np.rint(v)) < DELTA) & (np.rint(v) >= 1)     # (below level 1 there is no neighbour to fall to: 0 exactly)
+    sat = u >= SAT
+    other = np.where(v >= np.rint(v), want - 1, want + 1)            # the neighbour across the integer that v is close to
+    ok = (q == want) | (near & (q == other)) | (sat & ((q == 254) | (q == 255)))
+    assert ok.all(), (u[~ok][:5], q[~ok][:5], want[~ok][:5])
+    assert (near & ~sat).sum() < 1e-3 * u.size, int((near & ~sat).sum())
+
+
+def _check_loss(got, u, k_or_t, loss, rowmap, cols):
+    want = R.loss_rows64(u, k_or_t, loss, rowmap)
+    err = np.abs(got.astype(np.float64) - want)
+    if loss == "mse":
+        bound = R.mse_bound(cols, want)
+        print(f"eval mse cols {cols}: worst row at {float((err / np.maximum(bound, 1e-300)).max()):.3f} of the bound (D = {R.chain_depth(cols)})")
+        assert (err <= bound).all(), float((err / bound).max())
+        return
+    t = torch.from_numpy(R.targets_f32(R.gather(k_or_t, rowmap)[:len(u)]))
+    tl = F.binary_cross_entropy_with_logits(torch.from_numpy(u), t, reduction="none").double().sum(1).numpy() / cols
+    torch_dev = float(np.abs(tl - want).max())
+    t64 = t.double().numpy()
+    absum = np.abs(np.maximum(u.astype(np.float64), 0) - t64 * u + np.log1p(np.exp(-np.abs(u.astype(np.float64))))).sum(1) / cols
+    allow = 4.0 * torch_dev + (R.chain_depth(cols) + 1) * R.EPS32 * float(absum.max())
+    print(f"eval bce cols {cols}: engine max row error {float(err.max()):.3e}, torch f32 {torch_dev:.3e}, allowed {allow:.3e}")
+    assert float(err.max()) <= allow, (float(err.max()), allow)
+
+
+@pytest.mark.parametrize("act", ["f32", "bf16"])
+@pytest.mark.parametrize("loss", ["mse", "bce"])
+@pytest.mark.parametrize("rows,cols", SHAPES)
+def test_op_eval_against_the_yardsticks(rows, cols, loss, act):
+    """Every shape x loss kind x u dtype; inside: uint8 and float32 targets, with and without the row map, and every combination
+    of present and absent outputs (the subsets bit-identical to the launch that has all three).  u and targets are left as they were."""
+    from .gpu_util import dev
+    u, k, rowmap = _inputs(rows, cols, loss, act)
+    ud = dev(u, torch.bfloat16 if act == "bf16" else torch.float32)
+    u_before = ud.clone()
+    rm = dev(rowmap)
+    q_only = op_eval(ud, loss, want=(False, False, True))[2]
+    _check_q(q_only.cpu().numpy(), u, loss)
+    for tname in ("u8", "f32"):
+        tnp = k if tname == "u8" else (k.astype(np.float32) / np.float32(255.0))
+        td = dev(tnp)
+        t_before = td.clone()
+        for use_map in (False, True):
+            lr, st, q = op_eval(ud, loss, td, rm if use_map else None)
+            assert torch.equal(q, q_only)
+            qn = q.cpu().numpy()
+            t8 = R.t8_of(R.gather(tnp, rowmap if use_map else None)[:rows])
+            assert np.array_equal(st.cpu().numpy(), R.stats_of(qn.astype(np.int64), t8))          # the integer counts of the kernel's own q
+            lrn = lr.cpu().numpy()
+            assert np.isfinite(lrn).all()
+            _check_loss(lrn, u, tnp, loss, rowmap if use_map else None, cols)
+            for want in ((True, False, False), (False, True, False), (True, True, False), (True, False, True), (False, True, True)):
+                a, b, c = op_eval(ud, loss, td, rm if use_map else None, want)
+                assert a is None or torch.equal(a, lr)
+                assert b is None or torch.equal(b, st)
+                assert c is None or torch.equal(c, q)
+            a, b, c = op_eval(ud, loss, td, rm if use_map else None)                                # a second launch is bit-identical
+            assert torch.equal(a, lr) and torch.equal(b, st) and torch.equal(c, q)
+        assert torch.equal(td, t_before)
+    assert torch.equal(ud.view(torch.int16 if act == "bf16" else torch.int32), u_before.view(torch.int16 if act == "bf16" else torch.int32))
+
+
+@pytest.mark.parametrize("act", ["f32", "bf16"])
+@pytest.mark.parametrize("loss", ["mse", "bce"])
+@pytest.mark.parametrize("cols", [64, 2048, 2056, 19200])
+def test_op_eval_rows_are_local(cols, loss, act):
+    """The same row content at the first, a middle and the last batch row, at rows = 3 and 300, gives bit-identical results; a NaN
+    planted in one row makes that row's loss NaN and its level 0 there and leaves every other row bit-identical."""
+    from .gpu_util import dev
+    dt = torch.bfloat16 if act == "bf16" else torch.float32
+    u0, k0, _ = _inputs(1, cols, loss, act)
+    seen = []
+    for rows in (3, 300):
+        u, k, _ = _inputs(rows, cols, loss, act)
+        u, k = u.copy(), k[:rows].copy()
+        where = (0, rows // 2, rows - 1)
+        for r in where:
+            u[r], k[r] = u0[0], k0[0]
+        ud, kd = dev(u, dt), dev(k)
+        lr, st, q = op_eval(ud, loss, kd)
+        for r in where:
+            seen.append((lr[r].clone(), st[r].clone(), q[r].clone()))
+        # the NaN
+        r, c = where[1], cols // 2
+        un = ud.clone()
+        un[r, c] = float("nan")
+        lrn, stn, qn = op_eval(un, loss, kd)
+        assert bool(torch.isnan(lrn[r])) and int(qn[r, c]) == 0
+        keep = torch.arange(rows, device="cuda") != r
+        assert torch.equal(lrn[keep], lr[keep]) and torch.equal(stn[keep], st[keep]) and torch.equal(qn[keep], q[keep])
+        assert bool(torch.isfinite(lr).all())
+        qn[r, c] = q[r, c]
+        assert torch.equal(qn, q)                                   # the NaN row's other levels too
+    for a, b, c in seen[1:]:
+        assert torch.equal(a.view(torch.int32), seen[0][0].view(torch.int32)) and torch.equal(b, seen[0][1]) and torch.equal(c, seen[0][2])
+
+
+def test_op_eval_argument_errors_launch_nothing():
+    from ai_font_renderer_amd import _lib
+    from .gpu_util import ptr, stream
+    lib = _lib.lib()
+    u = torch.zeros(4, 24, device="cuda")
+    k = torch.zeros(4, 24, dtype=torch.uint8, device="cuda")
+    outs = [_guarded(n) for n in (16, 64, 96)]
+
+    def call(cols=24, tgt=k, want=(1, 1, 1), rows=4):
+        return lib.afr_op_eval(0, 0, ptr(u), ptr(tgt), 0, None, rows, cols, *[ptr(o[1]) if w else C.c_void_p(0) for o, w in zip(outs, want)], stream())
+
+    assert call(cols=12, rows=8) == _lib.AFR_EUNSUPPORTED
+    assert call(tgt=None, want=(0, 1, 1)) == _lib.AFR_EINVAL
+    assert call(tgt=None, want=(1, 0, 0)) == _lib.AFR_EINVAL
+    assert call(want=(0, 0, 0)) == _lib.AFR_EINVAL
+    torch.cuda.synchronize()
+    for buf, _ in outs:
+        assert bool((buf == 0xFF).all())                            # nothing ran
+    assert call() == 0 and call(tgt=None, want=(0, 0, 1)) == 0
+    torch.cuda.synchronize()
+
+
+# ----------------------------------------------------------------------------- plan level
+MODELS = ("sheet-mini", "glyph-small", "glyph-c1", "c5-mini")
+
+
+def _engine(cfg, dtype, loss, B, **kw):
+    from ai_font_renderer_amd.engine import Engine
+    eng = Engine(cfg, dtype=dtype, max_batch=B, loss=loss, **kw)
+    eng.load_params(synth.make_params(cfg))
+    return eng
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("loss", ["mse", "bce"])
+@pytest.mark.parametrize("name", MODELS)
+def test_engine_evaluate_against_forward_loss_grad_and_rows(name, loss, dtype):
+    from ai_font_renderer_amd import _lib
+    cfg, x, font, tu8 = lion_ref.case(name)
+    B, pix = x.shape[0], cfg.pixels
+    eng = _engine(cfg, dtype, loss, B)
+    # q against forward: the head is the same device function
+    y = eng.forward(x, font=font).cpu().numpy()
+    res = eng.evaluate(x, tu8, font=font, want_u8=True)
+    assert res.u8.dtype == torch.uint8 and tuple(res.u8.shape) == y.shape
+    assert np.array_equal(res.u8.cpu().numpy(), (y * 255).astype(np.uint8))
+    assert torch.equal(eng.render_u8(x, font=font), res.u8)
+    t8 = tu8.reshape(B, -1).numpy().astype(np.int64)
+    assert np.array_equal(res.stats.cpu().numpy(), R.stats_of(res.u8.reshape(B, -1).cpu().numpy().astype(np.int64), t8))
+    # loss against loss_grad on the same forward, and loss_grad after evaluate_last as if nothing had happened
+    me = B * pix * 3
+    eng.read_loss()
+    eng.forward(x, font=font, want_output=False)
+    eng.loss_grad(tu8, mean_elems=me)
+    du_plain, loss_plain = eng.debug_read("u").clone(), eng.read_loss()
+    eng.forward(x, font=font, want_output=False)
+    u_before = eng.debug_read("u").clone()
+    again = eng.evaluate_last(target=tu8, want_u8=True)
+    assert torch.equal(eng.debug_read("u").view(torch.int32), u_before.view(torch.int32))          # u is left bit-identical
+    with pytest.raises(_lib.AfrError) as e:                         # a batch that is not the forward's
+        eng.evaluate_last(target=tu8[:B - 1])
+    assert e.value.code == _lib.AFR_ESTATE
+    eng.loss_grad(tu8, mean_elems=me)
+    assert torch.equal(eng.debug_read("u").view(torch.int32), du_plain.view(torch.int32)) and eng.read_loss() == loss_plain
+    assert torch.equal(again.loss_rows, res.loss_rows) and torch.equal(again.stats, res.stats) and torch.equal(again.u8, res.u8)
+    total = float(res.loss_rows.double().sum()) * pix / me
+    assert abs(total - loss_plain) <= 1e-5 * abs(loss_plain), (total, loss_plain)
+    # the u buffer holds du now
+    for call in (lambda: eng.evaluate_last(target=tu8), lambda: eng.evaluate_last()):
+        with pytest.raises(_lib.AfrError) as e:
+            call()
+        assert e.value.code == _lib.AFR_ESTATE
+    eng.train_step(x, tu8, font=font, do_step=False)
+    eng.read_loss()
+    with pytest.raises(_lib.AfrError) as e:
+        eng.evaluate_last(target=tu8)
+    assert e.value.code == _lib.AFR_ESTATE
+    # rows against dense: a bound uint8 data set, duplicates in rows
+    eng.bind_dataset(x, tu8, font=font)
+    rows = torch.tensor([B - 1, 0, 3 % B, 3 % B, B // 2, 0], dtype=torch.int64)
+    a = eng.evaluate_rows(rows, want_u8=True)
+    b = eng.evaluate(x[rows], tu8[rows], font=None if font is None else font[rows], want_u8=True)
+    assert torch.equal(a.loss_rows.view(torch.int32), b.loss_rows.view(torch.int32)) and torch.equal(a.stats, b.stats) and torch.equal(a.u8, b.u8)
+    eng.forward_rows(rows, want_output=False)
+    c = eng.evaluate_last(rows=rows)
+    assert c.u8 is None and torch.equal(c.loss_rows, a.loss_rows) and torch.equal(c.stats, a.stats)
+    assert eng.error_flags() == 0
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_evaluate_inside_ema_weights_sees_the_average(dtype):
+    cfg, x, font, tu8 = lion_ref.case("glyph-small")
+    B = x.shape[0]
+    eng = _engine(cfg, dtype, "mse", B, ema_decay=0.5)
+    for _ in range(2):
+        eng.train_step(x, tu8, font=font)
+    eng.read_loss()
+    with eng.ema_weights():
+        a = eng.evaluate(x, tu8, font=font, want_u8=True)
+    ref = _engine(cfg, dtype, "mse", B)
+    ref.load_params(eng.ema_state_dict())
+    b = ref.evaluate(x, tu8, font=font, want_u8=True)
+    assert torch.equal(a.loss_rows.view(torch.int32), b.loss_rows.view(torch.int32)) and torch.equal(a.stats, b.stats) and torch.equal(a.u8, b.u8)
+    c = eng.evaluate(x, tu8, font=font)                            # and outside, the weights themselves
+    assert not torch.equal(c.loss_rows, a.loss_rows)
+    assert eng.error_flags() == 0
+
+
+def test_evaluate_splits_by_micro_batch():
+    cfg, x, font, tu8 = lion_ref.case("glyph-small")
+    from ai_font_renderer_amd.engine import EvalResult
+    one = _engine(cfg, "f32", "mse", 128)
+    whole = EvalResult.cat([one.evaluate(x[lo:lo + 128], tu8[lo:lo + 128], font=font[lo:lo + 128], want_u8=True) for lo in range(0, x.shape[0], 128)])
+    parts = _engine(cfg, "f32", "mse", x.shape[0], micro_batch=128).evaluate(x, tu8, font=font, want_u8=True)
+    assert parts.loss_rows.shape[0] == x.shape[0] == 300
+    assert torch.equal(whole.loss_rows, parts.loss_rows) and torch.equal(whole.stats, parts.stats) and torch.equal(whole.u8, parts.u8)
+
+
+@functools.lru_cache(maxsize=None)
+def _r0_model():
+    from ai_font_renderer_amd import model as M
+    m = M.AttentionFontRenderer(max_length=100, max_batch=16, init=False, dtype="f32", loss="mse")
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_params(m.config).items()})
+    m.eval()
+    return m
+
+
+def test_r0_dumps_within_one_level_counted_on_the_device():
+    """R0 in f32 mode on the reference's 15 test_strings against the reference's own dumps: the bar of tests/test_gpu_bf16x3.py
+    (within one level, in fewer than 1e-3 of the pixels), counted by the evaluation kernel."""
+    from ai_font_renderer_amd import helpers, model as M
+    m = _r0_model()
+    fx = load("sheet_r0.npz")
+    want = torch.from_numpy(oracle.sheet_to_u8(fx["test_eval_y"]))
+    codes = torch.from_numpy(helpers.encode_for_model(M.test_strings, 100, warn=False))
+    res = m.engine.evaluate(codes, want, want_u8=True)
+    st = res.stats.cpu().numpy()
+    assert st[:, 2].max() <= 1 and st[:, 1].sum() == 0 and st[:, 0].sum() < 1e-3 * want.numel(), st
+    assert np.array_equal(st, R.stats_of(res.u8.reshape(15, -1).cpu().numpy().astype(np.int64), want.reshape(15, -1).numpy().astype(np.int64)))
+
+
+def test_model_render_u8_is_binary_array_to_image_of_forward():
+    from ai_font_renderer_amd import helpers, model as M
+    m = _r0_model()
+    codes = torch.from_numpy(helpers.encode_for_model(M.test_strings, 100, warn=False))
+    q = m.render_u8(codes.to(M.device))
+    with torch.no_grad():
+        y = m(codes.to(M.device)).cpu().numpy()
+    assert q.dtype == torch.uint8 and tuple(q.shape) == (15, 80, 240)
+    for i in range(15):
+        assert np.array_equal(q[i].cpu().numpy(), np.array(helpers.binary_array_to_image(y[i])))
+    with pytest.raises(IndexError):
+        m.render_u8(torch.full((1, 5), 300, dtype=torch.int64))
+    with pytest.raises(ValueError):
+        m.render_u8(torch.zeros(5, dtype=torch.int64))
+
+
+_CHILD = """
+import sys
+sys.path.insert(0, {root!r})
+import torch
+from ai_font_renderer_amd import model as M
+M.NUM_SAMPLES, M.NUM_EPOCHS, M.OUTPUT_DIR = 96, 1, "out"
+torch.manual_seed(42)
+M.main(["model.py", "--train"])
+"""
+
+
+def _train_child(cwd, report):
+    env = {k: v for k, v in os.environ.items() if k != "AFR_VAL_REPORT"}
+    if report is not None:
+        env["AFR_VAL_REPORT"] = report
+    return subprocess.run([sys.executable, "-c", _CHILD.format(root=ROOT)], cwd=cwd, env=env, capture_output=True, text=True, timeout=600)
+
+
+def _files(root):
+    return sorted(os.path.relpath(os.path.join(d, f), root) for d, _, fs in os.walk(root) for f in fs)
+
+
+def test_val_report_in_the_training_cli(tmp_path):
+    """AFR_VAL_REPORT=2 python model.py --train in miniature (96 generated sheets, one epoch), each run a fresh child process: the
+    extra line on epoch 0 and the two bitmaps; without the variable the stdout and the file list are what they are today -- the
+    report run's, minus its own line, files and config entry."""
+    from PIL import Image
+    import shutil
+    from ai_font_renderer_amd import datagen
+    datagen.generate(str(tmp_path / "train_input"), 96)
+    for d in ("on", "off"):
+        os.makedirs(tmp_path / d)
+        shutil.copytree(tmp_path / "train_input", tmp_path / d / "train_input")
+    on, off = _train_child(tmp_path / "on", "2"), _train_child(tmp_path / "off", None)
+    assert on.returncode == 0 and off.returncode == 0, (on.stderr[-2000:], off.stderr[-2000:])
+    lines_on, lines_off = on.stdout.splitlines(), off.stdout.splitlines()
+    extra = [l for l in lines_on if l.startswith("Val report: ")]
+    assert len(extra) == 1 and lines_on.index(extra[0]) == [i for i, l in enumerate(lines_on) if l.startswith("Epoch 0, ")][0] + 1
+    assert "max level diff" in extra[0] and "worst 2: " in extra[0] and extra[0].count("(") == 2
+    assert [l for l in lines_on if l is not extra[0]] == lines_off                    # everything else byte for byte
+    assert not any("Val report" in l for l in lines_off)
+    for j in range(2):
+        img = Image.open(tmp_path / "on" / "out" / "epoch_0" / f"val_worst_{j}.bmp")
+        assert img.mode == "L" and img.size == (240, 80)
+    new = {os.path.join("out", "epoch_0", f"val_worst_{j}.bmp") for j in range(2)}
+    assert set(_files(tmp_path / "on")) - new == set(_files(tmp_path / "off")) and new <= set(_files(tmp_path / "on"))
+    cfg_on, cfg_off = ((tmp_path / d / "out" / "config.txt").read_text().splitlines() for d in ("on", "off"))
+    assert cfg_on == cfg_off + ["val_report = 2"]
+    bad = _train_child(tmp_path / "off", "zero")
+    assert bad.returncode != 0 and "AFR_VAL_REPORT" in bad.stderr

@@ -1,0 +1,193 @@
+#!/usr/bin/env python3
+"""What evaluating on the device costs, bf16, R0 at B = 1024 and C3 at B = 8192, one process.
+  python tools/eval_bench.py [--cases r0,c3] [--loss mse|bce] [--reps 5] [--launches 20] [--val-batches 8] [--out profiles/eval/eval_bench.jsonl]
+(a) kernel: an eval forward leaves u in the workspace; it is copied out once (afr_debug_copy) and the eval_rows launch
+    (afr_op_eval: per-row loss, counts and the u8 levels, all three outputs) takes turns with the mse_grad launch (afr_op_mse_grad,
+    du to a buffer of its own) on that same u and the same uint8 targets: R rounds of N event-timed launches each.  The eval pass
+    reads the same bytes and writes 1 byte per pixel where mse_grad writes 2, so the condition is that its median does not
+    exceed mse_grad's by more than mse_grad's own min-max spread ("within").  --loss bce: the BCE instantiations of both.
+(b) loop: the validation pass of model._run_epoch (forward_rows + [evaluate_last] + loss_grad_rows per batch; the training pass is
+    replaced by a stepper that does nothing) with the AFR_VAL_REPORT accumulator on and off, taking turns; the ratio, no bar.
+One JSON line per case and part."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from bench import make_inputs  # noqa: E402
+from ai_font_renderer_amd import _lib, synth  # noqa: E402
+from ai_font_renderer_amd import model as M  # noqa: E402
+from ai_font_renderer_amd.config import WORKLOADS  # noqa: E402
+from ai_font_renderer_amd.engine import Engine, _ptr, _stream  # noqa: E402
+
+
+def _stats(v, nd=3):
+    return dict(median=round(statistics.median(v), nd), min=round(min(v), nd), max=round(max(v), nd))
+
+
+def setup(name, loss="mse"):
+    """(engine, x, font, uint8 targets [B, pixels]) of a bench.py workload, bf16, everything on the device."""
+    cfg, B = WORKLOADS[name]["cfg"], WORKLOADS[name]["batch"]
+    eng = Engine(cfg, dtype="bf16", max_batch=B, loss=loss)
+    eng.load_params(synth.make_params(cfg))
+    x, font, tgt = make_inputs(name, cfg, B, 0)
+    t8 = M.helpers.targets_as_uint8(tgt)
+    assert t8 is not None
+    return eng, x.cuda(), None if font is None else font.cuda(), t8.cuda().reshape(B, -1).contiguous()
+
+
+def kernel_part(name, reps, launches, loss="mse"):
+    eng, x, font, t8 = setup(name, loss)
+    kind, grad = _lib.loss_kind(loss), (eng.lib.afr_op_bce_grad if loss == "bce" else eng.lib.afr_op_mse_grad)
+    B, pix = t8.shape
+    lib = eng.lib
+    eng.forward(x, font=font, want_output=False)
+    u = torch.empty(B, pix, dtype=torch.bfloat16, device="cuda")
+    n = C.c_size_t()
+    _lib.check(lib.afr_debug_copy(eng._plan, _lib.BUF_U, _ptr(u), u.numel() * 2, C.byref(n), _stream(eng.device)))
+    assert n.value == u.numel() * 2
+    du = torch.empty_like(u)
+    loss_rows = torch.empty(B, dtype=torch.float32, device="cuda")
+    stats = torch.empty(B, 4, dtype=torch.int32, device="cuda")
+    q = torch.empty(B, pix, dtype=torch.uint8, device="cuda")
+    accum, scratch = torch.zeros(1, device="cuda"), torch.zeros(1040, device="cuda")
+    s = _stream(eng.device)
+    forms = {
+        "eval_rows": lambda: _lib.check(lib.afr_op_eval(_lib.AFR_BF16, kind, _ptr(u), _ptr(t8), _lib.AFR_TARGET_U8, None, B, pix,
+                                                        _ptr(loss_rows), _ptr(stats), _ptr(q), s)),
+        "mse_grad": lambda: _lib.check(grad(_lib.AFR_BF16, _ptr(u), _ptr(t8), _lib.AFR_TARGET_U8, _ptr(du), B, pix, B * pix, _ptr(accum),
+                                                           _ptr(scratch), s)),
+    }
+    for f in forms.values():
+        for _ in range(launches):
+            f()
+    us = {k: [] for k in forms}
+    for _ in range(reps):
+        for k, f in forms.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            for _ in range(launches):
+                f()
+            b.record()
+            torch.cuda.synchronize()
+            us[k].append(a.elapsed_time(b) * 1e3 / launches)
+    # the loss the two agree on (the project's 1e-5 bar), as a check that both saw the same data
+    accum.zero_()
+    forms["mse_grad"]()
+    forms["eval_rows"]()
+    torch.cuda.synchronize()
+    la, lb = float(accum), float(loss_rows.double().sum()) / B
+    assert abs(la - lb) <= 1e-5 * abs(la), (la, lb)
+    em, mm = statistics.median(us["eval_rows"]), statistics.median(us["mse_grad"])
+    spread = max(us["mse_grad"]) - min(us["mse_grad"])
+    return dict(part="kernel", workload=name, dtype="bf16", loss=loss, rows=B, cols=pix, rounds=reps, launches_per_round=launches,
+                eval_rows_us=_stats(us["eval_rows"]), mse_grad_us=_stats(us["mse_grad"]), eval_minus_mse_us=round(em - mm, 3),
+                mse_grad_spread_us=round(spread, 3), within=bool(em - mm <= spread),
+                bytes=dict(eval_rows=B * pix * 4 + B * 20, mse_grad=B * pix * 5), eval_rows_GBps=round((B * pix * 4 + B * 20) / em / 1e3, 1),
+                mse_grad_GBps=round(B * pix * 5 / mm / 1e3, 1), mean_loss=la)
+
+
+class _NoTrain:
+    """The stepper of a pass that only validates: the training steps do nothing, the loss is the engine's accumulator."""
+
+    def __init__(self, eng):
+        self.eng = eng
+
+    def step_rows(self, *a, **k):
+        pass
+
+    step = step_rows
+
+    def global_loss(self):
+        return self.eng.read_loss()
+
+
+class _Order:
+    def __init__(self, val_rows):
+        self.train_size, self.val_size, self._val = 1, val_rows.numel(), val_rows
+
+    def train_epoch(self):
+        return torch.zeros(1, dtype=torch.int64)
+
+    def val_epoch(self):
+        return self._val
+
+
+class _Model:
+    """What _run_epoch asks of a model, around any engine."""
+
+    def __init__(self, eng):
+        self.engine, self._steps = eng, 0
+
+    def train(self):
+        pass
+
+    eval = train
+
+    def _next_step(self):
+        self._steps += 1
+        return self._steps
+
+
+def loop_part(name, reps, val_batches, loss="mse", k=8):
+    eng, x, font, t8 = setup(name, loss)
+    B, pix = t8.shape
+    eng.bind_dataset(x, t8, font=font)                      # the batch as the data set, walked val_batches times in a seeded order
+    g = torch.Generator().manual_seed(7)
+    order = _Order(torch.cat([torch.randperm(B, generator=g) for _ in range(val_batches)]))
+    model, stepper = _Model(eng), _NoTrain(eng)
+
+    def run(on):
+        rep = M._ValReport(k, eng.device) if on else None
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        _, val = M._run_epoch(model, stepper, order, x, t8, B, M.LEARNING_RATE, 0, 1, by_rows=True, report=rep)
+        if rep is not None:
+            rep.line(pix)                                   # the report's own device-to-host reads belong to its cost
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, val
+
+    for on in (False, True):
+        run(on)
+    ms, vals = {False: [], True: []}, set()
+    for _ in range(reps):
+        for on in (False, True):
+            t, v = run(on)
+            ms[on].append(t)
+            vals.add(v)
+    assert len(vals) == 1 and eng.error_flags() == 0        # the validation loss is the same with and without the report
+    return dict(part="loop", workload=name, dtype="bf16", loss=loss, batch=B, val_batches=val_batches, worst_k=k, rounds=reps,
+                val_pass_ms_off=_stats(ms[False]), val_pass_ms_on=_stats(ms[True]),
+                on_over_off=round(statistics.median(ms[True]) / statistics.median(ms[False]), 4), val_loss=vals.pop())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", default="r0,c3")
+    ap.add_argument("--loss", default="mse", choices=["mse", "bce"])
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--launches", type=int, default=20)
+    ap.add_argument("--val-batches", type=int, default=8)
+    ap.add_argument("--out", default=None, help="append the JSON lines to this file too")
+    a = ap.parse_args()
+    torch.cuda.set_device(0)
+    for name in a.cases.split(","):
+        for line in (kernel_part(name, a.reps, a.launches, a.loss), loop_part(name, a.reps, a.val_batches, a.loss)):
+            print(json.dumps(line), flush=True)
+            if a.out:
+                os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                with open(a.out, "a") as f:
+                    f.write(json.dumps(line) + "\n")
+            torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
