@@ -17,6 +17,7 @@ AFR_LOSS_MSE, AFR_LOSS_BCE = 0, 1
 LOSS_KINDS = {"mse": AFR_LOSS_MSE, "bce": AFR_LOSS_BCE}
 AFR_OPT_ADAMW, AFR_OPT_LION = 0, 1
 OPT_KINDS = {"adamw": AFR_OPT_ADAMW, "lion": AFR_OPT_LION}
+STAT_KINDS = {"params": 0, "grads": 1, "exp_avg": 2, "exp_avg_sq": 3, "ema": 4}      # AFR_STAT_*: the buffer afr_tensor_stats reads
 
 AFR_OK, AFR_EINVAL, AFR_ESTATE, AFR_EHIP, AFR_EUNSUPPORTED = 0, -1, -2, -3, -4
 
@@ -54,6 +55,11 @@ class AfrConfig(C.Structure):
 class AfrOptRange(C.Structure):
     """One merged range of the optimizer groups (include/afr.h afr_opt_range): flat elements up to `end` take these multipliers."""
     _fields_ = [("end", C.c_int64), ("lr_mult", C.c_float), ("wd_mult", C.c_float)]
+
+
+class AfrTensorSeg(C.Structure):
+    """One tensor of afr_op_tensor_stats' host table (include/afr.h afr_tensor_seg): numel elements from element off (a multiple of 4)."""
+    _fields_ = [("off", C.c_int64), ("numel", C.c_int64)]
 
 
 class AfrSheetParams(C.Structure):
@@ -111,6 +117,8 @@ SIGNATURES = {
     "afr_train_step_rows": (_i32, [_vp, _vp, _i32, _i64, _vp, _u64, _i32, _f32, _f32, _f32, _f32, _f32, _i64, _vp]),
     "afr_eval": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "afr_eval_rows": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "afr_tensor_stats_chunk": (_i32, []),
+    "afr_tensor_stats": (_i32, [_vp, _i32, _vp, _vp, _vp]),
     "afr_error_flags": (_i32, [_vp, _vp, C.POINTER(C.c_uint32)]),
     "afr_profile_dominant": (_i32, [_vp, _i32]),
     "afr_profile_read": (_i32, [_vp, C.c_char_p, _i32, C.POINTER(C.c_double), C.POINTER(_i64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -132,6 +140,8 @@ SIGNATURES = {
     "afr_op_mse_grad": (_i32, [_i32, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "afr_op_bce_grad": (_i32, [_i32, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "afr_op_eval": (_i32, [_i32, _i32, _vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "afr_op_tensor_stats_scratch_bytes": (_sz, [C.POINTER(AfrTensorSeg), _i32]),
+    "afr_op_tensor_stats": (_i32, [_vp, _vp, C.POINTER(AfrTensorSeg), _i32, _vp, _vp, _sz, _vp]),
     "afr_op_f32_to_bf16": (_i32, [_vp, _vp, _i64, _vp]),
     "afr_op_f32_to_fp8": (_i32, [_vp, _vp, _i64, _f32, _vp]),
     "afr_op_gemm_fp8": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),

@@ -148,6 +148,9 @@ struct afr_plan {
     std::vector<afr_opt_range> groups;
     std::vector<SumsqSeg> clip_segs;        // host copy of that table
     size_t o_clip = 0;
+    // per-tensor statistics (afr_tensor_stats): the partial records of launch 1, one per chunk of every tensor; tstats_ok is false
+    // for a table the kernels do not take (more than 256 tensors, or one of 2^32 elements or more) and nothing is carved then
+    size_t o_tstats = 0; bool tstats_ok = false;
     // weight EMA (afr_set_ema): E = the caller's buffer in the parameter layout (NULL = off), updated by every ema_every-th optimizer
     // step of the plan (ema_count of them since afr_set_ema).  ema_on (afr_use_ema): P and E have changed places, the forward
     // entry points read the EMA weights and every call that trains or steps is refused.
@@ -430,6 +433,12 @@ extern "C" int afr_plan_create(const afr_config* c, afr_plan** out) {
     p->o_sfont = carve(B * sizeof(int64_t));
     for (const Tensor& t : p->params) p->clip_segs.push_back(SumsqSeg{(long long)t.off, (long long)t.numel});
     p->o_clip = carve(CLIP_WS_TABLE * sizeof(float) + p->clip_segs.size() * sizeof(SumsqSeg));
+    {   // the statistics' partials, behind everything else: no existing offset moves
+        long long chunks = 0;
+        p->tstats_ok = p->clip_segs.size() <= (size_t)AFR_TSTATS_MAX_SEGS;
+        for (const SumsqSeg& sg : p->clip_segs) { chunks += afr_tstats_seg_blocks(sg.numel); if (sg.numel > 0xffffffffll) p->tstats_ok = false; }
+        if (p->tstats_ok) p->o_tstats = carve((size_t)chunks * sizeof(afr_tensor_stat));
+    }
     p->ws_need = off;
     *out = p;
     return AFR_OK;
@@ -1496,6 +1505,64 @@ extern "C" int afr_grad_sumsq(afr_plan* p, int64_t offset, int64_t n, float* out
     if (!p->G || !p->ws) return fail(AFR_ESTATE, "plan has no bound gradient buffer");
     DevGuard dg(p->device);
     return grad_sumsq_impl(p, offset, offset + n, out, nullptr, 1.f, nullptr, (hipStream_t)stream);
+}
+// ---- per-tensor statistics (include/afr.h): every check first, then elementwise.hip's pair of launches
+extern "C" int afr_tensor_stats_chunk(void) { return AFR_TSTATS_CHUNK; }
+extern "C" int afr_tensor_stats(afr_plan* p, int which, const float* minus, afr_tensor_stat* out, void* stream) {
+    if (!p) return fail(AFR_EINVAL, "null plan");
+    if (!out || ((uintptr_t)out & 15)) return fail(AFR_EINVAL, "afr_tensor_stats: out must be a 16-byte aligned device buffer of afr_param_count() records");
+    if ((uintptr_t)minus & 15) return fail(AFR_EINVAL, "afr_tensor_stats: minus must be 16-byte aligned");
+    const float* a = nullptr;
+    const char* what = nullptr;
+    switch (which) {
+        case AFR_STAT_PARAMS: a = p->P; what = "parameters"; break;
+        case AFR_STAT_GRADS: a = p->G; what = "gradients"; break;
+        case AFR_STAT_EXP_AVG: a = p->M; what = "exp_avg"; break;
+        case AFR_STAT_EXP_AVG_SQ: a = p->V; what = "exp_avg_sq"; break;
+        case AFR_STAT_EMA: a = p->E; what = "EMA (afr_set_ema)"; break;
+        default: return fail(AFR_EINVAL, "afr_tensor_stats: which must be one of AFR_STAT_* (0..4), got %d", which);
+    }
+    if (!p->ws) return fail(AFR_ESTATE, "afr_tensor_stats: the plan has no bound buffers (afr_bind)");
+    if (!a) return fail(AFR_ESTATE, "afr_tensor_stats: the plan has no %s buffer", what);
+    if (!p->tstats_ok) return fail(AFR_EUNSUPPORTED, "afr_tensor_stats: at most %d tensors of fewer than 2^32 elements each", AFR_TSTATS_MAX_SEGS);
+    DevGuard dg(p->device);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(p, s, "tensor_stats", 4.0 * (double)p->total, (minus ? 8.0 : 4.0) * (double)p->total);
+    HIPCHK(afr_launch_tensor_stats(a, minus, (const SumsqSeg*)((float*)(p->ws + p->o_clip) + CLIP_WS_TABLE), p->clip_segs.data(), (int)p->clip_segs.size(),
+                                   out, (afr_tensor_stat*)(p->ws + p->o_tstats), s));
+    return AFR_OK;
+}
+// the table checks of the op entry: AFR_OK, or the code with the message set
+static int tstats_check_segs(const afr_tensor_seg* segs, int nseg) {
+    if (nseg < 1 || nseg > AFR_TSTATS_MAX_SEGS) return fail(AFR_EINVAL, "afr_op_tensor_stats: nseg = %d must lie in 1..%d", nseg, AFR_TSTATS_MAX_SEGS);
+    if (!segs) return fail(AFR_EINVAL, "afr_op_tensor_stats: segs is null");
+    for (int k = 0; k < nseg; ++k) {
+        if (segs[k].off < 0 || (segs[k].off & 3)) return fail(AFR_EINVAL, "afr_op_tensor_stats: segs[%d].off = %lld must be a multiple of 4 and >= 0", k, (long long)segs[k].off);
+        if (segs[k].numel < 0) return fail(AFR_EINVAL, "afr_op_tensor_stats: segs[%d].numel = %lld is negative", k, (long long)segs[k].numel);
+    }
+    for (int k = 0; k < nseg; ++k)
+        if (segs[k].numel > 0xffffffffll || (segs[k].off >> 2) > 0xffffffffll)
+            return fail(AFR_EUNSUPPORTED, "afr_op_tensor_stats: segs[%d] has 2^32 elements or more, or starts at 2^34 or beyond", k);
+    return AFR_OK;
+}
+extern "C" size_t afr_op_tensor_stats_scratch_bytes(const afr_tensor_seg* segs, int nseg) {
+    if (tstats_check_segs(segs, nseg)) return 0;
+    long long chunks = 0;
+    for (int k = 0; k < nseg; ++k) chunks += afr_tstats_seg_blocks(segs[k].numel);
+    return (size_t)chunks * sizeof(afr_tensor_stat);
+}
+extern "C" int afr_op_tensor_stats(const float* a, const float* minus, const afr_tensor_seg* segs, int nseg, afr_tensor_stat* out, void* scratch,
+                                   size_t scratch_bytes, void* stream) {
+    if (!a || !out || !scratch) return fail(AFR_EINVAL, "afr_op_tensor_stats: a, out and scratch are required");
+    if (((uintptr_t)a | (uintptr_t)minus | (uintptr_t)out | (uintptr_t)scratch) & 15) return fail(AFR_EINVAL, "afr_op_tensor_stats: a, minus, out and scratch must be 16-byte aligned");
+    if (int rc = tstats_check_segs(segs, nseg)) return rc;
+    const size_t need = afr_op_tensor_stats_scratch_bytes(segs, nseg);
+    if (scratch_bytes < need) return fail(AFR_EINVAL, "afr_op_tensor_stats: scratch too small: %zu < %zu", scratch_bytes, need);
+    SumsqSeg tab[AFR_TSTATS_MAX_SEGS];
+    for (int k = 0; k < nseg; ++k) tab[k] = SumsqSeg{(long long)segs[k].off, (long long)segs[k].numel};
+    DevGuard dg(device_of(a));
+    HIPCHK(afr_launch_tensor_stats(a, minus, nullptr, tab, nseg, out, (afr_tensor_stat*)scratch, (hipStream_t)stream));
+    return AFR_OK;
 }
 extern "C" int afr_set_optimizer(afr_plan* p, int kind) {
     if (!p) return fail(AFR_EINVAL, "null plan");

@@ -341,6 +341,20 @@ constexpr int AFR_SUMSQ_MAX_BLOCKS = 1024, AFR_SUMSQ_COUNTER = 1024, AFR_SUMSQ_S
 hipError_t afr_launch_grad_sumsq(const float* g, const SumsqSeg* segs /* device */, const SumsqSeg* segs_host /* the same table */, int nseg,
                                  long long lo, long long hi, float* scratch, float* out, float* stats, float grad_scale, float max_norm,
                                  uint32_t* err, hipStream_t s);
+// Per-tensor statistics (elementwise.hip tstats_partial_kernel + tstats_finish_kernel; include/afr.h afr_tensor_stats): one
+// afr_tensor_stat per (offset, numel) segment of a, or of a - minus (minus NULL: none), the padding between segments never read.
+// Launch 1: one block per chunk of AFR_TSTATS_CHUNK elements of ONE segment (max(1, ceil(numel / CHUNK)) blocks per segment), one
+// 32-byte partial record per block into `partial`; launch 2: one wave per segment adds its partials in chunk order.  The segment
+// table reaches the kernels either as a device array (segs_dev: the plan's) or by value, built from segs_host (segs_dev NULL).
+// segs_host is always given: the host needs the block counts.  The callers (afr_api.hip) have checked pointers, alignment and the table.
+constexpr int AFR_TSTATS_CHUNK = 32768, AFR_TSTATS_MAX_SEGS = 256;
+struct afr_tensor_stat;
+static inline long long afr_tstats_seg_blocks(long long numel) {
+    const long long nb = (numel + AFR_TSTATS_CHUNK - 1) / AFR_TSTATS_CHUNK;
+    return nb ? nb : 1;
+}
+hipError_t afr_launch_tensor_stats(const float* a, const float* minus, const SumsqSeg* segs_dev, const SumsqSeg* segs_host, int nseg,
+                                   afr_tensor_stat* out, afr_tensor_stat* partial, hipStream_t s);
 // loss: u (act dtype) [rows][cols] -> du in place or to `du`; per-block partial sums to scratch, then
 // a 1-block finisher adds sum(scratch) to *loss_accum (deterministic order).
 int afr_mse_blocks(long long rows, long long cols);

@@ -443,6 +443,187 @@ hipError_t afr_launch_grad_sumsq(const float* g, const SumsqSeg* segs, const Sum
     return hipGetLastError();
 }
 
+// ----------------------------------------------------------------------- per-tensor statistics
+// One afr_tensor_stat (include/afr.h) per segment of the same (offset, numel) table: sum of x^2 and of x over the FINITE elements,
+// their minimum and maximum, and the counts of NaN, infinite and zero elements; x = a[i], or a[i] - minus[i] in f32.  Only the
+// segments' elements are read, never the padding between them.  Two launches, no atomics, no communication between blocks:
+//   tstats_partial_kernel  a block owns ONE chunk of AFR_TSTATS_CHUNK elements of ONE segment (a segment of n elements has
+//       max(1, ceil(n / CHUNK)) chunks; the block finds its pair by grad_sumsq_kernel's count).  Lane l takes the float4 l, l + 256,
+//       ... of the chunk in ascending order, 16-byte loads, four in flight (eight with minus); component c of every float4 goes to
+//       the lane's accumulator pair c: q_c = fmaf(x, x, q_c), s_c = s_c + x.  The <= 3 elements behind the segment's last whole
+//       float4 are loaded as scalars by lanes 0..2 of the segment's LAST chunk, into pair 0, after that lane's float4s.  Then
+//       (q0 + q1) + (q2 + q3), likewise s; the wave butterfly (offsets 32, 16, 8, 4, 2, 1); the four waves through LDS as
+//       (w0 + w1) + (w2 + w3); one 32-byte record per block, a plain vector store.
+//   tstats_finish_kernel   one wave per segment: lane l adds the partials of chunks l, l + 64, ... in ascending order, then the
+//       same butterfly, and lane 0 writes the record.
+// A record therefore depends on its segment's elements only -- not on the offset, the other segments or the grid -- and repeats
+// bit for bit.  Classification is by bit pattern (exponent all ones: infinity or NaN; no bit below the sign: zero), so the counts
+// do not depend on the denormal mode; minimum and maximum are taken on an order-preserving integer key of the bits for the same
+// reason (and come out as -0 < +0).  A non-finite element adds 0 to both sums and leaves minimum and maximum alone.
+static_assert(AFR_TSTATS_MAX_SEGS == SUMSQ_MAX_SEGS, "one table serves the norm and the statistics");
+static_assert(sizeof(afr_tensor_stat) == 32 && AFR_TSTATS_CHUNK % (4 * 4 * 256) == 0, "two 16-byte stores per record; whole trips of four loads");
+constexpr int TSTATS_C4 = AFR_TSTATS_CHUNK / 4;                          // float4 per chunk
+// the segment table as the kernels take it: the plan's device array, or by value (offsets in float4, both 32-bit: 2 KiB of argument)
+struct TStatTabDev { const SumsqSeg* segs; };
+struct TStatTabVal { unsigned off4[AFR_TSTATS_MAX_SEGS], numel[AFR_TSTATS_MAX_SEGS]; };
+__device__ __forceinline__ void tstat_seg(const TStatTabDev& t, int k, long long& off, unsigned& n) { const SumsqSeg sg = t.segs[k]; off = sg.off; n = (unsigned)sg.numel; }
+__device__ __forceinline__ void tstat_seg(const TStatTabVal& t, int k, long long& off, unsigned& n) { off = 4ll * t.off4[k]; n = t.numel[k]; }
+__device__ __forceinline__ unsigned tstat_chunks(unsigned n) { return n ? (unsigned)(((unsigned long long)n + AFR_TSTATS_CHUNK - 1) / AFR_TSTATS_CHUNK) : 1u; }
+// unsigned key with the order of the floats (-inf < -FLT_MAX < -0 < +0 < FLT_MAX < +inf; NaNs beyond either infinity), and back
+__device__ __forceinline__ unsigned tstat_key(unsigned bits) { return bits ^ ((unsigned)((int)bits >> 31) | 0x80000000u); }
+__device__ __forceinline__ unsigned tstat_unkey(unsigned k) { return (k & 0x80000000u) ? k ^ 0x80000000u : ~k; }
+constexpr unsigned TSTAT_KEY_LOWEST = 0x00800000u, TSTAT_KEY_HIGHEST = 0xff7fffffu;      // the keys of -FLT_MAX and FLT_MAX
+struct TStatAcc {
+    float q[4] = {0.f, 0.f, 0.f, 0.f}, s[4] = {0.f, 0.f, 0.f, 0.f};
+    unsigned kmin = 0xffffffffu, kmax = 0u, n_nan = 0u, n_inf = 0u, n_zero = 0u;
+    __device__ __forceinline__ void add(float x, int c) {
+        const unsigned bits = __float_as_uint(x), mag = bits & 0x7fffffffu;
+        const bool fin = mag < 0x7f800000u;
+        const float xf = fin ? x : 0.f;
+        q[c] = __builtin_fmaf(xf, xf, q[c]);
+        s[c] += xf;
+        const unsigned k = tstat_key(bits);
+        kmin = min(kmin, fin ? k : 0xffffffffu);
+        kmax = max(kmax, fin ? k : 0u);
+        n_nan += mag > 0x7f800000u; n_inf += mag == 0x7f800000u; n_zero += mag == 0u;
+    }
+    __device__ __forceinline__ void add4(const float4& v) { add(v.x, 0); add(v.y, 1); add(v.z, 2); add(v.w, 3); }
+};
+__device__ __forceinline__ unsigned wave_sum_u(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
+    return v;
+}
+__device__ __forceinline__ unsigned wave_min_u(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, (unsigned)__shfl_xor((int)v, o, 64));
+    return v;
+}
+__device__ __forceinline__ unsigned wave_max_u(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o, 64));
+    return v;
+}
+// the record of (sums, keys, counts): minimum +inf / maximum -inf when no finite element was met
+__device__ __forceinline__ void tstat_store(afr_tensor_stat* dst, float q, float s, unsigned kmin, unsigned kmax, unsigned n_nan, unsigned n_inf,
+                                            unsigned n_zero, unsigned numel) {
+    const unsigned mn = kmin > TSTAT_KEY_HIGHEST ? 0x7f800000u : tstat_unkey(kmin), mx = kmax < TSTAT_KEY_LOWEST ? 0xff800000u : tstat_unkey(kmax);
+    uint4* d = reinterpret_cast<uint4*>(dst);
+    d[0] = make_uint4(__float_as_uint(q), __float_as_uint(s), mn, mx);
+    d[1] = make_uint4(n_nan, n_inf, n_zero, numel);
+}
+template <bool MINUS, class Tab>
+__global__ __launch_bounds__(256) void tstats_partial_kernel(const float* __restrict__ a, const float* __restrict__ minus, Tab tab, int nseg,
+                                                             afr_tensor_stat* __restrict__ partial) {
+    __shared__ long long sb[AFR_TSTATS_MAX_SEGS];                     // the segments: first element, elements
+    __shared__ unsigned sn[AFR_TSTATS_MAX_SEGS];
+    __shared__ float shf[2][4];
+    __shared__ unsigned shu[5][4];
+    if ((int)threadIdx.x < nseg) {
+        long long off;
+        unsigned numel;
+        tstat_seg(tab, threadIdx.x, off, numel);
+        sb[threadIdx.x] = off; sn[threadIdx.x] = numel;
+    }
+    __syncthreads();
+    long long j = blockIdx.x, base = 0;                               // (the grid is the sum of the counts: every block finds its pair)
+    unsigned n = 0;
+    for (int k = 0; k < nseg; ++k) {
+        const unsigned nb = tstat_chunks(sn[k]);
+        if (j < nb) { base = sb[k]; n = sn[k]; break; }
+        j -= nb;
+    }
+    const long long n4 = n >> 2, c0 = j * TSTATS_C4, c1 = min(n4, c0 + TSTATS_C4);      // this chunk's float4s: [c0, c1)
+    const float4* src = reinterpret_cast<const float4*>(a + base);
+    const float4* sub = MINUS ? reinterpret_cast<const float4*>(minus + base) : nullptr;
+    auto diff = [](float4 v, const float4& w) { v.x -= w.x; v.y -= w.y; v.z -= w.z; v.w -= w.w; return v; };
+    TStatAcc acc;
+    long long i = c0 + threadIdx.x;
+    if (c1 - c0 == TSTATS_C4) {                                       // a whole chunk: unconditional loads
+        for (int t = 0; t < TSTATS_C4 / 256; t += 4, i += 4 * 256) {
+            float4 v[4], w[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = src[i + u * 256];
+            if constexpr (MINUS) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) w[u] = sub[i + u * 256];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc.add4(MINUS ? diff(v[u], w[u]) : v[u]);
+        }
+    } else {
+        for (; i < c1; i += 256) acc.add4(MINUS ? diff(src[i], sub[i]) : src[i]);
+    }
+    const long long last0 = (long long)(tstat_chunks(n) - 1) * AFR_TSTATS_CHUNK;      // first element of the segment's last chunk
+    const long long t = (n4 << 2) + threadIdx.x;                      // tail: lanes 0..2 of that chunk's block
+    if (j * (long long)AFR_TSTATS_CHUNK == last0 && t < n) acc.add(MINUS ? a[base + t] - minus[base + t] : a[base + t], 0);
+    const long long e0 = j * (long long)AFR_TSTATS_CHUNK;
+    const unsigned mine = n > e0 ? (unsigned)min((long long)AFR_TSTATS_CHUNK, (long long)n - e0) : 0u;      // elements of this chunk
+
+    const float q = wave_sum((acc.q[0] + acc.q[1]) + (acc.q[2] + acc.q[3])), s = wave_sum((acc.s[0] + acc.s[1]) + (acc.s[2] + acc.s[3]));
+    const unsigned kmin = wave_min_u(acc.kmin), kmax = wave_max_u(acc.kmax);
+    const unsigned n_nan = wave_sum_u(acc.n_nan), n_inf = wave_sum_u(acc.n_inf), n_zero = wave_sum_u(acc.n_zero);
+    if ((threadIdx.x & 63) == 0) {
+        const int w = threadIdx.x >> 6;
+        shf[0][w] = q; shf[1][w] = s;
+        shu[0][w] = kmin; shu[1][w] = kmax; shu[2][w] = n_nan; shu[3][w] = n_inf; shu[4][w] = n_zero;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        tstat_store(partial + blockIdx.x, (shf[0][0] + shf[0][1]) + (shf[0][2] + shf[0][3]), (shf[1][0] + shf[1][1]) + (shf[1][2] + shf[1][3]),
+                    min(min(shu[0][0], shu[0][1]), min(shu[0][2], shu[0][3])), max(max(shu[1][0], shu[1][1]), max(shu[1][2], shu[1][3])),
+                    (shu[2][0] + shu[2][1]) + (shu[2][2] + shu[2][3]), (shu[3][0] + shu[3][1]) + (shu[3][2] + shu[3][3]),
+                    (shu[4][0] + shu[4][1]) + (shu[4][2] + shu[4][3]), mine);
+}
+template <class Tab>
+__global__ __launch_bounds__(256) void tstats_finish_kernel(Tab tab, int nseg, const afr_tensor_stat* __restrict__ partial,
+                                                            afr_tensor_stat* __restrict__ out) {
+    const int lane = threadIdx.x & 63, t = blockIdx.x * 4 + (threadIdx.x >> 6);      // one wave per segment
+    if (t >= nseg) return;
+    long long off;
+    unsigned n, first = 0;                                            // first: the chunks of the segments in front of t
+    for (int k = lane; k < t; k += 64) { tstat_seg(tab, k, off, n); first += tstat_chunks(n); }
+    first = wave_sum_u(first);
+    tstat_seg(tab, t, off, n);
+    const unsigned chunks = tstat_chunks(n);
+    float q = 0.f, s = 0.f;
+    unsigned kmin = 0xffffffffu, kmax = 0u, n_nan = 0u, n_inf = 0u, n_zero = 0u, numel = 0u;
+    for (unsigned c = lane; c < chunks; c += 64) {
+        const uint4* r = reinterpret_cast<const uint4*>(partial + first + c);
+        const uint4 lo = r[0], hi = r[1];
+        q += __uint_as_float(lo.x); s += __uint_as_float(lo.y);
+        kmin = min(kmin, tstat_key(lo.z)); kmax = max(kmax, tstat_key(lo.w));
+        n_nan += hi.x; n_inf += hi.y; n_zero += hi.z; numel += hi.w;
+    }
+    q = wave_sum(q); s = wave_sum(s);
+    kmin = wave_min_u(kmin); kmax = wave_max_u(kmax);
+    n_nan = wave_sum_u(n_nan); n_inf = wave_sum_u(n_inf); n_zero = wave_sum_u(n_zero); numel = wave_sum_u(numel);
+    if (lane == 0) tstat_store(out + t, q, s, kmin, kmax, n_nan, n_inf, n_zero, numel);
+}
+hipError_t afr_launch_tensor_stats(const float* a, const float* minus, const SumsqSeg* segs_dev, const SumsqSeg* segs_host, int nseg,
+                                   afr_tensor_stat* out, afr_tensor_stat* partial, hipStream_t s) {
+    if (nseg < 1 || nseg > AFR_TSTATS_MAX_SEGS) return hipErrorInvalidValue;
+    long long blocks = 0;
+    TStatTabVal val;
+    for (int k = 0; k < nseg; ++k) {
+        const SumsqSeg& sg = segs_host[k];
+        if (sg.off < 0 || (sg.off & 3) || (sg.off >> 2) > 0xffffffffll || sg.numel < 0 || sg.numel > 0xffffffffll) return hipErrorInvalidValue;
+        val.off4[k] = (unsigned)(sg.off >> 2); val.numel[k] = (unsigned)sg.numel;
+        blocks += afr_tstats_seg_blocks(sg.numel);
+    }
+    if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
+    auto go = [&](const auto& tab) {
+        using Tab = std::decay_t<decltype(tab)>;
+        with_bool(minus != nullptr, [&](auto m) {
+            hipLaunchKernelGGL((tstats_partial_kernel<m(), Tab>), dim3((unsigned)blocks), dim3(256), 0, s, a, minus, tab, nseg, partial);
+        });
+        if (hipError_t e = hipGetLastError()) return e;           // (no finish over partials that were never written)
+        hipLaunchKernelGGL((tstats_finish_kernel<Tab>), dim3((unsigned)((nseg + 3) / 4)), dim3(256), 0, s, tab, nseg, partial, out);
+        return hipGetLastError();
+    };
+    return segs_dev ? go(TStatTabDev{segs_dev}) : go(val);
+}
+
 // ------------------------------------------------------------------------------- f32 -> bf16
 __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst,
                                                           long long n) {

@@ -76,6 +76,39 @@ class EvalResult:
         return EvalResult(j([r.loss_rows for r in parts]), j([r.stats for r in parts]), j([r.u8 for r in parts]))
 
 
+class TensorStats:
+    """What Engine.tensor_stats returns: one record per parameter tensor (include/afr.h afr_tensor_stat).  raw is the [n, 8] int32
+    tensor the library wrote, on the device (the engine keeps one per kind of request and writes the next request of that kind into
+    it again: read it before asking once more); names the tensor names in the same order.  cpu() makes the one synchronising copy and
+    returns self; after it sumsq, sum, min, max (float32) and n_nan, n_inf, n_zero, numel (uint32) are numpy views of that copy."""
+    FLOATS, COUNTS = ("sumsq", "sum", "min", "max"), ("n_nan", "n_inf", "n_zero", "numel")
+
+    def __init__(self, raw, names):
+        self.raw, self.names, self._host = raw, list(names), None
+
+    def cpu(self):
+        if self._host is None:
+            a = self.raw.cpu().numpy() if isinstance(self.raw, torch.Tensor) else np.asarray(self.raw)
+            if a.dtype != np.int32 or a.ndim != 2 or a.shape != (len(self.names), 8):
+                raise ValueError(f"expected an int32 array of shape ({len(self.names)}, 8), got {a.dtype} {a.shape}")
+            self._host = np.ascontiguousarray(a)
+            f, u = self._host.view(np.float32), self._host.view(np.uint32)
+            for i, k in enumerate(self.FLOATS):
+                setattr(self, k, f[:, i])
+            for i, k in enumerate(self.COUNTS):
+                setattr(self, k, u[:, 4 + i])
+        return self
+
+    def norm(self):
+        """sqrt(sumsq) per tensor, float64."""
+        return np.sqrt(self.cpu().sumsq.astype(np.float64))
+
+    def nonfinite(self):
+        """The names of the tensors that hold a NaN or an infinity."""
+        h = self.cpu()
+        return [nm for nm, a, b in zip(self.names, h.n_nan, h.n_inf) if int(a) + int(b) > 0]
+
+
 class Engine:
     """One plan + its device buffers.  `params[name]` are views into the flat float32 buffer in
     state_dict order, so checkpoints interchange with the reference (helpers.py:76-105)."""
@@ -138,6 +171,7 @@ class Engine:
         self.t = 0            # AdamW step counter (model.py:310)
         self._keep = None     # keeps the last inputs alive until backward has consumed them
         self._last_B = 0      # batch rows of the last forward / forward_rows (evaluate_last)
+        self._tstats = {}     # tensor_stats: the record buffers, allocated once per kind of request
         if self.ema_decay is not None:
             self.set_ema(self.ema_decay, self.ema_every)
         if lr_mult is not None or wd_mult is not None:
@@ -316,6 +350,27 @@ class Engine:
             out = torch.empty(1, dtype=torch.float32, device=self.device)
         self._call(self.lib.afr_grad_sumsq, self._plan, int(offset), n, _ptr(out))
         return out
+
+    def tensor_stats(self, which="grads", minus=None):
+        """Per-tensor statistics of a flat buffer, computed on the device in two launches (include/afr.h afr_tensor_stats): sum of
+        squares, sum, minimum and maximum over the finite elements and the counts of NaN, infinite and zero elements of every
+        parameter tensor, the padding between tensors never read.  which: "params" | "grads" | "exp_avg" | "exp_avg_sq" | "ema".
+        minus: a float32 device tensor of n_flat elements in the flat layout; the statistics are then those of buffer - minus.  The
+        update norm of a step: snap = eng.flat_params.clone(); the step; eng.tensor_stats("params", minus=snap).norm().
+        Nothing is copied or synchronised until the result's cpu().  Which gradients the buffer holds after a fused optimizer step
+        is described in the header."""
+        if which not in _lib.STAT_KINDS:
+            raise ValueError(f"which must be one of {sorted(_lib.STAT_KINDS)}, got {which!r}")
+        if minus is not None and (not isinstance(minus, torch.Tensor) or minus.dtype != torch.float32 or minus.device != self.device or
+                                  minus.numel() != self.n_flat or not minus.is_contiguous()):
+            raise ValueError(f"minus must be a contiguous float32 tensor of {self.n_flat} elements on {self.device}")
+        key = (which, minus is not None)
+        if key not in self._tstats:
+            with torch.cuda.device(self.device):
+                self._tstats[key] = torch.empty((len(self.layout), 8), dtype=torch.int32, device=self.device)
+        self._call(self.lib.afr_tensor_stats, self._plan, _lib.STAT_KINDS[which], _ptr(minus), _ptr(self._tstats[key]))
+        self._keep_minus = minus
+        return TensorStats(self._tstats[key], [nm for nm, _, _, _ in self.layout])
 
     def _read_clip_stats(self):
         if self._clip_stats is None or not self.max_grad_norm:

@@ -33,7 +33,15 @@ What is deliberately different from the reference, and why:
   * AFR_VAL_REPORT=<k> (k >= 1) adds a validation report, counted on the device (Engine.evaluate_last): on the epochs that print a
     status line, one more line with the rates of pixels whose 8-bit level is off by >= 1 and by >= 2 and of wrong-ink pixels, the
     largest level difference and the k validation sheets with the largest loss, whose predicted bitmaps are written as
-    epoch_<e>/val_worst_<j>.bmp.  Unset: nothing changes.
+    epoch_<e>/val_worst_<j>.bmp.  Unset: nothing changes;
+  * AFR_TENSOR_REPORT=1 adds a per-tensor report, computed on the device (Engine.tensor_stats): on the epochs that print a status
+    line, rank 0 prints a block headed "Tensor report:" with one line per parameter tensor -- the weight norm |p|, the gradient norm
+    |g|, |g|/|p|, the fraction of gradient elements that are exactly zero, the relative size |dp|/|p| of the epoch's last optimizer
+    step and the non-finite counts when there are any -- and one more line when the output head is dead (every gradient of
+    fc_output.weight zero).  The gradients are those of a probe: one forward + backward on rank 0's shard of the epoch's first
+    training batch after the validation pass, with a dropout step of its own, no optimizer step, and its loss discarded; the step
+    size comes from a snapshot of the weights taken before the epoch's last training batch.  Neither changes the run: every artefact
+    and every other line is what it is without the variable.  Unset: nothing changes.
 """
 import contextlib
 import datetime
@@ -103,6 +111,79 @@ def _val_report_from_env():
 
 
 VAL_REPORT = _val_report_from_env()     # read at import, like the settings above: a bad value stops the run before it starts
+
+
+def _tensor_report_from_env():
+    """AFR_TENSOR_REPORT = "1": the per-tensor report; unset or empty -> False (off).  Anything else is a ValueError."""
+    spec = os.environ.get("AFR_TENSOR_REPORT", "").strip()
+    if spec not in ("", "1"):
+        raise ValueError(f"AFR_TENSOR_REPORT must be 1 (print the per-tensor report) or unset, got {spec!r}")
+    return spec == "1"
+
+
+TENSOR_REPORT = _tensor_report_from_env()     # likewise read at import
+
+
+def _tensor_report_lines(p, g, d):
+    """The block AFR_TENSOR_REPORT prints, as a list of lines.  p, g, d: the statistics of the weights, of the probe's gradients and of
+    the last step's weight difference (TensorStats after cpu(), or anything with names, sumsq, n_nan, n_inf, n_zero, numel)."""
+    def norm(st, i):
+        return float(np.sqrt(np.float64(st.sumsq[i])))
+
+    def ratio(a, b):
+        return a / b if b > 0 else float("nan")
+
+    width = max(len(nm) for nm in p.names)
+    lines = ["Tensor report:"]
+    for i, nm in enumerate(p.names):
+        pn, gn, dn = norm(p, i), norm(g, i), norm(d, i)
+        line = (f"  {nm:<{width}}  |p| {pn:.4e}  |g| {gn:.4e}  |g|/|p| {ratio(gn, pn):.3e}  "
+                f"g zero {int(g.n_zero[i]) / max(1, int(g.numel[i])):.4f}  |dp|/|p| {ratio(dn, pn):.3e}")
+        bad = [f"{tag} {int(st.n_nan[i])} nan {int(st.n_inf[i])} inf" for tag, st in (("p", p), ("g", g), ("dp", d))
+               if int(st.n_nan[i]) + int(st.n_inf[i]) > 0]
+        lines.append(line + ("  NON-FINITE: " + ", ".join(bad) if bad else ""))
+    if "fc_output.weight" in g.names:
+        i = g.names.index("fc_output.weight")
+        if int(g.n_zero[i]) == int(g.numel[i]):
+            lines.append("Tensor report: DEAD OUTPUT HEAD (every gradient of fc_output.weight is zero)")
+    return lines
+
+
+class _TensorReport:
+    """What AFR_TENSOR_REPORT gathers during one epoch, on rank 0 alone and with no collective: the statistics of the last training
+    step's weight difference (against a snapshot of the weights, allocated once per model) and those of the weights and of a probe's
+    gradients.  Nothing here steps, advances a counter the run reads, or leaves a loss behind."""
+
+    def __init__(self, model):
+        self.model, self.eng = model, model.engine
+        self.first = None                         # (this rank's rows of the epoch's first training batch, its mean_elems)
+        self.p = self.g = self.d = None
+
+    def before_last_step(self):
+        if getattr(self.model, "_tensor_snapshot", None) is None:
+            self.model._tensor_snapshot = torch.empty_like(self.eng.flat_params)
+        self.model._tensor_snapshot.copy_(self.eng.flat_params)
+
+    def after_last_step(self):
+        self.d = self.eng.tensor_stats("params", minus=self.model._tensor_snapshot)
+
+    def probe(self, inputs=None, targets=None):
+        """Forward + loss + backward of the first training batch's rows (by data-set rows, or dense when inputs are given); the dropout
+        step is the next one the model WOULD draw, passed explicitly: model._next_step() does not move."""
+        eng, (rows, me) = self.eng, self.first
+        step = self.model._steps + 1
+        if inputs is None:
+            eng.forward_loss_rows(rows, step=step, mean_elems=me)
+        else:
+            eng.forward_loss(inputs.index_select(0, rows), targets.index_select(0, rows), step=step, mean_elems=me)
+        eng.backward()
+        eng.read_loss(reset=True)                 # the probe's loss is nobody's
+        self.g = eng.tensor_stats("grads").cpu()
+        self.p = eng.tensor_stats("params").cpu()
+        self.d = self.d.cpu()
+
+    def lines(self):
+        return _tensor_report_lines(self.p, self.g, self.d)
 
 
 class _ValReport:
@@ -307,6 +388,11 @@ class AttentionFontRenderer(nn.Module):
         self._steps += 1
         return self._steps
 
+    def tensor_stats(self, which="grads", minus=None):
+        """Per-tensor statistics of the engine's flat buffer `which` (or of its difference to `minus`), computed on the device:
+        Engine.tensor_stats.  The record buffer is allocated once and reused."""
+        return self.engine.tensor_stats(which, minus)
+
     def render_u8(self, codes):
         """uint8 [B, SHEET_HEIGHT, SHEET_WIDTH] on the device: binary_array_to_image's levels of the eval-mode forward(codes), quantised
         by the library (Engine.render_u8) instead of on the host.  The same shape, shadow-refresh and index checks as forward."""
@@ -396,13 +482,15 @@ def _step_hyper(eng, lr):
     return lr, WEIGHT_DECAY
 
 
-def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True, report=None):
+def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True, report=None, treport=None):
     """One epoch of the reference loop (model.py:288-333): the training pass over order.train_epoch(), then the validation
     pass; returns the two means of per-batch mean losses.  An engine that keeps a weight EMA validates from it.  by_rows: the engine has the data set bound (Engine.bind_dataset)
     and every step is driven by this rank's slice of the epoch's index vector -- the kernels read the rows where they lie.
     by_rows=False gathers each batch with index_select and hands the step dense tensors (the form tools/epoch_bench.py
     measures the other against).  report: a _ValReport (AFR_VAL_REPORT) that every validation batch is evaluated into between its
-    forward and its loss; None: the pass as it always was."""
+    forward and its loss; None: the pass as it always was.  treport: a _TensorReport (AFR_TENSOR_REPORT, rank 0 only): the weights are
+    snapshotted before the last training batch and compared after it, and once the validation loss has been read the first training
+    batch is run once more as a probe for its gradients."""
     from .parallel import shard_rows
     eng = model.engine
     pixels = targets[0].numel()
@@ -414,10 +502,17 @@ def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, wor
         mine = rows[shard_rows(rows.numel(), rank, world)]
         step_lr, step_wd = _step_hyper(eng, lr)
         hyper = dict(step=model._next_step(), lr=step_lr, betas=ADAM_BETAS, weight_decay=step_wd)
+        if treport is not None:
+            if b == 0:
+                treport.first = (mine, rows.numel() * pixels)
+            if b == nb - 1:
+                treport.before_last_step()
         if by_rows:
             stepper.step_rows(mine, rows.numel() * pixels, **hyper)
         else:
             stepper.step(inputs.index_select(0, mine), targets.index_select(0, mine), None, rows.numel() * pixels, **hyper)
+        if treport is not None and b == nb - 1:
+            treport.after_last_step()
     avg_train_loss = stepper.global_loss() / nb                 # mean of per-batch means (model.py:311,333)
 
     model.eval()
@@ -444,7 +539,10 @@ def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, wor
             if report.bitmaps and rank == 0 and report.idx.numel():      # the worst sheets once more, for their bitmaps (no collective)
                 report.u8 = (eng.evaluate_rows(report.idx, want_u8=True) if by_rows else
                              eng.evaluate(inputs.index_select(0, report.idx), want_u8=True)).u8
-    return avg_train_loss, stepper.global_loss() / max(nvb, 1)
+    avg_val_loss = stepper.global_loss() / max(nvb, 1)
+    if treport is not None:
+        treport.probe(*(() if by_rows else (inputs, targets)))
+    return avg_train_loss, avg_val_loss
 
 
 def train_attention_model(model, dataset, batch_size):
@@ -474,6 +572,8 @@ def train_attention_model(model, dataset, batch_size):
                 f.write(f"ema_decay = {eng.ema_decay:g}\nema_every = {eng.ema_every}\n")
             if VAL_REPORT:                      # likewise
                 f.write(f"val_report = {VAL_REPORT}\n")
+            if TENSOR_REPORT:                   # likewise
+                f.write("tensor_report = 1\n")
 
     order = _EpochOrder(len(dataset))
     print(f"Dataset split: {order.train_size} training samples, {order.val_size} validation samples")
@@ -503,7 +603,9 @@ def train_attention_model(model, dataset, batch_size):
     for epoch in range(NUM_EPOCHS):
         lr = lr_holder.param_groups[0]["lr"]
         report = _ValReport(VAL_REPORT, device, bitmaps=epoch % 5 == 0) if VAL_REPORT else None
-        avg_train_loss, avg_val_loss = _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True, report=report)
+        treport = _TensorReport(model) if TENSOR_REPORT and rank == 0 and epoch % 5 == 0 else None
+        avg_train_loss, avg_val_loss = _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True, report=report,
+                                                  treport=treport)
 
         scheduler.step(avg_val_loss)
         is_best = avg_val_loss < best_val_loss
@@ -527,6 +629,8 @@ def train_attention_model(model, dataset, batch_size):
                     print(report.line(targets[0].numel(), world))
                     for j in range(0 if report.u8 is None else report.u8.shape[0]):
                         helpers.u8_array_to_image(report.u8[j].cpu().numpy(), f"{OUTPUT_DIR}/epoch_{epoch}/val_worst_{j}.bmp")
+                if treport is not None:
+                    print("\n".join(treport.lines()))
                 with _eval_weights(eng):
                     render_strings(model, test_strings, output_dir=f"{OUTPUT_DIR}/epoch_{epoch}", sheet_height=SHEET_HEIGHT,
                                    sheet_width=SHEET_WIDTH, device=device)

@@ -310,6 +310,44 @@ int afr_eval(afr_plan* plan, const void* target /* or NULL */, int target_dtype,
              float* loss_rows /* or NULL */, uint32_t* stats /* or NULL */, uint8_t* q /* or NULL */, void* stream);
 int afr_eval_rows(afr_plan* plan, const int64_t* rows, int B, float* loss_rows, uint32_t* stats, uint8_t* q, void* stream);
 
+/* ---- per-tensor statistics of a flat buffer in the parameter layout (DESIGN.md 4 "Tensor statistics") ----
+ * One 32-byte record per parameter tensor, in afr_param_info order.  x is an element of the chosen buffer or, when a second buffer
+ * `minus` is given, x = a[i] - minus[i] in f32 (inf - inf then counts as a NaN).  Classification is by bit pattern -- exponent field
+ * all ones: infinity (mantissa 0) or NaN; (bits & 0x7fffffff) == 0: zero -- so the counts do not depend on the denormal mode: a
+ * denormal is finite and non-zero.  Only the tensor's elements are read, numel of them from its offset; the 64-element padding
+ * behind it (arbitrary values after the fused glyph step and the slab reduces) never is. */
+typedef struct afr_tensor_stat {
+    float    sumsq;   /* sum of x^2 over the FINITE elements, f32, fixed order                   */
+    float    sum;     /* sum of x   over the finite elements, f32, same order                    */
+    float    min, max;/* over the finite elements; +inf / -inf when there is none                */
+    uint32_t n_nan, n_inf, n_zero;   /* n_zero counts +0 and -0                                  */
+    uint32_t numel;   /* the tensor's element count as the launch saw it                         */
+} afr_tensor_stat;
+/* The order of the two sums, with C = afr_tensor_stats_chunk() elements (a compile-time constant of the library, 32768): a tensor of
+ * n elements is cut into max(1, ceil(n / C)) chunks, each summed by one 256-lane workgroup.  Lane l takes the groups of 4 elements
+ * l, l + 256, ... of its chunk in ascending order and keeps one accumulator pair per position c in the group:
+ * q_c = fmaf(x, x, q_c), s_c = s_c + x (a non-finite x enters as 0).  The <= 3 elements behind the tensor's last whole group are
+ * added by lanes 0..2 of the tensor's last chunk to their pair 0.  Then (q_0 + q_1) + (q_2 + q_3), six butterfly steps across the
+ * wave (offsets 32, 16, 8, 4, 2, 1), (w0 + w1) + (w2 + w3) over the four waves: the chunk's partial record.  A second launch gives
+ * one wave to each tensor: lane l adds the partials of chunks l, l + 64, ... in ascending order, then the same butterfly.
+ * LOCALITY: a tensor's record depends on that tensor's elements only -- not on its offset, the other tensors in the table or the
+ * launch geometry -- and repeats bit for bit.  No atomics, no communication between workgroups, inputs are only read.
+ * afr_tensor_stats reads the plan's bound buffer `which` as it stands, launches exactly those two kernels, allocates and synchronises
+ * nothing; its partials live in the plan workspace.  minus: NULL, or a device buffer in the flat layout (afr_param_elems() floats,
+ * 16-byte aligned).  out: device, afr_param_count() records, 16-byte aligned.
+ * GRADIENTS: which gradients a previous call left in the buffer is the caller's knowledge.  After afr_backward, after a
+ * do_step == 0 step, on a clipping plan, with AFR_CFG_UNFUSED_OPTIMIZER, or under data parallelism, every tensor's gradient is
+ * there; after a fused do_step != 0 step the tensors whose update was fused -- fc_output.weight and the slab-reduced tensors --
+ * hold older values.
+ * Errors, all detected before anything is launched: out NULL or misaligned, minus misaligned, an unknown `which` -> AFR_EINVAL; the
+ * named buffer not bound (no gradients or moments; AFR_STAT_EXP_AVG_SQ on a plan bound without it; AFR_STAT_EMA without afr_set_ema)
+ * -> AFR_ESTATE; more than 256 tensors, or one of 2^32 elements or more -> AFR_EUNSUPPORTED, never a silent drop.  Allowed while
+ * afr_use_ema is on: AFR_STAT_PARAMS then names the buffer the forward entry points currently read -- the average -- and AFR_STAT_EMA
+ * the other one. */
+enum { AFR_STAT_PARAMS = 0, AFR_STAT_GRADS = 1, AFR_STAT_EXP_AVG = 2, AFR_STAT_EXP_AVG_SQ = 3, AFR_STAT_EMA = 4 };
+int afr_tensor_stats_chunk(void);             /* host-only */
+int afr_tensor_stats(afr_plan* plan, int which, const float* minus /* or NULL */, afr_tensor_stat* out, void* stream);
+
 /* Set / read the device-side error word (bit 0: an embedding index outside [0,vocab), the
  * condition on which the reference raises IndexError; model.py:136,167; bit 1: a cooperative split-K
  * workgroup gave up waiting for its partners -- the step's results are invalid; bit 2: a row index of an afr_*_rows call
@@ -426,6 +464,18 @@ int afr_op_bce_grad(int act_dtype, const void* u, const void* target, int target
 int afr_op_eval(int act_dtype, int loss_kind, const void* u, const void* target /* or NULL */, int target_dtype,
                 const int32_t* rowmap /* or NULL */, int64_t rows, int64_t cols,
                 float* loss_rows, uint32_t* stats, uint8_t* q, void* stream);
+/* afr_tensor_stats' pair of launches on caller-owned buffers: record k describes the numel elements from a + off (of a - minus, minus
+ * or NULL in the same layout) of segs[k], a HOST array of nseg entries that is not read after the call returns (the table travels to
+ * the kernels as an argument).  Formulas, order and locality as above: a record is bit for bit what afr_tensor_stats gives for a
+ * tensor with the same elements.  a, minus, out and scratch are device pointers, 16-byte aligned; scratch holds
+ * afr_op_tensor_stats_scratch_bytes(segs, nseg) bytes (32 per chunk; 0 for a table that would be refused), needs no initialisation
+ * and keeps no state between calls.  Errors, before anything is launched: a, out, scratch or segs NULL or misaligned, nseg outside
+ * 1..256, an off negative or not a multiple of 4, numel < 0, scratch_bytes too small -> AFR_EINVAL; a numel of 2^32 or more, or an
+ * off of 2^34 or more -> AFR_EUNSUPPORTED. */
+typedef struct afr_tensor_seg { int64_t off, numel; } afr_tensor_seg;
+size_t afr_op_tensor_stats_scratch_bytes(const afr_tensor_seg* segs, int nseg);
+int afr_op_tensor_stats(const float* a, const float* minus /* or NULL */, const afr_tensor_seg* segs, int nseg,
+                        afr_tensor_stat* out, void* scratch, size_t scratch_bytes, void* stream);
 int afr_op_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);
 
 /* ---- the token-wise kernels of the per-pixel-token transformer (AFR_KIND_PIXEL), one launch each, exactly as the plan issues
