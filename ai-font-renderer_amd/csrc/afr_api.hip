@@ -109,6 +109,9 @@ struct afr_plan {
     // hyper-parameters of the optimizer step in progress (afr_train_step): set while backward runs, so that weight-gradient
     // products with a cooperative split-K tail apply AdamW themselves; adam_done lists the tensors they have updated
     bool step_on = false; AdamArgs st{};
+    // a monolithic fused step's loss partials, stored without the ticket (LossArgs::counter == NULL) by the forward's last GEMM;
+    // the fused first-layer backward of the SAME call adds them (backward_stage_impl) and clears this
+    LossSum loss_defer{};
     std::vector<int64_t> adam_done;
     // pixel-token transformer (AFR_KIND_PIXEL): per-block parameter offsets and the forward's workspace
     struct PixBlock { int64_t ln1g, ln1b, win, bin, wo, bo, ln2g, ln2b, w1, b1, w2, b2; };
@@ -1121,6 +1124,10 @@ static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int 
             if (combo && i == 1) { g.a_rowmap = (const int*)(p->ws + p->o_cidx); g.lda = p->h1c_ld; }
             if (bits && !last && p->o_mbits[i]) { g.mask_out = (unsigned char*)(p->ws + p->o_mbits[i]); g.ldmask = l.N / 8; }
             if (last && fl) g.loss = *fl;
+            if (last && fl && !fl->counter) {        // deferred sum: remember where the partials are and how they were produced
+                p->loss_defer.partial = fl->partial; p->loss_defer.inv_n = fl->inv_n; p->loss_defer.loss_accum = fl->loss_accum;
+                afr_gemm_tile_launch_shape(p->gemm_dtype, g, &p->loss_defer.n, &p->loss_defer.bd);
+            }
             int rc = run_gemm(p, s, g);
             if (rc) return rc;
             h = outp;
@@ -1356,8 +1363,10 @@ static int backward_stage_impl(afr_plan* p, int stage, int64_t* g_off, int64_t* 
             {
                 ProfScope ps(p, s, "glyph_l1_bwd_fused", 2.0 * B * l.N * (2.0 * E + 1.0), (double)B * l.N * 2.0 + (double)nb * st * 4.0);
                 if (p->combo_on) HIPCHK(afr_launch_glyph_l1_bwd_fused(dy, l.N, p->ws + p->o_h0c, E, p->ws + p->o_w1t, p->last_x, p->last_font, B, l.N,
-                                                                      c.vocab, c.n_fonts, sl, s, (const int*)(p->ws + p->o_cidx)));
-                else HIPCHK(afr_launch_glyph_l1_bwd_fused(dy, l.N, a, K0, p->ws + p->o_w1t, p->last_x, p->last_font, B, l.N, c.vocab, c.n_fonts, sl, s));
+                                                                      c.vocab, c.n_fonts, sl, s, (const int*)(p->ws + p->o_cidx), &p->loss_defer));
+                else HIPCHK(afr_launch_glyph_l1_bwd_fused(dy, l.N, a, K0, p->ws + p->o_w1t, p->last_x, p->last_font, B, l.N, c.vocab, c.n_fonts, sl, s,
+                                                          nullptr, &p->loss_defer));
+                p->loss_defer = LossSum{};
             }
             // block = (row block, column range): range cs's slabs are blocks cs, cs + CS, ...; every block has a dTab partial
             for (int cs = 0; cs < CS; ++cs) {
@@ -1827,8 +1836,16 @@ static int train_step_impl(afr_plan* p, const int64_t* x, const int64_t* font, c
         return AFR_OK;
     }
     // the loss and its gradient are computed in the epilogue of the last forward GEMM: u never touches HBM
-    const LossArgs fl = loss_args(p, true, target, tdtype, rowmap, mean_elems, loss_accum);
-    if ((rc = forward_impl(p, x, font, B, L, nullptr, 1, step, stream, &fl))) return rc;
+    LossArgs fl = loss_args(p, true, target, tdtype, rowmap, mean_elems, loss_accum);
+    // When this call runs the whole backward and the step itself (the branch ending in reduce_and_step below) and the first-layer
+    // backward is the fused kernel, nothing before the end of the step reads the loss: the forward's last GEMM only stores its
+    // partials (no ticket, no last-block sum at the end of that launch) and one workgroup appended to the first-layer backward's
+    // grid adds them -- the same arithmetic, bit for bit.  Every other path keeps the ticket.
+    p->loss_defer = LossSum{};
+    const bool defer_loss = fuse_opt && t >= 1 && !fused_step_eligible(p, B) && moments_bound(p) && p->cfg.kind == AFR_KIND_GLYPH && p->k0 &&
+                            p->l1f && !(p->cfg.reserved & AFR_CFG_L1_BWD_UNFUSED) && p->gemm_dtype == AFR_BF16;
+    if (defer_loss) fl.counter = nullptr;
+    if ((rc = forward_impl(p, x, font, B, L, nullptr, 1, step, stream, &fl))) { p->loss_defer = LossSum{}; return rc; }
     if (fuse_opt && fused_step_eligible(p, B)) {
         if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
         return sheet_fused_step(p, (hipStream_t)stream, h);
@@ -1840,7 +1857,7 @@ static int train_step_impl(afr_plan* p, const int64_t* x, const int64_t* font, c
         // weight-gradient products with a cooperative split-K tail apply this step's AdamW themselves
         p->step_on = true; p->adam_done.clear(); p->st = h;
         for (int st = 0; st < n; ++st)
-            if ((rc = backward_stage_impl(p, st, nullptr, nullptr, (hipStream_t)stream, &rt))) { p->step_on = false; return rc; }
+            if ((rc = backward_stage_impl(p, st, nullptr, nullptr, (hipStream_t)stream, &rt))) { p->step_on = false; p->loss_defer = LossSum{}; return rc; }
         p->step_on = false;
         p->next_stage = 0;
         p->have_du = false;

@@ -61,9 +61,17 @@ __device__ __forceinline__ float wave_max(float v) {
 // Hand-off form: sc1 (write-through) partial store, drained, agent-scope ticket; the reader uses sc1 loads only
 // (cdna_hip_programming.md Guideline 16 R1: no release fence -- it would flush every dirty line of the XCD's L2).
 // Must be called by all threads of the block; `sh` is >= blockDim.x floats of LDS free for use.
+// DEFERRABLE (the GEMM epilogues only): with counter == nullptr the block stores its partial -- the same sc1 store -- and
+// returns: no ticket, no barrier, no last-block work.  A later launch of the same stream adds the partials with
+// loss_sum_deferred (gemm.hip: the workgroup appended to glyph_l1_bwd_fused_kernel's grid).
+template <bool DEFERRABLE = false>
 __device__ __forceinline__ void loss_block_finish(float block_sum, float* partial, unsigned* counter, float* loss_accum,
                                                   float inv_n, float* sh) {
     __shared__ unsigned ticket_;
+    if (DEFERRABLE && !counter) {
+        if (threadIdx.x == 0) __hip_atomic_store(partial + blockIdx.x, block_sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
     if (threadIdx.x == 0) {
         __hip_atomic_store(partial + blockIdx.x, block_sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -84,6 +92,30 @@ __device__ __forceinline__ void loss_block_finish(float block_sum, float* partia
         loss_accum[0] += sh[0] * inv_n;
         __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-arm for the next call
     }
+}
+// The partials that a launch of `n` blocks of `bd` threads left with counter == nullptr, added by ONE later workgroup of at least
+// bd threads (all of them call): loss_block_finish's last-block arithmetic term for term -- the strided per-thread sums at the
+// PRODUCER's block size, the same LDS tree, the same final expression -- so the loss is bit for bit the ticket form's.  The
+// producer was an earlier launch of the same stream: plain loads.  The arrival counter is not touched (it stays zero).
+struct LossSum {
+    const float* partial = nullptr;   // NULL: nothing to add
+    int n = 0, bd = 0;                // blocks and threads per block of the launch that wrote the partials
+    float inv_n = 0.f;
+    float* loss_accum = nullptr;
+};
+__device__ __forceinline__ void loss_sum_deferred(const LossSum& l, float* sh) {
+    const int t = threadIdx.x, bd = l.bd;
+    if (t < bd) {
+        float a = 0.f;
+        for (int i = t; i < l.n; i += bd) a += l.partial[i];
+        sh[t] = a;
+    }
+    __syncthreads();
+    for (int o = bd >> 1; o > 0; o >>= 1) {
+        if (t < o) sh[t] += sh[t + o];
+        __syncthreads();
+    }
+    if (t == 0) l.loss_accum[0] += sh[0] * l.inv_n;
 }
 
 // Loss kinds of a plan (afr_config.loss; the values of AFR_LOSS_* in afr.h).  The kind is a template parameter of every kernel
@@ -267,6 +299,7 @@ struct GemmParams {
 };
 constexpr uint32_t AFR_ERR_INDEX = 1u, AFR_ERR_COOP_TIMEOUT = 2u, AFR_ERR_ROW = 4u, AFR_ERR_GRAD_NONFINITE = 8u;    // bits of the plan's device error word
 hipError_t afr_launch_gemm(int dtype, const GemmParams& p, hipStream_t s);
+void afr_gemm_tile_launch_shape(int dtype, const GemmParams& p, int* tiles, int* threads);   // of a product on the ring / tile kernels
 hipError_t afr_launch_gemm_fp8(const GemmParams& p, hipStream_t s);          // e4m3 x e4m3, both k-contiguous (gemm.hip fp8k)
 hipError_t afr_launch_f32_to_fp8(const float* src, unsigned char* dst, long long n, float inv_scale, hipStream_t s);
 // several independent products in one launch (falls back to one launch each when one of them does not qualify)
@@ -395,7 +428,7 @@ int afr_glyph_l1_bwd_fused_blocks(int B, int N1);
 long long afr_glyph_l1_bwd_fused_slab_floats(int B, int N1, int vocab, int n_fonts);   // [dW1 nc*E | db1 nc | dTab rows*E], nc = N1 / split
 hipError_t afr_launch_glyph_l1_bwd_fused(const void* d1, int ldd, const void* h0, int ldh, const void* W1T, const int64_t* x,
                                          const int64_t* font, int B, int N1, int vocab, int n_fonts, float* slabs, hipStream_t s,
-                                         const int* h0_rowmap = nullptr);
+                                         const int* h0_rowmap = nullptr, const LossSum* loss = nullptr);   // loss: one more workgroup adds deferred partials
 hipError_t afr_launch_glyph_l1_bwd(const float* slabs, int nslabs, long long slab_stride, const float* W1, int N1, int E,
                                    int vocab, int n_fonts, float* dw1, float* dtab_part, hipStream_t s);
 hipError_t afr_launch_glyph_embed_bwd(int act_dtype, const void* d, const int64_t* x, const int64_t* font, int B,

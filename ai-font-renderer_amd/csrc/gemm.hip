@@ -1177,7 +1177,7 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p, const int bi
         float bs = 0.f;
 #pragma unroll
         for (int w = 0; w < NW; ++w) bs += red[w];
-        loss_block_finish(bs, p.loss.partial, p.loss.counter, p.loss.loss_accum, p.loss.inv_n, red + 16);
+        loss_block_finish<true>(bs, p.loss.partial, p.loss.counter, p.loss.loss_accum, p.loss.inv_n, red + 16);   // (counter NULL: deferred sum)
     }
 #ifdef AFR_GEMM_TIMING
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1464,11 +1464,14 @@ __device__ __forceinline__ void gemm_bf16_256_body(const GemmParams& p, const in
         float* Wt = reinterpret_cast<float*>(smem) + wave * 4096;
         {
             const unsigned mine = tile_b + ((unsigned)z * 8u + (unsigned)wave) * (32u * 1024u) + (unsigned)lane * 16u;
+            // the rows this slice adds up itself stay in registers: nobody else reads them (z is workgroup-uniform: scalar branches)
 #pragma unroll
-            for (int i = 0; i < 8; ++i)
+            for (int i = 0; i < 8; ++i) {
+                if ((unsigned)(i - z * per) < (unsigned)per) continue;
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i][j]), rws, mine + (unsigned)(i * 4 + j) * 1024u, 0, 16);
+            }
         }
         // (Measured and dropped: requesting the first strip's optimizer state by LDS-DMA before / behind the park's stores, so
         // that it arrives under the park-wait-load chain -- strip_prefetch.  The finish got 4 us shorter, the park and the
@@ -1496,6 +1499,14 @@ __device__ __forceinline__ void gemm_bf16_256_body(const GemmParams& p, const in
             // slices >= S read past the descriptor (zeros): one code path for every S, and the sum starts from +0 exactly as
             // the slab reduction's does (bitwise equal results).  The range check looks at the VGPR offset only.
             const unsigned src = tile_b + (unsigned)wave * (32u * 1024u) + (unsigned)(i * 4) * 1024u + (unsigned)lane * 16u;
+            // this slice's own term: accumulator row i, picked by selects on the uniform i (never a dynamic register index)
+            f32x4 own[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                own[j] = acc[0][j];
+#pragma unroll
+                for (int i2 = 1; i2 < 8; ++i2) own[j] = i == i2 ? acc[i2][j] : own[j];
+            }
             f32x4 v[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1505,7 +1516,8 @@ __device__ __forceinline__ void gemm_bf16_256_body(const GemmParams& p, const in
 #pragma unroll
                 for (int zq = 0; zq < 4; ++zq) {
                     const int zz = 4 * h + zq;
-                    const unsigned vo = zz < S ? src + (unsigned)zz * (8u * 32u * 1024u) : 0x80000000u;
+                    // (slice z's own strip was never parked: its load reads past the descriptor too and is replaced below)
+                    const unsigned vo = (zz < S && zz != z) ? src + (unsigned)zz * (8u * 32u * 1024u) : 0x80000000u;
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
                         q[zq][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rws, vo, (unsigned)j * 1024u, 16));
@@ -1513,7 +1525,7 @@ __device__ __forceinline__ void gemm_bf16_256_body(const GemmParams& p, const in
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
 #pragma unroll
-                    for (int zq = 0; zq < 4; ++zq) v[j] += q[zq][j];
+                    for (int zq = 0; zq < 4; ++zq) v[j] += (4 * h + zq == z) ? own[j] : q[zq][j];      // still slice order 0 .. 7 from +0
             }
             strip_finish<OPT>(p, v, m0 + wr * 128 + 16 * i, n0 + wc * 64, Wt, lane, false);
         }
@@ -1650,10 +1662,16 @@ struct L1BwdArgs {
     int ldd, ldh, B, N1, vocab, n_fonts;
     int CS, ncols;                   // the N1 columns are cut into CS ranges of ncols (a multiple of 128): block = (row block, range)
     float* slabs; long long slab_stride; int o_b, o_tab;
+    int nwork;                       // blocks that compute; with loss.partial set the grid has ONE more, which only adds the step's
+    LossSum loss;                    // deferred loss partials (loss_sum_deferred): off the critical path, nobody waits for it
 };
 constexpr int L1_E = 32, L1_R = 64, L1_LDR = L1_R + 8;       // embedding width (compile time), glyphs per block, padded row of the overlay
 __global__ __launch_bounds__(512) void glyph_l1_bwd_fused_kernel(L1BwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) char sm[];
+    if ((int)blockIdx.x >= a.nwork) {                        // the appended workgroup (launched only with a.loss.partial set)
+        loss_sum_deferred(a.loss, reinterpret_cast<float*>(sm));
+        return;
+    }
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), r = lane & 15, q = lane >> 4;
     const int NS = a.ncols >> 7;                             // 128-column sub-tiles of this block's d1 columns
     const int rb = blockIdx.x / a.CS, n_lo = (blockIdx.x - rb * a.CS) * a.ncols;
@@ -2049,6 +2067,13 @@ hipError_t afr_launch_gemm_group(int dtype, const GemmParams* ps, int n, int til
 #endif
     return launch_grouped(ps, n, tile256, true, s);
 }
+// Tiles (blocks per K-slice) and threads per block of a product that afr_launch_gemm runs on the ring / tile kernels -- every
+// product with a fused loss does: whoever adds deferred loss partials needs the producer's grid and block size.
+void afr_gemm_tile_launch_shape(int dtype, const GemmParams& p, int* tiles, int* threads) {
+    const bool wide = dtype == AFR_BF16 && bf16_use_wide(p);
+    *tiles = ((p.M + (wide ? 255 : 127)) / (wide ? 256 : 128)) * ((p.N + 127) / 128);      // (f32k and x3k: 128 x 128 as well)
+    *threads = wide ? 512 : 256;
+}
 hipError_t afr_launch_gemm(int dtype, const GemmParams& p_in, hipStream_t s) {
 #ifdef AFR_GEMM_TIMING
     GemmParams p = p_in;
@@ -2071,7 +2096,8 @@ hipError_t afr_launch_gemm(int dtype, const GemmParams& p_in, hipStream_t s) {
     }
     if (dtype == AFR_BF16 && bf16_use_body256(p)) return launch_grouped(&p, 1, true, false, s);
     const bool wide = dtype == AFR_BF16 && bf16_use_wide(p);
-    const int tiles = ((p.M + (wide ? 255 : 127)) / (wide ? 256 : 128)) * ((p.N + 127) / 128);      // (f32k and x3k: 128 x 128 as well)
+    int tiles, threads_;
+    afr_gemm_tile_launch_shape(dtype, p, &tiles, &threads_);
     auto launch = [&](auto kernel, int threads) { hipLaunchKernelGGL(kernel, dim3(tiles * p.splitk), dim3(threads), 0, s, p); };
     // The kernels that exist: the four operand layouts, and for the forward layout (row-mapped targets) x (loss kind) -- never
     // their cross product (static_asserts in gemm_bf16_body).  al, bl, tr, loss arrive as tags.
@@ -2116,8 +2142,9 @@ long long afr_glyph_l1_bwd_fused_slab_floats(int B, int N1, int vocab, int n_fon
 }
 hipError_t afr_launch_glyph_l1_bwd_fused(const void* d1, int ldd, const void* h0, int ldh, const void* W1T, const int64_t* x,
                                          const int64_t* font, int B, int N1, int vocab, int n_fonts, float* slabs, hipStream_t s,
-                                         const int* h0_rowmap) {
+                                         const int* h0_rowmap, const LossSum* loss) {
     if (B <= 0) return hipSuccess;
+    if (loss && loss->partial && (loss->n < 1 || (loss->bd != 256 && loss->bd != 512) || !loss->loss_accum)) return hipErrorInvalidValue;
     bf16k::L1BwdArgs a;
     a.d1 = (const bf16_t*)d1; a.h0 = (const bf16_t*)h0; a.W1T = (const bf16_t*)W1T; a.x = x; a.font = font; a.h0_rowmap = h0_rowmap;
     a.ldd = ldd; a.ldh = ldh; a.B = B; a.N1 = N1; a.vocab = vocab; a.n_fonts = n_fonts;
@@ -2132,6 +2159,8 @@ hipError_t afr_launch_glyph_l1_bwd_fused(const void* d1, int ldd, const void* h0
         if (e != hipSuccess) return e;
         if (dev >= 0 && dev < 16) set[dev] = lds;
     }
-    hipLaunchKernelGGL(bf16k::glyph_l1_bwd_fused_kernel, dim3(afr_glyph_l1_bwd_fused_blocks(B, N1)), dim3(512), lds, s, a);
+    a.nwork = afr_glyph_l1_bwd_fused_blocks(B, N1);
+    if (loss && loss->partial) a.loss = *loss;
+    hipLaunchKernelGGL(bf16k::glyph_l1_bwd_fused_kernel, dim3(a.nwork + (a.loss.partial ? 1 : 0)), dim3(512), lds, s, a);
     return hipGetLastError();
 }
