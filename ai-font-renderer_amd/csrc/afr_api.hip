@@ -62,6 +62,13 @@ struct ProfRec { int tag; hipEvent_t a, b; double flops, bytes; };
 // has a counter of its own and its partials, one per block of that launch, behind it.
 constexpr int LOSS_WS_COUNTER = 1024, LOSS_WS_FUSED_COUNTER = 1032, LOSS_WS_FUSED_PARTIAL = 1040;
 struct AdamArgs { float lr, b1, b2, eps, wd; int64_t t; };      // the optimizer arguments of afr_train_step
+// The optimizer step ONE afr_train_step call is taking: made by train_step_impl and handed down to whatever applies part of it.
+// The entry points that only run a backward hand none, so they can never see a step, or a deferred loss sum, that is not theirs.
+struct StepCtx {
+    AdamArgs h;
+    int64_t done[AFR_MAX_HIDDEN + 1]; int ndone = 0;   // weights (flat offsets) a cooperative weight-gradient tail has stepped: one per Linear at most
+    LossSum loss{};   // deferred loss: partials the forward's last GEMM stored without the ticket; the fused first-layer backward adds them
+};
 // The clip scratch of a plan (o_clip), in floats: grad_sumsq_kernel's scratch, the word its sum goes to, the segment table
 constexpr int CLIP_WS_SUMSQ = AFR_SUMSQ_SCRATCH_FLOATS, CLIP_WS_TABLE = AFR_SUMSQ_SCRATCH_FLOATS + 8;
 static_assert(CLIP_WS_TABLE * sizeof(float) % alignof(SumsqSeg) == 0, "the segment table is aligned");
@@ -77,13 +84,6 @@ struct afr_plan {
     char* ws = nullptr;
     size_t ws_bytes = 0, ws_need = 0;
     int device = -1;               // the GPU that owns the bound buffers (afr_bind)
-    // products collected for ONE grouped launch (a layer's weight gradient + input gradient): see flush_gemms
-    bool defer = false;
-    int pend_tile256 = 0;
-    std::vector<GemmParams> pend;
-    std::vector<std::string> pend_tag;
-    double pend_flops = 0.0, pend_bytes = 0.0;
-    unsigned* pend_arrived = nullptr;   // the cooperative member's Layer::coop_arrived, advanced once the launch is enqueued
     // workspace offsets (bytes)
     size_t o_shadow = 0, o_err = 0, o_loss = 0, o_u = 0, o_z = 0, o_dz = 0, o_slab_e = 0, o_save = 0;
     std::vector<size_t> o_act;     // glyph: activations h0..h_nh
@@ -98,21 +98,14 @@ struct afr_plan {
     bool l1f = false; size_t o_l1f = 0;   // glyph, bf16: folded first layer's backward in one kernel (slabs [blocks][dW1|db1|dTab])
     // glyph, bf16 training steps: the first layer's output as a COMBINATION table (elementwise.hip glyph_combo_kernel): h1 / h0
     // are not materialised per glyph; the products that consume them gather table rows through cidx while staging
-    bool combo_ok = false, combo_on = false; size_t o_h1c = 0, o_h0c = 0, o_cidx = 0; int h1c_ld = 0;
+    bool combo_ok = false; size_t o_h1c = 0, o_h0c = 0, o_cidx = 0; int h1c_ld = 0;
     // glyph, bf16 training steps: hidden activations written by a GEMM epilogue also leave their ReLU mask as bits
     // (o_mbits[i] for the output of layer i, 0 = none); the next layer's input-gradient product reads those instead of the activation
-    std::vector<size_t> o_mbits; bool mbits_on = false;
+    std::vector<size_t> o_mbits;
     // bf16 glyph nets: TWO weight shadows.  A fused optimizer step writes every tensor's new bf16 copy into the one that is
     // not being read (a layer's weight-gradient workgroups update the weights while the same launch's input-gradient
     // workgroups still read them), and the roles swap when the step is complete.
     size_t o_shadow2 = 0; int shadow_cur = 0;
-    // hyper-parameters of the optimizer step in progress (afr_train_step): set while backward runs, so that weight-gradient
-    // products with a cooperative split-K tail apply AdamW themselves; adam_done lists the tensors they have updated
-    bool step_on = false; AdamArgs st{};
-    // a monolithic fused step's loss partials, stored without the ticket (LossArgs::counter == NULL) by the forward's last GEMM;
-    // the fused first-layer backward of the SAME call adds them (backward_stage_impl) and clears this
-    LossSum loss_defer{};
-    std::vector<int64_t> adam_done;
     // pixel-token transformer (AFR_KIND_PIXEL): per-block parameter offsets and the forward's workspace
     struct PixBlock { int64_t ln1g, ln1b, win, bin, wo, bo, ln2g, ln2b, w1, b1, w2, b2; };
     std::vector<PixBlock> pix;
@@ -129,14 +122,22 @@ struct afr_plan {
     int64_t emb_off = 0, font_off = 0;
     // sheet offsets
     int64_t s_pos = 0, s_emb = 0, s_win = 0, s_bin = 0, s_wo = 0, s_bo = 0, s_g = 0, s_b = 0, s_w1 = 0, s_b1 = 0, s_wout = 0, s_bout = 0;
-    // state left by the last forward
-    const int64_t* last_x = nullptr;
-    const int64_t* last_font = nullptr;
-    int last_B = 0, last_L = 0, last_ldx = 0, last_training = 0;
-    uint64_t last_step = 0;
-    bool have_du = false;
-    bool have_u = false;          // the u buffer holds the pre-activation of the last forward (afr_eval*): not yet overwritten by du
-    int next_stage = 0;
+    // What the last forward left for the loss, evaluation and backward entry points.  A forward (forward_impl's two exits, the
+    // one-launch small-net step) sets ALL of it through forward_done; the calls after it only move have_du / have_u / next_stage.
+    struct Last {
+        const int64_t *x = nullptr, *font = nullptr;
+        int B = 0, L = 0, ldx = 0, training = 0, next_stage = 0;
+        uint64_t step = 0;
+        bool have_du = false;         // the u buffer holds d(loss)/du: a backward may start
+        bool have_u = false;          // the u buffer holds the pre-activation of the last forward (afr_eval*): not yet overwritten by du
+        bool combo_on = false, mbits_on = false;   // glyph: the first layer ran as a combination table / the ReLU masks were left as bits
+        enum Holds { NOTHING, U, DU };      // what the u buffer holds when the forward returns
+        void forward_done(const int64_t* x_, const int64_t* font_, int B_, int L_, int ldx_, int training_, uint64_t step_, Holds h,
+                          bool combo = false, bool mbits = false) {
+            x = x_; font = font_; B = B_; L = L_; ldx = ldx_; training = training_; step = step_;
+            have_du = h == DU; have_u = h == U; next_stage = 0; combo_on = combo; mbits_on = mbits;
+        }
+    } last;
     // the bound data set (afr_bind_dataset; caller-owned device buffers) and the workspace staging of the afr_*_rows calls: the
     // narrowed row indices the loss kernels' row maps read, and the batch's codes / font ids for the id consumers
     const int64_t* ds_x = nullptr; const int64_t* ds_font = nullptr; const void* ds_target = nullptr;
@@ -169,6 +170,8 @@ struct afr_plan {
 };
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// the folded first layer's backward is the ONE fused kernel (gemm.hip glyph_l1_bwd_fused_kernel), not GEMM + extraction
+static inline bool l1_bwd_fused(const afr_plan* p) { return p->l1f && !(p->cfg.reserved & AFR_CFG_L1_BWD_UNFUSED); }
 
 static void add_param(afr_plan* p, const char* name, std::initializer_list<int64_t> shape) {
     Tensor t;
@@ -337,7 +340,7 @@ extern "C" int afr_plan_create(const afr_config* c, afr_plan** out) {
         p->o_slab_e = carve(eb * (size_t)(c->vocab + c->n_fonts) * E * sizeof(float));
         {
             const size_t ncombo = (size_t)c->vocab * (c->n_fonts > 0 ? c->n_fonts : 1);
-            if (c->dtype == AFR_BF16 && p->l1f && c->n_hidden >= 2 && ncombo <= 1024 && !(c->reserved & (AFR_CFG_NO_COMBO_TABLE | AFR_CFG_L1_BWD_UNFUSED))) {
+            if (c->dtype == AFR_BF16 && l1_bwd_fused(p) && c->n_hidden >= 2 && ncombo <= 1024 && !(c->reserved & AFR_CFG_NO_COMBO_TABLE)) {
                 p->combo_ok = true;
                 p->h1c_ld = c->hidden[0];
                 p->o_h1c = carve(ncombo * p->h1c_ld * 2); p->o_h0c = carve(ncombo * E * 2); p->o_cidx = carve(B * sizeof(int));
@@ -484,9 +487,9 @@ extern "C" int afr_bind(afr_plan* p, float* params, float* grads, float* m, floa
     p->device = dev;
     p->P = params; p->G = grads; p->M = m; p->V = v;
     p->ws = (char*)ws; p->ws_bytes = ws_bytes;
-    p->have_du = false; p->have_u = false;
+    p->last.have_du = false; p->last.have_u = false;
     p->wT_valid = false;
-    p->shadow_cur = 0; p->step_on = false; p->adam_done.clear();
+    p->shadow_cur = 0;
     for (auto& l : p->layers) {                          // cooperative split-K: arrival counters and their host count start at zero
         l.coop_arrived = 0;
         if (l.n_cnt) { DevGuard dg(dev); HIPCHK(hipMemset(p->ws + l.o_cnt, 0, (size_t)l.n_cnt * sizeof(unsigned))); }
@@ -656,6 +659,8 @@ static AdamHyper adam_hyper(const AdamArgs& h, int kind = OPT_ADAMW) {
     const float bc2 = (float)(1.0 - std::pow((double)h.b2, (double)h.t));
     return AdamHyper{1.f - h.lr * h.wd, h.b1, h.b2, h.eps, h.lr / bc1, (float)(1.0 / std::sqrt((double)bc2))};
 }
+// the step count every entry point that takes an optimizer step checks before its first launch (1 - beta^0 = 0 divides)
+static int check_step_count(int64_t t) { return t < 1 ? fail(AFR_EINVAL, "t starts at 1") : AFR_OK; }
 // ---- optimizer groups: the ONE place a tensor's (lr_i, wd_i) are formed; every site that steps takes them from here
 static inline float mul_f32(float a, float b) {      // one rounded product, never contracted into what follows
 #pragma clang fp contract(off)
@@ -759,7 +764,18 @@ static int check_operand_bytes(const GemmParams& g) {
     if (ea < (1ll << 31) && eb < (1ll << 31)) return AFR_OK;
     return fail(AFR_EUNSUPPORTED, "a bf16 GEMM operand must be smaller than 2 GiB (A %lld bytes, B %lld bytes)", ea, eb);
 }
-static int run_gemm(afr_plan* p, hipStream_t s, const GemmParams& g) {
+// Products collected for ONE grouped launch (a layer's weight gradient + input gradient).  A local of the function that launches
+// it: run_gemm collects into the batch it is handed, flush_gemms launches it, an early return simply drops it.
+struct GemmBatch {
+    static constexpr int MAX = 4;
+    int tile256 = 0, n = 0;
+    GemmParams g[MAX];
+    char tag[MAX][96];
+    double flops = 0.0, bytes = 0.0;
+    unsigned* arrived = nullptr;   // the cooperative member's Layer::coop_arrived, advanced once the launch is enqueued
+};
+// launches the product, or -- handed a batch, and the product can join a grouped launch -- collects it there
+static int run_gemm(afr_plan* p, hipStream_t s, const GemmParams& g, GemmBatch* batch = nullptr) {
     const int gdt = p->gemm_dtype, M = g.M, N = g.N, K = g.K;
     int rc;
     if (gdt == AFR_BF16 && (rc = check_operand_bytes(g))) return rc;
@@ -777,55 +793,45 @@ static int run_gemm(afr_plan* p, hipStream_t s, const GemmParams& g) {
             snprintf(tag, sizeof tag, "%s[%dx%dx%d]<%d,%d>", kn, M, N, K, (g.flags & AFR_GEMM_A_KSTRIDED) ? 1 : 0, (g.flags & AFR_GEMM_B_KSTRIDED) ? 1 : 0);
         else snprintf(tag, sizeof tag, "%s[%dx%dx%d]", kn, M, N, K);
     }
-    if (g.coop_ws && !(p->defer && p->pend_tile256 && p->pend.empty() && afr_gemm_groupable(gdt, g)))
+    const bool joins = batch && afr_gemm_groupable(gdt, g);
+    if (g.coop_ws && !(joins && batch->tile256 && batch->n == 0))
         return fail(AFR_ESTATE, "cooperative split-K product outside a 256x256 grouped launch");
-    if (g.b_rowmap && !(p->defer && p->pend_tile256 && afr_gemm_groupable(gdt, g)))
+    if (g.b_rowmap && !(joins && batch->tile256))
         return fail(AFR_ESTATE, "gathered k-strided operand outside a 256x256 grouped launch");
-    if (p->defer && afr_gemm_groupable(gdt, g) && p->pend.size() < 4) {
-        p->pend.push_back(g); p->pend_tag.push_back(tag); p->pend_flops += fl_; p->pend_bytes += by_;
+    if (joins && batch->n < GemmBatch::MAX) {
+        batch->g[batch->n] = g; strcpy(batch->tag[batch->n], tag); batch->flops += fl_; batch->bytes += by_; batch->n++;
         return AFR_OK;
     }
     ProfScope ps(p, s, tag, fl_, by_);
     HIPCHK(afr_launch_gemm(gdt, g, s));
     return AFR_OK;
 }
-// forget what run_gemm collected (after its launch, or when a call fails before it)
-static void drop_pending(afr_plan* p) {
-    p->defer = false;
-    p->pend.clear(); p->pend_tag.clear(); p->pend_flops = p->pend_bytes = 0.0;
-    p->pend_arrived = nullptr;
-}
-// launch what run_gemm collected while p->defer was set: one grouped launch (or the plain one when only one qualified)
-static int flush_gemms(afr_plan* p, hipStream_t s) {
-    p->defer = false;
-    if (p->pend.empty()) return AFR_OK;
-    std::string tag = p->pend.size() > 1 ? (p->pend_tile256 ? "gemm_bf16_group256" : "gemm_bf16_group") : p->pend_tag[0];
-    if (p->pend.size() > 1) {
-        tag += "[";
-        for (size_t i = 0; i < p->pend_tag.size(); ++i) tag += (i ? "+" : "") + p->pend_tag[i].substr(p->pend_tag[i].find('[') + 1, p->pend_tag[i].find(']') - p->pend_tag[i].find('[') - 1);
-        tag += "]";
+// launch what run_gemm collected: one grouped launch (or the plain one when only one product qualified)
+static int flush_gemms(afr_plan* p, hipStream_t s, const GemmBatch& b) {
+    if (!b.n) return AFR_OK;
+    char tag[GemmBatch::MAX * 96 + 32];
+    int len = snprintf(tag, sizeof tag, "%s", b.n > 1 ? (b.tile256 ? "gemm_bf16_group256[" : "gemm_bf16_group[") : b.tag[0]);
+    for (int i = 0; i < b.n && b.n > 1; ++i) {      // the members' shapes: what stands between the brackets of their tags
+        const char* shape = strchr(b.tag[i], '[') + 1;
+        len += snprintf(tag + len, sizeof tag - len, "%s%.*s%s", i ? "+" : "", (int)strcspn(shape, "]"), shape, i == b.n - 1 ? "]" : "");
     }
     hipError_t e;
-    {
-        ProfScope ps(p, s, tag.c_str(), p->pend_flops, p->pend_bytes);
-        e = afr_launch_gemm_group(p->gemm_dtype, p->pend.data(), (int)p->pend.size(), p->pend_tile256, s);
-    }
-    // the launch carries the cooperative member's arrivals: the host count follows only once it is enqueued
-    if (e == hipSuccess && p->pend_arrived) *p->pend_arrived = p->pend[0].coop_target;
-    drop_pending(p);
+    { ProfScope ps(p, s, tag, b.flops, b.bytes); e = afr_launch_gemm_group(p->gemm_dtype, b.g, b.n, b.tile256, s); }
     if (e != hipSuccess) return fail(AFR_EHIP, "grouped GEMM launch: %s", hipGetErrorString(e));
+    // the launch carries the cooperative member's arrivals: the host count follows only once it is enqueued
+    if (b.arrived) *b.arrived = b.g[0].coop_target;
     return AFR_OK;
 }
 // dW[N][K] = dy[B][N]^T . a[B][K] and db[N] = sum_b dy, reduced over the batch in ONE GEMM launch (the bias gradient
 // is the column sum of the A tiles the kernel already stages).  Small outputs use split-K partial slabs, summed later
 // by the grouped reduce; large ones (fc_output of the sheet model) write the gradient buffer directly.
 static int run_dw(afr_plan* p, hipStream_t s, afr_plan::Layer& l, const void* dy, const void* a, int Bn, RTable& rt, int sk_want = 0,
-                  bool coop = false, const int* a_rows = nullptr, int a_ld = 0) {
+                  bool coop = false, const int* a_rows = nullptr, int a_ld = 0, GemmBatch* batch = nullptr, StepCtx* step = nullptr) {
     if (a_rows && !coop) return fail(AFR_ESTATE, "gathered weight-gradient operand needs the cooperative 256x256 launch");
     const int N = l.N, K = l.K;
     int sk = sk_want > 0 ? sk_want : choose_splitk(N, K, Bn);
     if (sk > l.sk) sk = l.sk;
-    if (sk == 1) return run_gemm(p, s, lin_dw(dy, a, p->G + l.w_off, p->G + l.b_off, Bn, N, K));
+    if (sk == 1) return run_gemm(p, s, lin_dw(dy, a, p->G + l.w_off, p->G + l.b_off, Bn, N, K), batch);
     float* sw = (float*)(p->ws + l.o_slab_w);
     float* sb = (float*)(p->ws + l.o_slab_b);
     if (coop) {
@@ -837,15 +843,16 @@ static int run_dw(afr_plan* p, hipStream_t s, afr_plan::Layer& l, const void* dy
         g.coop_ws = sw; g.coop_cnt = (unsigned*)(p->ws + l.o_cnt); g.coop_target = l.coop_arrived + (unsigned)sk;
         g.err = (uint32_t*)(p->ws + p->o_err);
         if (a_rows) { g.b_rowmap = a_rows; g.ldb = a_ld; }      // the layer's input rows are gathered from a table whose rows are a_ld apart
-        if (p->step_on) set_fused_opt(p, g, l.w_off, shadow_wr(p), p->st);
-        int rc = run_gemm(p, s, g);
+        if (step && step->ndone == AFR_MAX_HIDDEN + 1) return fail(AFR_ESTATE, "more cooperative weight-gradient tails in one step than Linears");
+        if (step) set_fused_opt(p, g, l.w_off, shadow_wr(p), step->h);
+        int rc = run_gemm(p, s, g, batch);
         if (rc) return rc;
-        p->pend_arrived = &l.coop_arrived;                // run_gemm deferred it (a cooperative product is never launched alone)
-        if (p->step_on) p->adam_done.push_back(l.w_off);
+        batch->arrived = &l.coop_arrived;                 // (batch is non-null: run_gemm refuses a cooperative product it cannot collect)
+        if (step) step->done[step->ndone++] = l.w_off;
         afr_rtable_add(rt, p->G + l.b_off, sb, sk, N, N);
         return AFR_OK;
     }
-    int rc = run_gemm(p, s, lin_dw(dy, a, sw, sb, Bn, N, K, sk, (long long)N * K));
+    int rc = run_gemm(p, s, lin_dw(dy, a, sw, sb, Bn, N, K, sk, (long long)N * K), batch);
     if (rc) return rc;
     afr_rtable_add(rt, p->G + l.w_off, sw, sk, (long long)N * K, (long long)N * K);
     afr_rtable_add(rt, p->G + l.b_off, sb, sk, N, N);
@@ -911,7 +918,7 @@ extern "C" int afr_use_ema(afr_plan* p, int on, void* stream) {
     if (!p->P || !p->ws) return fail(AFR_ESTATE, "plan has no bound parameters");
     std::swap(p->P, p->E);
     p->ema_on = on != 0;
-    p->have_du = false; p->have_u = false; p->next_stage = 0;      // a saved forward belongs to the weights it ran with
+    p->last.have_du = false; p->last.have_u = false; p->last.next_stage = 0;      // a saved forward belongs to the weights it ran with
     return afr_sync_params(p, stream);          // the bf16 shadow and the transposed copies follow p->P
 }
 extern "C" int afr_op_ema(float* e, const float* p, int64_t n, float decay, const float* sumsq_dev, void* stream) {
@@ -955,16 +962,16 @@ static SheetParams sheet_params(const afr_plan* p) {
 // The sheet backward's stage 1 after its dz product: the fused front-end reverse into per-block slabs, registered in rt
 static int sheet_front_bwd(afr_plan* p, hipStream_t s, RTable& rt, double flops_per_string) {
     const afr_config& c = p->cfg;
-    const int B = p->last_B;
-    SheetDims d{p->last_L, c.max_length, c.embed_dim, c.heads, c.fc_dim, c.vocab};
+    const int B = p->last.B;
+    SheetDims d{p->last.L, c.max_length, c.embed_dim, c.heads, c.fc_dim, c.vocab};
     float* slabs = (float*)(p->ws + p->o_slab_e);
     // a slab is laid out like the flat buffer's first s_wout floats: the 10 small tensors (pos .. fc1.bias)
     SheetSlabOff so{(int)p->s_pos, (int)p->s_emb, (int)p->s_win, (int)p->s_bin, (int)p->s_wo, (int)p->s_bo, (int)p->s_g,
                     (int)p->s_b, (int)p->s_w1, (int)p->s_b1, (int)p->s_wout};
     {
         ProfScope ps(p, s, "sheet_bwd", flops_per_string * B, 0.0);
-        HIPCHK(afr_launch_sheet_bwd(c.dtype, d, sheet_params(p), make_drop(p, p->last_training, p->last_step), p->last_x,
-                                    p->last_ldx, B, p->ws + p->o_dz, c.ln_eps, slabs, so, s));
+        HIPCHK(afr_launch_sheet_bwd(c.dtype, d, sheet_params(p), make_drop(p, p->last.training, p->last.step), p->last.x,
+                                    p->last.ldx, B, p->ws + p->o_dz, c.ln_eps, slabs, so, s));
     }
     afr_rtable_add(rt, p->G, slabs, afr_sheet_blocks(B), (long long)so.total, (long long)so.total);
     return AFR_OK;
@@ -994,7 +1001,7 @@ static PairPlan pair_plan_for(const afr_plan* p, const afr_plan::Layer& l, int B
 }
 // A training forward at batch B runs the first layer as a combination table when every consumer of h1 / h0 can gather: the
 // second layer's forward on the 256x128 ring kernel, its gradient pair as a cooperative 256x256 launch, the fused first-layer
-// backward.
+// backward.  Decided once per call, before its first launch (decide_step, forward_loss_impl), and handed to forward_impl.
 static bool combo_for(const afr_plan* p, int B) {
     if (!p->combo_ok || p->layers.size() < 3) return false;
     const auto& l2 = p->layers[1];
@@ -1003,7 +1010,8 @@ static bool combo_for(const afr_plan* p, int B) {
 
 // ------------------------------------------------------------------------------------- forward
 static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int B, int L, float* y, int training,
-                        uint64_t step, void* stream, const LossArgs* fl /* the plan's, fused slots */) {
+                        uint64_t step, void* stream, const LossArgs* fl /* the plan's, fused slots */, bool combo = false,
+                        LossSum* defer = nullptr /* glyph: the last GEMM only stores its loss partials; *defer = how to add them */) {
     if (!p || !p->P) return fail(AFR_ESTATE, "plan has no bound parameters");
     if (training || fl) if (int rc = ema_guard(p, "a training forward")) return rc;
     DevGuard dg(p->device);
@@ -1014,6 +1022,7 @@ static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int 
     const int Pix = c.out_h * c.out_w;
     uint32_t* err = (uint32_t*)(p->ws + p->o_err);
     void* u = p->ws + p->o_u;
+    int Ldone = 1;      // the length the backward works with: the sheet model's is clipped
     if (c.kind == AFR_KIND_SHEET) {
         if (L <= 0) return fail(AFR_EINVAL, "sequence length must be positive");
         const int Lc = L < c.max_length ? L : c.max_length;               // model.py:163-164
@@ -1027,8 +1036,7 @@ static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int 
         if (fl) g.loss = *fl;
         int rc = run_gemm(p, s, g);
         if (rc) return rc;
-        p->last_L = Lc;
-        p->last_ldx = L;
+        Ldone = Lc;
     } else if (c.kind == AFR_KIND_PIXEL) {
         // BASELINE configs[4] (oracle.pixel_forward).  Token-wise kernels in pixel.hip, every Linear on the GEMM
         // kernels; the residual stream stays f32; every block keeps what its backward needs (its two residual inputs, LayerNorm
@@ -1076,14 +1084,11 @@ static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int 
             HIPCHK(afr_launch_pixel_head(c.dtype, (const float*)(p->ws + p->pxs.back().h1), (float*)(p->ws + p->o_hf), a, p->P + p->px_lnfg, p->P + p->px_lnfb,
                                          p->P + p->px_wout, p->P + p->px_bout, (float*)u, y, rows, d, c.ln_eps, s, c.loss));
         }
-        p->last_x = x; p->last_font = font; p->last_B = B; p->last_L = 1; p->last_training = training; p->last_step = step;
-        p->next_stage = 0; p->combo_on = false; p->mbits_on = false;
-        p->have_du = false; p->have_u = fl == nullptr;
         if (fl) {        // the loss on the f32 pre-clamp output (model.py:156,268-270): du in place over u
             ProfScope ps(p, s, fl->kind == AFR_LOSS_BCE ? "bce_grad" : "mse_grad", 0.0, (double)rows * 9.0);
             HIPCHK(afr_launch_mse_grad(AFR_F32, u, u, B, Pix, loss_slots(*fl, (float*)(p->ws + p->o_loss), false), s));
-            p->have_du = true;
         }
+        p->last.forward_done(x, font, B, 1, L, training, step, fl ? afr_plan::Last::DU : afr_plan::Last::U);
         return AFR_OK;
     } else {
         if (c.n_fonts > 0 && !font) return fail(AFR_EINVAL, "font ids are required when n_fonts > 0");
@@ -1091,7 +1096,6 @@ static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int 
         const int nl = (int)p->layers.size();
         const float* femb = c.n_fonts > 0 ? p->P + p->font_off : nullptr;
         int first = 0;
-        const bool combo = fl != nullptr && p->k0 && combo_for(p, B);
         if (combo) {
             // training step: the first layer as a combination table
             const auto& l = p->layers[0];
@@ -1124,26 +1128,22 @@ static int forward_impl(afr_plan* p, const int64_t* x, const int64_t* font, int 
             if (combo && i == 1) { g.a_rowmap = (const int*)(p->ws + p->o_cidx); g.lda = p->h1c_ld; }
             if (bits && !last && p->o_mbits[i]) { g.mask_out = (unsigned char*)(p->ws + p->o_mbits[i]); g.ldmask = l.N / 8; }
             if (last && fl) g.loss = *fl;
-            if (last && fl && !fl->counter) {        // deferred sum: remember where the partials are and how they were produced
-                p->loss_defer.partial = fl->partial; p->loss_defer.inv_n = fl->inv_n; p->loss_defer.loss_accum = fl->loss_accum;
-                afr_gemm_tile_launch_shape(p->gemm_dtype, g, &p->loss_defer.n, &p->loss_defer.bd);
+            if (last && fl && defer) {        // deferred sum: no ticket; tell the caller where the partials are and how they were produced
+                g.loss.counter = nullptr;
+                defer->partial = fl->partial; defer->inv_n = fl->inv_n; defer->loss_accum = fl->loss_accum;
+                afr_gemm_tile_launch_shape(p->gemm_dtype, g, &defer->n, &defer->bd);
             }
             int rc = run_gemm(p, s, g);
             if (rc) return rc;
             h = outp;
         }
-        p->last_L = 1;
     }
     if (y) {
         ProfScope ps(p, s, c.loss == AFR_LOSS_BCE ? "sigmoid_out" : "clamp_out", 0.0, 0.0);
         HIPCHK(afr_launch_clamp_out(c.dtype, u, y, (long long)B * Pix, s, c.loss));
     }
-    p->last_x = x; p->last_font = font; p->last_B = B; p->last_training = training; p->last_step = step;
-    p->next_stage = 0;
-    p->combo_on = c.kind == AFR_KIND_GLYPH && fl != nullptr && p->k0 && combo_for(p, B);
-    p->mbits_on = c.kind == AFR_KIND_GLYPH && fl != nullptr && c.dtype == AFR_BF16;
-    p->have_du = fl != nullptr;      // with the loss fused into the last layer's epilogue the buffer already holds du
-    p->have_u = fl == nullptr;
+    // (with the loss fused into the last layer's epilogue the buffer already holds du)
+    p->last.forward_done(x, font, B, Ldone, L, training, step, fl ? afr_plan::Last::DU : afr_plan::Last::U, combo, c.kind == AFR_KIND_GLYPH && fl && c.dtype == AFR_BF16);
     return AFR_OK;
 }
 extern "C" int afr_forward(afr_plan* p, const int64_t* x, const int64_t* font, int B, int L, float* y, int training,
@@ -1163,7 +1163,7 @@ static int loss_grad_impl(afr_plan* p, const void* target, int tdtype, const int
     if (!p || !p->P) return fail(AFR_ESTATE, "plan has no bound parameters");
     DevGuard dg(p->device);
     if (int rc = check_loss_args(target, tdtype, mean_elems, loss_accum)) return rc;
-    if (B != p->last_B) return fail(AFR_ESTATE, "loss_grad batch %d does not match the last forward (%d)", B, p->last_B);
+    if (B != p->last.B) return fail(AFR_ESTATE, "loss_grad batch %d does not match the last forward (%d)", B, p->last.B);
     hipStream_t s = (hipStream_t)stream;
     const int Pix = p->cfg.out_h * p->cfg.out_w;
     void* u = p->ws + p->o_u;
@@ -1171,7 +1171,7 @@ static int loss_grad_impl(afr_plan* p, const void* target, int tdtype, const int
     ProfScope ps(p, s, p->cfg.loss == AFR_LOSS_BCE ? "bce_grad" : "mse_grad", 0.0, (double)B * Pix * (2.0 * p->act_bytes + tb));
     HIPCHK(afr_launch_mse_grad(p->cfg.kind == AFR_KIND_PIXEL ? AFR_F32 : p->cfg.dtype, u, u, B, Pix,      // (the pixel transformer's pre-clamp output is f32 in both modes)
                                loss_args(p, false, target, tdtype, rowmap, mean_elems, loss_accum), s));
-    p->have_du = true; p->have_u = false;
+    p->last.have_du = true; p->last.have_u = false;
     return AFR_OK;
 }
 extern "C" int afr_loss_grad(afr_plan* p, const void* target, int tdtype, int B, int64_t mean_elems, float* loss_accum,
@@ -1190,9 +1190,9 @@ static int eval_impl(afr_plan* p, const void* target, int tdtype, const int* row
     if (B <= 0 || B > p->cfg.max_batch) return fail(AFR_EINVAL, "batch %d outside 1..max_batch=%d", B, p->cfg.max_batch);
     if (((uintptr_t)stats & 15) || ((uintptr_t)q & 7) || ((uintptr_t)loss_rows & 3) || ((uintptr_t)target & (tdtype == AFR_TARGET_U8 ? 7 : 15)))
         return fail(AFR_EINVAL, "afr_eval: stats must be 16-byte aligned, q 8-byte, uint8 targets 8-byte, float32 targets 16-byte");
-    if (p->last_B <= 0) return fail(AFR_ESTATE, "afr_eval needs afr_forward first");
-    if (B != p->last_B) return fail(AFR_ESTATE, "afr_eval batch %d does not match the last forward (%d)", B, p->last_B);
-    if (!p->have_u) return fail(AFR_ESTATE, "afr_eval: the output buffer no longer holds u (a loss has written du over it); run afr_forward again");
+    if (p->last.B <= 0) return fail(AFR_ESTATE, "afr_eval needs afr_forward first");
+    if (B != p->last.B) return fail(AFR_ESTATE, "afr_eval batch %d does not match the last forward (%d)", B, p->last.B);
+    if (!p->last.have_u) return fail(AFR_ESTATE, "afr_eval: the output buffer no longer holds u (a loss has written du over it); run afr_forward again");
     DevGuard dg(p->device);
     hipStream_t s = (hipStream_t)stream;
     const int Pix = p->cfg.out_h * p->cfg.out_w;
@@ -1212,10 +1212,10 @@ extern "C" int afr_set_output_grad(afr_plan* p, const float* dy, int B, void* st
     if (!p || !p->P) return fail(AFR_ESTATE, "plan has no bound parameters");
     DevGuard dg(p->device);
     if (!dy) return fail(AFR_EINVAL, "dy is null");
-    if (B != p->last_B) return fail(AFR_ESTATE, "batch %d does not match the last forward (%d)", B, p->last_B);
+    if (B != p->last.B) return fail(AFR_ESTATE, "batch %d does not match the last forward (%d)", B, p->last.B);
     HIPCHK(afr_launch_clamp_bwd(p->cfg.kind == AFR_KIND_PIXEL ? AFR_F32 : p->cfg.dtype, p->ws + p->o_u, dy, (long long)B * p->cfg.out_h * p->cfg.out_w, (hipStream_t)stream,
                                 p->cfg.loss));
-    p->have_du = true; p->have_u = false;
+    p->last.have_du = true; p->last.have_u = false;
     return AFR_OK;
 }
 
@@ -1236,7 +1236,7 @@ extern "C" int afr_set_output_grad(afr_plan* p, const float* dy, int B, void* st
 static int pixel_backward(afr_plan* p, hipStream_t s, int stage, int64_t* g_off, int64_t* g_len) {
     const afr_config& c = p->cfg;
     RTable rt;
-    const int B = p->last_B, d = c.embed_dim, ff = c.fc_dim, T = c.out_h * c.out_w, C = c.n_fonts > 0 ? 2 : 1;
+    const int B = p->last.B, d = c.embed_dim, ff = c.fc_dim, T = c.out_h * c.out_w, C = c.n_fonts > 0 ? 2 : 1;
     const long long rows = (long long)B * T;
     const int nbp = afr_pixel_bwd_blocks(rows);
     float* du = (float*)(p->ws + p->o_u);
@@ -1313,36 +1313,36 @@ static int pixel_backward(afr_plan* p, hipStream_t s, int stage, int64_t* g_off,
     if (l > 0) return AFR_OK;
     // positional table: the sum over the batch of the gradient of the residual stream's first value (model.py:140-141 idiom)
     HIPCHK(afr_launch_reduce(p->G + p->px_pos, dh, B, (long long)T * d, (long long)T * d, 1.f, 0, s));
-    HIPCHK(afr_launch_pixel_ctx_bwd((const float*)(p->ws + p->o_dctx), p->last_x, p->last_font, B, d, c.vocab, c.n_fonts, p->G + p->px_emb,
+    HIPCHK(afr_launch_pixel_ctx_bwd((const float*)(p->ws + p->o_dctx), p->last.x, p->last.font, B, d, c.vocab, c.n_fonts, p->G + p->px_emb,
                                     p->px_font >= 0 ? p->G + p->px_font : nullptr, s));
     return AFR_OK;
 }
 
-static int backward_stage_impl(afr_plan* p, int stage, int64_t* g_off, int64_t* g_len, hipStream_t s, RTable* shared_rt) {
+// step: the optimizer step this backward is part of (afr_train_step's staged fused path), NULL for a backward on its own
+static int backward_stage_impl(afr_plan* p, int stage, int64_t* g_off, int64_t* g_len, hipStream_t s, RTable* shared_rt, StepCtx* step = nullptr) {
     const afr_config& c = p->cfg;
-    const int B = p->last_B;
+    const int B = p->last.B;
     void* du = p->ws + p->o_u;
     int rc;
     // slab reductions: flushed per stage (so the stage's gradient range is final), or deferred to ONE grouped launch
     // at the end of a monolithic afr_backward (shared_rt)
     RTable local_rt;
     RTable& rt = shared_rt ? *shared_rt : local_rt;
-    auto flush = [&]() -> int { return shared_rt ? AFR_OK : run_reduce_group(p, s, rt); };
+    auto done = [&](int64_t off, int64_t len) -> int {      // the stage's last step: its slabs summed, its gradient range reported
+        if (int r = shared_rt ? AFR_OK : run_reduce_group(p, s, rt)) return r;
+        if (g_off) *g_off = off;
+        if (g_len) *g_len = len;
+        return AFR_OK;
+    };
     if (c.kind == AFR_KIND_PIXEL) return pixel_backward(p, s, stage, g_off, g_len);     // (its slab reductions are flushed per stage inside)
     if (c.kind == AFR_KIND_SHEET) {
         if (stage == 0) {
             if ((rc = run_dw(p, s, p->layers[0], du, p->ws + p->o_z, B, rt))) return rc;
-            if ((rc = flush())) return rc;
-            if (g_off) *g_off = p->s_wout;
-            if (g_len) *g_len = p->total - p->s_wout;
-            return AFR_OK;
+            return done(p->s_wout, p->total - p->s_wout);
         }
         if ((rc = run_gemm(p, s, lin_dx(p, p->layers[0], du, p->ws + p->o_dz, nullptr, B)))) return rc;
         if ((rc = sheet_front_bwd(p, s, rt, 7.0e6))) return rc;       // partial recompute + reverse: ~7 MFLOP of f32 work per string
-        if ((rc = flush())) return rc;
-        if (g_off) *g_off = 0;
-        if (g_len) *g_len = p->s_wout;
-        return AFR_OK;
+        return done(0, p->s_wout);
     }
     const int nl = (int)p->layers.size();
     const int i = nl - 1 - stage;
@@ -1355,18 +1355,17 @@ static int backward_stage_impl(afr_plan* p, int stage, int64_t* g_off, int64_t* 
         // and the per-table-row segment sums; a small kernel turns those into dEmb / dFont.  No input-gradient GEMM,
         // no scatter-add.
         const int K0 = p->k0, E = c.embed_dim;
-        if (p->l1f && !(c.reserved & AFR_CFG_L1_BWD_UNFUSED)) {
+        if (l1_bwd_fused(p)) {
             // throughput mode: one kernel per 64 glyphs (gemm.hip: glyph_l1_bwd_fused_kernel) -> [dW1 | db1 | dTab] slabs
             float* sl = (float*)(p->ws + p->o_l1f);
             const int CS = afr_glyph_l1_bwd_fused_split(B, l.N), nb = afr_glyph_l1_bwd_fused_blocks(B, l.N), nc = l.N / CS;
             const long long st = afr_glyph_l1_bwd_fused_slab_floats(B, l.N, c.vocab, c.n_fonts);
             {
                 ProfScope ps(p, s, "glyph_l1_bwd_fused", 2.0 * B * l.N * (2.0 * E + 1.0), (double)B * l.N * 2.0 + (double)nb * st * 4.0);
-                if (p->combo_on) HIPCHK(afr_launch_glyph_l1_bwd_fused(dy, l.N, p->ws + p->o_h0c, E, p->ws + p->o_w1t, p->last_x, p->last_font, B, l.N,
-                                                                      c.vocab, c.n_fonts, sl, s, (const int*)(p->ws + p->o_cidx), &p->loss_defer));
-                else HIPCHK(afr_launch_glyph_l1_bwd_fused(dy, l.N, a, K0, p->ws + p->o_w1t, p->last_x, p->last_font, B, l.N, c.vocab, c.n_fonts, sl, s,
-                                                          nullptr, &p->loss_defer));
-                p->loss_defer = LossSum{};
+                const LossSum* sum = step ? &step->loss : nullptr;      // the step's deferred loss partials: one more workgroup adds them
+                if (p->last.combo_on) HIPCHK(afr_launch_glyph_l1_bwd_fused(dy, l.N, p->ws + p->o_h0c, E, p->ws + p->o_w1t, p->last.x, p->last.font, B, l.N,
+                                                                      c.vocab, c.n_fonts, sl, s, (const int*)(p->ws + p->o_cidx), sum));
+                else HIPCHK(afr_launch_glyph_l1_bwd_fused(dy, l.N, a, K0, p->ws + p->o_w1t, p->last.x, p->last.font, B, l.N, c.vocab, c.n_fonts, sl, s, nullptr, sum));
             }
             // block = (row block, column range): range cs's slabs are blocks cs, cs + CS, ...; every block has a dTab partial
             for (int cs = 0; cs < CS; ++cs) {
@@ -1375,10 +1374,7 @@ static int backward_stage_impl(afr_plan* p, int stage, int64_t* g_off, int64_t* 
             }
             afr_rtable_add(rt, p->G + p->emb_off, sl + (size_t)nc * E + nc, nb, st, (long long)c.vocab * E);
             if (c.n_fonts > 0) afr_rtable_add(rt, p->G + p->font_off, sl + (size_t)nc * E + nc + (size_t)c.vocab * E, nb, st, (long long)c.n_fonts * E);
-            if ((rc = flush())) return rc;
-            if (g_off) *g_off = 0;
-            if (g_len) *g_len = l.b_off + (l.N + 63) / 64 * 64;
-            return AFR_OK;
+            return done(0, l.b_off + (l.N + 63) / 64 * 64);
         }
         int sk = choose_splitk(l.N, K0, B);
         if (sk > l.sk) sk = l.sk;
@@ -1398,56 +1394,45 @@ static int backward_stage_impl(afr_plan* p, int stage, int64_t* g_off, int64_t* 
         afr_rtable_add(rt, p->G + l.w_off, dw1, 1, 0, (long long)l.N * E);
         afr_rtable_add(rt, p->G + p->emb_off, part, nb, pstride, (long long)c.vocab * E);
         if (c.n_fonts > 0) afr_rtable_add(rt, p->G + p->font_off, part + (size_t)c.vocab * E, nb, pstride, (long long)c.n_fonts * E);
-        if ((rc = flush())) return rc;
-        if (g_off) *g_off = 0;
-        if (g_len) *g_len = l.b_off + (l.N + 63) / 64 * 64;
-        return AFR_OK;
+        return done(0, l.b_off + (l.N + 63) / 64 * 64);
     }
     // A layer's two gradient products both consume dy and are independent: when the input-gradient product alone fills the
     // chip with 256x128 tiles they go out as ONE grouped launch, the weight gradient first and split so that one of its
     // blocks runs twice the K-tiles of an input-gradient block (half the slabs of the stand-alone choice; a CU draws
     // either one long block or two short ones).
     const PairPlan pp = pair_plan_for(p, l, B);
-    const int sk_group = pp.sk_group, tile256 = pp.tile256;
-    const bool coop = pp.coop;
     // the layer whose input is the first layer's output: after a combination-table forward its rows are gathered from H1c
-    const bool gath = p->combo_on && i == 1;
+    const bool gath = p->last.combo_on && i == 1;
     const int* cidx = gath ? (const int*)(p->ws + p->o_cidx) : nullptr;
     if (gath) {
-        if (!coop) return fail(AFR_ESTATE, "combination-table forward without a cooperative gradient pair (batch changed?)");
+        if (!pp.coop) return fail(AFR_ESTATE, "combination-table forward without a cooperative gradient pair (batch changed?)");
         a = p->ws + p->o_h1c;
     }
-    p->pend_tile256 = tile256;
-    p->defer = sk_group > 0;
-    if ((rc = run_dw(p, s, l, dy, a, B, rt, sk_group, coop, cidx, p->h1c_ld))) { drop_pending(p); return rc; }
+    GemmBatch batch; batch.tile256 = pp.tile256;
+    GemmBatch* const bp = pp.sk_group > 0 ? &batch : nullptr;      // no grouped launch at this shape: each product goes out on its own
+    if ((rc = run_dw(p, s, l, dy, a, B, rt, pp.sk_group, pp.coop, cidx, p->h1c_ld, bp, step))) return rc;
     void* dx = p->ws + p->o_d[stage & 1];
     GemmParams g = lin_dx(p, l, dy, dx, i > 0 ? a : nullptr, B);
     if (gath) { g.aux_rowmap = cidx; g.ldaux = p->h1c_ld; }      // the ReLU gate is read from the gathered H1c rows
-    if (p->mbits_on && i >= 2 && p->o_mbits[i - 1]) { g.mask_in = (const unsigned char*)(p->ws + p->o_mbits[i - 1]); g.ldmask = l.K / 8; }
-    if ((rc = run_gemm(p, s, g))) { drop_pending(p); return rc; }
-    if ((rc = flush_gemms(p, s))) return rc;
+    if (p->last.mbits_on && i >= 2 && p->o_mbits[i - 1]) { g.mask_in = (const unsigned char*)(p->ws + p->o_mbits[i - 1]); g.ldmask = l.K / 8; }
+    if ((rc = run_gemm(p, s, g, bp))) return rc;
+    if ((rc = flush_gemms(p, s, batch))) return rc;
     const int64_t end = l.b_off + (l.N + 63) / 64 * 64;
     if (i > 0) {
-        if ((rc = flush())) return rc;
-        if (g_off) *g_off = l.w_off;
-        if (g_len) *g_len = end - l.w_off;
-        return AFR_OK;
+        return done(l.w_off, end - l.w_off);
     }
     float* slabs = (float*)(p->ws + p->o_slab_e);
     const int blocks = afr_embed_bwd_blocks(B);
     const long long rows = c.vocab + c.n_fonts;
     {
         ProfScope ps(p, s, "glyph_embed_bwd", 0.0, 0.0);
-        HIPCHK(afr_launch_glyph_embed_bwd(c.dtype, dx, p->last_x, p->last_font, B, c.embed_dim, c.vocab, c.n_fonts, slabs, s));
+        HIPCHK(afr_launch_glyph_embed_bwd(c.dtype, dx, p->last.x, p->last.font, B, c.embed_dim, c.vocab, c.n_fonts, slabs, s));
     }
     const long long stride = rows * c.embed_dim;
     afr_rtable_add(rt, p->G + p->emb_off, slabs, blocks, stride, (long long)c.vocab * c.embed_dim);
     if (c.n_fonts > 0)
         afr_rtable_add(rt, p->G + p->font_off, slabs + (size_t)c.vocab * c.embed_dim, blocks, stride, (long long)c.n_fonts * c.embed_dim);
-    if ((rc = flush())) return rc;
-    if (g_off) *g_off = 0;
-    if (g_len) *g_len = end;
-    return AFR_OK;
+    return done(0, end);
 }
 
 extern "C" int afr_backward_stages(const afr_plan* p) {
@@ -1462,12 +1447,12 @@ extern "C" int afr_backward_stage(afr_plan* p, int stage, int64_t* grad_offset, 
     DevGuard dg(p->device);
     const int n = afr_backward_stages(p);
     if (stage < 0 || stage >= n) return fail(AFR_EINVAL, "stage %d outside 0..%d", stage, n - 1);
-    if (stage == 0 && !p->have_du) return fail(AFR_ESTATE, "backward needs a forward + loss first");
-    if (stage != p->next_stage) return fail(AFR_ESTATE, "stages must run in order: expected %d, got %d", p->next_stage, stage);
+    if (stage == 0 && !p->last.have_du) return fail(AFR_ESTATE, "backward needs a forward + loss first");
+    if (stage != p->last.next_stage) return fail(AFR_ESTATE, "stages must run in order: expected %d, got %d", p->last.next_stage, stage);
     int rc = backward_stage_impl(p, stage, grad_offset, grad_elems, (hipStream_t)stream, nullptr);
     if (rc) return rc;
-    p->next_stage = stage + 1 == n ? 0 : stage + 1;
-    if (stage + 1 == n) p->have_du = false;
+    p->last.next_stage = stage + 1 == n ? 0 : stage + 1;
+    if (stage + 1 == n) p->last.have_du = false;
     return AFR_OK;
 }
 
@@ -1475,7 +1460,7 @@ extern "C" int afr_backward(afr_plan* p, void* stream) {
     if (!p || !p->P || !p->G) return fail(AFR_ESTATE, "plan has no bound parameter/gradient buffers");
     if (int rc = ema_guard(p, "afr_backward")) return rc;
     DevGuard dg(p->device);
-    if (!p->have_du) return fail(AFR_ESTATE, "afr_backward needs afr_forward + afr_loss_grad first");
+    if (!p->last.have_du) return fail(AFR_ESTATE, "afr_backward needs afr_forward + afr_loss_grad first");
     const int n = afr_backward_stages(p);
     RTable rt;
     for (int st = 0; st < n; ++st) {
@@ -1484,8 +1469,8 @@ extern "C" int afr_backward(afr_plan* p, void* stream) {
     }
     int rc = run_reduce_group(p, (hipStream_t)stream, rt);
     if (rc) return rc;
-    p->next_stage = 0;
-    p->have_du = false;
+    p->last.next_stage = 0;
+    p->last.have_du = false;
     return AFR_OK;
 }
 
@@ -1617,7 +1602,7 @@ extern "C" int afr_adamw_step(afr_plan* p, float lr, float b1, float b2, float e
         return fail(AFR_ESTATE, p && p->opt_kind == OPT_LION ? "Lion needs params, grads and exp_avg bound" : "AdamW needs params, grads and both moments bound");
     if (int rc = ema_guard(p, "an optimizer step")) return rc;
     DevGuard dg(p->device);
-    if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
+    if (int rc = check_step_count(t)) return rc;
     hipStream_t s = (hipStream_t)stream;
     bf16_t* shadow = shadow_rd(p);        // nothing reads the weights concurrently: updated in place
     const float* sumsq = nullptr;
@@ -1667,7 +1652,8 @@ static int split_segments_at_groups(const afr_plan* p, RTable& rt) {
     rt = nt;
     return AFR_OK;
 }
-static int reduce_and_step(afr_plan* p, hipStream_t s, RTable& rt, const AdamArgs& h, int64_t skip_off = -1) {
+static int reduce_and_step(afr_plan* p, hipStream_t s, RTable& rt, const StepCtx& step, int64_t skip_off = -1) {
+    const AdamArgs& h = step.h;
     bf16_t* shadow = shadow_wr(p);        // every tensor's new bf16 copy goes to the write shadow; the roles swap below
     const bool lion = p->opt_kind == OPT_LION;
     const bool grouped = !p->groups.empty();
@@ -1687,7 +1673,7 @@ static int reduce_and_step(afr_plan* p, hipStream_t s, RTable& rt, const AdamArg
     for (const Tensor& tn : p->params) {
         if (tn.off == skip_off) continue;
         bool done = false;                 // updated inside its weight-gradient GEMM (cooperative split-K tail)
-        for (int64_t o : p->adam_done) done = done || o == tn.off;
+        for (int k = 0; k < step.ndone; ++k) done = done || step.done[k] == tn.off;
         if (done) continue;
         // covered by the (disjoint) segments of the grouped reduce -- possibly several per tensor (column ranges)?
         int64_t cov = 0;
@@ -1704,7 +1690,6 @@ static int reduce_and_step(afr_plan* p, hipStream_t s, RTable& rt, const AdamArg
                                 grouped ? adam_hyper(ht, p->opt_kind) : rt.ad, 1.f, s, nullptr, 0.f, p->opt_kind));
     }
     if (p->o_shadow2) p->shadow_cur ^= 1;   // every tensor has been rewritten: the write shadow is the current one now
-    p->adam_done.clear();
     return ema_step(p, nullptr, s);         // the step's last parameter write is behind us (never a clipping plan here)
 }
 
@@ -1712,26 +1697,26 @@ static int reduce_and_step(afr_plan* p, hipStream_t s, RTable& rt, const AdamArg
 // parameters) gets its AdamW update in the epilogue of dW = du^T.z, tile by tile, so its gradient is never written to
 // or re-read from HBM (-8 bytes/parameter/step) and the update traffic overlaps other tiles' MFMA work.  dz = du.W
 // runs FIRST because it must see the pre-update weights.  The small tensors take the ordinary AdamW kernel.
-static bool fused_step_eligible(const afr_plan* p, int B) {
-    return p->cfg.kind == AFR_KIND_SHEET && moments_bound(p) && choose_splitk(p->layers[0].N, p->layers[0].K, B) == 1;
+static bool fused_step_eligible(const afr_plan* p, int B) {      // (the model and the shape; decide_step adds the rest)
+    return p->cfg.kind == AFR_KIND_SHEET && choose_splitk(p->layers[0].N, p->layers[0].K, B) == 1;
 }
-static int sheet_fused_step(afr_plan* p, hipStream_t s, const AdamArgs& h) {
+static int sheet_fused_step(afr_plan* p, hipStream_t s, const StepCtx& step) {
     const afr_plan::Layer& l = p->layers[0];      // fc_output
-    const int B = p->last_B;
+    const int B = p->last.B;
     void* du = p->ws + p->o_u;
     bf16_t* shadow = shadow_rd(p);        // the sheet model keeps ONE shadow: its input-gradient product runs before the update
     int rc;
     if ((rc = run_gemm(p, s, lin_dx(p, l, du, p->ws + p->o_dz, nullptr, B)))) return rc;
     GemmParams g = lin_dw(du, p->ws + p->o_z, p->G + l.w_off, p->G + l.b_off, B, l.N, l.K);
-    set_fused_opt(p, g, l.w_off, shadow, h);
+    set_fused_opt(p, g, l.w_off, shadow, step.h);
     if ((rc = run_gemm(p, s, g))) return rc;
     RTable rt;
     if ((rc = sheet_front_bwd(p, s, rt, 9.0e6))) return rc;
     // the ten small tensors are updated inside the slab reduction; fc_output.bias by the plain kernel; fc_output.weight
     // was updated in the dW GEMM above (skipped here)
-    if ((rc = reduce_and_step(p, s, rt, h, l.w_off))) return rc;
-    p->have_du = false;
-    p->next_stage = 0;
+    if ((rc = reduce_and_step(p, s, rt, step, l.w_off))) return rc;
+    p->last.have_du = false;
+    p->last.next_stage = 0;
     return AFR_OK;
 }
 
@@ -1793,8 +1778,7 @@ static int glyph1_fused(afr_plan* p, const int64_t* x, const int64_t* font, cons
             if (tn.off == l2.w_off) { sg.shT = (bf16_t*)(p->ws + p->o_w2t); sg.tN = Pix; sg.tK = N1; }
         }
     }
-    p->last_x = x; p->last_font = font; p->last_B = B; p->last_L = 1; p->last_training = 1;
-    p->have_du = false; p->have_u = false; p->next_stage = 0;
+    p->last.forward_done(x, font, B, /*L*/ 1, /*ldx*/ 1, /*training*/ 1, /*step*/ 0, afr_plan::Last::NOTHING);      // (nothing for a backward or an evaluation: the step is complete)
     return AFR_OK;
 }
 
@@ -1802,13 +1786,41 @@ static int forward_loss_impl(afr_plan* p, const int64_t* x, const int64_t* font,
                              int64_t mean_elems, float* loss_accum, uint64_t step, void* stream) {
     if (int rc = check_loss_args(target, tdtype, mean_elems, loss_accum)) return rc;
     const LossArgs fl = loss_args(p, true, target, tdtype, rowmap, mean_elems, loss_accum);
-    return forward_impl(p, x, font, B, L, nullptr, 1, step, stream, &fl);
+    return forward_impl(p, x, font, B, L, nullptr, 1, step, stream, &fl, combo_for(p, B));
 }
 extern "C" int afr_forward_loss(afr_plan* p, const int64_t* x, const int64_t* font, const void* target, int tdtype, int B, int L,
                                 int64_t mean_elems, float* loss_accum, uint64_t step, void* stream) {
     return forward_loss_impl(p, x, font, target, tdtype, nullptr, B, L, mean_elems, loss_accum, step, stream);
 }
 
+// ---- the way a training step goes: decided ONCE per call, before its first launch
+enum StepPath {
+    STEP_GLYPH1,          // small one-hidden-layer glyph net: forward + loss + backward in ONE launch, then the grouped reduce
+    STEP_SHEET_FUSED,     // sheet model: fc_output.weight is stepped inside its weight-gradient GEMM (sheet_fused_step)
+    STEP_STAGED_FUSED,    // the staged backward as one pass that carries the step (StepCtx), then reduce_and_step
+    STEP_UNFUSED          // afr_backward materialises every gradient, then afr_adamw_step when the call steps
+};
+// fuse_opt: the optimizer runs inside the path's own launches (GLYPH1: inside its grouped reduce); combo: combo_for
+struct StepPlan { StepPath path; bool fuse_opt, defer_loss, combo; };
+// Refuses (nothing enqueued, the plan unchanged) or fills `d` from the bound buffers, the optimizer and clipping settings, cfg.reserved
+static int decide_step(const afr_plan* p, int B, int do_step, int64_t t, StepPlan& d) {
+    if (!p->G) return fail(AFR_ESTATE, "plan has no bound gradient buffer");
+    if (do_step) if (int rc = check_step_count(t)) return rc;
+    const auto rs = p->cfg.reserved;
+    // (a clipping plan needs the global norm before any update: every gradient is materialised, then afr_adamw_step)
+    const bool fuse = do_step && !(rs & AFR_CFG_UNFUSED_OPTIMIZER) && !(p->clip_norm > 0.f) && moments_bound(p);
+    d = StepPlan{STEP_GLYPH1, fuse, false, false};
+    if (p->fused1 && !(rs & AFR_CFG_NO_FUSED_GLYPH1)) return AFR_OK;
+    d.path = !fuse ? STEP_UNFUSED : fused_step_eligible(p, B) ? STEP_SHEET_FUSED : p->cfg.kind != AFR_KIND_PIXEL ? STEP_STAGED_FUSED : STEP_UNFUSED;
+    d.fuse_opt = d.path != STEP_UNFUSED;
+    // When the call runs the whole backward and the step itself and the first-layer backward is the fused kernel, nothing before
+    // the end of the step reads the loss: the forward's last GEMM only stores its partials (no ticket, no last-block sum at the
+    // end of that launch) and one workgroup appended to the first-layer backward's grid adds them -- the same arithmetic, bit for
+    // bit.  Every other path keeps the ticket.
+    d.defer_loss = d.path == STEP_STAGED_FUSED && l1_bwd_fused(p) && p->gemm_dtype == AFR_BF16;
+    d.combo = combo_for(p, B);
+    return AFR_OK;
+}
 static int train_step_impl(afr_plan* p, const int64_t* x, const int64_t* font, const void* target, int tdtype, const int* rowmap, int B,
                            int L, int64_t mean_elems, float* loss_accum, uint64_t step, int do_step, float lr, float b1,
                            float b2, float eps, float wd, int64_t t, void* stream) {
@@ -1816,56 +1828,40 @@ static int train_step_impl(afr_plan* p, const int64_t* x, const int64_t* font, c
     if ((rc = check_loss_args(target, tdtype, mean_elems, loss_accum))) return rc;
     if (!p || !p->P) return fail(AFR_ESTATE, "plan has no bound parameters");
     if ((rc = ema_guard(p, "afr_train_step"))) return rc;
+    StepPlan d;
+    if ((rc = decide_step(p, B, do_step, t, d))) return rc;
     DevGuard dg(p->device);
-    const AdamArgs h{lr, b1, b2, eps, wd, t};
-    // (a clipping plan needs the global norm before any update: every gradient is materialised, then afr_adamw_step)
-    const bool fuse_opt = do_step && !(p->cfg.reserved & AFR_CFG_UNFUSED_OPTIMIZER) && !(p->clip_norm > 0.f);
-    if (p->fused1 && !(p->cfg.reserved & AFR_CFG_NO_FUSED_GLYPH1)) {
-        // small glyph net: forward + loss + backward in ONE launch, then the grouped reduce (with AdamW when stepping here)
-        if (!p->G) return fail(AFR_ESTATE, "plan has no bound gradient buffer");
-        RTable rt;
-        if ((rc = glyph1_fused(p, x, font, target, tdtype, rowmap, B, mean_elems, loss_accum, (hipStream_t)stream, rt))) return rc;
-        if (fuse_opt && moments_bound(p)) {
-            if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
-            rc = reduce_and_step(p, (hipStream_t)stream, rt, h);
+    hipStream_t s = (hipStream_t)stream;
+    StepCtx sc{AdamArgs{lr, b1, b2, eps, wd, t}};
+    RTable rt;
+    if (d.path != STEP_GLYPH1) {
+        // the loss and its gradient are computed in the epilogue of the last forward GEMM: u never touches HBM
+        const LossArgs fl = loss_args(p, true, target, tdtype, rowmap, mean_elems, loss_accum);
+        if ((rc = forward_impl(p, x, font, B, L, nullptr, 1, step, stream, &fl, d.combo, d.defer_loss ? &sc.loss : nullptr))) return rc;
+    }
+    switch (d.path) {
+    case STEP_GLYPH1:
+        if ((rc = glyph1_fused(p, x, font, target, tdtype, rowmap, B, mean_elems, loss_accum, s, rt))) return rc;
+        if (d.fuse_opt) {
+            rc = reduce_and_step(p, s, rt, sc);
             p->wT_valid = rc == AFR_OK;                 // the reduce's AdamW wrote W1T / W2T beside the shadow
             return rc;
         }
-        if ((rc = run_reduce_group(p, (hipStream_t)stream, rt))) return rc;
-        if (do_step && (rc = afr_adamw_step(p, lr, b1, b2, eps, wd, t, 1.f, stream))) return rc;
-        return AFR_OK;
-    }
-    // the loss and its gradient are computed in the epilogue of the last forward GEMM: u never touches HBM
-    LossArgs fl = loss_args(p, true, target, tdtype, rowmap, mean_elems, loss_accum);
-    // When this call runs the whole backward and the step itself (the branch ending in reduce_and_step below) and the first-layer
-    // backward is the fused kernel, nothing before the end of the step reads the loss: the forward's last GEMM only stores its
-    // partials (no ticket, no last-block sum at the end of that launch) and one workgroup appended to the first-layer backward's
-    // grid adds them -- the same arithmetic, bit for bit.  Every other path keeps the ticket.
-    p->loss_defer = LossSum{};
-    const bool defer_loss = fuse_opt && t >= 1 && !fused_step_eligible(p, B) && moments_bound(p) && p->cfg.kind == AFR_KIND_GLYPH && p->k0 &&
-                            p->l1f && !(p->cfg.reserved & AFR_CFG_L1_BWD_UNFUSED) && p->gemm_dtype == AFR_BF16;
-    if (defer_loss) fl.counter = nullptr;
-    if ((rc = forward_impl(p, x, font, B, L, nullptr, 1, step, stream, &fl))) { p->loss_defer = LossSum{}; return rc; }
-    if (fuse_opt && fused_step_eligible(p, B)) {
-        if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
-        return sheet_fused_step(p, (hipStream_t)stream, h);
-    }
-    if (fuse_opt && moments_bound(p) && p->cfg.kind != AFR_KIND_PIXEL) {
-        if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
-        const int n = afr_backward_stages(p);
-        RTable rt;
+        if ((rc = run_reduce_group(p, s, rt))) return rc;
+        break;
+    case STEP_SHEET_FUSED:
+        return sheet_fused_step(p, s, sc);
+    case STEP_STAGED_FUSED:
         // weight-gradient products with a cooperative split-K tail apply this step's AdamW themselves
-        p->step_on = true; p->adam_done.clear(); p->st = h;
-        for (int st = 0; st < n; ++st)
-            if ((rc = backward_stage_impl(p, st, nullptr, nullptr, (hipStream_t)stream, &rt))) { p->step_on = false; p->loss_defer = LossSum{}; return rc; }
-        p->step_on = false;
-        p->next_stage = 0;
-        p->have_du = false;
-        return reduce_and_step(p, (hipStream_t)stream, rt, h);
+        for (int st = 0, n = afr_backward_stages(p); st < n; ++st)
+            if ((rc = backward_stage_impl(p, st, nullptr, nullptr, s, &rt, &sc))) return rc;
+        p->last.next_stage = 0; p->last.have_du = false;
+        return reduce_and_step(p, s, rt, sc);
+    case STEP_UNFUSED:
+        if ((rc = afr_backward(p, stream))) return rc;
+        break;
     }
-    if ((rc = afr_backward(p, stream))) return rc;
-    if (do_step && (rc = afr_adamw_step(p, lr, b1, b2, eps, wd, t, 1.f, stream))) return rc;
-    return AFR_OK;
+    return do_step ? afr_adamw_step(p, lr, b1, b2, eps, wd, t, 1.f, stream) : AFR_OK;
 }
 extern "C" int afr_train_step(afr_plan* p, const int64_t* x, const int64_t* font, const void* target, int tdtype, int B,
                               int L, int64_t mean_elems, float* loss_accum, uint64_t step, int do_step, float lr, float b1,
@@ -1935,6 +1931,9 @@ extern "C" int afr_train_step_rows(afr_plan* p, const int64_t* rows, int B, int6
                                    int do_step, float lr, float b1, float b2, float eps, float wd, int64_t t, void* stream) {
     int Lc, rc;
     if ((rc = ema_guard(p, "afr_train_step_rows"))) return rc;
+    // the loss arguments and the step count before the staging kernel: a step refused for them enqueues nothing
+    if (p && p->ds_target && (rc = check_loss_args(p->ds_target, p->ds_tdtype, mean_elems, loss_accum))) return rc;
+    if (do_step && (rc = check_step_count(t))) return rc;
     if ((rc = rows_begin(p, rows, B, true, stream, &Lc))) return rc;
     return train_step_impl(p, (const int64_t*)(p->ws + p->o_sx), staged_font(p), p->ds_target, p->ds_tdtype, (const int*)(p->ws + p->o_ridx),
                            B, Lc, mean_elems, loss_accum, step, do_step, lr, b1, b2, eps, wd, t, stream);
@@ -1953,9 +1952,9 @@ extern "C" int afr_error_flags(afr_plan* p, void* stream, uint32_t* out) {
 extern "C" int afr_debug_copy(afr_plan* p, int which, void* dst, size_t cap, size_t* bytes_out, void* stream) {
     if (!p || !p->ws || !dst) return fail(AFR_EINVAL, "plan must be bound and dst non-null");
     DevGuard dg(p->device);
-    if (p->last_B <= 0) return fail(AFR_ESTATE, "no forward has run yet");
+    if (p->last.B <= 0) return fail(AFR_ESTATE, "no forward has run yet");
     const afr_config& c = p->cfg;
-    const size_t B = (size_t)p->last_B, ab = (size_t)p->act_bytes;
+    const size_t B = (size_t)p->last.B, ab = (size_t)p->act_bytes;
     size_t off = 0, bytes = 0;
     if (which == AFR_BUF_U) { off = p->o_u; bytes = B * c.out_h * c.out_w * ab; }
     else if (which == AFR_BUF_Z && c.kind == AFR_KIND_SHEET) { off = p->o_z; bytes = B * c.max_length * c.fc_dim * ab; }
@@ -1992,7 +1991,7 @@ extern "C" int afr_debug_sheet_gather(afr_plan* p, const int64_t* x, int B, int 
     dr.dbg_e0 = e0;
     HIPCHK(afr_launch_sheet_fwd(c.dtype, d, sheet_params(p), dr, x, L, B, p->ws + p->o_z, c.ln_eps, (uint32_t*)(p->ws + p->o_err),
                                 (hipStream_t)stream));
-    p->have_du = false;
+    p->last.have_du = false;
     return AFR_OK;
 }
 
@@ -2106,7 +2105,7 @@ extern "C" int afr_op_adamw(float* p, const float* g, float* m, float* v, void* 
 extern "C" int afr_op_adamw_clip(float* p, const float* g, float* m, float* v, void* shadow, int64_t n, float lr, float b1, float b2,
                                  float eps, float wd, int64_t t, float gscale, const float* sumsq, float max_norm, void* stream) {
     if (!p || !g || !m || !v || !sumsq) return fail(AFR_EINVAL, "null argument");
-    if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
+    if (int rc = check_step_count(t)) return rc;
     if (!(max_norm > 0.f) || std::isinf(max_norm)) return fail(AFR_EINVAL, "max_norm must be finite and > 0, got %g", (double)max_norm);
     DevGuard dg(device_of(p));
     HIPCHK(afr_launch_adamw(p, g, m, v, (bf16_t*)shadow, n, lr, wd, adam_hyper(AdamArgs{lr, b1, b2, eps, wd, t}), gscale, (hipStream_t)stream, sumsq,
@@ -2127,7 +2126,7 @@ extern "C" int afr_op_opt_groups(int kind, float* p, const float* g, float* m, f
                                  const float* sumsq, float max_norm, void* stream) {
     if (kind != AFR_OPT_ADAMW && kind != AFR_OPT_LION) return fail(AFR_EINVAL, "optimizer kind must be AFR_OPT_ADAMW (0) or AFR_OPT_LION (1), got %d", kind);
     if (!p || !g || !m || (kind == AFR_OPT_ADAMW && !v)) return fail(AFR_EINVAL, "null argument");
-    if (t < 1) return fail(AFR_EINVAL, "t starts at 1");
+    if (int rc = check_step_count(t)) return rc;
     if (sumsq && (!(max_norm > 0.f) || std::isinf(max_norm))) return fail(AFR_EINVAL, "max_norm must be finite and > 0, got %g", (double)max_norm);
     DevGuard dg(device_of(p));
     return opt_groups_launch(kind, p, g, m, v, (bf16_t*)shadow, n, first, ranges, n_ranges, AdamArgs{lr, b1, b2, eps, wd, kind == AFR_OPT_LION ? 1 : t}, gscale,
