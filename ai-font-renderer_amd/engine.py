@@ -165,11 +165,14 @@ class Engine:
         for i in range(self.lib.afr_param_count(self._plan)):
             _lib.check(self.lib.afr_param_info(self._plan, i, name, 128, C.byref(off), C.byref(numel), C.byref(ndim), shape))
             self.layout.append((name.value.decode(), tuple(shape[k] for k in range(ndim.value)), off.value, numel.value))
-        self.params = {nm: self.flat_params[o:o + k].view(shp) for nm, shp, o, k in self.layout}
-        self.grads = {nm: self.flat_grads[o:o + k].view(shp) for nm, shp, o, k in self.layout}
+        self.names = [nm for nm, _, _, _ in self.layout]
+        self.params, self.grads = self._views(self.flat_params), self._views(self.flat_grads)
         self.pixels = cfg.pixels
+        self._hw = (self._c.out_h, self._c.out_w)     # of one output: sheet_h x sheet_w, or the glyph's out_h x out_w
         self.t = 0            # AdamW step counter (model.py:310)
-        self._keep = None     # keeps the last inputs alive until backward has consumed them
+        # the tensors of an enqueued call, by slot, each until the next call that fills its slot: "in" (rows, x, font: until backward
+        # has consumed them), "target", "eval", "sumsq", "minus"
+        self._held = {}
         self._last_B = 0      # batch rows of the last forward / forward_rows (evaluate_last)
         self._tstats = {}     # tensor_stats: the record buffers, allocated once per kind of request
         if self.ema_decay is not None:
@@ -182,6 +185,10 @@ class Engine:
         (the engine may live on cuda:k while the process's current device is another GPU)."""
         with torch.cuda.device(self.device):
             _lib.check(fn(*args, _stream(self.device)))
+
+    def _views(self, flat):
+        """The per-tensor views of a flat buffer in the parameter layout, by name."""
+        return {nm: flat[o:o + k].view(shp) for nm, shp, o, k in self.layout}
 
     def _make_plan(self, max_batch):
         if self._plan:
@@ -210,11 +217,10 @@ class Engine:
         """dict name -> multiplier as the float array afr_set_param_groups takes, in layout order (missing names: 1.0); None stays None."""
         if mult is None:
             return None
-        names = [nm for nm, _, _, _ in self.layout]
         for nm in mult:
-            if nm not in names:
+            if nm not in self.names:
                 raise KeyError(f"{nm!r} is no parameter tensor of this model")
-        return (C.c_float * len(names))(*[float(mult.get(nm, 1.0)) for nm in names])
+        return (C.c_float * len(self.names))(*[float(mult.get(nm, 1.0)) for nm in self.names])
 
     def _apply_groups(self):
         """Hand the plan its groups (host-only call; ensure_batch's new plan gets them again) and read the merged table back."""
@@ -283,7 +289,7 @@ class Engine:
         if self.flat_ema is None:
             with torch.cuda.device(self.device):
                 self.flat_ema = torch.zeros(self.n_flat, dtype=torch.float32, device=self.device)
-            self.ema_params = {nm: self.flat_ema[o:o + k].view(shp) for nm, shp, o, k in self.layout}
+            self.ema_params = self._views(self.flat_ema)
         self._apply_ema()
         self.reset_ema()
 
@@ -297,7 +303,7 @@ class Engine:
     def ema_state_dict(self):
         if self.flat_ema is None:
             raise _lib.AfrError("no EMA set (Engine(ema_decay=...) / set_ema)")
-        return {nm: self.ema_params[nm].detach().clone() for nm, _, _, _ in self.layout}
+        return {nm: self.ema_params[nm].detach().clone() for nm in self.names}
 
     def ema_update(self, sumsq=None):
         """Count one optimizer step that the engine did not perform itself (adamw_range on slices: parallel.py) and update the EMA
@@ -305,7 +311,7 @@ class Engine:
         step) leaves the EMA untouched."""
         self._not_in_ema("ema_update")
         self._call(self.lib.afr_ema_update, self._plan, _ptr(sumsq))
-        self._keep_ss = sumsq
+        self._held["sumsq"] = sumsq
 
     @contextlib.contextmanager
     def ema_weights(self):
@@ -369,8 +375,8 @@ class Engine:
             with torch.cuda.device(self.device):
                 self._tstats[key] = torch.empty((len(self.layout), 8), dtype=torch.int32, device=self.device)
         self._call(self.lib.afr_tensor_stats, self._plan, _lib.STAT_KINDS[which], _ptr(minus), _ptr(self._tstats[key]))
-        self._keep_minus = minus
-        return TensorStats(self._tstats[key], [nm for nm, _, _, _ in self.layout])
+        self._held["minus"] = minus
+        return TensorStats(self._tstats[key], self.names)
 
     def _read_clip_stats(self):
         if self._clip_stats is None or not self.max_grad_norm:
@@ -395,25 +401,12 @@ class Engine:
         model has fonts), targets uint8 or float32 [N, pixels] / [N, H, W].  forward_rows / loss_grad_rows / forward_loss_rows /
         train_step_rows then take a vector of row indices; the kernels read the targets where they lie.  The engine holds
         references to the tensors, and binds them again when ensure_batch re-creates the plan."""
-        x, font = self._prep_x(x, font)
-        t, td = self._target(target)
-        if isinstance(self.cfg, SheetConfig):
-            if x.dim() != 2:
-                raise ValueError("sheet model takes int64 [N, L] codes")
-            L = x.shape[1]
-        else:
-            x, L = x.reshape(-1), 1
-        n = x.shape[0]
+        (_, x, font), (_, t), td, n, L, _ = self._batch(x, font, target)
         t = t.view(t.shape[0], -1)
         if t.shape != (n, self.pixels) or (font is not None and font.reshape(-1).shape[0] != n):
             raise ValueError(f"data set of {n} rows: targets {tuple(t.shape)} (expected {(n, self.pixels)}) / font ids do not match")
         self._ds = (x, None if font is None else font.reshape(-1), t, td, n, L)
         self._bind_ds()
-
-    def _rows(self, rows):
-        if self._ds is None:
-            raise _lib.AfrError("no data set bound: call bind_dataset before stepping by rows")
-        return rows.to(self.device, dtype=torch.int64, non_blocking=True).contiguous().reshape(-1)
 
     def ensure_batch(self, B):
         """Grow the plan's workspace for a larger batch; parameters, gradients and moments stay where they are."""
@@ -449,7 +442,7 @@ class Engine:
         self._call(self.lib.afr_sync_params, self._plan)
 
     def state_dict(self):
-        return {nm: self.params[nm].detach().clone() for nm, _, _, _ in self.layout}
+        return {nm: self.params[nm].detach().clone() for nm in self.names}
 
     def reset_optimizer(self):
         for moment in (self.exp_avg, self.exp_avg_sq):
@@ -457,56 +450,159 @@ class Engine:
                 moment.zero_()
         self.t = 0
 
-    # ---------------------------------------------------------------- the hot path
-    def _prep_x(self, x, font):
-        x = x.to(self.device, dtype=torch.int64, non_blocking=True).contiguous()
-        if font is not None:
-            font = font.to(self.device, dtype=torch.int64, non_blocking=True).contiguous()
-        return x, font
-
-    def forward(self, x, font=None, training=False, step=0, want_output=True):
-        x, font = self._prep_x(x, font)
-        if self.micro_batch and x.shape[0] > self.micro_batch:        # an inference forward of a large batch, micro_batch rows at a time
-            outs = [self.forward(x[lo:lo + self.micro_batch], None if font is None else font[lo:lo + self.micro_batch], training, step, want_output)
-                    for lo in range(0, x.shape[0], self.micro_batch)]
-            return torch.cat(outs) if want_output else None
-        self.ensure_batch(x.shape[0])
-        if isinstance(self.cfg, SheetConfig):
-            if x.dim() != 2:
-                raise ValueError("sheet model takes int64 [B, L] codes")
-            B, L = x.shape
+    # ---------------------------------------------------------------- the batch a call runs on
+    def _batch(self, x=None, font=None, target=None, rows=None, mean_elems=None):
+        """What every call below runs on: dense tensors (codes x, font ids, a target; each may be missing) or a vector of rows of the
+        bound data set.  Returns ((rows, x, font), (rows, t), td, B, L, me): the tensors on the engine's device in the types the
+        library reads (rows, x, font int64; t uint8 or float32, td its code), None where there is none; the sample count B; the codes
+        per sample L (sheet model: x is [B, L]; glyph and pixel models: x is flattened, L = 1); and me, the element count the loss is
+        the mean over, B * pixels unless mean_elems says otherwise.  With no tensor at all, B is that of the last forward
+        (evaluate_last).  The first two members are what an enqueued call keeps alive (self._held) when it reads the inputs and when
+        it reads the targets."""
+        dev, t, td, L = self.device, None, 0, 1
+        if rows is not None:
+            if self._ds is None:
+                raise _lib.AfrError("no data set bound: call bind_dataset before stepping by rows")
+            rows = rows.to(dev, dtype=torch.int64, non_blocking=True).contiguous().reshape(-1)
+            x, font, B = None, None, rows.shape[0]
         else:
-            x = x.reshape(-1)
-            B, L = x.shape[0], 1
+            if x is not None:
+                x = x.to(dev, dtype=torch.int64, non_blocking=True).contiguous()
+                if font is not None:
+                    font = font.to(dev, dtype=torch.int64, non_blocking=True).contiguous()
+                if isinstance(self.cfg, SheetConfig):
+                    if x.dim() != 2:
+                        raise ValueError("sheet model takes int64 [B, L] codes")
+                    L = x.shape[1]
+                else:
+                    x = x.reshape(-1)
+            if target is not None and target.dtype == torch.uint8:
+                t, td = target.to(dev, non_blocking=True).contiguous(), _lib.AFR_TARGET_U8
+            elif target is not None:
+                t, td = target.to(dev, dtype=torch.float32, non_blocking=True).contiguous(), _lib.AFR_TARGET_F32
+            B = x.shape[0] if x is not None else t.shape[0] if t is not None else self._last_B
+        return (rows, x, font), (rows, t), td, B, L, (B * self.pixels if mean_elems is None else int(mean_elems))
+
+    def _prep_x(self, x, font):
+        """The codes and font ids as the library reads them (the batch's; a glyph or pixel model's codes come back flattened)."""
+        return self._batch(x, font)[0][1:]
+
+    def _target(self, target):
+        """The target as the library reads it, and its type code."""
+        b = self._batch(target=target)
+        return b[1][1], b[2]
+
+    def _split(self, b):
+        """The micro-batches of a batch in order: samples [lo, hi) of every tensor, at most micro_batch of them; me stays the whole
+        batch's, so that the micro-steps' losses and gradients add up to the batch's."""
+        (rows, x, font), (_, t), td, B, L, me = b
+        for lo in range(0, B, self.micro_batch):
+            hi = min(B, lo + self.micro_batch)
+            rows_, x_, font_, t_ = (None if v is None else v[lo:hi] for v in (rows, x, font, t))
+            yield (rows_, x_, font_), (rows_, t_), td, hi - lo, L, me
+
+    # ---------------------------------------------------------------- the hot path: one body per operation, on a batch
+    def _forward(self, b, training, step, want_output):
+        (rows, x, font), _, _, B, L, _ = b
+        if self.micro_batch and B > self.micro_batch:        # an inference forward of a large batch, micro_batch rows at a time
+            outs = [self._forward(m, training, step, want_output) for m in self._split(b)]
+            return torch.cat(outs) if want_output else None
+        if B > self.max_batch:
+            self.ensure_batch(B)
         y = torch.empty(B, self.pixels, dtype=torch.float32, device=self.device) if want_output else None
-        self._call(self.lib.afr_forward, self._plan, _ptr(x), _ptr(font), B, L, _ptr(y), int(bool(training)), int(step))
-        self._keep = (x, font)
+        if rows is not None:
+            self._call(self.lib.afr_forward_rows, self._plan, _ptr(rows), B, _ptr(y), int(bool(training)), int(step))
+        else:
+            self._call(self.lib.afr_forward, self._plan, _ptr(x), _ptr(font), B, L, _ptr(y), int(bool(training)), int(step))
+        self._held["in"] = b[0]
         self._last_B = B
-        if y is None:
-            return None
-        h, w = (self.cfg.sheet_h, self.cfg.sheet_w) if isinstance(self.cfg, SheetConfig) else (self.cfg.out_h, self.cfg.out_w)     # glyph / pixel
-        return y.view(B, h, w)
+        return None if y is None else y.view(B, *self._hw)
+
+    def _loss_grad(self, b):
+        _, (rows, t), td, B, _, me = b
+        if rows is not None:
+            self._call(self.lib.afr_loss_grad_rows, self._plan, _ptr(rows), B, me, _ptr(self.loss_accum))
+        else:
+            self._call(self.lib.afr_loss_grad, self._plan, _ptr(t), td, B, me, _ptr(self.loss_accum))
+        self._held["target"] = b[1]
+
+    def _forward_loss(self, b, step):
+        (rows, x, font), (_, t), td, B, L, me = b
+        if self.micro_batch and B > self.micro_batch:
+            raise ValueError(f"forward_loss / backward work on one micro-batch (<= {self.micro_batch} samples); a batch of {B} "
+                             f"accumulates through train_step{'' if rows is None else '_rows'}")
+        if B > self.max_batch:
+            self.ensure_batch(B)
+        st = int(step if step is not None else self.t + 1)
+        if rows is not None:
+            self._call(self.lib.afr_forward_loss_rows, self._plan, _ptr(rows), B, me, _ptr(self.loss_accum), st)
+        else:
+            self._call(self.lib.afr_forward_loss, self._plan, _ptr(x), _ptr(font), _ptr(t), td, B, L, me, _ptr(self.loss_accum), st)
+        self._held["in"], self._held["target"] = b[0], b[1]
+
+    def _train_step(self, b, step=None, lr=1e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=5e-4, do_step=True):
+        (rows, x, font), (_, t), td, B, L, me = b
+        if self.micro_batch and B > self.micro_batch:
+            return self._train_step_accumulated(b, step, lr, betas, eps, weight_decay, do_step)
+        if B > self.max_batch:
+            self.ensure_batch(B)
+        if do_step:
+            self.t += 1
+        st = int(step if step is not None else self.t)
+        if rows is not None:
+            self._call(self.lib.afr_train_step_rows, self._plan, _ptr(rows), B, me, _ptr(self.loss_accum), st,
+                       int(bool(do_step)), lr, betas[0], betas[1], eps, weight_decay, max(self.t, 1))
+        else:
+            self._call(self.lib.afr_train_step, self._plan, _ptr(x), _ptr(font), _ptr(t), td, B, L, me, _ptr(self.loss_accum), st,
+                       int(bool(do_step)), lr, betas[0], betas[1], eps, weight_decay, max(self.t, 1))
+        self._held["in"], self._held["target"] = b[0], b[1]
+
+    def _train_step_accumulated(self, b, step, lr, betas, eps, weight_decay, do_step):
+        """Gradient accumulation: the batch in micro-steps of self.micro_batch samples (forward + loss + backward each, the loss
+        and its gradient scaled for the WHOLE batch through the batch's me), gradients summed in micro-step order, one AdamW step."""
+        if self._grad_acc is None:
+            self._grad_acc = torch.empty_like(self.flat_grads)
+        st = int(step if step is not None else self.t + (1 if do_step else 0))
+        for i, m in enumerate(self._split(b)):
+            # (models with dropout: micro-step i draws its masks from stream st * 65536 + i.  A micro-step does not step: its
+            # hyper-parameters are not read and stay the defaults)
+            self._train_step(m, step=st * 65536 + i if step is None else st, do_step=False)
+            # acc (+)= this micro-step's gradient, by the library's own slab-sum kernel (fixed order: micro-step by micro-step)
+            self._call(self.lib.afr_op_reduce, _ptr(self._grad_acc), _ptr(self.flat_grads), 1, self.n_flat, self.n_flat, 1.0, int(i > 0))
+        self._call(self.lib.afr_op_reduce, _ptr(self.flat_grads), _ptr(self._grad_acc), 1, self.n_flat, self.n_flat, 1.0, 0)
+        if do_step:
+            self.adamw_step(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+
+    def _evaluate_last(self, b, want_u8):
+        _, (rows, t), td, B, _, _ = b
+        need_t = rows is not None or t is not None
+        with torch.cuda.device(self.device):
+            loss_rows = torch.empty(B, dtype=torch.float32, device=self.device) if need_t else None
+            stats = torch.empty(B, 4, dtype=torch.int32, device=self.device) if need_t else None      # the library's uint32 words (<= pixels)
+            q = torch.empty(B, self.pixels, dtype=torch.uint8, device=self.device) if want_u8 or not need_t else None
+        if rows is not None:
+            self._call(self.lib.afr_eval_rows, self._plan, _ptr(rows), B, _ptr(loss_rows), _ptr(stats), _ptr(q))
+        else:
+            self._call(self.lib.afr_eval, self._plan, _ptr(t), td, B, _ptr(loss_rows), _ptr(stats), _ptr(q))
+        self._held["eval"] = b[1]
+        return EvalResult(loss_rows, None if stats is None else stats.to(torch.int64), None if q is None else q.view(B, *self._hw))
+
+    def _evaluate(self, b, want_u8):
+        t, B = b[1][1], b[3]
+        if t is not None and t.shape[0] != B:
+            raise ValueError(f"{t.shape[0]} targets for a batch of {B}")
+        if self.micro_batch and B > self.micro_batch:
+            return EvalResult.cat([self._evaluate(m, want_u8) for m in self._split(b)])
+        self._forward(b, False, 0, False)
+        return self._evaluate_last(b, want_u8)
+
+    # ---------------------------------------------------------------- the hot path: the public calls, dense and by rows
+    def forward(self, x, font=None, training=False, step=0, want_output=True):
+        return self._forward(self._batch(x, font), training, step, want_output)
 
     def forward_rows(self, rows, training=False, step=0, want_output=True):
         """forward() on the rows `rows` (int64 indices, duplicates allowed) of the bound data set."""
-        rows = self._rows(rows)
-        if self.micro_batch and rows.shape[0] > self.micro_batch:
-            outs = [self.forward_rows(rows[lo:lo + self.micro_batch], training, step, want_output) for lo in range(0, rows.shape[0], self.micro_batch)]
-            return torch.cat(outs) if want_output else None
-        B = rows.shape[0]
-        self.ensure_batch(B)
-        y = torch.empty(B, self.pixels, dtype=torch.float32, device=self.device) if want_output else None
-        self._call(self.lib.afr_forward_rows, self._plan, _ptr(rows), B, _ptr(y), int(bool(training)), int(step))
-        self._keep = (rows, None)
-        self._last_B = B
-        if y is None:
-            return None
-        h, w = (self.cfg.sheet_h, self.cfg.sheet_w) if isinstance(self.cfg, SheetConfig) else (self.cfg.out_h, self.cfg.out_w)
-        return y.view(B, h, w)
-
-    # ---------------------------------------------------------------- evaluation on the device
-    def _hw(self):
-        return (self.cfg.sheet_h, self.cfg.sheet_w) if isinstance(self.cfg, SheetConfig) else (self.cfg.out_h, self.cfg.out_w)
+        return self._forward(self._batch(rows=rows), training, step, want_output)
 
     def evaluate_last(self, target=None, rows=None, want_u8=False):
         """The evaluation kernel alone (afr_eval / afr_eval_rows: one launch, nothing allocated by the library) on the pre-activation
@@ -515,111 +611,54 @@ class Engine:
         forward_rows before it; neither: the bitmaps alone (want_u8 is then implied).  Returns an EvalResult."""
         if target is not None and rows is not None:
             raise ValueError("evaluate_last takes a target or rows, not both")
-        with torch.cuda.device(self.device):
-            if rows is not None:
-                rows = self._rows(rows)
-                B = rows.shape[0]
-            elif target is not None:
-                t, td = self._target(target)
-                B = t.shape[0]
-            else:
-                B, want_u8 = self._last_B, True
-            need_t = rows is not None or target is not None
-            loss_rows = torch.empty(B, dtype=torch.float32, device=self.device) if need_t else None
-            stats = torch.empty(B, 4, dtype=torch.int32, device=self.device) if need_t else None      # the library's uint32 words (<= pixels)
-            q = torch.empty(B, self.pixels, dtype=torch.uint8, device=self.device) if want_u8 else None
-        if rows is not None:
-            self._call(self.lib.afr_eval_rows, self._plan, _ptr(rows), B, _ptr(loss_rows), _ptr(stats), _ptr(q))
-            self._keep_e = rows
-        else:
-            self._call(self.lib.afr_eval, self._plan, _ptr(t) if need_t else C.c_void_p(0), td if need_t else 0, B, _ptr(loss_rows), _ptr(stats), _ptr(q))
-            self._keep_e = t if need_t else None
-        return EvalResult(loss_rows, None if stats is None else stats.to(torch.int64), None if q is None else q.view(B, *self._hw()))
+        return self._evaluate_last(self._batch(target=target, rows=rows), want_u8)
 
     def evaluate(self, x, target=None, font=None, want_u8=False):
         """An eval forward (no float32 output is materialised) followed by the evaluation kernel: per-sample loss and the 8-bit error
         counts against `target`, and with want_u8 (or without a target) the uint8 bitmaps.  A batch larger than micro_batch is split
         as forward() splits it."""
-        x, font = self._prep_x(x, font)
-        n = x.shape[0]
-        if self.micro_batch and n > self.micro_batch:
-            return EvalResult.cat([self.evaluate(x[lo:lo + self.micro_batch], None if target is None else target[lo:lo + self.micro_batch],
-                                                 None if font is None else font[lo:lo + self.micro_batch], want_u8)
-                                   for lo in range(0, n, self.micro_batch)])
-        if target is not None and target.shape[0] != n:
-            raise ValueError(f"{target.shape[0]} targets for a batch of {n}")
-        self.forward(x, font=font, training=False, want_output=False)
-        return self.evaluate_last(target=target, want_u8=want_u8)
+        return self._evaluate(self._batch(x, font, target), want_u8)
 
     def evaluate_rows(self, rows, want_u8=False):
         """evaluate() on rows of the bound data set (duplicates allowed), against their targets where they lie."""
-        rows = self._rows(rows)
-        if self.micro_batch and rows.shape[0] > self.micro_batch:
-            return EvalResult.cat([self.evaluate_rows(rows[lo:lo + self.micro_batch], want_u8) for lo in range(0, rows.shape[0], self.micro_batch)])
-        self.forward_rows(rows, training=False, want_output=False)
-        return self.evaluate_last(rows=rows, want_u8=want_u8)
+        return self._evaluate(self._batch(rows=rows), want_u8)
 
     def render_u8(self, x, font=None):
         """uint8 [B, H, W]: the levels binary_array_to_image would write for forward(x), quantised on the device."""
         return self.evaluate(x, font=font, want_u8=True).u8
 
+    def loss_grad(self, target, mean_elems=None):
+        self._loss_grad(self._batch(target=target, mean_elems=mean_elems))
+
     def loss_grad_rows(self, rows, mean_elems=None):
         """loss_grad() against the targets of data-set rows `rows` (the rows of the forward before it)."""
-        rows = self._rows(rows)
-        B = rows.shape[0]
-        me = int(mean_elems) if mean_elems is not None else B * self.pixels
-        self._call(self.lib.afr_loss_grad_rows, self._plan, _ptr(rows), B, me, _ptr(self.loss_accum))
-        self._keep_t = rows
+        self._loss_grad(self._batch(rows=rows, mean_elems=mean_elems))
+
+    def forward_loss(self, x, target, font=None, step=None, mean_elems=None):
+        """Training forward with the loss/grad fused into the last layer's epilogue (no optimizer step)."""
+        self._forward_loss(self._batch(x, font, target, mean_elems=mean_elems), step)
 
     def forward_loss_rows(self, rows, step=None, mean_elems=None):
         """forward_loss() on rows of the bound data set."""
-        rows = self._rows(rows)
-        B = rows.shape[0]
-        if self.micro_batch and B > self.micro_batch:
-            raise ValueError(f"forward_loss / backward work on one micro-batch (<= {self.micro_batch} samples); a batch of {B} "
-                             "accumulates through train_step_rows")
-        self.ensure_batch(B)
-        me = int(mean_elems) if mean_elems is not None else B * self.pixels
-        st = int(step if step is not None else self.t + 1)
-        self._call(self.lib.afr_forward_loss_rows, self._plan, _ptr(rows), B, me, _ptr(self.loss_accum), st)
-        self._keep = self._keep_t = (rows, None)
+        self._forward_loss(self._batch(rows=rows, mean_elems=mean_elems), step)
+
+    def train_step(self, x, target, font=None, step=None, lr=1e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=5e-4,
+                   mean_elems=None, do_step=True):
+        """zero_grad -> forward -> loss -> backward -> AdamW, one C call (model.py:292-310)."""
+        self._not_in_ema("train_step")
+        self._train_step(self._batch(x, font, target, mean_elems=mean_elems), step, lr, betas, eps, weight_decay, do_step)
 
     def train_step_rows(self, rows, step=None, lr=1e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=5e-4, mean_elems=None, do_step=True):
         """train_step() on rows of the bound data set: one C call, no gather in front of it."""
         self._not_in_ema("train_step_rows")
-        rows = self._rows(rows)
-        B = rows.shape[0]
-        if self.micro_batch and B > self.micro_batch:
-            def micro(lo, hi, st, me):
-                self.train_step_rows(rows[lo:hi], step=st, mean_elems=me, do_step=False)
-            return self._train_step_accumulated(B, micro, step, lr, betas, eps, weight_decay, mean_elems, do_step)
-        self.ensure_batch(B)
-        me = int(mean_elems) if mean_elems is not None else B * self.pixels
-        if do_step:
-            self.t += 1
-        st = int(step if step is not None else self.t)
-        self._call(self.lib.afr_train_step_rows, self._plan, _ptr(rows), B, me, _ptr(self.loss_accum), st,
-                   int(bool(do_step)), lr, betas[0], betas[1], eps, weight_decay, max(self.t, 1))
-        self._keep = self._keep_t = (rows, None)
-
-    def _target(self, target):
-        if target.dtype == torch.uint8:
-            return target.to(self.device, non_blocking=True).contiguous(), _lib.AFR_TARGET_U8
-        return target.to(self.device, dtype=torch.float32, non_blocking=True).contiguous(), _lib.AFR_TARGET_F32
-
-    def loss_grad(self, target, mean_elems=None):
-        t, td = self._target(target)
-        B = t.shape[0]
-        me = int(mean_elems) if mean_elems is not None else B * self.pixels
-        self._call(self.lib.afr_loss_grad, self._plan, _ptr(t), td, B, me, _ptr(self.loss_accum))
-        self._keep_t = t
+        self._train_step(self._batch(rows=rows, mean_elems=mean_elems), step, lr, betas, eps, weight_decay, do_step)
 
     def set_output_grad(self, dy):
         """dy = d(loss)/d(output) from a caller-side loss (autograd); float32 [B, pixels].  The output is the clamped one, or the
         sigmoid of a loss="bce" engine."""
         dy = dy.to(self.device, dtype=torch.float32).contiguous()
         self._call(self.lib.afr_set_output_grad, self._plan, _ptr(dy), dy.shape[0])
-        self._keep_t = dy
+        self._held["target"] = dy
 
     def backward(self):
         self._call(self.lib.afr_backward, self._plan)
@@ -633,24 +672,6 @@ class Engine:
         off, n = C.c_int64(), C.c_int64()
         self._call(self.lib.afr_backward_stage, self._plan, int(stage), C.byref(off), C.byref(n))
         return self.flat_grads[off.value:off.value + n.value]
-
-    def forward_loss(self, x, target, font=None, step=None, mean_elems=None):
-        """Training forward with the loss/grad fused into the last layer's epilogue (no optimizer step)."""
-        x, font = self._prep_x(x, font)
-        if self.micro_batch and x.shape[0] > self.micro_batch:
-            raise ValueError(f"forward_loss / backward work on one micro-batch (<= {self.micro_batch} samples); a batch of {x.shape[0]} "
-                             "accumulates through train_step")
-        self.ensure_batch(x.shape[0])
-        t, td = self._target(target)
-        if isinstance(self.cfg, SheetConfig):
-            B, L = x.shape
-        else:
-            x = x.reshape(-1)
-            B, L = x.shape[0], 1
-        me = int(mean_elems) if mean_elems is not None else B * self.pixels
-        st = int(step if step is not None else self.t + 1)
-        self._call(self.lib.afr_forward_loss, self._plan, _ptr(x), _ptr(font), _ptr(t), td, B, L, me, _ptr(self.loss_accum), st)
-        self._keep, self._keep_t = (x, font), t
 
     def adamw_step(self, lr=1e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=5e-4, grad_scale=1.0):
         """One optimizer step of the engine's kind (the name is the AdamW engine's; a Lion engine ignores eps)."""
@@ -666,72 +687,21 @@ class Engine:
         The EMA is not touched: the caller counts the step with ema_update once every slice is in place."""
         self._not_in_ema("adamw_range")
         self.t += 1
-        o, e = int(offset), int(offset) + int(n)
+        o, n, lion, null = int(offset), int(n), self.optimizer == "lion", C.c_void_p(0)
+        p, g, m = (_ptr(flat[o:o + n]) for flat in (self.flat_params, self.flat_grads, self.exp_avg))
+        v = null if lion else _ptr(self.exp_avg_sq[o:o + n])
+        clip = (_ptr(sumsq), float(self.max_grad_norm or 0.0))
         if self._ranges is not None:      # optimizer groups: the slice in one launch of the range-aware kernel, with the plan's table
-            lion = self.optimizer == "lion"
-            self._call(self.lib.afr_op_opt_groups, _lib.opt_kind(self.optimizer), _ptr(self.flat_params[o:e]), _ptr(self.flat_grads[o:e]),
-                       _ptr(self.exp_avg[o:e]), C.c_void_p(0) if lion else _ptr(self.exp_avg_sq[o:e]), C.c_void_p(0), int(n), o, self._ranges,
-                       len(self._ranges), lr, betas[0], betas[1], eps, weight_decay, self.t, grad_scale, _ptr(sumsq), float(self.max_grad_norm or 0.0))
-            self._keep_ss = sumsq
-            return
-        if self.optimizer == "lion":      # the same slice step by afr_op_lion, clipped when sumsq is given
-            self._call(self.lib.afr_op_lion, _ptr(self.flat_params[o:e]), _ptr(self.flat_grads[o:e]), _ptr(self.exp_avg[o:e]), C.c_void_p(0), int(n),
-                       lr, betas[0], betas[1], weight_decay, grad_scale, _ptr(sumsq), float(self.max_grad_norm or 0.0))
-            self._keep_ss = sumsq
-            return
-        if sumsq is not None:
-            self._call(self.lib.afr_op_adamw_clip, _ptr(self.flat_params[o:e]), _ptr(self.flat_grads[o:e]), _ptr(self.exp_avg[o:e]),
-                       _ptr(self.exp_avg_sq[o:e]), C.c_void_p(0), int(n), lr, betas[0], betas[1], eps, weight_decay, self.t, grad_scale,
-                       _ptr(sumsq), float(self.max_grad_norm or 0.0))
-            self._keep_ss = sumsq
-            return
-        self._call(self.lib.afr_op_adamw, _ptr(self.flat_params[o:e]), _ptr(self.flat_grads[o:e]), _ptr(self.exp_avg[o:e]),
-                   _ptr(self.exp_avg_sq[o:e]), C.c_void_p(0), int(n), lr, betas[0], betas[1], eps, weight_decay, self.t, grad_scale)
-
-    def train_step(self, x, target, font=None, step=None, lr=1e-3, betas=(0.9, 0.99), eps=1e-8, weight_decay=5e-4,
-                   mean_elems=None, do_step=True):
-        """zero_grad -> forward -> loss -> backward -> AdamW, one C call (model.py:292-310)."""
-        self._not_in_ema("train_step")
-        x, font = self._prep_x(x, font)
-        if self.micro_batch and x.shape[0] > self.micro_batch:
-            t, _ = self._target(target)
-
-            def micro(lo, hi, st, me):
-                self.train_step(x[lo:hi], t[lo:hi], font=None if font is None else font[lo:hi], step=st, mean_elems=me, do_step=False)
-            return self._train_step_accumulated(x.shape[0], micro, step, lr, betas, eps, weight_decay, mean_elems, do_step)
-        self.ensure_batch(x.shape[0])
-        t, td = self._target(target)
-        if isinstance(self.cfg, SheetConfig):
-            B, L = x.shape
+            fn, args = self.lib.afr_op_opt_groups, (_lib.opt_kind(self.optimizer), p, g, m, v, null, n, o, self._ranges, len(self._ranges),
+                                                    lr, betas[0], betas[1], eps, weight_decay, self.t, grad_scale, *clip)
+        elif lion:                        # the same slice step by afr_op_lion, clipped when sumsq is given
+            fn, args = self.lib.afr_op_lion, (p, g, m, null, n, lr, betas[0], betas[1], weight_decay, grad_scale, *clip)
         else:
-            x = x.reshape(-1)
-            B, L = x.shape[0], 1
-        me = int(mean_elems) if mean_elems is not None else B * self.pixels
-        if do_step:
-            self.t += 1
-        st = int(step if step is not None else self.t)
-        self._call(self.lib.afr_train_step, self._plan, _ptr(x), _ptr(font), _ptr(t), td, B, L, me, _ptr(self.loss_accum), st,
-                                           int(bool(do_step)), lr, betas[0], betas[1], eps, weight_decay, max(self.t, 1))
-        self._keep = (x, font)
-        self._keep_t = t
-
-    def _train_step_accumulated(self, B, micro, step, lr, betas, eps, weight_decay, mean_elems, do_step):
-        """Gradient accumulation: the batch in micro-steps of self.micro_batch samples (forward + loss + backward each, the loss
-        and its gradient scaled for the WHOLE batch through mean_elems), gradients summed in micro-step order, one AdamW step.
-        micro(lo, hi, step, mean_elems) runs batch rows [lo, hi) without an optimizer step (dense tensors or data-set rows)."""
-        me = int(mean_elems) if mean_elems is not None else B * self.pixels
-        if self._grad_acc is None:
-            self._grad_acc = torch.empty_like(self.flat_grads)
-        st = int(step if step is not None else self.t + (1 if do_step else 0))
-        for i, lo in enumerate(range(0, B, self.micro_batch)):
-            hi = min(B, lo + self.micro_batch)
-            # (models with dropout: micro-step i draws its masks from stream st * 65536 + i)
-            micro(lo, hi, st * 65536 + i if step is None else st, me)
-            # acc (+)= this micro-step's gradient, by the library's own slab-sum kernel (fixed order: micro-step by micro-step)
-            self._call(self.lib.afr_op_reduce, _ptr(self._grad_acc), _ptr(self.flat_grads), 1, self.n_flat, self.n_flat, 1.0, int(i > 0))
-        self._call(self.lib.afr_op_reduce, _ptr(self.flat_grads), _ptr(self._grad_acc), 1, self.n_flat, self.n_flat, 1.0, 0)
-        if do_step:
-            self.adamw_step(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+            fn, args = self.lib.afr_op_adamw, (p, g, m, v, null, n, lr, betas[0], betas[1], eps, weight_decay, self.t, grad_scale)
+            if sumsq is not None:
+                fn, args = self.lib.afr_op_adamw_clip, args + clip
+        self._call(fn, *args)
+        self._held["sumsq"] = sumsq
 
     def read_loss(self, reset=True):
         v = float(self.loss_accum.item())

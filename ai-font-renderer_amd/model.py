@@ -171,11 +171,7 @@ class _TensorReport:
         """Forward + loss + backward of the first training batch's rows (by data-set rows, or dense when inputs are given); the dropout
         step is the next one the model WOULD draw, passed explicitly: model._next_step() does not move."""
         eng, (rows, me) = self.eng, self.first
-        step = self.model._steps + 1
-        if inputs is None:
-            eng.forward_loss_rows(rows, step=step, mean_elems=me)
-        else:
-            eng.forward_loss(inputs.index_select(0, rows), targets.index_select(0, rows), step=step, mean_elems=me)
+        _batch_calls(eng, None, inputs, targets, rows).forward_loss(step=self.model._steps + 1, mean_elems=me)
         eng.backward()
         eng.read_loss(reset=True)                 # the probe's loss is nobody's
         self.g = eng.tensor_stats("grads").cpu()
@@ -482,6 +478,22 @@ def _step_hyper(eng, lr):
     return lr, WEIGHT_DECAY
 
 
+def _batch_calls(eng, stepper, inputs, targets, rows):
+    """The calls of one batch, bound to what they run on: the data-set rows `rows` themselves when inputs is None (the engine has the
+    data set bound), else the dense tensors gathered from inputs and targets with index_select (targets None: the codes alone).  The one
+    place an epoch chooses between the two forms.  step(mean_elems, **hyper) is the stepper's, the others are the engine's."""
+    from functools import partial
+    from types import SimpleNamespace
+    if inputs is None:
+        return SimpleNamespace(step=partial(stepper.step_rows, rows) if stepper else None, forward=partial(eng.forward_rows, rows),
+                               evaluate_last=partial(eng.evaluate_last, rows=rows), loss_grad=partial(eng.loss_grad_rows, rows),
+                               evaluate=partial(eng.evaluate_rows, rows), forward_loss=partial(eng.forward_loss_rows, rows))
+    x, t = inputs.index_select(0, rows), None if targets is None else targets.index_select(0, rows)
+    return SimpleNamespace(step=partial(stepper.step, x, t, None) if stepper else None, forward=partial(eng.forward, x),
+                           evaluate_last=partial(eng.evaluate_last, target=t), loss_grad=partial(eng.loss_grad, t),
+                           evaluate=partial(eng.evaluate, x), forward_loss=partial(eng.forward_loss, x, t))
+
+
 def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True, report=None, treport=None):
     """One epoch of the reference loop (model.py:288-333): the training pass over order.train_epoch(), then the validation
     pass; returns the two means of per-batch mean losses.  An engine that keeps a weight EMA validates from it.  by_rows: the engine has the data set bound (Engine.bind_dataset)
@@ -494,6 +506,7 @@ def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, wor
     from .parallel import shard_rows
     eng = model.engine
     pixels = targets[0].numel()
+    dense = (None, None) if by_rows else (inputs, targets)
     model.train()
     idx = order.train_epoch().to(inputs.device)
     nb = _num_batches(order.train_size, batch_size)
@@ -507,10 +520,7 @@ def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, wor
                 treport.first = (mine, rows.numel() * pixels)
             if b == nb - 1:
                 treport.before_last_step()
-        if by_rows:
-            stepper.step_rows(mine, rows.numel() * pixels, **hyper)
-        else:
-            stepper.step(inputs.index_select(0, mine), targets.index_select(0, mine), None, rows.numel() * pixels, **hyper)
+        _batch_calls(eng, stepper, *dense, mine).step(rows.numel() * pixels, **hyper)
         if treport is not None and b == nb - 1:
             treport.after_last_step()
     avg_train_loss = stepper.global_loss() / nb                 # mean of per-batch means (model.py:311,333)
@@ -522,26 +532,19 @@ def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, wor
         for b in range(nvb):
             rows = vidx[b * batch_size:(b + 1) * batch_size]
             mine = rows[shard_rows(rows.numel(), rank, world)]
-            if by_rows:
-                eng.forward_rows(mine, training=False, want_output=False)
-                if report is not None:
-                    report.add(eng.evaluate_last(rows=mine), mine)
-                eng.loss_grad_rows(mine, mean_elems=rows.numel() * pixels)
-            else:
-                eng.forward(inputs.index_select(0, mine), training=False, want_output=False)
-                tb = targets.index_select(0, mine)
-                if report is not None:
-                    report.add(eng.evaluate_last(target=tb), mine)
-                eng.loss_grad(tb, mean_elems=rows.numel() * pixels)
+            calls = _batch_calls(eng, None, *dense, mine)
+            calls.forward(training=False, want_output=False)
+            if report is not None:
+                report.add(calls.evaluate_last(), mine)
+            calls.loss_grad(mean_elems=rows.numel() * pixels)
         if report is not None:
             if world > 1:
                 report.all_reduce(_dist()[0])
             if report.bitmaps and rank == 0 and report.idx.numel():      # the worst sheets once more, for their bitmaps (no collective)
-                report.u8 = (eng.evaluate_rows(report.idx, want_u8=True) if by_rows else
-                             eng.evaluate(inputs.index_select(0, report.idx), want_u8=True)).u8
+                report.u8 = _batch_calls(eng, None, dense[0], None, report.idx).evaluate(want_u8=True).u8
     avg_val_loss = stepper.global_loss() / max(nvb, 1)
     if treport is not None:
-        treport.probe(*(() if by_rows else (inputs, targets)))
+        treport.probe(*dense)
     return avg_train_loss, avg_val_loss
 
 

@@ -96,25 +96,20 @@ class DataParallelStepper:
 
     def step(self, x, target, font=None, mean_elems=None, **hyper):
         """One optimiser step on this rank's shard.  mean_elems = global_rows * pixels."""
-        eng = self.engine
-        self._step(x.shape[0], mean_elems, hyper,
-                   lambda do_step, **kw: eng.train_step(x, target, font=font, mean_elems=mean_elems, do_step=do_step, **kw),
-                   lambda **kw: eng.forward_loss(x, target, font=font, mean_elems=mean_elems, **kw))
+        self._step("", x.shape[0], (x, target), dict(font=font, mean_elems=mean_elems), hyper)
 
     def step_rows(self, rows, mean_elems=None, **hyper):
         """step() on rows of the data set bound to the engine (Engine.bind_dataset): `rows` is this rank's shard of the batch's
         index vector.  The same schedules; nothing is gathered in front of the step."""
-        eng = self.engine
-        self._step(rows.shape[0], mean_elems, hyper,
-                   lambda do_step, **kw: eng.train_step_rows(rows, mean_elems=mean_elems, do_step=do_step, **kw),
-                   lambda **kw: eng.forward_loss_rows(rows, mean_elems=mean_elems, **kw))
+        self._step("_rows", rows.shape[0], (rows,), dict(mean_elems=mean_elems), hyper)
 
-    def _step(self, n_rows, mean_elems, hyper, train_step, forward_loss):
-        """The schedules of one step.  train_step(do_step, **hyper) and forward_loss(step=) are the engine calls on this
-        rank's shard, by dense tensors (step) or by data-set rows (step_rows)."""
+    def _step(self, form, n_rows, batch, kw, hyper):
+        """The schedules of one step.  The engine calls on this rank's shard are train_step<form> and forward_loss<form>, which
+        take (*batch, **kw): dense tensors (step, form "") or data-set rows (step_rows, form "_rows")."""
         eng = self.engine
+        train_step = getattr(eng, "train_step" + form)
         if (self.world == 1 and not (_schedule() == "shard-force" and self.dist is not None)) or self.dist is None:
-            train_step(True, **hyper)
+            train_step(*batch, do_step=True, **kw, **hyper)
             return
         opt = {k: v for k, v in hyper.items() if k in ("lr", "betas", "eps", "weight_decay")}
         stages = getattr(eng, "backward_stages", 0)
@@ -126,7 +121,7 @@ class DataParallelStepper:
             # produced it and overlaps the rest of the backward pass; everything else is one contiguous range
             # [0, start of that range) reduced when the last stage is done.  (One collective per stage overlapped more
             # bytes but paid ~20 us of cross-stream event hand-offs per collective: measured with a world of one.)
-            forward_loss(step=hyper.get("step"))
+            getattr(eng, "forward_loss" + form)(*batch, step=hyper.get("step"), **kw)
             first = eng.backward_stage(0)
             work = self.dist.all_reduce(first, async_op=True)
             for s in range(1, stages):
@@ -137,7 +132,7 @@ class DataParallelStepper:
             work.wait()
         elif self.sharded():
             # sharded optimizer: backward -> reduce-scatter -> AdamW on this rank's slice -> all-gather of the parameters
-            train_step(False, **hyper)
+            train_step(*batch, do_step=False, **kw, **hyper)
             ws = self.dist.get_world_size()               # == self.world except under shard-force (a world of one)
             rk = self.rank if ws == self.world else self.dist.get_rank()
             n = eng.flat_grads.numel() // ws
@@ -160,7 +155,7 @@ class DataParallelStepper:
                 eng.sync_params()               # bf16 mode: the shadow of the slices other ranks updated
             return
         else:
-            train_step(False, **hyper)
+            train_step(*batch, do_step=False, **kw, **hyper)
             if GRAD_BF16 and getattr(eng, "dtype", "f32") == "bf16":
                 g16 = eng.flat_grads.to(torch.bfloat16)
                 self.dist.all_reduce(g16)

@@ -131,3 +131,73 @@ def test_engine_calls_run_on_the_engines_device_and_its_stream(monkeypatch):
     eng._call(fn, 1, 2)
     assert seen == [("enter", eng.device), ("call", 1, 2, 0x5003), ("exit", eng.device)]
     eng.__dict__.clear()                                       # nothing for __del__ to tear down
+
+
+ENGINE_SURFACE = {
+    "__init__": "(self, cfg, dtype='f32', max_batch=1024, device=None, seed=42, rank=0, with_optimizer=True, flags=0, micro_batch=None, "
+                "loss='mse', max_grad_norm=None, optimizer='adamw', ema_decay=None, ema_every=1, lr_mult=None, wd_mult=None)",
+    "adamw_range": "(self, offset, n, lr=0.001, betas=(0.9, 0.99), eps=1e-08, weight_decay=0.0005, grad_scale=1.0, sumsq=None)",
+    "adamw_step": "(self, lr=0.001, betas=(0.9, 0.99), eps=1e-08, weight_decay=0.0005, grad_scale=1.0)",
+    "backward": "(self)",
+    "backward_stage": "(self, stage)",
+    "backward_stages": "property",
+    "bind_dataset": "(self, x, target, font=None)",
+    "clip_coef": "(self)",
+    "debug_read": "(self, which, index=0)",
+    "debug_sheet_gather": "(self, x)",
+    "ema_state_dict": "(self)",
+    "ema_update": "(self, sumsq=None)",
+    "ema_weights": "(self)",
+    "ensure_batch": "(self, B)",
+    "error_flags": "(self)",
+    "evaluate": "(self, x, target=None, font=None, want_u8=False)",
+    "evaluate_last": "(self, target=None, rows=None, want_u8=False)",
+    "evaluate_rows": "(self, rows, want_u8=False)",
+    "forward": "(self, x, font=None, training=False, step=0, want_output=True)",
+    "forward_loss": "(self, x, target, font=None, step=None, mean_elems=None)",
+    "forward_loss_rows": "(self, rows, step=None, mean_elems=None)",
+    "forward_rows": "(self, rows, training=False, step=0, want_output=True)",
+    "grad_norm": "(self)",
+    "grad_sumsq": "(self, offset=0, n=None)",
+    "load_params": "(self, tensors)",
+    "loss_grad": "(self, target, mean_elems=None)",
+    "loss_grad_rows": "(self, rows, mean_elems=None)",
+    "param_group_ranges": "(self)",
+    "profile": "(self, mode=1)",
+    "profile_read": "(self)",
+    "profile_table": "(self)",
+    "read_loss": "(self, reset=True)",
+    "render_u8": "(self, x, font=None)",
+    "reset_ema": "(self)",
+    "reset_optimizer": "(self)",
+    "set_ema": "(self, decay, every=1)",
+    "set_grad_clip": "(self, max_grad_norm)",
+    "set_output_grad": "(self, dy)",
+    "set_param_groups": "(self, lr_mult=None, wd_mult=None)",
+    "state_dict": "(self)",
+    "sync_params": "(self)",
+    "tensor_stats": "(self, which='grads', minus=None)",
+    "train_step": "(self, x, target, font=None, step=None, lr=0.001, betas=(0.9, 0.99), eps=1e-08, weight_decay=0.0005, mean_elems=None, "
+                  "do_step=True)",
+    "train_step_rows": "(self, rows, step=None, lr=0.001, betas=(0.9, 0.99), eps=1e-08, weight_decay=0.0005, mean_elems=None, do_step=True)",
+}
+STEPPER_SURFACE = {
+    "step": "(self, x, target, font=None, mean_elems=None, **hyper)",
+    "step_rows": "(self, rows, mean_elems=None, **hyper)",
+    "global_loss": "(self, reset=True)",
+}
+
+
+def test_public_surface_of_engine_and_stepper_is_pinned():
+    """Names and full signatures (parameter order, defaults) of every public method of Engine, its constructor included, and of the
+    stepper's three entry points.  A method added, removed or re-signed shows up here before it shows up in a caller."""
+    import inspect
+    from ai_font_renderer_amd.engine import Engine
+    from ai_font_renderer_amd.parallel import DataParallelStepper
+
+    def sig(m):
+        return "property" if isinstance(m, property) else str(inspect.signature(m.__func__ if isinstance(m, staticmethod) else m))
+
+    got = {n: sig(m) for n, m in vars(Engine).items() if n == "__init__" or (not n.startswith("_") and (callable(m) or isinstance(m, (property, staticmethod))))}
+    assert got == ENGINE_SURFACE
+    assert {n: sig(getattr(DataParallelStepper, n)) for n in STEPPER_SURFACE} == STEPPER_SURFACE

@@ -1,22 +1,40 @@
 #!/usr/bin/env python3
-"""Host issue time vs wall time per training step (is the launch stream host-bound?): python tools/hostbound.py"""
-import sys, time, torch
+"""Host issue time vs wall time per training step (is the launch stream host-bound?): python tools/hostbound.py
+--steps N: steps per reading (200).  --repeats R: R readings in the process, the median of each column is printed (1).
+--form dense|rows: train_step on the batch's tensors, or train_step_rows(arange(B)) with the batch itself bound as the data set.
+--workloads: comma-separated, in the order they run (c3,c2,c1)."""
+import argparse, statistics, sys, time, torch
 sys.path.insert(0, '.')
 from ai_font_renderer_amd import synth
 from ai_font_renderer_amd.config import WORKLOADS
 from ai_font_renderer_amd.engine import Engine
 import bench
-for name in ('c3', 'c2', 'c1'):
+ap = argparse.ArgumentParser()
+ap.add_argument('--steps', type=int, default=200)
+ap.add_argument('--repeats', type=int, default=1)
+ap.add_argument('--form', choices=('dense', 'rows'), default='dense')
+ap.add_argument('--workloads', default='c3,c2,c1')
+a = ap.parse_args()
+for name in a.workloads.split(','):
     cfg, B = WORKLOADS[name]['cfg'], WORKLOADS[name]['batch']
     eng = Engine(cfg, dtype=bench.DEFAULT_DTYPE[name], max_batch=B)
     eng.load_params(synth.make_params(cfg))
     x, font, t = bench.make_inputs(name, cfg, B, 0)
     x, t = x.cuda(), t.cuda(); font = font.cuda() if font is not None else None
-    for _ in range(20): eng.train_step(x, t, font=font)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(200): eng.train_step(x, t, font=font)
-    t1 = time.perf_counter()
-    torch.cuda.synchronize()
-    t2 = time.perf_counter()
-    print(f'{name}: host issue {1e6*(t1-t0)/200:.1f} us/step, wall {1e6*(t2-t0)/200:.1f} us/step')
+    if a.form == 'rows':
+        eng.bind_dataset(x, t, font)
+        rows = torch.arange(B, device='cuda')
+        step = lambda: eng.train_step_rows(rows)
+    else:
+        step = lambda: eng.train_step(x, t, font=font)
+    for _ in range(20): step()
+    host, wall = [], []
+    for _ in range(a.repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.steps): step()
+        t1 = time.perf_counter()
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        host.append(1e6*(t1-t0)/a.steps); wall.append(1e6*(t2-t0)/a.steps)
+    print(f'{name}: host issue {statistics.median(host):.{1 if a.repeats == 1 else 2}f} us/step, wall {statistics.median(wall):.{1 if a.repeats == 1 else 2}f} us/step')
