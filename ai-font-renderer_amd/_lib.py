@@ -78,6 +78,22 @@ class AfrSheetSlabLayout(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("pos", "emb", "w_in", "b_in", "w_o", "b_o", "ln_g", "ln_b", "w1", "b1", "total")]
 
 
+LIN_FWD, LIN_DX, LIN_DW, LIN_PAIR = 0, 1, 2, 3      # AFR_LIN_*: which product of a Linear afr_op_linear issues
+
+
+class AfrLinearTail(C.Structure):
+    """The step-only tails of one Linear product (include/afr.h afr_linear_tail); pointers are device pointers."""
+    _fields_ = [("ld_out", C.c_int32), ("ldx", C.c_int32), ("ldaux", C.c_int32), ("ld_db", C.c_int32),
+                ("target", C.c_void_p), ("target_rows", C.c_void_p), ("target_dtype", C.c_int32), ("loss_kind", C.c_int32),
+                ("mean_elems", C.c_int64), ("loss_accum", C.c_void_p), ("loss_scratch", C.c_void_p),
+                ("mask_out", C.c_void_p), ("x_rows", C.c_void_p),
+                ("aux", C.c_void_p), ("aux_rows", C.c_void_p), ("mask_in", C.c_void_p), ("ldmask", C.c_int32),
+                ("splitk", C.c_int32), ("db", C.c_void_p), ("opt_kind", C.c_int32), ("reserved", C.c_int32),
+                ("p", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("shadow", C.c_void_p),
+                ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
+                ("grad_scale", C.c_float), ("t", C.c_int64)]
+
+
 _vp, _i32, _i64, _f32, _u64, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64, C.c_size_t
 
 # name -> (restype, argtypes): every function include/afr.h declares
@@ -130,6 +146,8 @@ SIGNATURES = {
     "afr_op_gemm_fix": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
     "afr_op_gemm_pair_plan": (_i32, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_sz)]),
     "afr_op_gemm_pair": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "afr_op_linear_pair_plan": (_i32, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_sz)]),
+    "afr_op_linear": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.POINTER(AfrLinearTail), _vp, _sz, C.c_char_p, _i32, _vp]),
     "afr_op_reduce": (_i32, [_vp, _vp, _i32, _i64, _i64, _f32, _i32, _vp]),
     "afr_op_reduce_group": (_i32, [_i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "afr_op_adamw": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _f32, _vp]),

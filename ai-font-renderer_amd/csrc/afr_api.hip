@@ -737,10 +737,13 @@ static GemmParams lin_desc(int flags, const void* A, const void* B, void* C, int
     return g;
 }
 // forward: y = x . W^T + b, in the plan's activation dtype
-static GemmParams lin_fwd(const afr_plan* p, const afr_plan::Layer& l, const void* x, void* y, int B, int ep = 0) {
-    GemmParams g = lin_desc(AFR_GEMM_BIAS | out_flag(p) | ep, x, weight_ptr(p, l.w_off), y, B, l.N, l.K, l.K, l.K, l.N);
-    g.bias = p->P + l.b_off;
+static GemmParams lin_fwd(const void* x, const void* W, const float* bias, void* y, int B, int N, int K, int ep) {
+    GemmParams g = lin_desc(AFR_GEMM_BIAS | ep, x, W, y, B, N, K, K, K, N);
+    g.bias = bias;
     return g;
+}
+static GemmParams lin_fwd(const afr_plan* p, const afr_plan::Layer& l, const void* x, void* y, int B, int ep = 0) {
+    return lin_fwd(x, weight_ptr(p, l.w_off), p->P + l.b_off, y, B, l.N, l.K, out_flag(p) | ep);
 }
 // input gradient: dx = dy . W; aux [B][K] (the layer's input, NULL = none) masks it with ReLU's gate
 static GemmParams lin_dx(const void* dy, const void* W, void* dx, const void* aux, int B, int N, int K, int ep) {
@@ -2072,6 +2075,146 @@ extern "C" int afr_op_gemm_pair(const void* dy, const void* x, const void* W, co
     HIPCHK(hipMemsetAsync(cnt, 0, align_up(tiles * sizeof(unsigned), 256), s));
     g[0].coop_ws = (float*)workspace; g[0].coop_cnt = cnt; g[0].coop_target = (unsigned)sk;
     HIPCHK(afr_launch_gemm_group(AFR_BF16, g, 2, 1, s));
+    return AFR_OK;
+}
+// ---- afr_op_linear: one product of a Linear as the step issues it (lin_fwd / lin_dx / lin_dw + the tails, set by name)
+static size_t pair_workspace_bytes(int N, int K, const PairPlan& pp) {
+    if (!pp.coop) return 0;
+    const size_t tiles = (size_t)((N + 255) / 256) * ((K + 255) / 256);
+    return tiles * pp.sk_group * AFR_FIX_SLICE_BYTES + align_up(tiles * sizeof(unsigned), 256);
+}
+extern "C" int afr_op_linear_pair_plan(int B, int N, int K, int* tile256, int* splitk, int* coop, size_t* workspace_bytes) {
+    const PairPlan pp = pair_plan_shape(B, N, K);
+    if (pp.sk_group < 1) return fail(AFR_EUNSUPPORTED, "%d x %d x %d: the gradient pair does not leave as one grouped launch", B, N, K);
+    if (tile256) *tile256 = pp.tile256;
+    if (splitk) *splitk = pp.sk_group;
+    if (coop) *coop = pp.coop ? 1 : 0;
+    if (workspace_bytes) *workspace_bytes = pair_workspace_bytes(N, K, pp);
+    return AFR_OK;
+}
+// a launcher's answer: what it refuses (hipErrorInvalidValue before anything is launched) is a refusal, not a HIP failure
+static int launcher_rc(hipError_t e, const char* what) {
+    if (e == hipSuccess) return AFR_OK;
+    (void)hipGetLastError();
+    if (e == hipErrorInvalidValue)
+        return fail(AFR_EUNSUPPORTED, "afr_op_linear (%s): the GEMM launcher refuses this combination of dtype, operand layout, shape and tails", what);
+    return fail(AFR_EHIP, "afr_op_linear (%s): %s", what, hipGetErrorString(e));
+}
+// the ReLU gates of an input-gradient product (aux / aux_rows / mask_in), as backward_stage_impl sets them
+static int linear_set_gate(GemmParams& g, const afr_linear_tail& t, int dtype, int K) {
+    if (t.aux_rows && !t.aux) return fail(AFR_EINVAL, "aux_rows without aux");
+    if (t.ldaux && t.ldaux < K && !t.aux_rows) return fail(AFR_EINVAL, "ldaux = %d is smaller than K = %d", t.ldaux, K);
+    if (t.ldaux % (dtype == AFR_BF16 ? 8 : 4)) return fail(AFR_EUNSUPPORTED, "ldaux must be a multiple of %d", dtype == AFR_BF16 ? 8 : 4);
+    if (t.aux && t.ldaux) g.ldaux = t.ldaux;
+    if (t.aux_rows) g.aux_rowmap = t.aux_rows;
+    if (t.mask_in) {
+        if (dtype != AFR_BF16) return fail(AFR_EINVAL, "mask_in: bit masks exist with bf16 outputs only");
+        if (t.ldmask < K / 8) return fail(AFR_EINVAL, "ldmask = %d is smaller than K / 8 = %d", t.ldmask, K / 8);
+        g.flags |= AFR_GEMM_RELU_MASK; g.mask_in = t.mask_in; g.ldmask = t.ldmask;
+    }
+    return AFR_OK;
+}
+// the fused optimizer step of a weight-gradient product, as set_fused_opt sets it
+static int linear_set_opt(GemmParams& g, const afr_linear_tail& t, int dtype) {
+    if (!t.p) return AFR_OK;
+    if (t.shadow && dtype != AFR_BF16) return fail(AFR_EINVAL, "fused optimizer: the bf16 shadow exists in AFR_BF16 only");
+    if (t.opt_kind != AFR_OPT_ADAMW && t.opt_kind != AFR_OPT_LION) return fail(AFR_EINVAL, "optimizer kind must be AFR_OPT_ADAMW (0) or AFR_OPT_LION (1), got %d", t.opt_kind);
+    if (!t.m || (t.opt_kind == AFR_OPT_ADAMW && !t.v)) return fail(AFR_EINVAL, "fused optimizer: null moment");
+    if (int rc = check_step_count(t.t)) return rc;
+    if (t.grad_scale != 1.f) return fail(AFR_EUNSUPPORTED, "fused optimizer: the GEMM tails take the gradient unscaled (grad_scale must be 1, got %g)", (double)t.grad_scale);
+    g.ad_p = t.p; g.ad_m = t.m; g.ad_v = t.opt_kind == AFR_OPT_LION ? nullptr : t.v; g.ad_shadow = (bf16_t*)t.shadow;
+    g.ad = adam_hyper(AdamArgs{t.lr, t.beta1, t.beta2, t.eps, t.weight_decay, t.t}, t.opt_kind); g.ad_kind = t.opt_kind;
+    return AFR_OK;
+}
+extern "C" int afr_op_linear(int dtype, int which, const void* x, const void* W, const float* bias, const void* dy, void* out, void* out2,
+                             int B, int N, int K, const afr_linear_tail* tail, void* workspace, size_t workspace_bytes,
+                             char* kernel_name, int name_cap, void* stream) {
+    static const afr_linear_tail none = {};
+    const afr_linear_tail& t = tail ? *tail : none;
+    if (dtype != AFR_F32 && dtype != AFR_BF16 && dtype != AFR_BF16X3) return fail(AFR_EINVAL, "dtype must be AFR_F32, AFR_BF16 or AFR_BF16X3");
+    if (which < AFR_LIN_FWD || which > AFR_LIN_PAIR) return fail(AFR_EINVAL, "which must be AFR_LIN_FWD, _DX, _DW or _PAIR");
+    if (B <= 0 || N <= 0 || K <= 0) return fail(AFR_EINVAL, "bad Linear extents %d x %d x %d", B, N, K);
+    if (!out) return fail(AFR_EINVAL, "null output");
+    const bool fwd = which == AFR_LIN_FWD, dx = which == AFR_LIN_DX, dw = which == AFR_LIN_DW, pair = which == AFR_LIN_PAIR;
+    if (fwd ? (!x || !W || !bias) : dx ? (!dy || !W) : dw ? (!dy || !x) : (!dy || !x || !W || !out2)) return fail(AFR_EINVAL, "null operand");
+    if (kernel_name && name_cap < 1) return fail(AFR_EINVAL, "name_cap must be positive");
+    // a tail the product does not have is an error, not something to drop
+    if (!fwd && (t.target || t.target_rows || t.mask_out)) return fail(AFR_EINVAL, "the fused loss and mask_out belong to AFR_LIN_FWD");
+    if ((fwd || dw) && (t.aux || t.aux_rows || t.mask_in)) return fail(AFR_EINVAL, "aux, aux_rows and mask_in belong to AFR_LIN_DX / AFR_LIN_PAIR");
+    if ((fwd || dx) && (t.db || t.p || t.splitk > 1)) return fail(AFR_EINVAL, "db, splitk and the fused optimizer belong to AFR_LIN_DW / AFR_LIN_PAIR");
+    if (dx && t.x_rows) return fail(AFR_EINVAL, "x_rows belongs to AFR_LIN_FWD / AFR_LIN_PAIR");
+    if (dw && t.x_rows) return fail(AFR_EUNSUPPORTED, "a gathered weight-gradient operand needs the cooperative 256x256 launch (AFR_LIN_PAIR)");
+    const int v = dtype == AFR_BF16 ? 8 : 4;
+    const int out_w = (fwd ? N : K), ldo = t.ld_out ? t.ld_out : out_w, ldx = t.ldx ? t.ldx : K, ld_db = t.ld_db ? t.ld_db : N;
+    if (N % v || K % v || ldo % v || ldx % v) return fail(AFR_EUNSUPPORTED, "N, K and the leading dimensions must be multiples of %d", v);
+    if (ldo < out_w || ldx < K || ld_db < N || t.splitk < 0) return fail(AFR_EINVAL, "a leading dimension is smaller than its row, or splitk < 0");
+    if (pair && dtype != AFR_BF16) return fail(AFR_EUNSUPPORTED, "AFR_LIN_PAIR: grouped launches exist in AFR_BF16 only");
+    const int ob = dtype == AFR_BF16 ? AFR_GEMM_OUT_BF16 : 0;
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    DevGuard dg(device_of(out));
+    GemmParams g[2];
+    if (fwd) {
+        g[0] = lin_fwd(x, W, bias, out, B, N, K, ob | (t.mask_out ? AFR_GEMM_RELU : 0));
+        g[0].ldc = ldo;
+        if (t.target) {
+            if ((rc = check_loss_args(t.target, t.target_dtype, t.mean_elems, t.loss_accum))) return rc;
+            if (t.loss_kind != AFR_LOSS_MSE && t.loss_kind != AFR_LOSS_BCE) return fail(AFR_EINVAL, "loss kind must be AFR_LOSS_MSE (0) or AFR_LOSS_BCE (1), got %d", t.loss_kind);
+            if (!t.loss_scratch) return fail(AFR_EINVAL, "fused loss: null scratch");
+            if (t.mask_out) return fail(AFR_EINVAL, "the fused loss belongs to the last layer, mask_out to a hidden one");
+            g[0].loss = loss_args(t.loss_scratch, true, t.loss_kind, t.target, t.target_dtype, t.target_rows, t.mean_elems, t.loss_accum);
+        } else if (t.target_rows) return fail(AFR_EINVAL, "target_rows without target");
+        if (t.mask_out) {
+            if (dtype != AFR_BF16) return fail(AFR_EINVAL, "mask_out: bit masks exist with bf16 outputs only");
+            if (t.ldmask < N / 8) return fail(AFR_EINVAL, "ldmask = %d is smaller than N / 8 = %d", t.ldmask, N / 8);
+            g[0].mask_out = t.mask_out; g[0].ldmask = t.ldmask;
+        }
+        g[0].lda = ldx;
+        if (t.x_rows) g[0].a_rowmap = t.x_rows;
+    } else if (dx) {
+        g[0] = lin_dx(dy, W, out, t.aux, B, N, K, ob);
+        g[0].ldc = ldo;
+        if ((rc = linear_set_gate(g[0], t, dtype, K))) return rc;
+    } else if (dw) {
+        const int sk = t.splitk > 1 ? t.splitk : 1;
+        if (sk > 1 && t.p) return fail(AFR_EINVAL, "the fused optimizer step takes the whole gradient: splitk must be 1 (the cooperative pair splits inside its launch)");
+        g[0] = lin_dw(dy, x, (float*)out, t.db, B, N, K, sk, sk > 1 ? (long long)N * ldo : 0);
+        g[0].ldc = ldo; g[0].ldb = ldx;
+        if (t.db && sk > 1) g[0].colsum_stride = ld_db;
+        if ((rc = linear_set_opt(g[0], t, dtype))) return rc;
+    } else {
+        const PairPlan pp = pair_plan_shape(B, N, K);
+        const int sk = pp.sk_group;
+        if (sk < 1) return fail(AFR_EUNSUPPORTED, "%d x %d x %d: the gradient pair does not leave as one grouped launch", B, N, K);
+        if (!t.db) return fail(AFR_EINVAL, "AFR_LIN_PAIR: db is required");
+        if (t.x_rows && !pp.coop) return fail(AFR_EUNSUPPORTED, "a gathered weight-gradient operand needs the cooperative 256x256 launch");
+        if (t.p && !pp.coop) return fail(AFR_EUNSUPPORTED, "a fused optimizer step inside a grouped launch needs the cooperative 256x256 launch");
+        g[0] = lin_dw(dy, x, (float*)out, t.db, B, N, K, sk, pp.coop ? 0 : (long long)N * ldo);
+        g[0].ldc = ldo; g[0].ldb = ldx; g[0].colsum_stride = ld_db;
+        if (t.x_rows) g[0].b_rowmap = t.x_rows;
+        if ((rc = linear_set_opt(g[0], t, dtype))) return rc;
+        g[1] = lin_dx(dy, W, out2, t.aux, B, N, K, AFR_GEMM_OUT_BF16);
+        g[1].ldc = ldo;      // (both members are [.][K]: one ld_out serves dW / p / m / v and dx)
+        if ((rc = linear_set_gate(g[1], t, dtype, K))) return rc;
+        if (pp.coop) {
+            const size_t need = pair_workspace_bytes(N, K, pp);
+            if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255)) return fail(AFR_EINVAL, "workspace missing, too small or misaligned: %zu < %zu", workspace_bytes, need);
+            const size_t tiles = (size_t)((N + 255) / 256) * ((K + 255) / 256);
+            unsigned* cnt = (unsigned*)((char*)workspace + tiles * sk * AFR_FIX_SLICE_BYTES);
+            HIPCHK(hipMemsetAsync(cnt, 0, align_up(tiles * sizeof(unsigned), 256), s));
+            g[0].coop_ws = (float*)workspace; g[0].coop_cnt = cnt; g[0].coop_target = (unsigned)sk;
+        }
+        // (the grouped launcher would answer a member that cannot join with separate launches: here that is a refusal)
+        if (!afr_gemm_groupable(dtype, g[0]) || !afr_gemm_groupable(dtype, g[1]))
+            return fail(AFR_EUNSUPPORTED, "%d x %d x %d: a member of the pair cannot join a grouped launch", B, N, K);
+        if ((rc = check_operand_bytes(g[0])) || (rc = check_operand_bytes(g[1]))) return rc;
+        if ((rc = launcher_rc(afr_launch_gemm_group(dtype, g, 2, pp.tile256, s), "pair"))) return rc;
+        if (kernel_name) snprintf(kernel_name, name_cap, "%s", !pp.tile256 ? "gemm_bf16_group" : (t.p && t.opt_kind == AFR_OPT_LION) ? "gemm_bf16_group256_lion" : "gemm_bf16_group256");
+        return AFR_OK;
+    }
+    if (dtype == AFR_BF16 && (rc = check_operand_bytes(g[0]))) return rc;
+    if ((rc = launcher_rc(afr_launch_gemm(dtype, g[0], s), fwd ? "forward" : dx ? "input gradient" : "weight gradient"))) return rc;
+    if (kernel_name) snprintf(kernel_name, name_cap, "%s", afr_gemm_kernel_name(dtype, g[0]));
     return AFR_OK;
 }
 extern "C" int afr_op_reduce(float* dst, const float* slabs, int nslabs, int64_t stride, int64_t n, float scale, int acc,

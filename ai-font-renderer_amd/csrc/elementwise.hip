@@ -1292,7 +1292,7 @@ hipError_t afr_launch_glyph_l1_bwd(const float* slabs, int nslabs, long long sla
     return hipGetLastError();
 }
 
-// embedding_dense_backward (model.py:309): dEmb[x[b]] += d[b].  Deterministic, atomic-free: a block takes 256 glyph
+// embedding_dense_backward (model.py:309): dEmb[x[b]] += d[b].  Deterministic, atomic-free: a block takes EMB_BWD_ROWS (32) glyph
 // rows; thread (slot = tid>>5, c = tid&31) is the ONLY writer of LDS rows v with v%8 == slot, column c, and walks the
 // block's rows in order.  Block partials go to slabs[block][(vocab+n_fonts)*E]; afr_launch_reduce sums them in order.
 constexpr int EMB_BWD_ROWS = 32;
@@ -1300,7 +1300,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void glyph_embed_bwd_kernel(const T* __restrict__ d, const int64_t* __restrict__ x,
                                                               const int64_t* __restrict__ font, int B, int E, int vocab,
                                                               int n_fonts, float* __restrict__ slabs) {
-    extern __shared__ float sm[];                  // acc [(vocab+n_fonts)][E] | tile [256][E+1] | ids [256] | fids [256]
+    extern __shared__ float sm[];                  // acc [(vocab+n_fonts)][E] | tile [EMB_BWD_ROWS][E+1] | ids [EMB_BWD_ROWS] | fids [EMB_BWD_ROWS]
     const int rows_tot = vocab + n_fonts;
     const int LDT = E + 1;
     float* acc = sm;

@@ -419,6 +419,58 @@ int afr_op_gemm_fix(int flags, const void* A, const void* B, void* C, const floa
 int afr_op_gemm_pair_plan(int B, int N, int K, int* splitk, size_t* workspace_bytes);
 int afr_op_gemm_pair(const void* dy, const void* x, const void* W, const void* aux, float* dW, float* db_part, void* dX,
                      int B, int N, int K, void* workspace, size_t workspace_bytes, void* stream);
+/* One product of the Linear y[B][N] = x[B][K] . W[N][K]^T + b exactly as a training step issues it: the launch description the
+ * step builds for that product, with the tails a step hangs on it set from `tail`, through the step's launchers.  No afr_op_gemm*
+ * flag reaches these tails; this entry adds no kernel and no dispatch rule.  dtype AFR_F32 / AFR_BF16X3: f32 operands and outputs;
+ * AFR_BF16: bf16 x, W, dy, aux, y and dx.  dW, db, p, m, v are always float32.  N and K multiples of 8 (bf16) or 4.
+ *   AFR_LIN_FWD   out = y [B][N] = x . W^T + bias.  With tail->target: the fused loss -- out receives du instead, *loss_accum +=
+ *                 the loss (afr_config.loss semantics, afr_loss_grad's formulas; fused and unfused leave the same du bit for
+ *                 bit); target [rows][N] dense uint8 / float32, target_rows (or NULL) int32 [B]: row b's targets are row
+ *                 target_rows[b]; loss_scratch: 1040 + ceil(B/128) * ceil(N/128) floats, zero before the first call (afr_op_mse_grad's
+ *                 contract).  mask_out (AFR_BF16): AFR_GEMM_RELU is applied and bit n & 7 of mask_out[b * ldmask + n / 8] =
+ *                 [stored y(b, n) > 0].  x_rows (AFR_BF16): int32 [B], row b of x is row x_rows[b] of the table x, rows ldx apart.
+ *   AFR_LIN_DX    out = dx [B][K] = dy . W, gated by ReLU's mask: (aux[b][k] > 0) with aux [B][ldaux] (rows aux_rows[b] of a
+ *                 table when aux_rows is given), or bit k & 7 of mask_in[b * ldmask + k / 8] (AFR_BF16; read INSTEAD of aux).
+ *   AFR_LIN_DW    out = dW [N][K] = dy^T . x;  db [N] = column sums of dy (or NULL).  splitk > 1: out = splitk slabs, N * ld_out
+ *                 floats apart, and db = splitk rows ld_db apart: slice s covers batch rows [s * len, min(B, (s + 1) * len)), len =
+ *                 ceil(B / splitk) rounded up to the kernel's K-tile (32, bf16: 64); a slice that starts at or beyond B is zeros.
+ *                 With tail->p (splitk 1 only): the fused optimizer step -- dW is not stored; opt_kind AFR_OPT_ADAMW / AFR_OPT_LION is
+ *                 applied to p, m, v (Lion: v unused) and the bf16 `shadow` (or NULL) at the positions [n * ld_out + k].
+ *   AFR_LIN_PAIR  (AFR_BF16) both gradient products in ONE grouped launch as afr_op_linear_pair_plan describes it: out = dW
+ *                 (cooperative: the finished gradient, or the fused optimizer step as above) or its splitk slabs, db = splitk
+ *                 rows, out2 = dx [B][K] with the AFR_LIN_DX gates.  x_rows: the dW member reads x through the row map
+ *                 (cooperative launches only).  workspace: workspace_bytes of the plan, 256-byte aligned, contents free.
+ *                 The dx member reads W: a fused step leaves W itself alone (the new bf16 weights go to `shadow`).
+ * ld_out, ldx, ldaux, ld_db: leading dimensions in elements, 0 = dense.  kernel_name (or NULL) receives the kernel the launch ran on:
+ * "gemm_bf16<0,0,4>", "gemm_f32<1,1>", ..., "gemm_bf16_group", "gemm_bf16_group256", "gemm_bf16_group256_lion".
+ * Errors: null pointers, bad extents or strides, a tail that `which` does not have -> AFR_EINVAL; a combination the launchers
+ * refuse (a row map off the 256x128 ring, a BCE loss on gathered rows, ...) -> AFR_EUNSUPPORTED with a message: never a fallback. */
+enum { AFR_LIN_FWD = 0, AFR_LIN_DX = 1, AFR_LIN_DW = 2, AFR_LIN_PAIR = 3 };
+typedef struct afr_linear_tail {
+    int32_t ld_out, ldx, ldaux, ld_db;          /* elements; 0 = dense                                       */
+    /* forward */
+    const void* target; const int32_t* target_rows; int32_t target_dtype, loss_kind; int64_t mean_elems;
+    float* loss_accum; float* loss_scratch;
+    uint8_t* mask_out;
+    const int32_t* x_rows;                      /* forward: rows of x; pair: rows of x for the dW member     */
+    /* input gradient */
+    const void* aux; const int32_t* aux_rows; const uint8_t* mask_in;
+    int32_t ldmask;                             /* bytes per row of mask_out / mask_in                       */
+    /* weight gradient */
+    int32_t splitk;                             /* 0 or 1: none (AFR_LIN_PAIR: the plan's, not read)         */
+    float* db;
+    int32_t opt_kind, reserved;                 /* AFR_OPT_*                                                 */
+    float *p, *m, *v; void* shadow;             /* p != NULL: fused optimizer step                           */
+    float lr, beta1, beta2, eps, weight_decay, grad_scale;   /* grad_scale must be 1 (the fused tails take g unscaled) */
+    int64_t t;
+} afr_linear_tail;
+/* How AFR_LIN_PAIR launches at this shape (host-only): *tile256 = 1: 256x256 tiles (gemm_bf16_group256), 0: 256x128
+ * (gemm_bf16_group); *splitk = slices of the weight gradient; *coop = 1: the slices meet inside the launch, 0: splitk slabs.
+ * AFR_EUNSUPPORTED when the pair does not leave as one grouped launch at this shape. */
+int afr_op_linear_pair_plan(int B, int N, int K, int* tile256, int* splitk, int* coop, size_t* workspace_bytes);
+int afr_op_linear(int dtype, int which, const void* x, const void* W, const float* bias, const void* dy, void* out, void* out2,
+                  int B, int N, int K, const afr_linear_tail* tail /* or NULL */, void* workspace, size_t workspace_bytes,
+                  char* kernel_name /* or NULL */, int name_cap, void* stream);
 int afr_op_reduce(float* dst, const float* slabs, int nslabs, int64_t slab_stride, int64_t n,
                   float scale, int accumulate, void* stream);
 /* Several slab reductions in ONE launch (what a backward pass uses for all its split-K / per-block partial gradients):

@@ -117,3 +117,34 @@ def gemm_pair(dy, x, W, aux=None, repeats=1):
         torch.cuda.synchronize()
         outs.append((dW.cpu(), dbp.sum(0).cpu(), dX.float().cpu()))
     return outs, sk.value
+
+
+LIN_KINDS = {"fwd": _lib.LIN_FWD, "dx": _lib.LIN_DX, "dw": _lib.LIN_DW, "pair": _lib.LIN_PAIR}
+LIN_DTYPES = {"f32": _lib.AFR_F32, "bf16": _lib.AFR_BF16, "bf16x3": _lib.AFR_BF16X3}
+
+
+def linear(dtype, which, B, N, K, out, x=None, W=None, bias=None, dy=None, out2=None, workspace=None, **tail):
+    """One product of the Linear y[B][N] = x[B][K] . W[N][K]^T + b through afr_op_linear, on device tensors the caller owns
+    (`out` and whatever the tail names are written in place).  dtype 'f32' | 'bf16' | 'bf16x3'; which 'fwd' | 'dx' | 'dw' | 'pair';
+    tail: fields of afr_linear_tail by name, device tensors for the pointers.  Synchronises and returns the kernel's name."""
+    t = _lib.AfrLinearTail()
+    for k, v in tail.items():
+        if not hasattr(t, k):
+            raise TypeError(f"afr_linear_tail has no field {k!r}")
+        setattr(t, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
+    if "p" in tail and "grad_scale" not in tail:
+        t.grad_scale = 1.0
+    name = C.create_string_buffer(64)
+    _lib.check(_lib.lib().afr_op_linear(LIN_DTYPES[dtype], LIN_KINDS[which], ptr(x), ptr(W), ptr(bias), ptr(dy), ptr(out), ptr(out2), B, N, K,
+                                        C.byref(t), ptr(workspace), workspace.numel() * workspace.element_size() if workspace is not None else 0,
+                                        name, 64, stream()))
+    torch.cuda.synchronize()
+    return name.value.decode()
+
+
+def linear_pair_plan(B, N, K):
+    """afr_op_linear_pair_plan -> (tile256, splitk, coop, workspace_bytes), or None where the pair is not one grouped launch."""
+    t, s, c, w = C.c_int(), C.c_int(), C.c_int(), C.c_size_t()
+    if _lib.lib().afr_op_linear_pair_plan(B, N, K, C.byref(t), C.byref(s), C.byref(c), C.byref(w)) != 0:
+        return None
+    return t.value, s.value, c.value, w.value
