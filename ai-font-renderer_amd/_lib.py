@@ -178,6 +178,18 @@ SIGNATURES = {
     "afr_op_sheet_fwd": (_i32, [_i32, C.POINTER(AfrSheetParams), _vp, _i32, _i32, _i32, _i32, _i32, _f32, C.POINTER(AfrSheetDropout), _vp, _vp, _vp, _vp]),
     "afr_op_sheet_bwd": (_i32, [_i32, C.POINTER(AfrSheetParams), _vp, _i32, _i32, _i32, _i32, _i32, _f32, C.POINTER(AfrSheetDropout), _vp, _vp, _vp,
                                 C.POINTER(AfrSheetSlabLayout), _vp]),
+    "afr_glyph_k0": (_i32, [_i32, _i32, _i32]),
+    "afr_glyph_l1_bwd_blocks": (_i32, [_i32]),
+    "afr_embed_bwd_blocks": (_i32, [_i32]),
+    "afr_glyph_l1_bwd_fused_eligible": (_i32, [_i32, _i32, _i32, _i32, _i32]),
+    "afr_glyph_l1_bwd_fused_split": (_i32, [_i32, _i32]),
+    "afr_glyph_l1_bwd_fused_blocks": (_i32, [_i32, _i32]),
+    "afr_glyph_l1_bwd_fused_slab_floats": (C.c_longlong, [_i32, _i32, _i32, _i32]),
+    "afr_op_glyph_embed": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "afr_op_glyph_combo": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "afr_op_glyph_l1_bwd": (_i32, [_vp, _i32, C.c_longlong, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "afr_op_glyph_l1_bwd_fused": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "afr_op_glyph_embed_bwd": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
 }
 
 

@@ -337,6 +337,12 @@ extern "C" int afr_plan_create(const afr_config* c, afr_plan** out) {
                 p->o_w1t = carve((size_t)c->hidden[0] * E * 2);
             }
         }
+        // the plain embedding path's backward (glyph_embed_bwd_kernel) keeps the whole table's accumulator in one block's LDS
+        if (!p->k0 && afr_glyph_embed_bwd_lds_bytes(E, c->vocab, c->n_fonts) > 160 * 1024) {
+            delete p;
+            return fail(AFR_EUNSUPPORTED, "glyph net without a folded first layer: the embedding backward needs %zu bytes of LDS for (vocab + n_fonts) x embed_dim = %d x %d, above 160 KiB",
+                        afr_glyph_embed_bwd_lds_bytes(E, c->vocab, c->n_fonts), c->vocab + c->n_fonts, E);
+        }
         p->o_slab_e = carve(eb * (size_t)(c->vocab + c->n_fonts) * E * sizeof(float));
         {
             const size_t ncombo = (size_t)c->vocab * (c->n_fonts > 0 ? c->n_fonts : 1);
@@ -2484,5 +2490,102 @@ extern "C" int afr_op_sheet_bwd(int act_dtype, const afr_sheet_params* params, c
     SheetSlabOff so{lay->pos, lay->emb, lay->w_in, lay->b_in, lay->w_o, lay->b_o, lay->ln_g, lay->ln_b, lay->w1, lay->b1, lay->total};
     HIPCHK(afr_launch_sheet_bwd(act_dtype, d, sheet_op_params(params), sheet_op_drop(drop, const_cast<float*>(save)), x, ldx, B, dz, ln_eps, slabs, so,
                                 (hipStream_t)stream));
+    return AFR_OK;
+}
+
+// ---- the glyph nets' first-layer kernels one call each (include/afr.h): argument checks, then the launcher the plan calls
+constexpr size_t GLYPH_OP_LDS_MAX = 160 * 1024;
+static int glyph_op_shape(const char* what, int act_dtype, int B, int E, int vocab, int n_fonts) {
+    if (act_dtype != AFR_F32 && act_dtype != AFR_BF16) return fail(AFR_EINVAL, "%s: act_dtype must be AFR_F32 or AFR_BF16, got %d", what, act_dtype);
+    if (B < 1) return fail(AFR_EINVAL, "%s: B = %d must be >= 1", what, B);
+    if (vocab < 1 || n_fonts < 0) return fail(AFR_EINVAL, "%s: vocab = %d, n_fonts = %d", what, vocab, n_fonts);
+    if (E < 8 || E % 8) return fail(AFR_EUNSUPPORTED, "%s: E = %d must be a positive multiple of 8", what, E);
+    if ((long long)(vocab + (long long)n_fonts) * E >= (1ll << 31)) return fail(AFR_EUNSUPPORTED, "%s: a table must stay below 2^31 floats", what);
+    return AFR_OK;
+}
+static int glyph_op_n1(const char* what, int N1) {
+    if (N1 < 8 || N1 % 8) return fail(AFR_EUNSUPPORTED, "%s: N1 = %d must be a positive multiple of 8", what, N1);
+    return AFR_OK;
+}
+// the fold's post-pass stages K0 columns and E-wide rows per block (as the table + gather kernels do)
+static int glyph_op_fold(const char* what, int E, int vocab, int n_fonts) {
+    const long long K0 = (long long)E + ((long long)vocab + n_fonts + 7) / 8 * 8;
+    if (K0 > 512 || E > 128) return fail(AFR_EUNSUPPORTED, "%s: K0 = %lld, E = %d: the folded first layer takes K0 <= 512 and E <= 128", what, K0, E);
+    return AFR_OK;
+}
+static int glyph_op_lds(const char* what, size_t lds) {
+    if (lds > GLYPH_OP_LDS_MAX) return fail(AFR_EUNSUPPORTED, "%s: %zu bytes of dynamic LDS requested, above 160 KiB", what, lds);
+    return AFR_OK;
+}
+extern "C" int afr_op_glyph_embed(int act_dtype, const float* emb, const float* femb, const int64_t* x, const int64_t* font, int B, int E, int vocab,
+                                  int n_fonts, void* out, uint32_t* err, void* stream) {
+    const char* what = "afr_op_glyph_embed";
+    if (int rc = glyph_op_shape(what, act_dtype, B, E, vocab, n_fonts)) return rc;
+    if (!emb || !x || !out || !err || (n_fonts > 0 && !femb)) return fail(AFR_EINVAL, "%s: null argument", what);
+    DevGuard dg(device_of(out));
+    HIPCHK(afr_launch_glyph_embed(act_dtype, emb, femb, x, font, B, E, vocab, n_fonts, out, err, (hipStream_t)stream));
+    return AFR_OK;
+}
+extern "C" int afr_op_glyph_combo(const float* emb, const float* femb, const float* W1, const float* b1, const int64_t* x, const int64_t* font, int B,
+                                  int E, int N1, int vocab, int n_fonts, void* h1c, int ld1, void* h0c, int32_t* cidx, void* w1t, uint32_t* err,
+                                  void* stream) {
+    const char* what = "afr_op_glyph_combo";
+    if (int rc = glyph_op_shape(what, AFR_BF16, B, E, vocab, n_fonts)) return rc;
+    if (int rc = glyph_op_n1(what, N1)) return rc;
+    const size_t lds = (size_t)(256 * (E + 1) + 2 * 4 * E) * sizeof(float);      // glyph_combo_kernel: W [256][E+1] | 4 + 4 table rows
+    if (lds > 48 * 1024) return fail(AFR_EUNSUPPORTED, "%s: E = %d needs %zu bytes of staging, above the kernel's 48 KiB (E <= 40)", what, E, lds);
+    if (ld1 < N1) return fail(AFR_EINVAL, "%s: ld1 = %d is below N1 = %d", what, ld1, N1);
+    if ((long long)vocab * (n_fonts > 0 ? n_fonts : 1) * (long long)ld1 >= (1ll << 31)) return fail(AFR_EUNSUPPORTED, "%s: the combination table must stay below 2^31 elements", what);
+    if (!emb || !W1 || !b1 || !x || !h1c || !h0c || !cidx || !err || (n_fonts > 0 && !femb)) return fail(AFR_EINVAL, "%s: null argument", what);
+    if ((uintptr_t)W1 & 15) return fail(AFR_EINVAL, "%s: W1 must be 16-byte aligned", what);
+    DevGuard dg(device_of(h1c));
+    HIPCHK(afr_launch_glyph_combo(emb, femb, W1, b1, x, font, B, E, N1, vocab, n_fonts, nullptr, h1c, ld1, h0c, cidx, err, (hipStream_t)stream, w1t));
+    return AFR_OK;
+}
+extern "C" int afr_op_glyph_l1_bwd(const float* slabs, int nslabs, long long slab_stride, const float* W1, int N1, int E, int vocab, int n_fonts,
+                                   float* dw1, float* dtab_part, void* stream) {
+    const char* what = "afr_op_glyph_l1_bwd";
+    if (int rc = glyph_op_shape(what, AFR_F32, 1, E, vocab, n_fonts)) return rc;
+    if (int rc = glyph_op_n1(what, N1)) return rc;
+    if (int rc = glyph_op_fold(what, E, vocab, n_fonts)) return rc;
+    const int K0 = afr_glyph_k0(E, vocab, n_fonts);
+    if (nslabs < 1) return fail(AFR_EINVAL, "%s: nslabs = %d must be >= 1", what, nslabs);
+    if (slab_stride % 4 || (nslabs > 1 && slab_stride < (long long)N1 * K0))
+        return fail(AFR_EINVAL, "%s: slab_stride = %lld must be a multiple of 4 and at least N1 * K0 = %lld", what, slab_stride, (long long)N1 * K0);
+    if (!slabs || !W1 || !dw1 || !dtab_part) return fail(AFR_EINVAL, "%s: null argument", what);
+    if ((uintptr_t)slabs & 15) return fail(AFR_EINVAL, "%s: slabs must be 16-byte aligned", what);
+    const int G = std::max(1, std::min(1024 / (8 * K0 / 4), 8));                   // glyph_l1_bwd_kernel: S | W | the other lane groups' partials
+    if (int rc = glyph_op_lds(what, ((size_t)8 * (K0 + E) + (size_t)(G - 1) * 8 * K0) * sizeof(float))) return rc;
+    DevGuard dg(device_of(dw1));
+    HIPCHK(afr_launch_glyph_l1_bwd(slabs, nslabs, slab_stride, W1, N1, E, vocab, n_fonts, dw1, dtab_part, (hipStream_t)stream));
+    return AFR_OK;
+}
+extern "C" int afr_op_glyph_l1_bwd_fused(const void* d1, const void* h0, int ldh, const int32_t* h0_rowmap, const void* W1T, const int64_t* x,
+                                         const int64_t* font, int B, int N1, int vocab, int n_fonts, float* slabs, void* stream) {
+    const char* what = "afr_op_glyph_l1_bwd_fused";
+    if (int rc = glyph_op_shape(what, AFR_BF16, B, 32, vocab, n_fonts)) return rc;
+    if (int rc = glyph_op_n1(what, N1)) return rc;
+    if (!afr_glyph_l1_bwd_fused_eligible(AFR_BF16, 32, N1, vocab, n_fonts))
+        return fail(AFR_EUNSUPPORTED, "%s: N1 = %d, vocab + n_fonts = %d: the fused backward takes N1 a multiple of 128 in 256 .. 1024 and at most 144 table rows (E = 32)",
+                    what, N1, vocab + n_fonts);
+    if (ldh < 32 || ldh % 8) return fail(AFR_EINVAL, "%s: ldh = %d must be a multiple of 8, at least 32", what, ldh);
+    if ((long long)B * N1 * 2 >= (1ll << 31) || (!h0_rowmap && (long long)B * ldh * 2 >= (1ll << 31)))
+        return fail(AFR_EUNSUPPORTED, "%s: d1 and h0 must stay below 2 GiB", what);
+    if (!d1 || !h0 || !W1T || !x || !slabs) return fail(AFR_EINVAL, "%s: null argument", what);
+    if (((uintptr_t)d1 & 15) || ((uintptr_t)h0 & 15) || ((uintptr_t)W1T & 15) || ((uintptr_t)slabs & 15))
+        return fail(AFR_EINVAL, "%s: d1, h0, W1T and slabs must be 16-byte aligned", what);
+    if (int rc = glyph_op_lds(what, (size_t)(N1 / afr_glyph_l1_bwd_fused_split(B, N1) / 128 + 1) * 16384 + 2 * 64 * sizeof(int))) return rc;
+    DevGuard dg(device_of(slabs));
+    HIPCHK(afr_launch_glyph_l1_bwd_fused(d1, N1, h0, ldh, W1T, x, font, B, N1, vocab, n_fonts, slabs, (hipStream_t)stream, h0_rowmap, nullptr));
+    return AFR_OK;
+}
+extern "C" int afr_op_glyph_embed_bwd(int act_dtype, const void* d, const int64_t* x, const int64_t* font, int B, int E, int vocab, int n_fonts,
+                                      float* slabs, void* stream) {
+    const char* what = "afr_op_glyph_embed_bwd";
+    if (int rc = glyph_op_shape(what, act_dtype, B, E, vocab, n_fonts)) return rc;
+    if (int rc = glyph_op_lds(what, afr_glyph_embed_bwd_lds_bytes(E, vocab, n_fonts))) return rc;
+    if (!d || !x || !slabs) return fail(AFR_EINVAL, "%s: null argument", what);
+    DevGuard dg(device_of(slabs));
+    HIPCHK(afr_launch_glyph_embed_bwd(act_dtype, d, x, font, B, E, vocab, n_fonts, slabs, (hipStream_t)stream));
     return AFR_OK;
 }

@@ -411,7 +411,9 @@ hipError_t afr_launch_clamp_out(int act_dtype, const void* u, float* y, long lon
 hipError_t afr_launch_glyph_embed(int act_dtype, const float* emb, const float* font_emb, const int64_t* x,
                                   const int64_t* font, int B, int E, int vocab, int n_fonts, void* out,
                                   uint32_t* err_flag, hipStream_t s);
-int afr_embed_bwd_blocks(int B);
+// (the glyph getters below are also exported, include/afr.h: a caller of the afr_op_glyph_* entries sizes its buffers with them)
+extern "C" int afr_embed_bwd_blocks(int B);
+size_t afr_glyph_embed_bwd_lds_bytes(int E, int vocab, int n_fonts);      // dynamic LDS of glyph_embed_bwd_kernel; at most 160 KiB fit
 hipError_t afr_launch_glyph_l1_fwd(int act_dtype, const float* emb, const float* font_emb, const float* W1, const float* b1,
                                    const int64_t* x, const int64_t* font, int B, int E, int N1, int vocab, int n_fonts,
                                    float* table, void* h0, void* h1, uint32_t* err_flag, hipStream_t s, void* w1t = nullptr);
@@ -419,13 +421,13 @@ hipError_t afr_launch_glyph_combo(const float* emb, const float* font_emb, const
                                   const int64_t* font, int B, int E, int N1, int vocab, int n_fonts, float* table, void* h1c,
                                   int ld1 /* row stride of h1c, elements */, void* h0c, int* cidx, uint32_t* err_flag, hipStream_t s,
                                   void* w1t);
-int afr_glyph_k0(int E, int vocab, int n_fonts);
-int afr_glyph_l1_bwd_blocks(int N1);
+extern "C" int afr_glyph_k0(int E, int vocab, int n_fonts);
+extern "C" int afr_glyph_l1_bwd_blocks(int N1);
 // the same backward in one kernel (throughput mode, gemm.hip: glyph_l1_bwd_fused_kernel); W1T = bf16 [E][N1] from the forward
-bool afr_glyph_l1_bwd_fused_eligible(int dtype, int E, int N1, int vocab, int n_fonts);
-int afr_glyph_l1_bwd_fused_split(int B, int N1);                                  // column ranges per block of 64 glyphs
-int afr_glyph_l1_bwd_fused_blocks(int B, int N1);
-long long afr_glyph_l1_bwd_fused_slab_floats(int B, int N1, int vocab, int n_fonts);   // [dW1 nc*E | db1 nc | dTab rows*E], nc = N1 / split
+extern "C" int afr_glyph_l1_bwd_fused_eligible(int dtype, int E, int N1, int vocab, int n_fonts);   // 1 / 0
+extern "C" int afr_glyph_l1_bwd_fused_split(int B, int N1);                       // column ranges per block of 64 glyphs
+extern "C" int afr_glyph_l1_bwd_fused_blocks(int B, int N1);
+extern "C" long long afr_glyph_l1_bwd_fused_slab_floats(int B, int N1, int vocab, int n_fonts);   // [dW1 nc*E | db1 nc | dTab rows*E], nc = N1 / split
 hipError_t afr_launch_glyph_l1_bwd_fused(const void* d1, int ldd, const void* h0, int ldh, const void* W1T, const int64_t* x,
                                          const int64_t* font, int B, int N1, int vocab, int n_fonts, float* slabs, hipStream_t s,
                                          const int* h0_rowmap = nullptr, const LossSum* loss = nullptr);   // loss: one more workgroup adds deferred partials

@@ -1335,10 +1335,23 @@ __global__ __launch_bounds__(256) void glyph_embed_bwd_kernel(const T* __restric
     for (int i = threadIdx.x; i < rows_tot * E; i += 256) out[i] = acc[i];
 }
 int afr_embed_bwd_blocks(int B) { return (B + EMB_BWD_ROWS - 1) / EMB_BWD_ROWS; }
+size_t afr_glyph_embed_bwd_lds_bytes(int E, int vocab, int n_fonts) {
+    return ((size_t)(vocab + n_fonts) * E + (size_t)EMB_BWD_ROWS * (E + 1)) * sizeof(float) + 2 * EMB_BWD_ROWS * sizeof(int);
+}
 hipError_t afr_launch_glyph_embed_bwd(int act_dtype, const void* d, const int64_t* x, const int64_t* font, int B, int E,
                                       int vocab, int n_fonts, float* slabs, hipStream_t s) {
     if (B <= 0) return hipSuccess;
-    const size_t lds = ((size_t)(vocab + n_fonts) * E + (size_t)EMB_BWD_ROWS * (E + 1)) * sizeof(float) + 2 * EMB_BWD_ROWS * sizeof(int);
+    const size_t lds = afr_glyph_embed_bwd_lds_bytes(E, vocab, n_fonts);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;                  // the whole table's accumulator sits in one block's LDS
+    static size_t set[2][16];                        // largest dynamic-LDS opt-in made so far, per instantiation and device
+    int dev = 0;
+    const int ti = act_dtype == AFR_BF16 ? 1 : 0;
+    if (lds > 48 * 1024 && hipGetDevice(&dev) == hipSuccess && (dev < 0 || dev >= 16 || set[ti][dev] < lds)) {
+        hipError_t e = ti ? hipFuncSetAttribute((const void*)glyph_embed_bwd_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
+                          : hipFuncSetAttribute((const void*)glyph_embed_bwd_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        if (dev >= 0 && dev < 16) set[ti][dev] = lds;
+    }
     dim3 g(afr_embed_bwd_blocks(B)), b(256);
     if (act_dtype == AFR_BF16)
         hipLaunchKernelGGL(glyph_embed_bwd_kernel<bf16_t>, g, b, lds, s, (const bf16_t*)d, x, font, B, E, vocab, n_fonts, slabs);

@@ -2125,7 +2125,7 @@ hipError_t afr_launch_gemm(int dtype, const GemmParams& p_in, hipStream_t s) {
 }
 
 // ---- folded first layer, fused backward (bf16)
-bool afr_glyph_l1_bwd_fused_eligible(int dtype, int E, int N1, int vocab, int n_fonts) {
+int afr_glyph_l1_bwd_fused_eligible(int dtype, int E, int N1, int vocab, int n_fonts) {
     return dtype == AFR_BF16 && E == bf16k::L1_E && N1 % 128 == 0 && N1 >= 256 && N1 <= 1024 && vocab + n_fonts <= 144;
 }
 // column ranges per row block: enough blocks to cover the chip, ranges of whole 128-column sub-tiles

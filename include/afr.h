@@ -609,6 +609,53 @@ int afr_op_sheet_bwd(int act_dtype, const afr_sheet_params* params, const int64_
                      float ln_eps, const afr_sheet_dropout* drop /* or NULL */, const void* dz, const float* save /* or NULL */,
                      float* slabs, const afr_sheet_slab_layout* layout, void* stream);
 
+/* ---- the glyph nets' first layer (AFR_KIND_GLYPH), its kernels one call each, exactly as the plan issues them.  E = embed_dim,
+ * N1 = width of fc1, both multiples of 8; K0 = afr_glyph_k0(E, vocab, n_fonts) = E + (vocab + n_fonts rounded up to 8), the columns
+ * of the widened operand h0' = [h0 | one-hot of x | one-hot of vocab + font | zero pad].  act_dtype AFR_F32 or AFR_BF16 is the
+ * type T of the activations (out, d); the tables emb [vocab][E], femb [n_fonts][E], W1 [N1][E], b1 [N1], every slab and
+ * partial are float32; x, font are int64 [B].  n_fonts == 0: femb and font are not read.  font == NULL with n_fonts > 0 means
+ * font 0 for every glyph.  The forward kernels set bit 0 of *err (device word) for an index outside its table and clamp it; the
+ * backward kernels clamp without flagging.  Pointers not marked "or NULL" are required.
+ *   glyph_embed        out T [B][E] = emb[x] + femb[font].
+ *   glyph_combo        bf16, one launch: h1c [vocab * max(n_fonts, 1)][ld1] (ld1 >= N1; columns N1 .. ld1 are not written) = the h1
+ *                      row of combination c = x * max(n_fonts, 1) + font: relu((T[x] + b1) + T[vocab + font]) with
+ *                      T = [emb; femb] . W1^T in float32; h0c bf16 [..][E] = emb[x] + femb[font]; cidx int32 [B] = c of glyph b;
+ *                      w1t (or NULL): bf16 [E][N1] = W1^T.  E <= 40 (48 KiB of staging).
+ *   glyph_l1_bwd       the post-pass over the widened weight-gradient slabs [nslabs][N1][K0] (slab z at z * slab_stride floats, a
+ *                      multiple of 4): dw1 [N1][E] = the slab sum's first E columns; dtab_part [afr_glyph_l1_bwd_blocks(N1)]
+ *                      [vocab + n_fonts][E]: per block of 8 fc1 rows n, sum_n S[n][r] W1[n][k] with S = the one-hot columns.
+ *   glyph_l1_bwd_fused bf16, E = 32: one kernel per (64 glyphs, column range).  d1 bf16 [B][N1] (row stride N1), h0 bf16 rows of
+ *                      ldh elements whose first 32 are emb[x] + femb[font] (row b, or row h0_rowmap[b] with a row map), W1T bf16
+ *                      [32][N1].  slabs f32 [afr_glyph_l1_bwd_fused_blocks(B, N1)][afr_glyph_l1_bwd_fused_slab_floats(..)]:
+ *                      block (row block rb, range cs) = rb * split + cs holds [dW1 nc x 32 | db1 nc | dTab (vocab + n_fonts) x 32]
+ *                      for its nc = N1 / split columns, dTab from ITS columns' share of dh0, rounded to bf16 per glyph.
+ *                      Only where afr_glyph_l1_bwd_fused_eligible(AFR_BF16, 32, N1, vocab, n_fonts).
+ *   glyph_embed_bwd    slabs f32 [afr_embed_bwd_blocks(B)][vocab + n_fonts][E]: per block of 32 glyphs the sum of d[b] by table
+ *                      row, in b order.  The table's accumulator sits in LDS: ((vocab + n_fonts) E + 32 (E + 1)) floats + 256
+ *                      bytes must fit 160 KiB (AFR_EUNSUPPORTED beyond; afr_plan_create refuses such a glyph config).
+ * The table + gather pair of the folded forward (afr_launch_glyph_l1_fwd) has no entry of its own yet.
+ * Refused with a message before anything is launched: B < 1, vocab < 1, n_fonts < 0, a NULL required pointer (AFR_EINVAL); E or N1
+ * not a multiple of 8, the limits above, a dynamic-LDS request above 160 KiB (AFR_EUNSUPPORTED). */
+int afr_glyph_k0(int E, int vocab, int n_fonts);                 /* host-only getters, all of them */
+int afr_glyph_l1_bwd_blocks(int N1);
+int afr_embed_bwd_blocks(int B);
+int afr_glyph_l1_bwd_fused_eligible(int dtype, int E, int N1, int vocab, int n_fonts);   /* 1 or 0 */
+int afr_glyph_l1_bwd_fused_split(int B, int N1);                 /* column ranges per block of 64 glyphs */
+int afr_glyph_l1_bwd_fused_blocks(int B, int N1);
+long long afr_glyph_l1_bwd_fused_slab_floats(int B, int N1, int vocab, int n_fonts);
+int afr_op_glyph_embed(int act_dtype, const float* emb, const float* femb, const int64_t* x, const int64_t* font /* or NULL */, int B,
+                       int E, int vocab, int n_fonts, void* out, uint32_t* err, void* stream);
+int afr_op_glyph_combo(const float* emb, const float* femb, const float* W1, const float* b1, const int64_t* x,
+                       const int64_t* font /* or NULL */, int B, int E, int N1, int vocab, int n_fonts, void* h1c, int ld1, void* h0c,
+                       int32_t* cidx, void* w1t /* or NULL */, uint32_t* err, void* stream);
+int afr_op_glyph_l1_bwd(const float* slabs, int nslabs, long long slab_stride, const float* W1, int N1, int E, int vocab, int n_fonts,
+                        float* dw1, float* dtab_part, void* stream);
+int afr_op_glyph_l1_bwd_fused(const void* d1, const void* h0, int ldh, const int32_t* h0_rowmap /* or NULL */, const void* W1T,
+                              const int64_t* x, const int64_t* font /* or NULL */, int B, int N1, int vocab, int n_fonts,
+                              float* slabs, void* stream);
+int afr_op_glyph_embed_bwd(int act_dtype, const void* d, const int64_t* x, const int64_t* font /* or NULL */, int B, int E, int vocab,
+                           int n_fonts, float* slabs, void* stream);
+
 /* ---- fp8 building blocks of BASELINE configs[4] ("fp8 MFMA weights on CDNA4"; no counterpart in the reference) ----
  * Operands are OCP e4m3fn bytes (gfx950's native fp8: exponent bias 7, largest finite 448, no infinities) with ONE float
  * scale per tensor: value = scale * e4m3.  afr_op_f32_to_fp8: dst[i] = e4m3(src[i] / scale), round to nearest even,
