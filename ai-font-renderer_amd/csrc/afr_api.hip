@@ -1597,12 +1597,16 @@ extern "C" int afr_param_group_ranges(const afr_plan* p, afr_opt_range* out, int
     for (int k = 0; out && k < n && k < cap; ++k) out[k] = p->groups[k];
     return n;
 }
-// the grouped flat update of [first, first + n) of caller-owned buffers: the plan's own step and afr_op_opt_groups end here
-static int opt_groups_launch(int kind, float* P, const float* G, float* M, float* V, bf16_t* shadow, int64_t n, int64_t first, const afr_opt_range* r,
-                             int nr, const AdamArgs& h, float gscale, const float* sumsq, float max_norm, hipStream_t s) {
+// The flat update of n elements of caller-owned buffers, ONE launch: every site that steps outside a GEMM or the grouped reduce ends
+// here -- the plan's own step, the leftover tensors of a fused step and the afr_op_* optimizer entries.  sumsq: the clipped kernel.
+// rg: the slice is [rg->first, rg->first + n) of a flat buffer with these ranges (optimizer groups: the range-aware kernel).
+struct FlatRanges { const afr_opt_range* r; int n; int64_t first; };
+static int flat_step(int kind, float* P, const float* G, float* M, float* V, bf16_t* shadow, int64_t n, const AdamArgs& h, float gscale, hipStream_t s,
+                     const float* sumsq = nullptr, float max_norm = 0.f, const FlatRanges* rg = nullptr) {
     OptRangeTab tab;
-    if (int rc = build_range_tab(r, nr, first, n, h, kind, tab)) return rc;
-    HIPCHK(afr_launch_opt_groups(P, G, M, kind == OPT_LION ? nullptr : V, shadow, n, first, tab, adam_hyper(h, kind), gscale, s, sumsq, max_norm, kind));
+    if (rg) if (int rc = build_range_tab(rg->r, rg->n, rg->first, n, h, kind, tab)) return rc;
+    HIPCHK(afr_launch_flat_opt(FlatOpt{P, G, M, kind == OPT_LION ? nullptr : V, shadow, n, rg ? rg->first : 0, rg ? &tab : nullptr, h.lr, h.wd,
+                                       adam_hyper(h, kind), gscale, sumsq, max_norm, kind}, s));
     return AFR_OK;
 }
 extern "C" int afr_adamw_step(afr_plan* p, float lr, float b1, float b2, float eps, float wd, int64_t t, float gscale,
@@ -1621,16 +1625,13 @@ extern "C" int afr_adamw_step(afr_plan* p, float lr, float b1, float b2, float e
         if (rc) return rc;
         sumsq = cw + CLIP_WS_SUMSQ;
     }
-    const bool lion = p->opt_kind == OPT_LION;
-    if (!p->groups.empty()) {             // optimizer groups: the whole buffer in ONE launch of the range-aware kernel
-        ProfScope ps(p, s, lion ? (sumsq ? "lion_groups_clip" : "lion_groups") : (sumsq ? "adamw_groups_clip" : "adamw_groups"), 0.0,
-                     (double)p->total * ((lion ? 20.0 : 28.0) + (shadow ? 2.0 : 0.0)));
-        if (int rc = opt_groups_launch(p->opt_kind, p->P, p->G, p->M, p->V, shadow, p->total, 0, p->groups.data(), (int)p->groups.size(),
-                                       AdamArgs{lr, b1, b2, eps, wd, t}, gscale, sumsq, p->clip_norm, s)) return rc;
-    } else {
-        ProfScope ps(p, s, lion ? (sumsq ? "lion_clip" : "lion") : (sumsq ? "adamw_clip" : "adamw"), 0.0, (double)p->total * ((lion ? 20.0 : 28.0) + (shadow ? 2.0 : 0.0)));
-        HIPCHK(afr_launch_adamw(p->P, p->G, p->M, lion ? nullptr : p->V, shadow, p->total, lr, wd, adam_hyper(AdamArgs{lr, b1, b2, eps, wd, t}, p->opt_kind),
-                                gscale, s, sumsq, p->clip_norm, p->opt_kind));
+    const bool lion = p->opt_kind == OPT_LION, grouped = !p->groups.empty();
+    {                                     // the whole buffer in ONE launch (optimizer groups: of the range-aware kernel)
+        static const char* const tags[8] = {"adamw", "adamw_clip", "adamw_groups", "adamw_groups_clip", "lion", "lion_clip", "lion_groups", "lion_groups_clip"};
+        ProfScope ps(p, s, tags[lion * 4 + grouped * 2 + (sumsq != nullptr)], 0.0, (double)p->total * ((lion ? 20.0 : 28.0) + (shadow ? 2.0 : 0.0)));
+        const FlatRanges rg{p->groups.data(), (int)p->groups.size(), 0};
+        if (int rc = flat_step(p->opt_kind, p->P, p->G, p->M, p->V, shadow, p->total, AdamArgs{lr, b1, b2, eps, wd, t}, gscale, s, sumsq, p->clip_norm,
+                               grouped ? &rg : nullptr)) return rc;
     }
     p->wT_valid = false;
     return ema_step(p, sumsq, s);       // (a skipped step leaves the EMA alone too: the kernel reads the same sum)
@@ -1694,9 +1695,8 @@ static int reduce_and_step(afr_plan* p, hipStream_t s, RTable& rt, const StepCtx
         if (cov >= tn.numel) continue;
         const int64_t n = (tn.numel + 63) / 64 * 64;
         ProfScope ps(p, s, lion ? "lion" : "adamw", 0.0, (double)n * (lion ? 20.0 : 28.0));
-        const AdamArgs ht = args_at(p, h, tn.off);
-        HIPCHK(afr_launch_adamw(p->P + tn.off, p->G + tn.off, p->M + tn.off, lion ? nullptr : p->V + tn.off, shadow ? shadow + tn.off : nullptr, n, ht.lr, ht.wd,
-                                grouped ? adam_hyper(ht, p->opt_kind) : rt.ad, 1.f, s, nullptr, 0.f, p->opt_kind));
+        if ((rc = flat_step(p->opt_kind, p->P + tn.off, p->G + tn.off, p->M + tn.off, lion ? nullptr : p->V + tn.off, shadow ? shadow + tn.off : nullptr, n,
+                            args_at(p, h, tn.off), 1.f, s))) return rc;
     }
     if (p->o_shadow2) p->shadow_cur ^= 1;   // every tensor has been rewritten: the write shadow is the current one now
     return ema_step(p, nullptr, s);         // the step's last parameter write is behind us (never a clipping plan here)
@@ -2248,8 +2248,7 @@ extern "C" int afr_op_adamw(float* p, const float* g, float* m, float* v, void* 
                             float b2, float eps, float wd, int64_t t, float gscale, void* stream) {
     if (!p || !g || !m || !v || t < 1) return fail(AFR_EINVAL, "bad AdamW arguments");
     DevGuard dg(device_of(p));
-    HIPCHK(afr_launch_adamw(p, g, m, v, (bf16_t*)shadow, n, lr, wd, adam_hyper(AdamArgs{lr, b1, b2, eps, wd, t}), gscale, (hipStream_t)stream));
-    return AFR_OK;
+    return flat_step(OPT_ADAMW, p, g, m, v, (bf16_t*)shadow, n, AdamArgs{lr, b1, b2, eps, wd, t}, gscale, (hipStream_t)stream);
 }
 extern "C" int afr_op_adamw_clip(float* p, const float* g, float* m, float* v, void* shadow, int64_t n, float lr, float b1, float b2,
                                  float eps, float wd, int64_t t, float gscale, const float* sumsq, float max_norm, void* stream) {
@@ -2257,18 +2256,14 @@ extern "C" int afr_op_adamw_clip(float* p, const float* g, float* m, float* v, v
     if (int rc = check_step_count(t)) return rc;
     if (!(max_norm > 0.f) || std::isinf(max_norm)) return fail(AFR_EINVAL, "max_norm must be finite and > 0, got %g", (double)max_norm);
     DevGuard dg(device_of(p));
-    HIPCHK(afr_launch_adamw(p, g, m, v, (bf16_t*)shadow, n, lr, wd, adam_hyper(AdamArgs{lr, b1, b2, eps, wd, t}), gscale, (hipStream_t)stream, sumsq,
-                            max_norm));
-    return AFR_OK;
+    return flat_step(OPT_ADAMW, p, g, m, v, (bf16_t*)shadow, n, AdamArgs{lr, b1, b2, eps, wd, t}, gscale, (hipStream_t)stream, sumsq, max_norm);
 }
 extern "C" int afr_op_lion(float* p, const float* g, float* m, void* shadow, int64_t n, float lr, float b1, float b2, float wd,
                            float gscale, const float* sumsq, float max_norm, void* stream) {
     if (!p || !g || !m) return fail(AFR_EINVAL, "null argument");
     if (sumsq && (!(max_norm > 0.f) || std::isinf(max_norm))) return fail(AFR_EINVAL, "max_norm must be finite and > 0, got %g", (double)max_norm);
     DevGuard dg(device_of(p));
-    HIPCHK(afr_launch_adamw(p, g, m, nullptr, (bf16_t*)shadow, n, lr, wd, adam_hyper(AdamArgs{lr, b1, b2, 0.f, wd, 1}, OPT_LION), gscale,
-                            (hipStream_t)stream, sumsq, max_norm, OPT_LION));
-    return AFR_OK;
+    return flat_step(OPT_LION, p, g, m, nullptr, (bf16_t*)shadow, n, AdamArgs{lr, b1, b2, 0.f, wd, 1}, gscale, (hipStream_t)stream, sumsq, max_norm);
 }
 extern "C" int afr_op_opt_groups(int kind, float* p, const float* g, float* m, float* v, void* shadow, int64_t n, int64_t first,
                                  const afr_opt_range* ranges, int n_ranges, float lr, float b1, float b2, float eps, float wd, int64_t t, float gscale,
@@ -2278,8 +2273,9 @@ extern "C" int afr_op_opt_groups(int kind, float* p, const float* g, float* m, f
     if (int rc = check_step_count(t)) return rc;
     if (sumsq && (!(max_norm > 0.f) || std::isinf(max_norm))) return fail(AFR_EINVAL, "max_norm must be finite and > 0, got %g", (double)max_norm);
     DevGuard dg(device_of(p));
-    return opt_groups_launch(kind, p, g, m, v, (bf16_t*)shadow, n, first, ranges, n_ranges, AdamArgs{lr, b1, b2, eps, wd, kind == AFR_OPT_LION ? 1 : t}, gscale,
-                             sumsq, max_norm, (hipStream_t)stream);
+    const FlatRanges rg{ranges, n_ranges, first};
+    return flat_step(kind, p, g, m, v, (bf16_t*)shadow, n, AdamArgs{lr, b1, b2, eps, wd, kind == AFR_OPT_LION ? 1 : t}, gscale, (hipStream_t)stream, sumsq, max_norm,
+                     &rg);
 }
 extern "C" int afr_op_mse_grad(int act_dtype, const void* u, const void* target, int tdtype, void* du, int64_t rows,
                                int64_t cols, int64_t mean_elems, float* loss_accum, float* scratch, void* stream) {

@@ -342,25 +342,30 @@ static_assert(sizeof(RTableG) <= 4096, "the grouped reduce's table travels by va
 void afr_rtable_add(RTable& t, float* dst, const float* src, int nslabs, long long stride, long long n);
 // seg_ad (optional, t.adam only): t.nseg hypers, segment k is updated with seg_ad[k] instead of t.ad
 hipError_t afr_launch_reduce_group(const RTable& t, hipStream_t s, const AdamHyper* seg_ad = nullptr);
-// (lr and wd besides h: the kernel folds its decay = 1 - lr * wd on the device, as it always has; h.decay is not read)
+// The flat optimizer update (elementwise.hip adamw_kernel / opt_groups_kernel): AdamW or Lion over n elements (a multiple of 4) of p, g, m, v
+// (and the bf16 shadow, optional), one launch.
+// lr and wd besides h: the kernel folds its decay = 1 - lr * wd on the device, as it always has; h.decay is not read.
 // sumsq (device word, optional): clip by global gradient norm -- every lane derives coef = clip_coef(*sumsq, |grad_scale|, max_norm)
 // and the gradient enters the update as g * fl32(grad_scale * coef); a non-finite *sumsq leaves p/m/v/shadow untouched.
 // sumsq NULL: the unclipped kernel, bit for bit what it has always computed.
 // kind OPT_LION: the Lion update by the same kernel (v is not touched and may be NULL); the kernel folds decay = fl(1 - fl(lr * wd)),
 // uncontracted, which is what adam_hyper hands the other sites as h.decay.
-hipError_t afr_launch_adamw(float* p, const float* g, float* m, float* v, bf16_t* shadow, long long n, float lr, float wd,
-                            const AdamHyper& h, float grad_scale, hipStream_t s, const float* sumsq = nullptr, float max_norm = 0.f,
-                            int kind = OPT_ADAMW);
-// Optimizer groups (elementwise.hip opt_groups_kernel): the flat update of a slice whose tensors carry their own lr / weight decay.
-// Range k covers the quads (4 elements) [end4[k-1], end4[k]) of the FLAT buffer (end4[-1] = 0) and is updated with lr[k], wd[k] and
-// step[k] = the AdamHyper::step of (lr[k], t), all folded on the host; the kernel folds decay from lr[k], wd[k] as adamw_kernel does.
-// The table travels by value as a kernel argument.  The slice starts at flat element `first` (p, g, m, v, shadow point THERE) and
-// end4[n - 1] * 4 >= first + n elements.  h: b1, b2, eps and rsqrt_bc2 are read (global); sumsq / max_norm / kind as above.
+// tab (optional) -- optimizer groups: a slice whose tensors carry their own lr / weight decay, by the range-aware kernel.  Range k covers
+// the quads (4 elements) [end4[k-1], end4[k]) of the FLAT buffer (end4[-1] = 0) and is updated with lr[k], wd[k] and step[k] = the
+// AdamHyper::step of (lr[k], t), all folded on the host; the kernel folds decay from lr[k], wd[k] as the plain one does from lr, wd, which
+// it does not read, nor h.step.  The table travels by value as a kernel argument.  The slice starts at flat element `first` (p, g, m, v,
+// shadow point THERE) and end4[n - 1] * 4 >= first + n elements.
 constexpr int AFR_OPT_MAX_RANGES = 128;
 struct OptRangeTab { int n = 0; unsigned end4[AFR_OPT_MAX_RANGES]; float lr[AFR_OPT_MAX_RANGES], wd[AFR_OPT_MAX_RANGES], step[AFR_OPT_MAX_RANGES]; };
 static_assert(sizeof(OptRangeTab) <= 3072, "the range table travels by value as a kernel argument");
-hipError_t afr_launch_opt_groups(float* p, const float* g, float* m, float* v, bf16_t* shadow, long long n, long long first, const OptRangeTab& tab,
-                                 const AdamHyper& h, float grad_scale, hipStream_t s, const float* sumsq, float max_norm, int kind);
+struct FlatOpt {
+    float* p; const float* g; float* m; float* v; bf16_t* shadow;
+    long long n, first; const OptRangeTab* tab;
+    float lr, wd; AdamHyper h;
+    float grad_scale; const float* sumsq; float max_norm;
+    int kind;
+};
+hipError_t afr_launch_flat_opt(const FlatOpt& f, hipStream_t s);
 // Weight EMA (elementwise.hip ema_kernel): e = fma(p - e, fl(1 - decay), e) over n elements (a multiple of 4); sumsq as above: NULL,
 // or the device word whose non-finite value leaves e untouched.
 hipError_t afr_launch_ema(float* e, const float* p, long long n, float decay, const float* sumsq, hipStream_t s);

@@ -191,25 +191,34 @@ __device__ __forceinline__ float mul_rn(float a, float b) {
     return a * b;
 }
 __device__ __forceinline__ bool finite_f(float x) { return fabsf(x) <= 3.402823466e38f; }
-template <bool CLIP, int OPT = OPT_ADAMW>
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                    float* __restrict__ m, float* __restrict__ v,
-                                                    bf16_t* __restrict__ shadow, long long n4, float lr, float b1,
-                                                    float b2, float eps, float wd, float step_size, float rsqrt_bc2,
-                                                    float gscale, const float* __restrict__ sumsq, float max_norm) {
-    const AdamHyper h{OPT == OPT_LION ? 1.f - mul_rn(lr, wd) : 1.f - lr * wd, b1, b2, eps, step_size, rsqrt_bc2};
+// The pieces of the flat update, stated once for its two walks (adamw_kernel, opt_groups_kernel): what they share cannot drift apart.
+// The clip prologue: false = a non-finite *sumsq, the block returns and nothing is written.
+template <bool CLIP>
+__device__ __forceinline__ bool flat_clip(float& gscale, const float* __restrict__ sumsq, float max_norm) {
     if constexpr (CLIP) {
         const float ss = *sumsq;
-        if (!finite_f(ss)) return;
+        if (!finite_f(ss)) return false;
         float tn;
         gscale = mul_rn(gscale, clip_coef(ss, fabsf(gscale), max_norm, tn));
     }
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-        const float4 p4 = reinterpret_cast<float4*>(p)[i];
-        const float4 gg = reinterpret_cast<const float4*>(g)[i];
-        const float4 m4 = reinterpret_cast<float4*>(m)[i];
-        float4 v4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if constexpr (OPT == OPT_ADAMW) v4 = reinterpret_cast<float4*>(v)[i];
+    return true;
+}
+// the decay of one (lr, wd), per launch or per range
+template <int OPT> __device__ __forceinline__ float flat_decay(float lr, float wd) { return OPT == OPT_LION ? 1.f - mul_rn(lr, wd) : 1.f - lr * wd; }
+// one quad of p, g, m(, v) in flight: loaded, then updated with h and stored (v and the shadow where the kind / the caller has them)
+template <int OPT>
+struct FlatQuad {
+    float4 p4, gg, m4, v4;
+    __device__ __forceinline__ void load(const float* __restrict__ p, const float* __restrict__ g, const float* __restrict__ m, const float* __restrict__ v,
+                                         long long i) {
+        p4 = reinterpret_cast<const float4*>(p)[i];
+        gg = reinterpret_cast<const float4*>(g)[i];
+        m4 = reinterpret_cast<const float4*>(m)[i];
+        if constexpr (OPT == OPT_ADAMW) v4 = reinterpret_cast<const float4*>(v)[i];
+    }
+    template <bool CLIP>
+    __device__ __forceinline__ void step(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, bf16_t* __restrict__ shadow, long long i,
+                                         float gscale, const AdamHyper& h) const {
         f32x4 pp = {p4.x, p4.y, p4.z, p4.w}, mm = {m4.x, m4.y, m4.z, m4.w}, vv = {v4.x, v4.y, v4.z, v4.w};
         const f32x4 ge = (CLIP || OPT == OPT_LION) ? (f32x4){mul_rn(gg.x, gscale), mul_rn(gg.y, gscale), mul_rn(gg.z, gscale), mul_rn(gg.w, gscale)}
                                                    : (f32x4){gg.x * gscale, gg.y * gscale, gg.z * gscale, gg.w * gscale};
@@ -219,23 +228,27 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
         if constexpr (OPT == OPT_ADAMW) reinterpret_cast<float4*>(v)[i] = make_float4(vv[0], vv[1], vv[2], vv[3]);
         if (shadow) reinterpret_cast<bf16x4*>(shadow)[i] = o;
     }
-}
-hipError_t afr_launch_adamw(float* p, const float* g, float* m, float* v, bf16_t* shadow, long long n, float lr, float wd,
-                            const AdamHyper& h, float grad_scale, hipStream_t s, const float* sumsq, float max_norm, int kind) {
-    if (n <= 0) return hipSuccess;
-    if (n & 3) return hipErrorInvalidValue;   // flat buffers are padded to multiples of 64
-    with_bool(sumsq != nullptr, [&](auto clip) { with_opt(kind, [&](auto opt) {
-        hipLaunchKernelGGL((adamw_kernel<clip(), opt()>), dim3(grid_for(n / 4, 256, 4096)), dim3(256), 0, s, p, g, m, v, shadow, n / 4, lr,
-                           h.b1, h.b2, h.eps, wd, h.step, h.rsqrt_bc2, grad_scale, sumsq, max_norm);
-    }); });
-    return hipGetLastError();
+};
+template <bool CLIP, int OPT = OPT_ADAMW>
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                    float* __restrict__ m, float* __restrict__ v,
+                                                    bf16_t* __restrict__ shadow, long long n4, float lr, float b1,
+                                                    float b2, float eps, float wd, float step_size, float rsqrt_bc2,
+                                                    float gscale, const float* __restrict__ sumsq, float max_norm) {
+    const AdamHyper h{flat_decay<OPT>(lr, wd), b1, b2, eps, step_size, rsqrt_bc2};
+    if (!flat_clip<CLIP>(gscale, sumsq, max_norm)) return;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        FlatQuad<OPT> q{};
+        q.load(p, g, m, v, i);
+        q.template step<CLIP>(p, m, v, shadow, i, gscale, h);
+    }
 }
 
 // ----------------------------------------------------------------------------- optimizer groups
 // adamw_kernel's walk over a slice whose tensors carry their own (lr, wd): afr_set_param_groups / afr_op_opt_groups.  ONE launch for the
 // whole slice, the grid adamw_kernel would take.  The range table arrives by value; the block's first tab.n lanes fold each range's
-// decay exactly as adamw_kernel folds it from its scalars (so a range is updated bit for bit as adamw_kernel<CLIP, OPT> would update it
-// with that range's lr, wd) and park (end, decay, step) in LDS, ends relative to the slice.  A lane keeps a cursor into the table that
+// decay with the function adamw_kernel folds it with from its scalars (so a range is updated bit for bit as adamw_kernel<CLIP, OPT> would
+// update it with that range's lr, wd) and park (end, decay, step) in LDS, ends relative to the slice.  A lane keeps a cursor into the table that
 // only moves forward as its grid-stride index grows: at most tab.n LDS reads over the lane's whole life on top of two per quad, and no
 // extra global traffic -- the 16-byte accesses and the 28 (+2) / 20 (+2) bytes per element are adamw_kernel's.  Lanes of one wave may sit
 // in different ranges (tensor offsets are multiples of 64 elements, a wave covers 256).  No pow, no division: step is the host's.
@@ -246,30 +259,19 @@ __global__ __launch_bounds__(256) void opt_groups_kernel(float* __restrict__ p, 
                                                          const float* __restrict__ sumsq, float max_norm, OptRangeTab tab) {
     __shared__ unsigned s_end[AFR_OPT_MAX_RANGES];
     __shared__ float s_decay[AFR_OPT_MAX_RANGES], s_step[AFR_OPT_MAX_RANGES];
-    if constexpr (CLIP) {
-        const float ss = *sumsq;
-        if (!finite_f(ss)) return;
-        float tn;
-        gscale = mul_rn(gscale, clip_coef(ss, fabsf(gscale), max_norm, tn));
-    }
+    if (!flat_clip<CLIP>(gscale, sumsq, max_norm)) return;
     // the first trip's loads are issued AHEAD of the table staging, so that the block's start-up (table loads, LDS, barrier) hides
     // behind them instead of standing in front of its first byte in flight
     const long long stride = (long long)gridDim.x * 256;
     long long i = blockIdx.x * 256ll + threadIdx.x;
-    float4 p4 = make_float4(0.f, 0.f, 0.f, 0.f), gg = p4, m4 = p4, v4 = p4;
-    auto load = [&]() {
-        p4 = reinterpret_cast<float4*>(p)[i];
-        gg = reinterpret_cast<const float4*>(g)[i];
-        m4 = reinterpret_cast<float4*>(m)[i];
-        if constexpr (OPT == OPT_ADAMW) v4 = reinterpret_cast<float4*>(v)[i];
-    };
-    if (i < n4) load();
+    FlatQuad<OPT> q{};
+    if (i < n4) q.load(p, g, m, v, i);
     if ((int)threadIdx.x < tab.n) {
         const int k = threadIdx.x;
-        const float lr = tab.lr[k], wd = tab.wd[k];
+        const float lr = tab.lr[k], wd = tab.wd[k];      // (read ahead of end4: the other order costs a scalar instruction)
         const unsigned e = tab.end4[k];
         s_end[k] = e > first4 ? e - first4 : 0u;
-        s_decay[k] = OPT == OPT_LION ? 1.f - mul_rn(lr, wd) : 1.f - lr * wd;
+        s_decay[k] = flat_decay<OPT>(lr, wd);
         s_step[k] = tab.step[k];
     }
     __syncthreads();
@@ -277,28 +279,27 @@ __global__ __launch_bounds__(256) void opt_groups_kernel(float* __restrict__ p, 
     int cur = 0;
     while (i < n4) {
         while (cur < last && (unsigned long long)i >= s_end[cur]) ++cur;      // (the last range reaches the end of the slice)
-        const AdamHyper h{s_decay[cur], b1, b2, eps, s_step[cur], rsqrt_bc2};
-        f32x4 pp = {p4.x, p4.y, p4.z, p4.w}, mm = {m4.x, m4.y, m4.z, m4.w}, vv = {v4.x, v4.y, v4.z, v4.w};
-        const f32x4 ge = (CLIP || OPT == OPT_LION) ? (f32x4){mul_rn(gg.x, gscale), mul_rn(gg.y, gscale), mul_rn(gg.z, gscale), mul_rn(gg.w, gscale)}
-                                                   : (f32x4){gg.x * gscale, gg.y * gscale, gg.z * gscale, gg.w * gscale};
-        const bf16x4 o = opt_quad<OPT>(pp, mm, vv, ge, h);
-        reinterpret_cast<float4*>(p)[i] = make_float4(pp[0], pp[1], pp[2], pp[3]);
-        reinterpret_cast<float4*>(m)[i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
-        if constexpr (OPT == OPT_ADAMW) reinterpret_cast<float4*>(v)[i] = make_float4(vv[0], vv[1], vv[2], vv[3]);
-        if (shadow) reinterpret_cast<bf16x4*>(shadow)[i] = o;
+        q.template step<CLIP>(p, m, v, shadow, i, gscale, AdamHyper{s_decay[cur], b1, b2, eps, s_step[cur], rsqrt_bc2});
         i += stride;
-        if (i < n4) load();
+        if (i < n4) q.load(p, g, m, v, i);
     }
 }
-hipError_t afr_launch_opt_groups(float* p, const float* g, float* m, float* v, bf16_t* shadow, long long n, long long first, const OptRangeTab& tab,
-                                 const AdamHyper& h, float grad_scale, hipStream_t s, const float* sumsq, float max_norm, int kind) {
-    if (n <= 0) return hipSuccess;
+// f.tab == nullptr: adamw_kernel over the n elements with (f.lr, f.wd); else opt_groups_kernel with the table's ranges
+hipError_t afr_launch_flat_opt(const FlatOpt& f, hipStream_t s) {
+    if (f.n <= 0) return hipSuccess;
+    if (f.n & 3) return hipErrorInvalidValue;   // flat buffers are padded to multiples of 64
     // the table must cover the slice: a cursor that ran past it would hand the tail the last range's scalars silently
-    if ((n & 3) || (first & 3) || first < 0 || tab.n < 1 || tab.n > AFR_OPT_MAX_RANGES || (first + n) / 4 > (long long)tab.end4[tab.n - 1])
+    if (f.tab && ((f.first & 3) || f.first < 0 || f.tab->n < 1 || f.tab->n > AFR_OPT_MAX_RANGES || (f.first + f.n) / 4 > (long long)f.tab->end4[f.tab->n - 1]))
         return hipErrorInvalidValue;
-    with_bool(sumsq != nullptr, [&](auto clip) { with_opt(kind, [&](auto opt) {
-        hipLaunchKernelGGL((opt_groups_kernel<clip(), opt()>), dim3(grid_for(n / 4, 256, 4096)), dim3(256), 0, s, p, g, m, v, shadow, n / 4,
-                           (unsigned)(first / 4), h.b1, h.b2, h.eps, h.rsqrt_bc2, grad_scale, sumsq, max_norm, tab);
+    const long long n4 = f.n / 4;
+    const dim3 grid(grid_for(n4, 256, 4096));
+    with_bool(f.sumsq != nullptr, [&](auto clip) { with_opt(f.kind, [&](auto opt) {
+        if (f.tab)
+            hipLaunchKernelGGL((opt_groups_kernel<clip(), opt()>), grid, dim3(256), 0, s, f.p, f.g, f.m, f.v, f.shadow, n4, (unsigned)(f.first / 4), f.h.b1,
+                               f.h.b2, f.h.eps, f.h.rsqrt_bc2, f.grad_scale, f.sumsq, f.max_norm, *f.tab);
+        else
+            hipLaunchKernelGGL((adamw_kernel<clip(), opt()>), grid, dim3(256), 0, s, f.p, f.g, f.m, f.v, f.shadow, n4, f.lr, f.h.b1, f.h.b2, f.h.eps, f.wd,
+                               f.h.step, f.h.rsqrt_bc2, f.grad_scale, f.sumsq, f.max_norm);
     }); });
     return hipGetLastError();
 }

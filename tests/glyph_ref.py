@@ -27,29 +27,15 @@ import torch
 
 from ai_font_renderer_amd import synth
 
+from .util import bf16, ratio  # noqa: F401
+
 F64, F32, BF16 = torch.float64, torch.float32, torch.bfloat16
 U, UB = 2.0 ** -24, 2.0 ** -8
 L1_R, EMB_ROWS, GL1_ROWS, MAX_SPLIT = 64, 32, 8, 4      # glyphs per fused block, rows per embed_bwd block, fc1 rows per post-pass block
 
 
-def bf16(t):
-    """round to bfloat16, kept in the input's dtype"""
-    return t.to(F32).to(BF16).to(t.dtype)
-
-
 def bits(t):
     return t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
-
-
-def ratio(got, ref, bound):
-    """largest |got - ref| / bound; an element whose bound is 0 must be met exactly (inf otherwise)"""
-    err = (got.to(F64) - ref.to(F64)).abs()
-    if err.numel() == 0:
-        return 0.0
-    bound = bound.to(F64).expand_as(err)
-    r = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
-    r = torch.where(torch.isnan(err), torch.full_like(err, float("inf")), r)
-    return float(r.max())
 
 
 # ---------------------------------------------------------------------------------------------------------------- shapes

@@ -13,6 +13,8 @@ import torch
 
 from ai_font_renderer_amd import synth
 
+from .util import bf16, ratio  # noqa: F401
+
 U = 2.0 ** -24
 EPS = 1e-5                               # config.PixelConfig.ln_eps
 FWD_STRIDE = 8192 * 4                    # rows per trip of the forward kernels: pix_grid caps at 8192 blocks of 4 waves
@@ -33,11 +35,6 @@ def bwd_blocks(rows):
 
 def attn_chunk(tokens):
     return min(tokens, ATTN_CHUNK)
-
-
-def bf16(t):
-    """round to nearest even to bfloat16, returned in the input's dtype"""
-    return t.float().bfloat16().to(t.dtype)
 
 
 # ================================================================================================ restatements
@@ -331,14 +328,6 @@ def bound_attn_bwd(dO, q, kv, tokens, nsum):
 def bound_T(bound, ref, is_bf16):
     """an output stored in T: bf16 adds 2^-8 |ref| -- one rounding to nearest is 2^-9, the float32 error may carry it across a tie"""
     return bound + 2.0 ** -8 * ref.abs() if is_bf16 else bound
-
-
-def ratio(got, ref, bound):
-    """max over elements of |got - ref| / bound, a zero bound demanding equality; NaN / inf in got count as inf"""
-    err = torch.nan_to_num((got.double() - ref).abs(), nan=math.inf, posinf=math.inf)
-    bound = torch.broadcast_to(bound, err.shape)
-    r = torch.where(err == 0, torch.zeros_like(err), err / bound)          # 0 / 0 -> 0, x / 0 -> inf
-    return float(r.max()) if r.numel() else 0.0
 
 
 # ================================================================================================ inputs

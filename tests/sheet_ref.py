@@ -47,6 +47,8 @@ import torch
 
 from ai_font_renderer_amd import synth
 
+from .util import bf16, ratio  # noqa: F401
+
 U = 2.0 ** -24
 TINY = 2.0 ** -126
 E, H, D, F, QKV = 32, 4, 8, 64, 96
@@ -96,18 +98,6 @@ def pack_bits(keep):
     for j in range(L):
         out[..., (j & 1) * 2 + (j >> 6)] |= keep[..., j].to(torch.int64) << ((j >> 1) & 31)
     return out
-
-
-def bf16(t):
-    return t.float().bfloat16().to(t.dtype)
-
-
-def ratio(got, ref, bound):
-    """max over elements of |got - ref| / bound, a zero bound demanding equality; NaN / inf in got count as inf"""
-    err = torch.nan_to_num((got.double() - ref).abs(), nan=math.inf, posinf=math.inf)
-    bound = torch.broadcast_to(bound, err.shape)
-    r = torch.where(err == 0, torch.zeros_like(err), err / bound)
-    return float(r.max()) if r.numel() else 0.0
 
 
 # ================================================================================================ restatements

@@ -6,6 +6,7 @@ References: tests/bce_ref.py (the explicit formula, equal to F.binary_cross_entr
 oracle, and tests/golden/sheet_mini_bce.npz (the reference's own module graph with that loss; make_golden_bce.py).
 Tolerances are the project's: f32 / bf16x3 bitmaps 2e-5 max-abs, gradients 1e-4 relative, losses 1e-5
 relative; bf16 3e-2 relative against the oracle rounded at the engine's points (util.engine_rounding, u and du in bf16)."""
+import functools
 import os
 from dataclasses import replace
 
@@ -15,16 +16,14 @@ import torch
 import torch.nn.functional as F
 
 from . import bce_ref
+from . import opt_paths as OP
+from .opt_paths import no_error_bits_left_behind  # noqa: F401
 from .util import MINI, GlyphConfig, engine_rounding, fused1_eligible, glyph_inputs, load, maxabs, oracle, rnd_du, synth, tparams
 
 pytestmark = pytest.mark.gpu
 
 
-def _engine(cfg, dtype="f32", max_batch=64, **kw):
-    from ai_font_renderer_amd.engine import Engine
-    eng = Engine(cfg, dtype=dtype, max_batch=max_batch, loss="bce", **kw)
-    eng.load_params(synth.make_params(cfg))
-    return eng
+_engine = functools.partial(OP.engine, loss="bce")
 
 
 def _rel(got, ref):
@@ -423,15 +422,9 @@ def test_data_parallel_stepper_on_bce_engines_over_rccl_world1(schedule, monkeyp
     model in f32 equals the single-GPU BCE step of the same arithmetic exactly (as test_data_parallel_stepper_over_rccl_world1
     holds the MSE step); and
     a shard that carries mean_elems of a four times larger global batch scales loss and gradients by exactly 1/4."""
-    import torch.distributed as dist
-    from ai_font_renderer_amd import parallel
     from ai_font_renderer_amd.config import WORKLOADS
     from ai_font_renderer_amd.parallel import DataParallelStepper
-    monkeypatch.setattr(parallel, "OVERLAP_MIN_BYTES", 0 if schedule == "overlapped" else 1 << 40)
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ.setdefault("MASTER_PORT", str(29600 + os.getpid() % 300))
-    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-    try:
+    with OP.rccl_world_one(schedule, monkeypatch) as dist:
         c3 = WORKLOADS["c3"]["cfg"]
         xg, fg, tg = glyph_inputs(c3, 1024)
         cases = [(c3, "bf16", 1024, torch.from_numpy(xg).cuda(), torch.from_numpy(fg).cuda(), torch.from_numpy(tg).cuda()),
@@ -474,8 +467,6 @@ def test_data_parallel_stepper_on_bce_engines_over_rccl_world1(schedule, monkeyp
                 b.train_step(x, t, font=font, step=5, mean_elems=4 * me, do_step=False)
                 assert a.read_loss() == 4.0 * b.read_loss()
                 assert torch.equal(a.flat_grads, 4.0 * b.flat_grads)
-    finally:
-        dist.destroy_process_group()
 
 
 # ----------------------------------------------------------------------------- the training CLI and a real target

@@ -5,62 +5,25 @@ optimizer -- the one-call step, step by rows, gradient accumulation, the three d
 Adam's update m / sqrt(v) is almost invariant to a scale of the gradient, so every trajectory check here asserts exp_avg and
 exp_avg_sq (which carry coef and coef^2), not only the parameters: the parameters alone would pass without the feature."""
 import functools
-import os
-from dataclasses import replace
 
 import numpy as np
 import pytest
 import torch
 
-from . import clip_ref
-from .util import MINI, GlyphConfig, glyph_inputs, load, maxabs, synth, tparams
+from . import clip_ref, lion_ref
+from . import opt_paths as OP
+from .opt_paths import UNFUSED, assert_same_state, no_error_bits_left_behind  # noqa: F401
+from .opt_paths import engine as _engine
+from .opt_paths import state as _state
+from .util import MINI, glyph_inputs, load, maxabs, tparams
 
 pytestmark = pytest.mark.gpu
 
-UNFUSED = 1                                    # AFR_CFG_UNFUSED_OPTIMIZER
-NODROP = replace(MINI, p_embed=0.0, p_attn=0.0, p_fc=0.0)
-SMALL = GlyphConfig(hidden=(48, 40), out_h=4, out_w=6, n_fonts=2)       # the glyph twin's small net
-
-
-def _engine(cfg, dtype="f32", max_batch=64, **kw):
-    from ai_font_renderer_amd.engine import Engine
-    eng = Engine(cfg, dtype=dtype, max_batch=max_batch, **kw)
-    eng.load_params(synth.make_params(cfg))
-    return eng
-
-
-def _state(eng):
-    """(params, exp_avg, exp_avg_sq) as name -> tensor over the tensor elements (the padding between tensors is nobody's)."""
-    out = ({}, {}, {})
-    for nm, shp, o, k in eng.layout:
-        for d, flat in zip(out, (eng.flat_params, eng.exp_avg, eng.exp_avg_sq)):
-            d[nm] = flat[o:o + k].clone()
-    return out
-
-
-def _assert_same_state(a, b, what):
-    for da, db, tag in zip(_state(a), _state(b), ("param", "exp_avg", "exp_avg_sq")):
-        for k in da:
-            assert torch.equal(da[k], db[k]), (what, tag, k, float((da[k] - db[k]).abs().max()))
-
-
-def _c5_case():
-    from ai_font_renderer_amd.config import C5_MINI
-    fx = load("pixel_twin.npz")
-    return C5_MINI, torch.from_numpy(fx["x"]), torch.from_numpy(fx["font"]), torch.from_numpy(fx["target_u8"]), float(fx["lr"])
-
 
 def _case(name):
-    """(cfg, x, font, target u8, lr) of a fixture's inputs."""
-    from ai_font_renderer_amd.config import WORKLOADS
-    if name == "c5-mini":
-        return _c5_case()
-    if name == "sheet-mini":
-        fx = load("sheet_mini.npz")
-        return NODROP, torch.from_numpy(fx["x10"]), None, torch.from_numpy(fx["target_u8"]), 1e-3
-    cfg, B = (SMALL, 300) if name == "glyph-small" else (WORKLOADS["c1"]["cfg"], 95)
-    x, font, t = glyph_inputs(cfg, B)
-    return cfg, torch.from_numpy(x), torch.from_numpy(font) if cfg.n_fonts else None, torch.from_numpy(t), 1e-3
+    """(cfg, x, font, target u8, lr) of a fixture's inputs: lion_ref.case's, with the fixture's own learning rate."""
+    lr = float(load("pixel_twin.npz")["lr"]) if name == "c5-mini" else 1e-3
+    return (*lion_ref.case("glyph-c1" if name == "c1" else name), lr)
 
 
 # ----------------------------------------------------------------------------- 1. the norm kernel
@@ -165,9 +128,8 @@ def test_inactive_clip_equals_the_unfused_optimizer_step_bitwise(model, dtype):
         clip.train_step(x, t, font=font, lr=lr)
         assert clip.clip_coef() == 1.0, i
         assert ref.read_loss() == clip.read_loss(), i
-    _assert_same_state(clip, ref, model)
+    assert_same_state(clip, ref, model)
     assert abs(clip.grad_norm() - float(clip.grad_sumsq().sqrt())) <= 1e-6 * clip.grad_norm()
-    assert clip.error_flags() == 0 and ref.error_flags() == 0
 
 
 # ----------------------------------------------------------------------------- 3. a clip that bites, against the oracle
@@ -228,7 +190,6 @@ def test_active_clip_three_steps_vs_the_clipped_oracle(name, dtype):
         assert maxabs(got[0], ref[0]) <= pbar, (k, maxabs(got[0], ref[0]))
         assert maxabs(got[1], ref[1]) <= gbar * max(float(np.abs(ref[1]).max()), 1e-30), ("exp_avg", k)
         assert maxabs(got[2], ref[2]) <= 2 * gbar * max(float(np.abs(ref[2]).max()), 1e-30), ("exp_avg_sq", k)
-    assert eng.error_flags() == 0
 
 
 # ----------------------------------------------------------------------------- 4. entry points agree
@@ -239,19 +200,14 @@ def test_one_call_step_equals_backward_plus_adamw_step_and_the_step_by_rows(name
         cfg = MINI                                                         # with its dropouts: the step index keys the masks
     B = x.shape[0]
     max_norm = _clipped_reference(name)[0]                                # 0.25 x the step-1 norm: the clip bites
-    a, b, c = (_engine(cfg, dtype, B, max_grad_norm=max_norm) for _ in range(3))
-    c.bind_dataset(x, t, font=font)
-    rows = torch.arange(B)
-    for i in range(2):
-        a.train_step(x, t, font=font, step=i + 1)
-        b.train_step(x, t, font=font, step=i + 1, do_step=False)
-        b.adamw_step()
-        c.train_step_rows(rows, step=i + 1)
-        assert a.read_loss() == b.read_loss() == c.read_loss()
-        assert a.clip_coef() == b.clip_coef() == c.clip_coef() < 1.0
-    _assert_same_state(a, b, "train_step(do_step=0) + adamw_step")
-    _assert_same_state(a, c, "train_step_rows")
-    assert a.t == b.t == c.t == 2
+    quartet = OP.forms(cfg, dtype, B, x, t, font, max_grad_norm=max_norm)
+    a, u, b, c = quartet                                                  # (every form of a clipping plan ends in the CLIP kernel)
+    for _ in OP.steps_of(quartet, x, t, font, {}, steps=2):
+        assert a.clip_coef() == u.clip_coef() == b.clip_coef() == c.clip_coef() < 1.0
+    assert_same_state(a, u, "AFR_CFG_UNFUSED_OPTIMIZER")
+    assert_same_state(a, b, "train_step(do_step=0) + adamw_step")
+    assert_same_state(a, c, "train_step_rows")
+    assert a.t == 2
 
 
 # ----------------------------------------------------------------------------- 5. grad_scale
@@ -282,7 +238,7 @@ def test_grad_scale_enters_the_norm_and_the_update():
     c.flat_grads.mul_(-1.0)
     c.adamw_step(grad_scale=-1.0)
     assert c.grad_norm() == a.grad_norm() and c.clip_coef() == a.clip_coef()
-    _assert_same_state(c, a, "grad_scale = -1 on negated gradients")
+    assert_same_state(c, a, "grad_scale = -1 on negated gradients")
 
 
 # ----------------------------------------------------------------------------- 6. non-finite gradients skip the step
@@ -318,18 +274,13 @@ def test_clipped_step_over_micro_batches_equals_the_one_pass_clipped_step():
     bound: gradients within 2e-5 of each tensor's largest entry).  The norm of a vector moves by at most the norm of its
     change, |norm_acc - norm_whole| <= sqrt(sum_k n_k (2e-5 max|g_k|)^2); the coefficient by that relative amount; exp_avg by
     the gradient's bound plus the coefficient's; two further steps at lr = 1e-5 keep the losses within 1e-5 (as there)."""
-    from ai_font_renderer_amd.config import C5_MINI as cfg
-    B = 27
-    rng = np.random.default_rng(9)
-    x = torch.from_numpy((32 + (np.arange(B) * 11) % 95).astype(np.int64))
-    font = torch.from_numpy((np.arange(B) % 2).astype(np.int64))
-    tgt = torch.from_numpy(rng.integers(0, 256, (B, cfg.out_h, cfg.out_w), dtype=np.uint8))
+    cfg, B, x, font, tgt = OP.inputs(OP.ACC_CASE)
     probe = _engine(cfg, "f32", B)
     probe.train_step(x, tgt, font=font, do_step=False)
     norm1 = float(probe.grad_sumsq().sqrt())
     slack = float(np.sqrt(sum(k * (2e-5 * float(probe.flat_grads[o:o + k].abs().max())) ** 2 for _, _, o, k in probe.layout)))
     whole = _engine(cfg, "f32", B, max_grad_norm=0.25 * norm1)
-    acc = _engine(cfg, "f32", B, max_grad_norm=0.25 * norm1, micro_batch=8)
+    acc = _engine(cfg, "f32", B, max_grad_norm=0.25 * norm1, micro_batch=OP.ACC_MICRO_BATCH)
     assert acc.max_batch == 8
     for e in (whole, acc):
         e.train_step(x, tgt, font=font, lr=1e-5)
@@ -354,33 +305,12 @@ def test_data_parallel_schedules_equal_the_single_gpu_clipped_step_bitwise(sched
     """A glyph net and the sheet MINI model (dropout on), f32 and bf16, through the multi-rank code path at a world of one:
     every schedule ends in the same norm kernel and the same clipped update as the single-GPU step (sharded: the shard's range
     is the whole buffer, its walk is identical; its sum goes through all_reduce and afr_op_adamw_clip)."""
-    import torch.distributed as dist
-    from ai_font_renderer_amd import parallel
-    from ai_font_renderer_amd.parallel import DataParallelStepper
-    monkeypatch.setattr(parallel, "OVERLAP_MIN_BYTES", 0 if schedule == "overlapped" else 1 << 40)
-    if schedule == "shard-force":
-        monkeypatch.setenv("AFR_DP_SCHEDULE", "shard-force")
-    else:
-        monkeypatch.delenv("AFR_DP_SCHEDULE", raising=False)
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ.setdefault("MASTER_PORT", str(29600 + os.getpid() % 300))
-    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-    try:
-        xg, fg, tg = glyph_inputs(SMALL, 300)
-        glyph = (SMALL, 300, torch.from_numpy(xg).cuda(), torch.from_numpy(fg).cuda(), torch.from_numpy(tg).cuda())
-        sheet = (MINI, 37, torch.from_numpy(synth.encode_strings(synth.dataset_strings(37), MINI.max_length)).cuda(), None,
-                 torch.from_numpy(synth.synth_sheet_targets(37, MINI.sheet_h, MINI.sheet_w, tensor_id=931)).cuda())
-        for (cfg, B, x, font, t) in (glyph, sheet):
+    with OP.rccl_world_one(schedule, monkeypatch) as dist:
+        for (cfg, B, x, font, t) in (OP.inputs(c, "cuda") for c in OP.DP_CASES):
             for dtype in ("f32", "bf16"):
-                probe = _engine(cfg, dtype, B)
-                probe.train_step(x, t, font=font, step=1, do_step=False)
-                max_norm = 0.25 * float(probe.grad_sumsq().sqrt())
+                max_norm = 0.25 * OP.norm1(cfg, dtype, x, t, font, step=1)
                 me = B * cfg.pixels
-                eng = _engine(cfg, dtype, B, max_grad_norm=max_norm)
-                st = DataParallelStepper(eng, dist, world=1 if schedule == "shard-force" else 2)
-                assert st.sharded() == (schedule == "shard-force")
-                one = _engine(cfg, dtype, B, max_grad_norm=max_norm)
-                st1 = DataParallelStepper(one, None, 1)
+                eng, st, one, st1 = OP.dp_steppers(dist, schedule, lambda: _engine(cfg, dtype, B, max_grad_norm=max_norm))
                 for i in range(3):
                     st.step(x, t, font, mean_elems=me, step=i + 1)
                     st1.step(x, t, font, mean_elems=me, step=i + 1)
@@ -388,11 +318,8 @@ def test_data_parallel_schedules_equal_the_single_gpu_clipped_step_bitwise(sched
                     if schedule != "shard-force":                            # (the sharded update has no plan to leave statistics with)
                         assert eng.clip_coef() == one.clip_coef() and eng.grad_norm() == one.grad_norm()
                 assert st.global_loss() == st1.global_loss(), (cfg.kind, dtype)
-                _assert_same_state(eng, one, (schedule, cfg.kind, dtype))
+                assert_same_state(eng, one, (schedule, cfg.kind, dtype), shadows=False)
                 assert torch.equal(eng.forward(x, font), one.forward(x, font))   # (bf16: the shadow was re-synced)
-                assert eng.error_flags() == 0
-    finally:
-        dist.destroy_process_group()
 
 
 # ----------------------------------------------------------------------------- the Python surface
@@ -416,7 +343,7 @@ def test_engine_surface_replanning_and_the_facade(monkeypatch):
     eng2.set_grad_clip(0)
     eng2.train_step(x, t, font=font)
     eng2.train_step(x, t, font=font)
-    _assert_same_state(eng2, off, "clipping switched off")
+    assert_same_state(eng2, off, "clipping switched off")
     monkeypatch.setattr(M, "SHEET_HEIGHT", 8)
     monkeypatch.setattr(M, "SHEET_WIDTH", 24)
     monkeypatch.setattr(M, "CLIP_NORM", 0.75)                              # what AFR_CLIP_NORM=0.75 sets at import

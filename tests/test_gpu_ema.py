@@ -12,69 +12,23 @@ import pytest
 import torch
 
 from . import ema_ref, lion_ref
+from . import opt_paths as OP
 from .gpu_util import ptr, stream
-from .util import MINI, glyph_inputs, load, synth
+from .opt_paths import assert_same_state, no_error_bits_left_behind  # noqa: F401
+from .opt_paths import engine as _engine
+from .opt_paths import same as _same
+from .util import MINI, load, synth
 
 pytestmark = pytest.mark.gpu
 
-UNFUSED = 1                                    # AFR_CFG_UNFUSED_OPTIMIZER
 HYPER = {"adamw": dict(lr=1e-3), "lion": dict(lr=lion_ref.LR, betas=(lion_ref.B1, lion_ref.B2), weight_decay=lion_ref.WD)}
 CASE_DTYPES = [(n, d) for n in lion_ref.CASES for d in ("f32", "bf16")]
-
-
-def _engine(cfg, dtype="f32", max_batch=64, optimizer="adamw", **kw):
-    from ai_font_renderer_amd.engine import Engine
-    eng = Engine(cfg, dtype=dtype, max_batch=max_batch, optimizer=optimizer, **kw)
-    eng.load_params(synth.make_params(cfg))
-    return eng
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t.contiguous().view(torch.int16)
-
-
-def _same(a, b):
-    return torch.equal(_bits(a), _bits(b))
 
 
 def _op_ema(e, p, decay, sumsq=None, n=None):
     from ai_font_renderer_amd import _lib
     _lib.check(_lib.lib().afr_op_ema(ptr(e), ptr(p), p.numel() if n is None else n, decay, ptr(sumsq), stream()))
     torch.cuda.synchronize()
-
-
-def _elements(eng, flat):
-    """name -> the tensor elements of a flat buffer (the padding between tensors is nobody's)."""
-    return {nm: flat[o:o + k] for nm, _, o, k in eng.layout}
-
-
-def _shadows(eng):
-    """The bf16 weight shadow(s) that lead the workspace of a bf16 plan (a glyph plan keeps two), over the tensor elements."""
-    if eng.dtype != "bf16":
-        return []
-    n2 = eng.n_flat * 2
-    bufs = [eng.workspace[:n2].view(torch.bfloat16)]
-    if eng.cfg.kind == "glyph":
-        o2 = (n2 + 255) // 256 * 256
-        bufs.append(eng.workspace[o2:o2 + n2].view(torch.bfloat16))
-    return [torch.cat([b[o:o + k] for _, _, o, k in eng.layout]) for b in bufs]
-
-
-def _assert_same_state(a, b, what, ema=True, shadow=True):
-    """Parameters, moments, (EMA,) (bf16 shadows) of two engines over the tensor elements, bit for bit; and the step counter."""
-    bufs = [("param", a.flat_params, b.flat_params), ("exp_avg", a.exp_avg, b.exp_avg)]
-    if a.exp_avg_sq is not None:
-        bufs.append(("exp_avg_sq", a.exp_avg_sq, b.exp_avg_sq))
-    if ema:
-        bufs.append(("ema", a.flat_ema, b.flat_ema))
-    for tag, fa, fb in bufs:
-        ea, eb = _elements(a, fa), _elements(b, fb)
-        for k in ea:
-            assert _same(ea[k], eb[k]), (what, tag, k, float((ea[k] - eb[k]).abs().max()))
-    if shadow:
-        for i, (sa, sb) in enumerate(zip(_shadows(a), _shadows(b))):
-            assert _same(sa, sb), (what, "shadow", i)
-    assert a.t == b.t, (what, a.t, b.t)
 
 
 # ----------------------------------------------------------------------------- 1. the kernel against fp64, every element
@@ -126,7 +80,7 @@ def test_hook_fires_once_per_due_step_after_the_update_and_changes_nothing_else(
     and the loss of both equal the engine without an EMA throughout."""
     cfg, x, font, t = lion_ref.case(name)
     B, decay, hyper = x.shape[0], 0.9, HYPER[optimizer]
-    e1, e3, off = (_engine(cfg, dtype, B, optimizer, **kw) for kw in (dict(ema_decay=decay), dict(ema_decay=decay, ema_every=3), {}))
+    e1, e3, off = (_engine(cfg, dtype, B, optimizer=optimizer, **kw) for kw in (dict(ema_decay=decay), dict(ema_decay=decay, ema_every=3), {}))
     assert _same(e1.flat_ema, e1.flat_params) and off.flat_ema is None and e3.ema_every == 3
     mine1, mine3 = e1.flat_ema.clone(), e3.flat_ema.clone()
     for i in range(1, 8):
@@ -141,17 +95,13 @@ def test_hook_fires_once_per_due_step_after_the_update_and_changes_nothing_else(
             assert not _same(mine3, before)
         assert _same(e3.flat_ema, mine3), i
         for e in (e1, e3):
-            _assert_same_state(e, off, (i, "against the engine without an EMA"), ema=False)
+            assert_same_state(e, off, (i, "against the engine without an EMA"), ema=False)
     assert not _same(e1.flat_ema, e1.flat_params) and not _same(e1.flat_ema, e3.flat_ema)
-    for e in (e1, e3, off):
-        assert e.error_flags() == 0
 
 
 # ----------------------------------------------------------------------------- 4. every path ends in the same EMA
 def _norm1(cfg, dtype, x, t, font, optimizer):
-    probe = _engine(cfg, dtype, x.shape[0], optimizer)
-    probe.train_step(x, t, font=font, step=1, do_step=False)
-    return float(probe.grad_sumsq().sqrt())
+    return OP.norm1(cfg, dtype, x, t, font, step=1, optimizer=optimizer)
 
 
 def _paths_agree_bitwise(name, optimizer, clip):
@@ -177,30 +127,22 @@ def test_every_path_ends_in_the_same_ema(name, dtype, optimizer, clip):
     kw = dict(ema_decay=decay)
     if clip:
         kw["max_grad_norm"] = 0.25 * _norm1(cfg, dtype, x, t, font, optimizer)
-    fused, unfused, split, rows = (_engine(cfg, dtype, B, optimizer, flags=fl, **kw) for fl in (0, UNFUSED, 0, 0))
-    rows.bind_dataset(x, t, font=font)
-    idx = torch.arange(B)
-    engines = (fused, unfused, split, rows)
+    agree = _paths_agree_bitwise(name, optimizer, clip)
+    engines = OP.forms(cfg, dtype, B, x, t, font, optimizer=optimizer, **kw)
+    fused, unfused, split, rows = engines
     mine = [e.flat_ema.clone() for e in engines]
-    for i in range(3):
-        fused.train_step(x, t, font=font, step=i + 1, **hyper)
-        unfused.train_step(x, t, font=font, step=i + 1, **hyper)
-        split.train_step(x, t, font=font, step=i + 1, do_step=False)
-        split.adamw_step(**hyper)
-        rows.train_step_rows(idx, step=i + 1, **hyper)
+    for i in OP.steps_of(engines, x, t, font, hyper, same_loss=agree):
         for e, m in zip(engines, mine):
             _op_ema(m, e.flat_params, decay)
             assert _same(e.flat_ema, m), i
         if clip and i == 0:
             assert fused.clip_coef() < 0.26                               # the clip bites (later norms may have fallen below it)
-    if _paths_agree_bitwise(name, optimizer, clip):
+    if agree:
         pairs = ((fused, unfused, "AFR_CFG_UNFUSED_OPTIMIZER"), (fused, split, "train_step(do_step=0) + adamw_step"), (fused, rows, "train_step_rows"))
     else:
         pairs = ((fused, rows, "train_step_rows"), (unfused, split, "train_step(do_step=0) + adamw_step against AFR_CFG_UNFUSED_OPTIMIZER"))
     for one, other, what in pairs:
-        _assert_same_state(one, other, what, shadow=False)
-    for e in engines:
-        assert e.error_flags() == 0
+        assert_same_state(one, other, what, shadows=False)
 
 
 @pytest.mark.parametrize("clip", [False, True])
@@ -223,18 +165,17 @@ def test_micro_batch_accumulation_ends_in_the_same_ema(clip):
         whole.adamw_step()
         _op_ema(mine, acc.flat_params, decay)
         assert _same(acc.flat_ema, mine), i
-    _assert_same_state(acc, whole, "micro-batch accumulation")
-    assert acc.t == 3 and acc.error_flags() == 0
+    assert_same_state(acc, whole, "micro-batch accumulation")
+    assert acc.t == 3
 
 
 def test_cooperative_split_k_tail_ends_in_the_same_ema():
-    """C3's own layers at 8192 rows in bf16, the smallest shape that takes the cooperative split-K tail (test_gpu_lion says why): the
+    """C3's own layers at 8192 rows in bf16, the smallest shape that takes the cooperative split-K tail (opt_paths.COOP_CASE says why): the
     tail applies the optimizer inside the weight-gradient launch, the EMA pass follows the step's grouped reduce.  One-call step against
     AFR_CFG_UNFUSED_OPTIMIZER, two Lion steps with every = 2: unchanged after the first, the replay after the second, states bit-equal."""
-    from ai_font_renderer_amd.config import WORKLOADS
-    cfg, B, decay = WORKLOADS["c3"]["cfg"], 8192, 0.9
-    x, font, t = (torch.from_numpy(a) for a in glyph_inputs(cfg, B))
-    a, b = (_engine(cfg, "bf16", B, "lion", flags=fl, ema_decay=decay, ema_every=2) for fl in (0, UNFUSED))
+    decay = 0.9
+    cfg, B, x, font, t = OP.coop_inputs()
+    a, b = (_engine(cfg, "bf16", B, optimizer="lion", flags=fl, ema_decay=decay, ema_every=2) for fl in (0, OP.UNFUSED))
     a.profile(1)
     start = a.flat_ema.clone()
     for e in (a, b):
@@ -243,15 +184,14 @@ def test_cooperative_split_k_tail_ends_in_the_same_ema():
     for e in (a, b):
         e.train_step(x, t, font=font, **HYPER["lion"])
     table = a.profile_table()
-    assert any(r["kernel"].startswith("gemm_bf16_group256[") for r in table)
+    assert OP.ran_coop_tail(a)
     ema = [r for r in table if r["kernel"] == "ema"]
     assert len(ema) == 1 and ema[0]["launches"] == 1                       # one launch in two steps; 12 B per element (the table prints 6 digits)
     assert abs(ema[0]["algo_bytes"] - 12.0 * a.n_flat) <= 1e-5 * 12.0 * a.n_flat
     _op_ema(start, a.flat_params, decay)
     assert _same(a.flat_ema, start)
-    _assert_same_state(a, b, "cooperative tail", shadow=False)             # (the un-fused step updates its shadow in place, the fused one swaps two)
+    assert_same_state(a, b, "cooperative tail", shadows=False)             # (the un-fused step updates its shadow in place, the fused one swaps two)
     assert _same(a.forward(x[:256], font[:256]), b.forward(x[:256], font[:256]))
-    assert a.error_flags() == 0 and b.error_flags() == 0
 
 
 # ----------------------------------------------------------------------------- 5. data-parallel schedules over world-1 RCCL
@@ -261,46 +201,24 @@ def test_data_parallel_schedules_end_in_the_single_gpu_ema(schedule, clip, monke
     """test_gpu_lion's data-parallel case with an EMA: a glyph net and the sheet MINI model (dropout on), f32 and bf16, Lion (whose
     schedules all equal the single-GPU step bit for bit), and AdamW where clipping makes them (every step then ends in the one
     elementwise kernel).  After three steps flat_ema and the whole state equal the single-GPU engine's."""
-    import torch.distributed as dist
-    from ai_font_renderer_amd import parallel
-    from ai_font_renderer_amd.parallel import DataParallelStepper
-    monkeypatch.setattr(parallel, "OVERLAP_MIN_BYTES", 0 if schedule == "overlapped" else 1 << 40)
-    if schedule == "shard-force":
-        monkeypatch.setenv("AFR_DP_SCHEDULE", "shard-force")
-    else:
-        monkeypatch.delenv("AFR_DP_SCHEDULE", raising=False)
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ.setdefault("MASTER_PORT", str(29600 + os.getpid() % 300))
-    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-    try:
-        xg, fg, tg = glyph_inputs(lion_ref.SMALL, 300)
-        glyph = (lion_ref.SMALL, 300, torch.from_numpy(xg).cuda(), torch.from_numpy(fg).cuda(), torch.from_numpy(tg).cuda())
-        sheet = (MINI, 37, torch.from_numpy(synth.encode_strings(synth.dataset_strings(37), MINI.max_length)).cuda(), None,
-                 torch.from_numpy(synth.synth_sheet_targets(37, MINI.sheet_h, MINI.sheet_w, tensor_id=931)).cuda())
+    with OP.rccl_world_one(schedule, monkeypatch) as dist:
         for optimizer in ("lion", "adamw") if clip else ("lion",):
-            for (cfg, B, x, font, t) in (glyph, sheet):
+            for (cfg, B, x, font, t) in (OP.inputs(c, "cuda") for c in OP.DP_CASES):
                 for dtype in ("f32", "bf16"):
                     kw = dict(ema_decay=0.9)
                     if clip:
                         kw["max_grad_norm"] = 0.25 * _norm1(cfg, dtype, x, t, font, optimizer)
                     me = B * cfg.pixels
-                    eng = _engine(cfg, dtype, B, optimizer, **kw)
-                    st = DataParallelStepper(eng, dist, world=1 if schedule == "shard-force" else 2)
-                    assert st.sharded() == (schedule == "shard-force")
-                    one = _engine(cfg, dtype, B, optimizer, **kw)
-                    st1 = DataParallelStepper(one, None, 1)
+                    eng, st, one, st1 = OP.dp_steppers(dist, schedule, lambda: _engine(cfg, dtype, B, optimizer=optimizer, **kw))
                     for i in range(3):
                         st.step(x, t, font, mean_elems=me, step=i + 1, **HYPER[optimizer])
                         st1.step(x, t, font, mean_elems=me, step=i + 1, **HYPER[optimizer])
                     assert st.global_loss() == st1.global_loss(), (cfg.kind, dtype)
-                    _assert_same_state(eng, one, (schedule, optimizer, cfg.kind, dtype), shadow=False)
+                    assert_same_state(eng, one, (schedule, optimizer, cfg.kind, dtype), shadows=False)
                     assert not _same(eng.flat_ema, eng.flat_params)
                     with eng.ema_weights(), one.ema_weights():
                         assert _same(eng.forward(x, font), one.forward(x, font))
                     assert _same(eng.forward(x, font), one.forward(x, font))       # (bf16: the shadow was re-synced)
-                    assert eng.error_flags() == 0 and one.error_flags() == 0
-    finally:
-        dist.destroy_process_group()
 
 
 # ----------------------------------------------------------------------------- 6. a skipped step
@@ -405,9 +323,7 @@ def test_evaluation_from_the_ema(name, dtype):
         for i in range(3, 6):
             e.train_step(x, t, font=font, step=i + 1)
     assert eng.read_loss() == twin.read_loss()
-    _assert_same_state(eng, twin, "after the context")
-    for e in (eng, twin, other):
-        assert e.error_flags() == 0
+    assert_same_state(eng, twin, "after the context")
 
 
 def test_replan_inside_and_outside_the_context_keeps_the_ema():
@@ -425,7 +341,7 @@ def test_replan_inside_and_outside_the_context_keeps_the_ema():
     for e in (a, b):
         e.train_step(x, t, font=font)
     assert a.flat_ema.data_ptr() == buf
-    _assert_same_state(a, b, "after the re-plan", shadow=False)            # (a's new plan starts with its first shadow current, b's has swapped)
+    assert_same_state(a, b, "after the re-plan", shadows=False)            # (a's new plan starts with its first shadow current, b's has swapped)
     c = _engine(cfg, "f32", 64, ema_decay=0.5)
     mine = c.flat_ema.clone()
     c.train_step(x, t, font=font)                                         # the re-plan happens inside the training step
@@ -569,7 +485,7 @@ def test_thirty_lion_steps_stay_within_the_bound_of_the_fp64_replay():
     30 x 2^-22 x max|p| per tensor (max over the recorded parameters and the start)."""
     cfg, x, font, t = lion_ref.case("glyph-small")
     decay = 0.99
-    eng = _engine(cfg, "f32", x.shape[0], "lion", ema_decay=decay)
+    eng = _engine(cfg, "f32", x.shape[0], optimizer="lion", ema_decay=decay)
     ref = eng.flat_ema.cpu().double()
     top = eng.flat_params.abs().cpu().double()
     for _ in range(30):

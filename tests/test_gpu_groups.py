@@ -7,89 +7,28 @@ one step against torch's param groups (tests/groups_ref.py); and the surface.
 Gradients do not depend on the optimizer's scalars, so from the same state and batch a grouped engine and an ungrouped one see the
 same gradients to the last bit: the bitwise tests need no tolerance."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
 
 from . import clip_ref, groups_ref, lion_ref
+from . import opt_paths as OP
 from .groups_ref import B1, B2, EPS, LR, WD, f32_mul
 from .gpu_util import ptr, stream
-from .util import MINI, glyph_inputs, synth
+from .opt_paths import UNFUSED, assert_same_state, no_error_bits_left_behind  # noqa: F401
+from .opt_paths import assert_tensor_same as _assert_tensor_same
+from .opt_paths import engine as _engine
+from .opt_paths import probe_grads as _probe_grads
+from .opt_paths import seed_moments as _seed
 
 pytestmark = pytest.mark.gpu
 
-UNFUSED = 1                                    # AFR_CFG_UNFUSED_OPTIMIZER
 OPTS = ("adamw", "lion")
 
 
 def _hyper(lr=LR, wd=WD):
     return dict(lr=lr, betas=(B1, B2), eps=EPS, weight_decay=wd)
-
-
-@pytest.fixture(autouse=True)
-def _no_error_bits_left_behind():
-    engines = []
-    _engine.made = engines
-    yield
-    for eng in engines:
-        assert eng.error_flags() == 0
-
-
-def _engine(cfg, dtype="f32", max_batch=64, **kw):
-    from ai_font_renderer_amd.engine import Engine
-    eng = Engine(cfg, dtype=dtype, max_batch=max_batch, **kw)
-    eng.load_params(synth.make_params(cfg))
-    _engine.made.append(eng)
-    return eng
-
-
-def _shadows(eng):
-    """The bf16 weight shadow(s) of a bf16 engine (a glyph plan keeps two, 256-byte aligned one behind the other)."""
-    if eng.dtype != "bf16":
-        return []
-    n2 = eng.n_flat * 2
-    bufs = [eng.workspace[:n2].view(torch.bfloat16)]
-    if eng.cfg.kind == "glyph":
-        o2 = (n2 + 255) // 256 * 256
-        bufs.append(eng.workspace[o2:o2 + n2].view(torch.bfloat16))
-    return bufs
-
-
-def _flats(eng):
-    """Every flat buffer an optimizer step writes: (tag, tensor)."""
-    out = [("param", eng.flat_params), ("exp_avg", eng.exp_avg)]
-    if eng.exp_avg_sq is not None:
-        out.append(("exp_avg_sq", eng.exp_avg_sq))
-    return out + [(f"shadow{i}", b) for i, b in enumerate(_shadows(eng))]
-
-
-def _assert_same_engine(a, b, what):
-    """p, m, v and the bf16 shadows bit for bit, over the whole flat buffers (padding included: both took the same path)."""
-    for (tag, ta), (_, tb) in zip(_flats(a), _flats(b)):
-        assert torch.equal(ta, tb), (what, tag, int((ta != tb).sum()))
-
-
-def _assert_tensor_same(a, b, nm, what):
-    """Tensor nm of engine a bit-identical to that of engine b: p, m, v and the bf16 shadows, over the tensor's elements."""
-    (o, k), = [(o, k) for n, _, o, k in a.layout if n == nm]
-    for (tag, ta), (_, tb) in zip(_flats(a), _flats(b)):
-        assert torch.equal(ta[o:o + k], tb[o:o + k]), (what, tag, nm, int((ta[o:o + k] != tb[o:o + k]).sum()))
-
-
-def _probe_grads(cfg, dtype, x, t, font, step=1):
-    """({name: gradient} on the CPU, global norm) of the batch at the initial parameters: what the seeded state is scaled by."""
-    probe = _engine(cfg, dtype, x.shape[0])
-    probe.train_step(x, t, font=font, step=step, do_step=False)
-    return {nm: probe.grads[nm].detach().cpu().clone() for nm, _, _, _ in probe.layout}, float(probe.grad_sumsq().sqrt())
-
-
-def _seed(eng, M, V):
-    for nm, _, o, k in eng.layout:
-        eng.exp_avg[o:o + k].copy_(M[nm].reshape(-1))
-        if eng.exp_avg_sq is not None:
-            eng.exp_avg_sq[o:o + k].copy_(V[nm].reshape(-1))
 
 
 # ----------------------------------------------------------------------------- 1. the flat kernel, op level
@@ -268,7 +207,7 @@ def test_all_ones_is_the_identity_and_uniform_multipliers_scale_the_step_bitwise
             assert grouped.read_loss() == plain.read_loss(), (path, i)
             if path == "clipped":
                 assert grouped.clip_coef() == plain.clip_coef() and (i > 0 or plain.clip_coef() < 0.5)      # (the first step is clipped for sure)
-        _assert_same_engine(grouped, plain, (mode, path))
+        assert_same_state(grouped, plain, (mode, path), padding=True)      # (padding included: both took the same path)
         assert float(grouped.exp_avg.abs().max()) > 0
 
 
@@ -343,14 +282,9 @@ def test_stitch_through_micro_batch_accumulation(name, dtype, opt):
 
 @pytest.mark.parametrize("opt", OPTS)
 def test_stitch_through_the_cooperative_split_k_tail(opt):
-    """C3's own layers at its batch of 8192 in bf16, the shape test_gpu_lion.py takes for the tail (afr_op_gemm_pair_plan: a split of
+    """C3's own layers at its batch of 8192 in bf16, the shape opt_paths.COOP_CASE names for the tail (afr_op_gemm_pair_plan: a split of
     8): the weight-gradient launch applies the update itself, with the tensor's own scalars."""
-    from ai_font_renderer_amd import _lib
-    from ai_font_renderer_amd.config import WORKLOADS
-    cfg, B = WORKLOADS["c3"]["cfg"], 8192
-    sk, need = C.c_int(), C.c_size_t()
-    assert _lib.lib().afr_op_gemm_pair_plan(B, 1024, 1024, C.byref(sk), C.byref(need)) == 0 and sk.value == 8
-    x, font, t = (torch.from_numpy(a) for a in glyph_inputs(cfg, B))
+    cfg, B, x, font, t = OP.coop_inputs()
     gen = torch.Generator().manual_seed(11)
     lm, wm = groups_ref.two_groups(cfg)
     grouped = _engine(cfg, "bf16", B, optimizer=opt, lr_mult=lm, wd_mult=wm)
@@ -364,7 +298,7 @@ def test_stitch_through_the_cooperative_split_k_tail(opt):
     grouped.profile(1)
     for eng, (lr_i, wd_i) in [(grouped, (LR, WD))] + [(e, h) for h, e in plain.items()]:
         eng.train_step(x, t, font=font, **_hyper(lr_i, wd_i))
-    assert any(r["kernel"].startswith("gemm_bf16_group256[") for r in grouped.profile_table())
+    assert OP.ran_coop_tail(grouped)
     _assert_stitched(grouped, plain, ("cooperative tail", opt))
 
 
@@ -374,22 +308,9 @@ def test_stitch_through_the_data_parallel_schedules_at_world_one(schedule, opt, 
     """The three schedules over world-1 RCCL, a glyph net, the sheet MINI model (dropout on) and C5-mini, f32 and bf16, plain and clipped:
     one-allreduce and overlapped end in afr_adamw_step, shard-force in Engine.adamw_range on the slice -- afr_op_opt_groups with the
     plan's ranges (with the all-reduced sum of squares when clipping)."""
-    import torch.distributed as dist
-    from ai_font_renderer_amd import parallel
     from ai_font_renderer_amd.parallel import DataParallelStepper
-    monkeypatch.setattr(parallel, "OVERLAP_MIN_BYTES", 0 if schedule == "overlapped" else 1 << 40)
-    if schedule == "shard-force":
-        monkeypatch.setenv("AFR_DP_SCHEDULE", "shard-force")
-    else:
-        monkeypatch.delenv("AFR_DP_SCHEDULE", raising=False)
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ.setdefault("MASTER_PORT", str(29600 + os.getpid() % 300))
-    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-    try:
-        xg, fg, tg = glyph_inputs(lion_ref.SMALL, 300)
-        glyph = (lion_ref.SMALL, 300, torch.from_numpy(xg).cuda(), torch.from_numpy(fg).cuda(), torch.from_numpy(tg).cuda())
-        sheet = (MINI, 37, torch.from_numpy(synth.encode_strings(synth.dataset_strings(37), MINI.max_length)).cuda(), None,
-                 torch.from_numpy(synth.synth_sheet_targets(37, MINI.sheet_h, MINI.sheet_w, tensor_id=931)).cuda())
+    with OP.rccl_world_one(schedule, monkeypatch) as dist:
+        glyph, sheet = (OP.inputs(c, "cuda") for c in OP.DP_CASES)
         c5cfg, c5x, c5f, c5t = lion_ref.case("c5-mini")                    # the pixel plan: 35 ranges under the two groups
         pixel = (c5cfg, c5x.shape[0], c5x.cuda(), c5f.cuda(), c5t.cuda())
         for (cfg, B, x, font, t), dtype, clip in ((glyph, "f32", False), (glyph, "bf16", True), (sheet, "f32", True), (sheet, "bf16", False),
@@ -408,8 +329,6 @@ def test_stitch_through_the_data_parallel_schedules_at_world_one(schedule, opt, 
                 fresh = _engine(cfg, dtype, B)
                 fresh.load_params(grouped.state_dict())
                 assert torch.equal(grouped.forward(x, font), fresh.forward(x, font))
-    finally:
-        dist.destroy_process_group()
 
 
 # ----------------------------------------------------------------------------- 5. against torch's param groups
@@ -476,7 +395,7 @@ def test_surface_facade_ema_replanning_and_it_trains(monkeypatch):
     eng.train_step(x, t, font=font, **_hyper())
     twin.train_step(x, t, font=font, **_hyper())
     assert eng.max_batch >= 300 and eng.param_group_ranges() == table
-    _assert_same_engine(eng, twin, "re-planned")
+    assert_same_state(eng, twin, "re-planned", padding=True)
     eng.set_param_groups(None, None)
     assert eng.param_group_ranges() == []
     # thirty steps of glyph-small under the default rule lower the loss

@@ -5,76 +5,25 @@ split-K tail, the bitwise equalities between the paths that end in the optimizer
 The sign makes Lion discontinuous; lion_ref.compare therefore checks EVERY element -- the moment everywhere, decided parameters
 against the reference, undecided ones against the three legal outcomes -- and the undecided share is capped at 2 % of the model
 (tests/test_lion_cpu.py holds the reference alone to that cap for every input used here)."""
-import os
+import functools
 
 import numpy as np
 import pytest
 import torch
 
 from . import clip_ref, lion_ref
+from . import opt_paths as OP
 from .gpu_util import ptr, stream
 from .lion_ref import B1, B2, LR, WD
-from .util import MINI, glyph_inputs, synth
+from .opt_paths import assert_same_state, no_error_bits_left_behind  # noqa: F401
+from .opt_paths import assert_shadow_is_bf16_of_masters as _assert_shadow_is_bf16_of_masters
+from .opt_paths import state as _state
+from .util import MINI
 
 pytestmark = pytest.mark.gpu
 
-UNFUSED = 1                                    # AFR_CFG_UNFUSED_OPTIMIZER
 HYPER = dict(lr=LR, betas=(B1, B2), weight_decay=WD)
-
-
-@pytest.fixture(autouse=True)
-def _no_error_bits_left_behind():
-    """error_flags() == 0 after every test: each test's engines register here."""
-    engines = []
-    _engine.made = engines
-    yield
-    for eng in engines:
-        assert eng.error_flags() == 0
-
-
-def _engine(cfg, dtype="f32", max_batch=64, optimizer="lion", **kw):
-    from ai_font_renderer_amd.engine import Engine
-    eng = Engine(cfg, dtype=dtype, max_batch=max_batch, optimizer=optimizer, **kw)
-    eng.load_params(synth.make_params(cfg))
-    _engine.made.append(eng)
-    return eng
-
-
-def _seed_moment(eng, M):
-    for nm, shp, o, k in eng.layout:
-        eng.exp_avg[o:o + k].copy_(M[nm].reshape(-1))
-
-
-def _state(eng):
-    """(params, exp_avg) as name -> tensor over the tensor elements (the padding between tensors is nobody's)."""
-    out = ({}, {})
-    for nm, shp, o, k in eng.layout:
-        for d, flat in zip(out, (eng.flat_params, eng.exp_avg)):
-            d[nm] = flat[o:o + k].clone()
-    return out
-
-
-def _assert_same_state(a, b, what):
-    for da, db, tag in zip(_state(a), _state(b), ("param", "exp_avg")):
-        for k in da:
-            assert torch.equal(da[k], db[k]), (what, tag, k, float((da[k] - db[k]).abs().max()))
-
-
-def _assert_shadow_is_bf16_of_masters(eng, x, font):
-    """The bf16 copy of the weights the next forward reads equals bf16 of the f32 masters, tensor by tensor.  A glyph plan keeps TWO
-    shadows, 256-byte aligned one behind the other, whose roles swap after every fused step: one of them must be current, and --
-    the functional half -- a forward must equal, bit for bit, that of a fresh engine whose shadow load_params derived from the
-    same masters."""
-    n2 = eng.n_flat * 2
-    bufs = [eng.workspace[:n2].view(torch.bfloat16)]
-    if eng.cfg.kind == "glyph":
-        o2 = (n2 + 255) // 256 * 256
-        bufs.append(eng.workspace[o2:o2 + n2].view(torch.bfloat16))
-    want = eng.flat_params.to(torch.bfloat16)
-    assert any(all(torch.equal(b[o:o + k], want[o:o + k]) for _, _, o, k in eng.layout) for b in bufs)
-    fresh = _engine(eng.cfg, "bf16", eng.max_batch)
-    fresh.load_params(eng.state_dict())
-    assert torch.equal(eng.forward(x, font), fresh.forward(x, font))
+_engine = functools.partial(OP.engine, optimizer="lion")
 
 
 # ----------------------------------------------------------------------------- 1. the elementwise kernel (site 1), op level
@@ -167,7 +116,7 @@ def test_one_lion_step_from_a_seeded_moment_vs_the_oracle(name, dtype, clipped):
     cfg, x, font, t = lion_ref.case(name)
     eng = _engine(cfg, dtype, x.shape[0], max_grad_norm=ref["max_norm"])
     assert eng.exp_avg_sq is None
-    _seed_moment(eng, ref["M"])
+    OP.seed_moments(eng, ref["M"])
     p_old = _state(eng)[0]
     if name == "glyph-c1":
         eng.profile(1)
@@ -197,22 +146,12 @@ def test_one_lion_step_from_a_seeded_moment_vs_the_oracle(name, dtype, clipped):
 
 # ----------------------------------------------------------------------------- 3. the cooperative split-K tail (site 5)
 def test_cooperative_split_k_tail_equals_the_unfused_lion_step_bitwise():
-    """C3's own layers at its batch of 8192: afr_op_gemm_pair_plan reports the cooperative form for (8192, 1024, 1024) with a split
-    of 8 (input-gradient tiles 32 x 4 + weight-gradient tiles 16 x 8 slices = 256 workgroups).  The form needs a split of 2, 4 or
-    8, N >= B / 8, at least 192 workgroups and 232 input-gradient tiles of 256 x 128: (6144, 768, 1024) is the only smaller shape in
-    steps of 256 that qualifies, 0.56 of the work, and no workload has it -- so C3's own layer it is.  One Lion step from a seeded
-    moment, fused (the tail applies lion_quad) against AFR_CFG_UNFUSED_OPTIMIZER (the tail stores the gradient, the Lion kernel
-    follows): parameters, moment and shadow bit for bit."""
-    import ctypes as C
-    from ai_font_renderer_amd import _lib
-    from ai_font_renderer_amd.config import WORKLOADS
-    cfg, B = WORKLOADS["c3"]["cfg"], 8192
-    sk, need = C.c_int(), C.c_size_t()
-    assert _lib.lib().afr_op_gemm_pair_plan(B, 1024, 1024, C.byref(sk), C.byref(need)) == 0 and sk.value == 8
-    assert _lib.lib().afr_op_gemm_pair_plan(4096, 1024, 1024, C.byref(sk), C.byref(need)) != 0
-    x, font, t = (torch.from_numpy(a) for a in glyph_inputs(cfg, B))
+    """C3's own layers at its batch of 8192 (opt_paths.COOP_CASE says why that shape).  One Lion step from a seeded moment, fused (the
+    tail applies lion_quad) against AFR_CFG_UNFUSED_OPTIMIZER (the tail stores the gradient, the Lion kernel follows): parameters,
+    moment and shadow bit for bit."""
+    cfg, B, x, font, t = OP.coop_inputs()
     gen = torch.Generator().manual_seed(11)
-    a, b = _engine(cfg, "bf16", B), _engine(cfg, "bf16", B, flags=UNFUSED)
+    a, b = _engine(cfg, "bf16", B), _engine(cfg, "bf16", B, flags=OP.UNFUSED)
     m0 = (torch.randn(a.n_flat, generator=gen) * 1e-4).cuda()
     for e in (a, b):
         e.exp_avg.copy_(m0)
@@ -220,18 +159,15 @@ def test_cooperative_split_k_tail_equals_the_unfused_lion_step_bitwise():
     for e in (a, b):
         e.train_step(x, t, font=font, **HYPER)
     assert a.read_loss() == b.read_loss()
-    assert any(r["kernel"].startswith("gemm_bf16_group256[") for r in a.profile_table())
-    _assert_same_state(a, b, "cooperative tail")
+    assert OP.ran_coop_tail(a)
+    assert_same_state(a, b, "cooperative tail", shadows=False)             # (each engine's current shadow is checked below)
     assert not torch.equal(a.exp_avg, m0)
     for e in (a, b):
         _assert_shadow_is_bf16_of_masters(e, x[:256], font[:256])
 
 
 # ----------------------------------------------------------------------------- 4. path equalities, bitwise, three steps each
-def _norm1(cfg, dtype, x, t, font, step=None):
-    probe = _engine(cfg, dtype, x.shape[0])
-    probe.train_step(x, t, font=font, step=step, do_step=False)
-    return float(probe.grad_sumsq().sqrt())
+_norm1 = OP.norm1
 
 
 @pytest.mark.parametrize("clip", [False, True])
@@ -248,23 +184,16 @@ def test_fused_step_equals_unfused_step_and_the_step_by_rows_bitwise(name, dtype
     if name.startswith("sheet"):
         cfg = MINI
     B = x.shape[0]
-    kw = dict(max_grad_norm=0.25 * _norm1(cfg, dtype, x, t, font, step=1)) if clip else {}
-    fused, unfused, split, rows = (_engine(cfg, dtype, B, flags=fl, **kw) for fl in (0, UNFUSED, 0, 0))
-    rows.bind_dataset(x, t, font=font)
-    idx = torch.arange(B)
-    for i in range(3):
-        fused.train_step(x, t, font=font, step=i + 1, **HYPER)
-        unfused.train_step(x, t, font=font, step=i + 1, **HYPER)
-        split.train_step(x, t, font=font, step=i + 1, do_step=False)
-        split.adamw_step(**HYPER)
-        rows.train_step_rows(idx, step=i + 1, **HYPER)
-        assert fused.read_loss() == unfused.read_loss() == split.read_loss() == rows.read_loss(), i
+    kw = dict(max_grad_norm=0.25 * _norm1(cfg, dtype, x, t, font, step=1, optimizer="lion")) if clip else {}
+    quartet = OP.forms(cfg, dtype, B, x, t, font, optimizer="lion", **kw)
+    fused, unfused, split, rows = quartet
+    for _ in OP.steps_of(quartet, x, t, font, HYPER):
         if clip:
             assert fused.clip_coef() == unfused.clip_coef() == split.clip_coef() == rows.clip_coef() < 1.0
-    _assert_same_state(fused, unfused, "AFR_CFG_UNFUSED_OPTIMIZER")
-    _assert_same_state(fused, split, "train_step(do_step=0) + adamw_step")
-    _assert_same_state(fused, rows, "train_step_rows")
-    assert fused.t == unfused.t == split.t == rows.t == 3
+    assert_same_state(fused, unfused, "AFR_CFG_UNFUSED_OPTIMIZER", shadows=False)
+    assert_same_state(fused, split, "train_step(do_step=0) + adamw_step", shadows=False)
+    assert_same_state(fused, rows, "train_step_rows")
+    assert fused.t == 3
     if dtype == "bf16":
         for e in (fused, unfused):
             _assert_shadow_is_bf16_of_masters(e, x, font)
@@ -275,14 +204,9 @@ def test_micro_batch_accumulation_ends_in_the_same_lion_step_bitwise(clip):
     """C5-mini, micro_batch 8 of 27 glyphs.  Accumulated gradients differ from the whole batch's in the last bits (another order of
     summation: test_gpu_clip holds them to 2e-5), and a sign does not forgive that -- so the whole-batch engine is handed the
     accumulated gradient buffer and steps from it: what must be bit-equal is the optimizer step the accumulation path ends in."""
-    from ai_font_renderer_amd.config import C5_MINI as cfg
-    B = 27
-    rng = np.random.default_rng(9)
-    x = torch.from_numpy((32 + (np.arange(B) * 11) % 95).astype(np.int64))
-    font = torch.from_numpy((np.arange(B) % 2).astype(np.int64))
-    tgt = torch.from_numpy(rng.integers(0, 256, (B, cfg.out_h, cfg.out_w), dtype=np.uint8))
-    kw = dict(max_grad_norm=0.25 * _norm1(cfg, "f32", x, tgt, font)) if clip else {}
-    whole, acc = _engine(cfg, "f32", B, **kw), _engine(cfg, "f32", B, micro_batch=8, **kw)
+    cfg, B, x, font, tgt = OP.inputs(OP.ACC_CASE)
+    kw = dict(max_grad_norm=0.25 * _norm1(cfg, "f32", x, tgt, font, optimizer="lion")) if clip else {}
+    whole, acc = _engine(cfg, "f32", B, **kw), _engine(cfg, "f32", B, micro_batch=OP.ACC_MICRO_BATCH, **kw)
     assert acc.max_batch == 8 and acc.exp_avg_sq is None
     for i in range(3):
         acc.train_step(x, tgt, font=font, **HYPER)
@@ -293,8 +217,8 @@ def test_micro_batch_accumulation_ends_in_the_same_lion_step_bitwise(clip):
         whole.adamw_step(**HYPER)
         if clip:
             assert acc.clip_coef() == whole.clip_coef() < 1.0
-    _assert_same_state(acc, whole, "micro-batch accumulation")
-    assert acc.t == whole.t == 3
+    assert_same_state(acc, whole, "micro-batch accumulation")
+    assert acc.t == 3
 
 
 @pytest.mark.parametrize("clip", [False, True])
@@ -303,41 +227,20 @@ def test_data_parallel_schedules_equal_the_single_gpu_lion_step_bitwise(schedule
     """test_gpu_clip's data-parallel case with a Lion engine: a glyph net and the sheet MINI model (dropout on), f32 and bf16, over
     world-1 RCCL.  Every schedule ends in the Lion kernel on the same gradients as the single-GPU step (sharded: afr_op_lion on the
     slice, with the all-reduced sum of squares when clipping) -- the stepper needs no schedule of its own for the kind."""
-    import torch.distributed as dist
-    from ai_font_renderer_amd import parallel
-    from ai_font_renderer_amd.parallel import DataParallelStepper
-    monkeypatch.setattr(parallel, "OVERLAP_MIN_BYTES", 0 if schedule == "overlapped" else 1 << 40)
-    if schedule == "shard-force":
-        monkeypatch.setenv("AFR_DP_SCHEDULE", "shard-force")
-    else:
-        monkeypatch.delenv("AFR_DP_SCHEDULE", raising=False)
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ.setdefault("MASTER_PORT", str(29600 + os.getpid() % 300))
-    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-    try:
-        xg, fg, tg = glyph_inputs(lion_ref.SMALL, 300)
-        glyph = (lion_ref.SMALL, 300, torch.from_numpy(xg).cuda(), torch.from_numpy(fg).cuda(), torch.from_numpy(tg).cuda())
-        sheet = (MINI, 37, torch.from_numpy(synth.encode_strings(synth.dataset_strings(37), MINI.max_length)).cuda(), None,
-                 torch.from_numpy(synth.synth_sheet_targets(37, MINI.sheet_h, MINI.sheet_w, tensor_id=931)).cuda())
-        for (cfg, B, x, font, t) in (glyph, sheet):
+    with OP.rccl_world_one(schedule, monkeypatch) as dist:
+        for (cfg, B, x, font, t) in (OP.inputs(c, "cuda") for c in OP.DP_CASES):
             for dtype in ("f32", "bf16"):
-                kw = dict(max_grad_norm=0.25 * _norm1(cfg, dtype, x, t, font, step=1)) if clip else {}
+                kw = dict(max_grad_norm=0.25 * _norm1(cfg, dtype, x, t, font, step=1, optimizer="lion")) if clip else {}
                 me = B * cfg.pixels
-                eng = _engine(cfg, dtype, B, **kw)
-                st = DataParallelStepper(eng, dist, world=1 if schedule == "shard-force" else 2)
-                assert st.sharded() == (schedule == "shard-force")
-                one = _engine(cfg, dtype, B, **kw)
-                st1 = DataParallelStepper(one, None, 1)
+                eng, st, one, st1 = OP.dp_steppers(dist, schedule, lambda: _engine(cfg, dtype, B, **kw))
                 for i in range(3):
                     st.step(x, t, font, mean_elems=me, step=i + 1, **HYPER)
                     st1.step(x, t, font, mean_elems=me, step=i + 1, **HYPER)
                     if clip:
                         assert one.clip_coef() < 0.5
                 assert st.global_loss() == st1.global_loss(), (cfg.kind, dtype)
-                _assert_same_state(eng, one, (schedule, cfg.kind, dtype))
+                assert_same_state(eng, one, (schedule, cfg.kind, dtype), shadows=False)
                 assert torch.equal(eng.forward(x, font), one.forward(x, font))   # (bf16: the shadow was re-synced)
-    finally:
-        dist.destroy_process_group()
 
 
 # ----------------------------------------------------------------------------- 5. state and surface

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from .opt_paths import rccl_world_one
 from .util import GlyphConfig, glyph_inputs, synth
 
 pytestmark = pytest.mark.gpu
@@ -65,15 +66,9 @@ def test_staged_backward_equals_monolithic_and_covers_the_buffer(kind):
 
 @pytest.mark.parametrize("schedule", ["one-allreduce", "overlapped"])
 def test_data_parallel_stepper_over_rccl_world1(schedule, monkeypatch):
-    import torch.distributed as dist
-    from ai_font_renderer_amd import parallel
     from ai_font_renderer_amd.parallel import DataParallelStepper
-    # small models take one all-reduce after backward; force the two-collective overlapped schedule for the other case
-    monkeypatch.setattr(parallel, "OVERLAP_MIN_BYTES", 0 if schedule == "overlapped" else 1 << 40)
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ.setdefault("MASTER_PORT", str(29600 + os.getpid() % 300))
-    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-    try:
+    # small models take one all-reduce after backward; the two-collective overlapped schedule is forced for the other case
+    with rccl_world_one(schedule, monkeypatch) as dist:
         cfg, eng = _glyph_engine()
         x, font, t = glyph_inputs(cfg, 300)
         xt, ft, tt = torch.from_numpy(x).cuda(), torch.from_numpy(font).cuda(), torch.from_numpy(t).cuda()
@@ -88,23 +83,15 @@ def test_data_parallel_stepper_over_rccl_world1(schedule, monkeypatch):
             st2.step(xt, tt, ft, mean_elems=300 * cfg.pixels)
         assert st2.global_loss() == l_dp
         assert torch.equal(eng2.flat_params, p_dp)
-    finally:
-        dist.destroy_process_group()
 
 
 def test_pixel_transformer_through_the_data_parallel_step(monkeypatch):
     """BASELINE configs[4]'s model (C5-mini, bf16) through the multi-rank code path with the overlapped schedule (stage 0's range
     reduced asynchronously while the other blocks' stages run) over a world of one: the parameters of the single-GPU step."""
-    import torch.distributed as dist
-    from ai_font_renderer_amd import parallel
     from ai_font_renderer_amd.config import C5_MINI as cfg
     from ai_font_renderer_amd.engine import Engine
     from ai_font_renderer_amd.parallel import DataParallelStepper
-    monkeypatch.setattr(parallel, "OVERLAP_MIN_BYTES", 0)
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ.setdefault("MASTER_PORT", str(29600 + os.getpid() % 300))
-    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-    try:
+    with rccl_world_one("overlapped", monkeypatch) as dist:
         B = 24
         xt = torch.from_numpy((32 + (np.arange(B) * 11) % 95).astype(np.int64)).cuda()
         ft = torch.from_numpy((np.arange(B) % 2).astype(np.int64)).cuda()
@@ -120,24 +107,16 @@ def test_pixel_transformer_through_the_data_parallel_step(monkeypatch):
             del eng
         assert res[0][0] == res[1][0]
         assert torch.equal(res[0][1], res[1][1])
-    finally:
-        dist.destroy_process_group()
 
 
 def test_accumulating_rank_through_the_data_parallel_step(monkeypatch):
     """A rank whose batch exceeds its micro-batch (Engine(micro_batch=m): gradient accumulation) takes the plain schedule --
     accumulate, one all-reduce of the summed gradient, AdamW -- whatever the overlap threshold says; world of one over RCCL,
     equal to the same engine stepping by itself."""
-    import torch.distributed as dist
-    from ai_font_renderer_amd import parallel
     from ai_font_renderer_amd.config import C5_MINI as cfg
     from ai_font_renderer_amd.engine import Engine
     from ai_font_renderer_amd.parallel import DataParallelStepper
-    monkeypatch.setattr(parallel, "OVERLAP_MIN_BYTES", 0)
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ.setdefault("MASTER_PORT", str(29600 + os.getpid() % 300))
-    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-    try:
+    with rccl_world_one("overlapped", monkeypatch) as dist:
         B = 20
         xt = torch.from_numpy((32 + (np.arange(B) * 11) % 95).astype(np.int64)).cuda()
         ft = torch.from_numpy((np.arange(B) % 2).astype(np.int64)).cuda()
@@ -153,8 +132,6 @@ def test_accumulating_rank_through_the_data_parallel_step(monkeypatch):
             del eng
         assert res[0][0] == res[1][0]
         assert torch.equal(res[0][1], res[1][1])
-    finally:
-        dist.destroy_process_group()
 
 
 def test_c4_per_gpu_shard_through_the_data_parallel_step():

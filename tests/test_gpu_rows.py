@@ -5,27 +5,26 @@ A call by rows does the arithmetic of the dense call on the gathered rows, in th
 comparisons against gather-then-call are BITWISE (torch.equal), for every plan kind, every dtype and every loss path (the
 loss kernel, the f32 / bf16x3 tile epilogue, the bf16 ring epilogue's early uint8 and late float32 target forms, the fused
 small-net step).  One test anchors the path to the reference's own golden numbers instead of to the code under test."""
-import os
 from dataclasses import replace
 
 import numpy as np
 import pytest
 import torch
 
+from . import opt_paths as OP
+from .opt_paths import no_error_bits_left_behind  # noqa: F401
 from .util import MINI, R0, GlyphConfig, SheetConfig, load, maxabs, synth
 
 pytestmark = pytest.mark.gpu
 
 
 def _engine(cfg, dtype="f32", max_batch=64, **kw):
-    from ai_font_renderer_amd.engine import Engine
-    return Engine(cfg, dtype=dtype, max_batch=max_batch, **kw)
+    return OP.engine(cfg, dtype, max_batch, load=False, **kw)
 
 
 def _pair(cfg, dtype, max_batch, **kw):
     """Two engines holding the same parameters: one is driven by rows, the other by gathered tensors."""
-    a, b = _engine(cfg, dtype, max_batch, **kw), _engine(cfg, dtype, max_batch, **kw)
-    a.load_params(synth.make_params(cfg))
+    a, b = OP.engine(cfg, dtype, max_batch, **kw), _engine(cfg, dtype, max_batch, **kw)
     b.flat_params.copy_(a.flat_params)
     b.sync_params()
     return a, b
@@ -287,14 +286,8 @@ def test_micro_batch_accumulation_by_rows_equals_gather():
 
 @pytest.mark.parametrize("schedule", ["one-allreduce", "overlapped"])
 def test_step_rows_over_rccl_world1_equals_step_on_gathered_tensors(schedule, monkeypatch):
-    import torch.distributed as dist
-    from ai_font_renderer_amd import parallel
     from ai_font_renderer_amd.parallel import DataParallelStepper
-    monkeypatch.setattr(parallel, "OVERLAP_MIN_BYTES", 0 if schedule == "overlapped" else 1 << 40)
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ.setdefault("MASTER_PORT", str(29600 + os.getpid() % 300))
-    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-    try:
+    with OP.rccl_world_one(schedule, monkeypatch) as dist:
         cfg = GlyphConfig(hidden=(48, 40), out_h=4, out_w=6, n_fonts=2)
         ds = _glyph_dataset(cfg, 400, 952)
         er, ed = _pair(cfg, "f32", 512)
@@ -314,8 +307,6 @@ def test_step_rows_over_rccl_world1_equals_step_on_gathered_tensors(schedule, mo
         for _ in range(3):
             s1.step_rows(rows, mean_elems=300 * cfg.pixels)
         _same(one.flat_params, ed.flat_params, "parameters of the single-process step by rows")
-    finally:
-        dist.destroy_process_group()
 
 
 # ----------------------------------------------------------------------------- 6. the loop no longer gathers

@@ -35,6 +35,23 @@ def maxabs(a, b):
     return float(np.max(np.abs(a - b))) if a.size else 0.0
 
 
+def bf16(t):
+    """round to nearest even to bfloat16, returned in the input's dtype"""
+    return t.float().bfloat16().to(t.dtype)
+
+
+def ratio(got, ref, bound):
+    """largest |got - ref| / bound over the elements; an element whose bound is 0 must be met exactly (inf otherwise); NaN / inf in got
+    count as inf"""
+    err = (got.double() - ref).abs()
+    if err.numel() == 0:
+        return 0.0
+    bound = bound.double().expand_as(err)
+    inf = torch.full_like(err, float("inf"))
+    r = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, inf, torch.zeros_like(err)))
+    return float(torch.where(torch.isnan(err), inf, r).max())
+
+
 def glyph_inputs(cfg, B, seed=0):
     """Deterministic (char, font) pairs cycling over printable ASCII x fonts + hashed u8 targets."""
     i = np.arange(B)
