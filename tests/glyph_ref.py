@@ -27,15 +27,12 @@ import torch
 
 from ai_font_renderer_amd import synth
 
+from .op_harness import bits  # noqa: F401
 from .util import bf16, ratio  # noqa: F401
 
 F64, F32, BF16 = torch.float64, torch.float32, torch.bfloat16
 U, UB = 2.0 ** -24, 2.0 ** -8
 L1_R, EMB_ROWS, GL1_ROWS, MAX_SPLIT = 64, 32, 8, 4      # glyphs per fused block, rows per embed_bwd block, fc1 rows per post-pass block
-
-
-def bits(t):
-    return t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
 
 
 # ---------------------------------------------------------------------------------------------------------------- shapes

@@ -12,6 +12,7 @@ import torch
 
 from ai_font_renderer_amd.config import C5_MINI, WORKLOADS
 
+from .op_harness import bits  # the bit patterns: -0.0 is not +0.0, and a NaN equals itself
 from .util import MINI, GlyphConfig, glyph_inputs, synth
 
 UNFUSED = 1                                    # AFR_CFG_UNFUSED_OPTIMIZER
@@ -41,11 +42,6 @@ def engine(cfg, dtype="f32", max_batch=64, *, load=True, **kw):
 
 
 # ----------------------------------------------------------------------------- what two engines are compared on
-def bits(t):
-    """The bit patterns: -0.0 is not +0.0, and a NaN equals itself."""
-    return t.contiguous().view(torch.int32 if t.element_size() == 4 else torch.int16)
-
-
 def same(a, b):
     return torch.equal(bits(a), bits(b))
 

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from .util import GlyphConfig, engine_rounding, fused1_eligible, glyph_inputs, maxabs, oracle, rnd_du, synth, tparams
+from .util import GlyphConfig, bf16, engine_rounding, fused1_eligible, glyph_inputs, maxabs, oracle, rand, rnd_du, synth, tparams
 
 pytestmark = pytest.mark.gpu
 
@@ -25,14 +25,6 @@ def _engine(cfg, dtype="f32", max_batch=64, **kw):
 def _rel(got, ref):
     ref = np.asarray(ref, dtype=np.float64)
     return maxabs(got, ref) / max(1e-7, float(np.abs(ref).max()))
-
-
-def _rand(tid, shape, bound=1.0):
-    return torch.from_numpy(synth.hash_uniform(tid, shape, bound))
-
-
-def _b16(t):
-    return t.to(torch.bfloat16).to(torch.float32)
 
 
 # ----------------------------------------------------------------------------- whole steps at the benchmarked batch
@@ -142,7 +134,7 @@ WIDE_SHAPES = [(8192, 1024, 1024), (4000, 2040, 520)]       # grids of 256 tiles
 def test_wide_bf16_gemm_all_orientations_vs_fp64(ak, bk):
     from .gpu_util import gemm
     for si, (M, N, K) in enumerate(WIDE_SHAPES):
-        A, B = _b16(_rand(110 + si, (M, K))), _b16(_rand(120 + si, (N, K), 0.25))
+        A, B = bf16(rand(110 + si, (M, K))), bf16(rand(120 + si, (N, K), 0.25))
         ref = A.double() @ B.double().t()
         scale = float(ref.abs().max())
         got = gemm("bf16", A, B, ak, bk)
@@ -154,8 +146,8 @@ def test_wide_bf16_gemm_all_orientations_vs_fp64(ak, bk):
 def test_wide_bf16_gemm_epilogues_and_splitk():
     from .gpu_util import gemm
     M, N, K = 8192, 1024, 1024
-    A, B = _b16(_rand(131, (M, K))), _b16(_rand(132, (N, K), 0.2))
-    bias, aux = _rand(133, (N,)), _b16(_rand(134, (M, N)))
+    A, B = bf16(rand(131, (M, K))), bf16(rand(132, (N, K), 0.2))
+    bias, aux = rand(133, (N,)), bf16(rand(134, (M, N)))
     ref = A.double() @ B.double().t()
     scale = float(ref.abs().max())
     got = gemm("bf16", A, B, bias=bias, relu=True, out_bf16=True)                               # forward layer
@@ -167,7 +159,7 @@ def test_wide_bf16_gemm_epilogues_and_splitk():
     got = gemm("bf16", A, B, b_kstrided=True, aux=aux)
     assert float((got.double() - ref * (aux > 0)).abs().max()) < 1e-5 * scale
     # weight gradient: 1024 x 1024 output reduced over 8192, split-K 8 (256 blocks) and 3 (ragged split)
-    A2, B2 = _b16(_rand(141, (1024, 8192), 0.05)), _b16(_rand(142, (1024, 8192)))
+    A2, B2 = bf16(rand(141, (1024, 8192), 0.05)), bf16(rand(142, (1024, 8192)))
     ref2 = A2.double() @ B2.double().t()
     for sk in (8, 3):
         got = gemm("bf16", A2, B2, a_kstrided=True, b_kstrided=True, splitk=sk)
@@ -186,8 +178,8 @@ def test_in_launch_splitk_gemm(M, N, K, head, sk, ak, bk):
     fp64, the arrival counters left at zero, and bitwise equal results from launch to launch (the slices are added in
     slice order whichever workgroup arrives last)."""
     from .gpu_util import gemm_fix
-    A, B = _b16(_rand(151, (M, K))), _b16(_rand(152, (N, K), 0.2))
-    bias, aux = _rand(153, (N,)), _b16(_rand(154, (M, N)))
+    A, B = bf16(rand(151, (M, K))), bf16(rand(152, (N, K), 0.2))
+    bias, aux = rand(153, (N,)), bf16(rand(154, (M, N)))
     ref = A.double() @ B.double().t()
     scale = float(ref.abs().max())
     outs, cnt = gemm_fix(A, B, head, sk, a_kstrided=ak, b_kstrided=bk, repeats=3)
@@ -211,8 +203,8 @@ def test_grouped_gradient_pair_vs_fp64(B, N, K, sk_want):
     split-K + dX with the ReLU mask, one grid): dW and db against fp64 at f32-accumulation accuracy, dX at bf16 output
     accuracy, bitwise equal from launch to launch, and dX bitwise equal to the stand-alone afr_op_gemm product."""
     from .gpu_util import gemm, gemm_pair
-    dy, x = _b16(_rand(161, (B, N), 0.05)), _b16(_rand(162, (B, K)))
-    W, aux = _b16(_rand(163, (N, K), 0.2)), _b16(_rand(164, (B, K)))
+    dy, x = bf16(rand(161, (B, N), 0.05)), bf16(rand(162, (B, K)))
+    W, aux = bf16(rand(163, (N, K), 0.2)), bf16(rand(164, (B, K)))
     outs, sk = gemm_pair(dy, x, W, aux, repeats=3)
     assert sk == sk_want
     dW, db, dX = outs[0]

@@ -11,7 +11,7 @@ import torch
 
 from ai_font_renderer_amd import _lib
 from .gpu_util import dev, gemm, ptr, stream
-from .util import MINI, R0, glyph_inputs, load, maxabs, oracle, synth, tparams
+from .util import MINI, R0, glyph_inputs, load, maxabs, oracle, rand, synth, tparams
 
 pytestmark = pytest.mark.gpu
 
@@ -70,15 +70,11 @@ def _bound(A, B, K, C64, bias=None):
     return b
 
 
-def _rand(tid, shape, bound=1.0):
-    return torch.from_numpy(synth.hash_uniform(tid, shape, bound))
-
-
 # ----------------------------------------------------------------------------- op level
 @pytest.mark.parametrize("ak,bk", [(0, 0), (0, 1), (1, 0), (1, 1)])
 def test_op_gemm_all_orientations_ragged_vs_fp64(ak, bk):
     M, N, K = 200, 136, 264                                   # no extent a tile multiple (128 x 128 x 32)
-    A, B = _rand(701, (M, K)), _rand(702, (N, K))
+    A, B = rand(701, (M, K)), rand(702, (N, K))
     C64 = A.double() @ B.double().t()
     got = _gemm_x3(A, B, bool(ak), bool(bk))
     err = (got.double() - C64).abs()
@@ -90,8 +86,8 @@ def test_op_gemm_all_orientations_ragged_vs_fp64(ak, bk):
 
 def test_op_gemm_epilogues_and_splitk_vs_fp64():
     M, N, K = 160, 200, 200
-    A, B = _rand(711, (M, K)), _rand(712, (N, K))
-    bias, aux = _rand(713, (N,)), _rand(714, (M, N))
+    A, B = rand(711, (M, K)), rand(712, (N, K))
+    bias, aux = rand(713, (N,)), rand(714, (M, N))
     C64 = A.double() @ B.double().t()
     b = _bound(A, B, K, C64, bias)
     pre = C64 + bias.double()
@@ -101,7 +97,7 @@ def test_op_gemm_epilogues_and_splitk_vs_fp64():
     assert bool(((got.double() - pre * (aux > 0).double()).abs() <= b).all())
     # split-K partial slabs, at the depth of R0's fc_output products (K = 6400), k-strided operands as in a weight gradient
     M, N, K = 136, 264, 6400
-    A, B = _rand(715, (M, K)), _rand(716, (N, K))
+    A, B = rand(715, (M, K)), rand(716, (N, K))
     C64 = A.double() @ B.double().t()
     for sk, (ak, bk) in ((1, (0, 0)), (4, (1, 1)), (5, (0, 1))):
         got = _gemm_x3(A, B, ak, bk, splitk=sk)

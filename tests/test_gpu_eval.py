@@ -16,6 +16,7 @@ import torch.nn.functional as F
 
 from . import eval_ref as R
 from . import lion_ref
+from .op_harness import bands_kept, guarded_bytes
 from .util import ROOT, load, oracle, synth
 
 pytestmark = pytest.mark.gpu
@@ -52,15 +53,6 @@ def _inputs(rows, cols, loss, act):
     return u, k, rowmap
 
 
-def _guarded(nbytes, fill=0xFF):
-    buf = torch.full((nbytes + 512,), fill, dtype=torch.uint8, device="cuda")
-    return buf, buf[256:256 + nbytes]
-
-
-def _guards_ok(buf):
-    return bool((buf[:256] == 0xFF).all()) and bool((buf[-256:] == 0xFF).all())
-
-
 def op_eval(u_dev, loss, tgt=None, rowmap=None, want=(True, True, True)):
     """One afr_op_eval launch into guarded, pre-filled buffers (0xFF bytes: a NaN in loss_rows, 0xFFFFFFFF in stats).  Returns
     (loss_rows f32 [R] | None, stats int64 [R, 4] | None, q uint8 [R, C] | None) on the device."""
@@ -69,12 +61,12 @@ def op_eval(u_dev, loss, tgt=None, rowmap=None, want=(True, True, True)):
     rows, cols = u_dev.shape
     ad = _lib.AFR_BF16 if u_dev.dtype == torch.bfloat16 else _lib.AFR_F32
     td = _lib.AFR_TARGET_U8 if tgt is None or tgt.dtype == torch.uint8 else _lib.AFR_TARGET_F32
-    bufs = [_guarded(n) if w else (None, None) for n, w in zip((4 * rows, 16 * rows, rows * cols), want)]
+    bufs = [guarded_bytes(n) if w else (None, None) for n, w in zip((4 * rows, 16 * rows, rows * cols), want)]
     _lib.check(_lib.lib().afr_op_eval(ad, _lib.loss_kind(loss), ptr(u_dev), ptr(tgt), td, ptr(rowmap), rows, cols,
                                       ptr(bufs[0][1]), ptr(bufs[1][1]), ptr(bufs[2][1]), stream()))
     torch.cuda.synchronize()
     for b, _ in bufs:
-        assert b is None or _guards_ok(b)
+        assert b is None or all(bands_kept(b))
     lr = bufs[0][1].view(torch.float32) if want[0] else None
     st = bufs[1][1].view(torch.int32).view(rows, 4) if want[1] else None
     if st is not None:
@@ -194,7 +186,7 @@ def test_op_eval_argument_errors_launch_nothing():
     lib = _lib.lib()
     u = torch.zeros(4, 24, device="cuda")
     k = torch.zeros(4, 24, dtype=torch.uint8, device="cuda")
-    outs = [_guarded(n) for n in (16, 64, 96)]
+    outs = [guarded_bytes(n) for n in (16, 64, 96)]
 
     def call(cols=24, tgt=k, want=(1, 1, 1), rows=4):
         return lib.afr_op_eval(0, 0, ptr(u), ptr(tgt), 0, None, rows, cols, *[ptr(o[1]) if w else C.c_void_p(0) for o, w in zip(outs, want)], stream())

@@ -8,14 +8,11 @@ import numpy as np
 import pytest
 import torch
 
-from ai_font_renderer_amd import _lib, synth
+from ai_font_renderer_amd import _lib
 from .gpu_util import dev, ptr, stream
+from .util import rand
 
 pytestmark = pytest.mark.gpu
-
-
-def _rand(tid, shape, bound=1.0):
-    return torch.from_numpy(synth.hash_uniform(tid, shape, bound))
 
 
 def _to_fp8(x, scale):
@@ -30,7 +27,7 @@ def _to_fp8(x, scale):
 
 
 def test_f32_to_fp8_is_the_ocp_e4m3_cast():
-    x = torch.cat([_rand(301, (4099,), 600.0), _rand(302, (2048,), 2.0), _rand(303, (2048,), 0.02),
+    x = torch.cat([rand(301, (4099,), 600.0), rand(302, (2048,), 2.0), rand(303, (2048,), 0.02),
                    torch.tensor([0.0, -0.0, 448.0, -448.0, 449.0, 1e6, -1e6, 2.0 ** -9, 2.0 ** -10, 0.0009765625 * 1.5, 17.0, 18.0, 19.0, 20.0])])
     for scale in (1.0, 0.37):
         got, _ = _to_fp8(x, scale)
@@ -45,9 +42,9 @@ def test_f32_to_fp8_is_the_ocp_e4m3_cast():
 def test_fp8_gemm_vs_fp64(M, N, K):
     lib = _lib.lib()
     sa, sb = 0.011, 0.0042
-    A8, Av = _to_fp8(_rand(311, (M, K), 3.0), sa)
-    B8, Bv = _to_fp8(_rand(312, (N, K), 1.5), sb)
-    bias = _rand(313, (N,))
+    A8, Av = _to_fp8(rand(311, (M, K), 3.0), sa)
+    B8, Bv = _to_fp8(rand(312, (N, K), 1.5), sb)
+    bias = rand(313, (N,))
     ref = Av.double() @ Bv.double().t()
     scale = float(ref.abs().max())
     for flags, post in ((0, lambda r: r), (_lib.GEMM_BIAS | _lib.GEMM_RELU, lambda r: torch.relu(r + bias.double()))):
@@ -73,8 +70,8 @@ def test_fp8_gemm_rate_against_the_5pf_roof():
     dense fp8 peak; asserted only to beat the bf16 ring kernel's best (1.3 PF): the MX-scaled instruction is in use."""
     lib = _lib.lib()
     M = N = K = 8192
-    A8, _ = _to_fp8(_rand(321, (M, K), 3.0), 0.01)
-    B8, _ = _to_fp8(_rand(322, (N, K), 3.0), 0.01)
+    A8, _ = _to_fp8(rand(321, (M, K), 3.0), 0.01)
+    B8, _ = _to_fp8(rand(322, (N, K), 3.0), 0.01)
     Cb = torch.empty((M, N), dtype=torch.bfloat16, device="cuda")
     run = lambda: _lib.check(lib.afr_op_gemm_fp8(_lib.GEMM_OUT_BF16, ptr(A8), ptr(B8), ptr(Cb), C.c_void_p(0), M, N, K, K, K, N, 1e-4, stream()))
     for _ in range(5):

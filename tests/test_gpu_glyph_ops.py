@@ -8,10 +8,10 @@ chunk early, E at the combination kernel's staging limit (40) and at 8, K0 from 
 groups), row blocks of the fused backward that are ragged (1, 63, 65, 200 glyphs) and full (64) in both h0 forms, its unsplit
 (N1 = 384) and split (256: 2, 1024: 4 column ranges) grids, embedding-backward blocks of 1, 32 + 1 and many rows, tables up to 82 KB
 of LDS; codes spread over the whole vocabulary with repeats, codes 0 and vocab - 1, one-code batches, font = NULL.  Besides the
-error, every case checks: output buffers pre-filled with NaN (a sentinel for int32) hold none afterwards and their 64-element guard
-bands on both sides keep their bits; columns of h1c between N1 and ld1 keep their fill; a second launch repeats the first bit for
-bit; in-range indices leave the error word 0; out-of-range ones set bit 0 in the forward kernels, and in every kernel give the
-outputs of the clamped indices; table rows no glyph of a block used are +0 in its slab.
+error, every case checks: output buffers pre-filled with NaN (a sentinel for int32) hold none afterwards and their guard bands of
+256 bytes on both sides keep their bits (tests/op_harness.py); columns of h1c between N1 and ld1 keep their fill; a second launch
+repeats the first bit for bit; in-range indices leave the error word 0; out-of-range ones set bit 0 in the forward kernels, and in
+every kernel give the outputs of the clamped indices; table rows no glyph of a block used are +0 in its slab.
 
 Every case prints its largest error as a fraction of the bound (pytest -s).  Measured on MI355X, the largest per output over all
 cases:
@@ -31,66 +31,10 @@ import torch
 from ai_font_renderer_amd import _lib
 from . import glyph_ref as R
 from .gpu_util import dev, ptr, stream
+from .op_harness import Outs, bits, dt, judge, same, tt, twice
 
 pytestmark = pytest.mark.gpu
 F64, F32, BF16 = torch.float64, torch.float32, torch.bfloat16
-GUARD = 64                                                        # elements in front of and behind every output buffer
-SENTINEL = -0x5A5A5A5B                                            # fill of int32 outputs
-
-
-def _tt(is_bf16):
-    return BF16 if is_bf16 else F32
-
-
-def _dt(is_bf16):
-    return _lib.AFR_BF16 if is_bf16 else _lib.AFR_F32
-
-
-bits = R.bits
-
-
-def _fill(n, dtype):
-    return torch.full((n,), SENTINEL, dtype=dtype, device="cuda") if dtype == torch.int32 else torch.full((n,), float("nan"), dtype=dtype, device="cuda")
-
-
-class Outs:
-    """output buffers of one launch: NaN-filled (int32: a sentinel), with a guard band of GUARD elements on both sides"""
-
-    def __init__(self):
-        self.bufs = {}
-
-    def new(self, name, n, dtype):
-        t = _fill(n + 2 * GUARD, dtype)
-        self.bufs[name] = (t, n)
-        return C.c_void_p(t.data_ptr() + GUARD * t.element_size())
-
-    def finish(self, may_keep_fill=()):
-        """-> name -> CPU tensor; asserts that every guard band kept its bits and that no fill value is left inside"""
-        torch.cuda.synchronize()
-        out = {}
-        for name, (t, n) in self.bufs.items():
-            want = bits(_fill(GUARD, t.dtype))
-            assert torch.equal(bits(t[:GUARD]), want), f"{name}: the guard band in front of the buffer was written"
-            assert torch.equal(bits(t[GUARD + n:]), want), f"{name}: the guard band behind the buffer was written"
-            out[name] = t[GUARD:GUARD + n].cpu()
-            if name not in may_keep_fill:
-                left = (out[name] == SENTINEL) if t.dtype == torch.int32 else torch.isnan(out[name].float())
-                assert not bool(left.any()), f"{name}: {int(left.sum())} elements the kernel owns were not written"
-        return out
-
-
-def _same(a, b, what):
-    for k in a:
-        if isinstance(a[k], torch.Tensor):
-            assert torch.equal(bits(a[k]), bits(b[k])), f"{what}: {k} differs"
-        else:
-            assert a[k] == b[k], f"{what}: {k} differs"
-
-
-def _report(name, worst):
-    print(f"{name}: max error / bound " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
-    for k, v in worst.items():
-        assert v <= 1.0, (name, k, v)
 
 
 class Tables:
@@ -114,36 +58,31 @@ def run_embed(T, x, font, is_bf16):
     B = x.shape[0]
     xd, fd = _ids(x, font)
     o = Outs()
-    po = o.new("out", B * T.E, _tt(is_bf16))
+    po = o.new("out", (B, T.E), tt(is_bf16))
     err = torch.zeros(1, dtype=torch.int32, device="cuda")
-    _lib.check(_lib.lib().afr_op_glyph_embed(_dt(is_bf16), T.p("emb"), T.p("femb"), ptr(xd), ptr(fd), B, T.E, T.vocab, T.n_fonts, po, ptr(err), stream()))
-    out = o.finish()
-    return dict(out=out["out"].reshape(B, T.E), err=int(err.cpu()))
+    _lib.check(_lib.lib().afr_op_glyph_embed(dt(is_bf16), T.p("emb"), T.p("femb"), ptr(xd), ptr(fd), B, T.E, T.vocab, T.n_fonts, po, ptr(err), stream()))
+    return dict(o.finish(), err=int(err.cpu()))
 
 
 def run_combo(T, x, font, ld1, with_w1t=True):
     B, nco = x.shape[0], T.vocab * max(T.n_fonts, 1)
     xd, fd = _ids(x, font)
     o = Outs()
-    p1, p0, pc = o.new("h1c", nco * ld1, BF16), o.new("h0c", nco * T.E, BF16), o.new("cidx", B, torch.int32)
-    pw = o.new("w1t", T.E * T.N1, BF16) if with_w1t else C.c_void_p(0)
+    p1, p0, pc = o.new("h1c", (nco, ld1), BF16), o.new("h0c", (nco, T.E), BF16), o.new("cidx", B, torch.int32)
+    pw = o.new("w1t", (T.E, T.N1), BF16) if with_w1t else C.c_void_p(0)
     err = torch.zeros(1, dtype=torch.int32, device="cuda")
     _lib.check(_lib.lib().afr_op_glyph_combo(T.p("emb"), T.p("femb"), T.p("W1"), T.p("b1"), ptr(xd), ptr(fd), B, T.E, T.N1, T.vocab, T.n_fonts, p1, ld1,
                                              p0, pc, pw, ptr(err), stream()))
-    out = o.finish(may_keep_fill=("h1c",) if ld1 > T.N1 else ())
-    res = dict(h1c=out["h1c"].reshape(nco, ld1), h0c=out["h0c"].reshape(nco, T.E), cidx=out["cidx"], err=int(err.cpu()))
-    if with_w1t:
-        res["w1t"] = out["w1t"].reshape(T.E, T.N1)
-    return res
+    # h1c keeps its fill between N1 and ld1 (test_combo asserts that, and that no NaN is left below N1)
+    return dict(o.finish(may_keep_fill=("h1c",) if ld1 > T.N1 else ()), err=int(err.cpu()))
 
 
 def run_l1_bwd(slabs_d, nslabs, stride, W1d, N1, E, vocab, n_fonts):
     nb, R_ = (N1 + 7) // 8, vocab + n_fonts
     o = Outs()
-    pd, pp = o.new("dw1", N1 * E, F32), o.new("part", nb * R_ * E, F32)
+    pd, pp = o.new("dw1", (N1, E), F32), o.new("part", (nb, R_, E), F32)
     _lib.check(_lib.lib().afr_op_glyph_l1_bwd(ptr(slabs_d), nslabs, stride, ptr(W1d), N1, E, vocab, n_fonts, pd, pp, stream()))
-    out = o.finish()
-    return dict(dw1=out["dw1"].reshape(N1, E), part=out["part"].reshape(nb, R_, E))
+    return o.finish()
 
 
 def run_fused(I, B, N1, vocab, n_fonts, x=None, font="same"):
@@ -153,20 +92,20 @@ def run_fused(I, B, N1, vocab, n_fonts, x=None, font="same"):
     d1, h0, w1t = dev(I["d1"], BF16), dev(I["h0"], BF16), dev(I["W1"].t().contiguous(), BF16)
     rm = dev(I["rowmap"]) if I["rowmap"] is not None else None
     o = Outs()
-    ps = o.new("slabs", nb * fl, F32)
+    ps = o.new("slabs", (nb, fl), F32)
     _lib.check(lib.afr_op_glyph_l1_bwd_fused(ptr(d1), ptr(h0), I["ldh"], ptr(rm), ptr(w1t), ptr(xd), ptr(fd), B, N1, vocab, n_fonts, ps, stream()))
-    return o.finish()["slabs"].reshape(nb, fl)
+    return o.finish()["slabs"]
 
 
 def run_embed_bwd(d, x, font, vocab, n_fonts, is_bf16):
     B, E = d.shape
     nb = _lib.lib().afr_embed_bwd_blocks(B)
     xd, fd = _ids(x, font)
-    dd = dev(d, _tt(is_bf16))
+    dd = dev(d, tt(is_bf16))
     o = Outs()
-    ps = o.new("slabs", nb * (vocab + n_fonts) * E, F32)
-    _lib.check(_lib.lib().afr_op_glyph_embed_bwd(_dt(is_bf16), ptr(dd), ptr(xd), ptr(fd), B, E, vocab, n_fonts, ps, stream()))
-    return o.finish()["slabs"].reshape(nb, vocab + n_fonts, E)
+    ps = o.new("slabs", (nb, vocab + n_fonts, E), F32)
+    _lib.check(_lib.lib().afr_op_glyph_embed_bwd(dt(is_bf16), ptr(dd), ptr(xd), ptr(fd), B, E, vocab, n_fonts, ps, stream()))
+    return o.finish()["slabs"]
 
 
 # ------------------------------------------------------------------------------------------------------------------ embed
@@ -184,8 +123,7 @@ def test_embed(B, E, vocab, n_fonts, kind, is_bf16):
     T = Tables(E, 8, vocab, n_fonts, 100)
     x, font = R.ids_for(B, vocab, n_fonts, 110, kind)
     xc, fc, _ = R.clamp_ids(x, font, vocab, n_fonts)
-    a, b = run_embed(T, x, font, is_bf16), run_embed(T, x, font, is_bf16)
-    _same(a, b, "a second launch")
+    a = twice(lambda: run_embed(T, x, font, is_bf16))
     assert a["err"] == 0
     assert torch.equal(bits(a["out"]), bits(_embed_bits(T, xc, fc, is_bf16))), "embed is not emb[x] + femb[f] bit for bit"
     print(f"embed {B}x{E} vocab {vocab} fonts {n_fonts} {kind}: bit for bit")
@@ -221,8 +159,7 @@ def test_combo(B, E, N1, vocab, n_fonts, kind, pad):
     x, font = R.ids_for(B, vocab, n_fonts, 110, kind)
     xc, fc, _ = R.clamp_ids(x, font, vocab, n_fonts)
     ld1, nf = N1 + pad, max(n_fonts, 1)
-    a, b = run_combo(T, x, font, ld1), run_combo(T, x, font, ld1)
-    _same(a, b, "a second launch")
+    a = twice(lambda: run_combo(T, x, font, ld1))
     assert a["err"] == 0
     assert torch.equal(a["cidx"].long(), xc * nf + fc), "cidx is not x max(n_fonts, 1) + f"
     cx, cf = R.combo_ids(vocab, n_fonts)
@@ -234,8 +171,8 @@ def test_combo(B, E, N1, vocab, n_fonts, kind, pad):
     h1c = a["h1c"][:, :N1].contiguous()
     assert not bool(torch.isnan(h1c.float()).any())
     h1r, flips = _check_h1(name, h1c, Tr, Tb, T.t["b1"], cx, cf, vocab, n_fonts, True)
-    _same(dict(a, w1t=0), dict(run_combo(T, x, font, ld1, with_w1t=False), w1t=0), "without w1t")
-    _report(name, dict(h1c=h1r))
+    same(dict(a, w1t=0), dict(run_combo(T, x, font, ld1, with_w1t=False), w1t=0), "without w1t")
+    judge(name, dict(h1c=h1r))
     print(f"    gates that differ from fp64's: {flips} of {h1c.numel()}")
     if B >= 3:
         xb, fb = R.bad_ids(B, vocab, n_fonts, x, font)
@@ -243,7 +180,7 @@ def test_combo(B, E, N1, vocab, n_fonts, kind, pad):
         bad = run_combo(T, xb, fb, ld1)
         assert flag and bad["err"] & 1
         assert torch.equal(bad["cidx"].long(), xbc * nf + fbc)
-        _same(dict(bad, err=0, cidx=0), dict(a, cidx=0), "out-of-range indices")
+        same(dict(bad, err=0, cidx=0), dict(a, cidx=0), "out-of-range indices")
 
 
 # ------------------------------------------------------------------------------------------------------------------ post-pass
@@ -255,10 +192,9 @@ def test_l1_bwd_post_pass(nslabs, N1, E, vocab, n_fonts, gap):
     sl = torch.full((nslabs, stride), float("nan"), dtype=F32)            # the space between two slabs is never read
     sl[:, :N1 * K0] = R.make_d((nslabs, N1 * K0), 410)
     sd, Wd = dev(sl), dev(W1)
-    a, b = run_l1_bwd(sd, nslabs, stride, Wd, N1, E, vocab, n_fonts), run_l1_bwd(sd, nslabs, stride, Wd, N1, E, vocab, n_fonts)
-    _same(a, b, "a second launch")
+    a = twice(lambda: run_l1_bwd(sd, nslabs, stride, Wd, N1, E, vocab, n_fonts))
     dw1, bw, part, bp = R.l1_bwd_ref(sl[:, :N1 * K0].reshape(nslabs, N1, K0), W1, E, vocab, n_fonts)
-    _report(f"l1_bwd {nslabs} slabs {N1}x{K0} (E {E}) stride +{gap}", dict(dw1=R.ratio(a["dw1"], dw1, bw), dtab_part=R.ratio(a["part"], part, bp)))
+    judge(f"l1_bwd {nslabs} slabs {N1}x{K0} (E {E}) stride +{gap}", dict(dw1=R.ratio(a["dw1"], dw1, bw), dtab_part=R.ratio(a["part"], part, bp)))
 
 
 # ------------------------------------------------------------------------------------------------------------------ fused backward
@@ -281,7 +217,7 @@ def _check_fused(name, slabs, I, B, N1, vocab, n_fonts):
     # the fp64 sum of all slabs against the unsplit, unrounded gradient, under the sum of the block bounds
     whole = R.fused_ref(I["d1"], I["h0g"], I["W1"], I["xc"], I["fc"], vocab, n_fonts, 1, rnd=None)
     worst["dTab total"] = R.ratio(totT, sum(w["dTab"] for w in whole), boundT)
-    _report(name, worst)
+    judge(name, worst)
     print(f"    split {split}, blocks {len(blocks)}, partials near a bf16 rounding boundary: {sum(b['near'] for b in blocks)}")
     return split
 
@@ -289,8 +225,7 @@ def _check_fused(name, slabs, I, B, N1, vocab, n_fonts):
 @pytest.mark.parametrize("B,N1,vocab,n_fonts,form,kind", R.FUSED_CASES, ids=lambda v: str(v))
 def test_l1_bwd_fused(B, N1, vocab, n_fonts, form, kind):
     I = R.fused_inputs(B, N1, vocab, n_fonts, form, kind)
-    a, b = run_fused(I, B, N1, vocab, n_fonts), run_fused(I, B, N1, vocab, n_fonts)
-    assert torch.equal(bits(a), bits(b)), "a second launch differs"
+    a = twice(lambda: run_fused(I, B, N1, vocab, n_fonts))
     split = _check_fused(f"l1_bwd_fused {B}x{N1} vocab {vocab} fonts {n_fonts} {form} {kind}", a, I, B, N1, vocab, n_fonts)
     assert split == {256: 2, 384: 1, 1024: 4}[N1]
 
@@ -325,12 +260,11 @@ def test_embed_bwd(B, E, vocab, n_fonts, kind, is_bf16):
     x, font = R.ids_for(B, vocab, n_fonts, 300, kind)
     xc, fc, _ = R.clamp_ids(x, font, vocab, n_fonts)
     d = R.make_d((B, E), 310, round_bf16=is_bf16)
-    a, b = run_embed_bwd(d, x, font, vocab, n_fonts, is_bf16), run_embed_bwd(d, x, font, vocab, n_fonts, is_bf16)
-    assert torch.equal(bits(a), bits(b)), "a second launch differs"
+    a = twice(lambda: run_embed_bwd(d, x, font, vocab, n_fonts, is_bf16))
     assert torch.equal(bits(a), bits(R.embed_bwd_f32(d, xc, fc, vocab, n_fonts))), "a slab is not the float32 sum of its rows in order"
     ref, bnd, used = R.embed_bwd_ref(d, xc, fc, vocab, n_fonts)
     assert not bool(bits(a)[~used].any()), "a table row no glyph of the block used is not +0"
-    _report(f"embed_bwd {B}x{E} vocab {vocab} fonts {n_fonts} {kind} {'bf16' if is_bf16 else 'f32'}", dict(slabs=R.ratio(a, ref, bnd)))
+    judge(f"embed_bwd {B}x{E} vocab {vocab} fonts {n_fonts} {kind} {'bf16' if is_bf16 else 'f32'}", dict(slabs=R.ratio(a, ref, bnd)))
     if B >= 3:                                                    # clamped, not flagged (there is no error word)
         xb, fb = R.bad_ids(B, vocab, n_fonts, x, font)
         xbc, fbc, _ = R.clamp_ids(xb, fb, vocab, n_fonts)

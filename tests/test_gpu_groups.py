@@ -69,7 +69,7 @@ LAYOUTS = {
 GUARD = 64
 
 
-def _guarded(x, fill):
+def _between_guards(x, fill):
     """x on the device between two guard bands of GUARD elements; returns (whole buffer, the view of x)."""
     buf = torch.full((x.numel() + 2 * GUARD,), fill, dtype=x.dtype, device="cuda")
     buf[GUARD:GUARD + x.numel()].copy_(x)
@@ -125,7 +125,7 @@ def test_op_opt_groups_vs_fp64_and_the_plain_kernels_range_by_range(kind, layout
             factor = np.float32(gscale) * np.float32(coef)
         bufs = {}
         for who in ("grouped", "plain"):
-            bufs[who] = [_guarded(x, fill) for x, fill in ((p0, 7.0), (g, 7.0), (m0, 7.0), (v0, 7.0), (torch.zeros(n, dtype=torch.bfloat16), 3.0))]
+            bufs[who] = [_between_guards(x, fill) for x, fill in ((p0, 7.0), (g, 7.0), (m0, 7.0), (v0, 7.0), (torch.zeros(n, dtype=torch.bfloat16), 3.0))]
         (_, p), (_, gd), (_, m), (_, v), (_, sh) = bufs["grouped"]
         _op_groups(kind, p, gd, m, None if kind == "lion" else v, sh, first, ranges, t, gscale, ss, max_norm)
         (_, pp), (_, gp), (_, mp), (_, vp), (_, shp) = bufs["plain"]

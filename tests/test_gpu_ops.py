@@ -6,17 +6,9 @@ import numpy as np
 import pytest
 import torch
 
-from .util import oracle, synth
+from .util import bf16, oracle, rand, synth
 
 pytestmark = pytest.mark.gpu
-
-
-def _rand(tid, shape, bound=1.0):
-    return torch.from_numpy(synth.hash_uniform(tid, shape, bound))
-
-
-def _b16(t):
-    return t.to(torch.bfloat16).to(torch.float32)
 
 
 SHAPES = [(128, 128, 64), (200, 136, 96), (95, 256, 32), (300, 24, 640), (8, 1024, 1024 + 64)]
@@ -29,9 +21,9 @@ def test_gemm_all_orientations_and_ragged_shapes(dtype, ak, bk):
     for si, (M, N, K) in enumerate(SHAPES):
         if ak and M % 8:
             M = (M + 7) // 8 * 8           # a k-strided operand's contiguous extent must be a multiple of 8
-        A, B = _rand(10 + si, (M, K)), _rand(20 + si, (N, K))
+        A, B = rand(10 + si, (M, K)), rand(20 + si, (N, K))
         if dtype == "bf16":
-            A, B = _b16(A), _b16(B)
+            A, B = bf16(A), bf16(B)
         ref = A.double() @ B.double().t()
         got = gemm(dtype, A, B, ak, bk)
         tol = 2e-6 * K ** 0.5 + 1e-6
@@ -53,10 +45,10 @@ def test_gemm_identity_with_asymmetric_operand(dtype):
 def test_gemm_epilogues_and_splitk(dtype):
     from .gpu_util import gemm
     M, N, K = 264, 136, 320
-    A, B = _rand(31, (M, K)), _rand(32, (N, K), 0.2)
-    bias, aux = _rand(33, (N,)), _rand(34, (M, N))
+    A, B = rand(31, (M, K)), rand(32, (N, K), 0.2)
+    bias, aux = rand(33, (N,)), rand(34, (M, N))
     if dtype == "bf16":
-        A, B, aux = _b16(A), _b16(B), _b16(aux)
+        A, B, aux = bf16(A), bf16(B), bf16(aux)
     ref = A.double() @ B.double().t()
     scale = float(ref.abs().max())
     got = gemm(dtype, A, B, bias=bias, relu=True)
@@ -76,8 +68,8 @@ def test_bf16_gemm_with_a_thousand_256x256_tiles_takes_the_256x256_body_and_matc
     with the bias / ReLU / bf16-output / ReLU-gate epilogues, against fp64."""
     from .gpu_util import gemm
     M, N, K = 65536 + 40, 1024, 256                     # 257 x 4 tiles
-    A, B = _b16(_rand(61, (M, K))), _b16(_rand(62, (N, K), 0.2))
-    bias, aux = _rand(63, (N,)), _b16(_rand(64, (M, N)))
+    A, B = bf16(rand(61, (M, K))), bf16(rand(62, (N, K), 0.2))
+    bias, aux = rand(63, (N,)), bf16(rand(64, (M, N)))
     ref = A.double() @ B.double().t()
     scale = float(ref.abs().max())
     got = gemm("bf16", A, B)
@@ -89,16 +81,16 @@ def test_bf16_gemm_with_a_thousand_256x256_tiles_takes_the_256x256_body_and_matc
     del ref, got, aux
     # the forward layout with a long K and few columns (fc2: 2048 -> 512)
     M, N, K = 131072, 512, 512
-    A, B = _b16(_rand(65, (M, K))), _b16(_rand(66, (N, K), 0.2))
+    A, B = bf16(rand(65, (M, K))), bf16(rand(66, (N, K), 0.2))
     ref = A.double() @ B.double().t()
-    got = gemm("bf16", A, B, bias=_rand(67, (N,)), out_bf16=True)
-    assert float((got.double() - (ref + _rand(67, (N,)).double())).abs().max()) < 1e-2 * float(ref.abs().max())
+    got = gemm("bf16", A, B, bias=rand(67, (N,)), out_bf16=True)
+    assert float((got.double() - (ref + rand(67, (N,)).double())).abs().max()) < 1e-2 * float(ref.abs().max())
 
 
 def test_f32_gemm_is_a_k_ordered_fma_chain_close_to_fp64():
     """Parity mode: exact-f32 MFMA, error ~1e-7 * sum|a b| (the 1e-4 bitmap bar needs K=6400 products)."""
     from .gpu_util import gemm
-    A, B = _rand(41, (64, 6400)), _rand(42, (192, 6400), 0.0125)
+    A, B = rand(41, (64, 6400)), rand(42, (192, 6400), 0.0125)
     ref = A.double() @ B.double().t()
     got = gemm("f32", A, B)
     assert float((got.double() - ref).abs().max()) < 2e-5
@@ -110,7 +102,7 @@ def test_mse_grad_matches_oracle(act, tgt):
     from ai_font_renderer_amd import _lib
     from .gpu_util import dev, ptr, stream
     rows, cols = 37, 19200
-    u = _rand(51, (rows, cols), 1.5) + 0.3
+    u = rand(51, (rows, cols), 1.5) + 0.3
     u.view(-1)[:4] = torch.tensor([0.0, 1.0, -0.0, 1.0000001])          # inclusive clamp boundaries
     tu8 = synth.hash_u8(52, (rows, cols))
     tf = torch.from_numpy(tu8.astype(np.float32) / 255.0)
@@ -139,13 +131,13 @@ def test_adamw_three_steps_match_torch_optim():
     from ai_font_renderer_amd import _lib
     from .gpu_util import dev, ptr, stream
     n = 64 * 1000
-    p0 = _rand(61, (n,), 0.5)
+    p0 = rand(61, (n,), 0.5)
     p = torch.nn.Parameter(p0.clone())
     opt = torch.optim.AdamW([p], lr=1e-3, weight_decay=5e-4, betas=(0.9, 0.99))
     pd, md, vd = dev(p0), torch.zeros(n, device="cuda"), torch.zeros(n, device="cuda")
     shadow = torch.zeros(n, dtype=torch.bfloat16, device="cuda")
     for t in (1, 2, 3):
-        g = _rand(70 + t, (n,), 0.01)
+        g = rand(70 + t, (n,), 0.01)
         p.grad = g.clone()
         opt.step()
         _lib.check(_lib.lib().afr_op_adamw(ptr(pd), ptr(dev(g)), ptr(md), ptr(vd), ptr(shadow), n, 1e-3, 0.9, 0.99, 1e-8, 5e-4, t,
@@ -158,7 +150,7 @@ def test_adamw_three_steps_match_torch_optim():
 def test_reduce_and_convert():
     from ai_font_renderer_amd import _lib
     from .gpu_util import dev, ptr, stream
-    s = _rand(81, (7, 1003))
+    s = rand(81, (7, 1003))
     out = dev(torch.ones(1003))
     _lib.check(_lib.lib().afr_op_reduce(ptr(out), ptr(dev(s)), 7, 1003, 1003, 0.5, 1, stream()))
     torch.cuda.synchronize()

@@ -2,8 +2,8 @@
 output element against the fp64 restatement of tests/pixel_ref.py under its derived per-row / per-element bound.  The row counts
 drive the grid-stride loops through none, part of, exactly one and several extra trips, with the planted rows (constant, mean 1e3,
 1e-4, one channel x 1e4; score gaps 0 .. +-100) at the first and last rows of every trip.  Besides the error, each case checks:
-outputs pre-filled with NaN hold none afterwards (every slab included); a guard band of one row behind every output keeps its
-bits; the planted groups, equal in content, give bit-identical output rows wherever they sit (row locality); a second launch
+outputs pre-filled with NaN hold none afterwards (every slab included); guard bands of one row (256 bytes at the least) in front of
+and behind every output keep their bits (tests/op_harness.py); the planted groups, equal in content, give bit-identical output rows wherever they sit (row locality); a second launch
 repeats the first bit for bit; dhT is bf16(dh) exactly; h is the float32 sum exactly.
 
 Every case prints its largest error as a fraction of the bound (pytest -s).  Measured on MI355X, the largest per kernel:
@@ -23,56 +23,10 @@ import torch
 from ai_font_renderer_amd import _lib
 from . import pixel_ref as R
 from .gpu_util import dev, ptr, stream
+from .op_harness import Outs, bits, dt, judge, tt, twice
 
 pytestmark = pytest.mark.gpu
 F64 = torch.float64
-
-
-def _tt(is_bf16):
-    return torch.bfloat16 if is_bf16 else torch.float32
-
-
-def _dt(is_bf16):
-    return _lib.AFR_BF16 if is_bf16 else _lib.AFR_F32
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
-
-
-class Outs:
-    """output buffers of one launch: NaN-filled, each followed by a guard band of `guard` elements (at least one row)"""
-
-    def __init__(self):
-        self.bufs = {}
-
-    def new(self, name, shape, dtype, guard, init=None):
-        n = 1
-        for s in shape:
-            n *= s
-        t = torch.full((n + guard,), float("nan"), dtype=dtype, device="cuda")
-        if init is not None:
-            t[:n] = init.reshape(-1).to(device="cuda", dtype=dtype)
-        self.bufs[name] = (t, n, tuple(shape))
-        return ptr(t)
-
-    def finish(self):
-        """-> name -> CPU tensor; asserts that no NaN is left and that every guard band kept its bits"""
-        torch.cuda.synchronize()
-        out = {}
-        for name, (t, n, shape) in self.bufs.items():
-            assert not bool(torch.isnan(t[:n]).any()), f"{name}: NaN left in an element the kernel owns"
-            want = torch.full((t.numel() - n,), float("nan"), dtype=t.dtype, device="cuda")
-            assert torch.equal(_bits(t[n:]), _bits(want)), f"{name}: the guard band behind the buffer was written"
-            out[name] = t[:n].reshape(shape).cpu()
-        return out
-
-
-def _twice(launch):
-    a, b = launch(), launch()
-    for k in a:
-        assert torch.equal(_bits(a[k]), _bits(b[k])), f"{k}: a second launch on the same inputs differs"
-    return a
 
 
 def _locality(c, got, keys):
@@ -80,16 +34,7 @@ def _locality(c, got, keys):
     for k in keys:
         for a in c["anchors"]:
             n = min(R.GROUP, c["rows"] - a)
-            assert torch.equal(_bits(got[k][a:a + n]), _bits(got[k][0:n])), f"{k}: rows {a}..{a + n - 1} differ from rows 0..{n - 1} on equal inputs"
-
-
-def _judge(name, got, ref, bnd, keys):
-    worst = {}
-    for k in keys:
-        worst[k] = R.ratio(got[k].double().reshape(ref[k].shape), ref[k], bnd[k])
-    print(f"{name}: max error / bound " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
-    for k, v in worst.items():
-        assert v <= 1.0, (name, k, v)
+            assert torch.equal(bits(got[k][a:a + n]), bits(got[k][0:n])), f"{k}: rows {a}..{a + n - 1} differ from rows 0..{n - 1} on equal inputs"
 
 
 def _reduce(slabs, nslabs, n):
@@ -121,22 +66,22 @@ def _fwd_params():
 def test_add_ln(B, tokens, d, is_bf16, mode):
     lib = _lib.lib()
     c = R.add_ln_case(B, tokens, d, mode, is_bf16)
-    rows, T = c["rows"], _tt(is_bf16)
+    rows, T = c["rows"], tt(is_bf16)
     hin, pos, add = (None if c[k] is None else dev(c[k], torch.float32 if k != "add" else T) for k in ("hin", "pos", "add"))
     g, b = (None if c[k] is None else dev(c[k]) for k in ("g", "b"))
 
     def launch():
         o = Outs()
-        ph = o.new("h", (rows, d), torch.float32, d)
-        pn = o.new("n", (rows, d), T, d) if mode != "no_n" else C.c_void_p(0)
-        _lib.check(lib.afr_op_pixel_add_ln(_dt(is_bf16), ptr(hin), ph, ptr(pos), ptr(add), ptr(g), ptr(b), pn, rows, tokens, d, R.EPS, stream()))
+        ph = o.new("h", (rows, d), torch.float32, guard=d)
+        pn = o.new("n", (rows, d), T, guard=d) if mode != "no_n" else C.c_void_p(0)
+        _lib.check(lib.afr_op_pixel_add_ln(dt(is_bf16), ptr(hin), ph, ptr(pos), ptr(add), ptr(g), ptr(b), pn, rows, tokens, d, R.EPS, stream()))
         return o.finish()
-    got = _twice(launch)
+    got = twice(launch)
     ref = R.add_ln_run(c, F64)
     want_h = ref["h"].float() if mode == "pos" else c["hin"] + c["add"]          # a copy, or ONE float32 addition: exact
-    assert torch.equal(_bits(got["h"]), _bits(want_h))
+    assert torch.equal(bits(got["h"]), bits(want_h))
     _locality(c, got, list(got))
-    _judge(f"add_ln/{mode} {rows}x{d}", got, ref, R.add_ln_bounds(c, ref), list(got))
+    judge(f"add_ln/{mode} {rows}x{d}", got, ref, R.add_ln_bounds(c, ref), list(got))
 
 
 @pytest.mark.parametrize("variant", ["mse", "bce-y-only", "mse-u-only"])
@@ -146,22 +91,22 @@ def test_head(B, tokens, d, is_bf16, variant):
     loss = variant[:3]
     c = R.head_case(B, tokens, d, loss, is_bf16)
     rows = c["rows"]
-    hin, add = dev(c["hin"]), dev(c["add"], _tt(is_bf16))
+    hin, add = dev(c["hin"]), dev(c["add"], tt(is_bf16))
     g, b, w, bo = (dev(c[k]) for k in ("g", "b", "w", "bo"))
 
     def launch():
         o = Outs()
-        ph = o.new("h", (rows, d), torch.float32, d)
-        pu = o.new("u", (rows,), torch.float32, 64) if variant != "bce-y-only" else C.c_void_p(0)
-        py = o.new("y", (rows,), torch.float32, 64) if variant != "mse-u-only" else C.c_void_p(0)
-        _lib.check(lib.afr_op_pixel_head(_dt(is_bf16), _lib.LOSS_KINDS[loss], ptr(hin), ph, ptr(add), ptr(g), ptr(b), ptr(w), ptr(bo), pu, py,
+        ph = o.new("h", (rows, d), torch.float32, guard=d)
+        pu = o.new("u", (rows,), torch.float32, guard=64) if variant != "bce-y-only" else C.c_void_p(0)
+        py = o.new("y", (rows,), torch.float32, guard=64) if variant != "mse-u-only" else C.c_void_p(0)
+        _lib.check(lib.afr_op_pixel_head(dt(is_bf16), _lib.LOSS_KINDS[loss], ptr(hin), ph, ptr(add), ptr(g), ptr(b), ptr(w), ptr(bo), pu, py,
                                          rows, d, R.EPS, stream()))
         return o.finish()
-    got = _twice(launch)
+    got = twice(launch)
     ref = R.head_run(c, F64)
-    assert torch.equal(_bits(got["h"]), _bits(c["hin"] + c["add"]))              # ONE float32 addition: exact
+    assert torch.equal(bits(got["h"]), bits(c["hin"] + c["add"]))              # ONE float32 addition: exact
     _locality(c, got, list(got))
-    _judge(f"head/{variant} {rows}x{d}", got, ref, R.head_bounds(c, ref), list(got))
+    judge(f"head/{variant} {rows}x{d}", got, ref, R.head_bounds(c, ref), list(got))
 
 
 @pytest.mark.parametrize("Cn", [2, 1])
@@ -169,18 +114,18 @@ def test_head(B, tokens, d, is_bf16, variant):
 def test_attn(B, tokens, d, is_bf16, Cn):
     lib = _lib.lib()
     c = R.attn_case(B, tokens, d, Cn, is_bf16)
-    rows, T = c["rows"], _tt(is_bf16)
+    rows, T = c["rows"], tt(is_bf16)
     q, kv = dev(c["q"], T), dev(c["kv"], T)
 
     def launch():
         o = Outs()
-        po = o.new("o", (rows, d), T, d)
-        _lib.check(lib.afr_op_pixel_attn(_dt(is_bf16), ptr(q), ptr(kv), po, rows, tokens, d, d // 64, Cn, stream()))
+        po = o.new("o", (rows, d), T, guard=d)
+        _lib.check(lib.afr_op_pixel_attn(dt(is_bf16), ptr(q), ptr(kv), po, rows, tokens, d, d // 64, Cn, stream()))
         return o.finish()
-    got = _twice(launch)
+    got = twice(launch)
     ref = R.attn_run(c, F64)
     _locality(c, got, ["o"])
-    _judge(f"attn/C{Cn} {rows}x{d}", got, ref, R.attn_bounds(c, ref), ["o"])
+    judge(f"attn/C{Cn} {rows}x{d}", got, ref, R.attn_bounds(c, ref), ["o"])
 
 
 # row counts of the head / LayerNorm backward (512 blocks of 16 waves = 8192 rows per trip, one partial slab per block):
@@ -203,13 +148,13 @@ def _slab_checks(name, c, bounds, got, ref, K):
     nblk = _lib.lib().afr_pixel_bwd_blocks(rows)
     assert nblk == R.bwd_blocks(rows)
     if "dhT" in got:
-        assert torch.equal(_bits(got["dhT"]), _bits(got["dh"].bfloat16())), "dhT is not bf16(dh)"
+        assert torch.equal(bits(got["dhT"]), bits(got["dh"].bfloat16())), "dhT is not bf16(dh)"
     _locality(c, got, ["dh"])
     slabs = got["part"].reshape(nblk, K, d)
     host = dict(dh=got["dh"], part=slabs.double().sum(0))
-    _judge(name + " (slabs summed in fp64)", host, ref, bounds(c, ref, reduced=False), ["dh", "part"])
+    judge(name + " (slabs summed in fp64)", host, ref, bounds(c, ref, reduced=False), ["dh", "part"])
     devsum = dict(part=_reduce(got["part"], nblk, K * d).reshape(K, d))
-    _judge(name + " (afr_op_reduce)", devsum, ref, bounds(c, ref, reduced=True), ["part"])
+    judge(name + " (afr_op_reduce)", devsum, ref, bounds(c, ref, reduced=True), ["part"])
     return slabs
 
 
@@ -223,12 +168,12 @@ def test_head_bwd(B, tokens, d, is_bf16):
 
     def launch():
         o = Outs()
-        pdh = o.new("dh", (rows, d), torch.float32, d)
-        pT = o.new("dhT", (rows, d), torch.bfloat16, d) if is_bf16 else C.c_void_p(0)
-        pp = o.new("part", (nblk, 4, d), torch.float32, 4 * d)
-        _lib.check(lib.afr_op_pixel_head_bwd(_dt(is_bf16), ptr(du), ptr(hf), ptr(g), ptr(b), ptr(w), pdh, pT, pp, rows, d, R.EPS, stream()))
+        pdh = o.new("dh", (rows, d), torch.float32, guard=d)
+        pT = o.new("dhT", (rows, d), torch.bfloat16, guard=d) if is_bf16 else C.c_void_p(0)
+        pp = o.new("part", (nblk, 4, d), torch.float32, guard=4 * d)
+        _lib.check(lib.afr_op_pixel_head_bwd(dt(is_bf16), ptr(du), ptr(hf), ptr(g), ptr(b), ptr(w), pdh, pT, pp, rows, d, R.EPS, stream()))
         return o.finish()
-    got = _twice(launch)
+    got = twice(launch)
     ref = R.head_bwd_run(c, F64)
     slabs = _slab_checks(f"head_bwd {rows}x{d}", c, R.head_bwd_bounds, got, ref, 4)
     assert float(slabs[:, 3, 1:].abs().max()) == 0.0                             # only element 0 of the fourth row carries db_out
@@ -239,17 +184,17 @@ def test_ln_bwd_in_place(B, tokens, d, is_bf16):
     lib = _lib.lib()
     c = R.ln_bwd_case(B, tokens, d, is_bf16)
     rows = c["rows"]
-    dy, hin, g = dev(c["dy"], _tt(is_bf16)), dev(c["hin"]), dev(c["g"])
+    dy, hin, g = dev(c["dy"], tt(is_bf16)), dev(c["hin"]), dev(c["g"])
     nblk = R.bwd_blocks(rows)
 
     def launch():
         o = Outs()
-        pdh = o.new("dh", (rows, d), torch.float32, d, init=c["dh"])              # in place on dh, as the plan runs it
-        pT = o.new("dhT", (rows, d), torch.bfloat16, d) if is_bf16 else C.c_void_p(0)
-        pp = o.new("part", (nblk, 2, d), torch.float32, 2 * d)
-        _lib.check(lib.afr_op_pixel_ln_bwd(_dt(is_bf16), ptr(dy), ptr(hin), ptr(g), pdh, pT, pp, rows, d, R.EPS, stream()))
+        pdh = o.new("dh", (rows, d), torch.float32, guard=d, init=c["dh"])              # in place on dh, as the plan runs it
+        pT = o.new("dhT", (rows, d), torch.bfloat16, guard=d) if is_bf16 else C.c_void_p(0)
+        pp = o.new("part", (nblk, 2, d), torch.float32, guard=2 * d)
+        _lib.check(lib.afr_op_pixel_ln_bwd(dt(is_bf16), ptr(dy), ptr(hin), ptr(g), pdh, pT, pp, rows, d, R.EPS, stream()))
         return o.finish()
-    got = _twice(launch)
+    got = twice(launch)
     ref = R.ln_bwd_run(c, F64)
     _slab_checks(f"ln_bwd {rows}x{d}", c, R.ln_bwd_bounds, got, ref, 2)
 
@@ -262,7 +207,7 @@ def test_ln_bwd_in_place(B, tokens, d, is_bf16):
 def test_attn_bwd(B, tokens, d, Cn, is_bf16):
     lib = _lib.lib()
     c = R.attn_bwd_case(B, tokens, d, Cn, is_bf16)
-    rows, T = c["rows"], _tt(is_bf16)
+    rows, T = c["rows"], tt(is_bf16)
     dO, q, kv = dev(c["dO"], T), dev(c["q"], T), dev(c["kv"], T)
     chunk = lib.afr_pixel_attn_chunk(tokens)
     assert chunk == R.attn_chunk(tokens)
@@ -270,18 +215,18 @@ def test_attn_bwd(B, tokens, d, Cn, is_bf16):
 
     def launch():
         o = Outs()
-        pdq = o.new("dq", (rows, d), T, d)
-        pp = o.new("part", (chunks, B, 4 * d), torch.float32, 4 * d)
-        _lib.check(lib.afr_op_pixel_attn_bwd(_dt(is_bf16), ptr(dO), ptr(q), ptr(kv), pdq, pp, B, tokens, d, d // 64, Cn, stream()))
+        pdq = o.new("dq", (rows, d), T, guard=d)
+        pp = o.new("part", (chunks, B, 4 * d), torch.float32, guard=4 * d)
+        _lib.check(lib.afr_op_pixel_attn_bwd(dt(is_bf16), ptr(dO), ptr(q), ptr(kv), pdq, pp, B, tokens, d, d // 64, Cn, stream()))
         return o.finish()
-    got = _twice(launch)
+    got = twice(launch)
     ref = R.attn_bwd_run(c, F64)
     _locality(c, got, ["dq"])
     if Cn == 1:
         assert float(got["part"][:, :, 2 * d:].abs().max()) == 0.0 and float(got["dq"].float().abs().max()) == 0.0
     name = f"attn_bwd {B}x{tokens}x{d} C{Cn}"
-    _judge(name + " (slabs summed in fp64)", dict(dq=got["dq"], dkv=got["part"].double().sum(0)), ref, R.attn_bwd_bounds(c, ref, reduced=False), ["dq", "dkv"])
-    _judge(name + " (afr_op_reduce)", dict(dkv=_reduce(got["part"], chunks, B * 4 * d).reshape(B, 4 * d)), ref, R.attn_bwd_bounds(c, ref, reduced=True), ["dkv"])
+    judge(name + " (slabs summed in fp64)", dict(dq=got["dq"], dkv=got["part"].double().sum(0)), ref, R.attn_bwd_bounds(c, ref, reduced=False), ["dq", "dkv"])
+    judge(name + " (afr_op_reduce)", dict(dkv=_reduce(got["part"], chunks, B * 4 * d).reshape(B, 4 * d)), ref, R.attn_bwd_bounds(c, ref, reduced=True), ["dkv"])
 
 
 @pytest.mark.parametrize("B,d,n_fonts", [(1, 64, 3), (13, 192, 3), (40, 512, 3), (7, 320, 0)])
@@ -298,23 +243,23 @@ def test_ctx_and_ctx_bwd(B, d, n_fonts):
 
         def launch():
             o = Outs()
-            pc = o.new("ctx", (B, Cn, d), _tt(is_bf16), d)
-            _lib.check(lib.afr_op_pixel_ctx(_dt(is_bf16), ptr(emb), ptr(femb), ptr(x), ptr(font), B, d, I["vocab"], n_fonts, pc, ptr(err), stream()))
+            pc = o.new("ctx", (B, Cn, d), tt(is_bf16), guard=d)
+            _lib.check(lib.afr_op_pixel_ctx(dt(is_bf16), ptr(emb), ptr(femb), ptr(x), ptr(font), B, d, I["vocab"], n_fonts, pc, ptr(err), stream()))
             return o.finish()
-        got = _twice(launch)
-        assert torch.equal(_bits(got["ctx"]), _bits(want.to(_tt(is_bf16)))) and int(err.item()) == 0
+        got = twice(launch)
+        assert torch.equal(bits(got["ctx"]), bits(want.to(tt(is_bf16)))) and int(err.item()) == 0
 
     def launch_bwd():
         o = Outs()
-        pe = o.new("demb", (I["vocab"], d), torch.float32, d)
-        pf = o.new("dfont", (n_fonts, d), torch.float32, d) if n_fonts else C.c_void_p(0)
+        pe = o.new("demb", (I["vocab"], d), torch.float32, guard=d)
+        pf = o.new("dfont", (n_fonts, d), torch.float32, guard=d) if n_fonts else C.c_void_p(0)
         _lib.check(lib.afr_op_pixel_ctx_bwd(ptr(dctx), ptr(x), ptr(font), B, d, I["vocab"], n_fonts, pe, pf, stream()))
         return o.finish()
-    got = _twice(launch_bwd)
+    got = twice(launch_bwd)
     ref = R.ctx_bwd(I["dctx"].double(), I["x"], I["font"], I["vocab"], n_fonts)
     bnd = R.bound_ctx_bwd(I["dctx"].double(), I["x"], I["font"], I["vocab"], n_fonts)
     keys = ["demb"] + (["dfont"] if n_fonts else [])
-    _judge(f"ctx_bwd {B}x{d}", got, dict(demb=ref[0], dfont=ref[1]), dict(demb=bnd[0], dfont=bnd[1]), keys)
+    judge(f"ctx_bwd {B}x{d}", got, dict(demb=ref[0], dfont=ref[1]), dict(demb=bnd[0], dfont=bnd[1]), keys)
     used = set(I["x"].tolist())
     for v in range(I["vocab"]):
         if v not in used:

@@ -6,7 +6,8 @@ can fail: the L sweep (B = 3, max_length 120) walks the edges of the key pairs (
 persistent loop through one, exactly one, and up to three strings per block (600 = 2.34 trips); every batch mixes dataset strings,
 one-code strings (an occurrence chain of length L), a code at distances 7, 8, 9, 17, all-distinct codes, codes 0 and vocab - 1,
 and a rare code in strings 10, 266 and 522.  Besides the error, each case checks: buffers pre-filled with NaN hold none afterwards
-and their guard bands on both sides keep their bits; z beyond L*64 is +0; in training the saved keep bits are the packed synth
+(tests/op_harness.py checks z and the slabs of every launch, the case the float part of the save area) and their guard bands of 256
+bytes on both sides keep their bits; z beyond L*64 is +0; in training the saved keep bits are the packed synth
 masks; the kernel's ReLU gate (z > 0 where fc dropout kept the element) differs from fp64's only where |pre| is below its bound;
 a second launch repeats the first bit for bit; the backward without a save area (the recompute path) gives the same slabs bit for
 bit; every slab is finite, and the space between tensors, rows of dP at or beyond L and embedding rows of codes its block never
@@ -29,44 +30,10 @@ import torch
 from ai_font_renderer_amd import _lib
 from . import sheet_ref as R
 from .gpu_util import dev, ptr, stream
+from .op_harness import Outs, bits, dt, judge, tt, twice
 
 pytestmark = pytest.mark.gpu
 F64 = torch.float64
-GUARD = 64                                                        # elements in front of and behind every output buffer
-
-def _tt(is_bf16):
-    return torch.bfloat16 if is_bf16 else torch.float32
-
-
-def _dt(is_bf16):
-    return _lib.AFR_BF16 if is_bf16 else _lib.AFR_F32
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
-
-
-class Outs:
-    """output buffers of one launch: NaN-filled, with a guard band of GUARD elements on both sides"""
-
-    def __init__(self):
-        self.bufs = {}
-
-    def new(self, name, n, dtype):
-        t = torch.full((n + 2 * GUARD,), float("nan"), dtype=dtype, device="cuda")
-        self.bufs[name] = (t, n)
-        return C.c_void_p(t.data_ptr() + GUARD * t.element_size())
-
-    def finish(self):
-        """-> name -> CPU tensor; asserts that every guard band kept its bits"""
-        torch.cuda.synchronize()
-        out = {}
-        for name, (t, n) in self.bufs.items():
-            want = _bits(torch.full((GUARD,), float("nan"), dtype=t.dtype, device="cuda"))
-            assert torch.equal(_bits(t[:GUARD]), want), f"{name}: the guard band in front of the buffer was written"
-            assert torch.equal(_bits(t[GUARD + n:]), want), f"{name}: the guard band behind the buffer was written"
-            out[name] = t[GUARD:GUARD + n].cpu()
-        return out
 
 
 class Dev:
@@ -77,7 +44,7 @@ class Dev:
         self.P = {n: dev(t) for n, t in c["P"].items()}
         self.prm = _lib.AfrSheetParams(*[self.P[n].data_ptr() for n in R.NAMES])
         self.x = dev(c["x"] if x is None else x)
-        self.dz = dev(c["dz"], _tt(c["is_bf16"]))
+        self.dz = dev(c["dz"], tt(c["is_bf16"]))
         d = c["drop"]
         self.drop = None if d is None else _lib.AfrSheetDropout(d["seed"], d["step"], d["rank"], *d["p"])
         self.off, self.sizes, self.total = R.slab_layout(c["max_length"], c["vocab"])
@@ -91,27 +58,24 @@ class Dev:
         c = self.c
         B, L = c["B"], c["L"]
         o = Outs()
-        pz = o.new("z", B * c["max_length"] * R.F, _tt(c["is_bf16"]))
-        ps = o.new("save", B * L * R.SAVE_PER_POS, torch.float32) if save else C.c_void_p(0)
+        pz = o.new("z", (B, c["max_length"] * R.F), tt(c["is_bf16"]))
+        ps = o.new("save", (B, L * R.SAVE_PER_POS), torch.float32) if save else C.c_void_p(0)
         err = torch.zeros(1, dtype=torch.int32, device="cuda")
-        _lib.check(_lib.lib().afr_op_sheet_fwd(_dt(c["is_bf16"]), C.byref(self.prm), ptr(self.x), c["ldx"], B, L, c["max_length"], c["vocab"],
+        _lib.check(_lib.lib().afr_op_sheet_fwd(dt(c["is_bf16"]), C.byref(self.prm), ptr(self.x), c["ldx"], B, L, c["max_length"], c["vocab"],
                                                R.EPS, self._drop(drop), pz, ps, ptr(err), stream()))
-        out = o.finish()
-        out["err"] = int(err.cpu())
-        out["z"] = out["z"].reshape(B, -1)
-        if save:
-            out["save"] = out["save"].reshape(B, -1)
-        return out
+        # save may keep its fill: its keep words are bit patterns (a word of ones is a NaN) and are not written at all outside training;
+        # the float part of every row is checked for NaN by the case
+        return dict(o.finish(may_keep_fill=("save",)), err=int(err.cpu()))
 
     def bwd(self, save):
         c = self.c
         nb = R.blocks(c["B"])
         o = Outs()
-        psl = o.new("slabs", nb * self.total, torch.float32)
+        psl = o.new("slabs", (nb, self.total), torch.float32)
         sv = None if save is None else save.cuda().contiguous()
-        _lib.check(_lib.lib().afr_op_sheet_bwd(_dt(c["is_bf16"]), C.byref(self.prm), ptr(self.x), c["ldx"], c["B"], c["L"], c["max_length"],
+        _lib.check(_lib.lib().afr_op_sheet_bwd(dt(c["is_bf16"]), C.byref(self.prm), ptr(self.x), c["ldx"], c["B"], c["L"], c["max_length"],
                                                c["vocab"], R.EPS, self._drop(None), ptr(self.dz), ptr(sv), psl, C.byref(self.lay), stream()))
-        return o.finish()["slabs"].reshape(nb, self.total)
+        return o.finish()["slabs"]
 
 
 def split_save(save, L, training):
@@ -120,8 +84,8 @@ def split_save(save, L, training):
     o = save[:, :L * R.E].reshape(B, L, R.E)
     smax = save[:, L * 32:L * 36].reshape(B, R.H, L)
     sinv = save[:, L * 36:L * 40].reshape(B, R.H, L)
-    bits = (save[:, L * 40:].contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF).reshape(B, R.H, L, 4) if training else None
-    return dict(o=o, smax=smax, sinv=sinv, bits=bits)
+    keep = (bits(save[:, L * 40:]).to(torch.int64) & 0xFFFFFFFF).reshape(B, R.H, L, 4) if training else None
+    return dict(o=o, smax=smax, sinv=sinv, bits=keep)
 
 
 def grads_of(slabs, d, dtype=F64):
@@ -157,13 +121,6 @@ def _reference(B, L, ML, mode, kind, ldx):
     return P64, masks, scales, fw, R.fwd_bounds(P64, fw, False), R.fwd_bounds(P64, fw, True)["z"]
 
 
-def _judge(name, got, ref, bnd, keys):
-    worst = {k: R.ratio(got[k].double().reshape(ref[k].shape), ref[k], bnd[k]) for k in keys}
-    print(f"{name}: max error / bound " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
-    for k, v in worst.items():
-        assert v <= 1.0, (name, k, v)
-
-
 def _run_case(B, L, ML, mode, is_bf16, kind="generic", ldx=None):
     ldx = L if ldx is None else ldx
     name = f"{B}x{L} ldx {ldx} {mode} {kind} {'bf16' if is_bf16 else 'f32'}"
@@ -172,21 +129,18 @@ def _run_case(B, L, ML, mode, is_bf16, kind="generic", ldx=None):
     training = c["drop"] is not None
     d = Dev(c)
     # ---- forward
-    f1, f2 = d.fwd(), d.fwd()
-    for k in ("z", "save"):
-        assert torch.equal(_bits(f1[k]), _bits(f2[k])), f"{k}: a second launch on the same inputs differs"
+    f1 = twice(d.fwd)
     assert f1["err"] == 0
-    z = f1["z"]
-    assert not bool(torch.isnan(z.float()).any()), "z: NaN left in an element the kernel owns"
-    assert not bool(_bits(z[:, L * R.F:]).any()), "z beyond L*64 is not +0"
+    z = f1["z"]                                                   # (no NaN left in it: Outs.finish)
+    assert not bool(bits(z[:, L * R.F:]).any()), "z beyond L*64 is not +0"
     sv = split_save(f1["save"], L, training)
     assert not bool(torch.isnan(f1["save"][:, :L * 40]).any()), "save: NaN left in an element the kernel owns"     # (the keep words are compared below)
     got = dict(z=z.float(), o=sv["o"], smax=sv["smax"], sinv=sv["sinv"])
     bnd = dict(fb, z=zb16 if is_bf16 else fb["z"])
-    _judge(name, got, fw, bnd, ("z", "o", "smax", "sinv"))
+    judge(name, got, fw, bnd, ("z", "o", "smax", "sinv"))
     if training:
         assert torch.equal(sv["bits"], fw["bits"]), "the saved keep bits are not the packed synth masks"
-    assert torch.equal(_bits(d.fwd(save=False)["z"]), _bits(z)), "z depends on whether a save area is given"
+    assert torch.equal(bits(d.fwd(save=False)["z"]), bits(z)), "z depends on whether a save area is given"
     # ---- the kernel's ReLU gate: z > 0 where fc dropout kept the element (elsewhere df is zero whatever the gate)
     cache = fw["cache"]
     kept = (masks["fc"] != 0) if training else torch.ones_like(cache["gate"])
@@ -195,14 +149,13 @@ def _run_case(B, L, ML, mode, is_bf16, kind="generic", ldx=None):
     assert not bool((flipped & (cache["pre"].abs() >= fb["pre"])).any()), "a ReLU gate differs from fp64's where |pre| is not below its bound"
     print(f"    gates that differ from fp64's: {int(flipped.sum())} of {gate.numel()}")
     # ---- backward: with the save area, again, and without it (the recompute path)
-    s1 = d.bwd(f1["save"])
-    assert torch.equal(_bits(s1), _bits(d.bwd(f1["save"]))), "slabs: a second launch on the same inputs differs"
-    assert torch.equal(_bits(s1), _bits(d.bwd(None))), "slabs: the recompute path (save = NULL) differs from the saved one"
+    s1 = twice(lambda: d.bwd(f1["save"]))
+    assert torch.equal(bits(s1), bits(d.bwd(None))), "slabs: the recompute path (save = NULL) differs from the saved one"
     check_slab_zeros(s1, d, c, cache["tok"])
     fwg = fw if not bool(flipped.any()) else R.front_fwd(P64, c["x"], L, ML, masks, scales, relu_gate=gate)
     bw = R.front_bwd(P64, fwg, c["dz"].double())
     gb = R.bwd_bounds(P64, fwg, fb, bw)
-    _judge(name, grads_of(s1, d), bw["G"], gb, R.NAMES)
+    judge(name, grads_of(s1, d), bw["G"], gb, R.NAMES)
     return d, c, s1, fwg, fb, bw
 
 
@@ -233,8 +186,8 @@ def test_over_long_input_rows_are_truncated(is_bf16):
     c2 = dict(c, x=c["x"][:, :17].contiguous(), ldx=17)
     d2 = Dev(c2)
     f, f2 = d.fwd(), d2.fwd()
-    assert torch.equal(_bits(f["z"]), _bits(f2["z"])) and torch.equal(_bits(f["save"]), _bits(f2["save"]))
-    assert torch.equal(_bits(s1), _bits(d2.bwd(f2["save"])))
+    assert torch.equal(bits(f["z"]), bits(f2["z"])) and torch.equal(bits(f["save"]), bits(f2["save"]))
+    assert torch.equal(bits(s1), bits(d2.bwd(f2["save"])))
 
 
 @pytest.mark.parametrize("is_bf16", [False, True], ids=["f32", "bf16"])
@@ -260,12 +213,12 @@ def test_slab_totals_in_float32_orders(is_bf16):
         return a
     per = (nb + 3) // 4
     q = [chain(g * per, min(nb, (g + 1) * per)) for g in range(4)]
-    assert torch.equal(_bits(seq.cpu()), _bits(chain(0, nb))), "afr_op_reduce is not the sum in slab order"
-    assert torch.equal(_bits(grp.cpu()), _bits(((q[0] + q[1]) + q[2]) + q[3])), "the grouped reduce is not the plan's order"
+    assert torch.equal(bits(seq.cpu()), bits(chain(0, nb))), "afr_op_reduce is not the sum in slab order"
+    assert torch.equal(bits(grp.cpu()), bits(((q[0] + q[1]) + q[2]) + q[3])), "the grouped reduce is not the plan's order"
     P64 = {k: t.double() for k, t in c["P"].items()}
     gb = R.bwd_bounds(P64, fwg, fb, bw, reduced=True)
     for nm, tot in (("afr_op_reduce", seq), ("grouped reduce", grp)):
-        _judge(nm, grads_of(tot.cpu().unsqueeze(0), d), bw["G"], gb, R.NAMES)
+        judge(nm, grads_of(tot.cpu().unsqueeze(0), d), bw["G"], gb, R.NAMES)
 
 
 @pytest.mark.parametrize("is_bf16", [False, True], ids=["f32", "bf16"])
@@ -278,8 +231,8 @@ def test_no_dropout_is_independent_of_seed_and_step(is_bf16):
     L = c["L"]
     for seed, step in ((42, 3), (7, 0), (2 ** 40 + 1, 2 ** 33)):
         tr = d.fwd(drop=_lib.AfrSheetDropout(seed, step, 0, 0.0, 0.0, 0.0))
-        assert torch.equal(_bits(tr["z"]), _bits(ev["z"]))
-        assert torch.equal(_bits(tr["save"][:, :L * 40]), _bits(ev["save"][:, :L * 40]))
+        assert torch.equal(bits(tr["z"]), bits(ev["z"]))
+        assert torch.equal(bits(tr["save"][:, :L * 40]), bits(ev["save"][:, :L * 40]))
         want = R.pack_bits(torch.ones(5, R.H, L, L, dtype=torch.uint8))
         assert torch.equal(split_save(tr["save"], L, True)["bits"], want)
 
@@ -290,8 +243,8 @@ def test_row_locality(is_bf16):
     c = R.make_case(300, 24, 24, "eval", is_bf16)
     big = Dev(c).fwd()
     one = Dev(dict(c, B=1, x=c["x"][299:300].contiguous(), dz=c["dz"][299:300].contiguous())).fwd()
-    assert torch.equal(_bits(big["z"][299]), _bits(one["z"][0]))
-    assert torch.equal(_bits(big["save"][299, :24 * 40]), _bits(one["save"][0, :24 * 40]))
+    assert torch.equal(bits(big["z"][299]), bits(one["z"][0]))
+    assert torch.equal(bits(big["save"][299, :24 * 40]), bits(one["save"][0, :24 * 40]))
 
 
 @pytest.mark.parametrize("is_bf16", [False, True], ids=["f32", "bf16"])
@@ -303,6 +256,6 @@ def test_out_of_range_codes_set_the_flag_and_are_clamped(is_bf16):
     db, dc = Dev(c, bad), Dev(c, clamped)
     fb_, fc_ = db.fwd(), dc.fwd()
     assert fb_["err"] & 1 and fc_["err"] == 0
-    assert torch.equal(_bits(fb_["z"]), _bits(fc_["z"])) and torch.equal(_bits(fb_["save"]), _bits(fc_["save"]))
+    assert torch.equal(bits(fb_["z"]), bits(fc_["z"])) and torch.equal(bits(fb_["save"]), bits(fc_["save"]))
     for save in (fc_["save"], None):
-        assert torch.equal(_bits(db.bwd(save)), _bits(dc.bwd(save)))
+        assert torch.equal(bits(db.bwd(save)), bits(dc.bwd(save)))

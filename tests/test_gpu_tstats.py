@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from . import tstats_ref as R
+from .op_harness import bands_kept, guarded_bytes
 from .util import MINI, ROOT, GlyphConfig, glyph_inputs, load, synth
 
 pytestmark = pytest.mark.gpu
@@ -86,15 +87,6 @@ def _table(finite_only=False):
     return buf, tuple(segs)
 
 
-def _guarded(nbytes, fill=0xFF):
-    buf = torch.full((nbytes + 512,), fill, dtype=torch.uint8, device="cuda")
-    return buf, buf[256:256 + nbytes]
-
-
-def _guards_ok(buf):
-    return bool((buf[:256] == 0xFF).all()) and bool((buf[-256:] == 0xFF).all())
-
-
 def _seg_array(segs):
     from ai_font_renderer_amd import _lib
     return (_lib.AfrTensorSeg * len(segs))(*[_lib.AfrTensorSeg(int(o), int(n)) for o, n in segs])
@@ -109,12 +101,12 @@ def op_stats(a_dev, segs, minus=None):
     tab = _seg_array(segs)
     need = int(lib.afr_op_tensor_stats_scratch_bytes(tab, len(segs)))
     assert need == 32 * sum(R.chunks_of(n, _chunk()) for _, n in segs)
-    obuf, out = _guarded(32 * len(segs))
-    sbuf, scr = _guarded(need)
+    obuf, out = guarded_bytes(32 * len(segs))
+    sbuf, scr = guarded_bytes(need)
     _lib.check(lib.afr_op_tensor_stats(ptr(a_dev), ptr(minus), tab, len(segs), ptr(out), ptr(scr), need, stream()))
     del tab                                                     # the host table is not read after the call returns
     torch.cuda.synchronize()
-    assert _guards_ok(obuf) and _guards_ok(sbuf)
+    assert all(bands_kept(obuf)) and all(bands_kept(sbuf))
     raw = out.view(torch.int32).view(len(segs), 8).cpu().numpy()
     assert not (raw == -1).any() and not bool((scr.view(torch.int32) == -1).any())
     return raw
@@ -217,8 +209,8 @@ def test_op_argument_errors_launch_nothing():
     lib = _lib.lib()
     EI, EU = _lib.AFR_EINVAL, _lib.AFR_EUNSUPPORTED
     a = dev(np.ones(1024, dtype=np.float32))
-    obuf, out = _guarded(32 * 4)
-    sbuf, scr = _guarded(32 * 4)
+    obuf, out = guarded_bytes(32 * 4)
+    sbuf, scr = guarded_bytes(32 * 4)
 
     def call(segs=((0, 100), (128, 300)), a_=a, minus=None, out_=out, scr_=scr, nbytes=None, nseg=None):
         tab = _seg_array(segs) if segs else None
@@ -244,7 +236,7 @@ def test_op_argument_errors_launch_nothing():
     assert bool((obuf == 0xFF).all()) and bool((sbuf == 0xFF).all())             # nothing was launched
     assert call() == 0                                                           # and the same buffers do take a good call
     torch.cuda.synchronize()
-    assert not bool((out[:64] == 0xFF).all()) and _guards_ok(obuf) and _guards_ok(sbuf)
+    assert not bool((out[:64] == 0xFF).all()) and all(bands_kept(obuf)) and all(bands_kept(sbuf))
 
 
 # ------------------------------------------------------------------------------------------------------ plan level
@@ -330,7 +322,7 @@ def test_plan_refuses_buffers_it_does_not_have_and_follows_the_ema_switch():
         bare.tensor_stats("exp_avg")
     assert e.value.code == _lib.AFR_ESTATE
     lib = _lib.lib()
-    obuf, out = _guarded(32 * len(lion.layout))
+    obuf, out = guarded_bytes(32 * len(lion.layout))
     assert lib.afr_tensor_stats(lion._plan, 9, None, ptr(out), stream()) == _lib.AFR_EINVAL
     assert lib.afr_tensor_stats(lion._plan, 0, None, None, stream()) == _lib.AFR_EINVAL
     assert lib.afr_tensor_stats(lion._plan, 0, None, C.c_void_p(out.data_ptr() + 8), stream()) == _lib.AFR_EINVAL

@@ -40,13 +40,18 @@ def bf16(t):
     return t.float().bfloat16().to(t.dtype)
 
 
+def rand(tid, shape, bound=1.0):
+    """the project's hashed uniform values in [-bound, bound) as a float32 tensor"""
+    return torch.from_numpy(synth.hash_uniform(tid, shape, bound))
+
+
 def ratio(got, ref, bound):
-    """largest |got - ref| / bound over the elements; an element whose bound is 0 must be met exactly (inf otherwise); NaN / inf in got
-    count as inf"""
+    """largest |got - ref| / bound over the elements (bound: a tensor that expands to them, or a number); an element whose bound is 0
+    must be met exactly (inf otherwise); NaN / inf in got count as inf"""
     err = (got.double() - ref).abs()
     if err.numel() == 0:
         return 0.0
-    bound = bound.double().expand_as(err)
+    bound = torch.as_tensor(bound, dtype=torch.float64).expand_as(err)
     inf = torch.full_like(err, float("inf"))
     r = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, inf, torch.zeros_like(err)))
     return float(torch.where(torch.isnan(err), inf, r).max())
