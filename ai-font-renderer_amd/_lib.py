@@ -94,6 +94,17 @@ class AfrLinearTail(C.Structure):
                 ("grad_scale", C.c_float), ("t", C.c_int64)]
 
 
+class AfrGlyphAtlas(C.Structure):
+    """The glyph atlas afr_op_compose_sheets blits from (include/afr.h afr_glyph_atlas); pointers are device pointers."""
+    _fields_ = [("cells", C.c_void_p), ("adv64", C.c_void_p), ("kern64", C.c_void_p), ("n_codes", C.c_int32), ("cell_h", C.c_int32),
+                ("cell_w", C.c_int32), ("origin_x", C.c_int32), ("origin_y", C.c_int32)]
+
+
+class AfrSheetGeometry(C.Structure):
+    """Sheet size, wrap width in 1/64 px and the baselines of the lines that are drawn (include/afr.h afr_sheet_geometry)."""
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("wrap_width64", C.c_int32), ("n_lines", C.c_int32), ("baseline", C.c_int32 * 16)]
+
+
 _vp, _i32, _i64, _f32, _u64, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64, C.c_size_t
 
 # name -> (restype, argtypes): every function include/afr.h declares
@@ -161,6 +172,8 @@ SIGNATURES = {
     "afr_op_tensor_stats_scratch_bytes": (_sz, [C.POINTER(AfrTensorSeg), _i32]),
     "afr_op_tensor_stats": (_i32, [_vp, _vp, C.POINTER(AfrTensorSeg), _i32, _vp, _vp, _sz, _vp]),
     "afr_op_f32_to_bf16": (_i32, [_vp, _vp, _i64, _vp]),
+    "afr_op_dataset_text": (_i32, [_i64, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp]),
+    "afr_op_compose_sheets": (_i32, [C.POINTER(AfrGlyphAtlas), C.POINTER(AfrSheetGeometry), _vp, _i32, _vp, _i64, _vp, _vp, _vp]),
     "afr_op_f32_to_fp8": (_i32, [_vp, _vp, _i64, _f32, _vp]),
     "afr_op_gemm_fp8": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
     "afr_pixel_bwd_blocks": (_i32, [C.c_longlong]),

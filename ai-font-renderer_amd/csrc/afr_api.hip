@@ -2313,6 +2313,55 @@ extern "C" int afr_op_f32_to_bf16(const float* src, void* dst, int64_t n, void* 
     HIPCHK(afr_launch_f32_to_bf16(src, (bf16_t*)dst, n, (hipStream_t)stream));
     return AFR_OK;
 }
+extern "C" int afr_op_dataset_text(int64_t first_seed, const int64_t* seed_rows, const int64_t* out_rows, int64_t n, int min_len, int max_len,
+                                   int64_t* codes, int ldx, int32_t* len, void* stream) {
+    if (!codes) return fail(AFR_EINVAL, "afr_op_dataset_text: codes is null");
+    if (n < 1) return fail(AFR_EINVAL, "afr_op_dataset_text: n = %lld, must be >= 1", (long long)n);
+    if (ldx < 1) return fail(AFR_EINVAL, "afr_op_dataset_text: ldx = %d, must be positive", ldx);
+    if (ldx > CMP_MAX_LDX) return fail(AFR_EUNSUPPORTED, "afr_op_dataset_text: ldx = %d, at most %d codes per row", ldx, CMP_MAX_LDX);
+    if (min_len < 1 || max_len < min_len || max_len > ldx)
+        return fail(AFR_EINVAL, "afr_op_dataset_text: text lengths %d..%d must satisfy 1 <= min_len <= max_len <= ldx = %d", min_len, max_len, ldx);
+    if (((uintptr_t)codes & 7) || ((uintptr_t)seed_rows & 7) || ((uintptr_t)out_rows & 7) || ((uintptr_t)len & 3))
+        return fail(AFR_EINVAL, "afr_op_dataset_text: codes, seed_rows and out_rows must be 8-byte aligned, len 4-byte");
+    DevGuard dg(device_of(codes));
+    HIPCHK(afr_launch_dataset_text(first_seed, seed_rows, out_rows, n, min_len, max_len, codes, ldx, len, (hipStream_t)stream));
+    return AFR_OK;
+}
+extern "C" int afr_op_compose_sheets(const afr_glyph_atlas* atlas, const afr_sheet_geometry* geo, const int64_t* codes, int ldx,
+                                     const int64_t* out_rows, int64_t n, uint8_t* out, uint32_t* err, void* stream) {
+    if (!atlas || !geo || !codes || !out) return fail(AFR_EINVAL, "afr_op_compose_sheets: atlas, geo, codes or out is null");
+    if (!atlas->cells || !atlas->adv64) return fail(AFR_EINVAL, "afr_op_compose_sheets: the atlas's cells or adv64 is null");
+    if (n < 1) return fail(AFR_EINVAL, "afr_op_compose_sheets: n = %lld, must be >= 1", (long long)n);
+    if (geo->n_lines < 1 || geo->n_lines > CMP_MAX_LINES)
+        return fail(AFR_EINVAL, "afr_op_compose_sheets: n_lines = %d, must be 1..%d", geo->n_lines, CMP_MAX_LINES);
+    if (atlas->n_codes < 1 || atlas->cell_h < 1 || atlas->cell_w < 1 || geo->height < 1 || geo->width < 1 || ldx < 1 || geo->wrap_width64 < 0)
+        return fail(AFR_EINVAL, "afr_op_compose_sheets: sizes must be positive (n_codes %d, cell %d x %d, sheet %d x %d, ldx %d, wrap_width64 %d)",
+                    atlas->n_codes, atlas->cell_h, atlas->cell_w, geo->height, geo->width, ldx, geo->wrap_width64);
+    if (atlas->origin_x < 0 || atlas->origin_x >= atlas->cell_w || atlas->origin_y < 0 || atlas->origin_y >= atlas->cell_h)
+        return fail(AFR_EINVAL, "afr_op_compose_sheets: origin (%d, %d) outside the %d x %d cell", atlas->origin_x, atlas->origin_y, atlas->cell_w,
+                    atlas->cell_h);
+    if (((uintptr_t)atlas->cells & 3) || ((uintptr_t)atlas->adv64 & 3) || ((uintptr_t)atlas->kern64 & 1) || ((uintptr_t)codes & 7) ||
+        ((uintptr_t)out_rows & 7) || ((uintptr_t)out & 7) || ((uintptr_t)err & 3))
+        return fail(AFR_EINVAL, "afr_op_compose_sheets: out, codes and out_rows must be 8-byte aligned, cells, adv64 and err 4-byte, kern64 2-byte");
+    if (ldx > CMP_MAX_LDX) return fail(AFR_EUNSUPPORTED, "afr_op_compose_sheets: ldx = %d, at most %d codes per row", ldx, CMP_MAX_LDX);
+    if (geo->width % 8) return fail(AFR_EUNSUPPORTED, "afr_op_compose_sheets: width must be a multiple of 8 (got %d)", geo->width);
+    if ((long long)geo->height * geo->width >= (1ll << 31))
+        return fail(AFR_EUNSUPPORTED, "afr_op_compose_sheets: a sheet of %d x %d pixels is 2 GiB or more", geo->height, geo->width);
+    if ((long long)atlas->n_codes * atlas->cell_h * atlas->cell_w > AFR_COMPOSE_LDS_BUDGET || geo->width / 8 > AFR_COMPOSE_LDS_BUDGET)
+        return fail(AFR_EUNSUPPORTED, "afr_op_compose_sheets: the atlas's cells (%d x %d x %d bytes) or a row of %d pixels alone pass the LDS budget of %d bytes",
+                    atlas->n_codes, atlas->cell_h, atlas->cell_w, geo->width, AFR_COMPOSE_LDS_BUDGET);
+    const long long lds = (long long)afr_compose_dynamic_lds(atlas->n_codes, atlas->cell_h, atlas->cell_w, geo->n_lines, geo->width) +
+                          (long long)afr_compose_static_lds();
+    if (lds > AFR_COMPOSE_LDS_BUDGET)
+        return fail(AFR_EUNSUPPORTED, "afr_op_compose_sheets: the atlas's cells (%d x %d x %d bytes), the glyph ranges and the layout need %lld bytes of LDS, the budget is %d",
+                    atlas->n_codes, atlas->cell_h, atlas->cell_w, lds, AFR_COMPOSE_LDS_BUDGET);
+    ComposeArgs a{atlas->cells, atlas->adv64, atlas->kern64, atlas->n_codes, atlas->cell_h, atlas->cell_w, atlas->origin_x, atlas->origin_y,
+                  geo->height, geo->width, geo->wrap_width64, geo->n_lines, {}, codes, ldx, out_rows, n, out, err};
+    for (int i = 0; i < CMP_MAX_LINES; ++i) a.baseline[i] = i < geo->n_lines ? geo->baseline[i] : 0;
+    DevGuard dg(device_of(out));
+    HIPCHK(afr_launch_compose_sheets(a, (hipStream_t)stream));
+    return AFR_OK;
+}
 extern "C" int afr_op_f32_to_fp8(const float* src, void* dst, int64_t n, float scale, void* stream) {
     if (!src || !dst || n < 0 || !(scale > 0.f)) return fail(AFR_EINVAL, "bad f32 -> fp8 arguments");
     DevGuard dg(device_of(dst));

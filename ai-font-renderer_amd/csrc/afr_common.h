@@ -409,6 +409,22 @@ hipError_t afr_launch_eval_rows(int act_dtype, int loss_kind, const void* u, con
 hipError_t afr_launch_dataset_rows(const int64_t* rows, int B, long long n_rows, const int64_t* x, const int64_t* font, int L, int Lc,
                                    int* ridx, int64_t* sx, int64_t* sfont, uint32_t* err_flag, hipStream_t s);
 hipError_t afr_launch_f32_to_bf16(const float* src, bf16_t* dst, long long n, hipStream_t s);
+// the device data set (dataset.hip): the LCG text source, one lane per sample, and the sheet composer over a glyph atlas, one
+// workgroup per sheet in a capped grid.  The composer keeps the atlas's cells and a glyph range per line and 8-pixel column block in dynamic LDS
+// (afr_compose_dynamic_lds) beside afr_compose_static_lds() bytes of its own; the caller holds the sum under AFR_COMPOSE_LDS_BUDGET (what a workgroup may ask for without opting in to more).
+constexpr int CMP_MAX_LDX = 256, CMP_MAX_LINES = 16, AFR_COMPOSE_MAX_BLOCKS = 2048, AFR_COMPOSE_LDS_BUDGET = 65536;
+struct ComposeArgs {
+    const uint8_t* cells; const int32_t* adv64; const int16_t* kern64;      // afr_glyph_atlas
+    int n_codes, cell_h, cell_w, origin_x, origin_y;
+    int height, width, wrap_width64, n_lines, baseline[CMP_MAX_LINES];      // afr_sheet_geometry
+    const int64_t* codes; int ldx; const int64_t* out_rows; long long n; uint8_t* out; uint32_t* err;
+};
+size_t afr_compose_static_lds();
+size_t afr_compose_dynamic_lds(int n_codes, int cell_h, int cell_w, int n_lines, int width);
+int afr_compose_blocks(long long n);
+hipError_t afr_launch_dataset_text(long long first_seed, const int64_t* seed_rows, const int64_t* out_rows, long long n, int min_len, int max_len,
+                                   int64_t* codes, int ldx, int32_t* len, hipStream_t s);
+hipError_t afr_launch_compose_sheets(const ComposeArgs& a, hipStream_t s);
 // the output head and its backward for a caller-side loss: clamp(u, 0, 1), or sigmoid(u) on a LOSS_BCE plan
 hipError_t afr_launch_clamp_bwd(int act_dtype, void* u_inout, const float* dy, long long n, hipStream_t s, int loss_kind = LOSS_MSE);
 hipError_t afr_launch_clamp_out(int act_dtype, const void* u, float* y, long long n, hipStream_t s, int loss_kind = LOSS_MSE);

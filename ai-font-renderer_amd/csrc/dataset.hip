@@ -1,0 +1,198 @@
+// dataset.hip -- the sheet data set composed on the device (afr_op_dataset_text, afr_op_compose_sheets; include/afr.h): the seeded
+// text source and the wrap / pen / blit of the reference's offline generator (generate_font.ts:164-206 and :64-142), which
+// datagen.py restates on the CPU with PIL.  Integer arithmetic throughout: a sheet is bit for bit what datagen.render_sheet draws.
+#include "afr_common.h"
+
+// ------------------------------------------------------------------------------------------- text
+// One lane per sample: synth.lcg_text in integers.  int(rnd() * k) is (state * k) >> 32 -- state / 2^32 * k is exact in a double.
+// A sample writes pos <= length <= max_len <= ldx codes and zero-fills the rest of its row: every element of the row, once.
+__global__ __launch_bounds__(256) void dataset_text_kernel(long long first_seed, const int64_t* __restrict__ seed_rows,
+                                                           const int64_t* __restrict__ out_rows, long long n, int min_len, int max_len,
+                                                           int64_t* __restrict__ codes, int ldx, int32_t* __restrict__ len) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    uint32_t state = (uint32_t)(uint64_t)(first_seed + (seed_rows ? seed_rows[j] : j));      // the update is mod 2^32 from the start
+    const long long row = out_rows ? out_rows[j] : j;
+    int64_t* dst = codes + row * (long long)ldx;
+    auto draw = [&](uint32_t k) -> int {
+        state = state * 1664525u + 1013904223u;
+        return (int)(((uint64_t)state * k) >> 32);
+    };
+    const int length = draw((uint32_t)(max_len - min_len + 1)) + min_len;
+    int remaining = length, pos = 0;
+    while (remaining > 0) {
+        const int wl = min(draw(10u) + 1, remaining);
+        for (int i = 0; i < wl; ++i) dst[pos++] = 65 + draw(26u);
+        remaining -= wl;
+        if (remaining > 0) { dst[pos++] = 32; --remaining; }
+    }
+    for (; pos < ldx; ++pos) dst[pos] = 0;
+    if (len) len[row] = length;
+}
+
+hipError_t afr_launch_dataset_text(long long first_seed, const int64_t* seed_rows, const int64_t* out_rows, long long n, int min_len, int max_len,
+                                   int64_t* codes, int ldx, int32_t* len, hipStream_t s) {
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(dataset_text_kernel, dim3(blocks), dim3(256), 0, s, first_seed, seed_rows, out_rows, n, min_len, max_len, codes, ldx, len);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------- compose
+// One workgroup of 256 threads per sheet, grid-stride.  The atlas's cells are copied into LDS once per workgroup (the paint phase
+// gathers single bytes from them at per-lane addresses, which LDS serves and a global load does not); advances and kerning are read
+// once per character from global memory (L2 resident).  Per sheet:
+//   text    lane t holds code t; the text ends at the first 0 (ballot), codes outside the atlas are dropped and flagged, the rest is
+//           packed in order (ballot + popcount prefix);
+//   layout  lane t fetches its character's advance and its kerning against the character before it; ONE lane then walks the text
+//           (<= 256 characters, LDS only) and restates datagen.wrap_text over prefix sums: a line is always a contiguous piece of
+//           the text, [ls, le), so width64(line + " " + word) is a difference of two prefix sums less the kerning into the line's
+//           first character; lane t then turns its character's pen into a pixel, (pen64 + 32) >> 6;
+//   index   lane e of n_lines * width / 8 scans one line once for the first and the last glyph whose cell overlaps one 8-pixel column
+//           block (pens need not be monotonic under kerning, so this is a range to scan, not the set);
+//   paint   output driven: a lane owns 8 consecutive pixels, starts them at coverage 0, composites every glyph of that range whose
+//           cell covers them in (line, character) order and stores the 8 bytes once.
+struct ComposeLds {
+    int code[CMP_MAX_LDX + 1], adv[CMP_MAX_LDX + 1], kern[CMP_MAX_LDX + 1], S[CMP_MAX_LDX + 1], px[CMP_MAX_LDX + 1];
+    int ls[CMP_MAX_LINES], le[CMP_MAX_LINES], base[CMP_MAX_LINES];
+    int wave_zero[4], wave_count[4];
+    int n_lines;
+};
+size_t afr_compose_static_lds() { return sizeof(ComposeLds); }
+// dynamic LDS: the cells, padded to whole words, then one (first, last) pair of shorts per line and 8-pixel column block
+static __host__ __device__ inline size_t compose_cell_lds(int n_codes, int cell_h, int cell_w) { return ((size_t)n_codes * cell_h * cell_w + 3) & ~(size_t)3; }
+size_t afr_compose_dynamic_lds(int n_codes, int cell_h, int cell_w, int n_lines, int width) {
+    return compose_cell_lds(n_codes, cell_h, cell_w) + (size_t)n_lines * (width / 8) * sizeof(short2);
+}
+
+__global__ __launch_bounds__(256) void compose_sheets_kernel(ComposeArgs a) {
+    extern __shared__ __align__(16) uint8_t s_cells[];                 // [n_codes][cell_h][cell_w], padded to whole words
+    __shared__ ComposeLds L;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int cell_bytes = a.n_codes * a.cell_h * a.cell_w;
+    {
+        const uint32_t* src = (const uint32_t*)a.cells;                // 4-byte aligned (checked by the caller)
+        uint32_t* dst = (uint32_t*)s_cells;
+        for (int i = t; i < cell_bytes / 4; i += 256) dst[i] = src[i];
+        for (int i = (cell_bytes & ~3) + t; i < cell_bytes; i += 256) s_cells[i] = a.cells[i];
+        if (t < CMP_MAX_LINES) L.base[t] = a.baseline[t];
+    }
+    const int W8 = a.width >> 3, chunks = a.height * W8;
+    short2* s_range = (short2*)(s_cells + compose_cell_lds(a.n_codes, a.cell_h, a.cell_w));      // [n_lines][W8]
+    for (long long j = blockIdx.x; j < a.n; j += gridDim.x) {
+        __syncthreads();                                               // the cells are in; the sheet before this one is painted
+        // ---- text
+        const long long c = t < a.ldx ? a.codes[j * a.ldx + t] : 0;
+        const unsigned long long zeros = __ballot(c == 0);
+        if (lane == 0) L.wave_zero[wave] = zeros ? wave * 64 + __ffsll((long long)zeros) - 1 : CMP_MAX_LDX;
+        __syncthreads();
+        const int len = min(min(L.wave_zero[0], L.wave_zero[1]), min(L.wave_zero[2], L.wave_zero[3]));
+        const bool in_range = c >= 0 && c < a.n_codes;
+        const bool valid = t < len && in_range;
+        const unsigned long long keep = __ballot(valid), bad = __ballot(t < len && !in_range);
+        if (lane == 0) {
+            L.wave_count[wave] = __popcll(keep);
+            if (bad && a.err) atomicOr(a.err, AFR_ERR_INDEX);
+        }
+        __syncthreads();
+        int before = 0, n_txt = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) before += L.wave_count[w];
+            n_txt += L.wave_count[w];
+        }
+        if (valid) L.code[before + __popcll(keep & ((1ull << lane) - 1ull))] = (int)c;
+        __syncthreads();
+        // ---- layout
+        if (t < n_txt) {
+            const int cc = L.code[t];
+            L.adv[t] = a.adv64[cc];
+            L.kern[t] = t > 0 && a.kern64 ? (int)a.kern64[(size_t)L.code[t - 1] * a.n_codes + cc] : 0;
+        }
+        __syncthreads();
+        if (t == 0) {
+            // S = width of text[0, pos) with every kerning; width64(text[s, e)) = S[e] - S[s] - kern[s] for e > s.
+            // current = text[ls, le); the word being read starts at ws.
+            int S = 0, ls = 0, le = 0, S_ls = 0, ws = 0, S_ws = 0, nl = 0;
+            for (int pos = 0; pos <= n_txt && nl < a.n_lines; ++pos) {
+                L.S[pos] = S;
+                const bool end = pos == n_txt;
+                const int step = end ? 0 : L.adv[pos] + L.kern[pos];
+                if (end || L.code[pos] == 32) {
+                    const bool cur = le > ls;
+                    const int cs = cur ? ls : ws, S_cs = cur ? S_ls : S_ws;
+                    const int width = pos > cs ? S - S_cs - L.kern[cs] : 0;
+                    if (width > a.wrap_width64 && cur) {
+                        L.ls[nl] = ls; L.le[nl] = le; ++nl;            // emit current; current = word
+                        ls = ws; S_ls = S_ws;
+                    } else {
+                        ls = cs; S_ls = S_cs;                          // current = candidate
+                    }
+                    le = pos;
+                    ws = pos + 1; S_ws = S + step;
+                }
+                S += step;
+            }
+            if (nl < a.n_lines && le > ls) { L.ls[nl] = ls; L.le[nl] = le; ++nl; }
+            L.n_lines = nl;
+        }
+        __syncthreads();
+        const int nl = L.n_lines;
+        if (t < n_txt) {
+            for (int i = 0; i < nl; ++i) {
+                const int ls = L.ls[i];
+                if (t >= ls && t < L.le[i]) {
+                    const int pen64 = L.S[t] + L.kern[t] - L.S[ls] - L.kern[ls];      // 0 for the line's first character
+                    L.px[t] = (pen64 + 32) >> 6;
+                }
+            }
+        }
+        __syncthreads();
+        // ---- index
+        for (int e = t; e < nl * W8; e += 256) {
+            const int i = e / W8, x0 = (e - i * W8) << 3, le = L.le[i];
+            int first = le, last = L.ls[i] - 1;
+            for (int g = L.ls[i]; g < le; ++g) {
+                const int rx0 = x0 - L.px[g] + a.origin_x;
+                if (rx0 > -8 && rx0 < a.cell_w) { first = min(first, g); last = g; }
+            }
+            s_range[e] = make_short2((short)first, (short)last);
+        }
+        __syncthreads();
+        // ---- paint
+        uint8_t* dst = a.out + (size_t)(a.out_rows ? a.out_rows[j] : j) * (size_t)chunks * 8u;
+        for (int q = t; q < chunks; q += 256) {
+            const int y = q / W8, x0 = (q - y * W8) << 3;
+            unsigned m[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+            for (int i = 0; i < nl; ++i) {
+                const int ry = y - L.base[i] + a.origin_y;
+                if ((unsigned)ry >= (unsigned)a.cell_h) continue;
+                const short2 range = s_range[i * W8 + (x0 >> 3)];
+                for (int g = range.x; g <= range.y; ++g) {
+                    const int rx0 = x0 - L.px[g] + a.origin_x;         // the cell column under the chunk's first pixel
+                    if (rx0 <= -8 || rx0 >= a.cell_w) continue;
+                    const uint8_t* row = s_cells + (L.code[g] * a.cell_h + ry) * a.cell_w;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        const int rx = rx0 + k;
+                        if ((unsigned)rx < (unsigned)a.cell_w) {
+                            const unsigned b = row[rx];
+                            m[k] = m[k] + b - (m[k] * b + 127u) / 255u;
+                        }
+                    }
+                }
+            }
+            uint2 v;
+            v.x = (255u - m[0]) | (255u - m[1]) << 8 | (255u - m[2]) << 16 | (255u - m[3]) << 24;
+            v.y = (255u - m[4]) | (255u - m[5]) << 8 | (255u - m[6]) << 16 | (255u - m[7]) << 24;
+            *(uint2*)(dst + (size_t)q * 8u) = v;
+        }
+    }
+}
+
+int afr_compose_blocks(long long n) { return (int)(n < AFR_COMPOSE_MAX_BLOCKS ? n : AFR_COMPOSE_MAX_BLOCKS); }
+
+hipError_t afr_launch_compose_sheets(const ComposeArgs& a, hipStream_t s) {
+    const size_t lds = afr_compose_dynamic_lds(a.n_codes, a.cell_h, a.cell_w, a.n_lines, a.width);
+    hipLaunchKernelGGL(compose_sheets_kernel, dim3(afr_compose_blocks(a.n)), dim3(256), lds, s, a);
+    return hipGetLastError();
+}

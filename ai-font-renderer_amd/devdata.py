@@ -1,0 +1,213 @@
+"""The sheet data set composed on the device (csrc/dataset.hip): what datagen.generate writes as BMP files and
+helpers.load_string_dataset_u8 reads back, produced directly in HBM by two kernels -- afr_op_dataset_text (the seeded LCG text
+source of generate_font.ts:164-206, one lane per sample) and afr_op_compose_sheets (wrap, pens and blit of generate_font.ts:64-142
+over a per-glyph atlas, one workgroup per sheet).
+
+A sheet is a handful of glyph bitmaps blitted at integer pen positions, so the only thing PIL is still needed for is the atlas:
+GlyphAtlas.from_font draws each printable ASCII glyph once and measures advances and pair kerning; the kernels reproduce
+datagen.render_sheet's bytes from it exactly (tests/test_compose_cpu.py, tests/test_gpu_compose.py).
+
+    atlas = GlyphAtlas.from_font("FiraCode-Retina.ttf").to("cuda")
+    ds = reference_dataset(150000, atlas)            # TensorDataset(int64 codes [N, L], uint8 sheets [N, 80, 240]) in HBM
+
+Two things the atlas cannot reproduce, both outside the data set's alphabet (A-Z and space):
+  * glyph substitution.  A font that replaces a run of characters by another glyph -- Fira Code's ligatures, "fi", "<>", "->" -- draws
+    that glyph under raqm layout; the atlas knows single characters and pairs' kerning only, so such text composes differently;
+  * the .notdef box.  Codes outside 32..126 have a blank cell and no advance here, where PIL draws the font's missing-glyph box.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+import torch.utils.data as data
+
+from . import _lib
+
+FIRST_CODE, N_CODES = 32, 127            # one cell per code 0..126; 0..31 stay blank with advance 0
+MIN_TEXT_LENGTH = 10                     # generate_font.ts:205
+MAX_LINES = 16                           # afr_sheet_geometry.baseline
+MAX_LDX = 256
+
+
+class GlyphAtlas:
+    """cells uint8 [n_codes, cell_h, cell_w] (coverage 0..255 = 255 - pixel, every cell cropped to the same box around the origin),
+    adv64 int32 [n_codes] (advance in 1/64 px), kern64 int16 [n_codes, n_codes] (pair adjustment in 1/64 px), origin_x / origin_y
+    (the cell's column / row that the pen and the baseline fall on).  Tensors; .to(device) moves them."""
+
+    def __init__(self, cells, adv64, kern64, origin_x, origin_y):
+        self.cells = torch.as_tensor(cells, dtype=torch.uint8).contiguous()
+        self.adv64 = torch.as_tensor(adv64, dtype=torch.int32).contiguous()
+        self.kern64 = None if kern64 is None else torch.as_tensor(kern64, dtype=torch.int16).contiguous()
+        self.origin_x, self.origin_y = int(origin_x), int(origin_y)
+        n = self.cells.shape[0]
+        if self.cells.dim() != 3 or tuple(self.adv64.shape) != (n,) or (self.kern64 is not None and tuple(self.kern64.shape) != (n, n)):
+            raise ValueError("atlas: cells [n, h, w], adv64 [n] and kern64 [n, n] do not match")
+
+    n_codes = property(lambda self: self.cells.shape[0])
+    cell_h = property(lambda self: self.cells.shape[1])
+    cell_w = property(lambda self: self.cells.shape[2])
+    device = property(lambda self: self.cells.device)
+
+    @classmethod
+    def from_font(cls, font_or_path=None, size=12):
+        """font_or_path: a TTF path, a PIL FreeTypeFont, or None for Pillow's built-in scalable font at `size` (what datagen.generate
+        uses without a font).  Every code 32..126 is drawn alone with anchor="ls" at an integer origin; the cells are the common
+        bounding box of all the ink (and of the origin)."""
+        from PIL import Image, ImageDraw, ImageFont
+        if font_or_path is None:
+            font = ImageFont.load_default(size)
+        elif isinstance(font_or_path, (str, bytes)) or hasattr(font_or_path, "__fspath__"):
+            font = ImageFont.truetype(font_or_path, size)
+        else:
+            font = font_or_path
+        span = 4 * max(int(getattr(font, "size", size)), 8)
+        ox = oy = span
+        cov = np.zeros((N_CODES, 2 * span, 2 * span), dtype=np.uint8)
+        for code in range(FIRST_CODE, N_CODES):
+            img = Image.new("L", (2 * span, 2 * span), 255)
+            ImageDraw.Draw(img).text((ox, oy), chr(code), fill=0, font=font, anchor="ls")
+            cov[code] = 255 - np.asarray(img, dtype=np.uint8)
+        ink = cov.max(0) > 0
+        ink[oy, ox] = True
+        ys, xs = np.nonzero(ink.any(1))[0], np.nonzero(ink.any(0))[0]
+        if ys[0] == 0 or xs[0] == 0 or ys[-1] == 2 * span - 1 or xs[-1] == 2 * span - 1:
+            raise ValueError("atlas: a glyph reaches the edge of the drawing canvas")
+        cells = cov[:, ys[0]:ys[-1] + 1, xs[0]:xs[-1] + 1]
+        adv = np.zeros(N_CODES, dtype=np.int64)
+        for code in range(FIRST_CODE, N_CODES):
+            adv[code] = round(font.getlength(chr(code)) * 64)
+        kern = np.zeros((N_CODES, N_CODES), dtype=np.int64)
+        for a in range(FIRST_CODE, N_CODES):
+            for b in range(FIRST_CODE, N_CODES):
+                kern[a, b] = round(font.getlength(chr(a) + chr(b)) * 64) - adv[a] - adv[b]
+        if np.abs(kern).max() > 32767:
+            raise ValueError("atlas: a kerning pair does not fit 16 bits")
+        return cls(cells, adv.astype(np.int32), kern.astype(np.int16), ox - xs[0], oy - ys[0])
+
+    def to(self, device):
+        return GlyphAtlas(self.cells.to(device), self.adv64.to(device), None if self.kern64 is None else self.kern64.to(device),
+                          self.origin_x, self.origin_y)
+
+    def arrays(self):
+        """The atlas as numpy arrays by field name (what save writes)."""
+        out = dict(cells=self.cells.cpu().numpy(), adv64=self.adv64.cpu().numpy(), origin_x=np.int32(self.origin_x),
+                   origin_y=np.int32(self.origin_y))
+        if self.kern64 is not None:
+            out["kern64"] = self.kern64.cpu().numpy()
+        return out
+
+    def save(self, path):
+        np.savez_compressed(path, **self.arrays())
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            return cls(z["cells"], z["adv64"], z["kern64"] if "kern64" in z.files else None, int(z["origin_x"]), int(z["origin_y"]))
+
+    def _struct(self):
+        return _lib.AfrGlyphAtlas(self.cells.data_ptr(), self.adv64.data_ptr(), None if self.kern64 is None else self.kern64.data_ptr(),
+                                  self.n_codes, self.cell_h, self.cell_w, self.origin_x, self.origin_y)
+
+
+def sheet_geometry(height=80, width=240, line_height=14.4, atlas=None):
+    """afr_sheet_geometry of a sheet: wrap at the sheet's width, baseline of line i at floor((i + 1) * line_height + 0.5)
+    (generate_font.ts:125-130, rounded the way the rasteriser places a fractional baseline), and every line whose cell still touches
+    the sheet -- its top row, baseline - origin_y, lies above the bottom edge.  Without an atlas two line heights stand in for
+    origin_y, which may add a line nothing is drawn from."""
+    reach = atlas.origin_y if atlas is not None else int(math.ceil(2 * line_height))
+    base = []
+    while len(base) < MAX_LINES:
+        b = int(math.floor((len(base) + 1) * line_height + 0.5))
+        if b - reach >= height:
+            break
+        base.append(b)
+    if not base:
+        raise ValueError(f"sheet of height {height}: no line touches it")
+    g = _lib.AfrSheetGeometry(int(height), int(width), int(width) * 64, len(base))
+    for i, b in enumerate(base):
+        g.baseline[i] = b
+    return g
+
+
+def _stream(device):
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _rows(t, n, device, what):
+    if t is None:
+        return None
+    t = torch.as_tensor(t).to(device=device, dtype=torch.int64).contiguous().reshape(-1)
+    if n is not None and t.numel() != n:
+        raise ValueError(f"{what}: {t.numel()} entries for {n} samples")
+    return t
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def generate_codes(n, first_seed=42, max_length=100, device=None, out=None, rows=None, seed_rows=None, lens=None):
+    """afr_op_dataset_text: the texts of synth.lcg_text(first_seed + seed, 10, max_length) as zero-padded int64 codes.  Sample j of n
+    takes seed seed_rows[j] (default j) and goes to row rows[j] (default j) of out -- int64 [N, L >= max_length], default a new
+    [n, max_length] -- and of lens (int32 [N], optional with out).  Returns (out, lens)."""
+    if out is None:
+        if rows is not None:
+            raise ValueError("rows needs the buffer they are rows of (out)")
+        if device is None:
+            raise ValueError("generate_codes needs a device or an out tensor")
+        out = torch.empty((n, max_length), dtype=torch.int64, device=device)
+        lens = torch.empty(n, dtype=torch.int32, device=device)
+    device = out.device
+    if out.dtype != torch.int64 or out.dim() != 2 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous int64 [N, L] tensor")
+    if lens is not None and (lens.dtype != torch.int32 or lens.device != device or lens.numel() != out.shape[0] or not lens.is_contiguous()):
+        raise ValueError("lens must be a contiguous int32 [N] tensor beside out")
+    rows, seed_rows = _rows(rows, n, device, "rows"), _rows(seed_rows, n, device, "seed_rows")
+    if rows is None and n > out.shape[0]:
+        raise ValueError(f"{n} samples do not fit the {out.shape[0]} rows of out")
+    if rows is not None and n and (int(rows.min()) < 0 or int(rows.max()) >= out.shape[0]):
+        raise IndexError("rows outside out")
+    with torch.cuda.device(device):
+        _lib.check(_lib.lib().afr_op_dataset_text(int(first_seed), _ptr(seed_rows), _ptr(rows), n, MIN_TEXT_LENGTH, int(max_length),
+                                                   _ptr(out), out.shape[1], _ptr(lens), _stream(device)))
+    return out, lens
+
+
+def compose_sheets(atlas, codes, height=80, width=240, out=None, rows=None, line_height=14.4):
+    """afr_op_compose_sheets: uint8 [n, height, width] sheets of the int64 [n, L] codes, bit for bit datagen.render_sheet's for text the
+    font does not substitute glyphs in.  Sample j goes to row rows[j] (default j) of out (uint8 [N, height, width], default new).  A
+    code outside the atlas is an IndexError (it is skipped on the device and flagged; reading the flag waits for the launch)."""
+    device = atlas.device
+    codes = codes.to(device=device, dtype=torch.int64).contiguous()
+    if codes.dim() != 2:
+        raise ValueError("codes must be int64 [n, L]")
+    n = codes.shape[0]
+    if out is None:
+        if rows is not None:
+            raise ValueError("rows needs the buffer they are rows of (out)")
+        out = torch.empty((n, height, width), dtype=torch.uint8, device=device)
+    if out.dtype != torch.uint8 or out.device != device or not out.is_contiguous() or tuple(out.shape[1:]) != (height, width):
+        raise ValueError(f"out must be a contiguous uint8 [N, {height}, {width}] tensor on {device}")
+    rows = _rows(rows, n, device, "rows")
+    if rows is None and n > out.shape[0]:
+        raise ValueError(f"{n} samples do not fit the {out.shape[0]} rows of out")
+    if rows is not None and n and (int(rows.min()) < 0 or int(rows.max()) >= out.shape[0]):
+        raise IndexError("rows outside out")
+    a, g = atlas._struct(), sheet_geometry(height, width, line_height, atlas)
+    with torch.cuda.device(device):
+        err = torch.zeros(1, dtype=torch.int32, device=device)
+        _lib.check(_lib.lib().afr_op_compose_sheets(C.byref(a), C.byref(g), _ptr(codes), codes.shape[1], _ptr(rows), n, _ptr(out), _ptr(err),
+                                                     _stream(device)))
+        if int(err) & 1:
+            raise IndexError(f"a code outside the atlas's 0..{atlas.n_codes - 1}")
+    return out
+
+
+def reference_dataset(n, atlas, first_seed=42, max_length=100, height=80, width=240):
+    """TensorDataset(int64 [n, L] codes, uint8 [n, height, width] sheets) on the atlas's device: the tensors
+    helpers.load_string_dataset_u8 returns for the folder datagen.generate(out_dir, n, font, first_seed) writes -- L is the longest
+    text's length, as there."""
+    codes, lens = generate_codes(n, first_seed, max_length, device=atlas.device)
+    codes = codes[:, :int(lens.max())].contiguous()
+    return data.TensorDataset(codes, compose_sheets(atlas, codes, height, width))

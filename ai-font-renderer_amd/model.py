@@ -41,7 +41,14 @@ What is deliberately different from the reference, and why:
     fc_output.weight zero).  The gradients are those of a probe: one forward + backward on rank 0's shard of the epoch's first
     training batch after the validation pass, with a dropout step of its own, no optimizer step, and its loss discarded; the step
     size comes from a snapshot of the weights taken before the epoch's last training batch.  Neither changes the run: every artefact
-    and every other line is what it is without the variable.  Unset: nothing changes.
+    and every other line is what it is without the variable.  Unset: nothing changes;
+  * AFR_DEVICE_DATA=<font file> or AFR_DEVICE_DATA=default takes the data set from devdata.reference_dataset instead of train_input/:
+    the NUM_SAMPLES texts and their sheets are produced on the device from a glyph atlas of that font (default: Pillow's built-in
+    font, as datagen.generate without one), byte for byte the tensors the folder datagen.generate writes would load as.  Every rank
+    composes the same bytes; nothing is read from disk and nothing is broadcast.  Unset: the reference's folder;
+  * AFR_FRESH_DATA=1 (needs AFR_DEVICE_DATA) rewrites the training rows in place before every epoch e >= 1: row r gets the text of seed
+    42 + e * N + r (texts as long as the bound rows are wide, MAX_CHARS_PER_SHEET for the full data set) and its sheet.  The validation
+    rows never change and epoch 0 is the run without the variable.  Unset: the data set is fixed, as the reference's.
 """
 import contextlib
 import datetime
@@ -122,6 +129,23 @@ def _tensor_report_from_env():
 
 
 TENSOR_REPORT = _tensor_report_from_env()     # likewise read at import
+
+
+def _device_data_from_env():
+    """(AFR_DEVICE_DATA, AFR_FRESH_DATA) -> (None | "default" | the path of a font file, bool).  A font file that is not there, a
+    fresh-data value other than 1, or fresh data without device data is a ValueError."""
+    spec, fresh = os.environ.get("AFR_DEVICE_DATA", "").strip(), os.environ.get("AFR_FRESH_DATA", "").strip()
+    if spec and spec != "default" and not os.path.isfile(spec):
+        raise ValueError(f"AFR_DEVICE_DATA must be a font file or 'default' (Pillow's built-in font), got {spec!r}")
+    if fresh not in ("", "1"):
+        raise ValueError(f"AFR_FRESH_DATA must be 1 (new training rows every epoch) or unset, got {fresh!r}")
+    if fresh and not spec:
+        raise ValueError("AFR_FRESH_DATA=1 needs AFR_DEVICE_DATA: only a data set composed on the device can be rewritten")
+    return spec or None, fresh == "1"
+
+
+DEVICE_DATA, FRESH_DATA = _device_data_from_env()     # likewise read at import
+DATA_FIRST_SEED = 42                                  # sample i of the data set is the text of seed i + 42 (generate_font.ts:204)
 
 
 def _tensor_report_lines(p, g, d):
@@ -548,9 +572,22 @@ def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, wor
     return avg_train_loss, avg_val_loss
 
 
-def train_attention_model(model, dataset, batch_size):
+def _fresh_rows(atlas, n):
+    """AFR_FRESH_DATA: refresh(epoch, rows, inputs, targets) rewrites rows `rows` of the bound codes and sheets in place, on the current
+    stream: row r becomes the text of seed DATA_FIRST_SEED + epoch * n + r, as long as a row of inputs is wide at the most, and its sheet."""
+    from . import devdata
+
+    def refresh(epoch, rows, inputs, targets):
+        rows = rows.to(device)
+        devdata.generate_codes(rows.numel(), DATA_FIRST_SEED, max_length=inputs.shape[1], out=inputs, rows=rows, seed_rows=epoch * n + rows)
+        devdata.compose_sheets(atlas, inputs.index_select(0, rows), targets.shape[1], targets.shape[2], out=targets, rows=rows)
+    return refresh
+
+
+def train_attention_model(model, dataset, batch_size, refresh=None):
     """Reference model.py:209-384: config.txt, 80/20 split, AdamW + ReduceLROnPlateau + early stopping, progress
-    prints and test-string dumps every 5 epochs, training_results.txt.  Returns the model."""
+    prints and test-string dumps every 5 epochs, training_results.txt.  Returns the model.  refresh (AFR_FRESH_DATA, _fresh_rows): called
+    before every epoch >= 1 with the training rows of the split and the bound tensors, which it rewrites in place."""
     from .parallel import DataParallelStepper
     dist, world, rank = _dist()
     eng = model.engine
@@ -577,6 +614,10 @@ def train_attention_model(model, dataset, batch_size):
                 f.write(f"val_report = {VAL_REPORT}\n")
             if TENSOR_REPORT:                   # likewise
                 f.write("tensor_report = 1\n")
+            if DEVICE_DATA:                     # likewise
+                f.write(f"device_data = {DEVICE_DATA}\n")
+            if refresh is not None:             # likewise
+                f.write("fresh_data = 1\n")
 
     order = _EpochOrder(len(dataset))
     print(f"Dataset split: {order.train_size} training samples, {order.val_size} validation samples")
@@ -607,6 +648,8 @@ def train_attention_model(model, dataset, batch_size):
         lr = lr_holder.param_groups[0]["lr"]
         report = _ValReport(VAL_REPORT, device, bitmaps=epoch % 5 == 0) if VAL_REPORT else None
         treport = _TensorReport(model) if TENSOR_REPORT and rank == 0 and epoch % 5 == 0 else None
+        if refresh is not None and epoch >= 1:
+            refresh(epoch, order.train_idx, inputs, targets)
         avg_train_loss, avg_val_loss = _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True, report=report,
                                                   treport=treport)
 
@@ -666,14 +709,23 @@ def train_attention_model(model, dataset, batch_size):
 def train_string_renderer():
     """Reference model.py:389-421."""
     print("Creating sheet dataset...")
-    dataset = load_string_dataset(data_dir="train_input", num_samples=NUM_SAMPLES, sheet_height=SHEET_HEIGHT,
-                                  sheet_width=SHEET_WIDTH)
+    refresh = None
+    if DEVICE_DATA:
+        from . import datagen, devdata
+        atlas = devdata.GlyphAtlas.from_font(None if DEVICE_DATA == "default" else DEVICE_DATA, datagen.FONT_SIZE).to(device)
+        print(f"Composing {NUM_SAMPLES} samples on {device} from a glyph atlas of {DEVICE_DATA}...")
+        dataset = devdata.reference_dataset(NUM_SAMPLES, atlas, DATA_FIRST_SEED, MAX_CHARS_PER_SHEET, SHEET_HEIGHT, SHEET_WIDTH)
+        if FRESH_DATA:
+            refresh = _fresh_rows(atlas, NUM_SAMPLES)
+    else:
+        dataset = load_string_dataset(data_dir="train_input", num_samples=NUM_SAMPLES, sheet_height=SHEET_HEIGHT,
+                                      sheet_width=SHEET_WIDTH)
     print("Training attention-based sheet renderer with reduced embedding dimensions (32) and learned positional encoding...")
     batch_size = 1024                                              # the reference's GPU batch size (model.py:408-409)
     model = AttentionFontRenderer(max_length=MAX_CHARS_PER_SHEET, max_batch=batch_size)
     model = model.to(device)
     print(f"Using batch size {batch_size}")
-    return train_attention_model(model, dataset, batch_size)
+    return train_attention_model(model, dataset, batch_size, refresh)
 
 
 def main(argv=None):

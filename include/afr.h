@@ -530,6 +530,41 @@ int afr_op_tensor_stats(const float* a, const float* minus /* or NULL */, const 
                         afr_tensor_stat* out, void* scratch, size_t scratch_bytes, void* stream);
 int afr_op_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);
 
+/* ---- the sheet data set composed on the device: the two launches that replace the reference's offline generator
+ * (generate_font.ts:64-142,164-206 -- the seeded text source, the word wrap, and fillText line by line into a BMP per sample).  Plain
+ * ops: no plan, nothing allocated.  Everything is integer arithmetic, so the outputs are bit-exact functions of their arguments.
+ *   dataset_text   one lane per sample j of n: the text of the reference's LCG source for seed first_seed + (seed_rows ? seed_rows[j]
+ *                  : j) -- state = state * 1664525 + 1013904223 mod 2^32, int(rnd() * k) = (state * k) >> 32; a length in min_len ..
+ *                  max_len, words of 1..10 letters A-Z separated by single spaces -- as int64 codes, zero-padded, in row r = out_rows ?
+ *                  out_rows[j] : j of codes [rows][ldx]; len[r] (int32, or NULL) = the text's length.  Every element of a written row
+ *                  is written once; other rows are not touched.
+ *   compose_sheets one workgroup per sample j of n: row j of codes int64 [n][ldx] drawn as black text on a white uint8 sheet
+ *                  [height][width] in row r = out_rows ? out_rows[j] : j of out (64-bit addressing; every byte of a written row is
+ *                  written once).  The text is the codes up to the first 0 (or ldx).  It is split at every code 32, empty words
+ *                  included, and wrapped greedily: a word joins the current line (with one space) unless the line is non-empty and
+ *                  the joined width exceeds wrap_width64, where width64(s) = sum of adv64[c] over s + sum of kern64[prev][c] over
+ *                  adjacent pairs, spaces included; so a leading empty word vanishes and a word wider than the sheet keeps its own
+ *                  line and is clipped.  On line i < n_lines (later lines are not drawn) the pen starts at 0; a character with a
+ *                  predecessor on the line first adds kern64[prev][c], is drawn at px = (pen64 + 32) >> 6, then adds adv64[c].
+ *                  Pixel (y, x) starts with coverage m = 0; every glyph whose cell covers it, in (line, character) order, adds
+ *                  b = cells[c][y - baseline[i] + origin_y][x - px + origin_x] as m = m + b - (m * b + 127) / 255; the byte stored is
+ *                  255 - m.  A code outside [0, n_codes) sets bit 0 of *err (device word, or NULL) and is skipped: no advance, no
+ *                  kerning, no ink, as if the text did not hold it.
+ * The atlas's cells are kept in LDS beside the layout's arrays and one glyph range per line and 8-pixel column block.
+ * Errors, before anything is launched: a required pointer NULL or
+ * misaligned (codes, the row vectors and out 8 bytes; cells, adv64, len, err 4; kern64 2), n < 1, min_len < 1, max_len < min_len,
+ * max_len > ldx, n_lines outside 1..16, a non-positive size, an origin outside the cell -> AFR_EINVAL; ldx > 256, width not a multiple
+ * of 8, a sheet of 2 GiB or more, cells + ranges + layout above the 64 KiB LDS budget -> AFR_EUNSUPPORTED. */
+typedef struct afr_glyph_atlas { const uint8_t* cells;   /* device [n_codes][cell_h][cell_w], coverage 0..255 = 255 - pixel */
+                                 const int32_t* adv64;   /* device [n_codes], advance in 1/64 px                          */
+                                 const int16_t* kern64;  /* device [n_codes][n_codes] or NULL                             */
+                                 int32_t n_codes, cell_h, cell_w, origin_x, origin_y; } afr_glyph_atlas;
+typedef struct afr_sheet_geometry { int32_t height, width, wrap_width64, n_lines; int32_t baseline[16]; } afr_sheet_geometry;
+int afr_op_dataset_text(int64_t first_seed, const int64_t* seed_rows, const int64_t* out_rows, int64_t n, int min_len, int max_len,
+                        int64_t* codes, int ldx, int32_t* len /* or NULL */, void* stream);
+int afr_op_compose_sheets(const afr_glyph_atlas* atlas, const afr_sheet_geometry* geo, const int64_t* codes, int ldx,
+                          const int64_t* out_rows, int64_t n, uint8_t* out, uint32_t* err /* or NULL */, void* stream);
+
 /* ---- the token-wise kernels of the per-pixel-token transformer (AFR_KIND_PIXEL), one launch each, exactly as the plan issues
  * them.  One wave per token row: rows >= 1, d = 64 * heads <= 512 (the widths a plan can reach; AFR_EUNSUPPORTED otherwise),
  * C = context tokens per glyph, 1 or 2; act_dtype AFR_F32 or AFR_BF16 is the type T of the GEMM operands (ctx, add, n, q, kv, o,
