@@ -2327,39 +2327,72 @@ extern "C" int afr_op_dataset_text(int64_t first_seed, const int64_t* seed_rows,
     HIPCHK(afr_launch_dataset_text(first_seed, seed_rows, out_rows, n, min_len, max_len, codes, ldx, len, (hipStream_t)stream));
     return AFR_OK;
 }
-extern "C" int afr_op_compose_sheets(const afr_glyph_atlas* atlas, const afr_sheet_geometry* geo, const int64_t* codes, int ldx,
-                                     const int64_t* out_rows, int64_t n, uint8_t* out, uint32_t* err, void* stream) {
-    if (!atlas || !geo || !codes || !out) return fail(AFR_EINVAL, "afr_op_compose_sheets: atlas, geo, codes or out is null");
-    if (!atlas->cells || !atlas->adv64) return fail(AFR_EINVAL, "afr_op_compose_sheets: the atlas's cells or adv64 is null");
-    if (n < 1) return fail(AFR_EINVAL, "afr_op_compose_sheets: n = %lld, must be >= 1", (long long)n);
+// What afr_op_compose_sheets and afr_op_sheet_char_errors refuse alike: `dense` is the sheet-shaped buffer (out / pred), `rows` the row
+// vector, lds_bytes the kernel's whole LDS need.  -> AFR_OK or the failure, already recorded.
+static int sheet_args_check(const char* who, const char* dense_name, const afr_glyph_atlas* atlas, const afr_sheet_geometry* geo,
+                            const int64_t* codes, int ldx, const int64_t* rows, int64_t n, const void* dense, const uint32_t* err,
+                            bool lds_extra) {
+    if (!atlas || !geo || !codes || !dense) return fail(AFR_EINVAL, "%s: atlas, geo, codes or %s is null", who, dense_name);
+    if (!atlas->cells || !atlas->adv64) return fail(AFR_EINVAL, "%s: the atlas's cells or adv64 is null", who);
+    if (n < 1) return fail(AFR_EINVAL, "%s: n = %lld, must be >= 1", who, (long long)n);
     if (geo->n_lines < 1 || geo->n_lines > CMP_MAX_LINES)
-        return fail(AFR_EINVAL, "afr_op_compose_sheets: n_lines = %d, must be 1..%d", geo->n_lines, CMP_MAX_LINES);
+        return fail(AFR_EINVAL, "%s: n_lines = %d, must be 1..%d", who, geo->n_lines, CMP_MAX_LINES);
     if (atlas->n_codes < 1 || atlas->cell_h < 1 || atlas->cell_w < 1 || geo->height < 1 || geo->width < 1 || ldx < 1 || geo->wrap_width64 < 0)
-        return fail(AFR_EINVAL, "afr_op_compose_sheets: sizes must be positive (n_codes %d, cell %d x %d, sheet %d x %d, ldx %d, wrap_width64 %d)",
+        return fail(AFR_EINVAL, "%s: sizes must be positive (n_codes %d, cell %d x %d, sheet %d x %d, ldx %d, wrap_width64 %d)", who,
                     atlas->n_codes, atlas->cell_h, atlas->cell_w, geo->height, geo->width, ldx, geo->wrap_width64);
     if (atlas->origin_x < 0 || atlas->origin_x >= atlas->cell_w || atlas->origin_y < 0 || atlas->origin_y >= atlas->cell_h)
-        return fail(AFR_EINVAL, "afr_op_compose_sheets: origin (%d, %d) outside the %d x %d cell", atlas->origin_x, atlas->origin_y, atlas->cell_w,
+        return fail(AFR_EINVAL, "%s: origin (%d, %d) outside the %d x %d cell", who, atlas->origin_x, atlas->origin_y, atlas->cell_w,
                     atlas->cell_h);
     if (((uintptr_t)atlas->cells & 3) || ((uintptr_t)atlas->adv64 & 3) || ((uintptr_t)atlas->kern64 & 1) || ((uintptr_t)codes & 7) ||
-        ((uintptr_t)out_rows & 7) || ((uintptr_t)out & 7) || ((uintptr_t)err & 3))
-        return fail(AFR_EINVAL, "afr_op_compose_sheets: out, codes and out_rows must be 8-byte aligned, cells, adv64 and err 4-byte, kern64 2-byte");
-    if (ldx > CMP_MAX_LDX) return fail(AFR_EUNSUPPORTED, "afr_op_compose_sheets: ldx = %d, at most %d codes per row", ldx, CMP_MAX_LDX);
-    if (geo->width % 8) return fail(AFR_EUNSUPPORTED, "afr_op_compose_sheets: width must be a multiple of 8 (got %d)", geo->width);
+        ((uintptr_t)rows & 7) || ((uintptr_t)dense & 7) || ((uintptr_t)err & 3))
+        return fail(AFR_EINVAL, "%s: %s, codes and the row vector must be 8-byte aligned, cells, adv64 and err 4-byte, kern64 2-byte", who, dense_name);
+    if (ldx > CMP_MAX_LDX) return fail(AFR_EUNSUPPORTED, "%s: ldx = %d, at most %d codes per row", who, ldx, CMP_MAX_LDX);
+    if (geo->width % 8) return fail(AFR_EUNSUPPORTED, "%s: width must be a multiple of 8 (got %d)", who, geo->width);
     if ((long long)geo->height * geo->width >= (1ll << 31))
-        return fail(AFR_EUNSUPPORTED, "afr_op_compose_sheets: a sheet of %d x %d pixels is 2 GiB or more", geo->height, geo->width);
+        return fail(AFR_EUNSUPPORTED, "%s: a sheet of %d x %d pixels is 2 GiB or more", who, geo->height, geo->width);
     if ((long long)atlas->n_codes * atlas->cell_h * atlas->cell_w > AFR_COMPOSE_LDS_BUDGET || geo->width / 8 > AFR_COMPOSE_LDS_BUDGET)
-        return fail(AFR_EUNSUPPORTED, "afr_op_compose_sheets: the atlas's cells (%d x %d x %d bytes) or a row of %d pixels alone pass the LDS budget of %d bytes",
+        return fail(AFR_EUNSUPPORTED, "%s: the atlas's cells (%d x %d x %d bytes) or a row of %d pixels alone pass the LDS budget of %d bytes", who,
                     atlas->n_codes, atlas->cell_h, atlas->cell_w, geo->width, AFR_COMPOSE_LDS_BUDGET);
-    const long long lds = (long long)afr_compose_dynamic_lds(atlas->n_codes, atlas->cell_h, atlas->cell_w, geo->n_lines, geo->width) +
-                          (long long)afr_compose_static_lds();
+    const long long lds = lds_extra ? (long long)afr_charerr_dynamic_lds(atlas->n_codes, atlas->cell_h, atlas->cell_w, geo->n_lines, geo->width) +
+                                          (long long)afr_charerr_static_lds()
+                                    : (long long)afr_compose_dynamic_lds(atlas->n_codes, atlas->cell_h, atlas->cell_w, geo->n_lines, geo->width) +
+                                          (long long)afr_compose_static_lds();
     if (lds > AFR_COMPOSE_LDS_BUDGET)
-        return fail(AFR_EUNSUPPORTED, "afr_op_compose_sheets: the atlas's cells (%d x %d x %d bytes), the glyph ranges and the layout need %lld bytes of LDS, the budget is %d",
-                    atlas->n_codes, atlas->cell_h, atlas->cell_w, lds, AFR_COMPOSE_LDS_BUDGET);
+        return fail(AFR_EUNSUPPORTED, "%s: the atlas's cells (%d x %d x %d bytes), the glyph ranges and the layout%s need %lld bytes of LDS, the budget is %d",
+                    who, atlas->n_codes, atlas->cell_h, atlas->cell_w, lds_extra ? ", the position records and the code counters" : "", lds,
+                    AFR_COMPOSE_LDS_BUDGET);
+    return AFR_OK;
+}
+static ComposeArgs compose_args(const afr_glyph_atlas* atlas, const afr_sheet_geometry* geo, const int64_t* codes, int ldx, const int64_t* rows,
+                                int64_t n, uint8_t* out, uint32_t* err) {
     ComposeArgs a{atlas->cells, atlas->adv64, atlas->kern64, atlas->n_codes, atlas->cell_h, atlas->cell_w, atlas->origin_x, atlas->origin_y,
-                  geo->height, geo->width, geo->wrap_width64, geo->n_lines, {}, codes, ldx, out_rows, n, out, err};
+                  geo->height, geo->width, geo->wrap_width64, geo->n_lines, {}, codes, ldx, rows, n, out, err};
     for (int i = 0; i < CMP_MAX_LINES; ++i) a.baseline[i] = i < geo->n_lines ? geo->baseline[i] : 0;
+    return a;
+}
+extern "C" int afr_op_compose_sheets(const afr_glyph_atlas* atlas, const afr_sheet_geometry* geo, const int64_t* codes, int ldx,
+                                     const int64_t* out_rows, int64_t n, uint8_t* out, uint32_t* err, void* stream) {
+    if (const int rc = sheet_args_check("afr_op_compose_sheets", "out", atlas, geo, codes, ldx, out_rows, n, out, err, false)) return rc;
+    const ComposeArgs a = compose_args(atlas, geo, codes, ldx, out_rows, n, out, err);
     DevGuard dg(device_of(out));
     HIPCHK(afr_launch_compose_sheets(a, (hipStream_t)stream));
+    return AFR_OK;
+}
+extern "C" int afr_op_sheet_char_errors(const afr_glyph_atlas* atlas, const afr_sheet_geometry* geo, const int64_t* codes, int ldx,
+                                        const int64_t* code_rows, int64_t n, const uint8_t* pred, uint32_t* per_pos, uint64_t* by_code,
+                                        uint32_t* err, void* stream) {
+    const char* who = "afr_op_sheet_char_errors";
+    if (const int rc = sheet_args_check(who, "pred", atlas, geo, codes, ldx, code_rows, n, pred, err, true)) return rc;
+    // a record's sumsq is a uint32: 255^2 * pixels must fit
+    if ((long long)geo->height * geo->width > 66051)
+        return fail(AFR_EUNSUPPORTED, "%s: a sheet of %d x %d pixels: 65025 * pixels must fit 32 bits, at most 66051 pixels", who, geo->height,
+                    geo->width);
+    if (!per_pos && !by_code) return fail(AFR_EINVAL, "%s: per_pos and by_code are both NULL", who);
+    if (((uintptr_t)per_pos & 15) || ((uintptr_t)by_code & 7))
+        return fail(AFR_EINVAL, "%s: per_pos must be 16-byte aligned, by_code 8-byte", who);
+    const CharErrArgs a{compose_args(atlas, geo, codes, ldx, code_rows, n, nullptr, err), pred, per_pos, (unsigned long long*)by_code};
+    DevGuard dg(device_of(pred));
+    HIPCHK(afr_launch_sheet_char_errors(a, (hipStream_t)stream));
     return AFR_OK;
 }
 extern "C" int afr_op_f32_to_fp8(const float* src, void* dst, int64_t n, float scale, void* stream) {

@@ -425,6 +425,15 @@ int afr_compose_blocks(long long n);
 hipError_t afr_launch_dataset_text(long long first_seed, const int64_t* seed_rows, const int64_t* out_rows, long long n, int min_len, int max_len,
                                    int64_t* codes, int ldx, int32_t* len, hipStream_t s);
 hipError_t afr_launch_compose_sheets(const ComposeArgs& a, hipStream_t s);
+// afr_op_sheet_char_errors: compose's arguments (c.out unused, c.out_rows = the rows of codes the samples read) beside the dense
+// prediction and the two outputs.  LDS as compose's, plus the position records and one 64-bit counter set per code.
+struct CharErrArgs {
+    ComposeArgs c;
+    const uint8_t* pred; uint32_t* per_pos; unsigned long long* by_code;
+};
+size_t afr_charerr_static_lds();
+size_t afr_charerr_dynamic_lds(int n_codes, int cell_h, int cell_w, int n_lines, int width);
+hipError_t afr_launch_sheet_char_errors(const CharErrArgs& a, hipStream_t s);
 // the output head and its backward for a caller-side loss: clamp(u, 0, 1), or sigmoid(u) on a LOSS_BCE plan
 hipError_t afr_launch_clamp_bwd(int act_dtype, void* u_inout, const float* dy, long long n, hipStream_t s, int loss_kind = LOSS_MSE);
 hipError_t afr_launch_clamp_out(int act_dtype, const void* u, float* y, long long n, hipStream_t s, int loss_kind = LOSS_MSE);

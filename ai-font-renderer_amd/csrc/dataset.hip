@@ -1,6 +1,7 @@
 // dataset.hip -- the sheet data set composed on the device (afr_op_dataset_text, afr_op_compose_sheets; include/afr.h): the seeded
 // text source and the wrap / pen / blit of the reference's offline generator (generate_font.ts:164-206 and :64-142), which
 // datagen.py restates on the CPU with PIL.  Integer arithmetic throughout: a sheet is bit for bit what datagen.render_sheet draws.
+// afr_op_sheet_char_errors runs the same layout to attribute a prediction's error to the characters that own the pixels.
 #include "afr_common.h"
 
 // ------------------------------------------------------------------------------------------- text
@@ -64,100 +65,120 @@ size_t afr_compose_dynamic_lds(int n_codes, int cell_h, int cell_w, int n_lines,
     return compose_cell_lds(n_codes, cell_h, cell_w) + (size_t)n_lines * (width / 8) * sizeof(short2);
 }
 
+// The text, layout and index phases of one sheet, for the 256 threads of a workgroup: row `row` of a.codes is read, packed into L.code
+// (and, with POS, every packed character's index in its row into s_pos), wrapped and penned, and s_range filled.  Returns the number of
+// lines drawn; `placed` is whether lane t's packed character stands on one of them.  Ends behind a barrier.
+template <bool POS>
+__device__ __forceinline__ int sheet_layout(const ComposeArgs& a, ComposeLds& L, int* s_pos, short2* s_range, long long row, int t, int lane,
+                                            int wave, int W8, bool& placed) {
+    // ---- text
+    const long long c = t < a.ldx ? a.codes[row * a.ldx + t] : 0;
+    const unsigned long long zeros = __ballot(c == 0);
+    if (lane == 0) L.wave_zero[wave] = zeros ? wave * 64 + __ffsll((long long)zeros) - 1 : CMP_MAX_LDX;
+    __syncthreads();
+    const int len = min(min(L.wave_zero[0], L.wave_zero[1]), min(L.wave_zero[2], L.wave_zero[3]));
+    const bool in_range = c >= 0 && c < a.n_codes;
+    const bool valid = t < len && in_range;
+    const unsigned long long keep = __ballot(valid), bad = __ballot(t < len && !in_range);
+    if (lane == 0) {
+        L.wave_count[wave] = __popcll(keep);
+        if (bad && a.err) atomicOr(a.err, AFR_ERR_INDEX);
+    }
+    __syncthreads();
+    int before = 0, n_txt = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        if (w < wave) before += L.wave_count[w];
+        n_txt += L.wave_count[w];
+    }
+    if (valid) {
+        const int g = before + __popcll(keep & ((1ull << lane) - 1ull));
+        L.code[g] = (int)c;
+        if (POS) s_pos[g] = t;
+    }
+    __syncthreads();
+    // ---- layout
+    if (t < n_txt) {
+        const int cc = L.code[t];
+        L.adv[t] = a.adv64[cc];
+        L.kern[t] = t > 0 && a.kern64 ? (int)a.kern64[(size_t)L.code[t - 1] * a.n_codes + cc] : 0;
+    }
+    __syncthreads();
+    if (t == 0) {
+        // S = width of text[0, pos) with every kerning; width64(text[s, e)) = S[e] - S[s] - kern[s] for e > s.
+        // current = text[ls, le); the word being read starts at ws.
+        int S = 0, ls = 0, le = 0, S_ls = 0, ws = 0, S_ws = 0, nl = 0;
+        for (int pos = 0; pos <= n_txt && nl < a.n_lines; ++pos) {
+            L.S[pos] = S;
+            const bool end = pos == n_txt;
+            const int step = end ? 0 : L.adv[pos] + L.kern[pos];
+            if (end || L.code[pos] == 32) {
+                const bool cur = le > ls;
+                const int cs = cur ? ls : ws, S_cs = cur ? S_ls : S_ws;
+                const int width = pos > cs ? S - S_cs - L.kern[cs] : 0;
+                if (width > a.wrap_width64 && cur) {
+                    L.ls[nl] = ls; L.le[nl] = le; ++nl;            // emit current; current = word
+                    ls = ws; S_ls = S_ws;
+                } else {
+                    ls = cs; S_ls = S_cs;                          // current = candidate
+                }
+                le = pos;
+                ws = pos + 1; S_ws = S + step;
+            }
+            S += step;
+        }
+        if (nl < a.n_lines && le > ls) { L.ls[nl] = ls; L.le[nl] = le; ++nl; }
+        L.n_lines = nl;
+    }
+    __syncthreads();
+    const int nl = L.n_lines;
+    placed = false;
+    if (t < n_txt) {
+        for (int i = 0; i < nl; ++i) {
+            const int ls = L.ls[i];
+            if (t >= ls && t < L.le[i]) {
+                const int pen64 = L.S[t] + L.kern[t] - L.S[ls] - L.kern[ls];      // 0 for the line's first character
+                L.px[t] = (pen64 + 32) >> 6;
+                placed = true;
+            }
+        }
+    }
+    __syncthreads();
+    // ---- index
+    for (int e = t; e < nl * W8; e += 256) {
+        const int i = e / W8, x0 = (e - i * W8) << 3, le = L.le[i];
+        int first = le, last = L.ls[i] - 1;
+        for (int g = L.ls[i]; g < le; ++g) {
+            const int rx0 = x0 - L.px[g] + a.origin_x;
+            if (rx0 > -8 && rx0 < a.cell_w) { first = min(first, g); last = g; }
+        }
+        s_range[e] = make_short2((short)first, (short)last);
+    }
+    __syncthreads();
+    return nl;
+}
+
+// the atlas's cells (and the baselines) into LDS, once per workgroup
+__device__ __forceinline__ void sheet_cells_to_lds(const ComposeArgs& a, ComposeLds& L, uint8_t* s_cells, int t) {
+    const int cell_bytes = a.n_codes * a.cell_h * a.cell_w;
+    const uint32_t* src = (const uint32_t*)a.cells;                    // 4-byte aligned (checked by the caller)
+    uint32_t* dst = (uint32_t*)s_cells;
+    for (int i = t; i < cell_bytes / 4; i += 256) dst[i] = src[i];
+    for (int i = (cell_bytes & ~3) + t; i < cell_bytes; i += 256) s_cells[i] = a.cells[i];
+    if (t < CMP_MAX_LINES) L.base[t] = a.baseline[t];
+}
+
 __global__ __launch_bounds__(256) void compose_sheets_kernel(ComposeArgs a) {
     extern __shared__ __align__(16) uint8_t s_cells[];                 // [n_codes][cell_h][cell_w], padded to whole words
     __shared__ ComposeLds L;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int cell_bytes = a.n_codes * a.cell_h * a.cell_w;
-    {
-        const uint32_t* src = (const uint32_t*)a.cells;                // 4-byte aligned (checked by the caller)
-        uint32_t* dst = (uint32_t*)s_cells;
-        for (int i = t; i < cell_bytes / 4; i += 256) dst[i] = src[i];
-        for (int i = (cell_bytes & ~3) + t; i < cell_bytes; i += 256) s_cells[i] = a.cells[i];
-        if (t < CMP_MAX_LINES) L.base[t] = a.baseline[t];
-    }
+    sheet_cells_to_lds(a, L, s_cells, t);
     const int W8 = a.width >> 3, chunks = a.height * W8;
     short2* s_range = (short2*)(s_cells + compose_cell_lds(a.n_codes, a.cell_h, a.cell_w));      // [n_lines][W8]
     for (long long j = blockIdx.x; j < a.n; j += gridDim.x) {
         __syncthreads();                                               // the cells are in; the sheet before this one is painted
-        // ---- text
-        const long long c = t < a.ldx ? a.codes[j * a.ldx + t] : 0;
-        const unsigned long long zeros = __ballot(c == 0);
-        if (lane == 0) L.wave_zero[wave] = zeros ? wave * 64 + __ffsll((long long)zeros) - 1 : CMP_MAX_LDX;
-        __syncthreads();
-        const int len = min(min(L.wave_zero[0], L.wave_zero[1]), min(L.wave_zero[2], L.wave_zero[3]));
-        const bool in_range = c >= 0 && c < a.n_codes;
-        const bool valid = t < len && in_range;
-        const unsigned long long keep = __ballot(valid), bad = __ballot(t < len && !in_range);
-        if (lane == 0) {
-            L.wave_count[wave] = __popcll(keep);
-            if (bad && a.err) atomicOr(a.err, AFR_ERR_INDEX);
-        }
-        __syncthreads();
-        int before = 0, n_txt = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            if (w < wave) before += L.wave_count[w];
-            n_txt += L.wave_count[w];
-        }
-        if (valid) L.code[before + __popcll(keep & ((1ull << lane) - 1ull))] = (int)c;
-        __syncthreads();
-        // ---- layout
-        if (t < n_txt) {
-            const int cc = L.code[t];
-            L.adv[t] = a.adv64[cc];
-            L.kern[t] = t > 0 && a.kern64 ? (int)a.kern64[(size_t)L.code[t - 1] * a.n_codes + cc] : 0;
-        }
-        __syncthreads();
-        if (t == 0) {
-            // S = width of text[0, pos) with every kerning; width64(text[s, e)) = S[e] - S[s] - kern[s] for e > s.
-            // current = text[ls, le); the word being read starts at ws.
-            int S = 0, ls = 0, le = 0, S_ls = 0, ws = 0, S_ws = 0, nl = 0;
-            for (int pos = 0; pos <= n_txt && nl < a.n_lines; ++pos) {
-                L.S[pos] = S;
-                const bool end = pos == n_txt;
-                const int step = end ? 0 : L.adv[pos] + L.kern[pos];
-                if (end || L.code[pos] == 32) {
-                    const bool cur = le > ls;
-                    const int cs = cur ? ls : ws, S_cs = cur ? S_ls : S_ws;
-                    const int width = pos > cs ? S - S_cs - L.kern[cs] : 0;
-                    if (width > a.wrap_width64 && cur) {
-                        L.ls[nl] = ls; L.le[nl] = le; ++nl;            // emit current; current = word
-                        ls = ws; S_ls = S_ws;
-                    } else {
-                        ls = cs; S_ls = S_cs;                          // current = candidate
-                    }
-                    le = pos;
-                    ws = pos + 1; S_ws = S + step;
-                }
-                S += step;
-            }
-            if (nl < a.n_lines && le > ls) { L.ls[nl] = ls; L.le[nl] = le; ++nl; }
-            L.n_lines = nl;
-        }
-        __syncthreads();
-        const int nl = L.n_lines;
-        if (t < n_txt) {
-            for (int i = 0; i < nl; ++i) {
-                const int ls = L.ls[i];
-                if (t >= ls && t < L.le[i]) {
-                    const int pen64 = L.S[t] + L.kern[t] - L.S[ls] - L.kern[ls];      // 0 for the line's first character
-                    L.px[t] = (pen64 + 32) >> 6;
-                }
-            }
-        }
-        __syncthreads();
-        // ---- index
-        for (int e = t; e < nl * W8; e += 256) {
-            const int i = e / W8, x0 = (e - i * W8) << 3, le = L.le[i];
-            int first = le, last = L.ls[i] - 1;
-            for (int g = L.ls[i]; g < le; ++g) {
-                const int rx0 = x0 - L.px[g] + a.origin_x;
-                if (rx0 > -8 && rx0 < a.cell_w) { first = min(first, g); last = g; }
-            }
-            s_range[e] = make_short2((short)first, (short)last);
-        }
-        __syncthreads();
+        bool placed;
+        const int nl = sheet_layout<false>(a, L, nullptr, s_range, j, t, lane, wave, W8, placed);
         // ---- paint
         uint8_t* dst = a.out + (size_t)(a.out_rows ? a.out_rows[j] : j) * (size_t)chunks * 8u;
         for (int q = t; q < chunks; q += 256) {
@@ -189,10 +210,141 @@ __global__ __launch_bounds__(256) void compose_sheets_kernel(ComposeArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------ char errors
+// afr_op_sheet_char_errors: compose's text, layout and index phases over the same LDS, then a paint phase that loads where compose
+// stores.  A lane recomputes the coverage m of its 8 pixels (the target is 255 - m, never read) and remembers per pixel the glyph with
+// the largest cell value b > 0, the earlier one on a tie: the pixel's owner.  The 8 prediction bytes come in one load.  Pixels without
+// an owner are summed in registers and across the wave; owned pixels go to the owner's record in LDS, indexed by the character's
+// position in its row of codes, one integer add per field and run of pixels with the same owner.  After the sheet the records are
+// added by code into 64-bit LDS counters that live as long as the workgroup (a 32-bit sumsq holds one sheet, not several), stored
+// once to per_pos and cleared; the counters go to by_code at the end, one global atomic per non-zero field.
+struct CharErrLds {
+    int pos[CMP_MAX_LDX + 1];
+    __align__(16) uint32_t acc[CMP_MAX_LDX + 1][4];                    // {pixels, sumsq, off2, wrong} by position; slot ldx = background
+};
+size_t afr_charerr_static_lds() { return sizeof(ComposeLds) + sizeof(CharErrLds); }
+static __host__ __device__ inline size_t charerr_by_lds(int n_codes) { return (size_t)(n_codes + 1) * 5 * sizeof(unsigned long long); }
+size_t afr_charerr_dynamic_lds(int n_codes, int cell_h, int cell_w, int n_lines, int width) {
+    return charerr_by_lds(n_codes) + afr_compose_dynamic_lds(n_codes, cell_h, cell_w, n_lines, width);
+}
+
+__device__ __forceinline__ void charerr_add(uint32_t* rec, uint32_t pixels, uint32_t sumsq, uint32_t off2, uint32_t wrong) {
+    atomicAdd(&rec[0], pixels);
+    if (sumsq) atomicAdd(&rec[1], sumsq);
+    if (off2) atomicAdd(&rec[2], off2);
+    if (wrong) atomicAdd(&rec[3], wrong);
+}
+
+// one character (or one sheet's background) and its record into the workgroup's counters of its code
+__device__ __forceinline__ void charerr_by_code(unsigned long long* by, const uint32_t* rec) {
+    atomicAdd(&by[0], 1ull);
+#pragma unroll
+    for (int f = 0; f < 4; ++f)
+        if (rec[f]) atomicAdd(&by[1 + f], (unsigned long long)rec[f]);
+}
+
+__global__ __launch_bounds__(256) void sheet_char_errors_kernel(CharErrArgs ca) {
+    extern __shared__ __align__(16) uint8_t s_dyn[];                   // the by-code counters, then compose's cells and ranges
+    __shared__ ComposeLds L;
+    __shared__ CharErrLds X;
+    const ComposeArgs& a = ca.c;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    unsigned long long* s_by = (unsigned long long*)s_dyn;             // [n_codes + 1][5]
+    uint8_t* s_cells = s_dyn + charerr_by_lds(a.n_codes);
+    const int n_by = (a.n_codes + 1) * 5;
+    sheet_cells_to_lds(a, L, s_cells, t);
+    for (int e = t; e < n_by; e += 256) s_by[e] = 0ull;
+    for (int e = t; e < (CMP_MAX_LDX + 1) * 4; e += 256) (&X.acc[0][0])[e] = 0u;
+    const int W8 = a.width >> 3, chunks = a.height * W8;
+    short2* s_range = (short2*)(s_cells + compose_cell_lds(a.n_codes, a.cell_h, a.cell_w));      // [n_lines][W8]
+    for (long long j = blockIdx.x; j < a.n; j += gridDim.x) {
+        __syncthreads();                                               // LDS is set up; the sheet before this one is stored and cleared
+        bool placed;
+        const int nl = sheet_layout<true>(a, L, X.pos, s_range, a.out_rows ? a.out_rows[j] : j, t, lane, wave, W8, placed);
+        // ---- measure
+        const uint8_t* src = ca.pred + (size_t)j * (size_t)chunks * 8u;
+        uint32_t bg[4] = {0u, 0u, 0u, 0u};
+        for (int q = t; q < chunks; q += 256) {
+            const int y = q / W8, x0 = (q - y * W8) << 3;
+            unsigned m[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}, top[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+            int own[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            for (int i = 0; i < nl; ++i) {
+                const int ry = y - L.base[i] + a.origin_y;
+                if ((unsigned)ry >= (unsigned)a.cell_h) continue;
+                const short2 range = s_range[i * W8 + (x0 >> 3)];
+                for (int g = range.x; g <= range.y; ++g) {
+                    const int rx0 = x0 - L.px[g] + a.origin_x;
+                    if (rx0 <= -8 || rx0 >= a.cell_w) continue;
+                    const uint8_t* row = s_cells + (L.code[g] * a.cell_h + ry) * a.cell_w;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        const int rx = rx0 + k;
+                        if ((unsigned)rx < (unsigned)a.cell_w) {
+                            const unsigned b = row[rx];
+                            m[k] = m[k] + b - (m[k] * b + 127u) / 255u;
+                            if (b > top[k]) { top[k] = b; own[k] = g; }      // strictly larger: the earlier glyph keeps a tie
+                        }
+                    }
+                }
+            }
+            const uint2 v = *(const uint2*)(src + (size_t)q * 8u);
+            int run = -1;
+            uint32_t r[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int p = (int)(((k < 4 ? v.x : v.y) >> (8 * (k & 3))) & 255u), tl = 255 - (int)m[k];
+                const uint32_t d = (uint32_t)abs(p - tl);
+                const uint32_t sq = d * d, o2 = d >= 2u, wr = (p >= 128) != (tl >= 128);
+                if (top[k] == 0u) {
+                    bg[0] += 1u; bg[1] += sq; bg[2] += o2; bg[3] += wr;
+                } else {
+                    if (own[k] != run) {
+                        if (run >= 0) charerr_add(X.acc[X.pos[run]], r[0], r[1], r[2], r[3]);
+                        run = own[k];
+                        r[0] = r[1] = r[2] = r[3] = 0u;
+                    }
+                    r[0] += 1u; r[1] += sq; r[2] += o2; r[3] += wr;
+                }
+            }
+            if (run >= 0) charerr_add(X.acc[X.pos[run]], r[0], r[1], r[2], r[3]);
+        }
+#pragma unroll
+        for (int f = 0; f < 4; ++f) {
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) bg[f] += __shfl_xor(bg[f], off);
+            if (lane == 0 && bg[f]) atomicAdd(&X.acc[a.ldx][f], bg[f]);
+        }
+        __syncthreads();
+        // ---- by code: every character placed on a drawn line, and the background
+        if (ca.by_code) {
+            if (placed) charerr_by_code(s_by + L.code[t] * 5, X.acc[X.pos[t]]);
+            if (t == 0) charerr_by_code(s_by + a.n_codes * 5, X.acc[a.ldx]);
+        }
+        __syncthreads();
+        // ---- per position: every record of row j stored once, and cleared for the next sheet
+        for (int e = t; e <= a.ldx; e += 256) {
+            uint4* rec = (uint4*)X.acc[e];
+            if (ca.per_pos) ((uint4*)ca.per_pos)[(size_t)j * (size_t)(a.ldx + 1) + e] = *rec;
+            *rec = make_uint4(0u, 0u, 0u, 0u);
+        }
+    }
+    __syncthreads();
+    if (ca.by_code)
+        for (int e = t; e < n_by; e += 256)
+            if (s_by[e]) atomicAdd(ca.by_code + e, s_by[e]);
+}
+
 int afr_compose_blocks(long long n) { return (int)(n < AFR_COMPOSE_MAX_BLOCKS ? n : AFR_COMPOSE_MAX_BLOCKS); }
 
 hipError_t afr_launch_compose_sheets(const ComposeArgs& a, hipStream_t s) {
     const size_t lds = afr_compose_dynamic_lds(a.n_codes, a.cell_h, a.cell_w, a.n_lines, a.width);
     hipLaunchKernelGGL(compose_sheets_kernel, dim3(afr_compose_blocks(a.n)), dim3(256), lds, s, a);
+    return hipGetLastError();
+}
+
+hipError_t afr_launch_sheet_char_errors(const CharErrArgs& ca, hipStream_t s) {
+    const ComposeArgs& a = ca.c;
+    const size_t lds = afr_charerr_dynamic_lds(a.n_codes, a.cell_h, a.cell_w, a.n_lines, a.width);
+    hipLaunchKernelGGL(sheet_char_errors_kernel, dim3(afr_compose_blocks(a.n)), dim3(256), lds, s, ca);
     return hipGetLastError();
 }

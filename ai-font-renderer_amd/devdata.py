@@ -10,11 +10,15 @@ datagen.render_sheet's bytes from it exactly (tests/test_compose_cpu.py, tests/t
     atlas = GlyphAtlas.from_font("FiraCode-Retina.ttf").to("cuda")
     ds = reference_dataset(150000, atlas)            # TensorDataset(int64 codes [N, L], uint8 sheets [N, 80, 240]) in HBM
 
+char_errors(atlas, codes, pred) runs the same layout once more (afr_op_sheet_char_errors) to charge a prediction's error to the characters
+that own the pixels: the table AttentionFontRenderer.char_errors and AFR_CHAR_REPORT read.
+
 Two things the atlas cannot reproduce, both outside the data set's alphabet (A-Z and space):
   * glyph substitution.  A font that replaces a run of characters by another glyph -- Fira Code's ligatures, "fi", "<>", "->" -- draws
     that glyph under raqm layout; the atlas knows single characters and pairs' kerning only, so such text composes differently;
   * the .notdef box.  Codes outside 32..126 have a blank cell and no advance here, where PIL draws the font's missing-glyph box.
 """
+import collections
 import ctypes as C
 import math
 
@@ -202,6 +206,43 @@ def compose_sheets(atlas, codes, height=80, width=240, out=None, rows=None, line
         if int(err) & 1:
             raise IndexError(f"a code outside the atlas's 0..{atlas.n_codes - 1}")
     return out
+
+
+class CharErrors(collections.namedtuple("CharErrors", "per_pos by_code")):
+    """afr_op_sheet_char_errors' two tables as int64 tensors (the counters are below 2^63): per_pos [n, L + 1, 4] = {pixels, sumsq, off2,
+    wrong} of the character at each position of its row of codes, slot L the background; by_code [n_codes + 1, 5] = {chars, pixels,
+    sumsq, off2, wrong} summed by code, row n_codes the background with chars = sheets."""
+
+
+def char_errors(atlas, codes, pred, height=80, width=240, rows=None, by_code=None, line_height=14.4):
+    """afr_op_sheet_char_errors: how far the uint8 [n, height, width] prediction `pred` (AttentionFontRenderer.render_u8, evaluate's q) is
+    from the sheets compose_sheets draws, charged to the character that owns each pixel -- the glyph with the largest coverage there,
+    the earlier one on a tie; pixels no glyph inks are the background.  Sample j reads row rows[j] (default j) of the int64 [N, L]
+    codes, so a batch can read a bound data set's codes where they lie.  by_code (int64 [n_codes + 1, 5], default new and zero) is
+    added to.  A code outside the atlas is an IndexError, as in compose_sheets."""
+    device = atlas.device
+    codes = codes.to(device=device, dtype=torch.int64).contiguous()
+    if codes.dim() != 2:
+        raise ValueError("codes must be int64 [N, L]")
+    rows = _rows(rows, None, device, "rows")
+    n, L = codes.shape[0] if rows is None else rows.numel(), codes.shape[1]
+    if rows is not None and n and (int(rows.min()) < 0 or int(rows.max()) >= codes.shape[0]):
+        raise IndexError("rows outside codes")
+    if pred.dtype != torch.uint8 or pred.device != device or not pred.is_contiguous() or pred.numel() != n * height * width:
+        raise ValueError(f"pred must be a contiguous uint8 [{n}, {height}, {width}] tensor on {device}")
+    if by_code is None:
+        by_code = torch.zeros((atlas.n_codes + 1, 5), dtype=torch.int64, device=device)
+    if by_code.dtype != torch.int64 or by_code.device != device or not by_code.is_contiguous() or tuple(by_code.shape) != (atlas.n_codes + 1, 5):
+        raise ValueError(f"by_code must be a contiguous int64 [{atlas.n_codes + 1}, 5] tensor on {device}")
+    per_pos = torch.empty((n, L + 1, 4), dtype=torch.int32, device=device)
+    a, g = atlas._struct(), sheet_geometry(height, width, line_height, atlas)
+    with torch.cuda.device(device):
+        err = torch.zeros(1, dtype=torch.int32, device=device)
+        _lib.check(_lib.lib().afr_op_sheet_char_errors(C.byref(a), C.byref(g), _ptr(codes), L, _ptr(rows), n, _ptr(pred), _ptr(per_pos),
+                                                        _ptr(by_code), _ptr(err), _stream(device)))
+        if int(err) & 1:
+            raise IndexError(f"a code outside the atlas's 0..{atlas.n_codes - 1}")
+    return CharErrors(per_pos.to(torch.int64) & 0xFFFFFFFF, by_code)
 
 
 def reference_dataset(n, atlas, first_seed=42, max_length=100, height=80, width=240):

@@ -48,7 +48,12 @@ What is deliberately different from the reference, and why:
     composes the same bytes; nothing is read from disk and nothing is broadcast.  Unset: the reference's folder;
   * AFR_FRESH_DATA=1 (needs AFR_DEVICE_DATA) rewrites the training rows in place before every epoch e >= 1: row r gets the text of seed
     42 + e * N + r (texts as long as the bound rows are wide, MAX_CHARS_PER_SHEET for the full data set) and its sheet.  The validation
-    rows never change and epoch 0 is the run without the variable.  Unset: the data set is fixed, as the reference's.
+    rows never change and epoch 0 is the run without the variable.  Unset: the data set is fixed, as the reference's;
+  * AFR_CHAR_REPORT=<k> (k >= 1, needs AFR_DEVICE_DATA: the atlas is what says which character a pixel belongs to) adds a report of
+    the rendering error by character, counted on the device (devdata.char_errors after Engine.evaluate_last's bitmaps): on the
+    epochs that print a status line, a block headed "Char report:" with the background's rms level error and wrong-ink rate and the
+    k codes with the largest mean squared level error over the validation sheets, and epoch_<e>/char_errors.tsv with every code's
+    counters.  Nothing steps: every other line and artefact is what it is without the variable.  Unset: nothing changes.
 """
 import contextlib
 import datetime
@@ -145,6 +150,26 @@ def _device_data_from_env():
 
 
 DEVICE_DATA, FRESH_DATA = _device_data_from_env()     # likewise read at import
+
+
+def _char_report_from_env():
+    """AFR_CHAR_REPORT = "<k>", k >= 1: the per-character error report with the k worst codes; unset or empty -> None (off).  Anything
+    else, or the report without AFR_DEVICE_DATA (no atlas, no owners), is a ValueError."""
+    spec = os.environ.get("AFR_CHAR_REPORT", "").strip()
+    if not spec:
+        return None
+    try:
+        k = int(spec)
+    except ValueError:
+        k = 0
+    if k < 1:
+        raise ValueError(f"AFR_CHAR_REPORT must be an integer >= 1 (the number of worst characters to list), got {spec!r}")
+    if not os.environ.get("AFR_DEVICE_DATA", "").strip():
+        raise ValueError("AFR_CHAR_REPORT needs AFR_DEVICE_DATA: the glyph atlas the sheets are composed from defines which character owns a pixel")
+    return k
+
+
+CHAR_REPORT = _char_report_from_env()     # likewise read at import
 DATA_FIRST_SEED = 42                                  # sample i of the data set is the text of seed i + 42 (generate_font.ts:204)
 
 
@@ -237,6 +262,50 @@ class _ValReport:
         worst = ", ".join(f"{i}({v:.6f})" for i, v in zip(self.idx.tolist(), self.loss.tolist()))
         return (f"Val report: off by >= 1 level {s[0] / n:.6f}, off by >= 2 levels {s[1] / n:.6f}, wrong ink {s[2] / n:.6f}, "
                 f"max level diff {int(self.max)}, worst {len(self.idx)}{' of rank 0 shard' if world > 1 else ''}: {worst}")
+
+
+class _CharReport:
+    """What AFR_CHAR_REPORT keeps on the device during one validation pass: afr_op_sheet_char_errors' by-code table, which every
+    validation batch's launch adds to (the batch's rows of the bound codes, the evaluation's bitmaps)."""
+
+    def __init__(self, k, atlas, codes):
+        self.k, self.atlas, self.codes = int(k), atlas, codes
+        self.table = torch.zeros((atlas.n_codes + 1, 5), dtype=torch.int64, device=atlas.device)
+
+    def add(self, res, rows):
+        from . import devdata
+        if rows.numel():
+            devdata.char_errors(self.atlas, self.codes, res.u8.contiguous(), res.u8.shape[1], res.u8.shape[2], rows=rows, by_code=self.table)
+
+    def all_reduce(self, dist):
+        dist.all_reduce(self.table, op=dist.ReduceOp.SUM)
+
+    @staticmethod
+    def _rates(row):
+        chars, pixels, sumsq, off2, wrong = row
+        return float(np.sqrt(sumsq / pixels)) if pixels else 0.0, wrong / pixels if pixels else 0.0
+
+    def lines(self):
+        t = self.table.tolist()
+        bg = t[-1]
+        rms, wrong = self._rates(bg)
+        out = [f"Char report: {bg[0]} sheets, background rms level error {rms:.4f}, wrong ink {wrong:.6f}"]
+        inked = [c for c in range(len(t) - 1) if t[c][1] > 0]
+        for c in sorted(inked, key=lambda c: (-(t[c][2] / t[c][1]), c))[:self.k]:
+            rms, wrong = self._rates(t[c])
+            out.append(f"  code {c} {chr(c)!r}: rms level error {rms:.4f}, wrong ink {wrong:.6f}, chars {t[c][0]}")
+        return out
+
+    def write_tsv(self, path):
+        t = self.table.tolist()
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            f.write("code\tchar\tchars\tpixels\tsumsq\toff2\twrong\n")
+            for c, row in enumerate(t):
+                if c == len(t) - 1:
+                    f.write("\t".join(["background", ""] + [str(v) for v in row]) + "\n")
+                elif row[1] > 0:
+                    f.write("\t".join([str(c), chr(c) if 32 < c < 127 else ""] + [str(v) for v in row]) + "\n")
 
 
 def _eval_weights(eng):
@@ -424,6 +493,13 @@ class AttentionFontRenderer(nn.Module):
             raise IndexError("index out of range in self")          # what nn.Embedding raises in the reference
         return q
 
+    def char_errors(self, atlas, codes):
+        """devdata.char_errors of render_u8(codes) against the sheets the atlas composes for the same codes: the rendering error charged
+        to the character that owns each pixel.  Returns a devdata.CharErrors."""
+        from . import devdata
+        q = self.render_u8(codes)
+        return devdata.char_errors(atlas, codes, q, q.shape[1], q.shape[2])
+
     def forward(self, x):
         if x.dim() != 2:
             raise ValueError(f"expected [batch, seq_len] codes, got shape {tuple(x.shape)}")
@@ -518,7 +594,7 @@ def _batch_calls(eng, stepper, inputs, targets, rows):
                            evaluate=partial(eng.evaluate, x), forward_loss=partial(eng.forward_loss, x, t))
 
 
-def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True, report=None, treport=None):
+def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True, report=None, treport=None, creport=None):
     """One epoch of the reference loop (model.py:288-333): the training pass over order.train_epoch(), then the validation
     pass; returns the two means of per-batch mean losses.  An engine that keeps a weight EMA validates from it.  by_rows: the engine has the data set bound (Engine.bind_dataset)
     and every step is driven by this rank's slice of the epoch's index vector -- the kernels read the rows where they lie.
@@ -526,7 +602,8 @@ def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, wor
     measures the other against).  report: a _ValReport (AFR_VAL_REPORT) that every validation batch is evaluated into between its
     forward and its loss; None: the pass as it always was.  treport: a _TensorReport (AFR_TENSOR_REPORT, rank 0 only): the weights are
     snapshotted before the last training batch and compared after it, and once the validation loss has been read the first training
-    batch is run once more as a probe for its gradients."""
+    batch is run once more as a probe for its gradients.  creport: a _CharReport (AFR_CHAR_REPORT): every validation batch's bitmaps --
+    of the one evaluation it shares with report -- are measured against the sheets the atlas composes for the batch's rows."""
     from .parallel import shard_rows
     eng = model.engine
     pixels = targets[0].numel()
@@ -558,9 +635,15 @@ def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, wor
             mine = rows[shard_rows(rows.numel(), rank, world)]
             calls = _batch_calls(eng, None, *dense, mine)
             calls.forward(training=False, want_output=False)
-            if report is not None:
-                report.add(calls.evaluate_last(), mine)
+            if report is not None or creport is not None:
+                res = calls.evaluate_last(want_u8=creport is not None)
+                if report is not None:
+                    report.add(res, mine)
+                if creport is not None:
+                    creport.add(res, mine)
             calls.loss_grad(mean_elems=rows.numel() * pixels)
+        if creport is not None and world > 1:
+            creport.all_reduce(_dist()[0])
         if report is not None:
             if world > 1:
                 report.all_reduce(_dist()[0])
@@ -584,10 +667,11 @@ def _fresh_rows(atlas, n):
     return refresh
 
 
-def train_attention_model(model, dataset, batch_size, refresh=None):
+def train_attention_model(model, dataset, batch_size, refresh=None, atlas=None):
     """Reference model.py:209-384: config.txt, 80/20 split, AdamW + ReduceLROnPlateau + early stopping, progress
     prints and test-string dumps every 5 epochs, training_results.txt.  Returns the model.  refresh (AFR_FRESH_DATA, _fresh_rows): called
-    before every epoch >= 1 with the training rows of the split and the bound tensors, which it rewrites in place."""
+    before every epoch >= 1 with the training rows of the split and the bound tensors, which it rewrites in place.  atlas: the glyph
+    atlas the data set was composed from (AFR_CHAR_REPORT needs it)."""
     from .parallel import DataParallelStepper
     dist, world, rank = _dist()
     eng = model.engine
@@ -618,6 +702,10 @@ def train_attention_model(model, dataset, batch_size, refresh=None):
                 f.write(f"device_data = {DEVICE_DATA}\n")
             if refresh is not None:             # likewise
                 f.write("fresh_data = 1\n")
+            if CHAR_REPORT:                     # likewise
+                f.write(f"char_report = {CHAR_REPORT}\n")
+    if CHAR_REPORT and atlas is None:
+        raise ValueError("the character report needs the glyph atlas the data set was composed from (AFR_DEVICE_DATA)")
 
     order = _EpochOrder(len(dataset))
     print(f"Dataset split: {order.train_size} training samples, {order.val_size} validation samples")
@@ -648,10 +736,11 @@ def train_attention_model(model, dataset, batch_size, refresh=None):
         lr = lr_holder.param_groups[0]["lr"]
         report = _ValReport(VAL_REPORT, device, bitmaps=epoch % 5 == 0) if VAL_REPORT else None
         treport = _TensorReport(model) if TENSOR_REPORT and rank == 0 and epoch % 5 == 0 else None
+        creport = _CharReport(CHAR_REPORT, atlas, inputs) if CHAR_REPORT and epoch % 5 == 0 else None
         if refresh is not None and epoch >= 1:
             refresh(epoch, order.train_idx, inputs, targets)
         avg_train_loss, avg_val_loss = _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True, report=report,
-                                                  treport=treport)
+                                                  treport=treport, creport=creport)
 
         scheduler.step(avg_val_loss)
         is_best = avg_val_loss < best_val_loss
@@ -677,6 +766,9 @@ def train_attention_model(model, dataset, batch_size, refresh=None):
                         helpers.u8_array_to_image(report.u8[j].cpu().numpy(), f"{OUTPUT_DIR}/epoch_{epoch}/val_worst_{j}.bmp")
                 if treport is not None:
                     print("\n".join(treport.lines()))
+                if creport is not None:
+                    print("\n".join(creport.lines()))
+                    creport.write_tsv(f"{OUTPUT_DIR}/epoch_{epoch}/char_errors.tsv")
                 with _eval_weights(eng):
                     render_strings(model, test_strings, output_dir=f"{OUTPUT_DIR}/epoch_{epoch}", sheet_height=SHEET_HEIGHT,
                                    sheet_width=SHEET_WIDTH, device=device)
@@ -709,7 +801,7 @@ def train_attention_model(model, dataset, batch_size, refresh=None):
 def train_string_renderer():
     """Reference model.py:389-421."""
     print("Creating sheet dataset...")
-    refresh = None
+    refresh = atlas = None
     if DEVICE_DATA:
         from . import datagen, devdata
         atlas = devdata.GlyphAtlas.from_font(None if DEVICE_DATA == "default" else DEVICE_DATA, datagen.FONT_SIZE).to(device)
@@ -725,7 +817,7 @@ def train_string_renderer():
     model = AttentionFontRenderer(max_length=MAX_CHARS_PER_SHEET, max_batch=batch_size)
     model = model.to(device)
     print(f"Using batch size {batch_size}")
-    return train_attention_model(model, dataset, batch_size, refresh)
+    return train_attention_model(model, dataset, batch_size, refresh, atlas)
 
 
 def main(argv=None):

@@ -565,6 +565,32 @@ int afr_op_dataset_text(int64_t first_seed, const int64_t* seed_rows, const int6
 int afr_op_compose_sheets(const afr_glyph_atlas* atlas, const afr_sheet_geometry* geo, const int64_t* codes, int ldx,
                           const int64_t* out_rows, int64_t n, uint8_t* out, uint32_t* err /* or NULL */, void* stream);
 
+/* ---- rendering error attributed to characters: one launch that lays a text out exactly as compose_sheets does and measures a
+ * prediction against the sheet compose_sheets would draw, pixel by pixel, charging every pixel to the character that owns it.  A
+ * plain op: no plan, nothing allocated, one workgroup per sheet under compose's grid cap; integers only, so the result repeats
+ * bit for bit.
+ *   Sample j of n reads row r = code_rows ? code_rows[j] : j of codes int64 [rows][ldx] (text to the first 0, codes outside the
+ *   atlas flagged in bit 0 of *err and skipped, wrap, pens and n_lines as compose_sheets) and the dense prediction
+ *   pred uint8 [n][height][width] (afr_op_eval's q, for instance).  For pixel (y, x): m = the composed coverage, t = 255 - m the
+ *   target level (recomputed, never read), p = pred[j][y][x], d = |p - t|.  Among the glyphs whose cell value b at the pixel is
+ *   > 0, in (line, character) order, the OWNER is the one with the largest b, the earlier one on equal b; with none the pixel is
+ *   background.  The owner's record gains pixels += 1, sumsq += d * d, off2 += (d >= 2), wrong += ((p >= 128) != (t >= 128)) --
+ *   afr_op_eval's stats[1] and stats[3], split by owner.
+ *   per_pos uint32 [n][ldx + 1][4] (or NULL), {pixels, sumsq, off2, wrong}: indexed by the character's position in its row of
+ *                  codes (not in the packed text); slot ldx is the background.  Every element of row j is stored once; records
+ *                  of characters that own nothing -- spaces, characters on lines from n_lines on, skipped codes, positions
+ *                  behind the text -- are zero.
+ *   by_code uint64 [n_codes + 1][5] (or NULL), {chars, pixels, sumsq, off2, wrong}: ADDED to, the caller zeroes it.  chars counts
+ *                  the characters of the code that stand on a drawn line, whether or not they own a pixel; row n_codes is the
+ *                  background and its chars counts sheets.  A workgroup sums its sheets in LDS and issues one global integer
+ *                  atomic per non-zero field.
+ * Errors, before anything is launched: everything compose_sheets refuses (pred in the place of out), both outputs NULL, by_code
+ * not 8-byte or per_pos not 16-byte aligned -> AFR_EINVAL; compose_sheets' limits, the LDS budget with the records and counters
+ * counted, a sheet of more than 66051 pixels (65025 * pixels must fit 32 bits) -> AFR_EUNSUPPORTED. */
+int afr_op_sheet_char_errors(const afr_glyph_atlas* atlas, const afr_sheet_geometry* geo, const int64_t* codes, int ldx,
+                             const int64_t* code_rows /* or NULL */, int64_t n, const uint8_t* pred, uint32_t* per_pos /* or NULL */,
+                             uint64_t* by_code /* or NULL */, uint32_t* err /* or NULL */, void* stream);
+
 /* ---- the token-wise kernels of the per-pixel-token transformer (AFR_KIND_PIXEL), one launch each, exactly as the plan issues
  * them.  One wave per token row: rows >= 1, d = 64 * heads <= 512 (the widths a plan can reach; AFR_EUNSUPPORTED otherwise),
  * C = context tokens per glyph, 1 or 2; act_dtype AFR_F32 or AFR_BF16 is the type T of the GEMM operands (ctx, add, n, q, kv, o,
