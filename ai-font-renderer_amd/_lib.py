@@ -78,6 +78,11 @@ class AfrSheetSlabLayout(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("pos", "emb", "w_in", "b_in", "w_o", "b_o", "ln_g", "ln_b", "w1", "b1", "total")]
 
 
+class AfrGlyph1Layout(C.Structure):
+    """Offsets in floats of the six tensors inside one slab of the fused glyph step, and the slab's length (afr_glyph1_layout)."""
+    _fields_ = [(n, C.c_int32) for n in ("emb", "font", "w1", "b1", "w2", "b2", "total")]
+
+
 LIN_FWD, LIN_DX, LIN_DW, LIN_PAIR = 0, 1, 2, 3      # AFR_LIN_*: which product of a Linear afr_op_linear issues
 
 
@@ -204,6 +209,14 @@ SIGNATURES = {
     "afr_op_glyph_l1_bwd": (_i32, [_vp, _i32, C.c_longlong, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "afr_op_glyph_l1_bwd_fused": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "afr_op_glyph_embed_bwd": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "afr_op_glyph_l1_fwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "afr_glyph1_rows": (_i32, [_i32]),
+    "afr_glyph1_colsplit": (_i32, [_i32, _i32, _i32]),
+    "afr_glyph1_blocks": (_i32, [_i32, _i32, _i32]),
+    "afr_glyph1_eligible": (_i32, [_i32, _i32, _i32, _i32, _i32]),
+    "afr_op_glyph1_step": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
+                                  _i64, _vp, C.POINTER(AfrGlyph1Layout), _vp, _vp, _vp, _vp]),
+    "afr_op_transpose_bf16": (_i32, [_vp, _vp, _i32, _i32, _vp]),
 }
 
 

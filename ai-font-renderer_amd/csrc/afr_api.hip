@@ -2667,3 +2667,83 @@ extern "C" int afr_op_glyph_embed_bwd(int act_dtype, const void* d, const int64_
     HIPCHK(afr_launch_glyph_embed_bwd(act_dtype, d, x, font, B, E, vocab, n_fonts, slabs, (hipStream_t)stream));
     return AFR_OK;
 }
+
+// ---- the folded forward's table + gather pair, the fused step of the small glyph nets and its operand transpose, one call each
+extern "C" int afr_op_glyph_l1_fwd(int act_dtype, const float* emb, const float* femb, const float* W1, const float* b1, const int64_t* x,
+                                   const int64_t* font, int B, int E, int N1, int vocab, int n_fonts, float* table, void* h0p, void* h1, void* w1t,
+                                   uint32_t* err, void* stream) {
+    const char* what = "afr_op_glyph_l1_fwd";
+    if (int rc = glyph_op_shape(what, act_dtype, B, E, vocab, n_fonts)) return rc;
+    if (int rc = glyph_op_n1(what, N1)) return rc;
+    if (int rc = glyph_op_fold(what, E, vocab, n_fonts)) return rc;
+    if ((long long)B * std::max(N1, afr_glyph_k0(E, vocab, n_fonts)) >= (1ll << 31) || (long long)(vocab + n_fonts) * N1 >= (1ll << 31))
+        return fail(AFR_EUNSUPPORTED, "%s: h1, h0' and the table must stay below 2^31 elements", what);
+    if (!emb || !W1 || !b1 || !x || !table || !h0p || !h1 || !err || (n_fonts > 0 && !femb)) return fail(AFR_EINVAL, "%s: null argument", what);
+    if (((uintptr_t)emb & 15) || (n_fonts > 0 && ((uintptr_t)femb & 15)) ||((uintptr_t)W1 & 15) || ((uintptr_t)b1 & 15) || ((uintptr_t)table & 15) ||
+        ((uintptr_t)h0p & 15) || ((uintptr_t)h1 & 15))
+        return fail(AFR_EINVAL, "%s: emb, femb, W1, b1, table, h0p and h1 must be 16-byte aligned", what);
+    DevGuard dg(device_of(h1));
+    HIPCHK(afr_launch_glyph_l1_fwd(act_dtype, emb, femb, W1, b1, x, font, B, E, N1, vocab, n_fonts, table, h0p, h1, err, (hipStream_t)stream, w1t));
+    return AFR_OK;
+}
+extern "C" int afr_glyph1_blocks(int dtype, int B, int P) {
+    const int R = afr_glyph1_rows(dtype);
+    return B < 1 ? 0 : (B + R - 1) / R * afr_glyph1_colsplit(dtype, B, P);
+}
+extern "C" int afr_op_glyph1_step(int dtype, int loss_kind, const float* emb, const float* femb, const void* W1, const float* b1, const void* W2,
+                                  const float* b2, const void* W1T, const void* W2T, const int64_t* x, const int64_t* font, const void* target,
+                                  int target_dtype, const int32_t* target_rows, int B, int E, int N1, int P, int vocab, int n_fonts,
+                                  int64_t mean_elems, float* slabs, const afr_glyph1_layout* lay, float* loss_accum, float* loss_scratch,
+                                  uint32_t* err, void* stream) {
+    const char* what = "afr_op_glyph1_step";
+    if (dtype != AFR_F32 && dtype != AFR_BF16) return fail(AFR_EINVAL, "%s: dtype must be AFR_F32 or AFR_BF16, got %d", what, dtype);
+    if (loss_kind != AFR_LOSS_MSE && loss_kind != AFR_LOSS_BCE) return fail(AFR_EINVAL, "%s: loss kind must be AFR_LOSS_MSE (0) or AFR_LOSS_BCE (1), got %d", what, loss_kind);
+    if (target_dtype != AFR_TARGET_U8 && target_dtype != AFR_TARGET_F32) return fail(AFR_EINVAL, "%s: target_dtype must be AFR_TARGET_U8 or AFR_TARGET_F32, got %d", what, target_dtype);
+    if (B < 1) return fail(AFR_EINVAL, "%s: B = %d must be >= 1", what, B);
+    if (vocab < 1 || n_fonts < 0) return fail(AFR_EINVAL, "%s: vocab = %d, n_fonts = %d", what, vocab, n_fonts);
+    if (E < 1 || N1 < 1 || P < 1) return fail(AFR_EINVAL, "%s: E = %d, N1 = %d, P = %d must be >= 1", what, E, N1, P);
+    if (mean_elems < 1) return fail(AFR_EINVAL, "%s: mean_elems = %lld must be >= 1", what, (long long)mean_elems);
+    if (!afr_glyph1_eligible(E, N1, P, vocab, n_fonts))
+        return fail(AFR_EUNSUPPORTED, "%s: E = %d, N1 = %d, P = %d, vocab + n_fonts = %d: the fused step takes E 32 or 64, N1 and P multiples of 64 up to 256 and at most 264 table rows",
+                    what, E, N1, P, vocab + n_fonts);
+    if (int rc = glyph_op_lds(what, afr_glyph1_lds_bytes(dtype, E, N1, P, vocab + n_fonts))) return rc;
+    const bool b16 = dtype == AFR_BF16;
+    if (!emb || !W1 || !b1 || !W2 || !b2 || !x || !target || !slabs || !lay || !loss_accum || !loss_scratch || !err || (n_fonts > 0 && !femb) ||
+        (b16 && (!W1T || !W2T)))
+        return fail(AFR_EINVAL, "%s: null argument", what);
+    if (((uintptr_t)W1 & 15) || ((uintptr_t)W2 & 15) || (b16 && (((uintptr_t)W1T & 15) || ((uintptr_t)W2T & 15))) || ((uintptr_t)slabs & 15))
+        return fail(AFR_EINVAL, "%s: W1, W2, W1T, W2T and slabs must be 16-byte aligned", what);
+    // the six tensor ranges lie inside a slab, start on 16 bytes and do not overlap
+    if (lay->total < 4 || (lay->total & 3)) return fail(AFR_EINVAL, "%s: total = %d must be a positive multiple of 4", what, lay->total);
+    const long long off[6] = {lay->emb, lay->font, lay->w1, lay->b1, lay->w2, lay->b2};
+    const long long len[6] = {(long long)vocab * E, (long long)n_fonts * E, (long long)N1 * E, N1, (long long)P * N1, P};
+    for (int i = 0; i < 6; ++i) {
+        if (len[i] == 0) continue;
+        if (off[i] < 0 || (off[i] & 3) || off[i] + len[i] > lay->total)
+            return fail(AFR_EINVAL, "%s: tensor %d (offset %lld, %lld floats) must start on a multiple of 4 and lie inside total = %d", what, i, off[i], len[i], lay->total);
+        for (int j = 0; j < i; ++j)
+            if (len[j] && off[i] < off[j] + len[j] && off[j] < off[i] + len[i]) return fail(AFR_EINVAL, "%s: tensors %d and %d overlap", what, j, i);
+    }
+    DevGuard dg(device_of(slabs));
+    Glyph1Args a;
+    a.x = x; a.font = font;
+    a.loss = loss_args(loss_scratch, true, loss_kind, target, target_dtype, target_rows, mean_elems, loss_accum);
+    a.B = B; a.E = E; a.N1 = N1; a.P = P; a.vocab = vocab; a.n_fonts = n_fonts;
+    a.emb = emb; a.femb = n_fonts > 0 ? femb : nullptr; a.b1 = b1; a.b2 = b2;
+    a.W1 = W1; a.W2 = W2;
+    a.W1T = b16 ? W1T : W1; a.W2T = b16 ? W2T : W2;                  // f32: the masters again, gathered (as the plan hands them)
+    a.slabs = slabs; a.slab_stride = lay->total;
+    a.o_emb = lay->emb; a.o_font = n_fonts > 0 ? lay->font : 0; a.o_w1 = lay->w1; a.o_b1 = lay->b1; a.o_w2 = lay->w2; a.o_b2 = lay->b2;
+    a.err = err;
+    a.cs = afr_glyph1_colsplit(dtype, B, P);
+    HIPCHK(afr_launch_glyph1_step(dtype, a, (hipStream_t)stream));
+    return AFR_OK;
+}
+extern "C" int afr_op_transpose_bf16(const float* W, void* WT, int N, int K, void* stream) {
+    const char* what = "afr_op_transpose_bf16";
+    if (N < 1 || K < 1) return fail(AFR_EINVAL, "%s: N = %d, K = %d must be >= 1", what, N, K);
+    if (!W || !WT) return fail(AFR_EINVAL, "%s: null argument", what);
+    DevGuard dg(device_of(WT));
+    HIPCHK(afr_launch_transpose_bf16(W, (bf16_t*)WT, N, K, (hipStream_t)stream));
+    return AFR_OK;
+}

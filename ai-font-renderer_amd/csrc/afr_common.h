@@ -509,10 +509,12 @@ struct Glyph1Args {
     uint32_t* err;
     int cs = 1;                              // column split: cs blocks share a row block, each owning P / cs output columns
 };
-int afr_glyph1_rows(int dtype);
-int afr_glyph1_colsplit(int dtype, int B, int P);     // blocks per row block (1, 2 or 4) for a batch of B
+// (rows, colsplit, blocks and eligible are also exported, include/afr.h: a caller of afr_op_glyph1_step sizes its buffers with them)
+extern "C" int afr_glyph1_rows(int dtype);
+extern "C" int afr_glyph1_colsplit(int dtype, int B, int P);     // blocks per row block (1, 2 or 4) for a batch of B
+extern "C" int afr_glyph1_blocks(int dtype, int B, int P);       // row blocks x column split: the blocks (= slabs, loss partials) of a batch of B
 int afr_glyph1_max_blocks(int dtype, int max_batch, int P);   // the most blocks any batch <= max_batch launches (slab / loss-partial count)
-bool afr_glyph1_eligible(int E, int N1, int P, int vocab, int n_fonts);
+extern "C" int afr_glyph1_eligible(int E, int N1, int P, int vocab, int n_fonts);   // 1 / 0
 size_t afr_glyph1_lds_bytes(int dtype, int E, int N1, int P, int table_rows);
 hipError_t afr_launch_transpose_bf16(const float* W, bf16_t* WT, int N, int K, hipStream_t s);
 hipError_t afr_launch_glyph1_step(int dtype, const Glyph1Args& a, hipStream_t s);

@@ -437,7 +437,7 @@ int afr_glyph1_max_blocks(int dtype, int max_batch, int P) {
     if (alt > m) m = alt;
     return m;
 }
-bool afr_glyph1_eligible(int E, int N1, int P, int vocab, int n_fonts) {
+int afr_glyph1_eligible(int E, int N1, int P, int vocab, int n_fonts) {
     return E % 32 == 0 && E <= 64 && N1 % 64 == 0 && N1 <= 256 && P % 64 == 0 && P <= 256 && vocab + n_fonts <= 264;
 }
 size_t afr_glyph1_lds_bytes(int dtype, int E, int N1, int P, int table_rows) {

@@ -694,7 +694,9 @@ int afr_op_sheet_bwd(int act_dtype, const afr_sheet_params* params, const int64_
  *   glyph_embed_bwd    slabs f32 [afr_embed_bwd_blocks(B)][vocab + n_fonts][E]: per block of 32 glyphs the sum of d[b] by table
  *                      row, in b order.  The table's accumulator sits in LDS: ((vocab + n_fonts) E + 32 (E + 1)) floats + 256
  *                      bytes must fit 160 KiB (AFR_EUNSUPPORTED beyond; afr_plan_create refuses such a glyph config).
- * The table + gather pair of the folded forward (afr_launch_glyph_l1_fwd) has no entry of its own yet.
+ *   glyph_l1_fwd       the folded forward, two launches: table f32 [vocab + n_fonts][N1] = [emb; femb] . W1^T (and w1t, or NULL: bf16
+ *                      [E][N1] = W1^T), then h1 T [B][N1] = relu((table[x] + b1) + table[vocab + font]) and h0p T [B][K0] = h0'.
+ *                      E <= 128 and K0 <= 512, the plan's own fold condition; emb, femb, W1, b1, table, h0p, h1 16-byte aligned.
  * Refused with a message before anything is launched: B < 1, vocab < 1, n_fonts < 0, a NULL required pointer (AFR_EINVAL); E or N1
  * not a multiple of 8, the limits above, a dynamic-LDS request above 160 KiB (AFR_EUNSUPPORTED). */
 int afr_glyph_k0(int E, int vocab, int n_fonts);                 /* host-only getters, all of them */
@@ -716,6 +718,40 @@ int afr_op_glyph_l1_bwd_fused(const void* d1, const void* h0, int ldh, const int
                               float* slabs, void* stream);
 int afr_op_glyph_embed_bwd(int act_dtype, const void* d, const int64_t* x, const int64_t* font /* or NULL */, int B, int E, int vocab,
                            int n_fonts, float* slabs, void* stream);
+int afr_op_glyph_l1_fwd(int act_dtype, const float* emb, const float* femb, const float* W1, const float* b1, const int64_t* x,
+                        const int64_t* font /* or NULL */, int B, int E, int N1, int vocab, int n_fonts, float* table, void* h0p, void* h1,
+                        void* w1t /* or NULL */, uint32_t* err, void* stream);
+
+/* ---- the fused step of the small one-hidden-layer glyph nets (E -> N1 -> P), ONE launch: gather, fc1 + ReLU, fc_output, the loss head
+ * (AFR_LOSS_MSE: clamp + MSE; AFR_LOSS_BCE: BCE with logits), all six gradient products and the one-hot scatter, exactly as the plan
+ * issues it.  A block takes afr_glyph1_rows(dtype) glyphs (16 in AFR_F32, 64 in AFR_BF16) and one of the
+ * cs = afr_glyph1_colsplit(dtype, B, P) ranges of P / cs output columns: block rb * cs + pc leaves in slab rb * cs + pc (layout->total
+ * floats each, tensors at the layout's offsets) ITS rows [pc, pc + 1) * P / cs of dW2 [P][N1] and db2 [P], and -- from its columns'
+ * share of dh1 -- partial dW1 [N1][E], db1 [N1], dEmb [vocab][E] and dFont [n_fonts][E] (table rows none of its glyphs used: +0).
+ * Everything else of a slab is not written; the gradient is the sum over the slabs that own an element.
+ *   dtype      AFR_F32: W1 [N1][E], W2 [P][N1] are the float32 masters; W1T, W2T are not read.  AFR_BF16: W1, W2 bf16, and their
+ *              transposed copies W1T bf16 [E][N1], W2T bf16 [N1][P] (afr_op_transpose_bf16), all four required.
+ *   target     uint8 (pixel / 255.0f) or float32 [..][P] by target_dtype; the targets of glyph b are row b, or row target_rows[b].
+ *   layout     offsets in floats of emb, font, w1, b1, w2, b2 inside a slab and total, all multiples of 4; the ranges lie inside total
+ *              and do not overlap (font is not read when n_fonts == 0).
+ *   loss       *loss_accum += sum of the loss terms / mean_elems (mean_elems >= 1).  loss_scratch: 1040 + afr_glyph1_blocks(dtype, B, P)
+ *              floats, zero before the first call; the kernel re-arms its counter.
+ *   err        device word: bit 0 is set for an index outside its table, which is clamped.
+ * Refused with a message before anything is launched: a shape outside afr_glyph1_eligible (E 32 or 64, N1 and P multiples of 64 up to
+ * 256, vocab + n_fonts <= 264), a dynamic-LDS request above 160 KiB (AFR_EUNSUPPORTED); any other dtype, loss kind or target type, B < 1,
+ * mean_elems < 1, a NULL required pointer, W1 / W2 / W1T / W2T / slabs not 16-byte aligned, a bad layout (AFR_EINVAL).
+ * afr_op_transpose_bf16: WT bf16 [K][N] = the transpose of W f32 [N][K], rounded to nearest even. */
+typedef struct afr_glyph1_layout { int32_t emb, font, w1, b1, w2, b2, total; } afr_glyph1_layout;
+int afr_glyph1_rows(int dtype);                                  /* host-only getters */
+int afr_glyph1_colsplit(int dtype, int B, int P);
+int afr_glyph1_blocks(int dtype, int B, int P);                  /* row blocks x column split = slabs = loss partials */
+int afr_glyph1_eligible(int E, int N1, int P, int vocab, int n_fonts);   /* 1 or 0 */
+int afr_op_glyph1_step(int dtype, int loss_kind, const float* emb, const float* femb, const void* W1, const float* b1, const void* W2,
+                       const float* b2, const void* W1T /* or NULL in AFR_F32 */, const void* W2T /* or NULL in AFR_F32 */, const int64_t* x,
+                       const int64_t* font /* or NULL */, const void* target, int target_dtype, const int32_t* target_rows /* or NULL */,
+                       int B, int E, int N1, int P, int vocab, int n_fonts, int64_t mean_elems, float* slabs,
+                       const afr_glyph1_layout* layout, float* loss_accum, float* loss_scratch, uint32_t* err, void* stream);
+int afr_op_transpose_bf16(const float* W, void* WT, int N, int K, void* stream);
 
 /* ---- fp8 building blocks of BASELINE configs[4] ("fp8 MFMA weights on CDNA4"; no counterpart in the reference) ----
  * Operands are OCP e4m3fn bytes (gfx950's native fp8: exponent bias 7, largest finite 448, no infinities) with ONE float

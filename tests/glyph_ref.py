@@ -9,6 +9,7 @@ u = 2^-24 and ub = 2^-8 are the unit roundoffs of float32 and bfloat16.
                    |h1 - relu(pre)| <= B_pre (+ ub |ref| in bf16); the ReLU gate may differ from fp64's only where |pre| <= B_pre
     h0'            [embed | one-hot of x | one-hot of vocab + f | +0 pad]: the fused backward's dense operand, and the widened
                    operand behind the post-pass's slabs
+    l1_fwd         the folded forward's table + gather pair (afr_op_glyph_l1_fwd): table and h1 as above, h0' and w1t = bf16(W1)^T bit for bit
     combo          cidx = x max(n_fonts, 1) + f exact, h0c = bf16(embed) exact, h1c under the h1 bound in bf16
     l1_bwd         S = sum_z slab_z:  |dw1 - S[:, :E]| <= nslabs u sum_z |slab|;  per block of 8 fc1 rows
                    |dtab_part - sum_q S[q][E + r] W1[q][k]| <= (nslabs + 8) u sum_q sum_z |slab_z[q][E + r]| |W1[q][k]|
@@ -21,6 +22,37 @@ u = 2^-24 and ub = 2^-8 are the unit roundoffs of float32 and bfloat16.
                    of exact bf16 products is far more accurate than that bound, and none of them has been seen to straddle)
     embed_bwd      per block of 32 rows, per table row the float32 sum in row order, bit for bit (embed_bwd_f32); against fp64
                    under 32 u sum |d|
+
+THE FUSED STEP of the small glyph nets (csrc/glyph_fused.hip glyph1_step_kernel through afr_op_glyph1_step), the whole step in fp64
+per block (row block rb of R = 16 (f32) / 64 (bf16) glyphs, column range pc of P / cs output columns), u = 2^-24:
+
+    a product of K terms on the matrix cores with float32 accumulation     (K + 2) u sum |a| |b|   (the bias add of a forward product is
+                                                                           in the + 2: |bias| joins the sum)
+    a stage's bound                                                        its own term plus the earlier bounds carried through linearly
+                                                                           (and their product where two inexact factors meet)
+    pre1 = h0 . W1^T + b1     h0 exact (one float32 add, then the rounding to the operand type)
+    h1 = relu(pre1)           the gate is the reference's: the inputs keep |pre1| above 8 x its bound (step_inputs)
+    u = h1 . W2^T + b2        carried: B_h1 . |W2|^T
+    du, loss term             MSE: gates from the reference (u is kept 4 x its bound away from 0 and 1; in bf16 from 0 and 1 + 2^-8, the value
+                              above which bf16(u) leaves 1); du carries 2 / n B_u where the gate is open; BCE: |d sigmoid / du| <= 1/4.  The
+                              head's own arithmetic (fast exp / log, the quotient table of the u8 targets): 1e-6 max |du_ref|, the figure
+                              tests/test_gpu_linear_ops.py holds the fused loss head to
+    dW2, db2 (own rows)       (R + 2) u sum_b |du| |h1| + B_du^T |h1| + |du|^T B_h1 + B_du^T B_h1
+    dh1 (own columns)         (P / cs + 2) u |du| |W2| + B_du |W2|;  dpre1 = dh1 [pre1 > 0]
+    dW1, db1                  (R + 2) u sum_b |dpre1| |h0| + B_d1^T |h0|
+    dh0 = dpre1 . W1          (N1 + 2) u |dpre1| |W1| + B_d1 |W1|;   dTab = onehot^T dh0: (R + 2) u onehot^T |dh0| + onehot^T B_dh0
+    loss                      per term 4 u l (MSE) / 4 u (|u| (1 + t) + 1) (BCE: fma, 1 + e, log, add) + the carried |dl/du| B_u + B_u^2, and
+                              the float32 sum of all terms: LOSS_DEPTH u sum l (per-lane, wave, block and grid levels)
+    bf16                      the kernel rounds h0, h1, u (before the loss head), du, dpre1 and dh0 to bf16 and so does the reference (rnd).
+                              Where a reference value lies within its carried bound of a bf16 rounding boundary the two roundings may be
+                              one bf16 ulp apart: that element's bound is widened by bf16_ulp and the widening is carried on (fused_ref's
+                              `near`).  No other bf16 term enters, and none at all in float32.
+    the sum of all slabs      against the unsplit, UNROUNDED model: the summed block bounds plus step_model's a-priori term, formed from
+                              the unrounded values alone -- u |h0| for the float32 add of the embedding rows, and in bf16 half an ulp
+                              (2^-9 relative) at each rounding point, carried on linearly, a gate within its carried term of its
+                              threshold taken as undecided (step_model states the rule).  In float32 this term is some 1e-6 of the
+                              gradient; in bf16 a few per cent of it for dW2 / db2, while for dW1, db1 and dTab the undecided ReLU
+                              gates make it as large as the gradient at some cases (tests/test_glyph_ref_cpu.py prints it)
 """
 import numpy as np
 import torch
@@ -283,3 +315,386 @@ def fused_inputs(B, N1, vocab, n_fonts, form, kind, tid=700):
         h0 = bf16(embed_ref(t["emb"], t["femb"], cx, cf, n_fonts, F32))
         ldh, rowmap = 32, (xc * max(n_fonts, 1) + fc).to(torch.int32)
     return dict(d1=d1, W1=W1, x=x, font=font, xc=xc, fc=fc, h0g=h0g, h0=h0, ldh=ldh, rowmap=rowmap)
+
+
+# ================================================================================================================ folded forward
+# (B, E, N1, vocab, n_fonts, kind): the smallest shape; 65 chunks of 8 columns (128-wide thread rows), a ragged 256-row chunk of the
+# table and a ragged glyph block; E = 128 (136 KB of dynamic LDS, the opt-in); K0 = 448; K0 = 512, the limit; one code for every glyph
+L1_FWD_CASES = [(1, 32, 8, 128, 2, "spread"), (257, 32, 520, 100, 0, "spread"), (40, 128, 264, 128, 1, "nofont"), (300, 64, 200, 381, 3, "spread"),
+                (33, 32, 72, 478, 2, "spread"), (64, 32, 1024, 37, 3, "one")]
+
+
+def l1_fwd_ref(t, xc, fc, vocab, n_fonts, is_bf16):
+    """the table + gather pair from table_ref, h1_ref and h0p_ref -> dict: table fp64 and its bound bT; pre, its bound bp, h1 = relu(pre)
+    and its bound bh; h0p and w1t in the output type, bit for bit what the kernels leave"""
+    T, Tb = table_ref(t["emb"], t["femb"], t["W1"], n_fonts)
+    pre, bp, ref, bh = h1_ref(T, Tb, t["b1"], xc, fc, vocab, n_fonts, is_bf16)
+    h0p = h0p_ref(t["emb"], t["femb"], xc, fc, vocab, n_fonts, F32)            # one float32 add, ones and +0: the same bits in torch
+    return dict(table=T, bT=Tb, pre=pre, bp=bp, h1=ref, bh=bh, h0p=h0p.to(BF16) if is_bf16 else h0p, w1t=t["W1"].to(BF16).t().contiguous())
+
+
+# ================================================================================================================ fused step
+G1_ROWS = {False: 16, True: 64}
+G1_KB = {False: 16, True: 32}
+LOSS_DEPTH = 128        # 64 terms per lane at the most, 6 wave levels, 8 waves, ceil(blocks / threads) + 9 levels of the grid's finish
+# (B, E, N1, P, vocab, n_fonts): one glyph, split 4 (f32) / 2 (bf16); C1's shape with a ragged last block; E = 64 and widths that are no
+# powers of two; 264 table rows (the limit; a one-hot image of 272 rows), split 4 / 2; fonts and many repeats; split 1 in both types
+STEP_CASES = [(1, 32, 64, 64, 5, 0), (95, 32, 256, 256, 128, 0), (130, 64, 192, 128, 100, 3), (65, 32, 64, 192, 262, 2), (200, 32, 128, 256, 37, 3),
+              (8256, 32, 64, 64, 40, 2)]
+# the instantiation each case is judged in: (loss, target type, row-mapped); its target type and its row map are each flipped once more
+# in a launch that must repeat the judged one bit for bit, so a case runs three of the eight instantiations of its dtype
+STEP_VARIANTS = [("mse", "u8", False), ("bce", "f32", True), ("mse", "f32", True), ("bce", "u8", False), ("mse", "u8", True), ("bce", "f32", False)]
+
+
+def step_instantiations(i):
+    loss, tgt, rows = STEP_VARIANTS[i]
+    return {(loss, tgt, rows), (loss, "f32" if tgt == "u8" else "u8", rows), (loss, tgt, not rows)}
+
+
+def g1_eligible(E, N1, P, vocab, n_fonts):
+    return E % 32 == 0 and 0 < E <= 64 and N1 % 64 == 0 and 0 < N1 <= 256 and P % 64 == 0 and 0 < P <= 256 and vocab + n_fonts <= 264
+
+
+def g1_colsplit(is_bf16, B, P):
+    R, kb = G1_ROWS[is_bf16], G1_KB[is_bf16]
+    nrb, cs = (B + R - 1) // R, 4
+    while cs > 1 and ((P // cs) % kb or (P // 16) % cs or nrb * cs > 256):
+        cs //= 2
+    return cs
+
+
+def g1_blocks(is_bf16, B, P):
+    R = G1_ROWS[is_bf16]
+    return (B + R - 1) // R * g1_colsplit(is_bf16, B, P)
+
+
+def g1_layout(E, N1, P, vocab, n_fonts):
+    """a slab layout with the tensors out of order and space between them: name -> offset in floats, and the total"""
+    off, lay = 4, {}
+    for name, n in (("b2", P), ("emb", vocab * E), ("w1", N1 * E), ("font", n_fonts * E), ("w2", P * N1), ("b1", N1)):
+        lay[name] = off
+        off += (n + 3) // 4 * 4 + 8
+    return lay, off
+
+
+def _nudge(vals, base_bnd, coef, thresholds, b0, margin, step):
+    """the bias nearest b0, in steps of `step`, at which every vals + bias is more than margin x its bound away from every threshold; the
+    bound of an element is base_bnd + coef |bias|.  -> (bias, steps)"""
+    for j in range(4000):
+        for s in ((1,) if j == 0 else (1, -1)):
+            b = b0 + s * j * step
+            bnd = margin * (base_bnd + coef * abs(b))
+            if all(not bool(((vals + b - th).abs() <= bnd).any()) for th in thresholds):
+                return b, j
+    raise AssertionError("no bias within 4000 steps")
+
+
+def _near(x, bx, q):
+    """whether x lies within bx of a boundary of the bf16 cell that rounds to q (fused_ref's `near`), and the spacing there"""
+    ulp = bf16_ulp(q)
+    a, qa = x.abs(), q.abs()
+    lower = torch.where(qa == ulp * 128, ulp / 4, ulp / 2)
+    dist = torch.minimum((a - (qa + ulp / 2)).abs(), (a - (qa - lower)).abs())
+    return (dist <= bx) & (bx > 0), ulp
+
+
+def _round_point(x, bx, rnd, shares, name):
+    """a rounding point of the bf16 kernel: -> rnd(x) and the carried bound, widened by one ulp where x is near a rounding boundary"""
+    if rnd is None:
+        return x, bx
+    q = rnd(x)
+    near, ulp = _near(x, bx, q)
+    shares[name] = float(near.double().mean()) if near.numel() else 0.0
+    return q, bx + near * ulp
+
+
+def step_targets(B, P, tid=930):
+    """u8 pixel values [B][P] with 0 and 255 among them"""
+    k = torch.from_numpy(synth.hash_u8(tid, (B, P)).astype(np.int64))
+    k[0, 0], k[-1, -1] = 0, 255
+    return k
+
+
+def target_values(k):
+    """pixel / 255.0f as the kernels take it: one float32 division"""
+    return torch.from_numpy(k.numpy().astype(np.float32) / np.float32(255.0))
+
+
+def step_rowmap(B, tid=940):
+    """-> (rows of a data set of B + 19 rows, with duplicates; the table's size)"""
+    n = B + 19
+    rows = np.floor(synth.hash_u01(tid, B) * n).astype(np.int64).clip(0, n - 1)
+    if B >= 2:
+        rows[1] = rows[0]
+    if B >= 8:
+        rows[B - 1] = rows[B // 2]
+    return torch.from_numpy(rows), n
+
+
+def step_target_forms(B, P):
+    """-> u8 targets dense [B][P], the row map [B], and the table [B + 19][P] that holds glyph b's targets at row rows[b] (glyphs that
+    share a row share their targets)"""
+    rows, n = step_rowmap(B)
+    first = {}
+    k = step_targets(B, P)[[first.setdefault(r, b) for b, r in enumerate(rows.tolist())]]
+    table = step_targets(n, P, tid=960)
+    table[rows] = k
+    return k, rows, table
+
+
+def step_inputs(case, is_bf16, planted=True):
+    """The inputs of a fused-step case in the operand type's exact values (float32 tensors): tables and ids as make_tables(.., 900) and
+    make_ids(.., 910), W2 = hash_uniform(920) 1.6 / sqrt(N1), b2 = 0.5 + hash_uniform(921) 0.3; then each b1[n] moves in steps of 2^-14 until
+    every |pre1| of the batch exceeds 8 x its bound, and each b2[p] in steps of 2^-12 until every u is 4 x its bound away from 0 and from
+    1 (bf16: 1 + 2^-8): no gate of the kernel is left to its rounding.  Two planted columns sit ON the inclusive clamp's edges, exactly:
+    W2[p0] = 0, b2[p0] = 1 and W2[p1] = 0, b2[p1] = 0.  -> dict, `steps` = the most steps a b1 / a b2 took"""
+    B, E, N1, P, vocab, n_fonts = case
+    t = make_tables(E, N1, vocab, n_fonts, 900)
+    x, font = make_ids(B, vocab, n_fonts, 910)
+    xc, fc, _ = clamp_ids(x, font, vocab, n_fonts)
+    rn = bf16 if is_bf16 else (lambda v: v)
+    W1, b1 = rn(t["W1"]), t["b1"].clone()
+    W2 = rn(torch.from_numpy(synth.hash_uniform(920, (P, N1), 1.6 / N1 ** 0.5)))
+    b2 = (0.5 + torch.from_numpy(synth.hash_uniform(921, (P,), 0.3))).float()
+    p0, p1 = 3, P - 2
+    if planted:
+        W2[p0], W2[p1], b2[p0], b2[p1] = 0.0, 0.0, 1.0, 0.0
+    h0 = rn(embed_ref(t["emb"], t["femb"], xc, fc, n_fonts, F32)).double()
+    acc, mag = h0 @ W1.double().t(), (E + 2) * U * (h0.abs() @ W1.double().abs().t())
+    s1 = s2 = 0
+    for n in range(N1):
+        b, j = _nudge(acc[:, n], mag[:, n], (E + 2) * U, (0.0,), float(b1[n]), 8.0, 2.0 ** -14)
+        b1[n], s1 = b, max(s1, j)
+    I = dict(emb=t["emb"], femb=t["femb"], W1=W1, b1=b1, W2=W2, b2=b2, x=x, font=font, xc=xc, fc=fc, planted=(p0, p1) if planted else ())
+    pre = acc + b1.double()
+    bpre = mag + (E + 2) * U * b1.double().abs()
+    h1, bh1 = _round_point(pre.clamp_min(0), bpre * (pre > 0), bf16 if is_bf16 else None, {}, "h1")
+    acc2 = h1 @ W2.double().t()
+    mag2 = (N1 + 2) * U * (h1.abs() @ W2.double().abs().t()) + bh1 @ W2.double().abs().t()
+    for p in range(P):
+        if planted and p in (p0, p1):
+            continue
+        b, j = _nudge(acc2[:, p], mag2[:, p], (N1 + 2) * U, (0.0, 1.0 + (UB if is_bf16 else 0.0)), float(b2[p]), 4.0, 2.0 ** -12)
+        b2[p], s2 = b, max(s2, j)
+    I["steps"] = (s1, s2)
+    return I
+
+
+def step_ref(I, case, is_bf16, loss, cs, t, mean_elems, rnd="kernel", fault=None):
+    """The whole fused step in fp64.  I: step_inputs; t: the targets [B][P] as values (target_values), dense; rnd: "kernel" = the rounding
+    points of the instantiation (bf16: six; float32: none), None = the unrounded model.  -> dict of per-block tensors, first two axes
+    (row block, column range): dW2 [.., P/cs, N1], db2 [.., P/cs], dW1 [.., N1, E], db1 [.., N1], dTab [.., rows, E], lpart [..] (the
+    block's loss sum), each with its bound under "b" + name; used [row blocks][rows] bool; loss and bloss; near: rounding point -> share
+    of elements near a boundary; pre, bpre and u, bu [B][..] ahead of their rounding, for the margins.  The unrounded model adds the two
+    embedding rows in fp64; the kernel's float32 add is restated exactly otherwise.
+    fault (tests/test_glyph_ref_cpu.py plants one at a time): "dead_rows", "all_cols", "exclusive", "font_row", "unsplit_round"."""
+    B, E, N1, P, vocab, n_fonts = case
+    R, Rt, pcs = G1_ROWS[is_bf16], vocab + n_fonts, P // cs
+    rn = bf16 if (is_bf16 and rnd is not None) else None
+    near = {}
+    xc, fc = I["xc"], I["fc"]
+    W1, W2, b1, b2 = I["W1"].double(), I["W2"].double(), I["b1"].double(), I["b2"].double()
+    nrb = (B + R - 1) // R
+    Bp, live = nrb * R, torch.arange(nrb * R) < B
+    if Bp > B:        # the rows past the batch: the kernel runs them on code 0, font 0 and the last glyph's targets, and drops what they give
+        pad = Bp - B
+        xc, fc = torch.cat([xc, torch.zeros(pad, dtype=xc.dtype)]), torch.cat([fc, torch.zeros(pad, dtype=fc.dtype)])
+        t = torch.cat([t, t[-1:].expand(pad, P)])
+    t = t.double()
+    if fault == "dead_rows":
+        live = torch.ones(Bp, dtype=torch.bool)
+    lv = live.double()[:, None]
+    h0 = embed_ref(I["emb"], I["femb"], xc, fc, n_fonts, F64 if rnd is None else F32)      # the kernel's h0 is one float32 add, exact here
+    h0 = (h0 if rn is None else rn(h0)).double()
+    pre = h0 @ W1.t() + b1
+    bpre = (E + 2) * U * (h0.abs() @ W1.abs().t() + b1.abs())
+    gate1 = pre > 0
+    h1, bh1 = _round_point(pre.clamp_min(0), bpre * gate1, rn, near, "h1")
+    u = h1 @ W2.t() + b2
+    bu = (N1 + 2) * U * (h1.abs() @ W2.abs().t() + b2.abs()) + bh1 @ W2.abs().t()
+    ur, bur = _round_point(u, bu, rn, near, "u")
+    inv_n = 1.0 / mean_elems
+    if loss == "mse":
+        gate2 = ((ur > 0) & (ur < 1)) if fault == "exclusive" else ((ur >= 0) & (ur <= 1))
+        diff = ur.clamp(0, 1) - t
+        du, lt = 2 * inv_n * diff * gate2, diff * diff
+        bdu_c = 2 * inv_n * bur * gate2
+        blt = 4 * U * lt + 2 * diff.abs() * bur + bur * bur
+        own = gate2.double()
+    else:
+        s = torch.sigmoid(ur)
+        du = (s - t) * inv_n
+        lt = ur.clamp_min(0) - t * ur + torch.log1p(torch.exp(-ur.abs()))
+        bdu_c = 0.25 * inv_n * bur
+        blt = 4 * U * (ur.abs() * (1 + t) + 1) + (s - t).abs() * bur + bur * bur
+        own = torch.ones_like(du)
+    du, lt, blt = du * lv, lt * lv, blt * lv
+    bdu = (bdu_c + 1e-6 * float(du.abs().max()) * own) * lv
+    du, bdu = _round_point(du, bdu, rn, near, "du")
+    oh = torch.zeros(Bp, Rt, dtype=F64)
+    rows_live = torch.arange(Bp)[live]
+    oh[rows_live, xc[live]] = 1
+    if n_fonts > 0:
+        oh[rows_live, (0 if fault == "font_row" else vocab) + fc[live]] = 1
+    blk = lambda v: v.reshape(nrb, R, *v.shape[1:])                     # noqa: E731
+    h1b, bh1b, h0b, ohb = blk(h1), blk(bh1), blk(h0), blk(oh)
+    out = {k: [] for k in ("dW2", "bdW2", "db2", "bdb2", "dW1", "bdW1", "db1", "bdb1", "dTab", "bdTab", "lpart", "blpart")}
+    n_d1 = n_dh0 = 0.0
+    for pc in range(cs):
+        cols = slice(pc * pcs, (pc + 1) * pcs)
+        d, bd = blk(du[:, cols]), blk(bdu[:, cols])
+        out["dW2"].append(torch.einsum("nbp,nbk->npk", d, h1b))
+        out["bdW2"].append((R + 2) * U * torch.einsum("nbp,nbk->npk", d.abs(), h1b.abs()) + torch.einsum("nbp,nbk->npk", bd, h1b.abs() + bh1b)
+                           + torch.einsum("nbp,nbk->npk", d.abs(), bh1b))
+        out["db2"].append(d.sum(1))
+        out["bdb2"].append((R + 2) * U * d.abs().sum(1) + bd.sum(1))
+        out["lpart"].append(blk(lt[:, cols]).sum((1, 2)))
+        out["blpart"].append(blk(blt[:, cols]).sum((1, 2)))
+        dc = slice(None) if fault == "all_cols" else cols
+        K = P if fault == "all_cols" else pcs
+        dh1 = du[:, dc] @ W2[dc]
+        bdh1 = (K + 2) * U * (du[:, dc].abs() @ W2[dc].abs()) + bdu[:, dc] @ W2[dc].abs()
+        sh = {}
+        d1, bd1 = _round_point(dh1 * gate1, bdh1 * gate1, rn, sh, "d1")
+        dh0 = d1 @ W1
+        bdh0 = (N1 + 2) * U * (d1.abs() @ W1.abs()) + bd1 @ W1.abs()
+        if fault == "unsplit_round" and rn is not None:                 # a kernel that rounded its share of the UNSPLIT dh0
+            full = ((du @ W2) * gate1)
+            dh0q, bdh0q = rn(rn(full) @ W1) / cs, bdh0
+        else:
+            dh0q, bdh0q = _round_point(dh0, bdh0, rn, sh, "dh0")
+        n_d1, n_dh0 = n_d1 + sh.get("d1", 0.0) / cs, n_dh0 + sh.get("dh0", 0.0) / cs
+        d1b, bd1b = blk(d1), blk(bd1)
+        out["dW1"].append(torch.einsum("nbk,nbe->nke", d1b, h0b))
+        out["bdW1"].append((R + 2) * U * torch.einsum("nbk,nbe->nke", d1b.abs(), h0b.abs()) + torch.einsum("nbk,nbe->nke", bd1b, h0b.abs()))
+        out["db1"].append(d1b.sum(1))
+        out["bdb1"].append((R + 2) * U * d1b.abs().sum(1) + bd1b.sum(1))
+        out["dTab"].append(torch.einsum("nbr,nbe->nre", ohb, blk(dh0q)))
+        out["bdTab"].append((R + 2) * U * torch.einsum("nbr,nbe->nre", ohb, blk(dh0q).abs()) + torch.einsum("nbr,nbe->nre", ohb, blk(bdh0q)))
+    out = {k: torch.stack(v, 1) for k, v in out.items()}
+    if rn is not None:
+        near["d1"], near["dh0"] = n_d1, n_dh0
+    total = float(out["lpart"].sum())
+    out.update(used=ohb.sum(1) > 0, near=near, loss=total * inv_n, bloss=(float(out["blpart"].sum()) + LOSS_DEPTH * U * total) * inv_n,
+               u=u[:B], bu=bu[:B], pre=pre[:B], bpre=bpre[:B], du=du[:B], h1=h1[:B], bh1=bh1[:B])
+    return out
+
+
+def step_model(I, case, is_bf16, loss, cs, t, mean_elems):
+    """The UNROUNDED model (rnd = None: fp64, the two embedding rows added in fp64) as the gradient step_total names, and an a-priori
+    bound M of how far the kernel's arithmetic, taken as exact between its rounding points, may lie from it -- from the unrounded values
+    alone, nothing of step_ref's rounded chain or of a kernel's output enters.  r = 2^-9 in bf16 (half a bf16 ulp, relative: round to
+    nearest) at each of the six rounding points h0, h1, u, du, dpre1, dh0, and 0 in float32, where only the float32 add of the two
+    embedding rows (u |h0|) separates the kernel from the model.  Every term is carried on linearly, with the product where two inexact
+    factors meet; relu and clamp are 1-Lipschitz; sigmoid 1/4.  A GATE is not continuous: where |pre1| <= M_pre1 the rounded chain may
+    open or close the ReLU gate against the model, and dpre1 there is held to |dh1| + M_dh1; where u lies within M_u of 0 or of 1 the
+    clamp gate likewise, and du there to |2 / n (clamp(u) - t)| + 2 / n M_u (the planted columns' u is exact in every chain: M_u = 0,
+    their gate is the model's).  dpre1 and dh0 are rounded per column range (cs of them),
+    so their terms are formed per range and summed.  -> (model gradient, M), both dicts as step_total's."""
+    B, E, N1, P, vocab, n_fonts = case
+    r, pcs, inv_n = (UB / 2 if is_bf16 else 0.0), P // cs, 1.0 / mean_elems
+
+    def rt(v, m):        # the rounding's own term; none where an exactly representable value arrives without error (the planted columns' u)
+        return r * (v.abs() + m) * ~((m == 0) & (bf16(v) == v))
+    xc, fc, t = I["xc"], I["fc"], t.double()
+    W1, W2, b1, b2 = I["W1"].double(), I["W2"].double(), I["b1"].double(), I["b2"].double()
+    h0 = embed_ref(I["emb"], I["femb"], xc, fc, n_fonts, F64)
+    m_h0 = (U + r * (1 + U)) * h0.abs()
+    pre = h0 @ W1.t() + b1
+    m_pre = m_h0 @ W1.abs().t()
+    gate1, open1 = pre > 0, pre.abs() <= m_pre                       # open1: the gate is the rounded chain's to decide
+    h1 = pre.clamp_min(0)
+    m_h1 = m_pre + rt(h1, m_pre)
+    u = h1 @ W2.t() + b2
+    m_u = m_h1 @ W2.abs().t()
+    m_u = m_u + rt(u, m_u)
+    if loss == "mse":
+        d_open = 2 * inv_n * (u.clamp(0, 1) - t)
+        gate2 = (u >= 0) & (u <= 1)
+        open2 = ((u.abs() <= m_u) | ((u - 1).abs() <= m_u)) & (m_u > 0)
+        du = d_open * gate2
+        m_du = torch.where(open2, d_open.abs() + 2 * inv_n * m_u, 2 * inv_n * m_u * gate2)
+        mag = torch.where(open2, d_open.abs(), du.abs())
+    else:
+        du = (torch.sigmoid(u) - t) * inv_n
+        m_du, mag = 0.25 * inv_n * m_u, du.abs()
+    m_du = m_du + r * (mag + m_du)
+    oh = torch.zeros(B, vocab + n_fonts, dtype=F64)
+    oh[torch.arange(B), xc] = 1
+    if n_fonts > 0:
+        oh[torch.arange(B), vocab + fc] = 1
+    g = dict(w2=du.t() @ h1, b2=du.sum(0), w1=torch.zeros(N1, E, dtype=F64), b1=torch.zeros(N1, dtype=F64), tab=torch.zeros(vocab + n_fonts, E, dtype=F64))
+    M = dict(w2=m_du.t() @ (h1 + m_h1) + du.abs().t() @ m_h1, b2=m_du.sum(0), w1=torch.zeros_like(g["w1"]), b1=torch.zeros_like(g["b1"]),
+             tab=torch.zeros_like(g["tab"]))
+    for pc in range(cs):
+        cols = slice(pc * pcs, (pc + 1) * pcs)
+        dh1 = du[:, cols] @ W2[cols]
+        m_dh1 = m_du[:, cols] @ W2[cols].abs()
+        d1 = dh1 * gate1
+        m_d1 = torch.where(open1, dh1.abs() + m_dh1, m_dh1 * gate1)
+        m_d1 = m_d1 + r * (torch.where(open1, dh1.abs(), d1.abs()) + m_d1)
+        dh0 = d1 @ W1
+        m_dh0 = m_d1 @ W1.abs()
+        m_dh0 = m_dh0 + r * (dh0.abs() + m_dh0)
+        g["w1"] += d1.t() @ h0
+        g["b1"] += d1.sum(0)
+        g["tab"] += oh.t() @ dh0
+        M["w1"] += m_d1.t() @ (h0.abs() + m_h0) + d1.abs().t() @ m_h0
+        M["b1"] += m_d1.sum(0)
+        M["tab"] += oh.t() @ m_dh0
+    return g, M
+
+
+def step_total(ref, case):
+    """the block references summed into the gradient: dict emb+font rows [rows][E], w1, b1, w2, b2"""
+    B, E, N1, P, vocab, n_fonts = case
+    return dict(tab=ref["dTab"].sum((0, 1)), w1=ref["dW1"].sum((0, 1)), b1=ref["db1"].sum((0, 1)),
+                w2=ref["dW2"].sum(0).reshape(P, N1), b2=ref["db2"].sum(0).reshape(P))
+
+
+def step_autograd(I, case, loss, t, mean_elems):
+    """Embedding (+ font) -> Linear -> ReLU -> Linear -> clamp + MSE (or BCE with logits) in torch, fp64, autograd: the gradients as
+    step_total names them, and the loss"""
+    B, E, N1, P, vocab, n_fonts = case
+    leaf = lambda v: v.double().clone().requires_grad_(True)            # noqa: E731
+    emb, W1, b1, W2, b2 = leaf(I["emb"]), leaf(I["W1"]), leaf(I["b1"]), leaf(I["W2"]), leaf(I["b2"])
+    femb = leaf(I["femb"]) if n_fonts > 0 else None
+    h0 = torch.nn.functional.embedding(I["xc"], emb)
+    if n_fonts > 0:
+        h0 = h0 + torch.nn.functional.embedding(I["fc"], femb)
+    u = torch.nn.functional.linear(torch.relu(torch.nn.functional.linear(h0, W1, b1)), W2, b2)
+    if loss == "mse":
+        L = ((u.clamp(0, 1) - t.double()) ** 2).sum() / mean_elems
+    else:
+        L = torch.nn.functional.binary_cross_entropy_with_logits(u, t.double(), reduction="sum") / mean_elems
+    L.backward()
+    tab = torch.cat([emb.grad, femb.grad]) if n_fonts > 0 else emb.grad
+    return dict(tab=tab, w1=W1.grad, b1=b1.grad, w2=W2.grad, b2=b2.grad), float(L.detach())
+
+
+def slab_views(slabs, lay, case, cs):
+    """slabs [blocks][total] -> per block (first two axes: row block, column range) dW2 / db2 (the block's OWN rows), dW1, db1, dTab"""
+    B, E, N1, P, vocab, n_fonts = case
+    nb, pcs = slabs.shape[0], P // cs
+    s = slabs.reshape(nb // cs, cs, -1)
+    seg = lambda name, n: s[:, :, lay[name]:lay[name] + n]              # noqa: E731
+    w2, b2 = seg("w2", P * N1).reshape(-1, cs, cs, pcs, N1), seg("b2", P).reshape(-1, cs, cs, pcs)
+    idx = torch.arange(cs)
+    tab = seg("emb", vocab * E)
+    if n_fonts > 0:
+        tab = torch.cat([tab, seg("font", n_fonts * E)], 2)
+    return dict(dW2=w2[:, idx, idx], db2=b2[:, idx, idx], dW1=seg("w1", N1 * E).reshape(-1, cs, N1, E), db1=seg("b1", N1),
+                dTab=tab.reshape(-1, cs, vocab + n_fonts, E))
+
+
+def slab_owned(lay, total, case, cs):
+    """bool [cs][total]: the elements of a slab that a block of column range pc writes"""
+    B, E, N1, P, vocab, n_fonts = case
+    own = torch.zeros(cs, total, dtype=torch.bool)
+    for name, n in (("emb", vocab * E), ("font", n_fonts * E), ("w1", N1 * E), ("b1", N1)):
+        own[:, lay[name]:lay[name] + n] = True
+    pcs = P // cs
+    for pc in range(cs):
+        own[pc, lay["w2"] + pc * pcs * N1:lay["w2"] + (pc + 1) * pcs * N1] = True
+        own[pc, lay["b2"] + pc * pcs:lay["b2"] + (pc + 1) * pcs] = True
+    return own

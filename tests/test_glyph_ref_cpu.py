@@ -5,7 +5,11 @@ slabs without its rounding, the plain embedding backward) equals autograd's to 1
 replay bit for bit stay inside their fp64 bounds; (c) at the case shapes at most 0.1 % of the ReLU gates sit closer to zero than the
 bound of their pre-activation, from the reference inputs alone; (d) the getters answer what the checker's mirrors say; (e) every
 refusal returns its code and message -- none of them launches anything (the pointers are not memory, so every call made here must
-be one that is refused)."""
+be one that is refused).  For the fused step (step_ref, afr_op_glyph1_step) and the entries beside it: (f) the unrounded block
+references of the kernel's own split sum to autograd's gradients and loss of the whole net to 1e-12; (g) on every case's final inputs no
+ReLU or clamp gate is within 8 x / 4 x its bound of its threshold, and the planted columns sit on the clamp's edges exactly; (h) six
+planted faults each break a bound, in float32 and in bf16; (i) getters and mirrors agree; (j) the refusals of the three entries; (k) step_model, the a-priori distance
+of the kernel's arithmetic from the unrounded model: the rounded references' sum lies within it, planted faults' sums do not."""
 import ctypes as C
 
 import pytest
@@ -107,7 +111,7 @@ def test_b_fused_rounding_point_matters():
 
 
 # --------------------------------------------------------------------------------------------------------- (c)
-@pytest.mark.parametrize("case", [c[:6] for c in R.COMBO_CASES], ids=str)
+@pytest.mark.parametrize("case", [c[:6] for c in R.COMBO_CASES] + R.L1_FWD_CASES, ids=str)
 def test_c_relu_gates_near_zero_stay_under_the_cap(case):
     B, E, N1, vocab, n_fonts, kind = case
     t = R.make_tables(E, N1, vocab, n_fonts, 100)
@@ -222,3 +226,178 @@ def test_e_a_plan_whose_embedding_backward_cannot_fit_is_refused_at_creation():
         c = make_afr_config(cfg, "f32", 8)
         assert lib.afr_plan_create(C.byref(c), C.byref(plan)) == 0, lib.afr_last_error()
         lib.afr_plan_destroy(plan)
+
+
+# --------------------------------------------------------------------------------------------------------- the fused step's checker
+def _step(case, is_bf16, loss, **kw):
+    B, E, N1, P, vocab, n_fonts = case
+    I = R.step_inputs(case, is_bf16)
+    k, rows, table = R.step_target_forms(B, P)
+    cs = R.g1_colsplit(is_bf16, B, P)
+    return I, k, rows, table, cs, R.step_ref(I, case, is_bf16, loss, cs, R.target_values(k), B * P + 7, **kw)
+
+
+@pytest.mark.parametrize("case,loss", [((130, 64, 192, 128, 100, 3), "mse"), ((65, 32, 64, 192, 262, 2), "bce")])
+def test_f_step_ref_unrounded_is_autograd(case, loss):
+    """Embedding (+ font) -> Linear -> ReLU -> Linear -> clamp + MSE / BCE with logits, mean_elems != B P: the block references of the
+    kernel's own split, summed, are autograd's gradients"""
+    B, E, N1, P, vocab, n_fonts = case
+    for is_bf16 in (False, True):
+        I, k, _, _, cs, ref = _step(case, is_bf16, loss, rnd=None)
+        assert cs > 1
+        want, L = R.step_autograd(I, case, loss, R.target_values(k), B * P + 7)
+        got = R.step_total(ref, case)
+        for name in want:
+            assert rel(got[name], want[name]) <= 1e-12, name
+        assert abs(ref["loss"] - L) <= 1e-12 * abs(L)
+
+
+@pytest.mark.parametrize("case", R.STEP_CASES, ids=str)
+def test_g_no_gate_of_the_fused_step_is_left_to_rounding(case):
+    B, E, N1, P, vocab, n_fonts = case
+    for is_bf16 in (False, True):
+        I, _, _, _, _, ref = _step(case, is_bf16, "mse")
+        assert I["steps"][0] <= 2 and I["steps"][1] <= 15, I["steps"]
+        assert bool((ref["pre"].abs() > 8 * ref["bpre"]).all())
+        p0, p1 = I["planted"]
+        keep = torch.ones(P, dtype=torch.bool)
+        keep[[p0, p1]] = False
+        u, bu = ref["u"][:, keep], ref["bu"][:, keep]
+        for edge in (0.0, 1.0 + (R.UB if is_bf16 else 0.0)):
+            assert bool(((u - edge).abs() > 4 * bu).all()), edge
+        # the planted columns sit on the inclusive clamp's edges, exactly, and their gates are open
+        assert bool((ref["u"][:, p0] == 1.0).all()) and bool((ref["u"][:, p1] == 0.0).all())
+        assert 0.4 <= float((ref["pre"] > 0).double().mean()) <= 0.6
+        inside = float(((ref["u"] >= 0) & (ref["u"] <= 1)).double().mean())
+        assert 0.7 <= inside <= 0.97, inside
+        print(f"{case} {'bf16' if is_bf16 else 'f32'}: b1 / b2 steps {I['steps']}, u inside [0, 1] {inside:.3f}, near " +
+              ", ".join(f"{k} {v:.4f}" for k, v in ref["near"].items()))
+        assert ref["near"].get("h1", 0.0) <= 0.02
+
+
+STEP_FAULTS = [("dead_rows", (95, 32, 256, 256, 128, 0), "bce"), ("all_cols", (95, 32, 256, 256, 128, 0), "mse"), ("exclusive", (130, 64, 192, 128, 100, 3), "mse"),
+               ("font_row", (200, 32, 128, 256, 37, 3), "mse"), ("row_map", (95, 32, 256, 256, 128, 0), "bce"), ("unsplit_round", (200, 32, 128, 256, 37, 3), "mse")]
+
+
+@pytest.mark.parametrize("fault,case,loss", STEP_FAULTS, ids=lambda v: str(v))
+def test_h_a_planted_fault_of_the_fused_step_breaks_a_bound(fault, case, loss):
+    """one fault at a time in what a kernel could leave: some output exceeds its bound, in float32 and in bf16 (the rounding point: bf16)"""
+    B, E, N1, P, vocab, n_fonts = case
+    for is_bf16 in ((True,) if fault == "unsplit_round" else (False, True)):
+        I, k, rows, table, cs, ref = _step(case, is_bf16, loss)
+        if fault == "row_map":            # the targets of row b of the table instead of row rows[b]
+            got = R.step_ref(I, case, is_bf16, loss, cs, R.target_values(table[:B]), B * P + 7)
+        else:
+            got = R.step_ref(I, case, is_bf16, loss, cs, R.target_values(k), B * P + 7, fault=fault)
+        ratios = {n: R.ratio(got[n], ref[n], ref["b" + n]) for n in ("dW2", "db2", "dW1", "db1", "dTab")}
+        ratios["loss"] = abs(got["loss"] - ref["loss"]) / ref["bloss"]
+        print(f"{fault} {case} {'bf16' if is_bf16 else 'f32'}: " + ", ".join(f"{n} {v:.3g}" for n, v in ratios.items()))
+        assert max(ratios.values()) > 1.0
+        if fault == "exclusive":          # seen at the planted columns: db2 of the column whose u is exactly 1
+            bad = ((got["db2"] - ref["db2"]).abs() > ref["bdb2"]).reshape(-1, P)            # [row block][column]
+            assert all(bool(bad[:, p].any()) for p in I["planted"])                        # u exactly 1, and u exactly 0
+
+
+def test_i_fused_step_getters_answer_the_mirrors():
+    from ai_font_renderer_amd import _lib
+    lib = _lib.lib()
+    for bf, dtype in ((False, _lib.AFR_F32), (True, _lib.AFR_BF16)):
+        assert lib.afr_glyph1_rows(dtype) == R.G1_ROWS[bf]
+        for B in (1, 16, 17, 64, 65, 95, 1024, 1025, 2048, 4096, 4097, 8256, 16385):
+            for P in (64, 128, 192, 256):
+                assert lib.afr_glyph1_colsplit(dtype, B, P) == R.g1_colsplit(bf, B, P), (bf, B, P)
+                assert lib.afr_glyph1_blocks(dtype, B, P) == R.g1_blocks(bf, B, P)
+    assert [lib.afr_glyph1_colsplit(_lib.AFR_F32, B, 256) for B in (95, 1024, 1025, 2048, 2049)] == [4, 4, 2, 2, 1]
+    assert [lib.afr_glyph1_colsplit(_lib.AFR_BF16, B, 64) for B in (1, 8192, 8256)] == [2, 2, 1]
+    for case in R.STEP_CASES:
+        assert lib.afr_glyph1_eligible(*case[1:]) == 1 and R.g1_eligible(*case[1:])
+    for args in ((16, 64, 64, 5, 0), (96, 64, 64, 5, 0), (32, 96, 64, 5, 0), (32, 320, 64, 5, 0), (32, 64, 32, 5, 0), (32, 64, 320, 5, 0), (32, 64, 64, 263, 2),
+                 (32, 64, 64, 265, 0)):
+        assert lib.afr_glyph1_eligible(*args) == 0 and not R.g1_eligible(*args), args
+    assert lib.afr_glyph1_eligible(64, 256, 256, 262, 2) == 1
+
+
+def test_j_refusals_of_the_step_forward_and_transpose_entries():
+    from ai_font_renderer_amd import _lib
+    lib = _lib.lib()
+    EI, EU = _lib.AFR_EINVAL, _lib.AFR_EUNSUPPORTED
+    fk = C.c_void_p(0x1000)                                   # not memory: a launch on it could not succeed
+    err = lib.afr_last_error
+
+    def fwd(dt=0, emb=fk, femb=fk, W1=fk, b1=fk, x=fk, font=fk, B=4, E=32, N1=64, vocab=128, nf=2, table=fk, h0p=fk, h1=fk, w1t=None, er=fk):
+        return lib.afr_op_glyph_l1_fwd(dt, emb, femb, W1, b1, x, font, B, E, N1, vocab, nf, table, h0p, h1, w1t, er, None)
+
+    lay0 = dict(emb=0, font=4096, w1=4160, b1=6208, w2=6272, b2=10368, total=10432)      # vocab 128, 2 fonts, 32 -> 64 -> 64
+
+    def step(dt=1, loss=0, emb=fk, femb=fk, W1=fk, b1=fk, W2=fk, b2=fk, W1T=fk, W2T=fk, x=fk, font=fk, target=fk, tdt=0, rows=None, B=4, E=32, N1=64,
+             P=64, vocab=128, nf=2, mean=256, slabs=fk, lay=lay0, accum=fk, scratch=fk, er=fk):
+        la = _lib.AfrGlyph1Layout(*[lay[n] for n in ("emb", "font", "w1", "b1", "w2", "b2", "total")]) if lay is not None else None
+        return lib.afr_op_glyph1_step(dt, loss, emb, femb, W1, b1, W2, b2, W1T, W2T, x, font, target, tdt, rows, B, E, N1, P, vocab, nf, mean, slabs,
+                                      C.byref(la) if la is not None else None, accum, scratch, er, None)
+
+    def tr(W=fk, WT=fk, N=8, K=8):
+        return lib.afr_op_transpose_bf16(W, WT, N, K, None)
+
+    for call in (fwd, step):
+        assert call(B=0) == EI and b"B = 0" in err()
+        assert call(vocab=0) == EI and b"vocab" in err()
+        assert call(nf=-1) == EI
+    # the folded forward: the plan's fold condition
+    assert fwd(dt=2) == EI and b"act_dtype" in err()
+    assert fwd(E=20) == EU and b"multiple of 8" in err() and fwd(N1=60) == EU and b"multiple of 8" in err()
+    assert fwd(vocab=479) == EU and b"K0 = 520" in err()
+    assert fwd(E=136, vocab=16) == EU and b"E = 136" in err()
+    for n in ("emb", "femb", "W1", "b1", "x", "table", "h0p", "h1", "er"):
+        assert fwd(**{n: None}) == EI and b"null" in err(), n
+    assert fwd(table=C.c_void_p(0x1008)) == EI and b"16-byte" in err()
+    # the fused step
+    assert step(dt=2) == EI and b"dtype" in err() and step(dt=-1) == EI
+    assert step(loss=2) == EI and b"loss kind" in err()
+    assert step(tdt=2) == EI and b"target_dtype" in err()
+    assert step(mean=0) == EI and b"mean_elems" in err()
+    for kw in (dict(E=16), dict(E=96), dict(N1=96), dict(N1=320), dict(P=32), dict(P=320), dict(vocab=263)):
+        assert step(**kw) == EU and b"fused step" in err(), kw
+    assert step(E=0) == EI and step(N1=0) == EI and step(P=-64) == EI
+    for n in ("emb", "femb", "W1", "b1", "W2", "b2", "W1T", "W2T", "x", "target", "slabs", "lay", "accum", "scratch", "er"):
+        assert step(**{n: None}) == EI and b"null" in err(), n
+    for n in ("W1", "W2", "W1T", "W2T", "slabs"):
+        assert step(**{n: C.c_void_p(0x1008)}) == EI and b"16-byte" in err(), n
+    for bad, word in ((dict(total=10434), b"multiple of 4"), (dict(total=10428), b"inside"), (dict(font=4092), b"overlap"), (dict(b1=-64), b"inside"),
+                      (dict(w1=4162), b"multiple of 4"), (dict(b2=6272), b"overlap")):
+        assert step(lay=dict(lay0, **bad)) == EI and word in err(), bad
+    assert step(vocab=129) == EI and b"overlap" in err()                                  # the layout was made for 128 rows
+    # the transpose
+    assert tr(N=0) == EI and tr(K=-1) == EI and b"N = " in err()
+    assert tr(W=None) == EI and tr(WT=None) == EI and b"null" in err()
+
+
+@pytest.mark.parametrize("i", range(len(R.STEP_CASES)), ids=lambda i: str(R.STEP_CASES[i]))
+def test_k_model_bound_is_a_priori_holds_the_reference_and_is_not_hollow(i):
+    """step_model: its gradient is the unrounded block references' sum; the ROUNDED references' sum -- what a correct kernel leaves, up to
+    the block bounds -- lies within its a-priori term M of it; and sums with a planted fault leave M + the summed block bounds"""
+    case, loss = R.STEP_CASES[i], R.STEP_VARIANTS[i][0]
+    B, E, N1, P, vocab, n_fonts = case
+    for is_bf16 in (False, True):
+        I, k, _, _, cs, ref = _step(case, is_bf16, loss)
+        t, n = R.target_values(k), B * P + 7
+        whole, M = R.step_model(I, case, is_bf16, loss, cs, t, n)
+        plain = R.step_total(R.step_ref(I, case, is_bf16, loss, cs, t, n, rnd=None), case)
+        mine = R.step_total(ref, case)
+        bsum = R.step_total({name: ref["b" + name] for name in ("dW2", "db2", "dW1", "db1", "dTab")}, case)
+        for name in whole:
+            assert rel(whole[name], plain[name]) <= 1e-12, name
+        ratios = {name: R.ratio(mine[name], whole[name], M[name]) for name in whole}
+        size = {name: float((bsum[name] + M[name]).max() / whole[name].abs().max()) for name in whole}
+        print(f"{case} {'bf16' if is_bf16 else 'f32'}: rounded reference / M " + ", ".join(f"{a} {v:.3f}" for a, v in ratios.items())
+              + "; largest bound / largest |gradient| " + ", ".join(f"{a} {v:.2g}" for a, v in size.items()))
+        assert max(ratios.values()) <= 1.0
+        if not is_bf16:
+            assert max(size.values()) <= 0.05              # float32: the whole bound stays far below the gradient's own size
+        assert size["w2"] <= 0.6 and size["b2"] <= 0.6      # bf16: dW2 / db2 stay below the gradient's own size at every case
+        faults = {(95, 32, 256, 256, 128, 0): ("dead_rows", "all_cols"), (200, 32, 128, 256, 37, 3): ("font_row", "all_cols"),
+                  (130, 64, 192, 128, 100, 3): ("exclusive", "dead_rows"), (65, 32, 64, 192, 262, 2): ("font_row", "dead_rows")}.get(case, ())
+        for fault in faults:
+            bad = R.step_total(R.step_ref(I, case, is_bf16, loss, cs, t, n, fault=fault), case)
+            worst = max(R.ratio(bad[name], whole[name], bsum[name] + M[name]) for name in whole)
+            print(f"    {fault}: {worst:.3g}")
+            assert worst > 1.0, fault

@@ -1,8 +1,8 @@
 """GPU: the glyph nets' first-layer kernels (csrc/elementwise.hip glyph_embed / glyph_combo / glyph_l1_bwd / glyph_embed_bwd,
 csrc/gemm.hip glyph_l1_bwd_fused), ONE launch each through the afr_op_glyph_* entries, every output element against the fp64
 restatement of tests/glyph_ref.py under its derived bound, or bit for bit where the kernel's arithmetic is one rounding or a stated
-float32 order.  (The table + gather pair of the folded forward, glyph_table / glyph_l1_fwd, has no entry of its own yet and is not
-covered here; the combination kernel runs the same arithmetic.)  The shapes are the smallest at which each mechanism can fail
+float32 order.  (The table + gather pair of the folded forward, glyph_table / glyph_l1_fwd, and the fused step are tested in
+tests/test_gpu_glyph_step_ops.py.)  The shapes are the smallest at which each mechanism can fail
 (tests/glyph_ref.py *_CASES): combination counts that end a group of four early (101, 111) or fill it, fc1 widths that end a 256-row
 chunk early, E at the combination kernel's staging limit (40) and at 8, K0 from 48 to the post-pass's limit of 512 (8, 3 and 1 lane
 groups), row blocks of the fused backward that are ragged (1, 63, 65, 200 glyphs) and full (64) in both h0 forms, its unsplit
@@ -30,27 +30,12 @@ import torch
 
 from ai_font_renderer_amd import _lib
 from . import glyph_ref as R
+from .glyph_harness import Tables, check_h1 as _check_h1, ids_dev as _ids
 from .gpu_util import dev, ptr, stream
 from .op_harness import Outs, bits, dt, judge, same, tt, twice
 
 pytestmark = pytest.mark.gpu
 F64, F32, BF16 = torch.float64, torch.float32, torch.bfloat16
-
-
-class Tables:
-    """a case's parameters on the device"""
-
-    def __init__(self, E, N1, vocab, n_fonts, tid):
-        self.E, self.N1, self.vocab, self.n_fonts = E, N1, vocab, n_fonts
-        self.t = R.make_tables(E, N1, vocab, n_fonts, tid)
-        self.d = {k: (dev(v) if v is not None else None) for k, v in self.t.items()}
-
-    def p(self, k):
-        return ptr(self.d[k])
-
-
-def _ids(x, font):
-    return dev(x), (dev(font) if font is not None else None)
 
 
 # ------------------------------------------------------------------------------------------------------------------ launches
@@ -141,14 +126,6 @@ def _fwd_reference(E, N1, vocab, n_fonts):
     T = Tables(E, N1, vocab, n_fonts, 100)
     Tr, Tb = R.table_ref(T.t["emb"], T.t["femb"], T.t["W1"], n_fonts)
     return T, Tr, Tb
-
-
-def _check_h1(name, got_h1, Tr, Tb, b1, xc, fc, vocab, n_fonts, is_bf16):
-    pre, bp, ref, bnd = R.h1_ref(Tr, Tb, b1, xc, fc, vocab, n_fonts, is_bf16)
-    flipped = (got_h1.double() > 0) != (pre > 0)
-    assert not bool((flipped & (pre.abs() > bp)).any()), f"{name}: a ReLU gate differs from fp64's where |pre| is above its bound"
-    assert int(flipped.sum()) <= 1e-3 * pre.numel()
-    return R.ratio(got_h1, ref, bnd), int(flipped.sum())
 
 
 # ------------------------------------------------------------------------------------------------------------------ combination table
