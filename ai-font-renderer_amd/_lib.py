@@ -99,6 +99,17 @@ class AfrLinearTail(C.Structure):
                 ("grad_scale", C.c_float), ("t", C.c_int64)]
 
 
+class AfrReduceStep(C.Structure):
+    """The fused optimizer step of one grouped reduce (include/afr.h afr_reduce_step): gbase, p, m, v, shadow are device pointers;
+    lr_mult, wd_mult, shT, tN, tK host arrays with one entry per segment, or NULL."""
+    _fields_ = [("opt_kind", C.c_int32), ("reserved", C.c_int32),
+                ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
+                ("reserved2", C.c_float), ("t", C.c_int64),
+                ("gbase", C.c_void_p), ("p", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("shadow", C.c_void_p),
+                ("lr_mult", C.POINTER(C.c_float)), ("wd_mult", C.POINTER(C.c_float)),
+                ("shT", C.POINTER(C.c_void_p)), ("tN", C.POINTER(C.c_int32)), ("tK", C.POINTER(C.c_int32))]
+
+
 class AfrGlyphAtlas(C.Structure):
     """The glyph atlas afr_op_compose_sheets blits from (include/afr.h afr_glyph_atlas); pointers are device pointers."""
     _fields_ = [("cells", C.c_void_p), ("adv64", C.c_void_p), ("kern64", C.c_void_p), ("n_codes", C.c_int32), ("cell_h", C.c_int32),
@@ -166,6 +177,8 @@ SIGNATURES = {
     "afr_op_linear": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.POINTER(AfrLinearTail), _vp, _sz, C.c_char_p, _i32, _vp]),
     "afr_op_reduce": (_i32, [_vp, _vp, _i32, _i64, _i64, _f32, _i32, _vp]),
     "afr_op_reduce_group": (_i32, [_i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64), _vp]),
+    "afr_op_reduce_group_step": (_i32, [_i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64),
+                                        C.POINTER(AfrReduceStep), C.c_char_p, _i32, _vp]),
     "afr_op_adamw": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _f32, _vp]),
     "afr_op_adamw_clip": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _f32, _vp, _f32, _vp]),
     "afr_op_lion": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _vp, _f32, _vp]),

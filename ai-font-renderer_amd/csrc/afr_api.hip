@@ -2230,19 +2230,68 @@ extern "C" int afr_op_reduce(float* dst, const float* slabs, int nslabs, int64_t
     HIPCHK(afr_launch_reduce(dst, slabs, nslabs, stride, n, scale, acc, (hipStream_t)stream));
     return AFR_OK;
 }
+// ---- afr_op_reduce_group_step: the grouped reduce as reduce_and_step issues it (afr_rtable_add, adam_hyper, group_args, the launcher)
+extern "C" int afr_op_reduce_group_step(int nseg, float* const* dst, const float* const* slabs, const int* nslabs, const int64_t* stride,
+                                        const int64_t* n, const afr_reduce_step* step, char* kernel_name, int name_cap, void* stream) {
+    const char* who = "afr_op_reduce_group_step";
+    if (nseg < 1 || nseg > AFR_RT_MAXSEG) return fail(AFR_EINVAL, "a grouped reduce takes 1 to at most %d segments (got %d)", AFR_RT_MAXSEG, nseg);
+    if (!dst || !slabs || !nslabs || !stride || !n) return fail(AFR_EINVAL, "%s: null segment array", who);
+    if (kernel_name && name_cap < 1) return fail(AFR_EINVAL, "%s: name_cap must be positive", who);
+    const bool fused = step && step->p;
+    const int kind = fused ? step->opt_kind : OPT_ADAMW;
+    if (step && !fused && step->shT) {
+        for (int i = 0; i < nseg; ++i) if (step->shT[i]) return fail(AFR_EINVAL, "segment %d: shT without a fused step (step->p is null)", i);
+    }
+    AdamArgs h{};
+    if (fused) {
+        if (kind != AFR_OPT_ADAMW && kind != AFR_OPT_LION) return fail(AFR_EINVAL, "optimizer kind must be AFR_OPT_ADAMW (0) or AFR_OPT_LION (1), got %d", kind);
+        if (!step->gbase || !step->m || (kind == AFR_OPT_ADAMW && !step->v)) return fail(AFR_EINVAL, "%s: fused step: null gbase or moment", who);
+        if (step->shT && (!step->tN || !step->tK)) return fail(AFR_EINVAL, "%s: shT without tN and tK", who);
+        if (kind == AFR_OPT_ADAMW) if (int rc = check_step_count(step->t)) return rc;
+        h = AdamArgs{step->lr, step->beta1, step->beta2, step->eps, step->weight_decay, kind == AFR_OPT_LION ? 1 : step->t};
+    }
+    const bool grouped = fused && (step->lr_mult || step->wd_mult);
+    RTable rt;
+    AdamHyper seg_ad[AFR_RT_MAXSEG];
+    if (fused) {
+        rt.adam = 1; rt.ad = adam_hyper(h, kind); rt.kind = kind;
+        rt.gbase = step->gbase; rt.P = step->p; rt.M = step->m; rt.V = kind == OPT_LION ? nullptr : step->v; rt.shadow = (bf16_t*)step->shadow;
+    }
+    for (int i = 0; i < nseg; ++i) {
+        if (!dst[i] || !slabs[i]) return fail(AFR_EINVAL, "segment %d: null pointer", i);
+        if (nslabs[i] < 1) return fail(AFR_EINVAL, "segment %d: nslabs = %d, must be >= 1", i, nslabs[i]);
+        if (n[i] < 0 || (n[i] & 3)) return fail(AFR_EINVAL, "segment %d: length %lld is negative or not a multiple of 4", i, (long long)n[i]);
+        if (stride[i] & 3) return fail(AFR_EINVAL, "segment %d: stride %lld is not a multiple of 4", i, (long long)stride[i]);
+        afr_opt_range r{0, 1.f, 1.f};
+        if (fused) {
+            const ptrdiff_t off = (const char*)dst[i] - (const char*)step->gbase;
+            if (off < 0 || (off & 15)) return fail(AFR_EINVAL, "segment %d: dst - gbase is negative or not a multiple of 4 elements", i);
+            if (step->lr_mult) r.lr_mult = step->lr_mult[i];
+            if (step->wd_mult) r.wd_mult = step->wd_mult[i];
+            if (!mult_ok(r.lr_mult) || !mult_ok(r.wd_mult)) return fail(AFR_EINVAL, "segment %d: the multipliers must be finite and >= 0", i);
+            if (step->shT && step->shT[i]) {
+                const int tN = step->tN[i], tK = step->tK[i];
+                if (tK < 4 || tK % 4) return fail(AFR_EINVAL, "segment %d: shT with tK = %d, must be a positive multiple of 4", i, tK);
+                if (n[i] % tK) return fail(AFR_EINVAL, "segment %d: shT with a length %lld that is no multiple of tK = %d", i, (long long)n[i], tK);
+                if (tN < n[i] / tK) return fail(AFR_EINVAL, "segment %d: shT with pitch tN = %d smaller than its %lld rows", i, tN, (long long)(n[i] / tK));
+            }
+        }
+        const int k = rt.nseg;            // the table's number of this segment: afr_rtable_add drops a segment with n == 0
+        afr_rtable_add(rt, dst[i], slabs[i], nslabs[i], stride[i], n[i]);
+        if (rt.nseg == k || !fused) continue;
+        seg_ad[k] = adam_hyper(group_args(h, r), kind);
+        if (step->shT && step->shT[i]) { rt.seg[k].shT = (bf16_t*)step->shT[i]; rt.seg[k].tN = step->tN[i]; rt.seg[k].tK = step->tK[i]; }
+    }
+    if (kernel_name) snprintf(kernel_name, name_cap, "%s", afr_reduce_group_kernel_name(rt, grouped ? seg_ad : nullptr));
+    DevGuard dg(device_of(fused ? (const void*)step->p : (const void*)dst[0]));
+    HIPCHK(afr_launch_reduce_group(rt, (hipStream_t)stream, grouped ? seg_ad : nullptr));
+    return AFR_OK;
+}
+// (no segments: nothing to do, as it has always answered; everything else is the step form's, refusals included)
 extern "C" int afr_op_reduce_group(int nseg, float* const* dst, const float* const* slabs, const int* nslabs, const int64_t* stride,
                                    const int64_t* n, void* stream) {
-    if (nseg < 0 || (nseg > 0 && (!dst || !slabs || !nslabs || !stride || !n))) return fail(AFR_EINVAL, "bad grouped-reduce arguments");
-    if (nseg > AFR_RT_MAXSEG) return fail(AFR_EINVAL, "a grouped reduce takes at most %d segments (got %d)", AFR_RT_MAXSEG, nseg);
-    RTable rt;
-    for (int i = 0; i < nseg; ++i) {
-        if (!dst[i] || !slabs[i] || nslabs[i] < 1 || n[i] < 0 || (n[i] & 3)) return fail(AFR_EINVAL, "segment %d: null pointer, no slabs or length not a multiple of 4", i);
-        afr_rtable_add(rt, dst[i], slabs[i], nslabs[i], stride[i], n[i]);
-    }
     if (nseg == 0) return AFR_OK;
-    DevGuard dg(device_of(dst[0]));
-    HIPCHK(afr_launch_reduce_group(rt, (hipStream_t)stream));
-    return AFR_OK;
+    return afr_op_reduce_group_step(nseg, dst, slabs, nslabs, stride, n, nullptr, nullptr, 0, stream);
 }
 extern "C" int afr_op_adamw(float* p, const float* g, float* m, float* v, void* shadow, int64_t n, float lr, float b1,
                             float b2, float eps, float wd, int64_t t, float gscale, void* stream) {

@@ -342,6 +342,7 @@ static_assert(sizeof(RTableG) <= 4096, "the grouped reduce's table travels by va
 void afr_rtable_add(RTable& t, float* dst, const float* src, int nslabs, long long stride, long long n);
 // seg_ad (optional, t.adam only): t.nseg hypers, segment k is updated with seg_ad[k] instead of t.ad
 hipError_t afr_launch_reduce_group(const RTable& t, hipStream_t s, const AdamHyper* seg_ad = nullptr);
+const char* afr_reduce_group_kernel_name(const RTable& t, const AdamHyper* seg_ad);      // "reduce_group<OPT,GROUPS>" of that launch
 // The flat optimizer update (elementwise.hip adamw_kernel / opt_groups_kernel): AdamW or Lion over n elements (a multiple of 4) of p, g, m, v
 // (and the bf16 shadow, optional), one launch.
 // lr and wd besides h: the kernel folds its decay = 1 - lr * wd on the device, as it always has; h.decay is not read.

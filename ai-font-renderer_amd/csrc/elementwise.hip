@@ -170,6 +170,11 @@ hipError_t afr_launch_reduce_group(const RTable& t, hipStream_t s, const AdamHyp
     with_opt(t.adam ? t.kind : OPT_ADAMW, [&](auto opt) { hipLaunchKernelGGL(reduce_group_kernel<opt()>, dim3(t.nblocks), dim3(256), 0, s, t); });
     return hipGetLastError();
 }
+// the instantiation afr_launch_reduce_group takes for (t, seg_ad), as <OPT,GROUPS>: the launcher's own two decisions, restated beside it
+const char* afr_reduce_group_kernel_name(const RTable& t, const AdamHyper* seg_ad) {
+    const bool lion = t.adam && t.kind == OPT_LION;
+    return seg_ad ? (lion ? "reduce_group<1,1>" : "reduce_group<0,1>") : (lion ? "reduce_group<1,0>" : "reduce_group<0,0>");
+}
 
 // -------------------------------------------------------------------------------------- AdamW
 // torch.optim.AdamW single-tensor update (reference model.py:273,310), one pass over p,g,m,v:

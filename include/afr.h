@@ -478,6 +478,36 @@ int afr_op_reduce(float* dst, const float* slabs, int nslabs, int64_t slab_strid
  * error (AFR_EINVAL), never a silent drop.  n[i] must be a multiple of 4. */
 int afr_op_reduce_group(int nseg, float* const* dst, const float* const* slabs, const int* nslabs,
                         const int64_t* stride, const int64_t* n, void* stream);
+/* The grouped reduce exactly as a single-GPU training step issues it, in ONE launch: the step's table (one entry per segment, in the
+ * caller's order), its hypers and its launcher; this entry adds no kernel and no dispatch rule.  step NULL, or step->p NULL: the plain
+ * reduce above (afr_op_reduce_group calls this entry).  With step->p: the FUSED optimizer step -- the summed gradient of segment i is
+ * not stored; opt_kind AFR_OPT_ADAMW / AFR_OPT_LION is applied to the flat elements [dst[i] - gbase, + n[i]) of p, m and v (Lion: v is
+ * neither read nor written and may be NULL) and of the bf16 `shadow` (or NULL); dst[i] is only an address, nothing is read or written there.
+ *   lr_mult, wd_mult   HOST arrays [nseg] (or NULL: 1): optimizer groups.  Either one present selects the kernel that carries one hyper
+ *                      per segment; segment i is stepped with fl32(lr * lr_mult[i]), fl32(weight_decay * wd_mult[i]) (afr_set_param_groups).
+ *   shT, tN, tK        HOST arrays [nseg] (or NULL): where shT[i] is not NULL, segment i is a [n[i] / tK[i]][tK[i]] block of weight rows and
+ *                      its new bf16 weights are ALSO written transposed, shT[i][k * tN[i] + r] = bf16(p[r][k]): tN[i] is the pitch of the
+ *                      transposed copy (>= the segment's rows: a row range of a wider weight points shT[i] at its first column).
+ * A segment with n[i] == 0 is allowed and dropped, as in the plain form; lr_mult, wd_mult, shT, tN, tK stay indexed by the CALLER's
+ * segment i: the entry moves them to the table's own numbering.
+ * kernel_name (or NULL) receives the instantiation, "reduce_group<OPT,GROUPS>": "reduce_group<0,0>" (plain, and fused AdamW),
+ * "reduce_group<1,0>" (Lion), "reduce_group<0,1>", "reduce_group<1,1>" (with groups).
+ * Refused with AFR_EINVAL and a message, before anything is launched: null required pointers; nseg outside 1..32; n[i] negative or not
+ * a multiple of 4; nslabs[i] < 1; stride[i] not a multiple of 4; with a step: dst[i] - gbase negative or not a multiple of 4, t < 1
+ * (AdamW), an unknown kind, a multiplier that is negative or not finite, shT[i] with tK[i] % 4 != 0, with n[i] not a multiple of
+ * tK[i], or with tN[i] < n[i] / tK[i]; shT[i] without a fused step. */
+typedef struct afr_reduce_step {
+    int32_t opt_kind, reserved;                 /* AFR_OPT_*                                                 */
+    float lr, beta1, beta2, eps, weight_decay, reserved2;
+    int64_t t;
+    const float* gbase;                         /* the flat gradient buffer's first element                  */
+    float *p, *m, *v; void* shadow;             /* p != NULL: fused optimizer step                           */
+    const float* lr_mult; const float* wd_mult; /* host [nseg], or NULL                                      */
+    void* const* shT; const int32_t* tN; const int32_t* tK;   /* host [nseg], or NULL                        */
+} afr_reduce_step;
+int afr_op_reduce_group_step(int nseg, float* const* dst, const float* const* slabs, const int* nslabs, const int64_t* stride,
+                             const int64_t* n, const afr_reduce_step* step /* or NULL */, char* kernel_name /* or NULL */, int name_cap,
+                             void* stream);
 int afr_op_adamw(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr,
                  float beta1, float beta2, float eps, float weight_decay, int64_t t, float grad_scale,
                  void* stream);
