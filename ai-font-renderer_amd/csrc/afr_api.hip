@@ -106,6 +106,10 @@ struct afr_plan {
     // not being read (a layer's weight-gradient workgroups update the weights while the same launch's input-gradient
     // workgroups still read them), and the roles swap when the step is complete.
     size_t o_shadow2 = 0; int shadow_cur = 0;
+    // bf16 glyph nets: the chained gradient launch (gemm.hip GemmGroup::chain) hands the output layer's input gradient to the hidden
+    // layer's products inside ONE launch: a monotonic arrival counter per 256 rows of the batch (o_hand, 0 = none), the arrivals
+    // enqueued so far, and the CUs of the bound device (a chain wants a CU per workgroup)
+    size_t o_hand = 0; unsigned hand_arrived = 0; int n_cus = 0;
     // pixel-token transformer (AFR_KIND_PIXEL): per-block parameter offsets and the forward's workspace
     struct PixBlock { int64_t ln1g, ln1b, win, bin, wo, bo, ln2g, ln2b, w1, b1, w2, b2; };
     std::vector<PixBlock> pix;
@@ -451,6 +455,8 @@ extern "C" int afr_plan_create(const afr_config* c, afr_plan** out) {
         for (const SumsqSeg& sg : p->clip_segs) { chunks += afr_tstats_seg_blocks(sg.numel); if (sg.numel > 0xffffffffll) p->tstats_ok = false; }
         if (p->tstats_ok) p->o_tstats = carve((size_t)chunks * sizeof(afr_tensor_stat));
     }
+    if (c->kind == AFR_KIND_GLYPH && c->dtype == AFR_BF16 && p->layers.size() >= 3)      // (behind everything else as well)
+        p->o_hand = carve(((size_t)c->max_batch + 255) / 256 * sizeof(unsigned));
     p->ws_need = off;
     *out = p;
     return AFR_OK;
@@ -499,6 +505,13 @@ extern "C" int afr_bind(afr_plan* p, float* params, float* grads, float* m, floa
     for (auto& l : p->layers) {                          // cooperative split-K: arrival counters and their host count start at zero
         l.coop_arrived = 0;
         if (l.n_cnt) { DevGuard dg(dev); HIPCHK(hipMemset(p->ws + l.o_cnt, 0, (size_t)l.n_cnt * sizeof(unsigned))); }
+    }
+    p->hand_arrived = 0; p->n_cus = 0;
+    if (p->o_hand) {                                     // the chain's hand-off counters likewise; the device's CUs decide whether it chains
+        DevGuard dg(dev);
+        HIPCHK(hipMemset(p->ws + p->o_hand, 0, ((size_t)p->cfg.max_batch + 255) / 256 * sizeof(unsigned)));
+        int d = 0;
+        if (hipGetDevice(&d) == hipSuccess) (void)hipDeviceGetAttribute(&p->n_cus, hipDeviceAttributeMultiprocessorCount, d);
     }
     {   // the norm kernel's scratch starts at zero (it leaves it so) and its table of tensor elements is the parameter table
         DevGuard dg(dev);
@@ -780,8 +793,11 @@ struct GemmBatch {
     int tile256 = 0, n = 0;
     GemmParams g[MAX];
     char tag[MAX][96];
-    double flops = 0.0, bytes = 0.0;
-    unsigned* arrived = nullptr;   // the cooperative member's Layer::coop_arrived, advanced once the launch is enqueued
+    double fl[MAX] = {0.0, 0.0, 0.0, 0.0}, by[MAX] = {0.0, 0.0, 0.0, 0.0};
+    // the cooperative members' Layer::coop_arrived (member 0; a chain's second pair: member 2), advanced once the launch is enqueued
+    unsigned* arrived[2] = {nullptr, nullptr};
+    // chain: the batch collects TWO layers' pairs (dW_up, dX_up, dW_lo, dX_lo) for one chained launch (afr_launch_gemm_chain)
+    bool chain = false;
 };
 // launches the product, or -- handed a batch, and the product can join a grouped launch -- collects it there
 static int run_gemm(afr_plan* p, hipStream_t s, const GemmParams& g, GemmBatch* batch = nullptr) {
@@ -803,33 +819,50 @@ static int run_gemm(afr_plan* p, hipStream_t s, const GemmParams& g, GemmBatch* 
         else snprintf(tag, sizeof tag, "%s[%dx%dx%d]", kn, M, N, K);
     }
     const bool joins = batch && afr_gemm_groupable(gdt, g);
-    if (g.coop_ws && !(joins && batch->tile256 && batch->n == 0))
+    if (g.coop_ws && !(joins && batch->tile256 && (batch->n == 0 || (batch->chain && batch->n == 2))))
         return fail(AFR_ESTATE, "cooperative split-K product outside a 256x256 grouped launch");
     if (g.b_rowmap && !(joins && batch->tile256))
         return fail(AFR_ESTATE, "gathered k-strided operand outside a 256x256 grouped launch");
     if (joins && batch->n < GemmBatch::MAX) {
-        batch->g[batch->n] = g; strcpy(batch->tag[batch->n], tag); batch->flops += fl_; batch->bytes += by_; batch->n++;
+        batch->g[batch->n] = g; strcpy(batch->tag[batch->n], tag); batch->fl[batch->n] = fl_; batch->by[batch->n] = by_; batch->n++;
         return AFR_OK;
     }
     ProfScope ps(p, s, tag, fl_, by_);
     HIPCHK(afr_launch_gemm(gdt, g, s));
     return AFR_OK;
 }
-// launch what run_gemm collected: one grouped launch (or the plain one when only one product qualified)
-static int flush_gemms(afr_plan* p, hipStream_t s, const GemmBatch& b) {
-    if (!b.n) return AFR_OK;
+// launch what run_gemm collected: one grouped launch (or the plain one when only one product qualified); members [i0, i0 + n)
+static int flush_members(afr_plan* p, hipStream_t s, const GemmBatch& b, int i0, int n, bool chained) {
+    if (!n) return AFR_OK;
     char tag[GemmBatch::MAX * 96 + 32];
-    int len = snprintf(tag, sizeof tag, "%s", b.n > 1 ? (b.tile256 ? "gemm_bf16_group256[" : "gemm_bf16_group[") : b.tag[0]);
-    for (int i = 0; i < b.n && b.n > 1; ++i) {      // the members' shapes: what stands between the brackets of their tags
+    int len = snprintf(tag, sizeof tag, "%s", n > 1 ? (b.tile256 ? "gemm_bf16_group256[" : "gemm_bf16_group[") : b.tag[i0]);
+    double flops = 0.0, bytes = 0.0;
+    for (int i = i0; i < i0 + n && n > 1; ++i) {      // the members' shapes: what stands between the brackets of their tags
         const char* shape = strchr(b.tag[i], '[') + 1;
-        len += snprintf(tag + len, sizeof tag - len, "%s%.*s%s", i ? "+" : "", (int)strcspn(shape, "]"), shape, i == b.n - 1 ? "]" : "");
+        len += snprintf(tag + len, sizeof tag - len, "%s%.*s%s", i > i0 ? "+" : "", (int)strcspn(shape, "]"), shape, i == i0 + n - 1 ? "]" : "");
     }
+    for (int i = i0; i < i0 + n; ++i) { flops += b.fl[i]; bytes += b.by[i]; }
     hipError_t e;
-    { ProfScope ps(p, s, tag, b.flops, b.bytes); e = afr_launch_gemm_group(p->gemm_dtype, b.g, b.n, b.tile256, s); }
+    const unsigned hand = chained ? p->hand_arrived + afr_gemm_chain_arrivals(b.g) : 0u;
+    {
+        ProfScope ps(p, s, tag, flops, bytes);
+        if (chained) e = afr_launch_gemm_chain(p->gemm_dtype, b.g, (unsigned*)(p->ws + p->o_hand), hand, (uint32_t*)(p->ws + p->o_err), s);
+        else e = afr_launch_gemm_group(p->gemm_dtype, b.g + i0, n, b.tile256, s);
+    }
     if (e != hipSuccess) return fail(AFR_EHIP, "grouped GEMM launch: %s", hipGetErrorString(e));
-    // the launch carries the cooperative member's arrivals: the host count follows only once it is enqueued
-    if (b.arrived) *b.arrived = b.g[0].coop_target;
+    // the launch carries the cooperative members' arrivals (and a chain's hand-off arrivals): the host counts follow only once
+    // it is enqueued
+    for (int i = i0; i < i0 + n; i += 2)
+        if (b.arrived[i / 2] && b.g[i].coop_ws) *b.arrived[i / 2] = b.g[i].coop_target;
+    if (chained) p->hand_arrived = hand;
     return AFR_OK;
+}
+static int flush_gemms(afr_plan* p, hipStream_t s, const GemmBatch& b) {
+    if (!b.chain) return flush_members(p, s, b, 0, b.n, false);
+    // two layers' pairs: ONE chained launch when the launcher takes these descriptors on this device, else the two grouped launches
+    if (b.n == 4 && p->o_hand && afr_gemm_chain_ok(p->gemm_dtype, b.g)) return flush_members(p, s, b, 0, 4, true);
+    if (int rc = flush_members(p, s, b, 0, b.n < 2 ? b.n : 2, false)) return rc;
+    return flush_members(p, s, b, 2, b.n > 2 ? b.n - 2 : 0, false);
 }
 // dW[N][K] = dy[B][N]^T . a[B][K] and db[N] = sum_b dy, reduced over the batch in ONE GEMM launch (the bias gradient
 // is the column sum of the A tiles the kernel already stages).  Small outputs use split-K partial slabs, summed later
@@ -856,7 +889,7 @@ static int run_dw(afr_plan* p, hipStream_t s, afr_plan::Layer& l, const void* dy
         if (step) set_fused_opt(p, g, l.w_off, shadow_wr(p), step->h);
         int rc = run_gemm(p, s, g, batch);
         if (rc) return rc;
-        batch->arrived = &l.coop_arrived;                 // (batch is non-null: run_gemm refuses a cooperative product it cannot collect)
+        batch->arrived[(batch->n - 1) / 2] = &l.coop_arrived;      // (batch is non-null: run_gemm refuses a cooperative product it cannot collect)
         if (step) step->done[step->ndone++] = l.w_off;
         afr_rtable_add(rt, p->G + l.b_off, sb, sk, N, N);
         return AFR_OK;
@@ -1007,6 +1040,27 @@ static PairPlan pair_plan_for(const afr_plan* p, const afr_plan::Layer& l, int B
     if (pp.sk_group > l.sk) return PairPlan();                 // the plan's slab space bounds the split
     if (c.reserved & AFR_CFG_SLAB_SPLITK) pp.coop = false;     // keeps the slab path (A/B measurements, parity cross-checks)
     return pp;
+}
+// The output layer's and the last hidden layer's pairs leave as ONE chained launch (gemm.hip GemmGroup::chain) when both are
+// cooperative 256x256 pairs, the block counts of the swapped roles agree and the bound device has a CU per workgroup.  What the
+// shapes allow (cus: the device's compute units):
+static bool chain_plan_shape(int B, int N_up, int K_up, int K_lo, int cus, PairPlan* up = nullptr, PairPlan* lo = nullptr) {
+    const PairPlan pu = pair_plan_shape(B, N_up, K_up), pl = pair_plan_shape(B, K_up, K_lo);
+    if (up) *up = pu;
+    if (lo) *lo = pl;
+    return pu.coop && pl.coop && afr_gemm_chain_counts(B, N_up, K_up, pu.sk_group, K_lo, pl.sk_group, cus, nullptr, nullptr);
+}
+// ... and what this plan does at batch B (AFR_CFG_NO_PAIR_CHAIN, and every switch that takes a pair off the cooperative body,
+// keep the two launches; the hidden layer must be a pair of its own, i.e. not the folded first layer)
+static bool chain_for(const afr_plan* p, int B, int cus) {
+    const int nl = (int)p->layers.size();
+    if (p->cfg.kind != AFR_KIND_GLYPH || nl < 3 || !p->o_hand || (p->cfg.reserved & AFR_CFG_NO_PAIR_CHAIN)) return false;
+    const auto &lu = p->layers[nl - 1], &ll = p->layers[nl - 2];
+    if (lu.K != ll.N || !pair_plan_for(p, lu, B).coop || !pair_plan_for(p, ll, B).coop) return false;
+    return chain_plan_shape(B, lu.N, lu.K, ll.K, cus);
+}
+extern "C" int afr_plan_pair_chain(const afr_plan* p, int B, int cus) {
+    return p && B > 0 && B <= p->cfg.max_batch && chain_for(p, B, cus > 0 ? cus : p->n_cus) ? 1 : 0;
 }
 // A training forward at batch B runs the first layer as a combination table when every consumer of h1 / h0 can gather: the
 // second layer's forward on the 256x128 ring kernel, its gradient pair as a cooperative 256x256 launch, the fused first-layer
@@ -1328,7 +1382,11 @@ static int pixel_backward(afr_plan* p, hipStream_t s, int stage, int64_t* g_off,
 }
 
 // step: the optimizer step this backward is part of (afr_train_step's staged fused path), NULL for a backward on its own
-static int backward_stage_impl(afr_plan* p, int stage, int64_t* g_off, int64_t* g_len, hipStream_t s, RTable* shared_rt, StepCtx* step = nullptr) {
+// carry: a caller that runs every stage itself (afr_backward, the staged fused step) lends one GemmBatch to all of them, so that
+// stage 0 can leave its pair there for stage 1 to launch both as one chain; NULL (afr_backward_stage: each stage's gradient range
+// is final when the call returns, for the caller's all-reduce) keeps a launch per pair.
+static int backward_stage_impl(afr_plan* p, int stage, int64_t* g_off, int64_t* g_len, hipStream_t s, RTable* shared_rt, StepCtx* step = nullptr,
+                               GemmBatch* carry = nullptr) {
     const afr_config& c = p->cfg;
     const int B = p->last.B;
     void* du = p->ws + p->o_u;
@@ -1417,7 +1475,13 @@ static int backward_stage_impl(afr_plan* p, int stage, int64_t* g_off, int64_t* 
         if (!pp.coop) return fail(AFR_ESTATE, "combination-table forward without a cooperative gradient pair (batch changed?)");
         a = p->ws + p->o_h1c;
     }
-    GemmBatch batch; batch.tile256 = pp.tile256;
+    // a chain: the output layer (stage 0) only collects its pair into the carried batch; the layer below adds its own and launches
+    const bool chain_up = carry && stage == 0 && chain_for(p, B, p->n_cus);
+    const bool chain_lo = carry && stage == 1 && carry->chain && carry->n == 2;
+    if (carry && stage == 1 && carry->chain && !chain_lo) return fail(AFR_ESTATE, "the chained launch lost the output layer's pair");
+    GemmBatch local;
+    GemmBatch& batch = (chain_up || chain_lo) ? *carry : local;
+    if (!chain_lo) { batch = GemmBatch(); batch.tile256 = pp.tile256; batch.chain = chain_up; }
     GemmBatch* const bp = pp.sk_group > 0 ? &batch : nullptr;      // no grouped launch at this shape: each product goes out on its own
     if ((rc = run_dw(p, s, l, dy, a, B, rt, pp.sk_group, pp.coop, cidx, p->h1c_ld, bp, step))) return rc;
     void* dx = p->ws + p->o_d[stage & 1];
@@ -1425,7 +1489,7 @@ static int backward_stage_impl(afr_plan* p, int stage, int64_t* g_off, int64_t* 
     if (gath) { g.aux_rowmap = cidx; g.ldaux = p->h1c_ld; }      // the ReLU gate is read from the gathered H1c rows
     if (p->last.mbits_on && i >= 2 && p->o_mbits[i - 1]) { g.mask_in = (const unsigned char*)(p->ws + p->o_mbits[i - 1]); g.ldmask = l.K / 8; }
     if ((rc = run_gemm(p, s, g, bp))) return rc;
-    if ((rc = flush_gemms(p, s, batch))) return rc;
+    if (!chain_up && (rc = flush_gemms(p, s, batch))) return rc;
     const int64_t end = l.b_off + (l.N + 63) / 64 * 64;
     if (i > 0) {
         return done(l.w_off, end - l.w_off);
@@ -1472,8 +1536,9 @@ extern "C" int afr_backward(afr_plan* p, void* stream) {
     if (!p->last.have_du) return fail(AFR_ESTATE, "afr_backward needs afr_forward + afr_loss_grad first");
     const int n = afr_backward_stages(p);
     RTable rt;
+    GemmBatch carry;
     for (int st = 0; st < n; ++st) {
-        int rc = backward_stage_impl(p, st, nullptr, nullptr, (hipStream_t)stream, &rt);
+        int rc = backward_stage_impl(p, st, nullptr, nullptr, (hipStream_t)stream, &rt, nullptr, &carry);
         if (rc) return rc;
     }
     int rc = run_reduce_group(p, (hipStream_t)stream, rt);
@@ -1862,8 +1927,11 @@ static int train_step_impl(afr_plan* p, const int64_t* x, const int64_t* font, c
         return sheet_fused_step(p, s, sc);
     case STEP_STAGED_FUSED:
         // weight-gradient products with a cooperative split-K tail apply this step's AdamW themselves
+    {
+        GemmBatch carry;
         for (int st = 0, n = afr_backward_stages(p); st < n; ++st)
-            if ((rc = backward_stage_impl(p, st, nullptr, nullptr, s, &rt, &sc))) return rc;
+            if ((rc = backward_stage_impl(p, st, nullptr, nullptr, s, &rt, &sc, &carry))) return rc;
+    }
         p->last.next_stage = 0; p->last.have_du = false;
         return reduce_and_step(p, s, rt, sc);
     case STEP_UNFUSED:
@@ -2132,6 +2200,39 @@ static int linear_set_opt(GemmParams& g, const afr_linear_tail& t, int dtype) {
     g.ad = adam_hyper(AdamArgs{t.lr, t.beta1, t.beta2, t.eps, t.weight_decay, t.t}, t.opt_kind); g.ad_kind = t.opt_kind;
     return AFR_OK;
 }
+// the two members of AFR_LIN_PAIR as backward_stage_impl builds them (g[0] = dW, g[1] = dx); a cooperative pair's counters are zeroed on s
+static int linear_pair_members(int dtype, const afr_linear_tail& t, const void* x, const void* W, const void* dy, void* out, void* out2,
+                               int B, int N, int K, int ldo, int ldx, int ld_db, void* workspace, size_t workspace_bytes, hipStream_t s,
+                               GemmParams* g, PairPlan* plan) {
+    int rc;
+    const PairPlan pp = pair_plan_shape(B, N, K);
+    const int sk = pp.sk_group;
+    if (sk < 1) return fail(AFR_EUNSUPPORTED, "%d x %d x %d: the gradient pair does not leave as one grouped launch", B, N, K);
+    if (!t.db) return fail(AFR_EINVAL, "AFR_LIN_PAIR: db is required");
+    if (t.x_rows && !pp.coop) return fail(AFR_EUNSUPPORTED, "a gathered weight-gradient operand needs the cooperative 256x256 launch");
+    if (t.p && !pp.coop) return fail(AFR_EUNSUPPORTED, "a fused optimizer step inside a grouped launch needs the cooperative 256x256 launch");
+    g[0] = lin_dw(dy, x, (float*)out, t.db, B, N, K, sk, pp.coop ? 0 : (long long)N * ldo);
+    g[0].ldc = ldo; g[0].ldb = ldx; g[0].colsum_stride = ld_db;
+    if (t.x_rows) g[0].b_rowmap = t.x_rows;
+    if ((rc = linear_set_opt(g[0], t, dtype))) return rc;
+    g[1] = lin_dx(dy, W, out2, t.aux, B, N, K, AFR_GEMM_OUT_BF16);
+    g[1].ldc = ldo;      // (both members are [.][K]: one ld_out serves dW / p / m / v and dx)
+    if ((rc = linear_set_gate(g[1], t, dtype, K))) return rc;
+    if (pp.coop) {
+        const size_t need = pair_workspace_bytes(N, K, pp);
+        if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255)) return fail(AFR_EINVAL, "workspace missing, too small or misaligned: %zu < %zu", workspace_bytes, need);
+        const size_t tiles = (size_t)((N + 255) / 256) * ((K + 255) / 256);
+        unsigned* cnt = (unsigned*)((char*)workspace + tiles * sk * AFR_FIX_SLICE_BYTES);
+        HIPCHK(hipMemsetAsync(cnt, 0, align_up(tiles * sizeof(unsigned), 256), s));
+        g[0].coop_ws = (float*)workspace; g[0].coop_cnt = cnt; g[0].coop_target = (unsigned)sk;
+    }
+    // (the grouped launcher would answer a member that cannot join with separate launches: here that is a refusal)
+    if (!afr_gemm_groupable(dtype, g[0]) || !afr_gemm_groupable(dtype, g[1]))
+        return fail(AFR_EUNSUPPORTED, "%d x %d x %d: a member of the pair cannot join a grouped launch", B, N, K);
+    if ((rc = check_operand_bytes(g[0])) || (rc = check_operand_bytes(g[1]))) return rc;
+    *plan = pp;
+    return AFR_OK;
+}
 extern "C" int afr_op_linear(int dtype, int which, const void* x, const void* W, const float* bias, const void* dy, void* out, void* out2,
                              int B, int N, int K, const afr_linear_tail* tail, void* workspace, size_t workspace_bytes,
                              char* kernel_name, int name_cap, void* stream) {
@@ -2189,31 +2290,8 @@ extern "C" int afr_op_linear(int dtype, int which, const void* x, const void* W,
         if (t.db && sk > 1) g[0].colsum_stride = ld_db;
         if ((rc = linear_set_opt(g[0], t, dtype))) return rc;
     } else {
-        const PairPlan pp = pair_plan_shape(B, N, K);
-        const int sk = pp.sk_group;
-        if (sk < 1) return fail(AFR_EUNSUPPORTED, "%d x %d x %d: the gradient pair does not leave as one grouped launch", B, N, K);
-        if (!t.db) return fail(AFR_EINVAL, "AFR_LIN_PAIR: db is required");
-        if (t.x_rows && !pp.coop) return fail(AFR_EUNSUPPORTED, "a gathered weight-gradient operand needs the cooperative 256x256 launch");
-        if (t.p && !pp.coop) return fail(AFR_EUNSUPPORTED, "a fused optimizer step inside a grouped launch needs the cooperative 256x256 launch");
-        g[0] = lin_dw(dy, x, (float*)out, t.db, B, N, K, sk, pp.coop ? 0 : (long long)N * ldo);
-        g[0].ldc = ldo; g[0].ldb = ldx; g[0].colsum_stride = ld_db;
-        if (t.x_rows) g[0].b_rowmap = t.x_rows;
-        if ((rc = linear_set_opt(g[0], t, dtype))) return rc;
-        g[1] = lin_dx(dy, W, out2, t.aux, B, N, K, AFR_GEMM_OUT_BF16);
-        g[1].ldc = ldo;      // (both members are [.][K]: one ld_out serves dW / p / m / v and dx)
-        if ((rc = linear_set_gate(g[1], t, dtype, K))) return rc;
-        if (pp.coop) {
-            const size_t need = pair_workspace_bytes(N, K, pp);
-            if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255)) return fail(AFR_EINVAL, "workspace missing, too small or misaligned: %zu < %zu", workspace_bytes, need);
-            const size_t tiles = (size_t)((N + 255) / 256) * ((K + 255) / 256);
-            unsigned* cnt = (unsigned*)((char*)workspace + tiles * sk * AFR_FIX_SLICE_BYTES);
-            HIPCHK(hipMemsetAsync(cnt, 0, align_up(tiles * sizeof(unsigned), 256), s));
-            g[0].coop_ws = (float*)workspace; g[0].coop_cnt = cnt; g[0].coop_target = (unsigned)sk;
-        }
-        // (the grouped launcher would answer a member that cannot join with separate launches: here that is a refusal)
-        if (!afr_gemm_groupable(dtype, g[0]) || !afr_gemm_groupable(dtype, g[1]))
-            return fail(AFR_EUNSUPPORTED, "%d x %d x %d: a member of the pair cannot join a grouped launch", B, N, K);
-        if ((rc = check_operand_bytes(g[0])) || (rc = check_operand_bytes(g[1]))) return rc;
+        PairPlan pp;
+        if ((rc = linear_pair_members(dtype, t, x, W, dy, out, out2, B, N, K, ldo, ldx, ld_db, workspace, workspace_bytes, s, g, &pp))) return rc;
         if ((rc = launcher_rc(afr_launch_gemm_group(dtype, g, 2, pp.tile256, s), "pair"))) return rc;
         if (kernel_name) snprintf(kernel_name, name_cap, "%s", !pp.tile256 ? "gemm_bf16_group" : (t.p && t.opt_kind == AFR_OPT_LION) ? "gemm_bf16_group256_lion" : "gemm_bf16_group256");
         return AFR_OK;
@@ -2221,6 +2299,86 @@ extern "C" int afr_op_linear(int dtype, int which, const void* x, const void* W,
     if (dtype == AFR_BF16 && (rc = check_operand_bytes(g[0]))) return rc;
     if ((rc = launcher_rc(afr_launch_gemm(dtype, g[0], s), fwd ? "forward" : dx ? "input gradient" : "weight gradient"))) return rc;
     if (kernel_name) snprintf(kernel_name, name_cap, "%s", afr_gemm_kernel_name(dtype, g[0]));
+    return AFR_OK;
+}
+// ---- afr_op_linear_chain: two stacked Linears' pairs as the one chained launch of a glyph step (afr_launch_gemm_chain)
+static int chain_cus(int cus) {
+    if (cus > 0) return cus;
+    int d = 0, n = 0;
+    if (hipGetDevice(&d) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    return n;
+}
+extern "C" int afr_op_linear_chain_plan(int B, int N_up, int K_up, int K_lo, int cus, int* splitk_up, int* splitk_lo, int* blocks, size_t* workspace_bytes) {
+    PairPlan pu, pl;
+    if (!chain_plan_shape(B, N_up, K_up, K_lo, chain_cus(cus), &pu, &pl))
+        return fail(AFR_EUNSUPPORTED, "%d x (%d x %d over %d x %d): the two gradient pairs do not leave as one chained launch", B, N_up, K_up, K_up, K_lo);
+    int front = 0, back = 0;
+    afr_gemm_chain_counts(B, N_up, K_up, pu.sk_group, K_lo, pl.sk_group, 1 << 30, &front, &back);
+    if (splitk_up) *splitk_up = pu.sk_group;
+    if (splitk_lo) *splitk_lo = pl.sk_group;
+    if (blocks) *blocks = 2 * (front + back);
+    if (workspace_bytes) *workspace_bytes = pair_workspace_bytes(N_up, K_up, pu) + pair_workspace_bytes(K_up, K_lo, pl) + align_up(((size_t)B + 255) / 256 * sizeof(unsigned), 256);
+    return AFR_OK;
+}
+// the four products' shapes alone, in chain order (what the block map reads)
+static void chain_shapes(int B, int N_up, int K_up, int K_lo, const PairPlan& pu, const PairPlan& pl, GemmParams* g) {
+    g[0] = lin_dw(nullptr, nullptr, nullptr, nullptr, B, N_up, K_up, pu.sk_group);
+    g[1] = lin_dx(nullptr, nullptr, nullptr, nullptr, B, N_up, K_up, AFR_GEMM_OUT_BF16);
+    g[2] = lin_dw(nullptr, nullptr, nullptr, nullptr, B, K_up, K_lo, pl.sk_group);
+    g[3] = lin_dx(nullptr, nullptr, nullptr, nullptr, B, K_up, K_lo, AFR_GEMM_OUT_BF16);
+}
+extern "C" int afr_op_linear_chain_block(int B, int N_up, int K_up, int K_lo, int block, int* phase, int* member, int* tm, int* tn, int* slice) {
+    PairPlan pu, pl;
+    if (!phase || !member || !tm || !tn || !slice) return fail(AFR_EINVAL, "null output");
+    if (!chain_plan_shape(B, N_up, K_up, K_lo, 1 << 30, &pu, &pl))
+        return fail(AFR_EUNSUPPORTED, "%d x (%d x %d over %d x %d): the two gradient pairs do not leave as one chained launch", B, N_up, K_up, K_up, K_lo);
+    GemmParams g[4];
+    chain_shapes(B, N_up, K_up, K_lo, pu, pl, g);
+    if (!afr_gemm_chain_block(g, block, member, tm, tn, slice)) return fail(AFR_EINVAL, "block %d: outside the chained launch", block);
+    *phase = *member >= 2 ? 1 : 0;
+    return AFR_OK;
+}
+extern "C" int afr_op_linear_chain(const void* dy, const void* x_up, const void* W_up, void* out_up, void* mid, const afr_linear_tail* tail_up,
+                                   const void* x_lo, const void* W_lo, void* out_lo, void* dx_lo, const afr_linear_tail* tail_lo,
+                                   int B, int N_up, int K_up, int K_lo, void* workspace, size_t workspace_bytes,
+                                   char* kernel_name, int name_cap, void* stream) {
+    static const afr_linear_tail none = {};
+    const afr_linear_tail &tu = tail_up ? *tail_up : none, &tl = tail_lo ? *tail_lo : none;
+    if (!dy || !x_up || !W_up || !out_up || !mid || !x_lo || !W_lo || !out_lo || !dx_lo) return fail(AFR_EINVAL, "null operand");
+    if (kernel_name && name_cap < 1) return fail(AFR_EINVAL, "name_cap must be positive");
+    if (B <= 0 || N_up <= 0 || K_up <= 0 || K_lo <= 0) return fail(AFR_EINVAL, "bad Linear extents");
+    if (N_up % 8 || K_up % 8 || K_lo % 8) return fail(AFR_EUNSUPPORTED, "N and K must be multiples of 8");
+    for (const afr_linear_tail* t : {&tu, &tl}) {
+        if (t->target || t->target_rows || t->mask_out) return fail(AFR_EINVAL, "the fused loss and mask_out belong to AFR_LIN_FWD");
+        const int K = t == &tu ? K_up : K_lo;
+        if ((t->ld_out && t->ld_out != K) || (t->ldx && t->ldx != K && !t->x_rows) || (t->ldx && t->ldx < K)) return fail(AFR_EUNSUPPORTED, "afr_op_linear_chain: dense outputs and operands only");
+        if (t->ld_db && t->ld_db < (t == &tu ? N_up : K_up)) return fail(AFR_EINVAL, "ld_db is smaller than its row");
+    }
+    size_t need = 0;
+    int rc;
+    if ((rc = afr_op_linear_chain_plan(B, N_up, K_up, K_lo, 0, nullptr, nullptr, nullptr, &need))) return rc;
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255)) return fail(AFR_EINVAL, "workspace missing, too small or misaligned: %zu < %zu", workspace_bytes, need);
+    hipStream_t s = (hipStream_t)stream;
+    DevGuard dg(device_of(out_up));
+    GemmParams g[4];
+    PairPlan pu, pl;
+    const size_t wu = pair_workspace_bytes(N_up, K_up, pair_plan_shape(B, N_up, K_up)), wl = pair_workspace_bytes(K_up, K_lo, pair_plan_shape(B, K_up, K_lo));
+    char* w = (char*)workspace;
+    if ((rc = linear_pair_members(AFR_BF16, tu, x_up, W_up, dy, out_up, mid, B, N_up, K_up, K_up, tu.ldx ? tu.ldx : K_up, tu.ld_db ? tu.ld_db : N_up, w, wu, s, g, &pu))) return rc;
+    if ((rc = linear_pair_members(AFR_BF16, tl, x_lo, W_lo, mid, out_lo, dx_lo, B, K_up, K_lo, K_lo, tl.ldx ? tl.ldx : K_lo, tl.ld_db ? tl.ld_db : K_up, w + wu, wl, s, g + 2, &pl))) return rc;
+    unsigned* hand = (unsigned*)(w + wu + wl);
+    const size_t hb = align_up(((size_t)B + 255) / 256 * sizeof(unsigned), 256);
+    HIPCHK(hipMemsetAsync(hand, 0, hb, s));
+    static uint32_t* err_word[16];       // a device word for AFR_ERR_COOP_TIMEOUT (no plan here): allocated once per device, never read back
+    int dev = 0;
+    uint32_t* err = nullptr;
+    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16) {
+        if (!err_word[dev]) { HIPCHK(hipMalloc((void**)&err_word[dev], 256)); HIPCHK(hipMemset(err_word[dev], 0, 256)); }
+        err = err_word[dev];
+    }
+    g[0].err = err; g[2].err = err;
+    if ((rc = launcher_rc(afr_launch_gemm_chain(AFR_BF16, g, hand, afr_gemm_chain_arrivals(g), err, s), "chain"))) return rc;
+    if (kernel_name) snprintf(kernel_name, name_cap, "%s", (tu.p && tu.opt_kind == AFR_OPT_LION) ? "gemm_bf16_group256_lion" : "gemm_bf16_group256");
     return AFR_OK;
 }
 extern "C" int afr_op_reduce(float* dst, const float* slabs, int nslabs, int64_t stride, int64_t n, float scale, int acc,

@@ -251,6 +251,9 @@ __device__ __forceinline__ bf16_t f32_to_bf16(float x) { return (bf16_t)x; }
 // ---------------------------------------------------------------------------------------------
 // internal launchers (implemented in the .hip files, called from afr_api.cpp)
 // ---------------------------------------------------------------------------------------------
+// internal bit of GemmParams::flags (above the public AFR_GEMM_* bits of include/afr.h; set by the chained launcher only): the bf16
+// output tile of a product on the 256x256 body is stored write-through (sc1), for readers inside the same launch
+constexpr int AFR_GEMM_OUT_WTHRU = 1 << 20;
 struct GemmParams {
     const void* A; const void* B; void* C; const float* bias; const void* aux;
     int M, N, K;
@@ -293,6 +296,8 @@ struct GemmParams {
     // of mask_out[m * ldmask + n / 8] = [stored activation (m, n) > 0]; an input-gradient product with AFR_GEMM_RELU_MASK
     // reads mask_in in that layout INSTEAD of the activation aux (1/16 of its bytes: C3's 16.8 MB mask read becomes 1 MB)
     unsigned char* mask_out = nullptr; const unsigned char* mask_in = nullptr; int ldmask = 0;
+    // AFR_GEMM_OUT_WTHRU (a chained launch's dX_up, set by its launcher): the arrival counters of the output's 256-row blocks
+    unsigned* hand_cnt = nullptr;
 #ifdef AFR_GEMM_TIMING
     int dbg_slot = 0;     // kernel-development builds: which 1024-block region of the stamp buffer this launch writes
 #endif
@@ -306,6 +311,14 @@ hipError_t afr_launch_f32_to_fp8(const float* src, unsigned char* dst, long long
 bool afr_gemm_groupable(int dtype, const GemmParams& p);
 hipError_t afr_launch_gemm_group(int dtype, const GemmParams* ps, int n, int tile256, hipStream_t s);
 void afr_gemm_pair_plan(int B, int n_out, int k_in, int* tile256, int* splitk);
+// two layers' cooperative 256x256 pairs as ONE chained launch (gemm.hip, GemmGroup::chain).  ps[4] in chain order: dW_up, dX_up,
+// dW_lo, dX_lo, where dX_up's output is the dy of both lower products.  _counts: what the shapes allow on a device of `cus` CUs
+// (host-only); _ok: these descriptors on the current device; _block: the kernel's block map (host copy).
+bool afr_gemm_chain_counts(int B, int N_up, int K_up, int sk_up, int K_lo, int sk_lo, int cus, int* front, int* back);
+bool afr_gemm_chain_ok(int dtype, const GemmParams* ps);
+unsigned afr_gemm_chain_arrivals(const GemmParams* ps);
+hipError_t afr_launch_gemm_chain(int dtype, const GemmParams* ps, unsigned* hand_cnt, unsigned hand_target, uint32_t* err, hipStream_t s);
+bool afr_gemm_chain_block(const GemmParams* ps, int b, int* member, int* tm, int* tn, int* slice);
 // in-launch split-K for one bf16 product on 256x256 tiles (GemmParams::fix_ws): the workspace needs
 // (tiles - head_tiles) * splitk * AFR_FIX_SLICE_BYTES
 constexpr size_t AFR_FIX_SLICE_BYTES = 256 * 256 * 4;

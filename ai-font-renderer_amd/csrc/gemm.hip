@@ -29,12 +29,12 @@
 // than once per slow index (R0's dW GEMM re-read its 13 MB activation operand 75x, 1 GB of extra HBM reads per step,
 // before this).  Placement changes speed only, never results.
 // block -> position in its XCD's contiguous range of the walk (blocks b, b+8, ... share an XCD)
-__device__ __forceinline__ int xcd_walk(int b, int nb) {
+__host__ __device__ __forceinline__ int xcd_walk(int b, int nb) {
     const int q = nb >> 3, r = nb & 7, xcd = b & 7, idx = b >> 3;
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 // walk position t (0 .. tiles-1) -> tile coordinates; q, r describe the XCD ranges the walk is cut into (nb / 8, nb % 8)
-__device__ __forceinline__ void tile_coords(const GemmParams& p, int BM, int BN, int t, int q, int r, int& tm, int& tn) {
+__host__ __device__ __forceinline__ void tile_coords(const GemmParams& p, int BM, int BN, int t, int q, int r, int& tm, int& tn) {
     const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
     const int tiles = tiles_m * tiles_n;
     const bool n_slow = p.N > p.M;                   // the slow (grouped) dimension is the larger operand's
@@ -46,7 +46,7 @@ __device__ __forceinline__ void tile_coords(const GemmParams& p, int BM, int BN,
     if (r == 0 && q % tf == 0 && q / tf >= 1 && q / tf < 8 && tiles % q == 0) G = q / tf;
     const int grp = t / (G * tf);
     const int s0 = grp * G;
-    const int gs = min(G, ts - s0);
+    const int gs = G < ts - s0 ? G : ts - s0;
     const int rr = t - grp * G * tf;
     // Inside a group the FAST index runs fastest when the fast dimension is only a few tiles (R0's fc_output: 4 row tiles of
     // the batch against 150 column tiles of the 246 MB weight): the tiles that share one big-operand tile are then adjacent in
@@ -58,7 +58,7 @@ __device__ __forceinline__ void tile_coords(const GemmParams& p, int BM, int BN,
     tm = n_slow ? fidx : sidx;
     tn = n_slow ? sidx : fidx;
 }
-__device__ __forceinline__ void tile_of_block(const GemmParams& p, int BM, int BN, int b, int nb, int& tm, int& tn, int& z) {
+__host__ __device__ __forceinline__ void tile_of_block(const GemmParams& p, int BM, int BN, int b, int nb, int& tm, int& tn, int& z) {
     const int v = xcd_walk(b, nb);
     const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
     z = v / tiles;
@@ -560,7 +560,7 @@ __device__ __forceinline__ void epilogue_bias(const GemmParams& p, const int nb0
 template <int ALAY, int BLAY, int WM, bool SCALE = false, bool EARLYB_ = true, bool TROWS = false, int LOSS = LOSS_MSE, int OPT = OPT_ADAMW, class ACC>      // SCALE: the accumulators are multiplied by p.out_scale first (fp8 per-tensor scales)
 __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC& acc_at, const int mb, const int nb0, const int z,
                                                  float* Wt, const int lane, float& lsum, const float* lut255 = nullptr,
-                                                 const float (*pre_bias)[8] = nullptr) {
+                                                 const float (*pre_bias)[8] = nullptr, const bool wthru = false) {
     // Epilogue through LDS: the MFMA accumulators hold 4 consecutive n of 16 different rows per lane-group, which as
     // direct stores would be 32-byte pieces.  Each wave parks its 64x64 f32 tile in its own 16 KiB of LDS (16-B chunks
     // XOR-swizzled by row: conflict-free both ways) and streams it out row-contiguous: 8 lanes x 8 values = one 64-col
@@ -788,7 +788,12 @@ __device__ __forceinline__ void wave_epilogue_at(const GemmParams& p, const ACC&
             for (int r = 0; r < 8; ++r) o[r] = (bf16_t)v[r];
             // streaming stores: a kernel's dirty L2 lines are written back at its end, before the next kernel may start
             // (the XCDs' L2s are not coherent with each other); write-through output leaves nothing to drain (C3 -3.7 %)
-            __builtin_nontemporal_store(o, reinterpret_cast<bf16x8*>(Cb + (size_t)m * p.ldc + n));
+            // (wthru: the tile is handed to other workgroups of the SAME launch -- AFR_GEMM_OUT_WTHRU on the 256x256 body -- so its
+            // bytes are stored write-through (sc1); nt stores are not.  The body drains them with s_waitcnt vmcnt(0) before it arrives.)
+            if (wthru) {
+                typedef __attribute__((ext_vector_type(4))) unsigned u32x4_;
+                asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(Cb + (size_t)m * p.ldc + n), "v"(__builtin_bit_cast(u32x4_, o)) : "memory");
+            } else __builtin_nontemporal_store(o, reinterpret_cast<bf16x8*>(Cb + (size_t)m * p.ldc + n));
             if (p.mask_out) {                          // the ReLU mask of the STORED (bf16) values, one byte per 8 columns
                 unsigned bits = 0;
 #pragma unroll
@@ -1576,13 +1581,24 @@ __device__ __forceinline__ void gemm_bf16_256_body(const GemmParams& p, const in
     float bia[8];
     if (ALAY == 0 && BLAY == 0) epilogue_bias(p, n0 + wc * 64, lane, bia);       // one request for both halves, ahead of the first park
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
+    for (int hh = 0; hh < 2; ++hh) {
         wave_epilogue_at<ALAY, BLAY, 4, false, true, false, LOSS_MSE, (ALAY == 1 && BLAY == 1) ? OPT : OPT_ADAMW>(p, [&](int i, int j) {
             f32x4 v;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = h ? acc[4 + i][j][r] : acc[i][j][r];
-            return v; }, m0 + wr * 128 + h * 64, n0 + wc * 64, z, Wt, lane, lsum, nullptr, (ALAY == 0 && BLAY == 0) ? &bia : nullptr);
+            for (int r = 0; r < 4; ++r) v[r] = hh ? acc[4 + i][j][r] : acc[i][j][r];
+            return v; }, m0 + wr * 128 + hh * 64, n0 + wc * 64, z, Wt, lane, lsum, nullptr, (ALAY == 0 && BLAY == 0) ? &bia : nullptr,
+            ALAY == 0 && BLAY == 1 && (p.flags & AFR_GEMM_OUT_WTHRU));
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the wave's own LDS reads of pass 0 are done before pass 1 overwrites Wt
+    }
+    if (ALAY == 0 && BLAY == 1 && (p.flags & AFR_GEMM_OUT_WTHRU)) {
+        // A chained launch's producer (GemmGroup::chain): this tile is read by later workgroups of the SAME launch.  Producer form of
+        // MI355X_MICROARCH.md ("inter-workgroup visibility"): every byte of the tile was stored write-through (sc1, wave_epilogue_at),
+        // every storing wave drains its own stores, the workgroup meets at a barrier, ONE lane adds to the counter of the tile's
+        // 256-row block (m0 = 256 tm).  (Here, on values the epilogue has anyway, and not in the kernel around the body: the body
+        // leaves no SGPR free around its K loop, and whatever the kernel keeps across it spills.)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (tid == 0) (void)__hip_atomic_fetch_add(p.hand_cnt + (m0 >> 8), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 #ifdef AFR_GEMM_TIMING
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1603,7 +1619,16 @@ __global__ __launch_bounds__(128 * WM, 2) void gemm_bf16(GemmParams p) {
 // input-gradient blocks), and nothing waits for a device-wide kernel boundary in between: a CU's next block starts while
 // other CUs are still in their epilogues.  Products with a fused loss epilogue cannot be grouped (its arrival counter
 // counts the blocks of ONE launch).
-struct GemmGroup { int n; int blk0[5]; GemmParams p[4]; };
+// chain != 0 (gemm_bf16_group256 and its Lion twin only; n == 4): members 0, 1 are an upper Linear's pair (dW_up cooperative, dX_up)
+// and members 2, 3 the pair of the Linear below it (dW_lo cooperative, dX_lo), whose dy IS dX_up's output: it is handed over
+// inside the launch.  See gemm_bf16_group256.
+struct GemmGroup { int n; int blk0[5]; GemmParams p[4]; int chain = 0; unsigned hand_target = 0; unsigned* hand_cnt = nullptr; uint32_t* hand_err = nullptr; };
+// block -> its product
+__host__ __device__ __forceinline__ int group_member_of(const int n, const int* blk0, const int b) {
+    int i = 0;
+    while (i + 1 < n && b >= blk0[i + 1]) ++i;
+    return i;
+}
 // block -> (its product, its place among that product's blocks, the operand layouts as compile-time tags)
 template <class F>
 __device__ __forceinline__ void group_member(const GemmGroup& g, F&& body) {
@@ -1622,8 +1647,69 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_group(GemmGroup g) {
     __shared__ __attribute__((aligned(16))) char smem[RingGeom<4>::LDS_BYTES];
     group_member(g, [&](const GemmParams& p, int bid, int nblk, auto a, auto b) { gemm_bf16_body<a(), b(), 4>(p, bid, nblk, smem); });
 }
+// The consumer side of a chained launch's hand-off, AHEAD of a lower member's body, i.e. ahead of its first load of the handed-over
+// operand (nothing of it is alive inside the body).  hand_cnt holds one monotonic arrival counter per 256-row block of dX_up's
+// output; a launch adds one arrival per column tile to each (the end of gemm_bf16_256_body) and its readers wait for
+// hand_target, the host-advanced total after it.  Nothing is reset on the device.  Consumer form of MI355X_MICROARCH.md
+// ("inter-workgroup visibility"): ONE wave polls the counters with relaxed agent-scope loads and s_sleep (lane r: row block lo +
+// r; bounded like the cooperative tail: a producer that never ran sets AFR_ERR_COOP_TIMEOUT in the error word, nothing hangs),
+// then ONE agent-scope acquire, s_waitcnt vmcnt(0) (the invalidate has completed), the workgroup's barrier.  The operand loads
+// are LDS-DMA, which the sc1-load forms of that section's table do not cover: the acquire stays.
+// Row blocks read: the input gradient (member 3, A k-contiguous) its own 256 rows; a weight-gradient slice (member 2, A
+// k-strided) those of its K range.
+__device__ __forceinline__ void chain_wait(const GemmGroup& g) {
+    // (the block index goes through an empty asm: the compiler must not tie this function's member search to group_member's and
+    // thread the body into copies per outcome -- the body's LDS-DMA asm statements do not survive that)
+    int blk = blockIdx.x;
+    asm volatile("" : "+s"(blk));
+    const int i = group_member_of(g.n, g.blk0, blk);
+    if (i < 2) return;
+    const GemmParams& p = g.p[i];
+    int tm, tn, z;
+    tile_of_block(p, 256, 256, blk - g.blk0[i], g.blk0[i + 1] - g.blk0[i], tm, tn, z);
+    int lo = tm, hi = tm;
+    if (i == 2) {
+        int kbeg, kend;
+        k_range<BK>(p.K, p.splitk, z, kbeg, kend);
+        lo = kbeg >> 8; hi = (kend - 1) >> 8;               // (an empty K range: hi < lo, nothing to wait for)
+    }
+    if (threadIdx.x < 64) {
+        const int lane = threadIdx.x;
+        const bool mine = lo + lane <= hi;
+        unsigned spins = 0;
+        for (;;) {
+            bool ok = true;
+            if (mine) ok = (int)(__hip_atomic_load(g.hand_cnt + lo + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - g.hand_target) >= 0;
+            if (__builtin_amdgcn_ballot_w64(!ok) == 0ull) break;
+            __builtin_amdgcn_s_sleep(8);
+            if (++spins > (1u << 22)) {                              // seconds: a producer never ran
+                if (lane == 0 && g.hand_err) atomicOr(g.hand_err, AFR_ERR_COOP_TIMEOUT);
+                break;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+}
+// The 256x256 grouped launch.  Chained (C3's step: output layer dW3 + dX3, hidden layer dW2 + dX2, 128 workgroups each), the
+// grid is [dW3 | dX3 | dW2 | dX2].  A workgroup takes a whole CU (160 KiB of LDS) and the dispatcher hands workgroups out in grid
+// order, so on the 256 CUs the upper pair starts at once and the lower pair's workgroups take over CU by CU: the cooperative dW2
+// slices (long: park / wait / finish tail) follow the dX3 workgroups, which are done first, and the dX2 workgroups (short) follow
+// the dW3 ones -- every CU runs one long role and one short one, and a lower workgroup starts its K loop as soon as the dh2 rows
+// it reads exist (chain_wait) instead of at a kernel boundary behind the upper launch's last tail.
+// (The second role is a NEW workgroup and not a second pass of the same one over a phase loop: measured at compile time, whatever
+// the kernel keeps alive across the body -- a phase index, the block index, the argument pointer -- no longer fits beside the
+// body's K loop, which uses every VGPR and leaves no SGPR free: 60 spilled SGPRs, 140 spilled VGPRs, 564 bytes of scratch.)
+// Progress: no upper workgroup waits for a lower one, and every upper workgroup is handed out before any lower one.  The upper
+// pair is the unchained launch with its own guarantee (a cooperative set's partners are resident together whenever as many CUs
+// are free).  A lower workgroup only waits for upper workgroups' stores and for its cooperative partners, which become resident
+// as the upper workgroups -- who wait for nobody below -- leave their CUs: with as many CUs as the upper pair has workgroups
+// (the launcher asks for that) every dW2 slice is resident once the upper pair has gone.  Every wait is bounded
+// (AFR_ERR_COOP_TIMEOUT), none can hang.
 __global__ __launch_bounds__(512, 2) void gemm_bf16_group256(GemmGroup g) {
     __shared__ __attribute__((aligned(16))) char smem[10 * SUB];   // all 160 KiB: A ring 3 x 32 KiB + B ring 2 x 32 KiB
+    if (g.chain) chain_wait(g);
     group_member(g, [&](const GemmParams& p, int bid, int nblk, auto a, auto b) {
         if constexpr (a() && b()) {                                // gathered B rows: weight gradients only
             if (p.b_rowmap) { gemm_bf16_256_body<1, 1, 1>(p, bid, nblk, smem); return; }
@@ -1636,6 +1722,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_group256(GemmGroup g) {
 // and its code.)
 __global__ __launch_bounds__(512, 2) void gemm_bf16_group256_lion(GemmGroup g) {
     __shared__ __attribute__((aligned(16))) char smem[10 * SUB];
+    if (g.chain) chain_wait(g);
     group_member(g, [&](const GemmParams& p, int bid, int nblk, auto a, auto b) {
         if constexpr (a() && b()) {
             if (p.b_rowmap) gemm_bf16_256_body<1, 1, 1, OPT_LION>(p, bid, nblk, smem);
@@ -2066,6 +2153,93 @@ hipError_t afr_launch_gemm_group(int dtype, const GemmParams* ps, int n, int til
     ps = q;
 #endif
     return launch_grouped(ps, n, tile256, true, s);
+}
+// ---- two layers' gradient pairs chained into ONE launch (GemmGroup::chain; the kernel's comment has the role order)
+// Block counts of the four products of an upper Linear (N_up x K_up) and the one below it (K_up x K_lo) at batch B, on 256x256
+// tiles with the weight gradients cut sk_up / sk_lo ways: front = dX_up = dW_lo, back = dW_up = dX_lo, or no chain.  Whole
+// octets (blocks b, b + 8, ... keep sharing an XCD), at most 64 row blocks behind one wait (one lane polls each), and a CU per
+// workgroup of the upper pair: the lower pair's workgroups then take the CUs over one by one (gemm_bf16_group256).
+bool afr_gemm_chain_counts(int B, int N_up, int K_up, int sk_up, int K_lo, int sk_lo, int cus, int* front, int* back) {
+    if (B <= 0 || N_up <= 0 || K_up <= 0 || K_lo <= 0 || sk_up < 1 || sk_lo < 1) return false;
+    const long long rb = (B + 255) / 256, tu = (K_up + 255) / 256, tl = (K_lo + 255) / 256, tn = (N_up + 255) / 256;
+    const long long dx_up = rb * tu, dw_lo = tu * tl * sk_lo, dw_up = tn * tu * sk_up, dx_lo = rb * tl;
+    if (dx_up != dw_lo || dw_up != dx_lo || (dx_up & 7) || (dw_up & 7) || dx_up + dw_up > cus) return false;
+    const int klen = ((B + sk_lo - 1) / sk_lo + 63) / 64 * 64;          // k_range<64>: a slice's batch rows
+    if (klen / 256 + 2 > 64) return false;
+    if (front) *front = (int)dx_up;
+    if (back) *back = (int)dw_up;
+    return true;
+}
+// chain order of the descriptors: ps[0] = dW_up, ps[1] = dX_up, ps[2] = dW_lo, ps[3] = dX_lo (what two grouped pairs would launch)
+static bool chain_descriptors_ok(int dtype, const GemmParams* ps, int cus) {
+    if (dtype != AFR_BF16) return false;
+    for (int i = 0; i < 4; ++i) {
+        const GemmParams& p = ps[i];
+        const bool ak = p.flags & AFR_GEMM_A_KSTRIDED, bk = p.flags & AFR_GEMM_B_KSTRIDED;
+        if (!afr_gemm_groupable(dtype, p) || p.fix_ws || p.a_rowmap || p.colsum_stride < 0) return false;
+        if (i & 1) {      // input gradients: dy k-contiguous, W k-strided, bf16 out, whole K
+            if (ak || !bk || p.splitk != 1 || p.coop_ws || p.ad_p || p.b_rowmap || !(p.flags & AFR_GEMM_OUT_BF16)) return false;
+        } else {          // cooperative weight gradients (the checks of afr_launch_gemm_group)
+            const long long tiles = (long long)((p.M + 255) / 256) * ((p.N + 255) / 256);
+            const int S = p.splitk;
+            if (!ak || !bk || !p.coop_ws || !p.coop_cnt || (S != 2 && S != 4 && S != 8) || tiles * S > 256 ||
+                tiles * S * (long long)AFR_FIX_SLICE_BYTES >= (1ll << 31) || p.aux_rowmap) return false;
+        }
+    }
+    // the hand-off: dX_up's output IS the dy of both lower products, row for row
+    const GemmParams &wu = ps[0], &xu = ps[1], &wl = ps[2], &xl = ps[3];
+    if (xu.C != wl.A || xu.C != xl.A || xu.ldc != wl.lda || xu.ldc != xl.lda) return false;
+    if (xu.M != wl.K || xu.M != xl.M || xu.M != wu.K || xu.N != wl.M || xu.N != xl.K || xu.N != wu.N || xu.K != wu.M || xl.N != wl.N) return false;
+    if ((wu.ad_p != nullptr) != (wl.ad_p != nullptr) || (wu.ad_p && wu.ad_kind != wl.ad_kind)) return false;      // one kernel, one optimizer kind
+    return afr_gemm_chain_counts(xu.M, xu.K, xu.N, wu.splitk, xl.N, wl.splitk, cus, nullptr, nullptr);
+}
+static int device_cus() {
+    static int cus[16];
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    if (dev >= 0 && dev < 16 && cus[dev]) return cus[dev];
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    if (dev >= 0 && dev < 16) cus[dev] = n;
+    return n;
+}
+static void chain_group(const GemmParams* ps, unsigned* hand_cnt, bf16k::GemmGroup& g) {
+    g.n = 4; g.chain = 1;
+    int total = 0;
+    for (int i = 0; i < 4; ++i) {
+        g.p[i] = ps[i];
+        g.blk0[i] = total;
+        total += ((ps[i].M + 255) / 256) * ((ps[i].N + 255) / 256) * ps[i].splitk;
+    }
+    g.blk0[4] = total;
+    g.p[1].flags |= AFR_GEMM_OUT_WTHRU; g.p[1].hand_cnt = hand_cnt;      // dX_up: the handed-over tile leaves write-through, then arrives
+}
+bool afr_gemm_chain_ok(int dtype, const GemmParams* ps) { return chain_descriptors_ok(dtype, ps, device_cus()); }
+// hand_cnt: one counter per 256-row block of dX_up's output, monotonic; every launch adds ceil(K_up / 256) arrivals to each
+// (afr_gemm_chain_arrivals) and waits for hand_target = the total after it.  hipErrorInvalidValue: not a chain, nothing launched.
+unsigned afr_gemm_chain_arrivals(const GemmParams* ps) { return (unsigned)((ps[1].N + 255) / 256); }
+hipError_t afr_launch_gemm_chain(int dtype, const GemmParams* ps, unsigned* hand_cnt, unsigned hand_target, uint32_t* err, hipStream_t s) {
+    if (!hand_cnt || !afr_gemm_chain_ok(dtype, ps)) return hipErrorInvalidValue;
+    bf16k::GemmGroup g;
+    chain_group(ps, hand_cnt, g);
+    g.hand_cnt = hand_cnt; g.hand_target = hand_target; g.hand_err = err;
+#ifdef AFR_GEMM_TIMING
+    { const int s1 = g_dbg_slot++ & 63, s2 = g_dbg_slot++ & 63; g.p[0].dbg_slot = g.p[1].dbg_slot = s1; g.p[2].dbg_slot = g.p[3].dbg_slot = s2; }
+#endif
+    const bool lion = ps[0].ad_p && ps[0].ad_kind == OPT_LION;
+    if (lion) hipLaunchKernelGGL(bf16k::gemm_bf16_group256_lion, dim3(g.blk0[4]), dim3(512), 0, s, g);
+    else hipLaunchKernelGGL(bf16k::gemm_bf16_group256, dim3(g.blk0[4]), dim3(512), 0, s, g);
+    return hipGetLastError();
+}
+// Host copy of the kernel's block map: block b of the chained launch -> its member (the chain order of ps; 0, 1: the upper pair,
+// the launch's first phase; 2, 3: the lower pair), its 256x256 tile and its K-slice.  false: b is outside the grid.
+bool afr_gemm_chain_block(const GemmParams* ps, int b, int* member, int* tm, int* tn, int* slice) {
+    bf16k::GemmGroup g;
+    chain_group(ps, nullptr, g);
+    if (b < 0 || b >= g.blk0[4]) return false;
+    const int i = bf16k::group_member_of(4, g.blk0, b);
+    tile_of_block(g.p[i], 256, 256, b - g.blk0[i], g.blk0[i + 1] - g.blk0[i], *tm, *tn, *slice);
+    *member = i;
+    return true;
 }
 // Tiles (blocks per K-slice) and threads per block of a product that afr_launch_gemm runs on the ring / tile kernels -- every
 // product with a fused loss does: whoever adds deferred loss partials needs the producer's grid and block size.

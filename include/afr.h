@@ -84,14 +84,16 @@ typedef struct afr_config {
                             bit 6: the glyph nets' first layer through the gather kernel + dense h1 in training steps too,
                             instead of the (character, font) combination table gathered inside the consuming products
                             bit 7: ReLU masks of the input-gradient products read from the stored activations instead of the
-                            bit masks the forward epilogues leave (bits 6, 7: A/B measurements; bitwise equal results)      */
+                            bit masks the forward epilogues leave (bits 6, 7: A/B measurements; bitwise equal results)
+                            bit 8: the output layer's and the last hidden layer's cooperative gradient pairs as two grouped
+                            launches instead of ONE chained launch (A/B measurements; bitwise equal results)               */
     int32_t loss;        /* AFR_LOSS_*: the output head and loss of every entry point below (0 = clamp + MSE); any other
                             value is AFR_EINVAL.  Appended after `reserved` (the struct grew by 8 bytes with it): a zero-initialised
                             config means what it meant, a caller compiled against the older header must be rebuilt          */
 } afr_config;
 /* the bits of afr_config.reserved, as described above */
 enum { AFR_CFG_UNFUSED_OPTIMIZER = 1, AFR_CFG_NO_GROUPED_GEMM = 2, AFR_CFG_NO_FUSED_GLYPH1 = 4, AFR_CFG_L1_BWD_UNFUSED = 16,
-       AFR_CFG_SLAB_SPLITK = 32, AFR_CFG_NO_COMBO_TABLE = 64, AFR_CFG_RELU_MASK_FROM_ACT = 128 };
+       AFR_CFG_SLAB_SPLITK = 32, AFR_CFG_NO_COMBO_TABLE = 64, AFR_CFG_RELU_MASK_FROM_ACT = 128, AFR_CFG_NO_PAIR_CHAIN = 256 };
 
 typedef struct afr_plan afr_plan;
 
@@ -471,6 +473,31 @@ int afr_op_linear_pair_plan(int B, int N, int K, int* tile256, int* splitk, int*
 int afr_op_linear(int dtype, int which, const void* x, const void* W, const float* bias, const void* dy, void* out, void* out2,
                   int B, int N, int K, const afr_linear_tail* tail /* or NULL */, void* workspace, size_t workspace_bytes,
                   char* kernel_name /* or NULL */, int name_cap, void* stream);
+/* Two stacked Linears' gradient pairs as the ONE chained launch a glyph training step issues for its output layer and the hidden
+ * layer below it (AFR_BF16): upper y = x_up[B][K_up] . W_up[N_up][K_up]^T, lower x_up = relu(x_lo[B][K_lo] . W_lo[K_up][K_lo]^T).
+ * Every operand, output and tail means what it means in two AFR_LIN_PAIR calls -- the upper one with (dy, x_up, W_up) -> out_up =
+ * dW_up, mid = its dx [B][K_up]; the lower one with (mid as dy, x_lo, W_lo) -> out_lo = dW_lo, dx_lo [B][K_lo] -- and every result
+ * is bit for bit theirs; `mid` is handed from the upper pair's workgroups to the lower pair's inside the launch.  Dense leading dimensions
+ * only (the tails' ld_out / ldx must be 0 or the dense value; ldaux, ld_db and ldmask are free).
+ * afr_op_linear_chain_plan (host-only): AFR_OK with the two splits and the workspace size when the shapes chain on a device of
+ * `cus` compute units (0: the current device's), AFR_EUNSUPPORTED otherwise -- both pairs cooperative 256x256 launches, the block
+ * counts of the swapped roles equal (dx_up = dW_lo, dW_up = dx_lo) and whole octets, a CU per workgroup of the upper pair (a step
+ * then issues the two launches).  *blocks: the launch's grid, both pairs.
+ * afr_op_linear_chain_block (host-only): the kernel's block map.  Block `block` of the launch runs K-slice *slice of the 256x256
+ * tile (*tm, *tn) of product *member: 0 = dW_up, 1 = dx_up (mid), 2 = dW_lo, 3 = dx_lo; *phase = 0 for the upper pair, whose
+ * workgroups are handed out first, 1 for the lower pair, whose workgroups take the CUs over as the upper ones leave.
+ * AFR_EINVAL for a block outside the grid.  workspace: 256-byte aligned, contents free. */
+/* 1 when a backward (or training step) of this plan at batch B issues that chained launch on a device of `cus` compute units (0:
+ * the bound device's), 0 when it issues the two grouped launches: another model kind or dtype, fewer than two hidden layers,
+ * AFR_CFG_NO_PAIR_CHAIN / _NO_GROUPED_GEMM / _SLAB_SPLITK, a shape afr_op_linear_chain_plan refuses.  (afr_backward_stage always
+ * issues a launch per stage: its caller reduces each stage's gradient range while the next stage runs.) */
+int afr_plan_pair_chain(const afr_plan* plan, int B, int cus);
+int afr_op_linear_chain_plan(int B, int N_up, int K_up, int K_lo, int cus, int* splitk_up, int* splitk_lo, int* blocks, size_t* workspace_bytes);
+int afr_op_linear_chain_block(int B, int N_up, int K_up, int K_lo, int block, int* phase, int* member, int* tm, int* tn, int* slice);
+int afr_op_linear_chain(const void* dy, const void* x_up, const void* W_up, void* out_up, void* mid, const afr_linear_tail* tail_up,
+                        const void* x_lo, const void* W_lo, void* out_lo, void* dx_lo, const afr_linear_tail* tail_lo,
+                        int B, int N_up, int K_up, int K_lo, void* workspace, size_t workspace_bytes,
+                        char* kernel_name /* or NULL */, int name_cap, void* stream);
 int afr_op_reduce(float* dst, const float* slabs, int nslabs, int64_t slab_stride, int64_t n,
                   float scale, int accumulate, void* stream);
 /* Several slab reductions in ONE launch (what a backward pass uses for all its split-K / per-block partial gradients):
