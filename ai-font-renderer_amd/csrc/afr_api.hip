@@ -2817,8 +2817,8 @@ extern "C" int afr_op_glyph_combo(const float* emb, const float* femb, const flo
     const char* what = "afr_op_glyph_combo";
     if (int rc = glyph_op_shape(what, AFR_BF16, B, E, vocab, n_fonts)) return rc;
     if (int rc = glyph_op_n1(what, N1)) return rc;
-    const size_t lds = (size_t)(256 * (E + 1) + 2 * 4 * E) * sizeof(float);      // glyph_combo_kernel: W [256][E+1] | 4 + 4 table rows
-    if (lds > 48 * 1024) return fail(AFR_EUNSUPPORTED, "%s: E = %d needs %zu bytes of staging, above the kernel's 48 KiB (E <= 40)", what, E, lds);
+    // glyph_combo_kernel keeps a W1 row of E <= 40 floats per thread in registers (the bound its 48 KiB of LDS staging used to set)
+    if (E > 40) return fail(AFR_EUNSUPPORTED, "%s: E = %d is above the kernel's E <= 40 (a W1 row per thread; formerly 48 KiB of staging)", what, E);
     if (ld1 < N1) return fail(AFR_EINVAL, "%s: ld1 = %d is below N1 = %d", what, ld1, N1);
     if ((long long)vocab * (n_fonts > 0 ? n_fonts : 1) * (long long)ld1 >= (1ll << 31)) return fail(AFR_EUNSUPPORTED, "%s: the combination table must stay below 2^31 elements", what);
     if (!emb || !W1 || !b1 || !x || !h1c || !h0c || !cidx || !err || (n_fonts > 0 && !femb)) return fail(AFR_EINVAL, "%s: null argument", what);

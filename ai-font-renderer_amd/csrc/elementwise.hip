@@ -1150,22 +1150,28 @@ hipError_t afr_launch_glyph_l1_fwd(int act_dtype, const float* emb, const float*
 // (0.5 MB + 16 KB + 32 KB, L2-resident); the GEMM kernels that consume h1 / h0 gather their operand rows through cidx while
 // staging (GemmParams::a_rowmap / b_rowmap / aux_rowmap; LDS-DMA takes a per-lane source address, so a gathered row costs
 // what a dense one does).  Same values bit for bit as the gather kernel's h1 / h0, same FLOPs in every product.
-// One kernel: a block takes CB_COMBOS combinations x 256 fc1 rows (grid x: combination groups, then the batch's index
-// blocks; grid y: 256-row chunks of fc1), stages its W1 rows through LDS as glyph_table_kernel does and runs the SAME
-// arithmetic as the table + gather kernels, in the same order: t_c = fma chain over k from 0 of Emb[x][k] W1[n][k], t_f likewise
-// for the font row, v = (t_c + b1[n]) + t_f, ReLU, one rounding to bf16 -- bit for bit the dense path's h1.
-constexpr int CB_COMBOS = 4;
+// One kernel, a 1-D grid: [combination groups x row chunks of fc1 | the batch's index blocks].  A computing block takes
+// CB_COMBOS combinations x CB_ROWS fc1 rows: thread (row = tid & 63, wave = tid >> 6) keeps ITS W1 row in registers (E <= CB_MAXE
+// floats, read once: W1 passes L2 once per combination group, never through LDS) and runs the wave's CB_PER combinations, whose
+// embedding and font rows are the same for the whole wave (uniform addresses: read through the scalar cache, an FMA operand each).
+// The SAME arithmetic as the table + gather kernels, in the same order: t_c = fma chain over k from 0 of Emb[x][k] W1[n][k], t_f
+// likewise for the font row, v = (t_c + b1[n]) + t_f, ReLU, one rounding to bf16 -- bit for bit the dense path's h1.
+// EC: the embedding width at compile time (32, C3's) or 0 = E at run time; FONTS: n_fonts > 0.  With both known the k loop is
+// one straight block, so the table rows' scalar loads are issued in batches ahead of their FMAs instead of one wait per quad.
+constexpr int CB_COMBOS = 16, CB_ROWS = 64, CB_PER = 4, CB_MAXE = 40;
+template <int EC, bool FONTS>
 __global__ __launch_bounds__(256) void glyph_combo_kernel(const float* __restrict__ W1, const float* __restrict__ b1,
                                                           const float* __restrict__ emb, const float* __restrict__ femb,
                                                           const int64_t* __restrict__ x, const int64_t* __restrict__ font,
-                                                          int B, int E, int N1, int vocab, int n_fonts, int combo_blocks,
+                                                          int B, int E_, int N1, int vocab, int n_fonts, int combo_blocks,
                                                           bf16_t* __restrict__ h1c, int ld1, bf16_t* __restrict__ h0c, int* __restrict__ cidx,
                                                           bf16_t* __restrict__ w1t, uint32_t* err_flag) {
-    extern __shared__ float sm[];                         // W [256][E+1] | emb rows [CB][E] | font rows [CB][E]
+    const int E = EC ? EC : E_;
+    constexpr int KQ = (EC ? EC : CB_MAXE) / 4;           // k quads in the unrolled loops
     const int nf = max(n_fonts, 1), ncombo = vocab * nf;
-    if ((int)blockIdx.x >= combo_blocks) {                // the batch's combination indices (with the index check of the gather)
-        if (blockIdx.y != 0) return;
-        const int b = ((int)blockIdx.x - combo_blocks) * 256 + threadIdx.x;
+    const int row_chunks = (N1 + CB_ROWS - 1) / CB_ROWS;
+    if ((int)blockIdx.x >= combo_blocks * row_chunks) {   // the batch's combination indices (with the index check of the gather)
+        const int b = ((int)blockIdx.x - combo_blocks * row_chunks) * 256 + threadIdx.x;
         if (b >= B) return;
         long long xi = x[b], fi = (n_fonts > 0 && font) ? font[b] : 0;
         if (xi < 0 || xi >= vocab) { atomicOr(err_flag, 1u); xi = min(max(xi, 0ll), (long long)vocab - 1); }
@@ -1173,45 +1179,64 @@ __global__ __launch_bounds__(256) void glyph_combo_kernel(const float* __restric
         cidx[b] = (int)(xi * nf + fi);
         return;
     }
-    float* Ws = sm;
-    float* er = sm + 256 * (E + 1);
-    float* fr = er + CB_COMBOS * E;
-    const int c0 = blockIdx.x * CB_COMBOS, n0 = blockIdx.y * 256;
-    const int nn = min(256, N1 - n0), nc = min(CB_COMBOS, ncombo - c0);
-    const int E4 = E >> 2;
-    for (int i = threadIdx.x; i < nn * E4; i += 256) {
-        const float4 v = *reinterpret_cast<const float4*>(W1 + (size_t)n0 * E + 4 * i);
-        float* d = Ws + (i / E4) * (E + 1) + 4 * (i % E4);
-        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-    }
-    for (int i = threadIdx.x; i < nc * E; i += 256) {
-        const int c = c0 + i / E, k = i % E, xi = c / nf, fi = c - xi * nf;
-        er[i] = emb[(size_t)xi * E + k];
-        fr[i] = n_fonts > 0 ? femb[(size_t)fi * E + k] : 0.f;
-        if (blockIdx.y == 0) h0c[(size_t)c * E + k] = (bf16_t)(n_fonts > 0 ? er[i] + fr[i] : er[i]);      // H0c = bf16(Emb[x] + Font[f])
-    }
-    __syncthreads();
-    if ((int)threadIdx.x >= nn) return;
-    const float* w = Ws + threadIdx.x * (E + 1);
-    // the first group of blocks also leaves W1^T as bf16 [E][N1] (the fused first-layer backward reads fc1's weights k-contiguous)
-    if (w1t && blockIdx.x == 0)
-        for (int k = 0; k < E; ++k) w1t[(size_t)k * N1 + n0 + threadIdx.x] = (bf16_t)w[k];
-    float tc[CB_COMBOS], tf[CB_COMBOS];
+    const int cb = blockIdx.x / row_chunks, rc = blockIdx.x - cb * row_chunks;      // a combination group's row chunks are neighbours
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int n = rc * CB_ROWS + (threadIdx.x & 63), c0 = cb * CB_COMBOS;
+    const bool row = n < N1;
+    float4 w[KQ];
 #pragma unroll
-    for (int j = 0; j < CB_COMBOS; ++j) tc[j] = tf[j] = 0.f;
-    for (int k = 0; k < E; ++k) {
-        const float wv = w[k];
+    for (int kk = 0; kk < KQ; ++kk)
+        w[kk] = (4 * kk < E && row) ? *reinterpret_cast<const float4*>(W1 + (size_t)n * E + 4 * kk) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float bias = row ? b1[n] : 0.f;
+    if (rc == 0)                                          // H0c = bf16(Emb[x] + Font[f]): once per combination group
+        for (int i = threadIdx.x; i < min(CB_COMBOS, ncombo - c0) * E; i += 256) {
+            const int c = c0 + i / E, k = i % E, xi = c / nf, fi = c - xi * nf;
+            const float e = emb[(size_t)xi * E + k];
+            h0c[(size_t)c * E + k] = (bf16_t)(FONTS ? e + femb[(size_t)fi * E + k] : e);
+        }
+    // the first combination group also leaves W1^T as bf16 [E][N1] (the fused first-layer backward reads fc1's weights
+    // k-contiguous): each of its blocks the rows it holds, wave w the k quads kk = w mod 4 (128-byte stores, E / 4 per thread)
+    if (w1t && cb == 0 && row) {
 #pragma unroll
-        for (int j = 0; j < CB_COMBOS; ++j) {             // (rows past nc read stale LDS; never stored)
-            tc[j] = fmaf(er[j * E + k], wv, tc[j]);
-            tf[j] = fmaf(fr[j * E + k], wv, tf[j]);
+        for (int kk = 0; kk < KQ; ++kk)
+            if (4 * kk < E && (kk & 3) == wave) {
+                bf16_t* d = w1t + (size_t)(4 * kk) * N1 + n;
+                d[0] = (bf16_t)w[kk].x; d[N1] = (bf16_t)w[kk].y; d[2 * (size_t)N1] = (bf16_t)w[kk].z; d[3 * (size_t)N1] = (bf16_t)w[kk].w;
+            }
+    }
+    const int cw = c0 + wave * CB_PER;                    // this wave's combinations (those past ncombo repeat the last one; never stored)
+    float tc[CB_PER], tf[CB_PER];
+#pragma unroll
+    for (int j = 0; j < CB_PER; ++j) {
+        const int c = min(cw + j, ncombo - 1), xi = c / nf, fi = c - xi * nf;
+        const float* er = emb + (size_t)xi * E;
+        const float* fr = FONTS ? femb + (size_t)fi * E : er;
+        tc[j] = tf[j] = 0.f;
+#pragma unroll
+        for (int kk = 0; kk < KQ; ++kk) {
+            if (4 * kk < E) {
+                const float wk[4] = {w[kk].x, w[kk].y, w[kk].z, w[kk].w};
+                const float4 e4 = *reinterpret_cast<const float4*>(er + 4 * kk);
+                const float ev[4] = {e4.x, e4.y, e4.z, e4.w};
+#pragma unroll
+                for (int u = 0; u < 4; ++u) tc[j] = fmaf(ev[u], wk[u], tc[j]);
+                if (FONTS) {
+                    const float4 f4 = *reinterpret_cast<const float4*>(fr + 4 * kk);
+                    const float fv[4] = {f4.x, f4.y, f4.z, f4.w};
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) tf[j] = fmaf(fv[u], wk[u], tf[j]);
+                }
+            }
         }
     }
-    const float bias = b1[n0 + threadIdx.x];
-    for (int j = 0; j < nc; ++j) {
-        float v = tc[j] + bias;
-        if (n_fonts > 0) v += tf[j];
-        h1c[(size_t)(c0 + j) * ld1 + n0 + threadIdx.x] = (bf16_t)fmaxf(v, 0.f);
+    if (!row) return;
+#pragma unroll
+    for (int j = 0; j < CB_PER; ++j) {
+        if (cw + j < ncombo) {
+            float v = tc[j] + bias;
+            if (FONTS) v += tf[j];
+            h1c[(size_t)(cw + j) * ld1 + n] = (bf16_t)fmaxf(v, 0.f);
+        }
     }
 }
 // combination rows + combination indices (+ W1^T) in ONE launch; h1c [vocab * max(n_fonts,1)][ld1], h0c [..][E], cidx [B]
@@ -1221,12 +1246,16 @@ hipError_t afr_launch_glyph_combo(const float* emb, const float* font_emb, const
     if (B <= 0) return hipSuccess;
     if ((N1 & 7) || (E & 7) || E > 256) return hipErrorInvalidValue;
     (void)table;
-    const size_t lds = (size_t)(256 * (E + 1) + 2 * CB_COMBOS * E) * sizeof(float);
-    if (lds > 48 * 1024) return hipErrorInvalidValue;                  // the combination path is planned for E <= 32 .. 40
+    if (E > CB_MAXE) return hipErrorInvalidValue;                      // the combination path is planned for E <= 32 .. 40
     const int ncombo = vocab * (n_fonts > 0 ? n_fonts : 1);
     const int combo_blocks = (ncombo + CB_COMBOS - 1) / CB_COMBOS;
-    hipLaunchKernelGGL(glyph_combo_kernel, dim3(combo_blocks + (B + 255) / 256, (N1 + 255) / 256), dim3(256), lds, s, W1, b1, emb, font_emb,
-                       x, font, B, E, N1, vocab, n_fonts, combo_blocks, (bf16_t*)h1c, ld1, (bf16_t*)h0c, cidx, (bf16_t*)w1t, err_flag);
+    const dim3 grid(combo_blocks * ((N1 + CB_ROWS - 1) / CB_ROWS) + (B + 255) / 256);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, W1, b1, emb, font_emb, x, font, B, E, N1, vocab, n_fonts, combo_blocks, (bf16_t*)h1c, ld1,
+                           (bf16_t*)h0c, cidx, (bf16_t*)w1t, err_flag);
+    };
+    if (E == 32) n_fonts > 0 ? launch(glyph_combo_kernel<32, true>) : launch(glyph_combo_kernel<32, false>);
+    else n_fonts > 0 ? launch(glyph_combo_kernel<0, true>) : launch(glyph_combo_kernel<0, false>);
     return hipGetLastError();
 }
 
