@@ -196,6 +196,8 @@ SIGNATURES = {
     "afr_op_tensor_stats": (_i32, [_vp, _vp, C.POINTER(AfrTensorSeg), _i32, _vp, _vp, _sz, _vp]),
     "afr_op_f32_to_bf16": (_i32, [_vp, _vp, _i64, _vp]),
     "afr_op_dataset_text": (_i32, [_i64, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp]),
+    "afr_op_dataset_text_w": (_i32, [_i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "afr_op_text_weights": (_i32, [_vp, _i32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "afr_op_compose_sheets": (_i32, [C.POINTER(AfrGlyphAtlas), C.POINTER(AfrSheetGeometry), _vp, _i32, _vp, _i64, _vp, _vp, _vp]),
     "afr_op_sheet_char_errors": (_i32, [C.POINTER(AfrGlyphAtlas), C.POINTER(AfrSheetGeometry), _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "afr_op_f32_to_fp8": (_i32, [_vp, _vp, _i64, _f32, _vp]),

@@ -2534,6 +2534,38 @@ extern "C" int afr_op_dataset_text(int64_t first_seed, const int64_t* seed_rows,
     HIPCHK(afr_launch_dataset_text(first_seed, seed_rows, out_rows, n, min_len, max_len, codes, ldx, len, (hipStream_t)stream));
     return AFR_OK;
 }
+extern "C" int afr_op_dataset_text_w(int64_t first_seed, const int64_t* seed_rows, const int64_t* out_rows, int64_t n, int min_len, int max_len,
+                                     const uint32_t* cum, int64_t* codes, int ldx, int32_t* len, uint32_t* err, void* stream) {
+    if (!codes || !cum) return fail(AFR_EINVAL, "afr_op_dataset_text_w: codes or cum is null");
+    if (n < 1) return fail(AFR_EINVAL, "afr_op_dataset_text_w: n = %lld, must be >= 1", (long long)n);
+    if (ldx < 1) return fail(AFR_EINVAL, "afr_op_dataset_text_w: ldx = %d, must be positive", ldx);
+    if (ldx > CMP_MAX_LDX) return fail(AFR_EUNSUPPORTED, "afr_op_dataset_text_w: ldx = %d, at most %d codes per row", ldx, CMP_MAX_LDX);
+    if (min_len < 1 || max_len < min_len || max_len > ldx)
+        return fail(AFR_EINVAL, "afr_op_dataset_text_w: text lengths %d..%d must satisfy 1 <= min_len <= max_len <= ldx = %d", min_len, max_len, ldx);
+    if (((uintptr_t)codes & 7) || ((uintptr_t)seed_rows & 7) || ((uintptr_t)out_rows & 7) || ((uintptr_t)len & 3) || ((uintptr_t)cum & 3) ||
+        ((uintptr_t)err & 3))
+        return fail(AFR_EINVAL, "afr_op_dataset_text_w: codes, seed_rows and out_rows must be 8-byte aligned, cum, len and err 4-byte");
+    DevGuard dg(device_of(codes));
+    HIPCHK(afr_launch_dataset_text_w(first_seed, seed_rows, out_rows, n, min_len, max_len, cum, codes, ldx, len, err, (hipStream_t)stream));
+    return AFR_OK;
+}
+extern "C" int afr_op_text_weights(const uint64_t* by_code, int n_codes, const uint32_t* members, uint32_t floor_w, uint32_t gain, uint32_t* cum,
+                                   uint32_t* w, void* stream) {
+    const char* who = "afr_op_text_weights";
+    if (!members || !cum) return fail(AFR_EINVAL, "%s: members or cum is null", who);
+    if (by_code && n_codes < AFR_TEXT_FIRST + AFR_TEXT_CODES)
+        return fail(AFR_EINVAL, "%s: n_codes = %d, a by-code table must hold the codes up to %d", who, n_codes, AFR_TEXT_FIRST + AFR_TEXT_CODES - 1);
+    if (members[2] >> (AFR_TEXT_CODES - 64))
+        return fail(AFR_EINVAL, "%s: member bits above bit %d (code %d) are set", who, AFR_TEXT_CODES - 1, AFR_TEXT_FIRST + AFR_TEXT_CODES - 1);
+    if (!(members[0] | members[1] | members[2])) return fail(AFR_EINVAL, "%s: the member set is empty", who);
+    if (floor_w < 1u || floor_w > 65535u || gain > 65535u)
+        return fail(AFR_EINVAL, "%s: floor_w = %u must lie in 1..65535, gain = %u in 0..65535", who, floor_w, gain);
+    if (((uintptr_t)by_code & 7) || ((uintptr_t)cum & 3) || ((uintptr_t)w & 3))
+        return fail(AFR_EINVAL, "%s: by_code must be 8-byte aligned, cum and w 4-byte", who);
+    DevGuard dg(device_of(cum));
+    HIPCHK(afr_launch_text_weights((const unsigned long long*)by_code, members, floor_w, gain, cum, w, (hipStream_t)stream));
+    return AFR_OK;
+}
 // What afr_op_compose_sheets and afr_op_sheet_char_errors refuse alike: `dense` is the sheet-shaped buffer (out / pred), `rows` the row
 // vector, lds_bytes the kernel's whole LDS need.  -> AFR_OK or the failure, already recorded.
 static int sheet_args_check(const char* who, const char* dense_name, const afr_glyph_atlas* atlas, const afr_sheet_geometry* geo,

@@ -439,6 +439,12 @@ int afr_compose_blocks(long long n);
 hipError_t afr_launch_dataset_text(long long first_seed, const int64_t* seed_rows, const int64_t* out_rows, long long n, int min_len, int max_len,
                                    int64_t* codes, int ldx, int32_t* len, hipStream_t s);
 hipError_t afr_launch_compose_sheets(const ComposeArgs& a, hipStream_t s);
+// the weighted text source (cum: device [94] inclusive cumulative weights of the codes 33..126) and the one-workgroup launch that builds
+// its table from afr_op_sheet_char_errors' by-code counters (members: host, bit i = code 33 + i)
+hipError_t afr_launch_dataset_text_w(long long first_seed, const int64_t* seed_rows, const int64_t* out_rows, long long n, int min_len,
+                                     int max_len, const uint32_t* cum, int64_t* codes, int ldx, int32_t* len, uint32_t* err, hipStream_t s);
+hipError_t afr_launch_text_weights(const unsigned long long* by_code, const uint32_t members[3], uint32_t floor_w, uint32_t gain, uint32_t* cum,
+                                   uint32_t* w, hipStream_t s);
 // afr_op_sheet_char_errors: compose's arguments (c.out unused, c.out_rows = the rows of codes the samples read) beside the dense
 // prediction and the two outputs.  LDS as compose's, plus the position records and one 64-bit counter set per code.
 struct CharErrArgs {

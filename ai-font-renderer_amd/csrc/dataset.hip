@@ -38,6 +38,128 @@ hipError_t afr_launch_dataset_text(long long first_seed, const int64_t* seed_row
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------- weighted text
+// afr_op_dataset_text_w: dataset_text_kernel with the letter drawn from a table of weights (synth.lcg_text_weighted).  The 94 inclusive
+// cumulative weights go to LDS once per workgroup, padded to 128 entries with 2^32 - 1, which no draw r < total <= 2^32 - 1 reaches: the
+// seven-step search below then needs no bound check.  It counts the entries <= r, which is the smallest i with cum[i] > r; an entry of
+// zero width (cum[i] == cum[i - 1]) is passed over with its predecessor.  A table whose total is 0 draws nothing: zero rows, bit 0 of *err.
+constexpr int TXT_FIRST = 33, TXT_CODES = 94, TXT_PAD = 128;
+__global__ __launch_bounds__(256) void dataset_text_w_kernel(long long first_seed, const int64_t* __restrict__ seed_rows,
+                                                             const int64_t* __restrict__ out_rows, long long n, int min_len, int max_len,
+                                                             const uint32_t* __restrict__ cum, int64_t* __restrict__ codes, int ldx,
+                                                             int32_t* __restrict__ len, uint32_t* __restrict__ err) {
+    __shared__ uint32_t s_cum[TXT_PAD];
+    if (threadIdx.x < TXT_PAD) s_cum[threadIdx.x] = threadIdx.x < TXT_CODES ? cum[threadIdx.x] : 0xFFFFFFFFu;
+    __syncthreads();
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t total = s_cum[TXT_CODES - 1];
+    uint32_t state = (uint32_t)(uint64_t)(first_seed + (seed_rows ? seed_rows[j] : j));
+    const long long row = out_rows ? out_rows[j] : j;
+    int64_t* dst = codes + row * (long long)ldx;
+    auto draw = [&](uint32_t k) -> uint32_t {
+        state = state * 1664525u + 1013904223u;
+        return (uint32_t)(((uint64_t)state * k) >> 32);
+    };
+    int length = 0, pos = 0;
+    if (total != 0u) {
+        length = (int)draw((uint32_t)(max_len - min_len + 1)) + min_len;
+        int remaining = length;
+        while (remaining > 0) {
+            const int wl = min((int)draw(10u) + 1, remaining);
+            for (int i = 0; i < wl; ++i) {
+                const uint32_t r = draw(total);
+                int at = 0;
+#pragma unroll
+                for (int step = TXT_PAD / 2; step > 0; step >>= 1)
+                    if (s_cum[at + step - 1] <= r) at += step;
+                dst[pos++] = TXT_FIRST + at;
+            }
+            remaining -= wl;
+            if (remaining > 0) { dst[pos++] = 32; --remaining; }
+        }
+    } else if (threadIdx.x == 0 && err) {
+        atomicOr(err, AFR_ERR_INDEX);                                  // lane 0 of every workgroup has a sample (j < n)
+    }
+    for (; pos < ldx; ++pos) dst[pos] = 0;
+    if (len) len[row] = length;
+}
+
+hipError_t afr_launch_dataset_text_w(long long first_seed, const int64_t* seed_rows, const int64_t* out_rows, long long n, int min_len,
+                                     int max_len, const uint32_t* cum, int64_t* codes, int ldx, int32_t* len, uint32_t* err, hipStream_t s) {
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(dataset_text_w_kernel, dim3(blocks), dim3(256), 0, s, first_seed, seed_rows, out_rows, n, min_len, max_len, cum, codes, ldx,
+                       len, err);
+    return hipGetLastError();
+}
+
+// afr_op_text_weights: the table above from afr_op_sheet_char_errors' by-code counters, one workgroup of 128 lanes, lane i = code 33 + i
+// (synth.text_weights; the definition is in include/afr.h).  Two 64-bit sums over the members (a tree in LDS), the weight of each member
+// in registers, an inclusive scan of the 94 weights in LDS.  No atomics: a second launch stores the same words.
+struct TextWeightsArgs {
+    const unsigned long long* by_code; uint32_t members[3]; uint32_t floor_w, gain; uint32_t* cum; uint32_t* w;
+};
+__global__ __launch_bounds__(TXT_PAD) void text_weights_kernel(TextWeightsArgs a) {
+    __shared__ unsigned long long s_p[TXT_PAD], s_s[TXT_PAD];
+    __shared__ uint32_t s_w[TXT_PAD];
+    const int t = threadIdx.x;
+    const bool member = t < TXT_CODES && ((a.members[t >> 5] >> (t & 31)) & 1u);
+    const bool counted = member && a.by_code && a.gain;                // non-members and the background row are never read
+    unsigned long long pixels = counted ? a.by_code[(TXT_FIRST + t) * 5 + 1] : 0ull;
+    unsigned long long sumsq = counted ? a.by_code[(TXT_FIRST + t) * 5 + 2] : 0ull;
+    s_p[t] = pixels; s_s[t] = sumsq;
+    __syncthreads();
+    for (int off = TXT_PAD / 2; off > 0; off >>= 1) {
+        if (t < off) { s_p[t] += s_p[t + off]; s_s[t] += s_s[t + off]; }
+        __syncthreads();
+    }
+    unsigned long long P = s_p[0], S = s_s[0];
+    uint32_t w = member ? a.floor_w : 0u;
+    if (member && S != 0ull) {
+        const int k = max(0, 64 - __clzll((long long)S) - 47);         // S >> k < 2^47: every << 16 below stays inside 64 bits
+        P >>= k; S >>= k; pixels >>= k; sumsq >>= k;
+        const unsigned long long m_ref = max(1ull, (S << 16) / max(1ull, P));
+        unsigned long long rel = 1ull << 16;
+        if (pixels != 0ull) {
+            // min((q << 16) / m_ref, 16 << 16) without forming q << 16, which need not fit: q / m_ref >= 16 is the cap, else sixteen
+            // steps of long division on the remainder (< m_ref < 2^63, so its double fits)
+            const unsigned long long q = (sumsq << 16) / pixels;
+            unsigned long long hi = q / m_ref, rem = q - hi * m_ref;
+            if (hi >= 16ull) {
+                rel = 16ull << 16;
+            } else {
+                for (int b = 0; b < 16; ++b) {
+                    rem <<= 1; hi <<= 1;
+                    if (rem >= m_ref) { rem -= m_ref; hi |= 1ull; }
+                }
+                rel = hi;
+            }
+        }
+        w = a.floor_w + (uint32_t)(((unsigned long long)a.gain * rel) >> 16);
+    }
+    s_w[t] = w;
+    __syncthreads();
+    uint32_t c = w;
+    for (int off = 1; off < TXT_PAD; off <<= 1) {
+        const uint32_t left = t >= off ? s_w[t - off] : 0u;
+        __syncthreads();
+        c += left;
+        s_w[t] = c;
+        __syncthreads();
+    }
+    if (t < TXT_CODES) {
+        a.cum[t] = c;
+        if (a.w) a.w[t] = w;
+    }
+}
+
+hipError_t afr_launch_text_weights(const unsigned long long* by_code, const uint32_t members[3], uint32_t floor_w, uint32_t gain, uint32_t* cum,
+                                   uint32_t* w, hipStream_t s) {
+    const TextWeightsArgs a{by_code, {members[0], members[1], members[2]}, floor_w, gain, cum, w};
+    hipLaunchKernelGGL(text_weights_kernel, dim3(1), dim3(TXT_PAD), 0, s, a);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------- compose
 // One workgroup of 256 threads per sheet, grid-stride.  The atlas's cells are copied into LDS once per workgroup (the paint phase
 // gathers single bytes from them at per-lane addresses, which LDS serves and a global load does not); advances and kerning are read

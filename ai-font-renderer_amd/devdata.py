@@ -13,10 +13,18 @@ datagen.render_sheet's bytes from it exactly (tests/test_compose_cpu.py, tests/t
 char_errors(atlas, codes, pred) runs the same layout once more (afr_op_sheet_char_errors) to charge a prediction's error to the characters
 that own the pixels: the table AttentionFontRenderer.char_errors and AFR_CHAR_REPORT read.
 
-Two things the atlas cannot reproduce, both outside the data set's alphabet (A-Z and space):
+The texts' alphabet is the caller's.  afr_op_dataset_text restates the reference's generator (words of A-Z); afr_op_dataset_text_w draws
+each letter from a table of integer weights over the codes 33..126 instead -- text_weights(alphabet, by_code, floor_w, gain) builds the
+table on the device, with equal weights or steered by char_errors' by-code counters where they lie -- and generate_codes(..., cum=...)
+and reference_dataset(..., alphabet=...) draw from it.  With equal weights on A-Z the texts are the reference's byte for byte.
+
+Two things the atlas cannot reproduce:
   * glyph substitution.  A font that replaces a run of characters by another glyph -- Fira Code's ligatures, "fi", "<>", "->" -- draws
-    that glyph under raqm layout; the atlas knows single characters and pairs' kerning only, so such text composes differently;
-  * the .notdef box.  Codes outside 32..126 have a blank cell and no advance here, where PIL draws the font's missing-glyph box.
+    that glyph under raqm layout; the atlas knows single characters and pairs' kerning only.  With an alphabet that holds such pairs
+    (lower, letters, alnum, ascii) a Fira Code atlas composes what the atlas says, not what a shaping engine would draw; the data set
+    is self-consistent either way -- targets, char_errors and the steering all read the same layout -- and A-Z holds no such pair;
+  * the .notdef box.  Codes outside 32..126 have a blank cell and no advance here, where PIL draws the font's missing-glyph box.  No
+    alphabet reaches them: the text sources draw 32..126 only.
 """
 import collections
 import ctypes as C
@@ -151,10 +159,35 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-def generate_codes(n, first_seed=42, max_length=100, device=None, out=None, rows=None, seed_rows=None, lens=None):
+def text_weights(alphabet, by_code=None, floor_w=4096, gain=0, device=None):
+    """afr_op_text_weights: the letter table of the weighted text source, built on the device -> (cum, w), two int32 [94] tensors holding
+    uint32 words (the total stays below 2^27).  alphabet: a name or literal string (synth.alphabet_members) or the 94 flags themselves;
+    by_code: char_errors' int64 [n_codes + 1, 5] table where it lies on the device, or None for equal weights floor_w.  Every member
+    weighs floor_w + gain * min(its mean squared error / the alphabet's, 16): synth.text_weights in integers.  Nothing is read back."""
+    from . import synth
+    members = synth.alphabet_members(alphabet) if isinstance(alphabet, str) else [int(bool(m)) for m in alphabet]
+    words = (C.c_uint32 * 3)(*synth.members_words(members))
+    if by_code is not None:
+        if by_code.dtype != torch.int64 or by_code.dim() != 2 or by_code.shape[1] != 5 or not by_code.is_contiguous() or not by_code.is_cuda:
+            raise ValueError("by_code must be a contiguous int64 [n_codes + 1, 5] tensor on the device")
+        device = by_code.device
+    if device is None:
+        raise ValueError("text_weights needs a device or a by_code table")
+    device = torch.device(device)
+    cum, w = torch.empty(synth.TEXT_CODES, dtype=torch.int32, device=device), torch.empty(synth.TEXT_CODES, dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _lib.check(_lib.lib().afr_op_text_weights(_ptr(by_code), 0 if by_code is None else by_code.shape[0] - 1, words, int(floor_w), int(gain),
+                                                   _ptr(cum), _ptr(w), _stream(device)))
+    return cum, w
+
+
+def generate_codes(n, first_seed=42, max_length=100, device=None, out=None, rows=None, seed_rows=None, lens=None, cum=None, check_total=True):
     """afr_op_dataset_text: the texts of synth.lcg_text(first_seed + seed, 10, max_length) as zero-padded int64 codes.  Sample j of n
     takes seed seed_rows[j] (default j) and goes to row rows[j] (default j) of out -- int64 [N, L >= max_length], default a new
-    [n, max_length] -- and of lens (int32 [N], optional with out).  Returns (out, lens)."""
+    [n, max_length] -- and of lens (int32 [N], optional with out).  Returns (out, lens).  cum (text_weights' int32 [94] table on the
+    device): afr_op_dataset_text_w instead, the texts of synth.lcg_text_weighted; a table whose total is 0 is a ValueError (the rows are
+    zero-filled and flagged on the device; reading the flag waits for the launch, check_total=False leaves it unread -- for a table from
+    text_weights, whose total cannot be 0)."""
     if out is None:
         if rows is not None:
             raise ValueError("rows needs the buffer they are rows of (out)")
@@ -172,9 +205,18 @@ def generate_codes(n, first_seed=42, max_length=100, device=None, out=None, rows
         raise ValueError(f"{n} samples do not fit the {out.shape[0]} rows of out")
     if rows is not None and n and (int(rows.min()) < 0 or int(rows.max()) >= out.shape[0]):
         raise IndexError("rows outside out")
+    if cum is not None and (cum.dtype != torch.int32 or cum.device != device or cum.numel() != 94 or not cum.is_contiguous()):
+        raise ValueError(f"cum must be a contiguous int32 [94] tensor on {device} (text_weights' table)")
     with torch.cuda.device(device):
-        _lib.check(_lib.lib().afr_op_dataset_text(int(first_seed), _ptr(seed_rows), _ptr(rows), n, MIN_TEXT_LENGTH, int(max_length),
-                                                   _ptr(out), out.shape[1], _ptr(lens), _stream(device)))
+        if cum is None:
+            _lib.check(_lib.lib().afr_op_dataset_text(int(first_seed), _ptr(seed_rows), _ptr(rows), n, MIN_TEXT_LENGTH, int(max_length),
+                                                       _ptr(out), out.shape[1], _ptr(lens), _stream(device)))
+        else:
+            err = torch.zeros(1, dtype=torch.int32, device=device)
+            _lib.check(_lib.lib().afr_op_dataset_text_w(int(first_seed), _ptr(seed_rows), _ptr(rows), n, MIN_TEXT_LENGTH, int(max_length),
+                                                         _ptr(cum), _ptr(out), out.shape[1], _ptr(lens), _ptr(err), _stream(device)))
+            if check_total and int(err) & 1:
+                raise ValueError("the letter table's total weight is 0: no text can be drawn from it")
     return out, lens
 
 
@@ -245,10 +287,12 @@ def char_errors(atlas, codes, pred, height=80, width=240, rows=None, by_code=Non
     return CharErrors(per_pos.to(torch.int64) & 0xFFFFFFFF, by_code)
 
 
-def reference_dataset(n, atlas, first_seed=42, max_length=100, height=80, width=240):
+def reference_dataset(n, atlas, first_seed=42, max_length=100, height=80, width=240, alphabet=None):
     """TensorDataset(int64 [n, L] codes, uint8 [n, height, width] sheets) on the atlas's device: the tensors
     helpers.load_string_dataset_u8 returns for the folder datagen.generate(out_dir, n, font, first_seed) writes -- L is the longest
-    text's length, as there."""
-    codes, lens = generate_codes(n, first_seed, max_length, device=atlas.device)
+    text's length, as there.  alphabet (a name or literal, synth.alphabet_members): the texts come from the weighted source with equal
+    weights over that alphabet instead; "upper" gives the same bytes as None."""
+    cum = None if alphabet is None else text_weights(alphabet, device=atlas.device)[0]
+    codes, lens = generate_codes(n, first_seed, max_length, device=atlas.device, cum=cum)
     codes = codes[:, :int(lens.max())].contiguous()
     return data.TensorDataset(codes, compose_sheets(atlas, codes, height, width))

@@ -53,7 +53,18 @@ What is deliberately different from the reference, and why:
     the rendering error by character, counted on the device (devdata.char_errors after Engine.evaluate_last's bitmaps): on the
     epochs that print a status line, a block headed "Char report:" with the background's rms level error and wrong-ink rate and the
     k codes with the largest mean squared level error over the validation sheets, and epoch_<e>/char_errors.tsv with every code's
-    counters.  Nothing steps: every other line and artefact is what it is without the variable.  Unset: nothing changes.
+    counters.  Nothing steps: every other line and artefact is what it is without the variable.  Unset: nothing changes;
+  * AFR_ALPHABET=<name or characters> (needs AFR_DEVICE_DATA) draws the NUM_SAMPLES texts, and AFR_FRESH_DATA's, from the weighted text
+    source (devdata.text_weights, afr_op_dataset_text_w) with equal weights over that alphabet: upper, lower, letters, alnum, ascii, or
+    the literal set of the characters given (codes 33..126; the space separates words and is no letter).  With an alphabet other than
+    upper the test-string renders add a lower-case pangram, the digits and a line of punctuation, each filtered to the alphabet.  Unset,
+    or upper: byte for byte the run it is without the variable;
+  * AFR_STEER=<share> (0 <= share < 1, needs AFR_FRESH_DATA) steers the fresh texts by the characters' errors: every validation pass keeps
+    afr_op_sheet_char_errors' by-code table (AFR_CHAR_REPORT's mechanism, all-reduced, so every rank holds the same table), and the
+    rewrite before the next epoch draws its letters with weight floor_w + gain * min(the character's mean squared error / the
+    alphabet's, 16), floor_w = round((1 - share) * 4096), gain = round(share * 4096) -- built on the device from the table where it
+    lies (afr_op_text_weights).  The validation rows are never rewritten, so validation losses stay comparable.  On the epochs that
+    print a status line one more line names the five heaviest codes of the last rewrite.  Unset or 0: the run without it.
 """
 import contextlib
 import datetime
@@ -170,6 +181,47 @@ def _char_report_from_env():
 
 
 CHAR_REPORT = _char_report_from_env()     # likewise read at import
+
+
+def _alphabet_from_env():
+    """AFR_ALPHABET = one of synth's alphabet names or a literal string of characters -> the string; unset or empty -> None.  A literal
+    with a space or a code outside 33..126, or an alphabet without AFR_DEVICE_DATA, is a ValueError."""
+    spec = os.environ.get("AFR_ALPHABET", "")
+    if not spec:
+        return None
+    from . import synth
+    synth.alphabet_members(spec)
+    if not os.environ.get("AFR_DEVICE_DATA", "").strip():
+        raise ValueError("AFR_ALPHABET needs AFR_DEVICE_DATA: the folder data set's texts are what they are")
+    return spec
+
+
+def _steer_from_env():
+    """AFR_STEER = "<share>", a float in [0, 1): how much of a fresh text's letter weight follows the characters' errors; unset, empty
+    or 0 -> 0.0 (off).  Anything else, or a share without AFR_FRESH_DATA (nothing is redrawn), is a ValueError."""
+    spec = os.environ.get("AFR_STEER", "").strip()
+    if not spec:
+        return 0.0
+    try:
+        share = float(spec)
+    except ValueError:
+        share = -1.0
+    if not 0.0 <= share < 1.0:
+        raise ValueError(f"AFR_STEER must be a share in [0, 1), e.g. 0.5, got {spec!r}")
+    if os.environ.get("AFR_FRESH_DATA", "").strip() != "1":
+        raise ValueError("AFR_STEER needs AFR_FRESH_DATA=1: only texts that are redrawn every epoch can be steered")
+    return share
+
+
+ALPHABET, STEER = _alphabet_from_env(), _steer_from_env()     # likewise read at import
+STEER_UNIT = 4096                                             # floor_w + gain of the steered letter table: the weight of an average character
+
+
+def _steer_weights(share):
+    """(floor_w, gain) of devdata.text_weights for a steering share."""
+    return max(1, round((1.0 - share) * STEER_UNIT)), round(share * STEER_UNIT)
+
+
 DATA_FIRST_SEED = 42                                  # sample i of the data set is the text of seed i + 42 (generate_font.ts:204)
 
 
@@ -352,6 +404,25 @@ test_strings = [
     "EXACTLY TWENTY CHARS",
     " " * 20,
 ]
+
+
+# what an alphabet other than A-Z adds to them: a lower-case pangram, the digits, the punctuation
+EXTRA_TEST_STRINGS = (
+    "the quick brown fox jumps over the lazy dog",
+    "0123456789",
+    "!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~",
+)
+
+
+def _extra_test_strings(alphabet):
+    """EXTRA_TEST_STRINGS filtered to the alphabet's members and the space; strings nothing is left of are dropped.  None or upper: none."""
+    if alphabet is None or alphabet == "upper":
+        return []
+    from . import synth
+    members = synth.alphabet_members(alphabet)
+    keep = {" "} | {chr(synth.TEXT_FIRST + i) for i, m in enumerate(members) if m}
+    out = ["".join(c for c in s if c in keep).strip() for s in EXTRA_TEST_STRINGS]
+    return [s for s in out if s]
 
 
 # ---------------------------------------------------------------- model
@@ -602,7 +673,7 @@ def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, wor
     measures the other against).  report: a _ValReport (AFR_VAL_REPORT) that every validation batch is evaluated into between its
     forward and its loss; None: the pass as it always was.  treport: a _TensorReport (AFR_TENSOR_REPORT, rank 0 only): the weights are
     snapshotted before the last training batch and compared after it, and once the validation loss has been read the first training
-    batch is run once more as a probe for its gradients.  creport: a _CharReport (AFR_CHAR_REPORT): every validation batch's bitmaps --
+    batch is run once more as a probe for its gradients.  creport: a _CharReport (AFR_CHAR_REPORT, AFR_STEER): every validation batch's bitmaps --
     of the one evaluation it shares with report -- are measured against the sheets the atlas composes for the batch's rows."""
     from .parallel import shard_rows
     eng = model.engine
@@ -655,16 +726,35 @@ def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, wor
     return avg_train_loss, avg_val_loss
 
 
-def _fresh_rows(atlas, n):
-    """AFR_FRESH_DATA: refresh(epoch, rows, inputs, targets) rewrites rows `rows` of the bound codes and sheets in place, on the current
-    stream: row r becomes the text of seed DATA_FIRST_SEED + epoch * n + r, as long as a row of inputs is wide at the most, and its sheet."""
-    from . import devdata
+def _fresh_rows(atlas, n, alphabet=None, steer=0.0):
+    """AFR_FRESH_DATA: refresh(epoch, rows, inputs, targets, by_code=None) rewrites rows `rows` of the bound codes and sheets in place, on
+    the current stream: row r becomes the text of seed DATA_FIRST_SEED + epoch * n + r, as long as a row of inputs is wide at the most, and
+    its sheet.  alphabet (AFR_ALPHABET) or steer (AFR_STEER) take the texts from the weighted source: equal weights over the alphabet
+    (A-Z without one), or -- given by_code, the by-code table of the last validation pass -- _steer_weights(steer) of it.  The table, the
+    letter weights and the texts follow one another on the stream: nothing is read back.  refresh.w and refresh.by_code hold the last
+    rewrite's weights and the table they were built from."""
+    from . import devdata, synth
+    members = synth.alphabet_members(alphabet or "upper") if alphabet or steer else None
 
-    def refresh(epoch, rows, inputs, targets):
+    def refresh(epoch, rows, inputs, targets, by_code=None):
         rows = rows.to(device)
-        devdata.generate_codes(rows.numel(), DATA_FIRST_SEED, max_length=inputs.shape[1], out=inputs, rows=rows, seed_rows=epoch * n + rows)
+        cum = None
+        if members is not None:
+            floor_w, gain = _steer_weights(steer) if by_code is not None else (STEER_UNIT, 0)
+            cum, refresh.w = devdata.text_weights(members, by_code, floor_w, gain, device=device)
+            refresh.by_code = by_code
+        devdata.generate_codes(rows.numel(), DATA_FIRST_SEED, max_length=inputs.shape[1], out=inputs, rows=rows, seed_rows=epoch * n + rows, cum=cum,
+                               check_total=False)
         devdata.compose_sheets(atlas, inputs.index_select(0, rows), targets.shape[1], targets.shape[2], out=targets, rows=rows)
+    refresh.w = refresh.by_code = None
     return refresh
+
+
+def _steer_line(share, w, k=5):
+    """The status line of AFR_STEER, read from the weights of the last rewrite (int32 [94] on the device): the one host read steering adds."""
+    w = w.tolist()
+    top = sorted((i for i in range(len(w)) if w[i]), key=lambda i: (-w[i], i))[:k]
+    return f"Steer: share {share:g}, heaviest {len(top)} codes " + ", ".join(f"{33 + i} {chr(33 + i)!r} x{w[i] / STEER_UNIT:.2f}" for i in top)
 
 
 def train_attention_model(model, dataset, batch_size, refresh=None, atlas=None):
@@ -704,8 +794,16 @@ def train_attention_model(model, dataset, batch_size, refresh=None, atlas=None):
                 f.write("fresh_data = 1\n")
             if CHAR_REPORT:                     # likewise
                 f.write(f"char_report = {CHAR_REPORT}\n")
+            if ALPHABET:                        # likewise
+                f.write(f"alphabet = {ALPHABET}\n")
+            if STEER:                           # likewise
+                f.write(f"steer = {STEER:g}\n")
     if CHAR_REPORT and atlas is None:
         raise ValueError("the character report needs the glyph atlas the data set was composed from (AFR_DEVICE_DATA)")
+    if STEER and (atlas is None or refresh is None):
+        raise ValueError("steering needs the glyph atlas and the fresh-data rewrite (AFR_DEVICE_DATA, AFR_FRESH_DATA)")
+    strings = test_strings + _extra_test_strings(ALPHABET)
+    steer_table = None                          # AFR_STEER: the by-code table the last validation pass left on the device
 
     order = _EpochOrder(len(dataset))
     print(f"Dataset split: {order.train_size} training samples, {order.val_size} validation samples")
@@ -736,12 +834,15 @@ def train_attention_model(model, dataset, batch_size, refresh=None, atlas=None):
         lr = lr_holder.param_groups[0]["lr"]
         report = _ValReport(VAL_REPORT, device, bitmaps=epoch % 5 == 0) if VAL_REPORT else None
         treport = _TensorReport(model) if TENSOR_REPORT and rank == 0 and epoch % 5 == 0 else None
-        creport = _CharReport(CHAR_REPORT, atlas, inputs) if CHAR_REPORT and epoch % 5 == 0 else None
+        char_lines = bool(CHAR_REPORT) and epoch % 5 == 0
+        creport = _CharReport(CHAR_REPORT or 1, atlas, inputs) if char_lines or STEER else None      # steering keeps the table every epoch
         if refresh is not None and epoch >= 1:
-            refresh(epoch, order.train_idx, inputs, targets)
+            refresh(epoch, order.train_idx, inputs, targets, **(dict(by_code=steer_table) if STEER else {}))
         avg_train_loss, avg_val_loss = _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True, report=report,
                                                   treport=treport, creport=creport)
 
+        if STEER:
+            steer_table = creport.table
         scheduler.step(avg_val_loss)
         is_best = avg_val_loss < best_val_loss
         if is_best:
@@ -766,11 +867,13 @@ def train_attention_model(model, dataset, batch_size, refresh=None, atlas=None):
                         helpers.u8_array_to_image(report.u8[j].cpu().numpy(), f"{OUTPUT_DIR}/epoch_{epoch}/val_worst_{j}.bmp")
                 if treport is not None:
                     print("\n".join(treport.lines()))
-                if creport is not None:
+                if char_lines:
                     print("\n".join(creport.lines()))
                     creport.write_tsv(f"{OUTPUT_DIR}/epoch_{epoch}/char_errors.tsv")
+                if STEER and refresh.w is not None:
+                    print(_steer_line(STEER, refresh.w))
                 with _eval_weights(eng):
-                    render_strings(model, test_strings, output_dir=f"{OUTPUT_DIR}/epoch_{epoch}", sheet_height=SHEET_HEIGHT,
+                    render_strings(model, strings, output_dir=f"{OUTPUT_DIR}/epoch_{epoch}", sheet_height=SHEET_HEIGHT,
                                    sheet_width=SHEET_WIDTH, device=device)
             elif is_best:
                 print(f"Epoch {epoch}, New best validation loss: {avg_val_loss:.6f}")
@@ -806,9 +909,9 @@ def train_string_renderer():
         from . import datagen, devdata
         atlas = devdata.GlyphAtlas.from_font(None if DEVICE_DATA == "default" else DEVICE_DATA, datagen.FONT_SIZE).to(device)
         print(f"Composing {NUM_SAMPLES} samples on {device} from a glyph atlas of {DEVICE_DATA}...")
-        dataset = devdata.reference_dataset(NUM_SAMPLES, atlas, DATA_FIRST_SEED, MAX_CHARS_PER_SHEET, SHEET_HEIGHT, SHEET_WIDTH)
+        dataset = devdata.reference_dataset(NUM_SAMPLES, atlas, DATA_FIRST_SEED, MAX_CHARS_PER_SHEET, SHEET_HEIGHT, SHEET_WIDTH, alphabet=ALPHABET)
         if FRESH_DATA:
-            refresh = _fresh_rows(atlas, NUM_SAMPLES)
+            refresh = _fresh_rows(atlas, NUM_SAMPLES, ALPHABET, STEER)
     else:
         dataset = load_string_dataset(data_dir="train_input", num_samples=NUM_SAMPLES, sheet_height=SHEET_HEIGHT,
                                       sheet_width=SHEET_WIDTH)
@@ -831,7 +934,8 @@ def main(argv=None):
         if argv[1] == "--train":
             model = train_string_renderer()
             save_model(model)
-            render_strings(model, test_strings, output_dir=OUTPUT_DIR, sheet_height=SHEET_HEIGHT, sheet_width=SHEET_WIDTH, device=device)
+            render_strings(model, test_strings + _extra_test_strings(ALPHABET), output_dir=OUTPUT_DIR, sheet_height=SHEET_HEIGHT, sheet_width=SHEET_WIDTH,
+                           device=device)
         else:
             print(f"Unknown option: {argv[1]}")
             print("Available options: --train")
@@ -843,4 +947,5 @@ def main(argv=None):
             print("No saved model found. Training a new model...")
             model = train_string_renderer()
             save_model(model)
-        render_strings(model, test_strings, output_dir=OUTPUT_DIR, sheet_height=SHEET_HEIGHT, sheet_width=SHEET_WIDTH, device=device)
+        render_strings(model, test_strings + _extra_test_strings(ALPHABET), output_dir=OUTPUT_DIR, sheet_height=SHEET_HEIGHT, sheet_width=SHEET_WIDTH,
+                       device=device)

@@ -76,6 +76,101 @@ def lcg_text(seed, min_length=10, max_length=100):
     return "".join(out)
 
 
+# ---------------------------------------------------------------- weighted text (afr_op_dataset_text_w, afr_op_text_weights)
+TEXT_FIRST, TEXT_CODES = 33, 94          # the drawable codes 33..126: every printable ASCII character but the space
+REL_ONE, REL_CAP = 1 << 16, 16 << 16     # a character's error relative to the mean in 16.16 fixed point, and its cap
+_ALPHABETS = {
+    "upper": range(65, 91),
+    "lower": range(97, 123),
+    "letters": (*range(65, 91), *range(97, 123)),
+    "alnum": (*range(48, 58), *range(65, 91), *range(97, 123)),
+    "ascii": range(TEXT_FIRST, TEXT_FIRST + TEXT_CODES),
+}
+
+
+def alphabet_members(spec):
+    """The 94 flags (0 / 1, flag i = code 33 + i) of an alphabet: one of the names upper, lower, letters, alnum, ascii, or -- any other
+    string -- the literal set of its characters.  A literal that is empty or holds a space or a code outside 33..126 is a ValueError."""
+    if not isinstance(spec, str):
+        raise ValueError(f"an alphabet is a name ({', '.join(_ALPHABETS)}) or a string of characters, got {spec!r}")
+    codes = _ALPHABETS.get(spec)
+    if codes is None:
+        codes = [ord(c) for c in spec]
+        bad = sorted({c for c in codes if not TEXT_FIRST <= c < TEXT_FIRST + TEXT_CODES})
+        if bad or not codes:
+            raise ValueError(f"alphabet {spec!r}: " + ("empty" if not codes else
+                             f"codes {bad} lie outside {TEXT_FIRST}..{TEXT_FIRST + TEXT_CODES - 1} (the space separates words and is never drawn as a letter)"))
+    flags = [0] * TEXT_CODES
+    for c in codes:
+        flags[c - TEXT_FIRST] = 1
+    return flags
+
+
+def members_words(members):
+    """The 94 flags as the three 32-bit words afr_op_text_weights takes: bit i of the mask = code 33 + i."""
+    if len(members) != TEXT_CODES:
+        raise ValueError(f"{len(members)} member flags, expected {TEXT_CODES}")
+    mask = sum(1 << i for i, m in enumerate(members) if m)
+    return [(mask >> (32 * k)) & 0xFFFFFFFF for k in range(3)]
+
+
+def text_weights(by_code, members, floor_w, gain):
+    """Twin of afr_op_text_weights in Python integers -> (cum, w), two lists of 94.  by_code: rows [code] = {chars, pixels, sumsq, ...}
+    (afr_op_sheet_char_errors' table; only columns 1 and 2 of the member codes are read) or None; members: the 94 flags."""
+    if len(members) != TEXT_CODES or not any(members):
+        raise ValueError("members: 94 flags, at least one set")
+    if not 1 <= floor_w <= 65535 or not 0 <= gain <= 65535:
+        raise ValueError(f"floor_w {floor_w} must lie in 1..65535, gain {gain} in 0..65535")
+    A = [TEXT_FIRST + i for i in range(TEXT_CODES) if members[i]]
+    P = S = 0
+    if by_code is not None:
+        P, S = sum(int(by_code[c][1]) for c in A), sum(int(by_code[c][2]) for c in A)
+    w = [0] * TEXT_CODES
+    if by_code is None or gain == 0 or S == 0:
+        for c in A:
+            w[c - TEXT_FIRST] = floor_w
+    else:
+        k = max(0, S.bit_length() - 47)
+        m_ref = max(1, ((S >> k) << 16) // max(1, P >> k))
+        for c in A:
+            pixels, sumsq = int(by_code[c][1]) >> k, int(by_code[c][2]) >> k
+            rel = REL_ONE if pixels == 0 else min((((sumsq << 16) // pixels) << 16) // m_ref, REL_CAP)
+            w[c - TEXT_FIRST] = floor_w + ((gain * rel) >> 16)
+    cum, total = [], 0
+    for x in w:
+        total += x
+        cum.append(total)
+    return cum, w
+
+
+def lcg_text_weighted(seed, cum, min_length=10, max_length=100):
+    """Twin of afr_op_dataset_text_w: lcg_text with the letter drawn from the 94 inclusive cumulative weights `cum` -- r = (state *
+    cum[93]) >> 32 after the same LCG update, the letter 33 + (the smallest i with cum[i] > r).  A zero total is a ValueError."""
+    import bisect
+    cum = [int(c) for c in cum]
+    total = cum[-1]
+    if len(cum) != TEXT_CODES or total == 0:
+        raise ValueError("cum: 94 inclusive cumulative weights with a positive total")
+    state = int(seed) % 4294967296
+
+    def draw(k):
+        nonlocal state
+        state = (state * 1664525 + 1013904223) % 4294967296
+        return (state * k) >> 32
+
+    length = draw(max_length - min_length + 1) + min_length
+    out = []
+    remaining = length
+    while remaining > 0:
+        wl = min(draw(10) + 1, remaining)
+        out.append("".join(chr(TEXT_FIRST + bisect.bisect_right(cum, draw(total))) for _ in range(wl)))
+        remaining -= wl
+        if remaining > 0:
+            out.append(" ")
+            remaining -= 1
+    return "".join(out)
+
+
 def dataset_strings(n, first_seed=42):
     """Sample i (0-based) of the reference dataset uses seed i+42 (generate_font.ts:204)."""
     return [lcg_text(first_seed + i) for i in range(n)]

@@ -622,6 +622,41 @@ int afr_op_dataset_text(int64_t first_seed, const int64_t* seed_rows, const int6
 int afr_op_compose_sheets(const afr_glyph_atlas* atlas, const afr_sheet_geometry* geo, const int64_t* codes, int ldx,
                           const int64_t* out_rows, int64_t n, uint8_t* out, uint32_t* err /* or NULL */, void* stream);
 
+/* ---- the text source with any alphabet: dataset_text with the letter drawn from a table of integer weights over the codes 33..126,
+ * and the launch that builds the table on the device from afr_op_sheet_char_errors' by-code counters.  Plain ops, integers only.
+ *   dataset_text_w afr_op_dataset_text in every respect -- seed, row mapping, length draw, word-length draw, spaces, zero fill, len --
+ *                  but the letter: with total = cum[93], after the same LCG update r = (state * total) >> 32 and the letter is
+ *                  33 + (the smallest i with cum[i] > r).  cum: device uint32 [94], the inclusive cumulative weights, non-decreasing.
+ *                  An entry of weight 0 (cum[i] == cum[i - 1]) is never drawn; the space and code 0 are outside the table.  With a
+ *                  weight f on 65..90 alone the letter is 65 + ((state * 26 f) >> 32) / f = 65 + ((state * 26) >> 32): the texts are
+ *                  afr_op_dataset_text's byte for byte, from the same draws.  total == 0 sets bit 0 of *err (device word, or NULL);
+ *                  the rows are then zero-filled and len[r] = 0.  The table is read into LDS once per workgroup.
+ *   text_weights   one workgroup.  members (HOST, three words): bit i of the 94-bit mask = code 33 + i belongs to the alphabet A.
+ *                  by_code: device uint64 [n_codes + 1][5] as afr_op_sheet_char_errors leaves it, or NULL; only pixels (column 1)
+ *                  and sumsq (column 2) of the member codes are read -- never a non-member or the background row.  In integers, with
+ *                  P = sum over A of pixels and S = sum over A of sumsq (each must fit 64 bits):
+ *                    by_code NULL, gain == 0 or S == 0:  w_c = floor_w for every member c;
+ *                    otherwise  k = max(0, bit_length(S) - 47) and P, S and every pixels_c, sumsq_c are shifted right by k (so that
+ *                               each << 16 below stays inside 64 bits for any table),
+ *                               m_ref = max(1, (S << 16) / max(1, P)),
+ *                               rel_c = 1 << 16 for a member with pixels_c == 0 (a character never seen counts as average), else
+ *                               rel_c = min((((sumsq_c << 16) / pixels_c) << 16) / m_ref, 16 << 16)   (at most 16 times the mean),
+ *                               w_c   = floor_w + ((gain * rel_c) >> 16);
+ *                  non-members get w_c = 0.  cum (device uint32 [94]) = the inclusive sums of w, w (device uint32 [94], or NULL) the
+ *                  weights themselves.  A weight is at most 65535 * 17, so the total is below 2^27.  No atomics: the words repeat.
+ * Errors, before anything is launched: dataset_text_w -- everything afr_op_dataset_text refuses, cum NULL, cum or err not 4-byte
+ * aligned; text_weights -- members or cum NULL, by_code given with n_codes < 127, an empty member set, member bits above bit 93,
+ * floor_w outside 1..65535, gain above 65535, by_code not 8-byte or cum, w not 4-byte aligned -> AFR_EINVAL. */
+#define AFR_TEXT_FIRST 33      /* first drawable code */
+#define AFR_TEXT_CODES 94      /* codes 33..126 */
+int afr_op_dataset_text_w(int64_t first_seed, const int64_t* seed_rows, const int64_t* out_rows, int64_t n, int min_len, int max_len,
+                          const uint32_t* cum /* device [94], inclusive cumulative weights */,
+                          int64_t* codes, int ldx, int32_t* len /* or NULL */, uint32_t* err /* or NULL */, void* stream);
+int afr_op_text_weights(const uint64_t* by_code /* device [n_codes + 1][5] as afr_op_sheet_char_errors leaves it, or NULL */,
+                        int n_codes, const uint32_t members[3] /* host: bit i = code 33 + i is in the alphabet */,
+                        uint32_t floor_w /* 1..65535 */, uint32_t gain /* 0..65535 */,
+                        uint32_t* cum /* device [94] */, uint32_t* w /* device [94] or NULL */, void* stream);
+
 /* ---- rendering error attributed to characters: one launch that lays a text out exactly as compose_sheets does and measures a
  * prediction against the sheet compose_sheets would draw, pixel by pixel, charging every pixel to the character that owns it.  A
  * plain op: no plan, nothing allocated, one workgroup per sheet under compose's grid cap; integers only, so the result repeats
