@@ -200,6 +200,8 @@ SIGNATURES = {
     "afr_op_text_weights": (_i32, [_vp, _i32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "afr_op_compose_sheets": (_i32, [C.POINTER(AfrGlyphAtlas), C.POINTER(AfrSheetGeometry), _vp, _i32, _vp, _i64, _vp, _vp, _vp]),
     "afr_op_sheet_char_errors": (_i32, [C.POINTER(AfrGlyphAtlas), C.POINTER(AfrSheetGeometry), _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "afr_op_sheet_read_back": (_i32, [C.POINTER(AfrGlyphAtlas), C.POINTER(AfrSheetGeometry), _vp, _i32, _vp, _i64, _vp, C.POINTER(C.c_uint32),
+                                      _vp, _vp, _vp, _vp, _vp]),
     "afr_op_f32_to_fp8": (_i32, [_vp, _vp, _i64, _f32, _vp]),
     "afr_op_gemm_fp8": (_i32, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
     "afr_pixel_bwd_blocks": (_i32, [C.c_longlong]),

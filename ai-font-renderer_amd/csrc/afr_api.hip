@@ -2566,11 +2566,12 @@ extern "C" int afr_op_text_weights(const uint64_t* by_code, int n_codes, const u
     HIPCHK(afr_launch_text_weights((const unsigned long long*)by_code, members, floor_w, gain, cum, w, (hipStream_t)stream));
     return AFR_OK;
 }
-// What afr_op_compose_sheets and afr_op_sheet_char_errors refuse alike: `dense` is the sheet-shaped buffer (out / pred), `rows` the row
-// vector, lds_bytes the kernel's whole LDS need.  -> AFR_OK or the failure, already recorded.
+// What afr_op_compose_sheets, afr_op_sheet_char_errors and afr_op_sheet_read_back refuse alike: `dense` is the sheet-shaped buffer
+// (out / pred), `rows` the row vector, lds_extra which kernel's LDS need is held against the budget.  -> AFR_OK or the failure, already recorded.
+enum { SHEET_LDS_COMPOSE = 0, SHEET_LDS_CHARERR = 1, SHEET_LDS_READBACK = 2 };
 static int sheet_args_check(const char* who, const char* dense_name, const afr_glyph_atlas* atlas, const afr_sheet_geometry* geo,
                             const int64_t* codes, int ldx, const int64_t* rows, int64_t n, const void* dense, const uint32_t* err,
-                            bool lds_extra) {
+                            int lds_extra) {
     if (!atlas || !geo || !codes || !dense) return fail(AFR_EINVAL, "%s: atlas, geo, codes or %s is null", who, dense_name);
     if (!atlas->cells || !atlas->adv64) return fail(AFR_EINVAL, "%s: the atlas's cells or adv64 is null", who);
     if (n < 1) return fail(AFR_EINVAL, "%s: n = %lld, must be >= 1", who, (long long)n);
@@ -2592,14 +2593,17 @@ static int sheet_args_check(const char* who, const char* dense_name, const afr_g
     if ((long long)atlas->n_codes * atlas->cell_h * atlas->cell_w > AFR_COMPOSE_LDS_BUDGET || geo->width / 8 > AFR_COMPOSE_LDS_BUDGET)
         return fail(AFR_EUNSUPPORTED, "%s: the atlas's cells (%d x %d x %d bytes) or a row of %d pixels alone pass the LDS budget of %d bytes", who,
                     atlas->n_codes, atlas->cell_h, atlas->cell_w, geo->width, AFR_COMPOSE_LDS_BUDGET);
-    const long long lds = lds_extra ? (long long)afr_charerr_dynamic_lds(atlas->n_codes, atlas->cell_h, atlas->cell_w, geo->n_lines, geo->width) +
-                                          (long long)afr_charerr_static_lds()
-                                    : (long long)afr_compose_dynamic_lds(atlas->n_codes, atlas->cell_h, atlas->cell_w, geo->n_lines, geo->width) +
-                                          (long long)afr_compose_static_lds();
+    const int nc = atlas->n_codes, ch = atlas->cell_h, cw = atlas->cell_w;
+    const long long lds = lds_extra == SHEET_LDS_READBACK ? (long long)afr_readback_dynamic_lds(nc, ch, cw, geo->n_lines, geo->width) + (long long)afr_readback_static_lds()
+                          : lds_extra == SHEET_LDS_CHARERR ? (long long)afr_charerr_dynamic_lds(nc, ch, cw, geo->n_lines, geo->width) + (long long)afr_charerr_static_lds()
+                                                           : (long long)afr_compose_dynamic_lds(nc, ch, cw, geo->n_lines, geo->width) + (long long)afr_compose_static_lds();
     if (lds > AFR_COMPOSE_LDS_BUDGET)
         return fail(AFR_EUNSUPPORTED, "%s: the atlas's cells (%d x %d x %d bytes), the glyph ranges and the layout%s need %lld bytes of LDS, the budget is %d",
-                    who, atlas->n_codes, atlas->cell_h, atlas->cell_w, lds_extra ? ", the position records and the code counters" : "", lds,
-                    AFR_COMPOSE_LDS_BUDGET);
+                    who, nc, ch, cw,
+                    lds_extra == SHEET_LDS_READBACK  ? ", the position records, the waves' windows and the confusion counters"
+                    : lds_extra == SHEET_LDS_CHARERR ? ", the position records and the code counters"
+                                                     : "",
+                    lds, AFR_COMPOSE_LDS_BUDGET);
     return AFR_OK;
 }
 static ComposeArgs compose_args(const afr_glyph_atlas* atlas, const afr_sheet_geometry* geo, const int64_t* codes, int ldx, const int64_t* rows,
@@ -2611,7 +2615,7 @@ static ComposeArgs compose_args(const afr_glyph_atlas* atlas, const afr_sheet_ge
 }
 extern "C" int afr_op_compose_sheets(const afr_glyph_atlas* atlas, const afr_sheet_geometry* geo, const int64_t* codes, int ldx,
                                      const int64_t* out_rows, int64_t n, uint8_t* out, uint32_t* err, void* stream) {
-    if (const int rc = sheet_args_check("afr_op_compose_sheets", "out", atlas, geo, codes, ldx, out_rows, n, out, err, false)) return rc;
+    if (const int rc = sheet_args_check("afr_op_compose_sheets", "out", atlas, geo, codes, ldx, out_rows, n, out, err, SHEET_LDS_COMPOSE)) return rc;
     const ComposeArgs a = compose_args(atlas, geo, codes, ldx, out_rows, n, out, err);
     DevGuard dg(device_of(out));
     HIPCHK(afr_launch_compose_sheets(a, (hipStream_t)stream));
@@ -2621,7 +2625,7 @@ extern "C" int afr_op_sheet_char_errors(const afr_glyph_atlas* atlas, const afr_
                                         const int64_t* code_rows, int64_t n, const uint8_t* pred, uint32_t* per_pos, uint64_t* by_code,
                                         uint32_t* err, void* stream) {
     const char* who = "afr_op_sheet_char_errors";
-    if (const int rc = sheet_args_check(who, "pred", atlas, geo, codes, ldx, code_rows, n, pred, err, true)) return rc;
+    if (const int rc = sheet_args_check(who, "pred", atlas, geo, codes, ldx, code_rows, n, pred, err, SHEET_LDS_CHARERR)) return rc;
     // a record's sumsq is a uint32: 255^2 * pixels must fit
     if ((long long)geo->height * geo->width > 66051)
         return fail(AFR_EUNSUPPORTED, "%s: a sheet of %d x %d pixels: 65025 * pixels must fit 32 bits, at most 66051 pixels", who, geo->height,
@@ -2632,6 +2636,31 @@ extern "C" int afr_op_sheet_char_errors(const afr_glyph_atlas* atlas, const afr_
     const CharErrArgs a{compose_args(atlas, geo, codes, ldx, code_rows, n, nullptr, err), pred, per_pos, (unsigned long long*)by_code};
     DevGuard dg(device_of(pred));
     HIPCHK(afr_launch_sheet_char_errors(a, (hipStream_t)stream));
+    return AFR_OK;
+}
+extern "C" int afr_op_sheet_read_back(const afr_glyph_atlas* atlas, const afr_sheet_geometry* geo, const int64_t* codes, int ldx,
+                                      const int64_t* code_rows, int64_t n, const uint8_t* pred, const uint32_t* members, uint8_t* read,
+                                      uint32_t* score, uint64_t* confusion, uint32_t* err, void* stream) {
+    const char* who = "afr_op_sheet_read_back";
+    if (!atlas || !geo) return fail(AFR_EINVAL, "%s: atlas or geo is null", who);
+    // a window's score is a uint32: 255^2 * pixels must fit (asked before the LDS budget, which such a cell passes as well)
+    if ((long long)atlas->cell_h * atlas->cell_w > 66051)
+        return fail(AFR_EUNSUPPORTED, "%s: a cell of %d x %d pixels: 65025 * pixels must fit 32 bits, at most 66051 pixels", who, atlas->cell_h,
+                    atlas->cell_w);
+    if (const int rc = sheet_args_check(who, "pred", atlas, geo, codes, ldx, code_rows, n, pred, err, SHEET_LDS_READBACK)) return rc;
+    if (!members) return fail(AFR_EINVAL, "%s: members is null", who);
+    if (members[2] >> (AFR_TEXT_CODES - 64))
+        return fail(AFR_EINVAL, "%s: member bits above bit %d (code %d) are set", who, AFR_TEXT_CODES - 1, AFR_TEXT_FIRST + AFR_TEXT_CODES - 1);
+    if (atlas->n_codes < AFR_TEXT_FIRST + AFR_TEXT_CODES)
+        return fail(AFR_EINVAL, "%s: n_codes = %d, the atlas must hold the candidates' cells, the codes up to %d", who, atlas->n_codes,
+                    AFR_TEXT_FIRST + AFR_TEXT_CODES - 1);
+    if (atlas->n_codes > 256) return fail(AFR_EUNSUPPORTED, "%s: n_codes = %d, a code read back is stored in a byte: at most 256", who, atlas->n_codes);
+    if (!read && !score && !confusion) return fail(AFR_EINVAL, "%s: read, score and confusion are all NULL", who);
+    if (((uintptr_t)score & 7) || ((uintptr_t)confusion & 7)) return fail(AFR_EINVAL, "%s: score and confusion must be 8-byte aligned", who);
+    const ReadBackArgs a{compose_args(atlas, geo, codes, ldx, code_rows, n, nullptr, err), pred, {members[0], members[1], members[2]}, read, score,
+                         (unsigned long long*)confusion};
+    DevGuard dg(device_of(pred));
+    HIPCHK(afr_launch_sheet_read_back(a, (hipStream_t)stream));
     return AFR_OK;
 }
 extern "C" int afr_op_f32_to_fp8(const float* src, void* dst, int64_t n, float scale, void* stream) {

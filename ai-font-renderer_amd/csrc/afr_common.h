@@ -454,6 +454,16 @@ struct CharErrArgs {
 size_t afr_charerr_static_lds();
 size_t afr_charerr_dynamic_lds(int n_codes, int cell_h, int cell_w, int n_lines, int width);
 hipError_t afr_launch_sheet_char_errors(const CharErrArgs& a, hipStream_t s);
+// afr_op_sheet_read_back: compose's arguments (c.out unused, c.out_rows = the rows of codes the samples read) beside the dense
+// prediction, the candidates' 94-bit mask and the three outputs.  LDS as compose's, plus the position records, one staged window
+// (cell_h * cell_w halfwords) per wave and a 94 x 96 table of 16-bit confusion counters.
+struct ReadBackArgs {
+    ComposeArgs c;
+    const uint8_t* pred; uint32_t members[3]; uint8_t* read; uint32_t* score; unsigned long long* confusion;
+};
+size_t afr_readback_static_lds();
+size_t afr_readback_dynamic_lds(int n_codes, int cell_h, int cell_w, int n_lines, int width);
+hipError_t afr_launch_sheet_read_back(const ReadBackArgs& a, hipStream_t s);
 // the output head and its backward for a caller-side loss: clamp(u, 0, 1), or sigmoid(u) on a LOSS_BCE plan
 hipError_t afr_launch_clamp_bwd(int act_dtype, void* u_inout, const float* dy, long long n, hipStream_t s, int loss_kind = LOSS_MSE);
 hipError_t afr_launch_clamp_out(int act_dtype, const void* u, float* y, long long n, hipStream_t s, int loss_kind = LOSS_MSE);

@@ -456,6 +456,195 @@ __global__ __launch_bounds__(256) void sheet_char_errors_kernel(CharErrArgs ca) 
             if (s_by[e]) atomicAdd(ca.by_code + e, s_by[e]);
 }
 
+// -------------------------------------------------------------------------------------- read back
+// afr_op_sheet_read_back: compose's text, layout and index phases over the same LDS, then one WAVE per scored character (a character
+// on a drawn line, not a space, whose cell box clipped to the sheet -- its window -- is not empty), the characters dealt to the four
+// waves in turn.  Per character:
+//   stage   lane = window pixel: a = 255 - pred and ctx = compose's fold over every OTHER glyph that covers the pixel (the paint
+//           phase's loop over the lines and s_range, the scored glyph skipped) go to the wave's own LDS row as one halfword a | ctx << 8;
+//   score   lane = candidate.  The 96 slots are the codes 32..126 (slot 0, the blank, always; a slot 1 + i if member bit i is set or
+//           the code is the character's own) and slot 95 = the character's own code when it lies outside 32..126; a lane holds slots
+//           lane and lane + 64.  It walks the window once: the halfword is one broadcast read, the two cells' bytes are read at
+//           per-lane addresses; the two sums of (a - hyp)^2 stay in registers.  No reduction per candidate;
+//   pick    one 64-bit min over the wave of score << 32 | rank, rank 0 for the character's own code and code + 1 otherwise: the
+//           smallest score, the true code first among equals, then the smallest code.
+// The winner and the two scores go to records by position in LDS, stored once per row after the sheet's barrier and cleared.  The
+// confusion counts of the true codes 33..126 live in LDS for as long as the workgroup does, as 16-bit counters packed in pairs (a
+// 32-bit table beside Montserrat's cells would pass the LDS budget): a sheet adds at most ldx, so the table is added to global memory
+// -- one 64-bit atomic per non-zero counter -- whenever the next sheet could carry a counter past 65535, and at the end.  A true code
+// outside 33..126 (nothing the text sources draw) adds straight to global memory.
+constexpr int RB_SLOTS = 96, RB_CONF_WORDS = TXT_CODES * RB_SLOTS / 2, RB_CONF_MAX = 65535;
+struct ReadBackLds {
+    int pos[CMP_MAX_LDX + 1], line[CMP_MAX_LDX];
+    uint32_t rd[CMP_MAX_LDX];
+    __align__(8) uint2 sc[CMP_MAX_LDX];                                // {winner's score, score of the true code} by position
+};
+size_t afr_readback_static_lds() { return sizeof(ComposeLds) + sizeof(ReadBackLds); }
+static __host__ __device__ inline size_t readback_stage_lds(int cell_h, int cell_w) { return ((size_t)cell_h * cell_w * 2 + 3) & ~(size_t)3; }
+size_t afr_readback_dynamic_lds(int n_codes, int cell_h, int cell_w, int n_lines, int width) {
+    return (size_t)RB_CONF_WORDS * 4 + 4 * readback_stage_lds(cell_h, cell_w) + afr_compose_dynamic_lds(n_codes, cell_h, cell_w, n_lines, width);
+}
+
+// the workgroup's confusion counters added to global memory and cleared; a thread owns its words, so no barrier in between
+__device__ __forceinline__ void readback_flush(uint32_t* s_conf, unsigned long long* confusion, int n_codes, int t) {
+    for (int w = t; w < RB_CONF_WORDS; w += 256) {
+        const uint32_t v = s_conf[w];
+        if (!v) continue;
+        s_conf[w] = 0u;
+        const int e = 2 * w, r = e / RB_SLOTS, col = e - r * RB_SLOTS;      // RB_SLOTS is even: both halves lie in row r
+        unsigned long long* dst = confusion + (size_t)(TXT_FIRST + r) * n_codes + 32 + col;
+        if (v & 0xFFFFu) atomicAdd(dst, (unsigned long long)(v & 0xFFFFu));
+        if (v >> 16) atomicAdd(dst + 1, (unsigned long long)(v >> 16));
+    }
+}
+
+// bit i of the 94-bit mask (false outside it), without indexing the kernel argument by a register
+__device__ __forceinline__ bool readback_member(const uint32_t m[3], int i) {
+    if (i < 0 || i >= TXT_CODES) return false;
+    return ((i < 32 ? m[0] : i < 64 ? m[1] : m[2]) >> (i & 31)) & 1u;
+}
+
+// LDS written by some lanes of a wave is read by others of the same wave
+__device__ __forceinline__ void readback_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+__global__ __launch_bounds__(256) void sheet_read_back_kernel(ReadBackArgs ra) {
+    extern __shared__ __align__(16) uint8_t s_dyn[];                   // the confusion counters, the waves' windows, compose's cells and ranges
+    __shared__ ComposeLds L;
+    __shared__ ReadBackLds R;
+    const ComposeArgs& a = ra.c;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    uint32_t* s_conf = (uint32_t*)s_dyn;                               // [94][96] uint16, two to a word
+    const size_t stage = readback_stage_lds(a.cell_h, a.cell_w);
+    uint16_t* s_win = (uint16_t*)(s_dyn + (size_t)RB_CONF_WORDS * 4 + (size_t)wave * stage);
+    uint8_t* s_cells = s_dyn + (size_t)RB_CONF_WORDS * 4 + 4 * stage;
+    sheet_cells_to_lds(a, L, s_cells, t);
+    for (int e = t; e < RB_CONF_WORDS; e += 256) s_conf[e] = 0u;
+    R.rd[t] = 0u;
+    R.sc[t] = make_uint2(0u, 0u);
+    const int W8 = a.width >> 3, cell_px = a.cell_h * a.cell_w;
+    short2* s_range = (short2*)(s_cells + compose_cell_lds(a.n_codes, a.cell_h, a.cell_w));      // [n_lines][W8]
+    // this lane's two slots: whether the mask admits them, and their codes (slot 95 and a closed slot read the blank's cell, unused)
+    const int slot1 = lane + 64;
+    const bool open0 = lane == 0 || readback_member(ra.members, lane - 1);
+    const bool open1 = readback_member(ra.members, slot1 - 1);
+    int since = 0;                                                     // an upper bound of the largest counter in s_conf
+    for (long long j = blockIdx.x; j < a.n; j += gridDim.x) {
+        __syncthreads();                                               // LDS is set up; the sheet before this one is stored and cleared
+        if (ra.confusion && since + a.ldx > RB_CONF_MAX) {
+            readback_flush(s_conf, ra.confusion, a.n_codes, t);
+            since = 0;
+        }
+        since += a.ldx;
+        bool placed;
+        const int nl = sheet_layout<true>(a, L, R.pos, s_range, a.out_rows ? a.out_rows[j] : j, t, lane, wave, W8, placed);
+        int my_line = -1;
+        if (placed)
+            for (int i = 0; i < nl; ++i)
+                if (t >= L.ls[i] && t < L.le[i]) my_line = i;
+        R.line[t] = my_line;
+        __syncthreads();
+        // ---- score: wave `wave` takes the characters wave, wave + 4, ... up to the end of the last drawn line
+        const uint8_t* src = ra.pred + (size_t)j * (size_t)a.height * (size_t)a.width;
+        const int n_end = nl ? L.le[nl - 1] : 0;
+        for (int g = wave; g < n_end; g += 4) {
+            const int i = R.line[g], c = L.code[g];
+            if (i < 0 || c == 32) continue;
+            const int top = L.base[i] - a.origin_y, left = L.px[g] - a.origin_x;
+            const int y0 = max(top, 0), y1 = min(top + a.cell_h, a.height), x0 = max(left, 0), x1 = min(left + a.cell_w, a.width);
+            if (y0 >= y1 || x0 >= x1) continue;
+            const int ww = x1 - x0, np = ww * (y1 - y0);
+            // ---- stage
+            for (int p = lane; p < np; p += 64) {
+                const int wy = p / ww, y = y0 + wy, x = x0 + (p - wy * ww);
+                unsigned m = 0u;
+                for (int l = 0; l < nl; ++l) {
+                    const int ry = y - L.base[l] + a.origin_y;
+                    if ((unsigned)ry >= (unsigned)a.cell_h) continue;
+                    const short2 range = s_range[l * W8 + (x >> 3)];
+                    for (int o = range.x; o <= range.y; ++o) {
+                        const int rx = x - L.px[o] + a.origin_x;
+                        if (o == g || (unsigned)rx >= (unsigned)a.cell_w) continue;
+                        const unsigned b = s_cells[(L.code[o] * a.cell_h + ry) * a.cell_w + rx];
+                        m = m + b - (m * b + 127u) / 255u;
+                    }
+                }
+                s_win[p] = (uint16_t)((255u - src[(size_t)y * a.width + x]) | m << 8);
+            }
+            readback_wave_sync();
+            // ---- the lane's two candidates over the window
+            const bool own_far = c < 32 || c > 126;                    // the character's own code has no slot among 32..126: slot 95
+            const int k0 = 32 + lane, k1 = slot1 < RB_SLOTS - 1 ? 32 + slot1 : (own_far ? c : 32);
+            const bool use0 = open0 || k0 == c, use1 = open1 || k1 == c;
+            const uint8_t* cell0 = s_cells + k0 * cell_px + (y0 - top) * a.cell_w + (x0 - left);
+            const uint8_t* cell1 = s_cells + k1 * cell_px + (y0 - top) * a.cell_w + (x0 - left);
+            uint32_t s0 = 0u, s1 = 0u;
+            // eight pixels of a row at a time: their 24 LDS reads are issued together (the loop is bound by LDS latency, not by
+            // arithmetic), a row's last group re-reads the row's last pixel in the lanes' unused places and leaves it out of the sums
+            const uint16_t* win = s_win;
+            for (int wy = 0; wy < y1 - y0; ++wy, cell0 += a.cell_w, cell1 += a.cell_w, win += ww) {
+                for (int wx = 0; wx < ww; wx += 8) {
+                    unsigned v[8], b0[8], b1[8];
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        const int x = min(wx + k, ww - 1);
+                        v[k] = win[x]; b0[k] = cell0[x]; b1[k] = cell1[x];
+                    }
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        if (wx + k >= ww) break;
+                        const unsigned av = v[k] & 255u, m = v[k] >> 8;
+                        const int d0 = (int)av - (int)(m + b0[k] - (m * b0[k] + 127u) / 255u);
+                        const int d1 = (int)av - (int)(m + b1[k] - (m * b1[k] + 127u) / 255u);
+                        s0 += (uint32_t)(d0 * d0);
+                        s1 += (uint32_t)(d1 * d1);
+                    }
+                }
+            }
+            // ---- pick
+            const unsigned long long none = ~0ull;
+            const unsigned long long key0 = use0 ? (unsigned long long)s0 << 32 | (uint32_t)(k0 == c ? 0 : k0 + 1) : none;
+            const unsigned long long key1 = use1 ? (unsigned long long)s1 << 32 | (uint32_t)(k1 == c ? 0 : k1 + 1) : none;
+            unsigned long long best = key0 < key1 ? key0 : key1;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const unsigned long long other = __shfl_xor(best, off);
+                best = other < best ? other : best;
+            }
+            const int pos = R.pos[g];
+            if (k0 == c) R.sc[pos].y = s0;
+            if (k1 == c && use1) R.sc[pos].y = s1;
+            if (lane == 0) {
+                const int rank = (int)(uint32_t)best, rd = rank ? rank - 1 : c;
+                R.rd[pos] = (uint32_t)rd;
+                R.sc[pos].x = (uint32_t)(best >> 32);
+                if (ra.confusion) {
+                    if (c >= TXT_FIRST && c < TXT_FIRST + TXT_CODES) {  // then rd is one of 32..126
+                        const int e = (c - TXT_FIRST) * RB_SLOTS + rd - 32;
+                        atomicAdd(&s_conf[e >> 1], 1u << (16 * (e & 1)));
+                    } else {
+                        atomicAdd(ra.confusion + (size_t)c * a.n_codes + rd, 1ull);
+                    }
+                }
+            }
+            readback_wave_sync();                                      // the window is read before the next character's is staged
+        }
+        __syncthreads();
+        // ---- every element of row j stored once, and the records cleared for the next sheet
+        if (t < a.ldx) {
+            if (ra.read) ra.read[(size_t)j * a.ldx + t] = (uint8_t)R.rd[t];
+            if (ra.score) ((uint2*)ra.score)[(size_t)j * a.ldx + t] = R.sc[t];
+            R.rd[t] = 0u;
+            R.sc[t] = make_uint2(0u, 0u);
+        }
+    }
+    __syncthreads();
+    if (ra.confusion) readback_flush(s_conf, ra.confusion, a.n_codes, t);
+}
+
 int afr_compose_blocks(long long n) { return (int)(n < AFR_COMPOSE_MAX_BLOCKS ? n : AFR_COMPOSE_MAX_BLOCKS); }
 
 hipError_t afr_launch_compose_sheets(const ComposeArgs& a, hipStream_t s) {
@@ -468,5 +657,12 @@ hipError_t afr_launch_sheet_char_errors(const CharErrArgs& ca, hipStream_t s) {
     const ComposeArgs& a = ca.c;
     const size_t lds = afr_charerr_dynamic_lds(a.n_codes, a.cell_h, a.cell_w, a.n_lines, a.width);
     hipLaunchKernelGGL(sheet_char_errors_kernel, dim3(afr_compose_blocks(a.n)), dim3(256), lds, s, ca);
+    return hipGetLastError();
+}
+
+hipError_t afr_launch_sheet_read_back(const ReadBackArgs& ra, hipStream_t s) {
+    const ComposeArgs& a = ra.c;
+    const size_t lds = afr_readback_dynamic_lds(a.n_codes, a.cell_h, a.cell_w, a.n_lines, a.width);
+    hipLaunchKernelGGL(sheet_read_back_kernel, dim3(afr_compose_blocks(a.n)), dim3(256), lds, s, ra);
     return hipGetLastError();
 }

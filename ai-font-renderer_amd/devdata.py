@@ -287,6 +287,69 @@ def char_errors(atlas, codes, pred, height=80, width=240, rows=None, by_code=Non
     return CharErrors(per_pos.to(torch.int64) & 0xFFFFFFFF, by_code)
 
 
+class ReadBack(collections.namedtuple("ReadBack", "read score confusion codes")):
+    """afr_op_sheet_read_back's three outputs: read uint8 [n, L] (the code read at each position of its row of codes, 0 where no
+    character was scored), score int64 [n, L, 2] = {the winner's score, the true code's}, confusion int64 [n_codes, n_codes]
+    (confusion[c, r] = characters of code c read as r; the counters are below 2^63) -- and codes, the int64 [n, L] rows that were read."""
+
+    def texts(self):
+        """what was read, one string per sheet: the character read at every scored position, the row's own space where the row holds
+        one, nothing at any other position (behind the text, skipped codes, characters on no drawn line)"""
+        out = []
+        for rr, cr in zip(self.read.cpu().tolist(), self.codes.cpu().tolist()):
+            end = cr.index(0) if 0 in cr else len(cr)
+            out.append("".join(chr(r) if r else " " if c == 32 else "" for r, c in zip(rr[:end], cr[:end])))
+        return out
+
+    def rate(self):
+        """(scored characters, how many were read right, how many were read blank), from the confusion table"""
+        return confusion_rate(self.confusion)
+
+
+def confusion_rate(confusion):
+    """(scored characters, read right, read blank) of a confusion table; one transfer"""
+    scored, right, blank = torch.stack([confusion.sum(), confusion.diagonal().sum(), confusion[:, 32].sum()]).cpu().tolist()
+    return scored, right, blank
+
+
+def read_back(atlas, codes, pred, alphabet="upper", height=80, width=240, rows=None, confusion=None, line_height=14.4):
+    """afr_op_sheet_read_back: which glyph of the atlas each drawn character of the uint8 [n, height, width] prediction `pred`
+    (AttentionFontRenderer.render_u8, evaluate's q) looks like.  For every character on a drawn line but the space, every candidate --
+    the codes of `alphabet` (a name or literal string, synth.alphabet_members, or the 94 flags), the blank and the true code -- is put at
+    the character's pen over the neighbours compose_sheets draws there, and the candidate with the least squared distance to the
+    prediction over the character's cell box is what was read: the true code among equals, then the smallest.  Sample j reads row
+    rows[j] (default j) of the int64 [N, L] codes.  confusion (int64 [n_codes, n_codes], default new and zero) is added to.  A code
+    outside the atlas is an IndexError, as in compose_sheets.  -> ReadBack."""
+    from . import synth
+    device = atlas.device
+    codes = codes.to(device=device, dtype=torch.int64).contiguous()
+    if codes.dim() != 2:
+        raise ValueError("codes must be int64 [N, L]")
+    members = synth.alphabet_members(alphabet) if isinstance(alphabet, str) else [int(bool(m)) for m in alphabet]
+    words = (C.c_uint32 * 3)(*synth.members_words(members))
+    rows = _rows(rows, None, device, "rows")
+    n, L = codes.shape[0] if rows is None else rows.numel(), codes.shape[1]
+    if rows is not None and n and (int(rows.min()) < 0 or int(rows.max()) >= codes.shape[0]):
+        raise IndexError("rows outside codes")
+    if pred.dtype != torch.uint8 or pred.device != device or not pred.is_contiguous() or pred.numel() != n * height * width:
+        raise ValueError(f"pred must be a contiguous uint8 [{n}, {height}, {width}] tensor on {device}")
+    if confusion is None:
+        confusion = torch.zeros((atlas.n_codes, atlas.n_codes), dtype=torch.int64, device=device)
+    if (confusion.dtype != torch.int64 or confusion.device != device or not confusion.is_contiguous()
+            or tuple(confusion.shape) != (atlas.n_codes, atlas.n_codes)):
+        raise ValueError(f"confusion must be a contiguous int64 [{atlas.n_codes}, {atlas.n_codes}] tensor on {device}")
+    read = torch.empty((n, L), dtype=torch.uint8, device=device)
+    score = torch.empty((n, L, 2), dtype=torch.int32, device=device)
+    a, g = atlas._struct(), sheet_geometry(height, width, line_height, atlas)
+    with torch.cuda.device(device):
+        err = torch.zeros(1, dtype=torch.int32, device=device)
+        _lib.check(_lib.lib().afr_op_sheet_read_back(C.byref(a), C.byref(g), _ptr(codes), L, _ptr(rows), n, _ptr(pred), words, _ptr(read),
+                                                      _ptr(score), _ptr(confusion), _ptr(err), _stream(device)))
+        if int(err) & 1:
+            raise IndexError(f"a code outside the atlas's 0..{atlas.n_codes - 1}")
+    return ReadBack(read, score.to(torch.int64) & 0xFFFFFFFF, confusion, codes if rows is None else codes[rows])
+
+
 def reference_dataset(n, atlas, first_seed=42, max_length=100, height=80, width=240, alphabet=None):
     """TensorDataset(int64 [n, L] codes, uint8 [n, height, width] sheets) on the atlas's device: the tensors
     helpers.load_string_dataset_u8 returns for the folder datagen.generate(out_dir, n, font, first_seed) writes -- L is the longest

@@ -64,7 +64,13 @@ What is deliberately different from the reference, and why:
     rewrite before the next epoch draws its letters with weight floor_w + gain * min(the character's mean squared error / the
     alphabet's, 16), floor_w = round((1 - share) * 4096), gain = round(share * 4096) -- built on the device from the table where it
     lies (afr_op_text_weights).  The validation rows are never rewritten, so validation losses stay comparable.  On the epochs that
-    print a status line one more line names the five heaviest codes of the last rewrite.  Unset or 0: the run without it.
+    print a status line one more line names the five heaviest codes of the last rewrite.  Unset or 0: the run without it;
+  * AFR_READ_REPORT=<k> (k >= 1, needs AFR_DEVICE_DATA; the candidates are AFR_ALPHABET's codes, A-Z without one) reads the validation
+    sheets back on the device (devdata.read_back after Engine.evaluate_last's bitmaps): for every drawn character, which glyph of the
+    atlas at this pen explains the predicted pixels best.  On the epochs that print a status line, one line headed "Read report:" with
+    the share of characters read right, the share read blank and the k most frequent confusions as Q->O 312; epoch_<e>/confusion.tsv
+    with every non-zero counter; and epoch_<e>/read_back.txt, each rendered test string beside what was read from it.  Nothing steps:
+    every other line and artefact is what it is without the variable.  Unset: nothing changes.
 """
 import contextlib
 import datetime
@@ -181,6 +187,26 @@ def _char_report_from_env():
 
 
 CHAR_REPORT = _char_report_from_env()     # likewise read at import
+
+
+def _read_report_from_env():
+    """AFR_READ_REPORT = "<k>", k >= 1: the read-back report with the k most frequent confusions; unset or empty -> None (off).  Anything
+    else, or the report without AFR_DEVICE_DATA (no atlas, no candidates), is a ValueError."""
+    spec = os.environ.get("AFR_READ_REPORT", "").strip()
+    if not spec:
+        return None
+    try:
+        k = int(spec)
+    except ValueError:
+        k = 0
+    if k < 1:
+        raise ValueError(f"AFR_READ_REPORT must be an integer >= 1 (the number of confusions to list), got {spec!r}")
+    if not os.environ.get("AFR_DEVICE_DATA", "").strip():
+        raise ValueError("AFR_READ_REPORT needs AFR_DEVICE_DATA: the glyph atlas the sheets are composed from holds the candidates' cells")
+    return k
+
+
+READ_REPORT = _read_report_from_env()     # likewise read at import
 
 
 def _alphabet_from_env():
@@ -358,6 +384,62 @@ class _CharReport:
                     f.write("\t".join(["background", ""] + [str(v) for v in row]) + "\n")
                 elif row[1] > 0:
                     f.write("\t".join([str(c), chr(c) if 32 < c < 127 else ""] + [str(v) for v in row]) + "\n")
+
+
+class _ReadReport:
+    """What AFR_READ_REPORT keeps on the device during one validation pass: afr_op_sheet_read_back's confusion table, which every
+    validation batch's launch adds to (the batch's rows of the bound codes, the evaluation's bitmaps)."""
+
+    def __init__(self, k, atlas, codes, alphabet):
+        self.k, self.atlas, self.codes, self.alphabet = int(k), atlas, codes, alphabet or "upper"
+        self.table = torch.zeros((atlas.n_codes, atlas.n_codes), dtype=torch.int64, device=atlas.device)
+
+    def add(self, res, rows):
+        from . import devdata
+        if rows.numel():
+            devdata.read_back(self.atlas, self.codes, res.u8.contiguous(), self.alphabet, res.u8.shape[1], res.u8.shape[2], rows=rows,
+                              confusion=self.table)
+
+    def all_reduce(self, dist):
+        dist.all_reduce(self.table, op=dist.ReduceOp.SUM)
+
+    @staticmethod
+    def _name(c):
+        return chr(c) if 32 < c < 127 else "blank" if c == 32 else f"#{c}"
+
+    def _confusions(self):
+        """the non-zero counters off the diagonal as (count, true code, code read), the most frequent first, then by code"""
+        t = self.table.cpu()
+        at = torch.nonzero(t).tolist()
+        return sorted(((int(t[c, r]), c, r) for c, r in at if c != r), key=lambda e: (-e[0], e[1], e[2])), t
+
+    def line(self):
+        pairs, t = self._confusions()
+        scored, right, blank = int(t.sum()), int(t.diagonal().sum()), int(t[:, 32].sum())
+        n = max(1, scored)
+        worst = ", ".join(f"{self._name(c)}->{self._name(r)} {v}" for v, c, r in pairs[:self.k]) or "none"
+        return f"Read report: {scored} characters, read right {right / n:.6f}, read blank {blank / n:.6f}, confusions: {worst}"
+
+    def write_tsv(self, path):
+        pairs, t = self._confusions()
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            f.write("code\tchar\tread\tread_char\tcount\n")
+            for c, r in torch.nonzero(t).tolist():
+                f.write("\t".join([str(c), chr(c) if 32 < c < 127 else "", str(r), chr(r) if 32 < r < 127 else "", str(int(t[c, r]))]) + "\n")
+
+    def write_strings(self, model, strings, path):
+        """path: every test string, rendered by the model as render_strings renders it, beside what is read from the bitmap"""
+        codes = torch.from_numpy(helpers.encode_for_model(strings, model.max_length, warn=False)).to(self.atlas.device)
+        was_training = model.training
+        model.eval()
+        read = model.read_back(self.atlas, codes, self.alphabet).texts()
+        if was_training:
+            model.train()
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            for s, r in zip(strings, read):
+                f.write(f"{s[:model.max_length]}\n{r}\n\n")
 
 
 def _eval_weights(eng):
@@ -571,6 +653,13 @@ class AttentionFontRenderer(nn.Module):
         q = self.render_u8(codes)
         return devdata.char_errors(atlas, codes, q, q.shape[1], q.shape[2])
 
+    def read_back(self, atlas, codes, alphabet="upper"):
+        """devdata.read_back of render_u8(codes): for every character the atlas draws for the same codes, which candidate glyph of
+        `alphabet` (or the blank, or the character itself) explains the rendered pixels best.  Returns a devdata.ReadBack."""
+        from . import devdata
+        q = self.render_u8(codes)
+        return devdata.read_back(atlas, codes, q, alphabet, q.shape[1], q.shape[2])
+
     def forward(self, x):
         if x.dim() != 2:
             raise ValueError(f"expected [batch, seq_len] codes, got shape {tuple(x.shape)}")
@@ -665,7 +754,8 @@ def _batch_calls(eng, stepper, inputs, targets, rows):
                            evaluate=partial(eng.evaluate, x), forward_loss=partial(eng.forward_loss, x, t))
 
 
-def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True, report=None, treport=None, creport=None):
+def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True, report=None, treport=None, creport=None,
+               rreport=None):
     """One epoch of the reference loop (model.py:288-333): the training pass over order.train_epoch(), then the validation
     pass; returns the two means of per-batch mean losses.  An engine that keeps a weight EMA validates from it.  by_rows: the engine has the data set bound (Engine.bind_dataset)
     and every step is driven by this rank's slice of the epoch's index vector -- the kernels read the rows where they lie.
@@ -674,7 +764,8 @@ def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, wor
     forward and its loss; None: the pass as it always was.  treport: a _TensorReport (AFR_TENSOR_REPORT, rank 0 only): the weights are
     snapshotted before the last training batch and compared after it, and once the validation loss has been read the first training
     batch is run once more as a probe for its gradients.  creport: a _CharReport (AFR_CHAR_REPORT, AFR_STEER): every validation batch's bitmaps --
-    of the one evaluation it shares with report -- are measured against the sheets the atlas composes for the batch's rows."""
+    of the one evaluation it shares with report -- are measured against the sheets the atlas composes for the batch's rows.  rreport: a
+    _ReadReport (AFR_READ_REPORT): the same bitmaps are read back against the atlas's glyphs."""
     from .parallel import shard_rows
     eng = model.engine
     pixels = targets[0].numel()
@@ -706,15 +797,19 @@ def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, wor
             mine = rows[shard_rows(rows.numel(), rank, world)]
             calls = _batch_calls(eng, None, *dense, mine)
             calls.forward(training=False, want_output=False)
-            if report is not None or creport is not None:
-                res = calls.evaluate_last(want_u8=creport is not None)
+            if report is not None or creport is not None or rreport is not None:
+                res = calls.evaluate_last(want_u8=creport is not None or rreport is not None)
                 if report is not None:
                     report.add(res, mine)
                 if creport is not None:
                     creport.add(res, mine)
+                if rreport is not None:
+                    rreport.add(res, mine)
             calls.loss_grad(mean_elems=rows.numel() * pixels)
         if creport is not None and world > 1:
             creport.all_reduce(_dist()[0])
+        if rreport is not None and world > 1:
+            rreport.all_reduce(_dist()[0])
         if report is not None:
             if world > 1:
                 report.all_reduce(_dist()[0])
@@ -798,8 +893,12 @@ def train_attention_model(model, dataset, batch_size, refresh=None, atlas=None):
                 f.write(f"alphabet = {ALPHABET}\n")
             if STEER:                           # likewise
                 f.write(f"steer = {STEER:g}\n")
+            if READ_REPORT:                     # likewise
+                f.write(f"read_report = {READ_REPORT}\n")
     if CHAR_REPORT and atlas is None:
         raise ValueError("the character report needs the glyph atlas the data set was composed from (AFR_DEVICE_DATA)")
+    if READ_REPORT and atlas is None:
+        raise ValueError("the read-back report needs the glyph atlas the data set was composed from (AFR_DEVICE_DATA)")
     if STEER and (atlas is None or refresh is None):
         raise ValueError("steering needs the glyph atlas and the fresh-data rewrite (AFR_DEVICE_DATA, AFR_FRESH_DATA)")
     strings = test_strings + _extra_test_strings(ALPHABET)
@@ -836,10 +935,11 @@ def train_attention_model(model, dataset, batch_size, refresh=None, atlas=None):
         treport = _TensorReport(model) if TENSOR_REPORT and rank == 0 and epoch % 5 == 0 else None
         char_lines = bool(CHAR_REPORT) and epoch % 5 == 0
         creport = _CharReport(CHAR_REPORT or 1, atlas, inputs) if char_lines or STEER else None      # steering keeps the table every epoch
+        rreport = _ReadReport(READ_REPORT, atlas, inputs, ALPHABET) if READ_REPORT and epoch % 5 == 0 else None
         if refresh is not None and epoch >= 1:
             refresh(epoch, order.train_idx, inputs, targets, **(dict(by_code=steer_table) if STEER else {}))
         avg_train_loss, avg_val_loss = _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True, report=report,
-                                                  treport=treport, creport=creport)
+                                                  treport=treport, creport=creport, rreport=rreport)
 
         if STEER:
             steer_table = creport.table
@@ -872,6 +972,11 @@ def train_attention_model(model, dataset, batch_size, refresh=None, atlas=None):
                     creport.write_tsv(f"{OUTPUT_DIR}/epoch_{epoch}/char_errors.tsv")
                 if STEER and refresh.w is not None:
                     print(_steer_line(STEER, refresh.w))
+                if rreport is not None:
+                    print(rreport.line())
+                    rreport.write_tsv(f"{OUTPUT_DIR}/epoch_{epoch}/confusion.tsv")
+                    with _eval_weights(eng):
+                        rreport.write_strings(model, strings, f"{OUTPUT_DIR}/epoch_{epoch}/read_back.txt")
                 with _eval_weights(eng):
                     render_strings(model, strings, output_dir=f"{OUTPUT_DIR}/epoch_{epoch}", sheet_height=SHEET_HEIGHT,
                                    sheet_width=SHEET_WIDTH, device=device)

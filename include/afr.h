@@ -683,6 +683,38 @@ int afr_op_sheet_char_errors(const afr_glyph_atlas* atlas, const afr_sheet_geome
                              const int64_t* code_rows /* or NULL */, int64_t n, const uint8_t* pred, uint32_t* per_pos /* or NULL */,
                              uint64_t* by_code /* or NULL */, uint32_t* err /* or NULL */, void* stream);
 
+/* ---- rendered sheets read back: one launch that lays a text out exactly as compose_sheets does and asks, for every drawn
+ * character, which glyph of the atlas -- placed at this character's pen among its neighbours -- explains the predicted pixels
+ * best.  A plain op: no plan, nothing allocated, one workgroup per sheet under compose's grid cap; integers only and no order
+ * dependence, so all three outputs repeat bit for bit.
+ *   Sample j of n reads row r = code_rows ? code_rows[j] : j of codes int64 [rows][ldx] (text to the first 0, codes outside the
+ *   atlas flagged in bit 0 of *err and skipped, wrap, pens and n_lines as compose_sheets) and the dense prediction
+ *   pred uint8 [n][height][width].  A character is SCORED if it stands on a drawn line, its code c is not 32, and its window --
+ *   its cell box [baseline[i] - origin_y, + cell_h) x [px - origin_x, + cell_w) clipped to the sheet -- is not empty.  For every
+ *   window pixel (y, x): a = 255 - pred[j][y][x]; ctx = compose_sheets' fold m = m + b - (m * b + 127) / 255 from 0 over every
+ *   OTHER glyph whose cell covers the pixel, in (line, character) order, the scored glyph left out; for a candidate code k,
+ *   hyp_k = ctx + b_k - (ctx * b_k + 127) / 255 with b_k = cells[k] at the pixel's place in the cell -- the candidate goes on
+ *   last, at the true character's pen; candidates do not move with their own advance or kerning.  score_k = the sum of
+ *   (a - hyp_k)^2 over the window.  The candidates are the member codes (members, HOST, three words: bit i = code 33 + i), 32
+ *   (the blank: nothing was drawn here) and c itself, member or not.  The smallest score wins; among equal scores c wins if it
+ *   is one of them, otherwise the smallest code (so the blank comes first).
+ *   read      uint8  [n][ldx]    (or NULL): the winning code, indexed by the character's position in its row of codes (not in the
+ *                  packed text).
+ *   score     uint32 [n][ldx][2] (or NULL): {the winner's score, score_c}.
+ *                  Every element of row j of both is stored once; positions that are not scored hold 0.
+ *   confusion uint64 [n_codes][n_codes] (or NULL): confusion[c][read] += 1 per scored character: ADDED to, the caller zeroes it.
+ *                  A workgroup counts its sheets in LDS and issues one global integer atomic per non-zero counter.
+ * Errors, before anything is launched: everything compose_sheets refuses, as afr_op_sheet_char_errors does (pred in the place of
+ * out; the sheet itself may be of any size compose_sheets takes: no sum here runs over more than a window), members NULL, member bits above bit 93, an atlas of fewer than 127 codes (the candidates' cells), all three outputs NULL,
+ * score or confusion not 8-byte aligned -> AFR_EINVAL; compose_sheets' limits, a cell of more than 66051 pixels (65025 * pixels
+ * must fit 32 bits), more than 256 codes (read is a byte), the LDS budget with the records, the waves' windows and the confusion
+ * counters counted -> AFR_EUNSUPPORTED. */
+int afr_op_sheet_read_back(const afr_glyph_atlas* atlas, const afr_sheet_geometry* geo, const int64_t* codes, int ldx,
+                           const int64_t* code_rows /* or NULL */, int64_t n, const uint8_t* pred,
+                           const uint32_t members[3] /* host: bit i = code 33 + i is a candidate */,
+                           uint8_t* read /* [n][ldx] or NULL */, uint32_t* score /* [n][ldx][2] or NULL */,
+                           uint64_t* confusion /* [n_codes][n_codes] or NULL, ADDED to */, uint32_t* err /* or NULL */, void* stream);
+
 /* ---- the token-wise kernels of the per-pixel-token transformer (AFR_KIND_PIXEL), one launch each, exactly as the plan issues
  * them.  One wave per token row: rows >= 1, d = 64 * heads <= 512 (the widths a plan can reach; AFR_EUNSUPPORTED otherwise),
  * C = context tokens per glyph, 1 or 2; act_dtype AFR_F32 or AFR_BF16 is the type T of the GEMM operands (ctx, add, n, q, kv, o,
