@@ -180,6 +180,12 @@ SIGNATURES = {
     "afr_op_linear_chain_block": (_i32, [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
     "afr_op_linear_chain": (_i32, [_vp, _vp, _vp, _vp, _vp, C.POINTER(AfrLinearTail), _vp, _vp, _vp, _vp, C.POINTER(AfrLinearTail),
                                    _i32, _i32, _i32, _i32, _vp, _sz, C.c_char_p, _i32, _vp]),
+    "afr_op_linear_chain_l1_plan": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_sz)]),
+    "afr_op_linear_chain_l1_block": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32),
+                                            C.POINTER(_i32)]),
+    "afr_op_linear_chain_l1": (_i32, [_vp, _vp, _vp, _vp, _vp, C.POINTER(AfrLinearTail), _vp, _vp, _vp, _vp, C.POINTER(AfrLinearTail),
+                                      _i32, _i32, _i32, _i32, _vp, _sz, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp,
+                                      _vp, _i32, _i32, _f32, _vp, C.c_char_p, _i32, _vp]),
     "afr_op_reduce": (_i32, [_vp, _vp, _i32, _i64, _i64, _f32, _i32, _vp]),
     "afr_op_reduce_group": (_i32, [_i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64), _vp]),
     "afr_op_reduce_group_step": (_i32, [_i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64),

@@ -109,7 +109,9 @@ struct afr_plan {
     // bf16 glyph nets: the chained gradient launch (gemm.hip GemmGroup::chain) hands the output layer's input gradient to the hidden
     // layer's products inside ONE launch: a monotonic arrival counter per 256 rows of the batch (o_hand, 0 = none), the arrivals
     // enqueued so far, and the CUs of the bound device (a chain wants a CU per workgroup)
-    size_t o_hand = 0; unsigned hand_arrived = 0; int n_cus = 0;
+    // Behind those counters a second set of the same size: dX_lo's output handed to the first-layer role of the same launch
+    // (GemmGroup::l1; l1_cnt_of), with its own arrivals enqueued so far
+    size_t o_hand = 0; unsigned hand_arrived = 0; int n_cus = 0; unsigned l1_arrived = 0;
     // pixel-token transformer (AFR_KIND_PIXEL): per-block parameter offsets and the forward's workspace
     struct PixBlock { int64_t ln1g, ln1b, win, bin, wo, bo, ln2g, ln2b, w1, b1, w2, b2; };
     std::vector<PixBlock> pix;
@@ -456,7 +458,7 @@ extern "C" int afr_plan_create(const afr_config* c, afr_plan** out) {
         if (p->tstats_ok) p->o_tstats = carve((size_t)chunks * sizeof(afr_tensor_stat));
     }
     if (c->kind == AFR_KIND_GLYPH && c->dtype == AFR_BF16 && p->layers.size() >= 3)      // (behind everything else as well)
-        p->o_hand = carve(((size_t)c->max_batch + 255) / 256 * sizeof(unsigned));
+        p->o_hand = carve(2 * (((size_t)c->max_batch + 255) / 256) * sizeof(unsigned));
     p->ws_need = off;
     *out = p;
     return AFR_OK;
@@ -506,10 +508,10 @@ extern "C" int afr_bind(afr_plan* p, float* params, float* grads, float* m, floa
         l.coop_arrived = 0;
         if (l.n_cnt) { DevGuard dg(dev); HIPCHK(hipMemset(p->ws + l.o_cnt, 0, (size_t)l.n_cnt * sizeof(unsigned))); }
     }
-    p->hand_arrived = 0; p->n_cus = 0;
+    p->hand_arrived = 0; p->n_cus = 0; p->l1_arrived = 0;
     if (p->o_hand) {                                     // the chain's hand-off counters likewise; the device's CUs decide whether it chains
         DevGuard dg(dev);
-        HIPCHK(hipMemset(p->ws + p->o_hand, 0, ((size_t)p->cfg.max_batch + 255) / 256 * sizeof(unsigned)));
+        HIPCHK(hipMemset(p->ws + p->o_hand, 0, 2 * (((size_t)p->cfg.max_batch + 255) / 256) * sizeof(unsigned)));
         int d = 0;
         if (hipGetDevice(&d) == hipSuccess) (void)hipDeviceGetAttribute(&p->n_cus, hipDeviceAttributeMultiprocessorCount, d);
     }
@@ -798,7 +800,11 @@ struct GemmBatch {
     unsigned* arrived[2] = {nullptr, nullptr};
     // chain: the batch collects TWO layers' pairs (dW_up, dX_up, dW_lo, dX_lo) for one chained launch (afr_launch_gemm_chain)
     bool chain = false;
+    // a chain's fifth role (gemm.hip GemmGroup::l1): the folded first layer's fused backward rides the launch; the stage below finds
+    // l1_on set and only books the slabs.  l1_loss: the step's deferred loss partials, copied (the descriptor points at it)
+    bool l1_on = false; ChainL1 l1; LossSum l1_loss; double l1_fl = 0.0, l1_by = 0.0;
 };
+static unsigned* l1_cnt_of(const afr_plan* p) { return (unsigned*)(p->ws + p->o_hand) + ((size_t)p->cfg.max_batch + 255) / 256; }
 // launches the product, or -- handed a batch, and the product can join a grouped launch -- collects it there
 static int run_gemm(afr_plan* p, hipStream_t s, const GemmParams& g, GemmBatch* batch = nullptr) {
     const int gdt = p->gemm_dtype, M = g.M, N = g.N, K = g.K;
@@ -842,11 +848,15 @@ static int flush_members(afr_plan* p, hipStream_t s, const GemmBatch& b, int i0,
         len += snprintf(tag + len, sizeof tag - len, "%s%.*s%s", i > i0 ? "+" : "", (int)strcspn(shape, "]"), shape, i == i0 + n - 1 ? "]" : "");
     }
     for (int i = i0; i < i0 + n; ++i) { flops += b.fl[i]; bytes += b.by[i]; }
+    const bool l1 = chained && b.l1_on;               // (the row keeps its members' shapes; it gains the first-layer backward's work)
+    if (l1) { flops += b.l1_fl; bytes += b.l1_by; }
     hipError_t e;
     const unsigned hand = chained ? p->hand_arrived + afr_gemm_chain_arrivals(b.g) : 0u;
+    ChainL1 cl = b.l1;
+    if (l1) { cl.cnt = l1_cnt_of(p); cl.target = p->l1_arrived + afr_gemm_chain_l1_arrivals(b.g); if (b.l1_loss.partial) cl.loss = &b.l1_loss; }
     {
         ProfScope ps(p, s, tag, flops, bytes);
-        if (chained) e = afr_launch_gemm_chain(p->gemm_dtype, b.g, (unsigned*)(p->ws + p->o_hand), hand, (uint32_t*)(p->ws + p->o_err), s);
+        if (chained) e = afr_launch_gemm_chain(p->gemm_dtype, b.g, (unsigned*)(p->ws + p->o_hand), hand, (uint32_t*)(p->ws + p->o_err), s, l1 ? &cl : nullptr);
         else e = afr_launch_gemm_group(p->gemm_dtype, b.g + i0, n, b.tile256, s);
     }
     if (e != hipSuccess) return fail(AFR_EHIP, "grouped GEMM launch: %s", hipGetErrorString(e));
@@ -855,12 +865,18 @@ static int flush_members(afr_plan* p, hipStream_t s, const GemmBatch& b, int i0,
     for (int i = i0; i < i0 + n; i += 2)
         if (b.arrived[i / 2] && b.g[i].coop_ws) *b.arrived[i / 2] = b.g[i].coop_target;
     if (chained) p->hand_arrived = hand;
+    if (l1) p->l1_arrived = cl.target;
     return AFR_OK;
 }
-static int flush_gemms(afr_plan* p, hipStream_t s, const GemmBatch& b) {
-    if (!b.chain) return flush_members(p, s, b, 0, b.n, false);
+static int flush_gemms(afr_plan* p, hipStream_t s, GemmBatch& b) {
+    if (!b.chain) { b.l1_on = false; return flush_members(p, s, b, 0, b.n, false); }
     // two layers' pairs: ONE chained launch when the launcher takes these descriptors on this device, else the two grouped launches
-    if (b.n == 4 && p->o_hand && afr_gemm_chain_ok(p->gemm_dtype, b.g)) return flush_members(p, s, b, 0, 4, true);
+    // (the first-layer role rides only the chained launch, and only when the launcher takes it: else its own launch follows)
+    if (b.n == 4 && p->o_hand && afr_gemm_chain_ok(p->gemm_dtype, b.g)) {
+        if (b.l1_on) { ChainL1 t = b.l1; t.cnt = l1_cnt_of(p); b.l1_on = afr_gemm_chain_l1_ok(p->gemm_dtype, b.g, t); }
+        return flush_members(p, s, b, 0, 4, true);
+    }
+    b.l1_on = false;
     if (int rc = flush_members(p, s, b, 0, b.n < 2 ? b.n : 2, false)) return rc;
     return flush_members(p, s, b, 2, b.n > 2 ? b.n - 2 : 0, false);
 }
@@ -1427,7 +1443,10 @@ static int backward_stage_impl(afr_plan* p, int stage, int64_t* g_off, int64_t* 
             float* sl = (float*)(p->ws + p->o_l1f);
             const int CS = afr_glyph_l1_bwd_fused_split(B, l.N), nb = afr_glyph_l1_bwd_fused_blocks(B, l.N), nc = l.N / CS;
             const long long st = afr_glyph_l1_bwd_fused_slab_floats(B, l.N, c.vocab, c.n_fonts);
-            {
+            const bool rode = carry && carry->l1_on && carry->l1.d1 == dy;     // the chained launch above ran it as its fifth role
+            if (carry && carry->l1_on && !rode) return fail(AFR_ESTATE, "the chained launch ran the first-layer backward on another d1");
+            if (carry) carry->l1_on = false;
+            if (!rode) {
                 ProfScope ps(p, s, "glyph_l1_bwd_fused", 2.0 * B * l.N * (2.0 * E + 1.0), (double)B * l.N * 2.0 + (double)nb * st * 4.0);
                 const LossSum* sum = step ? &step->loss : nullptr;      // the step's deferred loss partials: one more workgroup adds them
                 if (p->last.combo_on) HIPCHK(afr_launch_glyph_l1_bwd_fused(dy, l.N, p->ws + p->o_h0c, E, p->ws + p->o_w1t, p->last.x, p->last.font, B, l.N,
@@ -1489,6 +1508,23 @@ static int backward_stage_impl(afr_plan* p, int stage, int64_t* g_off, int64_t* 
     if (gath) { g.aux_rowmap = cidx; g.ldaux = p->h1c_ld; }      // the ReLU gate is read from the gathered H1c rows
     if (p->last.mbits_on && i >= 2 && p->o_mbits[i - 1]) { g.mask_in = (const unsigned char*)(p->ws + p->o_mbits[i - 1]); g.ldmask = l.K / 8; }
     if ((rc = run_gemm(p, s, g, bp))) return rc;
+    if (chain_lo && i == 1 && p->k0 && l1_bwd_fused(p) && !(c.reserved & AFR_CFG_NO_L1_CHAIN)) {
+        // the layer below is the folded first layer and its fused backward reads exactly this dx: it rides the chained launch as a
+        // fifth role (the arguments of the stage below, which then only books the slabs).  flush_gemms drops it when the launcher
+        // does not take it.
+        const auto& l0 = p->layers[0];
+        const int E = c.embed_dim, nb1 = afr_glyph_l1_bwd_fused_blocks(B, l0.N);
+        ChainL1& d = batch.l1;
+        d = ChainL1();
+        d.d1 = dx; d.ldd = l0.N; d.W1T = p->ws + p->o_w1t; d.x = p->last.x; d.font = p->last.font; d.B = B; d.N1 = l0.N;
+        d.vocab = c.vocab; d.n_fonts = c.n_fonts; d.slabs = (float*)(p->ws + p->o_l1f);
+        if (p->last.combo_on) { d.h0 = p->ws + p->o_h0c; d.ldh = E; d.h0_rowmap = (const int*)(p->ws + p->o_cidx); }
+        else { d.h0 = p->ws + p->o_act[0]; d.ldh = p->k0; }
+        batch.l1_loss = step ? step->loss : LossSum();
+        batch.l1_fl = 2.0 * B * l0.N * (2.0 * E + 1.0);
+        batch.l1_by = (double)B * l0.N * 2.0 + (double)nb1 * afr_glyph_l1_bwd_fused_slab_floats(B, l0.N, c.vocab, c.n_fonts) * 4.0;
+        batch.l1_on = true;
+    }
     if (!chain_up && (rc = flush_gemms(p, s, batch))) return rc;
     const int64_t end = l.b_off + (l.N + 63) / 64 * 64;
     if (i > 0) {
@@ -2338,10 +2374,11 @@ extern "C" int afr_op_linear_chain_block(int B, int N_up, int K_up, int K_lo, in
     *phase = *member >= 2 ? 1 : 0;
     return AFR_OK;
 }
-extern "C" int afr_op_linear_chain(const void* dy, const void* x_up, const void* W_up, void* out_up, void* mid, const afr_linear_tail* tail_up,
-                                   const void* x_lo, const void* W_lo, void* out_lo, void* dx_lo, const afr_linear_tail* tail_lo,
-                                   int B, int N_up, int K_up, int K_lo, void* workspace, size_t workspace_bytes,
-                                   char* kernel_name, int name_cap, void* stream) {
+// (l1: the first-layer role of afr_op_linear_chain_l1, its counters and target filled in here)
+static int op_linear_chain(const void* dy, const void* x_up, const void* W_up, void* out_up, void* mid, const afr_linear_tail* tail_up,
+                           const void* x_lo, const void* W_lo, void* out_lo, void* dx_lo, const afr_linear_tail* tail_lo,
+                           int B, int N_up, int K_up, int K_lo, void* workspace, size_t workspace_bytes,
+                           char* kernel_name, int name_cap, void* stream, ChainL1* l1) {
     static const afr_linear_tail none = {};
     const afr_linear_tail &tu = tail_up ? *tail_up : none, &tl = tail_lo ? *tail_lo : none;
     if (!dy || !x_up || !W_up || !out_up || !mid || !x_lo || !W_lo || !out_lo || !dx_lo) return fail(AFR_EINVAL, "null operand");
@@ -2357,6 +2394,8 @@ extern "C" int afr_op_linear_chain(const void* dy, const void* x_up, const void*
     size_t need = 0;
     int rc;
     if ((rc = afr_op_linear_chain_plan(B, N_up, K_up, K_lo, 0, nullptr, nullptr, nullptr, &need))) return rc;
+    const size_t hb = align_up(((size_t)B + 255) / 256 * sizeof(unsigned), 256);
+    if (l1) need += hb;
     if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255)) return fail(AFR_EINVAL, "workspace missing, too small or misaligned: %zu < %zu", workspace_bytes, need);
     hipStream_t s = (hipStream_t)stream;
     DevGuard dg(device_of(out_up));
@@ -2367,8 +2406,7 @@ extern "C" int afr_op_linear_chain(const void* dy, const void* x_up, const void*
     if ((rc = linear_pair_members(AFR_BF16, tu, x_up, W_up, dy, out_up, mid, B, N_up, K_up, K_up, tu.ldx ? tu.ldx : K_up, tu.ld_db ? tu.ld_db : N_up, w, wu, s, g, &pu))) return rc;
     if ((rc = linear_pair_members(AFR_BF16, tl, x_lo, W_lo, mid, out_lo, dx_lo, B, K_up, K_lo, K_lo, tl.ldx ? tl.ldx : K_lo, tl.ld_db ? tl.ld_db : K_up, w + wu, wl, s, g + 2, &pl))) return rc;
     unsigned* hand = (unsigned*)(w + wu + wl);
-    const size_t hb = align_up(((size_t)B + 255) / 256 * sizeof(unsigned), 256);
-    HIPCHK(hipMemsetAsync(hand, 0, hb, s));
+    HIPCHK(hipMemsetAsync(hand, 0, l1 ? 2 * hb : hb, s));
     static uint32_t* err_word[16];       // a device word for AFR_ERR_COOP_TIMEOUT (no plan here): allocated once per device, never read back
     int dev = 0;
     uint32_t* err = nullptr;
@@ -2377,9 +2415,83 @@ extern "C" int afr_op_linear_chain(const void* dy, const void* x_up, const void*
         err = err_word[dev];
     }
     g[0].err = err; g[2].err = err;
-    if ((rc = launcher_rc(afr_launch_gemm_chain(AFR_BF16, g, hand, afr_gemm_chain_arrivals(g), err, s), "chain"))) return rc;
+    if (l1) {
+        l1->cnt = hand + hb / sizeof(unsigned); l1->target = afr_gemm_chain_l1_arrivals(g);
+        if (!afr_gemm_chain_l1_ok(AFR_BF16, g, *l1))
+            return fail(AFR_EUNSUPPORTED, "afr_op_linear_chain_l1: the first-layer backward does not ride this chained launch (d1 must be dx_lo, dense)");
+    }
+    if ((rc = launcher_rc(afr_launch_gemm_chain(AFR_BF16, g, hand, afr_gemm_chain_arrivals(g), err, s, l1), "chain"))) return rc;
     if (kernel_name) snprintf(kernel_name, name_cap, "%s", (tu.p && tu.opt_kind == AFR_OPT_LION) ? "gemm_bf16_group256_lion" : "gemm_bf16_group256");
     return AFR_OK;
+}
+extern "C" int afr_op_linear_chain(const void* dy, const void* x_up, const void* W_up, void* out_up, void* mid, const afr_linear_tail* tail_up,
+                                   const void* x_lo, const void* W_lo, void* out_lo, void* dx_lo, const afr_linear_tail* tail_lo,
+                                   int B, int N_up, int K_up, int K_lo, void* workspace, size_t workspace_bytes,
+                                   char* kernel_name, int name_cap, void* stream) {
+    return op_linear_chain(dy, x_up, W_up, out_up, mid, tail_up, x_lo, W_lo, out_lo, dx_lo, tail_lo, B, N_up, K_up, K_lo, workspace, workspace_bytes,
+                           kernel_name, name_cap, stream, nullptr);
+}
+// ---- afr_op_linear_chain_l1: that launch with the folded first layer's fused backward as its fifth role (GemmGroup::l1), as a glyph
+// step issues it: the refusals of afr_op_linear_chain and of afr_op_glyph_l1_bwd_fused (N1 = K_lo), and d1 must be dx_lo
+static int glyph_op_shape(const char* what, int act_dtype, int B, int E, int vocab, int n_fonts);
+static int glyph_op_n1(const char* what, int N1);
+static int chain_l1_refusals(const char* what, int B, int N1, int vocab, int n_fonts, int ldh, bool rowmap) {
+    if (int rc = glyph_op_shape(what, AFR_BF16, B, 32, vocab, n_fonts)) return rc;
+    if (int rc = glyph_op_n1(what, N1)) return rc;
+    if (!afr_glyph_l1_bwd_fused_eligible(AFR_BF16, 32, N1, vocab, n_fonts))
+        return fail(AFR_EUNSUPPORTED, "%s: N1 = %d, vocab + n_fonts = %d: the fused backward takes N1 a multiple of 128 in 256 .. 1024 and at most 144 table rows (E = 32)",
+                    what, N1, vocab + n_fonts);
+    if (ldh < 32 || ldh % 8) return fail(AFR_EINVAL, "%s: ldh = %d must be a multiple of 8, at least 32", what, ldh);
+    if ((long long)B * N1 * 2 >= (1ll << 31) || (!rowmap && (long long)B * ldh * 2 >= (1ll << 31)))
+        return fail(AFR_EUNSUPPORTED, "%s: d1 and h0 must stay below 2 GiB", what);
+    return AFR_OK;
+}
+extern "C" int afr_op_linear_chain_l1_plan(int B, int N_up, int K_up, int K_lo, int vocab, int n_fonts, int has_loss, int cus, int* blocks, size_t* workspace_bytes) {
+    const char* what = "afr_op_linear_chain_l1";
+    int nb = 0, rc;
+    size_t ws = 0;
+    if ((rc = afr_op_linear_chain_plan(B, N_up, K_up, K_lo, cus, nullptr, nullptr, &nb, &ws))) return rc;
+    if ((rc = chain_l1_refusals(what, B, K_lo, vocab, n_fonts, 32, true))) return rc;
+    if (blocks) *blocks = nb + afr_glyph_l1_bwd_fused_blocks(B, K_lo) + (has_loss ? 1 : 0);
+    if (workspace_bytes) *workspace_bytes = ws + align_up(((size_t)B + 255) / 256 * sizeof(unsigned), 256);
+    return AFR_OK;
+}
+extern "C" int afr_op_linear_chain_l1_block(int B, int N_up, int K_up, int K_lo, int vocab, int n_fonts, int has_loss, int block, int* role,
+                                            int* row_block, int* col_range, int* wait_block) {
+    if (!role || !row_block || !col_range || !wait_block) return fail(AFR_EINVAL, "null output");
+    int nb = 0, rc;
+    if ((rc = afr_op_linear_chain_l1_plan(B, N_up, K_up, K_lo, vocab, n_fonts, has_loss, 1 << 30, nullptr, nullptr))) return rc;
+    if ((rc = afr_op_linear_chain_plan(B, N_up, K_up, K_lo, 1 << 30, nullptr, nullptr, &nb, nullptr))) return rc;
+    *role = 0; *row_block = *col_range = *wait_block = -1;
+    if (block >= 0 && block < nb) return AFR_OK;                   // a GEMM member: afr_op_linear_chain_block has its tile
+    int ls = 0;
+    if (!afr_gemm_chain_l1_block(B, K_lo, has_loss != 0, block - nb, row_block, col_range, wait_block, &ls))
+        return fail(AFR_EINVAL, "block %d: outside the chained launch", block);
+    *role = ls ? 2 : 1;
+    return AFR_OK;
+}
+extern "C" int afr_op_linear_chain_l1(const void* dy, const void* x_up, const void* W_up, void* out_up, void* mid, const afr_linear_tail* tail_up,
+                                      const void* x_lo, const void* W_lo, void* out_lo, void* dx_lo, const afr_linear_tail* tail_lo,
+                                      int B, int N_up, int K_up, int K_lo, void* workspace, size_t workspace_bytes,
+                                      const void* d1, const void* h0, int ldh, const int32_t* h0_rowmap, const void* W1T, const int64_t* x,
+                                      const int64_t* font, int vocab, int n_fonts, float* slabs,
+                                      const float* loss_partial, int loss_n, int loss_bd, float loss_inv_n, float* loss_accum,
+                                      char* kernel_name, int name_cap, void* stream) {
+    const char* what = "afr_op_linear_chain_l1";
+    if (int rc = chain_l1_refusals(what, B, K_lo, vocab, n_fonts, ldh, h0_rowmap != nullptr)) return rc;
+    if (!d1 || !h0 || !W1T || !x || !slabs) return fail(AFR_EINVAL, "%s: null argument", what);
+    if (((uintptr_t)d1 & 15) || ((uintptr_t)h0 & 15) || ((uintptr_t)W1T & 15) || ((uintptr_t)slabs & 15))
+        return fail(AFR_EINVAL, "%s: d1, h0, W1T and slabs must be 16-byte aligned", what);
+    if (d1 != dx_lo) return fail(AFR_EUNSUPPORTED, "%s: d1 must be dx_lo, the lower input gradient this launch writes", what);
+    if (loss_partial && (loss_n < 1 || (loss_bd != 256 && loss_bd != 512) || !loss_accum))
+        return fail(AFR_EINVAL, "%s: deferred loss partials need n >= 1, a producer block size of 256 or 512 and an accumulator", what);
+    ChainL1 l1;
+    LossSum ls;
+    l1.d1 = d1; l1.ldd = K_lo; l1.h0 = h0; l1.ldh = ldh; l1.h0_rowmap = h0_rowmap; l1.W1T = W1T; l1.x = x; l1.font = font;
+    l1.B = B; l1.N1 = K_lo; l1.vocab = vocab; l1.n_fonts = n_fonts; l1.slabs = slabs;
+    if (loss_partial) { ls.partial = loss_partial; ls.n = loss_n; ls.bd = loss_bd; ls.inv_n = loss_inv_n; ls.loss_accum = loss_accum; l1.loss = &ls; }
+    return op_linear_chain(dy, x_up, W_up, out_up, mid, tail_up, x_lo, W_lo, out_lo, dx_lo, tail_lo, B, N_up, K_up, K_lo, workspace, workspace_bytes,
+                           kernel_name, name_cap, stream, &l1);
 }
 extern "C" int afr_op_reduce(float* dst, const float* slabs, int nslabs, int64_t stride, int64_t n, float scale, int acc,
                              void* stream) {

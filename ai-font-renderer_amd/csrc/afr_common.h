@@ -317,8 +317,25 @@ void afr_gemm_pair_plan(int B, int n_out, int k_in, int* tile256, int* splitk);
 bool afr_gemm_chain_counts(int B, int N_up, int K_up, int sk_up, int K_lo, int sk_lo, int cus, int* front, int* back);
 bool afr_gemm_chain_ok(int dtype, const GemmParams* ps);
 unsigned afr_gemm_chain_arrivals(const GemmParams* ps);
-hipError_t afr_launch_gemm_chain(int dtype, const GemmParams* ps, unsigned* hand_cnt, unsigned hand_target, uint32_t* err, hipStream_t s);
+// The folded first layer's fused backward as a FIFTH role of the chained launch (gemm.hip GemmGroup::l1): the arguments of
+// afr_launch_glyph_l1_bwd_fused, whose d1 must be dX_lo's output (ps[3].C, same leading dimension), and a second set of monotonic
+// arrival counters, one per 256-row block of d1: every launch adds ceil(N1 / 256) arrivals to each (afr_gemm_chain_l1_arrivals)
+// and its first-layer workgroups wait for `target`, the total after it.
+struct ChainL1 {
+    const void* d1 = nullptr; int ldd = 0; const void* h0 = nullptr; int ldh = 0; const void* W1T = nullptr;
+    const int64_t* x = nullptr; const int64_t* font = nullptr; int B = 0, N1 = 0, vocab = 0, n_fonts = 0;
+    float* slabs = nullptr; const int* h0_rowmap = nullptr; const LossSum* loss = nullptr;
+    unsigned* cnt = nullptr; unsigned target = 0;
+};
+bool afr_gemm_chain_l1_ok(int dtype, const GemmParams* ps, const ChainL1& l1);       // afr_gemm_chain_ok and the role's own conditions
+unsigned afr_gemm_chain_l1_arrivals(const GemmParams* ps);
+hipError_t afr_launch_gemm_chain(int dtype, const GemmParams* ps, unsigned* hand_cnt, unsigned hand_target, uint32_t* err, hipStream_t s,
+                                 const ChainL1* l1 = nullptr);
 bool afr_gemm_chain_block(const GemmParams* ps, int b, int* member, int* tm, int* tn, int* slice);
+// host copy of the block map of the first-layer range: block b of it (0 = the launch's block blk0[4]) -> its 64-glyph row block,
+// its column range and the 256-row block of d1 it waits for; *loss_sum = 1 (the rest -1): the appended loss-sum workgroup, which
+// exists only with deferred loss partials (has_loss).  false: b is outside the range.
+bool afr_gemm_chain_l1_block(int B, int N1, bool has_loss, int b, int* row_block, int* col_range, int* wait_block, int* loss_sum);
 // in-launch split-K for one bf16 product on 256x256 tiles (GemmParams::fix_ws): the workspace needs
 // (tiles - head_tiles) * splitk * AFR_FIX_SLICE_BYTES
 constexpr size_t AFR_FIX_SLICE_BYTES = 256 * 256 * 4;

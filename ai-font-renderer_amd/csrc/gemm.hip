@@ -1622,7 +1622,28 @@ __global__ __launch_bounds__(128 * WM, 2) void gemm_bf16(GemmParams p) {
 // chain != 0 (gemm_bf16_group256 and its Lion twin only; n == 4): members 0, 1 are an upper Linear's pair (dW_up cooperative, dX_up)
 // and members 2, 3 the pair of the Linear below it (dW_lo cooperative, dX_lo), whose dy IS dX_up's output: it is handed over
 // inside the launch.  See gemm_bf16_group256.
-struct GemmGroup { int n; int blk0[5]; GemmParams p[4]; int chain = 0; unsigned hand_target = 0; unsigned* hand_cnt = nullptr; uint32_t* hand_err = nullptr; };
+// A chained launch may carry a FIFTH role behind the four products: the folded first layer's fused backward (l1_blocks > 0: the
+// workgroups of glyph_l1_bwd_fused_kernel, blocks blk0[4] .. blk0[4] + l1_blocks - 1, plus its appended loss-sum workgroup when
+// l1.loss.partial is set), whose d1 IS dX_lo's output: a second hand-off (l1_cnt / l1_target, the form of hand_cnt / hand_target).
+// The arguments of the fused first-layer backward (glyph_l1_bwd_fused_kernel, below)
+struct L1BwdArgs {
+    const bf16_t* d1; const bf16_t* h0; const bf16_t* W1T; const int64_t* x; const int64_t* font;
+    const int* h0_rowmap;            // optional: glyph b's h0 row is row h0_rowmap[b] of the table h0 (combination table)
+    int ldd, ldh, B, N1, vocab, n_fonts;
+    int CS, ncols;                   // the N1 columns are cut into CS ranges of ncols (a multiple of 128): block = (row block, range)
+    float* slabs; long long slab_stride; int o_b, o_tab;
+    int nwork;                       // blocks that compute; with loss.partial set the grid has ONE more, which only adds the step's
+    LossSum loss;                    // deferred loss partials (loss_sum_deferred): off the critical path, nobody waits for it
+#ifdef AFR_GEMM_TIMING
+    int dbg_slot = 0;                // kernel-development builds: the stamp region of the role inside a chained launch
+#endif
+};
+struct GemmGroup {
+    int n; int blk0[5]; GemmParams p[4]; int chain = 0; unsigned hand_target = 0; unsigned* hand_cnt = nullptr; uint32_t* hand_err = nullptr;
+    int l1_blocks = 0; unsigned l1_target = 0; unsigned* l1_cnt = nullptr; L1BwdArgs l1{};
+};
+template <bool CHAINED>
+__device__ __forceinline__ void glyph_l1_bwd_fused_body(const L1BwdArgs& a, int blk, char* sm, const unsigned* cnt, unsigned target, uint32_t* err);
 // block -> its product
 __host__ __device__ __forceinline__ int group_member_of(const int n, const int* blk0, const int b) {
     int i = 0;
@@ -1707,9 +1728,27 @@ __device__ __forceinline__ void chain_wait(const GemmGroup& g) {
 // as the upper workgroups -- who wait for nobody below -- leave their CUs: with as many CUs as the upper pair has workgroups
 // (the launcher asks for that) every dW2 slice is resident once the upper pair has gone.  Every wait is bounded
 // (AFR_ERR_COOP_TIMEOUT), none can hang.
+// The FIFTH role (GemmGroup::l1_blocks > 0; C3: the grid is [dW3 | dX3 | dW2 | dX2 | L1], 128 x 4 + 256 (+ 1 loss-sum) workgroups):
+// the folded first layer's fused backward (glyph_l1_bwd_fused_body<true>), whose d1 is dX2's output.  dX2 (member 3) becomes a
+// producer exactly as dX3 is -- write-through tile, drained, one arrival per column tile on the counter of its 256-row block, in a
+// second set of counters (l1_cnt) -- and an L1 workgroup (64 glyphs x a column range) waits for the ONE counter of its row block
+// after it has requested everything that does not depend on d1.  It runs in the kernel's static LDS (it needs at most 8 x 16 KiB
+// + 512 B of the 160 KiB) and is selected AHEAD of chain_wait / group_member and returns behind its body: nothing of it is alive
+// around a GEMM body (see above what that costs).
+// Progress with the fifth role: L1 workgroups are LAST in the grid, so every workgroup they wait for (dX2's) and every cooperative
+// dW2 partner was handed out before the first of them -- an L1 workgroup never holds a CU that a workgroup somebody waits for
+// still needs; dX2 workgroups wait only for the upper pair, dW2 slices for the upper pair and each other, as before; the static
+// LDS keeps it at one workgroup per CU, so the residency argument above is unchanged; and the L1 wait is bounded like the others
+// (AFR_ERR_COOP_TIMEOUT).  The appended loss-sum workgroup waits for nobody (its partials are an earlier launch's).
 __global__ __launch_bounds__(512, 2) void gemm_bf16_group256(GemmGroup g) {
     __shared__ __attribute__((aligned(16))) char smem[10 * SUB];   // all 160 KiB: A ring 3 x 32 KiB + B ring 2 x 32 KiB
-    if (g.chain) chain_wait(g);
+    if (g.chain) {
+        if ((int)blockIdx.x >= g.blk0[4]) {                         // the fifth role: nothing of it is alive around a GEMM body
+            glyph_l1_bwd_fused_body<true>(g.l1, (int)blockIdx.x - g.blk0[4], smem, g.l1_cnt, g.l1_target, g.hand_err);
+            return;
+        }
+        chain_wait(g);
+    }
     group_member(g, [&](const GemmParams& p, int bid, int nblk, auto a, auto b) {
         if constexpr (a() && b()) {                                // gathered B rows: weight gradients only
             if (p.b_rowmap) { gemm_bf16_256_body<1, 1, 1>(p, bid, nblk, smem); return; }
@@ -1722,7 +1761,13 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_group256(GemmGroup g) {
 // and its code.)
 __global__ __launch_bounds__(512, 2) void gemm_bf16_group256_lion(GemmGroup g) {
     __shared__ __attribute__((aligned(16))) char smem[10 * SUB];
-    if (g.chain) chain_wait(g);
+    if (g.chain) {
+        if ((int)blockIdx.x >= g.blk0[4]) {                         // the fifth role: nothing of it is alive around a GEMM body
+            glyph_l1_bwd_fused_body<true>(g.l1, (int)blockIdx.x - g.blk0[4], smem, g.l1_cnt, g.l1_target, g.hand_err);
+            return;
+        }
+        chain_wait(g);
+    }
     group_member(g, [&](const GemmParams& p, int bid, int nblk, auto a, auto b) {
         if constexpr (a() && b()) {
             if (p.b_rowmap) gemm_bf16_256_body<1, 1, 1, OPT_LION>(p, bid, nblk, smem);
@@ -1743,31 +1788,35 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_group256_lion(GemmGroup g) {
 // and leaves them in its slab [dW1 | db1 | dTab]; the grouped reduce adds the slabs in block order.  This replaces a
 // weight-gradient GEMM against the 168-column widened operand (2.8 GFLOP, 14.5 us of mostly fixed cost, 22 MB of split-K
 // slabs) and the kernel that post-processed its slabs (9 us).
-struct L1BwdArgs {
-    const bf16_t* d1; const bf16_t* h0; const bf16_t* W1T; const int64_t* x; const int64_t* font;
-    const int* h0_rowmap;            // optional: glyph b's h0 row is row h0_rowmap[b] of the table h0 (combination table)
-    int ldd, ldh, B, N1, vocab, n_fonts;
-    int CS, ncols;                   // the N1 columns are cut into CS ranges of ncols (a multiple of 128): block = (row block, range)
-    float* slabs; long long slab_stride; int o_b, o_tab;
-    int nwork;                       // blocks that compute; with loss.partial set the grid has ONE more, which only adds the step's
-    LossSum loss;                    // deferred loss partials (loss_sum_deferred): off the critical path, nobody waits for it
-};
+// The body is a device function of block `blk` (L1BwdArgs stands ahead of GemmGroup): its own kernel calls it, and so does a
+// chained gemm_bf16_group256 launch as its fifth role (CHAINED), where d1 is dX_lo's output of the SAME launch: everything that
+// does not depend on d1 -- the W1^T fragments, the h0 image, the ids -- is requested ahead of the d1 pieces, while wave 0 waits
+// for the arrival counter of the workgroup's 256-row block of d1 (cnt[b0 >> 8] reaches target; the form of chain_wait: one wave
+// polls, bounded, one agent-scope acquire because the d1 loads are LDS-DMA, vmcnt(0) in that wave, the workgroup's barrier);
+// only then d1 is staged.  Same pieces, same images, same products in the same order as the stand-alone kernel: the slabs are
+// bit for bit the same.
 constexpr int L1_E = 32, L1_R = 64, L1_LDR = L1_R + 8;       // embedding width (compile time), glyphs per block, padded row of the overlay
-__global__ __launch_bounds__(512) void glyph_l1_bwd_fused_kernel(L1BwdArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char sm[];
-    if ((int)blockIdx.x >= a.nwork) {                        // the appended workgroup (launched only with a.loss.partial set)
+template <bool CHAINED>
+__device__ __forceinline__ void glyph_l1_bwd_fused_body(const L1BwdArgs& a, const int blk, char* sm, const unsigned* cnt, const unsigned target, uint32_t* err) {
+    if (blk >= a.nwork) {                                    // the appended workgroup (launched only with a.loss.partial set)
         loss_sum_deferred(a.loss, reinterpret_cast<float*>(sm));
         return;
     }
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), r = lane & 15, q = lane >> 4;
+#ifdef AFR_GEMM_TIMING
+    unsigned long long* stamps = CHAINED ? g_gemm_stamps : nullptr;
+    const L1BwdArgs& p = a;                                  // (GSLOT reads p.dbg_slot)
+    GSTAMP(0);
+    if (stamps && tid == 0) stamps[GSLOT * 8 + 5] = 2;       // the record's role word: 1 = cooperative split-K, 2 = first-layer role
+#endif
     const int NS = a.ncols >> 7;                             // 128-column sub-tiles of this block's d1 columns
-    const int rb = blockIdx.x / a.CS, n_lo = (blockIdx.x - rb * a.CS) * a.ncols;
+    const int rb = blk / a.CS, n_lo = (blk - rb * a.CS) * a.ncols;
     const int b0 = rb * L1_R, nb = min(L1_R, a.B - b0);
     char* Dimg = sm;                                         // [NS] images [64 k][128 x], 16 KiB each
     char* Himg = sm + NS * SUB;                              // h0 image (x < E valid, x == E: ones)
     int* ids = reinterpret_cast<int*>(sm + (NS + 1) * SUB);  // [64] codes, [64] vocab + font id (or -1)
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)sm;
-    float* slab = a.slabs + (size_t)blockIdx.x * a.slab_stride;
+    float* slab = a.slabs + (size_t)blk * a.slab_stride;
     // this wave's W1^T operands of the dh0 product (16 bytes per lane and k-step, <= 32 k-steps): independent of the staging
     // below, so they are requested first and arrive under it
     constexpr int L1_MAXKS = 32;
@@ -1783,19 +1832,48 @@ __global__ __launch_bounds__(512) void glyph_l1_bwd_fused_kernel(L1BwdArgs a) {
     {
         const i32x4 rD = make_rsrc(a.d1), rH = make_rsrc(a.h0);
         const int pieces = (NS + 1) * 16;
-        for (int pc = wave; pc < pieces; pc += 8) {
-            const int sidx = pc >> 4, inst = pc & 15;
-            if (sidx < NS) stage_inst<1>(rD, lds0 + sidx * SUB, a.ldd, a.N1, n_lo + sidx * 128, b0, b0 + nb, inst, lane);
-            else stage_inst<1>(rH, lds0 + NS * SUB, a.ldh, L1_E, 0, b0, b0 + nb, inst, lane, a.h0_rowmap);
+        if (!CHAINED) {
+            for (int pc = wave; pc < pieces; pc += 8) {
+                const int sidx = pc >> 4, inst = pc & 15;
+                if (sidx < NS) stage_inst<1>(rD, lds0 + sidx * SUB, a.ldd, a.N1, n_lo + sidx * 128, b0, b0 + nb, inst, lane);
+                else stage_inst<1>(rH, lds0 + NS * SUB, a.ldh, L1_E, 0, b0, b0 + nb, inst, lane, a.h0_rowmap);
+            }
         }
-        if (tid < L1_R) {
+        // (chained: wave 0 requests the ids and polls while waves 1..7 issue the 16 h0 pieces -- a gathered piece is two dependent round
+        // trips, row index then row, which must not stand between the poll and the d1 pieces; which wave issues a piece changes no byte)
+        if (CHAINED ? wave == 0 : tid < L1_R) {
             long long xi = tid < nb ? a.x[b0 + tid] : 0, fi = (tid < nb && a.n_fonts > 0 && a.font) ? a.font[b0 + tid] : 0;
+            if (CHAINED) {
+                unsigned spins = 0;
+                while ((int)(__hip_atomic_load(cnt + (b0 >> 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) < 0) {
+                    __builtin_amdgcn_s_sleep(8);
+                    if (++spins > (1u << 22)) {                          // seconds: dX_lo never ran
+                        if (lane == 0 && err) atomicOr(err, AFR_ERR_COOP_TIMEOUT);
+                        break;
+                    }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the invalidate has completed (this wave issued it)
+            }
             xi = min(max(xi, 0ll), (long long)a.vocab - 1);                  // out-of-range codes were flagged by the forward
             if (a.n_fonts > 0) fi = min(max(fi, 0ll), (long long)a.n_fonts - 1);
             ids[tid] = (int)xi; ids[L1_R + tid] = a.n_fonts > 0 ? a.vocab + (int)fi : -1;
+        } else if (CHAINED) {
+            for (int inst = wave - 1; inst < 16; inst += 7) stage_inst<1>(rH, lds0 + NS * SUB, a.ldh, L1_E, 0, b0, b0 + nb, inst, lane, a.h0_rowmap);
+        }
+        if (CHAINED) {
+            __builtin_amdgcn_s_barrier();                                // d1 has arrived; nobody waits here for its own requests
+#ifdef AFR_GEMM_TIMING
+            GSTAMP(1);
+#endif
+            for (int pc = wave; pc < NS * 16; pc += 8)
+                stage_inst<1>(rD, lds0 + (pc >> 4) * SUB, a.ldd, a.N1, n_lo + (pc >> 4) * 128, b0, b0 + nb, pc & 15, lane);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
+#ifdef AFR_GEMM_TIMING
+        GSTAMP(2);                                           // chained role: 0 entry, 1 d1 has arrived, 2 d1 is staged, 3 exit
+#endif
         if (tid < nb) {                                      // the ones column: element (k = tid, x = E) of the h0 image
             const int k = tid, xx = L1_E;
             *reinterpret_cast<unsigned short*>(Himg + k * 256 + (((xx >> 4) ^ fswz(k)) << 5) + (xx & 15) * 2) = 0x3F80;   // bf16 1.0
@@ -1867,6 +1945,15 @@ __global__ __launch_bounds__(512) void glyph_l1_bwd_fused_kernel(L1BwdArgs a) {
         const int v = vt * 16 + r;
         if (v < rows_tot) *reinterpret_cast<f32x4*>(slab + a.o_tab + (size_t)v * L1_E + et * 16 + 4 * q) = acc;
     }
+#ifdef AFR_GEMM_TIMING
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    GSTAMP(3);
+#endif
+}
+__global__ __launch_bounds__(512) void glyph_l1_bwd_fused_kernel(L1BwdArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char sm[];
+    glyph_l1_bwd_fused_body<false>(a, (int)blockIdx.x, sm, nullptr, 0u, nullptr);
 }
 }  // namespace bf16k
 
@@ -2217,17 +2304,51 @@ bool afr_gemm_chain_ok(int dtype, const GemmParams* ps) { return chain_descripto
 // hand_cnt: one counter per 256-row block of dX_up's output, monotonic; every launch adds ceil(K_up / 256) arrivals to each
 // (afr_gemm_chain_arrivals) and waits for hand_target = the total after it.  hipErrorInvalidValue: not a chain, nothing launched.
 unsigned afr_gemm_chain_arrivals(const GemmParams* ps) { return (unsigned)((ps[1].N + 255) / 256); }
-hipError_t afr_launch_gemm_chain(int dtype, const GemmParams* ps, unsigned* hand_cnt, unsigned hand_target, uint32_t* err, hipStream_t s) {
-    if (!hand_cnt || !afr_gemm_chain_ok(dtype, ps)) return hipErrorInvalidValue;
+// The first-layer role's arguments (what afr_launch_glyph_l1_bwd_fused passes its kernel)
+static void l1_args(const void* d1, int ldd, const void* h0, int ldh, const void* W1T, const int64_t* x, const int64_t* font, int B, int N1,
+                    int vocab, int n_fonts, float* slabs, const int* h0_rowmap, const LossSum* loss, bf16k::L1BwdArgs& a);
+static bool l1_loss_ok(const LossSum* loss) { return !(loss && loss->partial && (loss->n < 1 || (loss->bd != 256 && loss->bd != 512) || !loss->loss_accum)); }
+unsigned afr_gemm_chain_l1_arrivals(const GemmParams* ps) { return (unsigned)((ps[3].N + 255) / 256); }
+// d1 IS dX_lo's output, row for row; the role's images fit the kernel's static LDS (at most 8 x 16 KiB + 512 B of the 160 KiB)
+bool afr_gemm_chain_l1_ok(int dtype, const GemmParams* ps, const ChainL1& l) {
+    if (!afr_gemm_chain_ok(dtype, ps) || !l.cnt || !l.d1 || !l.h0 || !l.W1T || !l.x || !l.slabs || !l1_loss_ok(l.loss)) return false;
+    if (!afr_glyph_l1_bwd_fused_eligible(dtype, bf16k::L1_E, l.N1, l.vocab, l.n_fonts)) return false;
+    if (l.d1 != ps[3].C || l.ldd != ps[3].ldc || l.B != ps[3].M || l.N1 != ps[3].N || ps[3].hand_cnt) return false;
+    const size_t lds = (size_t)(l.N1 / afr_glyph_l1_bwd_fused_split(l.B, l.N1) / 128 + 1) * bf16k::SUB + 2 * bf16k::L1_R * sizeof(int);
+    return lds <= 10 * (size_t)bf16k::SUB;
+}
+bool afr_gemm_chain_l1_block(int B, int N1, bool has_loss, int b, int* row_block, int* col_range, int* wait_block, int* loss_sum) {
+    if (B <= 0 || N1 < 128) return false;
+    const int nwork = afr_glyph_l1_bwd_fused_blocks(B, N1), CS = afr_glyph_l1_bwd_fused_split(B, N1);
+    if (b < 0 || b >= nwork + (has_loss ? 1 : 0)) return false;
+    const bool ls = b >= nwork;
+    *loss_sum = ls ? 1 : 0;
+    *row_block = ls ? -1 : b / CS; *col_range = ls ? -1 : b % CS; *wait_block = ls ? -1 : (b / CS * bf16k::L1_R) >> 8;
+    return true;
+}
+hipError_t afr_launch_gemm_chain(int dtype, const GemmParams* ps, unsigned* hand_cnt, unsigned hand_target, uint32_t* err, hipStream_t s,
+                                 const ChainL1* l1) {
+    if (!hand_cnt || !(l1 ? afr_gemm_chain_l1_ok(dtype, ps, *l1) : afr_gemm_chain_ok(dtype, ps))) return hipErrorInvalidValue;
     bf16k::GemmGroup g;
     chain_group(ps, hand_cnt, g);
     g.hand_cnt = hand_cnt; g.hand_target = hand_target; g.hand_err = err;
+    int total = g.blk0[4];
+    if (l1) {
+        // dX_lo becomes a producer as dX_up is: write-through tile, drained, one arrival on its row block's counter of the second set
+        g.p[3].flags |= AFR_GEMM_OUT_WTHRU; g.p[3].hand_cnt = l1->cnt;
+        l1_args(l1->d1, l1->ldd, l1->h0, l1->ldh, l1->W1T, l1->x, l1->font, l1->B, l1->N1, l1->vocab, l1->n_fonts, l1->slabs, l1->h0_rowmap, l1->loss, g.l1);
+        g.l1_blocks = g.l1.nwork + (g.l1.loss.partial ? 1 : 0); g.l1_cnt = l1->cnt; g.l1_target = l1->target;
+        total += g.l1_blocks;
+#ifdef AFR_GEMM_TIMING
+        g.l1.dbg_slot = g_dbg_slot++ & 63;
+#endif
+    }
 #ifdef AFR_GEMM_TIMING
     { const int s1 = g_dbg_slot++ & 63, s2 = g_dbg_slot++ & 63; g.p[0].dbg_slot = g.p[1].dbg_slot = s1; g.p[2].dbg_slot = g.p[3].dbg_slot = s2; }
 #endif
     const bool lion = ps[0].ad_p && ps[0].ad_kind == OPT_LION;
-    if (lion) hipLaunchKernelGGL(bf16k::gemm_bf16_group256_lion, dim3(g.blk0[4]), dim3(512), 0, s, g);
-    else hipLaunchKernelGGL(bf16k::gemm_bf16_group256, dim3(g.blk0[4]), dim3(512), 0, s, g);
+    if (lion) hipLaunchKernelGGL(bf16k::gemm_bf16_group256_lion, dim3(total), dim3(512), 0, s, g);
+    else hipLaunchKernelGGL(bf16k::gemm_bf16_group256, dim3(total), dim3(512), 0, s, g);
     return hipGetLastError();
 }
 // Host copy of the kernel's block map: block b of the chained launch -> its member (the chain order of ps; 0, 1: the upper pair,
@@ -2318,13 +2439,9 @@ hipError_t afr_launch_glyph_l1_bwd_fused(const void* d1, int ldd, const void* h0
                                          const int64_t* font, int B, int N1, int vocab, int n_fonts, float* slabs, hipStream_t s,
                                          const int* h0_rowmap, const LossSum* loss) {
     if (B <= 0) return hipSuccess;
-    if (loss && loss->partial && (loss->n < 1 || (loss->bd != 256 && loss->bd != 512) || !loss->loss_accum)) return hipErrorInvalidValue;
+    if (!l1_loss_ok(loss)) return hipErrorInvalidValue;
     bf16k::L1BwdArgs a;
-    a.d1 = (const bf16_t*)d1; a.h0 = (const bf16_t*)h0; a.W1T = (const bf16_t*)W1T; a.x = x; a.font = font; a.h0_rowmap = h0_rowmap;
-    a.ldd = ldd; a.ldh = ldh; a.B = B; a.N1 = N1; a.vocab = vocab; a.n_fonts = n_fonts;
-    a.CS = afr_glyph_l1_bwd_fused_split(B, N1); a.ncols = N1 / a.CS;
-    a.slabs = slabs; a.slab_stride = afr_glyph_l1_bwd_fused_slab_floats(B, N1, vocab, n_fonts);
-    a.o_b = a.ncols * bf16k::L1_E; a.o_tab = a.o_b + a.ncols;
+    l1_args(d1, ldd, h0, ldh, W1T, x, font, B, N1, vocab, n_fonts, slabs, h0_rowmap, loss, a);
     const size_t lds = (size_t)(a.ncols / 128 + 1) * bf16k::SUB + 2 * bf16k::L1_R * sizeof(int);
     static size_t set[16];
     int dev = 0;
@@ -2333,8 +2450,16 @@ hipError_t afr_launch_glyph_l1_bwd_fused(const void* d1, int ldd, const void* h0
         if (e != hipSuccess) return e;
         if (dev >= 0 && dev < 16) set[dev] = lds;
     }
-    a.nwork = afr_glyph_l1_bwd_fused_blocks(B, N1);
-    if (loss && loss->partial) a.loss = *loss;
     hipLaunchKernelGGL(bf16k::glyph_l1_bwd_fused_kernel, dim3(a.nwork + (a.loss.partial ? 1 : 0)), dim3(512), lds, s, a);
     return hipGetLastError();
+}
+static void l1_args(const void* d1, int ldd, const void* h0, int ldh, const void* W1T, const int64_t* x, const int64_t* font, int B, int N1,
+                    int vocab, int n_fonts, float* slabs, const int* h0_rowmap, const LossSum* loss, bf16k::L1BwdArgs& a) {
+    a.d1 = (const bf16_t*)d1; a.h0 = (const bf16_t*)h0; a.W1T = (const bf16_t*)W1T; a.x = x; a.font = font; a.h0_rowmap = h0_rowmap;
+    a.ldd = ldd; a.ldh = ldh; a.B = B; a.N1 = N1; a.vocab = vocab; a.n_fonts = n_fonts;
+    a.CS = afr_glyph_l1_bwd_fused_split(B, N1); a.ncols = N1 / a.CS;
+    a.slabs = slabs; a.slab_stride = afr_glyph_l1_bwd_fused_slab_floats(B, N1, vocab, n_fonts);
+    a.o_b = a.ncols * bf16k::L1_E; a.o_tab = a.o_b + a.ncols;
+    a.nwork = afr_glyph_l1_bwd_fused_blocks(B, N1);
+    if (loss && loss->partial) a.loss = *loss;
 }

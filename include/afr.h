@@ -86,14 +86,18 @@ typedef struct afr_config {
                             bit 7: ReLU masks of the input-gradient products read from the stored activations instead of the
                             bit masks the forward epilogues leave (bits 6, 7: A/B measurements; bitwise equal results)
                             bit 8: the output layer's and the last hidden layer's cooperative gradient pairs as two grouped
-                            launches instead of ONE chained launch (A/B measurements; bitwise equal results)               */
+                            launches instead of ONE chained launch (A/B measurements; bitwise equal results)
+                            bit 9: the folded first layer's fused backward as a launch of its own behind that chained launch,
+                            instead of as the launch's fifth role, handed its d1 inside the launch (A/B measurements; bitwise
+                            equal results)                                                                                  */
     int32_t loss;        /* AFR_LOSS_*: the output head and loss of every entry point below (0 = clamp + MSE); any other
                             value is AFR_EINVAL.  Appended after `reserved` (the struct grew by 8 bytes with it): a zero-initialised
                             config means what it meant, a caller compiled against the older header must be rebuilt          */
 } afr_config;
 /* the bits of afr_config.reserved, as described above */
 enum { AFR_CFG_UNFUSED_OPTIMIZER = 1, AFR_CFG_NO_GROUPED_GEMM = 2, AFR_CFG_NO_FUSED_GLYPH1 = 4, AFR_CFG_L1_BWD_UNFUSED = 16,
-       AFR_CFG_SLAB_SPLITK = 32, AFR_CFG_NO_COMBO_TABLE = 64, AFR_CFG_RELU_MASK_FROM_ACT = 128, AFR_CFG_NO_PAIR_CHAIN = 256 };
+       AFR_CFG_SLAB_SPLITK = 32, AFR_CFG_NO_COMBO_TABLE = 64, AFR_CFG_RELU_MASK_FROM_ACT = 128, AFR_CFG_NO_PAIR_CHAIN = 256,
+       AFR_CFG_NO_L1_CHAIN = 512 };
 
 typedef struct afr_plan afr_plan;
 
@@ -498,6 +502,28 @@ int afr_op_linear_chain(const void* dy, const void* x_up, const void* W_up, void
                         const void* x_lo, const void* W_lo, void* out_lo, void* dx_lo, const afr_linear_tail* tail_lo,
                         int B, int N_up, int K_up, int K_lo, void* workspace, size_t workspace_bytes,
                         char* kernel_name /* or NULL */, int name_cap, void* stream);
+/* The same launch with the folded first layer's fused backward (afr_op_glyph_l1_bwd_fused; N1 = K_lo, E = 32) as its FIFTH role,
+ * as a glyph step issues it when the lower Linear's input is that first layer: the grid is [dW_up | dx_up | dW_lo | dx_lo | L1],
+ * the L1 range being that kernel's workgroups (64 glyphs x a column range each), which are handed the rows of d1 = dx_lo inside
+ * the launch (one arrival counter per 256-row block).  Every output is bit for bit that of afr_op_linear_chain followed by
+ * afr_op_glyph_l1_bwd_fused on its dx_lo.  The refusals are those of both: every one of afr_op_linear_chain, every one of
+ * afr_op_glyph_l1_bwd_fused, and AFR_EUNSUPPORTED when d1 is not dx_lo.  loss_partial (or NULL): deferred loss partials of a
+ * producer launch of loss_n blocks of loss_bd (256 or 512) threads; ONE appended workgroup adds sum * loss_inv_n to *loss_accum.
+ * afr_op_linear_chain_l1_plan (host-only): *blocks = the grid with the L1 range (and the loss-sum workgroup with has_loss),
+ * *workspace_bytes = afr_op_linear_chain_plan's plus the second set of counters.
+ * afr_op_linear_chain_l1_block (host-only): *role = 0 for a block of the four products (afr_op_linear_chain_block has its tile),
+ * 1 for a first-layer workgroup -- glyphs [64 *row_block, +64), column range *col_range, waiting for 256-row block *wait_block
+ * of dx_lo --, 2 for the appended loss-sum workgroup; AFR_EINVAL for a block outside the grid. */
+int afr_op_linear_chain_l1_plan(int B, int N_up, int K_up, int K_lo, int vocab, int n_fonts, int has_loss, int cus, int* blocks, size_t* workspace_bytes);
+int afr_op_linear_chain_l1_block(int B, int N_up, int K_up, int K_lo, int vocab, int n_fonts, int has_loss, int block, int* role,
+                                 int* row_block, int* col_range, int* wait_block);
+int afr_op_linear_chain_l1(const void* dy, const void* x_up, const void* W_up, void* out_up, void* mid, const afr_linear_tail* tail_up,
+                           const void* x_lo, const void* W_lo, void* out_lo, void* dx_lo, const afr_linear_tail* tail_lo,
+                           int B, int N_up, int K_up, int K_lo, void* workspace, size_t workspace_bytes,
+                           const void* d1, const void* h0, int ldh, const int32_t* h0_rowmap /* or NULL */, const void* W1T, const int64_t* x,
+                           const int64_t* font /* or NULL */, int vocab, int n_fonts, float* slabs,
+                           const float* loss_partial /* or NULL */, int loss_n, int loss_bd, float loss_inv_n, float* loss_accum,
+                           char* kernel_name /* or NULL */, int name_cap, void* stream);
 int afr_op_reduce(float* dst, const float* slabs, int nslabs, int64_t slab_stride, int64_t n,
                   float scale, int accumulate, void* stream);
 /* Several slab reductions in ONE launch (what a backward pass uses for all its split-K / per-block partial gradients):

@@ -48,8 +48,10 @@ for rep in range(3):
     us = lambda a: a * 0.01
     t0 = None
     prev_exit = None
+    other_exit = None
     print(f"--- rep {rep}")
-    for slot in range(64):
+    # (a chained launch's first-layer role stamps a region of its own, numbered ahead of the pairs': it is read after them)
+    for slot in sorted(range(64), key=lambda i: bool((s[i][s[i][:, 0] > 0][:, 5] == 2).any())):
         r = s[slot]
         r = r[r[:, 0] > 0]
         if len(r) == 0:
@@ -58,6 +60,18 @@ for rep in range(3):
         if t0 is None:
             t0 = r[:, 0].min()
         ent, land, kend, ex = r[:, 0], r[:, 1], r[:, 2], r[:, 3]
+        if (r[:, 5] == 2).all():
+            # the first-layer role of a chained launch (a region of its own): stamps 0 entry, 1 d1 has arrived (behind the
+            # requests that do not depend on it: W1^T, ids, h0 pieces), 2 d1 is staged, 3 exit
+            print(f"launch {slot}: {len(r):4d} wgs  first-layer role | entry {us(ent.min() - t0):7.2f}..{us(ent.max() - t0):7.2f} (med {us(np.median(ent) - t0):7.2f})"
+                  f"  entry -> d1 there med {us(np.median(land - ent)):5.2f} min {us((land - ent).min()):5.2f} max {us((land - ent).max()):5.2f}"
+                  f"  staging med {us(np.median(kend - land)):5.2f}  products med {us(np.median(ex - kend)):5.2f}"
+                  f"  exit {us(ex.min() - t0):7.2f}..{us(ex.max() - t0):7.2f} (med {us(np.median(ex) - t0):7.2f})")
+            half = np.sort(ent)[len(ent) // 2:]
+            print(f"      second half of the workgroups enters from {us(half.min() - t0):7.2f}; entered before the last dX exit of the region before: {(ent < other_exit).sum() if other_exit else 0} of {len(r)};"
+                  f" exits after the previous region's last exit ({us(prev_exit - t0) if prev_exit is not None else 0.0:7.2f}): {(ex > (prev_exit or 0)).sum()}")
+            prev_exit = max(prev_exit or 0, ex.max())
+            continue
         gap = us(ent.min() - prev_exit) if prev_exit is not None else 0.0
         line = (f"launch {slot}: {len(r):4d} wgs  gap {gap:6.2f} | entry {us(ent.min() - t0):7.2f}..{us(ent.max() - t0):7.2f}  prologue med {us(np.median(land - ent)):5.2f}"
                 f"  K loop med {us(np.median(kend - land)):6.2f} max {us((kend - land).max()):6.2f}  tail med {us(np.median(ex - kend)):5.2f} max {us((ex - kend).max()):5.2f}"
@@ -72,3 +86,4 @@ for rep in range(3):
             if len(ot):
                 print(f"      other wgs ({len(ot)}): K loop med {us(np.median(ot[:, 2] - ot[:, 1])):6.2f}  tail med {us(np.median(ot[:, 3] - ot[:, 2])):5.2f} max {us((ot[:, 3] - ot[:, 2]).max()):5.2f}   exit {us(ot[:, 3].max() - t0):7.2f}")
         prev_exit = ex.max()
+        other_exit = r[r[:, 5] != 1][:, 3].max() if (r[:, 5] != 1).any() else None
