@@ -204,6 +204,9 @@ SIGNATURES = {
     "afr_op_dataset_text": (_i32, [_i64, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp]),
     "afr_op_dataset_text_w": (_i32, [_i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     "afr_op_text_weights": (_i32, [_vp, _i32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "afr_op_dataset_text_m": (_i32, [_i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "afr_op_pair_errors": (_i32, [_vp, _i32, _vp, _i64, _vp, _vp, _vp]),
+    "afr_op_pair_weights": (_i32, [_vp, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "afr_op_compose_sheets": (_i32, [C.POINTER(AfrGlyphAtlas), C.POINTER(AfrSheetGeometry), _vp, _i32, _vp, _i64, _vp, _vp, _vp]),
     "afr_op_sheet_char_errors": (_i32, [C.POINTER(AfrGlyphAtlas), C.POINTER(AfrSheetGeometry), _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "afr_op_sheet_read_back": (_i32, [C.POINTER(AfrGlyphAtlas), C.POINTER(AfrSheetGeometry), _vp, _i32, _vp, _i64, _vp, C.POINTER(C.c_uint32),

@@ -2678,6 +2678,50 @@ extern "C" int afr_op_text_weights(const uint64_t* by_code, int n_codes, const u
     HIPCHK(afr_launch_text_weights((const unsigned long long*)by_code, members, floor_w, gain, cum, w, (hipStream_t)stream));
     return AFR_OK;
 }
+extern "C" int afr_op_dataset_text_m(int64_t first_seed, const int64_t* seed_rows, const int64_t* out_rows, int64_t n, int min_len, int max_len,
+                                     const uint32_t* cum2, int64_t* codes, int ldx, int32_t* len, uint32_t* err, void* stream) {
+    const char* who = "afr_op_dataset_text_m";
+    if (!codes || !cum2) return fail(AFR_EINVAL, "%s: codes or cum2 is null", who);
+    if (n < 1) return fail(AFR_EINVAL, "%s: n = %lld, must be >= 1", who, (long long)n);
+    if (ldx < 1) return fail(AFR_EINVAL, "%s: ldx = %d, must be positive", who, ldx);
+    if (ldx > CMP_MAX_LDX) return fail(AFR_EUNSUPPORTED, "%s: ldx = %d, at most %d codes per row", who, ldx, CMP_MAX_LDX);
+    if (min_len < 1 || max_len < min_len || max_len > ldx)
+        return fail(AFR_EINVAL, "%s: text lengths %d..%d must satisfy 1 <= min_len <= max_len <= ldx = %d", who, min_len, max_len, ldx);
+    if (((uintptr_t)codes & 7) || ((uintptr_t)seed_rows & 7) || ((uintptr_t)out_rows & 7) || ((uintptr_t)len & 3) || ((uintptr_t)cum2 & 3) ||
+        ((uintptr_t)err & 3))
+        return fail(AFR_EINVAL, "%s: codes, seed_rows and out_rows must be 8-byte aligned, cum2, len and err 4-byte", who);
+    DevGuard dg(device_of(codes));
+    HIPCHK(afr_launch_dataset_text_m(first_seed, seed_rows, out_rows, n, min_len, max_len, cum2, codes, ldx, len, err, (hipStream_t)stream));
+    return AFR_OK;
+}
+extern "C" int afr_op_pair_errors(const int64_t* codes, int ldx, const int64_t* code_rows, int64_t n, const uint32_t* per_pos, uint64_t* by_pair,
+                                  void* stream) {
+    const char* who = "afr_op_pair_errors";
+    if (!codes || !per_pos || !by_pair) return fail(AFR_EINVAL, "%s: codes, per_pos or by_pair is null", who);
+    if (n < 1) return fail(AFR_EINVAL, "%s: n = %lld, must be >= 1", who, (long long)n);
+    if (ldx < 1) return fail(AFR_EINVAL, "%s: ldx = %d, must be positive", who, ldx);
+    if (ldx > CMP_MAX_LDX) return fail(AFR_EUNSUPPORTED, "%s: ldx = %d, at most %d codes per row", who, ldx, CMP_MAX_LDX);
+    if (((uintptr_t)codes & 7) || ((uintptr_t)code_rows & 7) || ((uintptr_t)by_pair & 7) || ((uintptr_t)per_pos & 15))
+        return fail(AFR_EINVAL, "%s: codes, code_rows and by_pair must be 8-byte aligned, per_pos 16-byte", who);
+    DevGuard dg(device_of(by_pair));
+    HIPCHK(afr_launch_pair_errors(codes, ldx, code_rows, n, per_pos, (unsigned long long*)by_pair, (hipStream_t)stream));
+    return AFR_OK;
+}
+extern "C" int afr_op_pair_weights(const uint64_t* by_pair, const uint32_t* members, uint32_t floor_w, uint32_t gain, uint32_t min_chars,
+                                   uint32_t* cum2, uint32_t* w2, void* stream) {
+    const char* who = "afr_op_pair_weights";
+    if (!members || !cum2) return fail(AFR_EINVAL, "%s: members or cum2 is null", who);
+    if (members[2] >> (AFR_TEXT_CODES - 64))
+        return fail(AFR_EINVAL, "%s: member bits above bit %d (code %d) are set", who, AFR_TEXT_CODES - 1, AFR_TEXT_FIRST + AFR_TEXT_CODES - 1);
+    if (!(members[0] | members[1] | members[2])) return fail(AFR_EINVAL, "%s: the member set is empty", who);
+    if (floor_w < 1u || floor_w > 65535u || gain > 65535u)
+        return fail(AFR_EINVAL, "%s: floor_w = %u must lie in 1..65535, gain = %u in 0..65535", who, floor_w, gain);
+    if (((uintptr_t)by_pair & 7) || ((uintptr_t)cum2 & 3) || ((uintptr_t)w2 & 3))
+        return fail(AFR_EINVAL, "%s: by_pair must be 8-byte aligned, cum2 and w2 4-byte", who);
+    DevGuard dg(device_of(cum2));
+    HIPCHK(afr_launch_pair_weights((const unsigned long long*)by_pair, members, floor_w, gain, min_chars, cum2, w2, (hipStream_t)stream));
+    return AFR_OK;
+}
 // What afr_op_compose_sheets, afr_op_sheet_char_errors and afr_op_sheet_read_back refuse alike: `dense` is the sheet-shaped buffer
 // (out / pred), `rows` the row vector, lds_extra which kernel's LDS need is held against the budget.  -> AFR_OK or the failure, already recorded.
 enum { SHEET_LDS_COMPOSE = 0, SHEET_LDS_CHARERR = 1, SHEET_LDS_READBACK = 2 };

@@ -462,6 +462,15 @@ hipError_t afr_launch_dataset_text_w(long long first_seed, const int64_t* seed_r
                                      int max_len, const uint32_t* cum, int64_t* codes, int ldx, int32_t* len, uint32_t* err, hipStream_t s);
 hipError_t afr_launch_text_weights(const unsigned long long* by_code, const uint32_t members[3], uint32_t floor_w, uint32_t gain, uint32_t* cum,
                                    uint32_t* w, hipStream_t s);
+// the first-order Markov text source (cum2: device [95][94], one row of inclusive cumulative weights per context: row 0 at a word's
+// start, row 1 + i after letter i), the scatter of afr_op_sheet_char_errors' per-position records into the table by (preceding
+// character, character) (by_pair: device [95][94][4], added to) and the one-workgroup launch that builds cum2 from that table
+hipError_t afr_launch_dataset_text_m(long long first_seed, const int64_t* seed_rows, const int64_t* out_rows, long long n, int min_len,
+                                     int max_len, const uint32_t* cum2, int64_t* codes, int ldx, int32_t* len, uint32_t* err, hipStream_t s);
+hipError_t afr_launch_pair_errors(const int64_t* codes, int ldx, const int64_t* code_rows, long long n, const uint32_t* per_pos,
+                                  unsigned long long* by_pair, hipStream_t s);
+hipError_t afr_launch_pair_weights(const unsigned long long* by_pair, const uint32_t members[3], uint32_t floor_w, uint32_t gain,
+                                   uint32_t min_chars, uint32_t* cum2, uint32_t* w2, hipStream_t s);
 // afr_op_sheet_char_errors: compose's arguments (c.out unused, c.out_rows = the rows of codes the samples read) beside the dense
 // prediction and the two outputs.  LDS as compose's, plus the position records and one 64-bit counter set per code.
 struct CharErrArgs {

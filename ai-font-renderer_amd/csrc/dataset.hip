@@ -93,6 +93,20 @@ hipError_t afr_launch_dataset_text_w(long long first_seed, const int64_t* seed_r
     return hipGetLastError();
 }
 
+// A counter pair's mean squared error relative to the reference mean, in 16.16 fixed point: min((((sumsq << 16) / pixels) << 16) / m_ref,
+// 16 << 16) without forming q << 16, which need not fit: q / m_ref >= 16 is the cap, else sixteen steps of long division on the
+// remainder (< m_ref < 2^63, so its double fits).  pixels != 0, sumsq < 2^47, m_ref >= 1.  Shared by the two weight kernels.
+__device__ __forceinline__ unsigned long long text_rel_to_mean(unsigned long long sumsq, unsigned long long pixels, unsigned long long m_ref) {
+    const unsigned long long q = (sumsq << 16) / pixels;
+    unsigned long long hi = q / m_ref, rem = q - hi * m_ref;
+    if (hi >= 16ull) return 16ull << 16;
+    for (int b = 0; b < 16; ++b) {
+        rem <<= 1; hi <<= 1;
+        if (rem >= m_ref) { rem -= m_ref; hi |= 1ull; }
+    }
+    return hi;
+}
+
 // afr_op_text_weights: the table above from afr_op_sheet_char_errors' by-code counters, one workgroup of 128 lanes, lane i = code 33 + i
 // (synth.text_weights; the definition is in include/afr.h).  Two 64-bit sums over the members (a tree in LDS), the weight of each member
 // in registers, an inclusive scan of the 94 weights in LDS.  No atomics: a second launch stores the same words.
@@ -119,22 +133,7 @@ __global__ __launch_bounds__(TXT_PAD) void text_weights_kernel(TextWeightsArgs a
         const int k = max(0, 64 - __clzll((long long)S) - 47);         // S >> k < 2^47: every << 16 below stays inside 64 bits
         P >>= k; S >>= k; pixels >>= k; sumsq >>= k;
         const unsigned long long m_ref = max(1ull, (S << 16) / max(1ull, P));
-        unsigned long long rel = 1ull << 16;
-        if (pixels != 0ull) {
-            // min((q << 16) / m_ref, 16 << 16) without forming q << 16, which need not fit: q / m_ref >= 16 is the cap, else sixteen
-            // steps of long division on the remainder (< m_ref < 2^63, so its double fits)
-            const unsigned long long q = (sumsq << 16) / pixels;
-            unsigned long long hi = q / m_ref, rem = q - hi * m_ref;
-            if (hi >= 16ull) {
-                rel = 16ull << 16;
-            } else {
-                for (int b = 0; b < 16; ++b) {
-                    rem <<= 1; hi <<= 1;
-                    if (rem >= m_ref) { rem -= m_ref; hi |= 1ull; }
-                }
-                rel = hi;
-            }
-        }
+        const unsigned long long rel = pixels != 0ull ? text_rel_to_mean(sumsq, pixels, m_ref) : 1ull << 16;
         w = a.floor_w + (uint32_t)(((unsigned long long)a.gain * rel) >> 16);
     }
     s_w[t] = w;
@@ -157,6 +156,178 @@ hipError_t afr_launch_text_weights(const unsigned long long* by_code, const uint
                                    uint32_t* w, hipStream_t s) {
     const TextWeightsArgs a{by_code, {members[0], members[1], members[2]}, floor_w, gain, cum, w};
     hipLaunchKernelGGL(text_weights_kernel, dim3(1), dim3(TXT_PAD), 0, s, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------ Markov text
+// afr_op_dataset_text_m: dataset_text_w_kernel with one table row per context (synth.lcg_text_markov): row 0 at the start of a word, row
+// 1 + i after letter i.  The 95 rows go to LDS once per workgroup, each padded to 128 entries with 2^32 - 1 (48 640 bytes), so a draw is
+// the same seven-step search without a bound check, offset by the context's row.  A sample that reaches a row whose total is 0 stops,
+// zero-fills its whole row and flags bit 0 of *err -- one atomic per wave that holds such a sample.
+constexpr int TXT_CTX = TXT_CODES + 1;
+__global__ __launch_bounds__(256) void dataset_text_m_kernel(long long first_seed, const int64_t* __restrict__ seed_rows,
+                                                             const int64_t* __restrict__ out_rows, long long n, int min_len, int max_len,
+                                                             const uint32_t* __restrict__ cum2, int64_t* __restrict__ codes, int ldx,
+                                                             int32_t* __restrict__ len, uint32_t* __restrict__ err) {
+    __shared__ uint32_t s_cum[TXT_CTX * TXT_PAD];
+    for (int e = threadIdx.x; e < TXT_CTX * TXT_PAD; e += 256) {
+        const int r = e / TXT_PAD, c = e - r * TXT_PAD;
+        s_cum[e] = c < TXT_CODES ? cum2[r * TXT_CODES + c] : 0xFFFFFFFFu;
+    }
+    __syncthreads();
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    bool failed = false;
+    if (j < n) {
+        uint32_t state = (uint32_t)(uint64_t)(first_seed + (seed_rows ? seed_rows[j] : j));
+        const long long row = out_rows ? out_rows[j] : j;
+        int64_t* dst = codes + row * (long long)ldx;
+        auto draw = [&](uint32_t k) -> uint32_t {
+            state = state * 1664525u + 1013904223u;
+            return (uint32_t)(((uint64_t)state * k) >> 32);
+        };
+        int length = (int)draw((uint32_t)(max_len - min_len + 1)) + min_len, pos = 0;
+        int remaining = length;
+        while (remaining > 0 && !failed) {
+            const int wl = min((int)draw(10u) + 1, remaining);
+            const uint32_t* tab = s_cum;                               // a word starts in context 0
+            for (int i = 0; i < wl; ++i) {
+                const uint32_t total = tab[TXT_CODES - 1];
+                if (total == 0u) { failed = true; break; }
+                const uint32_t r = draw(total);
+                int at = 0;
+#pragma unroll
+                for (int step = TXT_PAD / 2; step > 0; step >>= 1)
+                    if (tab[at + step - 1] <= r) at += step;
+                dst[pos++] = TXT_FIRST + at;
+                tab = s_cum + (1 + at) * TXT_PAD;                      // at <= 93: r < total = tab[93] ends the search there at the latest
+            }
+            remaining -= wl;
+            if (remaining > 0 && !failed) { dst[pos++] = 32; --remaining; }
+        }
+        if (failed) length = pos = 0;
+        for (; pos < ldx; ++pos) dst[pos] = 0;
+        if (len) len[row] = length;
+    }
+    const unsigned long long any = __ballot(failed);
+    if (any && err && (threadIdx.x & 63) == __ffsll((long long)any) - 1) atomicOr(err, AFR_ERR_INDEX);
+}
+
+hipError_t afr_launch_dataset_text_m(long long first_seed, const int64_t* seed_rows, const int64_t* out_rows, long long n, int min_len,
+                                     int max_len, const uint32_t* cum2, int64_t* codes, int ldx, int32_t* len, uint32_t* err, hipStream_t s) {
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(dataset_text_m_kernel, dim3(blocks), dim3(256), 0, s, first_seed, seed_rows, out_rows, n, min_len, max_len, cum2, codes, ldx,
+                       len, err);
+    return hipGetLastError();
+}
+
+// afr_op_pair_errors: the table is 95 x 94 x 4 counters of 8 bytes, 285 760 bytes, so no workgroup can hold it in LDS whole.  The grid is
+// (chunks of samples) x (8 bands of 12 contexts): a workgroup keeps its band's 12 x 94 x 4 64-bit counters in LDS (36 096 bytes), walks
+// the positions of its chunk -- a lane reads its code and the code before it, and only when the context falls into the band and the
+// position contributes its record of per_pos, adding {1, pixels, sumsq, wrong} with LDS atomics -- and at the end adds every non-zero
+// counter to by_pair with one 64-bit global atomic.  Each band reads the codes once more (8 bytes a position) but every record is read
+// by one band only.  The host sizes the chunks for about 64 of them, 16 samples at the least: one global atomic then stands for the
+// adds of some hundreds of sheets.  Against one lane per position adding straight to by_pair (four global atomics per contribution,
+// a few hundred hot addresses) this form was measured several times faster at 30 000 sheets; profiles/pairs/ has both.
+constexpr int PAIR_BANDS = 8, PAIR_BAND_ROWS = 12, PAIR_BAND_WORDS = PAIR_BAND_ROWS * TXT_CODES * 4;
+static_assert(PAIR_BANDS * PAIR_BAND_ROWS >= TXT_CTX, "the bands cover every context");
+__global__ __launch_bounds__(256) void pair_errors_kernel(const int64_t* __restrict__ codes, int ldx, const int64_t* __restrict__ code_rows,
+                                                          long long n, long long chunk, const uint32_t* __restrict__ per_pos,
+                                                          unsigned long long* __restrict__ by_pair) {
+    __shared__ unsigned long long s_by[PAIR_BAND_WORDS];
+    const int t = threadIdx.x, lo = blockIdx.y * PAIR_BAND_ROWS;
+    for (int e = t; e < PAIR_BAND_WORDS; e += 256) s_by[e] = 0ull;
+    __syncthreads();
+    const long long j0 = (long long)blockIdx.x * chunk, j1 = min(n, j0 + chunk);
+    for (long long e = j0 * ldx + t; e < j1 * ldx; e += 256) {
+        const long long j = e / ldx;
+        const int i = (int)(e - j * ldx);
+        const int64_t* src = codes + (code_rows ? code_rows[j] : j) * (long long)ldx;
+        const long long c = src[i];
+        if (c < TXT_FIRST || c >= TXT_FIRST + TXT_CODES) continue;
+        const long long p = i > 0 ? src[i - 1] : 0;
+        const int r = (p >= TXT_FIRST && p < TXT_FIRST + TXT_CODES ? 1 + (int)(p - TXT_FIRST) : 0) - lo;
+        if ((unsigned)r >= (unsigned)PAIR_BAND_ROWS) continue;
+        const uint4 rec = ((const uint4*)per_pos)[(size_t)j * (size_t)(ldx + 1) + i];      // {pixels, sumsq, off2, wrong}
+        if (rec.x == 0u) continue;
+        unsigned long long* dst = s_by + (r * TXT_CODES + (int)(c - TXT_FIRST)) * 4;
+        atomicAdd(dst, 1ull);
+        atomicAdd(dst + 1, (unsigned long long)rec.x);
+        if (rec.y) atomicAdd(dst + 2, (unsigned long long)rec.y);
+        if (rec.w) atomicAdd(dst + 3, (unsigned long long)rec.w);
+    }
+    __syncthreads();
+    const int words = min(PAIR_BAND_WORDS, (TXT_CTX - lo) * TXT_CODES * 4);                // the last band ends with the table
+    for (int e = t; e < words; e += 256)
+        if (s_by[e]) atomicAdd(by_pair + (size_t)lo * TXT_CODES * 4 + e, s_by[e]);
+}
+
+hipError_t afr_launch_pair_errors(const int64_t* codes, int ldx, const int64_t* code_rows, long long n, const uint32_t* per_pos,
+                                  unsigned long long* by_pair, hipStream_t s) {
+    const long long chunk = max(16ll, (n + 63) / 64);
+    const unsigned chunks = (unsigned)((n + chunk - 1) / chunk);
+    hipLaunchKernelGGL(pair_errors_kernel, dim3(chunks, PAIR_BANDS), dim3(256), 0, s, codes, ldx, code_rows, n, chunk, per_pos, by_pair);
+    return hipGetLastError();
+}
+
+// afr_op_pair_weights: the Markov table from the pair counters, one workgroup of 256 lanes (synth.pair_weights; the definition is in
+// include/afr.h).  The lanes stride over the 95 x 94 pairs twice: once for the two 64-bit sums over the live pairs (a tree in LDS), once
+// for each pair's weight, kept in LDS; lane r < 95 then sums row r in order and stores its cumulative weights.  A record that is not
+// live is never read.  No atomics: a second launch stores the same words.
+struct PairWeightsArgs {
+    const unsigned long long* by_pair; uint32_t members[3]; uint32_t floor_w, gain, min_chars; uint32_t* cum2; uint32_t* w2;
+};
+__device__ __forceinline__ bool text_member(const uint32_t m[3], int i) {
+    return ((i < 32 ? m[0] : i < 64 ? m[1] : m[2]) >> (i & 31)) & 1u;
+}
+__global__ __launch_bounds__(256) void pair_weights_kernel(PairWeightsArgs a) {
+    __shared__ unsigned long long s_p[256], s_s[256];
+    __shared__ uint32_t s_w[TXT_CTX * TXT_CODES];
+    const int t = threadIdx.x;
+    const bool counted = a.by_pair && a.gain;
+    auto live = [&](int e) -> bool {
+        const int r = e / TXT_CODES, c = e - r * TXT_CODES;
+        return text_member(a.members, c) && (r == 0 || text_member(a.members, r - 1));
+    };
+    unsigned long long P = 0ull, S = 0ull;
+    if (counted)
+        for (int e = t; e < TXT_CTX * TXT_CODES; e += 256)
+            if (live(e)) { P += a.by_pair[e * 4 + 1]; S += a.by_pair[e * 4 + 2]; }
+    s_p[t] = P; s_s[t] = S;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (t < off) { s_p[t] += s_p[t + off]; s_s[t] += s_s[t + off]; }
+        __syncthreads();
+    }
+    P = s_p[0]; S = s_s[0];
+    const int k = S ? max(0, 64 - __clzll((long long)S) - 47) : 0;     // S >> k < 2^47: every << 16 below stays inside 64 bits
+    const unsigned long long m_ref = max(1ull, ((S >> k) << 16) / max(1ull, P >> k));
+    for (int e = t; e < TXT_CTX * TXT_CODES; e += 256) {
+        uint32_t w = 0u;
+        if (live(e)) {
+            unsigned long long rel = 1ull << 16;
+            if (S != 0ull) {
+                const unsigned long long chars = a.by_pair[e * 4], pixels = a.by_pair[e * 4 + 1] >> k, sumsq = a.by_pair[e * 4 + 2] >> k;
+                if (pixels != 0ull && chars >= a.min_chars) rel = text_rel_to_mean(sumsq, pixels, m_ref);
+            }
+            w = S != 0ull ? a.floor_w + (uint32_t)(((unsigned long long)a.gain * rel) >> 16) : a.floor_w;
+        }
+        s_w[e] = w;
+        if (a.w2) a.w2[e] = w;
+    }
+    __syncthreads();
+    if (t < TXT_CTX) {
+        uint32_t c = 0u;
+        for (int i = 0; i < TXT_CODES; ++i) {
+            c += s_w[t * TXT_CODES + i];
+            a.cum2[t * TXT_CODES + i] = c;
+        }
+    }
+}
+
+hipError_t afr_launch_pair_weights(const unsigned long long* by_pair, const uint32_t members[3], uint32_t floor_w, uint32_t gain,
+                                   uint32_t min_chars, uint32_t* cum2, uint32_t* w2, hipStream_t s) {
+    const PairWeightsArgs a{by_pair, {members[0], members[1], members[2]}, floor_w, gain, min_chars, cum2, w2};
+    hipLaunchKernelGGL(pair_weights_kernel, dim3(1), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -18,6 +18,11 @@ each letter from a table of integer weights over the codes 33..126 instead -- te
 table on the device, with equal weights or steered by char_errors' by-code counters where they lie -- and generate_codes(..., cum=...)
 and reference_dataset(..., alphabet=...) draw from it.  With equal weights on A-Z the texts are the reference's byte for byte.
 
+The letters can also depend on the letter before them: pair_errors(codes, per_pos) scatters char_errors' per-position records into a
+table by (preceding character, character), pair_weights(alphabet, by_pair, floor_w, gain, min_chars) builds a first-order Markov table
+from it (afr_op_pair_weights) and generate_codes(..., cum2=...) draws from that (afr_op_dataset_text_m) -- so a pair the model draws
+badly, "WW" say, can be made frequent, which no table of single letters can do.
+
 Two things the atlas cannot reproduce:
   * glyph substitution.  A font that replaces a run of characters by another glyph -- Fira Code's ligatures, "fi", "<>", "->" -- draws
     that glyph under raqm layout; the atlas knows single characters and pairs' kerning only.  With an alphabet that holds such pairs
@@ -181,13 +186,71 @@ def text_weights(alphabet, by_code=None, floor_w=4096, gain=0, device=None):
     return cum, w
 
 
-def generate_codes(n, first_seed=42, max_length=100, device=None, out=None, rows=None, seed_rows=None, lens=None, cum=None, check_total=True):
+PAIR_SHAPE = (95, 94)                    # [context][letter]: context 0 = word start, context 1 + i = after code 33 + i
+
+
+def pair_errors(codes, per_pos, rows=None, by_pair=None):
+    """afr_op_pair_errors: char_errors' per-position records (per_pos [n, L + 1, 4], as CharErrors holds them) scattered into the table
+    by (preceding character, character) -> int64 [95, 94, 4] = {chars, pixels, sumsq, wrong} on the device; context 0 is "no letter
+    before" (position 0, after a space or any code outside 33..126), context 1 + i "after code 33 + i".  Sample j reads row rows[j]
+    (default j) of the int64 [N, L] codes, as char_errors did.  by_pair (default new and zero) is added to.  Nothing is read back."""
+    device = per_pos.device
+    codes = codes.to(device=device, dtype=torch.int64).contiguous()
+    if codes.dim() != 2 or not per_pos.is_cuda:
+        raise ValueError("codes must be int64 [N, L], per_pos a tensor on the device")
+    rows = _rows(rows, None, device, "rows")
+    n, L = codes.shape[0] if rows is None else rows.numel(), codes.shape[1]
+    if rows is not None and n and (int(rows.min()) < 0 or int(rows.max()) >= codes.shape[0]):
+        raise IndexError("rows outside codes")
+    if per_pos.dtype not in (torch.int32, torch.int64) or tuple(per_pos.shape) != (n, L + 1, 4):
+        raise ValueError(f"per_pos must be an int32 or int64 [{n}, {L + 1}, 4] tensor (char_errors' records)")
+    per_pos = per_pos.to(torch.int32).contiguous()                    # the uint32 words afr_op_sheet_char_errors stored
+    if by_pair is None:
+        by_pair = torch.zeros(PAIR_SHAPE + (4,), dtype=torch.int64, device=device)
+    if by_pair.dtype != torch.int64 or by_pair.device != device or not by_pair.is_contiguous() or tuple(by_pair.shape) != PAIR_SHAPE + (4,):
+        raise ValueError(f"by_pair must be a contiguous int64 [95, 94, 4] tensor on {device}")
+    if n:
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib().afr_op_pair_errors(_ptr(codes), L, _ptr(rows), n, _ptr(per_pos), _ptr(by_pair), _stream(device)))
+    return by_pair
+
+
+def pair_weights(alphabet, by_pair=None, floor_w=4096, gain=0, min_chars=0, device=None):
+    """afr_op_pair_weights: the table of the Markov text source, built on the device -> (cum2, w2), two int32 [95, 94] tensors holding
+    uint32 words.  alphabet as text_weights'; by_pair: pair_errors' int64 [95, 94, 4] table where it lies on the device, or None for
+    equal weights floor_w on every pair of members.  A pair weighs floor_w + gain * min(its mean squared error / the table's, 16), a
+    pair seen fewer than min_chars times as the average: synth.pair_weights in integers.  Nothing is read back."""
+    from . import synth
+    members = synth.alphabet_members(alphabet) if isinstance(alphabet, str) else [int(bool(m)) for m in alphabet]
+    words = (C.c_uint32 * 3)(*synth.members_words(members))
+    if by_pair is not None:
+        if by_pair.dtype != torch.int64 or tuple(by_pair.shape) != PAIR_SHAPE + (4,) or not by_pair.is_contiguous() or not by_pair.is_cuda:
+            raise ValueError("by_pair must be a contiguous int64 [95, 94, 4] tensor on the device")
+        device = by_pair.device
+    if device is None:
+        raise ValueError("pair_weights needs a device or a by_pair table")
+    if not 0 <= int(min_chars) <= 0xFFFFFFFF:
+        raise ValueError(f"min_chars {min_chars} must lie in 0..2^32 - 1")
+    device = torch.device(device)
+    cum2, w2 = torch.empty(PAIR_SHAPE, dtype=torch.int32, device=device), torch.empty(PAIR_SHAPE, dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _lib.check(_lib.lib().afr_op_pair_weights(_ptr(by_pair), words, int(floor_w), int(gain), int(min_chars), _ptr(cum2), _ptr(w2),
+                                                   _stream(device)))
+    return cum2, w2
+
+
+def generate_codes(n, first_seed=42, max_length=100, device=None, out=None, rows=None, seed_rows=None, lens=None, cum=None, check_total=True,
+                   cum2=None):
     """afr_op_dataset_text: the texts of synth.lcg_text(first_seed + seed, 10, max_length) as zero-padded int64 codes.  Sample j of n
     takes seed seed_rows[j] (default j) and goes to row rows[j] (default j) of out -- int64 [N, L >= max_length], default a new
     [n, max_length] -- and of lens (int32 [N], optional with out).  Returns (out, lens).  cum (text_weights' int32 [94] table on the
     device): afr_op_dataset_text_w instead, the texts of synth.lcg_text_weighted; a table whose total is 0 is a ValueError (the rows are
     zero-filled and flagged on the device; reading the flag waits for the launch, check_total=False leaves it unread -- for a table from
-    text_weights, whose total cannot be 0)."""
+    text_weights, whose total cannot be 0).  cum2 (pair_weights' int32 [95, 94] table on the device): afr_op_dataset_text_m, the texts of
+    synth.lcg_text_markov; a sample that reaches a context whose total is 0 is a ValueError in the same way.  cum and cum2 together is a
+    ValueError."""
+    if cum is not None and cum2 is not None:
+        raise ValueError("cum and cum2 together: a text is drawn from one table")
     if out is None:
         if rows is not None:
             raise ValueError("rows needs the buffer they are rows of (out)")
@@ -207,8 +270,16 @@ def generate_codes(n, first_seed=42, max_length=100, device=None, out=None, rows
         raise IndexError("rows outside out")
     if cum is not None and (cum.dtype != torch.int32 or cum.device != device or cum.numel() != 94 or not cum.is_contiguous()):
         raise ValueError(f"cum must be a contiguous int32 [94] tensor on {device} (text_weights' table)")
+    if cum2 is not None and (cum2.dtype != torch.int32 or cum2.device != device or tuple(cum2.shape) != PAIR_SHAPE or not cum2.is_contiguous()):
+        raise ValueError(f"cum2 must be a contiguous int32 [95, 94] tensor on {device} (pair_weights' table)")
     with torch.cuda.device(device):
-        if cum is None:
+        if cum2 is not None:
+            err = torch.zeros(1, dtype=torch.int32, device=device)
+            _lib.check(_lib.lib().afr_op_dataset_text_m(int(first_seed), _ptr(seed_rows), _ptr(rows), n, MIN_TEXT_LENGTH, int(max_length),
+                                                         _ptr(cum2), _ptr(out), out.shape[1], _ptr(lens), _ptr(err), _stream(device)))
+            if check_total and int(err) & 1:
+                raise ValueError("a text reached a context of the pair table whose total weight is 0")
+        elif cum is None:
             _lib.check(_lib.lib().afr_op_dataset_text(int(first_seed), _ptr(seed_rows), _ptr(rows), n, MIN_TEXT_LENGTH, int(max_length),
                                                        _ptr(out), out.shape[1], _ptr(lens), _stream(device)))
         else:

@@ -70,7 +70,18 @@ What is deliberately different from the reference, and why:
     atlas at this pen explains the predicted pixels best.  On the epochs that print a status line, one line headed "Read report:" with
     the share of characters read right, the share read blank and the k most frequent confusions as Q->O 312; epoch_<e>/confusion.tsv
     with every non-zero counter; and epoch_<e>/read_back.txt, each rendered test string beside what was read from it.  Nothing steps:
-    every other line and artefact is what it is without the variable.  Unset: nothing changes.
+    every other line and artefact is what it is without the variable.  Unset: nothing changes;
+  * AFR_PAIR_REPORT=<k> (k >= 1, needs AFR_DEVICE_DATA) adds a report of the rendering error by (preceding character, character),
+    counted on the device (devdata.char_errors' per-position records scattered by devdata.pair_errors): on the epochs that print a
+    status line, a block headed "Pair report:" with the k pairs of the alphabet seen at least 8 times that have the largest mean squared
+    level error, as 'W' after 'W' (or: after word start), and epoch_<e>/pair_errors.tsv with every non-zero record.  Nothing steps:
+    every other line and artefact is what it is without the variable.  Unset: nothing changes;
+  * AFR_STEER_PAIRS=<share> (0 <= share < 1, needs AFR_FRESH_DATA, not together with a non-zero AFR_STEER) steers the fresh texts by the
+    pairs' errors: every validation pass keeps the pair table, and the rewrite before the next epoch draws every letter given the letter
+    before it (afr_op_dataset_text_m) with weight floor_w + gain * min(the pair's mean squared error / the table's, 16), a pair seen
+    fewer than 8 times counting as average -- AFR_STEER's floor_w and gain, built on the device from the table where it lies
+    (afr_op_pair_weights).  The validation rows are never rewritten.  On the epochs that print a status line one more line names the
+    five heaviest pairs of the last rewrite.  Unset or 0: the run without it.
 """
 import contextlib
 import datetime
@@ -239,7 +250,46 @@ def _steer_from_env():
     return share
 
 
+def _pair_report_from_env():
+    """AFR_PAIR_REPORT = "<k>", k >= 1: the per-pair error report with the k worst pairs; unset or empty -> None (off).  Anything else,
+    or the report without AFR_DEVICE_DATA (no atlas, no owners), is a ValueError."""
+    spec = os.environ.get("AFR_PAIR_REPORT", "").strip()
+    if not spec:
+        return None
+    try:
+        k = int(spec)
+    except ValueError:
+        k = 0
+    if k < 1:
+        raise ValueError(f"AFR_PAIR_REPORT must be an integer >= 1 (the number of worst pairs to list), got {spec!r}")
+    if not os.environ.get("AFR_DEVICE_DATA", "").strip():
+        raise ValueError("AFR_PAIR_REPORT needs AFR_DEVICE_DATA: the glyph atlas the sheets are composed from defines which character owns a pixel")
+    return k
+
+
+def _steer_pairs_from_env():
+    """AFR_STEER_PAIRS = "<share>", a float in [0, 1): how much of a fresh letter's weight follows the error of its pair with the letter
+    before it; unset, empty or 0 -> 0.0 (off).  Anything else, a share without AFR_FRESH_DATA (nothing is redrawn), or a share together
+    with a non-zero AFR_STEER (a text is drawn from one table) is a ValueError."""
+    spec = os.environ.get("AFR_STEER_PAIRS", "").strip()
+    if not spec:
+        return 0.0
+    try:
+        share = float(spec)
+    except ValueError:
+        share = -1.0
+    if not 0.0 <= share < 1.0:
+        raise ValueError(f"AFR_STEER_PAIRS must be a share in [0, 1), e.g. 0.5, got {spec!r}")
+    if os.environ.get("AFR_FRESH_DATA", "").strip() != "1":
+        raise ValueError("AFR_STEER_PAIRS needs AFR_FRESH_DATA=1: only texts that are redrawn every epoch can be steered")
+    if share and _steer_from_env():
+        raise ValueError("AFR_STEER_PAIRS and AFR_STEER together: the fresh texts are drawn from one table, by character or by pair")
+    return share
+
+
 ALPHABET, STEER = _alphabet_from_env(), _steer_from_env()     # likewise read at import
+PAIR_REPORT, STEER_PAIRS = _pair_report_from_env(), _steer_pairs_from_env()     # likewise
+PAIR_MIN_CHARS = 8                                            # a pair seen fewer times is not listed, and is steered as the average
 STEER_UNIT = 4096                                             # floor_w + gain of the steered letter table: the weight of an average character
 
 
@@ -384,6 +434,52 @@ class _CharReport:
                     f.write("\t".join(["background", ""] + [str(v) for v in row]) + "\n")
                 elif row[1] > 0:
                     f.write("\t".join([str(c), chr(c) if 32 < c < 127 else ""] + [str(v) for v in row]) + "\n")
+
+
+class _PairReport:
+    """What AFR_PAIR_REPORT and AFR_STEER_PAIRS keep on the device during one validation pass: afr_op_pair_errors' table by (preceding
+    character, character), which every validation batch adds to -- devdata.char_errors with its per-position records on the batch's
+    rows of the bound codes and the evaluation's bitmaps, then devdata.pair_errors on the same rows."""
+
+    def __init__(self, k, atlas, codes, alphabet):
+        from . import devdata, synth
+        self.k, self.atlas, self.codes = int(k), atlas, codes
+        self.members = synth.alphabet_members(alphabet or "upper")
+        self.table = torch.zeros(devdata.PAIR_SHAPE + (4,), dtype=torch.int64, device=atlas.device)
+
+    def add(self, res, rows):
+        from . import devdata
+        if rows.numel():
+            per_pos = devdata.char_errors(self.atlas, self.codes, res.u8.contiguous(), res.u8.shape[1], res.u8.shape[2], rows=rows).per_pos
+            devdata.pair_errors(self.codes, per_pos, rows=rows, by_pair=self.table)
+
+    def all_reduce(self, dist):
+        dist.all_reduce(self.table, op=dist.ReduceOp.SUM)
+
+    @staticmethod
+    def name(p, c):
+        return f"{chr(33 + c)!r} after " + (f"{chr(32 + p)!r}" if p else "word start")
+
+    def lines(self):
+        t = self.table.tolist()
+        letters = [i for i, m in enumerate(self.members) if m]
+        seen = [(p, c) for p in [0] + [1 + i for i in letters] for c in letters if t[p][c][0] >= PAIR_MIN_CHARS and t[p][c][1] > 0]
+        out = [f"Pair report: {len(seen)} pairs seen {PAIR_MIN_CHARS} times or more"]
+        for p, c in sorted(seen, key=lambda e: (-(t[e[0]][e[1]][2] / t[e[0]][e[1]][1]), e))[:self.k]:
+            chars, pixels, sumsq, wrong = t[p][c]
+            out.append(f"  {self.name(p, c)}: rms level error {float(np.sqrt(sumsq / pixels)):.4f}, wrong ink {wrong / pixels:.6f}, chars {chars}")
+        return out
+
+    def write_tsv(self, path):
+        t = self.table.tolist()
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            f.write("prev\tprev_char\tcode\tchar\tchars\tpixels\tsumsq\twrong\n")
+            for p, row in enumerate(t):
+                for c, rec in enumerate(row):
+                    if any(rec):
+                        f.write("\t".join(["" if p == 0 else str(32 + p), "" if p == 0 else chr(32 + p), str(33 + c), chr(33 + c)]
+                                          + [str(v) for v in rec]) + "\n")
 
 
 class _ReadReport:
@@ -755,7 +851,7 @@ def _batch_calls(eng, stepper, inputs, targets, rows):
 
 
 def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True, report=None, treport=None, creport=None,
-               rreport=None):
+               rreport=None, preport=None):
     """One epoch of the reference loop (model.py:288-333): the training pass over order.train_epoch(), then the validation
     pass; returns the two means of per-batch mean losses.  An engine that keeps a weight EMA validates from it.  by_rows: the engine has the data set bound (Engine.bind_dataset)
     and every step is driven by this rank's slice of the epoch's index vector -- the kernels read the rows where they lie.
@@ -765,7 +861,8 @@ def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, wor
     snapshotted before the last training batch and compared after it, and once the validation loss has been read the first training
     batch is run once more as a probe for its gradients.  creport: a _CharReport (AFR_CHAR_REPORT, AFR_STEER): every validation batch's bitmaps --
     of the one evaluation it shares with report -- are measured against the sheets the atlas composes for the batch's rows.  rreport: a
-    _ReadReport (AFR_READ_REPORT): the same bitmaps are read back against the atlas's glyphs."""
+    _ReadReport (AFR_READ_REPORT): the same bitmaps are read back against the atlas's glyphs.  preport: a _PairReport (AFR_PAIR_REPORT,
+    AFR_STEER_PAIRS): the same bitmaps once more, charged by (preceding character, character)."""
     from .parallel import shard_rows
     eng = model.engine
     pixels = targets[0].numel()
@@ -797,19 +894,23 @@ def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, wor
             mine = rows[shard_rows(rows.numel(), rank, world)]
             calls = _batch_calls(eng, None, *dense, mine)
             calls.forward(training=False, want_output=False)
-            if report is not None or creport is not None or rreport is not None:
-                res = calls.evaluate_last(want_u8=creport is not None or rreport is not None)
+            if report is not None or creport is not None or rreport is not None or preport is not None:
+                res = calls.evaluate_last(want_u8=creport is not None or rreport is not None or preport is not None)
                 if report is not None:
                     report.add(res, mine)
                 if creport is not None:
                     creport.add(res, mine)
                 if rreport is not None:
                     rreport.add(res, mine)
+                if preport is not None:
+                    preport.add(res, mine)
             calls.loss_grad(mean_elems=rows.numel() * pixels)
         if creport is not None and world > 1:
             creport.all_reduce(_dist()[0])
         if rreport is not None and world > 1:
             rreport.all_reduce(_dist()[0])
+        if preport is not None and world > 1:
+            preport.all_reduce(_dist()[0])
         if report is not None:
             if world > 1:
                 report.all_reduce(_dist()[0])
@@ -821,27 +922,32 @@ def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, wor
     return avg_train_loss, avg_val_loss
 
 
-def _fresh_rows(atlas, n, alphabet=None, steer=0.0):
-    """AFR_FRESH_DATA: refresh(epoch, rows, inputs, targets, by_code=None) rewrites rows `rows` of the bound codes and sheets in place, on
+def _fresh_rows(atlas, n, alphabet=None, steer=0.0, steer_pairs=0.0):
+    """AFR_FRESH_DATA: refresh(epoch, rows, inputs, targets, by_code=None, by_pair=None) rewrites rows `rows` of the bound codes and sheets in place, on
     the current stream: row r becomes the text of seed DATA_FIRST_SEED + epoch * n + r, as long as a row of inputs is wide at the most, and
     its sheet.  alphabet (AFR_ALPHABET) or steer (AFR_STEER) take the texts from the weighted source: equal weights over the alphabet
     (A-Z without one), or -- given by_code, the by-code table of the last validation pass -- _steer_weights(steer) of it.  The table, the
     letter weights and the texts follow one another on the stream: nothing is read back.  refresh.w and refresh.by_code hold the last
-    rewrite's weights and the table they were built from."""
+    rewrite's weights and the table they were built from.  steer_pairs (AFR_STEER_PAIRS) with by_pair, the pair table of the last
+    validation pass: the texts come from the Markov source instead, _steer_weights(steer_pairs) of the pairs' errors with
+    PAIR_MIN_CHARS; refresh.w2 and refresh.by_pair then hold the last rewrite's pair weights and their table."""
     from . import devdata, synth
-    members = synth.alphabet_members(alphabet or "upper") if alphabet or steer else None
+    members = synth.alphabet_members(alphabet or "upper") if alphabet or steer or steer_pairs else None
 
-    def refresh(epoch, rows, inputs, targets, by_code=None):
+    def refresh(epoch, rows, inputs, targets, by_code=None, by_pair=None):
         rows = rows.to(device)
-        cum = None
-        if members is not None:
+        cum = cum2 = None
+        if steer_pairs and by_pair is not None:
+            cum2, refresh.w2 = devdata.pair_weights(members, by_pair, *_steer_weights(steer_pairs), min_chars=PAIR_MIN_CHARS, device=device)
+            refresh.by_pair = by_pair
+        elif members is not None:
             floor_w, gain = _steer_weights(steer) if by_code is not None else (STEER_UNIT, 0)
             cum, refresh.w = devdata.text_weights(members, by_code, floor_w, gain, device=device)
             refresh.by_code = by_code
         devdata.generate_codes(rows.numel(), DATA_FIRST_SEED, max_length=inputs.shape[1], out=inputs, rows=rows, seed_rows=epoch * n + rows, cum=cum,
-                               check_total=False)
+                               cum2=cum2, check_total=False)
         devdata.compose_sheets(atlas, inputs.index_select(0, rows), targets.shape[1], targets.shape[2], out=targets, rows=rows)
-    refresh.w = refresh.by_code = None
+    refresh.w = refresh.by_code = refresh.w2 = refresh.by_pair = None
     return refresh
 
 
@@ -850,6 +956,14 @@ def _steer_line(share, w, k=5):
     w = w.tolist()
     top = sorted((i for i in range(len(w)) if w[i]), key=lambda i: (-w[i], i))[:k]
     return f"Steer: share {share:g}, heaviest {len(top)} codes " + ", ".join(f"{33 + i} {chr(33 + i)!r} x{w[i] / STEER_UNIT:.2f}" for i in top)
+
+
+def _steer_pairs_line(share, w2, k=5):
+    """The status line of AFR_STEER_PAIRS, read from the pair weights of the last rewrite (int32 [95, 94] on the device): the one host
+    read pair steering adds."""
+    w2 = w2.tolist()
+    top = sorted(((p, c) for p in range(len(w2)) for c in range(len(w2[p])) if w2[p][c]), key=lambda e: (-w2[e[0]][e[1]], e))[:k]
+    return f"Steer pairs: share {share:g}, heaviest {len(top)} pairs " + ", ".join(f"{_PairReport.name(p, c)} x{w2[p][c] / STEER_UNIT:.2f}" for p, c in top)
 
 
 def train_attention_model(model, dataset, batch_size, refresh=None, atlas=None):
@@ -895,13 +1009,24 @@ def train_attention_model(model, dataset, batch_size, refresh=None, atlas=None):
                 f.write(f"steer = {STEER:g}\n")
             if READ_REPORT:                     # likewise
                 f.write(f"read_report = {READ_REPORT}\n")
+            if PAIR_REPORT:                     # likewise
+                f.write(f"pair_report = {PAIR_REPORT}\n")
+            if STEER_PAIRS:                     # likewise
+                f.write(f"steer_pairs = {STEER_PAIRS:g}\n")
     if CHAR_REPORT and atlas is None:
         raise ValueError("the character report needs the glyph atlas the data set was composed from (AFR_DEVICE_DATA)")
     if READ_REPORT and atlas is None:
         raise ValueError("the read-back report needs the glyph atlas the data set was composed from (AFR_DEVICE_DATA)")
     if STEER and (atlas is None or refresh is None):
         raise ValueError("steering needs the glyph atlas and the fresh-data rewrite (AFR_DEVICE_DATA, AFR_FRESH_DATA)")
+    if PAIR_REPORT and atlas is None:
+        raise ValueError("the pair report needs the glyph atlas the data set was composed from (AFR_DEVICE_DATA)")
+    if STEER_PAIRS and (atlas is None or refresh is None):
+        raise ValueError("pair steering needs the glyph atlas and the fresh-data rewrite (AFR_DEVICE_DATA, AFR_FRESH_DATA)")
+    if STEER_PAIRS and STEER:
+        raise ValueError("AFR_STEER_PAIRS and AFR_STEER together: the fresh texts are drawn from one table")
     strings = test_strings + _extra_test_strings(ALPHABET)
+    pair_table = None                           # AFR_STEER_PAIRS: the pair table the last validation pass left on the device
     steer_table = None                          # AFR_STEER: the by-code table the last validation pass left on the device
 
     order = _EpochOrder(len(dataset))
@@ -936,13 +1061,18 @@ def train_attention_model(model, dataset, batch_size, refresh=None, atlas=None):
         char_lines = bool(CHAR_REPORT) and epoch % 5 == 0
         creport = _CharReport(CHAR_REPORT or 1, atlas, inputs) if char_lines or STEER else None      # steering keeps the table every epoch
         rreport = _ReadReport(READ_REPORT, atlas, inputs, ALPHABET) if READ_REPORT and epoch % 5 == 0 else None
+        pair_lines = bool(PAIR_REPORT) and epoch % 5 == 0
+        preport = _PairReport(PAIR_REPORT or 1, atlas, inputs, ALPHABET) if pair_lines or STEER_PAIRS else None      # likewise
         if refresh is not None and epoch >= 1:
-            refresh(epoch, order.train_idx, inputs, targets, **(dict(by_code=steer_table) if STEER else {}))
+            refresh(epoch, order.train_idx, inputs, targets, **(dict(by_code=steer_table) if STEER else {}),
+                    **(dict(by_pair=pair_table) if STEER_PAIRS else {}))
         avg_train_loss, avg_val_loss = _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True, report=report,
-                                                  treport=treport, creport=creport, rreport=rreport)
+                                                  treport=treport, creport=creport, rreport=rreport, **(dict(preport=preport) if preport else {}))
 
         if STEER:
             steer_table = creport.table
+        if STEER_PAIRS:
+            pair_table = preport.table
         scheduler.step(avg_val_loss)
         is_best = avg_val_loss < best_val_loss
         if is_best:
@@ -972,6 +1102,11 @@ def train_attention_model(model, dataset, batch_size, refresh=None, atlas=None):
                     creport.write_tsv(f"{OUTPUT_DIR}/epoch_{epoch}/char_errors.tsv")
                 if STEER and refresh.w is not None:
                     print(_steer_line(STEER, refresh.w))
+                if pair_lines:
+                    print("\n".join(preport.lines()))
+                    preport.write_tsv(f"{OUTPUT_DIR}/epoch_{epoch}/pair_errors.tsv")
+                if STEER_PAIRS and refresh.w2 is not None:
+                    print(_steer_pairs_line(STEER_PAIRS, refresh.w2))
                 if rreport is not None:
                     print(rreport.line())
                     rreport.write_tsv(f"{OUTPUT_DIR}/epoch_{epoch}/confusion.tsv")
@@ -1016,7 +1151,7 @@ def train_string_renderer():
         print(f"Composing {NUM_SAMPLES} samples on {device} from a glyph atlas of {DEVICE_DATA}...")
         dataset = devdata.reference_dataset(NUM_SAMPLES, atlas, DATA_FIRST_SEED, MAX_CHARS_PER_SHEET, SHEET_HEIGHT, SHEET_WIDTH, alphabet=ALPHABET)
         if FRESH_DATA:
-            refresh = _fresh_rows(atlas, NUM_SAMPLES, ALPHABET, STEER)
+            refresh = _fresh_rows(atlas, NUM_SAMPLES, ALPHABET, STEER, *((STEER_PAIRS,) if STEER_PAIRS else ()))
     else:
         dataset = load_string_dataset(data_dir="train_input", num_samples=NUM_SAMPLES, sheet_height=SHEET_HEIGHT,
                                       sheet_width=SHEET_WIDTH)

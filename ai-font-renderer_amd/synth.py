@@ -171,6 +171,92 @@ def lcg_text_weighted(seed, cum, min_length=10, max_length=100):
     return "".join(out)
 
 
+# ---------------------------------------------------------------- Markov text (afr_op_dataset_text_m, afr_op_pair_weights)
+TEXT_CONTEXTS = TEXT_CODES + 1           # row 0: the start of a word; row 1 + i: after code 33 + i
+
+
+def pair_table(w2):
+    """Any 95 x 94 table of non-negative integer weights (w2[context][letter]) -> cum2, the 95 lists of inclusive cumulative weights
+    afr_op_dataset_text_m draws from.  A negative weight, another shape, or a row total above 2^32 - 1 is a ValueError."""
+    rows = [[int(x) for x in row] for row in w2]
+    if len(rows) != TEXT_CONTEXTS or any(len(row) != TEXT_CODES for row in rows):
+        raise ValueError(f"w2: {TEXT_CONTEXTS} rows of {TEXT_CODES} weights")
+    cum2 = []
+    for r, row in enumerate(rows):
+        total, cum = 0, []
+        for x in row:
+            if x < 0:
+                raise ValueError(f"w2: a negative weight in row {r}")
+            total += x
+            cum.append(total)
+        if total > 0xFFFFFFFF:
+            raise ValueError(f"w2: row {r} sums to {total}, above 2^32 - 1")
+        cum2.append(cum)
+    return cum2
+
+
+def pair_weights(by_pair, members, floor_w, gain, min_chars):
+    """Twin of afr_op_pair_weights in Python integers -> (cum2, w2), two lists of 95 lists of 94.  by_pair: [context][letter] =
+    {chars, pixels, sumsq, wrong} (afr_op_pair_errors' table; only the records of live pairs are read) or None; members: the 94 flags."""
+    if len(members) != TEXT_CODES or not any(members):
+        raise ValueError("members: 94 flags, at least one set")
+    if not 1 <= floor_w <= 65535 or not 0 <= gain <= 65535:
+        raise ValueError(f"floor_w {floor_w} must lie in 1..65535, gain {gain} in 0..65535")
+    if min_chars < 0:
+        raise ValueError(f"min_chars {min_chars} must not be negative")
+    letters = [i for i in range(TEXT_CODES) if members[i]]
+    live = [(p, c) for p in [0] + [1 + i for i in letters] for c in letters]
+    P = S = 0
+    if by_pair is not None and gain:
+        P, S = sum(int(by_pair[p][c][1]) for p, c in live), sum(int(by_pair[p][c][2]) for p, c in live)
+    w2 = [[0] * TEXT_CODES for _ in range(TEXT_CONTEXTS)]
+    if S == 0:
+        for p, c in live:
+            w2[p][c] = floor_w
+    else:
+        k = max(0, S.bit_length() - 47)
+        m_ref = max(1, ((S >> k) << 16) // max(1, P >> k))
+        for p, c in live:
+            chars, pixels, sumsq = int(by_pair[p][c][0]), int(by_pair[p][c][1]) >> k, int(by_pair[p][c][2]) >> k
+            rel = REL_ONE if pixels == 0 or chars < min_chars else min((((sumsq << 16) // pixels) << 16) // m_ref, REL_CAP)
+            w2[p][c] = floor_w + ((gain * rel) >> 16)
+    return pair_table(w2), w2
+
+
+def lcg_text_markov(seed, cum2, min_length=10, max_length=100):
+    """Twin of afr_op_dataset_text_m: lcg_text_weighted with one row of cumulative weights per context -- cum2[0] at the start of every
+    word, cum2[1 + i] after letter i.  Reaching a row whose total is 0 is a ValueError (the device zero-fills the sample and flags it)."""
+    import bisect
+    cum2 = [[int(c) for c in row] for row in cum2]
+    if len(cum2) != TEXT_CONTEXTS or any(len(row) != TEXT_CODES for row in cum2):
+        raise ValueError(f"cum2: {TEXT_CONTEXTS} rows of {TEXT_CODES} inclusive cumulative weights")
+    state = int(seed) % 4294967296
+
+    def draw(k):
+        nonlocal state
+        state = (state * 1664525 + 1013904223) % 4294967296
+        return (state * k) >> 32
+
+    length = draw(max_length - min_length + 1) + min_length
+    out = []
+    remaining = length
+    while remaining > 0:
+        wl = min(draw(10) + 1, remaining)
+        ctx = 0
+        for _ in range(wl):
+            row = cum2[ctx]
+            if row[-1] == 0:
+                raise ValueError(f"cum2: the text of seed {seed} reaches context {ctx}, whose total weight is 0")
+            i = bisect.bisect_right(row, draw(row[-1]))
+            out.append(chr(TEXT_FIRST + i))
+            ctx = 1 + i
+        remaining -= wl
+        if remaining > 0:
+            out.append(" ")
+            remaining -= 1
+    return "".join(out)
+
+
 def dataset_strings(n, first_seed=42):
     """Sample i (0-based) of the reference dataset uses seed i+42 (generate_font.ts:204)."""
     return [lcg_text(first_seed + i) for i in range(n)]

@@ -683,6 +683,56 @@ int afr_op_text_weights(const uint64_t* by_code /* device [n_codes + 1][5] as af
                         uint32_t floor_w /* 1..65535 */, uint32_t gain /* 0..65535 */,
                         uint32_t* cum /* device [94] */, uint32_t* w /* device [94] or NULL */, void* stream);
 
+/* ---- the text source with context: a first-order Markov chain over the codes 33..126, an error table by (preceding character,
+ * character), and the launch that builds the chain's table from the error table on the device.  Plain ops, integers only.  A CONTEXT
+ * is one of 95 rows: row 0 = no letter before (the start of a word), row 1 + i = after letter i (code 33 + i).
+ *   dataset_text_m afr_op_dataset_text_w in every respect -- seed, row mapping, length draw, word-length draw, single spaces, zero
+ *                  fill, len, 64-bit row addressing -- but the letter.  cum2: device uint32 [95][94], per context the inclusive
+ *                  cumulative weights, non-decreasing within a row.  Every word starts in context 0; after letter i is drawn the
+ *                  context is row 1 + i.  A letter: the LCG update, r = (state * total) >> 32 with total = cum2[ctx][93], then the
+ *                  smallest i with cum2[ctx][i] > r.  A sample that reaches a context whose total is 0 (row 0 included) is
+ *                  zero-filled over its whole row, gets len[r] = 0 and sets bit 0 of *err (device word, or NULL); a zero row no
+ *                  sample reaches sets nothing.  If every row of cum2 equals one cum the texts are afr_op_dataset_text_w's byte for
+ *                  byte, from the same draws.  The table is read into LDS once per workgroup (95 rows padded to 128 entries).
+ *   pair_errors    sample j of n reads row r = code_rows ? code_rows[j] : j of codes int64
+ *                  [rows][ldx] and row j of per_pos uint32 [n][ldx + 1][4] = {pixels, sumsq, off2, wrong} as
+ *                  afr_op_sheet_char_errors leaves it (slot ldx, the background, is not read).  Position i CONTRIBUTES when its code
+ *                  c lies in 33..126 and its record's pixels > 0.  Its context is row 1 + (p - 33) if the code p at position i - 1
+ *                  lies in 33..126, and row 0 otherwise: position 0, a preceding space, any other preceding code.  (A wrapped line
+ *                  breaks at a space, so the text's predecessor is the line's; the layout is not run again.)
+ *                  by_pair: device uint64 [95][94][4] = {chars, pixels, sumsq, wrong}, ADDED to, the caller zeroes it; a
+ *                  contributing position adds {1, pixels, sumsq, wrong} to [context][c - 33].  Integer adds only: the table does
+ *                  not depend on their order and repeats bit for bit.  A workgroup sums a band of 12 contexts over its chunk of
+ *                  samples in LDS and issues one 64-bit global integer atomic per non-zero counter.
+ *   pair_weights   one workgroup.  members (HOST, three words) as text_weights'.  A pair (p, c) is LIVE when c is a member and p is
+ *                  row 0 or a member's row.  by_pair as pair_errors leaves it, or NULL; only the records of live pairs are read.
+ *                  In integers, with P = the sum of pixels and S = the sum of sumsq over all live pairs (each must fit 64 bits):
+ *                    by_pair NULL, gain == 0 or S == 0:  w = floor_w for every live pair;
+ *                    otherwise  k = max(0, bit_length(S) - 47) and P, S and every pixels, sumsq are shifted right by k,
+ *                               m_ref = max(1, (S << 16) / max(1, P))   -- one reference mean for the whole table,
+ *                               rel   = 1 << 16 for a live pair with pixels == 0 (after the shift) or chars < min_chars (chars is
+ *                                       not shifted): too little evidence counts as average, else
+ *                               rel   = min((((sumsq << 16) / pixels) << 16) / m_ref, 16 << 16),
+ *                               w     = floor_w + ((gain * rel) >> 16);
+ *                  pairs that are not live get w = 0, so the rows of non-member contexts are all zero -- and never reached, since
+ *                  only members are drawn.  cum2 (device uint32 [95][94]) = the inclusive sums of w along each row, w2 (device
+ *                  uint32 [95][94], or NULL) the weights themselves.  A row's total is below 2^27.  No atomics: the words repeat.
+ * Errors, before anything is launched: dataset_text_m -- everything afr_op_dataset_text_w refuses, with cum2 in the place of cum;
+ * pair_errors -- codes, per_pos or by_pair NULL, codes, code_rows or by_pair not 8-byte aligned, per_pos not 16-byte aligned, n < 1,
+ * ldx < 1 -> AFR_EINVAL, ldx > 256 -> AFR_EUNSUPPORTED; pair_weights -- members or cum2 NULL, an empty member set, member bits above
+ * bit 93, floor_w outside 1..65535, gain above 65535, by_pair not 8-byte or cum2, w2 not 4-byte aligned -> AFR_EINVAL. */
+#define AFR_TEXT_CONTEXTS 95   /* row 0 = word start, row 1 + i = after code 33 + i */
+int afr_op_dataset_text_m(int64_t first_seed, const int64_t* seed_rows, const int64_t* out_rows, int64_t n, int min_len, int max_len,
+                          const uint32_t* cum2 /* device [95][94], inclusive cumulative weights per context */,
+                          int64_t* codes, int ldx, int32_t* len /* or NULL */, uint32_t* err /* or NULL */, void* stream);
+int afr_op_pair_errors(const int64_t* codes, int ldx, const int64_t* code_rows /* or NULL */, int64_t n,
+                       const uint32_t* per_pos /* device [n][ldx + 1][4] as afr_op_sheet_char_errors leaves it */,
+                       uint64_t* by_pair /* device [95][94][4], ADDED to */, void* stream);
+int afr_op_pair_weights(const uint64_t* by_pair /* device [95][94][4] as afr_op_pair_errors leaves it, or NULL */,
+                        const uint32_t members[3] /* host: bit i = code 33 + i is in the alphabet */,
+                        uint32_t floor_w /* 1..65535 */, uint32_t gain /* 0..65535 */, uint32_t min_chars,
+                        uint32_t* cum2 /* device [95][94] */, uint32_t* w2 /* device [95][94] or NULL */, void* stream);
+
 /* ---- rendering error attributed to characters: one launch that lays a text out exactly as compose_sheets does and measures a
  * prediction against the sheet compose_sheets would draw, pixel by pixel, charging every pixel to the character that owns it.  A
  * plain op: no plan, nothing allocated, one workgroup per sheet under compose's grid cap; integers only, so the result repeats
