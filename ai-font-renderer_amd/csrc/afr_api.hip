@@ -2822,7 +2822,7 @@ extern "C" int afr_op_sheet_read_back(const afr_glyph_atlas* atlas, const afr_sh
 extern "C" int afr_op_f32_to_fp8(const float* src, void* dst, int64_t n, float scale, void* stream) {
     if (!src || !dst || n < 0 || !(scale > 0.f)) return fail(AFR_EINVAL, "bad f32 -> fp8 arguments");
     DevGuard dg(device_of(dst));
-    HIPCHK(afr_launch_f32_to_fp8(src, (unsigned char*)dst, n, 1.f / scale, (hipStream_t)stream));
+    HIPCHK(afr_launch_f32_to_fp8(src, (unsigned char*)dst, n, scale, (hipStream_t)stream));
     return AFR_OK;
 }
 extern "C" int afr_op_gemm_fp8(int flags, const void* A, const void* B, void* C, const float* bias, int M, int N, int K, int lda, int ldb,

@@ -306,7 +306,7 @@ constexpr uint32_t AFR_ERR_INDEX = 1u, AFR_ERR_COOP_TIMEOUT = 2u, AFR_ERR_ROW = 
 hipError_t afr_launch_gemm(int dtype, const GemmParams& p, hipStream_t s);
 void afr_gemm_tile_launch_shape(int dtype, const GemmParams& p, int* tiles, int* threads);   // of a product on the ring / tile kernels
 hipError_t afr_launch_gemm_fp8(const GemmParams& p, hipStream_t s);          // e4m3 x e4m3, both k-contiguous (gemm.hip fp8k)
-hipError_t afr_launch_f32_to_fp8(const float* src, unsigned char* dst, long long n, float inv_scale, hipStream_t s);
+hipError_t afr_launch_f32_to_fp8(const float* src, unsigned char* dst, long long n, float scale, hipStream_t s);
 // several independent products in one launch (falls back to one launch each when one of them does not qualify)
 bool afr_gemm_groupable(int dtype, const GemmParams& p);
 hipError_t afr_launch_gemm_group(int dtype, const GemmParams* ps, int n, int tile256, hipStream_t s);

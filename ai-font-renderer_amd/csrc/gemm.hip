@@ -1965,7 +1965,7 @@ __global__ __launch_bounds__(512) void glyph_l1_bwd_fused_kernel(L1BwdArgs a) {
 // Geometry = the 256x128 ring kernel's: 8 waves of 64x64, three LDS stages of 3 x 16 KiB filled by LDS-DMA; a sub-tile row is
 // 128 BYTES = 128 k here (64 k in bf16), so one K-tile is one MFMA k-step: a wave's 16 MFMAs (32 cycles each) per 48 KiB
 // staged, the same matrix-pipe time per staged byte as bf16 at twice the FLOPs.  Operand k order inside an MFMA is free as
-// long as A and B agree (probed with exact integer data): lane (r = lane & 15, q = lane >> 4) takes bytes 32 q .. 32 q + 31 of
+// long as A and B agree (exact integer data: the position cases of tests/test_gpu_fp8_ops.py): lane (r = lane & 15, q = lane >> 4) takes bytes 32 q .. 32 q + 31 of
 // row r for both.  One barrier per K-tile; the next tile's fragment reads and the refill of the slot just consumed are issued
 // under the current tile's MFMAs (two register sets of fragments, loop unrolled by two).
 namespace fp8k {

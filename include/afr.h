@@ -955,11 +955,23 @@ int afr_op_transpose_bf16(const float* W, void* WT, int N, int K, void* stream);
 
 /* ---- fp8 building blocks of BASELINE configs[4] ("fp8 MFMA weights on CDNA4"; no counterpart in the reference) ----
  * Operands are OCP e4m3fn bytes (gfx950's native fp8: exponent bias 7, largest finite 448, no infinities) with ONE float
- * scale per tensor: value = scale * e4m3.  afr_op_f32_to_fp8: dst[i] = e4m3(src[i] / scale), round to nearest even,
- * saturating.  afr_op_gemm_fp8: C[m][n] = scale_ab * sum_k A[m*lda+k] * B[n*ldb+k] (+bias[n]) (relu), f32 accumulation on
+ * scale per tensor: value = scale * e4m3.  afr_op_f32_to_fp8: dst[i] = e4m3(src[i] / scale) -- the quotient is the correctly
+ * rounded float32 division (NOT src[i] * (1.f / scale), another float32 that rounds to another byte next to a tie), rounded to
+ * the nearest e4m3 value, ties to the even code; saturating: every quotient beyond +-448, the infinities included, gives the
+ * largest finite value of its sign (0x7E / 0xFE); a NaN stays a NaN (byte & 0x7F == 0x7F) and never becomes a finite operand;
+ * a quotient that rounds to zero may keep either sign.  Byte-equal to torch's float8_e4m3fn cast of the clamped quotient.
+ * Errors (checked before a device is touched): src or dst NULL, n < 0, scale not > 0 (0, negative, NaN) -> AFR_EINVAL.
+ * afr_op_gemm_fp8: C[m][n] = scale_ab * sum_k A[m*lda+k] * B[n*ldb+k] (+bias[n]) (relu), f32 accumulation on
  * the MX-scaled matrix instruction (v_mfma_scale_f32_16x16x128_f8f6f4, unit block scales: fp8 at twice the bf16 rate),
  * C f32 or bf16 (AFR_GEMM_OUT_BF16); both operands k-contiguous (the forward form x . W^T), K, lda, ldb multiples of 16,
- * N and ldc multiples of 8.  flags: AFR_GEMM_BIAS | AFR_GEMM_RELU | AFR_GEMM_OUT_BF16. */
+ * N and ldc multiples of 8.  flags: AFR_GEMM_BIAS | AFR_GEMM_RELU | AFR_GEMM_OUT_BF16.  A is read at [0, M) x [0, K) through lda,
+ * B at [0, N) x [0, K) through ldb, C written at [0, M) x [0, N) through ldc and nowhere else; scale_ab multiplies the sum first,
+ * then the bias is added, then the ReLU taken, then a bf16 output rounded to nearest even: the AFR_GEMM_OUT_BF16 launch leaves the
+ * f32 launch's values rounded, the AFR_GEMM_RELU launch max(the launch without it, +0), bit for bit.  Integer-valued operands whose
+ * partial sums stay below 2^11 give the exact sum.  Errors, in this order and before a device is touched: A, B or C NULL, an
+ * extent <= 0 -> AFR_EINVAL; any other flag (AFR_GEMM_RELU_MASK, AFR_GEMM_A_KSTRIDED, AFR_GEMM_B_KSTRIDED) -> AFR_EUNSUPPORTED;
+ * AFR_GEMM_BIAS with bias NULL -> AFR_EINVAL; K, lda, ldb not multiples of 16 or N, ldc not multiples of 8 -> AFR_EUNSUPPORTED; an
+ * operand of 2 GiB or more (M * lda or N * ldb >= 2^31) -> AFR_EUNSUPPORTED. */
 int afr_op_f32_to_fp8(const float* src, void* dst_e4m3, int64_t n, float scale, void* stream);
 int afr_op_gemm_fp8(int flags, const void* A, const void* B, void* C, const float* bias, int M, int N, int K, int lda, int ldb,
                     int ldc, float scale_ab, void* stream);
