@@ -2632,66 +2632,67 @@ extern "C" int afr_op_f32_to_bf16(const float* src, void* dst, int64_t n, void* 
     HIPCHK(afr_launch_f32_to_bf16(src, (bf16_t*)dst, n, (hipStream_t)stream));
     return AFR_OK;
 }
+// What the three afr_op_dataset_text* entries refuse alike: `table` is the entry's letter table under its name (cum / cum2), both null for
+// the entry without one, which then has no err word either.  -> AFR_OK or the failure, already recorded.
+static int text_args_check(const char* who, const int64_t* seed_rows, const int64_t* out_rows, int64_t n, int min_len, int max_len,
+                           const char* table_name, const uint32_t* table, const int64_t* codes, int ldx, const int32_t* len, const uint32_t* err) {
+    if (!codes || (table_name && !table))
+        return table_name ? fail(AFR_EINVAL, "%s: codes or %s is null", who, table_name) : fail(AFR_EINVAL, "%s: codes is null", who);
+    if (n < 1) return fail(AFR_EINVAL, "%s: n = %lld, must be >= 1", who, (long long)n);
+    if (ldx < 1) return fail(AFR_EINVAL, "%s: ldx = %d, must be positive", who, ldx);
+    if (ldx > CMP_MAX_LDX) return fail(AFR_EUNSUPPORTED, "%s: ldx = %d, at most %d codes per row", who, ldx, CMP_MAX_LDX);
+    if (min_len < 1 || max_len < min_len || max_len > ldx)
+        return fail(AFR_EINVAL, "%s: text lengths %d..%d must satisfy 1 <= min_len <= max_len <= ldx = %d", who, min_len, max_len, ldx);
+    if (((uintptr_t)codes & 7) || ((uintptr_t)seed_rows & 7) || ((uintptr_t)out_rows & 7) || ((uintptr_t)len & 3) || ((uintptr_t)table & 3) ||
+        ((uintptr_t)err & 3))
+        return table_name ? fail(AFR_EINVAL, "%s: codes, seed_rows and out_rows must be 8-byte aligned, %s, len and err 4-byte", who, table_name)
+                          : fail(AFR_EINVAL, "%s: codes, seed_rows and out_rows must be 8-byte aligned, len 4-byte", who);
+    return AFR_OK;
+}
 extern "C" int afr_op_dataset_text(int64_t first_seed, const int64_t* seed_rows, const int64_t* out_rows, int64_t n, int min_len, int max_len,
                                    int64_t* codes, int ldx, int32_t* len, void* stream) {
-    if (!codes) return fail(AFR_EINVAL, "afr_op_dataset_text: codes is null");
-    if (n < 1) return fail(AFR_EINVAL, "afr_op_dataset_text: n = %lld, must be >= 1", (long long)n);
-    if (ldx < 1) return fail(AFR_EINVAL, "afr_op_dataset_text: ldx = %d, must be positive", ldx);
-    if (ldx > CMP_MAX_LDX) return fail(AFR_EUNSUPPORTED, "afr_op_dataset_text: ldx = %d, at most %d codes per row", ldx, CMP_MAX_LDX);
-    if (min_len < 1 || max_len < min_len || max_len > ldx)
-        return fail(AFR_EINVAL, "afr_op_dataset_text: text lengths %d..%d must satisfy 1 <= min_len <= max_len <= ldx = %d", min_len, max_len, ldx);
-    if (((uintptr_t)codes & 7) || ((uintptr_t)seed_rows & 7) || ((uintptr_t)out_rows & 7) || ((uintptr_t)len & 3))
-        return fail(AFR_EINVAL, "afr_op_dataset_text: codes, seed_rows and out_rows must be 8-byte aligned, len 4-byte");
+    if (const int rc = text_args_check("afr_op_dataset_text", seed_rows, out_rows, n, min_len, max_len, nullptr, nullptr, codes, ldx, len, nullptr))
+        return rc;
     DevGuard dg(device_of(codes));
     HIPCHK(afr_launch_dataset_text(first_seed, seed_rows, out_rows, n, min_len, max_len, codes, ldx, len, (hipStream_t)stream));
     return AFR_OK;
 }
 extern "C" int afr_op_dataset_text_w(int64_t first_seed, const int64_t* seed_rows, const int64_t* out_rows, int64_t n, int min_len, int max_len,
                                      const uint32_t* cum, int64_t* codes, int ldx, int32_t* len, uint32_t* err, void* stream) {
-    if (!codes || !cum) return fail(AFR_EINVAL, "afr_op_dataset_text_w: codes or cum is null");
-    if (n < 1) return fail(AFR_EINVAL, "afr_op_dataset_text_w: n = %lld, must be >= 1", (long long)n);
-    if (ldx < 1) return fail(AFR_EINVAL, "afr_op_dataset_text_w: ldx = %d, must be positive", ldx);
-    if (ldx > CMP_MAX_LDX) return fail(AFR_EUNSUPPORTED, "afr_op_dataset_text_w: ldx = %d, at most %d codes per row", ldx, CMP_MAX_LDX);
-    if (min_len < 1 || max_len < min_len || max_len > ldx)
-        return fail(AFR_EINVAL, "afr_op_dataset_text_w: text lengths %d..%d must satisfy 1 <= min_len <= max_len <= ldx = %d", min_len, max_len, ldx);
-    if (((uintptr_t)codes & 7) || ((uintptr_t)seed_rows & 7) || ((uintptr_t)out_rows & 7) || ((uintptr_t)len & 3) || ((uintptr_t)cum & 3) ||
-        ((uintptr_t)err & 3))
-        return fail(AFR_EINVAL, "afr_op_dataset_text_w: codes, seed_rows and out_rows must be 8-byte aligned, cum, len and err 4-byte");
+    if (const int rc = text_args_check("afr_op_dataset_text_w", seed_rows, out_rows, n, min_len, max_len, "cum", cum, codes, ldx, len, err)) return rc;
     DevGuard dg(device_of(codes));
     HIPCHK(afr_launch_dataset_text_w(first_seed, seed_rows, out_rows, n, min_len, max_len, cum, codes, ldx, len, err, (hipStream_t)stream));
     return AFR_OK;
 }
-extern "C" int afr_op_text_weights(const uint64_t* by_code, int n_codes, const uint32_t* members, uint32_t floor_w, uint32_t gain, uint32_t* cum,
-                                   uint32_t* w, void* stream) {
-    const char* who = "afr_op_text_weights";
-    if (!members || !cum) return fail(AFR_EINVAL, "%s: members or cum is null", who);
-    if (by_code && n_codes < AFR_TEXT_FIRST + AFR_TEXT_CODES)
+extern "C" int afr_op_dataset_text_m(int64_t first_seed, const int64_t* seed_rows, const int64_t* out_rows, int64_t n, int min_len, int max_len,
+                                     const uint32_t* cum2, int64_t* codes, int ldx, int32_t* len, uint32_t* err, void* stream) {
+    if (const int rc = text_args_check("afr_op_dataset_text_m", seed_rows, out_rows, n, min_len, max_len, "cum2", cum2, codes, ldx, len, err)) return rc;
+    DevGuard dg(device_of(codes));
+    HIPCHK(afr_launch_dataset_text_m(first_seed, seed_rows, out_rows, n, min_len, max_len, cum2, codes, ldx, len, err, (hipStream_t)stream));
+    return AFR_OK;
+}
+// What afr_op_text_weights and afr_op_pair_weights refuse alike: the member mask, the weight ranges and the alignment of the counter table
+// and of the two outputs, each under its name; n_codes is how many codes a given table holds (the pair table's shape is fixed: it holds
+// them all).  -> AFR_OK or the failure, already recorded.
+static int weights_args_check(const char* who, const char* table_name, const uint64_t* table, int n_codes, const uint32_t* members,
+                              uint32_t floor_w, uint32_t gain, const char* cum_name, const uint32_t* cum, const char* w_name, const uint32_t* w) {
+    if (!members || !cum) return fail(AFR_EINVAL, "%s: members or %s is null", who, cum_name);
+    if (table && n_codes < AFR_TEXT_FIRST + AFR_TEXT_CODES)
         return fail(AFR_EINVAL, "%s: n_codes = %d, a by-code table must hold the codes up to %d", who, n_codes, AFR_TEXT_FIRST + AFR_TEXT_CODES - 1);
     if (members[2] >> (AFR_TEXT_CODES - 64))
         return fail(AFR_EINVAL, "%s: member bits above bit %d (code %d) are set", who, AFR_TEXT_CODES - 1, AFR_TEXT_FIRST + AFR_TEXT_CODES - 1);
     if (!(members[0] | members[1] | members[2])) return fail(AFR_EINVAL, "%s: the member set is empty", who);
     if (floor_w < 1u || floor_w > 65535u || gain > 65535u)
         return fail(AFR_EINVAL, "%s: floor_w = %u must lie in 1..65535, gain = %u in 0..65535", who, floor_w, gain);
-    if (((uintptr_t)by_code & 7) || ((uintptr_t)cum & 3) || ((uintptr_t)w & 3))
-        return fail(AFR_EINVAL, "%s: by_code must be 8-byte aligned, cum and w 4-byte", who);
-    DevGuard dg(device_of(cum));
-    HIPCHK(afr_launch_text_weights((const unsigned long long*)by_code, members, floor_w, gain, cum, w, (hipStream_t)stream));
+    if (((uintptr_t)table & 7) || ((uintptr_t)cum & 3) || ((uintptr_t)w & 3))
+        return fail(AFR_EINVAL, "%s: %s must be 8-byte aligned, %s and %s 4-byte", who, table_name, cum_name, w_name);
     return AFR_OK;
 }
-extern "C" int afr_op_dataset_text_m(int64_t first_seed, const int64_t* seed_rows, const int64_t* out_rows, int64_t n, int min_len, int max_len,
-                                     const uint32_t* cum2, int64_t* codes, int ldx, int32_t* len, uint32_t* err, void* stream) {
-    const char* who = "afr_op_dataset_text_m";
-    if (!codes || !cum2) return fail(AFR_EINVAL, "%s: codes or cum2 is null", who);
-    if (n < 1) return fail(AFR_EINVAL, "%s: n = %lld, must be >= 1", who, (long long)n);
-    if (ldx < 1) return fail(AFR_EINVAL, "%s: ldx = %d, must be positive", who, ldx);
-    if (ldx > CMP_MAX_LDX) return fail(AFR_EUNSUPPORTED, "%s: ldx = %d, at most %d codes per row", who, ldx, CMP_MAX_LDX);
-    if (min_len < 1 || max_len < min_len || max_len > ldx)
-        return fail(AFR_EINVAL, "%s: text lengths %d..%d must satisfy 1 <= min_len <= max_len <= ldx = %d", who, min_len, max_len, ldx);
-    if (((uintptr_t)codes & 7) || ((uintptr_t)seed_rows & 7) || ((uintptr_t)out_rows & 7) || ((uintptr_t)len & 3) || ((uintptr_t)cum2 & 3) ||
-        ((uintptr_t)err & 3))
-        return fail(AFR_EINVAL, "%s: codes, seed_rows and out_rows must be 8-byte aligned, cum2, len and err 4-byte", who);
-    DevGuard dg(device_of(codes));
-    HIPCHK(afr_launch_dataset_text_m(first_seed, seed_rows, out_rows, n, min_len, max_len, cum2, codes, ldx, len, err, (hipStream_t)stream));
+extern "C" int afr_op_text_weights(const uint64_t* by_code, int n_codes, const uint32_t* members, uint32_t floor_w, uint32_t gain, uint32_t* cum,
+                                   uint32_t* w, void* stream) {
+    if (const int rc = weights_args_check("afr_op_text_weights", "by_code", by_code, n_codes, members, floor_w, gain, "cum", cum, "w", w)) return rc;
+    DevGuard dg(device_of(cum));
+    HIPCHK(afr_launch_text_weights((const unsigned long long*)by_code, members, floor_w, gain, cum, w, (hipStream_t)stream));
     return AFR_OK;
 }
 extern "C" int afr_op_pair_errors(const int64_t* codes, int ldx, const int64_t* code_rows, int64_t n, const uint32_t* per_pos, uint64_t* by_pair,
@@ -2709,15 +2710,7 @@ extern "C" int afr_op_pair_errors(const int64_t* codes, int ldx, const int64_t* 
 }
 extern "C" int afr_op_pair_weights(const uint64_t* by_pair, const uint32_t* members, uint32_t floor_w, uint32_t gain, uint32_t min_chars,
                                    uint32_t* cum2, uint32_t* w2, void* stream) {
-    const char* who = "afr_op_pair_weights";
-    if (!members || !cum2) return fail(AFR_EINVAL, "%s: members or cum2 is null", who);
-    if (members[2] >> (AFR_TEXT_CODES - 64))
-        return fail(AFR_EINVAL, "%s: member bits above bit %d (code %d) are set", who, AFR_TEXT_CODES - 1, AFR_TEXT_FIRST + AFR_TEXT_CODES - 1);
-    if (!(members[0] | members[1] | members[2])) return fail(AFR_EINVAL, "%s: the member set is empty", who);
-    if (floor_w < 1u || floor_w > 65535u || gain > 65535u)
-        return fail(AFR_EINVAL, "%s: floor_w = %u must lie in 1..65535, gain = %u in 0..65535", who, floor_w, gain);
-    if (((uintptr_t)by_pair & 7) || ((uintptr_t)cum2 & 3) || ((uintptr_t)w2 & 3))
-        return fail(AFR_EINVAL, "%s: by_pair must be 8-byte aligned, cum2 and w2 4-byte", who);
+    if (const int rc = weights_args_check("afr_op_pair_weights", "by_pair", by_pair, AFR_TEXT_FIRST + AFR_TEXT_CODES, members, floor_w, gain, "cum2", cum2, "w2", w2)) return rc;
     DevGuard dg(device_of(cum2));
     HIPCHK(afr_launch_pair_weights((const unsigned long long*)by_pair, members, floor_w, gain, min_chars, cum2, w2, (hipStream_t)stream));
     return AFR_OK;

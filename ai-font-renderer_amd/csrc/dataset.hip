@@ -5,30 +5,40 @@
 #include "afr_common.h"
 
 // ------------------------------------------------------------------------------------------- text
-// One lane per sample: synth.lcg_text in integers.  int(rnd() * k) is (state * k) >> 32 -- state / 2^32 * k is exact in a double.
-// A sample writes pos <= length <= max_len <= ldx codes and zero-fills the rest of its row: every element of the row, once.
-__global__ __launch_bounds__(256) void dataset_text_kernel(long long first_seed, const int64_t* __restrict__ seed_rows,
-                                                           const int64_t* __restrict__ out_rows, long long n, int min_len, int max_len,
-                                                           int64_t* __restrict__ codes, int ldx, int32_t* __restrict__ len) {
-    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
+// One lane per sample: synth.lcg_text in integers, the walk dataset_text_kernel and dataset_text_w_kernel share.  draw(k) is
+// int(rnd() * k) as (state * k) >> 32 -- state / 2^32 * k is exact in a double.  letter(draw) is the source's own part: the code of the
+// next letter.  live = false draws nothing: an empty sample.  A sample writes pos <= length <= max_len <= ldx codes and zero-fills the
+// rest of its row: every element of the row, once.  (dataset_text_m_kernel, whose source can fail in the middle of a text and carries
+// a context from letter to letter, keeps the same walk as a loop of its own: run through this one it measured 5 % slower.)
+template <class Letter>
+__device__ __forceinline__ void text_walk(long long first_seed, const int64_t* __restrict__ seed_rows, const int64_t* __restrict__ out_rows,
+                                          long long j, int min_len, int max_len, int64_t* __restrict__ codes, int ldx,
+                                          int32_t* __restrict__ len, bool live, Letter letter) {
     uint32_t state = (uint32_t)(uint64_t)(first_seed + (seed_rows ? seed_rows[j] : j));      // the update is mod 2^32 from the start
     const long long row = out_rows ? out_rows[j] : j;
     int64_t* dst = codes + row * (long long)ldx;
-    auto draw = [&](uint32_t k) -> int {
+    auto draw = [&](uint32_t k) -> uint32_t {
         state = state * 1664525u + 1013904223u;
-        return (int)(((uint64_t)state * k) >> 32);
+        return (uint32_t)(((uint64_t)state * k) >> 32);
     };
-    const int length = draw((uint32_t)(max_len - min_len + 1)) + min_len;
+    const int length = live ? (int)draw((uint32_t)(max_len - min_len + 1)) + min_len : 0;
     int remaining = length, pos = 0;
     while (remaining > 0) {
-        const int wl = min(draw(10u) + 1, remaining);
-        for (int i = 0; i < wl; ++i) dst[pos++] = 65 + draw(26u);
+        const int wl = min((int)draw(10u) + 1, remaining);
+        for (int i = 0; i < wl; ++i) dst[pos++] = letter(draw);
         remaining -= wl;
         if (remaining > 0) { dst[pos++] = 32; --remaining; }
     }
     for (; pos < ldx; ++pos) dst[pos] = 0;
     if (len) len[row] = length;
+}
+
+__global__ __launch_bounds__(256) void dataset_text_kernel(long long first_seed, const int64_t* __restrict__ seed_rows,
+                                                           const int64_t* __restrict__ out_rows, long long n, int min_len, int max_len,
+                                                           int64_t* __restrict__ codes, int ldx, int32_t* __restrict__ len) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    text_walk(first_seed, seed_rows, out_rows, j, min_len, max_len, codes, ldx, len, true, [](auto& draw) { return 65 + (int)draw(26u); });
 }
 
 hipError_t afr_launch_dataset_text(long long first_seed, const int64_t* seed_rows, const int64_t* out_rows, long long n, int min_len, int max_len,
@@ -41,9 +51,17 @@ hipError_t afr_launch_dataset_text(long long first_seed, const int64_t* seed_row
 // ---------------------------------------------------------------------------------- weighted text
 // afr_op_dataset_text_w: dataset_text_kernel with the letter drawn from a table of weights (synth.lcg_text_weighted).  The 94 inclusive
 // cumulative weights go to LDS once per workgroup, padded to 128 entries with 2^32 - 1, which no draw r < total <= 2^32 - 1 reaches: the
-// seven-step search below then needs no bound check.  It counts the entries <= r, which is the smallest i with cum[i] > r; an entry of
+// seven-step search then needs no bound check.  It counts the entries <= r, which is the smallest i with cum[i] > r; an entry of
 // zero width (cum[i] == cum[i - 1]) is passed over with its predecessor.  A table whose total is 0 draws nothing: zero rows, bit 0 of *err.
 constexpr int TXT_FIRST = 33, TXT_CODES = 94, TXT_PAD = 128;
+__device__ __forceinline__ int text_search(const uint32_t* tab, uint32_t r) {
+    int at = 0;
+#pragma unroll
+    for (int step = TXT_PAD / 2; step > 0; step >>= 1)
+        if (tab[at + step - 1] <= r) at += step;
+    return at;
+}
+
 __global__ __launch_bounds__(256) void dataset_text_w_kernel(long long first_seed, const int64_t* __restrict__ seed_rows,
                                                              const int64_t* __restrict__ out_rows, long long n, int min_len, int max_len,
                                                              const uint32_t* __restrict__ cum, int64_t* __restrict__ codes, int ldx,
@@ -54,35 +72,9 @@ __global__ __launch_bounds__(256) void dataset_text_w_kernel(long long first_see
     const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
     const uint32_t total = s_cum[TXT_CODES - 1];
-    uint32_t state = (uint32_t)(uint64_t)(first_seed + (seed_rows ? seed_rows[j] : j));
-    const long long row = out_rows ? out_rows[j] : j;
-    int64_t* dst = codes + row * (long long)ldx;
-    auto draw = [&](uint32_t k) -> uint32_t {
-        state = state * 1664525u + 1013904223u;
-        return (uint32_t)(((uint64_t)state * k) >> 32);
-    };
-    int length = 0, pos = 0;
-    if (total != 0u) {
-        length = (int)draw((uint32_t)(max_len - min_len + 1)) + min_len;
-        int remaining = length;
-        while (remaining > 0) {
-            const int wl = min((int)draw(10u) + 1, remaining);
-            for (int i = 0; i < wl; ++i) {
-                const uint32_t r = draw(total);
-                int at = 0;
-#pragma unroll
-                for (int step = TXT_PAD / 2; step > 0; step >>= 1)
-                    if (s_cum[at + step - 1] <= r) at += step;
-                dst[pos++] = TXT_FIRST + at;
-            }
-            remaining -= wl;
-            if (remaining > 0) { dst[pos++] = 32; --remaining; }
-        }
-    } else if (threadIdx.x == 0 && err) {
-        atomicOr(err, AFR_ERR_INDEX);                                  // lane 0 of every workgroup has a sample (j < n)
-    }
-    for (; pos < ldx; ++pos) dst[pos] = 0;
-    if (len) len[row] = length;
+    text_walk(first_seed, seed_rows, out_rows, j, min_len, max_len, codes, ldx, len, total != 0u,
+              [&](auto& draw) { return TXT_FIRST + text_search(s_cum, draw(total)); });
+    if (total == 0u && threadIdx.x == 0 && err) atomicOr(err, AFR_ERR_INDEX);      // lane 0 of every workgroup has a sample (j < n)
 }
 
 hipError_t afr_launch_dataset_text_w(long long first_seed, const int64_t* seed_rows, const int64_t* out_rows, long long n, int min_len,
@@ -193,11 +185,7 @@ __global__ __launch_bounds__(256) void dataset_text_m_kernel(long long first_see
             for (int i = 0; i < wl; ++i) {
                 const uint32_t total = tab[TXT_CODES - 1];
                 if (total == 0u) { failed = true; break; }
-                const uint32_t r = draw(total);
-                int at = 0;
-#pragma unroll
-                for (int step = TXT_PAD / 2; step > 0; step >>= 1)
-                    if (tab[at + step - 1] <= r) at += step;
+                const int at = text_search(tab, draw(total));
                 dst[pos++] = TXT_FIRST + at;
                 tab = s_cum + (1 + at) * TXT_PAD;                      // at <= 93: r < total = tab[93] ends the search there at the latest
             }

@@ -164,14 +164,76 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _codes_rows(codes, rows, device, shape="[N, L]"):
+    """The codes as a contiguous int64 [N, L] tensor on the device and the rows of them that are read -> (codes, rows, n, L): sample j of n
+    reads row rows[j], or row j of all N without rows."""
+    codes = codes.to(device=device, dtype=torch.int64).contiguous()
+    if codes.dim() != 2:
+        raise ValueError(f"codes must be int64 {shape}")
+    rows = _rows(rows, None, device, "rows")
+    n = codes.shape[0] if rows is None else rows.numel()
+    if rows is not None and n and (int(rows.min()) < 0 or int(rows.max()) >= codes.shape[0]):
+        raise IndexError("rows outside codes")
+    return codes, rows, n, codes.shape[1]
+
+
+def _out_rows(rows, n, out, device):
+    """The rows of out that n samples are written to: one per sample and inside out, or None for the first n, which out must have."""
+    rows = _rows(rows, n, device, "rows")
+    if rows is None and n > out.shape[0]:
+        raise ValueError(f"{n} samples do not fit the {out.shape[0]} rows of out")
+    if rows is not None and n and (int(rows.min()) < 0 or int(rows.max()) >= out.shape[0]):
+        raise IndexError("rows outside out")
+    return rows
+
+
+def _table(table, name, shape, device):
+    """A table of counters that a launch adds to: the caller's, or a new one of zeros."""
+    if table is None:
+        table = torch.zeros(shape, dtype=torch.int64, device=device)
+    if table.dtype != torch.int64 or table.device != device or not table.is_contiguous() or tuple(table.shape) != tuple(shape):
+        raise ValueError(f"{name} must be a contiguous int64 {list(shape)} tensor on {device}")
+    return table
+
+
+def _check_pred(pred, n, height, width, device):
+    if pred.dtype != torch.uint8 or pred.device != device or not pred.is_contiguous() or pred.numel() != n * height * width:
+        raise ValueError(f"pred must be a contiguous uint8 [{n}, {height}, {width}] tensor on {device}")
+
+
+def _outside(atlas):
+    """what the three sheet launches' flag means"""
+    return IndexError(f"a code outside the atlas's 0..{atlas.n_codes - 1}")
+
+
+def _member_words(alphabet):
+    """An alphabet -- a name or literal string (synth.alphabet_members) or the 94 flags themselves -- as the three words the entries take."""
+    from . import synth
+    members = synth.alphabet_members(alphabet) if isinstance(alphabet, str) else [int(bool(m)) for m in alphabet]
+    return (C.c_uint32 * 3)(*synth.members_words(members))
+
+
+_ERR = object()                          # stands in a launch's arguments for the pointer to its err word
+
+
+def _launch(device, entry, *args, flagged=None):
+    """entry(*args, stream) on the device's current stream, _ERR among the arguments replaced by a fresh, zero err word.  flagged: the
+    exception to raise when the launch set bit 0 of that word -- reading it waits for the launch; None leaves it unread.  The only place
+    that reads the flag."""
+    with torch.cuda.device(device):
+        err = torch.zeros(1, dtype=torch.int32, device=device) if any(a is _ERR for a in args) else None
+        _lib.check(entry(*[_ptr(err) if a is _ERR else a for a in args], _stream(device)))
+        if flagged is not None and int(err) & 1:
+            raise flagged
+
+
 def text_weights(alphabet, by_code=None, floor_w=4096, gain=0, device=None):
     """afr_op_text_weights: the letter table of the weighted text source, built on the device -> (cum, w), two int32 [94] tensors holding
     uint32 words (the total stays below 2^27).  alphabet: a name or literal string (synth.alphabet_members) or the 94 flags themselves;
     by_code: char_errors' int64 [n_codes + 1, 5] table where it lies on the device, or None for equal weights floor_w.  Every member
     weighs floor_w + gain * min(its mean squared error / the alphabet's, 16): synth.text_weights in integers.  Nothing is read back."""
     from . import synth
-    members = synth.alphabet_members(alphabet) if isinstance(alphabet, str) else [int(bool(m)) for m in alphabet]
-    words = (C.c_uint32 * 3)(*synth.members_words(members))
+    words = _member_words(alphabet)
     if by_code is not None:
         if by_code.dtype != torch.int64 or by_code.dim() != 2 or by_code.shape[1] != 5 or not by_code.is_contiguous() or not by_code.is_cuda:
             raise ValueError("by_code must be a contiguous int64 [n_codes + 1, 5] tensor on the device")
@@ -180,9 +242,8 @@ def text_weights(alphabet, by_code=None, floor_w=4096, gain=0, device=None):
         raise ValueError("text_weights needs a device or a by_code table")
     device = torch.device(device)
     cum, w = torch.empty(synth.TEXT_CODES, dtype=torch.int32, device=device), torch.empty(synth.TEXT_CODES, dtype=torch.int32, device=device)
-    with torch.cuda.device(device):
-        _lib.check(_lib.lib().afr_op_text_weights(_ptr(by_code), 0 if by_code is None else by_code.shape[0] - 1, words, int(floor_w), int(gain),
-                                                   _ptr(cum), _ptr(w), _stream(device)))
+    _launch(device, _lib.lib().afr_op_text_weights, _ptr(by_code), 0 if by_code is None else by_code.shape[0] - 1, words, int(floor_w), int(gain),
+            _ptr(cum), _ptr(w))
     return cum, w
 
 
@@ -195,23 +256,15 @@ def pair_errors(codes, per_pos, rows=None, by_pair=None):
     before" (position 0, after a space or any code outside 33..126), context 1 + i "after code 33 + i".  Sample j reads row rows[j]
     (default j) of the int64 [N, L] codes, as char_errors did.  by_pair (default new and zero) is added to.  Nothing is read back."""
     device = per_pos.device
-    codes = codes.to(device=device, dtype=torch.int64).contiguous()
     if codes.dim() != 2 or not per_pos.is_cuda:
         raise ValueError("codes must be int64 [N, L], per_pos a tensor on the device")
-    rows = _rows(rows, None, device, "rows")
-    n, L = codes.shape[0] if rows is None else rows.numel(), codes.shape[1]
-    if rows is not None and n and (int(rows.min()) < 0 or int(rows.max()) >= codes.shape[0]):
-        raise IndexError("rows outside codes")
+    codes, rows, n, L = _codes_rows(codes, rows, device)
     if per_pos.dtype not in (torch.int32, torch.int64) or tuple(per_pos.shape) != (n, L + 1, 4):
         raise ValueError(f"per_pos must be an int32 or int64 [{n}, {L + 1}, 4] tensor (char_errors' records)")
     per_pos = per_pos.to(torch.int32).contiguous()                    # the uint32 words afr_op_sheet_char_errors stored
-    if by_pair is None:
-        by_pair = torch.zeros(PAIR_SHAPE + (4,), dtype=torch.int64, device=device)
-    if by_pair.dtype != torch.int64 or by_pair.device != device or not by_pair.is_contiguous() or tuple(by_pair.shape) != PAIR_SHAPE + (4,):
-        raise ValueError(f"by_pair must be a contiguous int64 [95, 94, 4] tensor on {device}")
+    by_pair = _table(by_pair, "by_pair", PAIR_SHAPE + (4,), device)
     if n:
-        with torch.cuda.device(device):
-            _lib.check(_lib.lib().afr_op_pair_errors(_ptr(codes), L, _ptr(rows), n, _ptr(per_pos), _ptr(by_pair), _stream(device)))
+        _launch(device, _lib.lib().afr_op_pair_errors, _ptr(codes), L, _ptr(rows), n, _ptr(per_pos), _ptr(by_pair))
     return by_pair
 
 
@@ -220,9 +273,7 @@ def pair_weights(alphabet, by_pair=None, floor_w=4096, gain=0, min_chars=0, devi
     uint32 words.  alphabet as text_weights'; by_pair: pair_errors' int64 [95, 94, 4] table where it lies on the device, or None for
     equal weights floor_w on every pair of members.  A pair weighs floor_w + gain * min(its mean squared error / the table's, 16), a
     pair seen fewer than min_chars times as the average: synth.pair_weights in integers.  Nothing is read back."""
-    from . import synth
-    members = synth.alphabet_members(alphabet) if isinstance(alphabet, str) else [int(bool(m)) for m in alphabet]
-    words = (C.c_uint32 * 3)(*synth.members_words(members))
+    words = _member_words(alphabet)
     if by_pair is not None:
         if by_pair.dtype != torch.int64 or tuple(by_pair.shape) != PAIR_SHAPE + (4,) or not by_pair.is_contiguous() or not by_pair.is_cuda:
             raise ValueError("by_pair must be a contiguous int64 [95, 94, 4] tensor on the device")
@@ -233,9 +284,7 @@ def pair_weights(alphabet, by_pair=None, floor_w=4096, gain=0, min_chars=0, devi
         raise ValueError(f"min_chars {min_chars} must lie in 0..2^32 - 1")
     device = torch.device(device)
     cum2, w2 = torch.empty(PAIR_SHAPE, dtype=torch.int32, device=device), torch.empty(PAIR_SHAPE, dtype=torch.int32, device=device)
-    with torch.cuda.device(device):
-        _lib.check(_lib.lib().afr_op_pair_weights(_ptr(by_pair), words, int(floor_w), int(gain), int(min_chars), _ptr(cum2), _ptr(w2),
-                                                   _stream(device)))
+    _launch(device, _lib.lib().afr_op_pair_weights, _ptr(by_pair), words, int(floor_w), int(gain), int(min_chars), _ptr(cum2), _ptr(w2))
     return cum2, w2
 
 
@@ -263,31 +312,22 @@ def generate_codes(n, first_seed=42, max_length=100, device=None, out=None, rows
         raise ValueError("out must be a contiguous int64 [N, L] tensor")
     if lens is not None and (lens.dtype != torch.int32 or lens.device != device or lens.numel() != out.shape[0] or not lens.is_contiguous()):
         raise ValueError("lens must be a contiguous int32 [N] tensor beside out")
-    rows, seed_rows = _rows(rows, n, device, "rows"), _rows(seed_rows, n, device, "seed_rows")
-    if rows is None and n > out.shape[0]:
-        raise ValueError(f"{n} samples do not fit the {out.shape[0]} rows of out")
-    if rows is not None and n and (int(rows.min()) < 0 or int(rows.max()) >= out.shape[0]):
-        raise IndexError("rows outside out")
+    rows, seed_rows = _out_rows(rows, n, out, device), _rows(seed_rows, n, device, "seed_rows")
     if cum is not None and (cum.dtype != torch.int32 or cum.device != device or cum.numel() != 94 or not cum.is_contiguous()):
         raise ValueError(f"cum must be a contiguous int32 [94] tensor on {device} (text_weights' table)")
     if cum2 is not None and (cum2.dtype != torch.int32 or cum2.device != device or tuple(cum2.shape) != PAIR_SHAPE or not cum2.is_contiguous()):
         raise ValueError(f"cum2 must be a contiguous int32 [95, 94] tensor on {device} (pair_weights' table)")
-    with torch.cuda.device(device):
-        if cum2 is not None:
-            err = torch.zeros(1, dtype=torch.int32, device=device)
-            _lib.check(_lib.lib().afr_op_dataset_text_m(int(first_seed), _ptr(seed_rows), _ptr(rows), n, MIN_TEXT_LENGTH, int(max_length),
-                                                         _ptr(cum2), _ptr(out), out.shape[1], _ptr(lens), _ptr(err), _stream(device)))
-            if check_total and int(err) & 1:
-                raise ValueError("a text reached a context of the pair table whose total weight is 0")
-        elif cum is None:
-            _lib.check(_lib.lib().afr_op_dataset_text(int(first_seed), _ptr(seed_rows), _ptr(rows), n, MIN_TEXT_LENGTH, int(max_length),
-                                                       _ptr(out), out.shape[1], _ptr(lens), _stream(device)))
-        else:
-            err = torch.zeros(1, dtype=torch.int32, device=device)
-            _lib.check(_lib.lib().afr_op_dataset_text_w(int(first_seed), _ptr(seed_rows), _ptr(rows), n, MIN_TEXT_LENGTH, int(max_length),
-                                                         _ptr(cum), _ptr(out), out.shape[1], _ptr(lens), _ptr(err), _stream(device)))
-            if check_total and int(err) & 1:
-                raise ValueError("the letter table's total weight is 0: no text can be drawn from it")
+    # the entry, its table before out, its err word at the end, and what a set flag means: chosen once, launched once
+    if cum2 is not None:
+        entry, table, err = _lib.lib().afr_op_dataset_text_m, [_ptr(cum2)], [_ERR]
+        zero_total = "a text reached a context of the pair table whose total weight is 0"
+    elif cum is not None:
+        entry, table, err = _lib.lib().afr_op_dataset_text_w, [_ptr(cum)], [_ERR]
+        zero_total = "the letter table's total weight is 0: no text can be drawn from it"
+    else:
+        entry, table, err = _lib.lib().afr_op_dataset_text, [], []
+    _launch(device, entry, int(first_seed), _ptr(seed_rows), _ptr(rows), n, MIN_TEXT_LENGTH, int(max_length), *table, _ptr(out), out.shape[1],
+            _ptr(lens), *err, flagged=ValueError(zero_total) if err and check_total else None)
     return out, lens
 
 
@@ -296,28 +336,17 @@ def compose_sheets(atlas, codes, height=80, width=240, out=None, rows=None, line
     font does not substitute glyphs in.  Sample j goes to row rows[j] (default j) of out (uint8 [N, height, width], default new).  A
     code outside the atlas is an IndexError (it is skipped on the device and flagged; reading the flag waits for the launch)."""
     device = atlas.device
-    codes = codes.to(device=device, dtype=torch.int64).contiguous()
-    if codes.dim() != 2:
-        raise ValueError("codes must be int64 [n, L]")
-    n = codes.shape[0]
+    codes, _, n, L = _codes_rows(codes, None, device, "[n, L]")
     if out is None:
         if rows is not None:
             raise ValueError("rows needs the buffer they are rows of (out)")
         out = torch.empty((n, height, width), dtype=torch.uint8, device=device)
     if out.dtype != torch.uint8 or out.device != device or not out.is_contiguous() or tuple(out.shape[1:]) != (height, width):
         raise ValueError(f"out must be a contiguous uint8 [N, {height}, {width}] tensor on {device}")
-    rows = _rows(rows, n, device, "rows")
-    if rows is None and n > out.shape[0]:
-        raise ValueError(f"{n} samples do not fit the {out.shape[0]} rows of out")
-    if rows is not None and n and (int(rows.min()) < 0 or int(rows.max()) >= out.shape[0]):
-        raise IndexError("rows outside out")
+    rows = _out_rows(rows, n, out, device)
     a, g = atlas._struct(), sheet_geometry(height, width, line_height, atlas)
-    with torch.cuda.device(device):
-        err = torch.zeros(1, dtype=torch.int32, device=device)
-        _lib.check(_lib.lib().afr_op_compose_sheets(C.byref(a), C.byref(g), _ptr(codes), codes.shape[1], _ptr(rows), n, _ptr(out), _ptr(err),
-                                                     _stream(device)))
-        if int(err) & 1:
-            raise IndexError(f"a code outside the atlas's 0..{atlas.n_codes - 1}")
+    _launch(device, _lib.lib().afr_op_compose_sheets, C.byref(a), C.byref(g), _ptr(codes), L, _ptr(rows), n, _ptr(out), _ERR,
+            flagged=_outside(atlas))
     return out
 
 
@@ -334,27 +363,13 @@ def char_errors(atlas, codes, pred, height=80, width=240, rows=None, by_code=Non
     codes, so a batch can read a bound data set's codes where they lie.  by_code (int64 [n_codes + 1, 5], default new and zero) is
     added to.  A code outside the atlas is an IndexError, as in compose_sheets."""
     device = atlas.device
-    codes = codes.to(device=device, dtype=torch.int64).contiguous()
-    if codes.dim() != 2:
-        raise ValueError("codes must be int64 [N, L]")
-    rows = _rows(rows, None, device, "rows")
-    n, L = codes.shape[0] if rows is None else rows.numel(), codes.shape[1]
-    if rows is not None and n and (int(rows.min()) < 0 or int(rows.max()) >= codes.shape[0]):
-        raise IndexError("rows outside codes")
-    if pred.dtype != torch.uint8 or pred.device != device or not pred.is_contiguous() or pred.numel() != n * height * width:
-        raise ValueError(f"pred must be a contiguous uint8 [{n}, {height}, {width}] tensor on {device}")
-    if by_code is None:
-        by_code = torch.zeros((atlas.n_codes + 1, 5), dtype=torch.int64, device=device)
-    if by_code.dtype != torch.int64 or by_code.device != device or not by_code.is_contiguous() or tuple(by_code.shape) != (atlas.n_codes + 1, 5):
-        raise ValueError(f"by_code must be a contiguous int64 [{atlas.n_codes + 1}, 5] tensor on {device}")
+    codes, rows, n, L = _codes_rows(codes, rows, device)
+    _check_pred(pred, n, height, width, device)
+    by_code = _table(by_code, "by_code", (atlas.n_codes + 1, 5), device)
     per_pos = torch.empty((n, L + 1, 4), dtype=torch.int32, device=device)
     a, g = atlas._struct(), sheet_geometry(height, width, line_height, atlas)
-    with torch.cuda.device(device):
-        err = torch.zeros(1, dtype=torch.int32, device=device)
-        _lib.check(_lib.lib().afr_op_sheet_char_errors(C.byref(a), C.byref(g), _ptr(codes), L, _ptr(rows), n, _ptr(pred), _ptr(per_pos),
-                                                        _ptr(by_code), _ptr(err), _stream(device)))
-        if int(err) & 1:
-            raise IndexError(f"a code outside the atlas's 0..{atlas.n_codes - 1}")
+    _launch(device, _lib.lib().afr_op_sheet_char_errors, C.byref(a), C.byref(g), _ptr(codes), L, _ptr(rows), n, _ptr(pred), _ptr(per_pos),
+            _ptr(by_code), _ERR, flagged=_outside(atlas))
     return CharErrors(per_pos.to(torch.int64) & 0xFFFFFFFF, by_code)
 
 
@@ -391,33 +406,16 @@ def read_back(atlas, codes, pred, alphabet="upper", height=80, width=240, rows=N
     prediction over the character's cell box is what was read: the true code among equals, then the smallest.  Sample j reads row
     rows[j] (default j) of the int64 [N, L] codes.  confusion (int64 [n_codes, n_codes], default new and zero) is added to.  A code
     outside the atlas is an IndexError, as in compose_sheets.  -> ReadBack."""
-    from . import synth
     device = atlas.device
-    codes = codes.to(device=device, dtype=torch.int64).contiguous()
-    if codes.dim() != 2:
-        raise ValueError("codes must be int64 [N, L]")
-    members = synth.alphabet_members(alphabet) if isinstance(alphabet, str) else [int(bool(m)) for m in alphabet]
-    words = (C.c_uint32 * 3)(*synth.members_words(members))
-    rows = _rows(rows, None, device, "rows")
-    n, L = codes.shape[0] if rows is None else rows.numel(), codes.shape[1]
-    if rows is not None and n and (int(rows.min()) < 0 or int(rows.max()) >= codes.shape[0]):
-        raise IndexError("rows outside codes")
-    if pred.dtype != torch.uint8 or pred.device != device or not pred.is_contiguous() or pred.numel() != n * height * width:
-        raise ValueError(f"pred must be a contiguous uint8 [{n}, {height}, {width}] tensor on {device}")
-    if confusion is None:
-        confusion = torch.zeros((atlas.n_codes, atlas.n_codes), dtype=torch.int64, device=device)
-    if (confusion.dtype != torch.int64 or confusion.device != device or not confusion.is_contiguous()
-            or tuple(confusion.shape) != (atlas.n_codes, atlas.n_codes)):
-        raise ValueError(f"confusion must be a contiguous int64 [{atlas.n_codes}, {atlas.n_codes}] tensor on {device}")
+    words = _member_words(alphabet)
+    codes, rows, n, L = _codes_rows(codes, rows, device)
+    _check_pred(pred, n, height, width, device)
+    confusion = _table(confusion, "confusion", (atlas.n_codes, atlas.n_codes), device)
     read = torch.empty((n, L), dtype=torch.uint8, device=device)
     score = torch.empty((n, L, 2), dtype=torch.int32, device=device)
     a, g = atlas._struct(), sheet_geometry(height, width, line_height, atlas)
-    with torch.cuda.device(device):
-        err = torch.zeros(1, dtype=torch.int32, device=device)
-        _lib.check(_lib.lib().afr_op_sheet_read_back(C.byref(a), C.byref(g), _ptr(codes), L, _ptr(rows), n, _ptr(pred), words, _ptr(read),
-                                                      _ptr(score), _ptr(confusion), _ptr(err), _stream(device)))
-        if int(err) & 1:
-            raise IndexError(f"a code outside the atlas's 0..{atlas.n_codes - 1}")
+    _launch(device, _lib.lib().afr_op_sheet_read_back, C.byref(a), C.byref(g), _ptr(codes), L, _ptr(rows), n, _ptr(pred), words, _ptr(read),
+            _ptr(score), _ptr(confusion), _ERR, flagged=_outside(atlas))
     return ReadBack(read, score.to(torch.int64) & 0xFFFFFFFF, confusion, codes if rows is None else codes[rows])
 
 

@@ -88,6 +88,7 @@ import datetime
 import os
 import random
 import sys
+from functools import partial
 
 import numpy as np
 import torch
@@ -135,10 +136,10 @@ def _ema_from_env():
         raise ValueError(f"AFR_EMA must be <decay> or <decay>:<every>, e.g. 0.999 or 0.999:8, got {spec!r}") from None
 
 
-def _val_report_from_env():
-    """AFR_VAL_REPORT = "<k>", k >= 1: the validation report with the k worst sheets; unset or empty -> None (off).  Anything else is
-    a ValueError."""
-    spec = os.environ.get("AFR_VAL_REPORT", "").strip()
+def _count_from_env(name, what, atlas_for=None):
+    """<name> = "<k>", k >= 1: a report that lists k of `what`; unset or empty -> None (off).  Anything else is a ValueError, and so is --
+    with atlas_for, what the glyph atlas does for the report -- the report without AFR_DEVICE_DATA (no atlas)."""
+    spec = os.environ.get(name, "").strip()
     if not spec:
         return None
     try:
@@ -146,11 +147,41 @@ def _val_report_from_env():
     except ValueError:
         k = 0
     if k < 1:
-        raise ValueError(f"AFR_VAL_REPORT must be an integer >= 1 (the number of worst validation sheets to list), got {spec!r}")
+        raise ValueError(f"{name} must be an integer >= 1 (the number of {what} to list), got {spec!r}")
+    if atlas_for and not os.environ.get("AFR_DEVICE_DATA", "").strip():
+        raise ValueError(f"{name} needs AFR_DEVICE_DATA: the glyph atlas the sheets are composed from {atlas_for}")
     return k
 
 
-VAL_REPORT = _val_report_from_env()     # read at import, like the settings above: a bad value stops the run before it starts
+def _share_from_env(name, instead_of=None):
+    """<name> = "<share>", a float in [0, 1): how much of a fresh letter's weight follows the errors; unset, empty or 0 -> 0.0 (off).
+    Anything else, a share without AFR_FRESH_DATA (nothing is redrawn), or -- with instead_of -- a share together with a non-zero share of
+    that switch (a text is drawn from one table) is a ValueError."""
+    spec = os.environ.get(name, "").strip()
+    if not spec:
+        return 0.0
+    try:
+        share = float(spec)
+    except ValueError:
+        share = -1.0
+    if not 0.0 <= share < 1.0:
+        raise ValueError(f"{name} must be a share in [0, 1), e.g. 0.5, got {spec!r}")
+    if os.environ.get("AFR_FRESH_DATA", "").strip() != "1":
+        raise ValueError(f"{name} needs AFR_FRESH_DATA=1: only texts that are redrawn every epoch can be steered")
+    if share and instead_of and _share_from_env(instead_of):
+        raise ValueError(f"{name} and {instead_of} together: the fresh texts are drawn from one table, by character or by pair")
+    return share
+
+
+_OWNERS = "defines which character owns a pixel"
+# the validation report with the k worst sheets; the per-character and per-pair error reports with the k worst codes and pairs; the
+# read-back report with the k most frequent confusions; the shares of a fresh letter's weight that follow its error and its pair's
+_val_report_from_env = partial(_count_from_env, "AFR_VAL_REPORT", "worst validation sheets")
+_char_report_from_env = partial(_count_from_env, "AFR_CHAR_REPORT", "worst characters", _OWNERS)
+_read_report_from_env = partial(_count_from_env, "AFR_READ_REPORT", "confusions", "holds the candidates' cells")
+_pair_report_from_env = partial(_count_from_env, "AFR_PAIR_REPORT", "worst pairs", _OWNERS)
+_steer_from_env = partial(_share_from_env, "AFR_STEER")
+_steer_pairs_from_env = partial(_share_from_env, "AFR_STEER_PAIRS", "AFR_STEER")
 
 
 def _tensor_report_from_env():
@@ -159,9 +190,6 @@ def _tensor_report_from_env():
     if spec not in ("", "1"):
         raise ValueError(f"AFR_TENSOR_REPORT must be 1 (print the per-tensor report) or unset, got {spec!r}")
     return spec == "1"
-
-
-TENSOR_REPORT = _tensor_report_from_env()     # likewise read at import
 
 
 def _device_data_from_env():
@@ -177,49 +205,6 @@ def _device_data_from_env():
     return spec or None, fresh == "1"
 
 
-DEVICE_DATA, FRESH_DATA = _device_data_from_env()     # likewise read at import
-
-
-def _char_report_from_env():
-    """AFR_CHAR_REPORT = "<k>", k >= 1: the per-character error report with the k worst codes; unset or empty -> None (off).  Anything
-    else, or the report without AFR_DEVICE_DATA (no atlas, no owners), is a ValueError."""
-    spec = os.environ.get("AFR_CHAR_REPORT", "").strip()
-    if not spec:
-        return None
-    try:
-        k = int(spec)
-    except ValueError:
-        k = 0
-    if k < 1:
-        raise ValueError(f"AFR_CHAR_REPORT must be an integer >= 1 (the number of worst characters to list), got {spec!r}")
-    if not os.environ.get("AFR_DEVICE_DATA", "").strip():
-        raise ValueError("AFR_CHAR_REPORT needs AFR_DEVICE_DATA: the glyph atlas the sheets are composed from defines which character owns a pixel")
-    return k
-
-
-CHAR_REPORT = _char_report_from_env()     # likewise read at import
-
-
-def _read_report_from_env():
-    """AFR_READ_REPORT = "<k>", k >= 1: the read-back report with the k most frequent confusions; unset or empty -> None (off).  Anything
-    else, or the report without AFR_DEVICE_DATA (no atlas, no candidates), is a ValueError."""
-    spec = os.environ.get("AFR_READ_REPORT", "").strip()
-    if not spec:
-        return None
-    try:
-        k = int(spec)
-    except ValueError:
-        k = 0
-    if k < 1:
-        raise ValueError(f"AFR_READ_REPORT must be an integer >= 1 (the number of confusions to list), got {spec!r}")
-    if not os.environ.get("AFR_DEVICE_DATA", "").strip():
-        raise ValueError("AFR_READ_REPORT needs AFR_DEVICE_DATA: the glyph atlas the sheets are composed from holds the candidates' cells")
-    return k
-
-
-READ_REPORT = _read_report_from_env()     # likewise read at import
-
-
 def _alphabet_from_env():
     """AFR_ALPHABET = one of synth's alphabet names or a literal string of characters -> the string; unset or empty -> None.  A literal
     with a space or a code outside 33..126, or an alphabet without AFR_DEVICE_DATA, is a ValueError."""
@@ -233,62 +218,12 @@ def _alphabet_from_env():
     return spec
 
 
-def _steer_from_env():
-    """AFR_STEER = "<share>", a float in [0, 1): how much of a fresh text's letter weight follows the characters' errors; unset, empty
-    or 0 -> 0.0 (off).  Anything else, or a share without AFR_FRESH_DATA (nothing is redrawn), is a ValueError."""
-    spec = os.environ.get("AFR_STEER", "").strip()
-    if not spec:
-        return 0.0
-    try:
-        share = float(spec)
-    except ValueError:
-        share = -1.0
-    if not 0.0 <= share < 1.0:
-        raise ValueError(f"AFR_STEER must be a share in [0, 1), e.g. 0.5, got {spec!r}")
-    if os.environ.get("AFR_FRESH_DATA", "").strip() != "1":
-        raise ValueError("AFR_STEER needs AFR_FRESH_DATA=1: only texts that are redrawn every epoch can be steered")
-    return share
-
-
-def _pair_report_from_env():
-    """AFR_PAIR_REPORT = "<k>", k >= 1: the per-pair error report with the k worst pairs; unset or empty -> None (off).  Anything else,
-    or the report without AFR_DEVICE_DATA (no atlas, no owners), is a ValueError."""
-    spec = os.environ.get("AFR_PAIR_REPORT", "").strip()
-    if not spec:
-        return None
-    try:
-        k = int(spec)
-    except ValueError:
-        k = 0
-    if k < 1:
-        raise ValueError(f"AFR_PAIR_REPORT must be an integer >= 1 (the number of worst pairs to list), got {spec!r}")
-    if not os.environ.get("AFR_DEVICE_DATA", "").strip():
-        raise ValueError("AFR_PAIR_REPORT needs AFR_DEVICE_DATA: the glyph atlas the sheets are composed from defines which character owns a pixel")
-    return k
-
-
-def _steer_pairs_from_env():
-    """AFR_STEER_PAIRS = "<share>", a float in [0, 1): how much of a fresh letter's weight follows the error of its pair with the letter
-    before it; unset, empty or 0 -> 0.0 (off).  Anything else, a share without AFR_FRESH_DATA (nothing is redrawn), or a share together
-    with a non-zero AFR_STEER (a text is drawn from one table) is a ValueError."""
-    spec = os.environ.get("AFR_STEER_PAIRS", "").strip()
-    if not spec:
-        return 0.0
-    try:
-        share = float(spec)
-    except ValueError:
-        share = -1.0
-    if not 0.0 <= share < 1.0:
-        raise ValueError(f"AFR_STEER_PAIRS must be a share in [0, 1), e.g. 0.5, got {spec!r}")
-    if os.environ.get("AFR_FRESH_DATA", "").strip() != "1":
-        raise ValueError("AFR_STEER_PAIRS needs AFR_FRESH_DATA=1: only texts that are redrawn every epoch can be steered")
-    if share and _steer_from_env():
-        raise ValueError("AFR_STEER_PAIRS and AFR_STEER together: the fresh texts are drawn from one table, by character or by pair")
-    return share
-
-
-ALPHABET, STEER = _alphabet_from_env(), _steer_from_env()     # likewise read at import
-PAIR_REPORT, STEER_PAIRS = _pair_report_from_env(), _steer_pairs_from_env()     # likewise
+# read at import, like the settings above: a bad value stops the run before it starts
+VAL_REPORT, TENSOR_REPORT = _val_report_from_env(), _tensor_report_from_env()
+DEVICE_DATA, FRESH_DATA = _device_data_from_env()
+CHAR_REPORT, READ_REPORT = _char_report_from_env(), _read_report_from_env()
+ALPHABET, STEER = _alphabet_from_env(), _steer_from_env()
+PAIR_REPORT, STEER_PAIRS = _pair_report_from_env(), _steer_pairs_from_env()
 PAIR_MIN_CHARS = 8                                            # a pair seen fewer times is not listed, and is steered as the average
 STEER_UNIT = 4096                                             # floor_w + gain of the steered letter table: the weight of an average character
 
@@ -326,7 +261,32 @@ def _tensor_report_lines(p, g, d):
     return lines
 
 
-class _TensorReport:
+class _Report:
+    """What _run_epoch asks of a report: hooks at the moments of an epoch, each a no-op unless a report overrides it."""
+    takes_batches = False     # add() is fed every validation batch's evaluation (one Engine.evaluate_last, shared by all that take it) ...
+    needs_u8 = False          # ... and reads its bitmaps, res.u8
+    reduced = ()              # the tensors end_validation sums over the ranks
+
+    def before_step(self, b, nb, rows, mean_elems):
+        """before training batch b of nb; rows: this rank's rows of it"""
+
+    def after_step(self, b, nb, rows, mean_elems):
+        """after that batch's optimizer step"""
+
+    def add(self, res, rows):
+        """one validation batch: its evaluation and this rank's rows"""
+
+    def end_validation(self, dist, rank, evaluate):
+        """after the last validation batch, under the weights it was run with.  dist: torch.distributed when there are ranks to reduce
+        over, else None -- every rank issues the same collectives; evaluate(rows) evaluates data-set rows once more, with bitmaps."""
+        for t in self.reduced if dist is not None else ():
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+
+    def end_epoch(self, inputs=None, targets=None):
+        """once the validation loss has been read; the dense tensors when the epoch runs on them and not by rows"""
+
+
+class _TensorReport(_Report):
     """What AFR_TENSOR_REPORT gathers during one epoch, on rank 0 alone and with no collective: the statistics of the last training
     step's weight difference (against a snapshot of the weights, allocated once per model) and those of the weights and of a probe's
     gradients.  Nothing here steps, advances a counter the run reads, or leaves a loss behind."""
@@ -336,17 +296,21 @@ class _TensorReport:
         self.first = None                         # (this rank's rows of the epoch's first training batch, its mean_elems)
         self.p = self.g = self.d = None
 
-    def before_last_step(self):
-        if getattr(self.model, "_tensor_snapshot", None) is None:
-            self.model._tensor_snapshot = torch.empty_like(self.eng.flat_params)
-        self.model._tensor_snapshot.copy_(self.eng.flat_params)
+    def before_step(self, b, nb, rows, mean_elems):
+        if b == 0:
+            self.first = (rows, mean_elems)
+        if b == nb - 1:                           # the snapshot the last step is measured against
+            if getattr(self.model, "_tensor_snapshot", None) is None:
+                self.model._tensor_snapshot = torch.empty_like(self.eng.flat_params)
+            self.model._tensor_snapshot.copy_(self.eng.flat_params)
 
-    def after_last_step(self):
-        self.d = self.eng.tensor_stats("params", minus=self.model._tensor_snapshot)
+    def after_step(self, b, nb, rows, mean_elems):
+        if b == nb - 1:
+            self.d = self.eng.tensor_stats("params", minus=self.model._tensor_snapshot)
 
-    def probe(self, inputs=None, targets=None):
-        """Forward + loss + backward of the first training batch's rows (by data-set rows, or dense when inputs are given); the dropout
-        step is the next one the model WOULD draw, passed explicitly: model._next_step() does not move."""
+    def end_epoch(self, inputs=None, targets=None):
+        """The probe: forward + loss + backward of the first training batch's rows (by data-set rows, or dense when inputs are given); the
+        dropout step is the next one the model WOULD draw, passed explicitly: model._next_step() does not move."""
         eng, (rows, me) = self.eng, self.first
         _batch_calls(eng, None, inputs, targets, rows).forward_loss(step=self.model._steps + 1, mean_elems=me)
         eng.backward()
@@ -359,9 +323,10 @@ class _TensorReport:
         return _tensor_report_lines(self.p, self.g, self.d)
 
 
-class _ValReport:
+class _ValReport(_Report):
     """What AFR_VAL_REPORT keeps on the device during one validation pass: the column sums of the evaluation kernel's counts, their
     maximum, and the k largest per-sample losses with their data-set indices (merged batch by batch with torch.topk)."""
+    takes_batches = True
 
     def __init__(self, k, dev, bitmaps=False):
         self.k, self.bitmaps = int(k), bool(bitmaps)
@@ -380,10 +345,13 @@ class _ValReport:
         top = torch.topk(loss, min(self.k, loss.numel()))
         self.loss, self.idx = top.values, ids[top.indices]
 
-    def all_reduce(self, dist):
+    def end_validation(self, dist, rank, evaluate):
         """Every rank issues both collectives (the setting is rank-invariant); the worst list stays this rank's."""
-        dist.all_reduce(self.sums, op=dist.ReduceOp.SUM)
-        dist.all_reduce(self.max, op=dist.ReduceOp.MAX)
+        if dist is not None:
+            dist.all_reduce(self.sums, op=dist.ReduceOp.SUM)
+            dist.all_reduce(self.max, op=dist.ReduceOp.MAX)
+        if self.bitmaps and rank == 0 and self.idx.numel():               # the worst sheets once more, for their bitmaps (no collective)
+            self.u8 = evaluate(self.idx).u8
 
     def line(self, pixels, world=1):
         s, n = self.sums.tolist(), max(1, int(self.sums[3]) * pixels)
@@ -392,21 +360,43 @@ class _ValReport:
                 f"max level diff {int(self.max)}, worst {len(self.idx)}{' of rank 0 shard' if world > 1 else ''}: {worst}")
 
 
-class _CharReport:
-    """What AFR_CHAR_REPORT keeps on the device during one validation pass: afr_op_sheet_char_errors' by-code table, which every
-    validation batch's launch adds to (the batch's rows of the bound codes, the evaluation's bitmaps)."""
+def _write_tsv(path, header, rows):
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        for row in (header, *rows):
+            f.write("\t".join(str(v) for v in row) + "\n")
 
-    def __init__(self, k, atlas, codes):
-        self.k, self.atlas, self.codes = int(k), atlas, codes
-        self.table = torch.zeros((atlas.n_codes + 1, 5), dtype=torch.int64, device=atlas.device)
+
+class _CharErrorPass(_Report):
+    """What the character-error pass of the validation batches leaves on the device: afr_op_sheet_char_errors' by-code table, which every
+    batch's launch adds to (the batch's rows of the bound codes, the evaluation's bitmaps), and -- with pairs -- afr_op_pair_errors' table
+    by (preceding character, character), scattered from the same launch's per-position records on the same rows.  AFR_CHAR_REPORT and
+    AFR_STEER read by_code, AFR_PAIR_REPORT and AFR_STEER_PAIRS by_pair; only a table somebody reads is summed over the ranks."""
+    takes_batches = needs_u8 = True
+
+    def __init__(self, atlas, codes, by_code=True, pairs=False):
+        from . import devdata
+        self.atlas, self.codes = atlas, codes
+        self.by_code = torch.zeros((atlas.n_codes + 1, 5), dtype=torch.int64, device=atlas.device)
+        self.by_pair = torch.zeros(devdata.PAIR_SHAPE + (4,), dtype=torch.int64, device=atlas.device) if pairs else None
+        self.reduced = ((self.by_code,) if by_code else ()) + ((self.by_pair,) if pairs else ())
 
     def add(self, res, rows):
         from . import devdata
         if rows.numel():
-            devdata.char_errors(self.atlas, self.codes, res.u8.contiguous(), res.u8.shape[1], res.u8.shape[2], rows=rows, by_code=self.table)
+            per_pos = devdata.char_errors(self.atlas, self.codes, res.u8.contiguous(), res.u8.shape[1], res.u8.shape[2], rows=rows,
+                                          by_code=self.by_code).per_pos
+            if self.by_pair is not None:
+                devdata.pair_errors(self.codes, per_pos, rows=rows, by_pair=self.by_pair)
 
-    def all_reduce(self, dist):
-        dist.all_reduce(self.table, op=dist.ReduceOp.SUM)
+
+class _CharReport:
+    """AFR_CHAR_REPORT's block and char_errors.tsv, from the by-code table of a _CharErrorPass."""
+
+    def __init__(self, k, errors):
+        self.k, self.errors = int(k), errors
+
+    table = property(lambda self: self.errors.by_code)
 
     @staticmethod
     def _rates(row):
@@ -426,35 +416,19 @@ class _CharReport:
 
     def write_tsv(self, path):
         t = self.table.tolist()
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        with open(path, "w") as f:
-            f.write("code\tchar\tchars\tpixels\tsumsq\toff2\twrong\n")
-            for c, row in enumerate(t):
-                if c == len(t) - 1:
-                    f.write("\t".join(["background", ""] + [str(v) for v in row]) + "\n")
-                elif row[1] > 0:
-                    f.write("\t".join([str(c), chr(c) if 32 < c < 127 else ""] + [str(v) for v in row]) + "\n")
+        _write_tsv(path, ["code", "char", "chars", "pixels", "sumsq", "off2", "wrong"],
+                   [[c, chr(c) if 32 < c < 127 else ""] + row for c, row in enumerate(t[:-1]) if row[1] > 0] + [["background", ""] + t[-1]])
 
 
 class _PairReport:
-    """What AFR_PAIR_REPORT and AFR_STEER_PAIRS keep on the device during one validation pass: afr_op_pair_errors' table by (preceding
-    character, character), which every validation batch adds to -- devdata.char_errors with its per-position records on the batch's
-    rows of the bound codes and the evaluation's bitmaps, then devdata.pair_errors on the same rows."""
+    """AFR_PAIR_REPORT's block and pair_errors.tsv, from the pair table of a _CharErrorPass."""
 
-    def __init__(self, k, atlas, codes, alphabet):
-        from . import devdata, synth
-        self.k, self.atlas, self.codes = int(k), atlas, codes
+    def __init__(self, k, errors, alphabet):
+        from . import synth
+        self.k, self.errors = int(k), errors
         self.members = synth.alphabet_members(alphabet or "upper")
-        self.table = torch.zeros(devdata.PAIR_SHAPE + (4,), dtype=torch.int64, device=atlas.device)
 
-    def add(self, res, rows):
-        from . import devdata
-        if rows.numel():
-            per_pos = devdata.char_errors(self.atlas, self.codes, res.u8.contiguous(), res.u8.shape[1], res.u8.shape[2], rows=rows).per_pos
-            devdata.pair_errors(self.codes, per_pos, rows=rows, by_pair=self.table)
-
-    def all_reduce(self, dist):
-        dist.all_reduce(self.table, op=dist.ReduceOp.SUM)
+    table = property(lambda self: self.errors.by_pair)
 
     @staticmethod
     def name(p, c):
@@ -471,33 +445,26 @@ class _PairReport:
         return out
 
     def write_tsv(self, path):
-        t = self.table.tolist()
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        with open(path, "w") as f:
-            f.write("prev\tprev_char\tcode\tchar\tchars\tpixels\tsumsq\twrong\n")
-            for p, row in enumerate(t):
-                for c, rec in enumerate(row):
-                    if any(rec):
-                        f.write("\t".join(["" if p == 0 else str(32 + p), "" if p == 0 else chr(32 + p), str(33 + c), chr(33 + c)]
-                                          + [str(v) for v in rec]) + "\n")
+        _write_tsv(path, ["prev", "prev_char", "code", "char", "chars", "pixels", "sumsq", "wrong"],
+                   [["" if p == 0 else 32 + p, "" if p == 0 else chr(32 + p), 33 + c, chr(33 + c)] + rec
+                    for p, row in enumerate(self.table.tolist()) for c, rec in enumerate(row) if any(rec)])
 
 
-class _ReadReport:
+class _ReadReport(_Report):
     """What AFR_READ_REPORT keeps on the device during one validation pass: afr_op_sheet_read_back's confusion table, which every
     validation batch's launch adds to (the batch's rows of the bound codes, the evaluation's bitmaps)."""
+    takes_batches = needs_u8 = True
 
     def __init__(self, k, atlas, codes, alphabet):
         self.k, self.atlas, self.codes, self.alphabet = int(k), atlas, codes, alphabet or "upper"
         self.table = torch.zeros((atlas.n_codes, atlas.n_codes), dtype=torch.int64, device=atlas.device)
+        self.reduced = (self.table,)
 
     def add(self, res, rows):
         from . import devdata
         if rows.numel():
             devdata.read_back(self.atlas, self.codes, res.u8.contiguous(), self.alphabet, res.u8.shape[1], res.u8.shape[2], rows=rows,
                               confusion=self.table)
-
-    def all_reduce(self, dist):
-        dist.all_reduce(self.table, op=dist.ReduceOp.SUM)
 
     @staticmethod
     def _name(c):
@@ -517,12 +484,9 @@ class _ReadReport:
         return f"Read report: {scored} characters, read right {right / n:.6f}, read blank {blank / n:.6f}, confusions: {worst}"
 
     def write_tsv(self, path):
-        pairs, t = self._confusions()
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        with open(path, "w") as f:
-            f.write("code\tchar\tread\tread_char\tcount\n")
-            for c, r in torch.nonzero(t).tolist():
-                f.write("\t".join([str(c), chr(c) if 32 < c < 127 else "", str(r), chr(r) if 32 < r < 127 else "", str(int(t[c, r]))]) + "\n")
+        t = self.table.cpu()
+        _write_tsv(path, ["code", "char", "read", "read_char", "count"],
+                   [[c, chr(c) if 32 < c < 127 else "", r, chr(r) if 32 < r < 127 else "", int(t[c, r])] for c, r in torch.nonzero(t).tolist()])
 
     def write_strings(self, model, strings, path):
         """path: every test string, rendered by the model as render_strings renders it, beside what is read from the bitmap"""
@@ -850,19 +814,14 @@ def _batch_calls(eng, stepper, inputs, targets, rows):
                            evaluate=partial(eng.evaluate, x), forward_loss=partial(eng.forward_loss, x, t))
 
 
-def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True, report=None, treport=None, creport=None,
-               rreport=None, preport=None):
+def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True, reports=()):
     """One epoch of the reference loop (model.py:288-333): the training pass over order.train_epoch(), then the validation
     pass; returns the two means of per-batch mean losses.  An engine that keeps a weight EMA validates from it.  by_rows: the engine has the data set bound (Engine.bind_dataset)
     and every step is driven by this rank's slice of the epoch's index vector -- the kernels read the rows where they lie.
     by_rows=False gathers each batch with index_select and hands the step dense tensors (the form tools/epoch_bench.py
-    measures the other against).  report: a _ValReport (AFR_VAL_REPORT) that every validation batch is evaluated into between its
-    forward and its loss; None: the pass as it always was.  treport: a _TensorReport (AFR_TENSOR_REPORT, rank 0 only): the weights are
-    snapshotted before the last training batch and compared after it, and once the validation loss has been read the first training
-    batch is run once more as a probe for its gradients.  creport: a _CharReport (AFR_CHAR_REPORT, AFR_STEER): every validation batch's bitmaps --
-    of the one evaluation it shares with report -- are measured against the sheets the atlas composes for the batch's rows.  rreport: a
-    _ReadReport (AFR_READ_REPORT): the same bitmaps are read back against the atlas's glyphs.  preport: a _PairReport (AFR_PAIR_REPORT,
-    AFR_STEER_PAIRS): the same bitmaps once more, charged by (preceding character, character)."""
+    measures the other against).  reports: _Report objects, whose hooks are called in list order at their moments of the epoch; every
+    rank passes the same list but for reports that issue no collective.  Those that take batches share one evaluation per validation
+    batch, between its forward and its loss, with bitmaps if one of them reads bitmaps.  Without reports: the pass as it always was."""
     from .parallel import shard_rows
     eng = model.engine
     pixels = targets[0].numel()
@@ -875,50 +834,35 @@ def _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, wor
         mine = rows[shard_rows(rows.numel(), rank, world)]
         step_lr, step_wd = _step_hyper(eng, lr)
         hyper = dict(step=model._next_step(), lr=step_lr, betas=ADAM_BETAS, weight_decay=step_wd)
-        if treport is not None:
-            if b == 0:
-                treport.first = (mine, rows.numel() * pixels)
-            if b == nb - 1:
-                treport.before_last_step()
+        for r in reports:
+            r.before_step(b, nb, mine, rows.numel() * pixels)
         _batch_calls(eng, stepper, *dense, mine).step(rows.numel() * pixels, **hyper)
-        if treport is not None and b == nb - 1:
-            treport.after_last_step()
+        for r in reports:
+            r.after_step(b, nb, mine, rows.numel() * pixels)
     avg_train_loss = stepper.global_loss() / nb                 # mean of per-batch means (model.py:311,333)
 
     model.eval()
     vidx = order.val_epoch().to(inputs.device)
     nvb = _num_batches(order.val_size, batch_size)
+    takers = [r for r in reports if r.takes_batches]
+    want_u8 = any(r.needs_u8 for r in takers)
     with _eval_weights(eng):
         for b in range(nvb):
             rows = vidx[b * batch_size:(b + 1) * batch_size]
             mine = rows[shard_rows(rows.numel(), rank, world)]
             calls = _batch_calls(eng, None, *dense, mine)
             calls.forward(training=False, want_output=False)
-            if report is not None or creport is not None or rreport is not None or preport is not None:
-                res = calls.evaluate_last(want_u8=creport is not None or rreport is not None or preport is not None)
-                if report is not None:
-                    report.add(res, mine)
-                if creport is not None:
-                    creport.add(res, mine)
-                if rreport is not None:
-                    rreport.add(res, mine)
-                if preport is not None:
-                    preport.add(res, mine)
+            if takers:
+                res = calls.evaluate_last(want_u8=want_u8)
+                for r in takers:
+                    r.add(res, mine)
             calls.loss_grad(mean_elems=rows.numel() * pixels)
-        if creport is not None and world > 1:
-            creport.all_reduce(_dist()[0])
-        if rreport is not None and world > 1:
-            rreport.all_reduce(_dist()[0])
-        if preport is not None and world > 1:
-            preport.all_reduce(_dist()[0])
-        if report is not None:
-            if world > 1:
-                report.all_reduce(_dist()[0])
-            if report.bitmaps and rank == 0 and report.idx.numel():      # the worst sheets once more, for their bitmaps (no collective)
-                report.u8 = _batch_calls(eng, None, dense[0], None, report.idx).evaluate(want_u8=True).u8
+        for r in reports:
+            r.end_validation(_dist()[0] if world > 1 else None, rank,
+                             lambda rows: _batch_calls(eng, None, dense[0], None, rows).evaluate(want_u8=True))
     avg_val_loss = stepper.global_loss() / max(nvb, 1)
-    if treport is not None:
-        treport.probe(*dense)
+    for r in reports:
+        r.end_epoch(*dense)
     return avg_train_loss, avg_val_loss
 
 
@@ -966,6 +910,80 @@ def _steer_pairs_line(share, w2, k=5):
     return f"Steer pairs: share {share:g}, heaviest {len(top)} pairs " + ", ".join(f"{_PairReport.name(p, c)} x{w2[p][c] / STEER_UNIT:.2f}" for p, c in top)
 
 
+def _optional_config_lines(eng, fresh):
+    """The lines of config.txt that only a run with a non-default setting has, in their fixed order, from one table of (key, value or
+    None, format): a default run's artefacts stay as they were.  The switches are read as they stand when this runs."""
+    ema = eng.ema_decay is not None
+    table = (("loss", eng.loss if eng.loss != "mse" else None, ""), ("optimizer", eng.optimizer if eng.optimizer != "adamw" else None, ""),
+             ("max_grad_norm", eng.max_grad_norm or None, "g"), ("ema_decay", eng.ema_decay, "g"), ("ema_every", eng.ema_every if ema else None, ""),
+             ("val_report", VAL_REPORT or None, ""), ("tensor_report", 1 if TENSOR_REPORT else None, ""), ("device_data", DEVICE_DATA or None, ""),
+             ("fresh_data", 1 if fresh else None, ""), ("char_report", CHAR_REPORT or None, ""), ("alphabet", ALPHABET or None, ""),
+             ("steer", STEER or None, "g"), ("read_report", READ_REPORT or None, ""), ("pair_report", PAIR_REPORT or None, ""),
+             ("steer_pairs", STEER_PAIRS or None, "g"))
+    return [f"{key} = {value:{fmt}}" for key, value, fmt in table if value is not None]
+
+
+def _check_switches(atlas, refresh):
+    """What the reports and the steering need of a training run, from one table of (switch, what is missing, message); the first that is
+    on without it is a ValueError.  The switches are read as they stand when this runs."""
+    no_atlas, no_rewrite = atlas is None, atlas is None or refresh is None
+    for on, missing, message in (
+            (CHAR_REPORT, no_atlas, "the character report needs the glyph atlas the data set was composed from (AFR_DEVICE_DATA)"),
+            (READ_REPORT, no_atlas, "the read-back report needs the glyph atlas the data set was composed from (AFR_DEVICE_DATA)"),
+            (STEER, no_rewrite, "steering needs the glyph atlas and the fresh-data rewrite (AFR_DEVICE_DATA, AFR_FRESH_DATA)"),
+            (PAIR_REPORT, no_atlas, "the pair report needs the glyph atlas the data set was composed from (AFR_DEVICE_DATA)"),
+            (STEER_PAIRS, no_rewrite, "pair steering needs the glyph atlas and the fresh-data rewrite (AFR_DEVICE_DATA, AFR_FRESH_DATA)"),
+            (STEER_PAIRS, bool(STEER), "AFR_STEER_PAIRS and AFR_STEER together: the fresh texts are drawn from one table")):
+        if on and missing:
+            raise ValueError(message)
+
+
+def _epoch_reports(model, atlas, inputs, targets, refresh, strings, epoch, rank, world):
+    """The reports of one epoch, from the switches as they stand when this runs -> (reports, blocks, errors): the list _run_epoch drives;
+    what rank 0 prints after a status line, in its fixed order, as pairs (lines() -> the lines to print, artefacts(folder) -> the files
+    of the epoch's output folder, or None); and the _CharErrorPass among the reports (or None), whose tables the steering of the next
+    epoch reads.  The reports that only print are built on the epochs that print a status line; the validation report and the tables of
+    the steering are kept every epoch."""
+    status, eng = epoch % 5 == 0, model.engine
+    reports, blocks = [], []
+    if VAL_REPORT:
+        val = _ValReport(VAL_REPORT, device, bitmaps=status)
+        reports.append(val)
+
+        def worst_bitmaps(out):
+            for j in range(0 if val.u8 is None else val.u8.shape[0]):
+                helpers.u8_array_to_image(val.u8[j].cpu().numpy(), f"{out}/val_worst_{j}.bmp")
+        blocks.append((lambda: [val.line(targets[0].numel(), world)], worst_bitmaps))
+    if TENSOR_REPORT and rank == 0 and status:
+        reports.append(_TensorReport(model))
+        blocks.append((reports[-1].lines, None))
+    char_lines, pair_lines = bool(CHAR_REPORT) and status, bool(PAIR_REPORT) and status
+    errors = None
+    if char_lines or STEER or pair_lines or STEER_PAIRS:
+        errors = _CharErrorPass(atlas, inputs, by_code=char_lines or bool(STEER), pairs=pair_lines or bool(STEER_PAIRS))
+        reports.append(errors)
+    if char_lines:
+        chars = _CharReport(CHAR_REPORT, errors)
+        blocks.append((chars.lines, lambda out: chars.write_tsv(f"{out}/char_errors.tsv")))
+    if STEER:
+        blocks.append((lambda: [_steer_line(STEER, refresh.w)] if refresh.w is not None else [], None))
+    if pair_lines:
+        pairs = _PairReport(PAIR_REPORT, errors, ALPHABET)
+        blocks.append((pairs.lines, lambda out: pairs.write_tsv(f"{out}/pair_errors.tsv")))
+    if STEER_PAIRS:
+        blocks.append((lambda: [_steer_pairs_line(STEER_PAIRS, refresh.w2)] if refresh.w2 is not None else [], None))
+    if READ_REPORT and status:
+        read = _ReadReport(READ_REPORT, atlas, inputs, ALPHABET)
+        reports.append(read)
+
+        def read_files(out):
+            read.write_tsv(f"{out}/confusion.tsv")
+            with _eval_weights(eng):
+                read.write_strings(model, strings, f"{out}/read_back.txt")
+        blocks.append((lambda: [read.line()], read_files))
+    return reports, blocks, errors
+
+
 def train_attention_model(model, dataset, batch_size, refresh=None, atlas=None):
     """Reference model.py:209-384: config.txt, 80/20 split, AdamW + ReduceLROnPlateau + early stopping, progress
     prints and test-string dumps every 5 epochs, training_results.txt.  Returns the model.  refresh (AFR_FRESH_DATA, _fresh_rows): called
@@ -985,46 +1003,8 @@ def train_attention_model(model, dataset, batch_size, refresh=None, atlas=None):
                          ("max_chars_per_sheet", MAX_CHARS_PER_SHEET), ("num_samples", NUM_SAMPLES), ("data_size", len(dataset)),
                          ("random_seed", SEED), ("sheet_height", SHEET_HEIGHT), ("sheet_width", SHEET_WIDTH)):
                 f.write(f"{k} = {v}\n")
-            if eng.loss != "mse":               # only a non-default loss is recorded: a default run's artefacts stay as they were
-                f.write(f"loss = {eng.loss}\n")
-            if eng.optimizer != "adamw":        # likewise
-                f.write(f"optimizer = {eng.optimizer}\n")
-            if eng.max_grad_norm:               # likewise only when set
-                f.write(f"max_grad_norm = {eng.max_grad_norm:g}\n")
-            if eng.ema_decay is not None:       # likewise
-                f.write(f"ema_decay = {eng.ema_decay:g}\nema_every = {eng.ema_every}\n")
-            if VAL_REPORT:                      # likewise
-                f.write(f"val_report = {VAL_REPORT}\n")
-            if TENSOR_REPORT:                   # likewise
-                f.write("tensor_report = 1\n")
-            if DEVICE_DATA:                     # likewise
-                f.write(f"device_data = {DEVICE_DATA}\n")
-            if refresh is not None:             # likewise
-                f.write("fresh_data = 1\n")
-            if CHAR_REPORT:                     # likewise
-                f.write(f"char_report = {CHAR_REPORT}\n")
-            if ALPHABET:                        # likewise
-                f.write(f"alphabet = {ALPHABET}\n")
-            if STEER:                           # likewise
-                f.write(f"steer = {STEER:g}\n")
-            if READ_REPORT:                     # likewise
-                f.write(f"read_report = {READ_REPORT}\n")
-            if PAIR_REPORT:                     # likewise
-                f.write(f"pair_report = {PAIR_REPORT}\n")
-            if STEER_PAIRS:                     # likewise
-                f.write(f"steer_pairs = {STEER_PAIRS:g}\n")
-    if CHAR_REPORT and atlas is None:
-        raise ValueError("the character report needs the glyph atlas the data set was composed from (AFR_DEVICE_DATA)")
-    if READ_REPORT and atlas is None:
-        raise ValueError("the read-back report needs the glyph atlas the data set was composed from (AFR_DEVICE_DATA)")
-    if STEER and (atlas is None or refresh is None):
-        raise ValueError("steering needs the glyph atlas and the fresh-data rewrite (AFR_DEVICE_DATA, AFR_FRESH_DATA)")
-    if PAIR_REPORT and atlas is None:
-        raise ValueError("the pair report needs the glyph atlas the data set was composed from (AFR_DEVICE_DATA)")
-    if STEER_PAIRS and (atlas is None or refresh is None):
-        raise ValueError("pair steering needs the glyph atlas and the fresh-data rewrite (AFR_DEVICE_DATA, AFR_FRESH_DATA)")
-    if STEER_PAIRS and STEER:
-        raise ValueError("AFR_STEER_PAIRS and AFR_STEER together: the fresh texts are drawn from one table")
+            f.write("".join(line + "\n" for line in _optional_config_lines(eng, refresh is not None)))
+    _check_switches(atlas, refresh)
     strings = test_strings + _extra_test_strings(ALPHABET)
     pair_table = None                           # AFR_STEER_PAIRS: the pair table the last validation pass left on the device
     steer_table = None                          # AFR_STEER: the by-code table the last validation pass left on the device
@@ -1056,23 +1036,15 @@ def train_attention_model(model, dataset, batch_size, refresh=None, atlas=None):
     epoch = -1
     for epoch in range(NUM_EPOCHS):
         lr = lr_holder.param_groups[0]["lr"]
-        report = _ValReport(VAL_REPORT, device, bitmaps=epoch % 5 == 0) if VAL_REPORT else None
-        treport = _TensorReport(model) if TENSOR_REPORT and rank == 0 and epoch % 5 == 0 else None
-        char_lines = bool(CHAR_REPORT) and epoch % 5 == 0
-        creport = _CharReport(CHAR_REPORT or 1, atlas, inputs) if char_lines or STEER else None      # steering keeps the table every epoch
-        rreport = _ReadReport(READ_REPORT, atlas, inputs, ALPHABET) if READ_REPORT and epoch % 5 == 0 else None
-        pair_lines = bool(PAIR_REPORT) and epoch % 5 == 0
-        preport = _PairReport(PAIR_REPORT or 1, atlas, inputs, ALPHABET) if pair_lines or STEER_PAIRS else None      # likewise
+        reports, blocks, errors = _epoch_reports(model, atlas, inputs, targets, refresh, strings, epoch, rank, world)
         if refresh is not None and epoch >= 1:
-            refresh(epoch, order.train_idx, inputs, targets, **(dict(by_code=steer_table) if STEER else {}),
-                    **(dict(by_pair=pair_table) if STEER_PAIRS else {}))
-        avg_train_loss, avg_val_loss = _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True, report=report,
-                                                  treport=treport, creport=creport, rreport=rreport, **(dict(preport=preport) if preport else {}))
+            refresh(epoch, order.train_idx, inputs, targets, by_code=steer_table, by_pair=pair_table)
+        avg_train_loss, avg_val_loss = _run_epoch(model, stepper, order, inputs, targets, batch_size, lr, rank, world, by_rows=True, reports=reports)
 
         if STEER:
-            steer_table = creport.table
+            steer_table = errors.by_code
         if STEER_PAIRS:
-            pair_table = preport.table
+            pair_table = errors.by_pair
         scheduler.step(avg_val_loss)
         is_best = avg_val_loss < best_val_loss
         if is_best:
@@ -1091,27 +1063,12 @@ def train_attention_model(model, dataset, batch_size, refresh=None, atlas=None):
                 if is_best:
                     status += " (New Best)"
                 print(status)
-                if report is not None:
-                    print(report.line(targets[0].numel(), world))
-                    for j in range(0 if report.u8 is None else report.u8.shape[0]):
-                        helpers.u8_array_to_image(report.u8[j].cpu().numpy(), f"{OUTPUT_DIR}/epoch_{epoch}/val_worst_{j}.bmp")
-                if treport is not None:
-                    print("\n".join(treport.lines()))
-                if char_lines:
-                    print("\n".join(creport.lines()))
-                    creport.write_tsv(f"{OUTPUT_DIR}/epoch_{epoch}/char_errors.tsv")
-                if STEER and refresh.w is not None:
-                    print(_steer_line(STEER, refresh.w))
-                if pair_lines:
-                    print("\n".join(preport.lines()))
-                    preport.write_tsv(f"{OUTPUT_DIR}/epoch_{epoch}/pair_errors.tsv")
-                if STEER_PAIRS and refresh.w2 is not None:
-                    print(_steer_pairs_line(STEER_PAIRS, refresh.w2))
-                if rreport is not None:
-                    print(rreport.line())
-                    rreport.write_tsv(f"{OUTPUT_DIR}/epoch_{epoch}/confusion.tsv")
-                    with _eval_weights(eng):
-                        rreport.write_strings(model, strings, f"{OUTPUT_DIR}/epoch_{epoch}/read_back.txt")
+                for lines, artefacts in blocks:
+                    text = lines()
+                    if text:
+                        print("\n".join(text))
+                    if artefacts is not None:
+                        artefacts(f"{OUTPUT_DIR}/epoch_{epoch}")
                 with _eval_weights(eng):
                     render_strings(model, strings, output_dir=f"{OUTPUT_DIR}/epoch_{epoch}", sheet_height=SHEET_HEIGHT,
                                    sheet_width=SHEET_WIDTH, device=device)
@@ -1151,7 +1108,7 @@ def train_string_renderer():
         print(f"Composing {NUM_SAMPLES} samples on {device} from a glyph atlas of {DEVICE_DATA}...")
         dataset = devdata.reference_dataset(NUM_SAMPLES, atlas, DATA_FIRST_SEED, MAX_CHARS_PER_SHEET, SHEET_HEIGHT, SHEET_WIDTH, alphabet=ALPHABET)
         if FRESH_DATA:
-            refresh = _fresh_rows(atlas, NUM_SAMPLES, ALPHABET, STEER, *((STEER_PAIRS,) if STEER_PAIRS else ()))
+            refresh = _fresh_rows(atlas, NUM_SAMPLES, ALPHABET, STEER, STEER_PAIRS)
     else:
         dataset = load_string_dataset(data_dir="train_input", num_samples=NUM_SAMPLES, sheet_height=SHEET_HEIGHT,
                                       sheet_width=SHEET_WIDTH)

@@ -55,25 +55,35 @@ def hash_u8(tensor_id, shape, seed=SEED):
 
 
 # ---------------------------------------------------------------- text (generate_font.ts:164-199)
-def lcg_text(seed, min_length=10, max_length=100):
-    state = int(seed)
+def _lcg_walk(seed, min_length, max_length, letter):
+    """The walk the three text sources share (and csrc/dataset.hip's text_walk restates): the LCG state from the seed, the length, then
+    words of 1..10 letters with a space between them until the length is used up.  draw(k) is (state * k) >> 32 after one LCG update --
+    int(rnd() * k) of generate_font.ts, exact in integers; letter(draw, prev) -> the code of a word's next letter, prev the code before
+    it in the word (None at its start)."""
+    state = int(seed) % 4294967296
 
-    def rnd():
+    def draw(k):
         nonlocal state
         state = (state * 1664525 + 1013904223) % 4294967296
-        return state / 4294967296
+        return (state * k) >> 32
 
-    length = int(rnd() * (max_length - min_length + 1)) + min_length
+    remaining = draw(max_length - min_length + 1) + min_length
     out = []
-    remaining = length
     while remaining > 0:
-        wl = min(int(rnd() * 10) + 1, remaining)
-        out.append("".join(chr(65 + int(rnd() * 26)) for _ in range(wl)))
+        wl = min(draw(10) + 1, remaining)
+        prev = None
+        for _ in range(wl):
+            prev = letter(draw, prev)
+            out.append(chr(prev))
         remaining -= wl
         if remaining > 0:
             out.append(" ")
             remaining -= 1
     return "".join(out)
+
+
+def lcg_text(seed, min_length=10, max_length=100):
+    return _lcg_walk(seed, min_length, max_length, lambda draw, prev: 65 + draw(26))
 
 
 # ---------------------------------------------------------------- weighted text (afr_op_dataset_text_w, afr_op_text_weights)
@@ -151,24 +161,7 @@ def lcg_text_weighted(seed, cum, min_length=10, max_length=100):
     total = cum[-1]
     if len(cum) != TEXT_CODES or total == 0:
         raise ValueError("cum: 94 inclusive cumulative weights with a positive total")
-    state = int(seed) % 4294967296
-
-    def draw(k):
-        nonlocal state
-        state = (state * 1664525 + 1013904223) % 4294967296
-        return (state * k) >> 32
-
-    length = draw(max_length - min_length + 1) + min_length
-    out = []
-    remaining = length
-    while remaining > 0:
-        wl = min(draw(10) + 1, remaining)
-        out.append("".join(chr(TEXT_FIRST + bisect.bisect_right(cum, draw(total))) for _ in range(wl)))
-        remaining -= wl
-        if remaining > 0:
-            out.append(" ")
-            remaining -= 1
-    return "".join(out)
+    return _lcg_walk(seed, min_length, max_length, lambda draw, prev: TEXT_FIRST + bisect.bisect_right(cum, draw(total)))
 
 
 # ---------------------------------------------------------------- Markov text (afr_op_dataset_text_m, afr_op_pair_weights)
@@ -230,31 +223,15 @@ def lcg_text_markov(seed, cum2, min_length=10, max_length=100):
     cum2 = [[int(c) for c in row] for row in cum2]
     if len(cum2) != TEXT_CONTEXTS or any(len(row) != TEXT_CODES for row in cum2):
         raise ValueError(f"cum2: {TEXT_CONTEXTS} rows of {TEXT_CODES} inclusive cumulative weights")
-    state = int(seed) % 4294967296
 
-    def draw(k):
-        nonlocal state
-        state = (state * 1664525 + 1013904223) % 4294967296
-        return (state * k) >> 32
+    def letter(draw, prev):
+        ctx = 0 if prev is None else 1 + prev - TEXT_FIRST
+        row = cum2[ctx]
+        if row[-1] == 0:
+            raise ValueError(f"cum2: the text of seed {seed} reaches context {ctx}, whose total weight is 0")
+        return TEXT_FIRST + bisect.bisect_right(row, draw(row[-1]))
 
-    length = draw(max_length - min_length + 1) + min_length
-    out = []
-    remaining = length
-    while remaining > 0:
-        wl = min(draw(10) + 1, remaining)
-        ctx = 0
-        for _ in range(wl):
-            row = cum2[ctx]
-            if row[-1] == 0:
-                raise ValueError(f"cum2: the text of seed {seed} reaches context {ctx}, whose total weight is 0")
-            i = bisect.bisect_right(row, draw(row[-1]))
-            out.append(chr(TEXT_FIRST + i))
-            ctx = 1 + i
-        remaining -= wl
-        if remaining > 0:
-            out.append(" ")
-            remaining -= 1
-    return "".join(out)
+    return _lcg_walk(seed, min_length, max_length, letter)
 
 
 def dataset_strings(n, first_seed=42):

@@ -122,15 +122,18 @@ def test_val_report_setting_is_parsed_strictly(monkeypatch):
 
 
 class _Recorder:
-    """Stands in for the model, its engine and the stepper: every method call is recorded by name."""
+    """Stands in for the model, its engine and the stepper: every method call is recorded by name, evaluate_last's keyword arguments
+    are kept in eval_kwargs."""
 
     def __init__(self, calls, **attrs):
         self.__dict__.update(attrs)
-        self._calls = calls
+        self._calls, self.eval_kwargs = calls, []
 
     def __getattr__(self, name):
         def call(*a, **k):
             self._calls.append(name)
+            if name == "evaluate_last":
+                self.eval_kwargs.append(k)
             return _EVAL if name == "evaluate_last" else 0.0
         return call
 
@@ -160,7 +163,7 @@ def test_run_epoch_makes_no_new_call_when_the_report_is_off():
     assert off == ["step_rows"] * 2 + ["global_loss"] + ["forward_rows", "loss_grad_rows"] + ["global_loss"]
     assert run(by_rows=False) == ["step"] * 2 + ["global_loss"] + ["forward", "loss_grad"] + ["global_loss"]
     rep = M._ValReport(2, "cpu")
-    on = run(report=rep)
+    on = run(reports=[rep])
     assert on == ["step_rows"] * 2 + ["global_loss"] + ["forward_rows", "evaluate_last", "loss_grad_rows"] + ["global_loss"]
     # the accumulator: column sums, maximum, the two largest losses with the data-set indices of the validation rows
     assert rep.sums.tolist() == [8, 1, 1, 2] and int(rep.max) == 2
@@ -170,3 +173,23 @@ def test_run_epoch_makes_no_new_call_when_the_report_is_off():
     line = rep.line(8)
     assert line.startswith("Val report: off by >= 1 level 0.500000, off by >= 2 levels 0.062500, wrong ink 0.062500, max level diff 2, worst 2: ")
     assert line.endswith(f"{int(vidx[1])}(0.500000), {int(vidx[0])}(0.250000)")
+    # two reports that take batches still share one evaluation per batch, with bitmaps exactly when one of them reads bitmaps
+    fed = []
+
+    class Taker(M._Report):
+        takes_batches = True
+
+        def __init__(self, needs_u8):
+            self.needs_u8 = needs_u8
+
+        def add(self, res, rows):
+            fed.append((self, res, rows.tolist()))
+
+    for flags in ((False, False), (False, True), (True, False), (True, True)):
+        takers = [Taker(f) for f in flags]
+        del eng.eval_kwargs[:], fed[:]
+        assert run(reports=[M._Report()] + takers) == on
+        assert [k["want_u8"] for k in eng.eval_kwargs] == [any(flags)]
+        assert [(t, r) for t, r, _ in fed] == [(takers[0], _EVAL), (takers[1], _EVAL)] and fed[0][2] == fed[1][2] == vidx.tolist()
+    del eng.eval_kwargs[:]
+    assert run(reports=[M._Report()]) == off and eng.eval_kwargs == []      # a report that takes no batches asks for no evaluation

@@ -91,13 +91,13 @@ def validation_part(atlas, n_val, reps):
 
     def val_pass(with_report):
         def run():
-            creport = M._CharReport(10, atlas, x) if with_report else None
+            errors = M._CharErrorPass(atlas, x) if with_report else None
             for b in range((n_val + bs - 1) // bs):
                 rows = rows_all[b * bs:(b + 1) * bs]
                 calls = M._batch_calls(eng, None, None, None, rows)
                 calls.forward(training=False, want_output=False)
-                if creport is not None:
-                    creport.add(calls.evaluate_last(want_u8=True), rows)
+                if errors is not None:
+                    errors.add(calls.evaluate_last(want_u8=True), rows)
                 calls.loss_grad(mean_elems=rows.numel() * pixels)
             eng.read_loss()
         return run

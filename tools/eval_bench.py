@@ -149,7 +149,7 @@ def loop_part(name, reps, val_batches, loss="mse", k=8):
         rep = M._ValReport(k, eng.device) if on else None
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        _, val = M._run_epoch(model, stepper, order, x, t8, B, M.LEARNING_RATE, 0, 1, by_rows=True, report=rep)
+        _, val = M._run_epoch(model, stepper, order, x, t8, B, M.LEARNING_RATE, 0, 1, by_rows=True, reports=[rep] if on else ())
         if rep is not None:
             rep.line(pix)                                   # the report's own device-to-host reads belong to its cost
         torch.cuda.synchronize()

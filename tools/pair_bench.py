@@ -122,14 +122,14 @@ def epoch_part(atlas, n, reps):
     def epoch(steered):
         def run():
             state["epoch"] += 1
-            preport = M._PairReport(1, atlas, x, None) if steered else None
+            errors = M._CharErrorPass(atlas, x, by_code=False, pairs=True) if steered else None
             if steered:
                 pairs(state["epoch"], order.train_idx, x, t, by_pair=state["table"])
             else:
                 plain(state["epoch"], order.train_idx, x, t)
-            M._run_epoch(m, stepper, order, x, t, 1024, M.LEARNING_RATE, 0, 1, by_rows=True, preport=preport)
+            M._run_epoch(m, stepper, order, x, t, 1024, M.LEARNING_RATE, 0, 1, by_rows=True, reports=[errors] if steered else ())
             if steered:
-                state["table"] = preport.table
+                state["table"] = errors.by_pair
         return run
 
     def wall_ms(fn):

@@ -115,14 +115,14 @@ def epoch_part(atlas, n, reps):
     def epoch(steered):
         def run():
             state["epoch"] += 1
-            creport = M._CharReport(1, atlas, x) if steered else None
+            errors = M._CharErrorPass(atlas, x) if steered else None
             if steered:
                 steer(state["epoch"], order.train_idx, x, t, by_code=state["table"])
             else:
                 plain(state["epoch"], order.train_idx, x, t)
-            M._run_epoch(m, stepper, order, x, t, 1024, M.LEARNING_RATE, 0, 1, by_rows=True, creport=creport)
+            M._run_epoch(m, stepper, order, x, t, 1024, M.LEARNING_RATE, 0, 1, by_rows=True, reports=[errors] if steered else ())
             if steered:
-                state["table"] = creport.table
+                state["table"] = errors.by_code
         return run
 
     def wall_ms(fn):

@@ -126,7 +126,7 @@ def loop_leg(name, reps, train_batches, val_batches):
         tr = M._TensorReport(model) if on else None
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        M._run_epoch(model, stepper, order, x, t8, B, M.LEARNING_RATE, 0, 1, by_rows=True, treport=tr)
+        M._run_epoch(model, stepper, order, x, t8, B, M.LEARNING_RATE, 0, 1, by_rows=True, reports=[tr] if on else ())
         if tr is not None:
             tr.lines()                                          # (its device-to-host reads happened in the probe)
         torch.cuda.synchronize()
